@@ -2,7 +2,7 @@
 """Headline benchmark: SpMM effective GFLOP/s (+ algorithmic HBM GB/s) at
 M=N=K=4096, fp32, on MI355X -- BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path (the C-ABI entry sputnik_hip_spmm_batched:
@@ -26,6 +26,10 @@ value = 2*nnz*N*replicas_total / time  (effective GFLOP/s of the whole job).
 Rank 0 prints ONE JSON line.  Extra keys: `roofline` (HBM roof, algorithmic
 bytes / dominant kernel time), `roofline_valu` (the roof that actually binds
 fp32 SpMM at this size), `cpu_baseline`, `sweep`, `other_ops`.
+
+--dump-outputs DIR writes what the last timed step computed (C, see dump_outputs)
+as .npy files, so that two builds can be compared output for output: the inputs
+are seeded, identical from run to run for the same arguments.
 """
 import argparse
 import json
@@ -770,6 +774,31 @@ def other_ops(dev):
     return res
 
 
+DUMP_SAMPLE = 1 << 21       # elements of C written by --dump-outputs (8 MB of float32)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out, directory):
+    """What a caller of the timed path receives: C ([M, N], or [R, M, N] with R
+    replicas).  The whole of C is 64 MiB per replica, so two files stand for it:
+      spmm_out_sample.npy    float32 [DUMP_SAMPLE]: C at a fixed, seeded set of flat
+                             positions (ascending; the same positions in every run)
+      spmm_out_row_sums.npy  float64 [R*M]: every row of C summed in float64, so
+                             that no element goes unchecked
+    Called on the output of the last timed step, before anything else writes it."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    flat = out.reshape(-1)
+    n = min(DUMP_SAMPLE, flat.numel())
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), size=n, replace=False))
+    sample = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+    row_sums = out.reshape(-1, out.shape[-1]).double().sum(dim=1).cpu().numpy()
+    files = {"spmm_out_sample": sample, "spmm_out_row_sums": row_sums}
+    for name, arr in files.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
+    return sorted(files)
+
+
 def load_pmc_traffic(build_id, kernel):
     """HBM bytes per launch of the dominant kernel from the committed rocprofv3
     PMC passes (profiles/spmm_c2_d010_traffic.json, collected as
@@ -806,7 +835,12 @@ def main():
     ap.add_argument("--schedule-timeout-s", type=float, default=240.0,
                     help="N>1: a schedule that has not finished after this long ends the run; "
                          "rank 0 prints the line with the schedules measured so far")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/*.npy "
+                         "(rank 0's C: a seeded sample and its row sums, see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     # Contract: stdout carries ONE JSON line.  Libraries print there too (RCCL's
     # version banner at communicator creation, for one), so stdout is pointed at
     # stderr for the whole run and the result goes to the saved descriptor.
@@ -949,6 +983,8 @@ def main():
     if not distributed:
         ms_per_step = run_timed(problem.step)
         headline = "compute (one GPU: nothing to exchange)"
+        if args.dump_outputs:
+            dumped = dump_outputs(problem.out, args.dump_outputs)
     else:
         # North star / SURVEY.md 8e: the replica-sharded product WITH the all-gather of
         # C over RCCL.  Every schedule is timed the same way (W + K steps each):
@@ -1012,10 +1048,15 @@ def main():
         headline = pick_headline(timings)
         ms_per_step = timings[headline]
         multi = ex.report(timings, n_gpus)
+        if args.dump_outputs and rank == 0:
+            # every schedule that computes rewrites the rank's whole block of C each step
+            dumped = dump_outputs(problem.out, args.dump_outputs)
 
     result = None
     if rank == 0:
         result = core_result(headline, ms_per_step, multi)
+        if args.dump_outputs:
+            result["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         if not args.no_extras and n_gpus == 1:
             sweep = []
             for d in DENSITIES:

@@ -2,6 +2,7 @@
 """Generates tests/golden/*.npz -- run HERE (the reference is not on the GPU box).
 
     python oracle/make_golden.py            # needs /root/reference
+    python oracle/make_golden.py reference_layer   # only reference_layer_*.npz
 
 What comes from the reference itself (imported, never copied):
   * the input distribution: tests/connectors.py ``Uniform`` and
@@ -385,8 +386,99 @@ def many_mask_cases():
           attention=dense_rep.numpy())
 
 
+def reference_layer_cases():
+    """What the reference's own Python layer returns -- forward values and the
+    gradients autograd leaves on its inputs -- for the inputs of
+    tests/test_reference_dropin.py, run on CPU against this package's
+    ``torch_sputnik``.  Inputs and results only (float32, as the layer returned
+    them), so that the test needs nothing outside the repository."""
+    import importlib
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from helpers import make_csr
+    torch_cpu_backend.install()
+    from modules.spmm import Spmm  # reference: modules/spmm.py
+    from modules.sddmm import Sddmm  # reference: modules/sddmm.py
+    from modules.sparse_linear import SparseLinear  # reference: modules/sparse_linear.py
+
+    def T(x):
+        return torch.from_numpy(np.ascontiguousarray(x))
+
+    def np32(t):
+        return t.detach().numpy().astype(np.float32)
+
+    # Spmm.apply, loss sum(out^2): test_reference_spmm_function ("spmm") and
+    # test_own_functions_agree_with_reference_functions ("spmm_agree")
+    for name, (m, k, n, sparsity, seed, order) in {
+            "spmm": (18, 14, 9, 0.6, 1, "ascending"),
+            "spmm_agree": (20, 12, 5, 0.5, 5, "descending")}.items():
+        dense_a, vals, ri, ro, ci = make_csr(m, k, sparsity, seed=seed, order=order)
+        b = np.random.default_rng(seed + 1).uniform(-1, 1, (k, n)).astype(np.float32)
+        v, d = T(vals).requires_grad_(True), T(b).requires_grad_(True)
+        out = Spmm.apply(m, k, v, T(ri), T(ro), T(ci), d)
+        out.square().sum().backward()
+        _close32(out.detach().numpy(), dense_a.astype(np.float64) @ b, f"reference Spmm ({name}) fwd")
+        _save("reference_layer_" + name, m=m, k=k, values=vals, row_indices=ri, row_offsets=ro,
+              column_indices=ci, dense=b, out=np32(out), grad_values=np32(v.grad),
+              grad_dense=np32(d.grad))
+
+    # Sddmm.apply, loss sum(out^2): test_reference_sddmm_function
+    mask, _, ri, ro, ci = make_csr(16, 20, 0.7, seed=3, round_to=1)
+    rng = np.random.default_rng(4)
+    lhs = rng.uniform(-1, 1, (16, 6)).astype(np.float32)
+    rhs = rng.uniform(-1, 1, (20, 6)).astype(np.float32)
+    l, r = T(lhs).requires_grad_(True), T(rhs).requires_grad_(True)
+    out = Sddmm.apply(16, 20, T(ri), T(ro), T(ci), l, r)
+    out.square().sum().backward()
+    _close32(out.detach().numpy(), (lhs.astype(np.float64) @ rhs.T.astype(np.float64))[mask != 0],
+             "reference Sddmm fwd")
+    _save("reference_layer_sddmm", m=16, n=20, row_indices=ri, row_offsets=ro, column_indices=ci,
+          lhs=lhs, rhs=rhs, out=np32(out), grad_lhs=np32(l.grad), grad_rhs=np32(r.grad))
+
+    # SparseLinear, loss sum(y^2): test_reference_sparse_linear_module
+    torch.manual_seed(0)
+    out_f, in_f, seq, batch = 24, 16, 7, 3
+    w = (torch.randn(out_f, in_f) * (torch.rand(out_f, in_f) > 0.7)).float()
+    layer = SparseLinear(in_f, out_f)
+    with torch.no_grad():
+        layer.weight.copy_(w)
+    layer.setup_sparse_tensors()
+    x = torch.randn(batch, seq, in_f, requires_grad=True)
+    y = layer(x)
+    y.square().sum().backward()
+    _close32(y.detach().numpy(), (x.detach().double() @ w.double().t()).transpose(1, 2).numpy(),
+             "reference SparseLinear fwd")
+    _save("reference_layer_sparse_linear", weight=w.numpy(), x=np32(x), y=np32(y),
+          grad_x=np32(x.grad), grad_values=np32(layer.values.grad))
+
+    # the many-mask sketches (tests/transformer/functions.py) on the inputs of
+    # many_mask_b3_h2_s24.npz, with the topology tests/transformer/utils.py builds
+    # from its masks (stacked [b, s+1] offsets); the incoming gradients are the stored ones
+    path = os.path.join(REFERENCE, "tests", "transformer")
+    sys.path.insert(0, path)
+    functions = importlib.import_module("functions")
+    utils = importlib.import_module("utils")
+    sys.path.remove(path)
+    g = dict(np.load(os.path.join(GOLDEN, "many_mask_b3_h2_s24.npz")))
+    b, s = int(g["b"]), int(g["s"])
+    _, ri, ro, ci, nnzs = utils.dense_to_sparse_3d(T(g["masks"]))
+    q, k = T(g["q"]).requires_grad_(True), T(g["k"]).requires_grad_(True)
+    scores = functions.Sddmm.apply(b, s, s, nnzs, ri, ro, ci, q, k)
+    scores.backward(T(g["grad_scores"]))
+    wt, v = T(g["weights"]).requires_grad_(True), T(g["v"]).requires_grad_(True)
+    ctx = functions.Spmm.apply(b, s, s, nnzs, wt, ri, ro, ci, v)
+    ctx.backward(T(g["grad_context"]))
+    _close32(scores.detach().numpy(), g["scores"], "reference many-mask Sddmm fwd")
+    _close32(ctx.detach().numpy(), g["context"], "reference many-mask Spmm fwd")
+    _save("reference_layer_many_mask", row_indices=ri.numpy(), row_offsets=ro.numpy(),
+          column_indices=ci.numpy(), nnzs=nnzs.numpy(), scores=np32(scores), grad_q=np32(q.grad),
+          grad_k=np32(k.grad), context=np32(ctx), grad_weights=np32(wt.grad), grad_v=np32(v.grad))
+
+
 def main():
     os.makedirs(GOLDEN, exist_ok=True)
+    if sys.argv[1:] == ["reference_layer"]:   # only these files (they read many_mask_b3_h2_s24)
+        reference_layer_cases()
+        return
     # BASELINE.json config 1: 64^3, density 0.5
     spmm_case("spmm_c1_64_d050", 1101, 64, 64, 64, 0.5)
     spmm_case("spmm_2d_72x64x72", 1102, 72, 64, 72, 0.9)
@@ -400,6 +492,7 @@ def main():
     spmm_bias_cases()
     softmax_backward_case()
     many_mask_cases()
+    reference_layer_cases()
 
 
 if __name__ == "__main__":

@@ -4,8 +4,9 @@
 The product registers HIP kernels only (csrc/torch_binding.cpp) and raises on
 CPU tensors.  Tests of the *host logic* (autograd wrappers, modules, replica
 sharding, the reference's own modules imported against this package) need the
-ops to run without a GPU; they call ``install()`` from tests/conftest.py, which
-adds the oracle under the CPU dispatch key for the life of the test process.
+ops to run without a GPU; tests/conftest.py's ``cpu_ops`` fixture calls
+``install()``, which adds the oracle under the CPU dispatch key, and
+``uninstall()`` when the test module is done.
 Nothing outside tests/ and oracle/make_golden.py imports this module.
 """
 import numpy as np
@@ -292,3 +293,12 @@ def install():
     _lib.impl("permute_last", _permute_last, "CPU")
     _lib.impl("transpose_last2", _transpose_last2, "CPU")
     _lib.impl("transpose_last2_as", _transpose_last2_as, "CPU")
+
+
+def uninstall():
+    """Removes the CPU kernels again, so that tests later in the same process
+    see the product as it is: no CPU path."""
+    global _lib
+    if _lib is not None:
+        _lib._destroy()
+        _lib = None

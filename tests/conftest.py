@@ -52,11 +52,14 @@ def golden():
 @pytest.fixture(scope="module")
 def cpu_ops():
     """torch.ops.torch_sputnik.* answered on CPU by the oracle -- for tests of
-    the host logic only (see oracle/torch_cpu_backend.py)."""
+    the host logic only (see oracle/torch_cpu_backend.py).  Removed again after
+    the module: in a whole-suite run on the GPU box the tests that check that the
+    product has no CPU path come later in the same process."""
     from oracle import torch_cpu_backend
     torch_cpu_backend.install()
     import torch_sputnik_amd
-    return torch_sputnik_amd
+    yield torch_sputnik_amd
+    torch_cpu_backend.uninstall()
 
 
 def _reload_library_options():
