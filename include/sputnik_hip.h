@@ -222,10 +222,16 @@ SPUTNIK_HIP_API int sputnik_hip_spmm_typed(int m, int k, int n, int nonzeros, in
  * bias / ReLU epilogue of sputnik_hip_spmm_bias_batched.  At layer densities every tile of
  * the weight is occupied, and the tiles cost 1 / density times the sparse flops on a unit
  * sixteen times faster than the vector pipe.  An operand given as float32 (values_type /
- * dense_type = SPUTNIK_HIP_F32; the other, if half, has type tile_type) is NOT rounded to the
- * tile type: it enters as half planes whose sum is the value (float16: 22 bits, bfloat16:
- * 24), at one more tile product per plane pair.  sputnik_hip_spmm_typed takes this route by
- * itself for a half dense operand; this entry adds the float32 dense operand (the incoming
+ * dense_type = SPUTNIK_HIP_F32; the other, if half, has type tile_type) is not rounded to the
+ * tile type: it enters as half planes whose sum is the value, at one more tile product per
+ * plane pair
+ * (float16: two planes of the operand times a power of two taken on the device from its
+ * largest finite magnitude and undone exactly in the epilogue -- at least 22 bits of every
+ * value down to 2^-28 of that magnitude, an absolute error below 2^-50 of it beneath, over
+ * float32's whole range; an inf / NaN element stays non-finite (inf may come out as NaN)
+ * and leaves the others' range alone.  bfloat16: three planes, 24 bits.)  The workspace
+ * holds the planes and, for float16, their range.  sputnik_hip_spmm_typed takes this route
+ * by itself for a half dense operand; this entry adds the float32 dense operand (the incoming
  * gradient of modules/sparse_linear.py:60-65 in a half-storage layer).
  * Returns SPUTNIK_HIP_UNSUPPORTED where the route does not serve the call (k not a
  * multiple of 64, n not of 8, a grid under 192 tiles, density under 0.06 per tile
@@ -257,9 +263,15 @@ SPUTNIK_HIP_API int sputnik_hip_left_spmm_half_tiles(int m, int k, int n, int no
  * tile type -- sputnik_hip_sparse_linear_half_image, one launch per step, shared
  * by the forward pass and the input gradient.  dy [batch, out, seq] is given either in the
  * tile type (grad_type = tile_type) or as the PLANES of the float32 tensor
- * (sputnik_hip_half_planes, grad_type = SPUTNIK_HIP_F32): float32 operands are never rounded
- * to the storage type -- they enter as half planes whose sum is the value (float16: two
- * planes, 22 bits; bfloat16: three, 24 bits).  The weight gradient takes a plan
+ * (sputnik_hip_half_planes, grad_type = SPUTNIK_HIP_F32): float32 operands are not rounded
+ * to the storage type -- they enter as half planes whose sum is the value
+ * (float16: two planes of the operand times a power of two taken on the device from its
+ * largest finite magnitude and undone exactly in the epilogue -- at least 22 bits of every
+ * value down to 2^-28 of that magnitude, an absolute error below 2^-50 of it beneath, over
+ * float32's whole range; an inf / NaN element stays non-finite (inf may come out as NaN)
+ * and leaves the others' range alone.  bfloat16: three planes, 24 bits.)
+ * The image and the planes (sputnik_hip_sparse_linear_half_image_bytes,
+ * sputnik_hip_half_planes_bytes) carry that power of two behind the planes.  The weight gradient takes a plan
  * (sputnik_hip_sparse_linear_half_plan, topology only, may be NULL) and scratch for the
  * partial vectors of the workgroups that share a tile.
  * sputnik_hip_sparse_linear_half_supported: 1 where the three products take this route
@@ -319,8 +331,13 @@ SPUTNIK_HIP_API int sputnik_hip_sddmm_sum_typed(int m, int k, int n, int nonzero
  * (modules/sparse_linear.py:44-49 with the extension's storage types).  Where the
  * matrix-core route serves the shape (long reduction, mask density from 0.05: the dense
  * 128 x 128 tiles on v_mfma_f32_32x32x16_{f16,bf16}, sampled at the mask) the float32
- * operand is NOT rounded to the storage type: one pass splits it into two half planes,
- * v = hi + lo, and the tiles accumulate hi * x + lo * x (exact products, float32 sums).
+ * operand is not rounded to the storage type: one pass splits it into half planes,
+ * v = hi + lo, and the tiles accumulate hi * x + lo * x (exact products, float32 sums)
+ * (float16: two planes of the operand times a power of two taken on the device from its
+ * largest finite magnitude and undone exactly in the epilogue -- at least 22 bits of every
+ * value down to 2^-28 of that magnitude, an absolute error below 2^-50 of it beneath, over
+ * float32's whole range; an inf / NaN element stays non-finite (inf may come out as NaN)
+ * and leaves the others' range alone.  bfloat16: three planes, 24 bits).
  * `scratch` holds sputnik_hip_sddmm_sum_mixed_scratch_bytes(...) bytes (the planes, then the
  * partial vectors); workspace / planned as sputnik_hip_sddmm_sum_typed.  Returns
  * SPUTNIK_HIP_UNSUPPORTED for every other shape and for a float32 operand whose replicas do

@@ -982,3 +982,365 @@ def test_softmax_function_half_autograd(tsa, dev, dtype):
     want_dx = O.sparse_softmax_backward(y.detach().float().cpu().numpy(),
                                         go.float().cpu().numpy(), ro, 0.5)
     assert half_err(x.grad.float().cpu().numpy(), want_dx, dtype, ro) < TOL
+
+
+# ----------------------------------------------------------------------------
+# float32 operands on half tiles over float32's range: a float32 operand enters the
+# matrix-core products as half planes; on float16 tiles they are planes of the operand
+# times a power of two taken from its largest finite magnitude (csrc/mfma_tiles.h), so
+# that the split keeps 22 bits at any magnitude, and inf / NaN stay non-finite
+# ----------------------------------------------------------------------------
+FP16_MAGNITUDES = [1e-12, 1e-9, 1e-7, 1e-5, 1e3, 7e4, 1e6]
+RANGE_CASES = ([(torch.float16, g) for g in FP16_MAGNITUDES] +
+               [(torch.bfloat16, g) for g in FP16_MAGNITUDES + [1e-30, 1e30]])
+RANGE_IDS = [f"{str(t).split('.')[-1]}-{g:g}" for t, g in RANGE_CASES]
+
+
+def _spread(rng, shape, magnitude):
+    """float32 values with full mantissas at a global magnitude, spread over 2.5 decades."""
+    return (rng.uniform(-1, 1, size=shape) * magnitude *
+            10.0 ** rng.uniform(-2.5, 0, size=shape)).astype(np.float32)
+
+
+def _fp16_rounded(want):
+    """float64 -> float16 as the storage rounds it (inf beyond 65520)."""
+    with np.errstate(over="ignore"):
+        return np.asarray(want, np.float64).astype(np.float16)
+
+
+def _check_half_output(got, want, dtype):
+    """A result stored in `dtype`: +-inf exactly where the float64 value rounds past the
+    storage's range (both signs; a margin of 1e-4 around the edge either way), half_err
+    everywhere else."""
+    got = np.asarray(got, np.float64).copy()
+    want = np.asarray(want, np.float64).copy()
+    assert not np.isnan(got).any()
+    if dtype == torch.float16:
+        edge = 65520.0
+        over = np.abs(want) > edge * (1 + 1e-4)
+        near = np.abs(np.abs(want) - edge) <= edge * 1e-4
+        assert np.array_equal(got[over], np.sign(want[over]) * np.inf)
+        assert np.isfinite(got[~over & ~near]).all()
+        got[over | near] = 0.0
+        want[over | near] = 0.0
+    assert np.isfinite(got).all()
+    assert half_err(got, want, dtype) < TOL
+
+
+@pytest.mark.parametrize("tile,magnitude", RANGE_CASES, ids=RANGE_IDS)
+@pytest.mark.parametrize("values_kind,dense_kind", [("float", "half"), ("half", "float"), ("float", "float")])
+@pytest.mark.parametrize("m,k,n,sparsity,replicas", [(128, 64, 128, 0.5, 1), (200, 192, 136, 0.8, 3)])
+def test_left_spmm_half_tiles_float32_range(capi, dev, spmm_mfma, tile, magnitude, values_kind, dense_kind,
+                                            m, k, n, sparsity, replicas):
+    """left_spmm on the tiles with float32 values and / or a float32 dense operand at
+    magnitudes from 1e-12 to 1e6 (bfloat16: 1e-30 .. 1e30): the float32 bound against
+    float64 on the operands as stored, no NaN, no flush to zero."""
+    _, vals, ri, ro, ci = make_csr(m, k, sparsity, seed=m + k + 11, round_to=1, empty_rows=(m // 3,))
+    rng = np.random.default_rng(int(m + k + n))
+    if values_kind == "float":
+        v32 = _spread(rng, len(vals), magnitude)
+        v = T(v32, dev)
+    else:
+        v, v32 = rounded(rng.uniform(-1, 1, size=len(vals)), tile, dev)
+    if dense_kind == "float":
+        b32 = _spread(rng, (replicas, k, n), magnitude)
+        b = T(b32, dev)
+    else:
+        b, b32 = rounded(rng.uniform(-1, 1, size=(replicas, k, n)), tile, dev)
+    ws_bytes = capi.left_spmm_half_tiles_workspace_bytes(m, k, n, len(ci), replicas, v, b, tile)
+    if tile == torch.bfloat16 and values_kind == dense_kind == "float":
+        assert ws_bytes == 0
+        return
+    want = O.left_spmm(m, k, v32.astype(np.float64), ri, ro, ci, b32.astype(np.float64))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.full((replicas, m, n), float("nan"), device=dev)
+    capi.left_spmm_half_tiles(m, k, n, replicas, T(ro, dev), T(ci, dev), v, b, tile, out, ws)
+    got = out.cpu().numpy()
+    assert np.isfinite(got).all()
+    assert rel_err(got, want) < TOL
+
+
+@pytest.mark.parametrize("tile,magnitude", RANGE_CASES, ids=RANGE_IDS)
+@pytest.mark.parametrize("values_kind,grad_kind", [("float", "half"), ("half", "float"), ("float", "float")])
+@pytest.mark.parametrize("out_f,in_f,seq,batch,sparsity", [(128, 64, 64, 1, 0.5), (192, 320, 192, 3, 0.8)])
+def test_half_linear_float32_range(spmm_mfma, dev, tile, magnitude, values_kind, grad_kind, out_f, in_f, seq,
+                                   batch, sparsity):
+    """The three products of the sparse layer on half activations with float32 weights
+    (the image) and / or a float32 dy (half_planes) at magnitudes from 1e-12 to 1e6
+    (bfloat16: 1e-30 .. 1e30): forward and weight gradient (unplanned and planned) to the
+    float32 bound, dx in x's type to one unit in its last place (+-inf where the float64
+    value rounds past float16's range).  With both operands float32, dy is taken at
+    1 / magnitude, so that dx lies inside float16's range and the two operands' scales
+    have to cancel."""
+    from torch_sputnik_amd import ops
+    _, vals, ri, ro, ci = make_csr(out_f, in_f, sparsity, seed=out_f + in_f + seq + 5, round_to=1,
+                                   empty_rows=(out_f // 3,))
+    rng = np.random.default_rng(out_f + seq)
+    if values_kind == "float":
+        v32 = _spread(rng, len(vals), magnitude)
+        v = T(v32, dev)
+    else:
+        v, v32 = rounded(rng.uniform(-1, 1, size=len(vals)), tile, dev)
+    x, x32 = rounded(rng.uniform(-1, 1, size=(batch, seq, in_f)), tile, dev)
+    g_magnitude = 1.0 / magnitude if values_kind == "float" else magnitude
+    if grad_kind == "float":
+        g32 = _spread(rng, (batch, out_f, seq), g_magnitude)
+        g = T(g32, dev)
+    else:
+        g, g32 = rounded(rng.uniform(-1, 1, size=(batch, out_f, seq)), tile, dev)
+    w = np.zeros((out_f, in_f), np.float64)
+    rows = np.repeat(np.arange(out_f), np.diff(ro))
+    w[rows, ci] = v32
+    x64, g64 = x32.astype(np.float64), g32.astype(np.float64)
+    rod, cid = T(ro, dev), T(ci, dev)
+    image = ops.half_linear_image(out_f, in_f, v, rod, cid, tile)
+    if values_kind == "float":
+        y = ops.half_linear_forward(out_f, image, v.dtype, x)
+        assert rel_err(y.cpu().numpy(), np.einsum("oi,bsi->bos", w, x64)) < TOL
+    planes = grad_kind == "float"
+    grad = ops.half_planes(g, tile) if planes else g
+    if planes:
+        want_dw = np.einsum("bos,bsi->oi", g64, x64)[rows, ci]
+        for plan in (None, ops.half_linear_plan(out_f, in_f, rod, cid)):
+            dw = ops.half_linear_weight_gradient(out_f, rod, cid, grad, planes, x, plan).cpu().numpy()
+            assert np.isfinite(dw).all()
+            assert rel_err(dw[None, :], want_dw[None, :], ro) < TOL
+    dx = ops.half_linear_input_gradient(out_f, in_f, grad, planes, image, v.dtype, x, batch, seq)
+    if tile == torch.bfloat16 and values_kind == grad_kind == "float":
+        assert dx is None
+        return
+    _check_half_output(dx.float().cpu().numpy(), np.einsum("bos,oi->bsi", g64, w), tile)
+
+
+@pytest.mark.parametrize("tile,magnitude", RANGE_CASES, ids=RANGE_IDS)
+@pytest.mark.parametrize("wide", ["lhs", "rhs"])
+@pytest.mark.parametrize("m,k,n,sparsity,replicas", [(128, 64, 384, 0.5, 1), (200, 192, 130, 0.8, 3)])
+def test_sddmm_sum_mixed_float32_range(capi, dev, sddmm_mfma, tile, magnitude, wide, m, k, n, sparsity,
+                                       replicas):
+    """The summed SDDMM of a (float32, half) pair with the float32 operand at magnitudes
+    from 1e-12 to 1e6 (bfloat16: 1e-30 .. 1e30): the float32 bound, unplanned and planned."""
+    _, _, ri, ro, ci = make_csr(m, n, sparsity, seed=m + k + n + 2, empty_rows=(3,), round_to=1)
+    rng = np.random.default_rng(k + 29)
+    wide32 = _spread(rng, (replicas, m if wide == "lhs" else n, k), magnitude)
+    half_t, half32 = rounded(rng.uniform(-1, 1, size=(replicas, n if wide == "lhs" else m, k)), tile, dev)
+    lhs32, rhs32 = (wide32, half32) if wide == "lhs" else (half32, wide32)
+    lhs, rhs = (T(wide32, dev), half_t) if wide == "lhs" else (half_t, T(wide32, dev))
+    want = O.sddmm(m, n, ri, ro, ci, lhs32, rhs32).sum(axis=0)     # (float64)
+    topo = (T(ri, dev), T(ro, dev), T(ci, dev))
+    for planned in (False, True):
+        got = _sddmm_sum_mixed(capi, dev, m, k, n, replicas, topo, lhs, rhs, planned=planned).cpu().numpy()
+        assert np.isfinite(got).all()
+        assert rel_err(got[None, :], want[None, :], ro) < TOL
+
+
+@pytest.mark.parametrize("values_kind", ["float", "half"])
+def test_left_spmm_half_tiles_float32_exact_integers(capi, dev, spmm_mfma, mfma_tile, values_kind):
+    """float32 operands of small integers times powers of two far from 1 (2^-30, 2^20):
+    every product and sum is exact, so the planes' scale must be a power of two that the
+    epilogue undoes exactly -- the result is the exact matrix, and nothing outside
+    [R, m, n] is written."""
+    m, k, n, replicas = 328, 128, 136, 2
+    _, _, ri, ro, ci = make_csr(m, k, 0.6, seed=19, round_to=1)
+    rng = np.random.default_rng(21)
+    v32 = (rng.integers(-4, 5, size=len(ci)) * 2.0 ** -30).astype(np.float32)
+    b32 = (rng.integers(-4, 5, size=(replicas, k, n)) * 2.0 ** 20).astype(np.float32)
+    want = O.left_spmm(m, k, v32, ri, ro, ci, b32).astype(np.float32)
+    v = T(v32, dev) if values_kind == "float" else T(v32 * 2.0 ** 30, dev).half()
+    if values_kind == "half":
+        want = want * np.float32(2.0 ** 30)
+    b = T(b32, dev)
+    ws = torch.empty(capi.left_spmm_half_tiles_workspace_bytes(m, k, n, len(ci), replicas, v, b, torch.float16),
+                     dtype=torch.uint8, device=dev)
+    guard = torch.full((replicas * m * n + 4096,), 777.0, device=dev)
+    out = guard[:replicas * m * n].view(replicas, m, n)
+    capi.left_spmm_half_tiles(m, k, n, replicas, T(ro, dev), T(ci, dev), v, b, torch.float16, out, ws)
+    assert np.array_equal(out.cpu().numpy(), want)
+    assert bool((guard[replicas * m * n:] == 777.0).all())
+
+
+def test_half_linear_float32_exact_integers(spmm_mfma, mfma_tile, dev):
+    """The three products with float32 weights (integers times 2^-30) and a float32 dy
+    (integers times 2^20) on float16 tiles: exact matrices, bit for bit."""
+    from torch_sputnik_amd import ops
+    out_f, in_f, seq, batch = 320, 128, 384, 2
+    _, _, ri, ro, ci = make_csr(out_f, in_f, 0.6, seed=23, round_to=1)
+    rng = np.random.default_rng(25)
+    v32 = (rng.integers(-4, 5, size=len(ci)) * 2.0 ** -30).astype(np.float32)
+    x32 = rng.integers(-4, 5, size=(batch, seq, in_f)).astype(np.float32)
+    g32 = (rng.integers(-4, 5, size=(batch, out_f, seq)) * 2.0 ** 20).astype(np.float32)
+    rows = np.repeat(np.arange(out_f), np.diff(ro))
+    w = np.zeros((out_f, in_f), np.float64)
+    w[rows, ci] = v32
+    v, x, g = T(v32, dev), T(x32, dev).half(), T(g32, dev)
+    rod, cid = T(ro, dev), T(ci, dev)
+    image = ops.half_linear_image(out_f, in_f, v, rod, cid, torch.float16)
+    assert np.array_equal(ops.half_linear_forward(out_f, image, v.dtype, x).cpu().numpy(),
+                          np.einsum("oi,bsi->bos", w, x32).astype(np.float32))
+    planes = ops.half_planes(g, torch.float16)
+    want_dw = np.einsum("bos,bsi->oi", g32.astype(np.float64), x32)[rows, ci].astype(np.float32)
+    for plan in (None, ops.half_linear_plan(out_f, in_f, rod, cid)):
+        assert np.array_equal(ops.half_linear_weight_gradient(out_f, rod, cid, planes, True, x, plan).cpu().numpy(),
+                              want_dw)
+    want_dx = np.einsum("bos,oi->bsi", g32.astype(np.float64), w)
+    assert np.array_equal(want_dx.astype(np.float16).astype(np.float64), want_dx)   # (exact in float16)
+    dx = ops.half_linear_input_gradient(out_f, in_f, planes, True, image, v.dtype, x, batch, seq)
+    assert np.array_equal(dx.float().cpu().numpy(), want_dx.astype(np.float32))
+
+
+@pytest.mark.parametrize("bad", ["inf", "nan"])
+def test_half_linear_non_finite_dy_propagates(spmm_mfma, dev, bad):
+    """One inf / NaN in a float32 dy[b, o, s] among values near 1e-7 (what GradScaler
+    relies on): every weight-gradient entry of row o whose x column is nonzero comes out
+    non-finite, the entries of row o whose x column is all zeros are what the float32
+    vector path gives, and every other row keeps the float32 bound -- the non-finite
+    element does not take the others' range with it.  dx: the rows (b', s') != (b, s)
+    keep one unit in the last place."""
+    import torch_sputnik_amd as tsa
+    from torch_sputnik_amd import ops
+    out_f, in_f, seq, batch = 256, 192, 128, 2
+    _, vals, ri, ro, ci = make_csr(out_f, in_f, 0.7, seed=31, round_to=1)
+    rng = np.random.default_rng(32)
+    x32 = rng.uniform(-1, 1, size=(batch, seq, in_f))
+    zero_cols = np.array([0, 5, 77, 150])
+    x32[:, :, zero_cols] = 0.0
+    x, x32 = rounded(x32, torch.float16, dev)
+    g32 = _spread(rng, (batch, out_f, seq), 1e-7)
+    b0, o0, s0 = 1, int(np.argmax(np.diff(ro))), 37
+    g32[b0, o0, s0] = np.inf if bad == "inf" else np.nan
+    v32 = _spread(rng, len(vals), 1e4)      # (dx near 1e-2: float16 normals)
+    rows = np.repeat(np.arange(out_f), np.diff(ro))
+    rod, cid, g = T(ro, dev), T(ci, dev), T(g32, dev)
+    dw = ops.half_linear_weight_gradient(out_f, rod, cid, ops.half_planes(g, torch.float16), True, x).cpu().numpy()
+    # the float32 vector path: the summed SDDMM of float32 operands
+    vec = tsa.ops.sddmm_sum(out_f, in_f, T(ri, dev), rod, cid, g,
+                            x.float().transpose(1, 2).contiguous()).cpu().numpy()
+    in_row = rows == o0
+    zero_col = np.isin(ci, zero_cols)
+    assert (~np.isfinite(dw[in_row & ~zero_col])).all()
+    assert np.array_equal(dw[in_row & zero_col], vec[in_row & zero_col], equal_nan=True)
+    g64 = g32.astype(np.float64).copy()
+    g64[b0, o0, s0] = 0.0
+    want_dw = np.einsum("bos,bsi->oi", g64, x32.astype(np.float64))[rows, ci]
+    assert np.isfinite(dw[~in_row]).all()
+    kept_ro = np.concatenate([[0], np.cumsum(np.diff(ro)[np.arange(out_f) != o0])])
+    assert rel_err(dw[~in_row][None, :], want_dw[~in_row][None, :], kept_ro) < TOL
+    # dx: only the row (b0, s0) may see the non-finite element
+    image = ops.half_linear_image(out_f, in_f, T(v32, dev), rod, cid, torch.float16)
+    dx = ops.half_linear_input_gradient(out_f, in_f, ops.half_planes(g, torch.float16), True, image,
+                                        torch.float32, x, batch, seq).float().cpu().numpy()
+    w = np.zeros((out_f, in_f), np.float64)
+    w[rows, ci] = v32
+    assert (~np.isfinite(dx[b0, s0][w[o0] != 0])).all()
+    want_dx = np.einsum("bos,oi->bsi", g64, w)
+    keep = np.ones((batch, seq), bool)
+    keep[b0, s0] = False
+    assert half_err(dx[keep], want_dx[keep], torch.float16) < TOL
+
+
+def _c5_layer(dev, seq):
+    """config 5's layer (2048 x 2048 at density 0.2, batch 8) with float32 weights and
+    float16 activations, and the float64 dense weight it holds."""
+    import torch_sputnik_amd as tsa
+    from torch_sputnik_amd.synthetic import random_csr, uniform
+    features, batch = 2048, 8
+    ri, ro, ci, nnz = random_csr(features, features, 0.2, dev, seed=505)
+    rows = torch.repeat_interleave(torch.arange(features, device=dev), (ro[1:] - ro[:-1]).long())
+    w = torch.zeros(features, features, device=dev)
+    w[rows, ci.long()] = (uniform((nnz,), dev, 1) - 0.5) * 0.1 + 0.001
+    layer = tsa.SparseLinear(features, features).to(dev)
+    with torch.no_grad():
+        layer.weight.copy_(w)
+    layer.setup_sparse_tensors()
+    x = (uniform((batch, seq, features), dev, 2) - 0.5).to(torch.float16)
+    return layer, x, rows, ro, ci
+
+
+@pytest.mark.parametrize("loss", ["mean_over_3", "sum_times_2^16"])
+def test_c5_sparse_linear_float32_weights_loss_scales(dev, loss):
+    """config 5's layer, default dispatch (no knob), float16 activations and float32
+    weights, under the two losses that put dy far from 1: a mean-reduced loss over
+    [8, 2048, 512] divided by 3 (dy ~ 4e-8) and a sum-reduced loss times GradScaler's first
+    scale 2^16 (dy = 65536).  The float32 weight gradient keeps the float32 bound against
+    float64 autograd; x.grad (float16) keeps one unit in the last place, +-inf exactly where
+    the float64 value rounds past float16's range; nothing is NaN."""
+    from tests.helpers import rel_err_torch
+    layer, x0, rows, ro, ci = _c5_layer(dev, 512)
+    assert layer.values.dtype == torch.float32
+    x = x0.clone().requires_grad_(True)
+    y = layer(x)
+
+    def reduce(t):
+        return t.mean() / 3 if loss == "mean_over_3" else t.sum() * 65536
+
+    reduce(y).backward()
+    wd = torch.zeros(2048, 2048, dtype=torch.float64, device=dev)
+    wd[rows, ci.long()] = layer.values.detach().double()
+    wd.requires_grad_(True)
+    xd = x0.double().requires_grad_(True)
+    yd = torch.matmul(xd, wd.t()).transpose(1, 2)
+    reduce(yd).backward()
+    assert rel_err_torch(y.detach(), yd.detach()) < TOL
+    gv = layer.values.grad
+    assert gv.dtype == torch.float32 and bool(torch.isfinite(gv).all())
+    assert rel_err(gv.cpu().numpy(), wd.grad[rows, ci.long()].cpu().numpy(), ro.cpu().numpy()) < TOL
+    assert x.grad.dtype == torch.float16
+    _check_half_output(x.grad.float().cpu().numpy(), xd.grad.cpu().numpy(), torch.float16)
+
+
+@pytest.mark.parametrize("magnitude", [4e-8, 65536.0 * 3])
+def test_left_spmm_float32_values_op_route_range(ts, capi, dev, magnitude):
+    """The op level (torch_sputnik.left_spmm, no knob) at a layer's density and size, which
+    takes the float16 tiles by itself: float32 values at dy-like magnitudes (a mean loss
+    over config 5 divided by 3, GradScaler's 2^16) against float64."""
+    m, k, n, r = 1024, 1024, 512, 8
+    _, vals, ri, ro, ci = make_csr(m, k, 0.8, seed=93)
+    topo = (T(ri, dev), T(ro, dev), T(ci, dev))
+    rng = np.random.default_rng(94)
+    v32 = _spread(rng, len(vals), magnitude)
+    b, b32 = rounded(rng.uniform(-1, 1, size=(r, k, n)), torch.float16, dev)
+    assert capi.left_spmm_half_tiles_workspace_bytes(m, k, n, len(ci), r, T(v32, dev), b, torch.float16) > 0
+    out = ts.left_spmm(m, k, T(v32, dev), *topo, b)
+    got = out.cpu().numpy()
+    assert np.isfinite(got).all()
+    assert rel_err(got, O.left_spmm(m, k, v32, ri, ro, ci, b32)) < TOL
+
+
+def test_hip_graph_replay_rederives_the_range(spmm_mfma, dev):
+    """A float16-activation SparseLinear with float32 weights on the tiles, captured as one
+    training step, replayed with incoming gradients of magnitude 1, 1e-8 and 7e4: every
+    replay bit-identical to the eager step on the same inputs -- the planes' range is
+    found on the device at every replay, not fixed at capture."""
+    import torch_sputnik_amd as tsa
+    from torch_sputnik_amd import ops
+    from torch_sputnik_amd.graphs import capture_training_step
+    torch.manual_seed(3)
+    out_f = in_f = 256
+    batch, seq = 2, 256
+    layer = tsa.SparseLinear(in_f, out_f).to(dev)
+    with torch.no_grad():
+        layer.weight.copy_(torch.randn(out_f, in_f, device=dev) * (torch.rand(out_f, in_f, device=dev) < 0.3))
+    layer.setup_sparse_tensors()
+    assert ops.half_linear_supported(out_f, in_f, seq, batch, layer.column_indices.numel(), torch.float32,
+                                     torch.float16)
+    x = torch.randn(batch, seq, in_f, device=dev).half()
+    g = torch.randn(batch, out_f, seq, device=dev) / 3
+
+    def eager(xi, gi):
+        xg = xi.clone().requires_grad_(True)
+        layer.values.grad = None
+        out = layer(xg)
+        out.backward(gi)
+        return out.detach().clone(), xg.grad.clone(), layer.values.grad.clone()
+
+    want = eager(x, g)
+    step = capture_training_step(layer, x, grad_output=g)
+    for scale in (1.0, 1e-8, 7e4, 1.0):
+        gi = g * scale
+        wi = want if scale == 1.0 else eager(x, gi)
+        out = step(x, grad_output=gi)
+        torch.cuda.synchronize()
+        grads = {id(p): gp for p, gp in zip(step.params, step.param_grads)}
+        assert torch.equal(out, wi[0])
+        assert torch.equal(step.input_grads[0], wi[1])
+        assert torch.equal(grads[id(layer.values)], wi[2])
+        assert bool(torch.isfinite(wi[2]).all())

@@ -743,7 +743,7 @@ def sddmm_sum_mixed_scratch_bytes(m, k, n, nonzeros, replicas, lhs, rhs):
 def sddmm_sum_mixed(m, k, n, replicas, row_indices, row_offsets, column_indices, lhs, rhs, out,
                     workspace, scratch, planned=False):
     """The summed SDDMM on a (float32, half) pair of operands: the float32 one enters the
-    matrix-core product as two half planes (not rounded).  Raises (status -2) where that
+    matrix-core product as half planes over its range (include/sputnik_hip.h).  Raises (status -2) where that
     route does not serve the shape."""
     nonzeros = column_indices.numel()
     _require(out, torch.float32, "out")

@@ -38,19 +38,35 @@ int sddmm_mfma_launch(int m, int k, int n, int nonzeros, int replicas, const int
 // `half_type`, `count` elements apart, whose (scaled) sum is the value: how an operand that
 // arrives as float32 enters the half-operand product without being rounded to the storage
 // type (planes = that number above, the operand's plane stride = count).
+// float16 planes are of the values times 2^shift, the tensor's range (mfma_tiles.h), which
+// the call finds on the device and leaves in a trailer behind the planes: the buffer holds
+// split_planes_bytes(count, half_type); split_planes_shift points at the shift (bfloat16:
+// no trailer, null).
 int sddmm_mfma_planes_of(int half_type);
+size_t split_planes_bytes(int64_t count, int half_type);
+const int* split_planes_shift(const void* planes, int64_t count, int half_type);
 int sddmm_mfma_split_planes(int64_t count, const float* in, int half_type, void* planes,
                             hipStream_t stream);
+// the range's first launch: per-block maxima of `count` floats into a trailer
+int range_measure(int64_t count, const float* in, void* trailer, hipStream_t stream);
 
 // out[i] = partials[0][i] + ... + partials[parts - 1][i], index order (sddmm.hip)
 int sum_partial_vectors(int nonzeros, int parts, const float* partials, float* out, hipStream_t stream);
 
 // left_spmm (values shared by the replicas) as a dense contraction: the densified weight
 // against the dense operand [replicas][k][n] on half tiles of `tile_type` (spmm_mfma.hip).
-// A float32 operand enters as half planes (not rounded).  Workspace: the densified
-// weight's planes, then a float32 dense operand's.
+// A float32 operand enters as half planes (float16: over the range of the tensor's largest
+// finite magnitude, see split_planes_kernel).  Workspace: the densified weight's planes
+// (densified_bytes, with their range trailer), then a float32 dense operand's
+// (split_planes_bytes).
 bool spmm_mfma_shape(int m, int k, int n, int nonzeros, int replicas, int values_type,
                      int dense_type, int tile_type);
+// the weight's image [planes][rows_padded][k] (+ the range trailer of float32 values on
+// float16 tiles)
+size_t densified_bytes(int64_t rows_padded, int k, int values_type, int tile_type);
+int densify_into(int m, int k, int nonzeros, const int* row_offsets, const int* column_indices,
+                 const void* values, int values_type, int tile_type, void* image, int64_t rows_padded,
+                 hipStream_t stream);
 size_t spmm_mfma_workspace_bytes(int m, int k, int n, int replicas, int values_type, int dense_type,
                                  int tile_type);
 int spmm_mfma_launch(int m, int k, int n, int nonzeros, int replicas, const int* row_offsets,

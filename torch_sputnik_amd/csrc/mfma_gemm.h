@@ -22,9 +22,11 @@
 //
 // Planes: an operand that arrived as float32 is given as PA / PB half planes whose (scaled)
 // sum is the value (split_planes_kernel / densify_kernel); a step multiplies every pair of
-// planes whose order a + b stays below the longer plane count.  float16 keeps its low plane
-// scaled by 2^11 (out of the subnormals) and accumulates the order-1 products in a second
-// tile (ACCS = 2) that enters the result times 2^-11.
+// planes whose order a + b stays below the longer plane count.  float16 planes are of the
+// operand times 2^shift (its range, mfma_tiles.h: read from the trailer behind the planes
+// and undone in the epilogue), keep their low plane scaled by 2^11 (out of the subnormals)
+// and accumulate the order-1 products in a second tile (ACCS = 2) that enters the result
+// times 2^-11.
 //
 // Epilogues: kDense (float32 tile, bias / ReLU), kDenseHalf (rounded to T), kSampled (the
 // tile goes to LDS and the entries of a CSR mask that fall into it are stored: SDDMM).
@@ -78,8 +80,11 @@ struct Passes {
   }
 };
 
+// An operand split from float32 into float16 planes carries its range shift (mfma_tiles.h)
+// in the trailer behind them: at base + planes * plane_stride * 2 bytes rounded up to 256
+// (split_planes_bytes, densified_bytes).
 struct GemmOperand {
-  const void* base;        // plane 0, replica 0
+  const void* base;        // plane 0, replica 0 (the start of the planes' buffer)
   int64_t ld;              // elements between consecutive rows (k-contiguous) / k (k-major)
   int64_t replica_stride;  // elements
   int64_t plane_stride;    // elements
@@ -99,6 +104,10 @@ struct GemmOut {
   const int* plan;         // sddmm_mfma_plan_kernel's table, or null
   int nonzeros;
   int vector_columns;
+  // the range shifts of float16 planes (null: none); the result is multiplied by
+  // 2^-(*shift_a + *shift_b)
+  const int* shift_a;
+  const int* shift_b;
   // SPUTNIK_HIP_MFMA_DEBUG (timing experiments, wrong results): 1 no MFMAs, 2 no copies after
   // the prologue's, 4 no fragment reads
   int debug;
@@ -239,6 +248,12 @@ __global__ __launch_bounds__((TileGeometry<TM, EPI>::kThreads), (TM == 256 ? 1 :
     outer = work / (tiles_m * tiles_n);
   }
   const int r0 = rt * TM, c0 = ct * kTile;
+  // (read at the start: the epilogue's stores must not wait behind a load)
+  int shift = 0;
+  if constexpr (ACCS == 2) {
+    if (out.shift_a != nullptr) shift += *out.shift_a;
+    if (out.shift_b != nullptr) shift += *out.shift_b;
+  }
   // the (replica, k step) pairs this workgroup reduces
   const int s_begin = outer_is_split ? static_cast<int>(static_cast<int64_t>(total_steps) * outer / outers)
                                      : outer * steps_per_replica;
@@ -410,8 +425,10 @@ __global__ __launch_bounds__((TileGeometry<TM, EPI>::kThreads), (TM == 256 ? 1 :
     __syncthreads();   // (the epilogue below writes over the stages)
   }
 
+  // (float16 planes come with ACCS = 2: a route without them keeps its arithmetic)
   auto value = [&](int i, int j, int reg) {
-    return ACCS == 2 ? fmaf(acc[ACCS - 1][i][j][reg], low_scale, acc[0][i][j][reg]) : acc[0][i][j][reg];
+    return ACCS == 2 ? ldexpf(fmaf(acc[ACCS - 1][i][j][reg], low_scale, acc[0][i][j][reg]), -shift)
+                     : acc[0][i][j][reg];
   };
 
   if constexpr (EPI != kSampled) {
@@ -599,12 +616,21 @@ inline int launch_mfma_gemm_typed(int tile_type, int pa, int pb, int m, int n, i
                                   const GemmOperand& b, const GemmOut& out, hipStream_t stream,
                                   bool wide) {
   const float low = 1.f / kLowPlaneScale;
+  GemmOut o = out;
+  if (tile_type == SPUTNIK_HIP_F16) {
+    auto range_of = [](const GemmOperand& op, int planes) {
+      return reinterpret_cast<const int*>(static_cast<const char*>(op.base) +
+                                          (static_cast<size_t>(planes) * op.plane_stride * 2 + 255) / 256 * 256);
+    };
+    o.shift_a = pa == 2 ? range_of(a, pa) : nullptr;
+    o.shift_b = pb == 2 ? range_of(b, pb) : nullptr;
+  }
 #define SPUTNIK_HIP_GEMM(T, PA, PB, ACCS, LOW)                                                    \
   return wide ? launch_mfma_gemm<T, 256, AKM, BKM, PA, PB, ACCS, EPI>(m, n, k, replicas, outers,  \
-                                                                      outer_is_split, a, b, out,  \
+                                                                      outer_is_split, a, b, o,    \
                                                                       LOW, stream)                \
               : launch_mfma_gemm<T, 128, AKM, BKM, PA, PB, ACCS, EPI>(m, n, k, replicas, outers,  \
-                                                                      outer_is_split, a, b, out,  \
+                                                                      outer_is_split, a, b, o,    \
                                                                       LOW, stream)
   if (tile_type == SPUTNIK_HIP_F16) {
     if (pa == 1 && pb == 1) SPUTNIK_HIP_GEMM(_Float16, 1, 1, 1, 1.f);

@@ -40,6 +40,43 @@ static_assert(kTileBytes >= 2 * kStageBytes, "the float tile reuses the stages")
 
 constexpr float kLowPlaneScale = 2048.f;   // 2^11: the float16 split's low plane (see split_planes_kernel)
 
+// The float16 split's range.  A float32 operand is scaled by 2^shift before it is split,
+// shift = 14 - floor(log2(amax)) over its FINITE elements (0 when there are none), so that
+// its largest magnitude lies in [2^14, 2^15); the tile kernel's epilogue multiplies by
+// 2^-(shift_a + shift_b).  Both are exact (ldexp), so within the band where the unscaled
+// split was already right the planes and the results keep their bits.  Every value keeps 22
+// bits down to 2^-28 of the largest (the low plane leaves float16's subnormals there), the
+// error stays below 2^-50 of the largest beneath that, over float32's whole range
+// (subnormals included); without the shift only |v| in ~[1e-6, 65504) was covered.  The shift is found on the
+// device by two launches -- range_kernel writes one maximum per block, the splitting kernel
+// reduces them (every block the same way) -- and lives in a trailer behind the planes:
+//   int shift, then (at byte 256) kRangeBlocks per-block maxima (bits of |v|).
+// inf / NaN take no part in amax and come out of the split non-finite (inf - inf = NaN).
+constexpr int kRangeBlocks = 512;
+constexpr size_t kRangeBytes = 256 + 4 * kRangeBlocks;   // 2304: a multiple of 256
+constexpr int kRangeTop = 14;                            // amax * 2^shift in [2^14, 2^15)
+
+// shift from the bits of the largest finite |v| (the order of non-negative floats is that
+// of their bits)
+__device__ __forceinline__ int range_shift_of(unsigned amax_bits) {
+  if (amax_bits == 0) return 0;
+  const int e = static_cast<int>(amax_bits >> 23) - 127;   // (-127: a subnormal amax)
+  return kRangeTop - e;
+}
+
+// The shift from range_kernel's maxima; every thread of a 256-thread block calls it.
+__device__ __forceinline__ int range_shift(const unsigned* __restrict__ maxima) {
+  __shared__ unsigned wave_max[4];
+  unsigned v = max(maxima[threadIdx.x], maxima[threadIdx.x + 256]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, static_cast<unsigned>(__shfl_xor(static_cast<int>(v), o)));
+  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
+  return range_shift_of(v);
+}
+static_assert(kRangeBlocks == 512, "range_shift reads two maxima per thread of 256");
+
 // ints of the plan's row_ok part (the table sits behind it)
 __host__ __device__ inline int64_t plan_rows(int m) { return (static_cast<int64_t>(m) + 3) / 4 * 4; }
 

@@ -831,10 +831,10 @@ int sputnik_hip_sddmm_sum_typed(int m, int k, int n, int nonzeros, int replicas,
 }
 
 namespace {
-// (float32, half) operand pairs of the summed product: bytes of the float32 operand's two
-// half planes in front of the partial vectors in `scratch`
+// (float32, half) operand pairs of the summed product: bytes of the float32 operand's half
+// planes (and their range trailer) in front of the partial vectors in `scratch`
 size_t mixed_planes_bytes(int rows, int k, int replicas, int half_type) {
-  return (static_cast<size_t>(sddmm_mfma_planes_of(half_type)) * replicas * rows * k * 2 + 255) / 256 * 256;
+  return (split_planes_bytes(static_cast<int64_t>(replicas) * rows * k, half_type) + 255) / 256 * 256;
 }
 bool mixed_pair(int lhs_type, int rhs_type) {
   const bool lhs_half = lhs_type == SPUTNIK_HIP_F16 || lhs_type == SPUTNIK_HIP_BF16;

@@ -49,20 +49,29 @@ using namespace mfma_tiles;
 // round((v - p0) * scale1), p2 = round(v - p0 - p1) -- the products p * x are exact in
 // float32, so a float32 operand (the incoming gradient of modules/sparse_linear.py:44-49,
 // which no storage type rounds) keeps its bits on the matrix cores at PLANES times the tiles.
-//   float16: 2 planes, the low one scaled by 2^11 (scale1; the kernel accumulates it in a
-//     tile of its own and adds it times 2^-11): 22 bits of every value down to ~1e-6 --
-//     unscaled, the low plane of a value below 0.1 would sit in float16's subnormals;
-//   bfloat16: 3 planes as they are (float32's exponent range): 24 bits.
+//   float16: 2 planes of v * 2^shift (the range, mfma_tiles.h: the tensor's largest finite
+//     magnitude lands in [2^14, 2^15)), the low one scaled by 2^11 (scale1; the kernel
+//     accumulates it in a tile of its own and adds it times 2^-11): 22 bits of every value
+//     down to 2^-28 of the largest, an absolute error below 2^-50 of the largest beneath
+//     that; non-finite values stay non-finite.  Block 0 writes the shift for the tile kernel.
+//   bfloat16: 3 planes as they are (float32's exponent range): 24 bits; no range (maxima
+//     and shift_out null).
 template <typename T, int PLANES>
 __global__ __launch_bounds__(256) void split_planes_kernel(int64_t quads /* of 4 elements */,
                                                            const float* __restrict__ in,
                                                            T* __restrict__ out, int64_t plane_stride,
-                                                           float scale1) {
+                                                           float scale1, const unsigned* __restrict__ maxima,
+                                                           int* __restrict__ shift_out) {
   using T4 = T __attribute__((ext_vector_type(4)));
+  int shift = 0;
+  if (maxima != nullptr) {
+    shift = range_shift(maxima);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *shift_out = shift;
+  }
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < quads;
        i += static_cast<int64_t>(gridDim.x) * 256) {
     const float4 v4 = reinterpret_cast<const float4*>(in)[i];
-    float rest[4] = {v4.x, v4.y, v4.z, v4.w};
+    float rest[4] = {ldexpf(v4.x, shift), ldexpf(v4.y, shift), ldexpf(v4.z, shift), ldexpf(v4.w, shift)};
 #pragma unroll
     for (int p = 0; p < PLANES; ++p) {
       T4 h;
@@ -75,6 +84,60 @@ __global__ __launch_bounds__(256) void split_planes_kernel(int64_t quads /* of 4
       reinterpret_cast<T4*>(out + p * plane_stride)[i] = h;
     }
   }
+}
+
+// The range's first launch: per block the bits of the largest finite |v| of its share of
+// `count` floats (kRangeBlocks blocks, each writes its word: nothing is initialised).
+__global__ __launch_bounds__(256) void range_kernel(int64_t count, const float* __restrict__ in,
+                                                    unsigned* __restrict__ maxima) {
+  __shared__ unsigned wave_max[4];
+  const int64_t stride = static_cast<int64_t>(kRangeBlocks) * 256;
+  const int64_t first = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  unsigned m = 0;
+  auto take = [&](float v) {
+    const unsigned b = __float_as_uint(v) & 0x7fffffffu;
+    if (b < 0x7f800000u) m = max(m, b);
+  };
+  if (count % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0) {
+    const float4* in4 = reinterpret_cast<const float4*>(in);
+    const int64_t quads = count / 4;
+    // (eight independent loads in flight per thread: one at a time, a 32 MB dy took
+    // sixteen memory latencies)
+    constexpr int kUnroll = 8;
+    for (int64_t base = first; base < quads; base += kUnroll * stride) {
+      float4 v[kUnroll];
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        const int64_t i = base + u * stride;
+        v[u] = i < quads ? in4[i] : float4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        take(v[u].x);
+        take(v[u].y);
+        take(v[u].z);
+        take(v[u].w);
+      }
+    }
+  } else {
+    constexpr int kUnroll = 8;
+    for (int64_t base = first; base < count; base += kUnroll * stride) {
+      float v[kUnroll];
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        const int64_t i = base + u * stride;
+        v[u] = i < count ? in[i] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) take(v[u]);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, static_cast<unsigned>(__shfl_xor(static_cast<int>(m), o)));
+  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    maxima[blockIdx.x] = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
 }
 
 // The plan: per row, where its entry stream crosses the boundaries of the 128-column
@@ -184,6 +247,23 @@ int sddmm_mfma_launch(int m, int k, int n, int nonzeros, int replicas, const int
 
 int sddmm_mfma_planes_of(int half_type) { return half_type == SPUTNIK_HIP_BF16 ? 3 : 2; }
 
+size_t split_planes_bytes(int64_t count, int half_type) {
+  const size_t planes = (static_cast<size_t>(sddmm_mfma_planes_of(half_type)) * count * 2 + 255) / 256 * 256;
+  return planes + (half_type == SPUTNIK_HIP_F16 ? kRangeBytes : 0);
+}
+
+const int* split_planes_shift(const void* planes, int64_t count, int half_type) {
+  if (half_type != SPUTNIK_HIP_F16) return nullptr;
+  return reinterpret_cast<const int*>(static_cast<const char*>(planes) +
+                                      split_planes_bytes(count, half_type) - kRangeBytes);
+}
+
+int range_measure(int64_t count, const float* in, void* trailer, hipStream_t stream) {
+  hipLaunchKernelGGL(range_kernel, dim3(kRangeBlocks), dim3(256), 0, stream, count, in,
+                     reinterpret_cast<unsigned*>(static_cast<char*>(trailer) + 256));
+  return launch_status();
+}
+
 int sddmm_mfma_split_planes(int64_t count, const float* in, int half_type, void* planes,
                             hipStream_t stream) {
   if (count % 4 != 0 || !aligned_to(in, 16) || !aligned_to(planes, 8))
@@ -193,11 +273,15 @@ int sddmm_mfma_split_planes(int64_t count, const float* in, int half_type, void*
   const int64_t want = ceil_div64(quads, 256);
   const unsigned blocks = static_cast<unsigned>(want < 8192 ? want : 8192);
   if (half_type == SPUTNIK_HIP_F16) {
+    int* trailer = const_cast<int*>(split_planes_shift(planes, count, half_type));
+    const int st = range_measure(count, in, trailer, stream);
+    if (st != 0) return st;
     hipLaunchKernelGGL((split_planes_kernel<_Float16, 2>), dim3(blocks), dim3(256), 0, stream, quads,
-                       in, static_cast<_Float16*>(planes), count, kLowPlaneScale);
+                       in, static_cast<_Float16*>(planes), count, kLowPlaneScale,
+                       reinterpret_cast<const unsigned*>(reinterpret_cast<char*>(trailer) + 256), trailer);
   } else if (half_type == SPUTNIK_HIP_BF16) {
     hipLaunchKernelGGL((split_planes_kernel<__bf16, 3>), dim3(blocks), dim3(256), 0, stream, quads, in,
-                       static_cast<__bf16*>(planes), count, 1.f);
+                       static_cast<__bf16*>(planes), count, 1.f, nullptr, nullptr);
   } else {
     return SPUTNIK_HIP_INVALID_ARGUMENT;
   }

@@ -12,7 +12,8 @@
 // it over, and ONE densified image of the weight [out, in] (sputnik_hip_sparse_linear_half_image:
 // one launch: every row assembled in LDS and written whole) shared by the forward pass and the input
 // gradient.  float32 values and the float32 dy are not rounded to the storage type: they
-// enter as half planes whose sum is the value (mfma_gemm.h; dy is split once per backward
+// enter as half planes whose sum is the value (float16: over the tensor's range, the power
+// of two in the trailer behind the planes, mfma_tiles.h; dy is split once per backward
 // pass, sputnik_hip_half_planes, and both gradients read the planes).
 #include "mfma.h"
 #include "mfma_gemm.h"
@@ -53,10 +54,6 @@ bool served(int out_f, int in_f, int seq, int batch, int nonzeros, int values_ty
 
 }  // namespace
 
-// (spmm_mfma.hip)
-int densify_into(int m, int k, const int* row_offsets, const int* column_indices, const void* values,
-                 int values_type, int tile_type, void* image, int64_t rows_padded, hipStream_t stream);
-
 }  // namespace sputnik_hip
 
 using namespace sputnik_hip;
@@ -71,7 +68,7 @@ int sputnik_hip_sparse_linear_half_supported(int out_features, int in_features, 
 size_t sputnik_hip_sparse_linear_half_image_bytes(int out_features, int in_features, int values_type,
                                                   int tile_type) {
   if (out_features <= 0 || in_features <= 0 || !half_type(tile_type)) return 0;
-  return static_cast<size_t>(planes_of(values_type, tile_type)) * out_features * in_features * 2;
+  return densified_bytes(out_features, in_features, values_type, tile_type);
 }
 
 int sputnik_hip_sparse_linear_half_image(int out_features, int in_features, int nonzeros,
@@ -84,12 +81,12 @@ int sputnik_hip_sparse_linear_half_image(int out_features, int in_features, int 
   if (image == nullptr || !aligned_to(image, 16) ||
       image_bytes < sputnik_hip_sparse_linear_half_image_bytes(out_features, in_features, values_type, tile_type))
     return SPUTNIK_HIP_INVALID_ARGUMENT;
-  return densify_into(out_features, in_features, row_offsets, column_indices, values, values_type,
+  return densify_into(out_features, in_features, nonzeros, row_offsets, column_indices, values, values_type,
                       tile_type, image, out_features, stream);
 }
 
 size_t sputnik_hip_half_planes_bytes(int64_t count, int tile_type) {
-  return half_type(tile_type) && count > 0 ? static_cast<size_t>(sddmm_mfma_planes_of(tile_type)) * count * 2 : 0;
+  return half_type(tile_type) && count > 0 ? split_planes_bytes(count, tile_type) : 0;
 }
 
 int sputnik_hip_half_planes(int64_t count, const float* in, int tile_type, void* planes,

@@ -14,10 +14,13 @@
 //
 // Two launches per call:
 //   1. densify: the [m rounded up to 128, k] half image of the CSR matrix (one wave per row
-//      assembles the row in LDS and writes it whole: no memset, no 2-byte stores).  float32 values are NOT rounded to the storage type: they leave
+//      assembles the row in LDS and writes it whole: no memset, no 2-byte stores).  float32 values are not rounded to the storage type: they leave
 //      as half planes whose (scaled) sum is the value, as the float32 operand of the
-//      weight gradient does (sddmm_mfma.hip, split_planes_kernel) -- float16: two planes,
-//      the low one scaled by 2^11 and accumulated in a tile of its own; bfloat16: three.
+//      weight gradient does (sddmm_mfma.hip, split_planes_kernel) -- float16: two planes
+//      of the values times their range's power of two (a pass over the values before,
+//      mfma_tiles.h: 22 bits down to 2^-28 of the largest finite magnitude, inf / NaN stay
+//      non-finite), the low one scaled by 2^11 and accumulated in a tile of its own;
+//      bfloat16: three, 24 bits.
 //      A float32 DENSE operand (the incoming gradient in the backward pass) is split the
 //      same way into the workspace.
 //   2. the tile kernel: one workgroup (4 waves) = one 128 x 128 tile of one replica's
@@ -46,17 +49,25 @@ using namespace mfma_tiles;
 // it out whole in 16-byte pieces -- every byte of the image is written exactly once, no
 // memset pass, no 2-byte stores to memory (k a multiple of 8; rows beyond m come out zero;
 // k beyond 2048 in segments of 2048 columns, each walking the row's entries again).
-// TV = float: split into planes as split_planes_kernel does (sddmm_mfma.hip); TV = T: as
-// they are (PLANES = 1).  A column outside [0, k) is skipped.
+// TV = float: split into planes as split_planes_kernel does (sddmm_mfma.hip; float16: of
+// the values times 2^shift, from range_kernel's maxima, block 0 writes the shift); TV = T:
+// as they are (PLANES = 1).  A column outside [0, k) is skipped.
 template <typename T, typename TV, int PLANES>
 __global__ __launch_bounds__(256) void densify_kernel(int m, int rows, int k,
                                                       const int* __restrict__ row_offsets,
                                                       const int* __restrict__ column_indices,
                                                       const TV* __restrict__ values, T* __restrict__ image,
-                                                      int64_t plane_stride, float scale1) {
+                                                      int64_t plane_stride, float scale1,
+                                                      const unsigned* __restrict__ maxima,
+                                                      int* __restrict__ shift_out) {
   constexpr int kSeg = 2048;
   __shared__ __attribute__((aligned(16))) T segment[4][PLANES][kSeg];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int shift = 0;
+  if (maxima != nullptr) {   // (before any wave leaves: every thread takes part)
+    shift = range_shift(maxima);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *shift_out = shift;
+  }
   const int row = blockIdx.x * 4 + wave;
   if (row >= rows) return;
   const int p0 = row < m ? row_offsets[row] : 0, p1 = row < m ? row_offsets[row + 1] : 0;
@@ -70,7 +81,7 @@ __global__ __launch_bounds__(256) void densify_kernel(int m, int rows, int k,
     for (int p = p0 + lane; p < p1; p += 64) {
       const unsigned col = static_cast<unsigned>(column_indices[p] - c0);
       if (col >= static_cast<unsigned>(width)) continue;
-      float rest = static_cast<float>(values[p]);
+      float rest = ldexpf(static_cast<float>(values[p]), shift);
 #pragma unroll
       for (int z = 0; z < PLANES; ++z) {
         const float scaled = z == 1 ? rest * scale1 : rest;
@@ -103,22 +114,38 @@ int passes_of(int pa, int pb) {
 
 }  // namespace
 
-// The image [planes][rows_padded][k] of the tile type (one launch: every byte written once).
-int densify_into(int m, int k, const int* row_offsets, const int* column_indices, const void* values,
-                 int values_type, int tile_type, void* image, int64_t rows_padded, hipStream_t stream) {
+size_t densified_bytes(int64_t rows_padded, int k, int values_type, int tile_type) {
+  const size_t planes = (static_cast<size_t>(planes_of(values_type, tile_type)) * rows_padded * k * 2 + 255) / 256 * 256;
+  return planes + (values_type == SPUTNIK_HIP_F32 && tile_type == SPUTNIK_HIP_F16 ? kRangeBytes : 0);
+}
+
+// The image [planes][rows_padded][k] of the tile type, and the range trailer of float32
+// values on float16 tiles (densified_bytes in all).  Every byte of the planes is written once.
+int densify_into(int m, int k, int nonzeros, const int* row_offsets, const int* column_indices,
+                 const void* values, int values_type, int tile_type, void* image, int64_t rows_padded,
+                 hipStream_t stream) {
   if (k % 8 != 0 || !aligned_to(image, 16)) return SPUTNIK_HIP_INVALID_ARGUMENT;
   const int64_t a_plane = rows_padded * k;
   const dim3 rows_grid(static_cast<unsigned>(ceil_div64(rows_padded, 4)));
-#define SPUTNIK_HIP_DENSIFY(T, TV, PLANES, SCALE)                                                  \
+#define SPUTNIK_HIP_DENSIFY(T, TV, PLANES, SCALE, MAXIMA, SHIFT)                                   \
   hipLaunchKernelGGL((densify_kernel<T, TV, PLANES>), rows_grid, dim3(256), 0, stream, m,          \
                      static_cast<int>(rows_padded), k, row_offsets, column_indices,                \
-                     static_cast<const TV*>(values), static_cast<T*>(image), a_plane, SCALE)
+                     static_cast<const TV*>(values), static_cast<T*>(image), a_plane, SCALE,       \
+                     MAXIMA, SHIFT)
   if (tile_type == SPUTNIK_HIP_F16) {
-    if (values_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_DENSIFY(_Float16, float, 2, kLowPlaneScale);
-    else SPUTNIK_HIP_DENSIFY(_Float16, _Float16, 1, 1.f);
+    if (values_type == SPUTNIK_HIP_F32) {
+      char* trailer = static_cast<char*>(image) + densified_bytes(rows_padded, k, values_type, tile_type) -
+                      kRangeBytes;
+      const int st = range_measure(nonzeros, static_cast<const float*>(values), trailer, stream);
+      if (st != 0) return st;
+      SPUTNIK_HIP_DENSIFY(_Float16, float, 2, kLowPlaneScale, reinterpret_cast<const unsigned*>(trailer + 256),
+                          reinterpret_cast<int*>(trailer));
+    } else {
+      SPUTNIK_HIP_DENSIFY(_Float16, _Float16, 1, 1.f, nullptr, nullptr);
+    }
   } else {
-    if (values_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_DENSIFY(__bf16, float, 3, 1.f);
-    else SPUTNIK_HIP_DENSIFY(__bf16, __bf16, 1, 1.f);
+    if (values_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_DENSIFY(__bf16, float, 3, 1.f, nullptr, nullptr);
+    else SPUTNIK_HIP_DENSIFY(__bf16, __bf16, 1, 1.f, nullptr, nullptr);
   }
 #undef SPUTNIK_HIP_DENSIFY
   return launch_status();
@@ -151,9 +178,8 @@ bool spmm_mfma_shape(int m, int k, int n, int nonzeros, int replicas, int values
 
 size_t spmm_mfma_workspace_bytes(int m, int k, int n, int replicas, int values_type, int dense_type,
                                  int tile_type) {
-  const int pa = planes_of(values_type, tile_type), pb = planes_of(dense_type, tile_type);
-  size_t bytes = (static_cast<size_t>(pa) * padded_rows(m) * k * 2 + 255) / 256 * 256;
-  if (dense_type == SPUTNIK_HIP_F32) bytes += static_cast<size_t>(pb) * replicas * k * n * 2;
+  size_t bytes = densified_bytes(padded_rows(m), k, values_type, tile_type);
+  if (dense_type == SPUTNIK_HIP_F32) bytes += split_planes_bytes(static_cast<int64_t>(replicas) * k * n, tile_type);
   return bytes;
 }
 
@@ -164,8 +190,8 @@ int spmm_mfma_launch(int m, int k, int n, int nonzeros, int replicas, const int*
                      hipStream_t stream) {
   const int pa = planes_of(values_type, tile_type), pb = planes_of(dense_type, tile_type);
   const int64_t a_plane = padded_rows(m) * k;
-  const size_t a_bytes = (static_cast<size_t>(pa) * a_plane * 2 + 255) / 256 * 256;
-  int st = densify_into(m, k, row_offsets, column_indices, values, values_type, tile_type, workspace,
+  const size_t a_bytes = densified_bytes(padded_rows(m), k, values_type, tile_type);
+  int st = densify_into(m, k, nonzeros, row_offsets, column_indices, values, values_type, tile_type, workspace,
                         padded_rows(m), stream);
   if (st != 0) return st;
   const void* b = dense;

@@ -598,8 +598,9 @@ class HalfSparseLinearFunction(torch.autograd.Function):
     At a layer's density and size all three products run on the matrix cores and read
     their operands as the caller has them -- NO layout pass (csrc/sparse_linear_half.hip):
     the weight as one densified image (made in the forward pass, kept for the backward),
-    x [B, S, in], dy [B, out, S]; float32 values and the float32 dy enter as half planes,
-    not rounded.  Elsewhere the typed operators with the layout passes of
+    x [B, S, in], dy [B, out, S]; float32 values and the float32 dy enter as half planes
+    whose sum is the value (float16: over the tensor's range, 22 bits down to 2^-28 of its
+    largest finite magnitude; inf / NaN stay non-finite).  Elsewhere the typed operators with the layout passes of
     modules/sparse_linear.py:89 inside the Function (the half operand is what is kept)."""
 
     @staticmethod
@@ -650,7 +651,7 @@ class HalfSparseLinearFunction(torch.autograd.Function):
             grad_dense = None
             if grad_output.dim() == 3:
                 # W^T dy as a dense contraction on half tiles where that route serves the
-                # shape (the float32 gradient enters as half planes, not rounded)
+                # shape (the float32 gradient enters as half planes over its range)
                 values_t, _, row_offsets_t, column_indices_t = _transpose(
                     m, k, values, row_offsets, column_indices)
                 grad_dense = ops.left_spmm_half_tiles(k, m, values_t, row_offsets_t, column_indices_t,

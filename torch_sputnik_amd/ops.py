@@ -34,7 +34,7 @@ def left_spmm_half_tiles(m, k, values, row_offsets, column_indices, dense_matrix
     """left_spmm as a dense contraction on the matrix cores (the half-storage extension,
     csrc/spmm_mfma.hip): the densified weight against dense [R, k, n] on tiles of
     ``tile_dtype`` (float16 / bfloat16); `values` and `dense_matrix` float32 or of that
-    type -- a float32 operand enters as half planes, not rounded.  -> [R, m, n] float32,
+    type -- a float32 operand enters as half planes over its range.  -> [R, m, n] float32,
     or None where the route does not serve the call (take left_spmm then)."""
     import torch
     code = {torch.float16: 1, torch.bfloat16: 2}[tile_dtype]
