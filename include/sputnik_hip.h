@@ -311,6 +311,28 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_linear_half_input_gradient(int out_featur
                               const void* image, int values_type, int tile_type, void* grad_input,
                               int grad_input_type, sputnik_hip_stream_t stream);
 
+/*
+ * The same layer's forward pass in ROW orientation, the layout attention wants:
+ *   y[b][s][o] = sum_i x[b][s][i] W[o][i]
+ * x: element (b, s, i) at x + b * x_batch_stride + s * x_row_stride + i, in `tile_type`;
+ * y: element (b, s, o) at y + b * y_batch_stride + s * y_row_stride + o, stored as
+ * `y_type` (SPUTNIK_HIP_F32 or tile_type) -- e.g. one third of a [batch, seq, 3 * out]
+ * buffer.  W is the IMAGE of sputnik_hip_sparse_linear_half_image (it is this call's
+ * workspace and plan; float32 values enter as its planes, their range shift undone in the
+ * epilogue).  sputnik_hip_sparse_linear_half_rows_supported answers as
+ * sputnik_hip_sparse_linear_half_supported (the same tiles, transposed); the forward
+ * returns SPUTNIK_HIP_UNSUPPORTED for a call it does not serve (in not a multiple of 64,
+ * x not 16-byte aligned or its strides not multiples of 8 elements, a row stride of
+ * 2^24 elements or more) -- use the typed operators then.
+ */
+SPUTNIK_HIP_API int sputnik_hip_sparse_linear_half_rows_supported(int out_features, int in_features,
+                              int seq, int batch, int nonzeros, int values_type, int tile_type);
+SPUTNIK_HIP_API int sputnik_hip_sparse_linear_half_rows_forward(int out_features, int in_features,
+                              int seq, int batch, const void* image, int values_type, const void* x,
+                              int64_t x_batch_stride, int64_t x_row_stride, int tile_type, void* y,
+                              int y_type, int64_t y_batch_stride, int64_t y_row_stride,
+                              sputnik_hip_stream_t stream);
+
 /* sum over the replicas (sputnik_hip_sddmm_sum_batched{,_planned}) on operands stored as
  * `in_type`; the partial vectors and the result are float32.  Workspace / scratch sizes as
  * the float form's (sputnik_hip_sddmm_sum_workspace_bytes / _scratch_bytes).
@@ -697,6 +719,59 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_attention_forward_planned(int m, int n, i
                              int64_t v_stride, float scale, float* out, int64_t out_stride,
                              float* lse, int64_t lse_stride, const void* workspace,
                              size_t workspace_bytes, sputnik_hip_stream_t stream);
+
+/*
+ * The fused attention on float16 / bfloat16 storage (`dtype` SPUTNIK_HIP_F16 / BF16) with
+ * every operand a strided HEAD VIEW: element (b, h, row, c) of q, k, v and out at
+ *   base + b * batch_stride + h * head_stride + row * row_stride + c      (elements)
+ * for b < batch, h < heads (replica r = b * heads + h), so that q, k, v and the context can
+ * stay [B, S, E] tensors (head h = columns h*d .. h*d+d-1: batch_stride S*E, head_stride d,
+ * row_stride E) -- no head split or merge pass.  Values are widened in registers; scores,
+ * weights, the online softmax and every sum are float32.  `out` is stored as `out_type`:
+ * SPUTNIK_HIP_F32 or `dtype`.  `lse` (may be NULL): lse[r * lse_stride + row], float32.
+ * sputnik_hip_sparse_attention_heads_supported checks on the host everything the kernel
+ * assumes: a shape sputnik_hip_sparse_attention_supported serves (d = 64, a mask with
+ * entries), 16-byte aligned bases, strides non-negative and multiples of 16 bytes, and
+ * every replica's extent ((rows - 1) * row_stride + d elements) below 2^32 bytes.  The
+ * forward returns SPUTNIK_HIP_UNSUPPORTED for anything else: compose the typed operators
+ * then.  The workspace and the plan are those of sputnik_hip_sparse_attention_* (the plan
+ * is topology-only: sputnik_hip_sparse_attention_plan makes it for either kernel).
+ * Rows without entries produce zeros (and lse = -inf).
+ */
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_supported(int m, int n, int d, int nonzeros,
+                             int batch, int heads, int dtype, int out_type, const void* q,
+                             int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                             const void* k, int64_t k_batch_stride, int64_t k_head_stride,
+                             int64_t k_row_stride, const void* v, int64_t v_batch_stride,
+                             int64_t v_head_stride, int64_t v_row_stride, const void* out,
+                             int64_t out_batch_stride, int64_t out_head_stride,
+                             int64_t out_row_stride);
+
+SPUTNIK_HIP_API size_t sputnik_hip_sparse_attention_heads_workspace_bytes(int m, int n, int d,
+                                                                          int nonzeros);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_forward(int m, int n, int d, int nonzeros,
+                             int batch, int heads, const int* row_indices, const int* row_offsets,
+                             const int* column_indices, int dtype, const void* q,
+                             int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                             const void* k, int64_t k_batch_stride, int64_t k_head_stride,
+                             int64_t k_row_stride, const void* v, int64_t v_batch_stride,
+                             int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+                             int out_type, int64_t out_batch_stride, int64_t out_head_stride,
+                             int64_t out_row_stride, float* lse, int64_t lse_stride,
+                             void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_forward_planned(int m, int n, int d,
+                             int nonzeros, int batch, int heads, const int* row_indices,
+                             const int* row_offsets, const int* column_indices, int dtype,
+                             const void* q, int64_t q_batch_stride, int64_t q_head_stride,
+                             int64_t q_row_stride, const void* k, int64_t k_batch_stride,
+                             int64_t k_head_stride, int64_t k_row_stride, const void* v,
+                             int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride,
+                             float scale, void* out, int out_type, int64_t out_batch_stride,
+                             int64_t out_head_stride, int64_t out_row_stride, float* lse,
+                             int64_t lse_stride, const void* workspace, size_t workspace_bytes,
+                             sputnik_hip_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * "many mask" family: `masks` topologies of the same m x n shape, laid out

@@ -114,6 +114,10 @@ SIGNATURES = {
     "sputnik_hip_half_planes": (_c_int, [_c_i64, _c_ptr, _c_int, _c_ptr, _c_ptr]),
     "sputnik_hip_sparse_linear_half_forward": (_c_int, [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr, _c_int,
                                                                       _c_ptr, _c_int, _c_ptr, _c_ptr]),
+    "sputnik_hip_sparse_linear_half_rows_supported": (_c_int, [_c_int] * 7),
+    "sputnik_hip_sparse_linear_half_rows_forward": (_c_int, [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr, _c_i64, _c_i64,
+                                                                           _c_int, _c_ptr, _c_int, _c_i64, _c_i64,
+                                                                           _c_ptr]),
     "sputnik_hip_sparse_linear_half_plan_bytes": (_c_size, [_c_int] * 2),
     "sputnik_hip_sparse_linear_half_plan": (_c_int, [_c_int] * 2 + [_c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     "sputnik_hip_sparse_linear_half_scratch_bytes": (_c_size, [_c_int] * 7),
@@ -141,6 +145,14 @@ SIGNATURES = {
     "sputnik_hip_sparse_attention_forward_planned": (_c_int, [_c_int] * 5 + [
         _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_float, _c_ptr,
         _c_i64, _c_ptr, _c_i64, _c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_heads_supported": (_c_int, [_c_int] * 8 + [_c_ptr, _c_i64, _c_i64, _c_i64] * 4),
+    "sputnik_hip_sparse_attention_heads_workspace_bytes": (_c_size, [_c_int] * 4),
+    "sputnik_hip_sparse_attention_heads_forward": (_c_int, [_c_int] * 6 + [_c_ptr] * 3 + [_c_int] + [
+        _c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [_c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64,
+                                               _c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_heads_forward_planned": (_c_int, [_c_int] * 6 + [_c_ptr] * 3 + [_c_int] + [
+        _c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [_c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64,
+                                               _c_ptr, _c_size, _c_ptr]),
     "sputnik_hip_spmm_many_mask": (_c_int, [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr, _c_ptr, _c_i64,
                                                           _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr,
                                                           _c_i64, _c_ptr, _c_size, _c_ptr]),
@@ -576,6 +588,49 @@ def sparse_attention_forward(m, n, d, replicas, row_indices, row_offsets, column
         m, _ptr(workspace), _ws_bytes(workspace), _stream(out)),
         "sputnik_hip_sparse_attention_forward")
     return out
+
+
+def _head_view(t):
+    """(pointer, batch, head, row strides) of a [B, H, rows, d] view with a unit last stride."""
+    if not (t.is_cuda and t.dim() == 4 and t.stride(3) == 1):
+        raise ValueError("expected a [B, H, rows, d] GPU view with a unit last stride")
+    return [_ptr(t), t.stride(0), t.stride(1), t.stride(2)]
+
+
+def sparse_attention_heads_supported(m, n, d, nonzeros, q, k, v, out):
+    """Whether the half-storage fused kernel serves these [B, H, rows, d] views."""
+    views = _head_view(q) + _head_view(k) + _head_view(v) + _head_view(out)
+    return bool(lib().sputnik_hip_sparse_attention_heads_supported(
+        m, n, d, nonzeros, q.size(0), q.size(1), TYPE_CODES[q.dtype], TYPE_CODES[out.dtype], *views))
+
+
+def sparse_attention_heads_workspace_bytes(m, n, d, nonzeros):
+    return lib().sputnik_hip_sparse_attention_heads_workspace_bytes(m, n, d, nonzeros)
+
+
+def sparse_attention_heads_forward(m, n, d, row_indices, row_offsets, column_indices, q, k, v, scale, out,
+                                   lse=None, workspace=None, planned=False):
+    """Fused attention on float16 / bfloat16 head views q [B,H,m,d], k and v [B,H,n,d] into the
+    view `out` (float32 or the operands' type); lse [B*H, m] float32 or None.  `planned`: the
+    workspace holds sputnik_hip_sparse_attention_plan's pre-pass."""
+    fn = (lib().sputnik_hip_sparse_attention_heads_forward_planned if planned
+          else lib().sputnik_hip_sparse_attention_heads_forward)
+    _check(fn(m, n, d, column_indices.numel(), q.size(0), q.size(1), _ptr(row_indices), _ptr(row_offsets),
+              _ptr(column_indices), TYPE_CODES[q.dtype], *_head_view(q), *_head_view(k), *_head_view(v),
+              float(scale), _ptr(out), TYPE_CODES[out.dtype], *_head_view(out)[1:], _ptr(lse), m,
+              _ptr(workspace), _ws_bytes(workspace), _stream(out)),
+           "sputnik_hip_sparse_attention_heads_forward")
+    return out
+
+
+def sparse_linear_half_rows_forward(out_features, image, values_dtype, x, y):
+    """y[b][s][o] = sum_i x[b][s][i] W[o][i] from W's image (sputnik_hip_sparse_linear_half_image),
+    x [B, S, in] half, y a [B, S, out] view (float32 or x's type), both with unit last strides."""
+    _check(lib().sputnik_hip_sparse_linear_half_rows_forward(
+        out_features, x.size(2), x.size(1), x.size(0), _ptr(image), TYPE_CODES[values_dtype], _ptr(x),
+        x.stride(0), x.stride(1), TYPE_CODES[x.dtype], _ptr(y), TYPE_CODES[y.dtype], y.stride(0), y.stride(1),
+        _stream(x)), "sputnik_hip_sparse_linear_half_rows_forward")
+    return y
 
 
 def sddmm_plan(m, k, n, row_indices, row_offsets, column_indices, workspace):

@@ -90,7 +90,8 @@ __device__ __forceinline__ float dot4(const float4& a, const float4& b) {
 
 // Online-softmax update of one row with `e`-weighted V contributions still to
 // be added by the caller: returns the factor the old accumulators were scaled by.
-__device__ __forceinline__ void rescale(RowAcc& r, float m_new) {
+template <typename R>   // RowAcc, RowAccH<T>
+__device__ __forceinline__ void rescale(R& r, float m_new) {
   const float alpha = __expf(r.mx - m_new);  // mx = -inf gives 0
   r.l *= alpha;
   r.acc.x *= alpha;
@@ -316,6 +317,323 @@ bool supported(int m, int n, int d, int nonzeros) {
          static_cast<int64_t>(n) * kD * 4 < (int64_t{1} << 32);
 }
 
+// ---------------------------------------------------------------------------
+// The same kernel on float16 / bfloat16 storage, every operand a strided HEAD VIEW:
+// element (b, h, row, c) at base + b * batch + h * head + row * row_stride + c, replica
+// r = b * heads + h -- so q, k, v and the context can stay [B, S, E] tensors (head h =
+// columns h*64 .. h*64+63) with no head split or merge pass.  K / V tiles are staged as
+// half rows of 128 bytes (8 rows per 1 KiB copy: 16 KiB per operand and stage instead
+// of 32); scores are dot2 products of stored half pairs (RowAccH), V is widened in
+// registers, scores, weights and the online softmax are float32, the context is stored
+// as float32 or in the storage type.  The per-replica
+// bases are 64-bit scalar arithmetic; offsets inside a replica are 32-bit, which the
+// host predicate (heads_served) guarantees together with the 16-byte alignment of
+// every base and stride.
+// ---------------------------------------------------------------------------
+constexpr int kHRowBytes = kD * 2;                           // one half row: 128 bytes
+constexpr int kHTile = kBK * kD;                             // elements of one of K / V: 16 KiB
+constexpr int kHCopiesPerWave = (kBK / 8) / kWaves;          // 1 KiB copies of 8 rows each
+static_assert((kBK / 8) % kWaves == 0, "half stage copies split evenly over the waves");
+
+struct HeadView {
+  const void* base;
+  int64_t batch, head, row;   // strides in elements
+};
+
+template <typename T>
+struct Vec4;
+template <>
+struct Vec4<_Float16> {
+  using type = _Float16 __attribute__((ext_vector_type(4)));
+  using pair = _Float16 __attribute__((ext_vector_type(2)));
+  // a.x b.x + a.y b.y + c: the products exact, the sum float32 (v_dot2_f32_f16)
+  static __device__ __forceinline__ float dot2(pair a, pair b, float c) {
+    return __builtin_amdgcn_fdot2(a, b, c, false);
+  }
+};
+template <>
+struct Vec4<__bf16> {
+  using type = __bf16 __attribute__((ext_vector_type(4)));
+  using pair = __bf16 __attribute__((ext_vector_type(2)));
+  static __device__ __forceinline__ float dot2(pair a, pair b, float c) {
+    return __builtin_amdgcn_fdot2_f32_bf16(a, b, c, false);
+  }
+};
+template <>
+struct Vec4<float> {
+  using type = f4v;
+};
+
+// four consecutive elements (8-byte aligned for half storage), widened
+template <typename T>
+__device__ __forceinline__ f4v load4(const T* p) {
+  return __builtin_convertvector(*reinterpret_cast<const typename Vec4<T>::type*>(p), f4v);
+}
+
+__device__ __forceinline__ float dot4v(const f4v& a, const f4v& b) {
+  float s = a.x * b.x;
+  s = fmaf(a.y, b.y, s);
+  s = fmaf(a.z, b.z, s);
+  return fmaf(a.w, b.w, s);
+}
+
+template <typename T>
+__device__ __forceinline__ void stage_kv_half(T* __restrict__ tile, const T* __restrict__ k,
+                                              unsigned k_row_bytes, const T* __restrict__ v,
+                                              unsigned v_row_bytes, int n, int jc, int wave, int lane) {
+  const int g = lane >> 3, i = lane & 7;
+#pragma unroll
+  for (int j = 0; j < kHCopiesPerWave; ++j) {
+    const int r0 = (wave + j * kWaves) * 8;
+    const unsigned src_row = static_cast<unsigned>(min(jc + r0 + g, n - 1));  // past the last key: the last row
+    lds_dma_row(reinterpret_cast<const float*>(k), src_row * k_row_bytes + i * 16u,
+                reinterpret_cast<const float*>(tile + r0 * kD));
+    lds_dma_row(reinterpret_cast<const float*>(v), src_row * v_row_bytes + i * 16u,
+                reinterpret_cast<const float*>(tile + kHTile + r0 * kD));
+  }
+}
+
+// A row's state in the heads kernel: q as STORED (the score step multiplies half pairs with
+// v_dot2_f32_*: exact products, float32 sums -- no widening instruction per element, which
+// left the issue-bound kernel a quarter longer; the scale is applied to the float32 score).
+template <typename T>
+struct RowAccH {
+  typename Vec4<T>::pair q[4][2];   // elements 16t + 4((c + quad) % 4) .. +3 for c = 0..3
+  float4 acc;
+  float mx, l;
+};
+
+template <typename T, typename TO>
+__global__ __launch_bounds__(kThreads) void sparse_attention_heads_kernel(
+    int m, int n, int nonzeros, int slots, int nchunks, int heads, int replica0,
+    const int* __restrict__ row_indices, const int* __restrict__ row_offsets,
+    const int* __restrict__ column_indices, const int* __restrict__ table,
+    const int* __restrict__ row_ok, HeadView qv, HeadView kv, HeadView vv, float scale,
+    HeadView ov, float* __restrict__ lse, int64_t lse_stride) {
+  __shared__ __attribute__((aligned(16))) T tile[2][2 * kHTile];  // [buffer][K rows | V rows]
+
+  const int lane = threadIdx.x % kWave;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int g = lane >> 4, i = lane & 15;
+  const int qd = i >> 2, tq = i & 3;
+  const int e16 = 4 * tq + qd;
+  const unsigned long long work = xcd_local_index();
+  const int mblock = static_cast<int>(work % gridDim.x);
+  const int replica = replica0 + static_cast<int>(work / gridDim.x);
+  const int64_t b = replica / heads, h = replica - b * heads;
+  const T* __restrict__ q = static_cast<const T*>(qv.base) + (b * qv.batch + h * qv.head);
+  const T* __restrict__ k = static_cast<const T*>(kv.base) + (b * kv.batch + h * kv.head);
+  const T* __restrict__ v = static_cast<const T*>(vv.base) + (b * vv.batch + h * vv.head);
+  TO* __restrict__ out = static_cast<TO*>(const_cast<void*>(ov.base)) + (b * ov.batch + h * ov.head);
+  if (lse != nullptr) lse += replica * lse_stride;
+  // (in-replica offsets: below 2^32 bytes, heads_served)
+  const unsigned q_rs = static_cast<unsigned>(qv.row), k_rs = static_cast<unsigned>(kv.row),
+                 v_rs = static_cast<unsigned>(vv.row), o_rs = static_cast<unsigned>(ov.row);
+  const int slot0 = mblock * kBM + wave * (kRQ * 4);
+  const int last = nonzeros - 1;
+
+  using V4 = Vec4<T>;
+  using P2 = typename V4::pair;
+  RowAccH<T> st[kRQ];
+  int my_row[kRQ];
+#pragma unroll
+  for (int t = 0; t < kRQ; ++t) {
+    const int entry = dealt_index(slot0 + 4 * t + g, slots, kBM);
+    my_row[t] = entry < m ? row_indices[entry] : -1;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      typename V4::type qh = {};
+      if (my_row[t] >= 0)
+        qh = *reinterpret_cast<const typename V4::type*>(
+            q + (static_cast<unsigned>(my_row[t]) * q_rs + 16 * tq + 4 * ((c + qd) & 3)));
+      st[t].q[c][0] = P2{qh.x, qh.y};
+      st[t].q[c][1] = P2{qh.z, qh.w};
+    }
+    st[t].acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    st[t].mx = -INFINITY;
+    st[t].l = 0.f;
+  }
+
+  auto finish = [&]() {
+#pragma unroll
+    for (int t = 0; t < kRQ; ++t) {
+      if (my_row[t] < 0) continue;
+      const float inv = st[t].l > 0.f ? 1.f / st[t].l : 0.f;  // rows without entries give zeros
+      const f4v r = {st[t].acc.x * inv, st[t].acc.y * inv, st[t].acc.z * inv, st[t].acc.w * inv};
+      *reinterpret_cast<typename Vec4<TO>::type*>(out + (static_cast<unsigned>(my_row[t]) * o_rs + 4 * i)) =
+          __builtin_convertvector(r, typename Vec4<TO>::type);
+      if (lse != nullptr && i == 0)
+        lse[my_row[t]] = st[t].l > 0.f ? st[t].mx + __logf(st[t].l) : -INFINITY;
+    }
+  };
+
+  // Row blocks whose columns do not ascend inside rows: order-independent path,
+  // one entry at a time, K and V rows gathered from global memory.
+  if (!block_rows_ok(row_ok, mblock * kBM, kBM)) {
+    for (int t = 0; t < kRQ; ++t) {
+      const int p0 = my_row[t] >= 0 ? row_offsets[my_row[t]] : 0;
+      const int p1 = my_row[t] >= 0 ? row_offsets[my_row[t] + 1] : 0;
+      f4v q16 = {0.f, 0.f, 0.f, 0.f};   // elements 4i .. 4i+3 of scale * q
+      if (my_row[t] >= 0) q16 = load4(q + (static_cast<unsigned>(my_row[t]) * q_rs + 4 * i)) * scale;
+      for (int p = p0; p < p1; ++p) {
+        const unsigned col = static_cast<unsigned>(column_indices[p]);
+        const f4v kf = load4(k + (col * k_rs + 4 * i));
+        const f4v vf = load4(v + (col * v_rs + 4 * i));
+        const float s = group_sum<16>(dot4v(q16, kf));
+        if (s > st[t].mx) rescale(st[t], s);
+        const float e = __expf(s - st[t].mx);
+        st[t].l += e;
+        st[t].acc.x = fmaf(e, vf.x, st[t].acc.x);
+        st[t].acc.y = fmaf(e, vf.y, st[t].acc.y);
+        st[t].acc.z = fmaf(e, vf.z, st[t].acc.z);
+        st[t].acc.w = fmaf(e, vf.w, st[t].acc.w);
+      }
+    }
+    finish();
+    return;
+  }
+
+  const int* __restrict__ my_table = table + slot0 + g;
+  int ps[kRQ], pe[kRQ], wcol[kRQ][kWin];
+#pragma unroll
+  for (int t = 0; t < kRQ; ++t) {
+    ps[t] = my_table[4 * t];
+    pe[t] = my_table[slots + 4 * t];
+#pragma unroll
+    for (int w = 0; w < kWin; ++w) wcol[t][w] = column_indices[min(ps[t] + 16 * w + e16, last)];
+  }
+
+  const unsigned k_bytes = k_rs * 2u, v_bytes = v_rs * 2u;
+  stage_kv_half(tile[0], k, k_bytes, v, v_bytes, n, 0, wave, lane);
+  wait_vm<0>();
+  __syncthreads();
+
+  for (int c = 0; c < nchunks; ++c) {
+    const int buf = c & 1;
+    const bool more = c + 1 < nchunks;
+    if (more) stage_kv_half(tile[buf ^ 1], k, k_bytes, v, v_bytes, n, (c + 1) * kBK, wave, lane);
+
+    int pe_next[kRQ], ncol[kRQ][kWin];
+#pragma unroll
+    for (int t = 0; t < kRQ; ++t) {
+      pe_next[t] = more ? my_table[static_cast<int64_t>(c + 2) * slots + 4 * t] : pe[t];
+#pragma unroll
+      for (int w = 0; w < kWin; ++w)
+        ncol[t][w] = more ? column_indices[min(pe[t] + 16 * w + e16, last)] : 0;
+    }
+
+    const char* __restrict__ v_base =
+        reinterpret_cast<const char*>(&tile[buf][0] + kHTile) + i * 4 * sizeof(T);
+    const int jc = c * kBK;
+    const int k_lds = static_cast<int>(static_cast<unsigned>(
+        reinterpret_cast<uintptr_t>(AS_LDS(&tile[buf][0]))));   // LDS byte address of the K tile
+
+#pragma unroll
+    for (int t = 0; t < kRQ; ++t) {
+      const int cnt = pe[t] - ps[t];
+
+      auto window = [&](int ecol, int w0) {
+        const int left = cnt - w0;
+        if (left <= 0) return;
+        const bool valid = e16 < left;
+        const int roff = valid ? ((ecol - jc) * kHRowBytes) : 0;
+
+        // 1. scores, quad form (as above; a quarter row is 32 bytes here)
+        float s = 0.f;
+        const int kq = k_lds + 32 * tq;
+        auto scores4 = [&](auto Sc) {
+          constexpr int kS = decltype(Sc)::value;
+          typename V4::type bk[4];
+#pragma unroll
+          for (int c4 = 0; c4 < 4; ++c4)
+            bk[c4] = *reinterpret_cast<const __attribute__((address_space(3))) typename V4::type*>(
+                static_cast<unsigned>(quad_bcast_add<kS>(roff, kq + 8 * ((c4 + qd) & 3))));
+          float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+          for (int c4 = 0; c4 < 4; ++c4) {
+            a0 = V4::dot2(st[t].q[c4][0], P2{bk[c4].x, bk[c4].y}, a0);
+            a1 = V4::dot2(st[t].q[c4][1], P2{bk[c4].z, bk[c4].w}, a1);
+          }
+          const float total = group_sum<4>(a0 + a1);
+          s = (tq == kS) ? total : s;
+        };
+        scores4(std::integral_constant<int, 0>{});
+        if (left > 4) scores4(std::integral_constant<int, 1>{});
+        if (left > 8) scores4(std::integral_constant<int, 2>{});
+        if (left > 12) scores4(std::integral_constant<int, 3>{});
+        s = valid ? s * scale : -INFINITY;
+
+        // 2. online softmax over the window (at least one entry is valid)
+        const float m_new = fmaxf(st[t].mx, group_max<16>(s));
+        rescale(st[t], m_new);
+        const float e = valid ? __expf(s - m_new) : 0.f;
+        st[t].l += group_sum<16>(e);
+
+        // 3. weighted V rows; padded entries carry weight 0 and offset 0
+        const entry_pair ent = make_entry(roff, e);
+        float a4[4] = {st[t].acc.x, st[t].acc.y, st[t].acc.z, st[t].acc.w};
+        auto values4 = [&](auto G) {
+          constexpr int kG = decltype(G)::value;
+          const entry_pair e0 = row_bcast_entry<0 + kG / 4>(ent), e1 = row_bcast_entry<4 + kG / 4>(ent);
+          const entry_pair e2 = row_bcast_entry<8 + kG / 4>(ent), e3 = row_bcast_entry<12 + kG / 4>(ent);
+          const f4v b0 = load4(reinterpret_cast<const T*>(v_base + entry_off(e0)));
+          const f4v b1 = load4(reinterpret_cast<const T*>(v_base + entry_off(e1)));
+          const f4v b2 = load4(reinterpret_cast<const T*>(v_base + entry_off(e2)));
+          const f4v b3 = load4(reinterpret_cast<const T*>(v_base + entry_off(e3)));
+          SPUTNIK_HIP_FMA4(a4, entry_val(e0), b0);
+          SPUTNIK_HIP_FMA4(a4, entry_val(e1), b1);
+          SPUTNIK_HIP_FMA4(a4, entry_val(e2), b2);
+          SPUTNIK_HIP_FMA4(a4, entry_val(e3), b3);
+        };
+        values4(std::integral_constant<int, 0>{});
+        if (left > 4) values4(std::integral_constant<int, 4>{});
+        if (left > 8) values4(std::integral_constant<int, 8>{});
+        if (left > 12) values4(std::integral_constant<int, 12>{});
+        st[t].acc = make_float4(a4[0], a4[1], a4[2], a4[3]);
+      };
+#pragma unroll
+      for (int w = 0; w < kWin; ++w) window(wcol[t][w], 16 * w);
+      const int longest = max(max(__builtin_amdgcn_readlane(cnt, 0), __builtin_amdgcn_readlane(cnt, 16)),
+                              max(__builtin_amdgcn_readlane(cnt, 32), __builtin_amdgcn_readlane(cnt, 48)));
+      for (int w0 = 16 * kWin; w0 < longest; w0 += 16)
+        window(column_indices[min(ps[t] + w0 + e16, last)], w0);
+    }
+
+#pragma unroll
+    for (int t = 0; t < kRQ; ++t) {
+      ps[t] = pe[t];
+      pe[t] = pe_next[t];
+#pragma unroll
+      for (int w = 0; w < kWin; ++w) wcol[t][w] = ncol[t][w];
+    }
+    wait_vm<0>();     // the next K/V tiles have landed
+    __syncthreads();  // ... for every wave, and the current buffer is free
+  }
+  finish();
+}
+
+bool half_code(int t) { return t == SPUTNIK_HIP_F16 || t == SPUTNIK_HIP_BF16; }
+
+// Everything the heads kernel assumes about its operands, checked on the host: a served
+// mask (supported), 16-byte aligned bases and strides, non-negative strides, and every
+// replica's extent below 2^32 bytes (the kernel's in-replica offsets are 32-bit).
+bool view_ok(const HeadView& w, int rows, int elem_bytes) {
+  if (w.base == nullptr || !aligned_to(w.base, 16)) return false;
+  if (w.batch < 0 || w.head < 0 || w.row < 0) return false;
+  if ((w.batch * elem_bytes) % 16 != 0 || (w.head * elem_bytes) % 16 != 0 || (w.row * elem_bytes) % 16 != 0)
+    return false;
+  return (static_cast<int64_t>(rows - 1) * w.row + kD) * elem_bytes < (int64_t{1} << 32);
+}
+
+bool heads_served(int m, int n, int d, int nonzeros, int batch, int heads, int dtype, int out_type,
+                  const HeadView& q, const HeadView& k, const HeadView& v, const HeadView& o) {
+  if (!supported(m, n, d, nonzeros) || !half_code(dtype)) return false;
+  if (out_type != SPUTNIK_HIP_F32 && out_type != dtype) return false;
+  if (batch <= 0 || heads <= 0 || static_cast<int64_t>(batch) * heads >= (int64_t{1} << 31)) return false;
+  return view_ok(q, m, 2) && view_ok(k, n, 2) && view_ok(v, n, 2) &&
+         view_ok(o, m, out_type == SPUTNIK_HIP_F32 ? 4 : 2);
+}
+
 }  // namespace
 }  // namespace sputnik_hip
 
@@ -429,6 +747,119 @@ int sputnik_hip_sparse_attention_forward_planned(
                         q_stride, k, k_stride, v, v_stride, scale, out, out_stride, lse,
                         lse_stride, const_cast<void*>(workspace), workspace_bytes,
                         /*planned=*/true, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+template <typename T, typename TO>
+void launch_heads(dim3 grid, hipStream_t stream, int m, int n, int nonzeros, int slots, int nchunks,
+                  int heads, int replica0, const int* row_indices, const int* row_offsets,
+                  const int* column_indices, const int* table, const int* row_ok, const HeadView& q,
+                  const HeadView& k, const HeadView& v, float scale, const HeadView& o, float* lse,
+                  int64_t lse_stride) {
+  hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO>), grid, dim3(kThreads), 0, stream, m, n,
+                     nonzeros, slots, nchunks, heads, replica0, row_indices, row_offsets,
+                     column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride);
+}
+
+int heads_exec(int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
+               const int* row_offsets, const int* column_indices, int dtype, const HeadView& q,
+               const HeadView& k, const HeadView& v, float scale, const HeadView& o, int out_type,
+               float* lse, int64_t lse_stride, void* workspace, size_t workspace_bytes, bool planned,
+               hipStream_t stream) {
+  if (m < 0 || n < 0 || d < 0 || nonzeros < 0 || batch < 0 || heads < 0)
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (m == 0 || batch == 0 || heads == 0) return 0;
+  if (!heads_served(m, n, d, nonzeros, batch, heads, dtype, out_type, q, k, v, o))
+    return SPUTNIK_HIP_UNSUPPORTED;
+  if (workspace == nullptr || !aligned_to(workspace, 16) ||
+      workspace_bytes < sputnik_hip_sparse_attention_workspace_bytes(m, n, d, nonzeros))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const int slots = slots_of(m), nchunks = chunks_of(n);
+  int* row_ok = static_cast<int*>(workspace);
+  int* table = reinterpret_cast<int*>(static_cast<char*>(workspace) + row_ok_bytes(slots));
+  int st = 0;
+  if (!planned) {
+    hipLaunchKernelGGL((spmm_chunk_table_kernel<kBK>), dim3(ceil_div(slots, 4)), dim3(256), 0, stream,
+                       m, n, slots, kBM, nchunks, row_indices, row_offsets, column_indices, table,
+                       row_ok);
+    st = launch_status();
+    if (st != 0) return st;
+  }
+  const int replicas = batch * heads;
+  for (int r0 = 0; r0 < replicas; r0 += kMaxGridYZ) {
+    const dim3 grid(slots / kBM, min(replicas - r0, kMaxGridYZ));
+#define SPUTNIK_HIP_HEADS(T, TO)                                                                  \
+  launch_heads<T, TO>(grid, stream, m, n, nonzeros, slots, nchunks, heads, r0, row_indices,       \
+                      row_offsets, column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride)
+    if (dtype == SPUTNIK_HIP_F16 && out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS(_Float16, float);
+    else if (dtype == SPUTNIK_HIP_F16) SPUTNIK_HIP_HEADS(_Float16, _Float16);
+    else if (out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS(__bf16, float);
+    else SPUTNIK_HIP_HEADS(__bf16, __bf16);
+#undef SPUTNIK_HIP_HEADS
+    st = launch_status();
+    if (st != 0) return st;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sputnik_hip_sparse_attention_heads_supported(
+    int m, int n, int d, int nonzeros, int batch, int heads, int dtype, int out_type, const void* q,
+    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
+    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
+    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, const void* out,
+    int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride) {
+  return heads_served(m, n, d, nonzeros, batch, heads, dtype, out_type,
+                      HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
+                      HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
+                      HeadView{v, v_batch_stride, v_head_stride, v_row_stride},
+                      HeadView{out, out_batch_stride, out_head_stride, out_row_stride})
+             ? 1 : 0;
+}
+
+size_t sputnik_hip_sparse_attention_heads_workspace_bytes(int m, int n, int d, int nonzeros) {
+  return sputnik_hip_sparse_attention_workspace_bytes(m, n, d, nonzeros);
+}
+
+int sputnik_hip_sparse_attention_heads_forward(
+    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
+    const int* row_offsets, const int* column_indices, int dtype, const void* q,
+    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
+    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
+    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
+    float* lse, int64_t lse_stride, void* workspace, size_t workspace_bytes,
+    sputnik_hip_stream_t stream) {
+  return heads_exec(m, n, d, nonzeros, batch, heads, row_indices, row_offsets, column_indices, dtype,
+                    HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
+                    HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
+                    HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
+                    HeadView{out, out_batch_stride, out_head_stride, out_row_stride}, out_type, lse,
+                    lse_stride, workspace, workspace_bytes, /*planned=*/false, stream);
+}
+
+int sputnik_hip_sparse_attention_heads_forward_planned(
+    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
+    const int* row_offsets, const int* column_indices, int dtype, const void* q,
+    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
+    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
+    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
+    float* lse, int64_t lse_stride, const void* workspace, size_t workspace_bytes,
+    sputnik_hip_stream_t stream) {
+  return heads_exec(m, n, d, nonzeros, batch, heads, row_indices, row_offsets, column_indices, dtype,
+                    HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
+                    HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
+                    HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
+                    HeadView{out, out_batch_stride, out_head_stride, out_row_stride}, out_type, lse,
+                    lse_stride, const_cast<void*>(workspace), workspace_bytes, /*planned=*/true,
+                    stream);
 }
 
 }  // extern "C"

@@ -115,6 +115,44 @@ int sputnik_hip_sparse_linear_half_forward(int out_features, int in_features, in
                                                       wide_tile(out_features, seq, batch));
 }
 
+int sputnik_hip_sparse_linear_half_rows_supported(int out_features, int in_features, int seq, int batch,
+                                                  int nonzeros, int values_type, int tile_type) {
+  return served(out_features, in_features, seq, batch, nonzeros, values_type, tile_type) ? 1 : 0;
+}
+
+// Row orientation, y[b][s][o] = sum_i x[b][s][i] W[o][i]: the forward above with the operands
+// swapped -- A = x (m = seq, k-contiguous, any 16-byte row stride), B = the image (n = out) --
+// and the dense epilogues writing rows of the output with the caller's row stride.
+int sputnik_hip_sparse_linear_half_rows_forward(int out_features, int in_features, int seq, int batch,
+                                                const void* image, int values_type, const void* x,
+                                                int64_t x_batch_stride, int64_t x_row_stride, int tile_type,
+                                                void* y, int y_type, int64_t y_batch_stride,
+                                                int64_t y_row_stride, sputnik_hip_stream_t stream) {
+  if (!half_type(tile_type) || out_features <= 0 || in_features % kStep != 0 || seq <= 0 || batch <= 0)
+    return SPUTNIK_HIP_UNSUPPORTED;
+  if (y_type != SPUTNIK_HIP_F32 && y_type != tile_type) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  // (a tile's copy offsets are 32-bit: 128 rows of x_row_stride elements)
+  if (!aligned_to(image, 16) || !aligned_to(x, 16) || x_row_stride % 8 != 0 || x_batch_stride % 8 != 0 ||
+      x_row_stride < in_features || x_batch_stride < 0 || x_row_stride >= (int64_t{1} << 24))
+    return SPUTNIK_HIP_UNSUPPORTED;
+  if (!aligned_to(y, y_type == SPUTNIK_HIP_F32 ? 4 : 2) || y_row_stride < out_features || y_batch_stride < 0)
+    return SPUTNIK_HIP_UNSUPPORTED;
+  const int pw = planes_of(values_type, tile_type);
+  const GemmOperand a{x, x_row_stride, x_batch_stride, 0};
+  const GemmOperand b{image, in_features, 0, static_cast<int64_t>(out_features) * in_features};
+  GemmOut o{};
+  o.dense = y;
+  o.ld = y_row_stride;
+  o.outer_stride = y_batch_stride;
+  if (y_type == SPUTNIK_HIP_F32)
+    return launch_mfma_gemm_typed<false, false, kDense>(tile_type, 1, pw, seq, out_features, in_features,
+                                                        batch, batch, false, a, b, o, stream,
+                                                        wide_tile(seq, out_features, batch));
+  return launch_mfma_gemm_typed<false, false, kDenseHalf>(tile_type, 1, pw, seq, out_features, in_features,
+                                                          batch, batch, false, a, b, o, stream,
+                                                          wide_tile(seq, out_features, batch));
+}
+
 size_t sputnik_hip_sparse_linear_half_plan_bytes(int out_features, int in_features) {
   return out_features > 0 && in_features > 0 ? sddmm_mfma_plan_bytes(out_features, in_features) : 0;
 }

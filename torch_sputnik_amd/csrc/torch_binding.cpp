@@ -1211,6 +1211,159 @@ Tensor sparse_attention_planned(const Tensor& q, const Tensor& k, const Tensor& 
                                plan)[0];
 }
 
+// ---- the fused attention on half storage with strided head views (sputnik_hip.h:
+// sparse_attention_heads_*) ----
+struct HeadOperand {
+  Tensor t;                      // keeps the storage alive
+  int64_t batch, heads, rows, d;
+  int64_t batch_stride, head_stride, row_stride;
+};
+
+// [B, H, rows, d], [R, rows, d] (H = 1) or [rows, d] (B = H = 1) with unit stride along d.
+HeadOperand head_operand(const Tensor& x_in, const char* name) {
+  TORCH_CHECK(x_in.is_cuda(), name, " must be a GPU (HIP) tensor, got ", x_in.device());
+  TORCH_CHECK(x_in.dim() >= 2 && x_in.dim() <= 4, name, " must have 2, 3 or 4 dimensions, got ", x_in.dim());
+  const Tensor x = x_in.stride(-1) == 1 ? x_in : x_in.contiguous();
+  HeadOperand o;
+  o.t = x;
+  o.rows = x.size(-2);
+  o.d = x.size(-1);
+  o.row_stride = x.stride(-2);
+  if (x.dim() == 4) {
+    o.batch = x.size(0), o.heads = x.size(1);
+    o.batch_stride = x.stride(0), o.head_stride = x.stride(1);
+  } else if (x.dim() == 3) {
+    o.batch = x.size(0), o.heads = 1;
+    o.batch_stride = x.stride(0), o.head_stride = 0;
+  } else {
+    o.batch = 1, o.heads = 1;
+    o.batch_stride = 0, o.head_stride = 0;
+  }
+  return o;
+}
+
+// q [.., m, 64], k and v [.., n, 64] of one half type (any strides with a unit last one);
+// out in the layout of the [B, m, H, d] buffer it views ([B, m, E] for 4-D operands), stored
+// as out_type (0 float32, else the operands' type); lse [.., m] float32 on request.
+// A call the kernel does not serve is composed from the typed operators (no lse then).
+std::vector<Tensor> sparse_attention_heads(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in,
+                                           const Tensor& row_indices, const Tensor& row_offsets,
+                                           const Tensor& column_indices, double scale, int64_t out_type,
+                                           bool want_lse, const c10::optional<Tensor>& plan) {
+  const HeadOperand q = head_operand(q_in, "query"), k = head_operand(k_in, "key"),
+                    v = head_operand(v_in, "value");
+  const auto st = q.t.scalar_type();
+  const int dtype = type_code(st);
+  TORCH_CHECK(dtype == SPUTNIK_HIP_F16 || dtype == SPUTNIK_HIP_BF16,
+              "sparse_attention_heads: expected float16 / bfloat16 operands, got ", st);
+  TORCH_CHECK(k.t.scalar_type() == st && v.t.scalar_type() == st,
+              "sparse_attention_heads: query, key, value must have one type");
+  TORCH_CHECK(q.t.dim() == k.t.dim() && q.t.dim() == v.t.dim(), "query, key, value must match in dims");
+  TORCH_CHECK(k.t.sizes() == v.t.sizes(), "key and value must have one shape");
+  TORCH_CHECK(q.d == k.d, "query and key must have one head dimension");
+  TORCH_CHECK(q.batch == k.batch && q.heads == k.heads, "query and key must have one batch and head count");
+  TORCH_CHECK(q.t.device() == k.t.device() && q.t.device() == v.t.device(),
+              "query, key, value must be on one device");
+  const c10::DeviceGuard guard(q.t.device());
+  const int m = to_int(q.rows, "m"), n = to_int(k.rows, "n"), d = to_int(q.d, "d");
+  const int batch = to_int(q.batch, "batch"), heads = to_int(q.heads, "heads");
+  const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, q.t);
+  const auto out_st = out_type == SPUTNIK_HIP_F32 ? at::kFloat : st;
+  TORCH_CHECK(out_type == SPUTNIK_HIP_F32 || out_type == dtype,
+              "sparse_attention_heads: out_type is float32 or the operands' type");
+
+  Tensor buffer, out;   // out: the [.., m, d] view of `buffer` the kernel writes
+  if (q.t.dim() == 4) {
+    buffer = at::empty({q.batch, q.rows, q.heads, q.d}, q.t.options().dtype(out_st));
+    out = buffer.permute({0, 2, 1, 3});
+  } else {
+    out = buffer = at::empty(q.t.sizes(), q.t.options().dtype(out_st));
+  }
+  const HeadOperand o = head_operand(out, "out");
+  std::vector<int64_t> lse_shape(q.t.sizes().begin(), q.t.sizes().end() - 1);
+  Tensor lse = want_lse ? at::empty(lse_shape, q.t.options().dtype(at::kFloat)) : Tensor();
+
+  const bool served = sputnik_hip_sparse_attention_heads_supported(
+      m, n, d, topo.nonzeros, batch, heads, dtype, static_cast<int>(out_type), q.t.data_ptr(),
+      q.batch_stride, q.head_stride, q.row_stride, k.t.data_ptr(), k.batch_stride, k.head_stride,
+      k.row_stride, v.t.data_ptr(), v.batch_stride, v.head_stride, v.row_stride, o.t.data_ptr(),
+      o.batch_stride, o.head_stride, o.row_stride);
+  if (!served) {
+    TORCH_CHECK(!want_lse, "sparse_attention_heads: lse needs a call the fused kernel serves "
+                "(head dimension 64, 16-byte aligned views)");
+    // the typed operators on per-head copies in the storage type: float32 scores and
+    // weights, float32 product, narrowed into the output's layout
+    const int64_t replicas = q.batch * q.heads;
+    auto per_head = [&](const HeadOperand& x) {
+      const Tensor flat = x.t.reshape({replicas, x.rows, x.d});
+      return replicas == 1 ? flat[0] : flat;
+    };
+    const Tensor q3 = per_head(q), k3 = per_head(k), v3 = per_head(v);
+    const Tensor weights = sparse_softmax_scaled(
+        sddmm(m, n, topo.row_indices, topo.row_offsets, topo.column_indices, q3, k3),
+        topo.row_indices, topo.row_offsets, topo.column_indices, scale);
+    const Tensor product = spmm(m, n, weights, topo.row_indices, topo.row_offsets, topo.column_indices, v3);
+    out.copy_(product.reshape(out.sizes()));
+    return {out};
+  }
+  const size_t ws_bytes = sputnik_hip_sparse_attention_heads_workspace_bytes(m, n, d, topo.nonzeros);
+  Tensor workspace;
+  if (plan.has_value()) check_plan(*plan, ws_bytes, q.t);
+  else workspace = at::empty({static_cast<int64_t>(ws_bytes)}, q.t.options().dtype(at::kByte));
+  auto call = [&](auto forward, auto ws) {
+    return forward(m, n, d, topo.nonzeros, batch, heads, topo.row_indices.data_ptr<int>(),
+                   topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(), dtype,
+                   q.t.data_ptr(), q.batch_stride, q.head_stride, q.row_stride, k.t.data_ptr(),
+                   k.batch_stride, k.head_stride, k.row_stride, v.t.data_ptr(), v.batch_stride,
+                   v.head_stride, v.row_stride, static_cast<float>(scale), o.t.data_ptr(),
+                   static_cast<int>(out_type), o.batch_stride, o.head_stride, o.row_stride,
+                   want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(m), ws, ws_bytes,
+                   current_stream(q.t));
+  };
+  const int status = plan.has_value()
+                         ? call(sputnik_hip_sparse_attention_heads_forward_planned,
+                                static_cast<const void*>(plan->data_ptr()))
+                         : call(sputnik_hip_sparse_attention_heads_forward, workspace.data_ptr());
+  check_status(status, "sparse_attention_heads");
+  if (want_lse) return {out, lse};
+  return {out};
+}
+
+// y [batch, seq, out] = x W^T per batch element in ROW orientation (sputnik_hip.h:
+// sparse_linear_half_rows_forward), x [batch, seq, in] half with a unit last stride; stored
+// into `out` when given (any [batch, seq, out] view with a unit last stride, e.g. a column
+// slice of a wider buffer) as out_type (0 float32, else x's type).  An EMPTY tensor says the
+// route does not serve the call.
+Tensor half_linear_rows(int64_t out64, const Tensor& image, int64_t values_type, const Tensor& x_in,
+                        const c10::optional<Tensor>& out_in, int64_t out_type) {
+  TORCH_CHECK(x_in.is_cuda() && x_in.dim() == 3, "half_linear_rows: x must be a GPU tensor [batch, seq, in]");
+  const Tensor x = x_in.stride(2) == 1 ? x_in : x_in.contiguous();
+  const int tile = tile_code_of(x);
+  const c10::DeviceGuard guard(x.device());
+  const int out_f = to_int(out64, "out"), batch = to_int(x.size(0), "batch"), seq = to_int(x.size(1), "seq"),
+            in_f = to_int(x.size(2), "in");
+  TORCH_CHECK(out_type == SPUTNIK_HIP_F32 || out_type == tile, "half_linear_rows: out_type is float32 or x's type");
+  TORCH_CHECK(static_cast<size_t>(image.numel()) >=
+                  sputnik_hip_sparse_linear_half_image_bytes(out_f, in_f, static_cast<int>(values_type), tile),
+              "half_linear_rows: the image was made for another shape");
+  const auto out_st = out_type == SPUTNIK_HIP_F32 ? at::kFloat : x.scalar_type();
+  Tensor y;
+  if (out_in.has_value()) {
+    y = *out_in;
+    TORCH_CHECK(y.dim() == 3 && y.size(0) == batch && y.size(1) == seq && y.size(2) == out_f && y.stride(2) == 1,
+                "half_linear_rows: out must be a [batch, seq, out] view with a unit last stride");
+    TORCH_CHECK(y.scalar_type() == out_st && y.device() == x.device(), "half_linear_rows: out has another type or device");
+  } else {
+    y = at::empty({batch, seq, out_f}, x.options().dtype(out_st));
+  }
+  const int st = sputnik_hip_sparse_linear_half_rows_forward(
+      out_f, in_f, seq, batch, image.data_ptr(), static_cast<int>(values_type), x.data_ptr(), x.stride(0),
+      x.stride(1), tile, y.data_ptr(), static_cast<int>(out_type), y.stride(0), y.stride(1), current_stream(x));
+  if (st == SPUTNIK_HIP_UNSUPPORTED) return at::empty({0}, x.options().dtype(out_st));
+  check_status(st, "half_linear_rows");
+  return y;
+}
+
 Tensor spmm_bias(int64_t m, int64_t k, const Tensor& values, const Tensor& row_indices,
                  const Tensor& row_offsets, const Tensor& column_indices, const Tensor& bias,
                  const Tensor& dense) {
@@ -1628,6 +1781,13 @@ TORCH_LIBRARY(torch_sputnik, m) {
       "sparse_attention_planned(Tensor query, Tensor key, Tensor value, Tensor row_indices, "
       "Tensor row_offsets, Tensor column_indices, float scale, Tensor plan) -> Tensor");
   m.def(
+      "sparse_attention_heads(Tensor query, Tensor key, Tensor value, Tensor row_indices, "
+      "Tensor row_offsets, Tensor column_indices, float scale, int out_type, bool want_lse, "
+      "Tensor? plan) -> Tensor[]");
+  m.def(
+      "half_linear_rows(int out_features, Tensor image, int values_type, Tensor x, Tensor? out, "
+      "int out_type) -> Tensor");
+  m.def(
       "spmm_many_mask(int b, int m, int k, Tensor nonzeros, Tensor values, Tensor row_indices, "
       "Tensor row_offsets, Tensor column_indices, Tensor dense_matrix) -> Tensor");
   m.def(
@@ -1702,6 +1862,8 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("sddmm_sum_group_planned", &sddmm_sum_group_planned);
   m.impl("sparse_attention_plan", &sparse_attention_plan);
   m.impl("sparse_attention_planned", &sparse_attention_planned);
+  m.impl("sparse_attention_heads", &sparse_attention_heads);
+  m.impl("half_linear_rows", &half_linear_rows);
   m.impl("spmm_many_mask", &spmm_many_mask);
   m.impl("sddmm_many_mask", &sddmm_many_mask);
   m.impl("sparse_softmax_many_mask", &sparse_softmax_many_mask);

@@ -760,6 +760,51 @@ class SparseSoftmax(torch.autograd.Function):
         return grad_values, None, None, None, None
 
 
+def _attention_backward(query, key, value, topo, scale, grad_output, needs):
+    """Gradients of softmax(scale * sddmm(q, k)) @ v for [R, S, D] operands (float32, or one
+    half type: the typed operators, float32 scores, weights and gradients): the scores and
+    weights are recomputed, then
+
+        dV = P^T dO          dP = sddmm(dO, v)
+        dS = softmax'(P, dP) (sparse_softmax_backward, carries the scale)
+        dQ = dS k            dK = dS^T q
+
+    on the mask and its transpose (one csr_transpose with permutation per call, or the
+    cached transposed topology).  `needs`: which of (dQ, dK, dV) to compute."""
+    row_indices, row_offsets, column_indices = topo
+    m, n = query.size(-2), key.size(-2)
+    grad_output = _contiguous(grad_output)
+    scores = _sddmm(m, n, *topo, query, key)
+    weights = ops.sparse_softmax_scaled(scores, *topo, scale)
+    grad_weights = _sddmm(m, n, *topo, grad_output, value)
+    grad_scores = ops.sparse_softmax_backward(weights, grad_weights, row_offsets, scale)
+    grad_query = grad_key = grad_value = None
+    if needs[0]:
+        grad_query = _spmm(m, n, grad_scores, *topo, key)
+    if needs[1] or needs[2]:
+        if _cache is not None:
+            row_indices_t, row_offsets_t, column_indices_t, perm = _cache.lookup(
+                m, n, row_offsets, column_indices, grad_scores)
+        else:
+            _, row_offsets_t, column_indices_t, perm = ops.csr_transpose_with_permutation(
+                m, n, grad_scores.reshape(-1, grad_scores.shape[-1])[0].contiguous(),
+                row_offsets, column_indices, checked=False)
+            row_indices_t = diffsort(row_offsets_t)
+        def transposed_product(values, dense):
+            if ops.spmm_permuted_fused(n, m, dense.size(-1), perm.numel()):
+                return ops.spmm_permuted(n, m, values, perm, row_indices_t, row_offsets_t,
+                                         column_indices_t, dense)
+            values_t = (_permute_cached(values, perm) if _cache is not None
+                        else ops.permute_last(values, perm))
+            return _spmm(n, m, values_t, row_indices_t, row_offsets_t, column_indices_t, dense)
+
+        if needs[1]:
+            grad_key = transposed_product(grad_scores, query)
+        if needs[2]:
+            grad_value = transposed_product(weights, grad_output)
+    return grad_query, grad_key, grad_value
+
+
 class SparseAttentionFunction(torch.autograd.Function):
     """softmax(scale * sddmm(q, k)) @ v with the ONE-kernel forward
     (ops.sparse_attention) and a backward built from the separate operators.
@@ -783,38 +828,139 @@ class SparseAttentionFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_output):
         query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors
-        topo = (row_indices, row_offsets, column_indices)
-        m, n = query.size(-2), key.size(-2)
-        grad_output = _contiguous(grad_output)
-        scores = _sddmm(m, n, *topo, query, key)
-        weights = ops.sparse_softmax_scaled(scores, *topo, ctx.scale)
-        grad_weights = _sddmm(m, n, *topo, grad_output, value)
-        grad_scores = ops.sparse_softmax_backward(weights, grad_weights, row_offsets, ctx.scale)
-        grad_query = grad_key = grad_value = None
-        if ctx.needs_input_grad[0]:
-            grad_query = _spmm(m, n, grad_scores, *topo, key)
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            if _cache is not None:
-                row_indices_t, row_offsets_t, column_indices_t, perm = _cache.lookup(
-                    m, n, row_offsets, column_indices, grad_scores)
-            else:
-                _, row_offsets_t, column_indices_t, perm = ops.csr_transpose_with_permutation(
-                    m, n, grad_scores.reshape(-1, grad_scores.shape[-1])[0].contiguous(),
-                    row_offsets, column_indices, checked=False)
-                row_indices_t = diffsort(row_offsets_t)
-            def transposed_product(values, dense):
-                if ops.spmm_permuted_fused(n, m, dense.size(-1), perm.numel()):
-                    return ops.spmm_permuted(n, m, values, perm, row_indices_t, row_offsets_t,
-                                             column_indices_t, dense)
-                values_t = (_permute_cached(values, perm) if _cache is not None
-                            else ops.permute_last(values, perm))
-                return _spmm(n, m, values_t, row_indices_t, row_offsets_t, column_indices_t, dense)
-
-            if ctx.needs_input_grad[1]:
-                grad_key = transposed_product(grad_scores, query)
-            if ctx.needs_input_grad[2]:
-                grad_value = transposed_product(weights, grad_output)
+        grad_query, grad_key, grad_value = _attention_backward(
+            query, key, value, (row_indices, row_offsets, column_indices), ctx.scale, grad_output,
+            ctx.needs_input_grad[:3])
         return grad_query, grad_key, grad_value, None, None, None, None
+
+
+# ---------------------------------------------------------------------------
+# Half storage through attention (SparseAttention(half_storage=True)): q, k, v and the
+# context stay [B, S, E] tensors in the input's half type, every head a strided view
+# (element (b, h, s, c) at b*S*E + h*D + s*E + c).  Values are rounded to the storage type
+# at the projection outputs, the context and the module output only; scores, weights and
+# every sum are float32.
+# ---------------------------------------------------------------------------
+def _rows_route(m, k, values, column_indices, x):
+    """Whether y = x W^T takes the row-orientation tile kernel (ops.half_linear_rows)."""
+    return (x.is_cuda and x.dim() == 3 and x.stride(2) == 1 and x.data_ptr() % 16 == 0
+            and x.stride(1) % 8 == 0 and x.stride(0) % 8 == 0
+            and ops.half_linear_rows_supported(m, k, x.size(1), x.size(0), column_indices.numel(),
+                                               values.dtype, x.dtype))
+
+
+class HalfRowLinearFunction(torch.autograd.Function):
+    """y [B, S, out] = x W^T in x's half type, on the matrix cores with no layout pass
+    (ops.half_linear_rows: the weight's image against x as it is).  ``apply(m, k, values,
+    row_indices, row_offsets, column_indices, x)``.  Backward: dy goes to [B, out, S] in one
+    layout pass, then the half layer's weight and input gradients (HalfSparseLinearFunction)
+    read it, the image and x."""
+
+    @staticmethod
+    def forward(ctx, m, k, values, row_indices, row_offsets, column_indices, x):
+        ctx.shape = (m, k)
+        ctx.topology = (row_indices, row_offsets, column_indices)
+        image = ops.half_linear_image(m, k, values, row_offsets, column_indices, x.dtype)
+        ctx.save_for_backward(values, x, image)
+        return ops.half_linear_rows(m, image, values.dtype, x)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        m, k = ctx.shape
+        _, row_offsets, column_indices = ctx.topology
+        values, x, image = ctx.saved_tensors
+        x = x.contiguous()
+        grad = ops.transpose_last2(_contiguous(grad_output).to(x.dtype))   # [B, out, S]
+        grad_values = grad_x = None
+        if ctx.needs_input_grad[2]:
+            plan = None if _plans is None else _plans.half_linear(m, k, row_offsets, column_indices)
+            grad_values = ops.half_linear_weight_gradient(m, row_offsets, column_indices, grad, False, x, plan)
+        if ctx.needs_input_grad[6]:
+            grad_x = ops.half_linear_input_gradient(m, k, grad, False, image, values.dtype, x, x.size(0),
+                                                    x.size(1))
+            if grad_x is None:
+                grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices, grad, left=True)
+                grad_x = ops.transpose_last2(grad_dense, x.dtype)
+        return None, None, grad_values, None, None, None, grad_x
+
+
+def half_linear_rows(m, k, values, row_indices, row_offsets, column_indices, x):
+    """Differentiable y [B, S, m] = x W^T for x [B, S, k] in float16 / bfloat16, stored in
+    x's type.  A shape the row-orientation kernel does not serve goes through the half
+    layer in column orientation (HalfSparseLinearFunction) and a narrowing layout pass."""
+    if _rows_route(m, k, values, column_indices, x):
+        if torch.is_grad_enabled() and (x.requires_grad or values.requires_grad):
+            return HalfRowLinearFunction.apply(m, k, values, row_indices, row_offsets, column_indices, x)
+        values = values.detach()
+        image = ops.half_linear_image(m, k, values, row_offsets, column_indices, x.dtype)
+        y = ops.half_linear_rows(m, image, values.dtype, x)
+        if y is not None:
+            return y
+    y = HalfSparseLinearFunction.apply(m, k, values, row_indices, row_offsets, column_indices, x)
+    return transpose_last2(y, x.dtype)
+
+
+def _heads(x, heads):
+    """[B, S, E] -> the [B, H, S, E/H] view of its heads (no copy)."""
+    return x.unflatten(-1, (heads, x.size(-1) // heads)).transpose(1, 2)
+
+
+def _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale):
+    q, k, v = _heads(query, heads), _heads(key, heads), _heads(value, heads)
+    plan = None if _plans is None else _plans.attention(q.size(-2), k.size(-2), q.size(-1), row_indices,
+                                                        row_offsets, column_indices)
+    out = ops.sparse_attention_heads(q, k, v, row_indices, row_offsets, column_indices, scale, plan=plan)
+    # (the kernel's buffer is [B, S, H, D]: this is a view)
+    return out.transpose(1, 2).reshape(query.size(0), query.size(1), -1)
+
+
+class SparseAttentionHeadsFunction(torch.autograd.Function):
+    """`sparse_attention_heads` under autograd: the fused forward on the head views, and
+    the recomputing backward of SparseAttentionFunction (`_attention_backward`) on
+    contiguous per-head copies in the storage type; the gradients come back as [B, S, E]
+    in the inputs' type.  (Unlike the reference's raw softmax call, the gradient reaches
+    q and k.)"""
+
+    @staticmethod
+    def forward(ctx, query, key, value, heads, row_indices, row_offsets, column_indices, scale):
+        ctx.heads, ctx.scale = int(heads), float(scale)
+        ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices)
+        return _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors
+        heads = ctx.heads
+
+        def per_head(x):   # [B, S, E] -> [B*H, S, D], contiguous, in the storage type
+            return _heads(x.to(query.dtype), heads).reshape(-1, x.size(1), x.size(2) // heads)
+
+        grads = _attention_backward(per_head(query), per_head(key), per_head(value),
+                                    (row_indices, row_offsets, column_indices), ctx.scale,
+                                    per_head(grad_output), ctx.needs_input_grad[:3])
+
+        def merged(g, like):   # [B*H, S, D] -> [B, S, E] in like's type
+            if g is None:
+                return None
+            return g.reshape(like.size(0), heads, like.size(1), -1).transpose(1, 2).reshape(
+                like.shape).to(like.dtype)
+
+        return (merged(grads[0], query), merged(grads[1], key), merged(grads[2], value),
+                None, None, None, None, None)
+
+
+def sparse_attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale):
+    """softmax(scale * q k^T at the mask) v per head for [B, S, E] tensors in float16 /
+    bfloat16 (query [B, m, E], key and value [B, n, E], any strides with a unit last one),
+    E = heads * D: head h is columns h*D .. h*D+D-1 of every row -- read as strided views by
+    the fused kernel (ops.sparse_attention_heads), no head split or merge pass.  Returns the
+    context [B, m, E] in the inputs' type (rounded once); scores, weights and sums are
+    float32.  Differentiable: the backward recomputes the weights (SparseAttentionHeadsFunction),
+    and the gradient reaches q, k and v."""
+    if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
+        return SparseAttentionHeadsFunction.apply(query, key, value, heads, row_indices, row_offsets,
+                                                  column_indices, scale)
+    return _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale)
 
 
 # ---------------------------------------------------------------------------

@@ -104,7 +104,8 @@ class SparseAttention(nn.Module):
 
     def __init__(self, num_heads, embedding_size, max_sequence_length=512, device=None,
                  sparsity=0.9, mask_generator=None, differentiable_softmax=False,
-                 fused_inference=True, low_memory_training=False, fused_training=None):
+                 fused_inference=True, low_memory_training=False, fused_training=None,
+                 half_storage=False):
         super().__init__()
         assert embedding_size % num_heads == 0, \
             "Model dimension must be divisible by the number of heads."
@@ -138,6 +139,9 @@ class SparseAttention(nn.Module):
         # measured at config 3, the event traffic costs more than the overlap gives
         # (forward 0.253 ms on one stream, 0.28-0.30 ms on three; fwd+bwd 1.04 / 1.11).
         self.parallel_projections = False
+        # float16 / bfloat16 inputs (all three of one type) stay in that type through the
+        # forward pass: see _forward_half_storage.  Off: today's widening path.
+        self.half_storage = bool(half_storage)
 
     @property
     def fused_training(self):   # the flag's name in rounds 1-3
@@ -210,6 +214,9 @@ class SparseAttention(nn.Module):
         i.e. 7 passes (5 when query, key and value are one tensor) instead of 11, each
         one tiled kernel.  (`parallel_projections` runs the three input projections on
         side streams; measured slower at config 3, off by default.)"""
+        if self.half_storage and query.dtype in (torch.float16, torch.bfloat16) and \
+                key.dtype == query.dtype and value.dtype == query.dtype and query.dim() == 3:
+            return self._forward_half_storage(query, key, value)
         batch_size, seq = query.size(0), query.size(1)
         heads, dim = self.num_heads, self.head_dim
         inputs = (query, key, value)
@@ -251,6 +258,31 @@ class SparseAttention(nn.Module):
         # per-head shape so that its gradient can come back in the layout the
         # attention's backward wants, without a pass of its own)
         return self.linears[-1].project(context, dense_blocks=dim).transpose(1, 2)
+
+    def _forward_half_storage(self, query, key, value):
+        """``half_storage=True`` with float16 / bfloat16 inputs of one type: [B, S, E] in,
+        [B, S, E] out in that type, and every tensor the pass writes -- q, k, v, the context,
+        the output -- stored in it.  No head split or merge and no widening pass: the
+        projections are row-orientation tile products (functional.half_linear_rows), the
+        attention one fused launch on the heads' strided views
+        (functional.sparse_attention_heads).  Values are rounded to the storage type at the
+        projection outputs, the context and the output; scores, weights and every sum are
+        float32.  Under autograd the attention's backward recomputes the weights (as with
+        ``low_memory_training``), so the gradient goes through the softmax to q and k;
+        gradients come back in the type of what they differentiate (float32 `values` get
+        float32 gradients, half inputs half ones).  ``fused_inference``,
+        ``low_memory_training``, ``differentiable_softmax`` and ``parallel_projections`` do
+        not apply in this mode.  Shapes the kernels do not serve (head dimension other than
+        64, sizes off the tiles) are composed from the typed operators."""
+        def project(net, x):
+            return functional.half_linear_rows(net.output_features, net.input_features, net.values,
+                                               net.row_indices, net.row_offsets, net.column_indices, x)
+
+        q, k, v = (project(net, x) for net, x in zip(self.linears, (query, key, value)))
+        context = functional.sparse_attention_heads(q, k, v, self.num_heads, self.row_indices,
+                                                    self.row_offsets, self.column_indices,
+                                                    1.0 / math.sqrt(self.head_dim))
+        return project(self.linears[-1], context)
 
     @staticmethod
     def _project_group(nets, dense, split_rows):

@@ -379,6 +379,45 @@ def sparse_attention_planned(query, key, value, row_indices, row_offsets, column
                                          column_indices, float(scale), plan)
 
 
+def sparse_attention_heads(query, key, value, row_indices, row_offsets, column_indices, scale,
+                           out_dtype=None, with_lse=False, plan=None):
+    """The fused attention on float16 / bfloat16 storage, operands as strided head views:
+    [B, H, rows, 64] (e.g. ``x.unflatten(-1, (H, 64)).transpose(1, 2)`` of a [B, S, E]
+    tensor -- no copy), [R, rows, 64] or [rows, 64].  Scores, weights and sums are float32;
+    the result is stored as `out_dtype` (float32, or the operands' type by default) in a
+    buffer laid out [B, rows, H, 64] for 4-D operands (the returned [B, H, rows, 64] view
+    of it is a [B, S, E] context).  A call the kernel does not serve (head dimension other
+    than 64, views not 16-byte aligned) is composed from the typed operators; ``with_lse``
+    ([out, lse], lse float32 [.., rows]) needs a served call."""
+    out_code = _half_code(query.dtype if out_dtype is None else out_dtype)
+    outs = _ops.sparse_attention_heads(query, key, value, row_indices, row_offsets, column_indices,
+                                       float(scale), out_code, bool(with_lse), plan)
+    return outs if with_lse else outs[0]
+
+
+def half_linear_rows_supported(out_features, in_features, seq, batch, nonzeros, values_dtype, tile_dtype):
+    """Whether y [B, S, out] = x W^T (half_linear_rows) takes the matrix-core route."""
+    from . import capi
+    try:
+        vt, tt = _half_code(values_dtype), _half_code(tile_dtype)
+    except KeyError:
+        return False
+    if tt == 0:
+        return False
+    return bool(capi.lib().sputnik_hip_sparse_linear_half_rows_supported(
+        int(out_features), int(in_features), int(seq), int(batch), int(nonzeros), vt, tt))
+
+
+def half_linear_rows(out_features, image, values_dtype, x, out=None, out_dtype=None):
+    """y [B, S, out] = x W^T from W's image (half_linear_image) and x [B, S, in] half, in row
+    orientation (no layout pass), stored as `out_dtype` (x's type by default, or float32) --
+    into `out` when given (a [B, S, out] view with a unit last stride, e.g. a column slice
+    of a wider buffer).  None where the route does not serve the call (unaligned x)."""
+    code = _half_code(x.dtype if out_dtype is None else out_dtype)
+    y = _ops.half_linear_rows(int(out_features), image, _half_code(values_dtype), x, out, code)
+    return None if y.numel() == 0 else y
+
+
 _TYPE_CODES = None
 
 
