@@ -773,6 +773,83 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_forward_planned(int m, in
                              int64_t lse_stride, const void* workspace, size_t workspace_bytes,
                              sputnik_hip_stream_t stream);
 
+/*
+ * The fused attention with one mask per batch element (the "many mask" layout below:
+ * row_indices [masks * m], row_offsets [masks * (m + 1)] each starting at 0,
+ * column_indices concatenated, `nonzeros` [masks] a HOST array).  `replicas` is a
+ * multiple of `masks`; replica r uses mask r / (replicas / masks).  q [m,d], k and v
+ * [n,d] per replica as in sputnik_hip_sparse_attention_forward; `lse` may be NULL.
+ * All masks are served by one pre-pass launch and one attention launch, the heads of
+ * the densest masks started first; nothing waits for the host, so the planned form can
+ * be captured in a graph.  A mask without entries gives its replicas zeros (and
+ * lse = -inf), as do rows without entries; rows whose columns do not ascend are served
+ * in any order.
+ * Returns SPUTNIK_HIP_UNSUPPORTED for what the kernel does not serve (d != 64, operands
+ * or strides not 16-byte aligned, n * d * 4 bytes of 2^32 or more; the single-mask rules
+ * applied to the largest mask; more than 65535 replicas, which one launch cannot hold) and
+ * SPUTNIK_HIP_INVALID_ARGUMENT when replicas % masks != 0
+ * or the workspace is smaller than
+ * sputnik_hip_sparse_attention_many_mask_workspace_bytes(masks, m, n, d, max(nonzeros))
+ * (0: not served).  `plan` runs the topology-only pre-pass into the workspace for
+ * `forward_planned`; the plan is valid for both forms below while the topology tensors,
+ * masks, m, n and max(nonzeros) do not change.
+ */
+SPUTNIK_HIP_API size_t sputnik_hip_sparse_attention_many_mask_workspace_bytes(int masks, int m, int n,
+                             int d, int largest_nonzeros);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_many_mask_plan(int masks, int m, int n, int d,
+                             const int* nonzeros, const int* row_indices, const int* row_offsets,
+                             const int* column_indices, void* workspace, size_t workspace_bytes,
+                             sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_many_mask_forward(int masks, int m, int n, int d,
+                             const int* nonzeros, int replicas, const int* row_indices,
+                             const int* row_offsets, const int* column_indices, const float* q,
+                             int64_t q_stride, const float* k, int64_t k_stride, const float* v,
+                             int64_t v_stride, float scale, float* out, int64_t out_stride,
+                             float* lse, int64_t lse_stride, void* workspace,
+                             size_t workspace_bytes, sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_many_mask_forward_planned(int masks, int m, int n,
+                             int d, const int* nonzeros, int replicas, const int* row_indices,
+                             const int* row_offsets, const int* column_indices, const float* q,
+                             int64_t q_stride, const float* k, int64_t k_stride, const float* v,
+                             int64_t v_stride, float scale, float* out, int64_t out_stride,
+                             float* lse, int64_t lse_stride, const void* workspace,
+                             size_t workspace_bytes, sputnik_hip_stream_t stream);
+
+/*
+ * The same on float16 / bfloat16 head views (sputnik_hip_sparse_attention_heads_forward:
+ * strides in elements, out_type SPUTNIK_HIP_F32 or `dtype`): batch element b uses mask b,
+ * so `batch` must equal `masks` (else SPUTNIK_HIP_INVALID_ARGUMENT).  Served when
+ * sputnik_hip_sparse_attention_heads_supported serves the views for the largest mask;
+ * workspace and plan as above.
+ */
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_many_mask_forward(int masks, int m, int n,
+                             int d, const int* nonzeros, int batch, int heads,
+                             const int* row_indices, const int* row_offsets,
+                             const int* column_indices, int dtype, const void* q,
+                             int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                             const void* k, int64_t k_batch_stride, int64_t k_head_stride,
+                             int64_t k_row_stride, const void* v, int64_t v_batch_stride,
+                             int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+                             int out_type, int64_t out_batch_stride, int64_t out_head_stride,
+                             int64_t out_row_stride, float* lse, int64_t lse_stride,
+                             void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_many_mask_forward_planned(int masks, int m,
+                             int n, int d, const int* nonzeros, int batch, int heads,
+                             const int* row_indices, const int* row_offsets,
+                             const int* column_indices, int dtype, const void* q,
+                             int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                             const void* k, int64_t k_batch_stride, int64_t k_head_stride,
+                             int64_t k_row_stride, const void* v, int64_t v_batch_stride,
+                             int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+                             int out_type, int64_t out_batch_stride, int64_t out_head_stride,
+                             int64_t out_row_stride, float* lse, int64_t lse_stride,
+                             const void* workspace, size_t workspace_bytes,
+                             sputnik_hip_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * "many mask" family: `masks` topologies of the same m x n shape, laid out
  * as tests/transformer/utils.py:17-38 builds them:

@@ -20,8 +20,8 @@ from .ops import (  # noqa: F401
     sparse_softmax,
     spmm,
 )
-from .topology import dense_to_sparse, diffsort, generate_mask  # noqa: F401
+from .topology import dense_to_sparse, dense_to_sparse_3d, diffsort, generate_mask  # noqa: F401
 from .functional import Sddmm, SparseLinearFunction, SparseSoftmax, Spmm  # noqa: F401
-from .modules import SparseAttention, SparseLinear  # noqa: F401
+from .modules import SparseAttention, SparseCoreAttention, SparseLinear  # noqa: F401
 
 __version__ = "0.3.0"

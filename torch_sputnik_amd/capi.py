@@ -153,6 +153,20 @@ SIGNATURES = {
     "sputnik_hip_sparse_attention_heads_forward_planned": (_c_int, [_c_int] * 6 + [_c_ptr] * 3 + [_c_int] + [
         _c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [_c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64,
                                                _c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_many_mask_workspace_bytes": (_c_size, [_c_int] * 5),
+    "sputnik_hip_sparse_attention_many_mask_plan": (_c_int, [_c_int] * 4 + [_c_ptr] * 5 + [_c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_many_mask_forward": (_c_int, [_c_int] * 4 + [_c_ptr, _c_int] + [
+        _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_float, _c_ptr,
+        _c_i64, _c_ptr, _c_i64, _c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_many_mask_forward_planned": (_c_int, [_c_int] * 4 + [_c_ptr, _c_int] + [
+        _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_float, _c_ptr,
+        _c_i64, _c_ptr, _c_i64, _c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_heads_many_mask_forward": (_c_int, [_c_int] * 4 + [_c_ptr, _c_int, _c_int] + [
+        _c_ptr] * 3 + [_c_int] + [_c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [
+        _c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_heads_many_mask_forward_planned": (_c_int, [_c_int] * 4 + [
+        _c_ptr, _c_int, _c_int] + [_c_ptr] * 3 + [_c_int] + [_c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [
+        _c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_size, _c_ptr]),
     "sputnik_hip_spmm_many_mask": (_c_int, [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr, _c_ptr, _c_i64,
                                                           _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr,
                                                           _c_i64, _c_ptr, _c_size, _c_ptr]),
@@ -621,6 +635,48 @@ def sparse_attention_heads_forward(m, n, d, row_indices, row_offsets, column_ind
               _ptr(workspace), _ws_bytes(workspace), _stream(out)),
            "sputnik_hip_sparse_attention_heads_forward")
     return out
+
+
+# ---- the fused attention with one mask per batch element: these return the library's status
+# (0, SPUTNIK_HIP_UNSUPPORTED = -2, SPUTNIK_HIP_INVALID_ARGUMENT) instead of raising ----
+def sparse_attention_many_mask_workspace_bytes(masks, m, n, d, largest_nonzeros):
+    return lib().sputnik_hip_sparse_attention_many_mask_workspace_bytes(masks, m, n, d, largest_nonzeros)
+
+
+def sparse_attention_many_mask_plan(masks, m, n, d, nonzeros, row_indices, row_offsets, column_indices,
+                                    workspace):
+    arr, _ = _host_counts(nonzeros)
+    return lib().sputnik_hip_sparse_attention_many_mask_plan(
+        masks, m, n, d, arr, _ptr(row_indices), _ptr(row_offsets), _ptr(column_indices), _ptr(workspace),
+        _ws_bytes(workspace), _stream(row_offsets))
+
+
+def sparse_attention_many_mask_forward(masks, m, n, d, nonzeros, replicas, row_indices, row_offsets,
+                                       column_indices, q, k, v, scale, out, lse=None, workspace=None,
+                                       planned=False):
+    """q [R,m,d], k and v [R,n,d] float32 (contiguous), replica r under mask r // (R // masks);
+    lse [R, m] or None.  `planned`: the workspace holds the plan of
+    sparse_attention_many_mask_plan."""
+    arr, _ = _host_counts(nonzeros)
+    fn = (lib().sputnik_hip_sparse_attention_many_mask_forward_planned if planned
+          else lib().sputnik_hip_sparse_attention_many_mask_forward)
+    return fn(masks, m, n, d, arr, replicas, _ptr(row_indices), _ptr(row_offsets), _ptr(column_indices),
+              _ptr(q), m * d, _ptr(k), n * d, _ptr(v), n * d, float(scale), _ptr(out), m * d, _ptr(lse), m,
+              _ptr(workspace), _ws_bytes(workspace), _stream(out))
+
+
+def sparse_attention_heads_many_mask_forward(masks, m, n, d, nonzeros, row_indices, row_offsets,
+                                             column_indices, q, k, v, scale, out, lse=None,
+                                             workspace=None, planned=False):
+    """Half head views q [B,H,m,d], k and v [B,H,n,d], batch element b under mask b, into the view
+    `out` (float32 or the operands' type); lse [B*H, m] float32 or None."""
+    arr, _ = _host_counts(nonzeros)
+    fn = (lib().sputnik_hip_sparse_attention_heads_many_mask_forward_planned if planned
+          else lib().sputnik_hip_sparse_attention_heads_many_mask_forward)
+    return fn(masks, m, n, d, arr, q.size(0), q.size(1), _ptr(row_indices), _ptr(row_offsets),
+              _ptr(column_indices), TYPE_CODES[q.dtype], *_head_view(q), *_head_view(k), *_head_view(v),
+              float(scale), _ptr(out), TYPE_CODES[out.dtype], *_head_view(out)[1:], _ptr(lse), m,
+              _ptr(workspace), _ws_bytes(workspace), _stream(out))
 
 
 def sparse_linear_half_rows_forward(out_features, image, values_dtype, x, y):

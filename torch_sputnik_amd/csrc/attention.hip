@@ -101,6 +101,50 @@ __device__ __forceinline__ void rescale(R& r, float m_new) {
   r.mx = m_new;
 }
 
+// "Many mask" launches (MANY = true; common.h, select_mask): one topology per batch element,
+// shared by its `heads` replicas, every mask and replica in ONE launch.  The plan holds one
+// region per mask (row_ok, chunk table: spmm_chunk_table_masks_kernel) and the masks' start
+// order (mask_start_word).  The replicas are dealt over the XCDs whole (their row blocks
+// share K and V: one L2), several masks to each XCD (xcd_spread_replicas_index), and the
+// heads of the densest masks start first: their workgroups take several times the mean,
+// and started last they would run on alone.  MANY = false is the single-mask code as it was.
+__host__ __device__ __forceinline__ int64_t mask_plan_ints(int slots, int nchunks) {
+  // one mask's region: row_ok (row_ok_bytes), the chunk table, the spare start-order word;
+  // in 256-byte steps
+  const int64_t ints = (slots + 63) / 64 * 64 + static_cast<int64_t>(nchunks + 1) * slots + 1;
+  return (ints + 63) / 64 * 64;
+}
+
+struct WorkItem {
+  int mblock, replica;
+};
+// Grid work -> (row block, replica) of a many-mask launch, and the replica's topology and
+// plan; `nonzeros` becomes the mask's entry count.
+__device__ __forceinline__ WorkItem many_mask_work(int heads, int m, int slots, int nchunks,
+                                                   int& nonzeros,
+                                                   const int* __restrict__& row_indices,
+                                                   const int* __restrict__& row_offsets,
+                                                   const int* __restrict__& column_indices,
+                                                   const int* __restrict__& table,
+                                                   const int* __restrict__& row_ok) {
+  const int64_t plan_ints = mask_plan_ints(slots, nchunks);
+  const unsigned long long work = xcd_spread_replicas_index(gridDim.x, gridDim.y);
+  const int mblock = static_cast<int>(work % gridDim.x);
+  int replica = static_cast<int>(work / gridDim.x);
+  replica = row_ok[mask_start_word(replica / heads, plan_ints)] * heads + replica % heads;
+  const MaskPlace place = select_mask(heads, replica, m, 0, row_offsets);
+  row_offsets += static_cast<int64_t>(place.mask) * (m + 1);
+  row_indices += static_cast<int64_t>(place.mask) * m;
+  column_indices += place.first;
+  table += place.mask * plan_ints;
+  row_ok += place.mask * plan_ints;
+  nonzeros = place.nonzeros;
+  return WorkItem{mblock, replica};
+}
+
+// MANY: `nonzeros` is the number of replicas per mask (each mask's own count is read from
+// its row_offsets), q, k, v, out and lse start at replica 0 and the grid holds every replica.
+template <bool MANY>
 __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
     int m, int n, int nonzeros, int slots, int nchunks, const int* __restrict__ row_indices,
     const int* __restrict__ row_offsets, const int* __restrict__ column_indices,
@@ -116,9 +160,17 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
   const int qd = i >> 2, tq = i & 3;   // quad of the row group, lane of the quad
   const int e16 = 4 * tq + qd;         // this lane's entry of a 16-entry window
   // (the row blocks of a replica read the same K and V: one XCD, see xcd_local_index)
-  const unsigned long long work = xcd_local_index();
-  const int mblock = static_cast<int>(work % gridDim.x);
-  const int replica = static_cast<int>(work / gridDim.x);
+  WorkItem item;
+  if constexpr (MANY) {
+    const int heads = nonzeros;
+    item = many_mask_work(heads, m, slots, nchunks, nonzeros, row_indices, row_offsets,
+                          column_indices, table, row_ok);
+  } else {
+    const unsigned long long work = xcd_local_index();
+    item = WorkItem{static_cast<int>(work % gridDim.x), static_cast<int>(work / gridDim.x)};
+  }
+  const int mblock = item.mblock;
+  const int replica = item.replica;
   q += replica * q_stride;
   k += replica * k_stride;
   v += replica * v_stride;
@@ -158,6 +210,13 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
         lse[my_row[t]] = st[t].l > 0.f ? st[t].mx + __logf(st[t].l) : -INFINITY;
     }
   };
+
+  if constexpr (MANY) {
+    if (nonzeros == 0) {   // a mask without entries (none of its column_indices is read)
+      finish();
+      return;
+    }
+  }
 
   // Row blocks whose columns do not ascend inside rows: order-independent path,
   // one entry at a time, K and V rows gathered from global memory.
@@ -403,7 +462,9 @@ struct RowAccH {
   float mx, l;
 };
 
-template <typename T, typename TO>
+// MANY: batch element b uses mask b (`nonzeros` and `replica0` are not used: each mask's
+// count is read from its row_offsets, and the grid holds every replica).
+template <typename T, typename TO, bool MANY>
 __global__ __launch_bounds__(kThreads) void sparse_attention_heads_kernel(
     int m, int n, int nonzeros, int slots, int nchunks, int heads, int replica0,
     const int* __restrict__ row_indices, const int* __restrict__ row_offsets,
@@ -417,9 +478,16 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_heads_kernel(
   const int g = lane >> 4, i = lane & 15;
   const int qd = i >> 2, tq = i & 3;
   const int e16 = 4 * tq + qd;
-  const unsigned long long work = xcd_local_index();
-  const int mblock = static_cast<int>(work % gridDim.x);
-  const int replica = replica0 + static_cast<int>(work / gridDim.x);
+  WorkItem item;
+  if constexpr (MANY) {
+    item = many_mask_work(heads, m, slots, nchunks, nonzeros, row_indices, row_offsets,
+                          column_indices, table, row_ok);
+  } else {
+    const unsigned long long work = xcd_local_index();
+    item = WorkItem{static_cast<int>(work % gridDim.x), replica0 + static_cast<int>(work / gridDim.x)};
+  }
+  const int mblock = item.mblock;
+  const int replica = item.replica;
   const int64_t b = replica / heads, h = replica - b * heads;
   const T* __restrict__ q = static_cast<const T*>(qv.base) + (b * qv.batch + h * qv.head);
   const T* __restrict__ k = static_cast<const T*>(kv.base) + (b * kv.batch + h * kv.head);
@@ -466,6 +534,13 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_heads_kernel(
         lse[my_row[t]] = st[t].l > 0.f ? st[t].mx + __logf(st[t].l) : -INFINITY;
     }
   };
+
+  if constexpr (MANY) {
+    if (nonzeros == 0) {   // a mask without entries (none of its column_indices is read)
+      finish();
+      return;
+    }
+  }
 
   // Row blocks whose columns do not ascend inside rows: order-independent path,
   // one entry at a time, K and V rows gathered from global memory.
@@ -693,7 +768,7 @@ int attention_exec(int m, int n, int d, int nonzeros, int replicas, const int* r
   }
   for (int r0 = 0; r0 < replicas; r0 += kMaxGridYZ) {
     const int ry = min(replicas - r0, kMaxGridYZ);
-    hipLaunchKernelGGL(sparse_attention_kernel, dim3(slots / kBM, ry), dim3(kThreads), 0, stream,
+    hipLaunchKernelGGL(sparse_attention_kernel<false>, dim3(slots / kBM, ry), dim3(kThreads), 0, stream,
                        m, n, nonzeros, slots, nchunks, row_indices, row_offsets, column_indices,
                        table, row_ok, q + r0 * q_stride, q_stride, k + r0 * k_stride, k_stride,
                        v + r0 * v_stride, v_stride, scale, out + r0 * out_stride, out_stride,
@@ -759,7 +834,7 @@ void launch_heads(dim3 grid, hipStream_t stream, int m, int n, int nonzeros, int
                   const int* column_indices, const int* table, const int* row_ok, const HeadView& q,
                   const HeadView& k, const HeadView& v, float scale, const HeadView& o, float* lse,
                   int64_t lse_stride) {
-  hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO>), grid, dim3(kThreads), 0, stream, m, n,
+  hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, false>), grid, dim3(kThreads), 0, stream, m, n,
                      nonzeros, slots, nchunks, heads, replica0, row_indices, row_offsets,
                      column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride);
 }
@@ -860,6 +935,215 @@ int sputnik_hip_sparse_attention_heads_forward_planned(
                     HeadView{out, out_batch_stride, out_head_stride, out_row_stride}, out_type, lse,
                     lse_stride, const_cast<void*>(workspace), workspace_bytes, /*planned=*/true,
                     stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// Many masks (sputnik_hip.h, "many mask" family): one topology per batch element, all of
+// them served by ONE pre-pass launch and ONE attention launch.
+// ---------------------------------------------------------------------------
+namespace {
+
+// Bytes of one mask's plan region (mask_plan_ints).
+size_t mask_plan_bytes(int m, int n) {
+  return sizeof(int) * static_cast<size_t>(mask_plan_ints(slots_of(m), chunks_of(n)));
+}
+
+// Checks every many-mask entry point shares.  *largest = the largest entry count (the
+// kernels serve the launch when they serve it for the densest mask).
+int many_mask_args(int masks, int m, int n, int d, const int* nonzeros, int replicas, int* largest) {
+  if (masks <= 0 || m < 0 || n < 0 || d < 0 || replicas < 0 || nonzeros == nullptr)
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (replicas % masks != 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  *largest = 0;
+  for (int i = 0; i < masks; ++i) {
+    if (nonzeros[i] < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+    *largest = max(*largest, nonzeros[i]);
+  }
+  return 0;
+}
+
+// One launch holds every replica (grid y; the masks' start order covers the whole batch).
+// A launch with no entry at all is served too: every mask gives zeros.
+bool many_mask_supported(int masks, int m, int n, int d, int largest, int replicas) {
+  return masks <= kMaxGridYZ && replicas <= kMaxGridYZ && supported(m, n, d, max(largest, 1));
+}
+
+size_t many_mask_workspace(int masks, int m, int n, int d, int largest) {
+  if (masks <= 0 || !many_mask_supported(masks, m, n, d, largest, masks)) return 0;
+  return static_cast<size_t>(masks) * mask_plan_bytes(m, n);
+}
+
+int many_mask_plan_exec(int masks, int m, int n, const int* row_indices, const int* row_offsets,
+                        const int* column_indices, void* workspace, hipStream_t stream) {
+  const int slots = slots_of(m);
+  int* row_ok = static_cast<int*>(workspace);
+  int* table = reinterpret_cast<int*>(static_cast<char*>(workspace) + row_ok_bytes(slots));
+  hipLaunchKernelGGL((spmm_chunk_table_masks_kernel<kBK>), dim3(ceil_div(slots, 4), masks), dim3(256),
+                     0, stream, m, n, slots, kBM, chunks_of(n), row_indices, row_offsets,
+                     column_indices, table, row_ok,
+                     static_cast<int64_t>(mask_plan_bytes(m, n) / sizeof(int)));
+  return launch_status();
+}
+
+int attention_many_mask_exec(int masks, int m, int n, int d, const int* nonzeros, int replicas,
+                             const int* row_indices, const int* row_offsets,
+                             const int* column_indices, const float* q, int64_t q_stride,
+                             const float* k, int64_t k_stride, const float* v, int64_t v_stride,
+                             float scale, float* out, int64_t out_stride, float* lse,
+                             int64_t lse_stride, void* workspace, size_t workspace_bytes,
+                             bool planned, hipStream_t stream) {
+  int largest = 0;
+  int st = many_mask_args(masks, m, n, d, nonzeros, replicas, &largest);
+  if (st != 0) return st;
+  if (m == 0 || replicas == 0) return 0;
+  if (!many_mask_supported(masks, m, n, d, largest, replicas) || !aligned_to(q, 16) || !aligned_to(k, 16) ||
+      !aligned_to(v, 16) || !aligned_to(out, 16) || q_stride % 4 != 0 || k_stride % 4 != 0 ||
+      v_stride % 4 != 0 || out_stride % 4 != 0)
+    return SPUTNIK_HIP_UNSUPPORTED;
+  if (workspace == nullptr || !aligned_to(workspace, 16) ||
+      workspace_bytes < many_mask_workspace(masks, m, n, d, largest))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (!planned) {
+    st = many_mask_plan_exec(masks, m, n, row_indices, row_offsets, column_indices, workspace, stream);
+    if (st != 0) return st;
+  }
+  const int slots = slots_of(m), nchunks = chunks_of(n);
+  const int* row_ok = static_cast<const int*>(workspace);
+  const int* table = reinterpret_cast<const int*>(static_cast<const char*>(workspace) + row_ok_bytes(slots));
+  hipLaunchKernelGGL(sparse_attention_kernel<true>, dim3(slots / kBM, replicas), dim3(kThreads), 0,
+                     stream, m, n, replicas / masks, slots, nchunks, row_indices, row_offsets,
+                     column_indices, table, row_ok, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                     out_stride, lse, lse_stride);
+  return launch_status();
+}
+
+int heads_many_mask_exec(int masks, int m, int n, int d, const int* nonzeros, int batch, int heads,
+                         const int* row_indices, const int* row_offsets, const int* column_indices,
+                         int dtype, const HeadView& q, const HeadView& k, const HeadView& v,
+                         float scale, const HeadView& o, int out_type, float* lse,
+                         int64_t lse_stride, void* workspace, size_t workspace_bytes, bool planned,
+                         hipStream_t stream) {
+  if (batch < 0 || heads < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (static_cast<int64_t>(batch) * heads >= (int64_t{1} << 31)) return SPUTNIK_HIP_UNSUPPORTED;
+  if (batch != masks) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  int largest = 0;
+  int st = many_mask_args(masks, m, n, d, nonzeros, batch * heads, &largest);
+  if (st != 0) return st;
+  if (m == 0 || heads == 0) return 0;
+  if (!many_mask_supported(masks, m, n, d, largest, batch * heads) ||
+      !heads_served(m, n, d, max(largest, 1), batch, heads, dtype, out_type, q, k, v, o))
+    return SPUTNIK_HIP_UNSUPPORTED;
+  if (workspace == nullptr || !aligned_to(workspace, 16) ||
+      workspace_bytes < many_mask_workspace(masks, m, n, d, largest))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (!planned) {
+    st = many_mask_plan_exec(masks, m, n, row_indices, row_offsets, column_indices, workspace, stream);
+    if (st != 0) return st;
+  }
+  const int slots = slots_of(m), nchunks = chunks_of(n);
+  const int* row_ok = static_cast<const int*>(workspace);
+  const int* table = reinterpret_cast<const int*>(static_cast<const char*>(workspace) + row_ok_bytes(slots));
+  const dim3 grid(slots / kBM, batch * heads);
+#define SPUTNIK_HIP_HEADS_MM(T, TO)                                                                 \
+  hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, true>), grid, dim3(kThreads), 0, stream, \
+                     m, n, 0, slots, nchunks, heads, 0, row_indices, row_offsets, column_indices,   \
+                     table, row_ok, q, k, v, scale, o, lse, lse_stride)
+  if (dtype == SPUTNIK_HIP_F16 && out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS_MM(_Float16, float);
+  else if (dtype == SPUTNIK_HIP_F16) SPUTNIK_HIP_HEADS_MM(_Float16, _Float16);
+  else if (out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS_MM(__bf16, float);
+  else SPUTNIK_HIP_HEADS_MM(__bf16, __bf16);
+#undef SPUTNIK_HIP_HEADS_MM
+  return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sputnik_hip_sparse_attention_many_mask_workspace_bytes(int masks, int m, int n, int d,
+                                                              int largest_nonzeros) {
+  if (m < 0 || n < 0 || d < 0 || largest_nonzeros < 0) return 0;
+  return many_mask_workspace(masks, m, n, d, largest_nonzeros);
+}
+
+int sputnik_hip_sparse_attention_many_mask_plan(int masks, int m, int n, int d, const int* nonzeros,
+                                                const int* row_indices, const int* row_offsets,
+                                                const int* column_indices, void* workspace,
+                                                size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  int largest = 0;
+  const int st = many_mask_args(masks, m, n, d, nonzeros, masks, &largest);
+  if (st != 0) return st;
+  if (!many_mask_supported(masks, m, n, d, largest, masks)) return SPUTNIK_HIP_UNSUPPORTED;
+  if (workspace == nullptr || !aligned_to(workspace, 16) ||
+      workspace_bytes < many_mask_workspace(masks, m, n, d, largest))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (m == 0) return 0;
+  return many_mask_plan_exec(masks, m, n, row_indices, row_offsets, column_indices, workspace,
+                             static_cast<hipStream_t>(stream));
+}
+
+int sputnik_hip_sparse_attention_many_mask_forward(
+    int masks, int m, int n, int d, const int* nonzeros, int replicas, const int* row_indices,
+    const int* row_offsets, const int* column_indices, const float* q, int64_t q_stride,
+    const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
+    int64_t out_stride, float* lse, int64_t lse_stride, void* workspace, size_t workspace_bytes,
+    sputnik_hip_stream_t stream) {
+  return attention_many_mask_exec(masks, m, n, d, nonzeros, replicas, row_indices, row_offsets,
+                                  column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                                  out_stride, lse, lse_stride, workspace, workspace_bytes,
+                                  /*planned=*/false, static_cast<hipStream_t>(stream));
+}
+
+int sputnik_hip_sparse_attention_many_mask_forward_planned(
+    int masks, int m, int n, int d, const int* nonzeros, int replicas, const int* row_indices,
+    const int* row_offsets, const int* column_indices, const float* q, int64_t q_stride,
+    const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
+    int64_t out_stride, float* lse, int64_t lse_stride, const void* workspace,
+    size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  return attention_many_mask_exec(masks, m, n, d, nonzeros, replicas, row_indices, row_offsets,
+                                  column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                                  out_stride, lse, lse_stride, const_cast<void*>(workspace),
+                                  workspace_bytes, /*planned=*/true, static_cast<hipStream_t>(stream));
+}
+
+int sputnik_hip_sparse_attention_heads_many_mask_forward(
+    int masks, int m, int n, int d, const int* nonzeros, int batch, int heads,
+    const int* row_indices, const int* row_offsets, const int* column_indices, int dtype,
+    const void* q, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+    const void* k, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride,
+    const void* v, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride,
+    float scale, void* out, int out_type, int64_t out_batch_stride, int64_t out_head_stride,
+    int64_t out_row_stride, float* lse, int64_t lse_stride, void* workspace,
+    size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  return heads_many_mask_exec(masks, m, n, d, nonzeros, batch, heads, row_indices, row_offsets,
+                              column_indices, dtype,
+                              HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
+                              HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
+                              HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
+                              HeadView{out, out_batch_stride, out_head_stride, out_row_stride},
+                              out_type, lse, lse_stride, workspace, workspace_bytes,
+                              /*planned=*/false, static_cast<hipStream_t>(stream));
+}
+
+int sputnik_hip_sparse_attention_heads_many_mask_forward_planned(
+    int masks, int m, int n, int d, const int* nonzeros, int batch, int heads,
+    const int* row_indices, const int* row_offsets, const int* column_indices, int dtype,
+    const void* q, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+    const void* k, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride,
+    const void* v, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride,
+    float scale, void* out, int out_type, int64_t out_batch_stride, int64_t out_head_stride,
+    int64_t out_row_stride, float* lse, int64_t lse_stride, const void* workspace,
+    size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  return heads_many_mask_exec(masks, m, n, d, nonzeros, batch, heads, row_indices, row_offsets,
+                              column_indices, dtype,
+                              HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
+                              HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
+                              HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
+                              HeadView{out, out_batch_stride, out_head_stride, out_row_stride},
+                              out_type, lse, lse_stride, const_cast<void*>(workspace),
+                              workspace_bytes, /*planned=*/true, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -1607,6 +1607,183 @@ std::vector<Tensor> csr_transpose_many_mask(int64_t b, int64_t m64, int64_t n64,
   return {out_values, out_row_offsets, out_column_indices};
 }
 
+// ---- the fused attention with one mask per batch element (sputnik_hip.h:
+// sparse_attention_many_mask_*, sparse_attention_heads_many_mask_*) ----
+
+// softmax(scale * sddmm) @ v from the separate many-mask operators (float32, [R, S, D]):
+// what the fused kernels do not serve.
+Tensor attention_many_mask_composed(int64_t b, const Tensor& nonzeros, const Tensor& q,
+                                    const Tensor& k, const Tensor& v, const Tensor& row_indices,
+                                    const Tensor& row_offsets, const Tensor& column_indices,
+                                    double scale) {
+  const int64_t m = q.size(-2), n = k.size(-2);
+  const Tensor scores = sddmm_many_mask(b, m, n, nonzeros, row_indices, row_offsets,
+                                        column_indices, q, k);
+  const Tensor weights = sparse_softmax_many_mask_scaled(b, m, nonzeros, scores, row_indices,
+                                                         row_offsets, column_indices, scale);
+  return spmm_many_mask(b, m, n, nonzeros, weights, row_indices, row_offsets, column_indices, v);
+}
+
+// q [R, m, d], k and v [R, n, d] (float32; half storage is widened: the heads op keeps it);
+// replica r uses mask r / (R / b).  -> {out} or {out, lse [R, m]}.
+std::vector<Tensor> sparse_attention_many_mask(int64_t b, const Tensor& nonzeros, const Tensor& q_in,
+                                               const Tensor& k_in, const Tensor& v_in,
+                                               const Tensor& row_indices, const Tensor& row_offsets,
+                                               const Tensor& column_indices, double scale,
+                                               bool want_lse, const c10::optional<Tensor>& plan) {
+  const Tensor q = as_float(q_in, "query");
+  const Tensor k = as_float(k_in, "key");
+  const Tensor v = as_float(v_in, "value");
+  TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3,
+              "sparse_attention_many_mask: expected [replicas, rows, d] query, key, value");
+  TORCH_CHECK(k.sizes() == v.sizes(), "key and value must have one shape");
+  TORCH_CHECK(q.size(0) == k.size(0) && q.size(2) == k.size(2),
+              "query and key must have one replica count and head dimension");
+  TORCH_CHECK(q.device() == k.device() && q.device() == v.device(),
+              "query, key, value must be on one device");
+  const c10::DeviceGuard guard(q.device());
+  const ManyMask mm = check_many_mask(b, q.size(1), nonzeros, row_indices, row_offsets,
+                                      column_indices, q, q.size(0));
+  const int n = to_int(k.size(1), "n"), d = to_int(q.size(2), "d");
+  const size_t ws_bytes =
+      sputnik_hip_sparse_attention_many_mask_workspace_bytes(mm.masks, mm.m, n, d, mm.width);
+  Tensor out = at::empty_like(q);
+  Tensor lse = want_lse ? at::empty({mm.replicas, mm.m}, q.options()) : Tensor();
+  int status = SPUTNIK_HIP_UNSUPPORTED;
+  if (ws_bytes > 0) {
+    Tensor workspace;
+    if (plan.has_value()) check_plan(*plan, ws_bytes, q);
+    else workspace = at::empty({static_cast<int64_t>(ws_bytes)}, q.options().dtype(at::kByte));
+    auto call = [&](auto forward, auto ws) {
+      return forward(mm.masks, mm.m, n, d, mm.nonzeros.data(), mm.replicas,
+                     mm.row_indices.data_ptr<int>(), mm.row_offsets.data_ptr<int>(),
+                     mm.column_indices.data_ptr<int>(), q.data_ptr<float>(),
+                     static_cast<int64_t>(mm.m) * d, k.data_ptr<float>(),
+                     static_cast<int64_t>(n) * d, v.data_ptr<float>(), static_cast<int64_t>(n) * d,
+                     static_cast<float>(scale), out.data_ptr<float>(),
+                     static_cast<int64_t>(mm.m) * d, want_lse ? lse.data_ptr<float>() : nullptr,
+                     static_cast<int64_t>(mm.m), ws, ws_bytes, current_stream(q));
+    };
+    status = plan.has_value()
+                 ? call(sputnik_hip_sparse_attention_many_mask_forward_planned,
+                        static_cast<const void*>(plan->data_ptr()))
+                 : call(sputnik_hip_sparse_attention_many_mask_forward, workspace.data_ptr());
+  }
+  if (status == SPUTNIK_HIP_UNSUPPORTED) {
+    TORCH_CHECK(!want_lse, "sparse_attention_many_mask: lse needs a call the fused kernel serves "
+                "(head dimension 64, 16-byte aligned operands)");
+    return {attention_many_mask_composed(b, nonzeros, q, k, v, mm.row_indices, mm.row_offsets,
+                                         mm.column_indices, scale)};
+  }
+  check_status(status, "sparse_attention_many_mask");
+  if (want_lse) return {out, lse};
+  return {out};
+}
+
+// Topology-only pre-pass of both many-mask attention forms (16 unused bytes when the kernels
+// do not serve the shape: the planned call then composes the operators).
+Tensor sparse_attention_many_mask_plan(int64_t b, int64_t m64, int64_t n64, int64_t d64,
+                                       const Tensor& nonzeros, const Tensor& row_indices,
+                                       const Tensor& row_offsets, const Tensor& column_indices) {
+  TORCH_CHECK(row_offsets.is_cuda(), "row_offsets must be a GPU (HIP) tensor");
+  const c10::DeviceGuard guard(row_offsets.device());
+  const ManyMask mm = check_many_mask(b, m64, nonzeros, row_indices, row_offsets, column_indices,
+                                      row_offsets, b);
+  const int n = to_int(n64, "n"), d = to_int(d64, "d");
+  const size_t bytes =
+      sputnik_hip_sparse_attention_many_mask_workspace_bytes(mm.masks, mm.m, n, d, mm.width);
+  Tensor plan = make_plan_tensor(bytes, row_offsets);
+  if (bytes > 0)
+    check_status(sputnik_hip_sparse_attention_many_mask_plan(
+                     mm.masks, mm.m, n, d, mm.nonzeros.data(), mm.row_indices.data_ptr<int>(),
+                     mm.row_offsets.data_ptr<int>(), mm.column_indices.data_ptr<int>(),
+                     plan.data_ptr(), bytes, current_stream(row_offsets)),
+                 "sparse_attention_many_mask_plan");
+  return plan;
+}
+
+// q [B, H, m, d], k and v [B, H, n, d] views of one half type (any strides with a unit last
+// one; batch element b uses mask b, so B = b); out stored as out_type (0 float32, else the
+// operands' type) in a [B, m, H, d] buffer, returned as its [B, H, m, d] view; lse [B, H, m].
+// A call the kernel does not serve is composed from the float32 many-mask operators.
+std::vector<Tensor> sparse_attention_heads_many_mask(int64_t b, const Tensor& nonzeros,
+                                                     const Tensor& q_in, const Tensor& k_in,
+                                                     const Tensor& v_in, const Tensor& row_indices,
+                                                     const Tensor& row_offsets,
+                                                     const Tensor& column_indices, double scale,
+                                                     int64_t out_type, bool want_lse,
+                                                     const c10::optional<Tensor>& plan) {
+  TORCH_CHECK(q_in.dim() == 4 && k_in.dim() == 4 && v_in.dim() == 4,
+              "sparse_attention_heads_many_mask: expected [batch, heads, rows, d] views");
+  const HeadOperand q = head_operand(q_in, "query"), k = head_operand(k_in, "key"),
+                    v = head_operand(v_in, "value");
+  const auto st = q.t.scalar_type();
+  const int dtype = type_code(st);
+  TORCH_CHECK(dtype == SPUTNIK_HIP_F16 || dtype == SPUTNIK_HIP_BF16,
+              "sparse_attention_heads_many_mask: expected float16 / bfloat16 operands, got ", st);
+  TORCH_CHECK(k.t.scalar_type() == st && v.t.scalar_type() == st,
+              "sparse_attention_heads_many_mask: query, key, value must have one type");
+  TORCH_CHECK(k.t.sizes() == v.t.sizes(), "key and value must have one shape");
+  TORCH_CHECK(q.d == k.d, "query and key must have one head dimension");
+  TORCH_CHECK(q.batch == k.batch && q.heads == k.heads, "query and key must have one batch and head count");
+  TORCH_CHECK(q.t.device() == k.t.device() && q.t.device() == v.t.device(),
+              "query, key, value must be on one device");
+  TORCH_CHECK(out_type == SPUTNIK_HIP_F32 || out_type == dtype,
+              "sparse_attention_heads_many_mask: out_type is float32 or the operands' type");
+  const c10::DeviceGuard guard(q.t.device());
+  TORCH_CHECK(q.batch == b, "sparse_attention_heads_many_mask: batch (", q.batch,
+              ") must equal the number of masks (", b, ")");
+  const ManyMask mm = check_many_mask(b, q.rows, nonzeros, row_indices, row_offsets,
+                                      column_indices, q.t, q.batch * q.heads);
+  const int n = to_int(k.rows, "n"), d = to_int(q.d, "d");
+  const int heads = to_int(q.heads, "heads");
+  const auto out_st = out_type == SPUTNIK_HIP_F32 ? at::kFloat : st;
+  Tensor buffer = at::empty({q.batch, q.rows, q.heads, q.d}, q.t.options().dtype(out_st));
+  Tensor out = buffer.permute({0, 2, 1, 3});
+  const HeadOperand o = head_operand(out, "out");
+  Tensor lse = want_lse ? at::empty({q.batch, q.heads, q.rows}, q.t.options().dtype(at::kFloat))
+                        : Tensor();
+  const size_t ws_bytes =
+      sputnik_hip_sparse_attention_many_mask_workspace_bytes(mm.masks, mm.m, n, d, mm.width);
+  int status = SPUTNIK_HIP_UNSUPPORTED;
+  if (ws_bytes > 0) {
+    Tensor workspace;
+    if (plan.has_value()) check_plan(*plan, ws_bytes, q.t);
+    else workspace = at::empty({static_cast<int64_t>(ws_bytes)}, q.t.options().dtype(at::kByte));
+    auto call = [&](auto forward, auto ws) {
+      return forward(mm.masks, mm.m, n, d, mm.nonzeros.data(), mm.masks, heads,
+                     mm.row_indices.data_ptr<int>(), mm.row_offsets.data_ptr<int>(),
+                     mm.column_indices.data_ptr<int>(), dtype, q.t.data_ptr(), q.batch_stride,
+                     q.head_stride, q.row_stride, k.t.data_ptr(), k.batch_stride, k.head_stride,
+                     k.row_stride, v.t.data_ptr(), v.batch_stride, v.head_stride, v.row_stride,
+                     static_cast<float>(scale), o.t.data_ptr(), static_cast<int>(out_type),
+                     o.batch_stride, o.head_stride, o.row_stride,
+                     want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(mm.m), ws,
+                     ws_bytes, current_stream(q.t));
+    };
+    status = plan.has_value()
+                 ? call(sputnik_hip_sparse_attention_heads_many_mask_forward_planned,
+                        static_cast<const void*>(plan->data_ptr()))
+                 : call(sputnik_hip_sparse_attention_heads_many_mask_forward, workspace.data_ptr());
+  }
+  if (status == SPUTNIK_HIP_UNSUPPORTED) {
+    TORCH_CHECK(!want_lse, "sparse_attention_heads_many_mask: lse needs a call the fused kernel "
+                "serves (head dimension 64, 16-byte aligned views)");
+    // float32 per-head copies [B*H, rows, d] through the many-mask operators
+    auto per_head = [&](const HeadOperand& x) {
+      return x.t.to(at::kFloat).reshape({x.batch * x.heads, x.rows, x.d});
+    };
+    const Tensor product = attention_many_mask_composed(b, nonzeros, per_head(q), per_head(k),
+                                                        per_head(v), mm.row_indices,
+                                                        mm.row_offsets, mm.column_indices, scale);
+    out.copy_(product.reshape(out.sizes()));
+    return {out};
+  }
+  check_status(status, "sparse_attention_heads_many_mask");
+  if (want_lse) return {out, lse};
+  return {out};
+}
+
 // Layout pass of the reference's modules (modules/sparse_linear.py:89,
 // modules/sparse_attention.py:108-126): x[..., R, C] -> contiguous [..., C, R],
 // i.e. `x.transpose(-1, -2).contiguous()` as ONE tiled kernel, optionally
@@ -1805,6 +1982,17 @@ TORCH_LIBRARY(torch_sputnik, m) {
   m.def(
       "csr_transpose_many_mask(int b, int m, int n, Tensor nonzeros, Tensor values, "
       "Tensor row_offsets, Tensor column_indices) -> Tensor[]");
+  m.def(
+      "sparse_attention_many_mask(int b, Tensor nonzeros, Tensor query, Tensor key, Tensor value, "
+      "Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, bool want_lse, "
+      "Tensor? plan) -> Tensor[]");
+  m.def(
+      "sparse_attention_many_mask_plan(int b, int m, int n, int d, Tensor nonzeros, "
+      "Tensor row_indices, Tensor row_offsets, Tensor column_indices) -> Tensor");
+  m.def(
+      "sparse_attention_heads_many_mask(int b, Tensor nonzeros, Tensor query, Tensor key, "
+      "Tensor value, Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, "
+      "int out_type, bool want_lse, Tensor? plan) -> Tensor[]");
   m.def("permute_last(Tensor values, Tensor permutation) -> Tensor");
   m.def("permute_last_banded(Tensor values, Tensor dest_list, Tensor source_in_band) -> Tensor");
   m.def("permute_band_size() -> int", &permute_band_size);
@@ -1870,6 +2058,9 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("sparse_softmax_many_mask_scaled", &sparse_softmax_many_mask_scaled);
   m.impl("sparse_softmax_backward_many_mask", &sparse_softmax_backward_many_mask);
   m.impl("csr_transpose_many_mask", &csr_transpose_many_mask);
+  m.impl("sparse_attention_many_mask", &sparse_attention_many_mask);
+  m.impl("sparse_attention_many_mask_plan", &sparse_attention_many_mask_plan);
+  m.impl("sparse_attention_heads_many_mask", &sparse_attention_heads_many_mask);
   m.impl("permute_last", &permute_last);
   m.impl("permute_last_banded", &permute_last_banded);
   m.impl("spmm_permuted", &spmm_permuted);

@@ -239,6 +239,15 @@ class PlanCache(_TopologyCache):
                                                             column_indices),
                           row_indices, row_offsets, column_indices)
 
+    def attention_many_mask(self, b, m, n, d, nonzeros, row_indices, row_offsets, column_indices):
+        """Plan of the many-mask attention (ops.sparse_attention_many_mask_plan); `nonzeros` a
+        host list / tensor, part of the key."""
+        counts = tuple(int(c) for c in (nonzeros.tolist() if torch.is_tensor(nonzeros) else nonzeros))
+        return self._plan("attention_many_mask", (b, m, n, d, counts),
+                          lambda: ops.sparse_attention_many_mask_plan(b, m, n, d, counts, row_indices,
+                                                                      row_offsets, column_indices),
+                          row_indices, row_offsets, column_indices)
+
 
 # Both caches exist by default with scope "static": they serve the patterns that
 # modules register (see above) and nothing else.  `enable_*_cache(True)` widens
@@ -1061,3 +1070,182 @@ class CsrSoftmaxManyMask(torch.autograd.Function):
         grad_scores = ops.sparse_softmax_backward_many_mask(
             b, m, ctx.nonzeros, out, grad_output.contiguous(), row_offsets, scale)
         return None, None, None, grad_scores, None, None, None, None
+
+
+# ---------------------------------------------------------------------------
+# Fused attention with one mask per batch element (the reference's SparseCoreAttention,
+# tests/transformer/modules.py:9-81: sddmm_many_mask, sparse_softmax_many_mask, spmm_many_mask).
+# The forward is one kernel (ops.sparse_attention_many_mask / _heads_many_mask); the backward
+# recomputes the weights with the many-mask operators, which are float32 only: half inputs
+# get float32 per-head copies there, and their gradients are returned in the input's type.
+# ---------------------------------------------------------------------------
+def _many_mask_topology(b, m, n, d, nonzeros, row_indices, row_offsets, column_indices):
+    plan = None
+    if _plans is not None:
+        plan = _plans.attention_many_mask(b, m, n, d, nonzeros, row_indices, row_offsets,
+                                          column_indices)
+    return plan
+
+
+def _many_mask_composed(b, nonzeros, topo, query, key, value, scale):
+    """softmax(scale * sddmm) @ v from the separate many-mask operators, [R, S, D] float32
+    (the path of tensors the kernels do not serve, CPU tensors among them)."""
+    row_indices, row_offsets, column_indices = topo
+    m, n = query.size(-2), key.size(-2)
+    scores = ops.sddmm_many_mask(b, m, n, nonzeros, row_indices, row_offsets, column_indices,
+                                 query, key)
+    weights = ops.sparse_softmax_many_mask(b, m, nonzeros, scores, row_indices, row_offsets,
+                                           column_indices, scale)
+    return ops.spmm_many_mask(b, m, n, nonzeros, weights, row_indices, row_offsets,
+                              column_indices, value)
+
+
+def _many_mask_backward(b, nonzeros, topo, query, key, value, scale, grad_output, needs):
+    """Gradients of softmax(scale * sddmm_many_mask(q, k)) @ v for float32 [R, S, D] operands,
+    as _attention_backward with the many-mask operators: the weights are recomputed, then
+    dV = P^T dO, dP = sddmm(dO, v), dS = softmax'(P, dP), dQ = dS k, dK = dS^T q."""
+    row_indices, row_offsets, column_indices = topo
+    m, n = query.size(-2), key.size(-2)
+    grad_output = grad_output.contiguous()
+    scores = ops.sddmm_many_mask(b, m, n, nonzeros, *topo, query, key)
+    weights = ops.sparse_softmax_many_mask(b, m, nonzeros, scores, *topo, scale)
+    grad_weights = ops.sddmm_many_mask(b, m, n, nonzeros, *topo, grad_output, value)
+    grad_scores = ops.sparse_softmax_backward_many_mask(b, m, nonzeros, weights, grad_weights,
+                                                        row_offsets, scale)
+    grad_query = grad_key = grad_value = None
+    if needs[0]:
+        grad_query = ops.spmm_many_mask(b, m, n, nonzeros, grad_scores, *topo, key)
+    if needs[1] or needs[2]:
+        grad_t, row_offsets_t, column_indices_t = ops.csr_transpose_many_mask(
+            b, m, n, nonzeros, grad_scores, row_offsets, column_indices)
+        row_indices_t = diffsort_many_mask(row_offsets_t, b)
+        topo_t = (row_indices_t, row_offsets_t, column_indices_t)
+        if needs[1]:
+            grad_key = ops.spmm_many_mask(b, n, m, nonzeros, grad_t, *topo_t, query)
+        if needs[2]:
+            weights_t = ops.csr_transpose_many_mask(b, m, n, nonzeros, weights, row_offsets,
+                                                    column_indices)[0]
+            grad_value = ops.spmm_many_mask(b, n, m, nonzeros, weights_t, *topo_t, grad_output)
+    return grad_query, grad_key, grad_value
+
+
+def _many_mask_forward(b, nonzeros, topo, query, key, value, scale):
+    """[R, S, D] forward: the fused kernel on GPU tensors (the heads kernel for half storage,
+    whose [R, S, D] is a [b, R/b, S, D] head view), the composition elsewhere."""
+    if not query.is_cuda:
+        return _many_mask_composed(b, nonzeros, topo, query.float(), key.float(), value.float(),
+                                   scale).to(query.dtype)
+    plan = _many_mask_topology(b, query.size(-2), key.size(-2), query.size(-1), nonzeros, *topo)
+    if query.dtype in (torch.float16, torch.bfloat16):
+        def heads(x):
+            return x.unflatten(0, (b, x.size(0) // b))
+        out = ops.sparse_attention_heads_many_mask(b, nonzeros, *topo, heads(query), heads(key),
+                                                   heads(value), scale, plan=plan)
+        return out.flatten(0, 1)   # ([b, H, S, D] view of a [b, S, H, D] buffer: one copy)
+    return ops.sparse_attention_many_mask(b, nonzeros, *topo, query, key, value, scale, plan=plan)
+
+
+def _float_per_replica(x):
+    return x.to(torch.float32).contiguous()
+
+
+class SparseAttentionManyMaskFunction(torch.autograd.Function):
+    """sparse_attention_many_mask under autograd (apply(b, nonzeros, row_indices, row_offsets,
+    column_indices, query, key, value, scale))."""
+
+    @staticmethod
+    def forward(ctx, b, nonzeros, row_indices, row_offsets, column_indices, query, key, value, scale):
+        ctx.b, ctx.nonzeros, ctx.scale = int(b), nonzeros, float(scale)
+        ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices)
+        return _many_mask_forward(ctx.b, nonzeros, (row_indices, row_offsets, column_indices),
+                                  query, key, value, scale)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors
+        grads = _many_mask_backward(ctx.b, ctx.nonzeros, (row_indices, row_offsets, column_indices),
+                                    _float_per_replica(query), _float_per_replica(key),
+                                    _float_per_replica(value), ctx.scale,
+                                    _float_per_replica(grad_output), ctx.needs_input_grad[5:8])
+        grads = [None if g is None else g.to(x.dtype) for g, x in zip(grads, (query, key, value))]
+        return (None, None, None, None, None, *grads, None)
+
+
+def sparse_attention_many_mask(b, m, n, nonzeros, row_indices, row_offsets, column_indices, query,
+                               key, value, scale):
+    """softmax(scale * q k^T at the mask) v with one mask per batch element, for [R, S, D]
+    tensors (R = b * heads, replica r under mask r // heads), topology in the many-mask layout
+    of tests/transformer/utils.py:17-38 (``topology.dense_to_sparse_3d``), `nonzeros` a host
+    list or tensor.  float32, float16 or bfloat16: half inputs are read in their type by the
+    fused kernel and the result keeps it (scores, weights and sums float32).  Differentiable:
+    the backward recomputes the weights with the many-mask operators, which are float32 only
+    (half inputs: float32 copies, gradients returned in the input's type).  Head dimensions
+    other than 64, unaligned operands and CPU tensors take the composed operators."""
+    m, n = int(m), int(n)
+    if query.size(-2) != m or key.size(-2) != n:
+        raise ValueError(f"expected query rows {m} and key rows {n}, got {query.size(-2)}, {key.size(-2)}")
+    topo = (row_indices, row_offsets, column_indices)
+    if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
+        return SparseAttentionManyMaskFunction.apply(b, nonzeros, *topo, query, key, value, scale)
+    return _many_mask_forward(int(b), nonzeros, topo, query, key, value, scale)
+
+
+class SparseAttentionHeadsManyMaskFunction(torch.autograd.Function):
+    """sparse_attention_heads_many_mask under autograd ([B, S, H, D] views)."""
+
+    @staticmethod
+    def forward(ctx, query, key, value, nonzeros, row_indices, row_offsets, column_indices, scale):
+        ctx.nonzeros, ctx.scale = nonzeros, float(scale)
+        ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices)
+        return _heads_many_mask_forward(query, key, value, nonzeros,
+                                        (row_indices, row_offsets, column_indices), scale)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors
+        b, heads = query.size(0), query.size(2)
+
+        def per_head(x):   # [B, S, H, D] -> [B*H, S, D] float32
+            return x.to(torch.float32).transpose(1, 2).reshape(b * heads, x.size(1), x.size(3))
+
+        grads = _many_mask_backward(b, ctx.nonzeros, (row_indices, row_offsets, column_indices),
+                                    per_head(query), per_head(key), per_head(value), ctx.scale,
+                                    per_head(grad_output), ctx.needs_input_grad[:3])
+
+        def merged(g, like):   # [B*H, S, D] -> [B, S, H, D] in like's type
+            if g is None:
+                return None
+            return g.reshape(b, heads, like.size(1), -1).transpose(1, 2).to(like.dtype)
+
+        return (merged(grads[0], query), merged(grads[1], key), merged(grads[2], value),
+                None, None, None, None, None)
+
+
+def _heads_many_mask_forward(query, key, value, nonzeros, topo, scale):
+    b, heads = query.size(0), query.size(2)
+    q, k, v = (x.transpose(1, 2) for x in (query, key, value))   # [B, H, S, D] views
+    if query.is_cuda:
+        if query.dtype in (torch.float16, torch.bfloat16):
+            plan = _many_mask_topology(b, q.size(-2), k.size(-2), q.size(-1), nonzeros, *topo)
+            out = ops.sparse_attention_heads_many_mask(b, nonzeros, *topo, q, k, v, scale, plan=plan)
+            return out.transpose(1, 2)   # the kernel's [B, S, H, D] buffer
+        per_head = [x.reshape(b * heads, x.size(2), x.size(3)) for x in (q, k, v)]
+        out = _many_mask_forward(b, nonzeros, topo, *per_head, scale)
+    else:
+        per_head = [x.float().reshape(b * heads, x.size(2), x.size(3)) for x in (q, k, v)]
+        out = _many_mask_composed(b, nonzeros, topo, *per_head, scale)
+    return out.reshape(b, heads, query.size(1), -1).transpose(1, 2).to(query.dtype)
+
+
+def sparse_attention_heads_many_mask(query, key, value, nonzeros, row_indices, row_offsets,
+                                     column_indices, scale):
+    """The many-mask attention for [B, S, H, D] views (query [B, m, H, D], key and value
+    [B, n, H, D], any strides with a unit last one; batch element i under mask i): the layout
+    split_tensor_along_last_dim gives (tests/transformer/modules.py:98-111, head stride 3 D),
+    read in place by the fused kernel for float16 / bfloat16 -- no copy.  float32 views are
+    copied once to [B*H, S, D].  Returns [B, m, H, D] in the inputs' type (a contiguous
+    tensor).  Differentiable as sparse_attention_many_mask."""
+    topo = (row_indices, row_offsets, column_indices)
+    if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
+        return SparseAttentionHeadsManyMaskFunction.apply(query, key, value, nonzeros, *topo, scale)
+    return _heads_many_mask_forward(query, key, value, nonzeros, topo, scale)

@@ -21,7 +21,7 @@ import torch.nn as nn
 from . import functional, ops
 from .functional import (GroupProjectionFunction, HalfSparseLinearFunction, SparseAttentionFunction,
                          Sddmm, SparseLinearFunction, SparseSoftmax, Spmm)
-from .topology import dense_to_sparse, generate_mask
+from .topology import dense_to_sparse, dense_to_sparse_3d, generate_mask
 
 
 class SparseLinear(nn.Module):
@@ -306,3 +306,33 @@ class SparseAttention(nn.Module):
         if key not in streams:
             streams[key] = torch.cuda.Stream(device=device)
         return streams[key]
+
+
+class SparseCoreAttention(nn.Module):
+    """The attention core of the reference's transformer (tests/transformer/modules.py:9-81):
+    ``forward(query, key, value, mask)`` with query, key, value [b, s, n, hn] and `mask`
+    [b, 1, s, s] (a nonzero entry is attended; one mask per batch element, shared by its
+    heads) -> the context [s, b, n * hn].  The reference runs sddmm_many_mask,
+    sparse_softmax_many_mask and spmm_many_mask on [b*n, s, hn] copies; here the forward is
+    ONE fused kernel (functional.sparse_attention_heads_many_mask): float16 / bfloat16
+    inputs are read in place as head views, float32 inputs are copied once to [b*n, s, hn]
+    as the reference does.  ``topology=`` (the tuple topology.dense_to_sparse_3d returns)
+    lets a caller with a static mask skip the per-call conversion; `mask` is then unused."""
+
+    def __init__(self, seq_length, hidden_size, num_attention_heads):
+        super().__init__()
+        if hidden_size % num_attention_heads != 0:
+            raise ValueError(f"{hidden_size} is not divisible by {num_attention_heads}")
+        self.seq_length = seq_length
+        self.hidden_size_per_attention_head = hidden_size // num_attention_heads
+
+    def forward(self, query, key, value, mask=None, topology=None):
+        if topology is None:
+            topology = dense_to_sparse_3d(mask)
+        row_indices, row_offsets, column_indices, nonzeros = topology
+        b, s = query.size(0), query.size(1)
+        scale = 1.0 / math.sqrt(self.hidden_size_per_attention_head)
+        out = functional.sparse_attention_heads_many_mask(query, key, value, nonzeros, row_indices,
+                                                          row_offsets, column_indices, scale)
+        # [b, s, n, hn] -> [s, b, n * hn]
+        return out.permute(1, 0, 2, 3).reshape(s, b, -1)

@@ -236,6 +236,52 @@ def csr_transpose_many_mask(b, m, n, nonzeros, values, row_offsets, column_indic
                                         row_offsets, column_indices)
 
 
+def sparse_attention_many_mask(b, nonzeros, row_indices, row_offsets, column_indices, query, key,
+                               value, scale, with_lse=False, plan=None):
+    """softmax(scale * q k^T at the mask) v with one mask per batch element in ONE kernel:
+    query [R,S,D], key/value [R,S',D] (float32; half storage is widened -- the heads form
+    keeps it), replica r under mask r // (R // b); topology in the many-mask layout
+    (tests/transformer/utils.py:17-38).  -> [R,S,D] float32, or [out, lse] ``with_lse``.
+    What the kernel does not serve (head dimension other than 64, unaligned operands) is
+    composed from the many-mask operators (no lse then)."""
+    outs = _ops.sparse_attention_many_mask(int(b), _counts(nonzeros), query, key, value, row_indices,
+                                           row_offsets, column_indices, float(scale), bool(with_lse),
+                                           plan)
+    return outs if with_lse else outs[0]
+
+
+def sparse_attention_many_mask_with_lse(b, nonzeros, row_indices, row_offsets, column_indices, query,
+                                        key, value, scale):
+    return sparse_attention_many_mask(b, nonzeros, row_indices, row_offsets, column_indices, query,
+                                      key, value, scale, with_lse=True)
+
+
+def sparse_attention_many_mask_plan(b, m, n, d, nonzeros, row_indices, row_offsets, column_indices):
+    """Pre-pass of both many-mask attention forms over b masks of m x n, head dimension d."""
+    return _ops.sparse_attention_many_mask_plan(int(b), int(m), int(n), int(d), _counts(nonzeros),
+                                                row_indices, row_offsets, column_indices)
+
+
+def sparse_attention_many_mask_planned(b, nonzeros, row_indices, row_offsets, column_indices, query,
+                                       key, value, scale, plan, with_lse=False):
+    return sparse_attention_many_mask(b, nonzeros, row_indices, row_offsets, column_indices, query,
+                                      key, value, scale, with_lse=with_lse, plan=plan)
+
+
+def sparse_attention_heads_many_mask(b, nonzeros, row_indices, row_offsets, column_indices, query,
+                                     key, value, scale, out_dtype=None, with_lse=False, plan=None):
+    """The many-mask attention on float16 / bfloat16 head views [B, H, rows, 64] (any strides
+    with a unit last one; batch element i under mask i, so B = b), as
+    sparse_attention_heads: the result is stored as `out_dtype` (the operands' type by
+    default, or float32) in a [B, rows, H, 64] buffer and returned as its [B, H, rows, 64]
+    view; ``with_lse`` -> [out, lse [B, H, rows]]."""
+    out_code = _half_code(query.dtype if out_dtype is None else out_dtype)
+    outs = _ops.sparse_attention_heads_many_mask(int(b), _counts(nonzeros), query, key, value,
+                                                 row_indices, row_offsets, column_indices,
+                                                 float(scale), out_code, bool(with_lse), plan)
+    return outs if with_lse else outs[0]
+
+
 # ---------------------------------------------------------------------------
 # static topologies: plan once, run many times (no counterpart in the reference,
 # which re-derives everything per call, src/spmm_cuda.cu:48-57)

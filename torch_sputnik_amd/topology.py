@@ -39,3 +39,25 @@ def generate_mask(m, n, device="cpu", sparsity=0.9, round_to=4, generator=None):
     mask[:num_ones] = 1
     (generator or np.random.default_rng()).shuffle(mask)
     return torch.from_numpy(mask).reshape(m, n).to(device)
+
+
+def dense_to_sparse_3d(mask):
+    """Dense [b, s, s'] mask -> (row_indices [b, s], row_offsets [b, s + 1], column_indices
+    [sum nnz], nonzeros): one CSR topology per batch element in the "many mask" layout of
+    tests/transformer/utils.py:17-38 (each mask's offsets start at 0, column indices
+    concatenated), int32 indices, `nonzeros` a host list.  A nonzero entry is attended.
+    Also [b, 1, s, s'] (the reference's module squeezes its mask; only dim 1 is dropped
+    here, so b = 1 keeps its batch dimension)."""
+    if mask.dim() == 4:
+        mask = mask.squeeze(1)
+    if mask.dim() != 3:
+        raise ValueError(f"expected a [b, s, s'] or [b, 1, s, s'] mask, got {tuple(mask.shape)}")
+    row_indices, row_offsets, column_indices, nonzeros = [], [], [], []
+    for i in range(mask.size(0)):
+        csr = (mask[i] != 0).to_sparse_csr()
+        offsets = csr.crow_indices().to(torch.int32)
+        row_offsets.append(offsets)
+        row_indices.append(diffsort(offsets))
+        column_indices.append(csr.col_indices().to(torch.int32))
+        nonzeros.append(int(offsets[-1]))
+    return (torch.stack(row_indices), torch.stack(row_offsets), torch.cat(column_indices), nonzeros)
