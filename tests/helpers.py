@@ -105,3 +105,113 @@ def rel_err_torch(got, want):
     if bool(significant.any()):
         worst = max(worst, float((err[significant] / aw[significant]).max()))
     return worst
+
+
+# ---------------------------------------------------------------------------
+# many-mask family: masks of mixed kinds and float64 references (torch, any device)
+# ---------------------------------------------------------------------------
+MASK_KINDS = ("empty", "single", "uniform", "band", "global", "heavy_row", "empty_rows")
+
+
+def mask_of_kind(kind, m, n, rng):
+    """One [m, n] 0/1 mask: empty; a single entry; uniform at density 0.02-1; a band (local
+    window along the diagonal of the m x n rectangle); global tokens (full rows and columns
+    over a 2 % background); one full row in a <= 5 % mask (more than 32 entries in one key
+    chunk); uniform with forced empty rows."""
+    mask = np.zeros((m, n), dtype=bool)
+    if kind == "single":
+        mask[rng.integers(0, m), rng.integers(0, n)] = True
+    elif kind == "uniform":
+        mask = rng.random((m, n)) < rng.uniform(0.02, 1.0)
+    elif kind == "band":
+        width = int(rng.integers(0, 17))
+        centre = (np.arange(m)[:, None] * n) // max(m, 1)
+        mask = np.abs(np.arange(n)[None, :] - centre) <= width
+    elif kind == "global":
+        mask = rng.random((m, n)) < 0.02
+        mask[rng.choice(m, size=min(m, int(rng.integers(1, 4))), replace=False)] = True
+        mask[:, rng.choice(n, size=min(n, int(rng.integers(1, 4))), replace=False)] = True
+    elif kind == "heavy_row":
+        mask = rng.random((m, n)) < rng.uniform(0.0, 0.05)
+        mask[rng.integers(0, m)] = True
+    elif kind == "empty_rows":
+        mask = rng.random((m, n)) < rng.uniform(0.1, 0.6)
+        mask[rng.choice(m, size=max(1, m // 8), replace=False)] = False
+    else:
+        assert kind == "empty", kind
+    return mask
+
+
+def shuffle_columns(column_indices, row_offsets, mask_id, m, first, rng, every=3):
+    """Columns of every `every`-th row of mask `mask_id` (flat many-mask layout, its entries
+    from `first`) in random order, in place: the order-independent path of those row blocks."""
+    ro = row_offsets[mask_id * (m + 1):(mask_id + 1) * (m + 1)]
+    for r in range(0, m, every):
+        a, b = first + int(ro[r]), first + int(ro[r + 1])
+        if b - a > 1:
+            column_indices[a:b] = column_indices[a:b][rng.permutation(b - a)]
+
+
+def many_mask_entries(nonzeros, row_offsets, column_indices, m, heads, device):
+    """(replica, row, column, slot) long tensors of every served entry of a many-mask
+    topology (flat or [b, m + 1] offsets), replica r under mask r // heads."""
+    import torch
+    ro = torch.as_tensor(row_offsets).reshape(-1).to(device=device, dtype=torch.int64)
+    ci = torch.as_tensor(column_indices).reshape(-1).to(device=device, dtype=torch.int64)
+    parts, first = [], 0
+    for i, count in enumerate(int(c) for c in nonzeros):
+        offs = ro[i * (m + 1):(i + 1) * (m + 1)]
+        rows = torch.repeat_interleave(torch.arange(m, device=device), offs[1:] - offs[:-1])
+        cols = ci[first:first + count]
+        slots = torch.arange(count, device=device)
+        for h in range(heads):
+            parts.append((torch.full_like(slots, i * heads + h), rows, cols, slots))
+        first += count
+    if not parts:
+        empty = torch.zeros(0, dtype=torch.int64, device=device)
+        return empty, empty, empty, empty
+    return tuple(torch.cat([p[j] for p in parts]) for j in range(4))
+
+
+def ref_sddmm_many_mask(entries, width, lhs, rhs):
+    """[R, width] float64: lhs[r, row] . rhs[r, col] at every entry, 0 past a replica's count
+    (differentiable)."""
+    import torch
+    r, row, col, slot = entries
+    out = torch.zeros(lhs.size(0), width, dtype=torch.float64, device=lhs.device)
+    return out.index_put((r, slot), (lhs.double()[r, row] * rhs.double()[r, col]).sum(-1))
+
+
+def ref_spmm_many_mask(entries, m, values, dense):
+    """[R, m, N] float64: the sparse [m, k] of each replica (values[r, slot]) times dense[r]."""
+    import torch
+    r, row, col, slot = entries
+    a = torch.zeros(dense.size(0), m, dense.size(1), dtype=torch.float64, device=dense.device)
+    a = a.index_put((r, row, col), values.double()[r, slot])
+    return a @ dense.double()
+
+
+def ref_softmax_many_mask(entries, m, n, values, scale=1.0):
+    """Row softmax of scale * values over each replica's entries, [R, values.size(1)] float64
+    with zeros past a replica's count (differentiable)."""
+    import torch
+    r, row, col, slot = entries
+    dense = torch.full((values.size(0), m, n), float("-inf"), dtype=torch.float64,
+                       device=values.device)
+    dense = dense.index_put((r, row, col), scale * values.double()[r, slot])
+    probs = torch.softmax(dense, dim=-1)
+    out = torch.zeros(values.shape, dtype=torch.float64, device=values.device)
+    return out.index_put((r, slot), probs[r, row, col])
+
+
+def ref_attention_many_mask(q, k, v, dense_masks, scale):
+    """float64 dense masked softmax per replica, replica r under mask r // heads: q [R, m, d],
+    k and v [R, n, d], dense_masks [b, m, n] bool -> (out [R, m, d], lse [R, m]); rows
+    without entries give zeros and lse = -inf.  Differentiable (gradients of empty rows: 0)."""
+    import torch
+    q, k, v = (x.double() for x in (q, k, v))
+    heads = q.size(0) // dense_masks.size(0)
+    mask = torch.as_tensor(dense_masks).to(q.device).repeat_interleave(heads, 0)
+    s = (scale * q @ k.transpose(1, 2)).masked_fill(~mask, float("-inf"))
+    lse = torch.logsumexp(s, dim=-1)
+    return torch.softmax(s, dim=-1).nan_to_num(0.0) @ v, lse
