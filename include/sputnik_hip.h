@@ -851,6 +851,139 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_many_mask_forward_planned
                              sputnik_hip_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Attention dropout.  Dropout on the attention probabilities (between the softmax and the
+ * product with v), decided per stored entry by a counter-based generator so that the fused
+ * kernels, sparse_dropout on a values array and a backward's replay all drop the same ones:
+ *
+ *   key     = (seed lo, seed hi)
+ *   counter = (offset/4 lo, offset/4 hi, e >> 2, r)      Philox4x32-10, output word e & 3
+ *   keep    = word < min(floor((1 - p) 2^32), 2^32 - 1)  (double), kept x float(1/(1 - p))
+ *
+ * r is the replica (b * heads + h for head views), e the entry's index in its replica's row
+ * of the values array: the CSR position for one mask, the position inside the mask for many
+ * masks (the column of the [replicas, max(nonzeros)] arrays).  This is ATen's
+ * Philox4_32(seed, (r << 32) | (e >> 2), offset) for an offset that is a multiple of 4.
+ * 0 <= p < 1; any other p gives SPUTNIK_HIP_INVALID_ARGUMENT.  p = 0 runs the forms without
+ * dropout and touches neither the state nor rng_state_out.
+ *
+ * The state mirrors a PyTorch PhiloxCudaState: values, or (seed_ptr, offset_ptr) device
+ * pointers read when the kernel runs (offset = *offset_ptr + offset_intragraph), which is how
+ * a captured graph draws new masks on every replay.  `rng_state_out` (may be NULL), int64
+ * [2] in device memory, receives the {seed, offset} the call used; handing it back as
+ * {seed_ptr, offset_ptr} = {rng_state_out, rng_state_out + 1} replays the mask.
+ * ------------------------------------------------------------------------ */
+typedef struct sputnik_hip_philox_state {
+  uint64_t seed;
+  uint64_t offset;
+  const int64_t* seed_ptr;     /* NULL: `seed` holds it */
+  const int64_t* offset_ptr;   /* NULL: `offset` holds it */
+  uint64_t offset_intragraph;
+} sputnik_hip_philox_state;
+
+/* out[r, e] = x[r, e] * keep(r, e) * scale for x [rows, width] (row strides in elements) of
+ * `dtype` (SPUTNIK_HIP_F32 / F16 / BF16); out has x's type, the product is formed in float32
+ * and rounded once.  Many-mask arrays go in at their full [replicas, max(nonzeros)] width:
+ * zero padding stays zero.  `replica0` is the replica index of row 0. */
+SPUTNIK_HIP_API int sputnik_hip_sparse_dropout_typed(int rows, int width, int replica0, int dtype,
+                             const void* x, int64_t x_stride, void* out, int64_t out_stride,
+                             double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
+                             sputnik_hip_stream_t stream);
+
+/* The fused forms with dropout: the arguments of the form without, then p, the state and
+ * rng_state_out.  `lse` stays the log-sum-exp of the undropped scores (what a backward
+ * needs to rebuild the weights); the output is (sum_kept e_j v_j) * scale / sum_all e_j. */
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_forward_dropout(int m, int n, int d, int nonzeros,
+                             int replicas, const int* row_indices, const int* row_offsets,
+                             const int* column_indices, const float* q, int64_t q_stride,
+                             const float* k, int64_t k_stride, const float* v,
+                             int64_t v_stride, float scale, float* out, int64_t out_stride,
+                             float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+                             int64_t* rng_state_out, void* workspace, size_t workspace_bytes,
+                             sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_forward_planned_dropout(int m, int n, int d,
+                             int nonzeros, int replicas, const int* row_indices,
+                             const int* row_offsets, const int* column_indices, const float* q,
+                             int64_t q_stride, const float* k, int64_t k_stride, const float* v,
+                             int64_t v_stride, float scale, float* out, int64_t out_stride,
+                             float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+                             int64_t* rng_state_out, const void* workspace,
+                             size_t workspace_bytes, sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_forward_dropout(int m, int n, int d,
+                             int nonzeros, int batch, int heads, const int* row_indices,
+                             const int* row_offsets, const int* column_indices, int dtype,
+                             const void* q, int64_t q_batch_stride, int64_t q_head_stride,
+                             int64_t q_row_stride, const void* k, int64_t k_batch_stride,
+                             int64_t k_head_stride, int64_t k_row_stride, const void* v,
+                             int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride,
+                             float scale, void* out, int out_type, int64_t out_batch_stride,
+                             int64_t out_head_stride, int64_t out_row_stride, float* lse,
+                             int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+                             int64_t* rng_state_out, void* workspace, size_t workspace_bytes,
+                             sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_forward_planned_dropout(int m, int n, int d,
+                             int nonzeros, int batch, int heads, const int* row_indices,
+                             const int* row_offsets, const int* column_indices, int dtype,
+                             const void* q, int64_t q_batch_stride, int64_t q_head_stride,
+                             int64_t q_row_stride, const void* k, int64_t k_batch_stride,
+                             int64_t k_head_stride, int64_t k_row_stride, const void* v,
+                             int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride,
+                             float scale, void* out, int out_type, int64_t out_batch_stride,
+                             int64_t out_head_stride, int64_t out_row_stride, float* lse,
+                             int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+                             int64_t* rng_state_out, const void* workspace,
+                             size_t workspace_bytes, sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_many_mask_forward_dropout(int masks, int m, int n,
+                             int d, const int* nonzeros, int replicas, const int* row_indices,
+                             const int* row_offsets, const int* column_indices, const float* q,
+                             int64_t q_stride, const float* k, int64_t k_stride, const float* v,
+                             int64_t v_stride, float scale, float* out, int64_t out_stride,
+                             float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+                             int64_t* rng_state_out, void* workspace, size_t workspace_bytes,
+                             sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_many_mask_forward_planned_dropout(int masks, int m,
+                             int n, int d, const int* nonzeros, int replicas,
+                             const int* row_indices, const int* row_offsets,
+                             const int* column_indices, const float* q, int64_t q_stride,
+                             const float* k, int64_t k_stride, const float* v, int64_t v_stride,
+                             float scale, float* out, int64_t out_stride, float* lse,
+                             int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+                             int64_t* rng_state_out, const void* workspace,
+                             size_t workspace_bytes, sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_many_mask_forward_dropout(int masks, int m,
+                             int n, int d, const int* nonzeros, int batch, int heads,
+                             const int* row_indices, const int* row_offsets,
+                             const int* column_indices, int dtype, const void* q,
+                             int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                             const void* k, int64_t k_batch_stride, int64_t k_head_stride,
+                             int64_t k_row_stride, const void* v, int64_t v_batch_stride,
+                             int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+                             int out_type, int64_t out_batch_stride, int64_t out_head_stride,
+                             int64_t out_row_stride, float* lse, int64_t lse_stride, double p,
+                             sputnik_hip_philox_state rng, int64_t* rng_state_out,
+                             void* workspace, size_t workspace_bytes,
+                             sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_many_mask_forward_planned_dropout(int masks,
+                             int m, int n, int d, const int* nonzeros, int batch, int heads,
+                             const int* row_indices, const int* row_offsets,
+                             const int* column_indices, int dtype, const void* q,
+                             int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                             const void* k, int64_t k_batch_stride, int64_t k_head_stride,
+                             int64_t k_row_stride, const void* v, int64_t v_batch_stride,
+                             int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+                             int out_type, int64_t out_batch_stride, int64_t out_head_stride,
+                             int64_t out_row_stride, float* lse, int64_t lse_stride, double p,
+                             sputnik_hip_philox_state rng, int64_t* rng_state_out,
+                             const void* workspace, size_t workspace_bytes,
+                             sputnik_hip_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * "many mask" family: `masks` topologies of the same m x n shape, laid out
  * as tests/transformer/utils.py:17-38 builds them:
  *   row_indices    [masks * m]        local row ids of mask i at i*m

@@ -19,6 +19,17 @@ _c_ptr = ctypes.c_void_p
 _c_size = ctypes.c_size_t
 _c_float = ctypes.c_float
 
+
+class PhiloxState(ctypes.Structure):
+    """sputnik_hip_philox_state: seed and offset values, or device pointers to them (NULL:
+    the values are meant) plus the in-graph offset -- a PhiloxCudaState without torch."""
+    _fields_ = [("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+                ("seed_ptr", ctypes.c_void_p), ("offset_ptr", ctypes.c_void_p),
+                ("offset_intragraph", ctypes.c_uint64)]
+
+
+_DROP = [ctypes.c_double, PhiloxState, _c_ptr]   # p, state, rng_state_out
+
 # name -> (restype, argtypes); must list every symbol include/sputnik_hip.h declares.
 SIGNATURES = {
     "sputnik_hip_version": (ctypes.c_char_p, []),
@@ -167,6 +178,31 @@ SIGNATURES = {
     "sputnik_hip_sparse_attention_heads_many_mask_forward_planned": (_c_int, [_c_int] * 4 + [
         _c_ptr, _c_int, _c_int] + [_c_ptr] * 3 + [_c_int] + [_c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [
         _c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_dropout_typed": (_c_int, [_c_int] * 4 + [_c_ptr, _c_i64, _c_ptr, _c_i64] + _DROP + [_c_ptr]),
+    "sputnik_hip_sparse_attention_forward_dropout": (_c_int, [_c_int] * 5 + [
+        _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_float, _c_ptr,
+        _c_i64, _c_ptr, _c_i64] + _DROP + [_c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_forward_planned_dropout": (_c_int, [_c_int] * 5 + [
+        _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_float, _c_ptr,
+        _c_i64, _c_ptr, _c_i64] + _DROP + [_c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_heads_forward_dropout": (_c_int, [_c_int] * 6 + [_c_ptr] * 3 + [_c_int] + [
+        _c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [_c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64]
+        + _DROP + [_c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_heads_forward_planned_dropout": (_c_int, [_c_int] * 6 + [_c_ptr] * 3 + [
+        _c_int] + [_c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [
+        _c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64] + _DROP + [_c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_many_mask_forward_dropout": (_c_int, [_c_int] * 4 + [_c_ptr, _c_int] + [
+        _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_float, _c_ptr,
+        _c_i64, _c_ptr, _c_i64] + _DROP + [_c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_many_mask_forward_planned_dropout": (_c_int, [_c_int] * 4 + [
+        _c_ptr, _c_int] + [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_float,
+                           _c_ptr, _c_i64, _c_ptr, _c_i64] + _DROP + [_c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_heads_many_mask_forward_dropout": (_c_int, [_c_int] * 4 + [
+        _c_ptr, _c_int, _c_int] + [_c_ptr] * 3 + [_c_int] + [_c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [
+        _c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64] + _DROP + [_c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_heads_many_mask_forward_planned_dropout": (_c_int, [_c_int] * 4 + [
+        _c_ptr, _c_int, _c_int] + [_c_ptr] * 3 + [_c_int] + [_c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [
+        _c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64] + _DROP + [_c_ptr, _c_size, _c_ptr]),
     "sputnik_hip_spmm_many_mask": (_c_int, [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr, _c_ptr, _c_i64,
                                                           _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr,
                                                           _c_i64, _c_ptr, _c_size, _c_ptr]),

@@ -34,6 +34,11 @@
 // instructions (profiles/r3e_pmc_sq_attention_ops.json: 46.5 M per launch), a third
 // of them the broadcasts and the 45-instruction transposing reduction of the 16-lane
 // form.  Steps 2 and 3 are unchanged (step 3 finds entry u in lane 4 (u % 4) + u / 4).
+//
+// Attention dropout (philox.h): the instances with a DropArgs argument decide
+// per entry, in step 2, whether the weight handed to step 3 is kept; l and lse still take
+// every entry.
+#include "philox.h"
 #include "spmm_tiled_common.h"
 
 namespace sputnik_hip {
@@ -144,14 +149,29 @@ __device__ __forceinline__ WorkItem many_mask_work(int heads, int m, int slots, 
 
 // MANY: `nonzeros` is the number of replicas per mask (each mask's own count is read from
 // its row_offsets), q, k, v, out and lse start at replica 0 and the grid holds every replica.
-template <bool MANY>
+// Drop: attention dropout (philox.h), DROP = the pack holds one DropArgs.  The lane that
+// owns entry e16 of a window owns CSR position ps + w0 + e16 and decides whether it is kept;
+// the row sum still takes every entry (lse is that of the undropped scores), only the weight
+// handed to step 3 becomes 0 for a dropped entry, and finish() applies 1 / l and the keep
+// scale together.  DROP is a trailing parameter pack, not a bool and an argument, so that the
+// instances without it keep their argument list -- and their code: moving the body into an
+// inlined device function changes it (§3.9a of DESIGN.md).
+template <typename... D>
+__device__ __forceinline__ DropArgs drop_of(D... d) {
+  if constexpr (sizeof...(D) == 0) return DropArgs{};
+  else return (d, ...);
+}
+
+template <bool MANY, typename... Drop>
 __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
     int m, int n, int nonzeros, int slots, int nchunks, const int* __restrict__ row_indices,
     const int* __restrict__ row_offsets, const int* __restrict__ column_indices,
     const int* __restrict__ table, const int* __restrict__ row_ok, const float* __restrict__ q,
     int64_t q_stride, const float* __restrict__ k, int64_t k_stride, const float* __restrict__ v,
     int64_t v_stride, float scale, float* __restrict__ out, int64_t out_stride,
-    float* __restrict__ lse, int64_t lse_stride) {
+    float* __restrict__ lse, int64_t lse_stride, Drop... drop_arg) {
+  constexpr bool DROP = sizeof...(Drop) > 0;
+  const DropArgs drop = drop_of(drop_arg...);
   __shared__ float tile[2][2 * kTileFloats];  // [buffer][K rows | V rows]
 
   const int lane = threadIdx.x % kWave;
@@ -171,6 +191,9 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
   }
   const int mblock = item.mblock;
   const int replica = item.replica;
+  PhiloxKey key{};
+  if constexpr (DROP) key = philox_key(drop, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0);
+  const int drop_r = replica + drop.replica0;
   q += replica * q_stride;
   k += replica * k_stride;
   v += replica * v_stride;
@@ -202,7 +225,8 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
 #pragma unroll
     for (int t = 0; t < kRQ; ++t) {
       if (my_row[t] < 0) continue;
-      const float inv = st[t].l > 0.f ? 1.f / st[t].l : 0.f;  // rows without entries give zeros
+      float inv = st[t].l > 0.f ? 1.f / st[t].l : 0.f;  // rows without entries give zeros
+      if constexpr (DROP) inv *= drop.scale;
       *reinterpret_cast<float4*>(out + static_cast<int64_t>(my_row[t]) * kD + 4 * i) =
           make_float4(st[t].acc.x * inv, st[t].acc.y * inv, st[t].acc.z * inv,
                       st[t].acc.w * inv);
@@ -238,10 +262,12 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
         if (s > st[t].mx) rescale(st[t], s);
         const float e = __expf(s - st[t].mx);
         st[t].l += e;
-        st[t].acc.x = fmaf(e, vf.x, st[t].acc.x);
-        st[t].acc.y = fmaf(e, vf.y, st[t].acc.y);
-        st[t].acc.z = fmaf(e, vf.z, st[t].acc.z);
-        st[t].acc.w = fmaf(e, vf.w, st[t].acc.w);
+        float ek = e;
+        if constexpr (DROP) ek = philox_keep(key, drop.threshold, drop_r, p) ? e : 0.f;
+        st[t].acc.x = fmaf(ek, vf.x, st[t].acc.x);
+        st[t].acc.y = fmaf(ek, vf.y, st[t].acc.y);
+        st[t].acc.z = fmaf(ek, vf.z, st[t].acc.z);
+        st[t].acc.w = fmaf(ek, vf.w, st[t].acc.w);
       }
     }
     finish();
@@ -324,7 +350,9 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
         st[t].l += group_sum<16>(e);
 
         // 3. weighted V rows; padded entries carry weight 0 and offset 0
-        const entry_pair ent = make_entry(roff, e);
+        float ek = e;
+        if constexpr (DROP) ek = philox_keep(key, drop.threshold, drop_r, ps[t] + w0 + e16) ? e : 0.f;
+        const entry_pair ent = make_entry(roff, ek);
         float a4[4] = {st[t].acc.x, st[t].acc.y, st[t].acc.z, st[t].acc.w};
         auto values4 = [&](auto G) {
           constexpr int kG = decltype(G)::value;
@@ -464,13 +492,16 @@ struct RowAccH {
 
 // MANY: batch element b uses mask b (`nonzeros` and `replica0` are not used: each mask's
 // count is read from its row_offsets, and the grid holds every replica).
-template <typename T, typename TO, bool MANY>
+// Drop: attention dropout as in sparse_attention_kernel, with r = b * heads + h.
+template <typename T, typename TO, bool MANY, typename... Drop>
 __global__ __launch_bounds__(kThreads) void sparse_attention_heads_kernel(
     int m, int n, int nonzeros, int slots, int nchunks, int heads, int replica0,
     const int* __restrict__ row_indices, const int* __restrict__ row_offsets,
     const int* __restrict__ column_indices, const int* __restrict__ table,
     const int* __restrict__ row_ok, HeadView qv, HeadView kv, HeadView vv, float scale,
-    HeadView ov, float* __restrict__ lse, int64_t lse_stride) {
+    HeadView ov, float* __restrict__ lse, int64_t lse_stride, Drop... drop_arg) {
+  constexpr bool DROP = sizeof...(Drop) > 0;
+  const DropArgs drop = drop_of(drop_arg...);
   __shared__ __attribute__((aligned(16))) T tile[2][2 * kHTile];  // [buffer][K rows | V rows]
 
   const int lane = threadIdx.x % kWave;
@@ -488,6 +519,9 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_heads_kernel(
   }
   const int mblock = item.mblock;
   const int replica = item.replica;
+  PhiloxKey key{};
+  if constexpr (DROP) key = philox_key(drop, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0);
+  const int drop_r = replica;
   const int64_t b = replica / heads, h = replica - b * heads;
   const T* __restrict__ q = static_cast<const T*>(qv.base) + (b * qv.batch + h * qv.head);
   const T* __restrict__ k = static_cast<const T*>(kv.base) + (b * kv.batch + h * kv.head);
@@ -526,7 +560,8 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_heads_kernel(
 #pragma unroll
     for (int t = 0; t < kRQ; ++t) {
       if (my_row[t] < 0) continue;
-      const float inv = st[t].l > 0.f ? 1.f / st[t].l : 0.f;  // rows without entries give zeros
+      float inv = st[t].l > 0.f ? 1.f / st[t].l : 0.f;  // rows without entries give zeros
+      if constexpr (DROP) inv *= drop.scale;
       const f4v r = {st[t].acc.x * inv, st[t].acc.y * inv, st[t].acc.z * inv, st[t].acc.w * inv};
       *reinterpret_cast<typename Vec4<TO>::type*>(out + (static_cast<unsigned>(my_row[t]) * o_rs + 4 * i)) =
           __builtin_convertvector(r, typename Vec4<TO>::type);
@@ -558,10 +593,12 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_heads_kernel(
         if (s > st[t].mx) rescale(st[t], s);
         const float e = __expf(s - st[t].mx);
         st[t].l += e;
-        st[t].acc.x = fmaf(e, vf.x, st[t].acc.x);
-        st[t].acc.y = fmaf(e, vf.y, st[t].acc.y);
-        st[t].acc.z = fmaf(e, vf.z, st[t].acc.z);
-        st[t].acc.w = fmaf(e, vf.w, st[t].acc.w);
+        float ek = e;
+        if constexpr (DROP) ek = philox_keep(key, drop.threshold, drop_r, p) ? e : 0.f;
+        st[t].acc.x = fmaf(ek, vf.x, st[t].acc.x);
+        st[t].acc.y = fmaf(ek, vf.y, st[t].acc.y);
+        st[t].acc.z = fmaf(ek, vf.z, st[t].acc.z);
+        st[t].acc.w = fmaf(ek, vf.w, st[t].acc.w);
       }
     }
     finish();
@@ -645,7 +682,9 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_heads_kernel(
         st[t].l += group_sum<16>(e);
 
         // 3. weighted V rows; padded entries carry weight 0 and offset 0
-        const entry_pair ent = make_entry(roff, e);
+        float ek = e;
+        if constexpr (DROP) ek = philox_keep(key, drop.threshold, drop_r, ps[t] + w0 + e16) ? e : 0.f;
+        const entry_pair ent = make_entry(roff, ek);
         float a4[4] = {st[t].acc.x, st[t].acc.y, st[t].acc.z, st[t].acc.w};
         auto values4 = [&](auto G) {
           constexpr int kG = decltype(G)::value;
@@ -733,10 +772,14 @@ int attention_exec(int m, int n, int d, int nonzeros, int replicas, const int* r
                    int64_t q_stride, const float* k, int64_t k_stride, const float* v,
                    int64_t v_stride, float scale, float* out, int64_t out_stride, float* lse,
                    int64_t lse_stride, void* workspace, size_t workspace_bytes, bool planned,
-                   hipStream_t stream) {
+                   hipStream_t stream, const DropArgs* drop = nullptr) {
   if (m < 0 || n < 0 || d < 0 || nonzeros < 0 || replicas < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (m == 0 || replicas == 0) return 0;
+  if (m == 0 || replicas == 0) return drop != nullptr ? publish_rng_state(*drop, stream) : 0;
   if (nonzeros == 0 || n == 0) {  // every row is empty: zeros (and -inf log-sum-exp)
+    if (drop != nullptr) {
+      const int e = publish_rng_state(*drop, stream);
+      if (e != 0) return e;
+    }
     for (int r = 0; r < replicas; ++r) {
       hipError_t e = hipMemsetAsync(out + r * out_stride, 0, sizeof(float) * m * d, stream);
       if (e != hipSuccess) return static_cast<int>(e);
@@ -768,11 +811,22 @@ int attention_exec(int m, int n, int d, int nonzeros, int replicas, const int* r
   }
   for (int r0 = 0; r0 < replicas; r0 += kMaxGridYZ) {
     const int ry = min(replicas - r0, kMaxGridYZ);
+    if (drop != nullptr) {
+      DropArgs dr = *drop;   // replica numbers continue over the launches; the first publishes
+      dr.replica0 = r0;
+      if (r0 > 0) dr.rng_state_out = nullptr;
+      hipLaunchKernelGGL((sparse_attention_kernel<false, DropArgs>), dim3(slots / kBM, ry), dim3(kThreads), 0,
+                         stream, m, n, nonzeros, slots, nchunks, row_indices, row_offsets,
+                         column_indices, table, row_ok, q + r0 * q_stride, q_stride, k + r0 * k_stride,
+                         k_stride, v + r0 * v_stride, v_stride, scale, out + r0 * out_stride, out_stride,
+                         lse != nullptr ? lse + r0 * lse_stride : nullptr, lse_stride, dr);
+    } else {
     hipLaunchKernelGGL(sparse_attention_kernel<false>, dim3(slots / kBM, ry), dim3(kThreads), 0, stream,
                        m, n, nonzeros, slots, nchunks, row_indices, row_offsets, column_indices,
                        table, row_ok, q + r0 * q_stride, q_stride, k + r0 * k_stride, k_stride,
                        v + r0 * v_stride, v_stride, scale, out + r0 * out_stride, out_stride,
                        lse != nullptr ? lse + r0 * lse_stride : nullptr, lse_stride);
+    }
     st = launch_status();
     if (st != 0) return st;
   }
@@ -833,7 +887,15 @@ void launch_heads(dim3 grid, hipStream_t stream, int m, int n, int nonzeros, int
                   int heads, int replica0, const int* row_indices, const int* row_offsets,
                   const int* column_indices, const int* table, const int* row_ok, const HeadView& q,
                   const HeadView& k, const HeadView& v, float scale, const HeadView& o, float* lse,
-                  int64_t lse_stride) {
+                  int64_t lse_stride, const DropArgs* drop) {
+  if (drop != nullptr) {
+    DropArgs dr = *drop;   // (the kernel numbers its replicas from replica0 itself)
+    if (replica0 > 0) dr.rng_state_out = nullptr;
+    hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, false, DropArgs>), grid, dim3(kThreads), 0, stream,
+                       m, n, nonzeros, slots, nchunks, heads, replica0, row_indices, row_offsets,
+                       column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride, dr);
+    return;
+  }
   hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, false>), grid, dim3(kThreads), 0, stream, m, n,
                      nonzeros, slots, nchunks, heads, replica0, row_indices, row_offsets,
                      column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride);
@@ -843,10 +905,10 @@ int heads_exec(int m, int n, int d, int nonzeros, int batch, int heads, const in
                const int* row_offsets, const int* column_indices, int dtype, const HeadView& q,
                const HeadView& k, const HeadView& v, float scale, const HeadView& o, int out_type,
                float* lse, int64_t lse_stride, void* workspace, size_t workspace_bytes, bool planned,
-               hipStream_t stream) {
+               hipStream_t stream, const DropArgs* drop = nullptr) {
   if (m < 0 || n < 0 || d < 0 || nonzeros < 0 || batch < 0 || heads < 0)
     return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (m == 0 || batch == 0 || heads == 0) return 0;
+  if (m == 0 || batch == 0 || heads == 0) return drop != nullptr ? publish_rng_state(*drop, stream) : 0;
   if (!heads_served(m, n, d, nonzeros, batch, heads, dtype, out_type, q, k, v, o))
     return SPUTNIK_HIP_UNSUPPORTED;
   if (workspace == nullptr || !aligned_to(workspace, 16) ||
@@ -868,7 +930,8 @@ int heads_exec(int m, int n, int d, int nonzeros, int batch, int heads, const in
     const dim3 grid(slots / kBM, min(replicas - r0, kMaxGridYZ));
 #define SPUTNIK_HIP_HEADS(T, TO)                                                                  \
   launch_heads<T, TO>(grid, stream, m, n, nonzeros, slots, nchunks, heads, r0, row_indices,       \
-                      row_offsets, column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride)
+                      row_offsets, column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride, \
+                      drop)
     if (dtype == SPUTNIK_HIP_F16 && out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS(_Float16, float);
     else if (dtype == SPUTNIK_HIP_F16) SPUTNIK_HIP_HEADS(_Float16, _Float16);
     else if (out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS(__bf16, float);
@@ -993,11 +1056,11 @@ int attention_many_mask_exec(int masks, int m, int n, int d, const int* nonzeros
                              const float* k, int64_t k_stride, const float* v, int64_t v_stride,
                              float scale, float* out, int64_t out_stride, float* lse,
                              int64_t lse_stride, void* workspace, size_t workspace_bytes,
-                             bool planned, hipStream_t stream) {
+                             bool planned, hipStream_t stream, const DropArgs* drop = nullptr) {
   int largest = 0;
   int st = many_mask_args(masks, m, n, d, nonzeros, replicas, &largest);
   if (st != 0) return st;
-  if (m == 0 || replicas == 0) return 0;
+  if (m == 0 || replicas == 0) return drop != nullptr ? publish_rng_state(*drop, stream) : 0;
   if (!many_mask_supported(masks, m, n, d, largest, replicas) || !aligned_to(q, 16) || !aligned_to(k, 16) ||
       !aligned_to(v, 16) || !aligned_to(out, 16) || q_stride % 4 != 0 || k_stride % 4 != 0 ||
       v_stride % 4 != 0 || out_stride % 4 != 0)
@@ -1012,6 +1075,12 @@ int attention_many_mask_exec(int masks, int m, int n, int d, const int* nonzeros
   const int slots = slots_of(m), nchunks = chunks_of(n);
   const int* row_ok = static_cast<const int*>(workspace);
   const int* table = reinterpret_cast<const int*>(static_cast<const char*>(workspace) + row_ok_bytes(slots));
+  if (drop != nullptr)
+    hipLaunchKernelGGL((sparse_attention_kernel<true, DropArgs>), dim3(slots / kBM, replicas), dim3(kThreads),
+                       0, stream, m, n, replicas / masks, slots, nchunks, row_indices, row_offsets,
+                       column_indices, table, row_ok, q, q_stride, k, k_stride, v, v_stride, scale,
+                       out, out_stride, lse, lse_stride, *drop);
+  else
   hipLaunchKernelGGL(sparse_attention_kernel<true>, dim3(slots / kBM, replicas), dim3(kThreads), 0,
                      stream, m, n, replicas / masks, slots, nchunks, row_indices, row_offsets,
                      column_indices, table, row_ok, q, q_stride, k, k_stride, v, v_stride, scale, out,
@@ -1024,14 +1093,14 @@ int heads_many_mask_exec(int masks, int m, int n, int d, const int* nonzeros, in
                          int dtype, const HeadView& q, const HeadView& k, const HeadView& v,
                          float scale, const HeadView& o, int out_type, float* lse,
                          int64_t lse_stride, void* workspace, size_t workspace_bytes, bool planned,
-                         hipStream_t stream) {
+                         hipStream_t stream, const DropArgs* drop = nullptr) {
   if (batch < 0 || heads < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
   if (static_cast<int64_t>(batch) * heads >= (int64_t{1} << 31)) return SPUTNIK_HIP_UNSUPPORTED;
   if (batch != masks) return SPUTNIK_HIP_INVALID_ARGUMENT;
   int largest = 0;
   int st = many_mask_args(masks, m, n, d, nonzeros, batch * heads, &largest);
   if (st != 0) return st;
-  if (m == 0 || heads == 0) return 0;
+  if (m == 0 || heads == 0) return drop != nullptr ? publish_rng_state(*drop, stream) : 0;
   if (!many_mask_supported(masks, m, n, d, largest, batch * heads) ||
       !heads_served(m, n, d, max(largest, 1), batch, heads, dtype, out_type, q, k, v, o))
     return SPUTNIK_HIP_UNSUPPORTED;
@@ -1046,10 +1115,17 @@ int heads_many_mask_exec(int masks, int m, int n, int d, const int* nonzeros, in
   const int* row_ok = static_cast<const int*>(workspace);
   const int* table = reinterpret_cast<const int*>(static_cast<const char*>(workspace) + row_ok_bytes(slots));
   const dim3 grid(slots / kBM, batch * heads);
-#define SPUTNIK_HIP_HEADS_MM(T, TO)                                                                 \
-  hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, true>), grid, dim3(kThreads), 0, stream, \
-                     m, n, 0, slots, nchunks, heads, 0, row_indices, row_offsets, column_indices,   \
-                     table, row_ok, q, k, v, scale, o, lse, lse_stride)
+#define SPUTNIK_HIP_HEADS_MM(T, TO)                                                                   \
+  do {                                                                                                \
+    if (drop != nullptr)                                                                              \
+      hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, true, DropArgs>), grid, dim3(kThreads),  \
+                         0, stream, m, n, 0, slots, nchunks, heads, 0, row_indices, row_offsets,     \
+                         column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride, *drop);  \
+    else                                                                                              \
+      hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, true>), grid, dim3(kThreads), 0,       \
+                         stream, m, n, 0, slots, nchunks, heads, 0, row_indices, row_offsets,        \
+                         column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride);         \
+  } while (0)
   if (dtype == SPUTNIK_HIP_F16 && out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS_MM(_Float16, float);
   else if (dtype == SPUTNIK_HIP_F16) SPUTNIK_HIP_HEADS_MM(_Float16, _Float16);
   else if (out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS_MM(__bf16, float);
@@ -1145,5 +1221,152 @@ int sputnik_hip_sparse_attention_heads_many_mask_forward_planned(
                               out_type, lse, lse_stride, const_cast<void*>(workspace),
                               workspace_bytes, /*planned=*/true, static_cast<hipStream_t>(stream));
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// The forms with attention dropout (sputnik_hip.h, "Attention dropout"): the same checks and
+// launches with the DROP kernels; p = 0 is the form without.
+// ---------------------------------------------------------------------------
+extern "C" {
+
+#define SPUTNIK_HIP_DROP_ARGS()                                          \
+  DropArgs drop_store;                                                   \
+  if (!drop_args(p, rng, rng_state_out, &drop_store)) return SPUTNIK_HIP_INVALID_ARGUMENT; \
+  const DropArgs* drop = p > 0.0 ? &drop_store : nullptr
+
+int sputnik_hip_sparse_attention_forward_dropout(
+    int m, int n, int d, int nonzeros, int replicas, const int* row_indices, const int* row_offsets,
+    const int* column_indices, const float* q, int64_t q_stride, const float* k, int64_t k_stride,
+    const float* v, int64_t v_stride, float scale, float* out, int64_t out_stride, float* lse,
+    int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
+    void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  SPUTNIK_HIP_DROP_ARGS();
+  return attention_exec(m, n, d, nonzeros, replicas, row_indices, row_offsets, column_indices, q,
+                        q_stride, k, k_stride, v, v_stride, scale, out, out_stride, lse,
+                        lse_stride, workspace, workspace_bytes, /*planned=*/false, stream, drop);
+}
+
+int sputnik_hip_sparse_attention_forward_planned_dropout(
+    int m, int n, int d, int nonzeros, int replicas, const int* row_indices, const int* row_offsets,
+    const int* column_indices, const float* q, int64_t q_stride, const float* k, int64_t k_stride,
+    const float* v, int64_t v_stride, float scale, float* out, int64_t out_stride, float* lse,
+    int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
+    const void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  SPUTNIK_HIP_DROP_ARGS();
+  return attention_exec(m, n, d, nonzeros, replicas, row_indices, row_offsets, column_indices, q,
+                        q_stride, k, k_stride, v, v_stride, scale, out, out_stride, lse,
+                        lse_stride, const_cast<void*>(workspace), workspace_bytes,
+                        /*planned=*/true, stream, drop);
+}
+
+int sputnik_hip_sparse_attention_heads_forward_dropout(
+    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
+    const int* row_offsets, const int* column_indices, int dtype, const void* q,
+    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
+    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
+    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
+    float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
+    void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  SPUTNIK_HIP_DROP_ARGS();
+  return heads_exec(m, n, d, nonzeros, batch, heads, row_indices, row_offsets, column_indices, dtype,
+                    HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
+                    HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
+                    HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
+                    HeadView{out, out_batch_stride, out_head_stride, out_row_stride}, out_type, lse,
+                    lse_stride, workspace, workspace_bytes, /*planned=*/false, stream, drop);
+}
+
+int sputnik_hip_sparse_attention_heads_forward_planned_dropout(
+    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
+    const int* row_offsets, const int* column_indices, int dtype, const void* q,
+    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
+    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
+    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
+    float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
+    const void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  SPUTNIK_HIP_DROP_ARGS();
+  return heads_exec(m, n, d, nonzeros, batch, heads, row_indices, row_offsets, column_indices, dtype,
+                    HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
+                    HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
+                    HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
+                    HeadView{out, out_batch_stride, out_head_stride, out_row_stride}, out_type, lse,
+                    lse_stride, const_cast<void*>(workspace), workspace_bytes, /*planned=*/true,
+                    stream, drop);
+}
+
+int sputnik_hip_sparse_attention_many_mask_forward_dropout(
+    int masks, int m, int n, int d, const int* nonzeros, int replicas, const int* row_indices,
+    const int* row_offsets, const int* column_indices, const float* q, int64_t q_stride,
+    const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
+    int64_t out_stride, float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+    int64_t* rng_state_out, void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  SPUTNIK_HIP_DROP_ARGS();
+  return attention_many_mask_exec(masks, m, n, d, nonzeros, replicas, row_indices, row_offsets,
+                                  column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                                  out_stride, lse, lse_stride, workspace, workspace_bytes,
+                                  /*planned=*/false, static_cast<hipStream_t>(stream), drop);
+}
+
+int sputnik_hip_sparse_attention_many_mask_forward_planned_dropout(
+    int masks, int m, int n, int d, const int* nonzeros, int replicas, const int* row_indices,
+    const int* row_offsets, const int* column_indices, const float* q, int64_t q_stride,
+    const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
+    int64_t out_stride, float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+    int64_t* rng_state_out, const void* workspace, size_t workspace_bytes,
+    sputnik_hip_stream_t stream) {
+  SPUTNIK_HIP_DROP_ARGS();
+  return attention_many_mask_exec(masks, m, n, d, nonzeros, replicas, row_indices, row_offsets,
+                                  column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                                  out_stride, lse, lse_stride, const_cast<void*>(workspace),
+                                  workspace_bytes, /*planned=*/true, static_cast<hipStream_t>(stream),
+                                  drop);
+}
+
+int sputnik_hip_sparse_attention_heads_many_mask_forward_dropout(
+    int masks, int m, int n, int d, const int* nonzeros, int batch, int heads,
+    const int* row_indices, const int* row_offsets, const int* column_indices, int dtype,
+    const void* q, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+    const void* k, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride,
+    const void* v, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride,
+    float scale, void* out, int out_type, int64_t out_batch_stride, int64_t out_head_stride,
+    int64_t out_row_stride, float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+    int64_t* rng_state_out, void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  SPUTNIK_HIP_DROP_ARGS();
+  return heads_many_mask_exec(masks, m, n, d, nonzeros, batch, heads, row_indices, row_offsets,
+                              column_indices, dtype,
+                              HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
+                              HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
+                              HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
+                              HeadView{out, out_batch_stride, out_head_stride, out_row_stride},
+                              out_type, lse, lse_stride, workspace, workspace_bytes,
+                              /*planned=*/false, static_cast<hipStream_t>(stream), drop);
+}
+
+int sputnik_hip_sparse_attention_heads_many_mask_forward_planned_dropout(
+    int masks, int m, int n, int d, const int* nonzeros, int batch, int heads,
+    const int* row_indices, const int* row_offsets, const int* column_indices, int dtype,
+    const void* q, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+    const void* k, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride,
+    const void* v, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride,
+    float scale, void* out, int out_type, int64_t out_batch_stride, int64_t out_head_stride,
+    int64_t out_row_stride, float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+    int64_t* rng_state_out, const void* workspace, size_t workspace_bytes,
+    sputnik_hip_stream_t stream) {
+  SPUTNIK_HIP_DROP_ARGS();
+  return heads_many_mask_exec(masks, m, n, d, nonzeros, batch, heads, row_indices, row_offsets,
+                              column_indices, dtype,
+                              HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
+                              HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
+                              HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
+                              HeadView{out, out_batch_stride, out_head_stride, out_row_stride},
+                              out_type, lse, lse_stride, const_cast<void*>(workspace),
+                              workspace_bytes, /*planned=*/true, static_cast<hipStream_t>(stream),
+                              drop);
+}
+
+#undef SPUTNIK_HIP_DROP_ARGS
 
 }  // extern "C"

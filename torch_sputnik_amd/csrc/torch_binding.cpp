@@ -22,10 +22,12 @@
 // not registered here; the Python autograd.Functions stay the callers.
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
+#include <ATen/hip/HIPGeneratorImpl.h>   // at::CUDAGeneratorImpl on ROCm
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
 #include <algorithm>
+#include <mutex>
 #include <vector>
 
 #include "../../include/sputnik_hip.h"
@@ -1103,6 +1105,88 @@ std::vector<Tensor> csr_transpose_with_permutation(int64_t m, int64_t n, const T
   return csr_transpose_impl(m, n, values, row_offsets, column_indices, true, checked);
 }
 
+// ---- attention dropout (sputnik_hip.h, "Attention dropout") ----
+// One call's dropout: p, the Philox state and the int64 [2] device tensor that receives the
+// {seed, offset} the kernels resolve.  Fresh draws come from the device's default generator,
+// as torch.nn.functional.dropout's do: philox_cuda_state(4) under the generator's mutex gives
+// the offset before the call and advances it by 4, or, during graph capture, the seed and
+// offset pointers every replay refreshes.  A replay (`rng_state` given) reads the state from
+// that tensor and consumes nothing.
+struct Drop {
+  double p = 0.0;
+  sputnik_hip_philox_state rng{};
+  Tensor rng_state;
+  int64_t* rng_state_out = nullptr;   // NULL on a replay: the state is the input
+};
+
+void check_p(double p) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout probability must lie in [0, 1), got ", p);
+}
+
+Drop make_drop(double p, const c10::optional<Tensor>& rng_state, const Tensor& like) {
+  check_p(p);
+  Drop d;
+  d.p = p;
+  if (rng_state.has_value() && rng_state->defined()) {
+    const Tensor& st = *rng_state;
+    TORCH_CHECK(st.scalar_type() == at::kLong && st.numel() == 2 && st.is_contiguous() &&
+                    st.device() == like.device(),
+                "rng_state must be a contiguous int64 [2] tensor on ", like.device());
+    d.rng_state = st;
+    d.rng.seed_ptr = st.data_ptr<int64_t>();
+    d.rng.offset_ptr = st.data_ptr<int64_t>() + 1;
+    return d;
+  }
+  // p = 0 drops nothing and draws nothing: no state exists, and rng_state stays undefined
+  // (None in Python).  ops.sparse_dropout(values, 0) comes here; the attention ops refuse p = 0.
+  if (p == 0.0) return d;
+  d.rng_state = at::empty({2}, like.options().dtype(at::kLong));
+  d.rng_state_out = d.rng_state.data_ptr<int64_t>();
+  auto* gen = at::get_generator_or_default<at::CUDAGeneratorImpl>(
+      c10::nullopt, at::cuda::detail::getDefaultCUDAGenerator(like.device().index()));
+  at::PhiloxCudaState state;
+  {
+    std::lock_guard<std::mutex> lock(gen->mutex_);
+    state = gen->philox_cuda_state(4);
+  }
+  if (state.captured_) {
+    d.rng.seed_ptr = state.seed_.ptr;
+    d.rng.offset_ptr = state.offset_.ptr;
+    d.rng.offset_intragraph = state.offset_intragraph_;
+  } else {
+    d.rng.seed = state.seed_.val;
+    d.rng.offset = state.offset_.val;
+  }
+  return d;
+}
+
+// out = x * keep * scale on a values array ([nnz], or [R, width] with a unit last stride), in
+// x's type; row r is replica r.
+Tensor dropout_values(const Tensor& x_in, const Drop& d) {
+  TORCH_CHECK(x_in.is_cuda(), "sparse_dropout: values must be a GPU (HIP) tensor");
+  TORCH_CHECK(x_in.dim() == 1 || x_in.dim() == 2, "sparse_dropout: values must be [nnz] or [R, width]");
+  const int dtype = type_code(x_in.scalar_type());
+  TORCH_CHECK(dtype >= 0, "sparse_dropout: expected float32, float16 or bfloat16 values, got ",
+              x_in.scalar_type());
+  const Tensor x = x_in.dim() == 1 ? x_in.contiguous().view({1, -1})
+                                   : (x_in.stride(1) == 1 ? x_in : x_in.contiguous());
+  Tensor out = at::empty(x.sizes(), x.options());
+  const int rows = to_int(x.size(0), "rows"), width = to_int(x.size(1), "width");
+  check_status(sputnik_hip_sparse_dropout_typed(rows, width, 0, dtype, x.data_ptr(),
+                                                std::max<int64_t>(x.stride(0), width), out.data_ptr(),
+                                                width, d.p, d.rng, d.rng_state_out,
+                                                current_stream(x)),
+               "sparse_dropout");
+  return x_in.dim() == 1 ? out.view(x_in.sizes()) : out;
+}
+
+// -> {out, rng_state}
+std::vector<Tensor> sparse_dropout(const Tensor& values, double p, const c10::optional<Tensor>& rng_state) {
+  const c10::DeviceGuard guard(values.device());
+  const Drop d = make_drop(p, rng_state, values);
+  return {dropout_values(values, d), d.rng_state};
+}
+
 // Fused softmax(scale * sddmm(q, k)) @ v over a fixed mask
 // (modules/sparse_attention.py:66-82).  q [R,m,d] / [m,d]; k, v [R,n,d] / [n,d].
 // Shapes the fused kernel does not serve are composed from the three operators.
@@ -1111,7 +1195,8 @@ std::vector<Tensor> sparse_attention_impl(const Tensor& q_in, const Tensor& k_in
                                           const Tensor& row_offsets,
                                           const Tensor& column_indices, double scale,
                                           bool want_lse,
-                                          const c10::optional<Tensor>& plan = c10::nullopt) {
+                                          const c10::optional<Tensor>& plan = c10::nullopt,
+                                          const Drop* drop = nullptr) {
   const Tensor q = as_float(q_in, "query");
   const Tensor k = as_float(k_in, "key");
   const Tensor v = as_float(v_in, "value");
@@ -1129,18 +1214,40 @@ std::vector<Tensor> sparse_attention_impl(const Tensor& q_in, const Tensor& k_in
   const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, q);
 
   if (!sputnik_hip_sparse_attention_supported(m, n, d, topo.nonzeros)) {
-    TORCH_CHECK(!want_lse, "sparse_attention_with_lse: head dimension ", d,
+    TORCH_CHECK(!want_lse || drop != nullptr, "sparse_attention_with_lse: head dimension ", d,
                 " is not served by the fused kernel (64 is)");
     Tensor weights = sparse_softmax_scaled(
         sddmm(m, n, topo.row_indices, topo.row_offsets, topo.column_indices, q, k),
         topo.row_indices, topo.row_offsets, topo.column_indices, scale);
-    return {spmm(m, n, weights, topo.row_indices, topo.row_offsets, topo.column_indices, v)};
+    if (drop != nullptr) weights = dropout_values(weights, *drop);
+    Tensor out = spmm(m, n, weights, topo.row_indices, topo.row_offsets, topo.column_indices, v);
+    if (drop != nullptr) return {out, Tensor(), drop->rng_state};   // (no lse on this route)
+    return {out};
   }
   Tensor out = at::empty_like(q);
   Tensor lse;
   if (want_lse)
     lse = q.dim() == 3 ? at::empty({replicas, m}, q.options()) : at::empty({m}, q.options());
   const size_t ws_bytes = sputnik_hip_sparse_attention_workspace_bytes(m, n, d, topo.nonzeros);
+  if (drop != nullptr) {
+    Tensor workspace;
+    if (plan.has_value()) check_plan(*plan, ws_bytes, q);
+    else workspace = at::empty({static_cast<int64_t>(ws_bytes)}, q.options().dtype(at::kByte));
+    auto call = [&](auto forward, auto ws) {
+      return forward(m, n, d, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
+                     topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(),
+                     q.data_ptr<float>(), static_cast<int64_t>(m) * d, k.data_ptr<float>(),
+                     static_cast<int64_t>(n) * d, v.data_ptr<float>(), static_cast<int64_t>(n) * d,
+                     static_cast<float>(scale), out.data_ptr<float>(), static_cast<int64_t>(m) * d,
+                     want_lse ? lse.data_ptr<float>() : nullptr, m, drop->p, drop->rng,
+                     drop->rng_state_out, ws, ws_bytes, current_stream(q));
+    };
+    check_status(plan.has_value() ? call(sputnik_hip_sparse_attention_forward_planned_dropout,
+                                         static_cast<const void*>(plan->data_ptr()))
+                                  : call(sputnik_hip_sparse_attention_forward_dropout, workspace.data_ptr()),
+                 "sparse_attention_dropout");
+    return {out, want_lse ? lse : Tensor(), drop->rng_state};
+  }
   if (plan.has_value()) {
     check_plan(*plan, ws_bytes, q);
     check_status(sputnik_hip_sparse_attention_forward_planned(
@@ -1168,6 +1275,19 @@ std::vector<Tensor> sparse_attention_impl(const Tensor& q_in, const Tensor& k_in
                "sparse_attention");
   if (want_lse) return {out, lse};
   return {out};
+}
+
+// {out, lse, rng_state}: the fused attention with dropout p > 0 on the attention weights
+// (lse undefined where the composed route serves the call: head dimension other than 64).
+std::vector<Tensor> sparse_attention_dropout(const Tensor& q, const Tensor& k, const Tensor& v,
+                                             const Tensor& row_indices, const Tensor& row_offsets,
+                                             const Tensor& column_indices, double scale, double p,
+                                             const c10::optional<Tensor>& plan) {
+  TORCH_CHECK(p > 0.0 && p < 1.0, "sparse_attention_dropout: p must lie in (0, 1), got ", p);
+  const c10::DeviceGuard guard(q.device());
+  const Drop drop = make_drop(p, c10::nullopt, q);
+  return sparse_attention_impl(q, k, v, row_indices, row_offsets, column_indices, scale, true, plan,
+                               &drop);
 }
 
 Tensor sparse_attention(const Tensor& q, const Tensor& k, const Tensor& v,
@@ -1246,10 +1366,11 @@ HeadOperand head_operand(const Tensor& x_in, const char* name) {
 // out in the layout of the [B, m, H, d] buffer it views ([B, m, E] for 4-D operands), stored
 // as out_type (0 float32, else the operands' type); lse [.., m] float32 on request.
 // A call the kernel does not serve is composed from the typed operators (no lse then).
-std::vector<Tensor> sparse_attention_heads(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in,
+std::vector<Tensor> sparse_attention_heads_run(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in,
                                            const Tensor& row_indices, const Tensor& row_offsets,
                                            const Tensor& column_indices, double scale, int64_t out_type,
-                                           bool want_lse, const c10::optional<Tensor>& plan) {
+                                           bool want_lse, const c10::optional<Tensor>& plan,
+                                           const Drop* drop = nullptr) {
   const HeadOperand q = head_operand(q_in, "query"), k = head_operand(k_in, "key"),
                     v = head_operand(v_in, "value");
   const auto st = q.t.scalar_type();
@@ -1289,8 +1410,8 @@ std::vector<Tensor> sparse_attention_heads(const Tensor& q_in, const Tensor& k_i
       k.row_stride, v.t.data_ptr(), v.batch_stride, v.head_stride, v.row_stride, o.t.data_ptr(),
       o.batch_stride, o.head_stride, o.row_stride);
   if (!served) {
-    TORCH_CHECK(!want_lse, "sparse_attention_heads: lse needs a call the fused kernel serves "
-                "(head dimension 64, 16-byte aligned views)");
+    TORCH_CHECK(!want_lse || drop != nullptr, "sparse_attention_heads: lse needs a call the fused "
+                "kernel serves (head dimension 64, 16-byte aligned views)");
     // the typed operators on per-head copies in the storage type: float32 scores and
     // weights, float32 product, narrowed into the output's layout
     const int64_t replicas = q.batch * q.heads;
@@ -1299,11 +1420,14 @@ std::vector<Tensor> sparse_attention_heads(const Tensor& q_in, const Tensor& k_i
       return replicas == 1 ? flat[0] : flat;
     };
     const Tensor q3 = per_head(q), k3 = per_head(k), v3 = per_head(v);
-    const Tensor weights = sparse_softmax_scaled(
+    Tensor weights = sparse_softmax_scaled(
         sddmm(m, n, topo.row_indices, topo.row_offsets, topo.column_indices, q3, k3),
         topo.row_indices, topo.row_offsets, topo.column_indices, scale);
-    const Tensor product = spmm(m, n, weights, topo.row_indices, topo.row_offsets, topo.column_indices, v3);
+    if (drop != nullptr) weights = dropout_values(weights.dim() == 1 ? weights.view({1, -1}) : weights, *drop);
+    const Tensor product = spmm(m, n, replicas == 1 ? weights.view({-1}) : weights, topo.row_indices,
+                                topo.row_offsets, topo.column_indices, v3);
     out.copy_(product.reshape(out.sizes()));
+    if (drop != nullptr) return {out, Tensor(), drop->rng_state};
     return {out};
   }
   const size_t ws_bytes = sputnik_hip_sparse_attention_heads_workspace_bytes(m, n, d, topo.nonzeros);
@@ -1320,6 +1444,24 @@ std::vector<Tensor> sparse_attention_heads(const Tensor& q_in, const Tensor& k_i
                    want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(m), ws, ws_bytes,
                    current_stream(q.t));
   };
+  if (drop != nullptr) {
+    auto call_drop = [&](auto forward, auto ws) {
+      return forward(m, n, d, topo.nonzeros, batch, heads, topo.row_indices.data_ptr<int>(),
+                     topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(), dtype,
+                     q.t.data_ptr(), q.batch_stride, q.head_stride, q.row_stride, k.t.data_ptr(),
+                     k.batch_stride, k.head_stride, k.row_stride, v.t.data_ptr(), v.batch_stride,
+                     v.head_stride, v.row_stride, static_cast<float>(scale), o.t.data_ptr(),
+                     static_cast<int>(out_type), o.batch_stride, o.head_stride, o.row_stride,
+                     want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(m), drop->p,
+                     drop->rng, drop->rng_state_out, ws, ws_bytes, current_stream(q.t));
+    };
+    check_status(plan.has_value() ? call_drop(sputnik_hip_sparse_attention_heads_forward_planned_dropout,
+                                              static_cast<const void*>(plan->data_ptr()))
+                                  : call_drop(sputnik_hip_sparse_attention_heads_forward_dropout,
+                                              workspace.data_ptr()),
+                 "sparse_attention_heads_dropout");
+    return {out, want_lse ? lse : Tensor(), drop->rng_state};
+  }
   const int status = plan.has_value()
                          ? call(sputnik_hip_sparse_attention_heads_forward_planned,
                                 static_cast<const void*>(plan->data_ptr()))
@@ -1615,22 +1757,24 @@ std::vector<Tensor> csr_transpose_many_mask(int64_t b, int64_t m64, int64_t n64,
 Tensor attention_many_mask_composed(int64_t b, const Tensor& nonzeros, const Tensor& q,
                                     const Tensor& k, const Tensor& v, const Tensor& row_indices,
                                     const Tensor& row_offsets, const Tensor& column_indices,
-                                    double scale) {
+                                    double scale, const Drop* drop = nullptr) {
   const int64_t m = q.size(-2), n = k.size(-2);
   const Tensor scores = sddmm_many_mask(b, m, n, nonzeros, row_indices, row_offsets,
                                         column_indices, q, k);
-  const Tensor weights = sparse_softmax_many_mask_scaled(b, m, nonzeros, scores, row_indices,
-                                                         row_offsets, column_indices, scale);
+  Tensor weights = sparse_softmax_many_mask_scaled(b, m, nonzeros, scores, row_indices,
+                                                   row_offsets, column_indices, scale);
+  if (drop != nullptr) weights = dropout_values(weights, *drop);
   return spmm_many_mask(b, m, n, nonzeros, weights, row_indices, row_offsets, column_indices, v);
 }
 
 // q [R, m, d], k and v [R, n, d] (float32; half storage is widened: the heads op keeps it);
 // replica r uses mask r / (R / b).  -> {out} or {out, lse [R, m]}.
-std::vector<Tensor> sparse_attention_many_mask(int64_t b, const Tensor& nonzeros, const Tensor& q_in,
+std::vector<Tensor> sparse_attention_many_mask_run(int64_t b, const Tensor& nonzeros, const Tensor& q_in,
                                                const Tensor& k_in, const Tensor& v_in,
                                                const Tensor& row_indices, const Tensor& row_offsets,
                                                const Tensor& column_indices, double scale,
-                                               bool want_lse, const c10::optional<Tensor>& plan) {
+                                               bool want_lse, const c10::optional<Tensor>& plan,
+                                               const Drop* drop = nullptr) {
   const Tensor q = as_float(q_in, "query");
   const Tensor k = as_float(k_in, "key");
   const Tensor v = as_float(v_in, "value");
@@ -1664,18 +1808,38 @@ std::vector<Tensor> sparse_attention_many_mask(int64_t b, const Tensor& nonzeros
                      static_cast<int64_t>(mm.m) * d, want_lse ? lse.data_ptr<float>() : nullptr,
                      static_cast<int64_t>(mm.m), ws, ws_bytes, current_stream(q));
     };
-    status = plan.has_value()
-                 ? call(sputnik_hip_sparse_attention_many_mask_forward_planned,
-                        static_cast<const void*>(plan->data_ptr()))
-                 : call(sputnik_hip_sparse_attention_many_mask_forward, workspace.data_ptr());
+    auto call_drop = [&](auto forward, auto ws) {
+      return forward(mm.masks, mm.m, n, d, mm.nonzeros.data(), mm.replicas,
+                     mm.row_indices.data_ptr<int>(), mm.row_offsets.data_ptr<int>(),
+                     mm.column_indices.data_ptr<int>(), q.data_ptr<float>(),
+                     static_cast<int64_t>(mm.m) * d, k.data_ptr<float>(),
+                     static_cast<int64_t>(n) * d, v.data_ptr<float>(), static_cast<int64_t>(n) * d,
+                     static_cast<float>(scale), out.data_ptr<float>(),
+                     static_cast<int64_t>(mm.m) * d, want_lse ? lse.data_ptr<float>() : nullptr,
+                     static_cast<int64_t>(mm.m), drop->p, drop->rng, drop->rng_state_out, ws,
+                     ws_bytes, current_stream(q));
+    };
+    if (drop != nullptr)
+      status = plan.has_value()
+                   ? call_drop(sputnik_hip_sparse_attention_many_mask_forward_planned_dropout,
+                               static_cast<const void*>(plan->data_ptr()))
+                   : call_drop(sputnik_hip_sparse_attention_many_mask_forward_dropout, workspace.data_ptr());
+    else
+      status = plan.has_value()
+                   ? call(sputnik_hip_sparse_attention_many_mask_forward_planned,
+                          static_cast<const void*>(plan->data_ptr()))
+                   : call(sputnik_hip_sparse_attention_many_mask_forward, workspace.data_ptr());
   }
   if (status == SPUTNIK_HIP_UNSUPPORTED) {
-    TORCH_CHECK(!want_lse, "sparse_attention_many_mask: lse needs a call the fused kernel serves "
-                "(head dimension 64, 16-byte aligned operands)");
-    return {attention_many_mask_composed(b, nonzeros, q, k, v, mm.row_indices, mm.row_offsets,
-                                         mm.column_indices, scale)};
+    TORCH_CHECK(!want_lse || drop != nullptr, "sparse_attention_many_mask: lse needs a call the "
+                "fused kernel serves (head dimension 64, 16-byte aligned operands)");
+    const Tensor composed = attention_many_mask_composed(b, nonzeros, q, k, v, mm.row_indices,
+                                                         mm.row_offsets, mm.column_indices, scale, drop);
+    if (drop != nullptr) return {composed, Tensor(), drop->rng_state};
+    return {composed};
   }
   check_status(status, "sparse_attention_many_mask");
+  if (drop != nullptr) return {out, want_lse ? lse : Tensor(), drop->rng_state};
   if (want_lse) return {out, lse};
   return {out};
 }
@@ -1706,13 +1870,14 @@ Tensor sparse_attention_many_mask_plan(int64_t b, int64_t m64, int64_t n64, int6
 // one; batch element b uses mask b, so B = b); out stored as out_type (0 float32, else the
 // operands' type) in a [B, m, H, d] buffer, returned as its [B, H, m, d] view; lse [B, H, m].
 // A call the kernel does not serve is composed from the float32 many-mask operators.
-std::vector<Tensor> sparse_attention_heads_many_mask(int64_t b, const Tensor& nonzeros,
+std::vector<Tensor> sparse_attention_heads_many_mask_run(int64_t b, const Tensor& nonzeros,
                                                      const Tensor& q_in, const Tensor& k_in,
                                                      const Tensor& v_in, const Tensor& row_indices,
                                                      const Tensor& row_offsets,
                                                      const Tensor& column_indices, double scale,
                                                      int64_t out_type, bool want_lse,
-                                                     const c10::optional<Tensor>& plan) {
+                                                     const c10::optional<Tensor>& plan,
+                                                     const Drop* drop = nullptr) {
   TORCH_CHECK(q_in.dim() == 4 && k_in.dim() == 4 && v_in.dim() == 4,
               "sparse_attention_heads_many_mask: expected [batch, heads, rows, d] views");
   const HeadOperand q = head_operand(q_in, "query"), k = head_operand(k_in, "key"),
@@ -1761,27 +1926,112 @@ std::vector<Tensor> sparse_attention_heads_many_mask(int64_t b, const Tensor& no
                      want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(mm.m), ws,
                      ws_bytes, current_stream(q.t));
     };
-    status = plan.has_value()
-                 ? call(sputnik_hip_sparse_attention_heads_many_mask_forward_planned,
-                        static_cast<const void*>(plan->data_ptr()))
-                 : call(sputnik_hip_sparse_attention_heads_many_mask_forward, workspace.data_ptr());
+    auto call_drop = [&](auto forward, auto ws) {
+      return forward(mm.masks, mm.m, n, d, mm.nonzeros.data(), mm.masks, heads,
+                     mm.row_indices.data_ptr<int>(), mm.row_offsets.data_ptr<int>(),
+                     mm.column_indices.data_ptr<int>(), dtype, q.t.data_ptr(), q.batch_stride,
+                     q.head_stride, q.row_stride, k.t.data_ptr(), k.batch_stride, k.head_stride,
+                     k.row_stride, v.t.data_ptr(), v.batch_stride, v.head_stride, v.row_stride,
+                     static_cast<float>(scale), o.t.data_ptr(), static_cast<int>(out_type),
+                     o.batch_stride, o.head_stride, o.row_stride,
+                     want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(mm.m), drop->p,
+                     drop->rng, drop->rng_state_out, ws, ws_bytes, current_stream(q.t));
+    };
+    if (drop != nullptr)
+      status = plan.has_value()
+                   ? call_drop(sputnik_hip_sparse_attention_heads_many_mask_forward_planned_dropout,
+                               static_cast<const void*>(plan->data_ptr()))
+                   : call_drop(sputnik_hip_sparse_attention_heads_many_mask_forward_dropout,
+                               workspace.data_ptr());
+    else
+      status = plan.has_value()
+                   ? call(sputnik_hip_sparse_attention_heads_many_mask_forward_planned,
+                          static_cast<const void*>(plan->data_ptr()))
+                   : call(sputnik_hip_sparse_attention_heads_many_mask_forward, workspace.data_ptr());
   }
   if (status == SPUTNIK_HIP_UNSUPPORTED) {
-    TORCH_CHECK(!want_lse, "sparse_attention_heads_many_mask: lse needs a call the fused kernel "
-                "serves (head dimension 64, 16-byte aligned views)");
+    TORCH_CHECK(!want_lse || drop != nullptr, "sparse_attention_heads_many_mask: lse needs a call "
+                "the fused kernel serves (head dimension 64, 16-byte aligned views)");
     // float32 per-head copies [B*H, rows, d] through the many-mask operators
     auto per_head = [&](const HeadOperand& x) {
       return x.t.to(at::kFloat).reshape({x.batch * x.heads, x.rows, x.d});
     };
     const Tensor product = attention_many_mask_composed(b, nonzeros, per_head(q), per_head(k),
                                                         per_head(v), mm.row_indices,
-                                                        mm.row_offsets, mm.column_indices, scale);
+                                                        mm.row_offsets, mm.column_indices, scale, drop);
     out.copy_(product.reshape(out.sizes()));
+    if (drop != nullptr) return {out, Tensor(), drop->rng_state};
     return {out};
   }
   check_status(status, "sparse_attention_heads_many_mask");
+  if (drop != nullptr) return {out, want_lse ? lse : Tensor(), drop->rng_state};
   if (want_lse) return {out, lse};
   return {out};
+}
+
+// The dropout forms of the three ops above: {out, lse, rng_state} (lse undefined on the
+// composed route).
+std::vector<Tensor> sparse_attention_heads_dropout(const Tensor& q, const Tensor& k, const Tensor& v,
+                                                   const Tensor& row_indices, const Tensor& row_offsets,
+                                                   const Tensor& column_indices, double scale,
+                                                   int64_t out_type, double p,
+                                                   const c10::optional<Tensor>& plan) {
+  TORCH_CHECK(p > 0.0 && p < 1.0, "sparse_attention_heads_dropout: p must lie in (0, 1), got ", p);
+  const c10::DeviceGuard guard(q.device());
+  const Drop drop = make_drop(p, c10::nullopt, q);
+  return sparse_attention_heads_run(q, k, v, row_indices, row_offsets, column_indices, scale, out_type,
+                                    true, plan, &drop);
+}
+
+std::vector<Tensor> sparse_attention_many_mask_dropout(int64_t b, const Tensor& nonzeros, const Tensor& q,
+                                                       const Tensor& k, const Tensor& v,
+                                                       const Tensor& row_indices, const Tensor& row_offsets,
+                                                       const Tensor& column_indices, double scale, double p,
+                                                       const c10::optional<Tensor>& plan) {
+  TORCH_CHECK(p > 0.0 && p < 1.0, "sparse_attention_many_mask_dropout: p must lie in (0, 1), got ", p);
+  const c10::DeviceGuard guard(q.device());
+  const Drop drop = make_drop(p, c10::nullopt, q);
+  return sparse_attention_many_mask_run(b, nonzeros, q, k, v, row_indices, row_offsets, column_indices,
+                                        scale, true, plan, &drop);
+}
+
+std::vector<Tensor> sparse_attention_heads_many_mask_dropout(
+    int64_t b, const Tensor& nonzeros, const Tensor& q, const Tensor& k, const Tensor& v,
+    const Tensor& row_indices, const Tensor& row_offsets, const Tensor& column_indices, double scale,
+    int64_t out_type, double p, const c10::optional<Tensor>& plan) {
+  TORCH_CHECK(p > 0.0 && p < 1.0, "sparse_attention_heads_many_mask_dropout: p must lie in (0, 1), got ", p);
+  const c10::DeviceGuard guard(q.device());
+  const Drop drop = make_drop(p, c10::nullopt, q);
+  return sparse_attention_heads_many_mask_run(b, nonzeros, q, k, v, row_indices, row_offsets,
+                                              column_indices, scale, out_type, true, plan, &drop);
+}
+
+// the registered forms without dropout
+std::vector<Tensor> sparse_attention_heads(const Tensor& q, const Tensor& k, const Tensor& v,
+                                           const Tensor& row_indices, const Tensor& row_offsets,
+                                           const Tensor& column_indices, double scale, int64_t out_type,
+                                           bool want_lse, const c10::optional<Tensor>& plan) {
+  return sparse_attention_heads_run(q, k, v, row_indices, row_offsets, column_indices, scale, out_type,
+                                    want_lse, plan);
+}
+
+std::vector<Tensor> sparse_attention_many_mask(int64_t b, const Tensor& nonzeros, const Tensor& q,
+                                               const Tensor& k, const Tensor& v,
+                                               const Tensor& row_indices, const Tensor& row_offsets,
+                                               const Tensor& column_indices, double scale,
+                                               bool want_lse, const c10::optional<Tensor>& plan) {
+  return sparse_attention_many_mask_run(b, nonzeros, q, k, v, row_indices, row_offsets, column_indices,
+                                        scale, want_lse, plan);
+}
+
+std::vector<Tensor> sparse_attention_heads_many_mask(int64_t b, const Tensor& nonzeros, const Tensor& q,
+                                                     const Tensor& k, const Tensor& v,
+                                                     const Tensor& row_indices, const Tensor& row_offsets,
+                                                     const Tensor& column_indices, double scale,
+                                                     int64_t out_type, bool want_lse,
+                                                     const c10::optional<Tensor>& plan) {
+  return sparse_attention_heads_many_mask_run(b, nonzeros, q, k, v, row_indices, row_offsets,
+                                              column_indices, scale, out_type, want_lse, plan);
 }
 
 // Layout pass of the reference's modules (modules/sparse_linear.py:89,
@@ -1993,6 +2243,23 @@ TORCH_LIBRARY(torch_sputnik, m) {
       "sparse_attention_heads_many_mask(int b, Tensor nonzeros, Tensor query, Tensor key, "
       "Tensor value, Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, "
       "int out_type, bool want_lse, Tensor? plan) -> Tensor[]");
+  // attention dropout
+  m.def("sparse_dropout(Tensor values, float p, Tensor? rng_state) -> Tensor[]");
+  m.def(
+      "sparse_attention_dropout(Tensor query, Tensor key, Tensor value, Tensor row_indices, "
+      "Tensor row_offsets, Tensor column_indices, float scale, float p, Tensor? plan) -> Tensor[]");
+  m.def(
+      "sparse_attention_heads_dropout(Tensor query, Tensor key, Tensor value, Tensor row_indices, "
+      "Tensor row_offsets, Tensor column_indices, float scale, int out_type, float p, "
+      "Tensor? plan) -> Tensor[]");
+  m.def(
+      "sparse_attention_many_mask_dropout(int b, Tensor nonzeros, Tensor query, Tensor key, "
+      "Tensor value, Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, "
+      "float p, Tensor? plan) -> Tensor[]");
+  m.def(
+      "sparse_attention_heads_many_mask_dropout(int b, Tensor nonzeros, Tensor query, Tensor key, "
+      "Tensor value, Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, "
+      "int out_type, float p, Tensor? plan) -> Tensor[]");
   m.def("permute_last(Tensor values, Tensor permutation) -> Tensor");
   m.def("permute_last_banded(Tensor values, Tensor dest_list, Tensor source_in_band) -> Tensor");
   m.def("permute_band_size() -> int", &permute_band_size);
@@ -2061,6 +2328,11 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("sparse_attention_many_mask", &sparse_attention_many_mask);
   m.impl("sparse_attention_many_mask_plan", &sparse_attention_many_mask_plan);
   m.impl("sparse_attention_heads_many_mask", &sparse_attention_heads_many_mask);
+  m.impl("sparse_dropout", &sparse_dropout);
+  m.impl("sparse_attention_dropout", &sparse_attention_dropout);
+  m.impl("sparse_attention_heads_dropout", &sparse_attention_heads_dropout);
+  m.impl("sparse_attention_many_mask_dropout", &sparse_attention_many_mask_dropout);
+  m.impl("sparse_attention_heads_many_mask_dropout", &sparse_attention_heads_many_mask_dropout);
   m.impl("permute_last", &permute_last);
   m.impl("permute_last_banded", &permute_last_banded);
   m.impl("spmm_permuted", &spmm_permuted);

@@ -421,6 +421,54 @@ def _attention(query, key, value, row_indices, row_offsets, column_indices, scal
                                         column_indices, scale, plan)
 
 
+def _attention_dropout(query, key, value, row_indices, row_offsets, column_indices, scale, p):
+    """The fused forward with attention dropout p > 0 -> (out, rng_state)."""
+    plan = None if _plans is None else _plans.attention(query.size(-2), key.size(-2), query.size(-1),
+                                                        row_indices, row_offsets, column_indices)
+    out, _, rng_state = ops.sparse_attention_dropout(query, key, value, row_indices, row_offsets,
+                                                     column_indices, scale, p, plan)
+    return out, rng_state
+
+
+# ---------------------------------------------------------------------------
+# Attention dropout (ops.sparse_dropout, csrc/philox.h): the keep decision of entry e of
+# replica r is a function of (seed, offset, r, e) alone, so the fused forward, the composed
+# chain and the backward's replay from the saved rng_state drop the same entries.
+# ---------------------------------------------------------------------------
+def _replay(values, p, rng_state):
+    """values * keep * 1/(1-p) with the mask of `rng_state` (no generator state consumed)."""
+    return ops.sparse_dropout(values, p, rng_state)[0]
+
+
+class SparseDropout(torch.autograd.Function):
+    """Dropout on a sparse values array ([nnz] or [R, width], row r = replica r) with the
+    library's counter-based mask; the backward replays the mask from the saved rng_state:
+    grad * keep * 1/(1-p).  ``apply(values, p)``."""
+
+    @staticmethod
+    def forward(ctx, values, p):
+        out, rng_state = ops.sparse_dropout(values, p)
+        ctx.p = float(p)
+        ctx.save_for_backward(rng_state)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        rng_state, = ctx.saved_tensors
+        return _replay(_contiguous(grad_output), ctx.p, rng_state), None
+
+
+def sparse_dropout(values, p, training=True):
+    """Differentiable dropout of a sparse values array (ops.sparse_dropout): identity when
+    not `training` or p == 0 (nothing drawn then); ValueError for p outside [0, 1)."""
+    p = ops.check_dropout_p(p)
+    if not training or p == 0.0:
+        return values
+    if torch.is_grad_enabled() and values.requires_grad:
+        return SparseDropout.apply(values, p)
+    return ops.sparse_dropout(values, p)[0]
+
+
 class TransposeLast2(torch.autograd.Function):
     """``x.transpose(-1, -2).contiguous()`` as one tiled kernel (ops.transpose_last2):
     the layout pass of modules/sparse_linear.py:89 and
@@ -769,7 +817,7 @@ class SparseSoftmax(torch.autograd.Function):
         return grad_values, None, None, None, None
 
 
-def _attention_backward(query, key, value, topo, scale, grad_output, needs):
+def _attention_backward(query, key, value, topo, scale, grad_output, needs, dropout=None):
     """Gradients of softmax(scale * sddmm(q, k)) @ v for [R, S, D] operands (float32, or one
     half type: the typed operators, float32 scores, weights and gradients): the scores and
     weights are recomputed, then
@@ -779,13 +827,19 @@ def _attention_backward(query, key, value, topo, scale, grad_output, needs):
         dQ = dS k            dK = dS^T q
 
     on the mask and its transpose (one csr_transpose with permutation per call, or the
-    cached transposed topology).  `needs`: which of (dQ, dK, dV) to compute."""
+    cached transposed topology).  `needs`: which of (dQ, dK, dV) to compute.
+    `dropout` = (p, rng_state) of a forward with attention dropout: the mask is replayed,
+    Pd = drop(P), dV = Pd^T dO, dP = drop(sddmm(dO, v)), and the rest is unchanged."""
     row_indices, row_offsets, column_indices = topo
     m, n = query.size(-2), key.size(-2)
     grad_output = _contiguous(grad_output)
     scores = _sddmm(m, n, *topo, query, key)
     weights = ops.sparse_softmax_scaled(scores, *topo, scale)
     grad_weights = _sddmm(m, n, *topo, grad_output, value)
+    kept = weights
+    if dropout is not None:
+        kept = _replay(weights, *dropout)
+        grad_weights = _replay(grad_weights, *dropout)
     grad_scores = ops.sparse_softmax_backward(weights, grad_weights, row_offsets, scale)
     grad_query = grad_key = grad_value = None
     if needs[0]:
@@ -810,7 +864,7 @@ def _attention_backward(query, key, value, topo, scale, grad_output, needs):
         if needs[1]:
             grad_key = transposed_product(grad_scores, query)
         if needs[2]:
-            grad_value = transposed_product(weights, grad_output)
+            grad_value = transposed_product(kept, grad_output)
     return grad_query, grad_key, grad_value
 
 
@@ -825,22 +879,46 @@ class SparseAttentionFunction(torch.autograd.Function):
         dQ = dS k            dK = dS^T q
 
     on the mask and its transpose (one csr_transpose with permutation per call,
-    or the cached transposed topology)."""
+    or the cached transposed topology).  ``dropout_p`` > 0: dropout on the weights in the
+    fused forward (ops.sparse_attention_dropout), replayed by the backward from the saved
+    rng_state."""
 
     @staticmethod
-    def forward(ctx, query, key, value, row_indices, row_offsets, column_indices, scale):
+    def forward(ctx, query, key, value, row_indices, row_offsets, column_indices, scale,
+                dropout_p=0.0):
+        ctx.scale, ctx.p = float(scale), float(dropout_p)
+        if ctx.p > 0.0:
+            out, rng_state = _attention_dropout(query, key, value, row_indices, row_offsets,
+                                                column_indices, scale, ctx.p)
+            ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices,
+                                  rng_state)
+            return out
         out = _attention(query, key, value, row_indices, row_offsets, column_indices, scale)
-        ctx.scale = float(scale)
         ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices)
         return out
 
     @staticmethod
     def backward(ctx, grad_output):
-        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors
+        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors[:6]
+        dropout = (ctx.p, ctx.saved_tensors[6]) if ctx.p > 0.0 else None
         grad_query, grad_key, grad_value = _attention_backward(
             query, key, value, (row_indices, row_offsets, column_indices), ctx.scale, grad_output,
-            ctx.needs_input_grad[:3])
-        return grad_query, grad_key, grad_value, None, None, None, None
+            ctx.needs_input_grad[:3], dropout)
+        return grad_query, grad_key, grad_value, None, None, None, None, None
+
+
+def sparse_attention(query, key, value, row_indices, row_offsets, column_indices, scale,
+                     dropout_p=0.0):
+    """softmax(scale * q k^T at the mask) v for float32 [R, S, D] (or [S, D]) operands, one
+    fused kernel forward; differentiable (SparseAttentionFunction).  ``dropout_p``: dropout
+    on the attention weights (0 <= p < 1; the caller decides when it is training)."""
+    p = ops.check_dropout_p(dropout_p)
+    topo = (row_indices, row_offsets, column_indices)
+    if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
+        return SparseAttentionFunction.apply(query, key, value, *topo, scale, p)
+    if p > 0.0:
+        return _attention_dropout(query, key, value, *topo, scale, p)[0]
+    return _attention(query, key, value, *topo, scale)
 
 
 # ---------------------------------------------------------------------------
@@ -914,10 +992,15 @@ def _heads(x, heads):
     return x.unflatten(-1, (heads, x.size(-1) // heads)).transpose(1, 2)
 
 
-def _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale):
+def _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale, p=0.0):
+    """-> the context [B, S, E]; with p > 0 (dropout on the weights) -> (context, rng_state)."""
     q, k, v = _heads(query, heads), _heads(key, heads), _heads(value, heads)
     plan = None if _plans is None else _plans.attention(q.size(-2), k.size(-2), q.size(-1), row_indices,
                                                         row_offsets, column_indices)
+    if p > 0.0:
+        out, _, rng_state = ops.sparse_attention_heads_dropout(q, k, v, row_indices, row_offsets,
+                                                               column_indices, scale, p, plan=plan)
+        return out.transpose(1, 2).reshape(query.size(0), query.size(1), -1), rng_state
     out = ops.sparse_attention_heads(q, k, v, row_indices, row_offsets, column_indices, scale, plan=plan)
     # (the kernel's buffer is [B, S, H, D]: this is a view)
     return out.transpose(1, 2).reshape(query.size(0), query.size(1), -1)
@@ -931,14 +1014,21 @@ class SparseAttentionHeadsFunction(torch.autograd.Function):
     q and k.)"""
 
     @staticmethod
-    def forward(ctx, query, key, value, heads, row_indices, row_offsets, column_indices, scale):
-        ctx.heads, ctx.scale = int(heads), float(scale)
+    def forward(ctx, query, key, value, heads, row_indices, row_offsets, column_indices, scale,
+                dropout_p=0.0):
+        ctx.heads, ctx.scale, ctx.p = int(heads), float(scale), float(dropout_p)
+        if ctx.p > 0.0:
+            out, rng_state = _attention_heads(query, key, value, heads, row_indices, row_offsets,
+                                              column_indices, scale, ctx.p)
+            ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices, rng_state)
+            return out
         ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices)
         return _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale)
 
     @staticmethod
     def backward(ctx, grad_output):
-        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors
+        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors[:6]
+        dropout = (ctx.p, ctx.saved_tensors[6]) if ctx.p > 0.0 else None
         heads = ctx.heads
 
         def per_head(x):   # [B, S, E] -> [B*H, S, D], contiguous, in the storage type
@@ -946,7 +1036,7 @@ class SparseAttentionHeadsFunction(torch.autograd.Function):
 
         grads = _attention_backward(per_head(query), per_head(key), per_head(value),
                                     (row_indices, row_offsets, column_indices), ctx.scale,
-                                    per_head(grad_output), ctx.needs_input_grad[:3])
+                                    per_head(grad_output), ctx.needs_input_grad[:3], dropout)
 
         def merged(g, like):   # [B*H, S, D] -> [B, S, E] in like's type
             if g is None:
@@ -955,20 +1045,26 @@ class SparseAttentionHeadsFunction(torch.autograd.Function):
                 like.shape).to(like.dtype)
 
         return (merged(grads[0], query), merged(grads[1], key), merged(grads[2], value),
-                None, None, None, None, None)
+                None, None, None, None, None, None)
 
 
-def sparse_attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale):
+def sparse_attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale,
+                           dropout_p=0.0):
     """softmax(scale * q k^T at the mask) v per head for [B, S, E] tensors in float16 /
     bfloat16 (query [B, m, E], key and value [B, n, E], any strides with a unit last one),
     E = heads * D: head h is columns h*D .. h*D+D-1 of every row -- read as strided views by
     the fused kernel (ops.sparse_attention_heads), no head split or merge pass.  Returns the
     context [B, m, E] in the inputs' type (rounded once); scores, weights and sums are
     float32.  Differentiable: the backward recomputes the weights (SparseAttentionHeadsFunction),
-    and the gradient reaches q, k and v."""
+    and the gradient reaches q, k and v.  ``dropout_p``: dropout on the attention weights
+    (replica r = b * heads + h of the library's mask contract)."""
+    p = ops.check_dropout_p(dropout_p)
     if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
         return SparseAttentionHeadsFunction.apply(query, key, value, heads, row_indices, row_offsets,
-                                                  column_indices, scale)
+                                                  column_indices, scale, p)
+    if p > 0.0:
+        return _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices,
+                                scale, p)[0]
     return _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale)
 
 
@@ -1100,7 +1196,7 @@ def _many_mask_composed(b, nonzeros, topo, query, key, value, scale):
                               column_indices, value)
 
 
-def _many_mask_backward(b, nonzeros, topo, query, key, value, scale, grad_output, needs):
+def _many_mask_backward(b, nonzeros, topo, query, key, value, scale, grad_output, needs, dropout=None):
     """Gradients of softmax(scale * sddmm_many_mask(q, k)) @ v for float32 [R, S, D] operands,
     as _attention_backward with the many-mask operators: the weights are recomputed, then
     dV = P^T dO, dP = sddmm(dO, v), dS = softmax'(P, dP), dQ = dS k, dK = dS^T q."""
@@ -1110,6 +1206,10 @@ def _many_mask_backward(b, nonzeros, topo, query, key, value, scale, grad_output
     scores = ops.sddmm_many_mask(b, m, n, nonzeros, *topo, query, key)
     weights = ops.sparse_softmax_many_mask(b, m, nonzeros, scores, *topo, scale)
     grad_weights = ops.sddmm_many_mask(b, m, n, nonzeros, *topo, grad_output, value)
+    kept = weights
+    if dropout is not None:   # (p, rng_state): replay the forward's mask, as _attention_backward
+        kept = _replay(weights, *dropout)
+        grad_weights = _replay(grad_weights, *dropout)
     grad_scores = ops.sparse_softmax_backward_many_mask(b, m, nonzeros, weights, grad_weights,
                                                         row_offsets, scale)
     grad_query = grad_key = grad_value = None
@@ -1123,15 +1223,27 @@ def _many_mask_backward(b, nonzeros, topo, query, key, value, scale, grad_output
         if needs[1]:
             grad_key = ops.spmm_many_mask(b, n, m, nonzeros, grad_t, *topo_t, query)
         if needs[2]:
-            weights_t = ops.csr_transpose_many_mask(b, m, n, nonzeros, weights, row_offsets,
+            weights_t = ops.csr_transpose_many_mask(b, m, n, nonzeros, kept, row_offsets,
                                                     column_indices)[0]
             grad_value = ops.spmm_many_mask(b, n, m, nonzeros, weights_t, *topo_t, grad_output)
     return grad_query, grad_key, grad_value
 
 
-def _many_mask_forward(b, nonzeros, topo, query, key, value, scale):
+def _many_mask_forward(b, nonzeros, topo, query, key, value, scale, p=0.0):
     """[R, S, D] forward: the fused kernel on GPU tensors (the heads kernel for half storage,
-    whose [R, S, D] is a [b, R/b, S, D] head view), the composition elsewhere."""
+    whose [R, S, D] is a [b, R/b, S, D] head view), the composition elsewhere.  With dropout
+    p > 0 -> (out, rng_state)."""
+    if p > 0.0:
+        plan = _many_mask_topology(b, query.size(-2), key.size(-2), query.size(-1), nonzeros, *topo)
+        if query.dtype in (torch.float16, torch.bfloat16):
+            def heads(x):
+                return x.unflatten(0, (b, x.size(0) // b))
+            out, _, rng_state = ops.sparse_attention_heads_many_mask_dropout(
+                b, nonzeros, *topo, heads(query), heads(key), heads(value), scale, p, plan=plan)
+            return out.flatten(0, 1), rng_state
+        out, _, rng_state = ops.sparse_attention_many_mask_dropout(b, nonzeros, *topo, query, key, value,
+                                                                   scale, p, plan=plan)
+        return out, rng_state
     if not query.is_cuda:
         return _many_mask_composed(b, nonzeros, topo, query.float(), key.float(), value.float(),
                                    scale).to(query.dtype)
@@ -1154,25 +1266,31 @@ class SparseAttentionManyMaskFunction(torch.autograd.Function):
     column_indices, query, key, value, scale))."""
 
     @staticmethod
-    def forward(ctx, b, nonzeros, row_indices, row_offsets, column_indices, query, key, value, scale):
-        ctx.b, ctx.nonzeros, ctx.scale = int(b), nonzeros, float(scale)
-        ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices)
-        return _many_mask_forward(ctx.b, nonzeros, (row_indices, row_offsets, column_indices),
-                                  query, key, value, scale)
+    def forward(ctx, b, nonzeros, row_indices, row_offsets, column_indices, query, key, value, scale,
+                dropout_p=0.0):
+        ctx.b, ctx.nonzeros, ctx.scale, ctx.p = int(b), nonzeros, float(scale), float(dropout_p)
+        topo = (row_indices, row_offsets, column_indices)
+        if ctx.p > 0.0:
+            out, rng_state = _many_mask_forward(ctx.b, nonzeros, topo, query, key, value, scale, ctx.p)
+            ctx.save_for_backward(query, key, value, *topo, rng_state)
+            return out
+        ctx.save_for_backward(query, key, value, *topo)
+        return _many_mask_forward(ctx.b, nonzeros, topo, query, key, value, scale)
 
     @staticmethod
     def backward(ctx, grad_output):
-        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors
+        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors[:6]
+        dropout = (ctx.p, ctx.saved_tensors[6]) if ctx.p > 0.0 else None
         grads = _many_mask_backward(ctx.b, ctx.nonzeros, (row_indices, row_offsets, column_indices),
                                     _float_per_replica(query), _float_per_replica(key),
                                     _float_per_replica(value), ctx.scale,
-                                    _float_per_replica(grad_output), ctx.needs_input_grad[5:8])
+                                    _float_per_replica(grad_output), ctx.needs_input_grad[5:8], dropout)
         grads = [None if g is None else g.to(x.dtype) for g, x in zip(grads, (query, key, value))]
-        return (None, None, None, None, None, *grads, None)
+        return (None, None, None, None, None, *grads, None, None)
 
 
 def sparse_attention_many_mask(b, m, n, nonzeros, row_indices, row_offsets, column_indices, query,
-                               key, value, scale):
+                               key, value, scale, dropout_p=0.0):
     """softmax(scale * q k^T at the mask) v with one mask per batch element, for [R, S, D]
     tensors (R = b * heads, replica r under mask r // heads), topology in the many-mask layout
     of tests/transformer/utils.py:17-38 (``topology.dense_to_sparse_3d``), `nonzeros` a host
@@ -1180,13 +1298,17 @@ def sparse_attention_many_mask(b, m, n, nonzeros, row_indices, row_offsets, colu
     fused kernel and the result keeps it (scores, weights and sums float32).  Differentiable:
     the backward recomputes the weights with the many-mask operators, which are float32 only
     (half inputs: float32 copies, gradients returned in the input's type).  Head dimensions
-    other than 64, unaligned operands and CPU tensors take the composed operators."""
+    other than 64, unaligned operands and CPU tensors take the composed operators.
+    ``dropout_p``: dropout on the attention weights (entry e = position inside the mask)."""
     m, n = int(m), int(n)
+    p = ops.check_dropout_p(dropout_p)
     if query.size(-2) != m or key.size(-2) != n:
         raise ValueError(f"expected query rows {m} and key rows {n}, got {query.size(-2)}, {key.size(-2)}")
     topo = (row_indices, row_offsets, column_indices)
     if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
-        return SparseAttentionManyMaskFunction.apply(b, nonzeros, *topo, query, key, value, scale)
+        return SparseAttentionManyMaskFunction.apply(b, nonzeros, *topo, query, key, value, scale, p)
+    if p > 0.0:
+        return _many_mask_forward(int(b), nonzeros, topo, query, key, value, scale, p)[0]
     return _many_mask_forward(int(b), nonzeros, topo, query, key, value, scale)
 
 
@@ -1194,15 +1316,21 @@ class SparseAttentionHeadsManyMaskFunction(torch.autograd.Function):
     """sparse_attention_heads_many_mask under autograd ([B, S, H, D] views)."""
 
     @staticmethod
-    def forward(ctx, query, key, value, nonzeros, row_indices, row_offsets, column_indices, scale):
-        ctx.nonzeros, ctx.scale = nonzeros, float(scale)
-        ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices)
-        return _heads_many_mask_forward(query, key, value, nonzeros,
-                                        (row_indices, row_offsets, column_indices), scale)
+    def forward(ctx, query, key, value, nonzeros, row_indices, row_offsets, column_indices, scale,
+                dropout_p=0.0):
+        ctx.nonzeros, ctx.scale, ctx.p = nonzeros, float(scale), float(dropout_p)
+        topo = (row_indices, row_offsets, column_indices)
+        if ctx.p > 0.0:
+            out, rng_state = _heads_many_mask_forward(query, key, value, nonzeros, topo, scale, ctx.p)
+            ctx.save_for_backward(query, key, value, *topo, rng_state)
+            return out
+        ctx.save_for_backward(query, key, value, *topo)
+        return _heads_many_mask_forward(query, key, value, nonzeros, topo, scale)
 
     @staticmethod
     def backward(ctx, grad_output):
-        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors
+        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors[:6]
+        dropout = (ctx.p, ctx.saved_tensors[6]) if ctx.p > 0.0 else None
         b, heads = query.size(0), query.size(2)
 
         def per_head(x):   # [B, S, H, D] -> [B*H, S, D] float32
@@ -1210,7 +1338,7 @@ class SparseAttentionHeadsManyMaskFunction(torch.autograd.Function):
 
         grads = _many_mask_backward(b, ctx.nonzeros, (row_indices, row_offsets, column_indices),
                                     per_head(query), per_head(key), per_head(value), ctx.scale,
-                                    per_head(grad_output), ctx.needs_input_grad[:3])
+                                    per_head(grad_output), ctx.needs_input_grad[:3], dropout)
 
         def merged(g, like):   # [B*H, S, D] -> [B, S, H, D] in like's type
             if g is None:
@@ -1218,12 +1346,22 @@ class SparseAttentionHeadsManyMaskFunction(torch.autograd.Function):
             return g.reshape(b, heads, like.size(1), -1).transpose(1, 2).to(like.dtype)
 
         return (merged(grads[0], query), merged(grads[1], key), merged(grads[2], value),
-                None, None, None, None, None)
+                None, None, None, None, None, None)
 
 
-def _heads_many_mask_forward(query, key, value, nonzeros, topo, scale):
+def _heads_many_mask_forward(query, key, value, nonzeros, topo, scale, p=0.0):
+    """-> [B, m, H, D]; with dropout p > 0 -> (out, rng_state)."""
     b, heads = query.size(0), query.size(2)
     q, k, v = (x.transpose(1, 2) for x in (query, key, value))   # [B, H, S, D] views
+    if p > 0.0:
+        if query.dtype in (torch.float16, torch.bfloat16):
+            plan = _many_mask_topology(b, q.size(-2), k.size(-2), q.size(-1), nonzeros, *topo)
+            out, _, rng_state = ops.sparse_attention_heads_many_mask_dropout(b, nonzeros, *topo, q, k, v,
+                                                                             scale, p, plan=plan)
+            return out.transpose(1, 2), rng_state
+        per_head = [x.reshape(b * heads, x.size(2), x.size(3)) for x in (q, k, v)]
+        out, rng_state = _many_mask_forward(b, nonzeros, topo, *per_head, scale, p)
+        return out.reshape(b, heads, query.size(1), -1).transpose(1, 2).to(query.dtype), rng_state
     if query.is_cuda:
         if query.dtype in (torch.float16, torch.bfloat16):
             plan = _many_mask_topology(b, q.size(-2), k.size(-2), q.size(-1), nonzeros, *topo)
@@ -1238,14 +1376,18 @@ def _heads_many_mask_forward(query, key, value, nonzeros, topo, scale):
 
 
 def sparse_attention_heads_many_mask(query, key, value, nonzeros, row_indices, row_offsets,
-                                     column_indices, scale):
+                                     column_indices, scale, dropout_p=0.0):
     """The many-mask attention for [B, S, H, D] views (query [B, m, H, D], key and value
     [B, n, H, D], any strides with a unit last one; batch element i under mask i): the layout
     split_tensor_along_last_dim gives (tests/transformer/modules.py:98-111, head stride 3 D),
     read in place by the fused kernel for float16 / bfloat16 -- no copy.  float32 views are
     copied once to [B*H, S, D].  Returns [B, m, H, D] in the inputs' type (a contiguous
-    tensor).  Differentiable as sparse_attention_many_mask."""
+    tensor).  Differentiable as sparse_attention_many_mask; ``dropout_p`` as there (replica
+    r = b * heads + h)."""
+    p = ops.check_dropout_p(dropout_p)
     topo = (row_indices, row_offsets, column_indices)
     if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
-        return SparseAttentionHeadsManyMaskFunction.apply(query, key, value, nonzeros, *topo, scale)
+        return SparseAttentionHeadsManyMaskFunction.apply(query, key, value, nonzeros, *topo, scale, p)
+    if p > 0.0:
+        return _heads_many_mask_forward(query, key, value, nonzeros, topo, scale, p)[0]
     return _heads_many_mask_forward(query, key, value, nonzeros, topo, scale)

@@ -100,13 +100,17 @@ def get_clones(module, num_of_deep_copies):
 class SparseAttention(nn.Module):
     """Multi-head attention whose score matrix only exists at the nonzeros of a
     fixed random mask: SDDMM -> sparse softmax -> SpMM, with four SparseLinear
-    projections."""
+    projections.  ``attention_dropout`` = p: dropout on the attention probabilities (between
+    the softmax and the product with V) while the module is in training mode, on every path:
+    inside the fused kernels' online softmax, or sparse_dropout between the softmax and the
+    SpMM of the separate-operator path (the masks are the same: functional.sparse_dropout)."""
 
     def __init__(self, num_heads, embedding_size, max_sequence_length=512, device=None,
                  sparsity=0.9, mask_generator=None, differentiable_softmax=False,
                  fused_inference=True, low_memory_training=False, fused_training=None,
-                 half_storage=False):
+                 half_storage=False, attention_dropout=0.0):
         super().__init__()
+        self.attention_dropout = ops.check_dropout_p(attention_dropout)
         assert embedding_size % num_heads == 0, \
             "Model dimension must be divisible by the number of heads."
         self.head_dim = embedding_size // num_heads
@@ -156,20 +160,33 @@ class SparseAttention(nn.Module):
         return self._attention3d(self.four_d_to_three_d(query), self.four_d_to_three_d(key),
                                  self.four_d_to_three_d(value))
 
+    def _dropout_p(self):
+        """The attention dropout in force: p in training mode, 0 in eval()."""
+        return self.attention_dropout if self.training else 0.0
+
     def _attention3d(self, q3d, k3d, v3d, merged=False):
         """-> [B*H, S, D]; ``merged``: transposed, [B*H, D, S] (= [B, E, S], the k-major
         operand of the output projection), written that way by the last kernel where
         it can (the SpMM of the separate-operator path), else by a layout pass."""
         scale = 1.0 / math.sqrt(self.head_dim)
+        p = self._dropout_p()
         needs_grad = torch.is_grad_enabled() and (
             q3d.requires_grad or k3d.requires_grad or v3d.requires_grad)
         if self.fused_inference and not needs_grad:
-            out = functional._attention(q3d, k3d, v3d, self.row_indices, self.row_offsets,
-                                        self.column_indices, scale)
+            if p > 0.0:
+                out = functional._attention_dropout(q3d, k3d, v3d, self.row_indices, self.row_offsets,
+                                                    self.column_indices, scale, p)[0]
+            else:
+                out = functional._attention(q3d, k3d, v3d, self.row_indices, self.row_offsets,
+                                            self.column_indices, scale)
             return functional.transpose_last2(out) if merged else out
         if self.low_memory_training:
-            out = SparseAttentionFunction.apply(q3d, k3d, v3d, self.row_indices,
-                                                self.row_offsets, self.column_indices, scale)
+            if p > 0.0:
+                out = SparseAttentionFunction.apply(q3d, k3d, v3d, self.row_indices, self.row_offsets,
+                                                    self.column_indices, scale, p)
+            else:
+                out = SparseAttentionFunction.apply(q3d, k3d, v3d, self.row_indices,
+                                                    self.row_offsets, self.column_indices, scale)
             return functional.transpose_last2(out) if merged else out
 
         # [B*H, nnz]: scores only at the mask's nonzeros
@@ -187,6 +204,8 @@ class SparseAttention(nn.Module):
                    else ops.sparse_softmax_scaled)
         attention_weights = softmax(scores, self.row_indices, self.row_offsets,
                                     self.column_indices, scale)
+        if p > 0.0:   # (between the softmax and the product with V, as Megatron's attention_dropout)
+            attention_weights = functional.sparse_dropout(attention_weights, p)
         # [B*H, S, D] ([B*H, D, S] when merged)
         if merged and ours:
             return Spmm.apply(self.m, self.n, attention_weights, self.row_indices,
@@ -281,7 +300,7 @@ class SparseAttention(nn.Module):
         q, k, v = (project(net, x) for net, x in zip(self.linears, (query, key, value)))
         context = functional.sparse_attention_heads(q, k, v, self.num_heads, self.row_indices,
                                                     self.row_offsets, self.column_indices,
-                                                    1.0 / math.sqrt(self.head_dim))
+                                                    1.0 / math.sqrt(self.head_dim), self._dropout_p())
         return project(self.linears[-1], context)
 
     @staticmethod
@@ -317,12 +336,15 @@ class SparseCoreAttention(nn.Module):
     ONE fused kernel (functional.sparse_attention_heads_many_mask): float16 / bfloat16
     inputs are read in place as head views, float32 inputs are copied once to [b*n, s, hn]
     as the reference does.  ``topology=`` (the tuple topology.dense_to_sparse_3d returns)
-    lets a caller with a static mask skip the per-call conversion; `mask` is then unused."""
+    lets a caller with a static mask skip the per-call conversion; `mask` is then unused.
+    ``attention_dropout`` = p: Megatron's dropout on the attention probabilities, applied in
+    training mode inside the fused kernel (functional.sparse_attention_heads_many_mask)."""
 
-    def __init__(self, seq_length, hidden_size, num_attention_heads):
+    def __init__(self, seq_length, hidden_size, num_attention_heads, attention_dropout=0.0):
         super().__init__()
         if hidden_size % num_attention_heads != 0:
             raise ValueError(f"{hidden_size} is not divisible by {num_attention_heads}")
+        self.attention_dropout = ops.check_dropout_p(attention_dropout)
         self.seq_length = seq_length
         self.hidden_size_per_attention_head = hidden_size // num_attention_heads
 
@@ -332,7 +354,8 @@ class SparseCoreAttention(nn.Module):
         row_indices, row_offsets, column_indices, nonzeros = topology
         b, s = query.size(0), query.size(1)
         scale = 1.0 / math.sqrt(self.hidden_size_per_attention_head)
+        p = self.attention_dropout if self.training else 0.0
         out = functional.sparse_attention_heads_many_mask(query, key, value, nonzeros, row_indices,
-                                                          row_offsets, column_indices, scale)
+                                                          row_offsets, column_indices, scale, p)
         # [b, s, n, hn] -> [s, b, n * hn]
         return out.permute(1, 0, 2, 3).reshape(s, b, -1)

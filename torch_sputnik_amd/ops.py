@@ -486,3 +486,77 @@ def permute_last(values, permutation):
     int32 permutation (a static pattern's transposed order): one kernel, the
     permutation read once for all rows.  float32 out."""
     return _ops.permute_last(values, permutation)
+
+
+# ---------------------------------------------------------------------------
+# attention dropout (csrc/philox.h, sputnik_hip.h "Attention dropout"): entry e of replica r
+# is kept iff Philox4x32-10 word e & 3 of counter (offset/4, e >> 2, r) under key seed is below
+# floor((1 - p) 2^32); kept values are scaled by 1 / (1 - p).  Fresh draws come from the
+# device's default generator (offset + 4 per call, as torch.nn.functional.dropout); every
+# result carries the int64 [2] device tensor rng_state = {seed, offset} that replays it.
+# ---------------------------------------------------------------------------
+def check_dropout_p(p):
+    """0 <= p < 1 as a float, else ValueError."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability must lie in [0, 1), got {p}")
+    return p
+
+
+def sparse_dropout(values, p, rng_state=None):
+    """out = values * keep * 1/(1-p) for a values array [nnz] or [R, width] (row r = replica
+    r; rows may be strided; many-mask arrays at their full [R, max(nonzeros)] width) of
+    float32 / float16 / bfloat16, in values' type.  -> (out, rng_state).  With `rng_state`
+    given the mask is replayed from it and no generator state is consumed.  p = 0 is a copy
+    that draws nothing: rng_state is then None (or the one given)."""
+    p = check_dropout_p(p)
+    out, state = _ops.sparse_dropout(values, p, rng_state)
+    return out, state
+
+
+def _lse(lse):
+    return lse if lse is not None and lse.numel() > 0 else None
+
+
+def sparse_attention_dropout(query, key, value, row_indices, row_offsets, column_indices, scale, p,
+                             plan=None):
+    """sparse_attention with dropout p (0 < p < 1) on the attention weights, one kernel.
+    -> (out, lse, rng_state); lse (of the undropped scores) is None where the call is composed
+    from the operators (SDDMM, scaled softmax, sparse_dropout, SpMM: head dimension other than
+    64)."""
+    out, lse, state = _ops.sparse_attention_dropout(query, key, value, row_indices, row_offsets,
+                                                    column_indices, float(scale), float(p), plan)
+    return out, _lse(lse), state
+
+
+def sparse_attention_heads_dropout(query, key, value, row_indices, row_offsets, column_indices, scale,
+                                   p, out_dtype=None, plan=None):
+    """sparse_attention_heads with dropout p on the weights: r = b * heads + h.
+    -> (out, lse, rng_state) as sparse_attention_dropout."""
+    out_code = _half_code(query.dtype if out_dtype is None else out_dtype)
+    out, lse, state = _ops.sparse_attention_heads_dropout(query, key, value, row_indices, row_offsets,
+                                                          column_indices, float(scale), out_code,
+                                                          float(p), plan)
+    return out, _lse(lse), state
+
+
+def sparse_attention_many_mask_dropout(b, nonzeros, row_indices, row_offsets, column_indices, query,
+                                       key, value, scale, p, plan=None):
+    """sparse_attention_many_mask with dropout p on the weights (e = position inside the mask).
+    -> (out, lse, rng_state) as sparse_attention_dropout."""
+    out, lse, state = _ops.sparse_attention_many_mask_dropout(int(b), _counts(nonzeros), query, key,
+                                                              value, row_indices, row_offsets,
+                                                              column_indices, float(scale), float(p),
+                                                              plan)
+    return out, _lse(lse), state
+
+
+def sparse_attention_heads_many_mask_dropout(b, nonzeros, row_indices, row_offsets, column_indices,
+                                             query, key, value, scale, p, out_dtype=None, plan=None):
+    """sparse_attention_heads_many_mask with dropout p on the weights (r = b * heads + h).
+    -> (out, lse, rng_state) as sparse_attention_dropout."""
+    out_code = _half_code(query.dtype if out_dtype is None else out_dtype)
+    out, lse, state = _ops.sparse_attention_heads_many_mask_dropout(
+        int(b), _counts(nonzeros), query, key, value, row_indices, row_offsets, column_indices,
+        float(scale), out_code, float(p), plan)
+    return out, _lse(lse), state
