@@ -983,6 +983,57 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_many_mask_forward_planned
                              const void* workspace, size_t workspace_bytes,
                              sputnik_hip_stream_t stream);
 
+/*
+ * Fused sparse attention backward: the gradients of sputnik_hip_sparse_attention_forward
+ * (or its _dropout form) for one mask, without any [replicas, nonzeros] intermediate.
+ * With D_i = <dO_i, O_i>, every stored entry (i, j) gives
+ *   p  = exp(scale * <q_i, k_j> - lse_i)      pd = p * keep(r, e) / (1 - p_drop)
+ *   dp = <dO_i, v_j> * keep(r, e) / (1 - p_drop)       ds = p * (dp - D_i) * scale
+ *   dQ_i += ds * k_j     dK_j += ds * q_i     dV_j += pd * dO_i
+ * (keep = 1 and no factor for p = 0).  Arguments:
+ *   m, n, d, nonzeros, replicas, row_indices, row_offsets, column_indices, q, k, v, scale
+ *                  as in the forward; q [m,d], k and v [n,d] per replica.
+ *   t_row_indices, t_row_offsets, t_column_indices, permutation
+ *                  the transposed mask (n rows of query indices; t_row_indices orders its
+ *                  rows, e.g. by length) and the original entry of each of its slots, as
+ *                  sputnik_hip_csr_transpose returns them.  Read only for dK / dV, the
+ *                  permutation only with dropout.
+ *   out, grad_out  the forward's output O and its gradient dO, [m,d] per replica.
+ *   lse            the forward's log-sum-exp [replicas][lse_stride], of the undropped scores.
+ *   grad_q, grad_k, grad_v
+ *                  [m,d], [n,d], [n,d] per replica, each may be NULL when not wanted; every
+ *                  row is written (rows and key columns without entries get zeros).
+ *   p, rng         the forward's dropout p and a state that replays its mask (the
+ *                  forward's rng_state_out as {seed_ptr, offset_ptr}); p = 0: none.
+ *   workspace      at least sputnik_hip_sparse_attention_backward_workspace_bytes, 16-byte
+ *                  aligned, per call (the D_i of every row; nothing is kept between calls).
+ * Strides are per replica, in elements.  Two launches, no atomics (bitwise reproducible),
+ * no host synchronisation.  Served: d = 64, m * 64 * 4 and n * 64 * 4 below 2^32, 16-byte
+ * aligned operands and strides that are multiples of 4
+ * (sputnik_hip_sparse_attention_backward_supported); anything else returns
+ * SPUTNIK_HIP_UNSUPPORTED and the caller composes the backward from the operators.
+ */
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_backward_supported(int m, int n, int d,
+                                                                    int nonzeros);
+
+SPUTNIK_HIP_API size_t sputnik_hip_sparse_attention_backward_workspace_bytes(int m, int n, int d,
+                                                                             int nonzeros,
+                                                                             int replicas);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_backward(int m, int n, int d, int nonzeros,
+                             int replicas, const int* row_indices, const int* row_offsets,
+                             const int* column_indices, const int* t_row_indices,
+                             const int* t_row_offsets, const int* t_column_indices,
+                             const int* permutation, const float* q, int64_t q_stride,
+                             const float* k, int64_t k_stride, const float* v, int64_t v_stride,
+                             float scale, const float* out, int64_t out_stride,
+                             const float* grad_out, int64_t grad_out_stride, const float* lse,
+                             int64_t lse_stride, float* grad_q, int64_t grad_q_stride,
+                             float* grad_k, int64_t grad_k_stride, float* grad_v,
+                             int64_t grad_v_stride, double p, sputnik_hip_philox_state rng,
+                             void* workspace, size_t workspace_bytes,
+                             sputnik_hip_stream_t stream);
+
 /* ------------------------------------------------------------------------
  * "many mask" family: `masks` topologies of the same m x n shape, laid out
  * as tests/transformer/utils.py:17-38 builds them:

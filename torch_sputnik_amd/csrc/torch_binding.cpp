@@ -1331,6 +1331,97 @@ Tensor sparse_attention_planned(const Tensor& q, const Tensor& k, const Tensor& 
                                plan)[0];
 }
 
+// {out, lse} through a plan of sparse_attention_plan: the forward of the fused backward.
+std::vector<Tensor> sparse_attention_with_lse_planned(const Tensor& q, const Tensor& k,
+                                                      const Tensor& v, const Tensor& row_indices,
+                                                      const Tensor& row_offsets,
+                                                      const Tensor& column_indices, double scale,
+                                                      const Tensor& plan) {
+  return sparse_attention_impl(q, k, v, row_indices, row_offsets, column_indices, scale, true,
+                               plan);
+}
+
+// {grad_q, grad_k, grad_v} of the fused attention (sputnik_hip_sparse_attention_backward),
+// empty tensors for those not wanted.  q [R,m,d] / [m,d]; k, v [R,n,d] / [n,d]; out and
+// grad_out as q; lse [R,m] / [m] from the forward.  The transposed mask (t_*, permutation) is
+// needed for grad_k / grad_v only.  p > 0 replays the forward's mask from rng_state.
+std::vector<Tensor> sparse_attention_backward(
+    const Tensor& q_in, const Tensor& k_in, const Tensor& v_in, const Tensor& out_in,
+    const Tensor& grad_out_in, const Tensor& lse_in, const Tensor& row_indices,
+    const Tensor& row_offsets, const Tensor& column_indices,
+    const c10::optional<Tensor>& t_row_indices, const c10::optional<Tensor>& t_row_offsets,
+    const c10::optional<Tensor>& t_column_indices, const c10::optional<Tensor>& permutation,
+    double scale, double p, const c10::optional<Tensor>& rng_state, bool want_q, bool want_k,
+    bool want_v) {
+  const Tensor q = as_float(q_in, "query");
+  const Tensor k = as_float(k_in, "key");
+  const Tensor v = as_float(v_in, "value");
+  const Tensor out = as_float(out_in, "out");
+  const Tensor grad_out = as_float(grad_out_in, "grad_out");
+  const Tensor lse = as_float(lse_in, "lse");
+  TORCH_CHECK(q.dim() == 2 || q.dim() == 3, "expected 2-dim or 3-dim query, got ", q.dim());
+  TORCH_CHECK(k.dim() == q.dim() && v.dim() == q.dim(), "query, key, value must match in dims");
+  TORCH_CHECK(k.sizes() == v.sizes(), "key and value must have one shape");
+  TORCH_CHECK(out.sizes() == q.sizes() && grad_out.sizes() == q.sizes(),
+              "out and grad_out must have the shape of query");
+  TORCH_CHECK(q.size(-1) == k.size(-1), "query and key must have one head dimension");
+  TORCH_CHECK(q.device() == k.device() && q.device() == v.device() &&
+                  q.device() == out.device() && q.device() == grad_out.device() &&
+                  q.device() == lse.device(),
+              "query, key, value, out, grad_out, lse must be on one device");
+  const c10::DeviceGuard guard(q.device());
+  const int m = to_int(q.size(-2), "m"), n = to_int(k.size(-2), "n");
+  const int d = to_int(q.size(-1), "d");
+  const int replicas = q.dim() == 3 ? to_int(q.size(0), "replicas") : 1;
+  TORCH_CHECK(q.dim() == 2 || k.size(0) == replicas, "first dim of query and key must match");
+  TORCH_CHECK(lse.numel() == static_cast<int64_t>(replicas) * m, "lse must hold ", replicas,
+              " x ", m, " values");
+  const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, q);
+  TORCH_CHECK(sputnik_hip_sparse_attention_backward_supported(m, n, d, topo.nonzeros),
+              "sparse_attention_backward: shape not served (head dimension 64, m and n below 2^24)");
+  Topology t{};
+  Tensor perm;
+  if (want_k || want_v) {
+    TORCH_CHECK(t_row_indices.has_value() && t_row_offsets.has_value() &&
+                    t_column_indices.has_value(),
+                "sparse_attention_backward: grad_k / grad_v need the transposed mask");
+    t = check_topology(n, *t_row_indices, *t_row_offsets, *t_column_indices, q);
+    TORCH_CHECK(t.nonzeros == topo.nonzeros, "the transposed mask must hold the mask's entries");
+    if (p > 0.0) {
+      TORCH_CHECK(permutation.has_value(), "sparse_attention_backward: dropout needs the permutation");
+      perm = as_index(*permutation, "permutation", q);
+      TORCH_CHECK(perm.size(0) == topo.nonzeros, "permutation must hold one index per entry");
+    }
+  }
+  TORCH_CHECK(p == 0.0 || (rng_state.has_value() && rng_state->defined()),
+              "sparse_attention_backward: dropout needs the forward's rng_state");
+  const Drop drop = make_drop(p, rng_state, q);
+  Tensor grad_q = want_q ? at::empty_like(q) : at::empty({0}, q.options());
+  Tensor grad_k = want_k ? at::empty_like(k) : at::empty({0}, q.options());
+  Tensor grad_v = want_v ? at::empty_like(v) : at::empty({0}, q.options());
+  const size_t ws_bytes = sputnik_hip_sparse_attention_backward_workspace_bytes(
+      m, n, d, topo.nonzeros, replicas);
+  Tensor workspace = at::empty({static_cast<int64_t>(std::max<size_t>(ws_bytes, 16))},
+                               q.options().dtype(at::kByte));
+  const bool cols = want_k || want_v;
+  const int64_t qs = static_cast<int64_t>(m) * d, ks = static_cast<int64_t>(n) * d;
+  check_status(sputnik_hip_sparse_attention_backward(
+                   m, n, d, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
+                   topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(),
+                   cols ? t.row_indices.data_ptr<int>() : nullptr,
+                   cols ? t.row_offsets.data_ptr<int>() : nullptr,
+                   cols ? t.column_indices.data_ptr<int>() : nullptr,
+                   perm.defined() ? perm.data_ptr<int>() : nullptr, q.data_ptr<float>(), qs,
+                   k.data_ptr<float>(), ks, v.data_ptr<float>(), ks, static_cast<float>(scale),
+                   out.data_ptr<float>(), qs, grad_out.data_ptr<float>(), qs,
+                   lse.data_ptr<float>(), m, want_q ? grad_q.data_ptr<float>() : nullptr, qs,
+                   want_k ? grad_k.data_ptr<float>() : nullptr, ks,
+                   want_v ? grad_v.data_ptr<float>() : nullptr, ks, drop.p, drop.rng,
+                   workspace.data_ptr(), ws_bytes, current_stream(q)),
+               "sparse_attention_backward");
+  return {grad_q, grad_k, grad_v};
+}
+
 // ---- the fused attention on half storage with strided head views (sputnik_hip.h:
 // sparse_attention_heads_*) ----
 struct HeadOperand {
@@ -2175,6 +2266,16 @@ TORCH_LIBRARY(torch_sputnik, m) {
       "sparse_attention_with_lse(Tensor query, Tensor key, Tensor value, Tensor row_indices, "
       "Tensor row_offsets, Tensor column_indices, float scale) -> Tensor[]");
   m.def(
+      "sparse_attention_with_lse_planned(Tensor query, Tensor key, Tensor value, "
+      "Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, Tensor plan) "
+      "-> Tensor[]");
+  m.def(
+      "sparse_attention_backward(Tensor query, Tensor key, Tensor value, Tensor out, "
+      "Tensor grad_out, Tensor lse, Tensor row_indices, Tensor row_offsets, "
+      "Tensor column_indices, Tensor? t_row_indices, Tensor? t_row_offsets, "
+      "Tensor? t_column_indices, Tensor? permutation, float scale, float p, Tensor? rng_state, "
+      "bool want_q, bool want_k, bool want_v) -> Tensor[]");
+  m.def(
       "spmm_plan(int m, int k, int n, Tensor row_indices, Tensor row_offsets, "
       "Tensor column_indices) -> Tensor");
   m.def(
@@ -2299,6 +2400,8 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("sparse_softmax_backward", &sparse_softmax_backward);
   m.impl("sparse_attention", &sparse_attention);
   m.impl("sparse_attention_with_lse", &sparse_attention_with_lse);
+  m.impl("sparse_attention_with_lse_planned", &sparse_attention_with_lse_planned);
+  m.impl("sparse_attention_backward", &sparse_attention_backward);
   m.impl("spmm_plan", &spmm_plan);
   m.impl("spmm_planned", &spmm_planned);
   m.impl("left_spmm_planned", &left_spmm_planned);

@@ -817,6 +817,25 @@ class SparseSoftmax(torch.autograd.Function):
         return grad_values, None, None, None, None
 
 
+def _transposed_topology(m, n, row_offsets, column_indices, probe_values):
+    """(row_indices_t, row_offsets_t, column_indices_t, permutation) of the mask, for both
+    attention backwards: from the transpose cache, or one csr_transpose_with_permutation when
+    the cache is off.  `probe_values`: [..., nnz] values whose first row the transpose carries
+    along when it runs (its result is not used).  A mask without entries has the empty
+    transpose, built here (the transpose and the cache take a row of values, which an empty
+    mask does not have)."""
+    if column_indices.numel() == 0:
+        index = dict(dtype=torch.int32, device=row_offsets.device)
+        return (torch.arange(n, **index), torch.zeros(n + 1, **index),
+                torch.empty(0, **index), torch.empty(0, **index))
+    if _cache is not None:
+        return _cache.lookup(m, n, row_offsets, column_indices, probe_values)
+    _, row_offsets_t, column_indices_t, perm = ops.csr_transpose_with_permutation(
+        m, n, probe_values.reshape(-1, probe_values.shape[-1])[0].contiguous(),
+        row_offsets, column_indices, checked=False)
+    return diffsort(row_offsets_t), row_offsets_t, column_indices_t, perm
+
+
 def _attention_backward(query, key, value, topo, scale, grad_output, needs, dropout=None):
     """Gradients of softmax(scale * sddmm(q, k)) @ v for [R, S, D] operands (float32, or one
     half type: the typed operators, float32 scores, weights and gradients): the scores and
@@ -845,14 +864,8 @@ def _attention_backward(query, key, value, topo, scale, grad_output, needs, drop
     if needs[0]:
         grad_query = _spmm(m, n, grad_scores, *topo, key)
     if needs[1] or needs[2]:
-        if _cache is not None:
-            row_indices_t, row_offsets_t, column_indices_t, perm = _cache.lookup(
-                m, n, row_offsets, column_indices, grad_scores)
-        else:
-            _, row_offsets_t, column_indices_t, perm = ops.csr_transpose_with_permutation(
-                m, n, grad_scores.reshape(-1, grad_scores.shape[-1])[0].contiguous(),
-                row_offsets, column_indices, checked=False)
-            row_indices_t = diffsort(row_offsets_t)
+        row_indices_t, row_offsets_t, column_indices_t, perm = _transposed_topology(
+            m, n, row_offsets, column_indices, grad_scores)
         def transposed_product(values, dense):
             if ops.spmm_permuted_fused(n, m, dense.size(-1), perm.numel()):
                 return ops.spmm_permuted(n, m, values, perm, row_indices_t, row_offsets_t,
@@ -907,14 +920,85 @@ class SparseAttentionFunction(torch.autograd.Function):
         return grad_query, grad_key, grad_value, None, None, None, None, None
 
 
+# ---------------------------------------------------------------------------
+# Fused backward (ops.sparse_attention_backward): the forward keeps its output
+# and row log-sum-exp, the backward runs two kernels over the mask and its cached transpose.
+# ---------------------------------------------------------------------------
+def _attention_lse(query, key, value, row_indices, row_offsets, column_indices, scale, p):
+    """The fused forward that also returns lse -> (out, lse, rng_state or None), through the
+    cached plan of the mask when enabled."""
+    plan = None if _plans is None else _plans.attention(query.size(-2), key.size(-2), query.size(-1),
+                                                        row_indices, row_offsets, column_indices)
+    if p > 0.0:
+        return ops.sparse_attention_dropout(query, key, value, row_indices, row_offsets,
+                                            column_indices, scale, p, plan)
+    if plan is None:
+        out, lse = ops.sparse_attention_with_lse(query, key, value, row_indices, row_offsets,
+                                                 column_indices, scale)
+    else:
+        out, lse = ops.sparse_attention_with_lse_planned(query, key, value, row_indices,
+                                                         row_offsets, column_indices, scale, plan)
+    return out, lse, None
+
+
+def fused_backward_served(query, key, column_indices):
+    """Whether the fused forward and the fused backward both serve these operands: float32,
+    head dimension 64, a mask with entries, offsets within 32 bits.  Elsewhere
+    ``fused_backward=True`` trains on SparseAttentionFunction, as without the flag."""
+    m, n, d, nnz = query.size(-2), key.size(-2), query.size(-1), column_indices.numel()
+    return (query.dtype == torch.float32 and key.dtype == torch.float32 and query.is_cuda
+            and ops.sparse_attention_supported(m, n, d, nnz)
+            and ops.sparse_attention_backward_supported(m, n, d, nnz))
+
+
+class FusedBackwardAttentionFunction(torch.autograd.Function):
+    """softmax(scale * sddmm(q, k)) @ v with the one-kernel forward (keeping its output O and
+    row log-sum-exp) and the fused backward (ops.sparse_attention_backward): with
+    D_i = dO_i . O_i, per entry p = exp(scale q_i.k_j - lse_i), ds = p (dp - D_i) scale,
+    dQ += ds k, dK += ds q, dV += p dO -- two kernels over the mask and its (cached)
+    transpose, nothing of size [R, nnz] at any time.  ``dropout_p`` > 0: the forward's
+    dropout, replayed from the saved rng_state."""
+
+    @staticmethod
+    def forward(ctx, query, key, value, row_indices, row_offsets, column_indices, scale,
+                dropout_p=0.0):
+        ctx.scale, ctx.p = float(scale), float(dropout_p)
+        out, lse, rng_state = _attention_lse(query, key, value, row_indices, row_offsets,
+                                             column_indices, scale, ctx.p)
+        ctx.save_for_backward(query, key, value, out, lse, row_indices, row_offsets,
+                              column_indices, rng_state)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        query, key, value, out, lse, row_indices, row_offsets, column_indices, rng_state = \
+            ctx.saved_tensors
+        needs = tuple(ctx.needs_input_grad[:3])
+        transposed = None
+        if needs[1] or needs[2]:
+            # (the probe row is a broadcast zero, materialised only when a transpose runs)
+            probe = query.new_zeros(()).expand(1, column_indices.numel())
+            transposed = _transposed_topology(query.size(-2), key.size(-2), row_offsets,
+                                              column_indices, probe)
+        grad_query, grad_key, grad_value = ops.sparse_attention_backward(
+            query, key, value, out, _contiguous(grad_output), lse, row_indices, row_offsets,
+            column_indices, transposed, ctx.scale, ctx.p, rng_state, needs)
+        return grad_query, grad_key, grad_value, None, None, None, None, None
+
+
 def sparse_attention(query, key, value, row_indices, row_offsets, column_indices, scale,
-                     dropout_p=0.0):
+                     dropout_p=0.0, fused_backward=False):
     """softmax(scale * q k^T at the mask) v for float32 [R, S, D] (or [S, D]) operands, one
     fused kernel forward; differentiable (SparseAttentionFunction).  ``dropout_p``: dropout
-    on the attention weights (0 <= p < 1; the caller decides when it is training)."""
+    on the attention weights (0 <= p < 1; the caller decides when it is training).
+    ``fused_backward``: the backward runs the two fused kernels
+    (FusedBackwardAttentionFunction) where they serve the operands, and nothing of size
+    [R, nnz] is allocated; elsewhere the composed backward runs as without the flag."""
     p = ops.check_dropout_p(dropout_p)
     topo = (row_indices, row_offsets, column_indices)
     if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
+        if fused_backward and fused_backward_served(query, key, column_indices):
+            return FusedBackwardAttentionFunction.apply(query, key, value, *topo, scale, p)
         return SparseAttentionFunction.apply(query, key, value, *topo, scale, p)
     if p > 0.0:
         return _attention_dropout(query, key, value, *topo, scale, p)[0]

@@ -103,14 +103,19 @@ class SparseAttention(nn.Module):
     projections.  ``attention_dropout`` = p: dropout on the attention probabilities (between
     the softmax and the product with V) while the module is in training mode, on every path:
     inside the fused kernels' online softmax, or sparse_dropout between the softmax and the
-    SpMM of the separate-operator path (the masks are the same: functional.sparse_dropout)."""
+    SpMM of the separate-operator path (the masks are the same: functional.sparse_dropout).
+    ``fused_backward=True``: training runs the fused forward and the fused backward
+    (functional.FusedBackwardAttentionFunction), float32 only."""
 
     def __init__(self, num_heads, embedding_size, max_sequence_length=512, device=None,
                  sparsity=0.9, mask_generator=None, differentiable_softmax=False,
                  fused_inference=True, low_memory_training=False, fused_training=None,
-                 half_storage=False, attention_dropout=0.0):
+                 half_storage=False, attention_dropout=0.0, fused_backward=False):
         super().__init__()
         self.attention_dropout = ops.check_dropout_p(attention_dropout)
+        if half_storage and fused_backward:
+            raise ValueError("fused_backward serves float32 attention only; it cannot be "
+                             "combined with half_storage=True")
         assert embedding_size % num_heads == 0, \
             "Model dimension must be divisible by the number of heads."
         self.head_dim = embedding_size // num_heads
@@ -146,6 +151,11 @@ class SparseAttention(nn.Module):
         # float16 / bfloat16 inputs (all three of one type) stay in that type through the
         # forward pass: see _forward_half_storage.  Off: today's widening path.
         self.half_storage = bool(half_storage)
+        # Training on the fused forward and the fused backward: nothing of
+        # size [B*H, nnz] exists at any time, the backward included.  Takes precedence over
+        # low_memory_training; shapes the fused backward does not serve (head dimension other
+        # than 64) train as low_memory_training does.
+        self.fused_backward = bool(fused_backward)
 
     @property
     def fused_training(self):   # the flag's name in rounds 1-3
@@ -179,6 +189,11 @@ class SparseAttention(nn.Module):
             else:
                 out = functional._attention(q3d, k3d, v3d, self.row_indices, self.row_offsets,
                                             self.column_indices, scale)
+            return functional.transpose_last2(out) if merged else out
+        if self.fused_backward and needs_grad:
+            out = functional.sparse_attention(q3d, k3d, v3d, self.row_indices, self.row_offsets,
+                                              self.column_indices, scale, dropout_p=p,
+                                              fused_backward=True)
             return functional.transpose_last2(out) if merged else out
         if self.low_memory_training:
             if p > 0.0:

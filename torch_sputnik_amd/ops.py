@@ -425,6 +425,45 @@ def sparse_attention_planned(query, key, value, row_indices, row_offsets, column
                                          column_indices, float(scale), plan)
 
 
+def sparse_attention_with_lse_planned(query, key, value, row_indices, row_offsets, column_indices,
+                                      scale, plan):
+    """sparse_attention_with_lse through a plan of sparse_attention_plan -> [out, lse]."""
+    return _ops.sparse_attention_with_lse_planned(query, key, value, row_indices, row_offsets,
+                                                  column_indices, float(scale), plan)
+
+
+def sparse_attention_supported(m, n, d, nonzeros):
+    """True where the fused forward (sparse_attention*, with lse) serves the shape: head
+    dimension 64 and a mask with entries."""
+    from . import capi
+    return bool(capi.lib().sputnik_hip_sparse_attention_supported(int(m), int(n), int(d),
+                                                                  int(nonzeros)))
+
+
+def sparse_attention_backward_supported(m, n, d, nonzeros):
+    """True where sparse_attention_backward serves the shape (head dimension 64, 32-bit offsets)."""
+    from . import capi
+    return bool(capi.lib().sputnik_hip_sparse_attention_backward_supported(
+        int(m), int(n), int(d), int(nonzeros)))
+
+
+def sparse_attention_backward(query, key, value, out, grad_out, lse, row_indices, row_offsets,
+                              column_indices, transposed, scale, p=0.0, rng_state=None,
+                              needs=(True, True, True)):
+    """Gradients (dQ, dK, dV) of the fused attention, two kernels and nothing of size
+    [R, nnz]: `out` and `lse` from the forward (sparse_attention_with_lse or
+    sparse_attention_dropout), `grad_out` the gradient of out.  `transposed` =
+    (row_indices_t, row_offsets_t, column_indices_t, permutation) of the mask, as
+    csr_transpose_with_permutation and diffsort give them; it may be None when neither dK nor
+    dV is wanted.  p > 0: the forward's dropout, replayed from its rng_state.  `needs` picks
+    which of the three are computed; the others come back as None."""
+    t = transposed if transposed is not None else (None, None, None, None)
+    grads = _ops.sparse_attention_backward(query, key, value, out, grad_out, lse, row_indices,
+                                           row_offsets, column_indices, *t, float(scale),
+                                           float(p), rng_state, *(bool(x) for x in needs))
+    return tuple(g if want else None for g, want in zip(grads, needs))
+
+
 def sparse_attention_heads(query, key, value, row_indices, row_offsets, column_indices, scale,
                            out_dtype=None, with_lse=False, plan=None):
     """The fused attention on float16 / bfloat16 storage, operands as strided head views:
