@@ -753,263 +753,38 @@ bool heads_served(int m, int n, int d, int nonzeros, int batch, int heads, int d
 
 using namespace sputnik_hip;
 
-extern "C" {
-
-int sputnik_hip_sparse_attention_supported(int m, int n, int d, int nonzeros) {
-  return supported(m, n, d, nonzeros) ? 1 : 0;
-}
-
-size_t sputnik_hip_sparse_attention_workspace_bytes(int m, int n, int d, int nonzeros) {
-  if (!supported(m, n, d, nonzeros)) return 0;
-  return row_ok_bytes(slots_of(m)) +
-         sizeof(int) * static_cast<size_t>(chunks_of(n) + 1) * slots_of(m);
-}
-
-namespace {
-
-int attention_exec(int m, int n, int d, int nonzeros, int replicas, const int* row_indices,
-                   const int* row_offsets, const int* column_indices, const float* q,
-                   int64_t q_stride, const float* k, int64_t k_stride, const float* v,
-                   int64_t v_stride, float scale, float* out, int64_t out_stride, float* lse,
-                   int64_t lse_stride, void* workspace, size_t workspace_bytes, bool planned,
-                   hipStream_t stream, const DropArgs* drop = nullptr) {
-  if (m < 0 || n < 0 || d < 0 || nonzeros < 0 || replicas < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (m == 0 || replicas == 0) return drop != nullptr ? publish_rng_state(*drop, stream) : 0;
-  if (nonzeros == 0 || n == 0) {  // every row is empty: zeros (and -inf log-sum-exp)
-    if (drop != nullptr) {
-      const int e = publish_rng_state(*drop, stream);
-      if (e != 0) return e;
-    }
-    for (int r = 0; r < replicas; ++r) {
-      hipError_t e = hipMemsetAsync(out + r * out_stride, 0, sizeof(float) * m * d, stream);
-      if (e != hipSuccess) return static_cast<int>(e);
-      if (lse != nullptr) {
-        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lse + r * lse_stride),
-                              static_cast<int>(0xff800000u), m, stream);
-        if (e != hipSuccess) return static_cast<int>(e);
-      }
-    }
-    return 0;
-  }
-  if (!supported(m, n, d, nonzeros) || !aligned_to(q, 16) || !aligned_to(k, 16) ||
-      !aligned_to(v, 16) || !aligned_to(out, 16) || q_stride % 4 != 0 || k_stride % 4 != 0 ||
-      v_stride % 4 != 0 || out_stride % 4 != 0)
-    return SPUTNIK_HIP_UNSUPPORTED;
-  if (workspace == nullptr || !aligned_to(workspace, 16) ||
-      workspace_bytes < sputnik_hip_sparse_attention_workspace_bytes(m, n, d, nonzeros))
-    return SPUTNIK_HIP_INVALID_ARGUMENT;
-  const int slots = slots_of(m), nchunks = chunks_of(n);
-  int* row_ok = static_cast<int*>(workspace);
-  int* table = reinterpret_cast<int*>(static_cast<char*>(workspace) + row_ok_bytes(slots));
-  int st = 0;
-  if (!planned) {
-    hipLaunchKernelGGL((spmm_chunk_table_kernel<kBK>), dim3(ceil_div(slots, 4)),
-                       dim3(256), 0, stream, m, n, slots, kBM, nchunks, row_indices, row_offsets,
-                       column_indices, table, row_ok);
-    st = launch_status();
-    if (st != 0) return st;
-  }
-  for (int r0 = 0; r0 < replicas; r0 += kMaxGridYZ) {
-    const int ry = min(replicas - r0, kMaxGridYZ);
-    if (drop != nullptr) {
-      DropArgs dr = *drop;   // replica numbers continue over the launches; the first publishes
-      dr.replica0 = r0;
-      if (r0 > 0) dr.rng_state_out = nullptr;
-      hipLaunchKernelGGL((sparse_attention_kernel<false, DropArgs>), dim3(slots / kBM, ry), dim3(kThreads), 0,
-                         stream, m, n, nonzeros, slots, nchunks, row_indices, row_offsets,
-                         column_indices, table, row_ok, q + r0 * q_stride, q_stride, k + r0 * k_stride,
-                         k_stride, v + r0 * v_stride, v_stride, scale, out + r0 * out_stride, out_stride,
-                         lse != nullptr ? lse + r0 * lse_stride : nullptr, lse_stride, dr);
-    } else {
-    hipLaunchKernelGGL(sparse_attention_kernel<false>, dim3(slots / kBM, ry), dim3(kThreads), 0, stream,
-                       m, n, nonzeros, slots, nchunks, row_indices, row_offsets, column_indices,
-                       table, row_ok, q + r0 * q_stride, q_stride, k + r0 * k_stride, k_stride,
-                       v + r0 * v_stride, v_stride, scale, out + r0 * out_stride, out_stride,
-                       lse != nullptr ? lse + r0 * lse_stride : nullptr, lse_stride);
-    }
-    st = launch_status();
-    if (st != 0) return st;
-  }
-  return 0;
-}
-
-}  // namespace
-
-int sputnik_hip_sparse_attention_forward(int m, int n, int d, int nonzeros, int replicas,
-                                         const int* row_indices, const int* row_offsets,
-                                         const int* column_indices, const float* q,
-                                         int64_t q_stride, const float* k, int64_t k_stride,
-                                         const float* v, int64_t v_stride, float scale,
-                                         float* out, int64_t out_stride, float* lse,
-                                         int64_t lse_stride, void* workspace,
-                                         size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  return attention_exec(m, n, d, nonzeros, replicas, row_indices, row_offsets, column_indices, q,
-                        q_stride, k, k_stride, v, v_stride, scale, out, out_stride, lse,
-                        lse_stride, workspace, workspace_bytes, /*planned=*/false, stream);
-}
-
-int sputnik_hip_sparse_attention_plan(int m, int n, int d, int nonzeros, const int* row_indices,
-                                      const int* row_offsets, const int* column_indices,
-                                      void* workspace, size_t workspace_bytes,
-                                      sputnik_hip_stream_t stream) {
-  if (m < 0 || n < 0 || d < 0 || nonzeros < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (!supported(m, n, d, nonzeros)) return SPUTNIK_HIP_UNSUPPORTED;
-  if (workspace == nullptr || !aligned_to(workspace, 16) ||
-      workspace_bytes < sputnik_hip_sparse_attention_workspace_bytes(m, n, d, nonzeros))
-    return SPUTNIK_HIP_INVALID_ARGUMENT;
-  const int slots = slots_of(m);
-  int* row_ok = static_cast<int*>(workspace);
-  int* table = reinterpret_cast<int*>(static_cast<char*>(workspace) + row_ok_bytes(slots));
-  hipLaunchKernelGGL((spmm_chunk_table_kernel<kBK>), dim3(ceil_div(slots, 4)), dim3(256),
-                     0, stream, m, n, slots, kBM, chunks_of(n), row_indices, row_offsets,
-                     column_indices, table, row_ok);
-  return launch_status();
-}
-
-int sputnik_hip_sparse_attention_forward_planned(
-    int m, int n, int d, int nonzeros, int replicas, const int* row_indices,
-    const int* row_offsets, const int* column_indices, const float* q, int64_t q_stride,
-    const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
-    int64_t out_stride, float* lse, int64_t lse_stride, const void* workspace,
-    size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  return attention_exec(m, n, d, nonzeros, replicas, row_indices, row_offsets, column_indices, q,
-                        q_stride, k, k_stride, v, v_stride, scale, out, out_stride, lse,
-                        lse_stride, const_cast<void*>(workspace), workspace_bytes,
-                        /*planned=*/true, stream);
-}
-
-}  // extern "C"
-
-namespace {
-
-template <typename T, typename TO>
-void launch_heads(dim3 grid, hipStream_t stream, int m, int n, int nonzeros, int slots, int nchunks,
-                  int heads, int replica0, const int* row_indices, const int* row_offsets,
-                  const int* column_indices, const int* table, const int* row_ok, const HeadView& q,
-                  const HeadView& k, const HeadView& v, float scale, const HeadView& o, float* lse,
-                  int64_t lse_stride, const DropArgs* drop) {
-  if (drop != nullptr) {
-    DropArgs dr = *drop;   // (the kernel numbers its replicas from replica0 itself)
-    if (replica0 > 0) dr.rng_state_out = nullptr;
-    hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, false, DropArgs>), grid, dim3(kThreads), 0, stream,
-                       m, n, nonzeros, slots, nchunks, heads, replica0, row_indices, row_offsets,
-                       column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride, dr);
-    return;
-  }
-  hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, false>), grid, dim3(kThreads), 0, stream, m, n,
-                     nonzeros, slots, nchunks, heads, replica0, row_indices, row_offsets,
-                     column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride);
-}
-
-int heads_exec(int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
-               const int* row_offsets, const int* column_indices, int dtype, const HeadView& q,
-               const HeadView& k, const HeadView& v, float scale, const HeadView& o, int out_type,
-               float* lse, int64_t lse_stride, void* workspace, size_t workspace_bytes, bool planned,
-               hipStream_t stream, const DropArgs* drop = nullptr) {
-  if (m < 0 || n < 0 || d < 0 || nonzeros < 0 || batch < 0 || heads < 0)
-    return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (m == 0 || batch == 0 || heads == 0) return drop != nullptr ? publish_rng_state(*drop, stream) : 0;
-  if (!heads_served(m, n, d, nonzeros, batch, heads, dtype, out_type, q, k, v, o))
-    return SPUTNIK_HIP_UNSUPPORTED;
-  if (workspace == nullptr || !aligned_to(workspace, 16) ||
-      workspace_bytes < sputnik_hip_sparse_attention_workspace_bytes(m, n, d, nonzeros))
-    return SPUTNIK_HIP_INVALID_ARGUMENT;
-  const int slots = slots_of(m), nchunks = chunks_of(n);
-  int* row_ok = static_cast<int*>(workspace);
-  int* table = reinterpret_cast<int*>(static_cast<char*>(workspace) + row_ok_bytes(slots));
-  int st = 0;
-  if (!planned) {
-    hipLaunchKernelGGL((spmm_chunk_table_kernel<kBK>), dim3(ceil_div(slots, 4)), dim3(256), 0, stream,
-                       m, n, slots, kBM, nchunks, row_indices, row_offsets, column_indices, table,
-                       row_ok);
-    st = launch_status();
-    if (st != 0) return st;
-  }
-  const int replicas = batch * heads;
-  for (int r0 = 0; r0 < replicas; r0 += kMaxGridYZ) {
-    const dim3 grid(slots / kBM, min(replicas - r0, kMaxGridYZ));
-#define SPUTNIK_HIP_HEADS(T, TO)                                                                  \
-  launch_heads<T, TO>(grid, stream, m, n, nonzeros, slots, nchunks, heads, r0, row_indices,       \
-                      row_offsets, column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride, \
-                      drop)
-    if (dtype == SPUTNIK_HIP_F16 && out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS(_Float16, float);
-    else if (dtype == SPUTNIK_HIP_F16) SPUTNIK_HIP_HEADS(_Float16, _Float16);
-    else if (out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS(__bf16, float);
-    else SPUTNIK_HIP_HEADS(__bf16, __bf16);
-#undef SPUTNIK_HIP_HEADS
-    st = launch_status();
-    if (st != 0) return st;
-  }
-  return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int sputnik_hip_sparse_attention_heads_supported(
-    int m, int n, int d, int nonzeros, int batch, int heads, int dtype, int out_type, const void* q,
-    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
-    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
-    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, const void* out,
-    int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride) {
-  return heads_served(m, n, d, nonzeros, batch, heads, dtype, out_type,
-                      HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
-                      HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
-                      HeadView{v, v_batch_stride, v_head_stride, v_row_stride},
-                      HeadView{out, out_batch_stride, out_head_stride, out_row_stride})
-             ? 1 : 0;
-}
-
-size_t sputnik_hip_sparse_attention_heads_workspace_bytes(int m, int n, int d, int nonzeros) {
-  return sputnik_hip_sparse_attention_workspace_bytes(m, n, d, nonzeros);
-}
-
-int sputnik_hip_sparse_attention_heads_forward(
-    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
-    const int* row_offsets, const int* column_indices, int dtype, const void* q,
-    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
-    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
-    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
-    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
-    float* lse, int64_t lse_stride, void* workspace, size_t workspace_bytes,
-    sputnik_hip_stream_t stream) {
-  return heads_exec(m, n, d, nonzeros, batch, heads, row_indices, row_offsets, column_indices, dtype,
-                    HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
-                    HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
-                    HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
-                    HeadView{out, out_batch_stride, out_head_stride, out_row_stride}, out_type, lse,
-                    lse_stride, workspace, workspace_bytes, /*planned=*/false, stream);
-}
-
-int sputnik_hip_sparse_attention_heads_forward_planned(
-    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
-    const int* row_offsets, const int* column_indices, int dtype, const void* q,
-    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
-    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
-    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
-    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
-    float* lse, int64_t lse_stride, const void* workspace, size_t workspace_bytes,
-    sputnik_hip_stream_t stream) {
-  return heads_exec(m, n, d, nonzeros, batch, heads, row_indices, row_offsets, column_indices, dtype,
-                    HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
-                    HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
-                    HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
-                    HeadView{out, out_batch_stride, out_head_stride, out_row_stride}, out_type, lse,
-                    lse_stride, const_cast<void*>(workspace), workspace_bytes, /*planned=*/true,
-                    stream);
-}
-
-}  // extern "C"
-
 // ---------------------------------------------------------------------------
-// Many masks (sputnik_hip.h, "many mask" family): one topology per batch element, all of
-// them served by ONE pre-pass launch and ONE attention launch.
+// Host side.  Every forward entry point (operand layout x mask layout x planned x dropout)
+// fills one ForwardCall and goes through forward(): the checks, the pre-pass and the loop
+// over grid slices are written once, launch() picks the kernel instance.
 // ---------------------------------------------------------------------------
 namespace {
 
-// Bytes of one mask's plan region (mask_plan_ints).
-size_t mask_plan_bytes(int m, int n) {
+struct ForwardCall {
+  bool many;             // one mask per batch element (`masks` of them), else one for every replica
+  bool half;             // operands are head views of `dtype`, else float32 with heads = 1
+  int masks;
+  const int* nonzeros;   // [masks], or the address of the single mask's count
+  int m, n, d, batch, heads;   // float32 operands: batch = replicas
+  const int *row_indices, *row_offsets, *column_indices;
+  int dtype, out_type;
+  HeadView q, k, v, o;   // float32 operands: the base and, in `batch`, the replica stride
+  float scale;
+  float* lse;
+  int64_t lse_stride;
+  void* workspace;
+  size_t workspace_bytes;
+  bool planned;          // the workspace holds the pre-pass results already
+  hipStream_t stream;
+  const DropArgs* drop;
+};
+
+struct Plan {   // the workspace as the kernels read it
+  int slots, nchunks;
+  const int *row_ok, *table;
+};
+
+size_t mask_plan_bytes(int m, int n) {   // one mask's region of a many-mask plan
   return sizeof(int) * static_cast<size_t>(mask_plan_ints(slots_of(m), chunks_of(n)));
 }
 
@@ -1038,106 +813,394 @@ size_t many_mask_workspace(int masks, int m, int n, int d, int largest) {
   return static_cast<size_t>(masks) * mask_plan_bytes(m, n);
 }
 
-int many_mask_plan_exec(int masks, int m, int n, const int* row_indices, const int* row_offsets,
-                        const int* column_indices, void* workspace, hipStream_t stream) {
+size_t plan_bytes(int m, int n, int d, int nonzeros) {
+  if (!supported(m, n, d, nonzeros)) return 0;
+  return row_ok_bytes(slots_of(m)) + sizeof(int) * static_cast<size_t>(chunks_of(n) + 1) * slots_of(m);
+}
+
+// The topology-only pre-pass: row_ok and the chunk table, one region per mask.
+int prepass(bool many, int masks, int m, int n, const int* row_indices, const int* row_offsets,
+            const int* column_indices, void* workspace, hipStream_t stream) {
   const int slots = slots_of(m);
   int* row_ok = static_cast<int*>(workspace);
   int* table = reinterpret_cast<int*>(static_cast<char*>(workspace) + row_ok_bytes(slots));
-  hipLaunchKernelGGL((spmm_chunk_table_masks_kernel<kBK>), dim3(ceil_div(slots, 4), masks), dim3(256),
-                     0, stream, m, n, slots, kBM, chunks_of(n), row_indices, row_offsets,
-                     column_indices, table, row_ok,
-                     static_cast<int64_t>(mask_plan_bytes(m, n) / sizeof(int)));
-  return launch_status();
-}
-
-int attention_many_mask_exec(int masks, int m, int n, int d, const int* nonzeros, int replicas,
-                             const int* row_indices, const int* row_offsets,
-                             const int* column_indices, const float* q, int64_t q_stride,
-                             const float* k, int64_t k_stride, const float* v, int64_t v_stride,
-                             float scale, float* out, int64_t out_stride, float* lse,
-                             int64_t lse_stride, void* workspace, size_t workspace_bytes,
-                             bool planned, hipStream_t stream, const DropArgs* drop = nullptr) {
-  int largest = 0;
-  int st = many_mask_args(masks, m, n, d, nonzeros, replicas, &largest);
-  if (st != 0) return st;
-  if (m == 0 || replicas == 0) return drop != nullptr ? publish_rng_state(*drop, stream) : 0;
-  if (!many_mask_supported(masks, m, n, d, largest, replicas) || !aligned_to(q, 16) || !aligned_to(k, 16) ||
-      !aligned_to(v, 16) || !aligned_to(out, 16) || q_stride % 4 != 0 || k_stride % 4 != 0 ||
-      v_stride % 4 != 0 || out_stride % 4 != 0)
-    return SPUTNIK_HIP_UNSUPPORTED;
-  if (workspace == nullptr || !aligned_to(workspace, 16) ||
-      workspace_bytes < many_mask_workspace(masks, m, n, d, largest))
-    return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (!planned) {
-    st = many_mask_plan_exec(masks, m, n, row_indices, row_offsets, column_indices, workspace, stream);
-    if (st != 0) return st;
-  }
-  const int slots = slots_of(m), nchunks = chunks_of(n);
-  const int* row_ok = static_cast<const int*>(workspace);
-  const int* table = reinterpret_cast<const int*>(static_cast<const char*>(workspace) + row_ok_bytes(slots));
-  if (drop != nullptr)
-    hipLaunchKernelGGL((sparse_attention_kernel<true, DropArgs>), dim3(slots / kBM, replicas), dim3(kThreads),
-                       0, stream, m, n, replicas / masks, slots, nchunks, row_indices, row_offsets,
-                       column_indices, table, row_ok, q, q_stride, k, k_stride, v, v_stride, scale,
-                       out, out_stride, lse, lse_stride, *drop);
+  if (many)
+    hipLaunchKernelGGL((spmm_chunk_table_masks_kernel<kBK>), dim3(ceil_div(slots, 4), masks), dim3(256),
+                       0, stream, m, n, slots, kBM, chunks_of(n), row_indices, row_offsets,
+                       column_indices, table, row_ok,
+                       static_cast<int64_t>(mask_plan_bytes(m, n) / sizeof(int)));
   else
-  hipLaunchKernelGGL(sparse_attention_kernel<true>, dim3(slots / kBM, replicas), dim3(kThreads), 0,
-                     stream, m, n, replicas / masks, slots, nchunks, row_indices, row_offsets,
-                     column_indices, table, row_ok, q, q_stride, k, k_stride, v, v_stride, scale, out,
-                     out_stride, lse, lse_stride);
+    hipLaunchKernelGGL((spmm_chunk_table_kernel<kBK>), dim3(ceil_div(slots, 4)), dim3(256), 0, stream,
+                       m, n, slots, kBM, chunks_of(n), row_indices, row_offsets, column_indices, table,
+                       row_ok);
   return launch_status();
 }
 
-int heads_many_mask_exec(int masks, int m, int n, int d, const int* nonzeros, int batch, int heads,
-                         const int* row_indices, const int* row_offsets, const int* column_indices,
-                         int dtype, const HeadView& q, const HeadView& k, const HeadView& v,
-                         float scale, const HeadView& o, int out_type, float* lse,
-                         int64_t lse_stride, void* workspace, size_t workspace_bytes, bool planned,
-                         hipStream_t stream, const DropArgs* drop = nullptr) {
-  if (batch < 0 || heads < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (static_cast<int64_t>(batch) * heads >= (int64_t{1} << 31)) return SPUTNIK_HIP_UNSUPPORTED;
-  if (batch != masks) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  int largest = 0;
-  int st = many_mask_args(masks, m, n, d, nonzeros, batch * heads, &largest);
-  if (st != 0) return st;
-  if (m == 0 || heads == 0) return drop != nullptr ? publish_rng_state(*drop, stream) : 0;
-  if (!many_mask_supported(masks, m, n, d, largest, batch * heads) ||
-      !heads_served(m, n, d, max(largest, 1), batch, heads, dtype, out_type, q, k, v, o))
-    return SPUTNIK_HIP_UNSUPPORTED;
-  if (workspace == nullptr || !aligned_to(workspace, 16) ||
-      workspace_bytes < many_mask_workspace(masks, m, n, d, largest))
+// Replicas r0 .. r0 + count - 1 of a float32 call: the pointers advance to replica r0.  The
+// many-mask kernel takes the replicas per mask in the `nonzeros` slot.
+template <bool MANY, typename... Drop>
+void launch_float(const ForwardCall& c, const Plan& p, int r0, int count, Drop... drop) {
+  auto at = [r0](const HeadView& w) {
+    return const_cast<float*>(static_cast<const float*>(w.base)) + r0 * w.batch;
+  };
+  hipLaunchKernelGGL((sparse_attention_kernel<MANY, Drop...>), dim3(p.slots / kBM, count), dim3(kThreads), 0,
+                     c.stream, c.m, c.n, MANY ? c.batch / c.masks : *c.nonzeros, p.slots, p.nchunks,
+                     c.row_indices, c.row_offsets, c.column_indices, p.table, p.row_ok, at(c.q), c.q.batch,
+                     at(c.k), c.k.batch, at(c.v), c.v.batch, c.scale, at(c.o), c.o.batch,
+                     c.lse != nullptr ? c.lse + r0 * c.lse_stride : nullptr, c.lse_stride, drop...);
+}
+
+// ... of a half call: the views stay, the kernel numbers its replicas from r0 itself.  The
+// many-mask kernel reads neither `nonzeros` nor `replica0`.
+template <typename T, typename TO, bool MANY, typename... Drop>
+void launch_heads(const ForwardCall& c, const Plan& p, int r0, int count, Drop... drop) {
+  hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, MANY, Drop...>), dim3(p.slots / kBM, count),
+                     dim3(kThreads), 0, c.stream, c.m, c.n, MANY ? 0 : *c.nonzeros, p.slots, p.nchunks,
+                     c.heads, r0, c.row_indices, c.row_offsets, c.column_indices, p.table, p.row_ok, c.q,
+                     c.k, c.v, c.scale, c.o, c.lse, c.lse_stride, drop...);
+}
+
+// Picks the kernel instance from (half, dtype, out_type, many, drop != nullptr) and launches it.
+void launch(const ForwardCall& c, const Plan& p, int r0, int count) {
+  auto pick = [&](auto many, auto... drop) {
+    constexpr bool MANY = decltype(many)::value;
+    if (!c.half) launch_float<MANY>(c, p, r0, count, drop...);
+    else if (c.dtype == SPUTNIK_HIP_F16 && c.out_type == SPUTNIK_HIP_F32)
+      launch_heads<_Float16, float, MANY>(c, p, r0, count, drop...);
+    else if (c.dtype == SPUTNIK_HIP_F16) launch_heads<_Float16, _Float16, MANY>(c, p, r0, count, drop...);
+    else if (c.out_type == SPUTNIK_HIP_F32) launch_heads<__bf16, float, MANY>(c, p, r0, count, drop...);
+    else launch_heads<__bf16, __bf16, MANY>(c, p, r0, count, drop...);
+  };
+  if (c.drop == nullptr) {
+    if (c.many) pick(std::true_type{});
+    else pick(std::false_type{});
+    return;
+  }
+  DropArgs dr = *c.drop;   // replica numbers continue over the launches; the first publishes
+  if (!c.half) dr.replica0 = r0;
+  if (r0 > 0) dr.rng_state_out = nullptr;
+  if (c.many) pick(std::true_type{}, dr);
+  else pick(std::false_type{}, dr);
+}
+
+// A float32 single-mask call whose every row is empty: zeros (and -inf log-sum-exp).
+int fill_empty(const ForwardCall& c) {
+  if (c.drop != nullptr) {
+    const int e = publish_rng_state(*c.drop, c.stream);
+    if (e != 0) return e;
+  }
+  float* out = const_cast<float*>(static_cast<const float*>(c.o.base));
+  for (int r = 0; r < c.batch; ++r) {
+    hipError_t e = hipMemsetAsync(out + r * c.o.batch, 0, sizeof(float) * c.m * c.d, c.stream);
+    if (e != hipSuccess) return static_cast<int>(e);
+    if (c.lse != nullptr) {
+      e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.lse + r * c.lse_stride),
+                            static_cast<int>(0xff800000u), c.m, c.stream);
+      if (e != hipSuccess) return static_cast<int>(e);
+    }
+  }
+  return 0;
+}
+
+// What a call returns, in the order the conditions are tried.  The four forms (float32 or
+// half operands x one or many masks) came from four functions and do not agree everywhere;
+// the differences are kept and marked (*).  INVALID = SPUTNIK_HIP_INVALID_ARGUMENT,
+// UNSUPPORTED = SPUTNIK_HIP_UNSUPPORTED, "empty" = 0 after publishing the rng state when
+// dropping (every form), replicas = batch * heads.
+//
+//   float32, one mask     1. m, n, d, nonzeros or replicas < 0: INVALID
+//                         2. m == 0 or replicas == 0: empty
+//                     (*) 3. nonzeros == 0 or n == 0: served here -- rng state published, out
+//                            set to 0, lse to -inf, no kernel and no look at the workspace
+//                         4. not supported(m, n, d, nonzeros), a base not 16-byte aligned or
+//                            a stride not a multiple of 4: UNSUPPORTED
+//                         5. workspace NULL, unaligned or too small: INVALID
+//   half, one mask        1. as above, with batch and heads for replicas
+//                         2. m == 0, batch == 0 or heads == 0: empty
+//                     (*) 3. no branch for nonzeros == 0 or n == 0: heads_served refuses them
+//                            with everything else it refuses (types, views, batch * heads >=
+//                            2^31): UNSUPPORTED
+//                         4. workspace: INVALID
+//   float32, many masks   1. masks <= 0, m, n, d or replicas < 0, nonzeros NULL, replicas not
+//                            a multiple of masks, a count < 0: INVALID
+//                         2. m == 0 or replicas == 0: empty
+//                     (*) 3. more than 65535 masks or replicas, not supported for the densest
+//                            mask -- counted as 1 entry when all are empty, so a launch
+//                            without entries IS served, by the kernel -- or alignment as for
+//                            one mask: UNSUPPORTED.  (n == 0 is therefore UNSUPPORTED here.)
+//                         4. workspace: INVALID
+//   half, many masks  (*) 0. batch or heads < 0: INVALID; then batch * heads >= 2^31:
+//                            UNSUPPORTED; then batch != masks: INVALID -- all before step 1, so
+//                            the overflow is UNSUPPORTED even with otherwise invalid arguments
+//                         1. as float32 many masks
+//                         2. m == 0 or heads == 0: empty (batch == 0 was INVALID: masks <= 0)
+//                         3. as float32 many masks, with heads_served for the densest mask
+//                            (at least 1) in place of the alignment: UNSUPPORTED
+//                         4. workspace: INVALID
+// Then every form returns the first failing launch's hipError_t (pre-pass unless planned,
+// kernel), else 0.
+int forward(const ForwardCall& c) {
+  // (exact wherever it is used: the half forms refuse a product of 2^31 or more before)
+  const int replicas = static_cast<int>(static_cast<int64_t>(c.batch) * c.heads);
+  int largest = 0;   // entries of the densest mask
+  if (c.many) {
+    if (c.half) {
+      if (c.batch < 0 || c.heads < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+      if (static_cast<int64_t>(c.batch) * c.heads >= (int64_t{1} << 31)) return SPUTNIK_HIP_UNSUPPORTED;
+      if (c.batch != c.masks) return SPUTNIK_HIP_INVALID_ARGUMENT;
+    }
+    const int st = many_mask_args(c.masks, c.m, c.n, c.d, c.nonzeros, replicas, &largest);
+    if (st != 0) return st;
+  } else {
+    largest = *c.nonzeros;
+    if (c.m < 0 || c.n < 0 || c.d < 0 || largest < 0 || c.batch < 0 || c.heads < 0)
+      return SPUTNIK_HIP_INVALID_ARGUMENT;
+  }
+  if (c.m == 0 || c.batch == 0 || c.heads == 0)
+    return c.drop != nullptr ? publish_rng_state(*c.drop, c.stream) : 0;
+  if (!c.many && !c.half && (largest == 0 || c.n == 0)) return fill_empty(c);
+
+  const int densest = c.many ? max(largest, 1) : largest;
+  bool served = !c.many || many_mask_supported(c.masks, c.m, c.n, c.d, largest, replicas);
+  if (c.half)
+    served = served && heads_served(c.m, c.n, c.d, densest, c.batch, c.heads, c.dtype, c.out_type, c.q,
+                                    c.k, c.v, c.o);
+  else
+    served = served && supported(c.m, c.n, c.d, densest) && aligned_to(c.q.base, 16) &&
+             aligned_to(c.k.base, 16) && aligned_to(c.v.base, 16) && aligned_to(c.o.base, 16) &&
+             c.q.batch % 4 == 0 && c.k.batch % 4 == 0 && c.v.batch % 4 == 0 && c.o.batch % 4 == 0;
+  if (!served) return SPUTNIK_HIP_UNSUPPORTED;
+  const size_t need = c.many ? many_mask_workspace(c.masks, c.m, c.n, c.d, largest)
+                             : plan_bytes(c.m, c.n, c.d, largest);
+  if (c.workspace == nullptr || !aligned_to(c.workspace, 16) || c.workspace_bytes < need)
     return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (!planned) {
-    st = many_mask_plan_exec(masks, m, n, row_indices, row_offsets, column_indices, workspace, stream);
+
+  if (!c.planned) {
+    const int st = prepass(c.many, c.masks, c.m, c.n, c.row_indices, c.row_offsets, c.column_indices,
+                           c.workspace, c.stream);
     if (st != 0) return st;
   }
-  const int slots = slots_of(m), nchunks = chunks_of(n);
-  const int* row_ok = static_cast<const int*>(workspace);
-  const int* table = reinterpret_cast<const int*>(static_cast<const char*>(workspace) + row_ok_bytes(slots));
-  const dim3 grid(slots / kBM, batch * heads);
-#define SPUTNIK_HIP_HEADS_MM(T, TO)                                                                   \
-  do {                                                                                                \
-    if (drop != nullptr)                                                                              \
-      hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, true, DropArgs>), grid, dim3(kThreads),  \
-                         0, stream, m, n, 0, slots, nchunks, heads, 0, row_indices, row_offsets,     \
-                         column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride, *drop);  \
-    else                                                                                              \
-      hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, true>), grid, dim3(kThreads), 0,       \
-                         stream, m, n, 0, slots, nchunks, heads, 0, row_indices, row_offsets,        \
-                         column_indices, table, row_ok, q, k, v, scale, o, lse, lse_stride);         \
-  } while (0)
-  if (dtype == SPUTNIK_HIP_F16 && out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS_MM(_Float16, float);
-  else if (dtype == SPUTNIK_HIP_F16) SPUTNIK_HIP_HEADS_MM(_Float16, _Float16);
-  else if (out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_HEADS_MM(__bf16, float);
-  else SPUTNIK_HIP_HEADS_MM(__bf16, __bf16);
-#undef SPUTNIK_HIP_HEADS_MM
-  return launch_status();
+  const int slots = slots_of(c.m);
+  const Plan p{slots, chunks_of(c.n), static_cast<const int*>(c.workspace),
+               reinterpret_cast<const int*>(static_cast<const char*>(c.workspace) + row_ok_bytes(slots))};
+  // (many masks: one launch, the replicas fit the grid)
+  for (int r0 = 0; r0 < replicas; r0 += kMaxGridYZ) {
+    launch(c, p, r0, min(replicas - r0, kMaxGridYZ));
+    const int st = launch_status();
+    if (st != 0) return st;
+  }
+  return 0;
+}
+
+// The forms with attention dropout (sputnik_hip.h, "Attention dropout"): the same call with
+// the DROP kernels; p = 0 is the form without.
+int forward_dropout(ForwardCall c, double p, const sputnik_hip_philox_state& rng, int64_t* rng_state_out) {
+  DropArgs drop;
+  if (!drop_args(p, rng, rng_state_out, &drop)) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (p > 0.0) c.drop = &drop;
+  return forward(c);
+}
+
+// The argument lists of the C entry points as a ForwardCall: float32 operands ...
+ForwardCall float_call(bool many, int masks, const int* nonzeros, int m, int n, int d, int replicas,
+                       const int* row_indices, const int* row_offsets, const int* column_indices,
+                       const float* q, int64_t q_stride, const float* k, int64_t k_stride, const float* v,
+                       int64_t v_stride, float scale, float* out, int64_t out_stride, float* lse,
+                       int64_t lse_stride, const void* workspace, size_t workspace_bytes, bool planned,
+                       hipStream_t stream) {
+  return ForwardCall{many, /*half=*/false, masks, nonzeros, m, n, d, replicas, /*heads=*/1,
+                     row_indices, row_offsets, column_indices, SPUTNIK_HIP_F32, SPUTNIK_HIP_F32,
+                     HeadView{q, q_stride, 0, 0}, HeadView{k, k_stride, 0, 0}, HeadView{v, v_stride, 0, 0},
+                     HeadView{out, out_stride, 0, 0}, scale, lse, lse_stride, const_cast<void*>(workspace),
+                     workspace_bytes, planned, stream, /*drop=*/nullptr};
+}
+
+// ... and half head views.
+ForwardCall heads_call(bool many, int masks, const int* nonzeros, int m, int n, int d, int batch, int heads,
+                       const int* row_indices, const int* row_offsets, const int* column_indices, int dtype,
+                       const void* q, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                       const void* k, int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride,
+                       const void* v, int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride,
+                       float scale, void* out, int out_type, int64_t out_batch_stride,
+                       int64_t out_head_stride, int64_t out_row_stride, float* lse, int64_t lse_stride,
+                       const void* workspace, size_t workspace_bytes, bool planned, hipStream_t stream) {
+  return ForwardCall{many, /*half=*/true, masks, nonzeros, m, n, d, batch, heads, row_indices, row_offsets,
+                     column_indices, dtype, out_type,
+                     HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
+                     HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
+                     HeadView{v, v_batch_stride, v_head_stride, v_row_stride},
+                     HeadView{out, out_batch_stride, out_head_stride, out_row_stride}, scale, lse,
+                     lse_stride, const_cast<void*>(workspace), workspace_bytes, planned, stream,
+                     /*drop=*/nullptr};
 }
 
 }  // namespace
 
 extern "C" {
 
+int sputnik_hip_sparse_attention_supported(int m, int n, int d, int nonzeros) {
+  return supported(m, n, d, nonzeros) ? 1 : 0;
+}
+
+size_t sputnik_hip_sparse_attention_workspace_bytes(int m, int n, int d, int nonzeros) {
+  return plan_bytes(m, n, d, nonzeros);
+}
+
+int sputnik_hip_sparse_attention_plan(int m, int n, int d, int nonzeros, const int* row_indices,
+                                      const int* row_offsets, const int* column_indices,
+                                      void* workspace, size_t workspace_bytes,
+                                      sputnik_hip_stream_t stream) {
+  if (m < 0 || n < 0 || d < 0 || nonzeros < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (!supported(m, n, d, nonzeros)) return SPUTNIK_HIP_UNSUPPORTED;
+  if (workspace == nullptr || !aligned_to(workspace, 16) ||
+      workspace_bytes < plan_bytes(m, n, d, nonzeros))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  return prepass(false, 0, m, n, row_indices, row_offsets, column_indices, workspace, stream);
+}
+
+int sputnik_hip_sparse_attention_forward(int m, int n, int d, int nonzeros, int replicas,
+                                         const int* row_indices, const int* row_offsets,
+                                         const int* column_indices, const float* q,
+                                         int64_t q_stride, const float* k, int64_t k_stride,
+                                         const float* v, int64_t v_stride, float scale,
+                                         float* out, int64_t out_stride, float* lse,
+                                         int64_t lse_stride, void* workspace,
+                                         size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  return forward(float_call(false, 0, &nonzeros, m, n, d, replicas, row_indices, row_offsets,
+                            column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                            out_stride, lse, lse_stride, workspace, workspace_bytes,
+                            /*planned=*/false, stream));
+}
+
+int sputnik_hip_sparse_attention_forward_planned(
+    int m, int n, int d, int nonzeros, int replicas, const int* row_indices,
+    const int* row_offsets, const int* column_indices, const float* q, int64_t q_stride,
+    const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
+    int64_t out_stride, float* lse, int64_t lse_stride, const void* workspace,
+    size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  return forward(float_call(false, 0, &nonzeros, m, n, d, replicas, row_indices, row_offsets,
+                            column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                            out_stride, lse, lse_stride, workspace, workspace_bytes,
+                            /*planned=*/true, stream));
+}
+
+int sputnik_hip_sparse_attention_forward_dropout(
+    int m, int n, int d, int nonzeros, int replicas, const int* row_indices, const int* row_offsets,
+    const int* column_indices, const float* q, int64_t q_stride, const float* k, int64_t k_stride,
+    const float* v, int64_t v_stride, float scale, float* out, int64_t out_stride, float* lse,
+    int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
+    void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  return forward_dropout(float_call(false, 0, &nonzeros, m, n, d, replicas, row_indices, row_offsets,
+                                    column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                                    out_stride, lse, lse_stride, workspace, workspace_bytes,
+                                    /*planned=*/false, stream),
+                         p, rng, rng_state_out);
+}
+
+int sputnik_hip_sparse_attention_forward_planned_dropout(
+    int m, int n, int d, int nonzeros, int replicas, const int* row_indices, const int* row_offsets,
+    const int* column_indices, const float* q, int64_t q_stride, const float* k, int64_t k_stride,
+    const float* v, int64_t v_stride, float scale, float* out, int64_t out_stride, float* lse,
+    int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
+    const void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  return forward_dropout(float_call(false, 0, &nonzeros, m, n, d, replicas, row_indices, row_offsets,
+                                    column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                                    out_stride, lse, lse_stride, workspace, workspace_bytes,
+                                    /*planned=*/true, stream),
+                         p, rng, rng_state_out);
+}
+
+// ---- half storage, strided head views ----
+int sputnik_hip_sparse_attention_heads_supported(
+    int m, int n, int d, int nonzeros, int batch, int heads, int dtype, int out_type, const void* q,
+    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
+    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
+    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, const void* out,
+    int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride) {
+  return heads_served(m, n, d, nonzeros, batch, heads, dtype, out_type,
+                      HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
+                      HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
+                      HeadView{v, v_batch_stride, v_head_stride, v_row_stride},
+                      HeadView{out, out_batch_stride, out_head_stride, out_row_stride})
+             ? 1 : 0;
+}
+
+size_t sputnik_hip_sparse_attention_heads_workspace_bytes(int m, int n, int d, int nonzeros) {
+  return plan_bytes(m, n, d, nonzeros);
+}
+
+int sputnik_hip_sparse_attention_heads_forward(
+    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
+    const int* row_offsets, const int* column_indices, int dtype, const void* q,
+    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
+    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
+    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
+    float* lse, int64_t lse_stride, void* workspace, size_t workspace_bytes,
+    sputnik_hip_stream_t stream) {
+  return forward(heads_call(false, 0, &nonzeros, m, n, d, batch, heads, row_indices, row_offsets,
+                            column_indices, dtype, q, q_batch_stride, q_head_stride, q_row_stride, k,
+                            k_batch_stride, k_head_stride, k_row_stride, v, v_batch_stride, v_head_stride,
+                            v_row_stride, scale, out, out_type, out_batch_stride, out_head_stride,
+                            out_row_stride, lse, lse_stride, workspace, workspace_bytes,
+                            /*planned=*/false, stream));
+}
+
+int sputnik_hip_sparse_attention_heads_forward_planned(
+    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
+    const int* row_offsets, const int* column_indices, int dtype, const void* q,
+    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
+    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
+    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
+    float* lse, int64_t lse_stride, const void* workspace, size_t workspace_bytes,
+    sputnik_hip_stream_t stream) {
+  return forward(heads_call(false, 0, &nonzeros, m, n, d, batch, heads, row_indices, row_offsets,
+                            column_indices, dtype, q, q_batch_stride, q_head_stride, q_row_stride, k,
+                            k_batch_stride, k_head_stride, k_row_stride, v, v_batch_stride, v_head_stride,
+                            v_row_stride, scale, out, out_type, out_batch_stride, out_head_stride,
+                            out_row_stride, lse, lse_stride, workspace, workspace_bytes,
+                            /*planned=*/true, stream));
+}
+
+int sputnik_hip_sparse_attention_heads_forward_dropout(
+    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
+    const int* row_offsets, const int* column_indices, int dtype, const void* q,
+    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
+    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
+    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
+    float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
+    void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  return forward_dropout(
+      heads_call(false, 0, &nonzeros, m, n, d, batch, heads, row_indices, row_offsets, column_indices,
+                 dtype, q, q_batch_stride, q_head_stride, q_row_stride, k, k_batch_stride, k_head_stride,
+                 k_row_stride, v, v_batch_stride, v_head_stride, v_row_stride, scale, out, out_type,
+                 out_batch_stride, out_head_stride, out_row_stride, lse, lse_stride, workspace,
+                 workspace_bytes, /*planned=*/false, stream),
+      p, rng, rng_state_out);
+}
+
+int sputnik_hip_sparse_attention_heads_forward_planned_dropout(
+    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
+    const int* row_offsets, const int* column_indices, int dtype, const void* q,
+    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
+    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
+    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
+    float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
+    const void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  return forward_dropout(
+      heads_call(false, 0, &nonzeros, m, n, d, batch, heads, row_indices, row_offsets, column_indices,
+                 dtype, q, q_batch_stride, q_head_stride, q_row_stride, k, k_batch_stride, k_head_stride,
+                 k_row_stride, v, v_batch_stride, v_head_stride, v_row_stride, scale, out, out_type,
+                 out_batch_stride, out_head_stride, out_row_stride, lse, lse_stride, workspace,
+                 workspace_bytes, /*planned=*/true, stream),
+      p, rng, rng_state_out);
+}
+
+// ---- many masks (sputnik_hip.h, "many mask" family): one topology per batch element, all of
+// them served by ONE pre-pass launch and ONE attention launch ----
 size_t sputnik_hip_sparse_attention_many_mask_workspace_bytes(int masks, int m, int n, int d,
                                                               int largest_nonzeros) {
   if (m < 0 || n < 0 || d < 0 || largest_nonzeros < 0) return 0;
@@ -1156,8 +1219,7 @@ int sputnik_hip_sparse_attention_many_mask_plan(int masks, int m, int n, int d, 
       workspace_bytes < many_mask_workspace(masks, m, n, d, largest))
     return SPUTNIK_HIP_INVALID_ARGUMENT;
   if (m == 0) return 0;
-  return many_mask_plan_exec(masks, m, n, row_indices, row_offsets, column_indices, workspace,
-                             static_cast<hipStream_t>(stream));
+  return prepass(true, masks, m, n, row_indices, row_offsets, column_indices, workspace, stream);
 }
 
 int sputnik_hip_sparse_attention_many_mask_forward(
@@ -1166,10 +1228,10 @@ int sputnik_hip_sparse_attention_many_mask_forward(
     const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
     int64_t out_stride, float* lse, int64_t lse_stride, void* workspace, size_t workspace_bytes,
     sputnik_hip_stream_t stream) {
-  return attention_many_mask_exec(masks, m, n, d, nonzeros, replicas, row_indices, row_offsets,
-                                  column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
-                                  out_stride, lse, lse_stride, workspace, workspace_bytes,
-                                  /*planned=*/false, static_cast<hipStream_t>(stream));
+  return forward(float_call(true, masks, nonzeros, m, n, d, replicas, row_indices, row_offsets,
+                            column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                            out_stride, lse, lse_stride, workspace, workspace_bytes,
+                            /*planned=*/false, stream));
 }
 
 int sputnik_hip_sparse_attention_many_mask_forward_planned(
@@ -1178,10 +1240,37 @@ int sputnik_hip_sparse_attention_many_mask_forward_planned(
     const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
     int64_t out_stride, float* lse, int64_t lse_stride, const void* workspace,
     size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  return attention_many_mask_exec(masks, m, n, d, nonzeros, replicas, row_indices, row_offsets,
-                                  column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
-                                  out_stride, lse, lse_stride, const_cast<void*>(workspace),
-                                  workspace_bytes, /*planned=*/true, static_cast<hipStream_t>(stream));
+  return forward(float_call(true, masks, nonzeros, m, n, d, replicas, row_indices, row_offsets,
+                            column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                            out_stride, lse, lse_stride, workspace, workspace_bytes,
+                            /*planned=*/true, stream));
+}
+
+int sputnik_hip_sparse_attention_many_mask_forward_dropout(
+    int masks, int m, int n, int d, const int* nonzeros, int replicas, const int* row_indices,
+    const int* row_offsets, const int* column_indices, const float* q, int64_t q_stride,
+    const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
+    int64_t out_stride, float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+    int64_t* rng_state_out, void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
+  return forward_dropout(float_call(true, masks, nonzeros, m, n, d, replicas, row_indices, row_offsets,
+                                    column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                                    out_stride, lse, lse_stride, workspace, workspace_bytes,
+                                    /*planned=*/false, stream),
+                         p, rng, rng_state_out);
+}
+
+int sputnik_hip_sparse_attention_many_mask_forward_planned_dropout(
+    int masks, int m, int n, int d, const int* nonzeros, int replicas, const int* row_indices,
+    const int* row_offsets, const int* column_indices, const float* q, int64_t q_stride,
+    const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
+    int64_t out_stride, float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+    int64_t* rng_state_out, const void* workspace, size_t workspace_bytes,
+    sputnik_hip_stream_t stream) {
+  return forward_dropout(float_call(true, masks, nonzeros, m, n, d, replicas, row_indices, row_offsets,
+                                    column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
+                                    out_stride, lse, lse_stride, workspace, workspace_bytes,
+                                    /*planned=*/true, stream),
+                         p, rng, rng_state_out);
 }
 
 int sputnik_hip_sparse_attention_heads_many_mask_forward(
@@ -1193,14 +1282,12 @@ int sputnik_hip_sparse_attention_heads_many_mask_forward(
     float scale, void* out, int out_type, int64_t out_batch_stride, int64_t out_head_stride,
     int64_t out_row_stride, float* lse, int64_t lse_stride, void* workspace,
     size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  return heads_many_mask_exec(masks, m, n, d, nonzeros, batch, heads, row_indices, row_offsets,
-                              column_indices, dtype,
-                              HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
-                              HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
-                              HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
-                              HeadView{out, out_batch_stride, out_head_stride, out_row_stride},
-                              out_type, lse, lse_stride, workspace, workspace_bytes,
-                              /*planned=*/false, static_cast<hipStream_t>(stream));
+  return forward(heads_call(true, masks, nonzeros, m, n, d, batch, heads, row_indices, row_offsets,
+                            column_indices, dtype, q, q_batch_stride, q_head_stride, q_row_stride, k,
+                            k_batch_stride, k_head_stride, k_row_stride, v, v_batch_stride, v_head_stride,
+                            v_row_stride, scale, out, out_type, out_batch_stride, out_head_stride,
+                            out_row_stride, lse, lse_stride, workspace, workspace_bytes,
+                            /*planned=*/false, stream));
 }
 
 int sputnik_hip_sparse_attention_heads_many_mask_forward_planned(
@@ -1212,117 +1299,12 @@ int sputnik_hip_sparse_attention_heads_many_mask_forward_planned(
     float scale, void* out, int out_type, int64_t out_batch_stride, int64_t out_head_stride,
     int64_t out_row_stride, float* lse, int64_t lse_stride, const void* workspace,
     size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  return heads_many_mask_exec(masks, m, n, d, nonzeros, batch, heads, row_indices, row_offsets,
-                              column_indices, dtype,
-                              HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
-                              HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
-                              HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
-                              HeadView{out, out_batch_stride, out_head_stride, out_row_stride},
-                              out_type, lse, lse_stride, const_cast<void*>(workspace),
-                              workspace_bytes, /*planned=*/true, static_cast<hipStream_t>(stream));
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------
-// The forms with attention dropout (sputnik_hip.h, "Attention dropout"): the same checks and
-// launches with the DROP kernels; p = 0 is the form without.
-// ---------------------------------------------------------------------------
-extern "C" {
-
-#define SPUTNIK_HIP_DROP_ARGS()                                          \
-  DropArgs drop_store;                                                   \
-  if (!drop_args(p, rng, rng_state_out, &drop_store)) return SPUTNIK_HIP_INVALID_ARGUMENT; \
-  const DropArgs* drop = p > 0.0 ? &drop_store : nullptr
-
-int sputnik_hip_sparse_attention_forward_dropout(
-    int m, int n, int d, int nonzeros, int replicas, const int* row_indices, const int* row_offsets,
-    const int* column_indices, const float* q, int64_t q_stride, const float* k, int64_t k_stride,
-    const float* v, int64_t v_stride, float scale, float* out, int64_t out_stride, float* lse,
-    int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
-    void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  SPUTNIK_HIP_DROP_ARGS();
-  return attention_exec(m, n, d, nonzeros, replicas, row_indices, row_offsets, column_indices, q,
-                        q_stride, k, k_stride, v, v_stride, scale, out, out_stride, lse,
-                        lse_stride, workspace, workspace_bytes, /*planned=*/false, stream, drop);
-}
-
-int sputnik_hip_sparse_attention_forward_planned_dropout(
-    int m, int n, int d, int nonzeros, int replicas, const int* row_indices, const int* row_offsets,
-    const int* column_indices, const float* q, int64_t q_stride, const float* k, int64_t k_stride,
-    const float* v, int64_t v_stride, float scale, float* out, int64_t out_stride, float* lse,
-    int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
-    const void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  SPUTNIK_HIP_DROP_ARGS();
-  return attention_exec(m, n, d, nonzeros, replicas, row_indices, row_offsets, column_indices, q,
-                        q_stride, k, k_stride, v, v_stride, scale, out, out_stride, lse,
-                        lse_stride, const_cast<void*>(workspace), workspace_bytes,
-                        /*planned=*/true, stream, drop);
-}
-
-int sputnik_hip_sparse_attention_heads_forward_dropout(
-    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
-    const int* row_offsets, const int* column_indices, int dtype, const void* q,
-    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
-    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
-    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
-    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
-    float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
-    void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  SPUTNIK_HIP_DROP_ARGS();
-  return heads_exec(m, n, d, nonzeros, batch, heads, row_indices, row_offsets, column_indices, dtype,
-                    HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
-                    HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
-                    HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
-                    HeadView{out, out_batch_stride, out_head_stride, out_row_stride}, out_type, lse,
-                    lse_stride, workspace, workspace_bytes, /*planned=*/false, stream, drop);
-}
-
-int sputnik_hip_sparse_attention_heads_forward_planned_dropout(
-    int m, int n, int d, int nonzeros, int batch, int heads, const int* row_indices,
-    const int* row_offsets, const int* column_indices, int dtype, const void* q,
-    int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride, const void* k,
-    int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
-    int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
-    int out_type, int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride,
-    float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng, int64_t* rng_state_out,
-    const void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  SPUTNIK_HIP_DROP_ARGS();
-  return heads_exec(m, n, d, nonzeros, batch, heads, row_indices, row_offsets, column_indices, dtype,
-                    HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
-                    HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
-                    HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
-                    HeadView{out, out_batch_stride, out_head_stride, out_row_stride}, out_type, lse,
-                    lse_stride, const_cast<void*>(workspace), workspace_bytes, /*planned=*/true,
-                    stream, drop);
-}
-
-int sputnik_hip_sparse_attention_many_mask_forward_dropout(
-    int masks, int m, int n, int d, const int* nonzeros, int replicas, const int* row_indices,
-    const int* row_offsets, const int* column_indices, const float* q, int64_t q_stride,
-    const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
-    int64_t out_stride, float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
-    int64_t* rng_state_out, void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  SPUTNIK_HIP_DROP_ARGS();
-  return attention_many_mask_exec(masks, m, n, d, nonzeros, replicas, row_indices, row_offsets,
-                                  column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
-                                  out_stride, lse, lse_stride, workspace, workspace_bytes,
-                                  /*planned=*/false, static_cast<hipStream_t>(stream), drop);
-}
-
-int sputnik_hip_sparse_attention_many_mask_forward_planned_dropout(
-    int masks, int m, int n, int d, const int* nonzeros, int replicas, const int* row_indices,
-    const int* row_offsets, const int* column_indices, const float* q, int64_t q_stride,
-    const float* k, int64_t k_stride, const float* v, int64_t v_stride, float scale, float* out,
-    int64_t out_stride, float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
-    int64_t* rng_state_out, const void* workspace, size_t workspace_bytes,
-    sputnik_hip_stream_t stream) {
-  SPUTNIK_HIP_DROP_ARGS();
-  return attention_many_mask_exec(masks, m, n, d, nonzeros, replicas, row_indices, row_offsets,
-                                  column_indices, q, q_stride, k, k_stride, v, v_stride, scale, out,
-                                  out_stride, lse, lse_stride, const_cast<void*>(workspace),
-                                  workspace_bytes, /*planned=*/true, static_cast<hipStream_t>(stream),
-                                  drop);
+  return forward(heads_call(true, masks, nonzeros, m, n, d, batch, heads, row_indices, row_offsets,
+                            column_indices, dtype, q, q_batch_stride, q_head_stride, q_row_stride, k,
+                            k_batch_stride, k_head_stride, k_row_stride, v, v_batch_stride, v_head_stride,
+                            v_row_stride, scale, out, out_type, out_batch_stride, out_head_stride,
+                            out_row_stride, lse, lse_stride, workspace, workspace_bytes,
+                            /*planned=*/true, stream));
 }
 
 int sputnik_hip_sparse_attention_heads_many_mask_forward_dropout(
@@ -1334,15 +1316,13 @@ int sputnik_hip_sparse_attention_heads_many_mask_forward_dropout(
     float scale, void* out, int out_type, int64_t out_batch_stride, int64_t out_head_stride,
     int64_t out_row_stride, float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
     int64_t* rng_state_out, void* workspace, size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  SPUTNIK_HIP_DROP_ARGS();
-  return heads_many_mask_exec(masks, m, n, d, nonzeros, batch, heads, row_indices, row_offsets,
-                              column_indices, dtype,
-                              HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
-                              HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
-                              HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
-                              HeadView{out, out_batch_stride, out_head_stride, out_row_stride},
-                              out_type, lse, lse_stride, workspace, workspace_bytes,
-                              /*planned=*/false, static_cast<hipStream_t>(stream), drop);
+  return forward_dropout(
+      heads_call(true, masks, nonzeros, m, n, d, batch, heads, row_indices, row_offsets, column_indices,
+                 dtype, q, q_batch_stride, q_head_stride, q_row_stride, k, k_batch_stride, k_head_stride,
+                 k_row_stride, v, v_batch_stride, v_head_stride, v_row_stride, scale, out, out_type,
+                 out_batch_stride, out_head_stride, out_row_stride, lse, lse_stride, workspace,
+                 workspace_bytes, /*planned=*/false, stream),
+      p, rng, rng_state_out);
 }
 
 int sputnik_hip_sparse_attention_heads_many_mask_forward_planned_dropout(
@@ -1355,18 +1335,13 @@ int sputnik_hip_sparse_attention_heads_many_mask_forward_planned_dropout(
     int64_t out_row_stride, float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
     int64_t* rng_state_out, const void* workspace, size_t workspace_bytes,
     sputnik_hip_stream_t stream) {
-  SPUTNIK_HIP_DROP_ARGS();
-  return heads_many_mask_exec(masks, m, n, d, nonzeros, batch, heads, row_indices, row_offsets,
-                              column_indices, dtype,
-                              HeadView{q, q_batch_stride, q_head_stride, q_row_stride},
-                              HeadView{k, k_batch_stride, k_head_stride, k_row_stride},
-                              HeadView{v, v_batch_stride, v_head_stride, v_row_stride}, scale,
-                              HeadView{out, out_batch_stride, out_head_stride, out_row_stride},
-                              out_type, lse, lse_stride, const_cast<void*>(workspace),
-                              workspace_bytes, /*planned=*/true, static_cast<hipStream_t>(stream),
-                              drop);
+  return forward_dropout(
+      heads_call(true, masks, nonzeros, m, n, d, batch, heads, row_indices, row_offsets, column_indices,
+                 dtype, q, q_batch_stride, q_head_stride, q_row_stride, k, k_batch_stride, k_head_stride,
+                 k_row_stride, v, v_batch_stride, v_head_stride, v_row_stride, scale, out, out_type,
+                 out_batch_stride, out_head_stride, out_row_stride, lse, lse_stride, workspace,
+                 workspace_bytes, /*planned=*/true, stream),
+      p, rng, rng_state_out);
 }
-
-#undef SPUTNIK_HIP_DROP_ARGS
 
 }  // extern "C"

@@ -1187,6 +1187,34 @@ std::vector<Tensor> sparse_dropout(const Tensor& values, double p, const c10::op
   return {dropout_values(values, d), d.rng_state};
 }
 
+// What the fused attention ops return: {out}, {out, lse}, or with dropout
+// {out, lse or undefined, rng_state}.
+std::vector<Tensor> attention_result(const Tensor& out, const Tensor& lse, bool want_lse, const Drop* drop) {
+  if (drop != nullptr) return {out, want_lse ? lse : Tensor(), drop->rng_state};
+  if (want_lse) return {out, lse};
+  return {out};
+}
+
+// Runs one of a layout's four C forward functions.  `args(forward, tail...)` holds the
+// layout's argument list up to lse_stride; the tail is [p, rng, rng_state_out,] workspace,
+// workspace_bytes, stream.  The workspace is the plan if one is given (checked), else fresh.
+template <typename Args, typename F, typename FP, typename FD, typename FPD>
+int run_forward(const Args& args, F unplanned, FP planned, FD unplanned_dropout, FPD planned_dropout,
+                const c10::optional<Tensor>& plan, size_t ws_bytes, const Tensor& like, const Drop* drop) {
+  Tensor workspace;
+  if (plan.has_value()) check_plan(*plan, ws_bytes, like);
+  else workspace = at::empty({static_cast<int64_t>(ws_bytes)}, like.options().dtype(at::kByte));
+  const sputnik_hip_stream_t stream = current_stream(like);
+  auto with_workspace = [&](auto fresh, auto from_plan, auto... dropout) {
+    return plan.has_value()
+               ? args(from_plan, dropout..., static_cast<const void*>(plan->data_ptr()), ws_bytes, stream)
+               : args(fresh, dropout..., workspace.data_ptr(), ws_bytes, stream);
+  };
+  return drop != nullptr
+             ? with_workspace(unplanned_dropout, planned_dropout, drop->p, drop->rng, drop->rng_state_out)
+             : with_workspace(unplanned, planned);
+}
+
 // Fused softmax(scale * sddmm(q, k)) @ v over a fixed mask
 // (modules/sparse_attention.py:66-82).  q [R,m,d] / [m,d]; k, v [R,n,d] / [n,d].
 // Shapes the fused kernel does not serve are composed from the three operators.
@@ -1221,60 +1249,28 @@ std::vector<Tensor> sparse_attention_impl(const Tensor& q_in, const Tensor& k_in
         topo.row_indices, topo.row_offsets, topo.column_indices, scale);
     if (drop != nullptr) weights = dropout_values(weights, *drop);
     Tensor out = spmm(m, n, weights, topo.row_indices, topo.row_offsets, topo.column_indices, v);
-    if (drop != nullptr) return {out, Tensor(), drop->rng_state};   // (no lse on this route)
-    return {out};
+    return attention_result(out, Tensor(), false, drop);   // (no lse on this route)
   }
   Tensor out = at::empty_like(q);
   Tensor lse;
   if (want_lse)
     lse = q.dim() == 3 ? at::empty({replicas, m}, q.options()) : at::empty({m}, q.options());
   const size_t ws_bytes = sputnik_hip_sparse_attention_workspace_bytes(m, n, d, topo.nonzeros);
-  if (drop != nullptr) {
-    Tensor workspace;
-    if (plan.has_value()) check_plan(*plan, ws_bytes, q);
-    else workspace = at::empty({static_cast<int64_t>(ws_bytes)}, q.options().dtype(at::kByte));
-    auto call = [&](auto forward, auto ws) {
-      return forward(m, n, d, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
-                     topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(),
-                     q.data_ptr<float>(), static_cast<int64_t>(m) * d, k.data_ptr<float>(),
-                     static_cast<int64_t>(n) * d, v.data_ptr<float>(), static_cast<int64_t>(n) * d,
-                     static_cast<float>(scale), out.data_ptr<float>(), static_cast<int64_t>(m) * d,
-                     want_lse ? lse.data_ptr<float>() : nullptr, m, drop->p, drop->rng,
-                     drop->rng_state_out, ws, ws_bytes, current_stream(q));
-    };
-    check_status(plan.has_value() ? call(sputnik_hip_sparse_attention_forward_planned_dropout,
-                                         static_cast<const void*>(plan->data_ptr()))
-                                  : call(sputnik_hip_sparse_attention_forward_dropout, workspace.data_ptr()),
-                 "sparse_attention_dropout");
-    return {out, want_lse ? lse : Tensor(), drop->rng_state};
-  }
-  if (plan.has_value()) {
-    check_plan(*plan, ws_bytes, q);
-    check_status(sputnik_hip_sparse_attention_forward_planned(
-                     m, n, d, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
-                     topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(),
-                     q.data_ptr<float>(), static_cast<int64_t>(m) * d, k.data_ptr<float>(),
-                     static_cast<int64_t>(n) * d, v.data_ptr<float>(),
-                     static_cast<int64_t>(n) * d, static_cast<float>(scale),
-                     out.data_ptr<float>(), static_cast<int64_t>(m) * d,
-                     want_lse ? lse.data_ptr<float>() : nullptr, m, plan->data_ptr(), ws_bytes,
-                     current_stream(q)),
-                 "sparse_attention_planned");
-    if (want_lse) return {out, lse};
-    return {out};
-  }
-  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, q.options().dtype(at::kByte));
-  check_status(sputnik_hip_sparse_attention_forward(
-                   m, n, d, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
+  auto args = [&](auto forward, auto... tail) {
+    return forward(m, n, d, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
                    topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(),
                    q.data_ptr<float>(), static_cast<int64_t>(m) * d, k.data_ptr<float>(),
                    static_cast<int64_t>(n) * d, v.data_ptr<float>(), static_cast<int64_t>(n) * d,
-                   static_cast<float>(scale), out.data_ptr<float>(),
-                   static_cast<int64_t>(m) * d, want_lse ? lse.data_ptr<float>() : nullptr, m,
-                   workspace.data_ptr(), ws_bytes, current_stream(q)),
-               "sparse_attention");
-  if (want_lse) return {out, lse};
-  return {out};
+                   static_cast<float>(scale), out.data_ptr<float>(), static_cast<int64_t>(m) * d,
+                   want_lse ? lse.data_ptr<float>() : nullptr, m, tail...);
+  };
+  check_status(run_forward(args, sputnik_hip_sparse_attention_forward,
+                           sputnik_hip_sparse_attention_forward_planned,
+                           sputnik_hip_sparse_attention_forward_dropout,
+                           sputnik_hip_sparse_attention_forward_planned_dropout, plan, ws_bytes, q, drop),
+               drop != nullptr ? "sparse_attention_dropout"
+                               : plan.has_value() ? "sparse_attention_planned" : "sparse_attention");
+  return attention_result(out, lse, want_lse, drop);
 }
 
 // {out, lse, rng_state}: the fused attention with dropout p > 0 on the attention weights
@@ -1453,6 +1449,27 @@ HeadOperand head_operand(const Tensor& x_in, const char* name) {
   return o;
 }
 
+// What both heads ops ask of their operands (`op` names the op in the messages); -> the
+// operands' type code.
+int check_head_operands(const HeadOperand& q, const HeadOperand& k, const HeadOperand& v, int64_t out_type,
+                        const char* op) {
+  const auto st = q.t.scalar_type();
+  const int dtype = type_code(st);
+  TORCH_CHECK(dtype == SPUTNIK_HIP_F16 || dtype == SPUTNIK_HIP_BF16, op,
+              ": expected float16 / bfloat16 operands, got ", st);
+  TORCH_CHECK(k.t.scalar_type() == st && v.t.scalar_type() == st, op,
+              ": query, key, value must have one type");
+  TORCH_CHECK(q.t.dim() == k.t.dim() && q.t.dim() == v.t.dim(), "query, key, value must match in dims");
+  TORCH_CHECK(k.t.sizes() == v.t.sizes(), "key and value must have one shape");
+  TORCH_CHECK(q.d == k.d, "query and key must have one head dimension");
+  TORCH_CHECK(q.batch == k.batch && q.heads == k.heads, "query and key must have one batch and head count");
+  TORCH_CHECK(q.t.device() == k.t.device() && q.t.device() == v.t.device(),
+              "query, key, value must be on one device");
+  TORCH_CHECK(out_type == SPUTNIK_HIP_F32 || out_type == dtype, op,
+              ": out_type is float32 or the operands' type");
+  return dtype;
+}
+
 // q [.., m, 64], k and v [.., n, 64] of one half type (any strides with a unit last one);
 // out in the layout of the [B, m, H, d] buffer it views ([B, m, E] for 4-D operands), stored
 // as out_type (0 float32, else the operands' type); lse [.., m] float32 on request.
@@ -1464,25 +1481,13 @@ std::vector<Tensor> sparse_attention_heads_run(const Tensor& q_in, const Tensor&
                                            const Drop* drop = nullptr) {
   const HeadOperand q = head_operand(q_in, "query"), k = head_operand(k_in, "key"),
                     v = head_operand(v_in, "value");
+  const int dtype = check_head_operands(q, k, v, out_type, "sparse_attention_heads");
   const auto st = q.t.scalar_type();
-  const int dtype = type_code(st);
-  TORCH_CHECK(dtype == SPUTNIK_HIP_F16 || dtype == SPUTNIK_HIP_BF16,
-              "sparse_attention_heads: expected float16 / bfloat16 operands, got ", st);
-  TORCH_CHECK(k.t.scalar_type() == st && v.t.scalar_type() == st,
-              "sparse_attention_heads: query, key, value must have one type");
-  TORCH_CHECK(q.t.dim() == k.t.dim() && q.t.dim() == v.t.dim(), "query, key, value must match in dims");
-  TORCH_CHECK(k.t.sizes() == v.t.sizes(), "key and value must have one shape");
-  TORCH_CHECK(q.d == k.d, "query and key must have one head dimension");
-  TORCH_CHECK(q.batch == k.batch && q.heads == k.heads, "query and key must have one batch and head count");
-  TORCH_CHECK(q.t.device() == k.t.device() && q.t.device() == v.t.device(),
-              "query, key, value must be on one device");
   const c10::DeviceGuard guard(q.t.device());
   const int m = to_int(q.rows, "m"), n = to_int(k.rows, "n"), d = to_int(q.d, "d");
   const int batch = to_int(q.batch, "batch"), heads = to_int(q.heads, "heads");
   const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, q.t);
   const auto out_st = out_type == SPUTNIK_HIP_F32 ? at::kFloat : st;
-  TORCH_CHECK(out_type == SPUTNIK_HIP_F32 || out_type == dtype,
-              "sparse_attention_heads: out_type is float32 or the operands' type");
 
   Tensor buffer, out;   // out: the [.., m, d] view of `buffer` the kernel writes
   if (q.t.dim() == 4) {
@@ -1518,48 +1523,25 @@ std::vector<Tensor> sparse_attention_heads_run(const Tensor& q_in, const Tensor&
     const Tensor product = spmm(m, n, replicas == 1 ? weights.view({-1}) : weights, topo.row_indices,
                                 topo.row_offsets, topo.column_indices, v3);
     out.copy_(product.reshape(out.sizes()));
-    if (drop != nullptr) return {out, Tensor(), drop->rng_state};
-    return {out};
+    return attention_result(out, Tensor(), false, drop);
   }
   const size_t ws_bytes = sputnik_hip_sparse_attention_heads_workspace_bytes(m, n, d, topo.nonzeros);
-  Tensor workspace;
-  if (plan.has_value()) check_plan(*plan, ws_bytes, q.t);
-  else workspace = at::empty({static_cast<int64_t>(ws_bytes)}, q.t.options().dtype(at::kByte));
-  auto call = [&](auto forward, auto ws) {
+  auto args = [&](auto forward, auto... tail) {
     return forward(m, n, d, topo.nonzeros, batch, heads, topo.row_indices.data_ptr<int>(),
                    topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(), dtype,
                    q.t.data_ptr(), q.batch_stride, q.head_stride, q.row_stride, k.t.data_ptr(),
                    k.batch_stride, k.head_stride, k.row_stride, v.t.data_ptr(), v.batch_stride,
                    v.head_stride, v.row_stride, static_cast<float>(scale), o.t.data_ptr(),
                    static_cast<int>(out_type), o.batch_stride, o.head_stride, o.row_stride,
-                   want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(m), ws, ws_bytes,
-                   current_stream(q.t));
+                   want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(m), tail...);
   };
-  if (drop != nullptr) {
-    auto call_drop = [&](auto forward, auto ws) {
-      return forward(m, n, d, topo.nonzeros, batch, heads, topo.row_indices.data_ptr<int>(),
-                     topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(), dtype,
-                     q.t.data_ptr(), q.batch_stride, q.head_stride, q.row_stride, k.t.data_ptr(),
-                     k.batch_stride, k.head_stride, k.row_stride, v.t.data_ptr(), v.batch_stride,
-                     v.head_stride, v.row_stride, static_cast<float>(scale), o.t.data_ptr(),
-                     static_cast<int>(out_type), o.batch_stride, o.head_stride, o.row_stride,
-                     want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(m), drop->p,
-                     drop->rng, drop->rng_state_out, ws, ws_bytes, current_stream(q.t));
-    };
-    check_status(plan.has_value() ? call_drop(sputnik_hip_sparse_attention_heads_forward_planned_dropout,
-                                              static_cast<const void*>(plan->data_ptr()))
-                                  : call_drop(sputnik_hip_sparse_attention_heads_forward_dropout,
-                                              workspace.data_ptr()),
-                 "sparse_attention_heads_dropout");
-    return {out, want_lse ? lse : Tensor(), drop->rng_state};
-  }
-  const int status = plan.has_value()
-                         ? call(sputnik_hip_sparse_attention_heads_forward_planned,
-                                static_cast<const void*>(plan->data_ptr()))
-                         : call(sputnik_hip_sparse_attention_heads_forward, workspace.data_ptr());
-  check_status(status, "sparse_attention_heads");
-  if (want_lse) return {out, lse};
-  return {out};
+  check_status(run_forward(args, sputnik_hip_sparse_attention_heads_forward,
+                           sputnik_hip_sparse_attention_heads_forward_planned,
+                           sputnik_hip_sparse_attention_heads_forward_dropout,
+                           sputnik_hip_sparse_attention_heads_forward_planned_dropout, plan, ws_bytes, q.t,
+                           drop),
+               drop != nullptr ? "sparse_attention_heads_dropout" : "sparse_attention_heads");
+  return attention_result(out, lse, want_lse, drop);
 }
 
 // y [batch, seq, out] = x W^T per batch element in ROW orientation (sputnik_hip.h:
@@ -1886,10 +1868,7 @@ std::vector<Tensor> sparse_attention_many_mask_run(int64_t b, const Tensor& nonz
   Tensor lse = want_lse ? at::empty({mm.replicas, mm.m}, q.options()) : Tensor();
   int status = SPUTNIK_HIP_UNSUPPORTED;
   if (ws_bytes > 0) {
-    Tensor workspace;
-    if (plan.has_value()) check_plan(*plan, ws_bytes, q);
-    else workspace = at::empty({static_cast<int64_t>(ws_bytes)}, q.options().dtype(at::kByte));
-    auto call = [&](auto forward, auto ws) {
+    auto args = [&](auto forward, auto... tail) {
       return forward(mm.masks, mm.m, n, d, mm.nonzeros.data(), mm.replicas,
                      mm.row_indices.data_ptr<int>(), mm.row_offsets.data_ptr<int>(),
                      mm.column_indices.data_ptr<int>(), q.data_ptr<float>(),
@@ -1897,42 +1876,23 @@ std::vector<Tensor> sparse_attention_many_mask_run(int64_t b, const Tensor& nonz
                      static_cast<int64_t>(n) * d, v.data_ptr<float>(), static_cast<int64_t>(n) * d,
                      static_cast<float>(scale), out.data_ptr<float>(),
                      static_cast<int64_t>(mm.m) * d, want_lse ? lse.data_ptr<float>() : nullptr,
-                     static_cast<int64_t>(mm.m), ws, ws_bytes, current_stream(q));
+                     static_cast<int64_t>(mm.m), tail...);
     };
-    auto call_drop = [&](auto forward, auto ws) {
-      return forward(mm.masks, mm.m, n, d, mm.nonzeros.data(), mm.replicas,
-                     mm.row_indices.data_ptr<int>(), mm.row_offsets.data_ptr<int>(),
-                     mm.column_indices.data_ptr<int>(), q.data_ptr<float>(),
-                     static_cast<int64_t>(mm.m) * d, k.data_ptr<float>(),
-                     static_cast<int64_t>(n) * d, v.data_ptr<float>(), static_cast<int64_t>(n) * d,
-                     static_cast<float>(scale), out.data_ptr<float>(),
-                     static_cast<int64_t>(mm.m) * d, want_lse ? lse.data_ptr<float>() : nullptr,
-                     static_cast<int64_t>(mm.m), drop->p, drop->rng, drop->rng_state_out, ws,
-                     ws_bytes, current_stream(q));
-    };
-    if (drop != nullptr)
-      status = plan.has_value()
-                   ? call_drop(sputnik_hip_sparse_attention_many_mask_forward_planned_dropout,
-                               static_cast<const void*>(plan->data_ptr()))
-                   : call_drop(sputnik_hip_sparse_attention_many_mask_forward_dropout, workspace.data_ptr());
-    else
-      status = plan.has_value()
-                   ? call(sputnik_hip_sparse_attention_many_mask_forward_planned,
-                          static_cast<const void*>(plan->data_ptr()))
-                   : call(sputnik_hip_sparse_attention_many_mask_forward, workspace.data_ptr());
+    status = run_forward(args, sputnik_hip_sparse_attention_many_mask_forward,
+                         sputnik_hip_sparse_attention_many_mask_forward_planned,
+                         sputnik_hip_sparse_attention_many_mask_forward_dropout,
+                         sputnik_hip_sparse_attention_many_mask_forward_planned_dropout, plan, ws_bytes, q,
+                         drop);
   }
   if (status == SPUTNIK_HIP_UNSUPPORTED) {
     TORCH_CHECK(!want_lse || drop != nullptr, "sparse_attention_many_mask: lse needs a call the "
                 "fused kernel serves (head dimension 64, 16-byte aligned operands)");
     const Tensor composed = attention_many_mask_composed(b, nonzeros, q, k, v, mm.row_indices,
                                                          mm.row_offsets, mm.column_indices, scale, drop);
-    if (drop != nullptr) return {composed, Tensor(), drop->rng_state};
-    return {composed};
+    return attention_result(composed, Tensor(), false, drop);
   }
   check_status(status, "sparse_attention_many_mask");
-  if (drop != nullptr) return {out, want_lse ? lse : Tensor(), drop->rng_state};
-  if (want_lse) return {out, lse};
-  return {out};
+  return attention_result(out, lse, want_lse, drop);
 }
 
 // Topology-only pre-pass of both many-mask attention forms (16 unused bytes when the kernels
@@ -1973,19 +1933,8 @@ std::vector<Tensor> sparse_attention_heads_many_mask_run(int64_t b, const Tensor
               "sparse_attention_heads_many_mask: expected [batch, heads, rows, d] views");
   const HeadOperand q = head_operand(q_in, "query"), k = head_operand(k_in, "key"),
                     v = head_operand(v_in, "value");
+  const int dtype = check_head_operands(q, k, v, out_type, "sparse_attention_heads_many_mask");
   const auto st = q.t.scalar_type();
-  const int dtype = type_code(st);
-  TORCH_CHECK(dtype == SPUTNIK_HIP_F16 || dtype == SPUTNIK_HIP_BF16,
-              "sparse_attention_heads_many_mask: expected float16 / bfloat16 operands, got ", st);
-  TORCH_CHECK(k.t.scalar_type() == st && v.t.scalar_type() == st,
-              "sparse_attention_heads_many_mask: query, key, value must have one type");
-  TORCH_CHECK(k.t.sizes() == v.t.sizes(), "key and value must have one shape");
-  TORCH_CHECK(q.d == k.d, "query and key must have one head dimension");
-  TORCH_CHECK(q.batch == k.batch && q.heads == k.heads, "query and key must have one batch and head count");
-  TORCH_CHECK(q.t.device() == k.t.device() && q.t.device() == v.t.device(),
-              "query, key, value must be on one device");
-  TORCH_CHECK(out_type == SPUTNIK_HIP_F32 || out_type == dtype,
-              "sparse_attention_heads_many_mask: out_type is float32 or the operands' type");
   const c10::DeviceGuard guard(q.t.device());
   TORCH_CHECK(q.batch == b, "sparse_attention_heads_many_mask: batch (", q.batch,
               ") must equal the number of masks (", b, ")");
@@ -2003,10 +1952,7 @@ std::vector<Tensor> sparse_attention_heads_many_mask_run(int64_t b, const Tensor
       sputnik_hip_sparse_attention_many_mask_workspace_bytes(mm.masks, mm.m, n, d, mm.width);
   int status = SPUTNIK_HIP_UNSUPPORTED;
   if (ws_bytes > 0) {
-    Tensor workspace;
-    if (plan.has_value()) check_plan(*plan, ws_bytes, q.t);
-    else workspace = at::empty({static_cast<int64_t>(ws_bytes)}, q.t.options().dtype(at::kByte));
-    auto call = [&](auto forward, auto ws) {
+    auto args = [&](auto forward, auto... tail) {
       return forward(mm.masks, mm.m, n, d, mm.nonzeros.data(), mm.masks, heads,
                      mm.row_indices.data_ptr<int>(), mm.row_offsets.data_ptr<int>(),
                      mm.column_indices.data_ptr<int>(), dtype, q.t.data_ptr(), q.batch_stride,
@@ -2014,31 +1960,13 @@ std::vector<Tensor> sparse_attention_heads_many_mask_run(int64_t b, const Tensor
                      k.row_stride, v.t.data_ptr(), v.batch_stride, v.head_stride, v.row_stride,
                      static_cast<float>(scale), o.t.data_ptr(), static_cast<int>(out_type),
                      o.batch_stride, o.head_stride, o.row_stride,
-                     want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(mm.m), ws,
-                     ws_bytes, current_stream(q.t));
+                     want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(mm.m), tail...);
     };
-    auto call_drop = [&](auto forward, auto ws) {
-      return forward(mm.masks, mm.m, n, d, mm.nonzeros.data(), mm.masks, heads,
-                     mm.row_indices.data_ptr<int>(), mm.row_offsets.data_ptr<int>(),
-                     mm.column_indices.data_ptr<int>(), dtype, q.t.data_ptr(), q.batch_stride,
-                     q.head_stride, q.row_stride, k.t.data_ptr(), k.batch_stride, k.head_stride,
-                     k.row_stride, v.t.data_ptr(), v.batch_stride, v.head_stride, v.row_stride,
-                     static_cast<float>(scale), o.t.data_ptr(), static_cast<int>(out_type),
-                     o.batch_stride, o.head_stride, o.row_stride,
-                     want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(mm.m), drop->p,
-                     drop->rng, drop->rng_state_out, ws, ws_bytes, current_stream(q.t));
-    };
-    if (drop != nullptr)
-      status = plan.has_value()
-                   ? call_drop(sputnik_hip_sparse_attention_heads_many_mask_forward_planned_dropout,
-                               static_cast<const void*>(plan->data_ptr()))
-                   : call_drop(sputnik_hip_sparse_attention_heads_many_mask_forward_dropout,
-                               workspace.data_ptr());
-    else
-      status = plan.has_value()
-                   ? call(sputnik_hip_sparse_attention_heads_many_mask_forward_planned,
-                          static_cast<const void*>(plan->data_ptr()))
-                   : call(sputnik_hip_sparse_attention_heads_many_mask_forward, workspace.data_ptr());
+    status = run_forward(args, sputnik_hip_sparse_attention_heads_many_mask_forward,
+                         sputnik_hip_sparse_attention_heads_many_mask_forward_planned,
+                         sputnik_hip_sparse_attention_heads_many_mask_forward_dropout,
+                         sputnik_hip_sparse_attention_heads_many_mask_forward_planned_dropout, plan, ws_bytes,
+                         q.t, drop);
   }
   if (status == SPUTNIK_HIP_UNSUPPORTED) {
     TORCH_CHECK(!want_lse || drop != nullptr, "sparse_attention_heads_many_mask: lse needs a call "
@@ -2051,13 +1979,10 @@ std::vector<Tensor> sparse_attention_heads_many_mask_run(int64_t b, const Tensor
                                                         per_head(v), mm.row_indices,
                                                         mm.row_offsets, mm.column_indices, scale, drop);
     out.copy_(product.reshape(out.sizes()));
-    if (drop != nullptr) return {out, Tensor(), drop->rng_state};
-    return {out};
+    return attention_result(out, Tensor(), false, drop);
   }
   check_status(status, "sparse_attention_heads_many_mask");
-  if (drop != nullptr) return {out, want_lse ? lse : Tensor(), drop->rng_state};
-  if (want_lse) return {out, lse};
-  return {out};
+  return attention_result(out, lse, want_lse, drop);
 }
 
 // The dropout forms of the three ops above: {out, lse, rng_state} (lse undefined on the

@@ -410,24 +410,23 @@ def _sddmm(m, n, row_indices, row_offsets, column_indices, lhs_matrix, rhs_matri
         m, n, row_indices, row_offsets, column_indices, lhs_matrix, rhs_matrix, plan)
 
 
-def _attention(query, key, value, row_indices, row_offsets, column_indices, scale):
-    """Fused attention forward, through the cached plan of the mask when enabled."""
+def _attention_forward(query, key, value, row_indices, row_offsets, column_indices, scale, p=0.0,
+                       want_lse=False):
+    """Fused attention forward -> (out, lse or None, rng_state or None), through the cached
+    plan of the mask when enabled: the dropout op for p > 0, the lse ops for the fused
+    backward, else the plain ones."""
     plan = None if _plans is None else _plans.attention(query.size(-2), key.size(-2), query.size(-1),
                                                         row_indices, row_offsets, column_indices)
-    if plan is None:
-        return ops.sparse_attention(query, key, value, row_indices, row_offsets, column_indices,
-                                    scale)
-    return ops.sparse_attention_planned(query, key, value, row_indices, row_offsets,
-                                        column_indices, scale, plan)
-
-
-def _attention_dropout(query, key, value, row_indices, row_offsets, column_indices, scale, p):
-    """The fused forward with attention dropout p > 0 -> (out, rng_state)."""
-    plan = None if _plans is None else _plans.attention(query.size(-2), key.size(-2), query.size(-1),
-                                                        row_indices, row_offsets, column_indices)
-    out, _, rng_state = ops.sparse_attention_dropout(query, key, value, row_indices, row_offsets,
-                                                     column_indices, scale, p, plan)
-    return out, rng_state
+    operands = (query, key, value, row_indices, row_offsets, column_indices, scale)
+    if p > 0.0:
+        return ops.sparse_attention_dropout(*operands, p, plan)
+    if want_lse:
+        out, lse = (ops.sparse_attention_with_lse(*operands) if plan is None
+                    else ops.sparse_attention_with_lse_planned(*operands, plan))
+        return out, lse, None
+    out = (ops.sparse_attention(*operands) if plan is None
+           else ops.sparse_attention_planned(*operands, plan))
+    return out, None, None
 
 
 # ---------------------------------------------------------------------------
@@ -900,14 +899,13 @@ class SparseAttentionFunction(torch.autograd.Function):
     def forward(ctx, query, key, value, row_indices, row_offsets, column_indices, scale,
                 dropout_p=0.0):
         ctx.scale, ctx.p = float(scale), float(dropout_p)
+        out, _, rng_state = _attention_forward(query, key, value, row_indices, row_offsets,
+                                               column_indices, scale, ctx.p)
         if ctx.p > 0.0:
-            out, rng_state = _attention_dropout(query, key, value, row_indices, row_offsets,
-                                                column_indices, scale, ctx.p)
             ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices,
                                   rng_state)
-            return out
-        out = _attention(query, key, value, row_indices, row_offsets, column_indices, scale)
-        ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices)
+        else:
+            ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices)
         return out
 
     @staticmethod
@@ -924,23 +922,6 @@ class SparseAttentionFunction(torch.autograd.Function):
 # Fused backward (ops.sparse_attention_backward): the forward keeps its output
 # and row log-sum-exp, the backward runs two kernels over the mask and its cached transpose.
 # ---------------------------------------------------------------------------
-def _attention_lse(query, key, value, row_indices, row_offsets, column_indices, scale, p):
-    """The fused forward that also returns lse -> (out, lse, rng_state or None), through the
-    cached plan of the mask when enabled."""
-    plan = None if _plans is None else _plans.attention(query.size(-2), key.size(-2), query.size(-1),
-                                                        row_indices, row_offsets, column_indices)
-    if p > 0.0:
-        return ops.sparse_attention_dropout(query, key, value, row_indices, row_offsets,
-                                            column_indices, scale, p, plan)
-    if plan is None:
-        out, lse = ops.sparse_attention_with_lse(query, key, value, row_indices, row_offsets,
-                                                 column_indices, scale)
-    else:
-        out, lse = ops.sparse_attention_with_lse_planned(query, key, value, row_indices,
-                                                         row_offsets, column_indices, scale, plan)
-    return out, lse, None
-
-
 def fused_backward_served(query, key, column_indices):
     """Whether the fused forward and the fused backward both serve these operands: float32,
     head dimension 64, a mask with entries, offsets within 32 bits.  Elsewhere
@@ -963,8 +944,8 @@ class FusedBackwardAttentionFunction(torch.autograd.Function):
     def forward(ctx, query, key, value, row_indices, row_offsets, column_indices, scale,
                 dropout_p=0.0):
         ctx.scale, ctx.p = float(scale), float(dropout_p)
-        out, lse, rng_state = _attention_lse(query, key, value, row_indices, row_offsets,
-                                             column_indices, scale, ctx.p)
+        out, lse, rng_state = _attention_forward(query, key, value, row_indices, row_offsets,
+                                                 column_indices, scale, ctx.p, want_lse=True)
         ctx.save_for_backward(query, key, value, out, lse, row_indices, row_offsets,
                               column_indices, rng_state)
         return out
@@ -1000,9 +981,7 @@ def sparse_attention(query, key, value, row_indices, row_offsets, column_indices
         if fused_backward and fused_backward_served(query, key, column_indices):
             return FusedBackwardAttentionFunction.apply(query, key, value, *topo, scale, p)
         return SparseAttentionFunction.apply(query, key, value, *topo, scale, p)
-    if p > 0.0:
-        return _attention_dropout(query, key, value, *topo, scale, p)[0]
-    return _attention(query, key, value, *topo, scale)
+    return _attention_forward(query, key, value, *topo, scale, p)[0]
 
 
 # ---------------------------------------------------------------------------
@@ -1317,28 +1296,23 @@ def _many_mask_forward(b, nonzeros, topo, query, key, value, scale, p=0.0):
     """[R, S, D] forward: the fused kernel on GPU tensors (the heads kernel for half storage,
     whose [R, S, D] is a [b, R/b, S, D] head view), the composition elsewhere.  With dropout
     p > 0 -> (out, rng_state)."""
-    if p > 0.0:
-        plan = _many_mask_topology(b, query.size(-2), key.size(-2), query.size(-1), nonzeros, *topo)
-        if query.dtype in (torch.float16, torch.bfloat16):
-            def heads(x):
-                return x.unflatten(0, (b, x.size(0) // b))
-            out, _, rng_state = ops.sparse_attention_heads_many_mask_dropout(
-                b, nonzeros, *topo, heads(query), heads(key), heads(value), scale, p, plan=plan)
-            return out.flatten(0, 1), rng_state
-        out, _, rng_state = ops.sparse_attention_many_mask_dropout(b, nonzeros, *topo, query, key, value,
-                                                                   scale, p, plan=plan)
-        return out, rng_state
-    if not query.is_cuda:
+    if p == 0.0 and not query.is_cuda:
         return _many_mask_composed(b, nonzeros, topo, query.float(), key.float(), value.float(),
                                    scale).to(query.dtype)
     plan = _many_mask_topology(b, query.size(-2), key.size(-2), query.size(-1), nonzeros, *topo)
-    if query.dtype in (torch.float16, torch.bfloat16):
-        def heads(x):
-            return x.unflatten(0, (b, x.size(0) // b))
-        out = ops.sparse_attention_heads_many_mask(b, nonzeros, *topo, heads(query), heads(key),
-                                                   heads(value), scale, plan=plan)
-        return out.flatten(0, 1)   # ([b, H, S, D] view of a [b, S, H, D] buffer: one copy)
-    return ops.sparse_attention_many_mask(b, nonzeros, *topo, query, key, value, scale, plan=plan)
+    half = query.dtype in (torch.float16, torch.bfloat16)
+    if half:
+        query, key, value = (x.unflatten(0, (b, x.size(0) // b)) for x in (query, key, value))
+    operands = (b, nonzeros, *topo, query, key, value, scale)
+    if p > 0.0:
+        op = ops.sparse_attention_heads_many_mask_dropout if half else ops.sparse_attention_many_mask_dropout
+        out, _, rng_state = op(*operands, p, plan=plan)
+    else:
+        op = ops.sparse_attention_heads_many_mask if half else ops.sparse_attention_many_mask
+        out = op(*operands, plan=plan)
+    if half:
+        out = out.flatten(0, 1)   # ([b, H, S, D] view of a [b, S, H, D] buffer: one copy)
+    return (out, rng_state) if p > 0.0 else out
 
 
 def _float_per_replica(x):
@@ -1437,26 +1411,21 @@ def _heads_many_mask_forward(query, key, value, nonzeros, topo, scale, p=0.0):
     """-> [B, m, H, D]; with dropout p > 0 -> (out, rng_state)."""
     b, heads = query.size(0), query.size(2)
     q, k, v = (x.transpose(1, 2) for x in (query, key, value))   # [B, H, S, D] views
-    if p > 0.0:
-        if query.dtype in (torch.float16, torch.bfloat16):
-            plan = _many_mask_topology(b, q.size(-2), k.size(-2), q.size(-1), nonzeros, *topo)
+    if query.dtype in (torch.float16, torch.bfloat16) and (p > 0.0 or query.is_cuda):
+        plan = _many_mask_topology(b, q.size(-2), k.size(-2), q.size(-1), nonzeros, *topo)
+        if p > 0.0:
             out, _, rng_state = ops.sparse_attention_heads_many_mask_dropout(b, nonzeros, *topo, q, k, v,
                                                                              scale, p, plan=plan)
-            return out.transpose(1, 2), rng_state
-        per_head = [x.reshape(b * heads, x.size(2), x.size(3)) for x in (q, k, v)]
-        out, rng_state = _many_mask_forward(b, nonzeros, topo, *per_head, scale, p)
-        return out.reshape(b, heads, query.size(1), -1).transpose(1, 2).to(query.dtype), rng_state
-    if query.is_cuda:
-        if query.dtype in (torch.float16, torch.bfloat16):
-            plan = _many_mask_topology(b, q.size(-2), k.size(-2), q.size(-1), nonzeros, *topo)
+        else:
             out = ops.sparse_attention_heads_many_mask(b, nonzeros, *topo, q, k, v, scale, plan=plan)
-            return out.transpose(1, 2)   # the kernel's [B, S, H, D] buffer
+        out = out.transpose(1, 2)   # the kernel's [B, S, H, D] buffer
+    else:   # float32 views, CPU tensors: one copy to [B*H, S, D]
         per_head = [x.reshape(b * heads, x.size(2), x.size(3)) for x in (q, k, v)]
-        out = _many_mask_forward(b, nonzeros, topo, *per_head, scale)
-    else:
-        per_head = [x.float().reshape(b * heads, x.size(2), x.size(3)) for x in (q, k, v)]
-        out = _many_mask_composed(b, nonzeros, topo, *per_head, scale)
-    return out.reshape(b, heads, query.size(1), -1).transpose(1, 2).to(query.dtype)
+        out = _many_mask_forward(b, nonzeros, topo, *per_head, scale, p)
+        if p > 0.0:
+            out, rng_state = out
+        out = out.reshape(b, heads, query.size(1), -1).transpose(1, 2).to(query.dtype)
+    return (out, rng_state) if p > 0.0 else out
 
 
 def sparse_attention_heads_many_mask(query, key, value, nonzeros, row_indices, row_offsets,

@@ -183,12 +183,8 @@ class SparseAttention(nn.Module):
         needs_grad = torch.is_grad_enabled() and (
             q3d.requires_grad or k3d.requires_grad or v3d.requires_grad)
         if self.fused_inference and not needs_grad:
-            if p > 0.0:
-                out = functional._attention_dropout(q3d, k3d, v3d, self.row_indices, self.row_offsets,
-                                                    self.column_indices, scale, p)[0]
-            else:
-                out = functional._attention(q3d, k3d, v3d, self.row_indices, self.row_offsets,
-                                            self.column_indices, scale)
+            out = functional._attention_forward(q3d, k3d, v3d, self.row_indices, self.row_offsets,
+                                                self.column_indices, scale, p)[0]
             return functional.transpose_last2(out) if merged else out
         if self.fused_backward and needs_grad:
             out = functional.sparse_attention(q3d, k3d, v3d, self.row_indices, self.row_offsets,
