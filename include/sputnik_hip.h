@@ -1008,7 +1008,7 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_many_mask_forward_planned
  *   workspace      at least sputnik_hip_sparse_attention_backward_workspace_bytes, 16-byte
  *                  aligned, per call (the D_i of every row; nothing is kept between calls).
  * Strides are per replica, in elements.  Two launches, no atomics (bitwise reproducible),
- * no host synchronisation.  Served: d = 64, m * 64 * 4 and n * 64 * 4 below 2^32, 16-byte
+ * no host synchronisation.  Served: d = 64 or 128, m * d * 4 and n * d * 4 below 2^32, 16-byte
  * aligned operands and strides that are multiples of 4
  * (sputnik_hip_sparse_attention_backward_supported); anything else returns
  * SPUTNIK_HIP_UNSUPPORTED and the caller composes the backward from the operators.
@@ -1033,6 +1033,30 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_attention_backward(int m, int n, int d, i
                              int64_t grad_v_stride, double p, sputnik_hip_philox_state rng,
                              void* workspace, size_t workspace_bytes,
                              sputnik_hip_stream_t stream);
+
+/*
+ * Fused sparse attention forward in the row-group form: what
+ * sputnik_hip_sparse_attention_forward_dropout computes -- out, and lse (the log-sum-exp of
+ * the undropped scores; may be NULL) for sputnik_hip_sparse_attention_backward -- at head
+ * dimension 128, which the LDS-staged forward does not serve.  One 16-lane row group per
+ * query row gathers the K and V rows of the row's entries from L2 and keeps an online softmax
+ * in registers; one launch (per 65535 replicas), no workspace, no plan, no atomics (bitwise
+ * reproducible), no host synchronisation.  The order of a row's columns does not matter.
+ * The arguments are those of sputnik_hip_sparse_attention_forward_dropout without the
+ * workspace; p = 0 drops nothing and touches neither the state nor rng_state_out.
+ * Served (sputnik_hip_sparse_attention_rows_supported): d = 128, m, n and nonzeros above 0,
+ * m * d * 4 and n * d * 4 below 2^32, 16-byte aligned operands and strides that are multiples
+ * of 4; anything else returns SPUTNIK_HIP_UNSUPPORTED before any launch.
+ */
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_rows_supported(int m, int n, int d, int nonzeros);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_rows_forward(int m, int n, int d, int nonzeros,
+                             int replicas, const int* row_indices, const int* row_offsets,
+                             const int* column_indices, const float* q, int64_t q_stride,
+                             const float* k, int64_t k_stride, const float* v,
+                             int64_t v_stride, float scale, float* out, int64_t out_stride,
+                             float* lse, int64_t lse_stride, double p, sputnik_hip_philox_state rng,
+                             int64_t* rng_state_out, sputnik_hip_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * "many mask" family: `masks` topologies of the same m x n shape, laid out

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """The fused sparse attention backward (SparseAttention(fused_backward=True),
 functional.FusedBackwardAttentionFunction) against the composed one (low_memory_training,
-functional.SparseAttentionFunction): the backward ALONE, timed with device events (median of
---reps windows of --steps calls after --warmup), and the peak memory one backward allocates
-on top of what was live before it.  The mask is registered as static, so both backwards take
+functional.SparseAttentionFunction): the forward ALONE and the backward ALONE, each timed with
+device events (median of --reps windows of --steps calls after --warmup), and the peak memory
+one forward and one backward allocate on top of what was live before them.  --head-dim 64
+(the LDS-staged forward) or 128 (the row-group forward, ops.sparse_attention_rows); at any
+other width both routes are the composed one.  The mask is registered as static, so both backwards take
 the transposed topology and the kernel plans from the caches, as a module's do.
 
   c3:   config 3's attention, B = 8 x H = 8 replicas, S = 1024, d = 64, density 0.1
@@ -13,7 +15,8 @@ One JSON line per shape, route and dropout p.  Run under
 `rocprofv3 --kernel-trace --stats -- python tools/attention_backward_bench.py --shapes c3`
 for the kernel times.
 
-    python tools/attention_backward_bench.py [--shapes c3,long] [--p 0,0.1] [--out FILE]
+    python tools/attention_backward_bench.py [--shapes c3,long] [--p 0,0.1] [--head-dim 64]
+                                             [--out FILE]
 """
 import argparse
 import json
@@ -35,11 +38,8 @@ SHAPES = {
 }
 
 
-def time_backward(y, inputs, go, steps, warmup, reps):
-    """Median and minimum over `reps` windows of the per-call time (ms) of the backward."""
-    def call():
-        torch.autograd.grad(y, inputs, go, retain_graph=True)
-
+def time_call(call, steps, warmup, reps):
+    """Median and minimum over `reps` windows of the per-call time (ms) of `call`."""
     for _ in range(warmup):
         call()
     times = []
@@ -55,14 +55,15 @@ def time_backward(y, inputs, go, steps, warmup, reps):
     return statistics.median(times), min(times)
 
 
-def peak_backward_bytes(y, inputs, go):
+def peak_bytes(call):
+    """Peak of what `call` allocates on top of what was live before it (its result included)."""
     torch.cuda.synchronize()
     before = torch.cuda.memory_allocated()
     torch.cuda.reset_peak_memory_stats()
-    grads = torch.autograd.grad(y, inputs, go, retain_graph=True)
+    result = call()
     torch.cuda.synchronize()
     peak = torch.cuda.max_memory_allocated() - before
-    del grads
+    del result
     return peak
 
 
@@ -73,6 +74,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--head-dim", type=int, default=64)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -81,7 +83,8 @@ def main():
     out = open(args.out, "a") if args.out else None
     for name in args.shapes.split(","):
         shape = SHAPES[name]
-        R, S, d = shape["R"], shape["S"], 64
+        R, S, d = shape["R"], shape["S"], args.head_dim
+        scale = d ** -0.5
         topo = random_csr(S, S, shape["density"], dev, seed=3)[:3]
         nnz = topo[2].numel()
         functional.register_static_topology(*topo)
@@ -93,11 +96,19 @@ def main():
             # alternate the two routes, so that drift on the host touches both alike
             for rep in range(2):
                 for fused in (True, False):
-                    y = functional.sparse_attention(q, k, v, *topo, 0.125, dropout_p=p,
-                                                    fused_backward=fused)
-                    med, best = time_backward(y, (q, k, v), go, args.steps, args.warmup, args.reps)
-                    peak = peak_backward_bytes(y, (q, k, v), go)
-                    results.setdefault(fused, []).append((med, best, peak))
+                    def forward():
+                        return functional.sparse_attention(q, k, v, *topo, scale, dropout_p=p,
+                                                           fused_backward=fused)
+
+                    y = forward()
+
+                    def backward():
+                        return torch.autograd.grad(y, (q, k, v), go, retain_graph=True)
+
+                    med, best = time_call(backward, args.steps, args.warmup, args.reps)
+                    fwd, _ = time_call(forward, args.steps, args.warmup, args.reps)
+                    results.setdefault(fused, []).append(
+                        (med, best, peak_bytes(backward), fwd, peak_bytes(forward)))
                     del y
             for fused in (True, False):
                 med = min(r[0] for r in results[fused])
@@ -106,6 +117,8 @@ def main():
                             backward_ms=round(med, 4),
                             backward_min_ms=round(min(r[1] for r in results[fused]), 4),
                             peak_backward_mb=round(max(r[2] for r in results[fused]) / 1e6, 2),
+                            forward_ms=round(min(r[3] for r in results[fused]), 4),
+                            peak_forward_mb=round(max(r[4] for r in results[fused]) / 1e6, 2),
                             r_nnz_f32_mb=round(R * nnz * 4 / 1e6, 2),
                             grads_mb=round(3 * R * S * d * 4 / 1e6, 2),
                             device=torch.cuda.get_device_name(dev))

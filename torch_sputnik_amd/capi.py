@@ -191,6 +191,10 @@ SIGNATURES = {
         _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_float, _c_ptr, _c_i64, _c_ptr, _c_i64,
         _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64]
         + [ctypes.c_double, PhiloxState] + [_c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_rows_supported": (_c_int, [_c_int] * 4),
+    "sputnik_hip_sparse_attention_rows_forward": (_c_int, [_c_int] * 5 + [
+        _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_float, _c_ptr,
+        _c_i64, _c_ptr, _c_i64] + _DROP + [_c_ptr]),
     "sputnik_hip_sparse_attention_heads_forward_dropout": (_c_int, [_c_int] * 6 + [_c_ptr] * 3 + [_c_int] + [
         _c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [_c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64]
         + _DROP + [_c_ptr, _c_size, _c_ptr]),

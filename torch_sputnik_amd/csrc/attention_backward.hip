@@ -12,7 +12,7 @@
 //   rows:    one row group per query row i of the mask (in row_indices order: rows of like
 //            length side by side).  It forms D_i from the dO and O rows, stores it into the caller's workspace for
 //            the second launch and, when dQ is wanted, walks the row's entries: K and V rows
-//            gathered from L2 (float4 per lane, 256 contiguous bytes per row), the two dot
+//            gathered from L2 (float4 per lane, 256 contiguous bytes per load), the two dot
 //            products reduced over the 16 lanes by DPP, dQ_i accumulated in registers.
 //   columns: one row group per key row j of the TRANSPOSED mask (its row_indices order):
 //            slot t holds query row i and the original entry e = permutation[t], which keys
@@ -22,57 +22,24 @@
 // of the window (one Philox call per lane and window, keep_window) and a ballot shares the
 // bits.  Entries are taken kUnroll at a time so that their gathers are in flight together.
 // Rows without entries give zero gradient rows (their lse of -inf is never read).
-// Offsets inside a replica are 32-bit: m * 64 * 4 and n * 64 * 4 below 2^32 (supported()).
+// The kernels are templates on the head dimension D (64 or 128): a lane owns D / 16 columns,
+// one float4 at D = 64 and two at D = 128 (columns 4i.. and 64 + 4i..: attention_rowgroup.h).
+// Offsets inside a replica are 32-bit: m * D * 4 and n * D * 4 below 2^32 (supported()).
 #include <math.h>
 
 #include <utility>
 
-#include "common.h"
-#include "philox.h"
-#include "wave_utils.h"
+#include "attention_rowgroup.h"
 
 namespace sputnik_hip {
 namespace {
 
-constexpr int kD = 64;             // head dimension served
-constexpr int kGroup = 16;         // lanes per row group (4 columns each)
-constexpr int kThreads = 256;      // 16 row groups per workgroup
-constexpr int kRowsPerBlock = kThreads / kGroup;
-constexpr int kUnroll = 4;         // entries whose gathers are issued together
+using namespace rowgroup;
 
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
-  float s = a.x * b.x;
-  s = fmaf(a.y, b.y, s);
-  s = fmaf(a.z, b.z, s);
-  return fmaf(a.w, b.w, s);
-}
-
-__device__ __forceinline__ void fma4(float4& acc, float a, const float4& b) {
-  acc.x = fmaf(a, b.x, acc.x);
-  acc.y = fmaf(a, b.y, acc.y);
-  acc.z = fmaf(a, b.z, acc.z);
-  acc.w = fmaf(a, b.w, acc.w);
-}
-
-__device__ __forceinline__ float4 load4(const float* __restrict__ base, unsigned offset) {
-  return *reinterpret_cast<const float4*>(base + offset);
-}
-
-// Dropout decisions of the entries [w, end) of a row group's list, end - w <= 16, entry
-// w + u in bit u: lane u makes the one Philox call for list position w + u (original entry
-// entry_of(w + u)) and a ballot hands the decisions to the whole group -- one call per lane
-// and window instead of one per lane and entry.  Every lane of the group takes part.
-template <typename EntryOf>
-__device__ __forceinline__ unsigned keep_window(const PhiloxKey& key, const DropArgs& drop, int r,
-                                                int w, int end, EntryOf entry_of) {
-  const int i = threadIdx.x % kGroup;
-  const bool kept = w + i < end && philox_keep(key, drop.threshold, r, entry_of(w + i));
-  const int base = (threadIdx.x % kWave) & ~(kGroup - 1);
-  return static_cast<unsigned>(__ballot(kept) >> base) & 0xffffu;
-}
-
-__device__ __forceinline__ DropArgs drop_of() { return DropArgs{}; }
-__device__ __forceinline__ DropArgs drop_of(const DropArgs& d) { return d; }
+// Entries whose gathers are issued together, at either D.  Per entry a lane holds 2 * D / 16
+// floats of gathered rows; at D = 128 the columns kernel, with two accumulators and two rows
+// of its own besides, still stays out of scratch with four (104 VGPRs with dropout).
+constexpr int kUnroll = 4;
 
 // Pointers and strides of one launch (replica 0 of the launch at the bases).
 struct BackwardArgs {
@@ -95,7 +62,7 @@ struct BackwardArgs {
 };
 
 // Rows launch: D_i for every query row, and dQ_i when a.dq is set.
-template <typename... Drop>
+template <int D, typename... Drop>
 __global__ __launch_bounds__(kThreads) void attention_backward_rows_kernel(BackwardArgs a,
                                                                            Drop... drop_arg) {
   constexpr bool DROP = sizeof...(Drop) > 0;
@@ -105,30 +72,29 @@ __global__ __launch_bounds__(kThreads) void attention_backward_rows_kernel(Backw
   const int i = threadIdx.x % kGroup;
   const int replica = blockIdx.y;
   const int row = a.row_indices[slot];
-  const unsigned own = static_cast<unsigned>(row) * kD + 4 * i;
-  const float4 go = load4(a.dout + replica * a.dout_stride, own);
-  const float4 o = load4(a.out + replica * a.out_stride, own);
-  const float dterm = group_sum<kGroup>(dot4(go, o));
+  const unsigned own = static_cast<unsigned>(row) * D + 4 * i;
+  const Frag<D> go = load_frag<D>(a.dout + replica * a.dout_stride, own);
+  const Frag<D> o = load_frag<D>(a.out + replica * a.out_stride, own);
+  const float dterm = group_sum<kGroup>(dot(go, o));
   if (i == 0) a.dterm[static_cast<int64_t>(replica) * a.m + row] = dterm;
   if (a.dq == nullptr) return;
 
   const float* __restrict__ k = a.k + replica * a.k_stride;
   const float* __restrict__ v = a.v + replica * a.v_stride;
-  const float4 qf = load4(a.q + replica * a.q_stride, own);
-  const float4 qs = make_float4(qf.x * a.scale, qf.y * a.scale, qf.z * a.scale, qf.w * a.scale);
+  const Frag<D> qs = scaled(load_frag<D>(a.q + replica * a.q_stride, own), a.scale);
   const int p0 = a.row_offsets[row], p1 = a.row_offsets[row + 1];
   const float lse = p1 > p0 ? a.lse[replica * a.lse_stride + row] : 0.f;
   PhiloxKey key{};
   if constexpr (DROP) key = philox_key(drop, false);
   const int drop_r = replica + drop.replica0;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  Frag<D> acc = zero_frag<D>();
 
-  auto entry = [&](bool kept, const float4& kf, const float4& vf) {
-    const float s = group_sum<kGroup>(dot4(qs, kf));
-    float dp = group_sum<kGroup>(dot4(go, vf));
+  auto entry = [&](bool kept, const Frag<D>& kf, const Frag<D>& vf) {
+    const float s = group_sum<kGroup>(dot(qs, kf));
+    float dp = group_sum<kGroup>(dot(go, vf));
     if constexpr (DROP) dp = kept ? dp * drop.scale : 0.f;
     const float ds = __expf(s - lse) * (dp - dterm) * a.scale;
-    fma4(acc, ds, kf);
+    fma(acc, ds, kf);
   };
 
   for (int w = p0; w < p1; w += kGroup) {   // windows of 16 entries
@@ -137,26 +103,26 @@ __global__ __launch_bounds__(kThreads) void attention_backward_rows_kernel(Backw
     if constexpr (DROP) bits = keep_window(key, drop, drop_r, w, end, [](int e) { return e; });
     int p = w;
     for (; p + kUnroll <= end; p += kUnroll) {
-      float4 kf[kUnroll], vf[kUnroll];
+      Frag<D> kf[kUnroll], vf[kUnroll];
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
-        const unsigned col = static_cast<unsigned>(a.column_indices[p + u]) * kD + 4 * i;
-        kf[u] = load4(k, col);
-        vf[u] = load4(v, col);
+        const unsigned col = static_cast<unsigned>(a.column_indices[p + u]) * D + 4 * i;
+        kf[u] = load_frag<D>(k, col);
+        vf[u] = load_frag<D>(v, col);
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) entry((bits >> (p + u - w)) & 1u, kf[u], vf[u]);
     }
     for (; p < end; ++p) {
-      const unsigned col = static_cast<unsigned>(a.column_indices[p]) * kD + 4 * i;
-      entry((bits >> (p - w)) & 1u, load4(k, col), load4(v, col));
+      const unsigned col = static_cast<unsigned>(a.column_indices[p]) * D + 4 * i;
+      entry((bits >> (p - w)) & 1u, load_frag<D>(k, col), load_frag<D>(v, col));
     }
   }
-  *reinterpret_cast<float4*>(a.dq + replica * a.dq_stride + own) = acc;
+  store_frag<D>(a.dq + replica * a.dq_stride, own, acc);
 }
 
 // Columns launch over the transposed mask: dK_j and / or dV_j (a.dk, a.dv may be NULL).
-template <typename... Drop>
+template <int D, typename... Drop>
 __global__ __launch_bounds__(kThreads) void attention_backward_columns_kernel(BackwardArgs a,
                                                                               Drop... drop_arg) {
   constexpr bool DROP = sizeof...(Drop) > 0;
@@ -166,10 +132,9 @@ __global__ __launch_bounds__(kThreads) void attention_backward_columns_kernel(Ba
   const int i = threadIdx.x % kGroup;
   const int replica = blockIdx.y;
   const int row = a.row_indices[slot];   // key row j
-  const unsigned own = static_cast<unsigned>(row) * kD + 4 * i;
-  const float4 kf = load4(a.k + replica * a.k_stride, own);
-  const float4 ks = make_float4(kf.x * a.scale, kf.y * a.scale, kf.z * a.scale, kf.w * a.scale);
-  const float4 vf = load4(a.v + replica * a.v_stride, own);
+  const unsigned own = static_cast<unsigned>(row) * D + 4 * i;
+  const Frag<D> ks = scaled(load_frag<D>(a.k + replica * a.k_stride, own), a.scale);
+  const Frag<D> vf = load_frag<D>(a.v + replica * a.v_stride, own);
   const float* __restrict__ q = a.q + replica * a.q_stride;
   const float* __restrict__ dout = a.dout + replica * a.dout_stride;
   const float* __restrict__ lse = a.lse + replica * a.lse_stride;
@@ -177,20 +142,20 @@ __global__ __launch_bounds__(kThreads) void attention_backward_columns_kernel(Ba
   PhiloxKey key{};
   if constexpr (DROP) key = philox_key(drop, false);
   const int drop_r = replica + drop.replica0;
-  float4 acc_k = make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 acc_v = make_float4(0.f, 0.f, 0.f, 0.f);
+  Frag<D> acc_k = zero_frag<D>();
+  Frag<D> acc_v = zero_frag<D>();
 
-  auto entry = [&](bool kept, int qrow, const float4& qf, const float4& go) {
-    const float s = group_sum<kGroup>(dot4(qf, ks));
-    float dp = group_sum<kGroup>(dot4(go, vf));
+  auto entry = [&](bool kept, int qrow, const Frag<D>& qf, const Frag<D>& go) {
+    const float s = group_sum<kGroup>(dot(qf, ks));
+    float dp = group_sum<kGroup>(dot(go, vf));
     const float pr = __expf(s - lse[qrow]);
     float pd = pr;
     if constexpr (DROP) {
       dp = kept ? dp * drop.scale : 0.f;
       pd = kept ? pr * drop.scale : 0.f;
     }
-    fma4(acc_k, pr * (dp - dterm[qrow]) * a.scale, qf);
-    fma4(acc_v, pd, go);
+    fma(acc_k, pr * (dp - dterm[qrow]) * a.scale, qf);
+    fma(acc_v, pd, go);
   };
 
   const int t0 = a.row_offsets[row], t1 = a.row_offsets[row + 1];
@@ -202,35 +167,30 @@ __global__ __launch_bounds__(kThreads) void attention_backward_columns_kernel(Ba
     int t = w;
     for (; t + kUnroll <= end; t += kUnroll) {
       int qrow[kUnroll];
-      float4 qf[kUnroll], go[kUnroll];
+      Frag<D> qf[kUnroll], go[kUnroll];
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         qrow[u] = a.column_indices[t + u];
-        const unsigned off = static_cast<unsigned>(qrow[u]) * kD + 4 * i;
-        qf[u] = load4(q, off);
-        go[u] = load4(dout, off);
+        const unsigned off = static_cast<unsigned>(qrow[u]) * D + 4 * i;
+        qf[u] = load_frag<D>(q, off);
+        go[u] = load_frag<D>(dout, off);
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) entry((bits >> (t + u - w)) & 1u, qrow[u], qf[u], go[u]);
     }
     for (; t < end; ++t) {
       const int qrow = a.column_indices[t];
-      const unsigned off = static_cast<unsigned>(qrow) * kD + 4 * i;
-      entry((bits >> (t - w)) & 1u, qrow, load4(q, off), load4(dout, off));
+      const unsigned off = static_cast<unsigned>(qrow) * D + 4 * i;
+      entry((bits >> (t - w)) & 1u, qrow, load_frag<D>(q, off), load_frag<D>(dout, off));
     }
   }
-  if (a.dk != nullptr) *reinterpret_cast<float4*>(a.dk + replica * a.dk_stride + own) = acc_k;
-  if (a.dv != nullptr) *reinterpret_cast<float4*>(a.dv + replica * a.dv_stride + own) = acc_v;
+  if (a.dk != nullptr) store_frag<D>(a.dk + replica * a.dk_stride, own, acc_k);
+  if (a.dv != nullptr) store_frag<D>(a.dv + replica * a.dv_stride, own, acc_v);
 }
 
 bool supported(int m, int n, int d, int nonzeros) {
-  return d == kD && m > 0 && n > 0 && nonzeros >= 0 &&
-         static_cast<int64_t>(m) * kD * 4 < (int64_t{1} << 32) &&
-         static_cast<int64_t>(n) * kD * 4 < (int64_t{1} << 32);
-}
-
-bool operand_ok(const float* p, int64_t stride) {
-  return p == nullptr || (aligned_to(p, 16) && stride % 4 == 0 && stride >= 0);
+  return (d == 64 || d == 128) && m > 0 && n > 0 && nonzeros >= 0 && rows_fit_32_bits(m, d) &&
+         rows_fit_32_bits(n, d);
 }
 
 // Launch `kernel` once per 65535 replicas, the bases moved to the launch's first replica.
@@ -255,6 +215,31 @@ int launch_replicas(Kernel kernel, int rows, int replicas, BackwardArgs a, const
     if (st != 0) return st;
   }
   return 0;
+}
+
+template <int D>
+void launch_rows_kernel(dim3 grid, const BackwardArgs& b, const DropArgs* dr, int r0, hipStream_t s) {
+  if (dr != nullptr) {
+    DropArgs dd = *dr;
+    dd.replica0 = r0;
+    hipLaunchKernelGGL((attention_backward_rows_kernel<D, DropArgs>), grid, dim3(kThreads), 0, s,
+                       b, dd);
+  } else {
+    hipLaunchKernelGGL((attention_backward_rows_kernel<D>), grid, dim3(kThreads), 0, s, b);
+  }
+}
+
+template <int D>
+void launch_columns_kernel(dim3 grid, const BackwardArgs& b, const DropArgs* dr, int r0,
+                           hipStream_t s) {
+  if (dr != nullptr) {
+    DropArgs dd = *dr;
+    dd.replica0 = r0;
+    hipLaunchKernelGGL((attention_backward_columns_kernel<D, DropArgs>), grid, dim3(kThreads), 0,
+                       s, b, dd);
+  } else {
+    hipLaunchKernelGGL((attention_backward_columns_kernel<D>), grid, dim3(kThreads), 0, s, b);
+  }
 }
 
 }  // namespace
@@ -334,27 +319,15 @@ int sputnik_hip_sparse_attention_backward(
   a.dterm = static_cast<float*>(workspace);
   a.scale = scale;
 
-  auto launch_rows = [](dim3 grid, const BackwardArgs& b, const DropArgs* dr, int r0,
-                        hipStream_t s) {
-    if (dr != nullptr) {
-      DropArgs dd = *dr;
-      dd.replica0 = r0;
-      hipLaunchKernelGGL((attention_backward_rows_kernel<DropArgs>), grid, dim3(kThreads), 0, s,
-                         b, dd);
-    } else {
-      hipLaunchKernelGGL((attention_backward_rows_kernel<>), grid, dim3(kThreads), 0, s, b);
-    }
+  auto launch_rows = [d](dim3 grid, const BackwardArgs& b, const DropArgs* dr, int r0,
+                         hipStream_t s) {
+    if (d == 64) launch_rows_kernel<64>(grid, b, dr, r0, s);
+    else launch_rows_kernel<128>(grid, b, dr, r0, s);
   };
-  auto launch_columns = [](dim3 grid, const BackwardArgs& b, const DropArgs* dr, int r0,
-                           hipStream_t s) {
-    if (dr != nullptr) {
-      DropArgs dd = *dr;
-      dd.replica0 = r0;
-      hipLaunchKernelGGL((attention_backward_columns_kernel<DropArgs>), grid, dim3(kThreads), 0,
-                         s, b, dd);
-    } else {
-      hipLaunchKernelGGL((attention_backward_columns_kernel<>), grid, dim3(kThreads), 0, s, b);
-    }
+  auto launch_columns = [d](dim3 grid, const BackwardArgs& b, const DropArgs* dr, int r0,
+                            hipStream_t s) {
+    if (d == 64) launch_columns_kernel<64>(grid, b, dr, r0, s);
+    else launch_columns_kernel<128>(grid, b, dr, r0, s);
   };
 
   // 1. D (always: the columns launch reads it) and dQ

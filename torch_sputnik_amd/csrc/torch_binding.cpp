@@ -1337,6 +1337,48 @@ std::vector<Tensor> sparse_attention_with_lse_planned(const Tensor& q, const Ten
                                plan);
 }
 
+// {out, lse} or, with p > 0, {out, lse, rng_state}: the fused attention forward in the row-group
+// form (sputnik_hip_sparse_attention_rows_forward: head dimension 128), with dropout p on the
+// weights when p > 0.  float32 q [R,m,d] / [m,d]; k, v [R,n,d] / [n,d]; no plan.  A shape the
+// kernel does not serve is an error.
+std::vector<Tensor> sparse_attention_rows(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in,
+                                          const Tensor& row_indices, const Tensor& row_offsets,
+                                          const Tensor& column_indices, double scale, double p) {
+  for (const Tensor* t : {&q_in, &k_in, &v_in})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat,
+                "sparse_attention_rows: query, key, value must be float32 GPU (HIP) tensors");
+  check_p(p);
+  const Tensor q = q_in.contiguous(), k = k_in.contiguous(), v = v_in.contiguous();
+  TORCH_CHECK(q.dim() == 2 || q.dim() == 3, "expected 2-dim or 3-dim query, got ", q.dim());
+  TORCH_CHECK(k.dim() == q.dim() && v.dim() == q.dim(), "query, key, value must match in dims");
+  TORCH_CHECK(k.sizes() == v.sizes(), "key and value must have one shape");
+  TORCH_CHECK(q.size(-1) == k.size(-1), "query and key must have one head dimension");
+  TORCH_CHECK(q.device() == k.device() && q.device() == v.device(),
+              "query, key, value must be on one device");
+  const c10::DeviceGuard guard(q.device());
+  const int m = to_int(q.size(-2), "m"), n = to_int(k.size(-2), "n");
+  const int d = to_int(q.size(-1), "d");
+  const int replicas = q.dim() == 3 ? to_int(q.size(0), "replicas") : 1;
+  TORCH_CHECK(q.dim() == 2 || k.size(0) == replicas, "first dim of query and key must match");
+  const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, q);
+  TORCH_CHECK(sputnik_hip_sparse_attention_rows_supported(m, n, d, topo.nonzeros),
+              "sparse_attention_rows: shape not served (head dimension 128, a mask with entries, "
+              "m and n below 2^23)");
+  const Drop drop = make_drop(p, c10::nullopt, q);
+  Tensor out = at::empty_like(q);
+  Tensor lse = q.dim() == 3 ? at::empty({replicas, m}, q.options()) : at::empty({m}, q.options());
+  const int64_t qs = static_cast<int64_t>(m) * d, ks = static_cast<int64_t>(n) * d;
+  check_status(sputnik_hip_sparse_attention_rows_forward(
+                   m, n, d, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
+                   topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(),
+                   q.data_ptr<float>(), qs, k.data_ptr<float>(), ks, v.data_ptr<float>(), ks,
+                   static_cast<float>(scale), out.data_ptr<float>(), qs, lse.data_ptr<float>(), m,
+                   drop.p, drop.rng, drop.rng_state_out, current_stream(q)),
+               "sparse_attention_rows");
+  if (p > 0.0) return {out, lse, drop.rng_state};
+  return {out, lse};
+}
+
 // {grad_q, grad_k, grad_v} of the fused attention (sputnik_hip_sparse_attention_backward),
 // empty tensors for those not wanted.  q [R,m,d] / [m,d]; k, v [R,n,d] / [n,d]; out and
 // grad_out as q; lse [R,m] / [m] from the forward.  The transposed mask (t_*, permutation) is
@@ -1374,7 +1416,8 @@ std::vector<Tensor> sparse_attention_backward(
               " x ", m, " values");
   const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, q);
   TORCH_CHECK(sputnik_hip_sparse_attention_backward_supported(m, n, d, topo.nonzeros),
-              "sparse_attention_backward: shape not served (head dimension 64, m and n below 2^24)");
+              "sparse_attention_backward: shape not served (head dimension 64 or 128, m * d and n * d "
+              "below 2^30)");
   Topology t{};
   Tensor perm;
   if (want_k || want_v) {
@@ -2195,6 +2238,9 @@ TORCH_LIBRARY(torch_sputnik, m) {
       "Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, Tensor plan) "
       "-> Tensor[]");
   m.def(
+      "sparse_attention_rows(Tensor query, Tensor key, Tensor value, Tensor row_indices, "
+      "Tensor row_offsets, Tensor column_indices, float scale, float p) -> Tensor[]");
+  m.def(
       "sparse_attention_backward(Tensor query, Tensor key, Tensor value, Tensor out, "
       "Tensor grad_out, Tensor lse, Tensor row_indices, Tensor row_offsets, "
       "Tensor column_indices, Tensor? t_row_indices, Tensor? t_row_offsets, "
@@ -2326,6 +2372,7 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("sparse_attention", &sparse_attention);
   m.impl("sparse_attention_with_lse", &sparse_attention_with_lse);
   m.impl("sparse_attention_with_lse_planned", &sparse_attention_with_lse_planned);
+  m.impl("sparse_attention_rows", &sparse_attention_rows);
   m.impl("sparse_attention_backward", &sparse_attention_backward);
   m.impl("spmm_plan", &spmm_plan);
   m.impl("spmm_planned", &spmm_planned);

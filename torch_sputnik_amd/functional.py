@@ -922,19 +922,28 @@ class SparseAttentionFunction(torch.autograd.Function):
 # Fused backward (ops.sparse_attention_backward): the forward keeps its output
 # and row log-sum-exp, the backward runs two kernels over the mask and its cached transpose.
 # ---------------------------------------------------------------------------
+def _rows_forward_served(query, key, column_indices):
+    """Whether the row-group forward (ops.sparse_attention_rows: head dimension 128) serves."""
+    return ops.sparse_attention_rows_supported(query.size(-2), key.size(-2), query.size(-1),
+                                               column_indices.numel())
+
+
 def fused_backward_served(query, key, column_indices):
-    """Whether the fused forward and the fused backward both serve these operands: float32,
-    head dimension 64, a mask with entries, offsets within 32 bits.  Elsewhere
+    """Whether a fused forward and the fused backward both serve these operands: float32 on
+    the GPU, a mask with entries, offsets within 32 bits, and head dimension 64 (the LDS-staged
+    forward) or 128 (the row-group forward, ops.sparse_attention_rows).  Elsewhere
     ``fused_backward=True`` trains on SparseAttentionFunction, as without the flag."""
     m, n, d, nnz = query.size(-2), key.size(-2), query.size(-1), column_indices.numel()
     return (query.dtype == torch.float32 and key.dtype == torch.float32 and query.is_cuda
-            and ops.sparse_attention_supported(m, n, d, nnz)
-            and ops.sparse_attention_backward_supported(m, n, d, nnz))
+            and ops.sparse_attention_backward_supported(m, n, d, nnz)
+            and (ops.sparse_attention_supported(m, n, d, nnz)
+                 or ops.sparse_attention_rows_supported(m, n, d, nnz)))
 
 
 class FusedBackwardAttentionFunction(torch.autograd.Function):
-    """softmax(scale * sddmm(q, k)) @ v with the one-kernel forward (keeping its output O and
-    row log-sum-exp) and the fused backward (ops.sparse_attention_backward): with
+    """softmax(scale * sddmm(q, k)) @ v with a one-kernel forward (ops.sparse_attention* at
+    head dimension 64, ops.sparse_attention_rows at 128; keeping its output O and row
+    log-sum-exp) and the fused backward (ops.sparse_attention_backward): with
     D_i = dO_i . O_i, per entry p = exp(scale q_i.k_j - lse_i), ds = p (dp - D_i) scale,
     dQ += ds k, dK += ds q, dV += p dO -- two kernels over the mask and its (cached)
     transpose, nothing of size [R, nnz] at any time.  ``dropout_p`` > 0: the forward's
@@ -944,8 +953,12 @@ class FusedBackwardAttentionFunction(torch.autograd.Function):
     def forward(ctx, query, key, value, row_indices, row_offsets, column_indices, scale,
                 dropout_p=0.0):
         ctx.scale, ctx.p = float(scale), float(dropout_p)
-        out, lse, rng_state = _attention_forward(query, key, value, row_indices, row_offsets,
-                                                 column_indices, scale, ctx.p, want_lse=True)
+        if _rows_forward_served(query, key, column_indices):   # head dimension 128: no plan
+            out, lse, rng_state = ops.sparse_attention_rows(query, key, value, row_indices,
+                                                            row_offsets, column_indices, scale, ctx.p)
+        else:
+            out, lse, rng_state = _attention_forward(query, key, value, row_indices, row_offsets,
+                                                     column_indices, scale, ctx.p, want_lse=True)
         ctx.save_for_backward(query, key, value, out, lse, row_indices, row_offsets,
                               column_indices, rng_state)
         return out
@@ -973,8 +986,9 @@ def sparse_attention(query, key, value, row_indices, row_offsets, column_indices
     fused kernel forward; differentiable (SparseAttentionFunction).  ``dropout_p``: dropout
     on the attention weights (0 <= p < 1; the caller decides when it is training).
     ``fused_backward``: the backward runs the two fused kernels
-    (FusedBackwardAttentionFunction) where they serve the operands, and nothing of size
-    [R, nnz] is allocated; elsewhere the composed backward runs as without the flag."""
+    (FusedBackwardAttentionFunction) where they serve the operands (head dimension 64 or
+    128), and nothing of size [R, nnz] is allocated; elsewhere the composed backward runs as
+    without the flag."""
     p = ops.check_dropout_p(dropout_p)
     topo = (row_indices, row_offsets, column_indices)
     if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):

@@ -105,7 +105,7 @@ class SparseAttention(nn.Module):
     inside the fused kernels' online softmax, or sparse_dropout between the softmax and the
     SpMM of the separate-operator path (the masks are the same: functional.sparse_dropout).
     ``fused_backward=True``: training runs the fused forward and the fused backward
-    (functional.FusedBackwardAttentionFunction), float32 only."""
+    (functional.FusedBackwardAttentionFunction), float32 only, head dimension 64 or 128."""
 
     def __init__(self, num_heads, embedding_size, max_sequence_length=512, device=None,
                  sparsity=0.9, mask_generator=None, differentiable_softmax=False,
@@ -154,7 +154,7 @@ class SparseAttention(nn.Module):
         # Training on the fused forward and the fused backward: nothing of
         # size [B*H, nnz] exists at any time, the backward included.  Takes precedence over
         # low_memory_training; shapes the fused backward does not serve (head dimension other
-        # than 64) train as low_memory_training does.
+        # than 64 or 128) train as low_memory_training does.
         self.fused_backward = bool(fused_backward)
 
     @property

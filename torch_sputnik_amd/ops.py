@@ -441,10 +441,34 @@ def sparse_attention_supported(m, n, d, nonzeros):
 
 
 def sparse_attention_backward_supported(m, n, d, nonzeros):
-    """True where sparse_attention_backward serves the shape (head dimension 64, 32-bit offsets)."""
+    """True where sparse_attention_backward serves the shape (head dimension 64 or 128, 32-bit
+    offsets)."""
     from . import capi
     return bool(capi.lib().sputnik_hip_sparse_attention_backward_supported(
         int(m), int(n), int(d), int(nonzeros)))
+
+
+def sparse_attention_rows_supported(m, n, d, nonzeros):
+    """True where the row-group forward (sparse_attention_rows) serves the shape: head
+    dimension 128, a mask with entries, 32-bit offsets (m and n below 2^23)."""
+    from . import capi
+    return bool(capi.lib().sputnik_hip_sparse_attention_rows_supported(int(m), int(n), int(d),
+                                                                       int(nonzeros)))
+
+
+def sparse_attention_rows(query, key, value, row_indices, row_offsets, column_indices, scale, p=0.0):
+    """The fused attention forward at head dimension 128, in the row-group form: one kernel,
+    one 16-lane row group per query row that gathers K and V rows and keeps an online softmax
+    in registers; no plan, nothing of size [R, nnz].  float32 [R, S, 128] (or [S, 128])
+    operands, made contiguous.  -> (out, lse, rng_state): lse is the log-sum-exp of the
+    undropped scores (-inf for rows without entries), what sparse_attention_backward needs;
+    p > 0 is dropout on the weights (the sparse_attention_dropout contract: e = CSR position,
+    the generator offset advances by 4), p = 0 draws nothing and rng_state is None.  Raises
+    where sparse_attention_rows_supported is false."""
+    p = check_dropout_p(p)
+    outs = _ops.sparse_attention_rows(query, key, value, row_indices, row_offsets, column_indices,
+                                      float(scale), p)
+    return outs[0], outs[1], (outs[2] if p > 0.0 else None)
 
 
 def sparse_attention_backward(query, key, value, out, grad_out, lse, row_indices, row_offsets,
