@@ -327,6 +327,89 @@ def test_heads_many_mask_and_core_module(dev, dtype):
         assert torch.equal(layer(q, k, v, mask, topology=topology), plain(q, k, v, mask, topology=topology))
 
 
+@pytest.mark.parametrize("p", [0.0, 0.25])
+@pytest.mark.parametrize("layout", ["single", "heads", "many_mask", "heads_many_mask"])
+def test_recomputing_functions_partial_gradients(dev, layout, p):
+    """The four recomputing Functions behind the public calls: all three gradients against
+    float64, then q, k and v alone requiring grad -- the gradient asked for equals the full
+    run's bit for bit, the others are None.  m = 72 x n = 136: one partial query block, two
+    key chunks of the 128-row stage."""
+    from torch_sputnik_amd import functional, ops
+    B, H, m, n, d = 2, 2, 72, 136, 64
+    many, views = "many_mask" in layout, layout.startswith("heads")
+    dtype = torch.float16 if views else torch.float32
+    R, scale = B * H, 1 / math.sqrt(d)
+    dense, csr = make_masks(B if many else 1, m, n, 21)
+    if many:
+        nnz, topo = topo_many(csr, m, dev)
+        assert nnz[0] != nnz[1]
+        mask = torch.from_numpy(dense).repeat_interleave(H, 0)
+    else:
+        topo = topo_single(csr, dev)
+        mask = torch.from_numpy(dense[0]).expand(R, m, n)
+
+    def operand(x):   # [B, H, S, D] float32 -> the layout's operand
+        if layout == "heads":
+            return x.transpose(1, 2).reshape(B, x.size(2), H * d).to(dtype)
+        if layout == "heads_many_mask":
+            return x.transpose(1, 2).contiguous().to(dtype)
+        return x.reshape(R, x.size(2), d)
+
+    def head_views(t):   # operand -> [B, H, S, D] view
+        return (t.unflatten(-1, (H, d)) if layout == "heads" else t).transpose(1, 2)
+
+    def replicas(t):   # operand or gradient -> [R, S, D] on the CPU
+        return (head_views(t).reshape(R, -1, d) if views else t).cpu()
+
+    def call(q, k, v):
+        if layout == "single":
+            return functional.sparse_attention(q, k, v, *topo, scale, dropout_p=p)
+        if layout == "heads":
+            return functional.sparse_attention_heads(q, k, v, H, *topo, scale, dropout_p=p)
+        if layout == "many_mask":
+            return functional.sparse_attention_many_mask(B, m, n, nnz, *topo, q, k, v, scale, dropout_p=p)
+        return functional.sparse_attention_heads_many_mask(q, k, v, nnz, *topo, scale, dropout_p=p)
+
+    torch.manual_seed(8)
+    q, k, v, go = (operand(torch.randn(B, H, rows, d, device=dev)) for rows in (m, n, n, m))
+    factor, offset = torch.ones(R, m, n, dtype=torch.float64), gen(dev).get_offset()
+    if p > 0.0:   # the state of one forward with dropout; every run below starts at its offset
+        if layout == "single":
+            state = ops.sparse_attention_dropout(q, k, v, *topo, scale, p)[2]
+        elif layout == "heads":
+            state = ops.sparse_attention_heads_dropout(*map(head_views, (q, k, v)), *topo, scale, p)[2]
+        elif layout == "many_mask":
+            state = ops.sparse_attention_many_mask_dropout(B, nnz, *topo, q, k, v, scale, p)[2]
+        else:
+            state = ops.sparse_attention_heads_many_mask_dropout(
+                B, nnz, *topo, *map(head_views, (q, k, v)), scale, p)[2]
+        factor, offset = dense_keep(csr, state, R, p, m, n, H if many else R), int(state[1])
+
+    def run(needs):
+        xs = [t.clone().requires_grad_(need) for t, need in zip((q, k, v), needs)]
+        gen(dev).set_offset(offset)
+        y = call(*xs)
+        assert y.shape == go.shape and y.dtype == dtype
+        y.backward(go)
+        return [x.grad for x in xs]
+
+    full = run((True, True, True))
+    xd = [replicas(t).double().requires_grad_() for t in (q, k, v)]
+    want, _ = reference(*xd, mask, factor, scale)
+    want.backward(replicas(go).double())
+    for name, got, ref in zip("qkv", full, xd):
+        err = rel_err_torch(replicas(got).float(), ref.grad)
+        print(f"{layout} p={p} d{name}: rel err {err:.3e} (bound {TOL[dtype]:g})")
+        assert err < TOL[dtype]
+    for alone in range(3):
+        part = run(tuple(i == alone for i in range(3)))
+        for i, (got, whole) in enumerate(zip(part, full)):
+            if i == alone:
+                assert torch.equal(got, whole)
+            else:
+                assert got is None
+
+
 # ---------------------------------------------------------------------------
 # 6, 7: SparseAttention and the captured training step
 # ---------------------------------------------------------------------------

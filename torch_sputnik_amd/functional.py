@@ -412,12 +412,18 @@ def _sddmm(m, n, row_indices, row_offsets, column_indices, lhs_matrix, rhs_matri
 
 def _attention_forward(query, key, value, row_indices, row_offsets, column_indices, scale, p=0.0,
                        want_lse=False):
-    """Fused attention forward -> (out, lse or None, rng_state or None), through the cached
-    plan of the mask when enabled: the dropout op for p > 0, the lse ops for the fused
-    backward, else the plain ones."""
+    """Fused attention forward -> (out, lse or None, rng_state or None), as every private
+    forward helper of the attention layouts below returns: `rng_state` is None at p == 0.
+    `want_lse` (the fused backward) takes the row-group forward where it serves (head
+    dimension 128, ops.sparse_attention_rows: no plan); without it that shape stays on the
+    plain op.  Else through the cached plan of the mask when enabled: the dropout op for
+    p > 0, the lse ops for `want_lse`, or the plain ones."""
+    operands = (query, key, value, row_indices, row_offsets, column_indices, scale)
+    if want_lse and ops.sparse_attention_rows_supported(query.size(-2), key.size(-2), query.size(-1),
+                                                        column_indices.numel()):
+        return ops.sparse_attention_rows(*operands, p)
     plan = None if _plans is None else _plans.attention(query.size(-2), key.size(-2), query.size(-1),
                                                         row_indices, row_offsets, column_indices)
-    operands = (query, key, value, row_indices, row_offsets, column_indices, scale)
     if p > 0.0:
         return ops.sparse_attention_dropout(*operands, p, plan)
     if want_lse:
@@ -835,37 +841,28 @@ def _transposed_topology(m, n, row_offsets, column_indices, probe_values):
     return diffsort(row_offsets_t), row_offsets_t, column_indices_t, perm
 
 
-def _attention_backward(query, key, value, topo, scale, grad_output, needs, dropout=None):
-    """Gradients of softmax(scale * sddmm(q, k)) @ v for [R, S, D] operands (float32, or one
-    half type: the typed operators, float32 scores, weights and gradients): the scores and
-    weights are recomputed, then
+# ---------------------------------------------------------------------------
+# The recomputing backward.  Four Functions share it (SparseAttentionFunction, ...Heads...,
+# ...ManyMask..., ...HeadsManyMask...): each saves (query, key, value, *topo, rng_state),
+# brings its operands to contiguous [R, S, D] and runs `_attention_backward` on the operator
+# family of its mask layout.
+# ---------------------------------------------------------------------------
+_Operators = collections.namedtuple(
+    "_Operators", "sddmm softmax softmax_backward spmm transposed_products")
 
-        dV = P^T dO          dP = sddmm(dO, v)
-        dS = softmax'(P, dP) (sparse_softmax_backward, carries the scale)
-        dQ = dS k            dK = dS^T q
 
-    on the mask and its transpose (one csr_transpose with permutation per call, or the
-    cached transposed topology).  `needs`: which of (dQ, dK, dV) to compute.
-    `dropout` = (p, rng_state) of a forward with attention dropout: the mask is replayed,
-    Pd = drop(P), dV = Pd^T dO, dP = drop(sddmm(dO, v)), and the rest is unchanged."""
-    row_indices, row_offsets, column_indices = topo
-    m, n = query.size(-2), key.size(-2)
-    grad_output = _contiguous(grad_output)
-    scores = _sddmm(m, n, *topo, query, key)
-    weights = ops.sparse_softmax_scaled(scores, *topo, scale)
-    grad_weights = _sddmm(m, n, *topo, grad_output, value)
-    kept = weights
-    if dropout is not None:
-        kept = _replay(weights, *dropout)
-        grad_weights = _replay(grad_weights, *dropout)
-    grad_scores = ops.sparse_softmax_backward(weights, grad_weights, row_offsets, scale)
-    grad_query = grad_key = grad_value = None
-    if needs[0]:
-        grad_query = _spmm(m, n, grad_scores, *topo, key)
-    if needs[1] or needs[2]:
+def _single_mask_operators(topo, m, n):
+    """The operators of one m x n mask for `_attention_backward`: plan-cached sddmm / spmm,
+    and the transposed products through the mask's transposed topology (one csr_transpose
+    with permutation per call, or the cached one), gathered inside ops.spmm_permuted where
+    that serves."""
+    _, row_offsets, column_indices = topo
+
+    def transposed_products(grad_scores, kept, query, grad_output, needs_key, needs_value):
         row_indices_t, row_offsets_t, column_indices_t, perm = _transposed_topology(
             m, n, row_offsets, column_indices, grad_scores)
-        def transposed_product(values, dense):
+
+        def product(values, dense):
             if ops.spmm_permuted_fused(n, m, dense.size(-1), perm.numel()):
                 return ops.spmm_permuted(n, m, values, perm, row_indices_t, row_offsets_t,
                                          column_indices_t, dense)
@@ -873,27 +870,63 @@ def _attention_backward(query, key, value, topo, scale, grad_output, needs, drop
                         else ops.permute_last(values, perm))
             return _spmm(n, m, values_t, row_indices_t, row_offsets_t, column_indices_t, dense)
 
-        if needs[1]:
-            grad_key = transposed_product(grad_scores, query)
-        if needs[2]:
-            grad_value = transposed_product(kept, grad_output)
+        return (product(grad_scores, query) if needs_key else None,
+                product(kept, grad_output) if needs_value else None)
+
+    return _Operators(
+        sddmm=lambda lhs, rhs: _sddmm(m, n, *topo, lhs, rhs),
+        softmax=lambda scores, scale: ops.sparse_softmax_scaled(scores, *topo, scale),
+        softmax_backward=lambda weights, grad, scale: ops.sparse_softmax_backward(
+            weights, grad, row_offsets, scale),
+        spmm=lambda values, dense: _spmm(m, n, values, *topo, dense),
+        transposed_products=transposed_products)
+
+
+def _attention_backward(operators, query, key, value, scale, grad_output, needs, dropout=None):
+    """Gradients of softmax(scale * sddmm(q, k)) @ v for contiguous [R, S, D] operands on one
+    operator family (`_single_mask_operators`: float32 or one half type, the typed operators
+    with float32 scores, weights and gradients; `_many_mask_operators`: float32): the scores
+    and weights are recomputed, then
+
+        dV = P^T dO          dP = sddmm(dO, v)
+        dS = softmax'(P, dP) (the softmax backward, carries the scale)
+        dQ = dS k            dK = dS^T q
+
+    on the mask and, when dK or dV is wanted, its transpose.  `needs`: which of (dQ, dK, dV)
+    to compute.  `dropout` = (p, rng_state) of a forward with attention dropout: the mask is
+    replayed, Pd = drop(P), dV = Pd^T dO, dP = drop(sddmm(dO, v)), and the rest is unchanged."""
+    scores = operators.sddmm(query, key)
+    weights = operators.softmax(scores, scale)
+    grad_weights = operators.sddmm(grad_output, value)
+    kept = weights
+    if dropout is not None:
+        kept = _replay(weights, *dropout)
+        grad_weights = _replay(grad_weights, *dropout)
+    grad_scores = operators.softmax_backward(weights, grad_weights, scale)
+    grad_query = grad_key = grad_value = None
+    if needs[0]:
+        grad_query = operators.spmm(grad_scores, key)
+    if needs[1] or needs[2]:
+        grad_key, grad_value = operators.transposed_products(grad_scores, kept, query, grad_output,
+                                                             needs[1], needs[2])
     return grad_query, grad_key, grad_value
+
+
+def _saved(ctx):
+    """(query, key, value, topo, dropout) of a recomputing Function's backward; `dropout` is
+    (p, rng_state), or None for a forward without dropout (which saved rng_state = None)."""
+    query, key, value, row_indices, row_offsets, column_indices, rng_state = ctx.saved_tensors
+    dropout = (ctx.p, rng_state) if ctx.p > 0.0 else None
+    return query, key, value, (row_indices, row_offsets, column_indices), dropout
 
 
 class SparseAttentionFunction(torch.autograd.Function):
     """softmax(scale * sddmm(q, k)) @ v with the ONE-kernel forward
-    (ops.sparse_attention) and a backward built from the separate operators.
-    Nothing of size [R, nnz] is kept between the passes: the backward recomputes
-    the weights (sddmm + scaled softmax) and then runs the standard chain
-
-        dV = P^T dO          dP = sddmm(dO, v)
-        dS = softmax'(P, dP) (sparse_softmax_backward, carries the scale)
-        dQ = dS k            dK = dS^T q
-
-    on the mask and its transpose (one csr_transpose with permutation per call,
-    or the cached transposed topology).  ``dropout_p`` > 0: dropout on the weights in the
-    fused forward (ops.sparse_attention_dropout), replayed by the backward from the saved
-    rng_state."""
+    (ops.sparse_attention) and a backward built from the separate operators
+    (`_attention_backward`).  Nothing of size [R, nnz] is kept between the passes: the
+    backward recomputes the weights (sddmm + scaled softmax) before it runs the chain.
+    ``dropout_p`` > 0: dropout on the weights in the fused forward
+    (ops.sparse_attention_dropout), replayed by the backward from the saved rng_state."""
 
     @staticmethod
     def forward(ctx, query, key, value, row_indices, row_offsets, column_indices, scale,
@@ -901,33 +934,22 @@ class SparseAttentionFunction(torch.autograd.Function):
         ctx.scale, ctx.p = float(scale), float(dropout_p)
         out, _, rng_state = _attention_forward(query, key, value, row_indices, row_offsets,
                                                column_indices, scale, ctx.p)
-        if ctx.p > 0.0:
-            ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices,
-                                  rng_state)
-        else:
-            ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices)
+        ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices, rng_state)
         return out
 
     @staticmethod
     def backward(ctx, grad_output):
-        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors[:6]
-        dropout = (ctx.p, ctx.saved_tensors[6]) if ctx.p > 0.0 else None
-        grad_query, grad_key, grad_value = _attention_backward(
-            query, key, value, (row_indices, row_offsets, column_indices), ctx.scale, grad_output,
-            ctx.needs_input_grad[:3], dropout)
-        return grad_query, grad_key, grad_value, None, None, None, None, None
+        query, key, value, topo, dropout = _saved(ctx)
+        grads = _attention_backward(
+            _single_mask_operators(topo, query.size(-2), key.size(-2)), query, key, value,
+            ctx.scale, _contiguous(grad_output), ctx.needs_input_grad[:3], dropout)
+        return (*grads, None, None, None, None, None)
 
 
 # ---------------------------------------------------------------------------
 # Fused backward (ops.sparse_attention_backward): the forward keeps its output
 # and row log-sum-exp, the backward runs two kernels over the mask and its cached transpose.
 # ---------------------------------------------------------------------------
-def _rows_forward_served(query, key, column_indices):
-    """Whether the row-group forward (ops.sparse_attention_rows: head dimension 128) serves."""
-    return ops.sparse_attention_rows_supported(query.size(-2), key.size(-2), query.size(-1),
-                                               column_indices.numel())
-
-
 def fused_backward_served(query, key, column_indices):
     """Whether a fused forward and the fused backward both serve these operands: float32 on
     the GPU, a mask with entries, offsets within 32 bits, and head dimension 64 (the LDS-staged
@@ -953,12 +975,8 @@ class FusedBackwardAttentionFunction(torch.autograd.Function):
     def forward(ctx, query, key, value, row_indices, row_offsets, column_indices, scale,
                 dropout_p=0.0):
         ctx.scale, ctx.p = float(scale), float(dropout_p)
-        if _rows_forward_served(query, key, column_indices):   # head dimension 128: no plan
-            out, lse, rng_state = ops.sparse_attention_rows(query, key, value, row_indices,
-                                                            row_offsets, column_indices, scale, ctx.p)
-        else:
-            out, lse, rng_state = _attention_forward(query, key, value, row_indices, row_offsets,
-                                                     column_indices, scale, ctx.p, want_lse=True)
+        out, lse, rng_state = _attention_forward(query, key, value, row_indices, row_offsets,
+                                                 column_indices, scale, ctx.p, want_lse=True)
         ctx.save_for_backward(query, key, value, out, lse, row_indices, row_offsets,
                               column_indices, rng_state)
         return out
@@ -1069,18 +1087,31 @@ def _heads(x, heads):
     return x.unflatten(-1, (heads, x.size(-1) // heads)).transpose(1, 2)
 
 
+def _per_head(x, heads, dtype):
+    """[B, S, E] -> [B*H, S, D] in `dtype` (one copy for more than one head)."""
+    return _heads(x.to(dtype), heads).reshape(-1, x.size(1), x.size(2) // heads)
+
+
+def _merge_heads(g, like, heads):
+    """A gradient [B*H, S, D] (or None) -> [B, S, E] in the type of the input `like`."""
+    if g is None:
+        return None
+    return g.reshape(like.size(0), heads, like.size(1), -1).transpose(1, 2).reshape(
+        like.shape).to(like.dtype)
+
+
 def _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale, p=0.0):
-    """-> the context [B, S, E]; with p > 0 (dropout on the weights) -> (context, rng_state)."""
+    """-> (context [B, S, E], None, rng_state or None), as `_attention_forward`."""
     q, k, v = _heads(query, heads), _heads(key, heads), _heads(value, heads)
     plan = None if _plans is None else _plans.attention(q.size(-2), k.size(-2), q.size(-1), row_indices,
                                                         row_offsets, column_indices)
+    operands = (q, k, v, row_indices, row_offsets, column_indices, scale)
     if p > 0.0:
-        out, _, rng_state = ops.sparse_attention_heads_dropout(q, k, v, row_indices, row_offsets,
-                                                               column_indices, scale, p, plan=plan)
-        return out.transpose(1, 2).reshape(query.size(0), query.size(1), -1), rng_state
-    out = ops.sparse_attention_heads(q, k, v, row_indices, row_offsets, column_indices, scale, plan=plan)
+        out, _, rng_state = ops.sparse_attention_heads_dropout(*operands, p, plan=plan)
+    else:
+        out, rng_state = ops.sparse_attention_heads(*operands, plan=plan), None
     # (the kernel's buffer is [B, S, H, D]: this is a view)
-    return out.transpose(1, 2).reshape(query.size(0), query.size(1), -1)
+    return out.transpose(1, 2).reshape(query.size(0), query.size(1), -1), None, rng_state
 
 
 class SparseAttentionHeadsFunction(torch.autograd.Function):
@@ -1094,34 +1125,18 @@ class SparseAttentionHeadsFunction(torch.autograd.Function):
     def forward(ctx, query, key, value, heads, row_indices, row_offsets, column_indices, scale,
                 dropout_p=0.0):
         ctx.heads, ctx.scale, ctx.p = int(heads), float(scale), float(dropout_p)
-        if ctx.p > 0.0:
-            out, rng_state = _attention_heads(query, key, value, heads, row_indices, row_offsets,
-                                              column_indices, scale, ctx.p)
-            ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices, rng_state)
-            return out
-        ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices)
-        return _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale)
+        out, _, rng_state = _attention_heads(query, key, value, heads, row_indices, row_offsets,
+                                             column_indices, scale, ctx.p)
+        ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices, rng_state)
+        return out
 
     @staticmethod
     def backward(ctx, grad_output):
-        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors[:6]
-        dropout = (ctx.p, ctx.saved_tensors[6]) if ctx.p > 0.0 else None
-        heads = ctx.heads
-
-        def per_head(x):   # [B, S, E] -> [B*H, S, D], contiguous, in the storage type
-            return _heads(x.to(query.dtype), heads).reshape(-1, x.size(1), x.size(2) // heads)
-
-        grads = _attention_backward(per_head(query), per_head(key), per_head(value),
-                                    (row_indices, row_offsets, column_indices), ctx.scale,
-                                    per_head(grad_output), ctx.needs_input_grad[:3], dropout)
-
-        def merged(g, like):   # [B*H, S, D] -> [B, S, E] in like's type
-            if g is None:
-                return None
-            return g.reshape(like.size(0), heads, like.size(1), -1).transpose(1, 2).reshape(
-                like.shape).to(like.dtype)
-
-        return (merged(grads[0], query), merged(grads[1], key), merged(grads[2], value),
+        query, key, value, topo, dropout = _saved(ctx)
+        q, k, v, grad = (_per_head(x, ctx.heads, query.dtype) for x in (query, key, value, grad_output))
+        grads = _attention_backward(_single_mask_operators(topo, q.size(-2), k.size(-2)), q, k, v,
+                                    ctx.scale, _contiguous(grad), ctx.needs_input_grad[:3], dropout)
+        return (*(_merge_heads(g, x, ctx.heads) for g, x in zip(grads, (query, key, value))),
                 None, None, None, None, None, None)
 
 
@@ -1139,10 +1154,8 @@ def sparse_attention_heads(query, key, value, heads, row_indices, row_offsets, c
     if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
         return SparseAttentionHeadsFunction.apply(query, key, value, heads, row_indices, row_offsets,
                                                   column_indices, scale, p)
-    if p > 0.0:
-        return _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices,
-                                scale, p)[0]
-    return _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale)
+    return _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices,
+                            scale, p)[0]
 
 
 # ---------------------------------------------------------------------------
@@ -1249,15 +1262,13 @@ class CsrSoftmaxManyMask(torch.autograd.Function):
 # Fused attention with one mask per batch element (the reference's SparseCoreAttention,
 # tests/transformer/modules.py:9-81: sddmm_many_mask, sparse_softmax_many_mask, spmm_many_mask).
 # The forward is one kernel (ops.sparse_attention_many_mask / _heads_many_mask); the backward
-# recomputes the weights with the many-mask operators, which are float32 only: half inputs
+# is `_attention_backward` on the many-mask operators, which are float32 only: half inputs
 # get float32 per-head copies there, and their gradients are returned in the input's type.
 # ---------------------------------------------------------------------------
-def _many_mask_topology(b, m, n, d, nonzeros, row_indices, row_offsets, column_indices):
-    plan = None
-    if _plans is not None:
-        plan = _plans.attention_many_mask(b, m, n, d, nonzeros, row_indices, row_offsets,
-                                          column_indices)
-    return plan
+def _many_mask_plan(b, m, n, d, nonzeros, row_indices, row_offsets, column_indices):
+    if _plans is None:
+        return None
+    return _plans.attention_many_mask(b, m, n, d, nonzeros, row_indices, row_offsets, column_indices)
 
 
 def _many_mask_composed(b, nonzeros, topo, query, key, value, scale):
@@ -1273,47 +1284,60 @@ def _many_mask_composed(b, nonzeros, topo, query, key, value, scale):
                               column_indices, value)
 
 
-def _many_mask_backward(b, nonzeros, topo, query, key, value, scale, grad_output, needs, dropout=None):
-    """Gradients of softmax(scale * sddmm_many_mask(q, k)) @ v for float32 [R, S, D] operands,
-    as _attention_backward with the many-mask operators: the weights are recomputed, then
-    dV = P^T dO, dP = sddmm(dO, v), dS = softmax'(P, dP), dQ = dS k, dK = dS^T q."""
-    row_indices, row_offsets, column_indices = topo
-    m, n = query.size(-2), key.size(-2)
-    grad_output = grad_output.contiguous()
-    scores = ops.sddmm_many_mask(b, m, n, nonzeros, *topo, query, key)
-    weights = ops.sparse_softmax_many_mask(b, m, nonzeros, scores, *topo, scale)
-    grad_weights = ops.sddmm_many_mask(b, m, n, nonzeros, *topo, grad_output, value)
-    kept = weights
-    if dropout is not None:   # (p, rng_state): replay the forward's mask, as _attention_backward
-        kept = _replay(weights, *dropout)
-        grad_weights = _replay(grad_weights, *dropout)
-    grad_scores = ops.sparse_softmax_backward_many_mask(b, m, nonzeros, weights, grad_weights,
-                                                        row_offsets, scale)
-    grad_query = grad_key = grad_value = None
-    if needs[0]:
-        grad_query = ops.spmm_many_mask(b, m, n, nonzeros, grad_scores, *topo, key)
-    if needs[1] or needs[2]:
-        grad_t, row_offsets_t, column_indices_t = ops.csr_transpose_many_mask(
-            b, m, n, nonzeros, grad_scores, row_offsets, column_indices)
-        row_indices_t = diffsort_many_mask(row_offsets_t, b)
-        topo_t = (row_indices_t, row_offsets_t, column_indices_t)
-        if needs[1]:
+def _many_mask_operators(b, nonzeros, topo, m, n):
+    """The many-mask operators of b stacked m x n masks for `_attention_backward`; the
+    transposed products run one csr_transpose_many_mask per values array they transpose."""
+    _, row_offsets, column_indices = topo
+
+    def transpose(values):
+        return ops.csr_transpose_many_mask(b, m, n, nonzeros, values, row_offsets, column_indices)
+
+    def transposed_products(grad_scores, kept, query, grad_output, needs_key, needs_value):
+        grad_t, row_offsets_t, column_indices_t = transpose(grad_scores)
+        topo_t = (diffsort_many_mask(row_offsets_t, b), row_offsets_t, column_indices_t)
+        grad_key = grad_value = None
+        if needs_key:
             grad_key = ops.spmm_many_mask(b, n, m, nonzeros, grad_t, *topo_t, query)
-        if needs[2]:
-            weights_t = ops.csr_transpose_many_mask(b, m, n, nonzeros, kept, row_offsets,
-                                                    column_indices)[0]
-            grad_value = ops.spmm_many_mask(b, n, m, nonzeros, weights_t, *topo_t, grad_output)
-    return grad_query, grad_key, grad_value
+        if needs_value:
+            grad_value = ops.spmm_many_mask(b, n, m, nonzeros, transpose(kept)[0], *topo_t,
+                                            grad_output)
+        return grad_key, grad_value
+
+    return _Operators(
+        sddmm=lambda lhs, rhs: ops.sddmm_many_mask(b, m, n, nonzeros, *topo, lhs, rhs),
+        softmax=lambda scores, scale: ops.sparse_softmax_many_mask(b, m, nonzeros, scores, *topo,
+                                                                   scale),
+        softmax_backward=lambda weights, grad, scale: ops.sparse_softmax_backward_many_mask(
+            b, m, nonzeros, weights, grad, row_offsets, scale),
+        spmm=lambda values, dense: ops.spmm_many_mask(b, m, n, nonzeros, values, *topo, dense),
+        transposed_products=transposed_products)
+
+
+def _float_replicas(x):
+    """[R, S, D], or a [B, S, H, D] view, -> contiguous [R, S, D] float32 (R = B * H)."""
+    x = x.to(torch.float32)
+    if x.dim() == 3:
+        return x.contiguous()
+    return x.transpose(1, 2).reshape(x.size(0) * x.size(2), x.size(1), x.size(3))
+
+
+def _like_input(g, like):
+    """A gradient [R, S, D] (or None) -> the shape and type of the input `like`."""
+    if g is None:
+        return None
+    if like.dim() == 4:
+        g = g.reshape(like.size(0), like.size(2), like.size(1), -1).transpose(1, 2)
+    return g.to(like.dtype)
 
 
 def _many_mask_forward(b, nonzeros, topo, query, key, value, scale, p=0.0):
-    """[R, S, D] forward: the fused kernel on GPU tensors (the heads kernel for half storage,
-    whose [R, S, D] is a [b, R/b, S, D] head view), the composition elsewhere.  With dropout
-    p > 0 -> (out, rng_state)."""
+    """[R, S, D] forward -> (out, None, rng_state or None), as `_attention_forward`: the fused
+    kernel on GPU tensors (the heads kernel for half storage, whose [R, S, D] is a
+    [b, R/b, S, D] head view), the composition elsewhere."""
     if p == 0.0 and not query.is_cuda:
         return _many_mask_composed(b, nonzeros, topo, query.float(), key.float(), value.float(),
-                                   scale).to(query.dtype)
-    plan = _many_mask_topology(b, query.size(-2), key.size(-2), query.size(-1), nonzeros, *topo)
+                                   scale).to(query.dtype), None, None
+    plan = _many_mask_plan(b, query.size(-2), key.size(-2), query.size(-1), nonzeros, *topo)
     half = query.dtype in (torch.float16, torch.bfloat16)
     if half:
         query, key, value = (x.unflatten(0, (b, x.size(0) // b)) for x in (query, key, value))
@@ -1323,42 +1347,53 @@ def _many_mask_forward(b, nonzeros, topo, query, key, value, scale, p=0.0):
         out, _, rng_state = op(*operands, p, plan=plan)
     else:
         op = ops.sparse_attention_heads_many_mask if half else ops.sparse_attention_many_mask
-        out = op(*operands, plan=plan)
+        out, rng_state = op(*operands, plan=plan), None
     if half:
         out = out.flatten(0, 1)   # ([b, H, S, D] view of a [b, S, H, D] buffer: one copy)
-    return (out, rng_state) if p > 0.0 else out
+    return out, None, rng_state
 
 
-def _float_per_replica(x):
-    return x.to(torch.float32).contiguous()
+def _heads_many_mask_forward(query, key, value, nonzeros, topo, scale, p=0.0):
+    """[B, S, H, D] views -> ([B, m, H, D], None, rng_state or None), as `_attention_forward`."""
+    b, heads = query.size(0), query.size(2)
+    q, k, v = (x.transpose(1, 2) for x in (query, key, value))   # [B, H, S, D] views
+    if query.dtype in (torch.float16, torch.bfloat16) and (p > 0.0 or query.is_cuda):
+        plan = _many_mask_plan(b, q.size(-2), k.size(-2), q.size(-1), nonzeros, *topo)
+        operands = (b, nonzeros, *topo, q, k, v, scale)
+        if p > 0.0:
+            out, _, rng_state = ops.sparse_attention_heads_many_mask_dropout(*operands, p, plan=plan)
+        else:
+            out, rng_state = ops.sparse_attention_heads_many_mask(*operands, plan=plan), None
+        out = out.transpose(1, 2)   # the kernel's [B, S, H, D] buffer
+    else:   # float32 views, CPU tensors: one copy to [B*H, S, D]
+        per_head = [x.reshape(b * heads, x.size(2), x.size(3)) for x in (q, k, v)]
+        out, _, rng_state = _many_mask_forward(b, nonzeros, topo, *per_head, scale, p)
+        out = out.reshape(b, heads, query.size(1), -1).transpose(1, 2).to(query.dtype)
+    return out, None, rng_state
 
 
 class SparseAttentionManyMaskFunction(torch.autograd.Function):
     """sparse_attention_many_mask under autograd (apply(b, nonzeros, row_indices, row_offsets,
-    column_indices, query, key, value, scale))."""
+    column_indices, query, key, value, scale[, dropout_p])): [R, S, D] operands."""
 
     @staticmethod
     def forward(ctx, b, nonzeros, row_indices, row_offsets, column_indices, query, key, value, scale,
                 dropout_p=0.0):
         ctx.b, ctx.nonzeros, ctx.scale, ctx.p = int(b), nonzeros, float(scale), float(dropout_p)
         topo = (row_indices, row_offsets, column_indices)
-        if ctx.p > 0.0:
-            out, rng_state = _many_mask_forward(ctx.b, nonzeros, topo, query, key, value, scale, ctx.p)
-            ctx.save_for_backward(query, key, value, *topo, rng_state)
-            return out
-        ctx.save_for_backward(query, key, value, *topo)
-        return _many_mask_forward(ctx.b, nonzeros, topo, query, key, value, scale)
+        out, _, rng_state = _many_mask_forward(ctx.b, nonzeros, topo, query, key, value, scale, ctx.p)
+        ctx.save_for_backward(query, key, value, *topo, rng_state)
+        return out
 
     @staticmethod
     def backward(ctx, grad_output):
-        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors[:6]
-        dropout = (ctx.p, ctx.saved_tensors[6]) if ctx.p > 0.0 else None
-        grads = _many_mask_backward(ctx.b, ctx.nonzeros, (row_indices, row_offsets, column_indices),
-                                    _float_per_replica(query), _float_per_replica(key),
-                                    _float_per_replica(value), ctx.scale,
-                                    _float_per_replica(grad_output), ctx.needs_input_grad[5:8], dropout)
-        grads = [None if g is None else g.to(x.dtype) for g, x in zip(grads, (query, key, value))]
-        return (None, None, None, None, None, *grads, None, None)
+        query, key, value, topo, dropout = _saved(ctx)
+        q, k, v, grad = (_float_replicas(x) for x in (query, key, value, grad_output))
+        grads = _attention_backward(
+            _many_mask_operators(ctx.b, ctx.nonzeros, topo, q.size(-2), k.size(-2)), q, k, v,
+            ctx.scale, grad.contiguous(), ctx.needs_input_grad[5:8], dropout)
+        return (None, None, None, None, None,
+                *(_like_input(g, x) for g, x in zip(grads, (query, key, value))), None, None)
 
 
 def sparse_attention_many_mask(b, m, n, nonzeros, row_indices, row_offsets, column_indices, query,
@@ -1379,67 +1414,31 @@ def sparse_attention_many_mask(b, m, n, nonzeros, row_indices, row_offsets, colu
     topo = (row_indices, row_offsets, column_indices)
     if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
         return SparseAttentionManyMaskFunction.apply(b, nonzeros, *topo, query, key, value, scale, p)
-    if p > 0.0:
-        return _many_mask_forward(int(b), nonzeros, topo, query, key, value, scale, p)[0]
-    return _many_mask_forward(int(b), nonzeros, topo, query, key, value, scale)
+    return _many_mask_forward(int(b), nonzeros, topo, query, key, value, scale, p)[0]
 
 
 class SparseAttentionHeadsManyMaskFunction(torch.autograd.Function):
-    """sparse_attention_heads_many_mask under autograd ([B, S, H, D] views)."""
+    """sparse_attention_heads_many_mask under autograd: [B, S, H, D] views, batch element i
+    under mask i."""
 
     @staticmethod
     def forward(ctx, query, key, value, nonzeros, row_indices, row_offsets, column_indices, scale,
                 dropout_p=0.0):
         ctx.nonzeros, ctx.scale, ctx.p = nonzeros, float(scale), float(dropout_p)
         topo = (row_indices, row_offsets, column_indices)
-        if ctx.p > 0.0:
-            out, rng_state = _heads_many_mask_forward(query, key, value, nonzeros, topo, scale, ctx.p)
-            ctx.save_for_backward(query, key, value, *topo, rng_state)
-            return out
-        ctx.save_for_backward(query, key, value, *topo)
-        return _heads_many_mask_forward(query, key, value, nonzeros, topo, scale)
+        out, _, rng_state = _heads_many_mask_forward(query, key, value, nonzeros, topo, scale, ctx.p)
+        ctx.save_for_backward(query, key, value, *topo, rng_state)
+        return out
 
     @staticmethod
     def backward(ctx, grad_output):
-        query, key, value, row_indices, row_offsets, column_indices = ctx.saved_tensors[:6]
-        dropout = (ctx.p, ctx.saved_tensors[6]) if ctx.p > 0.0 else None
-        b, heads = query.size(0), query.size(2)
-
-        def per_head(x):   # [B, S, H, D] -> [B*H, S, D] float32
-            return x.to(torch.float32).transpose(1, 2).reshape(b * heads, x.size(1), x.size(3))
-
-        grads = _many_mask_backward(b, ctx.nonzeros, (row_indices, row_offsets, column_indices),
-                                    per_head(query), per_head(key), per_head(value), ctx.scale,
-                                    per_head(grad_output), ctx.needs_input_grad[:3], dropout)
-
-        def merged(g, like):   # [B*H, S, D] -> [B, S, H, D] in like's type
-            if g is None:
-                return None
-            return g.reshape(b, heads, like.size(1), -1).transpose(1, 2).to(like.dtype)
-
-        return (merged(grads[0], query), merged(grads[1], key), merged(grads[2], value),
+        query, key, value, topo, dropout = _saved(ctx)
+        q, k, v, grad = (_float_replicas(x) for x in (query, key, value, grad_output))
+        grads = _attention_backward(
+            _many_mask_operators(query.size(0), ctx.nonzeros, topo, q.size(-2), k.size(-2)), q, k, v,
+            ctx.scale, grad.contiguous(), ctx.needs_input_grad[:3], dropout)
+        return (*(_like_input(g, x) for g, x in zip(grads, (query, key, value))),
                 None, None, None, None, None, None)
-
-
-def _heads_many_mask_forward(query, key, value, nonzeros, topo, scale, p=0.0):
-    """-> [B, m, H, D]; with dropout p > 0 -> (out, rng_state)."""
-    b, heads = query.size(0), query.size(2)
-    q, k, v = (x.transpose(1, 2) for x in (query, key, value))   # [B, H, S, D] views
-    if query.dtype in (torch.float16, torch.bfloat16) and (p > 0.0 or query.is_cuda):
-        plan = _many_mask_topology(b, q.size(-2), k.size(-2), q.size(-1), nonzeros, *topo)
-        if p > 0.0:
-            out, _, rng_state = ops.sparse_attention_heads_many_mask_dropout(b, nonzeros, *topo, q, k, v,
-                                                                             scale, p, plan=plan)
-        else:
-            out = ops.sparse_attention_heads_many_mask(b, nonzeros, *topo, q, k, v, scale, plan=plan)
-        out = out.transpose(1, 2)   # the kernel's [B, S, H, D] buffer
-    else:   # float32 views, CPU tensors: one copy to [B*H, S, D]
-        per_head = [x.reshape(b * heads, x.size(2), x.size(3)) for x in (q, k, v)]
-        out = _many_mask_forward(b, nonzeros, topo, *per_head, scale, p)
-        if p > 0.0:
-            out, rng_state = out
-        out = out.reshape(b, heads, query.size(1), -1).transpose(1, 2).to(query.dtype)
-    return (out, rng_state) if p > 0.0 else out
 
 
 def sparse_attention_heads_many_mask(query, key, value, nonzeros, row_indices, row_offsets,
@@ -1455,6 +1454,4 @@ def sparse_attention_heads_many_mask(query, key, value, nonzeros, row_indices, r
     topo = (row_indices, row_offsets, column_indices)
     if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
         return SparseAttentionHeadsManyMaskFunction.apply(query, key, value, nonzeros, *topo, scale, p)
-    if p > 0.0:
-        return _heads_many_mask_forward(query, key, value, nonzeros, topo, scale, p)[0]
-    return _heads_many_mask_forward(query, key, value, nonzeros, topo, scale)
+    return _heads_many_mask_forward(query, key, value, nonzeros, topo, scale, p)[0]

@@ -192,12 +192,8 @@ class SparseAttention(nn.Module):
                                               fused_backward=True)
             return functional.transpose_last2(out) if merged else out
         if self.low_memory_training:
-            if p > 0.0:
-                out = SparseAttentionFunction.apply(q3d, k3d, v3d, self.row_indices, self.row_offsets,
-                                                    self.column_indices, scale, p)
-            else:
-                out = SparseAttentionFunction.apply(q3d, k3d, v3d, self.row_indices,
-                                                    self.row_offsets, self.column_indices, scale)
+            out = SparseAttentionFunction.apply(q3d, k3d, v3d, self.row_indices, self.row_offsets,
+                                                self.column_indices, scale, p)
             return functional.transpose_last2(out) if merged else out
 
         # [B*H, nnz]: scores only at the mask's nonzeros
