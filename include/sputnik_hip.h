@@ -79,6 +79,20 @@ SPUTNIK_HIP_API const char* sputnik_hip_spmm_kernel_name(int m, int k, int n, in
 SPUTNIK_HIP_API const char* sputnik_hip_sddmm_kernel_name(int m, int k, int n, int nonzeros,
                                                           int replicas, int elem_bytes,
                                                           int planned);
+/* The instance of the sparse softmax kernel (softmax.hip) that a call of this shape launches
+ * for its first grid slice under the current options: values stored as `dtype`
+ * (SPUTNIK_HIP_F32 / F16 / BF16), `backward` != 0 for the gradient.  The class is
+ * `lanes_per_row` lanes per row with `base_pieces` 16-byte pieces per lane always worked on
+ * and `pieces` at the most; `rows_per_group` consecutive rows per lane group, `depth` rows in
+ * flight ahead, `nontemporal` 0 none / 1 loads / 2 stores / 3 both.  Host only, launches
+ * nothing; any output pointer may be NULL.  Returns SPUTNIK_HIP_INVALID_ARGUMENT for a call
+ * that launches nothing (m, nonzeros or replicas < 1) or an unknown dtype.  For tests, which
+ * assert the instance they mean to reach. */
+SPUTNIK_HIP_API int sputnik_hip_sparse_softmax_route(int m, int nonzeros, int replicas, int dtype,
+                                                     int backward, int* lanes_per_row,
+                                                     int* base_pieces, int* pieces,
+                                                     int* rows_per_group, int* depth,
+                                                     int* nontemporal);
 
 /* ------------------------------------------------------------------------
  * SpMM   C[m,n] = A_csr[m,k] * B[k,n]
@@ -655,6 +669,11 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_softmax_scaled_batched(int m, int n, int 
  * row sums over the stored entries.  The reference calls the raw op inside
  * attention (modules/sparse_attention.py:76), which cuts the gradient; the
  * intended autograd wrapper is tests/transformer/functions.py:70-120.
+ * Aliasing: `grad_values` may be the very buffer `grad_out` (same pointer, same stride:
+ * the gradient is overwritten in place) -- every entry of a row is read before any entry
+ * of that row is written, and a row's result depends on its own entries only.  Any other
+ * overlap of the output with an input is not supported.  The same holds for the _typed
+ * and _many_mask forms.
  */
 SPUTNIK_HIP_API int sputnik_hip_sparse_softmax_backward_batched(int m, int nonzeros,
                              int replicas, const float* softmax_out, int64_t out_stride,

@@ -108,6 +108,39 @@ def rel_err_torch(got, want):
 
 
 # ---------------------------------------------------------------------------
+# half storage (float16 / bfloat16): the oracle runs on the ROUNDED inputs, and what is
+# left to compare is the arithmetic plus one rounding of the output
+# ---------------------------------------------------------------------------
+def ulp(want, dtype):
+    """Spacing of the storage type at |want| (float16 subnormals included)."""
+    import torch
+    a = np.abs(np.asarray(want, np.float64))
+    if dtype == torch.float16:
+        return np.spacing(np.minimum(a, 65000.0).astype(np.float16)).astype(np.float64)
+    if dtype == torch.bfloat16:
+        return 2.0 ** (np.floor(np.log2(np.maximum(a, 2.0 ** -126))) - 7)
+    return np.zeros_like(a)
+
+
+def half_err(got, want, dtype, row_offsets=None):
+    """rel_err of what is left of |got - want| after ONE unit in the last place of
+    the output's storage type (its rounding) has been taken off: the test is
+    ``half_err(...) < 1e-4``, the float32 bound on the arithmetic."""
+    got = np.asarray(got, np.float64)
+    want = np.asarray(want, np.float64)
+    diff = got - want
+    rest = np.sign(diff) * np.maximum(np.abs(diff) - ulp(want, dtype), 0.0)
+    return rel_err(want + rest, want, row_offsets)
+
+
+def rounded(x, dtype, dev):
+    """(device tensor in `dtype`, the same values as float32 numpy)."""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32))).to(dev).to(dtype)
+    return t, t.float().cpu().numpy()
+
+
+# ---------------------------------------------------------------------------
 # many-mask family: masks of mixed kinds and float64 references (torch, any device)
 # ---------------------------------------------------------------------------
 MASK_KINDS = ("empty", "single", "uniform", "band", "global", "heavy_row", "empty_rows")

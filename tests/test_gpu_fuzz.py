@@ -128,6 +128,7 @@ def test_fuzz_sddmm_planned_pair_flat(capi, dev, monkeypatch):
 
 def test_fuzz_sddmm_softmax_transpose(capi, dev, sddmm_kernel):
     rng = np.random.default_rng(77 + SEED_SHIFT)
+    grad_rng = np.random.default_rng(78 + SEED_SHIFT)   # (its own stream: the cases stay those of `rng`)
     for it in range(40 * SCALE):
         m, n, sparsity, empty, order, replicas = _case(rng, [16, 64, 128, 256, 300], [16, 64, 128, 256, 300])
         k = int(rng.choice([1, 5, 32, 64, 64, 128, 128, 200, 256, 320, 512, 768, 1024]))
@@ -151,6 +152,20 @@ def test_fuzz_sddmm_softmax_transpose(capi, dev, sddmm_kernel):
                                                    torch.empty_like(scores))
         want_p = O.sparse_softmax_scaled(got, ri, ro, ci, scale)
         assert rel_err(probs.cpu().numpy(), want_p, ro) < TOL, (it, m, n)
+
+        # The gradient, through the weights at the attention's own scale k ** -0.5.  (With the
+        # scales above, the rows of large k are one-hot to float32, and dx = y * (dy - sum dy y)
+        # of a one-hot row is a difference that cancels down to the last bits of its operands:
+        # float64 resolves it, no float32 evaluation holds a bound relative to that row's own
+        # vanishing magnitude.)
+        weights = capi.sparse_softmax_scaled_batched(m, replicas, scores, d_ri, d_ro, d_ci, k ** -0.5,
+                                                     torch.empty_like(scores))
+        assert rel_err(weights.cpu().numpy(), O.sparse_softmax_scaled(got, ri, ro, ci, k ** -0.5), ro) < TOL
+        grad = T(grad_rng.uniform(-1, 1, (replicas, nnz)).astype(np.float32), dev)
+        dscores = capi.sparse_softmax_backward_batched(m, replicas, weights, grad, d_ro, k ** -0.5,
+                                                       torch.full_like(weights, float("nan")))
+        want_d = O.sparse_softmax_backward(weights.cpu().numpy(), grad.cpu().numpy(), ro, k ** -0.5)
+        assert rel_err(dscores.cpu().numpy(), want_d, ro) < TOL, (it, m, n)
 
         tws = torch.empty(capi.csr_transpose_workspace_bytes(m, n, nnz), dtype=torch.uint8, device=dev)
         vt = torch.empty_like(probs)

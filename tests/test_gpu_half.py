@@ -14,33 +14,12 @@ import torch
 
 from oracle import c_oracle
 from oracle import sputnik_oracle as O
-from tests.helpers import make_csr, rel_err
+from tests.helpers import half_err, make_csr, rel_err, rounded
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4                                                  # float32 outputs
 HALF_TYPES = [torch.float16, torch.bfloat16]
-
-
-def ulp(want, dtype):
-    """Spacing of the storage type at |want| (float16 subnormals included)."""
-    a = np.abs(np.asarray(want, np.float64))
-    if dtype == torch.float16:
-        return np.spacing(np.minimum(a, 65000.0).astype(np.float16)).astype(np.float64)
-    if dtype == torch.bfloat16:
-        return 2.0 ** (np.floor(np.log2(np.maximum(a, 2.0 ** -126))) - 7)
-    return np.zeros_like(a)
-
-
-def half_err(got, want, dtype, row_offsets=None):
-    """rel_err of what is left of |got - want| after ONE unit in the last place of
-    the output's storage type (its rounding) has been taken off: the test is
-    ``half_err(...) < 1e-4``, the float32 bound on the arithmetic."""
-    got = np.asarray(got, np.float64)
-    want = np.asarray(want, np.float64)
-    diff = got - want
-    rest = np.sign(diff) * np.maximum(np.abs(diff) - ulp(want, dtype), 0.0)
-    return rel_err(want + rest, want, row_offsets)
 
 
 @pytest.fixture(scope="module")
@@ -64,12 +43,6 @@ def ts():
 
 def T(x, dev):
     return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-
-
-def rounded(x, dtype, dev):
-    """(device tensor in `dtype`, the same values as float32 numpy)."""
-    t = T(np.asarray(x, np.float32), dev).to(dtype)
-    return t, t.float().cpu().numpy()
 
 
 # ----------------------------------------------------------------------------

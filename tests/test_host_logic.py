@@ -259,3 +259,46 @@ def test_sparse_attention_matches_dense(cpu_ops):
     ctx = torch.matmul(probs, vd).transpose(1, 2).reshape(batch, seq, emb)
     want = torch.matmul(ctx, ws[3].t())
     assert rel_err(out.detach().numpy(), want.numpy()) < 1e-4
+
+
+def test_sparse_softmax_route_reports_the_launch_decisions(monkeypatch):
+    """sputnik_hip_sparse_softmax_route is host only: the class by mean row length and storage
+    type, two rows per group once m * replicas fills the chip, nontemporal stores for a forward
+    output of 128 MiB per grid slice, and the developer knobs."""
+    from torch_sputnik_amd import capi
+    for name in ("SPUTNIK_HIP_SOFTMAX_RPG", "SPUTNIK_HIP_SOFTMAX_DEPTH", "SPUTNIK_HIP_SOFTMAX_NT"):
+        monkeypatch.delenv(name, raising=False)
+    capi.reload_options()
+    try:
+        def route(*args, **kw):
+            r = capi.sparse_softmax_route(*args, **kw)
+            return ((r["lanes_per_row"], r["base_pieces"], r["pieces"]), r["rows_per_group"], r["depth"],
+                    r["nontemporal"])
+        # config 3's mask (1024 x 1024 at density 0.1): mean 102, need 102 + 23 + 3
+        assert route(1024, 104858, 64) == ((16, 2, 3), 2, 1, 0)
+        assert route(1024, 104858, 512) == ((16, 2, 3), 2, 1, 2)         # 215 MB out
+        assert route(1024, 104858, 512, backward=True) == ((16, 2, 3), 2, 1, 0)
+        assert route(1024, 104858, 64, torch.float16) == ((16, 1, 2), 2, 1, 0)
+        assert route(1024, 104858, 3) == ((16, 2, 3), 1, 1, 0)
+        # class boundaries (need = mean + ceil(sqrt(5 mean)) + 3 against 64 / 128 / 192 / 256 / 512)
+        wants = [(40, (16, 1, 2)), (100, (16, 2, 3)), (150, (16, 3, 4)), (200, (32, 2, 4)),
+                 (400, (32, 4, 4)), (600, (64, 4, 4))]
+        for mean, cls in wants:
+            assert route(10, 10 * mean, 1)[0] == cls, mean
+        for mean, cls in [(100, (16, 1, 2)), (200, (16, 2, 3)), (400, (32, 2, 3)), (600, (64, 2, 2))]:
+            assert route(10, 10 * mean, 1, torch.bfloat16)[0] == cls, mean
+        # the 128 MiB threshold is per grid slice of at most 65535 replicas
+        assert route(1, 512, 65536)[3] == 0 and route(1, 513, 65536)[3] == 2
+        monkeypatch.setenv("SPUTNIK_HIP_SOFTMAX_RPG", "40")
+        monkeypatch.setenv("SPUTNIK_HIP_SOFTMAX_NT", "3")
+        capi.reload_options()
+        assert route(1024, 104858, 3) == ((16, 2, 3), 16, 1, 3)
+        monkeypatch.setenv("SPUTNIK_HIP_SOFTMAX_DEPTH", "3")
+        capi.reload_options()
+        assert route(1024, 104858, 3) == ((16, 2, 3), 16, 3, 0)
+        with pytest.raises(RuntimeError):
+            capi.sparse_softmax_route(0, 10, 1)
+    finally:
+        for name in ("SPUTNIK_HIP_SOFTMAX_RPG", "SPUTNIK_HIP_SOFTMAX_DEPTH", "SPUTNIK_HIP_SOFTMAX_NT"):
+            monkeypatch.delenv(name, raising=False)
+        capi.reload_options()

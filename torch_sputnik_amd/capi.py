@@ -36,6 +36,7 @@ SIGNATURES = {
     "sputnik_hip_build_id": (ctypes.c_char_p, []),
     "sputnik_hip_spmm_kernel_name": (ctypes.c_char_p, [_c_int] * 5),
     "sputnik_hip_sddmm_kernel_name": (ctypes.c_char_p, [_c_int] * 7),
+    "sputnik_hip_sparse_softmax_route": (_c_int, [_c_int] * 5 + [_c_ptr] * 6),
     "sputnik_hip_reload_options": (None, []),
     "sputnik_hip_spmm": (_c_int, [_c_int] * 4 + [_c_ptr] * 7),
     "sputnik_hip_spmm_workspace_bytes": (_c_size, [_c_int] * 4),
@@ -267,6 +268,18 @@ def sddmm_kernel_name(m, k, n, nonzeros, replicas=1, elem_bytes=4, planned=False
                                                int(bool(planned))).decode()
 
 
+def sparse_softmax_route(m, nonzeros, replicas, dtype=torch.float32, backward=False):
+    """Kernel instance the sparse softmax launches for a call of this shape under the current
+    options: a dict of lanes_per_row, base_pieces, pieces (the class), rows_per_group, depth
+    and nontemporal.  Host only."""
+    names = ("lanes_per_row", "base_pieces", "pieces", "rows_per_group", "depth", "nontemporal")
+    outs = [_c_int(-1) for _ in names]
+    _check(lib().sputnik_hip_sparse_softmax_route(
+        m, nonzeros, replicas, TYPE_CODES[dtype], int(bool(backward)),
+        *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]), "sputnik_hip_sparse_softmax_route")
+    return {name: o.value for name, o in zip(names, outs)}
+
+
 def reload_options():
     """Re-read the SPUTNIK_HIP_* knobs from the environment (read once otherwise)."""
     lib().sputnik_hip_reload_options()
@@ -428,8 +441,14 @@ def spmm_bias_batched(m, k, n, replicas, row_indices, values, values_stride, row
     return out
 
 
+def _stride(stride, nonzeros):
+    return nonzeros if stride is None else int(stride)
+
+
 def sparse_softmax_scaled_batched(m, replicas, values, row_indices, row_offsets, column_indices,
-                                  scale, out):
+                                  scale, out, *, values_stride=None, out_stride=None):
+    """Replica r of an operand begins r * its stride elements into the tensor (default: the
+    rows follow each other, stride = nonzeros)."""
     nonzeros = column_indices.numel()
     for t, d, nm in ((values, torch.float32, "values"), (row_indices, torch.int32, "row_indices"),
                      (row_offsets, torch.int32, "row_offsets"),
@@ -437,23 +456,29 @@ def sparse_softmax_scaled_batched(m, replicas, values, row_indices, row_offsets,
                      (out, torch.float32, "out")):
         _require(t, d, nm)
     _check(lib().sputnik_hip_sparse_softmax_scaled_batched(
-        m, -1, nonzeros, replicas, _ptr(values), nonzeros, _ptr(row_indices), _ptr(row_offsets),
-        _ptr(column_indices), float(scale), _ptr(out), nonzeros, _stream(out)),
+        m, -1, nonzeros, replicas, _ptr(values), _stride(values_stride, nonzeros), _ptr(row_indices),
+        _ptr(row_offsets), _ptr(column_indices), float(scale), _ptr(out),
+        _stride(out_stride, nonzeros), _stream(out)),
         "sputnik_hip_sparse_softmax_scaled_batched")
     return out
 
 
 def sparse_softmax_backward_batched(m, replicas, softmax_out, grad_out, row_offsets, scale,
-                                    grad_values):
-    nonzeros = softmax_out.shape[-1]
+                                    grad_values, *, nonzeros=None, softmax_out_stride=None,
+                                    grad_out_stride=None, grad_values_stride=None):
+    """`nonzeros` (default: the last dimension of softmax_out) and one stride per operand
+    (default: nonzeros) describe operands that are flat views into padded buffers."""
+    if nonzeros is None:
+        nonzeros = softmax_out.shape[-1]
     for t, d, nm in ((softmax_out, torch.float32, "softmax_out"),
                      (grad_out, torch.float32, "grad_out"),
                      (row_offsets, torch.int32, "row_offsets"),
                      (grad_values, torch.float32, "grad_values")):
         _require(t, d, nm)
     _check(lib().sputnik_hip_sparse_softmax_backward_batched(
-        m, nonzeros, replicas, _ptr(softmax_out), nonzeros, _ptr(grad_out), nonzeros,
-        _ptr(row_offsets), float(scale), _ptr(grad_values), nonzeros, _stream(grad_values)),
+        m, nonzeros, replicas, _ptr(softmax_out), _stride(softmax_out_stride, nonzeros),
+        _ptr(grad_out), _stride(grad_out_stride, nonzeros), _ptr(row_offsets), float(scale),
+        _ptr(grad_values), _stride(grad_values_stride, nonzeros), _stream(grad_values)),
         "sputnik_hip_sparse_softmax_backward_batched")
     return grad_values
 
@@ -528,28 +553,36 @@ def sddmm_typed(m, k, n, replicas, row_indices, row_offsets, column_indices, lhs
     return out
 
 
-def sparse_softmax_typed(m, replicas, values, row_indices, row_offsets, column_indices, scale, out):
-    """softmax(scale * values) on float32 / float16 / bfloat16 storage (in and out alike)."""
+def sparse_softmax_typed(m, replicas, values, row_indices, row_offsets, column_indices, scale, out,
+                         *, values_stride=None, out_stride=None):
+    """softmax(scale * values) on float32 / float16 / bfloat16 storage (in and out alike);
+    strides in elements, default nonzeros."""
     nonzeros = column_indices.numel()
     for t, nm in ((row_indices, "row_indices"), (row_offsets, "row_offsets"),
                   (column_indices, "column_indices")):
         _require(t, torch.int32, nm)
     code = _type_code(values, out)
     _check(lib().sputnik_hip_sparse_softmax_typed(
-        m, -1, nonzeros, replicas, _ptr(values), nonzeros, _ptr(row_indices), _ptr(row_offsets),
-        _ptr(column_indices), float(scale), _ptr(out), nonzeros, code, _stream(out)),
+        m, -1, nonzeros, replicas, _ptr(values), _stride(values_stride, nonzeros), _ptr(row_indices),
+        _ptr(row_offsets), _ptr(column_indices), float(scale), _ptr(out),
+        _stride(out_stride, nonzeros), code, _stream(out)),
         "sputnik_hip_sparse_softmax_typed")
     return out
 
 
 def sparse_softmax_backward_typed(m, replicas, softmax_out, grad_out, row_offsets, scale,
-                                  grad_values):
-    nonzeros = softmax_out.shape[-1]
+                                  grad_values, *, nonzeros=None, softmax_out_stride=None,
+                                  grad_out_stride=None, grad_values_stride=None):
+    """`nonzeros` (default: the last dimension of softmax_out) and one stride per operand, in
+    elements (default: nonzeros)."""
+    if nonzeros is None:
+        nonzeros = softmax_out.shape[-1]
     _require(row_offsets, torch.int32, "row_offsets")
     code = _type_code(softmax_out, grad_out, grad_values)
     _check(lib().sputnik_hip_sparse_softmax_backward_typed(
-        m, nonzeros, replicas, _ptr(softmax_out), nonzeros, _ptr(grad_out), nonzeros,
-        _ptr(row_offsets), float(scale), _ptr(grad_values), nonzeros, code, _stream(grad_values)),
+        m, nonzeros, replicas, _ptr(softmax_out), _stride(softmax_out_stride, nonzeros),
+        _ptr(grad_out), _stride(grad_out_stride, nonzeros), _ptr(row_offsets), float(scale),
+        _ptr(grad_values), _stride(grad_values_stride, nonzeros), code, _stream(grad_values)),
         "sputnik_hip_sparse_softmax_backward_typed")
     return grad_values
 

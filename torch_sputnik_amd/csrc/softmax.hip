@@ -94,6 +94,12 @@ __device__ __forceinline__ float widen(T v) { return static_cast<float>(v); }
 // passes (re-reads served by L2).  exp is the hardware v_exp_f32 path (__expf):
 // relative error about 5e-6 at |x - max| ~ 88, far inside the 1e-4 budget; the
 // accurate library expf made the kernel VALU-bound.
+//
+// `out` may be the buffer `b` itself (the gradient overwritten in place: the header says so,
+// tests/test_gpu_softmax_instances.py pins it), `__restrict__` notwithstanding: a row's own
+// entries are loaded (fetch, or the strided passes' reads of a[q], b[q] before out[q]) before
+// any of them is stored, the stores touch the row's own entries only, and what a 16-byte
+// piece holds of a neighbouring row -- old or already overwritten -- is masked.
 template <typename T, int LPR, int BASE, int V, bool BACKWARD, int DEPTH, int NT>
 __global__ __launch_bounds__(kBlock) void sparse_softmax_rows_kernel(
     int m, int rows_per_group, int nonzeros, const T* __restrict__ a, int64_t a_stride,
@@ -301,33 +307,111 @@ __global__ __launch_bounds__(kBlock) void sparse_softmax_rows_kernel(
   }
 }
 
+// The launches in which no row can be fast (launch_rows' same_phase off): one row per group
+// of LPR lanes, the three strided passes of the kernel above and nothing else.  That kernel
+// loads its window of clamped pieces whether or not a row is fast, and without same_phase
+// the window is not one to load from: below two pieces of entries the buffer may hold no
+// whole aligned piece (qmax < qmin, and a byte offset below zero wraps to 4 GiB), and with
+// unequal strides the second operand's buffer is not where the first one's limits say.
+// (A kernel of its own rather than a branch around the loads of the other one: the branch
+// cost the benchmarked sizes 3-6 %.)
+template <typename T, int LPR, bool BACKWARD>
+__global__ __launch_bounds__(kBlock) void sparse_softmax_strided_kernel(
+    int m, const T* __restrict__ a, int64_t a_stride, const T* __restrict__ b, int64_t b_stride,
+    const int* __restrict__ row_offsets, T* __restrict__ out, int64_t out_stride, float scale,
+    int mask_heads, int first_replica, unsigned long long mask_members) {
+  if (mask_members != 0 &&
+      !((mask_members >> ((first_replica + static_cast<int>(blockIdx.y)) / mask_heads)) & 1ull))
+    return;
+  const int l = threadIdx.x % LPR;
+  const int row = (blockIdx.x * kBlock + threadIdx.x) / LPR;
+  const int replica = blockIdx.y;
+  if (mask_heads > 0) row_offsets += static_cast<int64_t>((first_replica + replica) / mask_heads) * (m + 1);
+  a += replica * a_stride;
+  if constexpr (BACKWARD) b += replica * b_stride;
+  out += replica * out_stride;
+  // (groups past the last row keep an empty row)
+  const int p0 = row < m ? row_offsets[row] : 0;
+  const int p1 = row < m ? row_offsets[row + 1] : 0;
+  if (p1 <= p0) return;
+  if constexpr (!BACKWARD) {
+    float mx = -INFINITY;
+    for (int q = p0 + l; q < p1; q += LPR) mx = fmaxf(mx, widen(a[q]) * scale);
+    mx = group_max<LPR>(mx);
+    float sum = 0.f;
+    for (int q = p0 + l; q < p1; q += LPR) sum += __expf(widen(a[q]) * scale - mx);
+    sum = group_sum<LPR>(sum);
+    const float inv = 1.f / sum;
+    for (int q = p0 + l; q < p1; q += LPR)
+      out[q] = static_cast<T>(__expf(widen(a[q]) * scale - mx) * inv);
+  } else {
+    float dot = 0.f;
+    for (int q = p0 + l; q < p1; q += LPR) dot = fmaf(widen(a[q]), widen(b[q]), dot);
+    dot = group_sum<LPR>(dot);
+    for (int q = p0 + l; q < p1; q += LPR)
+      out[q] = static_cast<T>(scale * widen(a[q]) * (widen(b[q]) - dot));
+  }
+}
+
 template <typename T>
 inline int phase_of(const T* p) {
   // alignment class of the first replica (the kernel recomputes it per replica)
   return static_cast<int>((reinterpret_cast<uintptr_t>(p) / sizeof(T)) % Piece<T>::kEntries);
 }
 
-template <typename T, int LPR, int BASE, int V, bool BACKWARD>
-int launch_rows(int m, int nonzeros, int replicas, const T* a, int64_t a_stride, const T* b,
-                int64_t b_stride, const int* row_offsets, T* out, int64_t out_stride,
-                float scale, hipStream_t stream, int mask_heads, unsigned long long mask_members) {
-  // Two rows per group once the grid fills the chip (256 CUs x 8 workgroups):
-  // measured at config 3's mask with 64 and 512 replicas (tools/softmax_sweep.sh),
-  // short workgroups whose dispatch staggers the read and the write phases beat
-  // longer runs per group (1 / 2 / 4 / 16 rows: 104 / 99 / 102 / 110 us at 512).
-  const int groups_per_block = kBlock / LPR;
+// The host's run-time choices for one launch; sputnik_hip_sparse_softmax_route reports
+// what these return, launch_rows launches what they return.
+//
+// Two rows per group once the grid fills the chip (256 CUs x 8 workgroups):
+// measured at config 3's mask with 64 and 512 replicas (tools/softmax_sweep.sh),
+// short workgroups whose dispatch staggers the read and the write phases beat
+// longer runs per group (1 / 2 / 4 / 16 rows: 104 / 99 / 102 / 110 us at 512).
+inline int rows_per_group_of(int m, int replicas, int lanes_per_row) {
+  const int groups_per_block = kBlock / lanes_per_row;
   const int64_t total_rows = static_cast<int64_t>(m) * replicas;
   int rows_per_group = static_cast<int>(total_rows / (int64_t{256} * 8 * groups_per_block));
   rows_per_group = max(1, min(rows_per_group, 2));
   if (options().softmax_rpg > 0) rows_per_group = min(options().softmax_rpg, 16);  // developer knob
-  const int depth = options().softmax_depth;                                       // developer knob
+  return rows_per_group;
+}
+// Rows in flight ahead of the one being reduced (developer knob): 2 and 3 exist, anything
+// else is 1.
+inline int depth_of() {
+  const int depth = options().softmax_depth;
+  return depth == 3 ? 3 : depth == 2 ? 2 : 1;
+}
+// Nontemporal STORES in the forward pass when the output is larger than the
+// caches can hand to the next kernel anyway (measured, 1024^2 mask at density
+// 0.1: 512 replicas, 215 MB out, 88.4 -> 75.8 us; 64 replicas 12.5 -> 12.2 us
+// alone but +8 us on the attention step that reads the 27 MB straight back).
+// In the backward pass they cost 4-5 %, nontemporal loads 15-35 % in both.
+// Developer knob: 0 = none, 1 = loads, 2 = stores, 3 = both.  Depths 2 and 3 are built
+// without the hint.  `slice_replicas`: those of one launch (at most kMaxGridYZ).
+inline int nontemporal_of(bool backward, int depth, int slice_replicas, int nonzeros,
+                          int elem_bytes) {
+  if (depth != 1) return 0;
+  const bool large_out =
+      static_cast<int64_t>(slice_replicas) * nonzeros * elem_bytes >= (int64_t{128} << 20);
+  const int nt = options().softmax_nt >= 0 ? options().softmax_nt
+                                          : (!backward && large_out) ? 2 : 0;
+  return nt >= 1 && nt <= 3 ? nt : 0;
+}
+
+template <typename T, int LPR, int BASE, int V, bool BACKWARD>
+int launch_rows(int m, int nonzeros, int replicas, const T* a, int64_t a_stride, const T* b,
+                int64_t b_stride, const int* row_offsets, T* out, int64_t out_stride,
+                float scale, hipStream_t stream, int mask_heads, unsigned long long mask_members) {
+  const int groups_per_block = kBlock / LPR;
+  const int rows_per_group = rows_per_group_of(m, replicas, LPR);
+  const int depth = depth_of();
   const int gx = ceil_div(ceil_div(m, rows_per_group), groups_per_block);
   // The fast path needs the inputs and the output of every replica aligned alike
   // and 32-bit byte offsets.  Its window of clamped 16-byte pieces is derived from
   // ONE stride and applied to every operand, so the strides must be EQUAL (fresh
   // allocations: the common case), not merely congruent: with a broadcast gradient
-  // (stride 0) or a padded input the unconditional loads of the other operand would
-  // reach up to a window outside its buffer.
+  // (stride 0) or a padded input the loads of the other operand would reach up to a
+  // window outside its buffer.  Without same_phase the launch goes to
+  // sparse_softmax_strided_kernel, which loads no window.
   const bool strides_alike = a_stride == out_stride && (!BACKWARD || a_stride == b_stride);
   for (int r0 = 0; r0 < replicas; r0 += kMaxGridYZ) {
     const int ry = min(replicas - r0, kMaxGridYZ);
@@ -344,17 +428,13 @@ int launch_rows(int m, int nonzeros, int replicas, const T* a, int64_t a_stride,
                      dim3(kBlock), 0, stream, m, rows_per_group, nonzeros, a_r, a_stride, b_r,   \
                      b_stride, row_offsets, out_r, out_stride, scale, same_phase, mask_heads, r0, \
                      mask_members)
-    // Nontemporal STORES in the forward pass when the output is larger than the
-    // caches can hand to the next kernel anyway (measured, 1024^2 mask at density
-    // 0.1: 512 replicas, 215 MB out, 88.4 -> 75.8 us; 64 replicas 12.5 -> 12.2 us
-    // alone but +8 us on the attention step that reads the 27 MB straight back).
-    // In the backward pass they cost 4-5 %, nontemporal loads 15-35 % in both.
-    // Developer knob: 0 = none, 1 = loads, 2 = stores, 3 = both.
-    const bool large_out =
-        static_cast<int64_t>(ry) * nonzeros * static_cast<int64_t>(sizeof(T)) >= (int64_t{128} << 20);
-    const int nt = options().softmax_nt >= 0 ? options().softmax_nt
-                                            : (!BACKWARD && large_out) ? 2 : 0;
-    if (depth == 3) SPUTNIK_HIP_SOFTMAX_LAUNCH(3, 0);
+    const int nt = nontemporal_of(BACKWARD, depth, ry, nonzeros, static_cast<int>(sizeof(T)));
+    if (!same_phase)
+      hipLaunchKernelGGL((sparse_softmax_strided_kernel<T, LPR, BACKWARD>),
+                         dim3(ceil_div(m, groups_per_block), ry), dim3(kBlock), 0, stream, m, a_r,
+                         a_stride, b_r, b_stride, row_offsets, out_r, out_stride, scale, mask_heads,
+                         r0, mask_members);
+    else if (depth == 3) SPUTNIK_HIP_SOFTMAX_LAUNCH(3, 0);
     else if (depth == 2) SPUTNIK_HIP_SOFTMAX_LAUNCH(2, 0);
     else if (nt == 1) SPUTNIK_HIP_SOFTMAX_LAUNCH(1, 1);
     else if (nt == 2) SPUTNIK_HIP_SOFTMAX_LAUNCH(1, 2);
@@ -380,9 +460,22 @@ inline int64_t entries_a_row_needs(int m, int64_t nonzeros) {
   while (dev * dev < 5 * mean) ++dev;   // ~ 2.2 * sqrt(mean)
   return mean + dev + 3;
 }
-// The float kernels' classes by that need (the cases of dispatch_rows below).
+// The float kernels' classes by that need (kFloatClasses below).
 inline int float_class_of(int64_t need) {
   return need <= 64 ? 0 : need <= 128 ? 1 : need <= 192 ? 2 : need <= 256 ? 3 : need <= 512 ? 4 : 5;
+}
+// A class of kernel instances: LPR lanes per row, BASE pieces per lane always worked on, V at
+// the most.
+struct RowsClass { int lanes_per_row, base_pieces, pieces; };
+constexpr RowsClass kFloatClasses[] = {{16, 1, 2}, {16, 2, 3}, {16, 3, 4}, {32, 2, 4}, {32, 4, 4}, {64, 4, 4}};
+constexpr RowsClass kHalfClasses[] = {{16, 1, 2}, {16, 2, 3}, {32, 2, 3}, {64, 2, 2}};
+// The class that serves a mask of `nonzeros` entries in m rows, stored as pieces of
+// `entries_per_piece` (half types: 8 entries per piece and lane, so twice the need per class).
+inline RowsClass rows_class_of(int entries_per_piece, int m, int64_t nonzeros) {
+  const int64_t need = entries_a_row_needs(m, nonzeros);
+  if (entries_per_piece == 8)
+    return kHalfClasses[need <= 128 ? 0 : need <= 256 ? 1 : need <= 512 ? 2 : 3];
+  return kFloatClasses[float_class_of(need)];
 }
 
 template <typename T, bool BACKWARD>
@@ -392,25 +485,27 @@ int dispatch_rows(int m, int nonzeros, int replicas, const T* a, int64_t a_strid
                   int typical_nonzeros = -1, unsigned long long mask_members = 0) {
   // (many masks: `nonzeros` is the width of a value row -- what may be read --, the
   // window is sized for `typical_nonzeros`, the largest mask of the launch)
-  const int64_t need = entries_a_row_needs(m, typical_nonzeros >= 0 ? typical_nonzeros : nonzeros);
+  const RowsClass c = rows_class_of(Piece<T>::kEntries, m, typical_nonzeros >= 0 ? typical_nonzeros : nonzeros);
 #define SPUTNIK_HIP_SOFTMAX_CASE(LPR, BASE, V)                                                    \
-  return launch_rows<T, LPR, BASE, V, BACKWARD>(m, nonzeros, replicas, a, a_stride, b, b_stride,  \
-                                                row_offsets, out, out_stride, scale, stream,      \
-                                                mask_heads, mask_members)
-  if constexpr (Piece<T>::kEntries == 8) {   // half types: 8 entries per piece and lane
-    if (need <= 128) SPUTNIK_HIP_SOFTMAX_CASE(16, 1, 2);
-    if (need <= 256) SPUTNIK_HIP_SOFTMAX_CASE(16, 2, 3);
-    if (need <= 512) SPUTNIK_HIP_SOFTMAX_CASE(32, 2, 3);
+  if (c.lanes_per_row == LPR && c.base_pieces == BASE && c.pieces == V)                           \
+    return launch_rows<T, LPR, BASE, V, BACKWARD>(m, nonzeros, replicas, a, a_stride, b, b_stride, \
+                                                  row_offsets, out, out_stride, scale, stream,    \
+                                                  mask_heads, mask_members)
+  if constexpr (Piece<T>::kEntries == 8) {
+    SPUTNIK_HIP_SOFTMAX_CASE(16, 1, 2);
+    SPUTNIK_HIP_SOFTMAX_CASE(16, 2, 3);
+    SPUTNIK_HIP_SOFTMAX_CASE(32, 2, 3);
     SPUTNIK_HIP_SOFTMAX_CASE(64, 2, 2);
   } else {
-    if (need <= 64) SPUTNIK_HIP_SOFTMAX_CASE(16, 1, 2);
-    if (need <= 128) SPUTNIK_HIP_SOFTMAX_CASE(16, 2, 3);
-    if (need <= 192) SPUTNIK_HIP_SOFTMAX_CASE(16, 3, 4);
-    if (need <= 256) SPUTNIK_HIP_SOFTMAX_CASE(32, 2, 4);
-    if (need <= 512) SPUTNIK_HIP_SOFTMAX_CASE(32, 4, 4);
+    SPUTNIK_HIP_SOFTMAX_CASE(16, 1, 2);
+    SPUTNIK_HIP_SOFTMAX_CASE(16, 2, 3);
+    SPUTNIK_HIP_SOFTMAX_CASE(16, 3, 4);
+    SPUTNIK_HIP_SOFTMAX_CASE(32, 2, 4);
+    SPUTNIK_HIP_SOFTMAX_CASE(32, 4, 4);
     SPUTNIK_HIP_SOFTMAX_CASE(64, 4, 4);
   }
 #undef SPUTNIK_HIP_SOFTMAX_CASE
+  return SPUTNIK_HIP_INVALID_ARGUMENT;   // (a class without an instance: unreachable)
 }
 
 // Storage type dispatch (SPUTNIK_HIP_F32 / F16 / BF16 of include/sputnik_hip.h): every
@@ -492,6 +587,25 @@ int softmax_many_mask(bool backward, int m, int width, int largest_nonzeros, int
 using namespace sputnik_hip;
 
 extern "C" {
+
+int sputnik_hip_sparse_softmax_route(int m, int nonzeros, int replicas, int dtype, int backward,
+                                     int* lanes_per_row, int* base_pieces, int* pieces,
+                                     int* rows_per_group, int* depth, int* nontemporal) {
+  if (dtype != SPUTNIK_HIP_F32 && dtype != SPUTNIK_HIP_F16 && dtype != SPUTNIK_HIP_BF16)
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (m <= 0 || nonzeros <= 0 || replicas <= 0) return SPUTNIK_HIP_INVALID_ARGUMENT;   // no launch
+  const int elem_bytes = dtype == SPUTNIK_HIP_F32 ? 4 : 2;
+  const RowsClass c = rows_class_of(16 / elem_bytes, m, nonzeros);
+  const int d = depth_of();
+  if (lanes_per_row) *lanes_per_row = c.lanes_per_row;
+  if (base_pieces) *base_pieces = c.base_pieces;
+  if (pieces) *pieces = c.pieces;
+  if (rows_per_group) *rows_per_group = rows_per_group_of(m, replicas, c.lanes_per_row);
+  if (depth) *depth = d;
+  if (nontemporal)
+    *nontemporal = nontemporal_of(backward != 0, d, min(replicas, kMaxGridYZ), nonzeros, elem_bytes);
+  return 0;
+}
 
 int sputnik_hip_sparse_softmax_typed(int m, int n, int nonzeros, int replicas, const void* values,
                                      int64_t values_stride, const int* row_indices,
