@@ -110,17 +110,19 @@ def test_keep_rate_and_fresh_masks(dev):
 # ---------------------------------------------------------------------------
 # 3-5: the fused forms against float64
 # ---------------------------------------------------------------------------
-def dense_keep(csr_masks, state, replicas, p, m, n, per_mask):
+def dense_keep(csr_masks, state, replicas, p, m, n, per_mask, only=None):
     """[R, m, n] float64 factor keep * scale from the (r, e) layout: e is the CSR position of
-    the replica's mask (per_mask: replicas // len(csr_masks) replicas per mask)."""
+    the replica's mask (per_mask: replicas // len(csr_masks) replicas per mask).  only: the
+    replica numbers to build it for ([len(only), m, n]), all of them by default."""
     width = max(len(ci) for _, ci in csr_masks) if csr_masks else 0
     keep = P.keep_mask_of(state, replicas, max(width, 1), p)
-    out = np.zeros((replicas, m, n))
-    for r in range(replicas):
+    which = range(replicas) if only is None else only
+    out = np.zeros((len(which), m, n))
+    for at, r in enumerate(which):
         ro, ci = csr_masks[r // per_mask]
         for i in range(m):
             for e in range(ro[i], ro[i + 1]):
-                out[r, i, ci[e]] = keep[r, e] * float(P.keep_scale(p))
+                out[at, i, ci[e]] = keep[r, e] * float(P.keep_scale(p))
     return torch.from_numpy(out)
 
 
@@ -206,6 +208,50 @@ def test_single_mask_f32_forward_backward(dev, case):
     want.backward(go.cpu().double())
     for got, ref in ((qg.grad, qd.grad), (kg.grad, kd.grad), (vg.grad, vd.grad)):
         assert rel_err_torch(got.cpu(), ref) < TOL[torch.float32]
+
+
+@pytest.mark.parametrize("p", [0.0, 0.25])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+def test_replicas_beyond_one_grid_slice(dev, dtype, p):
+    """R = 65537 replicas of a 4 x 4 mask: the forward runs in grid slices of 65535 replicas,
+    and the second slice has to number its replicas from 65535 on -- for its operands, its
+    lse rows and the (r, e) of the dropout mask.  float32 [R, 4, 64] and float16 [R, 4, 64]
+    (one head per batch element).  The replicas on both sides of the slice boundary against
+    float64, every replica against the composed chain with the same rng_state."""
+    from torch_sputnik_amd import ops
+    R, m, n, d = 65537, 4, 4, 64
+    probes = [0, 65534, 65535, 65536]
+    dense, csr = make_masks(1, m, n, 17, density=0.6)   # (make_masks leaves one row empty)
+    assert 0 in np.diff(csr[0][0]) and len(csr[0][1]) >= 4
+    topo = topo_single(csr, dev)
+    torch.manual_seed(9)
+    q, k, v = (torch.randn(R, m, d, device=dev).to(dtype) for _ in range(3))
+    scale, state = 1 / math.sqrt(d), None
+    if dtype == torch.float32:
+        if p > 0.0:
+            out, lse, state = ops.sparse_attention_dropout(q, k, v, *topo, scale, p)
+        else:
+            out, lse = ops.sparse_attention_with_lse(q, k, v, *topo, scale)
+    elif p > 0.0:
+        out, lse, state = ops.sparse_attention_heads_dropout(q, k, v, *topo, scale, p)
+    else:
+        out, lse = ops.sparse_attention_heads(q, k, v, *topo, scale, with_lse=True)
+    assert out.shape == (R, m, d) and out.dtype == dtype and lse.shape == (R, m)
+    factor = torch.ones(len(probes), m, n, dtype=torch.float64)
+    if p > 0.0:
+        factor = dense_keep(csr, state, R, p, m, n, R, only=probes)
+    mask = torch.from_numpy(dense[0]).expand(len(probes), m, n)
+    want, want_lse = reference(q[probes].cpu(), k[probes].cpu(), v[probes].cpu(), mask, factor, scale)
+    assert rel_err_torch(out[probes].float().cpu(), want) < TOL[dtype]
+    fin = torch.isfinite(want_lse)
+    assert torch.equal(torch.isfinite(lse[probes].cpu()), fin)
+    assert rel_err_torch(lse[probes].cpu()[fin], want_lse[fin]) < TOL[dtype]
+    # every replica: the float32 chain (on widened inputs for float16)
+    w = ops.sparse_softmax_scaled(ops.sddmm(m, n, *topo, q.float(), k.float()), *topo, scale)
+    if p > 0.0:
+        w = ops.sparse_dropout(w, p, state)[0]
+    composed = ops.spmm(m, n, w, *topo, v.float())
+    assert rel_err_torch(out.float(), composed) < (1e-4 if dtype == torch.float32 else TOL[dtype])
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])

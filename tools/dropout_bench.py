@@ -11,9 +11,14 @@ the device-side kernel times.
   the SparseAttention training step (forward + backward) with / without dropout
   many-mask: fused float32 and float16 heads forms with / without dropout
 
---compare-lib PATH: also time the fused forwards WITHOUT dropout through the C ABI of this
-build and of the library at PATH (a build of the parent commit): the A/B of the no-dropout
-kernels.
+--compare-lib PATH: also the A/B of the fused forward kernels against the library at PATH (a
+build of the parent commit), through the C ABI of both in this process, alternating
+--alternations times: float32 and float16 heads forms x one mask or many x with and without
+dropout, both libraries from one fixed Philox state.  --check-equal: first assert that out and
+lse of the two libraries are equal bit for bit at config 3's shape and at small shapes that
+reach every kernel path (m = 136 x n = 200: a partial row block and a partial last stage, a
+row of 40 entries in one chunk, a reversed row, a row and a mask without entries), for
+float32, float16 and bfloat16 storage and both output types.
 """
 import argparse
 import ctypes
@@ -51,48 +56,168 @@ def emit(name, ms, **extra):
 def bind(path):
     from torch_sputnik_amd import capi
     lib = ctypes.CDLL(path)
-    for name in ("sputnik_hip_sparse_attention_workspace_bytes", "sputnik_hip_sparse_attention_plan",
-                 "sputnik_hip_sparse_attention_forward_planned",
-                 "sputnik_hip_sparse_attention_heads_forward_planned"):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = capi.SIGNATURES[name]
+    for name, (restype, argtypes) in capi.SIGNATURES.items():
+        if name.startswith("sputnik_hip_sparse_attention_"):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     return lib
 
 
-def compare_libs(other, q, k, v, qh, kh, vh, topo, nnz, s, d, reps):
-    """The no-dropout fused forwards through two builds of the library."""
+class FusedProblem:
+    """One fused-forward problem on the device, callable through any build's C ABI: `batch`
+    x `heads` replicas of m x n attention at d = 64 under one mask (csr = (ri, ro, ci),
+    counts = its entry count) or one mask per batch element (concatenated csr, counts = a
+    list).  Operands are drawn once: float32 [R, rows, 64] and, for the heads forms, their
+    [B, rows, H * 64] images in float16 and bfloat16."""
+    CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+    RNG = dict(seed=0x5EED0123456789, offset=40)   # sputnik_hip_philox_state by value
+
+    def __init__(self, dev, m, n, batch, heads, csr, counts, seed=0):
+        self.m, self.n, self.d, self.batch, self.heads = m, n, 64, batch, heads
+        self.many = not isinstance(counts, int)
+        self.csr, self.counts = csr, counts
+        g = torch.Generator(device=dev).manual_seed(seed)
+        self.f32 = [torch.randn(batch * heads, rows, 64, device=dev, generator=g) for rows in (m, n, n)]
+        self.half = {t: [x.view(batch, heads, -1, 64).transpose(1, 2).reshape(batch, -1, heads * 64).to(t)
+                         for x in self.f32] for t in (torch.float16, torch.bfloat16)}
+        self.plans = {}
+
+    def plan(self, lib):
+        if lib not in self.plans:
+            stream = torch.cuda.current_stream().cuda_stream
+            ptrs = [t.data_ptr() for t in self.csr]
+            if self.many:
+                counts = (ctypes.c_int * len(self.counts))(*self.counts)
+                size = lib.sputnik_hip_sparse_attention_many_mask_workspace_bytes(
+                    len(self.counts), self.m, self.n, self.d, max(self.counts))
+                ws = torch.empty(size, dtype=torch.uint8, device=self.csr[0].device)
+                st = lib.sputnik_hip_sparse_attention_many_mask_plan(
+                    len(self.counts), self.m, self.n, self.d, counts, *ptrs, ws.data_ptr(), size, stream)
+            else:
+                size = lib.sputnik_hip_sparse_attention_workspace_bytes(self.m, self.n, self.d, self.counts)
+                ws = torch.empty(size, dtype=torch.uint8, device=self.csr[0].device)
+                st = lib.sputnik_hip_sparse_attention_plan(self.m, self.n, self.d, self.counts, *ptrs,
+                                                           ws.data_ptr(), size, stream)
+            assert st == 0 and size > 0
+            self.plans[lib] = ws
+        return self.plans[lib]
+
+    def outputs(self, dtype, out_dtype):
+        """(out, lse) buffers of a form: dtype float32 = the [R, rows, 64] form."""
+        dev = self.csr[0].device
+        shape = (self.batch * self.heads, self.m, 64) if dtype == torch.float32 else \
+            (self.batch, self.m, self.heads * 64)
+        return (torch.full(shape, float("nan"), dtype=out_dtype, device=dev),
+                torch.full((self.batch * self.heads, self.m), float("nan"), device=dev))
+
+    def forward(self, lib, dtype, p, out, lse):
+        """The planned fused forward of `lib` for operands of `dtype`, with dropout p > 0."""
+        from torch_sputnik_amd import capi
+        ws, half = self.plan(lib), dtype != torch.float32
+        name = "sputnik_hip_sparse_attention_" + ("heads_" if half else "") + \
+            ("many_mask_" if self.many else "") + "forward_planned" + ("_dropout" if p > 0 else "")
+        args = [self.m, self.n, self.d]
+        if self.many:
+            args = [len(self.counts)] + args + [(ctypes.c_int * len(self.counts))(*self.counts)]
+        else:
+            args += [self.counts]
+        topo = [t.data_ptr() for t in self.csr]
+        if half:
+            E = self.heads * 64
+            q, k, v = self.half[dtype]
+            args += [self.batch, self.heads, *topo, self.CODES[dtype]]
+            for t in (q, k, v):
+                args += [t.data_ptr(), t.size(1) * E, 64, E]
+            args += [1 / math.sqrt(64), out.data_ptr(), self.CODES[out.dtype], self.m * E, 64, E]
+        else:
+            args += [self.batch * self.heads, *topo]
+            for t in self.f32:
+                args += [t.data_ptr(), t.size(1) * 64]
+            args += [1 / math.sqrt(64), out.data_ptr(), self.m * 64]
+        args += [lse.data_ptr(), self.m]
+        if p > 0:
+            args += [p, capi.PhiloxState(self.RNG["seed"], self.RNG["offset"], None, None, 0), None]
+        args += [ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream]
+        st = getattr(lib, name)(*args)
+        assert st == 0, (name, st)
+
+
+def edge_csr(dev, masks, m, n, seed, empty_mask=None):
+    """CSR of `masks` random m x n masks (density 0.15) that reach every kernel path: mask 0 has
+    a row with 40 entries inside the first 128-key chunk (the on-demand loop), a row without
+    entries and a reversed row, whose row block takes the order-independent path.  The kernel
+    deals entry p of row_indices to row block p % blocks (dealt_index), so the reversed row is
+    taken from another block than the 40-entry row's, which then has ascending rows only."""
+    rng = np.random.default_rng(seed)
+    dense = rng.random((masks, m, n)) < 0.15
+    long_row, blocks = 3, -(-m // 128)
+    dense[0, long_row, :] = False
+    dense[0, long_row, :40] = True
+    dense[0, 5, :] = False
+    if empty_mask is not None:
+        dense[empty_mask] = False
+    ri, ro, ci, counts = [], [], [], []
+    for i in range(masks):
+        rows, cols = np.nonzero(dense[i])
+        offsets = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=m))])
+        order = np.argsort(-np.diff(offsets), kind="stable")
+        if i == 0:
+            block_of = {int(row): at % blocks for at, row in enumerate(order)}
+            reversed_row = next(int(row) for row in order if block_of[int(row)] != block_of[long_row])
+            a, b = offsets[reversed_row], offsets[reversed_row + 1]
+            assert blocks > 1 and b - a > 1
+            cols[a:b] = cols[a:b][::-1].copy()
+            ascending = [bool(np.all(np.diff(cols[offsets[r]:offsets[r + 1]]) > 0)) for r in range(m)]
+            assert not ascending[reversed_row]
+            assert all(ascending[r] for r in range(m) if block_of[r] == block_of[long_row])
+            in_chunk = np.bincount(rows[cols < 128], minlength=m)
+            assert in_chunk[long_row] == 40 > 32
+        ri.append(order)
+        ro.append(offsets)
+        ci.append(cols)
+        counts.append(len(cols))
+    csr = tuple(torch.from_numpy(np.concatenate(x).astype(np.int32)).to(dev) for x in (ri, ro, ci))
+    return csr, counts
+
+
+def compare_libs(other, problems, p, reps, alternations, check_equal):
+    """The planned fused forwards (float32 and float16 heads x one mask or many x with and
+    without dropout) through this build and the library at `other`, both from one fixed
+    Philox state.  Timing: the two libraries alternate `alternations` times in this process;
+    per form and library the median of `reps` events per alternation, the median of those,
+    and their spread (max - min).  check_equal: out and lse of both libraries must be equal
+    bit for bit, for every problem, storage type and output type."""
     from torch_sputnik_amd import _native
-    ri, ro, ci = topo
-    R = q.size(0)
-    stream = torch.cuda.current_stream().cuda_stream
-    for label, path in (("this_build", _native.KERNEL_LIB), ("compare_lib", other)):
-        lib = bind(path)
-        ws_bytes = lib.sputnik_hip_sparse_attention_workspace_bytes(s, s, d, nnz)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-        assert lib.sputnik_hip_sparse_attention_plan(s, s, d, nnz, ri.data_ptr(), ro.data_ptr(), ci.data_ptr(),
-                                                     ws.data_ptr(), ws_bytes, stream) == 0
-        out = torch.empty_like(q)
-        lse = torch.empty(R, s, device=q.device)
-
-        def f32():
-            st = lib.sputnik_hip_sparse_attention_forward_planned(
-                s, s, d, nnz, R, ri.data_ptr(), ro.data_ptr(), ci.data_ptr(), q.data_ptr(), s * d,
-                k.data_ptr(), s * d, v.data_ptr(), s * d, 1 / math.sqrt(d), out.data_ptr(), s * d,
-                lse.data_ptr(), s, ws.data_ptr(), ws_bytes, stream)
-            assert st == 0
-        emit(f"nodrop_fused_f32[{label}]", event_ms(f32, reps))
-        B, S, E = qh.shape
-        H = E // d
-        outh = torch.empty(B, S, E, dtype=torch.float16, device=q.device)
-
-        def f16():
-            st = lib.sputnik_hip_sparse_attention_heads_forward_planned(
-                s, s, d, nnz, B, H, ri.data_ptr(), ro.data_ptr(), ci.data_ptr(), 1,
-                qh.data_ptr(), S * E, d, E, kh.data_ptr(), S * E, d, E, vh.data_ptr(), S * E, d, E,
-                1 / math.sqrt(d), outh.data_ptr(), 1, S * E, d, E, lse.data_ptr(), s, ws.data_ptr(),
-                ws_bytes, stream)
-            assert st == 0
-        emit(f"nodrop_fused_heads_f16[{label}]", event_ms(f16, reps))
+    libs = (("this_build", bind(_native.KERNEL_LIB)), ("compare_lib", bind(other)))
+    if check_equal:
+        checked = 0
+        for name, prob in problems.items():
+            for dtype in (torch.float32, torch.float16, torch.bfloat16):
+                for out_dtype in {dtype, torch.float32}:
+                    for drop in (0.0, p):
+                        got = []
+                        for _, lib in libs:
+                            out, lse = prob.outputs(dtype, out_dtype)
+                            prob.forward(lib, dtype, drop, out, lse)
+                            got.append((out, lse))
+                        torch.cuda.synchronize()
+                        assert not torch.isnan(got[0][0]).any(), (name, dtype, out_dtype, drop)
+                        assert torch.equal(got[0][0], got[1][0]), ("out", name, dtype, out_dtype, drop)
+                        assert torch.equal(got[0][1], got[1][1]), ("lse", name, dtype, out_dtype, drop)
+                        checked += 1
+        print(json.dumps({"name": "compare_libs_bit_identical", "cases": checked}), flush=True)
+    forms = [(f"{'many_mask_' if key == 'c3_many' else ''}fused_{'f32' if dtype == torch.float32 else 'heads_f16'}"
+              f"{'_dropout' if drop else ''}", problems[key], dtype, drop)
+             for key in ("c3", "c3_many") for dtype in (torch.float32, torch.float16) for drop in (0.0, p)]
+    medians = {(form[0], label): [] for form in forms for label, _ in libs}
+    for _ in range(alternations):
+        for label, lib in libs:
+            for name, prob, dtype, drop in forms:
+                out, lse = prob.outputs(dtype, dtype)
+                medians[name, label].append(event_ms(lambda: prob.forward(lib, dtype, drop, out, lse), reps))
+    for (name, label), ms in medians.items():
+        emit(f"{name}[{label}]", statistics.median(ms), per_alternation=[round(t, 5) for t in ms],
+             spread=round(max(ms) - min(ms), 5))
 
 
 def main():
@@ -100,6 +225,8 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--p", type=float, default=0.1)
     ap.add_argument("--compare-lib", default=None)
+    ap.add_argument("--alternations", type=int, default=5)
+    ap.add_argument("--check-equal", action="store_true")
     args = ap.parse_args()
     from torch_sputnik_amd import SparseAttention, functional, ops
     from torch_sputnik_amd.topology import dense_to_sparse, dense_to_sparse_3d, generate_mask
@@ -176,7 +303,13 @@ def main():
             emit(name + "_dropout", event_ms(
                 lambda: functional.sparse_attention_heads_many_mask(*args3, mnnz, *mt, scale, p), reps))
     if args.compare_lib:
-        compare_libs(args.compare_lib, q, k, v, qh, kh, vh, topo, nnz, s, d, reps)
+        small, small_counts = edge_csr(dev, 1, 136, 200, 3)
+        small_many, small_many_counts = edge_csr(dev, 3, 136, 200, 4, empty_mask=1)
+        problems = {"c3": FusedProblem(dev, s, s, batch, heads, topo, nnz),
+                    "c3_many": FusedProblem(dev, s, s, batch, heads, mt, [int(c) for c in mnnz]),
+                    "small": FusedProblem(dev, 136, 200, 1, 3, small, small_counts[0]),
+                    "small_many": FusedProblem(dev, 136, 200, 3, 2, small_many, small_many_counts)}
+        compare_libs(args.compare_lib, problems, p, reps, args.alternations, args.check_equal)
 
 
 if __name__ == "__main__":

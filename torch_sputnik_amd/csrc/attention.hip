@@ -11,29 +11,30 @@
 // Decomposition (the 64-column SpMM kernel's, spmm_tiled64.hip): a workgroup
 // owns 128 query rows and walks the key/value rows in chunks of 128; each
 // chunk's K rows and V rows are staged into LDS by direct global->LDS copies
-// (double buffered).  A 16-lane row group owns one query row: its q fragment
-// (pre-multiplied by the scale), running maximum, running sum and 4 output
-// columns per lane stay in registers for the whole walk (online softmax).
-// Per 16-entry window of a row's columns inside the chunk:
-//   1. 16 partial dot products per lane against the K rows (ds_read_b128 of a
-//      DPP-broadcast address), then ONE transposing DPP reduction that leaves
-//      score u in lane u;
+// (double buffered).  A 16-lane row group owns one query row: its q fragment,
+// running maximum, running sum and 4 output columns per lane stay in registers
+// for the whole walk (online softmax).  Per 16-entry window of a row's columns
+// inside the chunk:
+//   1. scores in the QUAD form of sddmm_tiled.hip -- the four quads of a row group work
+//      on four different entries, lane (quad q, t) holds a quarter of the q row (16
+//      elements, chunk order rotated by q: no LDS bank conflict) and two quad_perm adds
+//      close a dot product; lane (q, t) ends up with the score of entry 4t + q, which is
+//      where that entry's column lives (the kernel is 80 % busy issuing vector
+//      instructions, profiles/r3e_pmc_sq_attention_ops.json; the 16-lane form before it
+//      spent a third of them on broadcasts and a 45-instruction transposing reduction);
 //   2. window maximum and sum with two 16-lane DPP all-reduces, one exp per
 //      lane, rescale of the accumulators;
 //   3. the weights go back out to all lanes entry by entry, paired with the
 //      tile offset in one 64-bit DPP broadcast, against the V rows (same
-//      offsets: the V tile sits at a fixed distance from the K tile).
+//      offsets: the V tile sits at a fixed distance from the K tile; step 3 finds
+//      entry u in lane 4 (u % 4) + u / 4).
 // Needs ascending columns inside rows (checked by the shared pre-pass); row
 // blocks that fail take an order-independent path (K, V gathered from L2).
 //
-// Round 3: step 1 in the QUAD form of sddmm_tiled.hip -- the four quads of a row group
-// work on four different entries, lane (quad q, t) holds a quarter of the scaled q row
-// (16 elements, chunk order rotated by q: no LDS bank conflict) and two quad_perm adds
-// close a dot product; lane (q, t) ends up with the score of entry 4t + q, which is
-// where that entry's column lives.  The kernel was 80 % busy issuing vector
-// instructions (profiles/r3e_pmc_sq_attention_ops.json: 46.5 M per launch), a third
-// of them the broadcasts and the 45-instruction transposing reduction of the 16-lane
-// form.  Steps 2 and 3 are unchanged (step 3 finds entry u in lane 4 (u % 4) + u / 4).
+// ONE kernel body, sparse_attention_kernel<T, TO, MANY, Drop...>, serves float32 [R, S, 64]
+// operands (T = TO = float) and float16 / bfloat16 head views (TO = float or T).  What
+// differs between the storage types is in Storage<T>: bytes per staged row, how q is kept,
+// the inner product of step 1 and where the scale goes, and how rows are addressed.
 //
 // Attention dropout (philox.h): the instances with a DropArgs argument decide
 // per entry, in step 2, whether the weight handed to step 3 is kept; l and lse still take
@@ -52,30 +53,123 @@ constexpr int kRQ = 2;      // row quads per wave (4 query rows each)
 constexpr int kBK = 128;    // key/value rows per LDS stage
 constexpr int kBM = kWaves * kRQ * 4;
 constexpr int kThreads = kWaves * kWave;
-constexpr int kTileFloats = kBK * kD;  // one of K / V: 32 KiB
-constexpr int kWin = 2;                // 16-entry windows prefetched per row and chunk
-constexpr int kCopiesPerWave = (kBK / 4) / kWaves;  // 1 KiB copies of 4 rows each
-static_assert((kBK / 4) % kWaves == 0, "stage copies split evenly over the waves");
-
-__device__ __forceinline__ void stage_kv(float* __restrict__ tile, const float* __restrict__ k,
-                                         const float* __restrict__ v, int n, int jc, int wave,
-                                         int lane) {
-  const int g = lane >> 4, i = lane & 15;
-#pragma unroll
-  for (int j = 0; j < kCopiesPerWave; ++j) {
-    const int r0 = (wave + j * kWaves) * 4;
-    const int src_row = min(jc + r0 + g, n - 1);  // past the last key: re-read the last row
-    const unsigned off = (static_cast<unsigned>(src_row) * kD + i * 4u) * 4u;
-    lds_dma_row(k, off, tile + r0 * kD);
-    lds_dma_row(v, off, tile + kTileFloats + r0 * kD);
-  }
-}
+constexpr int kTile = kBK * kD;  // elements of one of K / V per stage: 32 KiB float32, 16 KiB half
+constexpr int kWin = 2;          // 16-entry windows prefetched per row and chunk
 
 using f4v = float __attribute__((ext_vector_type(4)));
 using v2f = float __attribute__((ext_vector_type(2)));
 
+// An operand as a strided HEAD VIEW: element (b, h, row, c) at base + b * batch + h * head +
+// row * row_stride + c, replica r = b * heads + h -- so half q, k, v and the context can stay
+// [B, S, E] tensors (head h = columns h*64 .. h*64+63) with no head split or merge pass.
+// A float32 [R, S, 64] operand with replica stride s is the view (0, s, 64) of one batch
+// element with R heads (Storage<float>::batch_of).
+struct HeadView {
+  const void* base;
+  int64_t batch, head, row;   // strides in elements
+};
+
+template <typename T>
+struct Vec4;
+template <>
+struct Vec4<_Float16> {
+  using type = _Float16 __attribute__((ext_vector_type(4)));
+  using pair = _Float16 __attribute__((ext_vector_type(2)));
+  // a.x b.x + a.y b.y + c: the products exact, the sum float32 (v_dot2_f32_f16)
+  static __device__ __forceinline__ float dot2(pair a, pair b, float c) {
+    return __builtin_amdgcn_fdot2(a, b, c, false);
+  }
+};
+template <>
+struct Vec4<__bf16> {
+  using type = __bf16 __attribute__((ext_vector_type(4)));
+  using pair = __bf16 __attribute__((ext_vector_type(2)));
+  static __device__ __forceinline__ float dot2(pair a, pair b, float c) {
+    return __builtin_amdgcn_fdot2_f32_bf16(a, b, c, false);
+  }
+};
+template <>
+struct Vec4<float> {
+  using type = f4v;
+};
+
+// four consecutive elements (8-byte aligned for half storage), widened
+template <typename T>
+__device__ __forceinline__ f4v load4(const T* p) {
+  return __builtin_convertvector(*reinterpret_cast<const typename Vec4<T>::type*>(p), f4v);
+}
+
+// What the kernel body leaves to the storage type T of q, k and v.  Half (this one): q is
+// kept as STORED and step 1 multiplies half pairs with v_dot2_f32_* (exact products, float32
+// sums -- no widening instruction per element, which left the issue-bound kernel a quarter
+// longer), the scale is applied to the float32 score; rows are addressed through the view's
+// row stride with 32-bit offsets inside a replica (heads_served guarantees they fit).
+template <typename T>
+struct Storage {
+  using V4 = typename Vec4<T>::type;
+  using P2 = typename Vec4<T>::pair;
+  struct Q {
+    P2 lo, hi;
+  };
+  static constexpr int kRowBytes = kD * static_cast<int>(sizeof(T));   // one tile row
+  // replica r = b * heads + h of the view's (batch element, head)
+  static __device__ __forceinline__ int batch_of(int replica, int heads) { return replica / heads; }
+  static __device__ __forceinline__ unsigned row(int r, unsigned stride) {   // element offset
+    return static_cast<unsigned>(r) * stride;
+  }
+  static __device__ __forceinline__ unsigned row_bytes(unsigned stride) { return stride * 2u; }
+  static __device__ __forceinline__ Q keep_q(V4 q, float) { return Q{P2{q.x, q.y}, P2{q.z, q.w}}; }
+  static __device__ __forceinline__ void mac(v2f& a, const Q& q, V4 b) {
+    a.x = Vec4<T>::dot2(q.lo, P2{b.x, b.y}, a.x);
+    a.y = Vec4<T>::dot2(q.hi, P2{b.z, b.w}, a.y);
+  }
+  static __device__ __forceinline__ float score(float s, float scale) { return s * scale; }
+};
+// float32: q is scaled once at load and step 1 is a chain of packed FMAs; rows are 64
+// contiguous elements, and q / out row offsets are 64-bit (supported() bounds only n).  The
+// R replicas of an [R, S, 64] operand are the heads of ONE batch element: no division.
+template <>
+struct Storage<float> {
+  using V4 = f4v;
+  using Q = f4v;
+  static constexpr int kRowBytes = kD * 4;
+  static __device__ __forceinline__ int batch_of(int, int) { return 0; }   // one batch element, R heads
+  static __device__ __forceinline__ int64_t row(int r, unsigned) { return static_cast<int64_t>(r) * kD; }
+  static __device__ __forceinline__ unsigned row_bytes(unsigned) { return kRowBytes; }
+  static __device__ __forceinline__ Q keep_q(V4 q, float scale) { return q * scale; }
+  static __device__ __forceinline__ void mac(v2f& a, const Q& q, V4 b) {
+    a = __builtin_elementwise_fma(v2f{q.x, q.y}, v2f{b.x, b.y}, a);
+    a = __builtin_elementwise_fma(v2f{q.z, q.w}, v2f{b.z, b.w}, a);
+  }
+  static __device__ __forceinline__ float score(float s, float) { return s; }
+};
+
+// Stages key/value rows jc .. jc + kBK - 1 into `tile` ([K rows | V rows]) with 1 KiB copies:
+// 4 float32 or 8 half rows each, 16 bytes per lane.
+template <typename T>
+__device__ __forceinline__ void stage_kv(T* __restrict__ tile, const T* __restrict__ k,
+                                         unsigned k_row_bytes, const T* __restrict__ v,
+                                         unsigned v_row_bytes, int n, int jc, int wave, int lane) {
+  constexpr int kRows = 1024 / Storage<T>::kRowBytes;   // rows per copy
+  constexpr int kLanes = kWave / kRows;                 // lanes per row
+  constexpr int kCopiesPerWave = (kBK / kRows) / kWaves;
+  static_assert((kBK / kRows) % kWaves == 0, "stage copies split evenly over the waves");
+  const int g = lane / kLanes, i = lane % kLanes;
+#pragma unroll
+  for (int j = 0; j < kCopiesPerWave; ++j) {
+    const int r0 = (wave + j * kWaves) * kRows;
+    const unsigned src_row = static_cast<unsigned>(min(jc + r0 + g, n - 1));  // past the last key: the last row
+    lds_dma_row(reinterpret_cast<const float*>(k), src_row * k_row_bytes + i * 16u,
+                reinterpret_cast<const float*>(tile + r0 * kD));
+    lds_dma_row(reinterpret_cast<const float*>(v), src_row * v_row_bytes + i * 16u,
+                reinterpret_cast<const float*>(tile + kTile + r0 * kD));
+  }
+}
+
+template <typename T>
 struct RowAcc {
-  f4v q[4];    // scale * q, elements 16t + 4((c + quad) % 4) .. +3 for c = 0..3 (lane = (quad, t))
+  // elements 16t + 4((c + quad) % 4) .. +3 of the q row for c = 0..3 (lane = (quad, t))
+  typename Storage<T>::Q q[4];
   float4 acc;  // unnormalised output columns 4i .. 4i+3
   float mx, l;
 };
@@ -86,7 +180,7 @@ __device__ __forceinline__ int quad_bcast_add(int v, int add) {
   return __builtin_amdgcn_update_dpp(0, v, S * 0x55, 0xF, 0xF, true) + add;
 }
 
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
+__device__ __forceinline__ float dot4(const f4v& a, const f4v& b) {
   float s = a.x * b.x;
   s = fmaf(a.y, b.y, s);
   s = fmaf(a.z, b.z, s);
@@ -95,7 +189,7 @@ __device__ __forceinline__ float dot4(const float4& a, const float4& b) {
 
 // Online-softmax update of one row with `e`-weighted V contributions still to
 // be added by the caller: returns the factor the old accumulators were scaled by.
-template <typename R>   // RowAcc, RowAccH<T>
+template <typename R>
 __device__ __forceinline__ void rescale(R& r, float m_new) {
   const float alpha = __expf(r.mx - m_new);  // mx = -inf gives 0
   r.l *= alpha;
@@ -147,32 +241,37 @@ __device__ __forceinline__ WorkItem many_mask_work(int heads, int m, int slots, 
   return WorkItem{mblock, replica};
 }
 
-// MANY: `nonzeros` is the number of replicas per mask (each mask's own count is read from
-// its row_offsets), q, k, v, out and lse start at replica 0 and the grid holds every replica.
 // Drop: attention dropout (philox.h), DROP = the pack holds one DropArgs.  The lane that
-// owns entry e16 of a window owns CSR position ps + w0 + e16 and decides whether it is kept;
-// the row sum still takes every entry (lse is that of the undropped scores), only the weight
-// handed to step 3 becomes 0 for a dropped entry, and finish() applies 1 / l and the keep
-// scale together.  DROP is a trailing parameter pack, not a bool and an argument, so that the
-// instances without it keep their argument list -- and their code: moving the body into an
-// inlined device function changes it (§3.9a of DESIGN.md).
+// owns entry e16 of a window owns CSR position ps + w0 + e16 and decides whether it is kept
+// (replica r = b * heads + h); the row sum still takes every entry (lse is that of the
+// undropped scores), only the weight handed to step 3 becomes 0 for a dropped entry, and
+// finish() applies 1 / l and the keep scale together.  DROP is a trailing parameter pack, not
+// a bool and an argument, so that the instances without it keep their argument list.
 template <typename... D>
 __device__ __forceinline__ DropArgs drop_of(D... d) {
   if constexpr (sizeof...(D) == 0) return DropArgs{};
   else return (d, ...);
 }
 
-template <bool MANY, typename... Drop>
+// T: storage type of q, k, v (Storage<T>); TO: of the context (float, or T).
+// MANY = false: one mask for the grid's replicas replica0 .. replica0 + gridDim.y - 1 (a
+// slice of the call's), `nonzeros` its entry count.  MANY = true: batch element b uses mask
+// b; `nonzeros` and `replica0` are not used (each mask's count is read from its row_offsets,
+// and the grid holds every replica).
+// The body stays in the __global__ function: moved into an inlined device function it
+// compiles to other code (§3.9a of DESIGN.md).
+template <typename T, typename TO, bool MANY, typename... Drop>
 __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
-    int m, int n, int nonzeros, int slots, int nchunks, const int* __restrict__ row_indices,
-    const int* __restrict__ row_offsets, const int* __restrict__ column_indices,
-    const int* __restrict__ table, const int* __restrict__ row_ok, const float* __restrict__ q,
-    int64_t q_stride, const float* __restrict__ k, int64_t k_stride, const float* __restrict__ v,
-    int64_t v_stride, float scale, float* __restrict__ out, int64_t out_stride,
-    float* __restrict__ lse, int64_t lse_stride, Drop... drop_arg) {
+    int m, int n, int nonzeros, int slots, int nchunks, int heads, int replica0,
+    const int* __restrict__ row_indices, const int* __restrict__ row_offsets,
+    const int* __restrict__ column_indices, const int* __restrict__ table,
+    const int* __restrict__ row_ok, HeadView qv, HeadView kv, HeadView vv, float scale,
+    HeadView ov, float* __restrict__ lse, int64_t lse_stride, Drop... drop_arg) {
   constexpr bool DROP = sizeof...(Drop) > 0;
   const DropArgs drop = drop_of(drop_arg...);
-  __shared__ float tile[2][2 * kTileFloats];  // [buffer][K rows | V rows]
+  using S = Storage<T>;
+  using V4 = typename S::V4;
+  __shared__ __attribute__((aligned(16))) T tile[2][2 * kTile];  // [buffer][K rows | V rows]
 
   const int lane = threadIdx.x % kWave;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -182,27 +281,29 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
   // (the row blocks of a replica read the same K and V: one XCD, see xcd_local_index)
   WorkItem item;
   if constexpr (MANY) {
-    const int heads = nonzeros;
     item = many_mask_work(heads, m, slots, nchunks, nonzeros, row_indices, row_offsets,
                           column_indices, table, row_ok);
   } else {
     const unsigned long long work = xcd_local_index();
-    item = WorkItem{static_cast<int>(work % gridDim.x), static_cast<int>(work / gridDim.x)};
+    item = WorkItem{static_cast<int>(work % gridDim.x), replica0 + static_cast<int>(work / gridDim.x)};
   }
   const int mblock = item.mblock;
   const int replica = item.replica;
   PhiloxKey key{};
   if constexpr (DROP) key = philox_key(drop, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0);
-  const int drop_r = replica + drop.replica0;
-  q += replica * q_stride;
-  k += replica * k_stride;
-  v += replica * v_stride;
-  out += replica * out_stride;
+  const int drop_r = replica;
+  const int64_t b = S::batch_of(replica, heads), h = replica - b * heads;
+  const T* __restrict__ q = static_cast<const T*>(qv.base) + (b * qv.batch + h * qv.head);
+  const T* __restrict__ k = static_cast<const T*>(kv.base) + (b * kv.batch + h * kv.head);
+  const T* __restrict__ v = static_cast<const T*>(vv.base) + (b * vv.batch + h * vv.head);
+  TO* __restrict__ out = static_cast<TO*>(const_cast<void*>(ov.base)) + (b * ov.batch + h * ov.head);
   if (lse != nullptr) lse += replica * lse_stride;
+  const unsigned q_rs = static_cast<unsigned>(qv.row), k_rs = static_cast<unsigned>(kv.row),
+                 v_rs = static_cast<unsigned>(vv.row), o_rs = static_cast<unsigned>(ov.row);
   const int slot0 = mblock * kBM + wave * (kRQ * 4);
   const int last = nonzeros - 1;
 
-  RowAcc st[kRQ];
+  RowAcc<T> st[kRQ];
   int my_row[kRQ];
 #pragma unroll
   for (int t = 0; t < kRQ; ++t) {
@@ -210,11 +311,10 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
     my_row[t] = entry < m ? row_indices[entry] : -1;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      f4v qf = {0.f, 0.f, 0.f, 0.f};
+      V4 qs = {};
       if (my_row[t] >= 0)
-        qf = *reinterpret_cast<const f4v*>(q + static_cast<int64_t>(my_row[t]) * kD + 16 * tq +
-                                           4 * ((c + qd) & 3));
-      st[t].q[c] = qf * scale;
+        qs = *reinterpret_cast<const V4*>(q + (S::row(my_row[t], q_rs) + 16 * tq + 4 * ((c + qd) & 3)));
+      st[t].q[c] = S::keep_q(qs, scale);
     }
     st[t].acc = make_float4(0.f, 0.f, 0.f, 0.f);
     st[t].mx = -INFINITY;
@@ -227,9 +327,9 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
       if (my_row[t] < 0) continue;
       float inv = st[t].l > 0.f ? 1.f / st[t].l : 0.f;  // rows without entries give zeros
       if constexpr (DROP) inv *= drop.scale;
-      *reinterpret_cast<float4*>(out + static_cast<int64_t>(my_row[t]) * kD + 4 * i) =
-          make_float4(st[t].acc.x * inv, st[t].acc.y * inv, st[t].acc.z * inv,
-                      st[t].acc.w * inv);
+      const f4v r = {st[t].acc.x * inv, st[t].acc.y * inv, st[t].acc.z * inv, st[t].acc.w * inv};
+      *reinterpret_cast<typename Vec4<TO>::type*>(out + (S::row(my_row[t], o_rs) + 4 * i)) =
+          __builtin_convertvector(r, typename Vec4<TO>::type);
       if (lse != nullptr && i == 0)
         lse[my_row[t]] = st[t].l > 0.f ? st[t].mx + __logf(st[t].l) : -INFINITY;
     }
@@ -248,16 +348,12 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
     for (int t = 0; t < kRQ; ++t) {
       const int p0 = my_row[t] >= 0 ? row_offsets[my_row[t]] : 0;
       const int p1 = my_row[t] >= 0 ? row_offsets[my_row[t] + 1] : 0;
-      float4 q16 = make_float4(0.f, 0.f, 0.f, 0.f);   // elements 4i .. 4i+3 of scale * q
-      if (my_row[t] >= 0) {
-        const float4 qf =
-            *reinterpret_cast<const float4*>(q + static_cast<int64_t>(my_row[t]) * kD + 4 * i);
-        q16 = make_float4(qf.x * scale, qf.y * scale, qf.z * scale, qf.w * scale);
-      }
+      f4v q16 = {0.f, 0.f, 0.f, 0.f};   // elements 4i .. 4i+3 of scale * q
+      if (my_row[t] >= 0) q16 = load4(q + (S::row(my_row[t], q_rs) + 4 * i)) * scale;
       for (int p = p0; p < p1; ++p) {
-        const int64_t base = static_cast<int64_t>(column_indices[p]) * kD + 4 * i;
-        const float4 kf = *reinterpret_cast<const float4*>(k + base);
-        const float4 vf = *reinterpret_cast<const float4*>(v + base);
+        const int col = column_indices[p];
+        const f4v kf = load4(k + (S::row(col, k_rs) + 4 * i));
+        const f4v vf = load4(v + (S::row(col, v_rs) + 4 * i));
         const float s = group_sum<16>(dot4(q16, kf));
         if (s > st[t].mx) rescale(st[t], s);
         const float e = __expf(s - st[t].mx);
@@ -284,14 +380,15 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
     for (int w = 0; w < kWin; ++w) wcol[t][w] = column_indices[min(ps[t] + 16 * w + e16, last)];
   }
 
-  stage_kv(tile[0], k, v, n, 0, wave, lane);
+  const unsigned k_bytes = S::row_bytes(k_rs), v_bytes = S::row_bytes(v_rs);
+  stage_kv(tile[0], k, k_bytes, v, v_bytes, n, 0, wave, lane);
   wait_vm<0>();
   __syncthreads();
 
   for (int c = 0; c < nchunks; ++c) {
     const int buf = c & 1;
     const bool more = c + 1 < nchunks;
-    if (more) stage_kv(tile[buf ^ 1], k, v, n, (c + 1) * kBK, wave, lane);
+    if (more) stage_kv(tile[buf ^ 1], k, k_bytes, v, v_bytes, n, (c + 1) * kBK, wave, lane);
 
     int pe_next[kRQ], ncol[kRQ][kWin];
 #pragma unroll
@@ -302,8 +399,8 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
         ncol[t][w] = more ? column_indices[min(pe[t] + 16 * w + e16, last)] : 0;
     }
 
-    const char* __restrict__ k_base = reinterpret_cast<const char*>(&tile[buf][0] + i * 4);
-    const char* __restrict__ v_base = k_base + kTileFloats * sizeof(float);
+    const char* __restrict__ v_base =
+        reinterpret_cast<const char*>(&tile[buf][0] + kTile) + i * 4 * sizeof(T);
     const int jc = c * kBK;
     const int k_lds = static_cast<int>(static_cast<unsigned>(
         reinterpret_cast<uintptr_t>(AS_LDS(&tile[buf][0]))));   // LDS byte address of the K tile
@@ -316,24 +413,21 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
         const int left = cnt - w0;
         if (left <= 0) return;
         const bool valid = e16 < left;
-        const int roff = valid ? ((ecol - jc) * (kD * 4)) : 0;
+        const int roff = valid ? ((ecol - jc) * S::kRowBytes) : 0;
 
         // 1. scores, quad form: step S = entries 4S .. 4S+3, one per quad
         float s = 0.f;
-        const int kq = k_lds + 64 * tq;   // this lane's quarter of tile row 0
+        const int kq = k_lds + (S::kRowBytes / 4) * tq;   // this lane's quarter of tile row 0
         auto scores4 = [&](auto Sc) {
           constexpr int kS = decltype(Sc)::value;
-          f4v b[4];
+          V4 bk[4];
 #pragma unroll
-          for (int c = 0; c < 4; ++c)
-            b[c] = *reinterpret_cast<const __attribute__((address_space(3))) f4v*>(
-                static_cast<unsigned>(quad_bcast_add<kS>(roff, kq + 16 * ((c + qd) & 3))));
+          for (int c4 = 0; c4 < 4; ++c4)
+            bk[c4] = *reinterpret_cast<const __attribute__((address_space(3))) V4*>(
+                static_cast<unsigned>(quad_bcast_add<kS>(roff, kq + (S::kRowBytes / 16) * ((c4 + qd) & 3))));
           v2f a2 = {0.f, 0.f};
 #pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            a2 = __builtin_elementwise_fma(v2f{st[t].q[c].x, st[t].q[c].y}, v2f{b[c].x, b[c].y}, a2);
-            a2 = __builtin_elementwise_fma(v2f{st[t].q[c].z, st[t].q[c].w}, v2f{b[c].z, b[c].w}, a2);
-          }
+          for (int c4 = 0; c4 < 4; ++c4) S::mac(a2, st[t].q[c4], bk[c4]);
           const float total = group_sum<4>(a2.x + a2.y);
           s = (tq == kS) ? total : s;
         };
@@ -341,7 +435,7 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
         if (left > 4) scores4(std::integral_constant<int, 1>{});
         if (left > 8) scores4(std::integral_constant<int, 2>{});
         if (left > 12) scores4(std::integral_constant<int, 3>{});
-        s = valid ? s : -INFINITY;
+        s = valid ? S::score(s, scale) : -INFINITY;
 
         // 2. online softmax over the window (at least one entry is valid)
         const float m_new = fmaxf(st[t].mx, group_max<16>(s));
@@ -359,10 +453,10 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_kernel(
           // (entries kG .. kG+3 of the window sit in lanes kG/4, 4 + kG/4, 8 + kG/4, 12 + kG/4)
           const entry_pair e0 = row_bcast_entry<0 + kG / 4>(ent), e1 = row_bcast_entry<4 + kG / 4>(ent);
           const entry_pair e2 = row_bcast_entry<8 + kG / 4>(ent), e3 = row_bcast_entry<12 + kG / 4>(ent);
-          const float4 b0 = *reinterpret_cast<const float4*>(v_base + entry_off(e0));
-          const float4 b1 = *reinterpret_cast<const float4*>(v_base + entry_off(e1));
-          const float4 b2 = *reinterpret_cast<const float4*>(v_base + entry_off(e2));
-          const float4 b3 = *reinterpret_cast<const float4*>(v_base + entry_off(e3));
+          const f4v b0 = load4(reinterpret_cast<const T*>(v_base + entry_off(e0)));
+          const f4v b1 = load4(reinterpret_cast<const T*>(v_base + entry_off(e1)));
+          const f4v b2 = load4(reinterpret_cast<const T*>(v_base + entry_off(e2)));
+          const f4v b3 = load4(reinterpret_cast<const T*>(v_base + entry_off(e3)));
           SPUTNIK_HIP_FMA4(a4, entry_val(e0), b0);
           SPUTNIK_HIP_FMA4(a4, entry_val(e1), b1);
           SPUTNIK_HIP_FMA4(a4, entry_val(e2), b2);
@@ -404,331 +498,9 @@ bool supported(int m, int n, int d, int nonzeros) {
          static_cast<int64_t>(n) * kD * 4 < (int64_t{1} << 32);
 }
 
-// ---------------------------------------------------------------------------
-// The same kernel on float16 / bfloat16 storage, every operand a strided HEAD VIEW:
-// element (b, h, row, c) at base + b * batch + h * head + row * row_stride + c, replica
-// r = b * heads + h -- so q, k, v and the context can stay [B, S, E] tensors (head h =
-// columns h*64 .. h*64+63) with no head split or merge pass.  K / V tiles are staged as
-// half rows of 128 bytes (8 rows per 1 KiB copy: 16 KiB per operand and stage instead
-// of 32); scores are dot2 products of stored half pairs (RowAccH), V is widened in
-// registers, scores, weights and the online softmax are float32, the context is stored
-// as float32 or in the storage type.  The per-replica
-// bases are 64-bit scalar arithmetic; offsets inside a replica are 32-bit, which the
-// host predicate (heads_served) guarantees together with the 16-byte alignment of
-// every base and stride.
-// ---------------------------------------------------------------------------
-constexpr int kHRowBytes = kD * 2;                           // one half row: 128 bytes
-constexpr int kHTile = kBK * kD;                             // elements of one of K / V: 16 KiB
-constexpr int kHCopiesPerWave = (kBK / 8) / kWaves;          // 1 KiB copies of 8 rows each
-static_assert((kBK / 8) % kWaves == 0, "half stage copies split evenly over the waves");
-
-struct HeadView {
-  const void* base;
-  int64_t batch, head, row;   // strides in elements
-};
-
-template <typename T>
-struct Vec4;
-template <>
-struct Vec4<_Float16> {
-  using type = _Float16 __attribute__((ext_vector_type(4)));
-  using pair = _Float16 __attribute__((ext_vector_type(2)));
-  // a.x b.x + a.y b.y + c: the products exact, the sum float32 (v_dot2_f32_f16)
-  static __device__ __forceinline__ float dot2(pair a, pair b, float c) {
-    return __builtin_amdgcn_fdot2(a, b, c, false);
-  }
-};
-template <>
-struct Vec4<__bf16> {
-  using type = __bf16 __attribute__((ext_vector_type(4)));
-  using pair = __bf16 __attribute__((ext_vector_type(2)));
-  static __device__ __forceinline__ float dot2(pair a, pair b, float c) {
-    return __builtin_amdgcn_fdot2_f32_bf16(a, b, c, false);
-  }
-};
-template <>
-struct Vec4<float> {
-  using type = f4v;
-};
-
-// four consecutive elements (8-byte aligned for half storage), widened
-template <typename T>
-__device__ __forceinline__ f4v load4(const T* p) {
-  return __builtin_convertvector(*reinterpret_cast<const typename Vec4<T>::type*>(p), f4v);
-}
-
-__device__ __forceinline__ float dot4v(const f4v& a, const f4v& b) {
-  float s = a.x * b.x;
-  s = fmaf(a.y, b.y, s);
-  s = fmaf(a.z, b.z, s);
-  return fmaf(a.w, b.w, s);
-}
-
-template <typename T>
-__device__ __forceinline__ void stage_kv_half(T* __restrict__ tile, const T* __restrict__ k,
-                                              unsigned k_row_bytes, const T* __restrict__ v,
-                                              unsigned v_row_bytes, int n, int jc, int wave, int lane) {
-  const int g = lane >> 3, i = lane & 7;
-#pragma unroll
-  for (int j = 0; j < kHCopiesPerWave; ++j) {
-    const int r0 = (wave + j * kWaves) * 8;
-    const unsigned src_row = static_cast<unsigned>(min(jc + r0 + g, n - 1));  // past the last key: the last row
-    lds_dma_row(reinterpret_cast<const float*>(k), src_row * k_row_bytes + i * 16u,
-                reinterpret_cast<const float*>(tile + r0 * kD));
-    lds_dma_row(reinterpret_cast<const float*>(v), src_row * v_row_bytes + i * 16u,
-                reinterpret_cast<const float*>(tile + kHTile + r0 * kD));
-  }
-}
-
-// A row's state in the heads kernel: q as STORED (the score step multiplies half pairs with
-// v_dot2_f32_*: exact products, float32 sums -- no widening instruction per element, which
-// left the issue-bound kernel a quarter longer; the scale is applied to the float32 score).
-template <typename T>
-struct RowAccH {
-  typename Vec4<T>::pair q[4][2];   // elements 16t + 4((c + quad) % 4) .. +3 for c = 0..3
-  float4 acc;
-  float mx, l;
-};
-
-// MANY: batch element b uses mask b (`nonzeros` and `replica0` are not used: each mask's
-// count is read from its row_offsets, and the grid holds every replica).
-// Drop: attention dropout as in sparse_attention_kernel, with r = b * heads + h.
-template <typename T, typename TO, bool MANY, typename... Drop>
-__global__ __launch_bounds__(kThreads) void sparse_attention_heads_kernel(
-    int m, int n, int nonzeros, int slots, int nchunks, int heads, int replica0,
-    const int* __restrict__ row_indices, const int* __restrict__ row_offsets,
-    const int* __restrict__ column_indices, const int* __restrict__ table,
-    const int* __restrict__ row_ok, HeadView qv, HeadView kv, HeadView vv, float scale,
-    HeadView ov, float* __restrict__ lse, int64_t lse_stride, Drop... drop_arg) {
-  constexpr bool DROP = sizeof...(Drop) > 0;
-  const DropArgs drop = drop_of(drop_arg...);
-  __shared__ __attribute__((aligned(16))) T tile[2][2 * kHTile];  // [buffer][K rows | V rows]
-
-  const int lane = threadIdx.x % kWave;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int g = lane >> 4, i = lane & 15;
-  const int qd = i >> 2, tq = i & 3;
-  const int e16 = 4 * tq + qd;
-  WorkItem item;
-  if constexpr (MANY) {
-    item = many_mask_work(heads, m, slots, nchunks, nonzeros, row_indices, row_offsets,
-                          column_indices, table, row_ok);
-  } else {
-    const unsigned long long work = xcd_local_index();
-    item = WorkItem{static_cast<int>(work % gridDim.x), replica0 + static_cast<int>(work / gridDim.x)};
-  }
-  const int mblock = item.mblock;
-  const int replica = item.replica;
-  PhiloxKey key{};
-  if constexpr (DROP) key = philox_key(drop, blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0);
-  const int drop_r = replica;
-  const int64_t b = replica / heads, h = replica - b * heads;
-  const T* __restrict__ q = static_cast<const T*>(qv.base) + (b * qv.batch + h * qv.head);
-  const T* __restrict__ k = static_cast<const T*>(kv.base) + (b * kv.batch + h * kv.head);
-  const T* __restrict__ v = static_cast<const T*>(vv.base) + (b * vv.batch + h * vv.head);
-  TO* __restrict__ out = static_cast<TO*>(const_cast<void*>(ov.base)) + (b * ov.batch + h * ov.head);
-  if (lse != nullptr) lse += replica * lse_stride;
-  // (in-replica offsets: below 2^32 bytes, heads_served)
-  const unsigned q_rs = static_cast<unsigned>(qv.row), k_rs = static_cast<unsigned>(kv.row),
-                 v_rs = static_cast<unsigned>(vv.row), o_rs = static_cast<unsigned>(ov.row);
-  const int slot0 = mblock * kBM + wave * (kRQ * 4);
-  const int last = nonzeros - 1;
-
-  using V4 = Vec4<T>;
-  using P2 = typename V4::pair;
-  RowAccH<T> st[kRQ];
-  int my_row[kRQ];
-#pragma unroll
-  for (int t = 0; t < kRQ; ++t) {
-    const int entry = dealt_index(slot0 + 4 * t + g, slots, kBM);
-    my_row[t] = entry < m ? row_indices[entry] : -1;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      typename V4::type qh = {};
-      if (my_row[t] >= 0)
-        qh = *reinterpret_cast<const typename V4::type*>(
-            q + (static_cast<unsigned>(my_row[t]) * q_rs + 16 * tq + 4 * ((c + qd) & 3)));
-      st[t].q[c][0] = P2{qh.x, qh.y};
-      st[t].q[c][1] = P2{qh.z, qh.w};
-    }
-    st[t].acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    st[t].mx = -INFINITY;
-    st[t].l = 0.f;
-  }
-
-  auto finish = [&]() {
-#pragma unroll
-    for (int t = 0; t < kRQ; ++t) {
-      if (my_row[t] < 0) continue;
-      float inv = st[t].l > 0.f ? 1.f / st[t].l : 0.f;  // rows without entries give zeros
-      if constexpr (DROP) inv *= drop.scale;
-      const f4v r = {st[t].acc.x * inv, st[t].acc.y * inv, st[t].acc.z * inv, st[t].acc.w * inv};
-      *reinterpret_cast<typename Vec4<TO>::type*>(out + (static_cast<unsigned>(my_row[t]) * o_rs + 4 * i)) =
-          __builtin_convertvector(r, typename Vec4<TO>::type);
-      if (lse != nullptr && i == 0)
-        lse[my_row[t]] = st[t].l > 0.f ? st[t].mx + __logf(st[t].l) : -INFINITY;
-    }
-  };
-
-  if constexpr (MANY) {
-    if (nonzeros == 0) {   // a mask without entries (none of its column_indices is read)
-      finish();
-      return;
-    }
-  }
-
-  // Row blocks whose columns do not ascend inside rows: order-independent path,
-  // one entry at a time, K and V rows gathered from global memory.
-  if (!block_rows_ok(row_ok, mblock * kBM, kBM)) {
-    for (int t = 0; t < kRQ; ++t) {
-      const int p0 = my_row[t] >= 0 ? row_offsets[my_row[t]] : 0;
-      const int p1 = my_row[t] >= 0 ? row_offsets[my_row[t] + 1] : 0;
-      f4v q16 = {0.f, 0.f, 0.f, 0.f};   // elements 4i .. 4i+3 of scale * q
-      if (my_row[t] >= 0) q16 = load4(q + (static_cast<unsigned>(my_row[t]) * q_rs + 4 * i)) * scale;
-      for (int p = p0; p < p1; ++p) {
-        const unsigned col = static_cast<unsigned>(column_indices[p]);
-        const f4v kf = load4(k + (col * k_rs + 4 * i));
-        const f4v vf = load4(v + (col * v_rs + 4 * i));
-        const float s = group_sum<16>(dot4v(q16, kf));
-        if (s > st[t].mx) rescale(st[t], s);
-        const float e = __expf(s - st[t].mx);
-        st[t].l += e;
-        float ek = e;
-        if constexpr (DROP) ek = philox_keep(key, drop.threshold, drop_r, p) ? e : 0.f;
-        st[t].acc.x = fmaf(ek, vf.x, st[t].acc.x);
-        st[t].acc.y = fmaf(ek, vf.y, st[t].acc.y);
-        st[t].acc.z = fmaf(ek, vf.z, st[t].acc.z);
-        st[t].acc.w = fmaf(ek, vf.w, st[t].acc.w);
-      }
-    }
-    finish();
-    return;
-  }
-
-  const int* __restrict__ my_table = table + slot0 + g;
-  int ps[kRQ], pe[kRQ], wcol[kRQ][kWin];
-#pragma unroll
-  for (int t = 0; t < kRQ; ++t) {
-    ps[t] = my_table[4 * t];
-    pe[t] = my_table[slots + 4 * t];
-#pragma unroll
-    for (int w = 0; w < kWin; ++w) wcol[t][w] = column_indices[min(ps[t] + 16 * w + e16, last)];
-  }
-
-  const unsigned k_bytes = k_rs * 2u, v_bytes = v_rs * 2u;
-  stage_kv_half(tile[0], k, k_bytes, v, v_bytes, n, 0, wave, lane);
-  wait_vm<0>();
-  __syncthreads();
-
-  for (int c = 0; c < nchunks; ++c) {
-    const int buf = c & 1;
-    const bool more = c + 1 < nchunks;
-    if (more) stage_kv_half(tile[buf ^ 1], k, k_bytes, v, v_bytes, n, (c + 1) * kBK, wave, lane);
-
-    int pe_next[kRQ], ncol[kRQ][kWin];
-#pragma unroll
-    for (int t = 0; t < kRQ; ++t) {
-      pe_next[t] = more ? my_table[static_cast<int64_t>(c + 2) * slots + 4 * t] : pe[t];
-#pragma unroll
-      for (int w = 0; w < kWin; ++w)
-        ncol[t][w] = more ? column_indices[min(pe[t] + 16 * w + e16, last)] : 0;
-    }
-
-    const char* __restrict__ v_base =
-        reinterpret_cast<const char*>(&tile[buf][0] + kHTile) + i * 4 * sizeof(T);
-    const int jc = c * kBK;
-    const int k_lds = static_cast<int>(static_cast<unsigned>(
-        reinterpret_cast<uintptr_t>(AS_LDS(&tile[buf][0]))));   // LDS byte address of the K tile
-
-#pragma unroll
-    for (int t = 0; t < kRQ; ++t) {
-      const int cnt = pe[t] - ps[t];
-
-      auto window = [&](int ecol, int w0) {
-        const int left = cnt - w0;
-        if (left <= 0) return;
-        const bool valid = e16 < left;
-        const int roff = valid ? ((ecol - jc) * kHRowBytes) : 0;
-
-        // 1. scores, quad form (as above; a quarter row is 32 bytes here)
-        float s = 0.f;
-        const int kq = k_lds + 32 * tq;
-        auto scores4 = [&](auto Sc) {
-          constexpr int kS = decltype(Sc)::value;
-          typename V4::type bk[4];
-#pragma unroll
-          for (int c4 = 0; c4 < 4; ++c4)
-            bk[c4] = *reinterpret_cast<const __attribute__((address_space(3))) typename V4::type*>(
-                static_cast<unsigned>(quad_bcast_add<kS>(roff, kq + 8 * ((c4 + qd) & 3))));
-          float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-          for (int c4 = 0; c4 < 4; ++c4) {
-            a0 = V4::dot2(st[t].q[c4][0], P2{bk[c4].x, bk[c4].y}, a0);
-            a1 = V4::dot2(st[t].q[c4][1], P2{bk[c4].z, bk[c4].w}, a1);
-          }
-          const float total = group_sum<4>(a0 + a1);
-          s = (tq == kS) ? total : s;
-        };
-        scores4(std::integral_constant<int, 0>{});
-        if (left > 4) scores4(std::integral_constant<int, 1>{});
-        if (left > 8) scores4(std::integral_constant<int, 2>{});
-        if (left > 12) scores4(std::integral_constant<int, 3>{});
-        s = valid ? s * scale : -INFINITY;
-
-        // 2. online softmax over the window (at least one entry is valid)
-        const float m_new = fmaxf(st[t].mx, group_max<16>(s));
-        rescale(st[t], m_new);
-        const float e = valid ? __expf(s - m_new) : 0.f;
-        st[t].l += group_sum<16>(e);
-
-        // 3. weighted V rows; padded entries carry weight 0 and offset 0
-        float ek = e;
-        if constexpr (DROP) ek = philox_keep(key, drop.threshold, drop_r, ps[t] + w0 + e16) ? e : 0.f;
-        const entry_pair ent = make_entry(roff, ek);
-        float a4[4] = {st[t].acc.x, st[t].acc.y, st[t].acc.z, st[t].acc.w};
-        auto values4 = [&](auto G) {
-          constexpr int kG = decltype(G)::value;
-          const entry_pair e0 = row_bcast_entry<0 + kG / 4>(ent), e1 = row_bcast_entry<4 + kG / 4>(ent);
-          const entry_pair e2 = row_bcast_entry<8 + kG / 4>(ent), e3 = row_bcast_entry<12 + kG / 4>(ent);
-          const f4v b0 = load4(reinterpret_cast<const T*>(v_base + entry_off(e0)));
-          const f4v b1 = load4(reinterpret_cast<const T*>(v_base + entry_off(e1)));
-          const f4v b2 = load4(reinterpret_cast<const T*>(v_base + entry_off(e2)));
-          const f4v b3 = load4(reinterpret_cast<const T*>(v_base + entry_off(e3)));
-          SPUTNIK_HIP_FMA4(a4, entry_val(e0), b0);
-          SPUTNIK_HIP_FMA4(a4, entry_val(e1), b1);
-          SPUTNIK_HIP_FMA4(a4, entry_val(e2), b2);
-          SPUTNIK_HIP_FMA4(a4, entry_val(e3), b3);
-        };
-        values4(std::integral_constant<int, 0>{});
-        if (left > 4) values4(std::integral_constant<int, 4>{});
-        if (left > 8) values4(std::integral_constant<int, 8>{});
-        if (left > 12) values4(std::integral_constant<int, 12>{});
-        st[t].acc = make_float4(a4[0], a4[1], a4[2], a4[3]);
-      };
-#pragma unroll
-      for (int w = 0; w < kWin; ++w) window(wcol[t][w], 16 * w);
-      const int longest = max(max(__builtin_amdgcn_readlane(cnt, 0), __builtin_amdgcn_readlane(cnt, 16)),
-                              max(__builtin_amdgcn_readlane(cnt, 32), __builtin_amdgcn_readlane(cnt, 48)));
-      for (int w0 = 16 * kWin; w0 < longest; w0 += 16)
-        window(column_indices[min(ps[t] + w0 + e16, last)], w0);
-    }
-
-#pragma unroll
-    for (int t = 0; t < kRQ; ++t) {
-      ps[t] = pe[t];
-      pe[t] = pe_next[t];
-#pragma unroll
-      for (int w = 0; w < kWin; ++w) wcol[t][w] = ncol[t][w];
-    }
-    wait_vm<0>();     // the next K/V tiles have landed
-    __syncthreads();  // ... for every wave, and the current buffer is free
-  }
-  finish();
-}
-
 bool half_code(int t) { return t == SPUTNIK_HIP_F16 || t == SPUTNIK_HIP_BF16; }
 
-// Everything the heads kernel assumes about its operands, checked on the host: a served
+// Everything the kernel assumes about half head views, checked on the host: a served
 // mask (supported), 16-byte aligned bases and strides, non-negative strides, and every
 // replica's extent below 2^32 bytes (the kernel's in-replica offsets are 32-bit).
 bool view_ok(const HeadView& w, int rows, int elem_bytes) {
@@ -768,7 +540,7 @@ struct ForwardCall {
   int m, n, d, batch, heads;   // float32 operands: batch = replicas
   const int *row_indices, *row_offsets, *column_indices;
   int dtype, out_type;
-  HeadView q, k, v, o;   // float32 operands: the base and, in `batch`, the replica stride
+  HeadView q, k, v, o;   // float32 operands: (0, replica stride, 64), one batch element of R heads
   float scale;
   float* lse;
   int64_t lse_stride;
@@ -779,7 +551,7 @@ struct ForwardCall {
   const DropArgs* drop;
 };
 
-struct Plan {   // the workspace as the kernels read it
+struct Plan {   // the workspace as the kernel reads it
   int slots, nchunks;
   const int *row_ok, *table;
 };
@@ -836,27 +608,15 @@ int prepass(bool many, int masks, int m, int n, const int* row_indices, const in
   return launch_status();
 }
 
-// Replicas r0 .. r0 + count - 1 of a float32 call: the pointers advance to replica r0.  The
-// many-mask kernel takes the replicas per mask in the `nonzeros` slot.
-template <bool MANY, typename... Drop>
-void launch_float(const ForwardCall& c, const Plan& p, int r0, int count, Drop... drop) {
-  auto at = [r0](const HeadView& w) {
-    return const_cast<float*>(static_cast<const float*>(w.base)) + r0 * w.batch;
-  };
-  hipLaunchKernelGGL((sparse_attention_kernel<MANY, Drop...>), dim3(p.slots / kBM, count), dim3(kThreads), 0,
-                     c.stream, c.m, c.n, MANY ? c.batch / c.masks : *c.nonzeros, p.slots, p.nchunks,
-                     c.row_indices, c.row_offsets, c.column_indices, p.table, p.row_ok, at(c.q), c.q.batch,
-                     at(c.k), c.k.batch, at(c.v), c.v.batch, c.scale, at(c.o), c.o.batch,
-                     c.lse != nullptr ? c.lse + r0 * c.lse_stride : nullptr, c.lse_stride, drop...);
-}
-
-// ... of a half call: the views stay, the kernel numbers its replicas from r0 itself.  The
-// many-mask kernel reads neither `nonzeros` nor `replica0`.
+// Replicas r0 .. r0 + count - 1 of a call (every replica of a many-mask one): the views
+// stay, the kernel numbers its replicas from r0 itself.  `heads` is what the many-mask form
+// deals by: the replicas per mask.
 template <typename T, typename TO, bool MANY, typename... Drop>
-void launch_heads(const ForwardCall& c, const Plan& p, int r0, int count, Drop... drop) {
-  hipLaunchKernelGGL((sparse_attention_heads_kernel<T, TO, MANY, Drop...>), dim3(p.slots / kBM, count),
+void launch_kernel(const ForwardCall& c, const Plan& p, int r0, int count, Drop... drop) {
+  const int heads = c.half ? c.heads : MANY ? c.batch / c.masks : 1;
+  hipLaunchKernelGGL((sparse_attention_kernel<T, TO, MANY, Drop...>), dim3(p.slots / kBM, count),
                      dim3(kThreads), 0, c.stream, c.m, c.n, MANY ? 0 : *c.nonzeros, p.slots, p.nchunks,
-                     c.heads, r0, c.row_indices, c.row_offsets, c.column_indices, p.table, p.row_ok, c.q,
+                     heads, r0, c.row_indices, c.row_offsets, c.column_indices, p.table, p.row_ok, c.q,
                      c.k, c.v, c.scale, c.o, c.lse, c.lse_stride, drop...);
 }
 
@@ -864,20 +624,19 @@ void launch_heads(const ForwardCall& c, const Plan& p, int r0, int count, Drop..
 void launch(const ForwardCall& c, const Plan& p, int r0, int count) {
   auto pick = [&](auto many, auto... drop) {
     constexpr bool MANY = decltype(many)::value;
-    if (!c.half) launch_float<MANY>(c, p, r0, count, drop...);
+    if (!c.half) launch_kernel<float, float, MANY>(c, p, r0, count, drop...);
     else if (c.dtype == SPUTNIK_HIP_F16 && c.out_type == SPUTNIK_HIP_F32)
-      launch_heads<_Float16, float, MANY>(c, p, r0, count, drop...);
-    else if (c.dtype == SPUTNIK_HIP_F16) launch_heads<_Float16, _Float16, MANY>(c, p, r0, count, drop...);
-    else if (c.out_type == SPUTNIK_HIP_F32) launch_heads<__bf16, float, MANY>(c, p, r0, count, drop...);
-    else launch_heads<__bf16, __bf16, MANY>(c, p, r0, count, drop...);
+      launch_kernel<_Float16, float, MANY>(c, p, r0, count, drop...);
+    else if (c.dtype == SPUTNIK_HIP_F16) launch_kernel<_Float16, _Float16, MANY>(c, p, r0, count, drop...);
+    else if (c.out_type == SPUTNIK_HIP_F32) launch_kernel<__bf16, float, MANY>(c, p, r0, count, drop...);
+    else launch_kernel<__bf16, __bf16, MANY>(c, p, r0, count, drop...);
   };
   if (c.drop == nullptr) {
     if (c.many) pick(std::true_type{});
     else pick(std::false_type{});
     return;
   }
-  DropArgs dr = *c.drop;   // replica numbers continue over the launches; the first publishes
-  if (!c.half) dr.replica0 = r0;
+  DropArgs dr = *c.drop;   // only the first launch publishes the rng state
   if (r0 > 0) dr.rng_state_out = nullptr;
   if (c.many) pick(std::true_type{}, dr);
   else pick(std::false_type{}, dr);
@@ -891,7 +650,7 @@ int fill_empty(const ForwardCall& c) {
   }
   float* out = const_cast<float*>(static_cast<const float*>(c.o.base));
   for (int r = 0; r < c.batch; ++r) {
-    hipError_t e = hipMemsetAsync(out + r * c.o.batch, 0, sizeof(float) * c.m * c.d, c.stream);
+    hipError_t e = hipMemsetAsync(out + r * c.o.head, 0, sizeof(float) * c.m * c.d, c.stream);
     if (e != hipSuccess) return static_cast<int>(e);
     if (c.lse != nullptr) {
       e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.lse + r * c.lse_stride),
@@ -968,7 +727,7 @@ int forward(const ForwardCall& c) {
   else
     served = served && supported(c.m, c.n, c.d, densest) && aligned_to(c.q.base, 16) &&
              aligned_to(c.k.base, 16) && aligned_to(c.v.base, 16) && aligned_to(c.o.base, 16) &&
-             c.q.batch % 4 == 0 && c.k.batch % 4 == 0 && c.v.batch % 4 == 0 && c.o.batch % 4 == 0;
+             c.q.head % 4 == 0 && c.k.head % 4 == 0 && c.v.head % 4 == 0 && c.o.head % 4 == 0;
   if (!served) return SPUTNIK_HIP_UNSUPPORTED;
   const size_t need = c.many ? many_mask_workspace(c.masks, c.m, c.n, c.d, largest)
                              : plan_bytes(c.m, c.n, c.d, largest);
@@ -1010,8 +769,8 @@ ForwardCall float_call(bool many, int masks, const int* nonzeros, int m, int n, 
                        hipStream_t stream) {
   return ForwardCall{many, /*half=*/false, masks, nonzeros, m, n, d, replicas, /*heads=*/1,
                      row_indices, row_offsets, column_indices, SPUTNIK_HIP_F32, SPUTNIK_HIP_F32,
-                     HeadView{q, q_stride, 0, 0}, HeadView{k, k_stride, 0, 0}, HeadView{v, v_stride, 0, 0},
-                     HeadView{out, out_stride, 0, 0}, scale, lse, lse_stride, const_cast<void*>(workspace),
+                     HeadView{q, 0, q_stride, kD}, HeadView{k, 0, k_stride, kD}, HeadView{v, 0, v_stride, kD},
+                     HeadView{out, 0, out_stride, kD}, scale, lse, lse_stride, const_cast<void*>(workspace),
                      workspace_bytes, planned, stream, /*drop=*/nullptr};
 }
 
