@@ -72,6 +72,19 @@ SPUTNIK_HIP_API const char* sputnik_hip_build_id(void);
  * pointer is to a static string. */
 SPUTNIK_HIP_API const char* sputnik_hip_spmm_kernel_name(int m, int k, int n, int nonzeros,
                                                          int replicas);
+/* The same for sputnik_hip_spmm_typed, whose dispatch is its own (operands of values_type /
+ * dense_type, SPUTNIK_HIP_F32 / F16 / BF16; values_stride 0: shared values), when the workspace
+ * is as large as sputnik_hip_spmm_typed_workspace_bytes asks and the operands are aligned and
+ * contiguous: "left_spmm_half_tiles" (the matrix cores), "spmm_panel64_kernel" and
+ * "spmm_rowgather_kernel" (their half-reading forms), or the float32 kernel that runs on
+ * widened copies; "none" for a pair of types the call refuses. */
+SPUTNIK_HIP_API const char* sputnik_hip_spmm_typed_kernel_name(int m, int k, int n, int nonzeros,
+                                                               int replicas, int values_type,
+                                                               int64_t values_stride,
+                                                               int dense_type);
+/* Rows of the output tile sputnik_hip_left_spmm_half_tiles gives a workgroup for a call of
+ * this shape under the current options: 128 or 256 (0: nothing to launch).  Host only. */
+SPUTNIK_HIP_API int sputnik_hip_left_spmm_half_tiles_tile_rows(int m, int n, int replicas);
 /* The same for an SDDMM call (sddmm.hip, sddmm_tiled.hip, sddmm_flat.hip): operands of
  * `elem_bytes` (4: float32, 2: float16 / bfloat16), `planned` != 0 for a product on a
  * workspace that sputnik_hip_sddmm_plan filled ("sddmm_flat_kernel", "sddmm_quad_kernel",
@@ -79,6 +92,34 @@ SPUTNIK_HIP_API const char* sputnik_hip_spmm_kernel_name(int m, int k, int n, in
 SPUTNIK_HIP_API const char* sputnik_hip_sddmm_kernel_name(int m, int k, int n, int nonzeros,
                                                           int replicas, int elem_bytes,
                                                           int planned);
+/* The route a SUMMED SDDMM call of this shape takes (sputnik_hip_sddmm_sum_batched / _typed /
+ * _mixed and their planned forms) under the current options, when the workspace and the
+ * scratch buffer are as large as the size queries ask and the operands are 16-byte aligned:
+ * operands stored as `in_type` (SPUTNIK_HIP_F32 / F16 / BF16); `mixed` != 0: a (float32,
+ * half) pair whose half operand has `in_type`; `planned` != 0: on a workspace that
+ * sputnik_hip_sddmm_sum_plan filled.
+ *   kernel       SPUTNIK_HIP_SUM_ROWWAVE: the row-wave kernel writes one partial vector per
+ *                replica; _TILED: the rhs-stationary (float32) / quad (half) kernel writes one
+ *                per (replica, panel); _MFMA: the matrix-core kernel; _PLAIN: one replica of
+ *                one panel, nothing to sum -- the plain product (sputnik_hip_sddmm_kernel_name
+ *                for one replica, not planned, names its kernel when panel_width != 0; the
+ *                row-wave kernel otherwise)
+ *   panel_width  columns of k per panel (_TILED, _PLAIN on the LDS kernels; 0 otherwise)
+ *   panels       k / panel_width (1 otherwise)
+ *   slab_rows    rows of rhs per slab (_TILED, _PLAIN), rows of the output tile (_MFMA)
+ *   splits       workgroups that share an output tile (_MFMA; 1 otherwise)
+ * Host only, launches nothing; any output pointer may be NULL.  Returns
+ * SPUTNIK_HIP_INVALID_ARGUMENT for a call that launches nothing or an unknown type,
+ * SPUTNIK_HIP_UNSUPPORTED for a mixed pair the matrix-core route does not serve.  For tests,
+ * which assert the route they mean to reach. */
+#define SPUTNIK_HIP_SUM_ROWWAVE 0
+#define SPUTNIK_HIP_SUM_TILED 1
+#define SPUTNIK_HIP_SUM_MFMA 2
+#define SPUTNIK_HIP_SUM_PLAIN 3
+SPUTNIK_HIP_API int sputnik_hip_sddmm_sum_route(int m, int k, int n, int nonzeros, int replicas,
+                                                int in_type, int planned, int mixed, int* kernel,
+                                                int* panel_width, int* panels, int* slab_rows,
+                                                int* splits);
 /* The instance of the sparse softmax kernel (softmax.hip) that a call of this shape launches
  * for its first grid slice under the current options: values stored as `dtype`
  * (SPUTNIK_HIP_F32 / F16 / BF16), `backward` != 0 for the gradient.  The class is

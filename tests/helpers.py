@@ -23,6 +23,109 @@ def make_csr(m, n, sparsity, seed, round_to=4, empty_rows=(), order="descending"
     return values.astype(np.float32), vals, row_indices, row_offsets, column_indices
 
 
+# ---------------------------------------------------------------------------
+# structured masks for the single-mask SpMM / SDDMM routes: what a uniform mask cannot put in
+# front of a kernel -- a chunk of 256 entries next to empty ones, a wave of empty rows next to
+# a wave of full ones, a tile without an entry
+# ---------------------------------------------------------------------------
+STRUCTURED_KINDS = (
+    "causal", "band", "global_columns_one_chunk", "global_columns_per_chunk",
+    "heavy_rows_start", "heavy_rows_end", "heavy_rows_wave", "heavy_rows_block",
+    "last_chunk", "block_diagonal", "stride", "alternating", "corner", "uniform")
+
+
+def _heavy_first_row(kind, m, h):
+    """First of the h full rows: at the start, at the end, or with h // 2 rows in front of a
+    multiple of 8 (a wave's rows in the flat SpMM kernel) / of 128 (a workgroup's rows)."""
+    if kind == "heavy_rows_start":
+        return 0
+    if kind == "heavy_rows_end":
+        return m - h
+    if kind == "heavy_rows_wave":
+        edge = (h // 2 + 7) // 8 * 8 + 8
+        edge += 8 if edge % 128 == 0 else 0
+    else:
+        edge = (h // 2 + 127) // 128 * 128
+    first = edge - h // 2
+    assert first >= 0 and first + h <= m, f"{kind}: {h} rows around row {edge} do not fit {m} rows"
+    return first
+
+
+def structured_mask(kind, m, n, min_mean_row, rng, chunk=32):
+    """[m, n] bool mask of one of STRUCTURED_KINDS with at least min_mean_row * m entries (what
+    the LDS routes ask for: 16, or 4 for the 64-column SpMM and the tiled SDDMM).  `chunk`:
+    the K-chunk (SpMM) or slab (SDDMM) whose partial last piece `last_chunk` fills."""
+    rows, cols = np.arange(m)[:, None], np.arange(n)[None, :]
+    need = int(np.ceil(min_mean_row * m))
+    per_row = int(np.ceil(min_mean_row))
+    assert m >= 2 and n >= 2 * per_row, (m, n, min_mean_row)
+    if kind == "causal":            # row 0 holds column 0, the last row every column
+        mask = cols <= rows * (n - 1) // (m - 1)
+    elif kind == "band":
+        centre = rows * n // m
+        width = 0
+        while np.count_nonzero(np.abs(cols - centre) <= width) < need:
+            width += 1
+        mask = np.abs(cols - centre) <= width
+    elif kind == "global_columns_one_chunk":
+        mask = np.broadcast_to(cols < per_row, (m, n))
+    elif kind == "global_columns_per_chunk":   # one column per chunk, column n - 1 among them
+        chunks = -(-n // chunk)
+        held = {min((i * chunks // per_row) * chunk + (7 * i + i // chunks) % chunk, n - 2)
+                for i in range(per_row - 1)} | {n - 1}
+        assert len(held) == per_row, (sorted(held), per_row)
+        mask = np.broadcast_to(np.isin(np.arange(n), sorted(held))[None, :], (m, n))
+    elif kind.startswith("heavy_rows_"):
+        h = max(2, -(-need // n))
+        first = _heavy_first_row(kind, m, h)
+        mask = np.broadcast_to((rows >= first) & (rows < first + h), (m, n))
+    elif kind == "last_chunk":      # exactly the partial last chunk where that is long enough
+        c = n % chunk if n % chunk >= per_row else per_row
+        mask = np.broadcast_to(cols >= n - c, (m, n))
+    elif kind == "block_diagonal":  # 64 x 64 blocks ending in the bottom-right corner: the last
+        row_blocks, col_blocks = -(-m // 64), -(-n // 64)   # block is ragged in rows and columns
+        mask = cols // 64 == np.maximum(col_blocks - row_blocks + rows // 64, 0)
+    elif kind == "stride":
+        s = max(1, n // per_row)
+        mask = cols % s == rows % s
+    elif kind == "alternating":     # even rows full, odd rows one entry, each in another column
+        mask = (rows % 2 == 0) | (cols == (rows * 37 + 11) % n)
+    elif kind == "corner":
+        width = min(n, 100)
+        height = -(-need // width)
+        assert height <= m, (m, n, min_mean_row)
+        mask = (rows < height) & (cols < width)
+    else:
+        assert kind == "uniform", kind
+        density = min(1.0, 1.25 * min_mean_row / n + 4.0 / (m * n))
+        mask = O.random_mask(m, n, 1.0 - density, round_to=1, rng=rng) != 0
+    mask = np.ascontiguousarray(mask, dtype=bool)
+    assert np.count_nonzero(mask) >= need, (kind, m, n, np.count_nonzero(mask), need)
+    return mask
+
+
+def structured_csr(kind, m, n, min_mean_row, rng, order="descending", shuffle_every=0, chunk=32):
+    """(row_indices, row_offsets, column_indices), int32, of structured_mask(kind, ...).
+    order: "descending" row lengths (what diffsort gives real callers, ties by row number) or
+    "identity".  shuffle_every = 3: the columns of every third row in random order -- the
+    order-independent path of the LDS kernels, as shuffle_columns is for the many-mask layout."""
+    mask = structured_mask(kind, m, n, min_mean_row, rng, chunk=chunk)
+    lengths = mask.sum(axis=1)
+    row_offsets = np.concatenate(([0], np.cumsum(lengths))).astype(np.int32)
+    column_indices = np.nonzero(mask)[1].astype(np.int32)
+    if order == "descending":
+        row_indices = np.argsort(-lengths, kind="stable").astype(np.int32)
+    else:
+        assert order == "identity", order
+        row_indices = np.arange(m, dtype=np.int32)
+    if shuffle_every:
+        for r in range(0, m, shuffle_every):
+            a, b = int(row_offsets[r]), int(row_offsets[r + 1])
+            if b - a > 1:
+                column_indices[a:b] = column_indices[a:b][rng.permutation(b - a)]
+    return row_indices, row_offsets, column_indices
+
+
 def _row_view(a, row_offsets):
     """(values as [rows, width] or flat, row id per element or None)."""
     a = np.asarray(a, np.float64)

@@ -67,10 +67,11 @@ def test_spmm_bias_capi_vs_oracle(capi, dev, spmm_kernel, m, k, n, sparsity, rep
     capi.spmm_bias_batched(m, k, n, replicas, T(ri, dev), T(vals, dev), 0, T(ro, dev), T(ci, dev),
                            T(b, dev), T(bias, dev), relu, out, ws)
     got = out.cpu().numpy()
-    assert not np.isnan(got).any()
-    assert rel_err(got, want) < TOL
+    route = f"knob {spmm_kernel} -> {capi.spmm_kernel_name(m, k, n, len(ci), replicas)}"
+    assert not np.isnan(got).any(), route
+    assert rel_err(got, want) < TOL, route
     if relu:
-        assert (got >= 0).all() and (got == 0).any()
+        assert (got >= 0).all() and (got == 0).any(), route
 
 
 def test_spmm_null_bias_is_plain_spmm(capi, dev):
@@ -84,9 +85,10 @@ def test_spmm_null_bias_is_plain_spmm(capi, dev):
     assert torch.equal(a, c)
 
 
-@pytest.mark.parametrize("k", [512, 1600])   # 1600: four panels of the panel kernel
-def test_spmm_bias_unsorted_columns_take_the_fallback_epilogue(capi, dev, spmm_kernel, k):
-    m, n = 256, 256
+# 1600: four panels of the panel kernel; n = 512: the one width the 512-column and flat kernels take
+@pytest.mark.parametrize("k,n", [(512, 256), (1600, 256), (512, 512)], ids=["512", "1600", "512-n512"])
+def test_spmm_bias_unsorted_columns_take_the_fallback_epilogue(capi, dev, spmm_kernel, k, n):
+    m = 256
     _, vals, ri, ro, ci = make_csr(m, k, 0.7, seed=21)
     rng = np.random.default_rng(3)
     ci = ci.copy()
@@ -101,7 +103,9 @@ def test_spmm_bias_unsorted_columns_take_the_fallback_epilogue(capi, dev, spmm_k
     ws = torch.empty(capi.spmm_workspace_bytes(m, k, n, len(ci)), dtype=torch.uint8, device=dev)
     out = capi.spmm_bias_batched(m, k, n, 1, T(ri, dev), T(vals, dev), 0, T(ro, dev), T(ci, dev),
                                  T(b, dev), T(bias, dev), 1, torch.empty(m, n, device=dev), ws)
-    assert rel_err(out.cpu().numpy(), want) < TOL
+    # (the route the shape is planned for: row blocks with shuffled rows leave it in the launch)
+    route = f"knob {spmm_kernel} -> {capi.spmm_kernel_name(m, k, n, len(ci), 1)}"
+    assert rel_err(out.cpu().numpy(), want) < TOL, route
 
 
 @pytest.mark.parametrize("name", ["spmm_bias_72x64x72", "spmm_bias_relu_40x48x36"])

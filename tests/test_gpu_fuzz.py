@@ -74,8 +74,9 @@ def test_fuzz_spmm(capi, dev, spmm_kernel):
                                T(ci, dev) if len(ci) else dummy, T(b, dev),
                                None if bias is None else T(bias, dev), relu, out, ws)
         got = out.cpu().numpy()
-        assert not np.isnan(got).any(), (it, m, k, n)
-        assert rel_err(got, want) < TOL, (it, m, k, n, sparsity, order, replicas)
+        route = f"knob {spmm_kernel} -> {capi.spmm_kernel_name(m, k, n, len(ci), replicas)}"
+        assert not np.isnan(got).any(), (it, m, k, n, route)
+        assert rel_err(got, want) < TOL, (it, m, k, n, sparsity, order, replicas, route)
 
 
 def test_fuzz_sddmm_planned_pair_flat(capi, dev, monkeypatch):
@@ -144,8 +145,9 @@ def test_fuzz_sddmm_softmax_transpose(capi, dev, sddmm_kernel):
         scores = torch.full((replicas, nnz), float("nan"), device=dev)
         capi.sddmm_batched(m, k, n, replicas, d_ri, d_ro, d_ci, T(lhs, dev), T(rhs, dev), scores, ws)
         got = scores.cpu().numpy()
-        assert not np.isnan(got).any(), (it, m, k, n)
-        assert rel_err(got, O.sddmm(m, n, ri, ro, ci, lhs, rhs), ro) < TOL, (it, m, k, n, sparsity)
+        route = f"knob {sddmm_kernel} -> {capi.sddmm_kernel_name(m, k, n, len(ci), replicas)}"
+        assert not np.isnan(got).any(), (it, m, k, n, route)
+        assert rel_err(got, O.sddmm(m, n, ri, ro, ci, lhs, rhs), ro) < TOL, (it, m, k, n, sparsity, route)
 
         scale = float(rng.choice([1.0, 0.125, 2.0]))
         probs = capi.sparse_softmax_scaled_batched(m, replicas, scores, d_ri, d_ro, d_ci, scale,

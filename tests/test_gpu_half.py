@@ -188,8 +188,9 @@ def test_sddmm_half_capi_vs_oracle(capi, dev, sddmm_kernel, dtype, m, k, n, spar
     topo = (T(ri, dev), T(ro, dev), T(ci, dev))
     capi.sddmm_typed(m, k, n, replicas, *topo, lhs, rhs, out, ws)
     got = out.cpu().numpy()
-    assert not np.isnan(got).any()
-    assert rel_err(got, want, ro) < TOL
+    route = f"knob {sddmm_kernel} -> {capi.sddmm_kernel_name(m, k, n, len(ci), replicas, lhs.element_size())}"
+    assert not np.isnan(got).any(), route
+    assert rel_err(got, want, ro) < TOL, route
     # planned form: same plan as the float operator's; bit-identical result when the same
     # kernel runs, the pair-flat kernel (round 4: planned products with 128 / 256-byte rows)
     # against the oracle -- which quad computes an entry decides the order of its partial sums
@@ -220,8 +221,9 @@ def test_sddmm_half_output(capi, dev, sddmm_kernel, dtype, m, k, n, sparsity, re
     ws = torch.empty(capi.sddmm_workspace_bytes(m, k, n, len(ci)) + 16, dtype=torch.uint8, device=dev)
     capi.sddmm_typed(m, k, n, replicas, T(ri, dev), T(ro, dev), T(ci, dev), lhs, rhs, out, ws)
     got = out.float().cpu().numpy()
-    assert not np.isnan(got).any()
-    assert half_err(got, want, dtype, ro) < TOL
+    route = f"knob {sddmm_kernel} -> {capi.sddmm_kernel_name(m, k, n, len(ci), replicas, lhs.element_size())}"
+    assert not np.isnan(got).any(), route
+    assert half_err(got, want, dtype, ro) < TOL, route
 
 
 def test_sddmm_half_output_needs_one_pass(capi, dev):
@@ -793,7 +795,8 @@ def test_fuzz_typed_operators(capi, dev, sddmm_kernel):
         if nnz:
             got = out.cpu().numpy()
             assert not np.isnan(got).any(), what
-            assert rel_err(got, want, ro) < TOL, what + (k,)
+            assert rel_err(got, want, ro) < TOL, what + (
+                k, sddmm_kernel, capi.sddmm_kernel_name(m, k, n, nnz, replicas, lhs.element_size()))
 
         # softmax pair on half scores
         if nnz:

@@ -78,10 +78,11 @@ def test_spmm_capi_vs_oracle(capi, dev, spmm_kernel, m, k, n, sparsity, order, e
     capi.spmm_batched(m, k, n, 1, T(ri, dev), T(vals, dev), 0, T(ro, dev), T(ci, dev), T(b, dev),
                       out, ws)
     got = out.cpu().numpy()
-    assert not np.isnan(got).any(), "some output elements were never written"
-    assert rel_err(got, want) < TOL
+    route = f"knob {spmm_kernel} -> {capi.spmm_kernel_name(m, k, n, len(ci), 1)}"
+    assert not np.isnan(got).any(), f"some output elements were never written ({route})"
+    assert rel_err(got, want) < TOL, route
     for r in empty:
-        assert np.all(got[r] == 0)
+        assert np.all(got[r] == 0), route
 
 
 STRESS = [
@@ -116,8 +117,9 @@ def test_spmm_tiled_stress(capi, dev, spmm_kernel, m, k, n, sparsity, order):
     capi.spmm_batched(m, k, n, 1, T(ri, dev), T(vals, dev), 0, T(ro, dev), T(ci, dev), T(b, dev),
                       out, ws)
     got = out.cpu().numpy()
-    assert not np.isnan(got).any()
-    assert rel_err(got, want) < TOL
+    route = f"knob {spmm_kernel} -> {capi.spmm_kernel_name(m, k, n, len(ci), 1)}"
+    assert not np.isnan(got).any(), route
+    assert rel_err(got, want) < TOL, route
 
 
 TAIL_SHAPES = [
@@ -153,9 +155,10 @@ def test_spmm_partial_column_tiles(capi, dev, spmm_kernel, m, k, n, sparsity, re
     capi.spmm_batched(m, k, n, replicas, T(ri, dev), T(v, dev), 0 if replicas == 1 else len(vals),
                       T(ro, dev), T(ci, dev), T(b, dev), out, ws)
     got = out.cpu().numpy()
-    assert not np.isnan(got).any(), "some output elements were never written"
-    assert torch.isnan(flat[replicas * m * n:]).all(), "wrote past the end of the output"
-    assert rel_err(got.reshape(want.shape), want) < TOL
+    route = f"knob {spmm_kernel} -> {capi.spmm_kernel_name(m, k, n, len(ci), replicas)}"
+    assert not np.isnan(got).any(), f"some output elements were never written ({route})"
+    assert torch.isnan(flat[replicas * m * n:]).all(), f"wrote past the end of the output ({route})"
+    assert rel_err(got.reshape(want.shape), want) < TOL, route
 
 
 def test_spmm_full_size_linearity(capi, dev):
@@ -305,8 +308,9 @@ def test_spmm_batched_capi(capi, dev, spmm_kernel, replicas, shared, m, k, n):
     capi.spmm_batched(m, k, n, replicas, T(ri, dev), T(v, dev), 0 if shared else len(vals),
                       T(ro, dev), T(ci, dev), T(b, dev), out, ws)
     got = out.cpu().numpy()
-    assert not np.isnan(got).any()
-    assert rel_err(got, want) < TOL
+    route = f"knob {spmm_kernel} -> {capi.spmm_kernel_name(m, k, n, len(ci), replicas)}"
+    assert not np.isnan(got).any(), route
+    assert rel_err(got, want) < TOL, route
 
 
 @pytest.mark.parametrize("m,k,n", [(96, 200, 128), (256, 512, 256), (300, 1000, 512), (200, 300, 64)])
@@ -326,7 +330,9 @@ def test_spmm_unsorted_columns(capi, dev, spmm_kernel, m, k, n):
     ws = torch.empty(capi.spmm_workspace_bytes(m, k, n, len(ci)) + 16, dtype=torch.uint8, device=dev)
     capi.spmm_batched(m, k, n, 1, T(ri, dev), T(vals, dev), 0, T(ro, dev), T(ci, dev), T(b, dev),
                       out, ws)
-    assert rel_err(out.cpu().numpy(), want) < TOL
+    # (the route the shape is planned for: rows whose columns do not ascend leave it in the launch)
+    route = f"knob {spmm_kernel} -> {capi.spmm_kernel_name(m, k, n, len(ci), 1)}"
+    assert rel_err(out.cpu().numpy(), want) < TOL, route
 
 
 @pytest.fixture
@@ -669,8 +675,9 @@ def test_sddmm_capi_vs_oracle(capi, dev, sddmm_kernel, m, k, n, sparsity, replic
     capi.sddmm_batched(m, k, n, replicas, T(ri, dev), T(ro, dev), T(ci, dev), T(lhs, dev),
                        T(rhs, dev), out, ws)
     got = out.cpu().numpy()
-    assert not np.isnan(got).any()
-    assert rel_err(got, want, ro) < TOL    # rows = the mask's CSR rows
+    route = f"knob {sddmm_kernel} -> {capi.sddmm_kernel_name(m, k, n, len(ci), replicas)}"
+    assert not np.isnan(got).any(), route
+    assert rel_err(got, want, ro) < TOL, route    # rows = the mask's CSR rows
 
 
 # The pair-flat kernel (csrc/sddmm_flat.hip, round 4) serves PLANNED products whose rows are
@@ -775,9 +782,11 @@ def test_sddmm_sum_capi_vs_oracle(capi, dev, sddmm_kernel, sddmm_sum_slab, m, k,
     capi.sddmm_sum_batched(m, k, n, replicas, *topo, T(lhs, dev), T(rhs, dev), out, ws, scratch,
                            planned=planned)
     got = out.cpu().numpy()
-    assert not np.isnan(got).any()
+    route = f"knob {sddmm_kernel}, {sddmm_sum_slab} -> " \
+            f"{capi.sddmm_sum_route(m, k, n, len(ci), replicas, planned=planned) if len(ci) else 'nothing'}"
+    assert not np.isnan(got).any(), route
     # one row of `replicas * k` products per entry: the tolerance scales as for one long row
-    assert rel_err(got[None, :], want[None, :].astype(np.float32), ro) < TOL
+    assert rel_err(got[None, :], want[None, :].astype(np.float32), ro) < TOL, route
 
 
 def test_sddmm_sum_op_equals_the_summed_op(ts, dev):

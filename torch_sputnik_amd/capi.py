@@ -35,7 +35,10 @@ SIGNATURES = {
     "sputnik_hip_version": (ctypes.c_char_p, []),
     "sputnik_hip_build_id": (ctypes.c_char_p, []),
     "sputnik_hip_spmm_kernel_name": (ctypes.c_char_p, [_c_int] * 5),
+    "sputnik_hip_spmm_typed_kernel_name": (ctypes.c_char_p, [_c_int] * 6 + [_c_i64, _c_int]),
+    "sputnik_hip_left_spmm_half_tiles_tile_rows": (_c_int, [_c_int] * 3),
     "sputnik_hip_sddmm_kernel_name": (ctypes.c_char_p, [_c_int] * 7),
+    "sputnik_hip_sddmm_sum_route": (_c_int, [_c_int] * 8 + [_c_ptr] * 5),
     "sputnik_hip_sparse_softmax_route": (_c_int, [_c_int] * 5 + [_c_ptr] * 6),
     "sputnik_hip_reload_options": (None, []),
     "sputnik_hip_spmm": (_c_int, [_c_int] * 4 + [_c_ptr] * 7),
@@ -262,10 +265,40 @@ def spmm_kernel_name(m, k, n, nonzeros, replicas=1):
     return lib().sputnik_hip_spmm_kernel_name(m, k, n, nonzeros, replicas).decode()
 
 
+def spmm_typed_kernel_name(m, k, n, nonzeros, replicas, values_dtype, values_stride, dense_dtype):
+    """Kernel spmm_typed takes for a call of this shape and these storage types (its own
+    dispatch), with a workspace as large as spmm_typed_workspace_bytes asks.  Host only."""
+    return lib().sputnik_hip_spmm_typed_kernel_name(m, k, n, nonzeros, replicas, TYPE_CODES[values_dtype],
+                                                    values_stride, TYPE_CODES[dense_dtype]).decode()
+
+
+def left_spmm_half_tiles_tile_rows(m, n, replicas):
+    """Rows (128 / 256) of the matrix-core tile left_spmm_half_tiles launches.  Host only."""
+    return lib().sputnik_hip_left_spmm_half_tiles_tile_rows(m, n, replicas)
+
+
 def sddmm_kernel_name(m, k, n, nonzeros, replicas=1, elem_bytes=4, planned=False):
     """Device kernel the dispatcher picks for an SDDMM call of this shape."""
     return lib().sputnik_hip_sddmm_kernel_name(m, k, n, nonzeros, replicas, elem_bytes,
                                                int(bool(planned))).decode()
+
+
+SUM_KERNELS = ("rowwave", "tiled", "mfma", "plain")   # SPUTNIK_HIP_SUM_ROWWAVE / _TILED / _MFMA / _PLAIN
+
+
+def sddmm_sum_route(m, k, n, nonzeros, replicas, dtype=torch.float32, planned=False, mixed=False):
+    """Route of a summed SDDMM call of this shape under the current options, with a workspace and
+    scratch as large as the size queries ask: a dict of kernel (one of SUM_KERNELS), panel_width,
+    panels, slab_rows and splits (include/sputnik_hip.h).  `mixed`: a (float32, half) pair whose
+    half operand is `dtype`.  Host only."""
+    names = ("kernel", "panel_width", "panels", "slab_rows", "splits")
+    outs = [_c_int(-1) for _ in names]
+    _check(lib().sputnik_hip_sddmm_sum_route(
+        m, k, n, nonzeros, replicas, TYPE_CODES[dtype], int(bool(planned)), int(bool(mixed)),
+        *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]), "sputnik_hip_sddmm_sum_route")
+    route = {name: o.value for name, o in zip(names, outs)}
+    route["kernel"] = SUM_KERNELS[route["kernel"]]
+    return route
 
 
 def sparse_softmax_route(m, nonzeros, replicas, dtype=torch.float32, backward=False):

@@ -21,6 +21,8 @@ bool sddmm_mfma_shape(int m, int k, int n, int nonzeros, int replicas);
 // Workgroups that share one output tile (each reduces a contiguous range of the
 // (replica, k-step) pairs and writes its own partial vector); 1: straight into `out`.
 int sddmm_mfma_splits(int m, int k, int n, int replicas, int planes = 1);
+// Rows of the output tile a workgroup owns: 128 or 256 (SPUTNIK_HIP_MFMA_TILE, or by shape).
+int sddmm_mfma_tile_rows(int m, int n);
 // The plan (topology only, one small launch): per row, where its entries cross the tile
 // columns, and whether its columns ascend.  Optional: without it (plan == nullptr), and for
 // every tile with a row whose columns do not ascend, the kernel finds a tile's entries by
@@ -67,6 +69,8 @@ size_t densified_bytes(int64_t rows_padded, int k, int values_type, int tile_typ
 int densify_into(int m, int k, int nonzeros, const int* row_offsets, const int* column_indices,
                  const void* values, int values_type, int tile_type, void* image, int64_t rows_padded,
                  hipStream_t stream);
+// Rows of the output tile a workgroup owns: 128 or 256 (SPUTNIK_HIP_MFMA_TILE, or by shape).
+int spmm_mfma_tile_rows(int m, int n, int replicas);
 size_t spmm_mfma_workspace_bytes(int m, int k, int n, int replicas, int values_type, int dense_type,
                                  int tile_type);
 int spmm_mfma_launch(int m, int k, int n, int nonzeros, int replicas, const int* row_offsets,

@@ -41,6 +41,8 @@ inline size_t sddmm_many_mask_plan_bytes(int m, int k, int n, int nonzeros) {
 int sddmm_tiled_panels(int m, int k, int n, int nonzeros);
 bool sddmm_flat_applicable(int m, int k, int n, int nonzeros, int elem_bytes);   // sddmm_flat.hip
 int sddmm_tiled_panel_width(int k);
+int sddmm_tiled_slab_rows(int k);                                  // of the plain product's plan
+int sddmm_tiled_sum_slab_rows(int m, int k, int n, int nonzeros);  // of the summed form's plan
 int sddmm_tiled_launch_partials(int m, int k, int n, int nonzeros, int replicas,
                                 const int* row_indices, const int* row_offsets,
                                 const int* column_indices, const float* lhs, int64_t lhs_stride,
@@ -370,17 +372,52 @@ bool float_call_is_small(int m, int k, int n, int nonzeros, int replicas, bool p
   return tiled >= wave;
 }
 
+// The SHAPE part of that choice (the knob, then the two estimates): what the launch paths
+// below and the name / route queries at the end of this file share.  The operands' alignment
+// and the workspace's size are the caller's to add.
+bool wants_tiled(int m, int k, int n, int nonzeros, int replicas /* < 0: unknown */, bool planned,
+                 bool summed) {
+  const bool force_tiled = options().sddmm_kernel == 1;
+  const bool force_wave = options().sddmm_kernel == 2;
+  const bool small = replicas >= 0 && float_call_is_small(m, k, n, nonzeros, replicas, planned, summed);
+  return !force_wave && (force_tiled || !small);
+}
+
 bool takes_tiled(int m, int k, int n, int nonzeros, int replicas /* < 0: unknown */,
                  const float* lhs, int64_t lhs_stride, const float* rhs, int64_t rhs_stride,
                  const void* workspace, size_t workspace_bytes, bool summed = false,
                  bool planned = false) {
-  const bool force_tiled = options().sddmm_kernel == 1;
-  const bool force_wave = options().sddmm_kernel == 2;
-  const bool small = replicas >= 0 && float_call_is_small(m, k, n, nonzeros, replicas, planned, summed);
-  return !force_wave && (force_tiled || !small) && workspace != nullptr &&
+  return wants_tiled(m, k, n, nonzeros, replicas, planned, summed) && workspace != nullptr &&
          aligned_to(workspace, 16) &&
          sddmm_tiled_applicable(m, k, n, nonzeros, lhs, lhs_stride, rhs, rhs_stride) &&
          workspace_bytes >= sddmm_tiled_workspace_bytes(m, k, n, nonzeros, summed);
+}
+
+// The summed product's vector route: tiled partial vectors, one per (replica, panel), or the
+// row-wave kernel's per-replica products.  `tables_usable`: the tiled kernels serve the
+// operands and the workspace holds the summed form's tables (the caller's pointers say).
+// kernel: SPUTNIK_HIP_SUM_ROWWAVE / _TILED (sputnik_hip.h); _MFMA and _PLAIN are the callers'.
+struct SumRoute {
+  int kernel, panel_width, panels, slab_rows, splits;
+};
+SumRoute sum_vector_route(int m, int k, int n, int nonzeros, int replicas, bool half, bool planned,
+                          bool tables_usable) {
+  // (the float32 form has always estimated as if its plan were made by the call; the half
+  // form counts a plan made ahead)
+  bool tiled = tables_usable && wants_tiled(m, k, n, nonzeros, replicas, half && planned, /*summed=*/true);
+  // (the tiled form puts every (replica, panel) pair on grid z: beyond 65535 of them --
+  // a SparseLinear weight gradient over a very large batch -- the row-wave kernel, which
+  // walks z in chunks, writes the per-replica partial products instead)
+  if (tiled && static_cast<int64_t>(replicas) * sddmm_tiled_panels(m, k, n, nonzeros) > kMaxGridYZ)
+    tiled = false;
+  SumRoute r{SPUTNIK_HIP_SUM_ROWWAVE, 0, 1, 0, 1};
+  if (tiled) {
+    r.kernel = SPUTNIK_HIP_SUM_TILED;
+    r.panels = sddmm_tiled_panels(m, k, n, nonzeros);
+    r.panel_width = k / r.panels;
+    r.slab_rows = sddmm_tiled_sum_slab_rows(m, k, n, nonzeros);
+  }
+  return r;
 }
 
 int sddmm_exec(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
@@ -467,13 +504,10 @@ int sddmm_exec_half(int m, int k, int n, int nonzeros, int replicas, const int* 
     return 0;
   }
   const bool half_out = out_type != SPUTNIK_HIP_F32;
-  const bool force_tiled = options().sddmm_kernel == 1;
-  const bool force_wave = options().sddmm_kernel == 2;
   // (the float product's estimates: on the half sweep, tools/small_sddmm.py --half, the
   // one-number rule left 17 % mean regret, worst 2.9 x; these leave 1.1 %)
-  const bool small = float_call_is_small(m, k, n, nonzeros, replicas, planned);
-  const bool tiled = !force_wave && (force_tiled || !small) && workspace != nullptr &&
-                     aligned_to(workspace, 16) &&
+  const bool tiled = wants_tiled(m, k, n, nonzeros, replicas, planned, /*summed=*/false) &&
+                     workspace != nullptr && aligned_to(workspace, 16) &&
                      sddmm_tiled_applicable_half(m, k, n, nonzeros, lhs, lhs_stride, rhs, rhs_stride) &&
                      workspace_bytes >= sddmm_tiled_workspace_bytes(m, k, n, nonzeros) &&
                      (!half_out || sddmm_tiled_passes_half(k) == 1);
@@ -563,15 +597,13 @@ int sddmm_sum_exec(int m, int k, int n, int nonzeros, int replicas, const int* r
     const hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * static_cast<size_t>(nonzeros), stream);
     return static_cast<int>(e);
   }
-  bool tiled = takes_tiled(m, k, n, nonzeros, replicas, lhs, lhs_stride, rhs, rhs_stride,
-                           workspace, workspace_bytes, /*summed=*/true);
-  // (the tiled form puts every (replica, panel) pair on grid z: beyond 65535 of them --
-  // a SparseLinear weight gradient over a very large batch -- the row-wave kernel, which
-  // walks z in chunks, writes the per-replica partial products instead)
-  if (tiled && static_cast<int64_t>(replicas) * sddmm_tiled_panels(m, k, n, nonzeros) > kMaxGridYZ)
-    tiled = false;
-  const int panels = tiled ? sddmm_tiled_panels(m, k, n, nonzeros) : 1;
-  const int64_t parts = static_cast<int64_t>(replicas) * panels;
+  const bool tables_usable =
+      workspace != nullptr && aligned_to(workspace, 16) &&
+      sddmm_tiled_applicable(m, k, n, nonzeros, lhs, lhs_stride, rhs, rhs_stride) &&
+      workspace_bytes >= sddmm_tiled_workspace_bytes(m, k, n, nonzeros, /*summed=*/true);
+  const SumRoute route = sum_vector_route(m, k, n, nonzeros, replicas, /*half=*/false, planned, tables_usable);
+  const bool tiled = route.kernel == SPUTNIK_HIP_SUM_TILED;
+  const int64_t parts = static_cast<int64_t>(replicas) * route.panels;
   if (parts == 1)
     // One replica and one panel: the plain product, which plans for itself -- a plan made
     // for the summed form has that form's slabs and no pair-flat lists behind the tables,
@@ -674,18 +706,14 @@ int sddmm_sum_exec_half(int m, int k, int n, int nonzeros, int replicas, const i
     return sum_on_matrix_cores(m, k, n, nonzeros, replicas, row_offsets, column_indices, lhs,
                                lhs_stride, rhs, rhs_stride, in_type, out, workspace, workspace_bytes,
                                planned, scratch, scratch_bytes, stream, 1, 0, 0);
-  const bool force_tiled = options().sddmm_kernel == 1;
-  const bool force_wave = options().sddmm_kernel == 2;
-  const bool small = float_call_is_small(m, k, n, nonzeros, replicas, planned, /*summed=*/true);
-  bool tiled = !force_wave && (force_tiled || !small) && workspace != nullptr &&
-               aligned_to(workspace, 16) &&
-               sddmm_tiled_applicable_half(m, k, n, nonzeros, lhs, lhs_stride, rhs, rhs_stride) &&
-               sddmm_tiled_sum_half_served(m, k, n, nonzeros) &&
-               workspace_bytes >= sddmm_tiled_workspace_bytes(m, k, n, nonzeros, /*summed=*/true);
-  if (tiled && static_cast<int64_t>(replicas) * sddmm_tiled_panels(m, k, n, nonzeros) > kMaxGridYZ)
-    tiled = false;
-  const int panels = tiled ? sddmm_tiled_panels(m, k, n, nonzeros) : 1;
-  const int64_t parts = static_cast<int64_t>(replicas) * panels;
+  const bool tables_usable =
+      workspace != nullptr && aligned_to(workspace, 16) &&
+      sddmm_tiled_applicable_half(m, k, n, nonzeros, lhs, lhs_stride, rhs, rhs_stride) &&
+      sddmm_tiled_sum_half_served(m, k, n, nonzeros) &&
+      workspace_bytes >= sddmm_tiled_workspace_bytes(m, k, n, nonzeros, /*summed=*/true);
+  const SumRoute route = sum_vector_route(m, k, n, nonzeros, replicas, /*half=*/true, planned, tables_usable);
+  const bool tiled = route.kernel == SPUTNIK_HIP_SUM_TILED;
+  const int64_t parts = static_cast<int64_t>(replicas) * route.panels;
   if (parts == 1)   // (the plain product, planning for itself: see sddmm_sum_exec)
     return sddmm_exec_half(m, k, n, nonzeros, 1, row_indices, row_offsets, column_indices, lhs,
                            lhs_stride, rhs, rhs_stride, out, 0, in_type, SPUTNIK_HIP_F32,
@@ -945,16 +973,51 @@ int sputnik_hip_sddmm_typed(int m, int k, int n, int nonzeros, int replicas,
 const char* sputnik_hip_sddmm_kernel_name(int m, int k, int n, int nonzeros, int replicas,
                                           int elem_bytes, int planned) {
   if (m <= 0 || k <= 0 || n <= 0 || nonzeros <= 0 || replicas <= 0) return "none";
-  const bool force_tiled = options().sddmm_kernel == 1;
-  const bool force_wave = options().sddmm_kernel == 2;
-  const bool small = float_call_is_small(m, k, n, nonzeros, replicas, planned != 0);
   const bool shape = sddmm_tiled_workspace_bytes(m, k, n, nonzeros) != 0 &&
                      static_cast<int64_t>(n) * k * elem_bytes < (int64_t{1} << 32) &&
                      static_cast<int64_t>(m) * k * elem_bytes < (int64_t{1} << 32);
-  if (force_wave || !(force_tiled || !small) || !shape) return "sddmm_rowwave_kernel";
+  if (!wants_tiled(m, k, n, nonzeros, replicas, planned != 0, /*summed=*/false) || !shape)
+    return "sddmm_rowwave_kernel";
   if (planned != 0 && sddmm_flat_applicable(m, k, n, nonzeros, elem_bytes)) return "sddmm_flat_kernel";
   if (elem_bytes == 2 || sddmm_tiled_panel_width(k) == 64) return "sddmm_quad_kernel";
   return "sddmm_stationary_kernel";
+}
+
+int sputnik_hip_sddmm_sum_route(int m, int k, int n, int nonzeros, int replicas, int in_type,
+                                int planned, int mixed, int* kernel, int* panel_width, int* panels,
+                                int* slab_rows, int* splits) {
+  if (m <= 0 || k <= 0 || n <= 0 || nonzeros <= 0 || replicas <= 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const bool half = in_type == SPUTNIK_HIP_F16 || in_type == SPUTNIK_HIP_BF16;
+  if (!half && (in_type != SPUTNIK_HIP_F32 || mixed != 0)) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  SumRoute r{SPUTNIK_HIP_SUM_ROWWAVE, 0, 1, 0, 1};
+  if (half && sddmm_mfma_applicable(m, k, n, nonzeros, replicas, nullptr, 0, nullptr, 0)) {
+    r.kernel = SPUTNIK_HIP_SUM_MFMA;
+    r.slab_rows = sddmm_mfma_tile_rows(m, n);
+    r.splits = sddmm_mfma_splits(m, k, n, replicas, mixed != 0 ? sddmm_mfma_planes_of(in_type) : 1);
+  } else if (mixed != 0) {
+    return SPUTNIK_HIP_UNSUPPORTED;   // (a (float32, half) pair has the matrix-core route only)
+  } else {
+    const bool served = sddmm_tiled_workspace_bytes(m, k, n, nonzeros, /*summed=*/true) != 0 &&
+                        (half ? sddmm_tiled_applicable_half(m, k, n, nonzeros, nullptr, 0, nullptr, 0) &&
+                                    sddmm_tiled_sum_half_served(m, k, n, nonzeros)
+                              : sddmm_tiled_applicable(m, k, n, nonzeros, nullptr, 0, nullptr, 0));
+    r = sum_vector_route(m, k, n, nonzeros, replicas, half, planned != 0, served);
+    if (static_cast<int64_t>(replicas) * r.panels == 1) {
+      // nothing to sum: the plain product, planning for itself, on the summed form's workspace
+      const bool plain_tiled =
+          r.kernel == SPUTNIK_HIP_SUM_TILED &&
+          wants_tiled(m, k, n, nonzeros, 1, /*planned=*/false, /*summed=*/false) &&
+          sum_workspace_bytes(m, k, n, nonzeros) >= sddmm_tiled_workspace_bytes(m, k, n, nonzeros);
+      r = SumRoute{SPUTNIK_HIP_SUM_PLAIN, plain_tiled ? sddmm_tiled_panel_width(k) : 0, 1, 0, 1};
+      if (plain_tiled) r.slab_rows = sddmm_tiled_slab_rows(k);
+    }
+  }
+  if (kernel != nullptr) *kernel = r.kernel;
+  if (panel_width != nullptr) *panel_width = r.panel_width;
+  if (panels != nullptr) *panels = r.panels;
+  if (slab_rows != nullptr) *slab_rows = r.slab_rows;
+  if (splits != nullptr) *splits = r.splits;
+  return 0;
 }
 
 int sputnik_hip_sddmm(int m, int k, int n, int nonzeros, const int* row_indices,

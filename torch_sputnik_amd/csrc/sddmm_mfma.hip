@@ -211,6 +211,8 @@ int sddmm_mfma_splits(int m, int k, int n, int replicas, int planes) {
   return splits < 1 ? 1 : static_cast<int>(splits);
 }
 
+int sddmm_mfma_tile_rows(int m, int n) { return wide_tile(m, n, 0) ? 256 : kTile; }
+
 size_t sddmm_mfma_plan_bytes(int m, int n) {
   return sizeof(int) * static_cast<size_t>(plan_rows(m) + static_cast<int64_t>(m) * (ceil_div(n, kTile) + 1));
 }

@@ -879,6 +879,10 @@ int launch_partials(int m, int k, int n, int nonzeros, int replicas, int slots,
 }  // namespace
 
 int sddmm_tiled_panel_width(int k) { return panel_width(k); }
+int sddmm_tiled_slab_rows(int k) { return panel_width(k) != 0 ? slab_rows_of_width(panel_width(k)) : 0; }
+int sddmm_tiled_sum_slab_rows(int m, int k, int n, int nonzeros) {
+  return served(k) ? sum_slab_rows(m, k, n, nonzeros) : 0;
+}
 
 int sddmm_tiled_panels(int m, int k, int n, int nonzeros) {
   return served(k) ? k / sum_panel_width(m, k, n, nonzeros) : 1;

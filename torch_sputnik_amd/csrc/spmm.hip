@@ -544,6 +544,11 @@ size_t sputnik_hip_left_spmm_half_tiles_workspace_bytes(int m, int k, int n, int
   return spmm_mfma_workspace_bytes(m, k, n, replicas, values_type, dense_type, tile_type);
 }
 
+int sputnik_hip_left_spmm_half_tiles_tile_rows(int m, int n, int replicas) {
+  if (m <= 0 || n <= 0 || replicas <= 0) return 0;
+  return spmm_mfma_tile_rows(m, n, replicas);
+}
+
 int sputnik_hip_left_spmm_half_tiles(int m, int k, int n, int nonzeros, int replicas,
                                      const int* row_offsets, const int* column_indices,
                                      const void* values, int values_type, const void* dense,
@@ -562,6 +567,63 @@ int sputnik_hip_left_spmm_half_tiles(int m, int k, int n, int nonzeros, int repl
   return spmm_mfma_launch(m, k, n, nonzeros, replicas, row_offsets, column_indices, values,
                           values_type, dense, dense_type, dense_stride, tile_type, bias, relu, out,
                           out_stride, workspace, stream);
+}
+
+namespace {
+// The typed product's choices, shared by sputnik_hip_spmm_typed and the name query below.
+// Panel-resident kernel (the half panel is widened on its way into LDS) wherever it
+// applies and is not hopeless (at most four panels, i.e. k <= 2048; forced by the
+// "panel" knob up to its limit), otherwise the row-gather kernel, which reads half
+// rows of B straight from L2.  Neither needs the workspace.
+// (measured, tools/half_bench.py: attention P.V 1024^2 x 64 x 64 replicas 42.8 us native
+// against 61 for cast + float kernels, projection 19 against 36; 2048^2 x 512 x 8, four
+// panels: 366 against 189 -- so beyond two panels the operands are widened into the
+// workspace by one pass of this library and the chunked float kernels run)
+bool typed_takes_panel(int m, int k, int n, int nonzeros, int replicas, const void* dense,
+                       int dense_type, int64_t dense_stride, const float* out, int64_t out_stride) {
+  const int forced = options().spmm_kernel;
+  return nonzeros > 0 && (forced == 0 || forced == 3) &&
+         spmm_panel_applicable_typed(m, k, n, nonzeros, dense, dense_type, dense_stride, out, out_stride) &&
+         (forced == 3 || k <= 512 ||
+          (k <= 1024 && (nonzeros <= 320 * static_cast<int64_t>(m) || n <= 128))) &&
+         static_cast<int64_t>(nonzeros) * n * replicas >= (int64_t{1} << 22) &&
+         // (round 5, tools/spmm_dispatch_sweep.py --half: as for float operands the
+         // panel kernel needs workgroups against the row gather -- 1024^2 x 256,
+         // one replica, 16 of them: 35 against 23 us at density 0.1, 82 against 57
+         // at 0.3)
+         (forced == 3 ||
+          static_cast<int64_t>((m + 255) / 256) * ((n + 63) / 64) * replicas >= 96);
+}
+// The shape part of "widen the operands into the workspace and run the float kernels".
+bool typed_widens(int m, int k, int n, int nonzeros, int replicas, int values_type,
+                  int64_t values_stride, int dense_type) {
+  const bool big = static_cast<int64_t>(nonzeros) * n * replicas >= (int64_t{1} << 28);
+  return options().spmm_kernel == 0 && big && (values_stride == 0 || values_stride == nonzeros) &&
+         sputnik_hip_spmm_typed_workspace_bytes(m, k, n, nonzeros, replicas, values_type, values_stride,
+                                                dense_type) != 0;
+}
+}  // namespace
+
+const char* sputnik_hip_spmm_typed_kernel_name(int m, int k, int n, int nonzeros, int replicas,
+                                               int values_type, int64_t values_stride,
+                                               int dense_type) {
+  const auto known = [](int t) {
+    return t == SPUTNIK_HIP_F32 || t == SPUTNIK_HIP_F16 || t == SPUTNIK_HIP_BF16;
+  };
+  if (!known(values_type) || !known(dense_type) || m <= 0 || n <= 0 || replicas <= 0) return "none";
+  if (values_type == SPUTNIK_HIP_F32 && dense_type == SPUTNIK_HIP_F32)
+    return sputnik_hip_spmm_kernel_name(m, k, n, nonzeros, replicas);
+  if (values_type != SPUTNIK_HIP_F32 && dense_type != SPUTNIK_HIP_F32 && values_type != dense_type)
+    return "none";
+  if (values_stride == 0 && dense_type != SPUTNIK_HIP_F32 &&
+      spmm_mfma_shape(m, k, n, nonzeros, replicas, values_type, dense_type, dense_type))
+    return "left_spmm_half_tiles";
+  if (typed_takes_panel(m, k, n, nonzeros, replicas, nullptr, dense_type,
+                        static_cast<int64_t>(k) * n, nullptr, static_cast<int64_t>(m) * n))
+    return "spmm_panel64_kernel";
+  if (typed_widens(m, k, n, nonzeros, replicas, values_type, values_stride, dense_type))
+    return sputnik_hip_spmm_kernel_name(m, k, n, nonzeros, replicas);   // (on widened copies)
+  return "spmm_rowgather_kernel";
 }
 
 // Workspace of sputnik_hip_spmm_typed: the float form's, plus room for float copies of
@@ -625,36 +687,15 @@ int sputnik_hip_spmm_typed(int m, int k, int n, int nonzeros, int replicas,
   Epilogue epi;
   epi.bias = bias;
   epi.relu = relu != 0;
-  // Panel-resident kernel (the half panel is widened on its way into LDS) wherever it
-  // applies and is not hopeless (at most four panels, i.e. k <= 2048; forced by the
-  // "panel" knob up to its limit), otherwise the row-gather kernel, which reads half
-  // rows of B straight from L2.  Neither needs the workspace.
-  // (measured, tools/half_bench.py: attention P.V 1024^2 x 64 x 64 replicas 42.8 us native
-  // against 61 for cast + float kernels, projection 19 against 36; 2048^2 x 512 x 8, four
-  // panels: 366 against 189 -- so beyond two panels the operands are widened into the
-  // workspace by one pass of this library and the chunked float kernels run)
-  const int forced = options().spmm_kernel;
-  const bool panel_ok = nonzeros > 0 && (forced == 0 || forced == 3) &&
-                        spmm_panel_applicable_typed(m, k, n, nonzeros, dense, dense_type,
-                                                    dense_stride, out, out_stride) &&
-                        (forced == 3 || k <= 512 ||
-                         (k <= 1024 && (nonzeros <= 320 * static_cast<int64_t>(m) || n <= 128))) &&
-                        static_cast<int64_t>(nonzeros) * n * replicas >= (int64_t{1} << 22) &&
-                        // (round 5, tools/spmm_dispatch_sweep.py --half: as for float operands the
-                        // panel kernel needs workgroups against the row gather -- 1024^2 x 256,
-                        // one replica, 16 of them: 35 against 23 us at density 0.1, 82 against 57
-                        // at 0.3)
-                        (forced == 3 ||
-                         static_cast<int64_t>((m + 255) / 256) * ((n + 63) / 64) * replicas >= 96);
-  if (panel_ok)
+  // (typed_takes_panel above: the panel-resident kernel, else the widened float kernels, else
+  // the row gather)
+  if (typed_takes_panel(m, k, n, nonzeros, replicas, dense, dense_type, dense_stride, out, out_stride))
     return spmm_panel_launch_typed(m, k, n, nonzeros, replicas, row_indices, values, values_type,
                                    values_stride, row_offsets, column_indices, dense, dense_type,
                                    dense_stride, out, out_stride, stream, epi);
-  const bool big = static_cast<int64_t>(nonzeros) * n * replicas >= (int64_t{1} << 28);
-  if (forced == 0 && big && workspace != nullptr && aligned_to(workspace, 256) &&
-      dense_stride == static_cast<int64_t>(k) * n && (values_stride == 0 || values_stride == nonzeros) &&
-      sputnik_hip_spmm_typed_workspace_bytes(m, k, n, nonzeros, replicas, values_type,
-                                             values_stride, dense_type) != 0 &&
+  if (typed_widens(m, k, n, nonzeros, replicas, values_type, values_stride, dense_type) &&
+      workspace != nullptr && aligned_to(workspace, 256) &&
+      dense_stride == static_cast<int64_t>(k) * n &&
       workspace_bytes >= sputnik_hip_spmm_typed_workspace_bytes(m, k, n, nonzeros, replicas,
                                                                 values_type, values_stride,
                                                                 dense_type)) {

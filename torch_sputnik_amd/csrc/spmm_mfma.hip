@@ -176,6 +176,8 @@ bool spmm_mfma_shape(int m, int k, int n, int nonzeros, int replicas, int values
   return m >= kTile && n >= kTile && tiles >= 192 && density >= 0.06 * passes_of(pa, pb);
 }
 
+int spmm_mfma_tile_rows(int m, int n, int replicas) { return wide_tile(m, n, replicas) ? 256 : kTile; }
+
 size_t spmm_mfma_workspace_bytes(int m, int k, int n, int replicas, int values_type, int dense_type,
                                  int tile_type) {
   size_t bytes = densified_bytes(padded_rows(m), k, values_type, tile_type);
@@ -218,7 +220,7 @@ int spmm_mfma_launch(int m, int k, int n, int nonzeros, int replicas, const int*
   // src/left_replicated_spmm.cu:36 takes): its fragments are transposing reads
   return launch_mfma_gemm_typed<false, true, kDense>(tile_type, pa, pb, m, n, k, replicas, replicas,
                                                      /*outer_is_split=*/false, a, bop, o, stream,
-                                                     wide_tile(m, n, replicas));
+                                                     spmm_mfma_tile_rows(m, n, replicas) == 256);
 }
 
 }  // namespace sputnik_hip
