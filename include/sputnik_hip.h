@@ -551,7 +551,8 @@ SPUTNIK_HIP_API int sputnik_hip_csr_transpose_typed(int m, int n, int nonzeros, 
  * Preconditions (as for cusparseCsr2cscEx2 on valid CSR): column indices in
  * [0, n), a row stores a column at most once (order inside a row is free).
  * A violation is DETECTED on the device: the status word (the last 16 bytes of
- * the workspace) is non-zero afterwards, and the outputs are unspecified.
+ * the workspace) is non-zero afterwards, and the outputs are unspecified (a bad
+ * entry leaves a slot of the permutation unwritten; no value is read through it).
  * sputnik_hip_csr_transpose is asynchronous and leaves the word to the caller;
  * sputnik_hip_csr_transpose_checked (same arguments) waits for the stream and
  * returns SPUTNIK_HIP_INVALID_ARGUMENT.
@@ -579,6 +580,37 @@ SPUTNIK_HIP_API int sputnik_hip_csr_transpose(int m, int n, int nonzeros, int re
                               int* out_permutation, void* workspace,
                               size_t workspace_bytes,
                               sputnik_hip_stream_t stream);
+
+/* The launches sputnik_hip_csr_transpose makes for a call of this shape (transpose.hip); the
+ * entry takes its decisions from the same function this reports.
+ *   path   SPUTNIK_HIP_TRANSPOSE_NONE: an empty dimension or no entries, nothing launched;
+ *          _GROUPED: mask and count tables, scatter by chunk and group of 256 columns (up to
+ *          8192 columns); _WIDE: the tables, a scan of the column totals and the plain
+ *          scatter over column ranges of 8192; _SPARSE: the O(n + nnz) path, taken where the
+ *          tables would hold more than eight entries per nonzero (ceil(m / 32) * n >
+ *          8 * nonzeros: the condition sputnik_hip_csr_transpose_workspace_bytes sizes by)
+ *   chunks                  blocks of 32 source rows (_GROUPED, _WIDE)
+ *   ranges                  column ranges of 8192 (_GROUPED: 1, _WIDE)
+ *   groups                  column groups per chunk in the grouped scatter's grid, a multiple
+ *                           of 8 (_GROUPED)
+ *   parts                   workgroups per chunk and range in the plain scatter, 8 / 4 / 2 / 1
+ *                           with 32 / parts rows each (_WIDE)
+ *   scan_chunks_per_group   chunks each of the table scan's 16 groups walks (_GROUPED, _WIDE):
+ *                           up to 8 stay in registers, more take the kernel's second loops
+ *   long_rank_launch        1 if the bitmap ranking kernel for output rows of more than 2048
+ *                           entries is launched (nonzeros > 2048), else 0 (_SPARSE)
+ * Fields that do not apply to the path are -1.  Host only, launches nothing; any output pointer
+ * may be NULL.  Returns SPUTNIK_HIP_INVALID_ARGUMENT for a negative size or a shape whose grid
+ * does not exist (the entry returns the same).  For tests, which assert the route they mean
+ * to reach. */
+#define SPUTNIK_HIP_TRANSPOSE_NONE 0
+#define SPUTNIK_HIP_TRANSPOSE_GROUPED 1
+#define SPUTNIK_HIP_TRANSPOSE_WIDE 2
+#define SPUTNIK_HIP_TRANSPOSE_SPARSE 3
+SPUTNIK_HIP_API int sputnik_hip_csr_transpose_route(int m, int n, int nonzeros, int* path,
+                                                    int* chunks, int* ranges, int* groups,
+                                                    int* parts, int* scan_chunks_per_group,
+                                                    int* long_rank_launch);
 
 /* ========================================================================
  * Extensions around the five operators.  The reference binding
@@ -1189,6 +1221,30 @@ SPUTNIK_HIP_API int sputnik_hip_csr_transpose_many_mask(int masks, int m, int n,
                              int* out_column_indices, int* out_permutation,
                              void* workspace, size_t workspace_bytes,
                              sputnik_hip_stream_t stream);
+/* What sputnik_hip_csr_transpose_many_mask does for a batch of `masks` masks whose largest
+ * holds `largest_nonzeros` entries and which hold `total_nonzeros` together, with `heads`
+ * value rows per mask (0: no values passed) at least `largest_nonzeros` wide, with or without
+ * a permutation output, in a workspace of `workspace_bytes` (0: none); the entry takes its
+ * decision from the same function this reports, and from nothing else.  (That function also
+ * sends value rows NARROWER than `largest_nonzeros`, by either stride, mask after mask; the
+ * query has no stride input and answers for rows that are wide enough.)
+ *   one_launch   1: one launch per phase serves all masks; 0: mask after mask, each as
+ *                sputnik_hip_csr_transpose_route says (fewer than two masks, more than 8192
+ *                columns, a largest mask on the O(n + nnz) path, or a workspace without a
+ *                region per mask -- plus room for the permutation behind the regions when
+ *                several heads are moved and the caller takes no permutation)
+ *   values_by    SPUTNIK_HIP_MANY_VALUES_NONE / _SCATTER (one head: the values ride in the
+ *                scatter) / _GATHER (several heads: one gather through the permutation);
+ *                -1 mask after mask
+ * Host only, launches nothing; any output pointer may be NULL.  Returns
+ * SPUTNIK_HIP_INVALID_ARGUMENT for a negative argument. */
+#define SPUTNIK_HIP_MANY_VALUES_NONE 0
+#define SPUTNIK_HIP_MANY_VALUES_SCATTER 1
+#define SPUTNIK_HIP_MANY_VALUES_GATHER 2
+SPUTNIK_HIP_API int sputnik_hip_csr_transpose_many_mask_route(int masks, int m, int n,
+                             int largest_nonzeros, int64_t total_nonzeros, int heads,
+                             int with_permutation, size_t workspace_bytes, int* one_launch,
+                             int* values_by);
 
 /*
  * out[r][i] = in[r][permutation[i]], i < n, for `rows` value arrays (strides in

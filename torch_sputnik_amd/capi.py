@@ -93,6 +93,9 @@ SIGNATURES = {
     "sputnik_hip_csr_transpose": (_c_int, [_c_int] * 4 + [_c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_size, _c_ptr]),
+    "sputnik_hip_csr_transpose_route": (_c_int, [_c_int] * 3 + [_c_ptr] * 7),
+    "sputnik_hip_csr_transpose_many_mask_route": (_c_int, [_c_int] * 4 + [_c_i64, _c_int, _c_int, _c_size,
+                                                                         _c_ptr, _c_ptr]),
     "sputnik_hip_csr_transpose_checked": (_c_int, [_c_int] * 4 + [_c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_size, _c_ptr]),
@@ -424,6 +427,41 @@ def sparse_softmax_batched(m, replicas, values, row_indices, row_offsets, column
 
 def csr_transpose_workspace_bytes(m, n, nonzeros):
     return lib().sputnik_hip_csr_transpose_workspace_bytes(m, n, nonzeros)
+
+
+TRANSPOSE_PATHS = ("none", "grouped", "wide", "sparse")   # SPUTNIK_HIP_TRANSPOSE_NONE / _GROUPED / _WIDE / _SPARSE
+
+
+def csr_transpose_route(m, n, nonzeros):
+    """Launches csr_transpose makes for a call of this shape: a dict of path (one of
+    TRANSPOSE_PATHS), chunks, ranges, groups, parts, scan_chunks_per_group and long_rank_launch
+    (include/sputnik_hip.h); -1 where a field does not apply to the path.  Host only."""
+    names = ("path", "chunks", "ranges", "groups", "parts", "scan_chunks_per_group",
+             "long_rank_launch")
+    outs = [_c_int(-1) for _ in names]
+    _check(lib().sputnik_hip_csr_transpose_route(
+        m, n, nonzeros, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
+        "sputnik_hip_csr_transpose_route")
+    route = {name: o.value for name, o in zip(names, outs)}
+    route["path"] = TRANSPOSE_PATHS[route["path"]]
+    return route
+
+
+MANY_VALUES = ("none", "scatter", "gather")   # SPUTNIK_HIP_MANY_VALUES_NONE / _SCATTER / _GATHER
+
+
+def csr_transpose_many_mask_route(masks, m, n, nonzeros, heads, with_permutation, workspace_bytes):
+    """What csr_transpose_many_mask does for masks of these entry counts (a sequence) with `heads`
+    value rows per mask (0: no values) in a workspace of that size: a dict of one_launch (bool;
+    False = mask after mask) and values_by (one of MANY_VALUES, None mask after mask).  Host only."""
+    counts = [int(c) for c in nonzeros]
+    outs = [_c_int(-1), _c_int(-1)]
+    _check(lib().sputnik_hip_csr_transpose_many_mask_route(
+        masks, m, n, max(counts, default=0), sum(counts), heads, int(bool(with_permutation)),
+        workspace_bytes, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
+        "sputnik_hip_csr_transpose_many_mask_route")
+    one_launch, values_by = bool(outs[0].value), outs[1].value
+    return {"one_launch": one_launch, "values_by": MANY_VALUES[values_by] if values_by >= 0 else None}
 
 
 def csr_transpose(m, n, replicas, values, row_offsets, column_indices, out_values,

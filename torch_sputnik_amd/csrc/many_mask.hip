@@ -192,19 +192,17 @@ int sputnik_hip_csr_transpose_many_mask(int masks, int m, int n, const int* nonz
                                         sputnik_hip_stream_t stream) {
   const MaskWalk w = check(masks, m, n, nonzeros, replicas);
   if (!w.ok) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (masks > 1 && m > 0 && n > 0) {
+  {   // one launch per phase where csr_transpose_many_route (transpose.hip) says so: every
+      // condition is there, none here
     const bool with_values = values != nullptr && out_values != nullptr;
-    const int largest = largest_of(masks, nonzeros);
-    if (!with_values || (values_stride >= largest && out_values_stride >= largest)) {
-      int64_t total = 0;
-      for (int i = 0; i < masks; ++i) total += nonzeros[i];
-      const int st = csr_transpose_many_launch(
-          masks, m, n, largest, total, with_values ? w.heads : 0, with_values ? values : nullptr,
-          values_stride, row_offsets, column_indices, with_values ? out_values : nullptr,
-          out_values_stride, out_row_offsets, out_column_indices, out_permutation, workspace,
-          workspace_bytes, stream);
-      if (st >= 0) return st;
-    }
+    int64_t total = 0;
+    for (int i = 0; i < masks; ++i) total += nonzeros[i];
+    const int st = csr_transpose_many_launch(
+        masks, m, n, largest_of(masks, nonzeros), total, with_values ? w.heads : 0,
+        with_values ? values : nullptr, values_stride, row_offsets, column_indices,
+        with_values ? out_values : nullptr, out_values_stride, out_row_offsets, out_column_indices,
+        out_permutation, workspace, workspace_bytes, stream);
+    if (st >= 0) return st;
   }
   int64_t first = 0;
   for (int i = 0; i < masks; ++i) {

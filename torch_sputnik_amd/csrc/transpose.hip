@@ -84,6 +84,12 @@ __device__ __forceinline__ ManyPlace many_place(int mask, int m, const int* __re
 // that group g of every chunk has the same `workgroup id % 8` (see the scatter).
 inline int column_groups(int n) { return ceil_div(ceil_div(n, kGroupCols), 8) * 8; }
 
+// Chunks per chunk group of the table scan: what the scan kernel walks per thread, and what
+// the route query reports (more than the kernel's kKeep = 8 take its second loops).
+__host__ __device__ inline int scan_chunks_per_group(int chunks) {
+  return (chunks + kScanGroups - 1) / kScanGroups;
+}
+
 // A wave walks one row: lanes over the row's nonzeros (coalesced), kUnroll
 // requests per lane in flight before the first one is used -- a row of a few
 // hundred entries costs ONE memory latency, not one per 64 entries.
@@ -335,6 +341,9 @@ __global__ __launch_bounds__(kBlock) void transpose_sparse_values_kernel(
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= nonzeros) return;
   const int p = permutation[i];
+  // (a pattern the transpose is not defined for leaves slots of the permutation unwritten:
+  // the status word reports it, and no value is read through such a slot)
+  if (static_cast<unsigned>(p) >= static_cast<unsigned>(nonzeros)) return;
   for (int r = 0; r < replicas; ++r)
     out_values[r * out_values_stride + i] = static_cast<float>(values[r * values_stride + p]);
 }
@@ -368,12 +377,18 @@ __global__ __launch_bounds__(kBlock) void transpose_many_values_kernel(
   int p[kManyValuesUnroll];
 #pragma unroll
   for (int u = 0; u < kManyValuesUnroll; ++u) p[u] = i0 + u * kBlock < count ? permutation[i0 + u * kBlock] : 0;
-  float v[kManyValuesUnroll];
-#pragma unroll
-  for (int u = 0; u < kManyValuesUnroll; ++u) v[u] = i0 + u * kBlock < count ? values[p[u]] : 0.f;
+  // (a slot that an invalid mask left unwritten is no source index: nothing is read through
+  // it and nothing stored for it, as in transpose_sparse_values_kernel)
+  bool live[kManyValuesUnroll];
 #pragma unroll
   for (int u = 0; u < kManyValuesUnroll; ++u)
-    if (i0 + u * kBlock < count) out_values[i0 + u * kBlock] = v[u];
+    live[u] = i0 + u * kBlock < count && static_cast<unsigned>(p[u]) < static_cast<unsigned>(count);
+  float v[kManyValuesUnroll];
+#pragma unroll
+  for (int u = 0; u < kManyValuesUnroll; ++u) v[u] = live[u] ? values[p[u]] : 0.f;
+#pragma unroll
+  for (int u = 0; u < kManyValuesUnroll; ++u)
+    if (live[u]) out_values[i0 + u * kBlock] = v[u];
 }
 
 // table[chunk][c] = sum of popc(gmask[chunk'][c]) over chunk' < chunk;
@@ -400,7 +415,7 @@ __global__ __launch_bounds__(kWave* kScanGroups) void transpose_scan_table_kerne
   const int lane = threadIdx.x % kWave;
   const int group = threadIdx.x / kWave;
   const int c = blockIdx.x * kWave + lane;
-  const int per_group = (chunks + kScanGroups - 1) / kScanGroups;
+  const int per_group = scan_chunks_per_group(chunks);
   const int ch0 = min(chunks, group * per_group);
   const int ch1 = min(chunks, ch0 + per_group);
 
@@ -738,7 +753,81 @@ inline size_t status_offset(int m, int n, int nonzeros) {
   return (body + 15) / 16 * 16;
 }
 
+// The host's launch decisions for one transpose: sputnik_hip_csr_transpose launches what
+// this returns, sputnik_hip_csr_transpose_route reports it.  Fields that do not apply to
+// the path are -1.
+enum : int { kPathNone = SPUTNIK_HIP_TRANSPOSE_NONE, kPathGrouped = SPUTNIK_HIP_TRANSPOSE_GROUPED,
+             kPathWide = SPUTNIK_HIP_TRANSPOSE_WIDE, kPathSparse = SPUTNIK_HIP_TRANSPOSE_SPARSE };
+struct TransposeRoute {
+  int status = 0;   // SPUTNIK_HIP_INVALID_ARGUMENT: a grid the shape would need does not exist
+  int path = kPathNone;
+  int chunks = -1, ranges = -1, groups = -1, parts = -1;
+  int scan_chunks_per_group = -1;   // table paths
+  int long_rank_launch = -1;        // O(n + nnz) path: the bitmap kernel is launched
+};
+inline TransposeRoute transpose_route(int m, int n, int nonzeros) {
+  TransposeRoute r;
+  if (m < 0 || n < 0 || nonzeros < 0) {
+    r.status = SPUTNIK_HIP_INVALID_ARGUMENT;
+    return r;
+  }
+  if (m == 0 || n == 0 || nonzeros == 0) return r;
+  if (sparse_path(m, n, nonzeros)) {
+    r.path = kPathSparse;
+    r.long_rank_launch = nonzeros > kLongColumn;   // (a workgroup per output row; all but the long rows leave at once)
+    return r;
+  }
+  r.chunks = chunks_of(m);
+  r.ranges = ceil_div(n, kColsPerRange);
+  r.scan_chunks_per_group = scan_chunks_per_group(r.chunks);
+  const int groups = column_groups(n);
+  if (r.ranges == 1 && r.chunks <= 0x7fffffff / groups) {
+    r.path = kPathGrouped;
+    r.groups = groups;
+    return r;
+  }
+  r.path = kPathWide;
+  // Workgroups per chunk in the plain scatter: enough for about two per CU (the
+  // chunk's 32 rows split into parts of 16 / 8 / 4).
+  r.parts = 1;
+  while (r.parts < 8 && static_cast<int64_t>(r.chunks) * r.ranges * r.parts < 512) r.parts *= 2;
+  if (r.ranges > kMaxGridYZ || r.chunks > 0x7fffffff / r.parts) r.status = SPUTNIK_HIP_INVALID_ARGUMENT;
+  return r;
+}
+
 }  // namespace
+
+// The decisions of the "many mask" entry: csr_transpose_many_launch launches what this
+// returns, sputnik_hip_csr_transpose_many_mask_route reports it.  EVERY condition of "one
+// launch per phase" is here, the width of the value rows included (`value_row_width`: the
+// smaller of the two row strides, INT64_MAX where no values move): the entry asks nothing
+// of its own before it calls the launch.
+size_t csr_transpose_many_region_bytes(int m, int n, int largest_nonzeros);
+struct TransposeManyRoute {
+  bool one_launch;         // one launch per phase for all masks; mask after mask otherwise
+  bool gather;             // the values of all replicas move in ONE gather behind the scatter
+  size_t region_bytes;     // tables of one mask
+  size_t tables_bytes;     // ... of all masks: a permutation the caller does not take sits behind
+};
+TransposeManyRoute csr_transpose_many_route(int masks, int m, int n, int largest_nonzeros,
+                                            int64_t total_nonzeros, int heads, bool has_permutation,
+                                            bool has_workspace, size_t workspace_bytes,
+                                            int64_t value_row_width) {
+  TransposeManyRoute r;
+  r.region_bytes = csr_transpose_many_region_bytes(m, n, max(largest_nonzeros, 0));
+  r.gather = heads > 1;
+  r.tables_bytes = r.region_bytes * static_cast<size_t>(max(masks, 0));
+  const size_t need = r.tables_bytes + (r.gather && !has_permutation
+                                            ? sizeof(int) * static_cast<size_t>(total_nonzeros) : 0);
+  r.one_launch = !(
+      masks < 2 || masks > kMaxGridYZ || heads > kMaxGridYZ || largest_nonzeros <= 0 || m <= 0 || n <= 0 ||
+      (heads > 0 && value_row_width < largest_nonzeros) ||   // (the gather's grid covers `largest` of every row)
+      static_cast<int64_t>(ceil_div(largest_nonzeros, kBlock * kManyValuesUnroll)) * max(heads, 1) * masks >=
+          (int64_t{1} << 32) ||
+      n > kColsPerRange || sparse_path(m, n, largest_nonzeros) ||
+      chunks_of(m) > 0x7fffffff / column_groups(n) || !has_workspace || workspace_bytes < need);
+  return r;
+}
 
 // All masks of a "many mask" batch in three launches (many_mask.hip).  Taken when the
 // LARGEST mask is a table-path matrix of one column range (every attention mask is) and
@@ -765,20 +854,18 @@ int csr_transpose_many_launch(int masks, int m, int n, int largest_nonzeros, int
                               int64_t out_values_stride, int* out_row_offsets,
                               int* out_column_indices, int* out_permutation, void* workspace,
                               size_t workspace_bytes, hipStream_t stream) {
+  const TransposeManyRoute route =
+      csr_transpose_many_route(masks, m, n, largest_nonzeros, total_nonzeros, heads,
+                               out_permutation != nullptr, workspace != nullptr, workspace_bytes,
+                               heads == 0                          ? INT64_MAX
+                               : values_stride < out_values_stride ? values_stride
+                                                                   : out_values_stride);
+  if (!route.one_launch) return -1;
   const int chunks = chunks_of(m);
   const int groups = column_groups(n);
-  const size_t region_bytes = csr_transpose_many_region_bytes(m, n, largest_nonzeros);
-  const bool gather = heads > 1;
-  const size_t tables_bytes = region_bytes * static_cast<size_t>(masks);
-  const size_t need = tables_bytes + (gather && out_permutation == nullptr
-                                          ? sizeof(int) * static_cast<size_t>(total_nonzeros) : 0);
-  if (masks < 2 || masks > kMaxGridYZ || heads > kMaxGridYZ || largest_nonzeros <= 0 ||
-      static_cast<int64_t>(ceil_div(largest_nonzeros, kBlock * kManyValuesUnroll)) * max(heads, 1) * masks >=
-          (int64_t{1} << 32) ||
-      n > kColsPerRange || sparse_path(m, n, largest_nonzeros) || chunks > 0x7fffffff / groups ||
-      workspace == nullptr || workspace_bytes < need)
-    return -1;
-  const int64_t region = static_cast<int64_t>(region_bytes / sizeof(int));
+  const bool gather = route.gather;
+  const size_t tables_bytes = route.tables_bytes;
+  const int64_t region = static_cast<int64_t>(route.region_bytes / sizeof(int));
   mask_t* gmask = static_cast<mask_t*>(workspace);
   int* table = reinterpret_cast<int*>(gmask + static_cast<size_t>(chunks) * n);
   int* totals = table + static_cast<size_t>(chunks) * n;
@@ -826,19 +913,17 @@ int sputnik_hip_csr_transpose(int m, int n, int nonzeros, int replicas, const fl
                               int* out_column_indices, int* out_permutation, void* workspace,
                               size_t workspace_bytes, sputnik_hip_stream_t stream) {
   if (m < 0 || n < 0 || nonzeros < 0 || replicas < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (n == 0) {
-    return static_cast<int>(hipMemsetAsync(out_row_offsets, 0, sizeof(int), stream));
-  }
-  if (m == 0 || nonzeros == 0) {
-    return static_cast<int>(
-        hipMemsetAsync(out_row_offsets, 0, sizeof(int) * (static_cast<size_t>(n) + 1), stream));
+  const TransposeRoute route = transpose_route(m, n, nonzeros);
+  if (route.path == kPathNone) {   // an empty dimension or no entries: the offsets alone
+    return static_cast<int>(hipMemsetAsync(
+        out_row_offsets, 0, sizeof(int) * (n == 0 ? size_t{1} : static_cast<size_t>(n) + 1), stream));
   }
   if (workspace == nullptr ||
       workspace_bytes < sputnik_hip_csr_transpose_workspace_bytes(m, n, nonzeros))
     return SPUTNIK_HIP_INVALID_ARGUMENT;
 
   int* status = reinterpret_cast<int*>(static_cast<char*>(workspace) + status_offset(m, n, nonzeros));
-  if (sparse_path(m, n, nonzeros)) {
+  if (route.path == kPathSparse) {
     int* counts = static_cast<int*>(workspace);
     int* cursor = counts + n;
     int* tmp_row = cursor + n;
@@ -858,7 +943,7 @@ int sputnik_hip_csr_transpose(int m, int n, int nonzeros, int replicas, const fl
     hipLaunchKernelGGL(transpose_sparse_rank_kernel, dim3(ceil_div(n, kWaves)), dim3(kBlock), 0,
                        stream, n, out_row_offsets, tmp_row, tmp_src, out_column_indices, perm,
                        status);
-    if (nonzeros > kLongColumn)   // (a workgroup per output row; all but the long rows leave at once)
+    if (route.long_rank_launch)
       hipLaunchKernelGGL(transpose_sparse_rank_long_kernel, dim3(n), dim3(kBlock), 0, stream, m,
                          out_row_offsets, tmp_row, tmp_src, out_column_indices, perm, status);
     hipLaunchKernelGGL(transpose_sparse_values_kernel<float>, dim3(ceil_div(nonzeros, kBlock)),
@@ -866,17 +951,15 @@ int sputnik_hip_csr_transpose(int m, int n, int nonzeros, int replicas, const fl
                        out_values, out_values_stride);
     return launch_status();
   }
-  const int chunks = chunks_of(m);
-  const int ranges = ceil_div(n, kColsPerRange);
-  if (ranges > kMaxGridYZ) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (route.status != 0) return route.status;
+  const int chunks = route.chunks;
+  const int ranges = route.ranges;
   mask_t* gmask = static_cast<mask_t*>(workspace);
   int* table = reinterpret_cast<int*>(gmask + static_cast<size_t>(chunks) * n);
   int* totals = table + static_cast<size_t>(chunks) * n;
   int* balances = totals + n;
   const size_t range_cols = static_cast<size_t>(min(n, kColsPerRange));
   const size_t lds_bytes = sizeof(mask_t) * range_cols;
-  const int groups = column_groups(n);
-  const bool grouped = ranges == 1 && chunks <= 0x7fffffff / groups;
 
   hipLaunchKernelGGL(transpose_mask_kernel, dim3(chunks, ranges), dim3(kMaskBlock), lds_bytes,
                      stream, m, n, row_offsets, column_indices, gmask, balances, int64_t{0});
@@ -887,29 +970,59 @@ int sputnik_hip_csr_transpose(int m, int n, int nonzeros, int replicas, const fl
                      chunks * ranges, status, int64_t{0});
   st = launch_status();
   if (st != 0) return st;
-  if (grouped) {
-    hipLaunchKernelGGL(transpose_scatter_grouped_kernel, dim3(chunks * groups), dim3(kGroupBlock),
-                       0, stream, m, n, groups, replicas, values, values_stride, row_offsets,
-                       column_indices, gmask, table, totals, out_row_offsets,
-                       out_values, out_values_stride, out_column_indices, out_permutation,
-                       int64_t{0});
+  if (route.path == kPathGrouped) {
+    hipLaunchKernelGGL(transpose_scatter_grouped_kernel, dim3(chunks * route.groups),
+                       dim3(kGroupBlock), 0, stream, m, n, route.groups, replicas, values,
+                       values_stride, row_offsets, column_indices, gmask, table, totals,
+                       out_row_offsets, out_values, out_values_stride, out_column_indices,
+                       out_permutation, int64_t{0});
     return launch_status();
   }
   hipLaunchKernelGGL(transpose_scan_totals_kernel, dim3(1), dim3(kScanBlock), 0, stream, n,
                      totals, out_row_offsets);
   st = launch_status();
   if (st != 0) return st;
-  // Workgroups per chunk in the plain scatter: enough for about two per CU (the
-  // chunk's 32 rows split into parts of 16 / 8 / 4).
-  int parts = 1;
-  while (parts < 8 && static_cast<int64_t>(chunks) * ranges * parts < 512) parts *= 2;
-  if (chunks > 0x7fffffff / parts) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const int parts = route.parts;
   hipLaunchKernelGGL(transpose_scatter_kernel, dim3(chunks * parts, ranges), dim3(kBlock),
                      lds_bytes + sizeof(int) * range_cols, stream, m, n, parts,
                      kRowsPerChunk / parts, replicas, values, values_stride, row_offsets,
                      column_indices, gmask, table, out_row_offsets, out_values, out_values_stride,
                      out_column_indices, out_permutation);
   return launch_status();
+}
+
+int sputnik_hip_csr_transpose_route(int m, int n, int nonzeros, int* path, int* chunks, int* ranges,
+                                    int* groups, int* parts, int* scan_chunks_per_group,
+                                    int* long_rank_launch) {
+  const TransposeRoute r = transpose_route(m, n, nonzeros);
+  if (r.status != 0) return r.status;
+  if (path) *path = r.path;
+  if (chunks) *chunks = r.chunks;
+  if (ranges) *ranges = r.ranges;
+  if (groups) *groups = r.groups;
+  if (parts) *parts = r.parts;
+  if (scan_chunks_per_group) *scan_chunks_per_group = r.scan_chunks_per_group;
+  if (long_rank_launch) *long_rank_launch = r.long_rank_launch;
+  return 0;
+}
+
+int sputnik_hip_csr_transpose_many_mask_route(int masks, int m, int n, int largest_nonzeros,
+                                              int64_t total_nonzeros, int heads,
+                                              int with_permutation, size_t workspace_bytes,
+                                              int* one_launch, int* values_by) {
+  if (masks < 0 || m < 0 || n < 0 || largest_nonzeros < 0 || total_nonzeros < 0 || heads < 0)
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const TransposeManyRoute r =
+      csr_transpose_many_route(masks, m, n, largest_nonzeros, total_nonzeros, heads,
+                               with_permutation != 0, workspace_bytes > 0, workspace_bytes,
+                               /*value_row_width=*/INT64_MAX);
+  if (one_launch) *one_launch = r.one_launch;
+  if (values_by)
+    *values_by = !r.one_launch ? -1
+                 : heads == 0  ? SPUTNIK_HIP_MANY_VALUES_NONE
+                 : r.gather    ? SPUTNIK_HIP_MANY_VALUES_GATHER
+                               : SPUTNIK_HIP_MANY_VALUES_SCATTER;
+  return 0;
 }
 
 int sputnik_hip_csr_transpose_checked(int m, int n, int nonzeros, int replicas,
