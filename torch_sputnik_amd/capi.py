@@ -736,22 +736,101 @@ def sparse_attention_workspace_bytes(m, n, d, nonzeros):
     return lib().sputnik_hip_sparse_attention_workspace_bytes(m, n, d, nonzeros)
 
 
+def _drop(p, rng, rng_state_out):
+    """The (p, state, rng_state_out) arguments of a `_dropout` entry point, or () for the form
+    without them: no state and no output given.  `rng`: a PhiloxState, or (seed, offset)."""
+    if rng is None and rng_state_out is None:
+        if p:
+            raise ValueError("dropout needs a Philox state: rng=PhiloxState(...) or (seed, offset)")
+        return ()
+    if rng is None:
+        rng = PhiloxState()
+    elif not isinstance(rng, PhiloxState):
+        rng = PhiloxState(seed=int(rng[0]), offset=int(rng[1]))
+    return (float(p), rng, _ptr(rng_state_out))
+
+
+def _float_attention_operands(m, n, d, column_indices, q_stride, k_stride, v_stride, out_stride,
+                              lse_stride, nonzeros):
+    """The defaults of the float32 attention forms: replicas follow each other (q and out
+    m * d, k and v n * d, lse m elements apart) and every entry of column_indices is meant."""
+    return (column_indices.numel() if nonzeros is None else int(nonzeros), _stride(q_stride, m * d),
+            _stride(k_stride, n * d), _stride(v_stride, n * d), _stride(out_stride, m * d),
+            _stride(lse_stride, m))
+
+
 def sparse_attention_forward(m, n, d, replicas, row_indices, row_offsets, column_indices, q, k, v,
-                             scale, out, lse=None, workspace=None):
-    """Fused softmax(scale * q k^T at the mask) v.  q [R,m,d], k and v [R,n,d]."""
-    nonzeros = column_indices.numel()
+                             scale, out, lse=None, workspace=None, *, q_stride=None, k_stride=None,
+                             v_stride=None, out_stride=None, lse_stride=None, nonzeros=None, p=0.0,
+                             rng=None, rng_state_out=None):
+    """Fused softmax(scale * q k^T at the mask) v.  q [R,m,d], k and v [R,n,d].  Replica r of an
+    operand begins r * its stride elements into the tensor (default: the replicas follow each
+    other); `rng` or `rng_state_out` select the `_dropout` form (p = 0: nothing is dropped)."""
+    nonzeros, qs, ks, vs, os_, ls = _float_attention_operands(
+        m, n, d, column_indices, q_stride, k_stride, v_stride, out_stride, lse_stride, nonzeros)
     for t, dt, nm in ((row_indices, torch.int32, "row_indices"),
                       (row_offsets, torch.int32, "row_offsets"),
                       (column_indices, torch.int32, "column_indices"), (q, torch.float32, "q"),
                       (k, torch.float32, "k"), (v, torch.float32, "v"),
                       (out, torch.float32, "out")):
         _require(t, dt, nm)
-    _check(lib().sputnik_hip_sparse_attention_forward(
+    drop = _drop(p, rng, rng_state_out)
+    name = "sputnik_hip_sparse_attention_forward" + ("_dropout" if drop else "")
+    _check(getattr(lib(), name)(
         m, n, d, nonzeros, replicas, _ptr(row_indices), _ptr(row_offsets), _ptr(column_indices),
-        _ptr(q), m * d, _ptr(k), n * d, _ptr(v), n * d, float(scale), _ptr(out), m * d, _ptr(lse),
-        m, _ptr(workspace), _ws_bytes(workspace), _stream(out)),
-        "sputnik_hip_sparse_attention_forward")
+        _ptr(q), qs, _ptr(k), ks, _ptr(v), vs, float(scale), _ptr(out), os_, _ptr(lse), ls, *drop,
+        _ptr(workspace), _ws_bytes(workspace), _stream(out)), name)
     return out
+
+
+def sparse_attention_rows_supported(m, n, d, nonzeros):
+    return bool(lib().sputnik_hip_sparse_attention_rows_supported(m, n, d, nonzeros))
+
+
+def sparse_attention_rows_forward(m, n, d, replicas, row_indices, row_offsets, column_indices, q, k,
+                                  v, scale, out, lse=None, *, q_stride=None, k_stride=None,
+                                  v_stride=None, out_stride=None, lse_stride=None, nonzeros=None,
+                                  p=0.0, rng=None, rng_state_out=None):
+    """The row-group forward (d = 128): sparse_attention_forward's arguments without a
+    workspace.  Returns the library's status."""
+    nonzeros, qs, ks, vs, os_, ls = _float_attention_operands(
+        m, n, d, column_indices, q_stride, k_stride, v_stride, out_stride, lse_stride, nonzeros)
+    drop = _drop(p, rng, rng_state_out) or (0.0, PhiloxState(), None)
+    return lib().sputnik_hip_sparse_attention_rows_forward(
+        m, n, d, nonzeros, replicas, _ptr(row_indices), _ptr(row_offsets), _ptr(column_indices),
+        _ptr(q), qs, _ptr(k), ks, _ptr(v), vs, float(scale), _ptr(out), os_, _ptr(lse), ls, *drop,
+        _stream(out))
+
+
+def sparse_attention_backward_supported(m, n, d, nonzeros):
+    return bool(lib().sputnik_hip_sparse_attention_backward_supported(m, n, d, nonzeros))
+
+
+def sparse_attention_backward_workspace_bytes(m, n, d, nonzeros, replicas):
+    return lib().sputnik_hip_sparse_attention_backward_workspace_bytes(m, n, d, nonzeros, replicas)
+
+
+def sparse_attention_backward(m, n, d, replicas, row_indices, row_offsets, column_indices,
+                              t_row_indices, t_row_offsets, t_column_indices, permutation, q, k, v,
+                              scale, out, grad_out, lse, grad_q, grad_k, grad_v, workspace, *,
+                              q_stride=None, k_stride=None, v_stride=None, out_stride=None,
+                              grad_out_stride=None, lse_stride=None, grad_q_stride=None,
+                              grad_k_stride=None, grad_v_stride=None, nonzeros=None, p=0.0, rng=None):
+    """sputnik_hip_sparse_attention_backward: any of grad_q, grad_k, grad_v may be None; one
+    stride per operand as in sparse_attention_forward.  `rng` replays the forward's dropout:
+    a PhiloxState (values, or seed_ptr / offset_ptr into a published rng_state_out) or
+    (seed, offset).  Returns the library's status."""
+    nonzeros, qs, ks, vs, os_, ls = _float_attention_operands(
+        m, n, d, column_indices, q_stride, k_stride, v_stride, out_stride, lse_stride, nonzeros)
+    drop = _drop(p, rng, None) or (0.0, PhiloxState())
+    first = next(t for t in (grad_q, grad_k, grad_v, q) if t is not None)
+    return lib().sputnik_hip_sparse_attention_backward(
+        m, n, d, nonzeros, replicas, _ptr(row_indices), _ptr(row_offsets), _ptr(column_indices),
+        _ptr(t_row_indices), _ptr(t_row_offsets), _ptr(t_column_indices), _ptr(permutation),
+        _ptr(q), qs, _ptr(k), ks, _ptr(v), vs, float(scale), _ptr(out), os_, _ptr(grad_out),
+        _stride(grad_out_stride, m * d), _ptr(lse), ls, _ptr(grad_q), _stride(grad_q_stride, m * d),
+        _ptr(grad_k), _stride(grad_k_stride, n * d), _ptr(grad_v), _stride(grad_v_stride, n * d),
+        drop[0], drop[1], _ptr(workspace), _ws_bytes(workspace), _stream(first))
 
 
 def _head_view(t):
@@ -773,17 +852,21 @@ def sparse_attention_heads_workspace_bytes(m, n, d, nonzeros):
 
 
 def sparse_attention_heads_forward(m, n, d, row_indices, row_offsets, column_indices, q, k, v, scale, out,
-                                   lse=None, workspace=None, planned=False):
+                                   lse=None, workspace=None, planned=False, *, lse_stride=None,
+                                   nonzeros=None, p=0.0, rng=None, rng_state_out=None):
     """Fused attention on float16 / bfloat16 head views q [B,H,m,d], k and v [B,H,n,d] into the
-    view `out` (float32 or the operands' type); lse [B*H, m] float32 or None.  `planned`: the
-    workspace holds sputnik_hip_sparse_attention_plan's pre-pass."""
-    fn = (lib().sputnik_hip_sparse_attention_heads_forward_planned if planned
-          else lib().sputnik_hip_sparse_attention_heads_forward)
-    _check(fn(m, n, d, column_indices.numel(), q.size(0), q.size(1), _ptr(row_indices), _ptr(row_offsets),
-              _ptr(column_indices), TYPE_CODES[q.dtype], *_head_view(q), *_head_view(k), *_head_view(v),
-              float(scale), _ptr(out), TYPE_CODES[out.dtype], *_head_view(out)[1:], _ptr(lse), m,
-              _ptr(workspace), _ws_bytes(workspace), _stream(out)),
-           "sputnik_hip_sparse_attention_heads_forward")
+    view `out` (float32 or the operands' type); lse [B*H, lse_stride] float32 or None.
+    `planned`: the workspace holds sputnik_hip_sparse_attention_plan's pre-pass; `rng` or
+    `rng_state_out`: the `_dropout` form."""
+    drop = _drop(p, rng, rng_state_out)
+    name = ("sputnik_hip_sparse_attention_heads_forward" + ("_planned" if planned else "")
+            + ("_dropout" if drop else ""))
+    _check(getattr(lib(), name)(
+        m, n, d, column_indices.numel() if nonzeros is None else int(nonzeros), q.size(0), q.size(1),
+        _ptr(row_indices), _ptr(row_offsets), _ptr(column_indices), TYPE_CODES[q.dtype], *_head_view(q),
+        *_head_view(k), *_head_view(v), float(scale), _ptr(out), TYPE_CODES[out.dtype],
+        *_head_view(out)[1:], _ptr(lse), _stride(lse_stride, m), *drop, _ptr(workspace),
+        _ws_bytes(workspace), _stream(out)), name)
     return out
 
 
@@ -803,30 +886,41 @@ def sparse_attention_many_mask_plan(masks, m, n, d, nonzeros, row_indices, row_o
 
 def sparse_attention_many_mask_forward(masks, m, n, d, nonzeros, replicas, row_indices, row_offsets,
                                        column_indices, q, k, v, scale, out, lse=None, workspace=None,
-                                       planned=False):
-    """q [R,m,d], k and v [R,n,d] float32 (contiguous), replica r under mask r // (R // masks);
-    lse [R, m] or None.  `planned`: the workspace holds the plan of
-    sparse_attention_many_mask_plan."""
+                                       planned=False, *, q_stride=None, k_stride=None, v_stride=None,
+                                       out_stride=None, lse_stride=None, p=0.0, rng=None,
+                                       rng_state_out=None):
+    """q [R,m,d], k and v [R,n,d] float32, replica r under mask r // (R // masks); lse
+    [R, lse_stride] or None; one stride per operand as in sparse_attention_forward.  `planned`:
+    the workspace holds the plan of sparse_attention_many_mask_plan; `rng` or `rng_state_out`:
+    the `_dropout` form."""
     arr, _ = _host_counts(nonzeros)
-    fn = (lib().sputnik_hip_sparse_attention_many_mask_forward_planned if planned
-          else lib().sputnik_hip_sparse_attention_many_mask_forward)
-    return fn(masks, m, n, d, arr, replicas, _ptr(row_indices), _ptr(row_offsets), _ptr(column_indices),
-              _ptr(q), m * d, _ptr(k), n * d, _ptr(v), n * d, float(scale), _ptr(out), m * d, _ptr(lse), m,
-              _ptr(workspace), _ws_bytes(workspace), _stream(out))
+    _, qs, ks, vs, os_, ls = _float_attention_operands(
+        m, n, d, column_indices, q_stride, k_stride, v_stride, out_stride, lse_stride, 0)
+    drop = _drop(p, rng, rng_state_out)
+    name = ("sputnik_hip_sparse_attention_many_mask_forward" + ("_planned" if planned else "")
+            + ("_dropout" if drop else ""))
+    return getattr(lib(), name)(
+        masks, m, n, d, arr, replicas, _ptr(row_indices), _ptr(row_offsets), _ptr(column_indices),
+        _ptr(q), qs, _ptr(k), ks, _ptr(v), vs, float(scale), _ptr(out), os_, _ptr(lse), ls, *drop,
+        _ptr(workspace), _ws_bytes(workspace), _stream(out))
 
 
 def sparse_attention_heads_many_mask_forward(masks, m, n, d, nonzeros, row_indices, row_offsets,
                                              column_indices, q, k, v, scale, out, lse=None,
-                                             workspace=None, planned=False):
+                                             workspace=None, planned=False, *, lse_stride=None,
+                                             p=0.0, rng=None, rng_state_out=None):
     """Half head views q [B,H,m,d], k and v [B,H,n,d], batch element b under mask b, into the view
-    `out` (float32 or the operands' type); lse [B*H, m] float32 or None."""
+    `out` (float32 or the operands' type); lse [B*H, lse_stride] float32 or None.  `rng` or
+    `rng_state_out`: the `_dropout` form."""
     arr, _ = _host_counts(nonzeros)
-    fn = (lib().sputnik_hip_sparse_attention_heads_many_mask_forward_planned if planned
-          else lib().sputnik_hip_sparse_attention_heads_many_mask_forward)
-    return fn(masks, m, n, d, arr, q.size(0), q.size(1), _ptr(row_indices), _ptr(row_offsets),
-              _ptr(column_indices), TYPE_CODES[q.dtype], *_head_view(q), *_head_view(k), *_head_view(v),
-              float(scale), _ptr(out), TYPE_CODES[out.dtype], *_head_view(out)[1:], _ptr(lse), m,
-              _ptr(workspace), _ws_bytes(workspace), _stream(out))
+    drop = _drop(p, rng, rng_state_out)
+    name = ("sputnik_hip_sparse_attention_heads_many_mask_forward" + ("_planned" if planned else "")
+            + ("_dropout" if drop else ""))
+    return getattr(lib(), name)(
+        masks, m, n, d, arr, q.size(0), q.size(1), _ptr(row_indices), _ptr(row_offsets),
+        _ptr(column_indices), TYPE_CODES[q.dtype], *_head_view(q), *_head_view(k), *_head_view(v),
+        float(scale), _ptr(out), TYPE_CODES[out.dtype], *_head_view(out)[1:], _ptr(lse),
+        _stride(lse_stride, m), *drop, _ptr(workspace), _ws_bytes(workspace), _stream(out))
 
 
 def sparse_linear_half_rows_forward(out_features, image, values_dtype, x, y):
@@ -1025,13 +1119,19 @@ def sparse_attention_plan(m, n, d, row_indices, row_offsets, column_indices, wor
 
 
 def sparse_attention_forward_planned(m, n, d, replicas, row_indices, row_offsets, column_indices,
-                                     q, k, v, scale, out, lse, workspace):
-    nonzeros = column_indices.numel()
-    _check(lib().sputnik_hip_sparse_attention_forward_planned(
+                                     q, k, v, scale, out, lse, workspace, *, q_stride=None,
+                                     k_stride=None, v_stride=None, out_stride=None, lse_stride=None,
+                                     nonzeros=None, p=0.0, rng=None, rng_state_out=None):
+    """sparse_attention_forward on a workspace that holds sparse_attention_plan's pre-pass (the
+    same keywords)."""
+    nonzeros, qs, ks, vs, os_, ls = _float_attention_operands(
+        m, n, d, column_indices, q_stride, k_stride, v_stride, out_stride, lse_stride, nonzeros)
+    drop = _drop(p, rng, rng_state_out)
+    name = "sputnik_hip_sparse_attention_forward_planned" + ("_dropout" if drop else "")
+    _check(getattr(lib(), name)(
         m, n, d, nonzeros, replicas, _ptr(row_indices), _ptr(row_offsets), _ptr(column_indices),
-        _ptr(q), m * d, _ptr(k), n * d, _ptr(v), n * d, float(scale), _ptr(out), m * d, _ptr(lse),
-        m, _ptr(workspace), _ws_bytes(workspace), _stream(out)),
-        "sputnik_hip_sparse_attention_forward_planned")
+        _ptr(q), qs, _ptr(k), ks, _ptr(v), vs, float(scale), _ptr(out), os_, _ptr(lse), ls, *drop,
+        _ptr(workspace), _ws_bytes(workspace), _stream(out)), name)
     return out
 
 
