@@ -973,3 +973,49 @@ def test_permute_last_matches_index_select(dev, rows, n):
     perm = torch.randperm(n, device=dev, generator=g).to(torch.int32)
     assert torch.equal(ops.permute_last(values, perm), values.index_select(-1, perm.long()))
     assert torch.equal(ops.permute_last(values[0].contiguous(), perm), values[0][perm.long()])
+
+
+# ----------------------------------------------------------------------------
+# SDDMM across the 65535-replica limit of a grid dimension
+# ----------------------------------------------------------------------------
+@pytest.mark.parametrize("kernel,dtype,name", [
+    ("wave", torch.float32, "sddmm_rowwave_kernel"),
+    ("tiled", torch.float32, "sddmm_quad_kernel"),
+    ("tiled", torch.float16, "sddmm_quad_kernel")])
+def test_sddmm_beyond_65535_replicas(capi, dev, monkeypatch, kernel, dtype, name):
+    """65537 replicas: the launchers cut the replicas into slices of at most 65535 (a grid
+    dimension's limit), the second slice starting at replica 65535.  Replicas 0 .. 65534 hold
+    the same operands and must agree bit for bit; 65535 and 65536, the second slice, hold their
+    own.  Against a float64 product of the (rounded) operands."""
+    m = n = 16
+    k, replicas = 64, 65537
+    ro = np.arange(m + 1, dtype=np.int32) * 4
+    ci = np.sort((np.arange(m)[:, None] + np.array([0, 3, 7, 12])) % n, axis=1).astype(np.int32).ravel()
+    ri = np.arange(m, dtype=np.int32)
+    rng = np.random.default_rng(65537)
+    distinct = (0, replicas - 2, replicas - 1)
+    lhs3 = torch.from_numpy(rng.uniform(-1, 1, size=(3, m, k)).astype(np.float32)).to(dtype)
+    rhs3 = torch.from_numpy(rng.uniform(-1, 1, size=(3, n, k)).astype(np.float32)).to(dtype)
+    rows = np.repeat(np.arange(m), 4)
+    want = np.einsum("rpk,rpk->rp", lhs3.double().numpy()[:, rows], rhs3.double().numpy()[:, ci])
+
+    def operand(three):
+        x = three[0].to(dev).expand(replicas, -1, -1).contiguous()
+        x[replicas - 2:] = three[1:].to(dev)
+        return x
+    lhs, rhs = operand(lhs3), operand(rhs3)
+    out = torch.full((replicas, len(ci)), float("nan"), device=dev)
+    ws = torch.empty(capi.sddmm_workspace_bytes(m, k, n, len(ci)) + 16, dtype=torch.uint8, device=dev)
+    monkeypatch.setenv("SPUTNIK_HIP_SDDMM_KERNEL", kernel)
+    capi.reload_options()
+    try:
+        assert capi.sddmm_kernel_name(m, k, n, len(ci), replicas, lhs.element_size()) == name
+        capi.sddmm_typed(m, k, n, replicas, T(ri, dev), T(ro, dev), T(ci, dev), lhs, rhs, out, ws)
+        torch.cuda.synchronize()
+    finally:
+        monkeypatch.delenv("SPUTNIK_HIP_SDDMM_KERNEL", raising=False)
+        capi.reload_options()
+    got = out[list(distinct)].cpu().numpy()
+    assert not np.isnan(got).any()
+    assert rel_err(got, want, ro) < TOL
+    assert torch.equal(out[1:replicas - 2], out[:1].expand(replicas - 3, -1))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where the LDS-tiled SDDMM (pre-pass + stationary kernel) overtakes the row-wave kernel
 (one launch): both forced through SPUTNIK_HIP_SDDMM_KERNEL, per-call form (the pre-pass
-inside the call), and what the automatic rule picks (csrc/sddmm.hip, takes_tiled).
+inside the call), and what the automatic rule picks (csrc/sddmm.hip, plain_route).
 
     python tools/small_sddmm.py [--summed] [--half]      (--half: float16 operands; --summed: the form summed over the replicas,
                                                  the weight gradient of a layer: sddmm_sum_batched)

@@ -16,13 +16,13 @@
 #include <algorithm>
 
 #include "common.h"
+#include "sddmm_tiled.h"
 
 namespace sputnik_hip {
 int softmax_many_mask(bool backward, int m, int width, int largest_nonzeros, int replicas, int heads,
                       const float* a, int64_t a_stride, const float* b, int64_t b_stride,
                       const int* row_offsets, float* out, int64_t out_stride, float scale,
                       hipStream_t stream, int masks, const int* mask_nonzeros);
-size_t sddmm_tiled_workspace_bytes(int m, int k, int n, int nonzeros, bool summed);
 bool spmm_panel_applicable(int m, int k, int n, int nonzeros, const float* dense,
                            int64_t dense_stride, const float* out, int64_t out_stride);
 int spmm_panel_launch(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,

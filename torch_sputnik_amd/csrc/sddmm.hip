@@ -16,56 +16,10 @@
 #include "common.h"
 #include "mfma.h"
 #include "options.h"
+#include "sddmm_tiled.h"
 #include "wave_utils.h"
 
 namespace sputnik_hip {
-
-bool sddmm_tiled_applicable(int m, int k, int n, int nonzeros, const float* lhs,
-                            int64_t lhs_stride, const float* rhs, int64_t rhs_stride);
-size_t sddmm_tiled_workspace_bytes(int m, int k, int n, int nonzeros, bool summed = false);
-int sddmm_tiled_plan(int m, int k, int n, int nonzeros, const int* row_indices,
-                     const int* row_offsets, const int* column_indices, void* workspace,
-                     hipStream_t stream, bool summed = false, bool with_flat = false, int masks = 1,
-                     int64_t mask_plan_ints = 0);
-int sddmm_tiled_launch(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
-                       const int* row_offsets, const int* column_indices, const float* lhs,
-                       int64_t lhs_stride, const float* rhs, int64_t rhs_stride, float* out,
-                       int64_t out_stride, const void* workspace, hipStream_t stream,
-                       int mask_heads = 0, int64_t mask_plan_ints = 0, bool flat = false);
-// Bytes between the plans of consecutive masks in a "many mask" workspace.
-// (the last word of a region is spare: the masks' start order, mask_start_word)
-inline size_t sddmm_many_mask_plan_bytes(int m, int k, int n, int nonzeros) {
-  return (sddmm_tiled_workspace_bytes(m, k, n, nonzeros) + sizeof(int) + 255) / 256 * 256;
-}
-
-int sddmm_tiled_panels(int m, int k, int n, int nonzeros);
-bool sddmm_flat_applicable(int m, int k, int n, int nonzeros, int elem_bytes);   // sddmm_flat.hip
-int sddmm_tiled_panel_width(int k);
-int sddmm_tiled_slab_rows(int k);                                  // of the plain product's plan
-int sddmm_tiled_sum_slab_rows(int m, int k, int n, int nonzeros);  // of the summed form's plan
-int sddmm_tiled_launch_partials(int m, int k, int n, int nonzeros, int replicas,
-                                const int* row_indices, const int* row_offsets,
-                                const int* column_indices, const float* lhs, int64_t lhs_stride,
-                                const float* rhs, int64_t rhs_stride, float* partials,
-                                const void* workspace, hipStream_t stream);
-
-// native half operands (sddmm_tiled.hip)
-bool sddmm_tiled_applicable_half(int m, int k, int n, int nonzeros, const void* lhs,
-                                 int64_t lhs_stride, const void* rhs, int64_t rhs_stride);
-int sddmm_tiled_passes_half(int k);
-int sddmm_tiled_launch_half(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
-                            const int* row_offsets, const int* column_indices, const void* lhs,
-                            int64_t lhs_stride, const void* rhs, int64_t rhs_stride, void* out,
-                            int64_t out_stride, int in_type, int out_type, const void* workspace,
-                            hipStream_t stream, int mask_heads = 0, int64_t mask_plan_ints = 0,
-                            bool flat = false);
-bool sddmm_tiled_sum_half_served(int m, int k, int n, int nonzeros);
-int sddmm_tiled_launch_partials_half(int m, int k, int n, int nonzeros, int replicas,
-                                     const int* row_indices, const int* row_offsets,
-                                     const int* column_indices, const void* lhs,
-                                     int64_t lhs_stride, const void* rhs, int64_t rhs_stride,
-                                     int in_type, float* partials, const void* workspace,
-                                     hipStream_t stream);
 
 namespace {
 
@@ -185,41 +139,33 @@ __global__ __launch_bounds__(kBlock) void sddmm_rowwave_kernel(
 }
 
 template <typename T, typename TO, int VEC, int LPN, int KSL>
-int launch(int m, int k, int replicas, const int* row_indices, const int* row_offsets,
-           const int* column_indices, const T* lhs, int64_t lhs_stride, const T* rhs,
-           int64_t rhs_stride, TO* out, int64_t out_stride, hipStream_t stream,
-           int mask_heads) {
-  const int gx = ceil_div(m, kWavesPerBlock);
-  for (int r0 = 0; r0 < replicas; r0 += kMaxGridYZ) {
-    const int ry = min(replicas - r0, kMaxGridYZ);
+int launch(const SddmmArgs& a) {
+  const T* lhs = static_cast<const T*>(a.lhs);
+  const T* rhs = static_cast<const T*>(a.rhs);
+  TO* out = static_cast<TO*>(a.out);
+  const int gx = ceil_div(a.m, kWavesPerBlock);
+  for (int r0 = 0; r0 < a.replicas; r0 += kMaxGridYZ) {
+    const int ry = min(a.replicas - r0, kMaxGridYZ);
     hipLaunchKernelGGL((sddmm_rowwave_kernel<T, TO, VEC, LPN, KSL>), dim3(gx, ry), dim3(kBlock), 0,
-                       stream, m, k, row_indices, row_offsets, column_indices,
-                       lhs + r0 * lhs_stride, lhs_stride, rhs + r0 * rhs_stride, rhs_stride,
-                       out + r0 * out_stride, out_stride, mask_heads, r0);
+                       a.stream, a.m, a.k, a.row_indices, a.row_offsets, a.column_indices,
+                       lhs + r0 * a.lhs_stride, a.lhs_stride, rhs + r0 * a.rhs_stride, a.rhs_stride,
+                       out + r0 * a.out_stride, a.out_stride, a.mask_heads, r0);
     const int st = launch_status();
     if (st != 0) return st;
   }
   return 0;
 }
 
-template <int VEC, typename T = float, typename TO = float>
-int launch_vec(int m, int k, int replicas, const int* row_indices, const int* row_offsets,
-               const int* column_indices, const T* lhs, int64_t lhs_stride, const T* rhs,
-               int64_t rhs_stride, TO* out, int64_t out_stride, hipStream_t stream,
-               int mask_heads = 0) {
-  const int lanes = ceil_div(k, VEC);
-#define SPUTNIK_HIP_SD(LPN, KSL)                                                                \
-  return launch<T, TO, VEC, LPN, KSL>(m, k, replicas, row_indices, row_offsets, column_indices, \
-                                      lhs, lhs_stride, rhs, rhs_stride, out, out_stride, stream, \
-                                      mask_heads)
-  if (lanes <= 4) SPUTNIK_HIP_SD(4, 1);
-  if (lanes <= 8) SPUTNIK_HIP_SD(8, 1);
-  if (lanes <= 16) SPUTNIK_HIP_SD(16, 1);
-  if (lanes <= 32) SPUTNIK_HIP_SD(32, 1);
-  if (lanes <= 64) SPUTNIK_HIP_SD(64, 1);
-  if (lanes <= 128) SPUTNIK_HIP_SD(64, 2);
-  SPUTNIK_HIP_SD(64, 4);
-#undef SPUTNIK_HIP_SD
+template <typename T, typename TO, int VEC>
+int launch_vec(const SddmmArgs& a) {
+  const int lanes = ceil_div(a.k, VEC);
+  if (lanes <= 4) return launch<T, TO, VEC, 4, 1>(a);
+  if (lanes <= 8) return launch<T, TO, VEC, 8, 1>(a);
+  if (lanes <= 16) return launch<T, TO, VEC, 16, 1>(a);
+  if (lanes <= 32) return launch<T, TO, VEC, 32, 1>(a);
+  if (lanes <= 64) return launch<T, TO, VEC, 64, 1>(a);
+  if (lanes <= 128) return launch<T, TO, VEC, 64, 2>(a);
+  return launch<T, TO, VEC, 64, 4>(a);
 }
 
 // out[i] = partials[0][i] + partials[1][i] + ... in that order (deterministic).
@@ -287,23 +233,20 @@ int vector_width_of(const void* p, int64_t width, int64_t stride, size_t elem) {
   return 1;
 }
 
-// Row-wave kernel on half operands.  single: the whole k in one panel (64 lanes x VEC x 4).
+// Widest vector both operands support, in elements of their storage type.  (For float32
+// this is vector_width of common.h: 4 and 2 elements are 16 and 8 bytes.)
+int rowwave_vec(const SddmmArgs& a) {
+  const size_t elem = sddmm_elem_bytes(a.in_type);
+  return min(vector_width_of(a.lhs, a.k, a.lhs_stride, elem), vector_width_of(a.rhs, a.k, a.rhs_stride, elem));
+}
+
+// The row-wave kernel on operands of type T, output TO.
 template <typename T, typename TO>
-int rowwave_half(int m, int k, int replicas, const int* row_indices, const int* row_offsets,
-                 const int* column_indices, const void* lhs, int64_t lhs_stride, const void* rhs,
-                 int64_t rhs_stride, void* out, int64_t out_stride, hipStream_t stream) {
-  const T* l = static_cast<const T*>(lhs);
-  const T* r = static_cast<const T*>(rhs);
-  TO* o = static_cast<TO*>(out);
-  const int vec = min(vector_width_of(lhs, k, lhs_stride, sizeof(T)),
-                      vector_width_of(rhs, k, rhs_stride, sizeof(T)));
-  switch (vec) {
-    case 4: return launch_vec<4, T, TO>(m, k, replicas, row_indices, row_offsets, column_indices, l,
-                                        lhs_stride, r, rhs_stride, o, out_stride, stream);
-    case 2: return launch_vec<2, T, TO>(m, k, replicas, row_indices, row_offsets, column_indices, l,
-                                        lhs_stride, r, rhs_stride, o, out_stride, stream);
-    default: return launch_vec<1, T, TO>(m, k, replicas, row_indices, row_offsets, column_indices, l,
-                                         lhs_stride, r, rhs_stride, o, out_stride, stream);
+int rowwave(const SddmmArgs& a) {
+  switch (rowwave_vec(a)) {
+    case 4: return launch_vec<T, TO, 4>(a);
+    case 2: return launch_vec<T, TO, 2>(a);
+    default: return launch_vec<T, TO, 1>(a);
   }
 }
 
@@ -372,25 +315,14 @@ bool float_call_is_small(int m, int k, int n, int nonzeros, int replicas, bool p
   return tiled >= wave;
 }
 
-// The SHAPE part of that choice (the knob, then the two estimates): what the launch paths
-// below and the name / route queries at the end of this file share.  The operands' alignment
-// and the workspace's size are the caller's to add.
+// The SHAPE part of that choice (the knob, then the two estimates).  The operands' alignment
+// and the workspace's size are added by plain_route and sum_route below.
 bool wants_tiled(int m, int k, int n, int nonzeros, int replicas /* < 0: unknown */, bool planned,
                  bool summed) {
   const bool force_tiled = options().sddmm_kernel == 1;
   const bool force_wave = options().sddmm_kernel == 2;
   const bool small = replicas >= 0 && float_call_is_small(m, k, n, nonzeros, replicas, planned, summed);
   return !force_wave && (force_tiled || !small);
-}
-
-bool takes_tiled(int m, int k, int n, int nonzeros, int replicas /* < 0: unknown */,
-                 const float* lhs, int64_t lhs_stride, const float* rhs, int64_t rhs_stride,
-                 const void* workspace, size_t workspace_bytes, bool summed = false,
-                 bool planned = false) {
-  return wants_tiled(m, k, n, nonzeros, replicas, planned, summed) && workspace != nullptr &&
-         aligned_to(workspace, 16) &&
-         sddmm_tiled_applicable(m, k, n, nonzeros, lhs, lhs_stride, rhs, rhs_stride) &&
-         workspace_bytes >= sddmm_tiled_workspace_bytes(m, k, n, nonzeros, summed);
 }
 
 // The summed product's vector route: tiled partial vectors, one per (replica, panel), or the
@@ -402,8 +334,9 @@ struct SumRoute {
 };
 SumRoute sum_vector_route(int m, int k, int n, int nonzeros, int replicas, bool half, bool planned,
                           bool tables_usable) {
-  // (the float32 form has always estimated as if its plan were made by the call; the half
-  // form counts a plan made ahead)
+  // (float32: the form has always estimated as if its plan were made by the call; half: it
+  // counts a plan made ahead.  ADVICE.md, "takes_tiled(...) in sddmm_sum_exec is called
+  // without the `planned` flag": kept as it is, passing it changes routes)
   bool tiled = tables_usable && wants_tiled(m, k, n, nonzeros, replicas, half && planned, /*summed=*/true);
   // (the tiled form puts every (replica, panel) pair on grid z: beyond 65535 of them --
   // a SparseLinear weight gradient over a very large batch -- the row-wave kernel, which
@@ -420,118 +353,95 @@ SumRoute sum_vector_route(int m, int k, int n, int nonzeros, int replicas, bool 
   return r;
 }
 
-int sddmm_exec(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
-               const int* row_offsets, const int* column_indices, const float* lhs,
-               int64_t lhs_stride, const float* rhs, int64_t rhs_stride, float* out,
-               int64_t out_stride, void* workspace, size_t workspace_bytes, bool planned,
-               hipStream_t stream, int mask_heads = 0, const int* mask_nonzeros = nullptr) {
-  // mask_heads > 0 ("many mask", many_mask.hip): concatenated topologies, replica r
-  // under number r / mask_heads; `nonzeros` = the largest mask's count (kernel choice
-  // and plan size), mask_nonzeros (host) = every mask's count; `workspace` holds one
-  // plan per mask, sddmm_many_mask_plan_bytes apart.
-  if (m < 0 || k < 0 || n < 0 || nonzeros < 0 || replicas < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (m == 0 || nonzeros == 0 || replicas == 0) return 0;
-  if (k == 0) {
-    for (int r = 0; r < replicas; ++r) {
-      const hipError_t e =
-          hipMemsetAsync(out + r * out_stride, 0, sizeof(float) * static_cast<size_t>(nonzeros), stream);
+// The plain product's route: SddmmKernel::kRowWave, or the kernel sddmm_tiled_launch runs.
+// The one decision of the launch path (sddmm_exec) and of sputnik_hip_sddmm_kernel_name.
+// mask_heads > 0 ("many mask", float32 only): the workspace holds one plan per mask,
+// sddmm_many_mask_plan_bytes apart.  A half OUTPUT needs the product in one pass (later
+// passes would add into rounded values).
+// (the float product's estimates serve half operands too: on the half sweep,
+// tools/small_sddmm.py --half, the one-number rule left 17 % mean regret, worst 2.9 x; these
+// leave 1.1 %)
+SddmmKernel plain_route(const SddmmArgs& a, bool planned) {
+  const int masks = a.mask_heads > 0 ? a.replicas / a.mask_heads : 1;
+  const bool tiled =
+      wants_tiled(a.m, a.k, a.n, a.nonzeros, a.replicas, planned, /*summed=*/false) &&
+      a.workspace != nullptr && aligned_to(a.workspace, 16) &&
+      sddmm_tiled_applicable(a, sddmm_elem_bytes(a.in_type)) &&
+      a.workspace_bytes / masks >= sddmm_tiled_workspace_bytes(a.m, a.k, a.n, a.nonzeros) &&
+      (a.mask_heads == 0 ||
+       sddmm_many_mask_plan_bytes(a.m, a.k, a.n, a.nonzeros) * masks <= a.workspace_bytes) &&
+      (a.out_type == SPUTNIK_HIP_F32 || sddmm_tiled_passes_half(a.k) == 1);
+  // (a plan that was made ahead of the call carries the pair-flat kernel's lists too)
+  return tiled ? sddmm_tiled_kernel(a, /*flat=*/planned) : SddmmKernel::kRowWave;
+}
+
+// SDDMM on float32 operands, or on float16 / bfloat16 operands read as they are (in_type),
+// output float32 or in_type.  What differs between the two is in this function, in
+// plain_route and in sum_route, marked "float32:" / "half:".
+// A half output the kernels cannot give in one pass: SPUTNIK_HIP_UNSUPPORTED, the caller
+// takes a float output.
+int sddmm_exec(SddmmArgs a, bool planned) {
+  const bool half = a.in_type != SPUTNIK_HIP_F32;
+  const bool half_out = a.out_type != SPUTNIK_HIP_F32;
+  const size_t out_elem = sddmm_elem_bytes(a.out_type);
+  if (a.m < 0 || a.k < 0 || a.n < 0 || a.nonzeros < 0 || a.replicas < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  // half: the types and (below) the pointers' alignment are checked; float32: they never were
+  if (half && ((a.in_type != SPUTNIK_HIP_F16 && a.in_type != SPUTNIK_HIP_BF16) ||
+               (half_out && a.out_type != a.in_type)))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (a.m == 0 || a.nonzeros == 0 || a.replicas == 0) return 0;
+  if (half && (!aligned_to(a.lhs, 2) || !aligned_to(a.rhs, 2) || !aligned_to(a.out, out_elem)))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (a.k == 0) {
+    for (int r = 0; r < a.replicas; ++r) {
+      const hipError_t e = hipMemsetAsync(static_cast<char*>(a.out) + r * a.out_stride * out_elem, 0,
+                                          out_elem * static_cast<size_t>(a.nonzeros), a.stream);
       if (e != hipSuccess) return static_cast<int>(e);
     }
     return 0;
   }
-  const int masks = mask_heads > 0 ? replicas / mask_heads : 1;
-  const size_t plan_bytes = sddmm_many_mask_plan_bytes(m, k, n, nonzeros);
-  if (takes_tiled(m, k, n, nonzeros, replicas, lhs, lhs_stride, rhs, rhs_stride, workspace,
-                  mask_heads > 0 ? workspace_bytes / masks : workspace_bytes, /*summed=*/false,
-                  planned) &&
-      (mask_heads == 0 || plan_bytes * masks <= workspace_bytes)) {
+  if (a.mask_heads > 0)
+    a.mask_plan_ints = static_cast<int64_t>(sddmm_many_mask_plan_bytes(a.m, a.k, a.n, a.nonzeros) / sizeof(int));
+  if (plain_route(a, planned) != SddmmKernel::kRowWave) {
     if (!planned) {
       // (many mask: the tables of all topologies in ONE launch, round 4; the masks share
       // m, n and k, so they share the table's shape)
-      const int st = sddmm_tiled_plan(m, k, n, nonzeros, row_indices, row_offsets, column_indices,
-                                      workspace, stream, /*summed=*/false, /*with_flat=*/false,
-                                      mask_heads > 0 ? masks : 1,
-                                      static_cast<int64_t>(plan_bytes / sizeof(int)));
+      const int st = sddmm_tiled_plan(a, /*summed=*/false, /*with_flat=*/false,
+                                      a.mask_heads > 0 ? a.replicas / a.mask_heads : 1);
       if (st != 0) return st;
     }
-    // (a plan that was made ahead of the call carries the pair-flat kernel's lists too)
-    return sddmm_tiled_launch(m, k, n, nonzeros, replicas, row_indices, row_offsets,
-                              column_indices, lhs, lhs_stride, rhs, rhs_stride, out, out_stride,
-                              workspace, stream, mask_heads, static_cast<int64_t>(plan_bytes / sizeof(int)),
-                              /*flat=*/planned);
+    return sddmm_tiled_launch(a, /*flat=*/planned);
   }
-  int vec = vector_width(lhs, k, lhs_stride);
-  vec = min(vec, vector_width(rhs, k, rhs_stride));
-  switch (vec) {
-    case 4:
-      return launch_vec<4>(m, k, replicas, row_indices, row_offsets, column_indices, lhs,
-                           lhs_stride, rhs, rhs_stride, out, out_stride, stream, mask_heads);
-    case 2:
-      return launch_vec<2>(m, k, replicas, row_indices, row_offsets, column_indices, lhs,
-                           lhs_stride, rhs, rhs_stride, out, out_stride, stream, mask_heads);
-    default:
-      return launch_vec<1>(m, k, replicas, row_indices, row_offsets, column_indices, lhs,
-                           lhs_stride, rhs, rhs_stride, out, out_stride, stream, mask_heads);
-  }
+  // half output on the row-wave kernel: the whole k in one panel (64 lanes x VEC x 4)
+  if (half_out && (a.k > 1024 || rowwave_vec(a) * 256 < a.k)) return SPUTNIK_HIP_UNSUPPORTED;
+  if (!half) return rowwave<float, float>(a);
+  if (a.in_type == SPUTNIK_HIP_F16) return half_out ? rowwave<_Float16, _Float16>(a) : rowwave<_Float16, float>(a);
+  return half_out ? rowwave<__bf16, __bf16>(a) : rowwave<__bf16, float>(a);
 }
 
-}  // namespace
-
-namespace {
-
-// SDDMM on float16 / bfloat16 operands read as they are (in_type), output float or
-// in_type.  A half OUTPUT needs the product in one pass (later passes would add into
-// rounded values): SPUTNIK_HIP_UNSUPPORTED otherwise, the caller takes a float output.
-int sddmm_exec_half(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
-                    const int* row_offsets, const int* column_indices, const void* lhs,
-                    int64_t lhs_stride, const void* rhs, int64_t rhs_stride, void* out,
-                    int64_t out_stride, int in_type, int out_type, void* workspace,
-                    size_t workspace_bytes, bool planned, hipStream_t stream) {
-  if (m < 0 || k < 0 || n < 0 || nonzeros < 0 || replicas < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if ((in_type != SPUTNIK_HIP_F16 && in_type != SPUTNIK_HIP_BF16) ||
-      (out_type != SPUTNIK_HIP_F32 && out_type != in_type))
-    return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (m == 0 || nonzeros == 0 || replicas == 0) return 0;
-  const size_t out_elem = out_type == SPUTNIK_HIP_F32 ? 4 : 2;
-  if (!aligned_to(lhs, 2) || !aligned_to(rhs, 2) || !aligned_to(out, out_elem))
-    return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (k == 0) {
-    for (int r = 0; r < replicas; ++r) {
-      const hipError_t e = hipMemsetAsync(static_cast<char*>(out) + r * out_stride * out_elem, 0,
-                                          out_elem * static_cast<size_t>(nonzeros), stream);
-      if (e != hipSuccess) return static_cast<int>(e);
-    }
-    return 0;
-  }
-  const bool half_out = out_type != SPUTNIK_HIP_F32;
-  // (the float product's estimates: on the half sweep, tools/small_sddmm.py --half, the
-  // one-number rule left 17 % mean regret, worst 2.9 x; these leave 1.1 %)
-  const bool tiled = wants_tiled(m, k, n, nonzeros, replicas, planned, /*summed=*/false) &&
-                     workspace != nullptr && aligned_to(workspace, 16) &&
-                     sddmm_tiled_applicable_half(m, k, n, nonzeros, lhs, lhs_stride, rhs, rhs_stride) &&
-                     workspace_bytes >= sddmm_tiled_workspace_bytes(m, k, n, nonzeros) &&
-                     (!half_out || sddmm_tiled_passes_half(k) == 1);
-  if (tiled) {
-    if (!planned) {
-      const int st = sddmm_tiled_plan(m, k, n, nonzeros, row_indices, row_offsets, column_indices,
-                                      workspace, stream);
-      if (st != 0) return st;
-    }
-    return sddmm_tiled_launch_half(m, k, n, nonzeros, replicas, row_indices, row_offsets,
-                                   column_indices, lhs, lhs_stride, rhs, rhs_stride, out, out_stride,
-                                   in_type, out_type, workspace, stream, 0, 0, /*flat=*/planned);
-  }
-  if (half_out && k > 1024) return SPUTNIK_HIP_UNSUPPORTED;   // (row-wave panel: 64 lanes x 4 x 4)
-  if (half_out && min(vector_width_of(lhs, k, lhs_stride, 2), vector_width_of(rhs, k, rhs_stride, 2)) * 256 < k)
-    return SPUTNIK_HIP_UNSUPPORTED;
-#define SPUTNIK_HIP_RW(T, TO)                                                                   \
-  return rowwave_half<T, TO>(m, k, replicas, row_indices, row_offsets, column_indices, lhs,      \
-                             lhs_stride, rhs, rhs_stride, out, out_stride, stream)
-  if (in_type == SPUTNIK_HIP_F16 && !half_out) SPUTNIK_HIP_RW(_Float16, float);
-  if (in_type == SPUTNIK_HIP_F16) SPUTNIK_HIP_RW(_Float16, _Float16);
-  if (!half_out) SPUTNIK_HIP_RW(__bf16, float);
-  SPUTNIK_HIP_RW(__bf16, __bf16);
-#undef SPUTNIK_HIP_RW
+// A call of the C interface.
+SddmmArgs call_of(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
+                  const int* row_offsets, const int* column_indices, const void* lhs, int64_t lhs_stride,
+                  const void* rhs, int64_t rhs_stride, void* out, int64_t out_stride, int in_type,
+                  int out_type, const void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return SddmmArgs{m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices, lhs, lhs_stride,
+                   rhs, rhs_stride, out, out_stride, in_type, out_type, const_cast<void*>(workspace),
+                   workspace_bytes, stream, 0, 0};
+}
+// A mask and its workspace alone: what the plan entry points have.
+SddmmArgs topology_of(int m, int k, int n, int nonzeros, const int* row_indices, const int* row_offsets,
+                      const int* column_indices, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return call_of(m, k, n, nonzeros, 0, row_indices, row_offsets, column_indices, nullptr, 0, nullptr, 0,
+                 nullptr, 0, SPUTNIK_HIP_F32, SPUTNIK_HIP_F32, workspace, workspace_bytes, stream);
+}
+// The call the name / route queries speak of, which know its shape alone: operands as the
+// bindings pass them (aligned, contiguous; float32 output) and a workspace of the size the
+// workspace query reports.  Its pointers pass every test of the route functions, which never
+// follow them.
+SddmmArgs shape_call(int m, int k, int n, int nonzeros, int replicas, int in_type, size_t workspace_bytes) {
+  alignas(16) static char workspace;
+  return call_of(m, k, n, nonzeros, replicas, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0,
+                 in_type, SPUTNIK_HIP_F32, &workspace, workspace_bytes, nullptr);
 }
 
 }  // namespace
@@ -543,9 +453,13 @@ int sputnik_hip_internal_sddmm_many_mask(int masks, int m, int k, int n, const i
                     const float* lhs, int64_t lhs_stride, const float* rhs, int64_t rhs_stride,
                     float* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
                     hipStream_t stream) {
-  return sddmm_exec(m, k, n, largest, replicas, row_indices, row_offsets, column_indices, lhs,
-                    lhs_stride, rhs, rhs_stride, out, out_stride, workspace, workspace_bytes,
-                    /*planned=*/false, stream, replicas / masks, nonzeros);
+  // concatenated topologies, replica r under number r / mask_heads; `largest` = the largest
+  // mask's count (kernel choice and plan size)
+  SddmmArgs a = call_of(m, k, n, largest, replicas, row_indices, row_offsets, column_indices, lhs, lhs_stride,
+                        rhs, rhs_stride, out, out_stride, SPUTNIK_HIP_F32, SPUTNIK_HIP_F32, workspace,
+                        workspace_bytes, stream);
+  a.mask_heads = replicas / masks;
+  return sddmm_exec(a, /*planned=*/false);
 }
 
 int sputnik_hip_sddmm_batched(int m, int k, int n, int nonzeros, int replicas,
@@ -554,9 +468,10 @@ int sputnik_hip_sddmm_batched(int m, int k, int n, int nonzeros, int replicas,
                               const float* rhs, int64_t rhs_stride, float* out,
                               int64_t out_stride, void* workspace, size_t workspace_bytes,
                               sputnik_hip_stream_t stream) {
-  return sddmm_exec(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices, lhs,
-                    lhs_stride, rhs, rhs_stride, out, out_stride, workspace, workspace_bytes,
-                    /*planned=*/false, stream);
+  return sddmm_exec(call_of(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices, lhs,
+                            lhs_stride, rhs, rhs_stride, out, out_stride, SPUTNIK_HIP_F32, SPUTNIK_HIP_F32,
+                            workspace, workspace_bytes, stream),
+                    /*planned=*/false);
 }
 
 namespace {
@@ -580,71 +495,6 @@ size_t sum_workspace_bytes(int m, int k, int n, int nonzeros) {
 int64_t sum_parts(int m, int k, int n, int nonzeros, int replicas) {
   const bool tiled_shape = sddmm_tiled_workspace_bytes(m, k, n, nonzeros) != 0;
   return static_cast<int64_t>(replicas) * (tiled_shape ? sddmm_tiled_panels(m, k, n, nonzeros) : 1);
-}
-
-// `leave_parts` != nullptr: the call stops in front of its last launch and says how many
-// partial vectors of `nonzeros` floats it left in `scratch` (0: `out` is complete) -- for
-// sputnik_hip_sddmm_sum_group_planned, which adds the vectors of several calls in one launch.
-int sddmm_sum_exec(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
-                   const int* row_offsets, const int* column_indices, const float* lhs,
-                   int64_t lhs_stride, const float* rhs, int64_t rhs_stride, float* out,
-                   void* workspace, size_t workspace_bytes, bool planned, void* scratch,
-                   size_t scratch_bytes, hipStream_t stream, int* leave_parts = nullptr) {
-  if (leave_parts != nullptr) *leave_parts = 0;
-  if (m < 0 || k < 0 || n < 0 || nonzeros < 0 || replicas < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (m == 0 || nonzeros == 0) return 0;
-  if (k == 0 || replicas == 0) {
-    const hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * static_cast<size_t>(nonzeros), stream);
-    return static_cast<int>(e);
-  }
-  const bool tables_usable =
-      workspace != nullptr && aligned_to(workspace, 16) &&
-      sddmm_tiled_applicable(m, k, n, nonzeros, lhs, lhs_stride, rhs, rhs_stride) &&
-      workspace_bytes >= sddmm_tiled_workspace_bytes(m, k, n, nonzeros, /*summed=*/true);
-  const SumRoute route = sum_vector_route(m, k, n, nonzeros, replicas, /*half=*/false, planned, tables_usable);
-  const bool tiled = route.kernel == SPUTNIK_HIP_SUM_TILED;
-  const int64_t parts = static_cast<int64_t>(replicas) * route.panels;
-  if (parts == 1)
-    // One replica and one panel: the plain product, which plans for itself -- a plan made
-    // for the summed form has that form's slabs and no pair-flat lists behind the tables,
-    // and the plain dispatch may choose differently from the `tiled` above.
-    return sddmm_exec(m, k, n, nonzeros, 1, row_indices, row_offsets, column_indices, lhs,
-                      lhs_stride, rhs, rhs_stride, out, 0, tiled ? workspace : nullptr,
-                      tiled ? workspace_bytes : 0, /*planned=*/false, stream);
-  if (scratch == nullptr || !aligned_to(scratch, 16) ||
-      scratch_bytes < sizeof(float) * static_cast<size_t>(parts) * nonzeros)
-    return SPUTNIK_HIP_INVALID_ARGUMENT;
-  float* partials = static_cast<float*>(scratch);
-  int st;
-  if (tiled) {
-    if (!planned) {
-      st = sddmm_tiled_plan(m, k, n, nonzeros, row_indices, row_offsets, column_indices,
-                            workspace, stream, /*summed=*/true);
-      if (st != 0) return st;
-    }
-    st = sddmm_tiled_launch_partials(m, k, n, nonzeros, replicas, row_indices, row_offsets,
-                                     column_indices, lhs, lhs_stride, rhs, rhs_stride, partials,
-                                     workspace, stream);
-  } else {
-    // (row-wave kernel: the workspace, planned for the summed form or not, is not used)
-    st = sddmm_exec(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices, lhs,
-                    lhs_stride, rhs, rhs_stride, partials, nonzeros, nullptr, 0, false, stream);
-  }
-  if (st != 0) return st;
-  const int nparts = static_cast<int>(parts);
-  if (leave_parts != nullptr) {
-    *leave_parts = nparts;
-    return 0;
-  }
-  if (nonzeros % 4 == 0 && aligned_to(out, 16)) {
-    hipLaunchKernelGGL(sum_partials_kernel<4>, dim3(ceil_div(nonzeros / 4, kBlock)), dim3(kBlock),
-                       0, stream, nonzeros / 4, nparts, static_cast<int64_t>(nonzeros), partials,
-                       out);
-  } else {
-    hipLaunchKernelGGL(sum_partials_kernel<1>, dim3(ceil_div(nonzeros, kBlock)), dim3(kBlock), 0,
-                       stream, nonzeros, nparts, static_cast<int64_t>(nonzeros), partials, out);
-  }
-  return launch_status();
 }
 
 // Long reductions over a mask that occupies every tile: the dense tiles on the matrix
@@ -678,77 +528,104 @@ int sum_on_matrix_cores(int m, int k, int n, int nonzeros, int replicas, const i
                                    lhs_stride, rhs, rhs_stride, in_type, dst, splits, plan, stream,
                                    planes, lhs_plane_stride, rhs_plane_stride);
   if (st != 0 || splits == 1) return st;
-  if (nonzeros % 4 == 0 && aligned_to(out, 16)) {
-    hipLaunchKernelGGL(sum_partials_kernel<4>, dim3(ceil_div(nonzeros / 4, kBlock)), dim3(kBlock),
-                       0, stream, nonzeros / 4, splits, static_cast<int64_t>(nonzeros), dst, out);
-  } else {
-    hipLaunchKernelGGL(sum_partials_kernel<1>, dim3(ceil_div(nonzeros, kBlock)), dim3(kBlock), 0,
-                       stream, nonzeros, splits, static_cast<int64_t>(nonzeros), dst, out);
-  }
-  return launch_status();
+  return sum_partials_launch(nonzeros, splits, dst, out, stream);   // (dst = scratch: on 16 bytes)
 }
 
-// The same on float16 / bfloat16 operands read as they are; partial vectors and the
-// sum are float32.
-int sddmm_sum_exec_half(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
-                        const int* row_offsets, const int* column_indices, const void* lhs,
-                        int64_t lhs_stride, const void* rhs, int64_t rhs_stride, int in_type,
-                        float* out, void* workspace, size_t workspace_bytes, bool planned,
-                        void* scratch, size_t scratch_bytes, hipStream_t stream) {
-  if (m < 0 || k < 0 || n < 0 || nonzeros < 0 || replicas < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (in_type != SPUTNIK_HIP_F16 && in_type != SPUTNIK_HIP_BF16) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (m == 0 || nonzeros == 0) return 0;
-  if (k == 0 || replicas == 0) {
-    const hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * static_cast<size_t>(nonzeros), stream);
+// The plain product a summed call of one replica and one panel is.  with_workspace: the
+// vector route took the tiled kernels (the row-wave kernel needs no workspace).
+SddmmArgs one_part_call(const SddmmArgs& a, bool with_workspace) {
+  SddmmArgs b = a;
+  b.replicas = 1;
+  b.out_stride = 0;
+  b.out_type = SPUTNIK_HIP_F32;
+  if (!with_workspace) {
+    b.workspace = nullptr;
+    b.workspace_bytes = 0;
+  }
+  return b;
+}
+
+// The summed product's route, every kernel of it: the one decision of sddmm_sum_exec and of
+// sputnik_hip_sddmm_sum_route.  planes: of a (float32, half) pair's float32 operand (1: none).
+SumRoute sum_route(const SddmmArgs& a, bool planned, int planes = 1) {
+  const bool half = a.in_type != SPUTNIK_HIP_F32;
+  // half: the matrix-core route is tried first; float32 has none
+  if (half && sddmm_mfma_applicable(a.m, a.k, a.n, a.nonzeros, a.replicas, a.lhs, a.lhs_stride, a.rhs,
+                                    a.rhs_stride))
+    return SumRoute{SPUTNIK_HIP_SUM_MFMA, 0, 1, sddmm_mfma_tile_rows(a.m, a.n),
+                    sddmm_mfma_splits(a.m, a.k, a.n, a.replicas, planes)};
+  const bool tables_usable =
+      a.workspace != nullptr && aligned_to(a.workspace, 16) &&
+      sddmm_tiled_applicable(a, sddmm_elem_bytes(a.in_type)) &&
+      (!half || sddmm_tiled_sum_half_served(a.m, a.k, a.n, a.nonzeros)) &&
+      a.workspace_bytes >= sddmm_tiled_workspace_bytes(a.m, a.k, a.n, a.nonzeros, /*summed=*/true);
+  SumRoute r = sum_vector_route(a.m, a.k, a.n, a.nonzeros, a.replicas, half, planned, tables_usable);
+  if (static_cast<int64_t>(a.replicas) * r.panels == 1) {
+    // One replica and one panel, nothing to sum: the plain product, which plans for itself
+    // on the summed form's workspace -- a plan made for the summed form has that form's slabs
+    // and no pair-flat lists behind the tables, and the plain dispatch may choose differently
+    // from the vector route above.
+    const bool tiled = plain_route(one_part_call(a, r.kernel == SPUTNIK_HIP_SUM_TILED), false) !=
+                       SddmmKernel::kRowWave;
+    r = SumRoute{SPUTNIK_HIP_SUM_PLAIN, tiled ? sddmm_tiled_panel_width(a.k) : 0, 1,
+                 tiled ? sddmm_tiled_slab_rows(a.k) : 0, 1};
+  }
+  return r;
+}
+
+// The summed product on float32 or half operands; partial vectors and the sum are float32.
+// `leave_parts` != nullptr: the call stops in front of its last launch and says how many
+// partial vectors of `nonzeros` floats it left in `scratch` (0: `out` is complete) -- for
+// sputnik_hip_sddmm_sum_group_planned, which adds the vectors of several calls in one launch.
+int sddmm_sum_exec(const SddmmArgs& a, bool planned, void* scratch, size_t scratch_bytes,
+                   int* leave_parts = nullptr) {
+  float* out = static_cast<float*>(a.out);
+  if (leave_parts != nullptr) *leave_parts = 0;
+  if (a.m < 0 || a.k < 0 || a.n < 0 || a.nonzeros < 0 || a.replicas < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (a.in_type != SPUTNIK_HIP_F32 && a.in_type != SPUTNIK_HIP_F16 && a.in_type != SPUTNIK_HIP_BF16)
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (a.m == 0 || a.nonzeros == 0) return 0;
+  if (a.k == 0 || a.replicas == 0) {
+    const hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * static_cast<size_t>(a.nonzeros), a.stream);
     return static_cast<int>(e);
   }
-  if (sddmm_mfma_applicable(m, k, n, nonzeros, replicas, lhs, lhs_stride, rhs, rhs_stride))
-    return sum_on_matrix_cores(m, k, n, nonzeros, replicas, row_offsets, column_indices, lhs,
-                               lhs_stride, rhs, rhs_stride, in_type, out, workspace, workspace_bytes,
-                               planned, scratch, scratch_bytes, stream, 1, 0, 0);
-  const bool tables_usable =
-      workspace != nullptr && aligned_to(workspace, 16) &&
-      sddmm_tiled_applicable_half(m, k, n, nonzeros, lhs, lhs_stride, rhs, rhs_stride) &&
-      sddmm_tiled_sum_half_served(m, k, n, nonzeros) &&
-      workspace_bytes >= sddmm_tiled_workspace_bytes(m, k, n, nonzeros, /*summed=*/true);
-  const SumRoute route = sum_vector_route(m, k, n, nonzeros, replicas, /*half=*/true, planned, tables_usable);
+  const SumRoute route = sum_route(a, planned);
+  if (route.kernel == SPUTNIK_HIP_SUM_MFMA)
+    return sum_on_matrix_cores(a.m, a.k, a.n, a.nonzeros, a.replicas, a.row_offsets, a.column_indices,
+                               a.lhs, a.lhs_stride, a.rhs, a.rhs_stride, a.in_type, out, a.workspace,
+                               a.workspace_bytes, planned, scratch, scratch_bytes, a.stream, 1, 0, 0);
+  if (route.kernel == SPUTNIK_HIP_SUM_PLAIN)
+    // ("with parts==1 ... call the plain exec with planned=false on the caller's
+    // workspace": a workspace handed over as a const plan is rewritten here.  Kept as it is:
+    // the fix changes routes and timing)
+    // (route.panel_width != 0: the plain product takes the tiled kernels, sum_route)
+    return sddmm_exec(one_part_call(a, route.panel_width != 0), /*planned=*/false);
   const bool tiled = route.kernel == SPUTNIK_HIP_SUM_TILED;
-  const int64_t parts = static_cast<int64_t>(replicas) * route.panels;
-  if (parts == 1)   // (the plain product, planning for itself: see sddmm_sum_exec)
-    return sddmm_exec_half(m, k, n, nonzeros, 1, row_indices, row_offsets, column_indices, lhs,
-                           lhs_stride, rhs, rhs_stride, out, 0, in_type, SPUTNIK_HIP_F32,
-                           tiled ? workspace : nullptr, tiled ? workspace_bytes : 0,
-                           /*planned=*/false, stream);
+  const int64_t parts = static_cast<int64_t>(a.replicas) * route.panels;
   if (scratch == nullptr || !aligned_to(scratch, 16) ||
-      scratch_bytes < sizeof(float) * static_cast<size_t>(parts) * nonzeros)
+      scratch_bytes < sizeof(float) * static_cast<size_t>(parts) * a.nonzeros)
     return SPUTNIK_HIP_INVALID_ARGUMENT;
-  float* partials = static_cast<float*>(scratch);
+  SddmmArgs p = a;   // the partial vectors: one per (replica, panel), or one per replica
+  p.out = scratch;
+  p.out_type = SPUTNIK_HIP_F32;
   int st;
   if (tiled) {
-    if (!planned) {
-      st = sddmm_tiled_plan(m, k, n, nonzeros, row_indices, row_offsets, column_indices,
-                            workspace, stream, /*summed=*/true);
-      if (st != 0) return st;
-    }
-    st = sddmm_tiled_launch_partials_half(m, k, n, nonzeros, replicas, row_indices, row_offsets,
-                                          column_indices, lhs, lhs_stride, rhs, rhs_stride, in_type,
-                                          partials, workspace, stream);
+    st = planned ? 0 : sddmm_tiled_plan(a, /*summed=*/true);
+    if (st == 0) st = sddmm_tiled_launch_partials(p);
   } else {
-    st = sddmm_exec_half(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices, lhs,
-                         lhs_stride, rhs, rhs_stride, partials, nonzeros, in_type, SPUTNIK_HIP_F32,
-                         nullptr, 0, false, stream);
+    // (row-wave kernel: the workspace, planned for the summed form or not, is not used)
+    p.out_stride = a.nonzeros;
+    p.workspace = nullptr;
+    p.workspace_bytes = 0;
+    st = sddmm_exec(p, /*planned=*/false);
   }
   if (st != 0) return st;
-  const int nparts = static_cast<int>(parts);
-  if (nonzeros % 4 == 0 && aligned_to(out, 16)) {
-    hipLaunchKernelGGL(sum_partials_kernel<4>, dim3(ceil_div(nonzeros / 4, kBlock)), dim3(kBlock),
-                       0, stream, nonzeros / 4, nparts, static_cast<int64_t>(nonzeros), partials,
-                       out);
-  } else {
-    hipLaunchKernelGGL(sum_partials_kernel<1>, dim3(ceil_div(nonzeros, kBlock)), dim3(kBlock), 0,
-                       stream, nonzeros, nparts, static_cast<int64_t>(nonzeros), partials, out);
+  if (leave_parts != nullptr) {
+    *leave_parts = static_cast<int>(parts);
+    return 0;
   }
-  return launch_status();
+  return sum_partials_launch(a.nonzeros, static_cast<int>(parts), static_cast<const float*>(scratch), out,
+                             a.stream);
 }
 
 }  // namespace
@@ -775,8 +652,9 @@ int sputnik_hip_sddmm_sum_plan(int m, int k, int n, int nonzeros, const int* row
   const size_t need = sddmm_tiled_workspace_bytes(m, k, n, nonzeros, /*summed=*/true);
   if (need == 0 || workspace_bytes < need)
     return 0;  // nothing (else) to plan: the row-wave kernel needs no workspace
-  return sddmm_tiled_plan(m, k, n, nonzeros, row_indices, row_offsets, column_indices, workspace,
-                          stream, /*summed=*/true);
+  return sddmm_tiled_plan(topology_of(m, k, n, nonzeros, row_indices, row_offsets, column_indices, workspace,
+                                      workspace_bytes, stream),
+                          /*summed=*/true);
 }
 
 size_t sputnik_hip_sddmm_sum_scratch_bytes(int m, int k, int n, int nonzeros, int replicas) {
@@ -795,9 +673,9 @@ int sputnik_hip_sddmm_sum_batched(int m, int k, int n, int nonzeros, int replica
                                   float* out, void* workspace, size_t workspace_bytes,
                                   void* scratch, size_t scratch_bytes,
                                   sputnik_hip_stream_t stream) {
-  return sddmm_sum_exec(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices,
-                        lhs, lhs_stride, rhs, rhs_stride, out, workspace, workspace_bytes,
-                        /*planned=*/false, scratch, scratch_bytes, stream);
+  return sputnik_hip_sddmm_sum_typed(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices,
+                                     lhs, lhs_stride, rhs, rhs_stride, SPUTNIK_HIP_F32, out, workspace,
+                                     workspace_bytes, /*planned=*/0, scratch, scratch_bytes, stream);
 }
 
 int sputnik_hip_sddmm_sum_batched_planned(int m, int k, int n, int nonzeros, int replicas,
@@ -807,9 +685,10 @@ int sputnik_hip_sddmm_sum_batched_planned(int m, int k, int n, int nonzeros, int
                                           int64_t rhs_stride, float* out, const void* workspace,
                                           size_t workspace_bytes, void* scratch,
                                           size_t scratch_bytes, sputnik_hip_stream_t stream) {
-  return sddmm_sum_exec(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices,
-                        lhs, lhs_stride, rhs, rhs_stride, out, const_cast<void*>(workspace),
-                        workspace_bytes, /*planned=*/true, scratch, scratch_bytes, stream);
+  return sputnik_hip_sddmm_sum_typed(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices,
+                                     lhs, lhs_stride, rhs, rhs_stride, SPUTNIK_HIP_F32, out,
+                                     const_cast<void*>(workspace), workspace_bytes, /*planned=*/1, scratch,
+                                     scratch_bytes, stream);
 }
 
 int sputnik_hip_sddmm_sum_group_planned(int m, int k, int n, int replicas, int count,
@@ -823,10 +702,11 @@ int sputnik_hip_sddmm_sum_group_planned(int m, int k, int n, int replicas, int c
   for (int p = 0; p < count; ++p) {
     const sputnik_hip_sddmm_sum_problem& q = problems[p];
     int parts = 0;
-    const int st = sddmm_sum_exec(m, k, n, q.nonzeros, replicas, q.row_indices, q.row_offsets,
-                                  q.column_indices, q.lhs, lhs_stride, q.rhs, rhs_stride, q.out,
-                                  const_cast<void*>(q.workspace), q.workspace_bytes, /*planned=*/true,
-                                  q.scratch, q.scratch_bytes, stream, &parts);
+    const int st = sddmm_sum_exec(call_of(m, k, n, q.nonzeros, replicas, q.row_indices, q.row_offsets,
+                                          q.column_indices, q.lhs, lhs_stride, q.rhs, rhs_stride, q.out, 0,
+                                          SPUTNIK_HIP_F32, SPUTNIK_HIP_F32, q.workspace, q.workspace_bytes,
+                                          stream),
+                                  /*planned=*/true, q.scratch, q.scratch_bytes, &parts);
     if (st != 0) return st;
     if (parts == 0) continue;   // (`out` is complete: an empty mask, or one replica of one panel)
     g.partials[sums] = static_cast<const float*>(q.scratch);
@@ -848,14 +728,10 @@ int sputnik_hip_sddmm_sum_typed(int m, int k, int n, int nonzeros, int replicas,
                                 const void* rhs, int64_t rhs_stride, int in_type, float* out,
                                 void* workspace, size_t workspace_bytes, int planned,
                                 void* scratch, size_t scratch_bytes, sputnik_hip_stream_t stream) {
-  if (in_type == SPUTNIK_HIP_F32)
-    return sddmm_sum_exec(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices,
-                          static_cast<const float*>(lhs), lhs_stride,
-                          static_cast<const float*>(rhs), rhs_stride, out, workspace,
-                          workspace_bytes, planned != 0, scratch, scratch_bytes, stream);
-  return sddmm_sum_exec_half(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices,
-                             lhs, lhs_stride, rhs, rhs_stride, in_type, out, workspace,
-                             workspace_bytes, planned != 0, scratch, scratch_bytes, stream);
+  return sddmm_sum_exec(call_of(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices, lhs,
+                                lhs_stride, rhs, rhs_stride, out, 0, in_type, SPUTNIK_HIP_F32, workspace,
+                                workspace_bytes, stream),
+                        planned != 0, scratch, scratch_bytes);
 }
 
 namespace {
@@ -937,8 +813,9 @@ int sputnik_hip_sddmm_plan(int m, int k, int n, int nonzeros, const int* row_ind
       sddmm_tiled_workspace_bytes(m, k, n, nonzeros) == 0 ||
       workspace_bytes < sddmm_tiled_workspace_bytes(m, k, n, nonzeros))
     return 0;  // nothing to plan: the row-wave kernel needs no workspace
-  return sddmm_tiled_plan(m, k, n, nonzeros, row_indices, row_offsets, column_indices, workspace,
-                          stream, /*summed=*/false, /*with_flat=*/true);
+  return sddmm_tiled_plan(topology_of(m, k, n, nonzeros, row_indices, row_offsets, column_indices, workspace,
+                                      workspace_bytes, stream),
+                          /*summed=*/false, /*with_flat=*/true);
 }
 
 int sputnik_hip_sddmm_batched_planned(int m, int k, int n, int nonzeros, int replicas,
@@ -947,9 +824,10 @@ int sputnik_hip_sddmm_batched_planned(int m, int k, int n, int nonzeros, int rep
                                       int64_t lhs_stride, const float* rhs, int64_t rhs_stride,
                                       float* out, int64_t out_stride, const void* workspace,
                                       size_t workspace_bytes, sputnik_hip_stream_t stream) {
-  return sddmm_exec(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices, lhs,
-                    lhs_stride, rhs, rhs_stride, out, out_stride, const_cast<void*>(workspace),
-                    workspace_bytes, /*planned=*/true, stream);
+  return sddmm_exec(call_of(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices, lhs,
+                            lhs_stride, rhs, rhs_stride, out, out_stride, SPUTNIK_HIP_F32, SPUTNIK_HIP_F32,
+                            workspace, workspace_bytes, stream),
+                    /*planned=*/true);
 }
 
 int sputnik_hip_sddmm_typed(int m, int k, int n, int nonzeros, int replicas,
@@ -958,29 +836,26 @@ int sputnik_hip_sddmm_typed(int m, int k, int n, int nonzeros, int replicas,
                             const void* rhs, int64_t rhs_stride, int in_type, void* out,
                             int64_t out_stride, int out_type, void* workspace,
                             size_t workspace_bytes, int planned, sputnik_hip_stream_t stream) {
-  if (in_type == SPUTNIK_HIP_F32) {
-    if (out_type != SPUTNIK_HIP_F32) return SPUTNIK_HIP_INVALID_ARGUMENT;
-    return sddmm_exec(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices,
-                      static_cast<const float*>(lhs), lhs_stride, static_cast<const float*>(rhs),
-                      rhs_stride, static_cast<float*>(out), out_stride, workspace, workspace_bytes,
-                      planned != 0, stream);
-  }
-  return sddmm_exec_half(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices, lhs,
-                         lhs_stride, rhs, rhs_stride, out, out_stride, in_type, out_type, workspace,
-                         workspace_bytes, planned != 0, stream);
+  if (in_type == SPUTNIK_HIP_F32 && out_type != SPUTNIK_HIP_F32) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  return sddmm_exec(call_of(m, k, n, nonzeros, replicas, row_indices, row_offsets, column_indices, lhs,
+                            lhs_stride, rhs, rhs_stride, out, out_stride, in_type, out_type, workspace,
+                            workspace_bytes, stream),
+                    planned != 0);
 }
 
+// The two queries take the decision of the launch paths (plain_route, sum_route) on the call
+// as the bindings make it: see shape_call.
 const char* sputnik_hip_sddmm_kernel_name(int m, int k, int n, int nonzeros, int replicas,
                                           int elem_bytes, int planned) {
   if (m <= 0 || k <= 0 || n <= 0 || nonzeros <= 0 || replicas <= 0) return "none";
-  const bool shape = sddmm_tiled_workspace_bytes(m, k, n, nonzeros) != 0 &&
-                     static_cast<int64_t>(n) * k * elem_bytes < (int64_t{1} << 32) &&
-                     static_cast<int64_t>(m) * k * elem_bytes < (int64_t{1} << 32);
-  if (!wants_tiled(m, k, n, nonzeros, replicas, planned != 0, /*summed=*/false) || !shape)
-    return "sddmm_rowwave_kernel";
-  if (planned != 0 && sddmm_flat_applicable(m, k, n, nonzeros, elem_bytes)) return "sddmm_flat_kernel";
-  if (elem_bytes == 2 || sddmm_tiled_panel_width(k) == 64) return "sddmm_quad_kernel";
-  return "sddmm_stationary_kernel";
+  switch (plain_route(shape_call(m, k, n, nonzeros, replicas, elem_bytes == 2 ? SPUTNIK_HIP_F16 : SPUTNIK_HIP_F32,
+                                 sddmm_tiled_workspace_bytes(m, k, n, nonzeros)),
+                      planned != 0)) {
+    case SddmmKernel::kFlat: return "sddmm_flat_kernel";
+    case SddmmKernel::kQuad: return "sddmm_quad_kernel";
+    case SddmmKernel::kStationary: return "sddmm_stationary_kernel";
+    default: return "sddmm_rowwave_kernel";
+  }
 }
 
 int sputnik_hip_sddmm_sum_route(int m, int k, int n, int nonzeros, int replicas, int in_type,
@@ -989,29 +864,10 @@ int sputnik_hip_sddmm_sum_route(int m, int k, int n, int nonzeros, int replicas,
   if (m <= 0 || k <= 0 || n <= 0 || nonzeros <= 0 || replicas <= 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
   const bool half = in_type == SPUTNIK_HIP_F16 || in_type == SPUTNIK_HIP_BF16;
   if (!half && (in_type != SPUTNIK_HIP_F32 || mixed != 0)) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  SumRoute r{SPUTNIK_HIP_SUM_ROWWAVE, 0, 1, 0, 1};
-  if (half && sddmm_mfma_applicable(m, k, n, nonzeros, replicas, nullptr, 0, nullptr, 0)) {
-    r.kernel = SPUTNIK_HIP_SUM_MFMA;
-    r.slab_rows = sddmm_mfma_tile_rows(m, n);
-    r.splits = sddmm_mfma_splits(m, k, n, replicas, mixed != 0 ? sddmm_mfma_planes_of(in_type) : 1);
-  } else if (mixed != 0) {
-    return SPUTNIK_HIP_UNSUPPORTED;   // (a (float32, half) pair has the matrix-core route only)
-  } else {
-    const bool served = sddmm_tiled_workspace_bytes(m, k, n, nonzeros, /*summed=*/true) != 0 &&
-                        (half ? sddmm_tiled_applicable_half(m, k, n, nonzeros, nullptr, 0, nullptr, 0) &&
-                                    sddmm_tiled_sum_half_served(m, k, n, nonzeros)
-                              : sddmm_tiled_applicable(m, k, n, nonzeros, nullptr, 0, nullptr, 0));
-    r = sum_vector_route(m, k, n, nonzeros, replicas, half, planned != 0, served);
-    if (static_cast<int64_t>(replicas) * r.panels == 1) {
-      // nothing to sum: the plain product, planning for itself, on the summed form's workspace
-      const bool plain_tiled =
-          r.kernel == SPUTNIK_HIP_SUM_TILED &&
-          wants_tiled(m, k, n, nonzeros, 1, /*planned=*/false, /*summed=*/false) &&
-          sum_workspace_bytes(m, k, n, nonzeros) >= sddmm_tiled_workspace_bytes(m, k, n, nonzeros);
-      r = SumRoute{SPUTNIK_HIP_SUM_PLAIN, plain_tiled ? sddmm_tiled_panel_width(k) : 0, 1, 0, 1};
-      if (plain_tiled) r.slab_rows = sddmm_tiled_slab_rows(k);
-    }
-  }
+  const SumRoute r = sum_route(shape_call(m, k, n, nonzeros, replicas, in_type, sum_workspace_bytes(m, k, n, nonzeros)),
+                               planned != 0, mixed != 0 ? sddmm_mfma_planes_of(in_type) : 1);
+  // (a (float32, half) pair has the matrix-core route only)
+  if (mixed != 0 && r.kernel != SPUTNIK_HIP_SUM_MFMA) return SPUTNIK_HIP_UNSUPPORTED;
   if (kernel != nullptr) *kernel = r.kernel;
   if (panel_width != nullptr) *panel_width = r.panel_width;
   if (panels != nullptr) *panels = r.panels;

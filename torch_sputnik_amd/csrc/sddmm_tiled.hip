@@ -29,19 +29,10 @@
 
 #include "options.h"
 #include "sddmm_dot.h"
+#include "sddmm_tiled.h"
 #include "spmm_tiled_common.h"
 
 namespace sputnik_hip {
-
-// sddmm_flat.hip: the pair-flat kernel for planned masks and rows of 128 / 256 bytes
-bool sddmm_flat_applicable(int m, int k, int n, int nonzeros, int elem_bytes);
-size_t sddmm_flat_plan_bytes(int m, int n, int nonzeros);
-int sddmm_flat_plan(int m, int n, int nonzeros, const int* row_indices, const int* row_offsets,
-                    const int* column_indices, void* plan, hipStream_t stream);
-int sddmm_flat_launch(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
-                      const void* lhs, int64_t lhs_stride, const void* rhs, int64_t rhs_stride,
-                      void* out, int64_t out_stride, int in_type, int out_type, const void* plan,
-                      hipStream_t stream);
 
 namespace {
 
@@ -709,225 +700,139 @@ inline int width_for(int m, int k, int n, int nonzeros, bool summed) {
 }
 inline bool served(int k) { return panel_width(k) != 0 && k / panel_width(k) <= kMaxPanels; }
 
-// The chunk table is the SpMM one with the mask's columns (n) in the role of k,
-// cut at slab boundaries.  Topology only: a caller with a static mask runs it once.
-template <int KV, int ROWS = default_slab_rows(KV)>
-int plan(int m, int n, int slots, const int* row_indices, const int* row_offsets,
-         const int* column_indices, int* table, int* row_ok, hipStream_t stream, int masks,
-         int64_t mask_plan_ints) {
-  using S = Slab<KV, ROWS>;
-  if (masks > 1) {   // concatenated topologies: all masks' tables in one launch
-    if (masks > kMaxGridYZ) return SPUTNIK_HIP_INVALID_ARGUMENT;
-    hipLaunchKernelGGL((spmm_chunk_table_masks_kernel<S::kRows>), dim3(ceil_div(slots, 4), masks),
-                       dim3(256), 0, stream, m, n, slots, kSGroups * kSRows, ceil_div(n, S::kRows),
-                       row_indices, row_offsets, column_indices, table, row_ok, mask_plan_ints);
-    return launch_status();
-  }
-  hipLaunchKernelGGL((spmm_chunk_table_kernel<S::kRows>), dim3(ceil_div(slots, 4)),
-                     dim3(256), 0, stream, m, n, slots, kSGroups * kSRows, ceil_div(n, S::kRows),
-                     row_indices, row_offsets, column_indices, table, row_ok);
-  return launch_status();
+// The workspace: the rows' status words, then (256-byte aligned) the chunk table.
+struct Tables {
+  int* row_ok;
+  int* table;
+};
+inline Tables tables_in(const void* workspace, int slots) {
+  char* base = static_cast<char*>(const_cast<void*>(workspace));
+  return Tables{reinterpret_cast<int*>(base), reinterpret_cast<int*>(base + row_ok_bytes(slots))};
 }
 
-template <int KV>
-int launch(int m, int k, int n, int nonzeros, int replicas, int slots, const int* row_indices,
-           const int* row_offsets, const int* column_indices, const int* table,
-           const int* row_ok, const float* lhs, int64_t lhs_stride, const float* rhs,
-           int64_t rhs_stride, float* out, int64_t out_stride, int debug, hipStream_t stream,
-           int mask_heads, int64_t mask_plan_ints) {
-  using S = Slab<KV>;
-  const int slabs = ceil_div(n, S::kRows);
-  int st = 0;
+// The one map from a panel width (and the summed form's 80-row variant of 256) to its kernel
+// geometry: f(Geometry<KV, ROWS>).  Half operands run panels of at most 256 columns, so their
+// 512 keeps the plan's 64-row slabs with KV = 4 (Quad below: two passes per 512).
+template <int KV, int ROWS>
+struct Geometry {
+  static constexpr int kv = KV, rows = ROWS;
+};
+template <typename F>
+int with_geometry(int width, int rows, F&& f) {
+  switch (width) {
+    case 64: return f(Geometry<1, 256>{});
+    case 128: return f(Geometry<2, 128>{});
+    case 256: return rows == 80 ? f(Geometry<4, 80>{}) : f(Geometry<4, 128>{});
+    case 512: return f(Geometry<8, 64>{});
+    default: return SPUTNIK_HIP_INVALID_ARGUMENT;
+  }
+}
+
+// A kernel instance as the launcher needs it.  `next`: the instance that adds a later panel
+// into the output (nullptr: this geometry and output type only ever run one pass).
+template <typename T, typename TO>
+struct Instance {
+  using Kernel = void (*)(int, int, int, int, const int*, const int*, const int*, const int*,
+                          const int*, const T*, int64_t, const T*, int64_t, int, TO*, int64_t, int,
+                          int, int, int64_t, int);
+  Kernel first, next;
+  int kdim, rows, slab_bytes, threads;
+};
+template <int KV, int ROWS, bool WITH_NEXT>
+Instance<float, float> stationary_instance() {
+  using S = Slab<KV, ROWS>;
+  Instance<float, float> inst{sddmm_stationary_kernel<KV, false, ROWS>, nullptr, S::kdim, S::kRows,
+                              S::kBytes, S::kThreads};
+  if constexpr (WITH_NEXT) inst.next = sddmm_stationary_kernel<KV, true, ROWS>;
+  return inst;
+}
+template <int KV, int ROWS, typename T, typename TO, bool WITH_NEXT>
+Instance<T, TO> quad_instance() {
+  using Q = Quad<KV, ROWS, T>;
+  Instance<T, TO> inst{sddmm_quad_kernel<KV, ROWS, T, TO, false>, nullptr, Q::kdim, ROWS, Q::kBytes,
+                       Q::kThreads};
+  if constexpr (WITH_NEXT) inst.next = sddmm_quad_kernel<KV, ROWS, T, TO, true>;
+  return inst;
+}
+
+// The launches of one call.  side_by_side (the summed form): every (replica, panel) pair in
+// ONE launch on grid z, each writing its own [nonzeros] vector (z = replica * panels + panel)
+// -- for callers that sum the replicas anyway (the gradient of a weight shared by a batch),
+// so that the panels need not run one after the other.  Otherwise one launch per panel,
+// later panels adding into the output, the replicas in slices of at most kMaxGridYZ.
+template <typename T, typename TO>
+int launch_instance(const Instance<T, TO>& inst, const SddmmArgs& a, int debug, bool side_by_side) {
+  const int slots = slots_of(a.m);
+  const Tables t = tables_in(a.workspace, slots);
+  const int slabs = ceil_div(a.n, inst.rows);
   const int row_blocks = slots / (kSGroups * kSRows);
+  const T* lhs = static_cast<const T*>(a.lhs);
+  const T* rhs = static_cast<const T*>(a.rhs);
+  TO* out = static_cast<TO*>(a.out);
   if (row_blocks > kMaxGridYZ) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  auto run = [&](typename Instance<T, TO>::Kernel kernel, int z, int r0, int k0, int panels) {
+    hipLaunchKernelGGL(kernel, dim3(slabs, launch_rows_y(slabs, row_blocks, z, debug, inst.slab_bytes), z),
+                       dim3(inst.threads), 0, a.stream, a.m, a.n, a.nonzeros, slots, a.row_indices,
+                       a.row_offsets, a.column_indices, t.table, t.row_ok, lhs + r0 * a.lhs_stride + k0,
+                       a.lhs_stride, rhs + r0 * a.rhs_stride + k0, a.rhs_stride, a.k,
+                       out + r0 * a.out_stride, a.out_stride, panels, debug, a.mask_heads,
+                       a.mask_plan_ints, r0);
+    return launch_status();
+  };
+  if (side_by_side) {
+    const int panels = a.k / inst.kdim;
+    if (static_cast<int64_t>(a.replicas) * panels > kMaxGridYZ) return SPUTNIK_HIP_INVALID_ARGUMENT;
+    return run(inst.first, a.replicas * panels, 0, 0, panels);
+  }
   // (more than one mask: their tables came from spmm_chunk_table_masks_kernel, which also
   // ranks them; the knob's word keeps its low bits)
-  debug &= ~kMasksLargestFirst;
-  if (mask_heads > 0 && replicas > mask_heads && replicas <= kMaxGridYZ && !(debug & 64))
+  if (a.mask_heads > 0 && a.replicas > a.mask_heads && a.replicas <= kMaxGridYZ && !(debug & 64))
     debug |= kMasksLargestFirst;
-  for (int k0 = 0; k0 < k; k0 += S::kdim) {  // one launch per panel; later panels accumulate
-    for (int r0 = 0; r0 < replicas; r0 += kMaxGridYZ) {
-      const int rz = min(replicas - r0, kMaxGridYZ);
-      if constexpr (KV == 1) {   // quad form (debug bit 8: the 16-lanes-per-entry kernel; k = 128:
-                                 // 8 chunks per lane and step ran at 128 against 79 us)
-        if (!(debug & 8)) {
-#define SPUTNIK_HIP_QUAD(ACC)                                                                     \
-  hipLaunchKernelGGL((sddmm_quad_kernel<KV, S::kRows, float, float, ACC>),                        \
-                     dim3(slabs, launch_rows_y(slabs, row_blocks, rz, debug, Quad<KV, S::kRows, float>::kBytes), rz), \
-                     dim3(Quad<KV, S::kRows, float>::kThreads), 0,                                \
-                     stream, m, n, nonzeros, slots, row_indices, row_offsets, column_indices,     \
-                     table, row_ok, lhs + r0 * lhs_stride + k0, lhs_stride,                       \
-                     rhs + r0 * rhs_stride + k0, rhs_stride, k, out + r0 * out_stride,            \
-                     out_stride, 1, debug, mask_heads, mask_plan_ints, r0)
-          if (k0 != 0) SPUTNIK_HIP_QUAD(true);
-          else SPUTNIK_HIP_QUAD(false);
-#undef SPUTNIK_HIP_QUAD
-          st = launch_status();
-          if (st != 0) return st;
-          continue;
-        }
-      }
-#define SPUTNIK_HIP_STAT(ACC)                                                                     \
-  hipLaunchKernelGGL((sddmm_stationary_kernel<KV, ACC>),                                          \
-                     dim3(slabs, launch_rows_y(slabs, row_blocks, rz, debug, S::kBytes), rz),                \
-                     dim3(S::kThreads), 0, stream, m, n, nonzeros, slots, row_indices,            \
-                     row_offsets, column_indices, table, row_ok, lhs + r0 * lhs_stride + k0,      \
-                     lhs_stride, rhs + r0 * rhs_stride + k0, rhs_stride, k,                       \
-                     out + r0 * out_stride, out_stride, 1, debug, mask_heads, mask_plan_ints, r0)
-      if (k0 != 0) SPUTNIK_HIP_STAT(true);
-      else SPUTNIK_HIP_STAT(false);
-#undef SPUTNIK_HIP_STAT
-      st = launch_status();
+  for (int k0 = 0; k0 < a.k; k0 += inst.kdim) {  // one launch per panel; later panels accumulate
+    if (k0 != 0 && inst.next == nullptr) return SPUTNIK_HIP_INVALID_ARGUMENT;
+    for (int r0 = 0; r0 < a.replicas; r0 += kMaxGridYZ) {
+      const int st = run(k0 != 0 ? inst.next : inst.first, min(a.replicas - r0, kMaxGridYZ), r0, k0, 1);
       if (st != 0) return st;
     }
   }
   return 0;
 }
 
-// Half operands (T = _Float16 / __bf16), output float or T.  W = width the plan was
-// made for (its slab rows); the kernel's panels are at most 256 wide.
-template <int KV, int ROWS, typename T, typename TO>
-int launch_half(int m, int k, int n, int nonzeros, int replicas, int slots, const int* row_indices,
-                const int* row_offsets, const int* column_indices, const int* table,
-                const int* row_ok, const T* lhs, int64_t lhs_stride, const T* rhs,
-                int64_t rhs_stride, TO* out, int64_t out_stride, int panels_z, int debug,
-                hipStream_t stream, int mask_heads, int64_t mask_plan_ints) {
-  using Q = Quad<KV, ROWS, T>;
-  const int slabs = ceil_div(n, ROWS);
-  const int row_blocks = slots / (kSGroups * kSRows);
-  if (row_blocks > kMaxGridYZ) return SPUTNIK_HIP_INVALID_ARGUMENT;
-  if (panels_z > 1) {   // every (replica, panel) pair at once, each into its own vector
-    if (static_cast<int64_t>(replicas) * panels_z > kMaxGridYZ) return SPUTNIK_HIP_INVALID_ARGUMENT;
-    hipLaunchKernelGGL((sddmm_quad_kernel<KV, ROWS, T, TO, false>),
-                       dim3(slabs, launch_rows_y(slabs, row_blocks, static_cast<int64_t>(replicas) * panels_z, debug, Q::kBytes),
-                            replicas * panels_z),
-                       dim3(Q::kThreads), 0, stream, m, n, nonzeros, slots, row_indices, row_offsets,
-                       column_indices, table, row_ok, lhs, lhs_stride, rhs, rhs_stride, k, out,
-                       out_stride, panels_z, debug, 0, int64_t{0}, 0);
-    return launch_status();
-  }
-  for (int k0 = 0; k0 < k; k0 += Q::kdim) {
-    for (int r0 = 0; r0 < replicas; r0 += kMaxGridYZ) {
-      const int rz = min(replicas - r0, kMaxGridYZ);
-#define SPUTNIK_HIP_QUADH(ACC)                                                                    \
-  hipLaunchKernelGGL((sddmm_quad_kernel<KV, ROWS, T, TO, ACC>),                                   \
-                     dim3(slabs, launch_rows_y(slabs, row_blocks, rz, debug, Q::kBytes), rz),       \
-                     dim3(Q::kThreads), 0, stream, m, n, nonzeros, slots, row_indices,            \
-                     row_offsets, column_indices, table, row_ok, lhs + r0 * lhs_stride + k0,      \
-                     lhs_stride, rhs + r0 * rhs_stride + k0, rhs_stride, k,                       \
-                     out + r0 * out_stride, out_stride, 1, debug, mask_heads, mask_plan_ints, r0)
-      if (k0 != 0) SPUTNIK_HIP_QUADH(true);
-      else SPUTNIK_HIP_QUADH(false);
-#undef SPUTNIK_HIP_QUADH
-      const int st = launch_status();
-      if (st != 0) return st;
-    }
-  }
-  return 0;
-}
-
+// Only instances a call can reach exist (DESIGN.md lists the ones that do not):
+//   * float32 runs the quad kernel at panel width 64 of the plain product only (k = 128: 8
+//     chunks per lane and step ran at 128 against 79 us; SPUTNIK_HIP_SDDMM_DEBUG bit 8: the
+//     16-lanes-per-entry kernel there too), half operands run it at every width;
+//   * the 80-row slab belongs to the summed form: float output, one pass;
+//   * a half output is refused for more than one pass (sddmm_tiled_passes_half), so it has no
+//     accumulating instance and none at width 512.
 template <typename T, typename TO>
-int launch_half_width(int width, int rows /* of the plan's slabs */, int m, int k, int n, int nonzeros, int replicas, int slots,
-                      const int* row_indices, const int* row_offsets, const int* column_indices,
-                      const int* table, const int* row_ok, const void* lhs, int64_t lhs_stride,
-                      const void* rhs, int64_t rhs_stride, void* out, int64_t out_stride,
-                      int panels_z, int debug, hipStream_t stream, int mask_heads,
-                      int64_t mask_plan_ints) {
-#define SPUTNIK_HIP_SDH(KV, ROWS)                                                                  \
-  return launch_half<KV, ROWS, T, TO>(m, k, n, nonzeros, replicas, slots, row_indices, row_offsets, \
-                                      column_indices, table, row_ok, static_cast<const T*>(lhs),   \
-                                      lhs_stride, static_cast<const T*>(rhs), rhs_stride,          \
-                                      static_cast<TO*>(out), out_stride, panels_z, debug, stream,  \
-                                      mask_heads, mask_plan_ints)
-  switch (width) {
-    case 64: SPUTNIK_HIP_SDH(1, 256);
-    case 128: SPUTNIK_HIP_SDH(2, 128);
-    case 256:
-      if (rows == 80) SPUTNIK_HIP_SDH(4, 80);
-      SPUTNIK_HIP_SDH(4, 128);
-    case 512: SPUTNIK_HIP_SDH(4, 64);   // the plan's slabs (64 rows), panels of 256
-    default: return SPUTNIK_HIP_INVALID_ARGUMENT;
-  }
-#undef SPUTNIK_HIP_SDH
+int launch_typed(const SddmmArgs& a, int width, int rows, bool quad, bool side_by_side) {
+  const int debug = options().sddmm_debug & ~kMasksLargestFirst;  // timing experiments only
+  return with_geometry(width, rows, [&](auto geometry) {
+    constexpr int KV = decltype(geometry)::kv, ROWS = decltype(geometry)::rows;
+    constexpr bool kWithNext = std::is_same_v<TO, float> && ROWS != 80;
+    if constexpr (std::is_same_v<T, float>) {
+      if constexpr (KV == 1) {
+        if (quad) return launch_instance(quad_instance<KV, ROWS, float, float, true>(), a, debug, side_by_side);
+      }
+      return launch_instance(stationary_instance<KV, ROWS, kWithNext>(), a, debug, side_by_side);
+    } else if constexpr (!std::is_same_v<TO, float> && (KV == 8 || ROWS == 80)) {
+      return static_cast<int>(SPUTNIK_HIP_INVALID_ARGUMENT);
+    } else {
+      return launch_instance(quad_instance<(KV < 4 ? KV : 4), ROWS, T, TO, kWithNext>(), a, debug, side_by_side);
+    }
+  });
+}
+int launch_of_types(const SddmmArgs& a, int width, int rows, bool quad, bool side_by_side) {
+  const int in = a.in_type, out = a.out_type;
+  if (in == SPUTNIK_HIP_F32 && out == SPUTNIK_HIP_F32) return launch_typed<float, float>(a, width, rows, quad, side_by_side);
+  if (in == SPUTNIK_HIP_F16 && out == SPUTNIK_HIP_F32) return launch_typed<_Float16, float>(a, width, rows, quad, side_by_side);
+  if (in == SPUTNIK_HIP_F16 && out == SPUTNIK_HIP_F16) return launch_typed<_Float16, _Float16>(a, width, rows, quad, side_by_side);
+  if (in == SPUTNIK_HIP_BF16 && out == SPUTNIK_HIP_F32) return launch_typed<__bf16, float>(a, width, rows, quad, side_by_side);
+  if (in == SPUTNIK_HIP_BF16 && out == SPUTNIK_HIP_BF16) return launch_typed<__bf16, __bf16>(a, width, rows, quad, side_by_side);
+  return SPUTNIK_HIP_INVALID_ARGUMENT;
 }
 
-// Every (replica, panel) pair in ONE launch, each writing its own [nonzeros]
-// vector of `partials` (z = replica * panels + panel): for callers that sum the
-// replicas anyway (the gradient of a weight shared by a batch), so that the
-// panels need not run one after the other.
-template <int KV, int ROWS = default_slab_rows(KV)>
-int launch_partials(int m, int k, int n, int nonzeros, int replicas, int slots,
-                    const int* row_indices, const int* row_offsets, const int* column_indices,
-                    const int* table, const int* row_ok, const float* lhs, int64_t lhs_stride,
-                    const float* rhs, int64_t rhs_stride, float* partials, int debug,
-                    hipStream_t stream) {
-  using S = Slab<KV, ROWS>;
-  const int slabs = ceil_div(n, S::kRows);
-  const int row_blocks = slots / (kSGroups * kSRows);
-  const int panels = k / S::kdim;
-  if (row_blocks > kMaxGridYZ || static_cast<int64_t>(replicas) * panels > kMaxGridYZ)
-    return SPUTNIK_HIP_INVALID_ARGUMENT;
-  hipLaunchKernelGGL((sddmm_stationary_kernel<KV, false, ROWS>),
-                     dim3(slabs, launch_rows_y(slabs, row_blocks, static_cast<int64_t>(replicas) * panels, debug, S::kBytes),
-                          replicas * panels),
-                     dim3(S::kThreads), 0, stream, m, n, nonzeros, slots, row_indices, row_offsets,
-                     column_indices, table, row_ok, lhs, lhs_stride, rhs, rhs_stride, k,
-                     partials, static_cast<int64_t>(nonzeros), panels, debug, 0, int64_t{0}, 0);
-  return launch_status();
-}
-
-}  // namespace
-
-int sddmm_tiled_panel_width(int k) { return panel_width(k); }
-int sddmm_tiled_slab_rows(int k) { return panel_width(k) != 0 ? slab_rows_of_width(panel_width(k)) : 0; }
-int sddmm_tiled_sum_slab_rows(int m, int k, int n, int nonzeros) {
-  return served(k) ? sum_slab_rows(m, k, n, nonzeros) : 0;
-}
-
-int sddmm_tiled_panels(int m, int k, int n, int nonzeros) {
-  return served(k) ? k / sum_panel_width(m, k, n, nonzeros) : 1;
-}
-
-int sddmm_tiled_launch_partials(int m, int k, int n, int nonzeros, int replicas,
-                                const int* row_indices, const int* row_offsets,
-                                const int* column_indices, const float* lhs, int64_t lhs_stride,
-                                const float* rhs, int64_t rhs_stride, float* partials,
-                                const void* workspace, hipStream_t stream) {
-  const int debug = options().sddmm_debug & ~kMasksLargestFirst;
-  const int slots = slots_of(m);
-  const int* row_ok = static_cast<const int*>(workspace);
-  const int* table =
-      reinterpret_cast<const int*>(static_cast<const char*>(workspace) + row_ok_bytes(slots));
-#define SPUTNIK_HIP_SD(KV)                                                                  \
-  return launch_partials<KV>(m, k, n, nonzeros, replicas, slots, row_indices, row_offsets, \
-                             column_indices, table, row_ok, lhs, lhs_stride, rhs,          \
-                             rhs_stride, partials, debug, stream)
-  switch (sum_panel_width(m, k, n, nonzeros)) {
-    case 64: SPUTNIK_HIP_SD(1);
-    case 128: SPUTNIK_HIP_SD(2);
-    case 256:
-      if (sum_slab_rows(m, k, n, nonzeros) == 80)
-        return launch_partials<4, 80>(m, k, n, nonzeros, replicas, slots, row_indices, row_offsets,
-                                      column_indices, table, row_ok, lhs, lhs_stride, rhs,
-                                      rhs_stride, partials, debug, stream);
-      SPUTNIK_HIP_SD(4);
-    case 512: SPUTNIK_HIP_SD(8);
-    default: return SPUTNIK_HIP_INVALID_ARGUMENT;
-  }
-#undef SPUTNIK_HIP_SD
-}
-
-bool sddmm_tiled_applicable(int m, int k, int n, int nonzeros, const float* lhs,
-                            int64_t lhs_stride, const float* rhs, int64_t rhs_stride) {
-  return served(k) && n >= 16 && m >= 16 && nonzeros >= 4 * static_cast<int64_t>(m) &&
-         static_cast<int64_t>(n) * k * 4 < (int64_t{1} << 32) &&
-         static_cast<int64_t>(m) * k * 4 < (int64_t{1} << 32) && nonzeros < (1 << 29) &&
-         aligned_to(lhs, 16) && aligned_to(rhs, 16) && lhs_stride % 4 == 0 && rhs_stride % 4 == 0;
-}
-
-// `summed`: for sddmm_tiled_launch_partials (its panel width, hence its slabs and
-// its chunk table, can differ from the plain product's).
-namespace {
 // Tables of the rhs-stationary kernels alone.
 size_t table_bytes(int m, int k, int n, int nonzeros, bool summed) {
   if (!served(k) || n < 16 || m < 16 || nonzeros < 4 * static_cast<int64_t>(m)) return 0;
@@ -944,7 +849,35 @@ bool flat_shape(int m, int k, int n, int nonzeros) {
 size_t flat_plan_offset(int m, int k, int n, int nonzeros) {
   return (table_bytes(m, k, n, nonzeros, false) + 255) / 256 * 256;
 }
+
 }  // namespace
+
+int sddmm_tiled_panel_width(int k) { return panel_width(k); }
+int sddmm_tiled_slab_rows(int k) { return panel_width(k) != 0 ? slab_rows_of_width(panel_width(k)) : 0; }
+int sddmm_tiled_sum_slab_rows(int m, int k, int n, int nonzeros) {
+  return served(k) ? sum_slab_rows(m, k, n, nonzeros) : 0;
+}
+int sddmm_tiled_panels(int m, int k, int n, int nonzeros) {
+  return served(k) ? k / sum_panel_width(m, k, n, nonzeros) : 1;
+}
+// Kernel launches the plain product makes for one replica on half operands (more than one:
+// later passes add into the output, which a half OUTPUT would round every time).
+int sddmm_tiled_passes_half(int k) { return served(k) ? k / min(panel_width(k), 256) : 1; }
+// Summed form on half operands: float partial vectors, one per (replica, panel).
+// Served when the summed plan's panel width is at most 256 (always, up to k = 4096).
+bool sddmm_tiled_sum_half_served(int m, int k, int n, int nonzeros) {
+  return served(k) && sum_panel_width(m, k, n, nonzeros) <= 256;
+}
+
+// 32-bit byte offsets inside an operand; rows that start on 16 bytes.
+bool sddmm_tiled_applicable(const SddmmArgs& a, int elem_bytes) {
+  const int64_t per16 = 16 / elem_bytes;
+  return served(a.k) && a.n >= 16 && a.m >= 16 && a.nonzeros >= 4 * static_cast<int64_t>(a.m) &&
+         static_cast<int64_t>(a.n) * a.k * elem_bytes < (int64_t{1} << 32) &&
+         static_cast<int64_t>(a.m) * a.k * elem_bytes < (int64_t{1} << 32) && a.nonzeros < (1 << 29) &&
+         aligned_to(a.lhs, 16) && aligned_to(a.rhs, 16) && a.lhs_stride % per16 == 0 &&
+         a.rhs_stride % per16 == 0;
+}
 
 size_t sddmm_tiled_workspace_bytes(int m, int k, int n, int nonzeros, bool summed) {
   const size_t tables = table_bytes(m, k, n, nonzeros, summed);
@@ -952,138 +885,70 @@ size_t sddmm_tiled_workspace_bytes(int m, int k, int n, int nonzeros, bool summe
   return flat_plan_offset(m, k, n, nonzeros) + sddmm_flat_plan_bytes(m, n, nonzeros);
 }
 
+// The chunk table is the SpMM one with the mask's columns (n) in the role of k,
+// cut at slab boundaries.  Topology only: a caller with a static mask runs it once.
 // with_flat: also the pair-flat kernel's plan (sddmm_flat.hip) -- for plans that are KEPT
 // (sputnik_hip_sddmm_plan: a static mask); a call that plans for itself and throws the
 // plan away takes the tables only (one 5 us launch against a memset and four launches).
-int sddmm_tiled_plan(int m, int k, int n, int nonzeros, const int* row_indices,
-                     const int* row_offsets, const int* column_indices, void* workspace,
-                     hipStream_t stream, bool summed, bool with_flat, int masks,
-                     int64_t mask_plan_ints) {
-  if (with_flat && !summed && flat_shape(m, k, n, nonzeros)) {
-    const int st = sddmm_flat_plan(m, n, nonzeros, row_indices, row_offsets, column_indices,
-                                   static_cast<char*>(workspace) + flat_plan_offset(m, k, n, nonzeros),
-                                   stream);
+// masks > 1: concatenated topologies, all masks' tables in one launch.
+int sddmm_tiled_plan(const SddmmArgs& a, bool summed, bool with_flat, int masks) {
+  if (with_flat && !summed && flat_shape(a.m, a.k, a.n, a.nonzeros)) {
+    const int st = sddmm_flat_plan(a.m, a.n, a.nonzeros, a.row_indices, a.row_offsets, a.column_indices,
+                                   static_cast<char*>(a.workspace) + flat_plan_offset(a.m, a.k, a.n, a.nonzeros),
+                                   a.stream);
     if (st != 0) return st;
   }
-  const int slots = slots_of(m);
-  int* row_ok = static_cast<int*>(workspace);
-  int* table = reinterpret_cast<int*>(static_cast<char*>(workspace) + row_ok_bytes(slots));
-  switch (width_for(m, k, n, nonzeros, summed)) {
-    case 64: return plan<1>(m, n, slots, row_indices, row_offsets, column_indices, table, row_ok, stream, masks, mask_plan_ints);
-    case 128: return plan<2>(m, n, slots, row_indices, row_offsets, column_indices, table, row_ok, stream, masks, mask_plan_ints);
-    case 256:
-      if (rows_for(m, k, n, nonzeros, summed) == 80)
-        return plan<4, 80>(m, n, slots, row_indices, row_offsets, column_indices, table, row_ok, stream, masks, mask_plan_ints);
-      return plan<4>(m, n, slots, row_indices, row_offsets, column_indices, table, row_ok, stream, masks, mask_plan_ints);
-    case 512: return plan<8>(m, n, slots, row_indices, row_offsets, column_indices, table, row_ok, stream, masks, mask_plan_ints);
-    default: return SPUTNIK_HIP_INVALID_ARGUMENT;
-  }
+  const int slots = slots_of(a.m);
+  const Tables t = tables_in(a.workspace, slots);
+  return with_geometry(width_for(a.m, a.k, a.n, a.nonzeros, summed), rows_for(a.m, a.k, a.n, a.nonzeros, summed),
+                       [&](auto geometry) {
+    constexpr int ROWS = decltype(geometry)::rows;
+    if (masks > 1) {
+      if (masks > kMaxGridYZ) return static_cast<int>(SPUTNIK_HIP_INVALID_ARGUMENT);
+      hipLaunchKernelGGL((spmm_chunk_table_masks_kernel<ROWS>), dim3(ceil_div(slots, 4), masks),
+                         dim3(256), 0, a.stream, a.m, a.n, slots, kSGroups * kSRows, ceil_div(a.n, ROWS),
+                         a.row_indices, a.row_offsets, a.column_indices, t.table, t.row_ok,
+                         a.mask_plan_ints);
+    } else {
+      hipLaunchKernelGGL((spmm_chunk_table_kernel<ROWS>), dim3(ceil_div(slots, 4)), dim3(256), 0,
+                         a.stream, a.m, a.n, slots, kSGroups * kSRows, ceil_div(a.n, ROWS),
+                         a.row_indices, a.row_offsets, a.column_indices, t.table, t.row_ok);
+    }
+    return launch_status();
+  });
 }
 
-// Kernels only, on a planned workspace.
-int sddmm_tiled_launch(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
-                       const int* row_offsets, const int* column_indices, const float* lhs,
-                       int64_t lhs_stride, const float* rhs, int64_t rhs_stride, float* out,
-                       int64_t out_stride, const void* workspace, hipStream_t stream,
-                       int mask_heads, int64_t mask_plan_ints, bool flat) {
-  if (flat && mask_heads == 0 && sddmm_flat_applicable(m, k, n, nonzeros, 4))
-    return sddmm_flat_launch(m, k, n, nonzeros, replicas, row_indices, lhs, lhs_stride, rhs,
-                             rhs_stride, out, out_stride, SPUTNIK_HIP_F32, SPUTNIK_HIP_F32,
-                             static_cast<const char*>(workspace) + flat_plan_offset(m, k, n, nonzeros),
-                             stream);
-  const int debug = options().sddmm_debug & ~kMasksLargestFirst;  // timing experiments only
-  const int slots = slots_of(m);
-  const int* row_ok = static_cast<const int*>(workspace);
-  const int* table =
-      reinterpret_cast<const int*>(static_cast<const char*>(workspace) + row_ok_bytes(slots));
-#define SPUTNIK_HIP_SD(KV)                                                               \
-  return launch<KV>(m, k, n, nonzeros, replicas, slots, row_indices, row_offsets,        \
-                    column_indices, table, row_ok, lhs, lhs_stride, rhs, rhs_stride, out, \
-                    out_stride, debug, stream, mask_heads, mask_plan_ints)
-  switch (panel_width(k)) {
-    case 64: SPUTNIK_HIP_SD(1);
-    case 128: SPUTNIK_HIP_SD(2);
-    case 256: SPUTNIK_HIP_SD(4);
-    case 512: SPUTNIK_HIP_SD(8);
-    default: return SPUTNIK_HIP_INVALID_ARGUMENT;
-  }
-#undef SPUTNIK_HIP_SD
+SddmmKernel sddmm_tiled_kernel(const SddmmArgs& a, bool flat) {
+  const int elem_bytes = sddmm_elem_bytes(a.in_type);
+  if (flat && a.mask_heads == 0 && sddmm_flat_applicable(a.m, a.k, a.n, a.nonzeros, elem_bytes))
+    return SddmmKernel::kFlat;
+  const bool quad = elem_bytes == 2 || (panel_width(a.k) == 64 && !(options().sddmm_debug & 8));
+  return quad ? SddmmKernel::kQuad : SddmmKernel::kStationary;
 }
 
-
-// Native half operands (in_type SPUTNIK_HIP_F16 / BF16; out_type float or in_type).
-bool sddmm_tiled_applicable_half(int m, int k, int n, int nonzeros, const void* lhs,
-                                 int64_t lhs_stride, const void* rhs, int64_t rhs_stride) {
-  return served(k) && n >= 16 && m >= 16 && nonzeros >= 4 * static_cast<int64_t>(m) &&
-         static_cast<int64_t>(n) * k * 2 < (int64_t{1} << 32) &&
-         static_cast<int64_t>(m) * k * 2 < (int64_t{1} << 32) && nonzeros < (1 << 29) &&
-         aligned_to(lhs, 16) && aligned_to(rhs, 16) && lhs_stride % 8 == 0 && rhs_stride % 8 == 0;
-}
-// Kernel launches the plain product makes for one replica (more than one: later
-// passes add into the output, which a half OUTPUT would round every time).
-int sddmm_tiled_passes_half(int k) { return served(k) ? k / min(panel_width(k), 256) : 1; }
-
-int sddmm_tiled_launch_half(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
-                            const int* row_offsets, const int* column_indices, const void* lhs,
-                            int64_t lhs_stride, const void* rhs, int64_t rhs_stride, void* out,
-                            int64_t out_stride, int in_type, int out_type, const void* workspace,
-                            hipStream_t stream, int mask_heads, int64_t mask_plan_ints, bool flat) {
-  if (flat && mask_heads == 0 && sddmm_flat_applicable(m, k, n, nonzeros, 2))
-    return sddmm_flat_launch(m, k, n, nonzeros, replicas, row_indices, lhs, lhs_stride, rhs,
-                             rhs_stride, out, out_stride, in_type, out_type,
-                             static_cast<const char*>(workspace) + flat_plan_offset(m, k, n, nonzeros),
-                             stream);
-  const int debug = options().sddmm_debug & ~kMasksLargestFirst;
-  const int slots = slots_of(m);
-  const int* row_ok = static_cast<const int*>(workspace);
-  const int* table =
-      reinterpret_cast<const int*>(static_cast<const char*>(workspace) + row_ok_bytes(slots));
-  const int width = panel_width(k);
-#define SPUTNIK_HIP_SDT(T, TO)                                                                    \
-  return launch_half_width<T, TO>(width, slab_rows_of_width(width), m, k, n, nonzeros, replicas, slots, row_indices, \
-                                  row_offsets, column_indices, table, row_ok, lhs, lhs_stride,    \
-                                  rhs, rhs_stride, out, out_stride, 1, debug, stream, mask_heads, \
-                                  mask_plan_ints)
-  if (in_type == SPUTNIK_HIP_F16 && out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_SDT(_Float16, float);
-  if (in_type == SPUTNIK_HIP_F16 && out_type == SPUTNIK_HIP_F16) SPUTNIK_HIP_SDT(_Float16, _Float16);
-  if (in_type == SPUTNIK_HIP_BF16 && out_type == SPUTNIK_HIP_F32) SPUTNIK_HIP_SDT(__bf16, float);
-  if (in_type == SPUTNIK_HIP_BF16 && out_type == SPUTNIK_HIP_BF16) SPUTNIK_HIP_SDT(__bf16, __bf16);
-#undef SPUTNIK_HIP_SDT
-  return SPUTNIK_HIP_INVALID_ARGUMENT;
+int sddmm_tiled_launch(const SddmmArgs& a, bool flat) {
+  const SddmmKernel kernel = sddmm_tiled_kernel(a, flat);
+  if (kernel == SddmmKernel::kFlat)
+    return sddmm_flat_launch(a.m, a.k, a.n, a.nonzeros, a.replicas, a.row_indices, a.lhs, a.lhs_stride,
+                             a.rhs, a.rhs_stride, a.out, a.out_stride, a.in_type, a.out_type,
+                             static_cast<const char*>(a.workspace) + flat_plan_offset(a.m, a.k, a.n, a.nonzeros),
+                             a.stream);
+  const int width = panel_width(a.k);
+  return launch_of_types(a, width, width != 0 ? slab_rows_of_width(width) : 0,
+                         kernel == SddmmKernel::kQuad, /*side_by_side=*/false);
 }
 
-// Summed form on half operands: float partial vectors, one per (replica, panel).
-// Served when the summed plan's panel width is at most 256 (always, up to k = 4096).
-bool sddmm_tiled_sum_half_served(int m, int k, int n, int nonzeros) {
-  return served(k) && sum_panel_width(m, k, n, nonzeros) <= 256;
-}
-int sddmm_tiled_launch_partials_half(int m, int k, int n, int nonzeros, int replicas,
-                                     const int* row_indices, const int* row_offsets,
-                                     const int* column_indices, const void* lhs,
-                                     int64_t lhs_stride, const void* rhs, int64_t rhs_stride,
-                                     int in_type, float* partials, const void* workspace,
-                                     hipStream_t stream) {
-  const int debug = options().sddmm_debug & ~kMasksLargestFirst;
-  const int slots = slots_of(m);
-  const int* row_ok = static_cast<const int*>(workspace);
-  const int* table =
-      reinterpret_cast<const int*>(static_cast<const char*>(workspace) + row_ok_bytes(slots));
-  const int width = sum_panel_width(m, k, n, nonzeros);
-  if (width > 256) return SPUTNIK_HIP_UNSUPPORTED;
-  const int panels = k / width;
-  if (in_type == SPUTNIK_HIP_F16)
-    return launch_half_width<_Float16, float>(width, sum_slab_rows(m, k, n, nonzeros), m, k, n, nonzeros, replicas, slots, row_indices,
-                                              row_offsets, column_indices, table, row_ok, lhs,
-                                              lhs_stride, rhs, rhs_stride, partials,
-                                              static_cast<int64_t>(nonzeros), panels, debug, stream,
-                                              0, int64_t{0});
-  if (in_type == SPUTNIK_HIP_BF16)
-    return launch_half_width<__bf16, float>(width, sum_slab_rows(m, k, n, nonzeros), m, k, n, nonzeros, replicas, slots, row_indices,
-                                            row_offsets, column_indices, table, row_ok, lhs,
-                                            lhs_stride, rhs, rhs_stride, partials,
-                                            static_cast<int64_t>(nonzeros), panels, debug, stream,
-                                            0, int64_t{0});
-  return SPUTNIK_HIP_INVALID_ARGUMENT;
+int sddmm_tiled_launch_partials(const SddmmArgs& a) {
+  const int width = sum_panel_width(a.m, a.k, a.n, a.nonzeros);
+  const bool half = sddmm_elem_bytes(a.in_type) == 2;
+  if (half && width > 256) return SPUTNIK_HIP_UNSUPPORTED;
+  SddmmArgs p = a;   // (one vector per (replica, panel); one topology for all replicas)
+  p.out_type = SPUTNIK_HIP_F32;
+  p.out_stride = a.nonzeros;
+  p.mask_heads = 0;
+  p.mask_plan_ints = 0;
+  return launch_of_types(p, width, sum_slab_rows(a.m, a.k, a.n, a.nonzeros), /*quad=*/half,
+                         /*side_by_side=*/true);
 }
 
 }  // namespace sputnik_hip
