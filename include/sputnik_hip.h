@@ -120,6 +120,40 @@ SPUTNIK_HIP_API int sputnik_hip_sddmm_sum_route(int m, int k, int n, int nonzero
                                                 int in_type, int planned, int mixed, int* kernel,
                                                 int* panel_width, int* panels, int* slab_rows,
                                                 int* splits);
+/* What an SDDMM call of this shape launches under the current options, down to the kernel
+ * instance and its grid, when the workspace (and the summed form's scratch) are as large as
+ * the size queries ask and the operands are 16-byte aligned and contiguous: operands stored as
+ * `in_type`, output as `out_type` (SPUTNIK_HIP_F32 / F16 / BF16; float32 or in_type);
+ * `planned` != 0: on a workspace that sputnik_hip_sddmm_plan / _sum_plan filled; `summed` != 0:
+ * the summed form (sputnik_hip_sddmm_sum_batched / _typed; out_type float32), whose launch of
+ * the partial products is described; `mask_heads` > 0: a sputnik_hip_sddmm_many_mask call of
+ * replicas / mask_heads masks, `nonzeros` the largest mask's count (float32, not summed).
+ *   family       SPUTNIK_HIP_SDDMM_ROWWAVE / _FLAT / _QUAD / _STATIONARY, or _MFMA (the summed
+ *                form's matrix-core route)
+ *   panel_width  columns of k a launch works on (_QUAD, _STATIONARY; _FLAT: k; 0 otherwise)
+ *   slab_rows    rows of rhs per slab (_QUAD, _STATIONARY; _MFMA: rows of the output tile)
+ *   passes       launches per replica slice, one panel each (1 for the summed form, whose
+ *                panels lie side by side on grid z)
+ *   accumulates  1: passes after the first run the instance that adds into the output
+ *   grid_x, grid_y, grid_z   of the first launch (_QUAD, _STATIONARY; 0 otherwise): slabs, the
+ *                row blocks of 256 rows a launch spreads over y, replicas (summed: replicas *
+ *                panels)
+ *   row_blocks   ceil(m / 256): with grid_y < row_blocks a workgroup walks several row blocks
+ * The call runs the launch path itself and launches nothing; any output pointer may be NULL.
+ * Returns SPUTNIK_HIP_INVALID_ARGUMENT for a call that launches nothing or for types no entry
+ * point accepts, SPUTNIK_HIP_UNSUPPORTED where the call itself would.  For tests, which assert
+ * the instance and the grid they mean to reach. */
+#define SPUTNIK_HIP_SDDMM_ROWWAVE 0
+#define SPUTNIK_HIP_SDDMM_FLAT 1
+#define SPUTNIK_HIP_SDDMM_QUAD 2
+#define SPUTNIK_HIP_SDDMM_STATIONARY 3
+#define SPUTNIK_HIP_SDDMM_MFMA 4
+SPUTNIK_HIP_API int sputnik_hip_sddmm_launch_shape(int m, int k, int n, int nonzeros, int replicas,
+                                                   int in_type, int out_type, int planned,
+                                                   int summed, int mask_heads, int* family,
+                                                   int* panel_width, int* slab_rows, int* passes,
+                                                   int* accumulates, int* grid_x, int* grid_y,
+                                                   int* grid_z, int* row_blocks);
 /* The instance of the sparse softmax kernel (softmax.hip) that a call of this shape launches
  * for its first grid slice under the current options: values stored as `dtype`
  * (SPUTNIK_HIP_F32 / F16 / BF16), `backward` != 0 for the gradient.  The class is

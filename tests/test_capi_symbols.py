@@ -49,6 +49,24 @@ def test_workspace_queries_are_host_only():
     assert capi.csr_transpose_workspace_bytes(0, 0, 0) == 0
 
 
+def test_sddmm_launch_query_is_host_only():
+    """sputnik_hip_sddmm_launch_shape runs the launch path without a device and reports the
+    instance and the grid: the row-wave kernel below the tiled route's shapes, and the LDS
+    kernels' family, panel, slab, passes and grid at config 3's shape (1024 x 64 x 1024)."""
+    import torch
+    from torch_sputnik_amd import capi
+    assert "sputnik_hip_sddmm_launch_shape" in declared_symbols()
+    assert set(capi.SDDMM_FAMILIES) == {"rowwave", "flat", "quad", "stationary", "mfma"}
+    assert capi.sddmm_launch_shape(72, 72, 72, 500, 1)["family"] == "rowwave"
+    shape = capi.sddmm_launch_shape(1024, 64, 1024, 104860, 64)
+    assert shape == dict(family="quad", panel_width=64, slab_rows=256, passes=1, accumulates=False,
+                         grid_x=4, grid_y=4, grid_z=64, row_blocks=4)
+    assert capi.sddmm_launch_shape(1024, 64, 1024, 104860, 64, planned=True)["family"] == "flat"
+    half = capi.sddmm_launch_shape(1024, 512, 1024, 104860, 8, torch.float16)
+    assert (half["family"], half["panel_width"], half["slab_rows"], half["passes"], half["accumulates"]) == \
+        ("quad", 256, 64, 2, True)
+
+
 def test_ops_registered_without_cpu_kernels():
     """The product registers HIP kernels only: CPU tensors must raise."""
     import pytest

@@ -39,6 +39,7 @@ SIGNATURES = {
     "sputnik_hip_left_spmm_half_tiles_tile_rows": (_c_int, [_c_int] * 3),
     "sputnik_hip_sddmm_kernel_name": (ctypes.c_char_p, [_c_int] * 7),
     "sputnik_hip_sddmm_sum_route": (_c_int, [_c_int] * 8 + [_c_ptr] * 5),
+    "sputnik_hip_sddmm_launch_shape": (_c_int, [_c_int] * 10 + [_c_ptr] * 9),
     "sputnik_hip_sparse_softmax_route": (_c_int, [_c_int] * 5 + [_c_ptr] * 6),
     "sputnik_hip_reload_options": (None, []),
     "sputnik_hip_spmm": (_c_int, [_c_int] * 4 + [_c_ptr] * 7),
@@ -302,6 +303,28 @@ def sddmm_sum_route(m, k, n, nonzeros, replicas, dtype=torch.float32, planned=Fa
     route = {name: o.value for name, o in zip(names, outs)}
     route["kernel"] = SUM_KERNELS[route["kernel"]]
     return route
+
+
+SDDMM_FAMILIES = ("rowwave", "flat", "quad", "stationary", "mfma")   # SPUTNIK_HIP_SDDMM_ROWWAVE / ...
+
+
+def sddmm_launch_shape(m, k, n, nonzeros, replicas, dtype=torch.float32, out_dtype=torch.float32,
+                       planned=False, summed=False, mask_heads=0):
+    """What an SDDMM call of this shape launches under the current options: a dict of family (one
+    of SDDMM_FAMILIES), panel_width, slab_rows, passes, accumulates, grid_x, grid_y, grid_z and
+    row_blocks (include/sputnik_hip.h).  `summed`: the summed form; `mask_heads` > 0: a many-mask
+    call, `nonzeros` the largest mask's count.  Host only."""
+    names = ("family", "panel_width", "slab_rows", "passes", "accumulates", "grid_x", "grid_y",
+             "grid_z", "row_blocks")
+    outs = [_c_int(-1) for _ in names]
+    _check(lib().sputnik_hip_sddmm_launch_shape(
+        m, k, n, nonzeros, replicas, TYPE_CODES[dtype], TYPE_CODES[out_dtype], int(bool(planned)),
+        int(bool(summed)), mask_heads, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
+        "sputnik_hip_sddmm_launch_shape")
+    shape = {name: o.value for name, o in zip(names, outs)}
+    shape["family"] = SDDMM_FAMILIES[shape["family"]]
+    shape["accumulates"] = bool(shape["accumulates"])
+    return shape
 
 
 def sparse_softmax_route(m, nonzeros, replicas, dtype=torch.float32, backward=False):

@@ -380,7 +380,7 @@ SddmmKernel plain_route(const SddmmArgs& a, bool planned) {
 // plain_route and in sum_route, marked "float32:" / "half:".
 // A half output the kernels cannot give in one pass: SPUTNIK_HIP_UNSUPPORTED, the caller
 // takes a float output.
-int sddmm_exec(SddmmArgs a, bool planned) {
+int sddmm_exec(SddmmArgs a, bool planned, SddmmLaunchShape* shape = nullptr) {
   const bool half = a.in_type != SPUTNIK_HIP_F32;
   const bool half_out = a.out_type != SPUTNIK_HIP_F32;
   const size_t out_elem = sddmm_elem_bytes(a.out_type);
@@ -403,17 +403,21 @@ int sddmm_exec(SddmmArgs a, bool planned) {
   if (a.mask_heads > 0)
     a.mask_plan_ints = static_cast<int64_t>(sddmm_many_mask_plan_bytes(a.m, a.k, a.n, a.nonzeros) / sizeof(int));
   if (plain_route(a, planned) != SddmmKernel::kRowWave) {
-    if (!planned) {
+    if (!planned && shape == nullptr) {
       // (many mask: the tables of all topologies in ONE launch, round 4; the masks share
       // m, n and k, so they share the table's shape)
       const int st = sddmm_tiled_plan(a, /*summed=*/false, /*with_flat=*/false,
                                       a.mask_heads > 0 ? a.replicas / a.mask_heads : 1);
       if (st != 0) return st;
     }
-    return sddmm_tiled_launch(a, /*flat=*/planned);
+    return sddmm_tiled_launch(a, /*flat=*/planned, shape);
   }
   // half output on the row-wave kernel: the whole k in one panel (64 lanes x VEC x 4)
   if (half_out && (a.k > 1024 || rowwave_vec(a) * 256 < a.k)) return SPUTNIK_HIP_UNSUPPORTED;
+  if (shape != nullptr) {
+    *shape = SddmmLaunchShape{SddmmKernel::kRowWave, 0, 0, 1, false, 0, 0, 0, 0};
+    return 0;
+  }
   if (!half) return rowwave<float, float>(a);
   if (a.in_type == SPUTNIK_HIP_F16) return half_out ? rowwave<_Float16, _Float16>(a) : rowwave<_Float16, float>(a);
   return half_out ? rowwave<__bf16, __bf16>(a) : rowwave<__bf16, float>(a);
@@ -577,8 +581,9 @@ SumRoute sum_route(const SddmmArgs& a, bool planned, int planes = 1) {
 // `leave_parts` != nullptr: the call stops in front of its last launch and says how many
 // partial vectors of `nonzeros` floats it left in `scratch` (0: `out` is complete) -- for
 // sputnik_hip_sddmm_sum_group_planned, which adds the vectors of several calls in one launch.
+// `shape` != nullptr: nothing is launched, the launch of the partial products is described there.
 int sddmm_sum_exec(const SddmmArgs& a, bool planned, void* scratch, size_t scratch_bytes,
-                   int* leave_parts = nullptr) {
+                   int* leave_parts = nullptr, SddmmLaunchShape* shape = nullptr) {
   float* out = static_cast<float*>(a.out);
   if (leave_parts != nullptr) *leave_parts = 0;
   if (a.m < 0 || a.k < 0 || a.n < 0 || a.nonzeros < 0 || a.replicas < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
@@ -590,6 +595,10 @@ int sddmm_sum_exec(const SddmmArgs& a, bool planned, void* scratch, size_t scrat
     return static_cast<int>(e);
   }
   const SumRoute route = sum_route(a, planned);
+  if (route.kernel == SPUTNIK_HIP_SUM_MFMA && shape != nullptr) {
+    *shape = SddmmLaunchShape{SddmmKernel::kMfma, 0, route.slab_rows, 1, false, 0, 0, 0, 0};
+    return 0;
+  }
   if (route.kernel == SPUTNIK_HIP_SUM_MFMA)
     return sum_on_matrix_cores(a.m, a.k, a.n, a.nonzeros, a.replicas, a.row_offsets, a.column_indices,
                                a.lhs, a.lhs_stride, a.rhs, a.rhs_stride, a.in_type, out, a.workspace,
@@ -599,27 +608,27 @@ int sddmm_sum_exec(const SddmmArgs& a, bool planned, void* scratch, size_t scrat
     // workspace": a workspace handed over as a const plan is rewritten here.  Kept as it is:
     // the fix changes routes and timing)
     // (route.panel_width != 0: the plain product takes the tiled kernels, sum_route)
-    return sddmm_exec(one_part_call(a, route.panel_width != 0), /*planned=*/false);
+    return sddmm_exec(one_part_call(a, route.panel_width != 0), /*planned=*/false, shape);
   const bool tiled = route.kernel == SPUTNIK_HIP_SUM_TILED;
   const int64_t parts = static_cast<int64_t>(a.replicas) * route.panels;
-  if (scratch == nullptr || !aligned_to(scratch, 16) ||
-      scratch_bytes < sizeof(float) * static_cast<size_t>(parts) * a.nonzeros)
+  if (shape == nullptr && (scratch == nullptr || !aligned_to(scratch, 16) ||
+                           scratch_bytes < sizeof(float) * static_cast<size_t>(parts) * a.nonzeros))
     return SPUTNIK_HIP_INVALID_ARGUMENT;
   SddmmArgs p = a;   // the partial vectors: one per (replica, panel), or one per replica
   p.out = scratch;
   p.out_type = SPUTNIK_HIP_F32;
   int st;
   if (tiled) {
-    st = planned ? 0 : sddmm_tiled_plan(a, /*summed=*/true);
-    if (st == 0) st = sddmm_tiled_launch_partials(p);
+    st = planned || shape != nullptr ? 0 : sddmm_tiled_plan(a, /*summed=*/true);
+    if (st == 0) st = sddmm_tiled_launch_partials(p, shape);
   } else {
     // (row-wave kernel: the workspace, planned for the summed form or not, is not used)
     p.out_stride = a.nonzeros;
     p.workspace = nullptr;
     p.workspace_bytes = 0;
-    st = sddmm_exec(p, /*planned=*/false);
+    st = sddmm_exec(p, /*planned=*/false, shape);
   }
-  if (st != 0) return st;
+  if (st != 0 || shape != nullptr) return st;
   if (leave_parts != nullptr) {
     *leave_parts = static_cast<int>(parts);
     return 0;
@@ -873,6 +882,47 @@ int sputnik_hip_sddmm_sum_route(int m, int k, int n, int nonzeros, int replicas,
   if (panels != nullptr) *panels = r.panels;
   if (slab_rows != nullptr) *slab_rows = r.slab_rows;
   if (splits != nullptr) *splits = r.splits;
+  return 0;
+}
+
+// The launch query runs the launch path itself (sddmm_exec / sddmm_sum_exec down to
+// launch_instance in sddmm_tiled.hip) on the call the bindings would make (shape_call), with a
+// SddmmLaunchShape to fill in place of the launches: no decision is restated here.
+int sputnik_hip_sddmm_launch_shape(int m, int k, int n, int nonzeros, int replicas, int in_type,
+                                   int out_type, int planned, int summed, int mask_heads,
+                                   int* family, int* panel_width, int* slab_rows, int* passes,
+                                   int* accumulates, int* grid_x, int* grid_y, int* grid_z,
+                                   int* row_blocks) {
+  if (m <= 0 || k <= 0 || n <= 0 || nonzeros <= 0 || replicas <= 0 || mask_heads < 0)
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const bool half = in_type == SPUTNIK_HIP_F16 || in_type == SPUTNIK_HIP_BF16;
+  if (!half && in_type != SPUTNIK_HIP_F32) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (out_type != SPUTNIK_HIP_F32 && (out_type != in_type || summed != 0)) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  // (many masks: float32, the plain product, whole groups of `mask_heads` replicas)
+  if (mask_heads > 0 && (half || summed != 0 || replicas % mask_heads != 0)) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  SddmmLaunchShape shape{};
+  int st;
+  if (summed != 0) {
+    st = sddmm_sum_exec(shape_call(m, k, n, nonzeros, replicas, in_type, sum_workspace_bytes(m, k, n, nonzeros)),
+                        planned != 0, nullptr, 0, nullptr, &shape);
+  } else {
+    const size_t bytes = mask_heads > 0 ? sddmm_many_mask_plan_bytes(m, k, n, nonzeros) * (replicas / mask_heads)
+                                        : sddmm_tiled_workspace_bytes(m, k, n, nonzeros);
+    SddmmArgs a = shape_call(m, k, n, nonzeros, replicas, in_type, bytes);
+    a.out_type = out_type;
+    a.mask_heads = mask_heads;
+    st = sddmm_exec(a, planned != 0, &shape);
+  }
+  if (st != 0) return st;
+  if (family != nullptr) *family = static_cast<int>(shape.kernel);
+  if (panel_width != nullptr) *panel_width = shape.panel_width;
+  if (slab_rows != nullptr) *slab_rows = shape.slab_rows;
+  if (passes != nullptr) *passes = shape.passes;
+  if (accumulates != nullptr) *accumulates = shape.accumulates ? 1 : 0;
+  if (grid_x != nullptr) *grid_x = shape.slabs;
+  if (grid_y != nullptr) *grid_y = shape.grid_y;
+  if (grid_z != nullptr) *grid_z = shape.grid_z;
+  if (row_blocks != nullptr) *row_blocks = shape.row_blocks;
   return 0;
 }
 

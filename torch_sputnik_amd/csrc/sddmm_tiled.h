@@ -26,7 +26,18 @@ struct SddmmArgs {
 };
 inline int sddmm_elem_bytes(int type) { return type == SPUTNIK_HIP_F32 ? 4 : 2; }
 
-enum class SddmmKernel { kRowWave, kFlat, kQuad, kStationary };
+// (the values are the SPUTNIK_HIP_SDDMM_* family codes of include/sputnik_hip.h; kMfma: the
+// summed form's matrix-core route, sddmm_mfma.hip)
+enum class SddmmKernel { kRowWave = 0, kFlat = 1, kQuad = 2, kStationary = 3, kMfma = 4 };
+
+// What a call launches, as sputnik_hip_sddmm_launch_shape reports it (include/sputnik_hip.h):
+// filled by the launch functions below INSTEAD of launching when they are handed one.
+struct SddmmLaunchShape {
+  SddmmKernel kernel;
+  int panel_width, slab_rows, passes;
+  bool accumulates;          // later passes run the instance that adds into the output
+  int slabs, grid_y, grid_z, row_blocks;   // of the first launch (grid x = slabs)
+};
 
 // sddmm_tiled.hip.  `summed`: the form summed over the replicas (its panel width, hence
 // its slabs and its chunk table, can differ from the plain product's).
@@ -35,8 +46,9 @@ size_t sddmm_tiled_workspace_bytes(int m, int k, int n, int nonzeros, bool summe
 int sddmm_tiled_plan(const SddmmArgs& a, bool summed = false, bool with_flat = false, int masks = 1);
 // Kernels only, on a planned workspace.  `flat`: the plan carries the pair-flat kernel's lists.
 SddmmKernel sddmm_tiled_kernel(const SddmmArgs& a, bool flat);   // which one the launch runs
-int sddmm_tiled_launch(const SddmmArgs& a, bool flat = false);
-int sddmm_tiled_launch_partials(const SddmmArgs& a);   // a.out: float [replicas * panels][nonzeros]
+int sddmm_tiled_launch(const SddmmArgs& a, bool flat = false, SddmmLaunchShape* shape = nullptr);
+// a.out: float [replicas * panels][nonzeros]
+int sddmm_tiled_launch_partials(const SddmmArgs& a, SddmmLaunchShape* shape = nullptr);
 int sddmm_tiled_panels(int m, int k, int n, int nonzeros);
 int sddmm_tiled_panel_width(int k);
 int sddmm_tiled_slab_rows(int k);                                  // of the plain product's plan

@@ -755,43 +755,71 @@ Instance<T, TO> quad_instance() {
   return inst;
 }
 
+// What one call launches: every decision of launch_instance (plan_launches makes them), which
+// the launch query (sputnik_hip_sddmm_launch_shape) reads back instead of launching.  `z`: grid z
+// of the first launch; `debug`: the kernels' word (the knob's, plus kMasksLargestFirst); grid y
+// of a launch over z replicas / pairs: rows_y(z).
+struct LaunchPlan {
+  int slots, slabs, row_blocks, slab_bytes, passes, panels_on_z, z, debug;
+  int rows_y(int64_t z_here) const { return launch_rows_y(slabs, row_blocks, z_here, debug, slab_bytes); }
+};
+template <typename T, typename TO>
+int plan_launches(const Instance<T, TO>& inst, const SddmmArgs& a, int debug, bool side_by_side, LaunchPlan* plan) {
+  const int slots = slots_of(a.m);
+  LaunchPlan p{slots, ceil_div(a.n, inst.rows), slots / (kSGroups * kSRows), inst.slab_bytes, 1, 1, 0, debug};
+  if (p.row_blocks > kMaxGridYZ) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (side_by_side) {
+    p.panels_on_z = a.k / inst.kdim;
+    if (static_cast<int64_t>(a.replicas) * p.panels_on_z > kMaxGridYZ) return SPUTNIK_HIP_INVALID_ARGUMENT;
+    p.z = a.replicas * p.panels_on_z;
+  } else {
+    // (more than one mask: their tables came from spmm_chunk_table_masks_kernel, which also
+    // ranks them; the knob's word keeps its low bits)
+    if (a.mask_heads > 0 && a.replicas > a.mask_heads && a.replicas <= kMaxGridYZ && !(debug & 64))
+      p.debug |= kMasksLargestFirst;
+    p.passes = a.k / inst.kdim;   // one launch per panel; later panels accumulate
+    if (p.passes > 1 && inst.next == nullptr) return SPUTNIK_HIP_INVALID_ARGUMENT;
+    p.z = min(a.replicas, kMaxGridYZ);   // (of the first slice)
+  }
+  *plan = p;
+  return 0;
+}
+
 // The launches of one call.  side_by_side (the summed form): every (replica, panel) pair in
 // ONE launch on grid z, each writing its own [nonzeros] vector (z = replica * panels + panel)
 // -- for callers that sum the replicas anyway (the gradient of a weight shared by a batch),
 // so that the panels need not run one after the other.  Otherwise one launch per panel,
 // later panels adding into the output, the replicas in slices of at most kMaxGridYZ.
+// `shape` != nullptr: nothing is launched, the call's launches are described there.
 template <typename T, typename TO>
-int launch_instance(const Instance<T, TO>& inst, const SddmmArgs& a, int debug, bool side_by_side) {
-  const int slots = slots_of(a.m);
-  const Tables t = tables_in(a.workspace, slots);
-  const int slabs = ceil_div(a.n, inst.rows);
-  const int row_blocks = slots / (kSGroups * kSRows);
+int launch_instance(const Instance<T, TO>& inst, const SddmmArgs& a, int debug, bool side_by_side,
+                    bool quad, SddmmLaunchShape* shape) {
+  LaunchPlan plan;
+  if (const int st = plan_launches(inst, a, debug, side_by_side, &plan); st != 0) return st;
+  if (shape != nullptr) {
+    *shape = SddmmLaunchShape{quad ? SddmmKernel::kQuad : SddmmKernel::kStationary, inst.kdim, inst.rows,
+                              plan.passes, plan.passes > 1, plan.slabs,
+                              plan.rows_y(plan.z), plan.z, plan.row_blocks};
+    return 0;
+  }
+  const Tables t = tables_in(a.workspace, plan.slots);
   const T* lhs = static_cast<const T*>(a.lhs);
   const T* rhs = static_cast<const T*>(a.rhs);
   TO* out = static_cast<TO*>(a.out);
-  if (row_blocks > kMaxGridYZ) return SPUTNIK_HIP_INVALID_ARGUMENT;
   auto run = [&](typename Instance<T, TO>::Kernel kernel, int z, int r0, int k0, int panels) {
-    hipLaunchKernelGGL(kernel, dim3(slabs, launch_rows_y(slabs, row_blocks, z, debug, inst.slab_bytes), z),
-                       dim3(inst.threads), 0, a.stream, a.m, a.n, a.nonzeros, slots, a.row_indices,
+    hipLaunchKernelGGL(kernel, dim3(plan.slabs, plan.rows_y(z), z),
+                       dim3(inst.threads), 0, a.stream, a.m, a.n, a.nonzeros, plan.slots, a.row_indices,
                        a.row_offsets, a.column_indices, t.table, t.row_ok, lhs + r0 * a.lhs_stride + k0,
                        a.lhs_stride, rhs + r0 * a.rhs_stride + k0, a.rhs_stride, a.k,
-                       out + r0 * a.out_stride, a.out_stride, panels, debug, a.mask_heads,
+                       out + r0 * a.out_stride, a.out_stride, panels, plan.debug, a.mask_heads,
                        a.mask_plan_ints, r0);
     return launch_status();
   };
-  if (side_by_side) {
-    const int panels = a.k / inst.kdim;
-    if (static_cast<int64_t>(a.replicas) * panels > kMaxGridYZ) return SPUTNIK_HIP_INVALID_ARGUMENT;
-    return run(inst.first, a.replicas * panels, 0, 0, panels);
-  }
-  // (more than one mask: their tables came from spmm_chunk_table_masks_kernel, which also
-  // ranks them; the knob's word keeps its low bits)
-  if (a.mask_heads > 0 && a.replicas > a.mask_heads && a.replicas <= kMaxGridYZ && !(debug & 64))
-    debug |= kMasksLargestFirst;
-  for (int k0 = 0; k0 < a.k; k0 += inst.kdim) {  // one launch per panel; later panels accumulate
-    if (k0 != 0 && inst.next == nullptr) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (side_by_side) return run(inst.first, plan.z, 0, 0, plan.panels_on_z);
+  for (int pass = 0; pass < plan.passes; ++pass) {
     for (int r0 = 0; r0 < a.replicas; r0 += kMaxGridYZ) {
-      const int st = run(k0 != 0 ? inst.next : inst.first, min(a.replicas - r0, kMaxGridYZ), r0, k0, 1);
+      const int st = run(pass != 0 ? inst.next : inst.first, min(a.replicas - r0, kMaxGridYZ), r0,
+                         pass * inst.kdim, 1);
       if (st != 0) return st;
     }
   }
@@ -806,30 +834,32 @@ int launch_instance(const Instance<T, TO>& inst, const SddmmArgs& a, int debug, 
 //   * a half output is refused for more than one pass (sddmm_tiled_passes_half), so it has no
 //     accumulating instance and none at width 512.
 template <typename T, typename TO>
-int launch_typed(const SddmmArgs& a, int width, int rows, bool quad, bool side_by_side) {
+int launch_typed(const SddmmArgs& a, int width, int rows, bool quad, bool side_by_side,
+                 SddmmLaunchShape* shape) {
   const int debug = options().sddmm_debug & ~kMasksLargestFirst;  // timing experiments only
   return with_geometry(width, rows, [&](auto geometry) {
     constexpr int KV = decltype(geometry)::kv, ROWS = decltype(geometry)::rows;
     constexpr bool kWithNext = std::is_same_v<TO, float> && ROWS != 80;
     if constexpr (std::is_same_v<T, float>) {
       if constexpr (KV == 1) {
-        if (quad) return launch_instance(quad_instance<KV, ROWS, float, float, true>(), a, debug, side_by_side);
+        if (quad) return launch_instance(quad_instance<KV, ROWS, float, float, true>(), a, debug, side_by_side, true, shape);
       }
-      return launch_instance(stationary_instance<KV, ROWS, kWithNext>(), a, debug, side_by_side);
+      return launch_instance(stationary_instance<KV, ROWS, kWithNext>(), a, debug, side_by_side, false, shape);
     } else if constexpr (!std::is_same_v<TO, float> && (KV == 8 || ROWS == 80)) {
       return static_cast<int>(SPUTNIK_HIP_INVALID_ARGUMENT);
     } else {
-      return launch_instance(quad_instance<(KV < 4 ? KV : 4), ROWS, T, TO, kWithNext>(), a, debug, side_by_side);
+      return launch_instance(quad_instance<(KV < 4 ? KV : 4), ROWS, T, TO, kWithNext>(), a, debug, side_by_side, true, shape);
     }
   });
 }
-int launch_of_types(const SddmmArgs& a, int width, int rows, bool quad, bool side_by_side) {
+int launch_of_types(const SddmmArgs& a, int width, int rows, bool quad, bool side_by_side,
+                    SddmmLaunchShape* shape) {
   const int in = a.in_type, out = a.out_type;
-  if (in == SPUTNIK_HIP_F32 && out == SPUTNIK_HIP_F32) return launch_typed<float, float>(a, width, rows, quad, side_by_side);
-  if (in == SPUTNIK_HIP_F16 && out == SPUTNIK_HIP_F32) return launch_typed<_Float16, float>(a, width, rows, quad, side_by_side);
-  if (in == SPUTNIK_HIP_F16 && out == SPUTNIK_HIP_F16) return launch_typed<_Float16, _Float16>(a, width, rows, quad, side_by_side);
-  if (in == SPUTNIK_HIP_BF16 && out == SPUTNIK_HIP_F32) return launch_typed<__bf16, float>(a, width, rows, quad, side_by_side);
-  if (in == SPUTNIK_HIP_BF16 && out == SPUTNIK_HIP_BF16) return launch_typed<__bf16, __bf16>(a, width, rows, quad, side_by_side);
+  if (in == SPUTNIK_HIP_F32 && out == SPUTNIK_HIP_F32) return launch_typed<float, float>(a, width, rows, quad, side_by_side, shape);
+  if (in == SPUTNIK_HIP_F16 && out == SPUTNIK_HIP_F32) return launch_typed<_Float16, float>(a, width, rows, quad, side_by_side, shape);
+  if (in == SPUTNIK_HIP_F16 && out == SPUTNIK_HIP_F16) return launch_typed<_Float16, _Float16>(a, width, rows, quad, side_by_side, shape);
+  if (in == SPUTNIK_HIP_BF16 && out == SPUTNIK_HIP_F32) return launch_typed<__bf16, float>(a, width, rows, quad, side_by_side, shape);
+  if (in == SPUTNIK_HIP_BF16 && out == SPUTNIK_HIP_BF16) return launch_typed<__bf16, __bf16>(a, width, rows, quad, side_by_side, shape);
   return SPUTNIK_HIP_INVALID_ARGUMENT;
 }
 
@@ -926,8 +956,12 @@ SddmmKernel sddmm_tiled_kernel(const SddmmArgs& a, bool flat) {
   return quad ? SddmmKernel::kQuad : SddmmKernel::kStationary;
 }
 
-int sddmm_tiled_launch(const SddmmArgs& a, bool flat) {
+int sddmm_tiled_launch(const SddmmArgs& a, bool flat, SddmmLaunchShape* shape) {
   const SddmmKernel kernel = sddmm_tiled_kernel(a, flat);
+  if (kernel == SddmmKernel::kFlat && shape != nullptr) {   // (its grid is its plan's: sddmm_flat.hip)
+    *shape = SddmmLaunchShape{kernel, a.k, 0, 1, false, 0, 0, 0, 0};
+    return 0;
+  }
   if (kernel == SddmmKernel::kFlat)
     return sddmm_flat_launch(a.m, a.k, a.n, a.nonzeros, a.replicas, a.row_indices, a.lhs, a.lhs_stride,
                              a.rhs, a.rhs_stride, a.out, a.out_stride, a.in_type, a.out_type,
@@ -935,10 +969,10 @@ int sddmm_tiled_launch(const SddmmArgs& a, bool flat) {
                              a.stream);
   const int width = panel_width(a.k);
   return launch_of_types(a, width, width != 0 ? slab_rows_of_width(width) : 0,
-                         kernel == SddmmKernel::kQuad, /*side_by_side=*/false);
+                         kernel == SddmmKernel::kQuad, /*side_by_side=*/false, shape);
 }
 
-int sddmm_tiled_launch_partials(const SddmmArgs& a) {
+int sddmm_tiled_launch_partials(const SddmmArgs& a, SddmmLaunchShape* shape) {
   const int width = sum_panel_width(a.m, a.k, a.n, a.nonzeros);
   const bool half = sddmm_elem_bytes(a.in_type) == 2;
   if (half && width > 256) return SPUTNIK_HIP_UNSUPPORTED;
@@ -948,7 +982,7 @@ int sddmm_tiled_launch_partials(const SddmmArgs& a) {
   p.mask_heads = 0;
   p.mask_plan_ints = 0;
   return launch_of_types(p, width, sum_slab_rows(a.m, a.k, a.n, a.nonzeros), /*quad=*/half,
-                         /*side_by_side=*/true);
+                         /*side_by_side=*/true, shape);
 }
 
 }  // namespace sputnik_hip
