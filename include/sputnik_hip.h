@@ -1280,6 +1280,82 @@ SPUTNIK_HIP_API int sputnik_hip_csr_transpose_many_mask_route(int masks, int m, 
                              int with_permutation, size_t workspace_bytes, int* one_launch,
                              int* values_by);
 
+/* ========================================================================
+ * CSR topologies from dense masks / matrices, built on the device (topology.hip).
+ * What topology.dense_to_sparse, dense_to_sparse_3d, diffsort and
+ * functional.diffsort_many_mask compute (modules/sparse_attention.py:12-36,
+ * tests/transformer/utils.py:17-62 of the reference), in a fixed number of
+ * launches for any number of masks.  No workspace.
+ *
+ * `dense` holds `masks` matrices of m x n elements of `element_bytes` (1, 2, 4 or 8)
+ * bytes: element (i, r, c) at dense + i * batch_stride + r * row_stride + c, strides
+ * in ELEMENTS and >= 0 (0: one matrix shared by all masks, or one row by all rows),
+ * the last dimension dense.  An element is a nonzero exactly when torch's `x != 0`
+ * says so, decided on its bits: `floating` = 0 (bool and integer types) any bit set,
+ * `floating` = 1 (float16, bfloat16, float32, float64) any bit but the sign -- -0.0
+ * is no entry, NaN, +-inf and denormals are.
+ * ====================================================================== */
+
+/* Phase 1.  row_offsets [masks][m + 1] (int32, each mask's starting at 0), nonzeros [masks]
+ * (int32) and bases [masks] (int64: the entries of the masks in front, where a mask's
+ * column_indices start in the concatenated many-mask layout), all on the device.  Three
+ * launches (rows, a scan per mask, the bases); asynchronous.  The caller reads `nonzeros`
+ * back to size column_indices -- the one synchronisation of a build.
+ * SPUTNIK_HIP_INVALID_ARGUMENT: a negative size or stride, an element width other than
+ * 1 / 2 / 4 / 8, m * n above INT_MAX (a mask's count must fit its int32 offsets), a grid
+ * above INT_MAX workgroups, a pointer that is NULL or not aligned to its element. */
+SPUTNIK_HIP_API int sputnik_hip_dense_to_csr_count(int masks, int m, int n, const void* dense,
+                             int element_bytes, int floating, int64_t batch_stride,
+                             int64_t row_stride, int* row_offsets, int* nonzeros, int64_t* bases,
+                             sputnik_hip_stream_t stream);
+
+/* Phase 2, given phase 1's row_offsets and bases: column_indices [sum of nonzeros] (int32),
+ * ascending inside every row, the masks' arrays back to back; and, `values` not NULL, the
+ * kept elements themselves, copied bit for bit in the source type, in the same order.  One
+ * launch: per step of 64 elements a wave ballot and a lane prefix count place the kept
+ * ones.  Arguments are checked as in phase 1. */
+SPUTNIK_HIP_API int sputnik_hip_dense_to_csr_fill(int masks, int m, int n, const void* dense,
+                             int element_bytes, int floating, int64_t batch_stride,
+                             int64_t row_stride, const int* row_offsets, const int64_t* bases,
+                             int* column_indices, void* values, sputnik_hip_stream_t stream);
+
+/* The instance count and fill run for a call of this shape; both entries take their
+ * decisions from the same function this reports, and from nothing else.
+ *   elements_per_lane    elements of one 16-byte load: 16 / element_bytes
+ *   rows_per_wave        16 / 8 / 4 / 2 / 1: a group of 64 / rows_per_wave lanes walks a row,
+ *                        (64 / rows_per_wave) * elements_per_lane columns per step; the most
+ *                        rows whose group still covers n columns in one step, i.e. it halves
+ *                        above n = 4, 8, 16 and 32 times elements_per_lane
+ *   rows_per_workgroup   4 waves: 4 * rows_per_wave
+ *   grid                 masks * ceil(m / rows_per_workgroup) workgroups of 256 threads
+ * Host only, launches nothing; any output pointer may be NULL.  Returns
+ * SPUTNIK_HIP_INVALID_ARGUMENT where the entries would for these sizes. */
+SPUTNIK_HIP_API int sputnik_hip_dense_to_csr_launch_shape(int masks, int m, int n, int element_bytes,
+                             int* rows_per_wave, int* elements_per_lane,
+                             int* rows_per_workgroup, int* grid);
+
+/* row_indices [masks][m] (int32): the rows of each mask by ascending length
+ * row_offsets[i][r + 1] - row_offsets[i][r], ties by ascending row -- exactly
+ * torch.argsort(lengths, stable=True), the reference's diffsort (modules/spmm.py:4-6).
+ * row_offsets [masks][m + 1] may come from anywhere (phase 1, a transpose).  ONE launch for all
+ * masks, one workgroup per mask sorting the unique 64-bit keys (length, row) in LDS; nothing
+ * on the host depends on the data, so the launch can be captured in a graph.  `n` bounds no
+ * length (every int32 length fits the key); it is validated only.  Serves m <= 16384:
+ * SPUTNIK_HIP_INVALID_ARGUMENT beyond, and for a negative size or a NULL pointer. */
+SPUTNIK_HIP_API int sputnik_hip_csr_row_order(int masks, int m, int n, const int* row_offsets,
+                             int* row_indices, sputnik_hip_stream_t stream);
+
+/* Whether sputnik_hip_csr_row_order serves a call of this shape, and with which instance; the
+ * entry takes its decisions from the same function this reports, and from nothing else.
+ *   served      1 for m <= 16384, else 0 (the other fields are -1 then)
+ *   capacity    keys the instance holds in LDS: 2048 (m <= 2048) or 16384
+ *   threads     its workgroup: 256 or 1024
+ *   sort_size   keys the network sorts: the power of two at or above m
+ * Host only, launches nothing; any output pointer may be NULL.  Returns
+ * SPUTNIK_HIP_INVALID_ARGUMENT for a negative size. */
+SPUTNIK_HIP_API int sputnik_hip_csr_row_order_route(int masks, int m, int n, int* served,
+                             int* capacity, int* threads, int* sort_size);
+
 /*
  * out[r][i] = in[r][permutation[i]], i < n, for `rows` value arrays (strides in
  * elements) that share one permutation: the values of a static pattern in the

@@ -20,7 +20,13 @@ from .ops import (  # noqa: F401
     sparse_softmax,
     spmm,
 )
-from .topology import dense_to_sparse, dense_to_sparse_3d, diffsort, generate_mask  # noqa: F401
+from .topology import (  # noqa: F401
+    dense_to_sparse,
+    dense_to_sparse_3d,
+    diffsort,
+    enable_device_build,
+    generate_mask,
+)
 from .functional import Sddmm, SparseLinearFunction, SparseSoftmax, Spmm  # noqa: F401
 from .modules import SparseAttention, SparseCoreAttention, SparseLinear  # noqa: F401
 

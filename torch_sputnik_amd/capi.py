@@ -97,6 +97,13 @@ SIGNATURES = {
     "sputnik_hip_csr_transpose_route": (_c_int, [_c_int] * 3 + [_c_ptr] * 7),
     "sputnik_hip_csr_transpose_many_mask_route": (_c_int, [_c_int] * 4 + [_c_i64, _c_int, _c_int, _c_size,
                                                                          _c_ptr, _c_ptr]),
+    "sputnik_hip_dense_to_csr_count": (_c_int, [_c_int] * 3 + [_c_ptr, _c_int, _c_int, _c_i64, _c_i64,
+                                                              _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
+    "sputnik_hip_dense_to_csr_fill": (_c_int, [_c_int] * 3 + [_c_ptr, _c_int, _c_int, _c_i64, _c_i64,
+                                                             _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
+    "sputnik_hip_dense_to_csr_launch_shape": (_c_int, [_c_int] * 4 + [_c_ptr] * 4),
+    "sputnik_hip_csr_row_order": (_c_int, [_c_int] * 3 + [_c_ptr, _c_ptr, _c_ptr]),
+    "sputnik_hip_csr_row_order_route": (_c_int, [_c_int] * 3 + [_c_ptr] * 4),
     "sputnik_hip_csr_transpose_checked": (_c_int, [_c_int] * 4 + [_c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_size, _c_ptr]),
@@ -485,6 +492,32 @@ def csr_transpose_many_mask_route(masks, m, n, nonzeros, heads, with_permutation
         "sputnik_hip_csr_transpose_many_mask_route")
     one_launch, values_by = bool(outs[0].value), outs[1].value
     return {"one_launch": one_launch, "values_by": MANY_VALUES[values_by] if values_by >= 0 else None}
+
+
+def dense_to_csr_launch_shape(masks, m, n, element_bytes):
+    """The count / fill instance of the device topology build for `masks` dense matrices of
+    m x n elements of that width: a dict of rows_per_wave, elements_per_lane, rows_per_workgroup
+    and grid (include/sputnik_hip.h).  Host only; raises for sizes the entries reject."""
+    names = ("rows_per_wave", "elements_per_lane", "rows_per_workgroup", "grid")
+    outs = [_c_int(-1) for _ in names]
+    _check(lib().sputnik_hip_dense_to_csr_launch_shape(
+        masks, m, n, element_bytes, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
+        "sputnik_hip_dense_to_csr_launch_shape")
+    return {name: o.value for name, o in zip(names, outs)}
+
+
+def csr_row_order_route(masks, m, n):
+    """Whether the row-order kernel serves `masks` masks of m rows and n columns, and how: a dict
+    of served (bool), capacity, threads and sort_size (include/sputnik_hip.h; -1 where it does
+    not serve).  Host only."""
+    names = ("served", "capacity", "threads", "sort_size")
+    outs = [_c_int(-1) for _ in names]
+    _check(lib().sputnik_hip_csr_row_order_route(
+        masks, m, n, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
+        "sputnik_hip_csr_row_order_route")
+    route = {name: o.value for name, o in zip(names, outs)}
+    route["served"] = bool(route["served"])
+    return route
 
 
 def csr_transpose(m, n, replicas, values, row_offsets, column_indices, out_values,

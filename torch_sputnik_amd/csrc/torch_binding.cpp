@@ -1865,6 +1865,85 @@ std::vector<Tensor> csr_transpose_many_mask(int64_t b, int64_t m64, int64_t n64,
   return {out_values, out_row_offsets, out_column_indices};
 }
 
+// ---- CSR topologies built on the device (sputnik_hip.h: dense_to_csr_*, csr_row_order) ----
+
+// row_offsets [m + 1] or [b, m + 1] -> row_indices [m] / [b, m]: the rows of every mask by
+// ascending length, ties by row (topology.diffsort).  One launch on the current stream, no
+// synchronisation, torch allocations only: capturable.
+Tensor row_order(const Tensor& row_offsets_in) {
+  TORCH_CHECK(row_offsets_in.is_cuda(), "row_offsets must be a GPU (HIP) tensor, got ",
+              row_offsets_in.device());
+  TORCH_CHECK(row_offsets_in.scalar_type() == at::kInt, "row_offsets must be int32, got ",
+              row_offsets_in.scalar_type());
+  TORCH_CHECK((row_offsets_in.dim() == 1 || row_offsets_in.dim() == 2) && row_offsets_in.size(-1) >= 1,
+              "row_offsets should be [m + 1] or [b, m + 1], got ", row_offsets_in.sizes());
+  const c10::DeviceGuard guard(row_offsets_in.device());
+  const Tensor row_offsets = row_offsets_in.contiguous();
+  const int masks = row_offsets.dim() == 2 ? to_int(row_offsets.size(0), "b") : 1;
+  const int m = to_int(row_offsets.size(-1) - 1, "m");
+  int served = 0;
+  check_status(sputnik_hip_csr_row_order_route(masks, m, 0, &served, nullptr, nullptr, nullptr),
+               "row_order");
+  TORCH_CHECK(served, "torch_sputnik::row_order: ", m, " rows per mask are beyond the kernel "
+              "(sputnik_hip_csr_row_order_route); take torch.argsort");
+  Tensor row_indices = row_offsets.dim() == 2 ? at::empty({masks, m}, row_offsets.options())
+                                              : at::empty({m}, row_offsets.options());
+  check_status(sputnik_hip_csr_row_order(masks, m, 0, row_offsets.data_ptr<int>(),
+                                         row_indices.data_ptr<int>(), current_stream(row_offsets)),
+               "row_order");
+  return row_indices;
+}
+
+// dense [m, n], [b, m, n] or [b, 1, m, n] -> [row_indices, row_offsets, column_indices,
+// nonzeros (int64, host)] (+ values, 2-D only): topology.dense_to_sparse / dense_to_sparse_3d.
+// Count and row order are launched, the b counts are read back -- the ONE synchronisation: the
+// operators take `nonzeros` on the host, and column_indices is allocated at its exact size --
+// and the fill is launched.  Views with a dense last dimension are read in place.
+std::vector<Tensor> dense_to_csr(const Tensor& dense_in, bool with_values) {
+  TORCH_CHECK(dense_in.is_cuda(), "dense must be a GPU (HIP) tensor, got ", dense_in.device());
+  TORCH_CHECK(dense_in.dim() >= 2 && dense_in.dim() <= 4,
+              "expected a [m, n], [b, m, n] or [b, 1, m, n] tensor, got ", dense_in.sizes());
+  TORCH_CHECK(dense_in.dim() != 4 || dense_in.size(1) == 1,
+              "expected a [b, 1, m, n] tensor, got ", dense_in.sizes());
+  TORCH_CHECK(!with_values || dense_in.dim() == 2, "values are returned for 2-D inputs only");
+  const auto type = dense_in.scalar_type();
+  TORCH_CHECK(!c10::isComplexType(type) && !c10::isQIntType(type), "unsupported element type ", type);
+  const c10::DeviceGuard guard(dense_in.device());
+  Tensor dense = dense_in.dim() == 4 ? dense_in.select(1, 0) : dense_in;
+  if (dense.size(-1) > 1 && dense.stride(-1) != 1) dense = dense.contiguous();
+  const bool batched = dense.dim() == 3;
+  const int masks = batched ? to_int(dense.size(0), "b") : 1;
+  const int m = to_int(dense.size(-2), "m"), n = to_int(dense.size(-1), "n");
+  const int64_t batch_stride = batched && masks > 1 ? dense.stride(0) : 0;
+  const int64_t row_stride = m > 1 ? dense.stride(-2) : 0;
+  const int element_bytes = static_cast<int>(dense.element_size());
+  const int floating = c10::isFloatingType(type) ? 1 : 0;
+  const auto index_options = dense.options().dtype(at::kInt);
+  Tensor row_offsets = batched ? at::empty({masks, m + 1}, index_options) : at::empty({m + 1}, index_options);
+  Tensor counts = at::empty({masks}, index_options);
+  Tensor bases = at::empty({masks}, dense.options().dtype(at::kLong));
+  const auto stream = current_stream(dense);
+  check_status(sputnik_hip_dense_to_csr_count(masks, m, n, dense.data_ptr(), element_bytes, floating,
+                                              batch_stride, row_stride, row_offsets.data_ptr<int>(),
+                                              counts.data_ptr<int>(), bases.data_ptr<int64_t>(), stream),
+               "dense_to_csr (count)");
+  Tensor row_indices = row_order(row_offsets);
+  Tensor nonzeros = counts.to(at::kCPU).to(at::kLong);   // the synchronisation
+  const int64_t total = nonzeros.sum().item<int64_t>();
+  Tensor column_indices = at::empty({total}, index_options);
+  Tensor values;
+  if (with_values) values = at::empty({total}, dense.options());
+  if (total > 0)
+    check_status(sputnik_hip_dense_to_csr_fill(masks, m, n, dense.data_ptr(), element_bytes, floating,
+                                               batch_stride, row_stride, row_offsets.data_ptr<int>(),
+                                               bases.data_ptr<int64_t>(), column_indices.data_ptr<int>(),
+                                               with_values ? values.data_ptr() : nullptr, stream),
+                 "dense_to_csr (fill)");
+  std::vector<Tensor> out{row_indices, row_offsets, column_indices, nonzeros};
+  if (with_values) out.push_back(values);
+  return out;
+}
+
 // ---- the fused attention with one mask per batch element (sputnik_hip.h:
 // sparse_attention_many_mask_*, sparse_attention_heads_many_mask_*) ----
 
@@ -2304,6 +2383,8 @@ TORCH_LIBRARY(torch_sputnik, m) {
   m.def(
       "csr_transpose_many_mask(int b, int m, int n, Tensor nonzeros, Tensor values, "
       "Tensor row_offsets, Tensor column_indices) -> Tensor[]");
+  m.def("dense_to_csr(Tensor dense, bool with_values) -> Tensor[]");
+  m.def("row_order(Tensor row_offsets) -> Tensor");
   m.def(
       "sparse_attention_many_mask(int b, Tensor nonzeros, Tensor query, Tensor key, Tensor value, "
       "Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, bool want_lse, "
@@ -2400,6 +2481,8 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("sparse_softmax_many_mask_scaled", &sparse_softmax_many_mask_scaled);
   m.impl("sparse_softmax_backward_many_mask", &sparse_softmax_backward_many_mask);
   m.impl("csr_transpose_many_mask", &csr_transpose_many_mask);
+  m.impl("dense_to_csr", &dense_to_csr);
+  m.impl("row_order", &row_order);
   m.impl("sparse_attention_many_mask", &sparse_attention_many_mask);
   m.impl("sparse_attention_many_mask_plan", &sparse_attention_many_mask_plan);
   m.impl("sparse_attention_heads_many_mask", &sparse_attention_heads_many_mask);

@@ -16,7 +16,7 @@ import collections
 import torch
 
 from . import ops
-from .topology import diffsort
+from .topology import diffsort, diffsort_many
 
 
 def _identity(*tensors):
@@ -1165,9 +1165,9 @@ def sparse_attention_heads(query, key, value, heads, row_indices, row_offsets, c
 # ---------------------------------------------------------------------------
 def diffsort_many_mask(row_offsets, masks):
     """Per-mask ``diffsort`` of stacked / concatenated offsets
-    (tests/transformer/utils.py:51-62) -> flat [masks * rows]."""
-    per_mask = row_offsets.reshape(masks, -1)
-    return torch.cat([diffsort(per_mask[i]) for i in range(masks)])
+    (tests/transformer/utils.py:51-62) -> flat [masks * rows].  On the GPU one launch for
+    all masks and no synchronisation (``topology.diffsort_many``)."""
+    return diffsort_many(row_offsets, masks)
 
 
 class SpmmManyMask(torch.autograd.Function):

@@ -344,6 +344,11 @@ class SparseCoreAttention(nn.Module):
     inputs are read in place as head views, float32 inputs are copied once to [b*n, s, hn]
     as the reference does.  ``topology=`` (the tuple topology.dense_to_sparse_3d returns)
     lets a caller with a static mask skip the per-call conversion; `mask` is then unused.
+    A dynamic GPU mask costs one device build per forward (topology.dense_to_sparse_3d ->
+    ops.dense_to_csr): five small launches and ONE host synchronisation for any b, where the
+    torch loop took a dozen launches and a synchronisation per batch element
+    (tools/topology_build_bench.py measures both; topology.enable_device_build(False) brings
+    the loop back).
     ``attention_dropout`` = p: Megatron's dropout on the attention probabilities, applied in
     training mode inside the fused kernel (functional.sparse_attention_heads_many_mask)."""
 

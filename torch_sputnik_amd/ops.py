@@ -236,6 +236,24 @@ def csr_transpose_many_mask(b, m, n, nonzeros, values, row_offsets, column_indic
                                         row_offsets, column_indices)
 
 
+def dense_to_csr(dense, with_values=False):
+    """CSR topology of a dense mask or matrix, built on the device (csrc/topology.hip):
+    dense [m, n], [b, m, n] or [b, 1, m, n] of any real dtype, an element is an entry where
+    ``x != 0``.  -> [row_indices, row_offsets, column_indices, nonzeros] in the many-mask layout
+    (row_indices [b, m], row_offsets [b, m + 1], no batch dimension for 2-D input; `nonzeros`
+    an int64 host tensor, the form ``_counts`` passes through), plus ``values`` (the entries in
+    the input's dtype, 2-D input only) ``with_values``.  A fixed number of launches and one
+    synchronisation for any b; views with a dense last dimension are read in place."""
+    return _ops.dense_to_csr(dense, bool(with_values))
+
+
+def row_order(row_offsets):
+    """row_offsets [m + 1] or [b, m + 1] (int32) -> row_indices [m] / [b, m]: every mask's rows
+    by ascending length, ties by row -- ``topology.diffsort`` per mask in one launch, no
+    synchronisation.  Raises beyond the rows ``capi.csr_row_order_route`` serves."""
+    return _ops.row_order(row_offsets)
+
+
 def sparse_attention_many_mask(b, nonzeros, row_indices, row_offsets, column_indices, query, key,
                                value, scale, with_lse=False, plan=None):
     """softmax(scale * q k^T at the mask) v with one mask per batch element in ONE kernel:

@@ -1,8 +1,43 @@
 """CSR topology helpers the reference duplicates in every module
 (modules/spmm.py:4-6, modules/sparse_linear.py:5-16,
-modules/sparse_attention.py:12-36).  Pure torch, device-agnostic."""
+modules/sparse_attention.py:12-36).  CPU tensors take pure torch; GPU tensors are
+built by the device kernels of csrc/topology.hip (``ops.dense_to_csr``,
+``ops.row_order``) where their host queries serve the shape -- the same integers
+either way (``enable_device_build``)."""
 import numpy as np
 import torch
+
+from . import capi, ops
+
+_device_build = True
+
+# element types ops.dense_to_csr reads: 1, 2, 4 and 8 bytes wide, every real dtype of torch
+_BUILD_DTYPES = (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64,
+                 torch.float16, torch.bfloat16, torch.float32, torch.float64)
+
+
+def enable_device_build(enabled=True):
+    """True (the default): GPU tensors get their topologies from the device kernels
+    (a fixed number of launches, one synchronisation per build, none per row order).
+    False: the torch path for every tensor -- the same results, for comparison."""
+    global _device_build
+    _device_build = bool(enabled)
+    return _device_build
+
+
+def _row_order_served(masks, rows):
+    """(the kernel's limit is on the rows alone; its 64-bit keys hold every length)"""
+    return rows >= 0 and capi.csr_row_order_route(masks, rows, 0)["served"]
+
+
+def _build_served(dense, masks, m, n):
+    if not (_device_build and dense.is_cuda and dense.dtype in _BUILD_DTYPES):
+        return False
+    try:
+        capi.dense_to_csr_launch_shape(masks, m, n, dense.element_size())
+    except RuntimeError:   # (more than INT_MAX elements per mask, or workgroups)
+        return False
+    return _row_order_served(masks, m)
 
 
 def diffsort(row_offsets):
@@ -12,13 +47,30 @@ def diffsort(row_offsets):
     descending=True)[:-1]`` (modules/spmm.py:4-6), always
     int32 (the reference forgets the cast in modules/sparse_linear.py:5-7).
     """
+    if (_device_build and row_offsets.is_cuda and row_offsets.dtype == torch.int32
+            and row_offsets.dim() == 1 and row_offsets.numel() >= 1
+            and _row_order_served(1, row_offsets.numel() - 1)):
+        return ops.row_order(row_offsets)
     lengths = row_offsets[1:] - row_offsets[:-1]
     return torch.argsort(lengths, stable=True).to(torch.int32)
+
+
+def diffsort_many(row_offsets, masks):
+    """Per-mask ``diffsort`` of stacked / concatenated offsets -> flat [masks * rows]
+    (``functional.diffsort_many_mask``): one launch for all masks on the GPU."""
+    per_mask = row_offsets.reshape(masks, -1)
+    if (_device_build and per_mask.is_cuda and per_mask.dtype == torch.int32 and masks >= 1
+            and per_mask.size(1) >= 1 and _row_order_served(masks, per_mask.size(1) - 1)):
+        return ops.row_order(per_mask).reshape(-1)
+    return torch.cat([diffsort(per_mask[i]) for i in range(masks)])
 
 
 def dense_to_sparse(matrix):
     """2-D dense tensor -> (values, row_indices, row_offsets, column_indices),
     int32 indices, as modules/sparse_linear.py:9-16 builds them."""
+    if matrix.dim() == 2 and _build_served(matrix, 1, matrix.size(0), matrix.size(1)):
+        row_indices, row_offsets, column_indices, _, values = ops.dense_to_csr(matrix.detach(), True)
+        return values, row_indices, row_offsets, column_indices
     csr = matrix.detach().to_sparse_csr()
     values = csr.values().clone()
     row_offsets = csr.crow_indices().to(torch.int32)
@@ -52,6 +104,9 @@ def dense_to_sparse_3d(mask):
         mask = mask.squeeze(1)
     if mask.dim() != 3:
         raise ValueError(f"expected a [b, s, s'] or [b, 1, s, s'] mask, got {tuple(mask.shape)}")
+    if mask.size(0) >= 1 and _build_served(mask, mask.size(0), mask.size(1), mask.size(2)):
+        row_indices, row_offsets, column_indices, nonzeros = ops.dense_to_csr(mask.detach(), False)
+        return row_indices, row_offsets, column_indices, nonzeros.tolist()
     row_indices, row_offsets, column_indices, nonzeros = [], [], [], []
     for i in range(mask.size(0)):
         csr = (mask[i] != 0).to_sparse_csr()
