@@ -1356,6 +1356,63 @@ SPUTNIK_HIP_API int sputnik_hip_csr_row_order(int masks, int m, int n, const int
 SPUTNIK_HIP_API int sputnik_hip_csr_row_order_route(int masks, int m, int n, int* served,
                              int* capacity, int* threads, int* sort_size);
 
+/* ------------------------------------------------------------------------
+ * Top-k selection over a dense floating matrix, written straight out as a CSR topology:
+ * magnitude pruning and the regrowth step of SET / RigL (topology.magnitude_prune,
+ * SparseLinear.update_topology).
+ *
+ * `scores` is m x n elements of `element_bytes` = 2 (float16, bfloat16) or 4 (float32),
+ * element (r, c) at scores + r * row_stride + c (elements; row_stride >= 0).  An element's
+ * KEY is its bit pattern with the sign bit cleared, read as an unsigned integer: ranking by
+ * key is ranking by |x|; -0.0 and 0.0 tie, denormals rank by their bits whatever the float
+ * unit's denormal mode, inf ranks above every finite value and NaN above inf.
+ *   total_mode = 0   every row keeps its `count` (0 <= count <= n) largest keys, ties to the
+ *                    lowest column
+ *   total_mode = 1   the matrix keeps its `count` (0 <= count <= m * n) largest keys, ties to
+ *                    the lowest flat (row-major) index
+ * Exactly that many elements are kept; zeros are kept where the count demands it.
+ *
+ * Outputs (device): row_offsets [m + 1], row_indices [m] (the rows by ascending length, ties by
+ * row), column_indices [nonzeros] ascending inside a row, nonzeros = m * count or count; and,
+ * `values` not NULL, values [nonzeros]: the elements of `values_from` (m x n elements of
+ * `value_bytes` = 2 or 4, row stride `values_row_stride`) at the kept positions, bit for bit.
+ * Every size is known before the first launch: the call never synchronises.
+ *
+ * Launches: per row, one select launch (an MSB-first radix select with 8-bit digits per row,
+ * histograms in LDS) and the fill.  Total: a clear of the 256-bin histograms in `workspace`
+ * (on the stream), one histogram launch per digit (integer atomic adds, so the result does
+ * not depend on their order), a rows launch, a scan launch, the fill and the row order.
+ * `workspace`: sputnik_hip_topk_to_csr_workspace_bytes(m, n, total_mode) bytes, 4-byte
+ * aligned, the call's own until its launches have run (it need not be cleared).
+ *
+ * SPUTNIK_HIP_INVALID_ARGUMENT: an element width other than 2 / 4, a negative size or stride,
+ * m * n above INT_MAX, a count out of range, total mode with more rows than
+ * sputnik_hip_csr_row_order serves (16384), a missing or misaligned pointer, a workspace too
+ * small.
+ * ---------------------------------------------------------------------- */
+SPUTNIK_HIP_API int sputnik_hip_topk_to_csr(int m, int n, const void* scores, int element_bytes,
+                             int64_t row_stride, int total_mode, int64_t count,
+                             const void* values_from, int value_bytes, int64_t values_row_stride,
+                             void* workspace, size_t workspace_bytes, int* row_indices,
+                             int* row_offsets, int* column_indices, void* values,
+                             sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API size_t sputnik_hip_topk_to_csr_workspace_bytes(int m, int n, int total_mode);
+
+/* The instance sputnik_hip_topk_to_csr runs for a call of this shape; the entry takes its
+ * decisions from the same function this reports, and from nothing else.
+ *   served               1, or 0 in total mode with m above 16384 (the row-order limit; per-row
+ *                        mode has rows of equal length and needs no sort)
+ *   rows_per_wave, elements_per_lane, rows_per_workgroup, grid
+ *                        the walk of every launch over the matrix: that of
+ *                        sputnik_hip_dense_to_csr_launch_shape(1, m, n, element_bytes)
+ *   digit_passes         8-bit digits of a key: 2 or 4
+ * Host only, launches nothing; any output pointer may be NULL.  Returns
+ * SPUTNIK_HIP_INVALID_ARGUMENT where the entry would for these sizes. */
+SPUTNIK_HIP_API int sputnik_hip_topk_to_csr_launch_shape(int m, int n, int element_bytes, int total_mode,
+                             int* served, int* rows_per_wave, int* elements_per_lane,
+                             int* rows_per_workgroup, int* digit_passes, int* grid);
+
 /*
  * out[r][i] = in[r][permutation[i]], i < n, for `rows` value arrays (strides in
  * elements) that share one permutation: the values of a static pattern in the

@@ -104,6 +104,10 @@ SIGNATURES = {
     "sputnik_hip_dense_to_csr_launch_shape": (_c_int, [_c_int] * 4 + [_c_ptr] * 4),
     "sputnik_hip_csr_row_order": (_c_int, [_c_int] * 3 + [_c_ptr, _c_ptr, _c_ptr]),
     "sputnik_hip_csr_row_order_route": (_c_int, [_c_int] * 3 + [_c_ptr] * 4),
+    "sputnik_hip_topk_to_csr": (_c_int, [_c_int, _c_int, _c_ptr, _c_int, _c_i64, _c_int, _c_i64, _c_ptr, _c_int,
+                                         _c_i64, _c_ptr, _c_size] + [_c_ptr] * 5),
+    "sputnik_hip_topk_to_csr_workspace_bytes": (_c_size, [_c_int] * 3),
+    "sputnik_hip_topk_to_csr_launch_shape": (_c_int, [_c_int] * 4 + [_c_ptr] * 6),
     "sputnik_hip_csr_transpose_checked": (_c_int, [_c_int] * 4 + [_c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_size, _c_ptr]),
@@ -518,6 +522,21 @@ def csr_row_order_route(masks, m, n):
     route = {name: o.value for name, o in zip(names, outs)}
     route["served"] = bool(route["served"])
     return route
+
+
+def topk_to_csr_launch_shape(m, n, element_bytes, total):
+    """The instance of the device top-k-to-CSR build for m x n scores of that width (2 or 4
+    bytes), ``total`` mode or per row: a dict of served (bool; total mode stops at the row-order
+    kernel's rows), rows_per_wave, elements_per_lane, rows_per_workgroup, digit_passes and grid
+    (include/sputnik_hip.h).  Host only; raises for sizes the entry rejects."""
+    names = ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "digit_passes", "grid")
+    outs = [_c_int(-1) for _ in names]
+    _check(lib().sputnik_hip_topk_to_csr_launch_shape(
+        m, n, element_bytes, int(bool(total)), *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
+        "sputnik_hip_topk_to_csr_launch_shape")
+    shape = {name: o.value for name, o in zip(names, outs)}
+    shape["served"] = bool(shape["served"])
+    return shape
 
 
 def csr_transpose(m, n, replicas, values, row_offsets, column_indices, out_values,

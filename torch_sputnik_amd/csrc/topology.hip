@@ -25,6 +25,8 @@
 // is ever read.
 #include <limits.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "wave_utils.h"
 
@@ -300,6 +302,458 @@ inline bool dense_ok(const void* dense, int element_bytes, int64_t batch_stride,
   return dense != nullptr && aligned_to(dense, element_bytes) && batch_stride >= 0 && row_stride >= 0;
 }
 
+// ---------------------------------------------------------------------------
+// Top-k selection over a dense floating matrix, written straight out as a CSR topology
+// (sputnik_hip_topk_to_csr).  An element's KEY is its bit pattern without the sign bit, read
+// as an unsigned integer: ranking by key is ranking by |x|, -0.0 ties with 0.0, denormals rank
+// by their bits, inf above every finite value and NaN above inf.  Both modes come down to a
+// pair (T_r, q_r) per row: an element is kept iff key > T_r, or key == T_r and it is among the
+// first q_r such elements of its row (ascending column).
+//   per row   every row keeps its k largest keys: ONE launch selects (T_r, q_r) of every row
+//             by an MSB-first radix select, 8-bit digits, a 256-bin histogram per row in LDS;
+//             it writes offsets r * k and row_indices r as well (equal lengths: no sort)
+//   total     the matrix keeps its K largest keys, ties to the lowest flat index: one launch
+//             per digit merges the workgroups' LDS histograms into 256 global bins (integer
+//             atomic adds, order independent); every later workgroup derives the digits chosen
+//             so far from those bins itself.  A rows launch counts g_r = #(key > T) and
+//             t_r = #(key == T), a scan launch turns Q = K - #(key > T) into the rows' quotas
+//             q_r = clamp(Q - ties of the rows in front, 0, t_r) and the offsets.
+// The fill is the ballot + lane-prefix placement of topology_rows_kernel plus a tie count
+// carried across the steps of a row.  Every walk is the 16-byte-piece walk described at the
+// top of this file; a row is RE-READ per digit pass (it comes from L2: a 2048 x 2048 float32
+// matrix is 16 MB) rather than held in registers, which would bound n, or in LDS, which the
+// per-row histograms already fill.  Every count is an integer, every store a vector store:
+// results are bitwise reproducible.  Nothing on the host depends on the data.
+// ---------------------------------------------------------------------------
+constexpr int kDigitBits = 8;
+constexpr int kDigitBins = 1 << kDigitBits;
+constexpr int kMaxDigitPasses = 4;
+constexpr unsigned kNoThreshold = 0xffffffffu;   // above every key: nothing is kept by it
+static_assert(kDigitBins == kBuildBlock, "one thread per bin when a workgroup merges its histogram");
+
+struct TopkShape {
+  int status = 0;
+  int served = 0, digit_passes = 0;
+  BuildShape walk;
+};
+inline TopkShape topk_shape(int m, int n, int element_bytes, int total_mode) {
+  TopkShape t;
+  if ((element_bytes != 2 && element_bytes != 4) || (total_mode != 0 && total_mode != 1)) {
+    t.status = SPUTNIK_HIP_INVALID_ARGUMENT;
+    return t;
+  }
+  t.walk = build_shape(1, m, n, element_bytes);
+  t.status = t.walk.status;
+  if (t.status != 0) return t;
+  t.digit_passes = element_bytes * 8 / kDigitBits;
+  // total mode: rows of unequal lengths, ordered by the row-order kernel
+  t.served = total_mode ? order_route(1, m, n).served : 1;
+  return t;
+}
+
+// workspace, in 32-bit words.  per row: thresholds [m], quotas [m].
+// total: bins [4][256], threshold [1], quotas [m], ties [m].
+inline size_t topk_workspace_words(int m, int total_mode) {
+  return total_mode ? static_cast<size_t>(kMaxDigitPasses) * kDigitBins + 1 + 2 * static_cast<size_t>(m)
+                    : 2 * static_cast<size_t>(m);
+}
+
+// One group of lanes on one row: the walk of topology_rows_kernel.
+template <typename U>
+struct RowWalk {
+  static constexpr int V = kLoadBytes / sizeof(U);
+  const U* src;
+  bool live;
+  int n, lead, steps, group_lanes, group_lane;
+
+  __device__ __forceinline__ RowWalk(const U* dense, int64_t row, int64_t row_stride, int m, int n_,
+                                     int rows_per_wave) {
+    const int lane = threadIdx.x % kWave;
+    n = n_;
+    group_lanes = kWave / rows_per_wave;
+    group_lane = lane % group_lanes;
+    live = row < m;
+    src = dense + (live ? row * row_stride : int64_t{0});
+    lead = live ? static_cast<int>((reinterpret_cast<uintptr_t>(src) % kLoadBytes) / sizeof(U)) : 0;
+    const bool any_lead = __ballot(lead != 0) != 0ull;
+    const int64_t span = static_cast<int64_t>(group_lanes) * V;
+    steps = static_cast<int>((static_cast<int64_t>(n) + (any_lead ? V - 1 : 0) + span - 1) / span);
+  }
+  // My piece of step s, its first column, and a bit per element that lies inside the row
+  // (the others read as 0 and are not loaded).
+  __device__ __forceinline__ Piece<U> load(int s, int64_t* first_column, unsigned* valid) const {
+    const int64_t c0 = (static_cast<int64_t>(s) * group_lanes + group_lane) * V - lead;
+    Piece<U> v;
+    if (live && c0 >= 0 && c0 + V <= n) {
+      v = *reinterpret_cast<const Piece<U>*>(src + c0);
+      *valid = (1u << V) - 1u;
+    } else {
+      unsigned in = 0;
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const bool inside = live && c0 + e >= 0 && c0 + e < n;
+        v.e[e] = inside ? src[c0 + e] : U{0};
+        in |= (inside ? 1u : 0u) << e;
+      }
+      *valid = in;
+    }
+    *first_column = c0;
+    return v;
+  }
+};
+
+template <typename U>
+__device__ __forceinline__ unsigned key_of(U bits) {
+  return static_cast<unsigned>(bits & static_cast<U>(static_cast<U>(~U{0}) >> 1));
+}
+
+// Histogram of digit `shift / 8` of the row's keys whose higher digits equal `prefix`.
+template <typename U>
+__device__ __forceinline__ void digit_histogram(const RowWalk<U>& walk, int shift, unsigned prefix,
+                                                unsigned* __restrict__ bins) {
+  constexpr int V = RowWalk<U>::V;
+  for (int s = 0; s < walk.steps; ++s) {
+    int64_t c0;
+    unsigned valid;
+    const Piece<U> v = walk.load(s, &c0, &valid);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned key = key_of(v.e[e]);
+      // (64 bit: the first pass shifts everything out and compares with prefix 0)
+      if (((valid >> e) & 1u) && static_cast<unsigned>(static_cast<uint64_t>(key) >> (shift + kDigitBits)) == prefix)
+        atomicAdd(&bins[(key >> shift) & (kDigitBins - 1)], 1u);
+    }
+  }
+}
+
+// Per-row mode: (T_r, q_r), the offsets r * k and the row order 0 .. m - 1.
+template <typename U>
+__global__ __launch_bounds__(kBuildBlock) void topk_row_select_kernel(
+    int m, int n, int rows_per_wave, int k, const U* __restrict__ scores, int64_t row_stride,
+    unsigned* __restrict__ thresholds, int* __restrict__ quotas, int* __restrict__ row_offsets,
+    int* __restrict__ row_indices) {
+  constexpr int P = sizeof(U) * 8 / kDigitBits;
+  __shared__ unsigned hist[kBuildWaves * kMaxRowsPerWave][kDigitBins];   // 64 KiB
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int group_lanes = kWave / rows_per_wave;
+  const int group = lane / group_lanes, group_lane = lane % group_lanes;
+  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
+  const unsigned long long group_mask =
+      (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
+  const RowWalk<U> walk(scores, row, row_stride, m, n, rows_per_wave);
+  unsigned* __restrict__ bins = hist[wave * rows_per_wave + group];
+  const int chunk = kDigitBins / group_lanes;   // my bins: 4 .. 256 consecutive ones
+  const int base = group_lane * chunk;
+
+  unsigned prefix = 0;
+  int need = k;   // still to take among the elements whose higher digits equal the prefix
+  for (int p = 0; p < P; ++p) {
+    const int shift = kDigitBits * (P - 1 - p);
+    for (int j = 0; j < chunk; ++j) bins[base + j] = 0u;
+    __syncthreads();
+    digit_histogram(walk, shift, prefix, bins);
+    __syncthreads();
+    unsigned mine = 0;
+    for (int j = 0; j < chunk; ++j) mine += bins[base + j];
+    unsigned incl = mine;   // elements in my bins and in those of the group's lanes above me
+    for (int off = 1; off < group_lanes; off <<= 1) {
+      const unsigned up = __shfl_down(incl, off, kWave);
+      if (group_lane + off < group_lanes) incl += up;
+    }
+    const unsigned above = incl - mine;
+    // the lane whose bins hold the need-th largest element
+    const bool owner = need > 0 && above < static_cast<unsigned>(need) && static_cast<unsigned>(need) <= above + mine;
+    int digit = 0, left = 0;
+    if (owner) {
+      unsigned acc = above;
+      for (int j = chunk - 1; j >= 0; --j) {
+        const unsigned c = bins[base + j];
+        if (acc + c >= static_cast<unsigned>(need)) {
+          digit = base + j;
+          left = need - static_cast<int>(acc);
+          break;
+        }
+        acc += c;
+      }
+    }
+    const unsigned long long who = __ballot(owner) & group_mask;
+    const int from = who != 0ull ? __ffsll(who) - 1 : lane;
+    digit = __shfl(digit, from, kWave);
+    left = __shfl(left, from, kWave);
+    prefix = (prefix << kDigitBits) | static_cast<unsigned>(digit);
+    need = who != 0ull ? left : 0;   // (no owner: k = 0, or no row here)
+    __syncthreads();                 // (the bins are cleared again)
+  }
+  if (walk.live && group_lane == 0) {
+    thresholds[row] = k > 0 ? prefix : kNoThreshold;
+    quotas[row] = need;
+    row_offsets[row] = static_cast<int>(row * k);
+    row_indices[row] = static_cast<int>(row);
+    if (row == m - 1) row_offsets[m] = static_cast<int>(static_cast<int64_t>(m) * k);
+  }
+}
+
+// Total mode: the digits chosen by the first `passes` passes, from their global bins; by EVERY
+// thread of a workgroup of at least kDigitBins threads.  *need = what is still to take among
+// the keys with that prefix; after the last pass the prefix is T and *need is Q.
+// `shared`: kDigitBins / kWave + 2 words.
+__device__ __forceinline__ unsigned total_select(const unsigned* bins, int passes, unsigned count,
+                                                 unsigned* shared, unsigned* need_out) {
+  constexpr int kBinWaves = kDigitBins / kWave;
+  const int t = threadIdx.x, lane = t % kWave, wave = t / kWave;
+  unsigned prefix = 0, need = count;
+  for (int p = 0; p < passes; ++p) {
+    const unsigned c = t < kDigitBins ? bins[p * kDigitBins + t] : 0u;
+    unsigned incl = c;   // keys in my bin and in the wave's bins above it
+    for (int off = 1; off < kWave; off <<= 1) {
+      const unsigned up = __shfl_down(incl, off, kWave);
+      if (lane + off < kWave) incl += up;
+    }
+    if (lane == 0 && wave < kBinWaves) shared[wave] = incl;
+    __syncthreads();
+    unsigned above = incl - c;
+    for (int w = wave + 1; w < kBinWaves; ++w) above += shared[w];
+    if (t < kDigitBins && need > 0 && above < need && need <= above + c) {
+      shared[kBinWaves] = static_cast<unsigned>(t);
+      shared[kBinWaves + 1] = need - above;
+    }
+    __syncthreads();
+    if (need > 0) {
+      prefix = (prefix << kDigitBits) | shared[kBinWaves];
+      need = shared[kBinWaves + 1];
+    }
+    __syncthreads();
+  }
+  *need_out = need;
+  return prefix;
+}
+constexpr int kSelectWords = kDigitBins / kWave + 2;
+
+// One digit pass over the whole matrix: this workgroup's rows into an LDS histogram, that into
+// bins[pass][*] with one integer atomic add per non-empty bin.
+template <typename U>
+__global__ __launch_bounds__(kBuildBlock) void topk_total_hist_kernel(
+    int m, int n, int rows_per_wave, int pass, unsigned count, const U* __restrict__ scores,
+    int64_t row_stride, unsigned* bins) {
+  constexpr int P = sizeof(U) * 8 / kDigitBits;
+  __shared__ unsigned hist[kDigitBins];
+  __shared__ unsigned select[kSelectWords];
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int group = lane / (kWave / rows_per_wave);
+  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
+  unsigned need;
+  const unsigned prefix = total_select(bins, pass, count, select, &need);
+  hist[threadIdx.x] = 0u;
+  __syncthreads();
+  const RowWalk<U> walk(scores, row, row_stride, m, n, rows_per_wave);
+  digit_histogram(walk, kDigitBits * (P - 1 - pass), prefix, hist);
+  __syncthreads();
+  const unsigned c = hist[threadIdx.x];
+  if (c != 0u) atomicAdd(&bins[pass * kDigitBins + threadIdx.x], c);
+}
+
+// Total mode: row_offsets[row + 1] = #(key > T), ties[row] = #(key == T).
+template <typename U>
+__global__ __launch_bounds__(kBuildBlock) void topk_total_rows_kernel(
+    int m, int n, int rows_per_wave, unsigned count, const U* __restrict__ scores, int64_t row_stride,
+    const unsigned* __restrict__ bins, int* __restrict__ row_offsets, int* __restrict__ ties) {
+  constexpr int V = RowWalk<U>::V, P = sizeof(U) * 8 / kDigitBits;
+  __shared__ unsigned select[kSelectWords];
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int group_lanes = kWave / rows_per_wave;
+  const int group = lane / group_lanes, group_lane = lane % group_lanes;
+  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
+  unsigned need;
+  const unsigned prefix = total_select(bins, P, count, select, &need);
+  const unsigned threshold = count > 0 ? prefix : kNoThreshold;
+  const RowWalk<U> walk(scores, row, row_stride, m, n, rows_per_wave);
+  int greater = 0, equal = 0;
+  for (int s = 0; s < walk.steps; ++s) {
+    int64_t c0;
+    unsigned valid;
+    const Piece<U> v = walk.load(s, &c0, &valid);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned key = key_of(v.e[e]);
+      const bool in = (valid >> e) & 1u;
+      greater += in && key > threshold ? 1 : 0;
+      equal += in && key == threshold ? 1 : 0;
+    }
+  }
+  for (int o = group_lanes / 2; o > 0; o >>= 1) {
+    greater += __shfl_xor(greater, o, kWave);
+    equal += __shfl_xor(equal, o, kWave);
+  }
+  if (walk.live && group_lane == 0) {
+    row_offsets[row + 1] = greater;
+    ties[row] = equal;
+  }
+}
+
+// Total mode, one workgroup: quotas[r] = clamp(Q - ties of the rows in front, 0, ties[r]); the
+// lengths #(key > T) + quotas[r], scanned in place into the offsets; *threshold = T.
+__global__ __launch_bounds__(kScanBlock) void topk_total_scan_kernel(
+    int m, int digit_passes, unsigned count, const unsigned* __restrict__ bins, const int* __restrict__ ties,
+    int* __restrict__ quotas, int* __restrict__ offsets, unsigned* __restrict__ threshold) {
+  __shared__ int wave_sums[kScanBlock / kWave];
+  __shared__ unsigned select[kSelectWords];
+  unsigned need;
+  const unsigned prefix = total_select(bins, digit_passes, count, select, &need);
+  const int64_t quota = need;
+  const int t = threadIdx.x;
+  const int64_t per = (static_cast<int64_t>(m) + kScanBlock - 1) / kScanBlock;
+  const int64_t i0 = min(static_cast<int64_t>(m), t * per), i1 = min(static_cast<int64_t>(m), i0 + per);
+  int mine = 0;
+  for (int64_t i = i0; i < i1; ++i) mine += ties[i];
+  int total;
+  int64_t ties_before = block_exclusive_scan(mine, wave_sums, &total);
+  __syncthreads();   // (wave_sums is written again)
+  mine = 0;
+  for (int64_t i = i0; i < i1; ++i) {
+    const int tied = ties[i];
+    const int q = static_cast<int>(max(int64_t{0}, min(static_cast<int64_t>(tied), quota - ties_before)));
+    ties_before += tied;
+    quotas[i] = q;
+    const int length = offsets[1 + i] + q;
+    offsets[1 + i] = length;
+    mine += length;
+  }
+  int running = block_exclusive_scan(mine, wave_sums, &total);
+  for (int64_t i = i0; i < i1; ++i) {
+    running += offsets[1 + i];
+    offsets[1 + i] = running;
+  }
+  if (t == 0) {
+    offsets[0] = 0;
+    *threshold = count > 0 ? prefix : kNoThreshold;
+  }
+}
+
+// The kept columns of every row, ascending, from row_offsets[row] onwards; VB != 0: and the
+// elements of `values_from` (VB bytes each) at the kept positions, bit for bit.
+template <typename U, int VB>
+__global__ __launch_bounds__(kBuildBlock) void topk_fill_kernel(
+    int m, int n, int rows_per_wave, const U* __restrict__ scores, int64_t row_stride,
+    const unsigned* __restrict__ thresholds, int threshold_stride, const int* __restrict__ quotas,
+    const int* __restrict__ row_offsets, const void* __restrict__ values_from, int64_t values_row_stride,
+    int* __restrict__ column_indices, void* __restrict__ values) {
+  constexpr int V = RowWalk<U>::V;
+  using W = typename std::conditional<VB == 2, uint16_t, uint32_t>::type;
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int group_lanes = kWave / rows_per_wave;
+  const int group = lane / group_lanes;
+  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
+  const unsigned long long group_mask =
+      (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
+  const unsigned long long below = group_mask & ((1ull << lane) - 1ull);
+  const RowWalk<U> walk(scores, row, row_stride, m, n, rows_per_wave);
+  const unsigned threshold = walk.live ? thresholds[row * threshold_stride] : kNoThreshold;
+  const int quota = walk.live ? quotas[row] : 0;
+  const W* __restrict__ payload =
+      static_cast<const W*>(values_from) + (VB != 0 && walk.live ? row * values_row_stride : int64_t{0});
+  int64_t out = walk.live ? row_offsets[row] : 0;
+  const int64_t end = walk.live ? row_offsets[row + 1] : 0;   // (no store ever leaves the row's slots)
+  int ties_seen = 0;   // elements equal to the threshold in the steps behind
+  for (int s = 0; s < walk.steps; ++s) {
+    int64_t c0;
+    unsigned valid;
+    const Piece<U> v = walk.load(s, &c0, &valid);
+    unsigned greater = 0, equal = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned key = key_of(v.e[e]);
+      greater |= (key > threshold ? 1u : 0u) << e;
+      equal |= (key == threshold ? 1u : 0u) << e;
+    }
+    greater &= valid;
+    equal &= valid;
+    // column order: lane after lane, element after element inside a lane
+    int ties_before = 0, ties_step = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned long long b = __ballot((equal >> e) & 1u);
+      ties_before += __popcll(b & below);
+      ties_step += __popcll(b & group_mask);
+    }
+    unsigned flags = greater;
+    int rank = ties_seen + ties_before;
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      if ((equal >> e) & 1u) {
+        if (rank < quota) flags |= 1u << e;
+        ++rank;
+      }
+    ties_seen += ties_step;
+    int before = 0, total = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned long long b = __ballot((flags >> e) & 1u);
+      before += __popcll(b & below);
+      total += __popcll(b & group_mask);
+    }
+    int64_t p = out + before;
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      if (((flags >> e) & 1u) && p < end) {
+        column_indices[p] = static_cast<int>(c0 + e);
+        if constexpr (VB != 0) static_cast<W*>(values)[p] = payload[c0 + e];
+        ++p;
+      }
+    out += total;
+  }
+}
+
+template <typename U>
+int launch_topk(const TopkShape& t, int m, int n, const void* scores_, int64_t row_stride, int total_mode,
+                unsigned count, const void* values_from, int value_bytes, int64_t values_row_stride,
+                unsigned* workspace, int* row_indices, int* row_offsets, int* column_indices, void* values,
+                hipStream_t stream) {
+  const U* scores = static_cast<const U*>(scores_);
+  const int rows = t.walk.rows_per_wave;
+  const dim3 grid(t.walk.grid), block(kBuildBlock);
+  const unsigned* thresholds;
+  const int* quotas;
+  if (!total_mode) {
+    unsigned* th = workspace;
+    int* q = reinterpret_cast<int*>(workspace + m);
+    hipLaunchKernelGGL((topk_row_select_kernel<U>), grid, block, 0, stream, m, n, rows, static_cast<int>(count),
+                       scores, row_stride, th, q, row_offsets, row_indices);
+    thresholds = th;
+    quotas = q;
+  } else {
+    unsigned* bins = workspace;
+    unsigned* th = workspace + kMaxDigitPasses * kDigitBins;
+    int* q = reinterpret_cast<int*>(th + 1);
+    int* ties = q + m;
+    if (hipMemsetAsync(bins, 0, sizeof(unsigned) * kMaxDigitPasses * kDigitBins, stream) != hipSuccess)
+      return launch_status();
+    for (int p = 0; p < t.digit_passes; ++p)
+      hipLaunchKernelGGL((topk_total_hist_kernel<U>), grid, block, 0, stream, m, n, rows, p, count, scores,
+                         row_stride, bins);
+    hipLaunchKernelGGL((topk_total_rows_kernel<U>), grid, block, 0, stream, m, n, rows, count, scores, row_stride,
+                       bins, row_offsets, ties);
+    hipLaunchKernelGGL(topk_total_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, m, t.digit_passes, count,
+                       bins, ties, q, row_offsets, th);
+    thresholds = th;
+    quotas = q;
+  }
+  int st = launch_status();
+  if (st != 0) return st;
+  if (count > 0 && column_indices != nullptr) {
+    const int stride = total_mode ? 0 : 1;
+#define SPUTNIK_TOPK_FILL(VB)                                                                             \
+  hipLaunchKernelGGL((topk_fill_kernel<U, VB>), grid, block, 0, stream, m, n, rows, scores, row_stride,   \
+                     thresholds, stride, quotas, row_offsets, values_from, values_row_stride,             \
+                     column_indices, values)
+    if (values == nullptr) SPUTNIK_TOPK_FILL(0);
+    else if (value_bytes == 2) SPUTNIK_TOPK_FILL(2);
+    else SPUTNIK_TOPK_FILL(4);
+#undef SPUTNIK_TOPK_FILL
+    st = launch_status();
+  }
+  return st;
+}
+
 }  // namespace
 }  // namespace sputnik_hip
 
@@ -381,6 +835,59 @@ int sputnik_hip_csr_row_order(int masks, int m, int n, const int* row_offsets, i
     hipLaunchKernelGGL((topology_row_order_kernel<kOrderLargeRows, kOrderLargeBlock>), dim3(masks),
                        dim3(kOrderLargeBlock), 0, stream, m, r.sort_size, row_offsets, row_indices);
   return launch_status();
+}
+
+int sputnik_hip_topk_to_csr_launch_shape(int m, int n, int element_bytes, int total_mode, int* served,
+                                         int* rows_per_wave, int* elements_per_lane, int* rows_per_workgroup,
+                                         int* digit_passes, int* grid) {
+  const TopkShape t = topk_shape(m, n, element_bytes, total_mode);
+  if (t.status != 0) return t.status;
+  if (served) *served = t.served;
+  if (rows_per_wave) *rows_per_wave = t.walk.rows_per_wave;
+  if (elements_per_lane) *elements_per_lane = t.walk.elements_per_lane;
+  if (rows_per_workgroup) *rows_per_workgroup = t.walk.rows_per_workgroup;
+  if (digit_passes) *digit_passes = t.digit_passes;
+  if (grid) *grid = t.walk.grid;
+  return 0;
+}
+
+size_t sputnik_hip_topk_to_csr_workspace_bytes(int m, int n, int total_mode) {
+  if (m < 0 || n < 0) return 0;
+  return sizeof(unsigned) * topk_workspace_words(m, total_mode != 0);
+}
+
+int sputnik_hip_topk_to_csr(int m, int n, const void* scores, int element_bytes, int64_t row_stride,
+                            int total_mode, int64_t count, const void* values_from, int value_bytes,
+                            int64_t values_row_stride, void* workspace, size_t workspace_bytes,
+                            int* row_indices, int* row_offsets, int* column_indices, void* values,
+                            sputnik_hip_stream_t stream_) {
+  const TopkShape t = topk_shape(m, n, element_bytes, total_mode);
+  if (t.status != 0) return t.status;
+  if (!t.served) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const int64_t most = total_mode ? static_cast<int64_t>(m) * n : n;
+  if (count < 0 || count > most || row_offsets == nullptr) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (m == 0) return static_cast<int>(hipMemsetAsync(row_offsets, 0, sizeof(int), stream));
+  const int64_t nonzeros = total_mode ? count : count * m;
+  if (row_indices == nullptr || (nonzeros > 0 && column_indices == nullptr) ||
+      (n > 0 && !dense_ok(scores, element_bytes, 0, row_stride)) || workspace == nullptr ||
+      !aligned_to(workspace, sizeof(unsigned)) ||
+      workspace_bytes < sizeof(unsigned) * topk_workspace_words(m, total_mode))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (values != nullptr &&
+      ((value_bytes != 2 && value_bytes != 4) || values_row_stride < 0 || !aligned_to(values, value_bytes) ||
+       (nonzeros > 0 && (values_from == nullptr || !aligned_to(values_from, value_bytes)))))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const int st =
+      element_bytes == 2
+          ? launch_topk<uint16_t>(t, m, n, scores, row_stride, total_mode, static_cast<unsigned>(count), values_from,
+                                  value_bytes, values_row_stride, static_cast<unsigned*>(workspace), row_indices,
+                                  row_offsets, column_indices, values, stream)
+          : launch_topk<uint32_t>(t, m, n, scores, row_stride, total_mode, static_cast<unsigned>(count), values_from,
+                                  value_bytes, values_row_stride, static_cast<unsigned*>(workspace), row_indices,
+                                  row_offsets, column_indices, values, stream);
+  if (st != 0 || !total_mode) return st;
+  return sputnik_hip_csr_row_order(1, m, n, row_offsets, row_indices, stream_);
 }
 
 }  // extern "C"

@@ -1944,6 +1944,60 @@ std::vector<Tensor> dense_to_csr(const Tensor& dense_in, bool with_values) {
   return out;
 }
 
+// scores [m, n] (float32 / float16 / bfloat16) -> [row_indices, row_offsets, column_indices,
+// values]: the CSR topology of the `per_row` largest |scores| of every row, or of the `total`
+// largest of the matrix (the other one -1), with the elements of `values_from` (same shape, any
+// 2- or 4-byte dtype; the scores themselves by default) at the kept positions.  Every size is
+// known up front: no synchronisation.  The workspace is this call's own allocation, on the
+// stream's allocator, so no other call can be writing its histograms.
+std::vector<Tensor> topk_to_csr(const Tensor& scores_in, int64_t per_row, int64_t total,
+                                const c10::optional<Tensor>& values_from_in) {
+  TORCH_CHECK(scores_in.is_cuda(), "scores must be a GPU (HIP) tensor, got ", scores_in.device());
+  TORCH_CHECK(scores_in.dim() == 2, "expected [m, n] scores, got ", scores_in.sizes());
+  const auto type = scores_in.scalar_type();
+  TORCH_CHECK(type == at::kFloat || type == at::kHalf || type == at::kBFloat16,
+              "scores must be float32, float16 or bfloat16, got ", type);
+  TORCH_CHECK((per_row >= 0) != (total >= 0), "give exactly one of per_row / total");
+  const c10::DeviceGuard guard(scores_in.device());
+  const Tensor scores = scores_in.size(1) > 1 && scores_in.stride(1) != 1 ? scores_in.contiguous() : scores_in;
+  const int m = to_int(scores.size(0), "m"), n = to_int(scores.size(1), "n");
+  const int total_mode = total >= 0 ? 1 : 0;
+  const int64_t count = total_mode ? total : per_row;
+  const int element_bytes = static_cast<int>(scores.element_size());
+  int served = 0;
+  check_status(sputnik_hip_topk_to_csr_launch_shape(m, n, element_bytes, total_mode, &served, nullptr, nullptr,
+                                                    nullptr, nullptr, nullptr),
+               "topk_to_csr");
+  TORCH_CHECK(served, "torch_sputnik::topk_to_csr: total mode over ", m, " rows is beyond the row-order "
+              "kernel (sputnik_hip_topk_to_csr_launch_shape); take topology.magnitude_prune");
+  TORCH_CHECK(count <= (total_mode ? static_cast<int64_t>(m) * n : static_cast<int64_t>(n)),
+              "torch_sputnik::topk_to_csr: ", count, " entries asked of ", total_mode ? "a matrix" : "rows",
+              " of ", total_mode ? static_cast<int64_t>(m) * n : static_cast<int64_t>(n));
+  Tensor values_from = values_from_in.has_value() ? *values_from_in : scores;
+  TORCH_CHECK(values_from.is_cuda() && values_from.device() == scores.device() &&
+                  values_from.sizes() == scores.sizes(),
+              "values_from must be a tensor of the scores' shape on their device, got ", values_from.sizes());
+  TORCH_CHECK(values_from.element_size() == 2 || values_from.element_size() == 4,
+              "values_from must have 2- or 4-byte elements, got ", values_from.scalar_type());
+  if (n > 1 && values_from.stride(1) != 1) values_from = values_from.contiguous();
+  const int64_t nonzeros = total_mode ? count : count * m;
+  const auto index_options = scores.options().dtype(at::kInt);
+  Tensor row_indices = at::empty({m}, index_options);
+  Tensor row_offsets = at::empty({m + 1}, index_options);
+  Tensor column_indices = at::empty({nonzeros}, index_options);
+  Tensor values = at::empty({nonzeros}, values_from.options());
+  const size_t ws_bytes = sputnik_hip_topk_to_csr_workspace_bytes(m, n, total_mode);
+  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, scores.options().dtype(at::kByte));
+  check_status(sputnik_hip_topk_to_csr(
+                   m, n, scores.data_ptr(), element_bytes, m > 1 ? scores.stride(0) : 0, total_mode, count,
+                   values_from.data_ptr(), static_cast<int>(values_from.element_size()),
+                   m > 1 ? values_from.stride(0) : 0, workspace.data_ptr(), ws_bytes, row_indices.data_ptr<int>(),
+                   row_offsets.data_ptr<int>(), column_indices.data_ptr<int>(), values.data_ptr(),
+                   current_stream(scores)),
+               "topk_to_csr");
+  return {row_indices, row_offsets, column_indices, values};
+}
+
 // ---- the fused attention with one mask per batch element (sputnik_hip.h:
 // sparse_attention_many_mask_*, sparse_attention_heads_many_mask_*) ----
 
@@ -2385,6 +2439,7 @@ TORCH_LIBRARY(torch_sputnik, m) {
       "Tensor row_offsets, Tensor column_indices) -> Tensor[]");
   m.def("dense_to_csr(Tensor dense, bool with_values) -> Tensor[]");
   m.def("row_order(Tensor row_offsets) -> Tensor");
+  m.def("topk_to_csr(Tensor scores, int per_row, int total, Tensor? values_from) -> Tensor[]");
   m.def(
       "sparse_attention_many_mask(int b, Tensor nonzeros, Tensor query, Tensor key, Tensor value, "
       "Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, bool want_lse, "
@@ -2483,6 +2538,7 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("csr_transpose_many_mask", &csr_transpose_many_mask);
   m.impl("dense_to_csr", &dense_to_csr);
   m.impl("row_order", &row_order);
+  m.impl("topk_to_csr", &topk_to_csr);
   m.impl("sparse_attention_many_mask", &sparse_attention_many_mask);
   m.impl("sparse_attention_many_mask_plan", &sparse_attention_many_mask_plan);
   m.impl("sparse_attention_heads_many_mask", &sparse_attention_heads_many_mask);

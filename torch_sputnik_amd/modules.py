@@ -11,6 +11,8 @@ the fixed random mask drawn at construction.
 Differences: the attention mask is created on the device given (default: the
 current GPU) instead of a hard ``.cuda()``; ``differentiable_softmax=True``
 opts in to a softmax with a gradient.
+Additions: ``SparseLinear.from_dense`` builds a ready layer from a dense weight by
+magnitude, ``SparseLinear.update_topology`` is one drop-and-grow step (SET, RigL).
 """
 import copy
 import math
@@ -18,7 +20,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import functional, ops
+from . import functional, ops, topology
 from .functional import (GroupProjectionFunction, HalfSparseLinearFunction, SparseAttentionFunction,
                          Sddmm, SparseLinearFunction, SparseSoftmax, Spmm)
 from .topology import dense_to_sparse, dense_to_sparse_3d, generate_mask
@@ -45,6 +47,108 @@ class SparseLinear(nn.Module):
         # the pattern by calling setup_sparse_tensors() again -- do not write into
         # the index tensors through .data or a raw pointer: functional.py.)
         functional.register_static_topology(row_indices, row_offsets, column_indices)
+
+    @classmethod
+    def from_dense(cls, weight, density=None, nonzeros=None, per_row=False):
+        """A sparse layer from a trained dense ``[out, in]`` weight (a ``nn.Linear.weight``) by
+        magnitude: the ``round(density * out * in)`` (or ``nonzeros``) entries of largest
+        ``|weight|`` are kept, ``per_row`` that share of every row
+        (``topology.magnitude_prune``; on a GPU weight the selection and the CSR build run on
+        the device without a host synchronisation).  The module lives on the weight's device,
+        ``values`` is a Parameter in the weight's dtype, the topology is registered as static:
+        ready to call.  As everywhere in this module ``weight`` and ``bias`` are uninitialised
+        parameters and the bias is never applied -- a ``nn.Linear``'s bias is NOT carried over;
+        add it behind the layer."""
+        if weight.dim() != 2:
+            raise ValueError(f"from_dense: expected an [out, in] weight, got {tuple(weight.shape)}")
+        module = cls(weight.size(1), weight.size(0)).to(device=weight.device, dtype=weight.dtype)
+        values, row_indices, row_offsets, column_indices = topology.magnitude_prune(
+            weight.detach(), density=density, nonzeros=nonzeros, per_row=per_row)
+        module._set_topology(nn.Parameter(values), row_indices, row_offsets, column_indices)
+        return module
+
+    def _set_topology(self, values, row_indices, row_offsets, column_indices):
+        if values is not None:
+            self.values = values
+        self.row_indices = row_indices
+        self.row_offsets = row_offsets
+        self.column_indices = column_indices
+        functional.register_static_topology(row_indices, row_offsets, column_indices)
+
+    @torch.no_grad()
+    def update_topology(self, drop_fraction, grow_scores=None, generator=None):
+        """One drop-and-grow step of dynamic sparse training (SET, RigL) with an unchanged
+        number of entries ``nnz``:
+
+        1. ``d = int(drop_fraction * nnz)`` entries are dropped: the ``nnz - d`` of largest
+           ``|values|`` are kept, ties to the lower entry index.
+        2. ``d`` entries are grown where ``|grow_scores|`` (``[out, in]``, e.g. the magnitude of
+           the dense weight gradient, RigL) is largest outside the kept positions, ties to the
+           lower flat index; non-finite scores count as the largest finite value;
+           ``grow_scores=None`` draws uniform random scores with ``generator`` (SET).  Positions
+           dropped in step 1 are eligible.
+        3. The new values are written INTO the existing ``values`` Parameter -- an optimizer
+           keeps its handle -- kept ones bit for bit, grown ones exactly 0.  The index tensors
+           are replaced by new ones (the old ones are unregistered, never written to), so no
+           cached plan, transposed topology or half image of the old pattern serves the new.
+
+        Returns ``source``, int64 ``[nnz]``: for every new entry the index of that entry in the
+        old ``values``, or -1 where it was grown -- to permute or reset optimizer state.
+        ``d == 0`` changes nothing (``source = arange(nnz)``).
+
+        Selection and CSR build are one ``topology.topk_to_csr`` call (on the device for a GPU
+        module).  Out of scope: regrowth per row, and the dense weight gradient itself -- pass
+        e.g. ``dy.flatten(0, 1).T @ x.flatten(0, 1)``."""
+        values = self.values.detach()
+        nnz = values.numel()
+        device = values.device
+        d = int(drop_fraction * nnz)
+        if not 0 <= d <= nnz:
+            raise ValueError(f"update_topology: drop_fraction {drop_fraction} is outside 0 .. 1")
+        if d == 0:
+            return torch.arange(nnz, dtype=torch.int64, device=device)
+        out_f, in_f = self.output_features, self.input_features
+        rank_values = values if values.dtype in topology._TOPK_DTYPES else values.float()
+        order = torch.argsort(topology.magnitude_keys(rank_values), descending=True, stable=True)
+        kept = torch.sort(order[:nnz - d]).values                     # old entry indices, ascending
+        lengths = (self.row_offsets[1:] - self.row_offsets[:-1]).to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(out_f, device=device), lengths, output_size=nnz)
+        flat = rows * in_f + self.column_indices.to(torch.int64)      # ascending: CSR is row major
+        kept_flat = flat[kept]
+
+        if grow_scores is None:
+            where = generator.device if generator is not None else device
+            scores = torch.rand(out_f, in_f, generator=generator, device=where).to(device)
+        else:
+            if tuple(grow_scores.shape) != (out_f, in_f):
+                raise ValueError(f"update_topology: grow_scores should be [{out_f}, {in_f}], got "
+                                 f"{tuple(grow_scores.shape)}")
+            scores = grow_scores.detach().to(device)
+            if scores.dtype not in topology._TOPK_DTYPES:
+                scores = scores.float()
+            largest = torch.finfo(scores.dtype).max
+            scores = torch.nan_to_num(scores.abs(), nan=largest, posinf=largest)
+        scores = scores.contiguous()
+        scores.view(-1)[kept_flat] = float("inf")                      # Kept comes first ...
+        image = torch.zeros(out_f, in_f, dtype=values.dtype, device=device)
+        bits = topology._BIT_VIEWS[values.element_size()]                # ... and carries its values,
+        image.view(bits).view(-1)[kept_flat] = values.contiguous().view(bits)[kept]   # bit for bit
+        row_indices, row_offsets, column_indices, new_values = topology.topk_to_csr(
+            scores, total=nnz, values_from=image)
+
+        new_lengths = (row_offsets[1:] - row_offsets[:-1]).to(torch.int64)
+        new_rows = torch.repeat_interleave(torch.arange(out_f, device=device), new_lengths, output_size=nnz)
+        new_flat = new_rows * in_f + column_indices.to(torch.int64)
+        at = torch.searchsorted(kept_flat, new_flat).clamp_(max=kept_flat.numel() - 1)
+        if kept_flat.numel():
+            source = torch.where(kept_flat[at] == new_flat, kept[at], torch.full_like(at, -1))
+        else:
+            source = torch.full_like(new_flat, -1)
+
+        self.values.copy_(new_values)
+        functional.unregister_static_topology(self.row_indices, self.row_offsets, self.column_indices)
+        self._set_topology(None, row_indices, row_offsets, column_indices)
+        return source
 
     def forward(self, x):
         # [B, S, in] -> the k-major operand [B, in, S] of left_spmm: the reference's

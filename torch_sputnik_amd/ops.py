@@ -254,6 +254,39 @@ def row_order(row_offsets):
     return _ops.row_order(row_offsets)
 
 
+_TOPK_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def topk_to_csr(scores, per_row=None, total=None, values_from=None):
+    """The CSR topology of the largest ``|scores|`` of a dense [m, n] float32 / float16 /
+    bfloat16 matrix, selected and written out on the device (csrc/topology.hip): ``per_row = k``
+    keeps the k largest of every row (ties to the lowest column), ``total = K`` the K largest of
+    the matrix (ties to the lowest flat index) -- exactly one of the two.  Magnitudes rank by
+    the bit pattern without the sign: NaN above inf above every finite value, -0.0 with 0.0.
+    -> (row_indices, row_offsets, column_indices, values); ``values`` are the elements of
+    ``values_from`` (same shape, any 2- or 4-byte dtype; default: the scores) at the kept
+    positions, bit for bit.  No host synchronisation.  Raises for CPU tensors and for shapes
+    ``capi.topk_to_csr_launch_shape`` does not serve (total mode above 16384 rows)."""
+    if (per_row is None) == (total is None):
+        raise ValueError("topk_to_csr: give exactly one of per_row / total")
+    if scores.dim() != 2:
+        raise ValueError(f"topk_to_csr: expected [m, n] scores, got {tuple(scores.shape)}")
+    if scores.dtype not in _TOPK_DTYPES:
+        raise ValueError(f"topk_to_csr: scores must be float32, float16 or bfloat16, got {scores.dtype}")
+    m, n = scores.shape
+    count, most = (int(total), m * n) if per_row is None else (int(per_row), n)
+    if not 0 <= count <= most:
+        raise ValueError(f"topk_to_csr: {'total' if per_row is None else 'per_row'} = {count} is outside 0 .. {most}")
+    if values_from is not None and (values_from.shape != scores.shape or values_from.device != scores.device
+                                    or values_from.element_size() not in (2, 4)):
+        raise ValueError("topk_to_csr: values_from must have the scores' shape and device and 2- or 4-byte "
+                         f"elements, got {tuple(values_from.shape)} {values_from.dtype} on {values_from.device}")
+    if not scores.is_cuda:
+        raise RuntimeError("topk_to_csr: GPU tensors only (topology.magnitude_prune serves CPU tensors)")
+    return tuple(_ops.topk_to_csr(scores, -1 if per_row is None else count, -1 if total is None else count,
+                                  values_from))
+
+
 def sparse_attention_many_mask(b, nonzeros, row_indices, row_offsets, column_indices, query, key,
                                value, scale, with_lse=False, plan=None):
     """softmax(scale * q k^T at the mask) v with one mask per batch element in ONE kernel:

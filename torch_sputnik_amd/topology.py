@@ -78,6 +78,115 @@ def dense_to_sparse(matrix):
     return values, diffsort(row_offsets), row_offsets, column_indices
 
 
+_TOPK_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def magnitude_keys(x):
+    """The selection key of every element of a float32 / float16 / bfloat16 tensor, int64: its
+    bit pattern with the sign bit cleared, read as an unsigned integer.  Ranking by key is
+    ranking by ``|x|``; -0.0 ties with 0.0, denormals rank by their bits, inf ranks above every
+    finite value and NaN above inf."""
+    x = x.contiguous()
+    if x.element_size() == 2:
+        return x.view(torch.int16).to(torch.int64) & 0x7fff
+    return x.view(torch.int32).to(torch.int64) & 0x7fffffff
+
+
+_BIT_VIEWS = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def _take_bits(tensor, flat):
+    """``tensor.reshape(-1)[flat]`` as a copy of bits (a NaN keeps its payload and sign)"""
+    bits = tensor.contiguous().view(_BIT_VIEWS[tensor.element_size()]).reshape(-1)
+    return bits[flat].view(tensor.dtype)
+
+
+def _topk_served(scores, values_from, total):
+    if not (_device_build and scores.is_cuda and scores.dtype in _TOPK_DTYPES):
+        return False
+    if values_from is not None and values_from.element_size() not in (2, 4):
+        return False
+    try:
+        return capi.topk_to_csr_launch_shape(scores.size(0), scores.size(1), scores.element_size(),
+                                             total)["served"]
+    except RuntimeError:   # (more than INT_MAX elements)
+        return False
+
+
+def topk_to_csr(scores, per_row=None, total=None, values_from=None):
+    """``ops.topk_to_csr`` for any tensor: the device build where it serves the call, else the
+    same rule in torch -- a stable descending sort of the keys (``magnitude_keys``), so ties go
+    to the lowest column (per row) or flat index (total).  Scores of another dtype are ranked
+    as ``.float()``.  -> (row_indices, row_offsets, column_indices, values), the same integers
+    and value bits on both paths."""
+    if (per_row is None) == (total is None):
+        raise ValueError("topk_to_csr: give exactly one of per_row / total")
+    if scores.dim() != 2:
+        raise ValueError(f"topk_to_csr: expected [m, n] scores, got {tuple(scores.shape)}")
+    m, n = scores.shape
+    count, most = (int(total), m * n) if per_row is None else (int(per_row), n)
+    if not 0 <= count <= most:
+        raise ValueError(f"topk_to_csr: {'total' if per_row is None else 'per_row'} = {count} is outside 0 .. {most}")
+    if values_from is None:
+        values_from = scores
+    elif values_from.shape != scores.shape or values_from.device != scores.device:
+        raise ValueError("topk_to_csr: values_from must have the scores' shape and device, got "
+                         f"{tuple(values_from.shape)} on {values_from.device}")
+    scores, values_from = scores.detach(), values_from.detach()
+    if scores.dtype not in _TOPK_DTYPES:
+        scores = scores.float()
+    if _topk_served(scores, values_from, per_row is None):
+        return ops.topk_to_csr(scores, per_row, total, values_from)
+    keys = magnitude_keys(scores)
+    int32 = dict(dtype=torch.int32, device=scores.device)
+    if per_row is not None:
+        kept = torch.argsort(keys, dim=1, descending=True, stable=True)[:, :count]
+        columns = torch.sort(kept, dim=1).values
+        row_offsets = torch.arange(m + 1, **int32) * count
+        flat = (columns + torch.arange(m, device=scores.device)[:, None] * n).reshape(-1)
+        return (torch.arange(m, **int32), row_offsets, columns.reshape(-1).to(torch.int32),
+                _take_bits(values_from, flat))
+    kept = torch.argsort(keys.reshape(-1), descending=True, stable=True)[:count]
+    flat = torch.sort(kept).values
+    rows = torch.div(flat, max(n, 1), rounding_mode="floor")
+    row_offsets = torch.zeros(m + 1, **int32)
+    row_offsets[1:] = torch.cumsum(torch.bincount(rows, minlength=m), 0)
+    return (diffsort(row_offsets), row_offsets, (flat - rows * n).to(torch.int32),
+            _take_bits(values_from, flat))
+
+
+def magnitude_prune(matrix, density=None, nonzeros=None, per_row=False):
+    """Dense [m, n] matrix -> (values, row_indices, row_offsets, column_indices), the tuple of
+    ``dense_to_sparse``, keeping its entries of largest magnitude.
+
+    ``density``: keep ``round(density * m * n)`` entries of the matrix, or ``per_row``
+    ``round(density * n)`` of every row.  ``nonzeros``: that number itself (of every row,
+    ``per_row``).  Give one of the two.  Exactly that many entries are kept, ties to the lowest
+    flat index (column, ``per_row``); zeros are kept as explicit entries where the count demands
+    it.  The ranking is that of ``magnitude_keys``.
+
+    GPU float32 / float16 / bfloat16 matrices are selected and written out by the device
+    kernels (``ops.topk_to_csr``; no host synchronisation); CPU tensors, other dtypes (ranked as
+    ``.float()``), ``enable_device_build(False)`` and matrix-wide selection over more than 16384
+    rows take the same rule in torch.  Both give the same integers and value bits."""
+    if matrix.dim() != 2:
+        raise ValueError(f"magnitude_prune: expected a [m, n] matrix, got {tuple(matrix.shape)}")
+    if (density is None) == (nonzeros is None):
+        raise ValueError("magnitude_prune: give exactly one of density / nonzeros")
+    m, n = matrix.shape
+    most = n if per_row else m * n
+    if density is not None:
+        if not 0.0 <= density <= 1.0:
+            raise ValueError(f"magnitude_prune: density {density} is outside 0 .. 1")
+        nonzeros = round(density * most)
+    count = int(nonzeros)
+    if not 0 <= count <= most:
+        raise ValueError(f"magnitude_prune: {count} entries asked of {most}")
+    row_indices, row_offsets, column_indices, values = topk_to_csr(
+        matrix, per_row=count if per_row else None, total=None if per_row else count)
+    return values, row_indices, row_offsets, column_indices
+
+
 def generate_mask(m, n, device="cpu", sparsity=0.9, round_to=4, generator=None):
     """Random 0/1 mask with the nonzero count of modules/sparse_attention.py:25-36:
     ``int(m*n*sparsity)`` zeros rounded DOWN to a multiple of ``round_to``.
