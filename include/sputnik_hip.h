@@ -1413,6 +1413,73 @@ SPUTNIK_HIP_API int sputnik_hip_topk_to_csr_launch_shape(int m, int n, int eleme
                              int* served, int* rows_per_wave, int* elements_per_lane,
                              int* rows_per_workgroup, int* digit_passes, int* grid);
 
+/* ------------------------------------------------------------------------
+ * Per-row drop-and-grow of a CSR topology (topology.regrow_per_row,
+ * SparseLinear.update_topology(..., per_row=True)): every row keeps its length, drops its
+ * entries of smallest magnitude and grows as many where a dense score matrix is largest.
+ *
+ * Inputs (device): the pattern of an m x n matrix -- row_offsets [m + 1], column_indices
+ * [nonzeros], ascending inside a row, int32 --, values [nonzeros] of `value_bytes` = 2 or 4,
+ * drop_counts [m] (int32) and `scores`, m x n elements of `score_bytes` = 2 (float16, bfloat16)
+ * or 4 (float32), element (r, c) at scores + r * scores_row_stride + c (elements; stride >= 0).
+ * KEYS are those of sputnik_hip_topk_to_csr: the bit pattern without the sign.  For row r of
+ * len_r entries, d_r = clamp(drop_counts[r], 0, len_r) and c_r = len_r - d_r:
+ *   Kept_r    the c_r entries of largest value key, ties to the lower column
+ *   Grown_r   the d_r columns outside Kept_r of largest score key, ties to the lowest column;
+ *             a score key is clamped to `score_key_limit` (the key of the dtype's largest
+ *             finite value: 0x7f7fffff float32, 0x7bff float16, 0x7f7f bfloat16 -- NaN and inf
+ *             count as that value).  Columns dropped in this call are eligible.
+ * The new row is Kept_r and Grown_r in ascending column order in the row's own slots
+ * [row_offsets[r], row_offsets[r + 1]): out_column_indices [nonzeros]; out_values [nonzeros]:
+ * a kept entry's old value bit for bit, all bits zero for a grown one; out_source [nonzeros]
+ * (int64): a kept entry's old index, -1 for a grown one.  row_offsets is not written.
+ *
+ * ONE launch, one group of lanes per row: a radix select over the row's old values, the old and
+ * the kept columns marked in an LDS bitmap, a radix select over the score row outside the kept
+ * columns, and the fill, in which a running count of old bits is the old entry index.  Every
+ * count is an integer and every store a vector store to a slot one lane owns: two calls give
+ * equal arrays.  Nothing is read back; `workspace` is
+ * sputnik_hip_csr_regrow_workspace_bytes(...) bytes (0 today: it may be NULL).
+ * m = 0 or nonzeros = 0 launches nothing.  A column index outside 0 .. n - 1, a column stored
+ * twice or offsets that do not ascend inside 0 .. nonzeros are caller errors with an
+ * unspecified result, but nothing outside the arrays is read or written.
+ *
+ * SPUTNIK_HIP_INVALID_ARGUMENT: an element width other than 2 / 4, a negative size or stride,
+ * m * n above INT_MAX, n above the served limit (sputnik_hip_csr_regrow_launch_shape), a
+ * missing or misaligned pointer, a workspace too small.
+ * ---------------------------------------------------------------------- */
+SPUTNIK_HIP_API int sputnik_hip_csr_regrow(int m, int n, int nonzeros, const int* row_offsets,
+                             const int* column_indices, const void* values, int value_bytes,
+                             const int* drop_counts, const void* scores, int score_bytes,
+                             int64_t scores_row_stride, unsigned score_key_limit, void* workspace,
+                             size_t workspace_bytes, int* out_column_indices, void* out_values,
+                             int64_t* out_source, sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API size_t sputnik_hip_csr_regrow_workspace_bytes(int m, int n, int nonzeros);
+
+/* The instance sputnik_hip_csr_regrow runs for a call of this shape; the entry takes its
+ * decisions from the same function this reports, and from nothing else.
+ *   served               1 for n <= max_n, else 0 (every field but max_n is -1 then)
+ *   max_n                the widest row served: 4 rows per workgroup, each with a 256-bin
+ *                        histogram and two bits per column, in the 64 KiB of LDS a launch gets
+ *                        without asking for more: 32 * ((65536 / 4 - 1024) / 8) = 61440
+ *   elements_per_lane    score elements of one 16-byte load: 16 / score_bytes
+ *   rows_per_wave        8 / 4 / 2 / 1: that of sputnik_hip_dense_to_csr_launch_shape(1, m, n,
+ *                        score_bytes), but at most 8 (64 rows of histogram and bitmap do not
+ *                        fit 64 KiB)
+ *   rows_per_workgroup   4 waves: 4 * rows_per_wave
+ *   value_digit_passes, score_digit_passes
+ *                        8-bit digits of a value key and of a score key: the element bytes
+ *   lds_bytes            dynamic LDS of the launch: rows_per_workgroup * (1024 + 8 * ceil(n / 32))
+ *   grid                 ceil(m / rows_per_workgroup) workgroups of 256 threads
+ * Host only, launches nothing; any output pointer may be NULL.  Returns
+ * SPUTNIK_HIP_INVALID_ARGUMENT for a negative size, an element width other than 2 / 4 and
+ * m * n above INT_MAX. */
+SPUTNIK_HIP_API int sputnik_hip_csr_regrow_launch_shape(int m, int n, int score_bytes, int value_bytes,
+                             int* served, int* rows_per_wave, int* elements_per_lane,
+                             int* rows_per_workgroup, int* value_digit_passes,
+                             int* score_digit_passes, int* lds_bytes, int* max_n, int* grid);
+
 /*
  * out[r][i] = in[r][permutation[i]], i < n, for `rows` value arrays (strides in
  * elements) that share one permutation: the values of a static pattern in the

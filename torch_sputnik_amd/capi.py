@@ -108,6 +108,10 @@ SIGNATURES = {
                                          _c_i64, _c_ptr, _c_size] + [_c_ptr] * 5),
     "sputnik_hip_topk_to_csr_workspace_bytes": (_c_size, [_c_int] * 3),
     "sputnik_hip_topk_to_csr_launch_shape": (_c_int, [_c_int] * 4 + [_c_ptr] * 6),
+    "sputnik_hip_csr_regrow": (_c_int, [_c_int] * 3 + [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_int, _c_i64,
+                                        ctypes.c_uint, _c_ptr, _c_size] + [_c_ptr] * 4),
+    "sputnik_hip_csr_regrow_workspace_bytes": (_c_size, [_c_int] * 3),
+    "sputnik_hip_csr_regrow_launch_shape": (_c_int, [_c_int] * 4 + [_c_ptr] * 9),
     "sputnik_hip_csr_transpose_checked": (_c_int, [_c_int] * 4 + [_c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_size, _c_ptr]),
@@ -534,6 +538,23 @@ def topk_to_csr_launch_shape(m, n, element_bytes, total):
     _check(lib().sputnik_hip_topk_to_csr_launch_shape(
         m, n, element_bytes, int(bool(total)), *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
         "sputnik_hip_topk_to_csr_launch_shape")
+    shape = {name: o.value for name, o in zip(names, outs)}
+    shape["served"] = bool(shape["served"])
+    return shape
+
+
+def csr_regrow_launch_shape(m, n, score_bytes, value_bytes):
+    """The instance of the per-row drop-and-grow kernel for an m x n pattern with scores and
+    values of those widths (2 or 4 bytes): a dict of served (bool: n <= max_n; the fields but
+    max_n are -1 where it is not), rows_per_wave, elements_per_lane, rows_per_workgroup,
+    value_digit_passes, score_digit_passes, lds_bytes, max_n and grid (include/sputnik_hip.h).
+    Host only; raises for sizes the entry rejects."""
+    names = ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "value_digit_passes",
+             "score_digit_passes", "lds_bytes", "max_n", "grid")
+    outs = [_c_int(-1) for _ in names]
+    _check(lib().sputnik_hip_csr_regrow_launch_shape(
+        m, n, score_bytes, value_bytes, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
+        "sputnik_hip_csr_regrow_launch_shape")
     shape = {name: o.value for name, o in zip(names, outs)}
     shape["served"] = bool(shape["served"])
     return shape

@@ -426,6 +426,46 @@ __device__ __forceinline__ void digit_histogram(const RowWalk<U>& walk, int shif
   }
 }
 
+// One digit of a row's radix select, from the row's filled bins: the digit whose bin holds the
+// need-th largest of the elements counted, to every lane of the group; *need becomes what is
+// still to take inside that bin, or 0 where there is nothing to take (need = 0, no row here).
+// A lane owns the `chunk` consecutive bins from `base`.
+__device__ __forceinline__ unsigned pick_digit(const unsigned* __restrict__ bins, int base, int chunk,
+                                               int group_lane, int group_lanes, unsigned long long group_mask,
+                                               int* need_io) {
+  const int lane = threadIdx.x % kWave;
+  const int need = *need_io;
+  unsigned mine = 0;
+  for (int j = 0; j < chunk; ++j) mine += bins[base + j];
+  unsigned incl = mine;   // elements in my bins and in those of the group's lanes above me
+  for (int off = 1; off < group_lanes; off <<= 1) {
+    const unsigned up = __shfl_down(incl, off, kWave);
+    if (group_lane + off < group_lanes) incl += up;
+  }
+  const unsigned above = incl - mine;
+  // the lane whose bins hold the need-th largest element
+  const bool owner = need > 0 && above < static_cast<unsigned>(need) && static_cast<unsigned>(need) <= above + mine;
+  int digit = 0, left = 0;
+  if (owner) {
+    unsigned acc = above;
+    for (int j = chunk - 1; j >= 0; --j) {
+      const unsigned c = bins[base + j];
+      if (acc + c >= static_cast<unsigned>(need)) {
+        digit = base + j;
+        left = need - static_cast<int>(acc);
+        break;
+      }
+      acc += c;
+    }
+  }
+  const unsigned long long who = __ballot(owner) & group_mask;
+  const int from = who != 0ull ? __ffsll(who) - 1 : lane;
+  digit = __shfl(digit, from, kWave);
+  left = __shfl(left, from, kWave);
+  *need_io = who != 0ull ? left : 0;   // (no owner: nothing to take, or no row here)
+  return static_cast<unsigned>(digit);
+}
+
 // Per-row mode: (T_r, q_r), the offsets r * k and the row order 0 .. m - 1.
 template <typename U>
 __global__ __launch_bounds__(kBuildBlock) void topk_row_select_kernel(
@@ -453,36 +493,8 @@ __global__ __launch_bounds__(kBuildBlock) void topk_row_select_kernel(
     __syncthreads();
     digit_histogram(walk, shift, prefix, bins);
     __syncthreads();
-    unsigned mine = 0;
-    for (int j = 0; j < chunk; ++j) mine += bins[base + j];
-    unsigned incl = mine;   // elements in my bins and in those of the group's lanes above me
-    for (int off = 1; off < group_lanes; off <<= 1) {
-      const unsigned up = __shfl_down(incl, off, kWave);
-      if (group_lane + off < group_lanes) incl += up;
-    }
-    const unsigned above = incl - mine;
-    // the lane whose bins hold the need-th largest element
-    const bool owner = need > 0 && above < static_cast<unsigned>(need) && static_cast<unsigned>(need) <= above + mine;
-    int digit = 0, left = 0;
-    if (owner) {
-      unsigned acc = above;
-      for (int j = chunk - 1; j >= 0; --j) {
-        const unsigned c = bins[base + j];
-        if (acc + c >= static_cast<unsigned>(need)) {
-          digit = base + j;
-          left = need - static_cast<int>(acc);
-          break;
-        }
-        acc += c;
-      }
-    }
-    const unsigned long long who = __ballot(owner) & group_mask;
-    const int from = who != 0ull ? __ffsll(who) - 1 : lane;
-    digit = __shfl(digit, from, kWave);
-    left = __shfl(left, from, kWave);
-    prefix = (prefix << kDigitBits) | static_cast<unsigned>(digit);
-    need = who != 0ull ? left : 0;   // (no owner: k = 0, or no row here)
-    __syncthreads();                 // (the bins are cleared again)
+    prefix = (prefix << kDigitBits) | pick_digit(bins, base, chunk, group_lane, group_lanes, group_mask, &need);
+    __syncthreads();   // (the bins are cleared again)
   }
   if (walk.live && group_lane == 0) {
     thresholds[row] = k > 0 ? prefix : kNoThreshold;
@@ -754,6 +766,245 @@ int launch_topk(const TopkShape& t, int m, int n, const void* scores_, int64_t r
   return st;
 }
 
+// ---------------------------------------------------------------------------
+// Per-row drop-and-grow of a CSR topology (sputnik_hip_csr_regrow): every row keeps the c_r of
+// its len_r entries with the largest value keys and takes the d_r = len_r - c_r columns outside
+// them with the largest score keys, in its own slots.  ONE launch: the group of lanes that
+// walks a row decides everything about it, and what the phases hand each other -- (T_v, q_v),
+// the old / kept bits of the columns, (T_s, q_s) -- stays in its registers and in its part of
+// LDS.  (A select + fill pair, as the top-k build has, would have to write the kept bits of
+// every row out and read them back, or mark them twice.)
+//   1  radix select over values[row_offsets[r] ..] (a ragged read, lane after lane): (T_v, q_v)
+//   2  the row's entries again: the old columns and the kept ones into two bit planes in LDS
+//   3  radix select over the dense score row outside the kept columns, keys clamped to the
+//      largest finite one: (T_s, q_s)
+//   4  the fill walk of topk_fill_kernel over the score row; a running count of old bits is
+//      the old entry index of a kept column
+// LDS of a row: the 256 bins and 2 * ceil(n / 32) words of bit planes.  Four rows of that at
+// one row per wave fit 64 KiB up to n = kRegrowMaxN; 64 rows (16 per wave) do not at any n, so
+// the narrowest instance is 8 rows per wave.
+// ---------------------------------------------------------------------------
+constexpr int kRegrowLdsBytes = 64 * 1024;   // what a launch gets without asking for more
+constexpr int kRegrowMaxRowsPerWave = 8;
+constexpr int kRegrowMaxN = 32 * ((kRegrowLdsBytes / kBuildWaves - kDigitBins * 4) / 8);
+static_assert(kBuildWaves * kRegrowMaxRowsPerWave * (kDigitBins + 2 * 2) * 4 <= kRegrowLdsBytes,
+              "8 rows per wave: n <= 8 * 8 columns, 2 words per plane");
+
+struct RegrowShape {
+  int status = 0;
+  int served = 0, max_n = kRegrowMaxN;
+  int rows_per_wave = -1, elements_per_lane = -1, rows_per_workgroup = -1;
+  int value_passes = -1, score_passes = -1, words = -1, lds_bytes = -1, grid = -1;
+};
+inline RegrowShape regrow_shape(int m, int n, int score_bytes, int value_bytes) {
+  RegrowShape r;
+  if ((score_bytes != 2 && score_bytes != 4) || (value_bytes != 2 && value_bytes != 4)) {
+    r.status = SPUTNIK_HIP_INVALID_ARGUMENT;
+    return r;
+  }
+  const BuildShape walk = build_shape(1, m, n, score_bytes);
+  r.status = walk.status;
+  if (r.status != 0 || n > kRegrowMaxN) return r;
+  r.served = 1;
+  r.rows_per_wave = min(walk.rows_per_wave, kRegrowMaxRowsPerWave);
+  r.elements_per_lane = walk.elements_per_lane;
+  r.rows_per_workgroup = kBuildWaves * r.rows_per_wave;
+  r.value_passes = value_bytes * 8 / kDigitBits;
+  r.score_passes = score_bytes * 8 / kDigitBits;
+  r.words = n / 32 + (n % 32 != 0 ? 1 : 0);
+  r.lds_bytes = r.rows_per_workgroup * (kDigitBins + 2 * r.words) * static_cast<int>(sizeof(unsigned));
+  r.grid = static_cast<int>(ceil_div64(m, r.rows_per_workgroup));
+  return r;
+}
+
+// Bit e of the result: the plane's bit of column first_column + e, e < 32; columns outside
+// the plane read 0.  first_column >= -31 (a piece starts at most V - 1 columns before its row).
+__device__ __forceinline__ unsigned plane_bits(const unsigned* __restrict__ plane, int words, int64_t first_column) {
+  const int64_t shifted = first_column + 32;
+  const int64_t w = (shifted >> 5) - 1;
+  const unsigned lo = w >= 0 && w < words ? plane[w] : 0u;
+  const unsigned hi = w + 1 < words ? plane[w + 1] : 0u;
+  return static_cast<unsigned>(((static_cast<uint64_t>(hi) << 32) | lo) >> (shifted & 31));
+}
+
+template <typename S, typename W>
+__global__ __launch_bounds__(kBuildBlock) void csr_regrow_kernel(
+    int m, int n, int nonzeros, int rows_per_wave, int words, unsigned key_limit,
+    const int* __restrict__ row_offsets, const int* __restrict__ column_indices, const W* __restrict__ values,
+    const int* __restrict__ drop_counts, const S* __restrict__ scores, int64_t row_stride,
+    int* __restrict__ out_columns, W* __restrict__ out_values, int64_t* __restrict__ out_source) {
+  constexpr int V = RowWalk<S>::V;
+  constexpr int PV = sizeof(W) * 8 / kDigitBits, PS = sizeof(S) * 8 / kDigitBits;
+  extern __shared__ unsigned regrow_lds[];   // per row: bins [256], old bits [words], kept bits [words]
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int group_lanes = kWave / rows_per_wave;
+  const int group = lane / group_lanes, group_lane = lane % group_lanes;
+  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
+  const unsigned long long group_mask =
+      (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
+  const unsigned long long below = group_mask & ((1ull << lane) - 1ull);
+  const RowWalk<S> walk(scores, row, row_stride, m, n, rows_per_wave);
+  unsigned* __restrict__ bins = regrow_lds + (wave * rows_per_wave + group) * (kDigitBins + 2 * words);
+  unsigned* __restrict__ old_bits = bins + kDigitBins;
+  unsigned* __restrict__ kept_bits = old_bits + words;
+  const int chunk = kDigitBins / group_lanes;
+  const int base = group_lane * chunk;
+
+  // the row's slots, inside [0, nonzeros) whatever the offsets say
+  int begin = 0, end = 0, drop = 0;
+  if (walk.live) {
+    begin = min(max(row_offsets[row], 0), nonzeros);
+    end = min(max(row_offsets[row + 1], begin), nonzeros);
+    drop = min(max(drop_counts[row], 0), end - begin);
+  }
+  const int length = end - begin, keep = length - drop;
+  // steps of the walk over the row's entries, the most of the wave's rows: every lane of the
+  // wave takes part in every ballot
+  int entry_steps = static_cast<int>((static_cast<int64_t>(length) + group_lanes - 1) / group_lanes);
+  for (int o = kWave / 2; o > 0; o >>= 1) entry_steps = max(entry_steps, __shfl_xor(entry_steps, o, kWave));
+
+  // 1: (T_v, q_v) of the keep largest value keys
+  unsigned prefix = 0;
+  int need = keep;
+  for (int p = 0; p < PV; ++p) {
+    const int shift = kDigitBits * (PV - 1 - p);
+    for (int j = 0; j < chunk; ++j) bins[base + j] = 0u;
+    __syncthreads();
+    for (int64_t i = static_cast<int64_t>(begin) + group_lane; i < end; i += group_lanes) {
+      const unsigned key = key_of(values[i]);
+      if (static_cast<unsigned>(static_cast<uint64_t>(key) >> (shift + kDigitBits)) == prefix)
+        atomicAdd(&bins[(key >> shift) & (kDigitBins - 1)], 1u);
+    }
+    __syncthreads();
+    prefix = (prefix << kDigitBits) | pick_digit(bins, base, chunk, group_lane, group_lanes, group_mask, &need);
+    __syncthreads();
+  }
+  const unsigned value_threshold = keep > 0 ? prefix : kNoThreshold;
+  const int value_quota = need;
+
+  // 2: the old and the kept columns.  A column outside the row sets no bit.
+  for (int j = group_lane; j < 2 * words; j += group_lanes) old_bits[j] = 0u;
+  __syncthreads();
+  int ties_seen = 0;
+  for (int s = 0; s < entry_steps; ++s) {
+    const int64_t i = static_cast<int64_t>(begin) + static_cast<int64_t>(s) * group_lanes + group_lane;
+    const bool in = i < end;
+    const unsigned key = in ? key_of(values[i]) : 0u;
+    const int column = in ? column_indices[i] : -1;
+    const bool tie = in && key == value_threshold;
+    const unsigned long long b = __ballot(tie);
+    const int rank = ties_seen + __popcll(b & below);
+    ties_seen += __popcll(b & group_mask);
+    if (in && static_cast<unsigned>(column) < static_cast<unsigned>(n)) {
+      const unsigned bit = 1u << (column & 31);
+      atomicOr(&old_bits[column >> 5], bit);
+      if (key > value_threshold || (tie && rank < value_quota)) atomicOr(&kept_bits[column >> 5], bit);
+    }
+  }
+  __syncthreads();
+
+  // 3: (T_s, q_s) of the drop largest score keys outside the kept columns
+  prefix = 0;
+  need = drop;
+  for (int p = 0; p < PS; ++p) {
+    const int shift = kDigitBits * (PS - 1 - p);
+    for (int j = 0; j < chunk; ++j) bins[base + j] = 0u;
+    __syncthreads();
+    for (int s = 0; s < walk.steps; ++s) {
+      int64_t c0;
+      unsigned valid;
+      const Piece<S> v = walk.load(s, &c0, &valid);
+      const unsigned open = valid & ~plane_bits(kept_bits, words, c0);
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const unsigned key = min(key_of(v.e[e]), key_limit);
+        if (((open >> e) & 1u) && static_cast<unsigned>(static_cast<uint64_t>(key) >> (shift + kDigitBits)) == prefix)
+          atomicAdd(&bins[(key >> shift) & (kDigitBins - 1)], 1u);
+      }
+    }
+    __syncthreads();
+    prefix = (prefix << kDigitBits) | pick_digit(bins, base, chunk, group_lane, group_lanes, group_mask, &need);
+    __syncthreads();
+  }
+  const unsigned score_threshold = drop > 0 ? prefix : kNoThreshold;
+  const int score_quota = need;
+
+  // 4: the new row, ascending, into [begin, end)
+  int64_t out = begin;
+  int old_seen = 0;   // old columns in the steps behind
+  ties_seen = 0;      // open columns equal to the threshold in the steps behind
+  for (int s = 0; s < walk.steps; ++s) {
+    int64_t c0;
+    unsigned valid;
+    const Piece<S> v = walk.load(s, &c0, &valid);
+    const unsigned old = valid & plane_bits(old_bits, words, c0);
+    const unsigned kept = valid & plane_bits(kept_bits, words, c0);
+    unsigned greater = 0, equal = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned key = min(key_of(v.e[e]), key_limit);
+      greater |= (key > score_threshold ? 1u : 0u) << e;
+      equal |= (key == score_threshold ? 1u : 0u) << e;
+    }
+    greater &= valid & ~kept;
+    equal &= valid & ~kept;
+    // column order: lane after lane, element after element inside a lane
+    int ties_before = 0, ties_step = 0, old_before = 0, old_step = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned long long t = __ballot((equal >> e) & 1u);
+      ties_before += __popcll(t & below);
+      ties_step += __popcll(t & group_mask);
+      const unsigned long long o = __ballot((old >> e) & 1u);
+      old_before += __popcll(o & below);
+      old_step += __popcll(o & group_mask);
+    }
+    unsigned flags = kept | greater;
+    int rank = ties_seen + ties_before;
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      if ((equal >> e) & 1u) {
+        if (rank < score_quota) flags |= 1u << e;
+        ++rank;
+      }
+    ties_seen += ties_step;
+    int before = 0, total = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned long long b = __ballot((flags >> e) & 1u);
+      before += __popcll(b & below);
+      total += __popcll(b & group_mask);
+    }
+    int64_t p = out + before;
+    int64_t from = static_cast<int64_t>(begin) + old_seen + old_before;   // old entries in front of my piece
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      if (((flags >> e) & 1u) && p < end) {
+        const bool carried = ((kept >> e) & 1u) && from < end;
+        out_columns[p] = static_cast<int>(c0 + e);
+        out_values[p] = carried ? values[from] : W{0};
+        out_source[p] = carried ? from : int64_t{-1};
+        ++p;
+      }
+      from += (old >> e) & 1u;
+    }
+    out += total;
+    old_seen += old_step;
+  }
+}
+
+template <typename S, typename W>
+int launch_regrow(const RegrowShape& r, int m, int n, int nonzeros, const int* row_offsets,
+                  const int* column_indices, const void* values, const int* drop_counts, const void* scores,
+                  int64_t row_stride, unsigned key_limit, int* out_columns, void* out_values,
+                  int64_t* out_source, hipStream_t stream) {
+  hipLaunchKernelGGL((csr_regrow_kernel<S, W>), dim3(r.grid), dim3(kBuildBlock), r.lds_bytes, stream, m, n,
+                     nonzeros, r.rows_per_wave, r.words, key_limit, row_offsets, column_indices,
+                     static_cast<const W*>(values), drop_counts, static_cast<const S*>(scores), row_stride,
+                     out_columns, static_cast<W*>(out_values), out_source);
+  return launch_status();
+}
+
 }  // namespace
 }  // namespace sputnik_hip
 
@@ -888,6 +1139,59 @@ int sputnik_hip_topk_to_csr(int m, int n, const void* scores, int element_bytes,
                                   row_offsets, column_indices, values, stream);
   if (st != 0 || !total_mode) return st;
   return sputnik_hip_csr_row_order(1, m, n, row_offsets, row_indices, stream_);
+}
+
+int sputnik_hip_csr_regrow_launch_shape(int m, int n, int score_bytes, int value_bytes, int* served,
+                                        int* rows_per_wave, int* elements_per_lane, int* rows_per_workgroup,
+                                        int* value_digit_passes, int* score_digit_passes, int* lds_bytes,
+                                        int* max_n, int* grid) {
+  const RegrowShape r = regrow_shape(m, n, score_bytes, value_bytes);
+  if (r.status != 0) return r.status;
+  if (served) *served = r.served;
+  if (rows_per_wave) *rows_per_wave = r.rows_per_wave;
+  if (elements_per_lane) *elements_per_lane = r.elements_per_lane;
+  if (rows_per_workgroup) *rows_per_workgroup = r.rows_per_workgroup;
+  if (value_digit_passes) *value_digit_passes = r.value_passes;
+  if (score_digit_passes) *score_digit_passes = r.score_passes;
+  if (lds_bytes) *lds_bytes = r.lds_bytes;
+  if (max_n) *max_n = r.max_n;
+  if (grid) *grid = r.grid;
+  return 0;
+}
+
+size_t sputnik_hip_csr_regrow_workspace_bytes(int m, int n, int nonzeros) {
+  return 0;   // one launch: what its phases hand each other stays in registers and LDS
+}
+
+int sputnik_hip_csr_regrow(int m, int n, int nonzeros, const int* row_offsets, const int* column_indices,
+                           const void* values, int value_bytes, const int* drop_counts, const void* scores,
+                           int score_bytes, int64_t scores_row_stride, unsigned score_key_limit,
+                           void* workspace, size_t workspace_bytes, int* out_column_indices, void* out_values,
+                           int64_t* out_source, sputnik_hip_stream_t stream_) {
+  const RegrowShape r = regrow_shape(m, n, score_bytes, value_bytes);
+  if (r.status != 0) return r.status;
+  if (!r.served || nonzeros < 0 || scores_row_stride < 0 ||
+      score_key_limit >= (1u << (8 * score_bytes - 1)))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (m == 0 || nonzeros == 0) return 0;
+  if (row_offsets == nullptr || column_indices == nullptr || drop_counts == nullptr || values == nullptr ||
+      !aligned_to(values, value_bytes) || scores == nullptr || !aligned_to(scores, score_bytes) ||
+      out_column_indices == nullptr || out_values == nullptr || !aligned_to(out_values, value_bytes) ||
+      out_source == nullptr || !aligned_to(out_source, sizeof(int64_t)) ||
+      !aligned_to(row_offsets, sizeof(int)) || !aligned_to(column_indices, sizeof(int)) ||
+      !aligned_to(drop_counts, sizeof(int)) || !aligned_to(out_column_indices, sizeof(int)))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+#define SPUTNIK_REGROW(S, W)                                                                                \
+  return launch_regrow<S, W>(r, m, n, nonzeros, row_offsets, column_indices, values, drop_counts, scores, \
+                             scores_row_stride, score_key_limit, out_column_indices, out_values, out_source, stream)
+  if (score_bytes == 2) {
+    if (value_bytes == 2) SPUTNIK_REGROW(uint16_t, uint16_t);
+    SPUTNIK_REGROW(uint16_t, uint32_t);
+  }
+  if (value_bytes == 2) SPUTNIK_REGROW(uint32_t, uint16_t);
+  SPUTNIK_REGROW(uint32_t, uint32_t);
+#undef SPUTNIK_REGROW
 }
 
 }  // extern "C"

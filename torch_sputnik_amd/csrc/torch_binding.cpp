@@ -1998,6 +1998,64 @@ std::vector<Tensor> topk_to_csr(const Tensor& scores_in, int64_t per_row, int64_
   return {row_indices, row_offsets, column_indices, values};
 }
 
+// One per-row drop-and-grow step of the CSR pattern (row_offsets [m + 1], column_indices [nnz])
+// with `values` [nnz] under dense `scores` [m, n] -> [column_indices, values, source (int64)] of
+// the new pattern in the same slots (sputnik_hip.h: sputnik_hip_csr_regrow).  nnz is known up
+// front: one launch, no synchronisation, torch allocations only.  Scores with a dense last
+// dimension are read in place.
+std::vector<Tensor> csr_regrow(const Tensor& values_in, const Tensor& row_offsets_in,
+                               const Tensor& column_indices_in, const Tensor& drop_counts_in,
+                               const Tensor& scores_in) {
+  TORCH_CHECK(values_in.is_cuda(), "values must be a GPU (HIP) tensor, got ", values_in.device());
+  for (const Tensor* t : {&row_offsets_in, &column_indices_in, &drop_counts_in, &scores_in})
+    TORCH_CHECK(t->device() == values_in.device(), "every tensor must be on ", values_in.device(), ", got ",
+                t->device());
+  const auto floating = [](const Tensor& t) {
+    return t.scalar_type() == at::kFloat || t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16;
+  };
+  TORCH_CHECK(floating(values_in), "values must be float32, float16 or bfloat16, got ", values_in.scalar_type());
+  TORCH_CHECK(floating(scores_in), "scores must be float32, float16 or bfloat16, got ", scores_in.scalar_type());
+  for (const Tensor* t : {&row_offsets_in, &column_indices_in, &drop_counts_in})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1, "row_offsets, column_indices and drop_counts "
+                "must be 1-D int32 tensors, got ", t->scalar_type(), " ", t->sizes());
+  TORCH_CHECK(scores_in.dim() == 2, "expected [m, n] scores, got ", scores_in.sizes());
+  TORCH_CHECK(row_offsets_in.numel() == scores_in.size(0) + 1 && drop_counts_in.numel() == scores_in.size(0),
+              "row_offsets should be [m + 1] and drop_counts [m] for [m, n] scores ", scores_in.sizes(),
+              ", got ", row_offsets_in.sizes(), " and ", drop_counts_in.sizes());
+  TORCH_CHECK(values_in.dim() == 1 && values_in.numel() == column_indices_in.numel(),
+              "values should be [nnz] like column_indices ", column_indices_in.sizes(), ", got ", values_in.sizes());
+  const c10::DeviceGuard guard(values_in.device());
+  const Tensor scores = scores_in.size(1) > 1 && scores_in.stride(1) != 1 ? scores_in.contiguous() : scores_in;
+  const Tensor values = values_in.contiguous(), row_offsets = row_offsets_in.contiguous();
+  const Tensor column_indices = column_indices_in.contiguous(), drop_counts = drop_counts_in.contiguous();
+  const int m = to_int(scores.size(0), "m"), n = to_int(scores.size(1), "n");
+  const int nonzeros = to_int(values.numel(), "nnz");
+  const int score_bytes = static_cast<int>(scores.element_size());
+  const int value_bytes = static_cast<int>(values.element_size());
+  int served = 0, max_n = 0;
+  check_status(sputnik_hip_csr_regrow_launch_shape(m, n, score_bytes, value_bytes, &served, nullptr, nullptr,
+                                                   nullptr, nullptr, nullptr, nullptr, &max_n, nullptr),
+               "csr_regrow");
+  TORCH_CHECK(served, "torch_sputnik::csr_regrow: n = ", n, " is beyond the ", max_n, " columns the kernel's "
+              "LDS bitmap holds (sputnik_hip_csr_regrow_launch_shape); take topology.regrow_per_row");
+  // the key of the largest finite value of the scores' dtype
+  const unsigned key_limit = scores.scalar_type() == at::kFloat ? 0x7f7fffffu
+                             : scores.scalar_type() == at::kHalf ? 0x7bffu : 0x7f7fu;
+  Tensor out_columns = at::empty_like(column_indices);
+  Tensor out_values = at::empty_like(values);
+  Tensor source = at::empty({static_cast<int64_t>(nonzeros)}, column_indices.options().dtype(at::kLong));
+  const size_t ws_bytes = sputnik_hip_csr_regrow_workspace_bytes(m, n, nonzeros);
+  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, scores.options().dtype(at::kByte));
+  check_status(sputnik_hip_csr_regrow(
+                   m, n, nonzeros, row_offsets.data_ptr<int>(), column_indices.data_ptr<int>(), values.data_ptr(),
+                   value_bytes, drop_counts.data_ptr<int>(), scores.data_ptr(), score_bytes,
+                   m > 1 ? scores.stride(0) : 0, key_limit, ws_bytes ? workspace.data_ptr() : nullptr, ws_bytes,
+                   out_columns.data_ptr<int>(), out_values.data_ptr(), source.data_ptr<int64_t>(),
+                   current_stream(values)),
+               "csr_regrow");
+  return {out_columns, out_values, source};
+}
+
 // ---- the fused attention with one mask per batch element (sputnik_hip.h:
 // sparse_attention_many_mask_*, sparse_attention_heads_many_mask_*) ----
 
@@ -2440,6 +2498,8 @@ TORCH_LIBRARY(torch_sputnik, m) {
   m.def("dense_to_csr(Tensor dense, bool with_values) -> Tensor[]");
   m.def("row_order(Tensor row_offsets) -> Tensor");
   m.def("topk_to_csr(Tensor scores, int per_row, int total, Tensor? values_from) -> Tensor[]");
+  m.def("csr_regrow(Tensor values, Tensor row_offsets, Tensor column_indices, Tensor drop_counts, "
+        "Tensor scores) -> Tensor[]");
   m.def(
       "sparse_attention_many_mask(int b, Tensor nonzeros, Tensor query, Tensor key, Tensor value, "
       "Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, bool want_lse, "
@@ -2539,6 +2599,7 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("dense_to_csr", &dense_to_csr);
   m.impl("row_order", &row_order);
   m.impl("topk_to_csr", &topk_to_csr);
+  m.impl("csr_regrow", &csr_regrow);
   m.impl("sparse_attention_many_mask", &sparse_attention_many_mask);
   m.impl("sparse_attention_many_mask_plan", &sparse_attention_many_mask_plan);
   m.impl("sparse_attention_heads_many_mask", &sparse_attention_heads_many_mask);

@@ -76,9 +76,10 @@ class SparseLinear(nn.Module):
         functional.register_static_topology(row_indices, row_offsets, column_indices)
 
     @torch.no_grad()
-    def update_topology(self, drop_fraction, grow_scores=None, generator=None):
+    def update_topology(self, drop_fraction, grow_scores=None, generator=None, per_row=False):
         """One drop-and-grow step of dynamic sparse training (SET, RigL) with an unchanged
-        number of entries ``nnz``:
+        number of entries ``nnz``, ranked over the whole matrix or, ``per_row=True``, inside
+        every row (below).  Matrix-wide:
 
         1. ``d = int(drop_fraction * nnz)`` entries are dropped: the ``nnz - d`` of largest
            ``|values|`` are kept, ties to the lower entry index.
@@ -97,8 +98,25 @@ class SparseLinear(nn.Module):
         ``d == 0`` changes nothing (``source = arange(nnz)``).
 
         Selection and CSR build are one ``topology.topk_to_csr`` call (on the device for a GPU
-        module).  Out of scope: regrowth per row, and the dense weight gradient itself -- pass
-        e.g. ``dy.flatten(0, 1).T @ x.flatten(0, 1)``."""
+        module).
+
+        ``per_row=True`` (SET per neuron, RigL with a fixed fan-in): every row keeps its
+        length.  Row r of ``len_r`` entries drops ``d_r = floor(float64(len_r) *
+        drop_fraction)`` of them -- its entries of smallest ``|values|``, ties dropping the
+        higher column -- and grows ``d_r`` where ``|grow_scores[r]|`` is largest outside the
+        kept columns, ties to the lowest column; a layer from ``from_dense(per_row=True)``
+        stays row balanced.  ``grow_scores`` is passed as it is: the sign is ignored and NaN and
+        inf count as the dtype's largest finite value inside the rule
+        (``topology.regrow_per_row``, which is one kernel launch without a host
+        synchronisation for a GPU module).  Values, ``source`` and the replaced index tensors
+        are as in 3; ``row_indices`` and ``row_offsets`` are replaced by clones.  Where not
+        even a full row could drop an entry (``floor(in_features * drop_fraction) == 0``)
+        nothing changes.
+
+        Out of scope: the dense weight gradient itself -- pass e.g.
+        ``dy.flatten(0, 1).T @ x.flatten(0, 1)``."""
+        if per_row:
+            return self._update_topology_per_row(drop_fraction, grow_scores, generator)
         values = self.values.detach()
         nnz = values.numel()
         device = values.device
@@ -148,6 +166,33 @@ class SparseLinear(nn.Module):
         self.values.copy_(new_values)
         functional.unregister_static_topology(self.row_indices, self.row_offsets, self.column_indices)
         self._set_topology(None, row_indices, row_offsets, column_indices)
+        return source
+
+    def _update_topology_per_row(self, drop_fraction, grow_scores, generator):
+        values = self.values.detach()
+        nnz = values.numel()
+        device = values.device
+        out_f, in_f = self.output_features, self.input_features
+        if not 0.0 <= drop_fraction <= 1.0:
+            raise ValueError(f"update_topology: drop_fraction {drop_fraction} is outside 0 .. 1")
+        if grow_scores is not None and tuple(grow_scores.shape) != (out_f, in_f):
+            raise ValueError(f"update_topology: grow_scores should be [{out_f}, {in_f}], got "
+                             f"{tuple(grow_scores.shape)}")
+        # len_r <= in_features is known on the host; the lengths themselves are not read back
+        if math.floor(float(in_f) * drop_fraction) == 0:
+            return torch.arange(nnz, dtype=torch.int64, device=device)
+        lengths = self.row_offsets[1:] - self.row_offsets[:-1]
+        drop_counts = torch.floor(lengths.to(torch.float64) * drop_fraction).to(torch.int32)
+        if grow_scores is None:
+            where = generator.device if generator is not None else device
+            scores = torch.rand(out_f, in_f, generator=generator, device=where).to(device)
+        else:
+            scores = grow_scores.detach().to(device)
+        column_indices, new_values, source = topology.regrow_per_row(
+            values, self.row_offsets, self.column_indices, drop_counts, scores)
+        self.values.copy_(new_values)
+        functional.unregister_static_topology(self.row_indices, self.row_offsets, self.column_indices)
+        self._set_topology(None, self.row_indices.clone(), self.row_offsets.clone(), column_indices)
         return source
 
     def forward(self, x):

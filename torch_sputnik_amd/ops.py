@@ -287,6 +287,48 @@ def topk_to_csr(scores, per_row=None, total=None, values_from=None):
                                   values_from))
 
 
+def check_regrow_arguments(values, row_offsets, column_indices, drop_counts, scores):
+    """ValueError unless the five tensors are one CSR pattern with its values, drop counts and
+    dense scores (shapes, int32 indices, one device).  Dtypes of values and scores are the
+    caller's matter."""
+    if scores.dim() != 2:
+        raise ValueError(f"csr_regrow: expected [m, n] scores, got {tuple(scores.shape)}")
+    m = scores.size(0)
+    for name, t, size in (("row_offsets", row_offsets, m + 1), ("drop_counts", drop_counts, m),
+                          ("column_indices", column_indices, values.numel())):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != size:
+            raise ValueError(f"csr_regrow: {name} should be int32 [{size}], got {t.dtype} {tuple(t.shape)}")
+    if values.dim() != 1:
+        raise ValueError(f"csr_regrow: values should be [nnz], got {tuple(values.shape)}")
+    for name, t in (("row_offsets", row_offsets), ("column_indices", column_indices),
+                    ("drop_counts", drop_counts), ("scores", scores)):
+        if t.device != values.device:
+            raise ValueError(f"csr_regrow: {name} is on {t.device}, values on {values.device}")
+
+
+def csr_regrow(values, row_offsets, column_indices, drop_counts, scores):
+    """One per-row drop-and-grow step of a CSR pattern on the device (csrc/topology.hip): row r
+    of ``len_r`` entries drops ``d_r = clamp(drop_counts[r], 0, len_r)`` of them and grows as
+    many.  Kept: the ``len_r - d_r`` entries of largest ``|values|``, ties to the lower column.
+    Grown: the ``d_r`` columns outside the kept ones of largest ``|scores[r]|``, ties to the
+    lowest column; NaN and inf scores count as the dtype's largest finite value; columns dropped
+    in this call are eligible.  Magnitudes rank by the bit pattern without the sign
+    (``topology.magnitude_keys``).  values [nnz] and scores [m, n] are float32 / float16 /
+    bfloat16, each of its own dtype; row_offsets [m + 1], column_indices [nnz] (ascending inside
+    a row) and drop_counts [m] are int32.  -> (column_indices, values, source) of the new
+    pattern in the same slots, ascending inside a row: a kept entry carries its value bit for
+    bit and its old index in ``source`` (int64), a grown one is +0.0 and -1.  One launch, no
+    host synchronisation.  Raises for CPU tensors and for ``n`` beyond
+    ``capi.csr_regrow_launch_shape(...)["max_n"]``."""
+    check_regrow_arguments(values, row_offsets, column_indices, drop_counts, scores)
+    for name, t in (("values", values), ("scores", scores)):
+        if t.dtype not in _TOPK_DTYPES:
+            raise ValueError(f"csr_regrow: {name} must be float32, float16 or bfloat16, got {t.dtype}")
+    if not values.is_cuda:
+        raise RuntimeError("csr_regrow: GPU tensors only (topology.regrow_per_row serves CPU tensors)")
+    return tuple(_ops.csr_regrow(values, row_offsets, column_indices, drop_counts, scores))
+
+
 def sparse_attention_many_mask(b, nonzeros, row_indices, row_offsets, column_indices, query, key,
                                value, scale, with_lse=False, plan=None):
     """softmax(scale * q k^T at the mask) v with one mask per batch element in ONE kernel:

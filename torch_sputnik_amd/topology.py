@@ -187,6 +187,82 @@ def magnitude_prune(matrix, density=None, nonzeros=None, per_row=False):
     return values, row_indices, row_offsets, column_indices
 
 
+def _regrow_served(values, scores):
+    if not (_device_build and values.is_cuda and values.dtype in _TOPK_DTYPES and scores.dtype in _TOPK_DTYPES):
+        return False
+    try:
+        return capi.csr_regrow_launch_shape(scores.size(0), scores.size(1), scores.element_size(),
+                                            values.element_size())["served"]
+    except RuntimeError:   # (more than INT_MAX elements)
+        return False
+
+
+def _first_in_stable_order(keys, counts):
+    """bool [m, n]: the counts[r] first columns of row r in the stable descending order of its
+    keys (largest key first, lowest column among equals)"""
+    m, n = keys.shape
+    order = torch.argsort(keys, dim=1, descending=True, stable=True)
+    rank = torch.empty_like(order).scatter_(1, order, torch.arange(n, device=keys.device).expand(m, n))
+    return rank < counts[:, None]
+
+
+def regrow_per_row(values, row_offsets, column_indices, drop_counts, scores):
+    """``ops.csr_regrow`` for any tensor: one per-row drop-and-grow step of the CSR pattern
+    (row_offsets [m + 1], column_indices [nnz], int32, ascending inside a row) with ``values``
+    [nnz] under dense ``scores`` [m, n].  Row r of ``len_r`` entries has
+    ``d_r = clamp(drop_counts[r], 0, len_r)``:
+
+    * Kept: its ``len_r - d_r`` entries of largest value key (``magnitude_keys``: NaN above inf,
+      -0.0 with 0.0), ties to the lower column.
+    * Grown: the ``d_r`` columns outside Kept of largest score key, ties to the lowest column; a
+      score key is clamped to that of the dtype's largest finite value (NaN and inf count as
+      it); the sign is ignored; columns dropped in this step are eligible.
+    * The new row is Kept and Grown in ascending column order in the row's own slots.
+
+    -> (column_indices int32 [nnz], values [nnz], source int64 [nnz]), new tensors: a kept entry
+    carries its value bit for bit and its old entry index, a grown one is +0.0 and -1.
+    ``row_offsets`` does not change.
+
+    GPU float32 / float16 / bfloat16 values and scores take the device kernel where
+    ``capi.csr_regrow_launch_shape`` serves ``n`` (one launch, no host synchronisation); CPU
+    tensors, other dtypes (ranked as ``.float()``), wider rows and ``enable_device_build(False)``
+    take the same rule in torch: per row a stable descending argsort of the keys, with the kept
+    columns forced first.  Both give the same integers and value bits."""
+    ops.check_regrow_arguments(values, row_offsets, column_indices, drop_counts, scores)
+    values, scores = values.detach(), scores.detach()
+    if scores.dtype not in _TOPK_DTYPES:
+        scores = scores.float()
+    if _regrow_served(values, scores):
+        return ops.csr_regrow(values, row_offsets, column_indices, drop_counts, scores)
+    m, n = scores.shape
+    nnz = column_indices.numel()
+    index = dict(dtype=torch.int64, device=values.device)
+    lengths = (row_offsets[1:] - row_offsets[:-1]).to(torch.int64)
+    rows = torch.repeat_interleave(torch.arange(m, **index), lengths, output_size=nnz)
+    flat = rows * n + column_indices.to(torch.int64)
+    drop = torch.minimum(drop_counts.to(torch.int64).clamp(min=0), lengths)
+    # dense images of the old entries: their value keys (-1 elsewhere: behind every entry) and
+    # their indices
+    value_keys = torch.full((m * n,), -1, **index)
+    value_keys[flat] = magnitude_keys(values if values.dtype in _TOPK_DTYPES else values.float())
+    entry = torch.full((m * n,), -1, **index)
+    entry[flat] = torch.arange(nnz, **index)
+    kept = _first_in_stable_order(value_keys.view(m, n), lengths - drop)
+    limit = int(magnitude_keys(torch.tensor([torch.finfo(scores.dtype).max], dtype=scores.dtype))[0])
+    score_keys = magnitude_keys(scores).clamp(max=limit)
+    score_keys = torch.where(kept, limit + 1, score_keys)              # Kept comes first
+    new = _first_in_stable_order(score_keys, lengths).view(-1)
+    # the flat positions of the new entries, ascending; nnz of them, so nothing is read back
+    slot = torch.where(new, torch.cumsum(new, 0) - 1, nnz)
+    new_flat = torch.empty(nnz + 1, **index).scatter_(0, slot, torch.arange(m * n, **index))[:nnz]
+    carried = kept.view(-1)[new_flat]
+    source = torch.where(carried, entry[new_flat], -1)
+    bits = values.contiguous().view(_BIT_VIEWS[values.element_size()])
+    new_bits = torch.where(carried, bits[source.clamp(min=0)], torch.zeros(1, dtype=bits.dtype, device=bits.device))
+    new_columns = new_flat - torch.div(new_flat, max(n, 1), rounding_mode="floor") * n
+    return new_columns.to(torch.int32), new_bits.view(values.dtype), source
+
+
 def generate_mask(m, n, device="cpu", sparsity=0.9, round_to=4, generator=None):
     """Random 0/1 mask with the nonzero count of modules/sparse_attention.py:25-36:
     ``int(m*n*sparsity)`` zeros rounded DOWN to a multiple of ``round_to``.
