@@ -401,6 +401,45 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_linear_half_input_gradient(int out_featur
                               int grad_input_type, sputnik_hip_stream_t stream);
 
 /*
+ * The DENSE weight gradient of the layer (RigL's grow scores):
+ *   dense_grad[o][i] = sum_b sum_s dy[b][o][s] x[b][s][i]     float32, row stride dense_ld
+ * sputnik_hip_sparse_linear_half_weight_gradient_dense is the weight gradient above with a
+ * second output: the sampled epilogue holds the whole 128 x 128 float32 tile in LDS and
+ * stores the entries under the mask; here the tile is stored as well, so ONE launch gives
+ * grad_values[nonzeros] and dense_grad[out, in], and grad_values[p] equals the image element
+ * at entry p's (row, column) bit for bit.  Arguments and conditions as the weight gradient's
+ * (seq a multiple of 64, in a multiple of 8, 16-byte aligned operands), and dense_grad
+ * 16-byte aligned with dense_ld a multiple of 4, at least in_features.  Always one workgroup
+ * per tile (a tile shared by several would need a partial image per split): no scratch.
+ * Only elements with o < out_features and i < in_features are written.
+ *
+ * sputnik_hip_sparse_linear_dense_weight_gradient is the standalone form -- no mask, nothing
+ * sampled -- for layers off the tile route and float32 layers.  grad_type and x_type are
+ * each tile_type (the tensor itself) or SPUTNIK_HIP_F32 (the PLANES of the float32 tensor,
+ * sputnik_hip_half_planes over the whole tensor).  x_layout: SPUTNIK_HIP_X_BSI, x
+ * [batch, seq, in] (as the half layer has it), or SPUTNIK_HIP_X_BIS, x [batch, in, seq] (the
+ * k-major operand of left_spmm).  Served (.._supported, host only, 1 / 0): seq a multiple of
+ * 64, in a multiple of 8, out * in, out * seq and in * seq below 2^30, any density;
+ * float16 tiles with any pair of operand types, bfloat16 tiles with at most one float32
+ * operand (nine plane pairs are not built: SPUTNIK_HIP_UNSUPPORTED).  Operands 16-byte
+ * aligned.  Neither form accumulates into dense_grad.
+ */
+#define SPUTNIK_HIP_X_BSI 0
+#define SPUTNIK_HIP_X_BIS 1
+SPUTNIK_HIP_API int sputnik_hip_sparse_linear_half_weight_gradient_dense(int out_features, int in_features,
+                              int seq, int batch, int nonzeros, const int* row_offsets,
+                              const int* column_indices, const void* grad_output, int grad_type,
+                              const void* x, int tile_type, float* grad_values, const void* plan,
+                              float* dense_grad, int64_t dense_ld, sputnik_hip_stream_t stream);
+SPUTNIK_HIP_API int sputnik_hip_sparse_linear_dense_weight_gradient_supported(int out_features,
+                              int in_features, int seq, int batch, int grad_type, int x_type,
+                              int x_layout, int tile_type);
+SPUTNIK_HIP_API int sputnik_hip_sparse_linear_dense_weight_gradient(int out_features, int in_features,
+                              int seq, int batch, const void* grad_output, int grad_type,
+                              const void* x, int x_type, int x_layout, int tile_type,
+                              float* dense_grad, int64_t dense_ld, sputnik_hip_stream_t stream);
+
+/*
  * The same layer's forward pass in ROW orientation, the layout attention wants:
  *   y[b][s][o] = sum_i x[b][s][i] W[o][i]
  * x: element (b, s, i) at x + b * x_batch_stride + s * x_row_stride + i, in `tile_type`;

@@ -158,6 +158,11 @@ SIGNATURES = {
     "sputnik_hip_sparse_linear_half_weight_gradient": (_c_int, [_c_int] * 5 + [_c_ptr, _c_ptr, _c_ptr, _c_int,
                                                                               _c_ptr, _c_int, _c_ptr, _c_ptr,
                                                                               _c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_linear_half_weight_gradient_dense": (_c_int, [_c_int] * 5 + [
+        _c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
+    "sputnik_hip_sparse_linear_dense_weight_gradient_supported": (_c_int, [_c_int] * 8),
+    "sputnik_hip_sparse_linear_dense_weight_gradient": (_c_int, [_c_int] * 4 + [
+        _c_ptr, _c_int, _c_ptr, _c_int, _c_int, _c_int, _c_ptr, _c_i64, _c_ptr]),
     "sputnik_hip_sparse_linear_half_input_gradient": (_c_int, [_c_int] * 4 + [_c_ptr, _c_int, _c_ptr, _c_int,
                                                                              _c_int, _c_ptr, _c_int, _c_ptr]),
     "sputnik_hip_sddmm_sum_group_planned": (_c_int, [_c_int] * 5 + [_c_ptr, _c_i64, _c_i64, _c_ptr]),

@@ -29,7 +29,15 @@
 // times 2^-11.
 //
 // Epilogues: kDense (float32 tile, bias / ReLU), kDenseHalf (rounded to T), kSampled (the
-// tile goes to LDS and the entries of a CSR mask that fall into it are stored: SDDMM).
+// tile goes to LDS and the entries of a CSR mask that fall into it are stored: SDDMM),
+// kSampledDense (kSampled, and the WHOLE tile is stored as well, to the float32 image
+// out.dense [m][out.ld]: a layer's weight gradient under its mask together with the dense
+// one -- RigL's grow scores -- from one launch.  Both outputs are read from the tile in LDS,
+// so an entry of `sampled` and the image element at its place are the same bits; the image
+// is written in 16-byte pieces -- n % 4 == 0, out.ld % 4 == 0 and a 16-byte aligned image
+// are the host's to check -- and only at row < m, col < n.  This epilogue runs with ONE
+// split (outers == 1): a tile that two workgroups share would need a partial image per
+// split and a second pass over it).
 //
 // Where the time of a launch goes (config 5's forward pass, one plane pair, 34.4 dense GFLOP;
 // SPUTNIK_HIP_MFMA_DEBUG switches parts off, tools/half_linear_bench.py): 40.4 us, of which
@@ -52,7 +60,10 @@ namespace mfma_tiles {
 
 typedef short s4v __attribute__((__vector_size__(8)));
 
-constexpr int kDense = 0, kSampled = 1, kDenseHalf = 2;
+constexpr int kDense = 0, kSampled = 1, kDenseHalf = 2, kSampledDense = 3;
+
+// (the epilogues that put the tile into LDS)
+constexpr bool samples(int epi) { return epi == kSampled || epi == kSampledDense; }
 
 // The (A plane, B plane) pairs a step multiplies.
 template <int PA, int PB>
@@ -210,7 +221,7 @@ struct TileGeometry {
   static constexpr int kStage = kABytes + kBBytes;
   static constexpr int kTileFloats = TM * kPitch;                 // the sampled epilogue's tile
   static constexpr int kBounds = 4 * (TM + 4);
-  static constexpr int kSmem = EPI == kSampled && kTileFloats * 4 + kBounds > kStages * kStage
+  static constexpr int kSmem = samples(EPI) && kTileFloats * 4 + kBounds > kStages * kStage
                                    ? kTileFloats * 4 + kBounds : kStages * kStage;
 };
 
@@ -431,7 +442,7 @@ __global__ __launch_bounds__((TileGeometry<TM, EPI>::kThreads), (TM == 256 ? 1 :
                      : acc[0][i][j][reg];
   };
 
-  if constexpr (EPI != kSampled) {
+  if constexpr (!samples(EPI)) {
     // ---- the accumulators' 32 x 32 blocks (column = lane & 31: 128- / 64-byte runs) ----
     // (vmcnt retires in order: a load between the stores would make every store wait for
     // the ones before it -- the bias values are all fetched BEFORE the first store, and
@@ -485,6 +496,19 @@ __global__ __launch_bounds__((TileGeometry<TM, EPI>::kThreads), (TM == 256 ? 1 :
         }
     float* __restrict__ o = out.sampled + static_cast<int64_t>(outer) * out.nonzeros;
     const int* __restrict__ column_indices = out.column_indices;
+    // kSampledDense: the tile as it stands in LDS to the image, a row's 512 bytes by 32
+    // consecutive lanes (called behind the rendezvous that follows the tile's writes)
+    auto store_image = [&]() {
+      float* __restrict__ image = static_cast<float*>(out.dense);
+#pragma unroll
+      for (int it = 0; it < kTile / 8; ++it) {   // TM * 32 pieces over 2 * TM threads
+        const int piece = it * G::kThreads + static_cast<int>(threadIdx.x);
+        const int row = piece >> 5, col = (piece & 31) * 4;
+        const float4 v = *reinterpret_cast<const float4*>(tile_lds + row * kPitch + col);
+        if (r0 + row < m && c0 + col < n)   // (n % 4 == 0: a piece lies inside or outside)
+          *reinterpret_cast<float4*>(image + static_cast<int64_t>(r0 + row) * out.ld + (c0 + col)) = v;
+      }
+    };
     // With a plan (sddmm_mfma_plan: where every row's entries cross the tile columns) whose
     // rows all have ascending columns, a row's entries inside this tile are one known run.
     bool by_table = out.plan != nullptr;
@@ -517,6 +541,7 @@ __global__ __launch_bounds__((TileGeometry<TM, EPI>::kThreads), (TM == 256 ? 1 :
           const int p = from[j] + l16 + 16 * e;
           cols[j][e] = p < to[j] ? column_indices[p] : c0;
         }
+      if constexpr (EPI == kSampledDense) store_image();   // (stores, behind the loads above)
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float* tile_row = tile_lds + (group + kGroups * j) * kPitch - c0;
@@ -539,6 +564,8 @@ __global__ __launch_bounds__((TileGeometry<TM, EPI>::kThreads), (TM == 256 ? 1 :
     if (threadIdx.x <= TM)
       bounds[threadIdx.x] = out.row_offsets[min(r0 + static_cast<int>(threadIdx.x), m)];
     __syncthreads();
+    // (the walk below interleaves loads and stores as it is: the image goes first)
+    if constexpr (EPI == kSampledDense) store_image();
     const int first = bounds[0], last = bounds[TM];
     // a lane takes four consecutive entries per round; its row moves forward only
     int row = 0;

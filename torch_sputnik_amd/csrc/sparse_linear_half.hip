@@ -15,6 +15,11 @@
 // enter as half planes whose sum is the value (float16: over the tensor's range, the power
 // of two in the trailer behind the planes, mfma_tiles.h; dy is split once per backward
 // pass, sputnik_hip_half_planes, and both gradients read the planes).
+//
+// The DENSE weight gradient (RigL's grow scores) is the weight gradient's tiles stored whole:
+// .._weight_gradient_dense writes them next to the sampled entries from one launch
+// (kSampledDense), sputnik_hip_sparse_linear_dense_weight_gradient is the same contraction
+// without a mask, for layers off this route and float32 layers.
 #include "mfma.h"
 #include "mfma_gemm.h"
 #include "options.h"
@@ -204,6 +209,101 @@ int sputnik_hip_sparse_linear_half_weight_gradient(int out_features, int in_feat
                                                                wide_tile(out_features, in_features, 0));
   if (st != 0 || splits == 1) return st;
   return sum_partial_vectors(nonzeros, splits, static_cast<const float*>(scratch), grad_values, stream);
+}
+
+// The weight gradient above and, from the same tiles, the DENSE one: dense_grad[o][i] (row
+// stride dense_ld) = sum_b sum_s dy[b][o][s] x[b][s][i] at every (o, i) -- RigL's grow
+// scores.  The sampled epilogue has the whole float32 tile in LDS and stores the entries
+// under the mask; kSampledDense stores the tile as well, so grad_values[p] and the image
+// element at entry p's place are the same bits.  One workgroup per tile (no splits: a shared
+// tile would need a partial image per split), hence no scratch.
+int sputnik_hip_sparse_linear_half_weight_gradient_dense(int out_features, int in_features, int seq,
+                                                         int batch, int nonzeros, const int* row_offsets,
+                                                         const int* column_indices, const void* grad_output,
+                                                         int grad_type, const void* x, int tile_type,
+                                                         float* grad_values, const void* plan,
+                                                         float* dense_grad, int64_t dense_ld,
+                                                         sputnik_hip_stream_t stream) {
+  if (!half_type(tile_type) || seq % kStep != 0 || in_features % 8 != 0 || out_features <= 0 ||
+      batch <= 0 || nonzeros <= 0)
+    return SPUTNIK_HIP_UNSUPPORTED;
+  if (grad_type != SPUTNIK_HIP_F32 && grad_type != tile_type) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (grad_values == nullptr || dense_grad == nullptr || dense_ld < in_features)
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (!aligned_to(grad_output, 16) || !aligned_to(x, 16) || !aligned_to(dense_grad, 16) || dense_ld % 4 != 0)
+    return SPUTNIK_HIP_UNSUPPORTED;
+  const int pg = planes_of(grad_type, tile_type);
+  const int64_t per_replica = static_cast<int64_t>(out_features) * seq;
+  const GemmOperand a{grad_output, seq, per_replica, per_replica * batch};
+  const GemmOperand b{x, in_features, static_cast<int64_t>(seq) * in_features, 0};   // k = s major
+  GemmOut o{};
+  o.dense = dense_grad;
+  o.ld = dense_ld;
+  o.sampled = grad_values;
+  o.row_offsets = row_offsets;
+  o.column_indices = column_indices;
+  o.plan = static_cast<const int*>(plan);
+  o.nonzeros = nonzeros;
+  o.vector_columns = aligned_to(column_indices, 16) ? 1 : 0;
+  return launch_mfma_gemm_typed<false, true, kSampledDense>(tile_type, pg, 1, out_features, in_features,
+                                                            seq, batch, 1, true, a, b, o, stream,
+                                                            wide_tile(out_features, in_features, 0));
+}
+
+// The dense weight gradient on its own (no mask, nothing sampled), for layers off the tile
+// route and float32 layers: either operand in the tile type or as the planes of the float32
+// tensor (sputnik_hip_half_planes over the whole tensor); x [batch, seq, in] (k-major B
+// operand) or [batch, in, seq] (k-contiguous).  One workgroup per tile reduces all
+// (batch, s) steps -- the dense epilogue of one summed output.
+int sputnik_hip_sparse_linear_dense_weight_gradient_supported(int out_features, int in_features, int seq,
+                                                              int batch, int grad_type, int x_type,
+                                                              int x_layout, int tile_type) {
+  if (!half_type(tile_type)) return 0;
+  if ((grad_type != SPUTNIK_HIP_F32 && grad_type != tile_type) ||
+      (x_type != SPUTNIK_HIP_F32 && x_type != tile_type))
+    return 0;
+  if (x_layout != SPUTNIK_HIP_X_BSI && x_layout != SPUTNIK_HIP_X_BIS) return 0;
+  if (out_features <= 0 || in_features <= 0 || seq <= 0 || batch <= 0) return 0;
+  if (seq % kStep != 0 || in_features % 8 != 0) return 0;
+  if (static_cast<int64_t>(out_features) * in_features >= (int64_t{1} << 30) ||
+      static_cast<int64_t>(out_features) * seq >= (int64_t{1} << 30) ||
+      static_cast<int64_t>(in_features) * seq >= (int64_t{1} << 30))
+    return 0;
+  // (bfloat16: nine plane pairs are not built)
+  if (tile_type == SPUTNIK_HIP_BF16 && grad_type == SPUTNIK_HIP_F32 && x_type == SPUTNIK_HIP_F32) return 0;
+  return 1;
+}
+
+int sputnik_hip_sparse_linear_dense_weight_gradient(int out_features, int in_features, int seq, int batch,
+                                                    const void* grad_output, int grad_type, const void* x,
+                                                    int x_type, int x_layout, int tile_type,
+                                                    float* dense_grad, int64_t dense_ld,
+                                                    sputnik_hip_stream_t stream) {
+  if (!half_type(tile_type) || (grad_type != SPUTNIK_HIP_F32 && grad_type != tile_type) ||
+      (x_type != SPUTNIK_HIP_F32 && x_type != tile_type) ||
+      (x_layout != SPUTNIK_HIP_X_BSI && x_layout != SPUTNIK_HIP_X_BIS))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (grad_output == nullptr || x == nullptr || dense_grad == nullptr || dense_ld < in_features)
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (!sputnik_hip_sparse_linear_dense_weight_gradient_supported(out_features, in_features, seq, batch,
+                                                                 grad_type, x_type, x_layout, tile_type))
+    return SPUTNIK_HIP_UNSUPPORTED;
+  if (!aligned_to(grad_output, 16) || !aligned_to(x, 16) || !aligned_to(dense_grad, 4))
+    return SPUTNIK_HIP_UNSUPPORTED;
+  const int pg = planes_of(grad_type, tile_type), px = planes_of(x_type, tile_type);
+  const int64_t g_replica = static_cast<int64_t>(out_features) * seq;
+  const int64_t x_replica = static_cast<int64_t>(seq) * in_features;
+  const GemmOperand a{grad_output, seq, g_replica, g_replica * batch};
+  const GemmOperand b{x, x_layout == SPUTNIK_HIP_X_BSI ? in_features : seq, x_replica, x_replica * batch};
+  GemmOut o{};
+  o.dense = dense_grad;
+  o.ld = dense_ld;
+  const bool wide = wide_tile(out_features, in_features, 0);
+  if (x_layout == SPUTNIK_HIP_X_BSI)
+    return launch_mfma_gemm_typed<false, true, kDense>(tile_type, pg, px, out_features, in_features, seq,
+                                                       batch, 1, true, a, b, o, stream, wide);
+  return launch_mfma_gemm_typed<false, false, kDense>(tile_type, pg, px, out_features, in_features, seq,
+                                                      batch, 1, true, a, b, o, stream, wide);
 }
 
 // grad_input stored as grad_input_type (SPUTNIK_HIP_F32 or tile_type), [batch, seq, in].

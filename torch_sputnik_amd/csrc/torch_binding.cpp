@@ -28,6 +28,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <tuple>
 #include <vector>
 
 #include "../../include/sputnik_hip.h"
@@ -643,6 +644,73 @@ Tensor half_linear_weight_gradient(int64_t out64, const Tensor& row_offsets, con
                    scratch_bytes ? scratch.data_ptr() : nullptr, scratch_bytes, current_stream(x)),
                "half_linear_weight_gradient");
   return out;
+}
+
+// The weight gradient and, from the same tiles, the dense one: (grad_values [nnz], dense
+// [out, in]), both float32, one launch; grad_values[p] == dense[row_p, col_p] bit for bit.
+std::tuple<Tensor, Tensor> half_linear_weight_gradient_dense(int64_t out64, const Tensor& row_offsets,
+                                                             const Tensor& column_indices, const Tensor& grad,
+                                                             bool grad_is_planes, const Tensor& x_in,
+                                                             const c10::optional<Tensor>& plan) {
+  const Tensor x = x_in.contiguous();
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3,
+              "half_linear_weight_gradient_dense: x must be a GPU tensor [batch, seq, in]");
+  const int tile = tile_code_of(x);
+  const c10::DeviceGuard guard(x.device());
+  const int out_f = to_int(out64, "out"), batch = to_int(x.size(0), "batch"), seq = to_int(x.size(1), "seq"),
+            in_f = to_int(x.size(2), "in");
+  const Tensor ro = as_index(row_offsets, "row_offsets", x);
+  const Tensor ci = as_index(column_indices, "column_indices", x);
+  TORCH_CHECK(ro.size(0) == out_f + 1, "half_linear_weight_gradient_dense: row_offsets do not match out_features");
+  const int nonzeros = to_int(ci.size(0), "nonzeros");
+  const int grad_type = grad_is_planes ? SPUTNIK_HIP_F32 : tile;
+  const Tensor g = grad.contiguous();
+  const size_t want = grad_is_planes
+                          ? sputnik_hip_half_planes_bytes(static_cast<int64_t>(batch) * out_f * seq, tile)
+                          : static_cast<size_t>(batch) * out_f * seq * 2;
+  TORCH_CHECK(static_cast<size_t>(g.numel()) * g.element_size() >= want,
+              "half_linear_weight_gradient_dense: grad does not hold [batch, out, seq]");
+  Tensor out = at::empty({nonzeros}, x.options().dtype(at::kFloat));
+  Tensor dense = at::empty({out_f, in_f}, x.options().dtype(at::kFloat));
+  check_status(sputnik_hip_sparse_linear_half_weight_gradient_dense(
+                   out_f, in_f, seq, batch, nonzeros, ro.data_ptr<int>(), ci.data_ptr<int>(), g.data_ptr(),
+                   grad_type, x.data_ptr(), tile, out.data_ptr<float>(),
+                   plan.has_value() ? plan->data_ptr() : nullptr, dense.data_ptr<float>(), in_f,
+                   current_stream(x)),
+               "half_linear_weight_gradient_dense");
+  return std::make_tuple(out, dense);
+}
+
+// dense [out, in] float32 = sum over (batch, s) of dy x; either operand in the tile type or
+// as the planes of its float32 tensor (half_planes); x_layout 0: x [batch, seq, in], 1: x
+// [batch, in, seq].  The caller has asked sputnik_hip_sparse_linear_dense_weight_gradient_supported.
+Tensor dense_weight_gradient(const Tensor& grad, bool grad_is_planes, const Tensor& x_in, bool x_is_planes,
+                             int64_t x_layout, int64_t tile_type, int64_t out64, int64_t in64, int64_t seq64,
+                             int64_t batch64) {
+  TORCH_CHECK(grad.is_cuda() && x_in.is_cuda() && grad.device() == x_in.device(),
+              "dense_weight_gradient: expected GPU operands on one device");
+  const int tile = static_cast<int>(tile_type);
+  const c10::DeviceGuard guard(grad.device());
+  const int out_f = to_int(out64, "out"), in_f = to_int(in64, "in"), seq = to_int(seq64, "seq"),
+            batch = to_int(batch64, "batch");
+  TORCH_CHECK(out_f > 0 && in_f > 0 && seq > 0 && batch > 0, "dense_weight_gradient: empty operand");
+  const Tensor g = grad.contiguous(), x = x_in.contiguous();
+  const auto holds = [&](const Tensor& t, bool planes, int64_t count) {
+    const size_t want = planes ? sputnik_hip_half_planes_bytes(count, tile) : static_cast<size_t>(count) * 2;
+    return want > 0 && static_cast<size_t>(t.numel()) * t.element_size() >= want &&
+           (planes || type_code(t.scalar_type()) == tile);
+  };
+  TORCH_CHECK(holds(g, grad_is_planes, static_cast<int64_t>(batch) * out_f * seq),
+              "dense_weight_gradient: grad does not hold [batch, out, seq]");
+  TORCH_CHECK(holds(x, x_is_planes, static_cast<int64_t>(batch) * seq * in_f),
+              "dense_weight_gradient: x does not hold [batch, seq, in]");
+  Tensor dense = at::empty({out_f, in_f}, g.options().dtype(at::kFloat));
+  check_status(sputnik_hip_sparse_linear_dense_weight_gradient(
+                   out_f, in_f, seq, batch, g.data_ptr(), grad_is_planes ? SPUTNIK_HIP_F32 : tile, x.data_ptr(),
+                   x_is_planes ? SPUTNIK_HIP_F32 : tile, static_cast<int>(x_layout), tile,
+                   dense.data_ptr<float>(), in_f, current_stream(g)),
+               "dense_weight_gradient");
+  return dense;
 }
 
 // dx [batch, seq, in] in `like`'s type (the activations'), or an EMPTY tensor where the
@@ -2388,6 +2456,10 @@ TORCH_LIBRARY(torch_sputnik, m) {
         "-> Tensor");
   m.def("half_linear_weight_gradient(int out_features, Tensor row_offsets, Tensor column_indices, "
         "Tensor grad, bool grad_is_planes, Tensor x, Tensor? plan) -> Tensor");
+  m.def("half_linear_weight_gradient_dense(int out_features, Tensor row_offsets, Tensor column_indices, "
+        "Tensor grad, bool grad_is_planes, Tensor x, Tensor? plan) -> (Tensor, Tensor)");
+  m.def("dense_weight_gradient(Tensor grad, bool grad_is_planes, Tensor x, bool x_is_planes, int x_layout, "
+        "int tile_type, int out_features, int in_features, int seq, int batch) -> Tensor");
   m.def("half_linear_input_gradient(int out_features, int in_features, Tensor grad, bool grad_is_planes, "
         "Tensor image, int values_type, Tensor like, int batch, int seq) -> Tensor");
   m.def(
@@ -2581,6 +2653,8 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("half_linear_forward", &half_linear_forward);
   m.impl("half_linear_plan", &half_linear_plan);
   m.impl("half_linear_weight_gradient", &half_linear_weight_gradient);
+  m.impl("half_linear_weight_gradient_dense", &half_linear_weight_gradient_dense);
+  m.impl("dense_weight_gradient", &dense_weight_gradient);
   m.impl("half_linear_input_gradient", &half_linear_input_gradient);
   m.impl("sddmm_sum", &sddmm_sum);
   m.impl("sddmm_sum_plan", &sddmm_sum_plan);

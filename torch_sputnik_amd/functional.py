@@ -600,20 +600,42 @@ class Sddmm(torch.autograd.Function):
         return None, None, None, None, None, grad_lhs, grad_rhs, None
 
 
+def _armed(sink):
+    """The layer a Function was handed as ``dense_grad_sink`` if it collects the dense weight
+    gradient NOW -- asked when the backward runs, so arming between forward and backward
+    counts -- else None."""
+    return sink if sink is not None and getattr(sink, "_collects_dense_grad", False) else None
+
+
+def _collect_dense_grad(sink, dense):
+    """Adds one backward's dense weight gradient [out, in] into ``sink.dense_grad`` the way
+    autograd fills ``.grad``: the first one is kept as the kernel wrote it, later ones are
+    added in place (micro-batches, a layer used twice in one graph)."""
+    with torch.no_grad():
+        if sink.dense_grad is None:
+            sink.dense_grad = dense
+        else:
+            sink.dense_grad.add_(dense)
+
+
 class SparseLinearFunction(torch.autograd.Function):
     """One sparse weight x a batch of dense matrices (left_spmm).  ``apply(m, k,
     values, row_indices, row_offsets, column_indices, dense[, split_rows[,
-    dense_blocks]])`` with dense [B,k,n] -> [B,m,n]; with ``split_rows = d`` the
+    dense_blocks[, dense_grad_sink]]])`` with dense [B,k,n] -> [B,m,n]; with ``split_rows = d`` the
     product comes back head split, [B * m/d, n, d] (every block of d output rows
     transposed, written by the kernel's store phase:
     modules/sparse_attention.py:38-45,108-126).  ``dense_blocks = d``: `dense` is
     given as [B * k/d, d, n] (the same memory: merged heads) and its gradient is
     handed back in that shape as the transposed view of a head-split buffer the
-    kernel wrote (see `Spmm`, ``transposed_grads``)."""
+    kernel wrote (see `Spmm`, ``transposed_grads``).  ``dense_grad_sink`` (the
+    ``SparseLinear``, or None): while it is armed the backward also adds the DENSE weight gradient
+    ``sum_b dy_b dense_b^T`` [m, k] into ``sink.dense_grad`` (ops.dense_weight_grad on the
+    normalised [B, m, n] / [B, k, n] forms: one tile launch, no layout copy)."""
 
     @staticmethod
     def forward(ctx, m, k, values, row_indices, row_offsets, column_indices, dense,
-                split_rows=0, dense_blocks=0):
+                split_rows=0, dense_blocks=0, dense_grad_sink=None):
+        ctx.dense_grad_sink = dense_grad_sink
         ctx.shape = (m, k)
         ctx.topology = (row_indices, row_offsets, column_indices)
         ctx.split_rows = int(split_rows)
@@ -633,6 +655,9 @@ class SparseLinearFunction(torch.autograd.Function):
         else:
             grad_output = _contiguous(grad_output)
         grad_values = grad_dense = None
+        sink = _armed(ctx.dense_grad_sink)
+        if sink is not None:
+            _collect_dense_grad(sink, ops.dense_weight_grad(grad_output, dense, "bis"))
         if ctx.needs_input_grad[2]:
             # the [B,nnz] products summed over B (what autograd makes of the
             # reference's result for the shared `values`), inside the call
@@ -648,14 +673,14 @@ class SparseLinearFunction(torch.autograd.Function):
                                               grad_output, left=True)
                 if dense.dim() == 2:
                     grad_dense = grad_dense[0]
-        return None, None, grad_values, None, None, None, grad_dense, None, None
+        return None, None, grad_values, None, None, None, grad_dense, None, None, None
 
 
 class HalfSparseLinearFunction(torch.autograd.Function):
     """``SparseLinear.forward`` for activations stored in float16 / bfloat16 (BASELINE
     config 5; the reference knows float32 only, src/left_replicated_spmm.cu:34-38):
-    ``apply(m, k, values, row_indices, row_offsets, column_indices, x)`` with x [B, S, in]
-    -> [B, out, S] float32.
+    ``apply(m, k, values, row_indices, row_offsets, column_indices, x[, dense_grad_sink])``
+    with x [B, S, in] -> [B, out, S] float32.
 
     At a layer's density and size all three products run on the matrix cores and read
     their operands as the caller has them -- NO layout pass (csrc/sparse_linear_half.hip):
@@ -663,10 +688,16 @@ class HalfSparseLinearFunction(torch.autograd.Function):
     x [B, S, in], dy [B, out, S]; float32 values and the float32 dy enter as half planes
     whose sum is the value (float16: over the tensor's range, 22 bits down to 2^-28 of its
     largest finite magnitude; inf / NaN stay non-finite).  Elsewhere the typed operators with the layout passes of
-    modules/sparse_linear.py:89 inside the Function (the half operand is what is kept)."""
+    modules/sparse_linear.py:89 inside the Function (the half operand is what is kept).
+
+    ``dense_grad_sink`` (the ``SparseLinear``, or None): while it is armed the backward also adds the dense
+    weight gradient into ``sink.dense_grad``.  On the tile route it is the weight gradient's
+    own launch that stores it (ops.half_linear_weight_gradient_dense: the tiles it samples,
+    stored whole); elsewhere one ops.dense_weight_grad launch on dy and the kept operand."""
 
     @staticmethod
-    def forward(ctx, m, k, values, row_indices, row_offsets, column_indices, x):
+    def forward(ctx, m, k, values, row_indices, row_offsets, column_indices, x, dense_grad_sink=None):
+        ctx.dense_grad_sink = dense_grad_sink
         ctx.shape = (m, k)
         ctx.topology = (row_indices, row_offsets, column_indices)
         ctx.in_dtype = x.dtype
@@ -694,18 +725,29 @@ class HalfSparseLinearFunction(torch.autograd.Function):
             # dy as planes, once for both gradients (float32 dy), or as it is (dy in x's type)
             planes = grad_output.dtype == torch.float32
             grad = ops.half_planes(grad_output, x.dtype) if planes else grad_output.to(x.dtype)
+            sink = _armed(ctx.dense_grad_sink)
             if ctx.needs_input_grad[2]:
                 plan = None if _plans is None else _plans.half_linear(m, k, row_offsets, column_indices)
-                grad_values = ops.half_linear_weight_gradient(m, row_offsets, column_indices, grad, planes,
-                                                              x, plan)
+                if sink is None:
+                    grad_values = ops.half_linear_weight_gradient(m, row_offsets, column_indices, grad,
+                                                                  planes, x, plan)
+                else:
+                    grad_values, dense_grad = ops.half_linear_weight_gradient_dense(
+                        m, row_offsets, column_indices, grad, planes, x, plan)
+                    _collect_dense_grad(sink, dense_grad)
+            elif sink is not None:   # (frozen values: nothing is sampled)
+                _collect_dense_grad(sink, ops.dense_weight_grad(grad_output, x, "bsi"))
             if ctx.needs_input_grad[6]:
                 grad_x = ops.half_linear_input_gradient(m, k, grad, planes, image, values.dtype, x, batch, seq)
                 if grad_x is None:   # (bfloat16 tiles with float32 values AND a float32 dy)
                     grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices, grad_output,
                                                   left=True)
                     grad_x = ops.transpose_last2(grad_dense, ctx.in_dtype)
-            return None, None, grad_values, None, None, None, grad_x
+            return None, None, grad_values, None, None, None, grad_x, None
         values, dense = ctx.saved_tensors
+        sink = _armed(ctx.dense_grad_sink)
+        if sink is not None:
+            _collect_dense_grad(sink, ops.dense_weight_grad(grad_output, dense, "bis"))
         if ctx.needs_input_grad[2]:
             grad_values = _sddmm(m, k, row_indices, row_offsets, column_indices, grad_output, dense,
                                  sum_replicas=True)
@@ -722,7 +764,7 @@ class HalfSparseLinearFunction(torch.autograd.Function):
                 grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices, grad_output,
                                               left=True)
             grad_x = ops.transpose_last2(grad_dense, ctx.in_dtype)
-        return None, None, grad_values, None, None, None, grad_x
+        return None, None, grad_values, None, None, None, grad_x, None
 
 
 class GroupProjectionFunction(torch.autograd.Function):

@@ -12,7 +12,8 @@ Differences: the attention mask is created on the device given (default: the
 current GPU) instead of a hard ``.cuda()``; ``differentiable_softmax=True``
 opts in to a softmax with a gradient.
 Additions: ``SparseLinear.from_dense`` builds a ready layer from a dense weight by
-magnitude, ``SparseLinear.update_topology`` is one drop-and-grow step (SET, RigL).
+magnitude, ``SparseLinear.update_topology`` is one drop-and-grow step (SET, RigL),
+``SparseLinear.collect_dense_grad`` / ``rigl_update`` gather RigL's grow scores in the backward.
 """
 import copy
 import math
@@ -35,6 +36,49 @@ class SparseLinear(nn.Module):
         self.output_features = output_features
         self.weight = nn.Parameter(torch.empty(output_features, input_features))
         self.bias = nn.Parameter(torch.empty(output_features))
+        # RigL's grow scores (collect_dense_grad): None, or the [out, in] float32 dense weight
+        # gradient summed over the backwards since it was cleared.  A plain attribute --
+        # neither a Parameter nor a buffer: not in state_dict, not moved by .to().
+        self.dense_grad = None
+        self._collects_dense_grad = False
+
+    def collect_dense_grad(self, enabled=True):
+        """Arms (or disarms) the collection of the DENSE weight gradient: while armed, every
+        backward through ``forward`` / ``project`` adds ``sum_b dy_b x_b`` -- ``[out, in]``
+        float32, at the masked-out positions too -- into ``self.dense_grad``, as autograd
+        adds into ``.grad``: the first backward keeps the kernel's tensor, later ones
+        ``add_`` into it, so micro-batches and a layer used twice in one graph sum up.
+        With half activations on the tile route the weight gradient's own launch stores it
+        (its float32 tiles, whole: ``ops.half_linear_weight_gradient_dense``); otherwise one
+        more tile launch (``ops.dense_weight_grad``).  The flag is looked at when the backward
+        runs, so arming between forward and backward counts.  A disarmed layer launches what
+        it always did.  Returns ``self``.
+
+        Not collected: layers reached through ``SparseAttention``'s grouped self-attention
+        projection (``GroupProjectionFunction``) or its ``half_storage`` projections
+        (``functional.half_linear_rows``) -- their ``dense_grad`` stays None -- and armed
+        layers inside ``graphs.capture_training_step`` (the attribute is rebound by Python
+        code that a replay does not run)."""
+        self._collects_dense_grad = bool(enabled)
+        return self
+
+    def zero_dense_grad(self):
+        """Drops what ``collect_dense_grad`` gathered (``dense_grad = None``); stays armed."""
+        self.dense_grad = None
+
+    @torch.no_grad()
+    def rigl_update(self, drop_fraction, per_row=False):
+        """One RigL step from the collected gradient: ``update_topology(drop_fraction,
+        grow_scores=self.dense_grad, per_row=per_row)`` -- drop by ``|values|``, grow where
+        ``|dense_grad|`` is largest -- then ``dense_grad`` is cleared; the layer stays armed.
+        Returns ``source`` as ``update_topology`` does.  RuntimeError if nothing was collected
+        (not armed, no backward since the last clear, or a route that does not collect)."""
+        if self.dense_grad is None:
+            raise RuntimeError("rigl_update: no dense gradient collected -- call collect_dense_grad() "
+                               "before the backward pass")
+        source = self.update_topology(drop_fraction, grow_scores=self.dense_grad, per_row=per_row)
+        self.dense_grad = None
+        return source
 
     def setup_sparse_tensors(self):
         values, row_indices, row_offsets, column_indices = dense_to_sparse(self.weight)
@@ -113,8 +157,10 @@ class SparseLinear(nn.Module):
         even a full row could drop an entry (``floor(in_features * drop_fraction) == 0``)
         nothing changes.
 
-        Out of scope: the dense weight gradient itself -- pass e.g.
-        ``dy.flatten(0, 1).T @ x.flatten(0, 1)``."""
+        The dense weight gradient for RigL's ``grow_scores`` comes from the layer itself:
+        ``collect_dense_grad()`` before the backward pass leaves it in ``dense_grad``, and
+        ``rigl_update`` is this call on it; ``ops.dense_weight_grad(dy, x)`` computes it from
+        operands of your own."""
         if per_row:
             return self._update_topology_per_row(drop_fraction, grow_scores, generator)
         values = self.values.detach()
@@ -207,7 +253,7 @@ class SparseLinear(nn.Module):
             if torch.is_grad_enabled() and (x.requires_grad or self.values.requires_grad):
                 return HalfSparseLinearFunction.apply(
                     self.output_features, self.input_features, self.values, self.row_indices,
-                    self.row_offsets, self.column_indices, x)
+                    self.row_offsets, self.column_indices, x, self)
             values = self.values.detach()
             if x.is_cuda and ops.half_linear_supported(self.output_features, self.input_features, x.size(1),
                                                        x.size(0), self.column_indices.numel(), values.dtype,
@@ -239,7 +285,8 @@ class SparseLinear(nn.Module):
                                       self.column_indices, dense, split_rows)
         return SparseLinearFunction.apply(
             self.output_features, self.input_features, self.values, self.row_indices,
-            self.row_offsets, self.column_indices, dense, split_rows, dense_blocks)
+            self.row_offsets, self.column_indices, dense, split_rows, dense_blocks,
+            self)
 
 
 def get_clones(module, num_of_deep_copies):

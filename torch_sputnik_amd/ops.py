@@ -4,7 +4,9 @@ backed by ``torch.ops.torch_sputnik.*`` (HIP kernels for gfx950), followed by
 the extensions whose call sites exist only in the reference's tests
 (``spmm_bias``, the ``*_many_mask`` family) or not at all (softmax gradient).
 
-GPU only: a CPU tensor raises from the dispatcher; there is no fallback.
+GPU only: a CPU tensor raises from the dispatcher; there is no fallback.  (One documented
+exception: ``dense_weight_grad``, which the module flow calls on layers of any size, computes
+what its kernel does not serve with ``torch.einsum``.)
 """
 import torch
 
@@ -97,6 +99,75 @@ def half_linear_weight_gradient(out_features, row_offsets, column_indices, grad,
     dy [batch, out, seq] in x's type, or the planes of the float32 dy (`half_planes`)."""
     return _ops.half_linear_weight_gradient(int(out_features), row_offsets, column_indices, grad,
                                             bool(grad_is_planes), x, plan)
+
+
+def half_linear_weight_gradient_dense(out_features, row_offsets, column_indices, grad, grad_is_planes, x,
+                                      plan=None):
+    """``half_linear_weight_gradient`` and, from the same launch, the DENSE weight gradient:
+    -> ``(grad_values [nnz], dense [out, in])``, both float32.  The kernel has every float32
+    tile of ``sum_b dy_b x_b`` in LDS to sample it at the mask; here it stores the tile as
+    well, so ``grad_values`` equals ``dense[rows, columns]`` bit for bit.  One workgroup per
+    tile (no splits, no scratch)."""
+    return _ops.half_linear_weight_gradient_dense(int(out_features), row_offsets, column_indices, grad,
+                                                  bool(grad_is_planes), x, plan)
+
+
+_X_LAYOUTS = {"bsi": 0, "bis": 1}
+
+
+def dense_weight_grad_supported(out_features, in_features, seq, batch, grad_dtype, x_dtype, x_layout,
+                                tile_dtype):
+    """Whether ``dense_weight_grad`` runs these sizes and operand types on the matrix cores
+    (host only: sputnik_hip_sparse_linear_dense_weight_gradient_supported)."""
+    from . import capi
+    try:
+        gt, xt, tt = _half_code(grad_dtype), _half_code(x_dtype), _half_code(tile_dtype)
+    except KeyError:
+        return False
+    return bool(capi.lib().sputnik_hip_sparse_linear_dense_weight_gradient_supported(
+        int(out_features), int(in_features), int(seq), int(batch), gt, xt, _X_LAYOUTS[x_layout], tt))
+
+
+def dense_weight_grad(grad_output, x, x_layout="bsi"):
+    """The dense weight gradient of a linear layer, ``[out, in]`` float32 =
+    ``sum_b sum_s dy[b, o, s] x[b, s, i]`` -- RigL's grow scores -- from the operands as a
+    layer has them: ``grad_output`` [B, out, S] and ``x`` [B, S, in] (``x_layout="bsi"``) or
+    [B, in, S] (``"bis"``, the k-major operand of ``SparseLinear.project``); 2-D operands
+    count as B = 1.  No transposed copy and no per-batch partial products: one tile launch on
+    the matrix cores, float32 accumulation.  Operands are float16, bfloat16 or float32; a
+    float32 operand is split into half planes whose sum is the value (``half_planes``), the
+    tile type is the half operand's, float16 for two float32 operands.  No host
+    synchronisation.
+
+    Calls the kernel does not serve -- CPU tensors, two different half types, other dtypes,
+    ``S % 64 != 0``, ``in % 8 != 0``, bfloat16 against two float32 planes... -- are computed
+    by ``torch.einsum`` on float32 copies (same shape and dtype of the result)."""
+    if x_layout not in _X_LAYOUTS:
+        raise ValueError(f"dense_weight_grad: x_layout should be 'bsi' or 'bis', got {x_layout!r}")
+    if grad_output.dim() == 2:
+        grad_output = grad_output.unsqueeze(0)
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+    if grad_output.dim() != 3 or x.dim() != 3:
+        raise ValueError("dense_weight_grad: expected [B, out, S] and [B, S, in] / [B, in, S] operands")
+    batch, out_f, seq = grad_output.shape
+    in_f = x.size(2) if x_layout == "bsi" else x.size(1)
+    if x.size(0) != batch or (x.size(1) if x_layout == "bsi" else x.size(2)) != seq:
+        raise ValueError(f"dense_weight_grad: operands {tuple(grad_output.shape)} and {tuple(x.shape)} "
+                         f"do not match in layout {x_layout!r}")
+    halves = {t.dtype for t in (grad_output, x)} - {torch.float32}
+    tile = next(iter(halves)) if len(halves) == 1 else torch.float16
+    if len(halves) <= 1 and grad_output.is_cuda and x.is_cuda and grad_output.device == x.device and \
+            dense_weight_grad_supported(out_f, in_f, seq, batch, grad_output.dtype, x.dtype, x_layout, tile):
+        grad_output, x = grad_output.detach().contiguous(), x.detach().contiguous()
+        g_planes, x_planes = grad_output.dtype == torch.float32, x.dtype == torch.float32
+        if (grad_output.data_ptr() | x.data_ptr()) % 16 == 0:
+            return _ops.dense_weight_gradient(
+                half_planes(grad_output, tile) if g_planes else grad_output, g_planes,
+                half_planes(x, tile) if x_planes else x, x_planes, _X_LAYOUTS[x_layout], _half_code(tile),
+                out_f, in_f, seq, batch)
+    return torch.einsum("bos,bsi->oi" if x_layout == "bsi" else "bos,bis->oi",
+                        grad_output.detach().float(), x.detach().float())
 
 
 def half_linear_input_gradient(out_features, in_features, grad, grad_is_planes, image, values_dtype,
