@@ -1519,6 +1519,86 @@ SPUTNIK_HIP_API int sputnik_hip_csr_regrow_launch_shape(int m, int n, int score_
                              int* rows_per_workgroup, int* value_digit_passes,
                              int* score_digit_passes, int* lds_bytes, int* max_n, int* grid);
 
+/* ------------------------------------------------------------------------
+ * Top-k over the entries of a CSR pattern, written out as a smaller CSR pattern
+ * (topology.prune_csr, SparseLinear.prune_to): gradual magnitude pruning of a layer that has
+ * no dense weight any more.
+ *
+ * Inputs (device): the pattern of an m x n matrix -- row_offsets [m + 1], column_indices
+ * [nonzeros], ascending inside a row, int32 -- and values [nonzeros] of `value_bytes` = 2 or 4.
+ * KEYS are those of sputnik_hip_topk_to_csr: the bit pattern without the sign.  Among equal
+ * keys the lower entry index wins (the lower column inside a row, the lower flat index across
+ * rows).
+ *   total_mode = 1   the `count` (0 <= count <= nonzeros) entries of largest key are kept
+ *   total_mode = 0   row r of len_r entries keeps its min(len_r, count) entries of largest key
+ *                    (0 <= count <= n)
+ * Outputs (device): out_row_offsets [m + 1]; out_row_indices [m] (the rows by ascending new
+ * length, ties by row); and for every kept entry, in the order of the old arrays:
+ * out_column_indices, out_values (the old value bit for bit) and out_source (int64: its index in
+ * the old arrays; it ascends).  The three hold `out_capacity` entries; a slot at or beyond it
+ * is not written.  n enters the argument check alone.
+ *
+ * Total mode: the new size is `count`, known up front (out_capacity >= count): one call that
+ * never synchronises and can be captured in a graph.  Launches: a clear launch for the 256-bin
+ * histograms in `workspace` (a kernel: every replay of a captured call clears them), one
+ * histogram launch per digit over the FLAT values array (16-byte loads, LDS histogram, integer
+ * atomic adds into the global bins), a rows launch that counts the entries above and at the
+ * threshold, a scan launch (offsets, the rows' shares of the tie quota), the fill, the row order.
+ * Per-row mode: the new size sum min(len_r, count) is on the device.  A caller that has room
+ * for `nonzeros` entries makes one call.  A caller that wants the size first makes two, as
+ * with sputnik_hip_dense_to_csr_count / _fill:
+ *   out_column_indices == NULL   out_row_offsets (one scan launch) and out_row_indices only;
+ *                                out_row_offsets[m] is the size
+ *   out_row_indices == NULL      the fill alone, under the out_row_offsets the former call wrote
+ * The fill is ONE launch: the group of lanes that walks a row's entries selects the row's
+ * threshold (histogram in LDS) and places the kept entries by wave ballot.
+ * A row's entries are walked in 16-byte pieces by a group of 64 / rows_per_wave lanes
+ * (sputnik_hip_csr_topk_launch_shape: from the mean row length nonzeros / m); a longer row
+ * takes more steps, any length is served.  Every count is an integer and every store a vector
+ * store to a slot one lane owns: two calls give equal arrays.  `workspace`:
+ * sputnik_hip_csr_topk_workspace_bytes(...) bytes (0 per row: it may be NULL), 4-byte aligned,
+ * the call's own until its launches have run.
+ * m = 0, nonzeros = 0 and count = 0 write the zero offsets and the row order and nothing else.
+ * Offsets that do not ascend inside 0 .. nonzeros are a caller error with an unspecified result,
+ * but nothing outside the arrays is read or written.
+ *
+ * SPUTNIK_HIP_INVALID_ARGUMENT: a value width other than 2 / 4, a negative size, a count out of
+ * range, m above the rows sputnik_hip_csr_row_order serves (16384), out_capacity below count
+ * (total mode), a missing or misaligned pointer, a workspace too small.
+ * ---------------------------------------------------------------------- */
+SPUTNIK_HIP_API int sputnik_hip_csr_topk(int m, int n, int nonzeros, const int* row_offsets,
+                             const int* column_indices, const void* values, int value_bytes,
+                             int total_mode, int64_t count, void* workspace, size_t workspace_bytes,
+                             int* out_row_indices, int* out_row_offsets, int* out_column_indices,
+                             void* out_values, int64_t* out_source, int64_t out_capacity,
+                             sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API size_t sputnik_hip_csr_topk_workspace_bytes(int m, int n, int nonzeros, int total_mode);
+
+/* The instance sputnik_hip_csr_topk runs for a call of this shape; the entry takes its
+ * decisions from the same function this reports, and from nothing else.
+ *   served               1, or 0 for m above 16384 (the row-order limit; every other field is
+ *                        -1 then)
+ *   elements_per_lane    values of one 16-byte load: 16 / value_bytes
+ *   rows_per_wave        16 / 8 / 4 / 2 / 1: the most whose group of lanes covers a row of the
+ *                        mean length nonzeros / m (integer division; 0 for m = 0) in one step
+ *   group_lanes          64 / rows_per_wave; one step covers group_lanes * elements_per_lane
+ *                        entries
+ *   rows_per_workgroup   4 waves: 4 * rows_per_wave
+ *   digit_passes         8-bit digits of a key: the value bytes
+ *   rows_grid            ceil(m / rows_per_workgroup) workgroups of 256 threads: every launch
+ *                        that walks rows
+ *   flat_grid            total mode: workgroups of a digit pass over the flat values array,
+ *                        ceil((nonzeros / elements_per_lane + 2) / (8 * 256)); 0 per row and
+ *                        for nonzeros = 0
+ * Host only, launches nothing; any output pointer may be NULL.  Returns
+ * SPUTNIK_HIP_INVALID_ARGUMENT for a negative size, a value width other than 2 / 4 and a
+ * total_mode other than 0 / 1. */
+SPUTNIK_HIP_API int sputnik_hip_csr_topk_launch_shape(int m, int n, int nonzeros, int value_bytes,
+                             int total_mode, int* served, int* rows_per_wave, int* group_lanes,
+                             int* elements_per_lane, int* rows_per_workgroup, int* digit_passes,
+                             int* rows_grid, int* flat_grid);
+
 /*
  * out[r][i] = in[r][permutation[i]], i < n, for `rows` value arrays (strides in
  * elements) that share one permutation: the values of a static pattern in the

@@ -112,6 +112,10 @@ SIGNATURES = {
                                         ctypes.c_uint, _c_ptr, _c_size] + [_c_ptr] * 4),
     "sputnik_hip_csr_regrow_workspace_bytes": (_c_size, [_c_int] * 3),
     "sputnik_hip_csr_regrow_launch_shape": (_c_int, [_c_int] * 4 + [_c_ptr] * 9),
+    "sputnik_hip_csr_topk": (_c_int, [_c_int] * 3 + [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_int, _c_i64, _c_ptr, _c_size]
+                             + [_c_ptr] * 5 + [_c_i64, _c_ptr]),
+    "sputnik_hip_csr_topk_workspace_bytes": (_c_size, [_c_int] * 4),
+    "sputnik_hip_csr_topk_launch_shape": (_c_int, [_c_int] * 5 + [_c_ptr] * 8),
     "sputnik_hip_csr_transpose_checked": (_c_int, [_c_int] * 4 + [_c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_size, _c_ptr]),
@@ -560,6 +564,24 @@ def csr_regrow_launch_shape(m, n, score_bytes, value_bytes):
     _check(lib().sputnik_hip_csr_regrow_launch_shape(
         m, n, score_bytes, value_bytes, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
         "sputnik_hip_csr_regrow_launch_shape")
+    shape = {name: o.value for name, o in zip(names, outs)}
+    shape["served"] = bool(shape["served"])
+    return shape
+
+
+def csr_topk_launch_shape(m, n, nonzeros, value_bytes, total):
+    """The instance of the top-k over the entries of an m x n CSR pattern of `nonzeros` values of
+    that width (2 or 4 bytes), ``total`` mode or per row: a dict of served (bool: m within the
+    row-order kernel's rows; the other fields are -1 where it is not), rows_per_wave,
+    group_lanes, elements_per_lane, rows_per_workgroup, digit_passes, rows_grid and flat_grid
+    (include/sputnik_hip.h).  The group width follows the mean row length ``nonzeros // m``.
+    Host only; raises for sizes the entry rejects."""
+    names = ("served", "rows_per_wave", "group_lanes", "elements_per_lane", "rows_per_workgroup",
+             "digit_passes", "rows_grid", "flat_grid")
+    outs = [_c_int(-1) for _ in names]
+    _check(lib().sputnik_hip_csr_topk_launch_shape(
+        m, n, nonzeros, value_bytes, int(bool(total)), *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
+        "sputnik_hip_csr_topk_launch_shape")
     shape = {name: o.value for name, o in zip(names, outs)}
     shape["served"] = bool(shape["served"])
     return shape

@@ -1,5 +1,6 @@
 // CSR topologies from dense masks / matrices, built on the device for gfx950
-// (include/sputnik_hip.h: sputnik_hip_dense_to_csr_*, sputnik_hip_csr_row_order).
+// (include/sputnik_hip.h: sputnik_hip_dense_to_csr_*, sputnik_hip_csr_row_order), and the
+// selections that write one out: sputnik_hip_topk_to_csr, sputnik_hip_csr_regrow, sputnik_hip_csr_topk.
 //
 // Replaces the torch loop of topology.dense_to_sparse_3d (per mask: != 0, to_sparse_csr, two
 // casts, a stable argsort and a host read of the count) by a fixed number of launches for any
@@ -366,6 +367,7 @@ struct RowWalk {
   bool live;
   int n, lead, steps, group_lanes, group_lane;
 
+  __device__ __forceinline__ RowWalk() {}   // (entry_walk: the entries of a CSR row)
   __device__ __forceinline__ RowWalk(const U* dense, int64_t row, int64_t row_stride, int m, int n_,
                                      int rows_per_wave) {
     const int lane = threadIdx.x % kWave;
@@ -1005,6 +1007,381 @@ int launch_regrow(const RegrowShape& r, int m, int n, int nonzeros, const int* r
   return launch_status();
 }
 
+// ---------------------------------------------------------------------------
+// Top-k over the entries of a CSR pattern, written out as a smaller CSR pattern
+// (sputnik_hip_csr_topk): gradual magnitude pruning of a layer that has no dense weight any
+// more.  The keys and the pair (T, q) are those of the dense top-k above; what is ranked are
+// the nnz stored values, and a kept entry keeps its column, its value bits and its old index.
+// The kept set is the old pattern filtered, so its columns are in order already.
+//   per row   the new lengths min(len_r, k) follow from the offsets alone: one scan launch; then
+//             ONE launch in which the group of lanes that walks a row's entries selects
+//             (T_r, q_r) (histogram in LDS) and fills the row's new slots
+//   total     one launch per digit over the FLAT values array (entries, not rows), a rows
+//             launch for g_r and t_r, the scan launch of the dense top-k, the fill
+// A row's entries are walked like a dense row: values + row_offsets[r] is the row start, the
+// 16-byte pieces are laid out from that address rounded down to 16 bytes.  The group width
+// comes from the mean row length nnz / m; a longer row takes more steps.
+// ---------------------------------------------------------------------------
+constexpr int kFlatSteps = 8;   // 16-byte pieces per lane of a workgroup of the flat walk
+
+struct CsrTopkShape {
+  int status = 0;
+  int served = 0;
+  int rows_per_wave = -1, group_lanes = -1, elements_per_lane = -1, rows_per_workgroup = -1;
+  int digit_passes = -1, rows_grid = -1, flat_grid = -1;
+};
+inline CsrTopkShape csr_topk_shape(int m, int nonzeros, int value_bytes, int total_mode) {
+  CsrTopkShape s;
+  if (m < 0 || nonzeros < 0 || (value_bytes != 2 && value_bytes != 4) || (total_mode != 0 && total_mode != 1)) {
+    s.status = SPUTNIK_HIP_INVALID_ARGUMENT;
+    return s;
+  }
+  if (!order_route(1, m, 0).served) return s;   // (rows of unequal lengths in both modes)
+  s.served = 1;
+  s.elements_per_lane = kLoadBytes / value_bytes;
+  const int mean = m > 0 ? nonzeros / m : 0;
+  // the most rows per wave whose group of lanes still covers a row of mean length in one step
+  s.rows_per_wave = kMaxRowsPerWave;
+  while (s.rows_per_wave > 1 && mean > (kWave / s.rows_per_wave) * s.elements_per_lane) s.rows_per_wave /= 2;
+  s.group_lanes = kWave / s.rows_per_wave;
+  s.rows_per_workgroup = kBuildWaves * s.rows_per_wave;
+  s.digit_passes = value_bytes * 8 / kDigitBits;
+  s.rows_grid = static_cast<int>(ceil_div64(m, s.rows_per_workgroup));
+  // pieces of the flat walk: at most V - 1 elements of lead in front of the array
+  const int64_t pieces = static_cast<int64_t>(nonzeros) / s.elements_per_lane + 2;
+  s.flat_grid = total_mode && nonzeros > 0 ? static_cast<int>(ceil_div64(pieces, int64_t{kBuildBlock} * kFlatSteps)) : 0;
+  return s;
+}
+
+// The 16-byte piece whose first element is src[c0], of an array of n elements: one wide load
+// where it lies inside the array, else element by element, inside the array only.
+template <typename U>
+__device__ __forceinline__ Piece<U> load_piece(const U* __restrict__ src, int64_t c0, int64_t n, unsigned* valid) {
+  constexpr int V = kLoadBytes / sizeof(U);
+  Piece<U> v;
+  if (c0 >= 0 && c0 + V <= n) {
+    v = *reinterpret_cast<const Piece<U>*>(src + c0);
+    *valid = (1u << V) - 1u;
+  } else {
+    unsigned in = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const bool inside = c0 + e >= 0 && c0 + e < n;
+      v.e[e] = inside ? src[c0 + e] : U{0};
+      in |= (inside ? 1u : 0u) << e;
+    }
+    *valid = in;
+  }
+  return v;
+}
+
+// The slots [begin, end) of a row's entries, inside [0, nonzeros) whatever the offsets say.
+__device__ __forceinline__ void row_slots(const int* __restrict__ row_offsets, int64_t row, bool live, int nonzeros,
+                                          int* begin, int* end) {
+  *begin = 0;
+  *end = 0;
+  if (live) {
+    *begin = min(max(row_offsets[row], 0), nonzeros);
+    *end = min(max(row_offsets[row + 1], *begin), nonzeros);
+  }
+}
+
+// The walk of one group of lanes over the entries [begin, end) of its row; every lane of the
+// wave takes as many steps as the wave's longest row needs (the fill's ballots are the wave's).
+template <typename U>
+__device__ __forceinline__ RowWalk<U> entry_walk(const U* __restrict__ values, int begin, int end, bool live,
+                                                 int rows_per_wave) {
+  constexpr int V = kLoadBytes / sizeof(U);
+  RowWalk<U> w;
+  w.n = end - begin;
+  w.group_lanes = kWave / rows_per_wave;
+  w.group_lane = (threadIdx.x % kWave) % w.group_lanes;
+  w.live = live;
+  w.src = values + begin;
+  w.lead = static_cast<int>((reinterpret_cast<uintptr_t>(w.src) % kLoadBytes) / sizeof(U));
+  const int64_t span = static_cast<int64_t>(w.group_lanes) * V;
+  int steps = static_cast<int>((static_cast<int64_t>(w.n) + w.lead + span - 1) / span);
+  for (int o = kWave / 2; o > 0; o >>= 1) steps = max(steps, __shfl_xor(steps, o, kWave));
+  w.steps = steps;
+  return w;
+}
+
+// The entries of the walk's row with key > threshold, and the first `quota` with key ==
+// threshold, into the slots [out, end) in entry order: column, value bits and old index.
+template <typename U>
+__device__ __forceinline__ void csr_fill_row(const RowWalk<U>& walk, int begin, unsigned threshold, int quota,
+                                             int64_t out, int64_t end, unsigned long long group_mask,
+                                             unsigned long long below, const int* __restrict__ column_indices,
+                                             int* __restrict__ out_columns, U* __restrict__ out_values,
+                                             int64_t* __restrict__ out_source) {
+  constexpr int V = RowWalk<U>::V;
+  int ties_seen = 0;   // entries equal to the threshold in the steps behind
+  for (int s = 0; s < walk.steps; ++s) {
+    int64_t c0;
+    unsigned valid;
+    const Piece<U> v = walk.load(s, &c0, &valid);
+    unsigned greater = 0, equal = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned key = key_of(v.e[e]);
+      greater |= (key > threshold ? 1u : 0u) << e;
+      equal |= (key == threshold ? 1u : 0u) << e;
+    }
+    greater &= valid;
+    equal &= valid;
+    // entry order: lane after lane, element after element inside a lane
+    int ties_before = 0, ties_step = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned long long b = __ballot((equal >> e) & 1u);
+      ties_before += __popcll(b & below);
+      ties_step += __popcll(b & group_mask);
+    }
+    unsigned flags = greater;
+    int rank = ties_seen + ties_before;
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      if ((equal >> e) & 1u) {
+        if (rank < quota) flags |= 1u << e;
+        ++rank;
+      }
+    ties_seen += ties_step;
+    int before = 0, total = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned long long b = __ballot((flags >> e) & 1u);
+      before += __popcll(b & below);
+      total += __popcll(b & group_mask);
+    }
+    int64_t p = out + before;
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      if (((flags >> e) & 1u) && p < end) {
+        const int64_t from = begin + c0 + e;   // (a valid element: inside the row's slots)
+        out_columns[p] = column_indices[from];
+        out_values[p] = v.e[e];
+        out_source[p] = from;
+        ++p;
+      }
+    out += total;
+  }
+}
+
+// The new slots of a row, inside [0, capacity) whatever the offsets say.
+__device__ __forceinline__ void new_slots(const int* __restrict__ out_offsets, int64_t row, bool live,
+                                          int64_t capacity, int64_t* out, int64_t* end) {
+  *out = live ? max(out_offsets[row], 0) : 0;
+  *end = live ? min(static_cast<int64_t>(out_offsets[row + 1]), capacity) : 0;
+}
+
+// Per-row mode, one workgroup: out_offsets = the scan of min(len_r, k).
+__global__ __launch_bounds__(kScanBlock) void csr_topk_lengths_kernel(int m, int nonzeros, int k,
+                                                                      const int* __restrict__ row_offsets,
+                                                                      int* __restrict__ out_offsets) {
+  __shared__ int wave_sums[kScanBlock / kWave];
+  const int t = threadIdx.x;
+  const int64_t per = (static_cast<int64_t>(m) + kScanBlock - 1) / kScanBlock;
+  const int64_t i0 = min(static_cast<int64_t>(m), t * per), i1 = min(static_cast<int64_t>(m), i0 + per);
+  int mine = 0;
+  for (int64_t i = i0; i < i1; ++i) {
+    int begin, end;
+    row_slots(row_offsets, i, true, nonzeros, &begin, &end);
+    mine += min(end - begin, k);
+  }
+  int total;
+  int running = block_exclusive_scan(mine, wave_sums, &total);
+  for (int64_t i = i0; i < i1; ++i) {
+    int begin, end;
+    row_slots(row_offsets, i, true, nonzeros, &begin, &end);
+    running += min(end - begin, k);
+    out_offsets[1 + i] = running;
+  }
+  if (t == 0) out_offsets[0] = 0;
+}
+
+// Per-row mode: select and fill of every row in one launch.
+template <typename U>
+__global__ __launch_bounds__(kBuildBlock) void csr_topk_rows_kernel(
+    int m, int nonzeros, int rows_per_wave, int k, const int* __restrict__ row_offsets,
+    const int* __restrict__ column_indices, const U* __restrict__ values, const int* __restrict__ out_offsets,
+    int64_t capacity, int* __restrict__ out_columns, U* __restrict__ out_values, int64_t* __restrict__ out_source) {
+  constexpr int P = sizeof(U) * 8 / kDigitBits;
+  __shared__ unsigned hist[kBuildWaves * kMaxRowsPerWave][kDigitBins];   // 64 KiB
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int group_lanes = kWave / rows_per_wave;
+  const int group = lane / group_lanes, group_lane = lane % group_lanes;
+  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
+  const bool live = row < m;
+  const unsigned long long group_mask =
+      (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
+  const unsigned long long below = group_mask & ((1ull << lane) - 1ull);
+  int begin, end;
+  row_slots(row_offsets, row, live, nonzeros, &begin, &end);
+  const RowWalk<U> walk = entry_walk(values, begin, end, live, rows_per_wave);
+  unsigned* __restrict__ bins = hist[wave * rows_per_wave + group];
+  const int chunk = kDigitBins / group_lanes;
+  const int base = group_lane * chunk;
+
+  const int keep = min(end - begin, k);
+  unsigned prefix = 0;
+  int need = keep;
+  for (int p = 0; p < P; ++p) {
+    const int shift = kDigitBits * (P - 1 - p);
+    for (int j = 0; j < chunk; ++j) bins[base + j] = 0u;
+    __syncthreads();
+    digit_histogram(walk, shift, prefix, bins);
+    __syncthreads();
+    prefix = (prefix << kDigitBits) | pick_digit(bins, base, chunk, group_lane, group_lanes, group_mask, &need);
+    __syncthreads();   // (the bins are cleared again)
+  }
+  const unsigned threshold = keep > 0 ? prefix : kNoThreshold;
+  int64_t out, out_end;
+  new_slots(out_offsets, row, live, capacity, &out, &out_end);
+  csr_fill_row(walk, begin, threshold, need, out, out_end, group_mask, below, column_indices, out_columns,
+               out_values, out_source);
+}
+
+// Total mode: the global bins of every digit pass start at zero.
+static_assert(kMaxDigitPasses * kDigitBins == kScanBlock, "one thread per bin");
+__global__ __launch_bounds__(kScanBlock) void csr_topk_clear_kernel(unsigned* __restrict__ bins) {
+  bins[threadIdx.x] = 0u;
+}
+
+// Total mode, one digit pass over the flat values array: this workgroup's kFlatSteps * 256
+// pieces into an LDS histogram, that into bins[pass][*] with one integer atomic add per
+// non-empty bin.
+template <typename U>
+__global__ __launch_bounds__(kBuildBlock) void csr_topk_flat_hist_kernel(int nonzeros, int pass, unsigned count,
+                                                                         const U* __restrict__ values,
+                                                                         unsigned* bins) {
+  constexpr int V = kLoadBytes / sizeof(U), P = sizeof(U) * 8 / kDigitBits;
+  __shared__ unsigned hist[kDigitBins];
+  __shared__ unsigned select[kSelectWords];
+  unsigned need;
+  const unsigned prefix = total_select(bins, pass, count, select, &need);
+  hist[threadIdx.x] = 0u;
+  __syncthreads();
+  const int shift = kDigitBits * (P - 1 - pass);
+  const int lead = static_cast<int>((reinterpret_cast<uintptr_t>(values) % kLoadBytes) / sizeof(U));
+  for (int s = 0; s < kFlatSteps; ++s) {
+    const int64_t piece = (static_cast<int64_t>(blockIdx.x) * kFlatSteps + s) * kBuildBlock + threadIdx.x;
+    unsigned valid;
+    const Piece<U> v = load_piece(values, piece * V - lead, static_cast<int64_t>(nonzeros), &valid);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned key = key_of(v.e[e]);
+      if (((valid >> e) & 1u) && static_cast<unsigned>(static_cast<uint64_t>(key) >> (shift + kDigitBits)) == prefix)
+        atomicAdd(&hist[(key >> shift) & (kDigitBins - 1)], 1u);
+    }
+  }
+  __syncthreads();
+  const unsigned c = hist[threadIdx.x];
+  if (c != 0u) atomicAdd(&bins[pass * kDigitBins + threadIdx.x], c);
+}
+
+// Total mode: out_offsets[row + 1] = #(key > T), ties[row] = #(key == T) of the row's entries.
+template <typename U>
+__global__ __launch_bounds__(kBuildBlock) void csr_topk_total_rows_kernel(
+    int m, int nonzeros, int rows_per_wave, unsigned count, const int* __restrict__ row_offsets,
+    const U* __restrict__ values, const unsigned* __restrict__ bins, int* __restrict__ out_offsets,
+    int* __restrict__ ties) {
+  constexpr int V = RowWalk<U>::V, P = sizeof(U) * 8 / kDigitBits;
+  __shared__ unsigned select[kSelectWords];
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int group_lanes = kWave / rows_per_wave;
+  const int group = lane / group_lanes, group_lane = lane % group_lanes;
+  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
+  const bool live = row < m;
+  unsigned need;
+  const unsigned prefix = total_select(bins, P, count, select, &need);
+  const unsigned threshold = count > 0 ? prefix : kNoThreshold;
+  int begin, end;
+  row_slots(row_offsets, row, live, nonzeros, &begin, &end);
+  const RowWalk<U> walk = entry_walk(values, begin, end, live, rows_per_wave);
+  int greater = 0, equal = 0;
+  for (int s = 0; s < walk.steps; ++s) {
+    int64_t c0;
+    unsigned valid;
+    const Piece<U> v = walk.load(s, &c0, &valid);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const unsigned key = key_of(v.e[e]);
+      const bool in = (valid >> e) & 1u;
+      greater += in && key > threshold ? 1 : 0;
+      equal += in && key == threshold ? 1 : 0;
+    }
+  }
+  for (int o = group_lanes / 2; o > 0; o >>= 1) {
+    greater += __shfl_xor(greater, o, kWave);
+    equal += __shfl_xor(equal, o, kWave);
+  }
+  if (live && group_lane == 0) {
+    out_offsets[row + 1] = greater;
+    ties[row] = equal;
+  }
+}
+
+// Total mode: the fill of every row under the one threshold and the rows' quotas.
+template <typename U>
+__global__ __launch_bounds__(kBuildBlock) void csr_topk_total_fill_kernel(
+    int m, int nonzeros, int rows_per_wave, const int* __restrict__ row_offsets,
+    const int* __restrict__ column_indices, const U* __restrict__ values, const unsigned* __restrict__ threshold,
+    const int* __restrict__ quotas, const int* __restrict__ out_offsets, int64_t capacity,
+    int* __restrict__ out_columns, U* __restrict__ out_values, int64_t* __restrict__ out_source) {
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int group_lanes = kWave / rows_per_wave;
+  const int group = lane / group_lanes;
+  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
+  const bool live = row < m;
+  const unsigned long long group_mask =
+      (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
+  const unsigned long long below = group_mask & ((1ull << lane) - 1ull);
+  int begin, end;
+  row_slots(row_offsets, row, live, nonzeros, &begin, &end);
+  const RowWalk<U> walk = entry_walk(values, begin, end, live, rows_per_wave);
+  int64_t out, out_end;
+  new_slots(out_offsets, row, live, capacity, &out, &out_end);
+  csr_fill_row(walk, begin, *threshold, live ? quotas[row] : 0, out, out_end, group_mask, below, column_indices,
+               out_columns, out_values, out_source);
+}
+
+// `fill`: the output arrays are there.  Per-row mode with `offsets`: the scan launch first.
+template <typename U>
+int launch_csr_topk(const CsrTopkShape& s, int m, int nonzeros, const int* row_offsets, const int* column_indices,
+                    const void* values_, int total_mode, unsigned count, bool offsets, bool fill,
+                    unsigned* workspace, int* out_offsets, int64_t capacity, int* out_columns, void* out_values_,
+                    int64_t* out_source, hipStream_t stream) {
+  const U* values = static_cast<const U*>(values_);
+  U* out_values = static_cast<U*>(out_values_);
+  const dim3 grid(s.rows_grid), block(kBuildBlock);
+  if (!total_mode) {
+    if (offsets)
+      hipLaunchKernelGGL(csr_topk_lengths_kernel, dim3(1), dim3(kScanBlock), 0, stream, m, nonzeros,
+                         static_cast<int>(count), row_offsets, out_offsets);
+    if (fill)
+      hipLaunchKernelGGL((csr_topk_rows_kernel<U>), grid, block, 0, stream, m, nonzeros, s.rows_per_wave,
+                         static_cast<int>(count), row_offsets, column_indices, values, out_offsets, capacity,
+                         out_columns, out_values, out_source);
+    return launch_status();
+  }
+  unsigned* bins = workspace;
+  unsigned* th = workspace + kMaxDigitPasses * kDigitBins;
+  int* q = reinterpret_cast<int*>(th + 1);
+  int* ties = q + m;
+  hipLaunchKernelGGL(csr_topk_clear_kernel, dim3(1), dim3(kScanBlock), 0, stream, bins);
+  for (int p = 0; p < s.digit_passes; ++p)
+    hipLaunchKernelGGL((csr_topk_flat_hist_kernel<U>), dim3(s.flat_grid), block, 0, stream, nonzeros, p, count,
+                       values, bins);
+  hipLaunchKernelGGL((csr_topk_total_rows_kernel<U>), grid, block, 0, stream, m, nonzeros, s.rows_per_wave, count,
+                     row_offsets, values, bins, out_offsets, ties);
+  hipLaunchKernelGGL(topk_total_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, m, s.digit_passes, count, bins,
+                     ties, q, out_offsets, th);
+  hipLaunchKernelGGL((csr_topk_total_fill_kernel<U>), grid, block, 0, stream, m, nonzeros, s.rows_per_wave,
+                     row_offsets, column_indices, values, th, q, out_offsets, capacity, out_columns, out_values,
+                     out_source);
+  return launch_status();
+}
+
 }  // namespace
 }  // namespace sputnik_hip
 
@@ -1192,6 +1569,82 @@ int sputnik_hip_csr_regrow(int m, int n, int nonzeros, const int* row_offsets, c
   if (value_bytes == 2) SPUTNIK_REGROW(uint32_t, uint16_t);
   SPUTNIK_REGROW(uint32_t, uint32_t);
 #undef SPUTNIK_REGROW
+}
+
+int sputnik_hip_csr_topk_launch_shape(int m, int n, int nonzeros, int value_bytes, int total_mode, int* served,
+                                      int* rows_per_wave, int* group_lanes, int* elements_per_lane,
+                                      int* rows_per_workgroup, int* digit_passes, int* rows_grid, int* flat_grid) {
+  if (n < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const CsrTopkShape s = csr_topk_shape(m, nonzeros, value_bytes, total_mode);
+  if (s.status != 0) return s.status;
+  if (served) *served = s.served;
+  if (rows_per_wave) *rows_per_wave = s.rows_per_wave;
+  if (group_lanes) *group_lanes = s.group_lanes;
+  if (elements_per_lane) *elements_per_lane = s.elements_per_lane;
+  if (rows_per_workgroup) *rows_per_workgroup = s.rows_per_workgroup;
+  if (digit_passes) *digit_passes = s.digit_passes;
+  if (rows_grid) *rows_grid = s.rows_grid;
+  if (flat_grid) *flat_grid = s.flat_grid;
+  return 0;
+}
+
+size_t sputnik_hip_csr_topk_workspace_bytes(int m, int n, int nonzeros, int total_mode) {
+  if (m < 0 || n < 0 || nonzeros < 0 || !total_mode) return 0;   // per row: registers and LDS only
+  return sizeof(unsigned) * topk_workspace_words(m, 1);
+}
+
+int sputnik_hip_csr_topk(int m, int n, int nonzeros, const int* row_offsets, const int* column_indices,
+                         const void* values, int value_bytes, int total_mode, int64_t count, void* workspace,
+                         size_t workspace_bytes, int* out_row_indices, int* out_row_offsets,
+                         int* out_column_indices, void* out_values, int64_t* out_source, int64_t out_capacity,
+                         sputnik_hip_stream_t stream_) {
+  if (n < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const CsrTopkShape s = csr_topk_shape(m, nonzeros, value_bytes, total_mode);
+  if (s.status != 0) return s.status;
+  if (!s.served || count < 0 || count > (total_mode ? static_cast<int64_t>(nonzeros) : static_cast<int64_t>(n)) ||
+      out_capacity < 0 || out_row_offsets == nullptr || !aligned_to(out_row_offsets, sizeof(int)))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const bool empty = m == 0 || nonzeros == 0 || count == 0;
+  // per-row mode in two halves: no columns = offsets and row order only; columns but no
+  // row_indices = the fill under the offsets a former call wrote.  Total mode is one call.
+  const bool fill = total_mode || out_column_indices != nullptr;
+  const bool offsets = total_mode || !fill || out_row_indices != nullptr;
+  if ((m > 0 && offsets && out_row_indices == nullptr) ||
+      (out_row_indices != nullptr && !aligned_to(out_row_indices, sizeof(int))) ||
+      (total_mode && out_capacity < count))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (fill && !empty &&
+      (out_column_indices == nullptr || !aligned_to(out_column_indices, sizeof(int)) || out_values == nullptr ||
+       !aligned_to(out_values, value_bytes) || out_source == nullptr || !aligned_to(out_source, sizeof(int64_t))))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (!empty) {
+    if (row_offsets == nullptr || !aligned_to(row_offsets, sizeof(int)) ||
+        (fill && (column_indices == nullptr || !aligned_to(column_indices, sizeof(int)) || values == nullptr ||
+                  !aligned_to(values, value_bytes))))
+      return SPUTNIK_HIP_INVALID_ARGUMENT;
+    const size_t ws_bytes = sputnik_hip_csr_topk_workspace_bytes(m, n, nonzeros, total_mode);
+    if (ws_bytes > 0 && (workspace == nullptr || !aligned_to(workspace, sizeof(unsigned)) || workspace_bytes < ws_bytes))
+      return SPUTNIK_HIP_INVALID_ARGUMENT;
+  }
+  if (empty) {
+    // nothing is kept: the zero offsets and the row order 0 .. m - 1 of equal lengths
+    if (offsets && hipMemsetAsync(out_row_offsets, 0, sizeof(int) * (static_cast<size_t>(m) + 1), stream) != hipSuccess)
+      return launch_status();
+  } else {
+    const int st = value_bytes == 2
+                       ? launch_csr_topk<uint16_t>(s, m, nonzeros, row_offsets, column_indices, values, total_mode,
+                                                   static_cast<unsigned>(count), offsets, fill,
+                                                   static_cast<unsigned*>(workspace), out_row_offsets, out_capacity,
+                                                   out_column_indices, out_values, out_source, stream)
+                       : launch_csr_topk<uint32_t>(s, m, nonzeros, row_offsets, column_indices, values, total_mode,
+                                                   static_cast<unsigned>(count), offsets, fill,
+                                                   static_cast<unsigned*>(workspace), out_row_offsets, out_capacity,
+                                                   out_column_indices, out_values, out_source, stream);
+    if (st != 0) return st;
+  }
+  if (out_row_indices == nullptr || m == 0) return launch_status();
+  return sputnik_hip_csr_row_order(1, m, n, out_row_offsets, out_row_indices, stream_);
 }
 
 }  // extern "C"

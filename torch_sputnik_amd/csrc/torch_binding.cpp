@@ -27,6 +27,7 @@
 #include <torch/library.h>
 
 #include <algorithm>
+#include <limits>
 #include <mutex>
 #include <tuple>
 #include <vector>
@@ -2124,6 +2125,75 @@ std::vector<Tensor> csr_regrow(const Tensor& values_in, const Tensor& row_offset
   return {out_columns, out_values, source};
 }
 
+// The CSR pattern (row_offsets [m + 1], column_indices [nnz]) with `values` [nnz] -> [row_indices,
+// row_offsets, column_indices, values, source (int64)] of its `total` entries of largest |value|,
+// or of the `per_row` largest of every row (the other one -1): sputnik_hip.h:
+// sputnik_hip_csr_topk.  Total mode knows its size up front: no synchronisation, torch
+// allocations only.  Per-row mode reads the new size out_row_offsets[m] back once -- the ONE
+// synchronisation, as in dense_to_csr -- between the offsets half and the fill half of the call.
+// The op does not know the matrix width: any per_row >= 0 is taken (a row keeps
+// min(len_r, per_row)).
+std::vector<Tensor> csr_topk(const Tensor& values_in, const Tensor& row_offsets_in,
+                             const Tensor& column_indices_in, int64_t per_row, int64_t total) {
+  TORCH_CHECK(values_in.is_cuda(), "values must be a GPU (HIP) tensor, got ", values_in.device());
+  for (const Tensor* t : {&row_offsets_in, &column_indices_in}) {
+    TORCH_CHECK(t->device() == values_in.device(), "every tensor must be on ", values_in.device(), ", got ",
+                t->device());
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1, "row_offsets and column_indices must be 1-D "
+                "int32 tensors, got ", t->scalar_type(), " ", t->sizes());
+  }
+  const auto type = values_in.scalar_type();
+  TORCH_CHECK(type == at::kFloat || type == at::kHalf || type == at::kBFloat16,
+              "values must be float32, float16 or bfloat16, got ", type);
+  TORCH_CHECK(row_offsets_in.numel() >= 1, "row_offsets should be [m + 1], got ", row_offsets_in.sizes());
+  TORCH_CHECK(values_in.dim() == 1 && values_in.numel() == column_indices_in.numel(),
+              "values should be [nnz] like column_indices ", column_indices_in.sizes(), ", got ", values_in.sizes());
+  TORCH_CHECK((per_row >= 0) != (total >= 0), "give exactly one of per_row / total");
+  const c10::DeviceGuard guard(values_in.device());
+  const Tensor values = values_in.contiguous(), row_offsets = row_offsets_in.contiguous();
+  const Tensor column_indices = column_indices_in.contiguous();
+  const int m = to_int(row_offsets.numel() - 1, "m");
+  const int nonzeros = to_int(values.numel(), "nnz");
+  const int total_mode = total >= 0 ? 1 : 0;
+  const int n = std::numeric_limits<int>::max();   // (not known here: bounds per_row alone)
+  const int64_t count = total_mode ? total : std::min<int64_t>(per_row, n);
+  const int value_bytes = static_cast<int>(values.element_size());
+  int served = 0;
+  check_status(sputnik_hip_csr_topk_launch_shape(m, n, nonzeros, value_bytes, total_mode, &served, nullptr,
+                                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
+               "csr_topk");
+  TORCH_CHECK(served, "torch_sputnik::csr_topk: ", m, " rows are beyond the row-order kernel "
+              "(sputnik_hip_csr_topk_launch_shape); take topology.prune_csr");
+  TORCH_CHECK(!total_mode || count <= nonzeros, "torch_sputnik::csr_topk: ", count, " entries asked of ", nonzeros);
+  const auto index_options = row_offsets.options();
+  Tensor out_row_indices = at::empty({m}, index_options);
+  Tensor out_row_offsets = at::empty({m + 1}, index_options);
+  const size_t ws_bytes = sputnik_hip_csr_topk_workspace_bytes(m, n, nonzeros, total_mode);
+  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, values.options().dtype(at::kByte));
+  const auto stream = current_stream(values);
+  int64_t kept = count;
+  if (!total_mode) {
+    check_status(sputnik_hip_csr_topk(m, n, nonzeros, row_offsets.data_ptr<int>(), nullptr, nullptr, value_bytes,
+                                      0, count, nullptr, 0, out_row_indices.data_ptr<int>(),
+                                      out_row_offsets.data_ptr<int>(), nullptr, nullptr, nullptr, 0, stream),
+                 "csr_topk (offsets)");
+    kept = out_row_offsets[m].item<int>();   // the synchronisation
+    TORCH_CHECK(kept >= 0 && kept <= nonzeros, "torch_sputnik::csr_topk: row_offsets do not ascend inside 0 .. ",
+                nonzeros);
+  }
+  Tensor out_columns = at::empty({kept}, index_options);
+  Tensor out_values = at::empty({kept}, values.options());
+  Tensor source = at::empty({kept}, index_options.dtype(at::kLong));
+  if (total_mode || kept > 0)
+    check_status(sputnik_hip_csr_topk(
+                     m, n, nonzeros, row_offsets.data_ptr<int>(), column_indices.data_ptr<int>(), values.data_ptr(),
+                     value_bytes, total_mode, count, ws_bytes ? workspace.data_ptr() : nullptr, ws_bytes,
+                     total_mode ? out_row_indices.data_ptr<int>() : nullptr, out_row_offsets.data_ptr<int>(),
+                     out_columns.data_ptr<int>(), out_values.data_ptr(), source.data_ptr<int64_t>(), kept, stream),
+                 "csr_topk");
+  return {out_row_indices, out_row_offsets, out_columns, out_values, source};
+}
+
 // ---- the fused attention with one mask per batch element (sputnik_hip.h:
 // sparse_attention_many_mask_*, sparse_attention_heads_many_mask_*) ----
 
@@ -2572,6 +2642,7 @@ TORCH_LIBRARY(torch_sputnik, m) {
   m.def("topk_to_csr(Tensor scores, int per_row, int total, Tensor? values_from) -> Tensor[]");
   m.def("csr_regrow(Tensor values, Tensor row_offsets, Tensor column_indices, Tensor drop_counts, "
         "Tensor scores) -> Tensor[]");
+  m.def("csr_topk(Tensor values, Tensor row_offsets, Tensor column_indices, int per_row, int total) -> Tensor[]");
   m.def(
       "sparse_attention_many_mask(int b, Tensor nonzeros, Tensor query, Tensor key, Tensor value, "
       "Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, bool want_lse, "
@@ -2674,6 +2745,7 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("row_order", &row_order);
   m.impl("topk_to_csr", &topk_to_csr);
   m.impl("csr_regrow", &csr_regrow);
+  m.impl("csr_topk", &csr_topk);
   m.impl("sparse_attention_many_mask", &sparse_attention_many_mask);
   m.impl("sparse_attention_many_mask_plan", &sparse_attention_many_mask_plan);
   m.impl("sparse_attention_heads_many_mask", &sparse_attention_heads_many_mask);

@@ -13,7 +13,8 @@ current GPU) instead of a hard ``.cuda()``; ``differentiable_softmax=True``
 opts in to a softmax with a gradient.
 Additions: ``SparseLinear.from_dense`` builds a ready layer from a dense weight by
 magnitude, ``SparseLinear.update_topology`` is one drop-and-grow step (SET, RigL),
-``SparseLinear.collect_dense_grad`` / ``rigl_update`` gather RigL's grow scores in the backward.
+``SparseLinear.collect_dense_grad`` / ``rigl_update`` gather RigL's grow scores in the backward,
+``SparseLinear.prune_to`` is one step of gradual magnitude pruning (the layer becomes sparser).
 """
 import copy
 import math
@@ -239,6 +240,53 @@ class SparseLinear(nn.Module):
         self.values.copy_(new_values)
         functional.unregister_static_topology(self.row_indices, self.row_offsets, self.column_indices)
         self._set_topology(None, self.row_indices.clone(), self.row_offsets.clone(), column_indices)
+        return source
+
+    @torch.no_grad()
+    def prune_to(self, density=None, nonzeros=None, per_row=False):
+        """One step of gradual magnitude pruning: the layer keeps its entries of largest
+        ``|values|`` and becomes sparser.  ``density``: ``round(density * out * in)`` entries of
+        the matrix stay, or ``per_row`` ``round(density * in)`` of every row (a shorter row
+        keeps what it has); ``nonzeros``: that number itself (of every row, ``per_row``).  Give
+        exactly one of the two.  Among equal magnitudes the lower entry index stays
+        (``topology.prune_csr``: on a GPU module the selection runs over the layer's own values
+        on the device, no dense image is built).
+
+        A matrix-wide target at or above the current ``nnz`` changes nothing: the same
+        Parameter, ``source = arange(nnz)``.  Otherwise ``values`` is REPLACED by a new, shorter
+        ``nn.Parameter`` (the old one's ``requires_grad``, no ``.grad``), kept entries bit for
+        bit; the index tensors are replaced by new ones (the old ones are unregistered, never
+        written to), so no cached plan, transposed topology or half image of the old pattern
+        serves the new one.  ``dense_grad`` is left alone.
+
+        Returns ``source``, int64 ``[new nnz]``, ascending: for every new entry its index in the
+        old ``values``.  An optimizer holds the old Parameter; hand its state over::
+
+            old = layer.values
+            source = layer.prune_to(density=topology.gradual_density(step, t0, t1, d_i, d_f))
+            topology.remap_optimizer_state(optimizer, old, layer.values, source)
+        """
+        if (density is None) == (nonzeros is None):
+            raise ValueError("prune_to: give exactly one of density / nonzeros")
+        out_f, in_f = self.output_features, self.input_features
+        most = in_f if per_row else out_f * in_f
+        if density is not None:
+            if not 0.0 <= density <= 1.0:
+                raise ValueError(f"prune_to: density {density} is outside 0 .. 1")
+            nonzeros = round(density * most)
+        count = int(nonzeros)
+        if not 0 <= count <= most:
+            raise ValueError(f"prune_to: {count} entries asked of {most}")
+        old = self.values
+        nnz = old.numel()
+        if not per_row and count >= nnz:
+            return torch.arange(nnz, dtype=torch.int64, device=old.device)
+        row_indices, row_offsets, column_indices, values, source = topology.prune_csr(
+            old.detach(), self.row_offsets, self.column_indices, in_f,
+            per_row=count if per_row else None, total=None if per_row else count)
+        functional.unregister_static_topology(self.row_indices, self.row_offsets, self.column_indices)
+        self._set_topology(nn.Parameter(values, requires_grad=old.requires_grad), row_indices, row_offsets,
+                           column_indices)
         return source
 
     def forward(self, x):

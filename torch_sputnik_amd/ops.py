@@ -400,6 +400,51 @@ def csr_regrow(values, row_offsets, column_indices, drop_counts, scores):
     return tuple(_ops.csr_regrow(values, row_offsets, column_indices, drop_counts, scores))
 
 
+def check_csr_topk_arguments(values, row_offsets, column_indices, per_row, total):
+    """ValueError unless the three tensors are one CSR pattern with its values (shapes, int32
+    indices, one device) and exactly one of per_row / total is a count in range (``total`` at
+    most nnz, ``per_row`` at least 0).  -> the count.  The dtype of values is the caller's
+    matter."""
+    if (per_row is None) == (total is None):
+        raise ValueError("csr_topk: give exactly one of per_row / total")
+    if values.dim() != 1:
+        raise ValueError(f"csr_topk: values should be [nnz], got {tuple(values.shape)}")
+    if row_offsets.dtype != torch.int32 or row_offsets.dim() != 1 or row_offsets.numel() < 1:
+        raise ValueError(f"csr_topk: row_offsets should be int32 [m + 1], got {row_offsets.dtype} "
+                         f"{tuple(row_offsets.shape)}")
+    if column_indices.dtype != torch.int32 or column_indices.dim() != 1 or column_indices.numel() != values.numel():
+        raise ValueError(f"csr_topk: column_indices should be int32 [{values.numel()}], got "
+                         f"{column_indices.dtype} {tuple(column_indices.shape)}")
+    for name, t in (("row_offsets", row_offsets), ("column_indices", column_indices)):
+        if t.device != values.device:
+            raise ValueError(f"csr_topk: {name} is on {t.device}, values on {values.device}")
+    count = int(total if per_row is None else per_row)
+    if count < 0 or (per_row is None and count > values.numel()):
+        raise ValueError(f"csr_topk: {'total' if per_row is None else 'per_row'} = {count} is outside 0 .. "
+                         f"{values.numel() if per_row is None else 'n'}")
+    return count
+
+
+def csr_topk(values, row_offsets, column_indices, per_row=None, total=None):
+    """The entries of largest ``|values|`` of a CSR pattern, written out as a smaller CSR pattern
+    on the device (csrc/topology.hip): ``total = K`` keeps the K largest of all nnz entries,
+    ``per_row = k`` the ``min(len_r, k)`` largest of every row -- exactly one of the two; among
+    equal magnitudes the lower entry index wins.  Magnitudes rank by the bit pattern without the
+    sign (``topology.magnitude_keys``).  values [nnz] is float32 / float16 / bfloat16,
+    row_offsets [m + 1] and column_indices [nnz] (ascending inside a row) are int32.
+    -> (row_indices, row_offsets, column_indices, values, source): a kept entry carries its
+    column, its value bit for bit and, in ``source`` (int64, ascending), its index in the old
+    arrays.  ``total`` never synchronises; ``per_row`` reads the new size back once.  Raises for
+    CPU tensors and for more rows than ``capi.csr_topk_launch_shape`` serves (16384)."""
+    count = check_csr_topk_arguments(values, row_offsets, column_indices, per_row, total)
+    if values.dtype not in _TOPK_DTYPES:
+        raise ValueError(f"csr_topk: values must be float32, float16 or bfloat16, got {values.dtype}")
+    if not values.is_cuda:
+        raise RuntimeError("csr_topk: GPU tensors only (topology.prune_csr serves CPU tensors)")
+    return tuple(_ops.csr_topk(values, row_offsets, column_indices, -1 if per_row is None else count,
+                               -1 if total is None else count))
+
+
 def sparse_attention_many_mask(b, nonzeros, row_indices, row_offsets, column_indices, query, key,
                                value, scale, with_lse=False, plan=None):
     """softmax(scale * q k^T at the mask) v with one mask per batch element in ONE kernel:

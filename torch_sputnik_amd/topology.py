@@ -263,6 +263,112 @@ def regrow_per_row(values, row_offsets, column_indices, drop_counts, scores):
     return new_columns.to(torch.int32), new_bits.view(values.dtype), source
 
 
+def _csr_topk_served(values, m, n, total):
+    if not (_device_build and values.is_cuda and values.dtype in _TOPK_DTYPES):
+        return False
+    try:
+        return capi.csr_topk_launch_shape(m, n, values.numel(), values.element_size(), total)["served"]
+    except RuntimeError:   # (sizes beyond int32)
+        return False
+
+
+def prune_csr(values, row_offsets, column_indices, n, per_row=None, total=None):
+    """``ops.csr_topk`` for any tensor: the entries of largest magnitude of the CSR pattern
+    (row_offsets [m + 1], column_indices [nnz], int32, ascending inside a row) of an ``m x n``
+    matrix with ``values`` [nnz], as a smaller CSR pattern -- one step of gradual magnitude
+    pruning, without a dense image.  ``total = K`` (``0 <= K <= nnz``) keeps the K entries of
+    largest key (``magnitude_keys``: NaN above inf, -0.0 with 0.0); ``per_row = k``
+    (``0 <= k <= n``) keeps the ``min(len_r, k)`` largest of every row.  Among equal keys the
+    lower entry index wins: the lower column inside a row, the lower flat index across rows.
+
+    -> (row_indices, row_offsets, column_indices, values, source), new tensors: a kept entry
+    carries its column, its value bit for bit and, in ``source`` (int64, ascending), its index
+    in the old arrays.
+
+    GPU float32 / float16 / bfloat16 values take the device kernels up to 16384 rows
+    (``capi.csr_topk_launch_shape``; ``total`` without a host synchronisation, ``per_row`` with
+    the one read of the new size); CPU tensors, other dtypes (ranked as ``.float()``), more rows
+    and ``enable_device_build(False)`` take the same rule in torch: a stable descending argsort
+    of the keys.  Both give the same integers and value bits."""
+    count = ops.check_csr_topk_arguments(values, row_offsets, column_indices, per_row, total)
+    if per_row is not None and count > n:
+        raise ValueError(f"prune_csr: per_row = {count} is outside 0 .. {n}")
+    values = values.detach()
+    m, nnz = row_offsets.numel() - 1, values.numel()
+    if _csr_topk_served(values, m, n, per_row is None):
+        return ops.csr_topk(values, row_offsets, column_indices, per_row=per_row, total=total)
+    index = dict(dtype=torch.int64, device=values.device)
+    keys = magnitude_keys(values if values.dtype in _TOPK_DTYPES else values.float())
+    order = torch.argsort(keys, descending=True, stable=True)     # key descending, index ascending
+    lengths = (row_offsets[1:] - row_offsets[:-1]).to(torch.int64)
+    rows = torch.repeat_interleave(torch.arange(m, **index), lengths, output_size=nnz)
+    if per_row is None:
+        source = torch.sort(order[:count]).values
+    else:
+        # a stable sort by row keeps that order inside every row: an entry's rank in its row is
+        # its position behind the row's start
+        by_row = order[torch.argsort(rows[order], stable=True)]
+        rank = torch.empty(nnz, **index)
+        rank[by_row] = torch.arange(nnz, **index) - row_offsets[:-1].to(torch.int64)[rows[by_row]]
+        source = torch.nonzero(rank < count).reshape(-1)
+    new_offsets = torch.zeros(m + 1, dtype=torch.int32, device=values.device)
+    new_offsets[1:] = torch.cumsum(torch.bincount(rows[source], minlength=m), 0)
+    return (diffsort(new_offsets), new_offsets, column_indices[source], _take_bits(values, source), source)
+
+
+def gradual_density(step, begin_step, end_step, initial_density, final_density):
+    """The density at ``step`` of the cubic schedule of gradual magnitude pruning (Zhu & Gupta,
+    "To prune, or not to prune", 2017): ``d_f + (d_i - d_f) * (1 - (t - t0) / (t1 - t0)) ** 3``
+    between ``begin_step`` t0 and ``end_step`` t1, ``initial_density`` d_i up to t0 and
+    ``final_density`` d_f from t1 on.  A pure function of Python floats: pass the result to
+    ``SparseLinear.prune_to(density=...)`` every few hundred steps."""
+    if end_step < begin_step:
+        raise ValueError(f"gradual_density: end_step {end_step} is before begin_step {begin_step}")
+    if step <= begin_step:
+        return float(initial_density)
+    if step >= end_step:
+        return float(final_density)
+    left = 1.0 - (step - begin_step) / (end_step - begin_step)
+    return float(final_density + (initial_density - final_density) * left ** 3)
+
+
+def remap_optimizer_state(optimizer, old_parameter, new_parameter, source):
+    """Hands an optimizer's state over a topology step.  ``source`` [new nnz] (int64) is what
+    ``SparseLinear.prune_to`` / ``update_topology`` / ``rigl_update`` return: for every new
+    entry its index in the old ``values``, or -1 for a grown one.
+
+    Every tensor in ``optimizer.state[old_parameter]`` of ``old_parameter``'s shape (momentum
+    buffer, Adam's moments) becomes ``where(source >= 0, state[source], 0)`` at
+    ``new_parameter``'s length -- a copy of bits for carried entries, zero for grown ones; other
+    entries (``step``) are kept.  The state moves to the key ``new_parameter`` and
+    ``new_parameter`` takes ``old_parameter``'s slot in ``optimizer.param_groups``.  With
+    ``old_parameter is new_parameter`` (after ``update_topology``, which writes into the
+    Parameter) only the tensors are rewritten.  Plain torch indexing."""
+    source = source.to(torch.int64)
+    if source.dim() != 1 or source.numel() != new_parameter.numel():
+        raise ValueError(f"remap_optimizer_state: source should be [{new_parameter.numel()}], got "
+                         f"{tuple(source.shape)}")
+    if old_parameter is not new_parameter:
+        slots = [(group, i) for group in optimizer.param_groups
+                 for i, p in enumerate(group["params"]) if p is old_parameter]
+        if not slots:
+            raise ValueError("remap_optimizer_state: old_parameter is not in optimizer.param_groups")
+        for group, i in slots:
+            group["params"][i] = new_parameter
+    state = optimizer.state.pop(old_parameter, None)
+    if state is None:      # (no step taken yet: nothing to carry)
+        return
+    carried = source >= 0
+    at = source.clamp(min=0)
+    for name, t in list(state.items()):
+        if torch.is_tensor(t) and t.shape == old_parameter.shape and t.dim() == 1:
+            where = carried.to(t.device)
+            bits = t.contiguous().view(_BIT_VIEWS[t.element_size()])
+            moved = torch.where(where, bits[at.to(t.device)], torch.zeros(1, dtype=bits.dtype, device=t.device))
+            state[name] = moved.view(t.dtype).reshape(new_parameter.shape)
+    optimizer.state[new_parameter] = state
+
+
 def generate_mask(m, n, device="cpu", sparsity=0.9, round_to=4, generator=None):
     """Random 0/1 mask with the nonzero count of modules/sparse_attention.py:25-36:
     ``int(m*n*sparsity)`` zeros rounded DOWN to a multiple of ``round_to``.
