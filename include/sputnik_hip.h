@@ -1599,6 +1599,88 @@ SPUTNIK_HIP_API int sputnik_hip_csr_topk_launch_shape(int m, int n, int nonzeros
                              int* elements_per_lane, int* rows_per_workgroup, int* digit_passes,
                              int* rows_grid, int* flat_grid);
 
+/* ------------------------------------------------------------------------
+ * ONE top-k across the entries of several CSR patterns, each written out as a smaller CSR
+ * pattern (topology.prune_csr_global, topology.prune_layers_to): global magnitude pruning, the
+ * layers of a model ranked together.
+ *
+ * Inputs: `layers` patterns in the caller's order.  HOST arrays of `layers` elements: rows
+ * (m_l), nonzeros (nnz_l), and the DEVICE pointers row_offsets[l] [m_l + 1], column_indices[l]
+ * [nnz_l] (int32, ascending inside a row) and values[l] [nnz_l], all of `value_bytes` = 2 or 4.
+ * The pointer arrays are read on the host during the call and travel to the kernels as
+ * arguments; nothing is copied to the device.
+ * The `count` (0 <= count <= sum nnz_l) entries of largest KEY over all layers are kept; the
+ * keys are those of sputnik_hip_csr_topk.  Among equal keys the entry of the lower layer wins,
+ * then the lower entry index.  With layers = 1 the result is sputnik_hip_csr_topk's in total
+ * mode.
+ *
+ * How many entries a layer keeps is on the device, so the call has two halves around ONE read
+ * of out_nonzeros, whatever `layers` is:
+ *   _select   a clear launch for the 256-bin histograms in `workspace` (a kernel, as in
+ *             sputnik_hip_csr_topk); per digit, one launch per `layers_per_launch` layers over
+ *             their FLAT values arrays -- a workgroup finds its layer and its pieces in a table
+ *             among its arguments, and every launch adds into the same bins; per layer a rows
+ *             launch (entries above and at the one threshold) and, in layer order, a scan
+ *             launch that hands the layer its share of the tie quota (what the layers in front
+ *             left of it), writes out_row_offsets[l] [m_l + 1] and out_nonzeros[l].
+ *             out_nonzeros: device, int32 [layers].  Never synchronises.
+ *   _fill     with out_capacity[l] (host) = the out_nonzeros[l] read back: per layer the fill of
+ *             out_column_indices[l], out_values[l] (the old value bit for bit) and out_source[l]
+ *             (int64: the index in the layer's old arrays; it ascends), out_capacity[l] entries
+ *             each -- a slot at or beyond it is not written --, and the row order
+ *             out_row_indices[l] [m_l] of out_row_offsets[l].  A layer with out_capacity[l] = 0
+ *             takes no fill launch and its three pointers may be NULL.
+ * Both halves take the same layers, the same `workspace`
+ * (sputnik_hip_csr_topk_global_workspace_bytes(layers, rows) bytes, 4-byte aligned, the call's
+ * own from _select until _fill's launches have run) and the same out_row_offsets.
+ * Every count is an integer and every store a vector store to a slot one lane owns: two calls
+ * give equal arrays.  A layer may have no rows or no entries, and may keep none.
+ * Offsets that do not ascend inside 0 .. nnz_l are a caller error with an unspecified result,
+ * but nothing outside the arrays is read or written.
+ *
+ * SPUTNIK_HIP_INVALID_ARGUMENT: a value width other than 2 / 4, a negative size, a count out of
+ * range, a layer of more rows than sputnik_hip_csr_row_order serves (16384), sum nnz_l above
+ * INT_MAX, an out_capacity[l] outside 0 .. nnz_l, a missing or misaligned pointer, a workspace
+ * too small.
+ * ---------------------------------------------------------------------- */
+SPUTNIK_HIP_API int sputnik_hip_csr_topk_global_select(int layers, const int* rows, const int* nonzeros,
+                             const int* const* row_offsets, const void* const* values, int value_bytes,
+                             int64_t count, void* workspace, size_t workspace_bytes,
+                             int* const* out_row_offsets, int* out_nonzeros, sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_csr_topk_global_fill(int layers, const int* rows, const int* nonzeros,
+                             const int* const* row_offsets, const int* const* column_indices,
+                             const void* const* values, int value_bytes, void* workspace,
+                             size_t workspace_bytes, const int64_t* out_capacity,
+                             int* const* out_row_indices, int* const* out_row_offsets,
+                             int* const* out_column_indices, void* const* out_values,
+                             int64_t* const* out_source, sputnik_hip_stream_t stream);
+
+/* 4 * (4 * 256 + 2 + 2 * sum rows[l]) bytes: the bins, the threshold, the ties handed out so
+ * far, and per row its quota and its ties.  0 for a negative size. */
+SPUTNIK_HIP_API size_t sputnik_hip_csr_topk_global_workspace_bytes(int layers, const int* rows);
+
+/* The instance sputnik_hip_csr_topk_global_select runs for these layers (HOST arrays rows and
+ * nonzeros of `layers` elements); the entries take their decisions from the same function this
+ * reports, and from nothing else.
+ *   served                   1, or 0 where a layer has more than 16384 rows or sum nnz_l is
+ *                            above INT_MAX (every other field is -1 then)
+ *   digit_passes             8-bit digits of a key: the value bytes
+ *   layers_per_launch        layers one digit launch takes in its argument table (32)
+ *   elements_per_workgroup   entries one workgroup of the flat walk covers: 8 * 256 16-byte
+ *                            pieces = 2048 * 16 / value_bytes; layer l takes
+ *                            ceil((nnz_l / (16 / value_bytes) + 2) / 2048) workgroups, none for
+ *                            nnz_l = 0
+ *   digit_launches           argument tables per digit: ceil(layers / layers_per_launch); a table
+ *                            whose layers are all empty is not launched
+ * Per layer, the rows, scan and fill launches are those sputnik_hip_csr_topk_launch_shape
+ * reports for (m_l, nnz_l) in total mode.
+ * Host only, launches nothing; any output pointer may be NULL.  Returns
+ * SPUTNIK_HIP_INVALID_ARGUMENT for a negative size and a value width other than 2 / 4. */
+SPUTNIK_HIP_API int sputnik_hip_csr_topk_global_launch_shape(int layers, const int* rows, const int* nonzeros,
+                             int value_bytes, int* served, int* digit_passes, int* layers_per_launch,
+                             int* elements_per_workgroup, int* digit_launches);
+
 /*
  * out[r][i] = in[r][permutation[i]], i < n, for `rows` value arrays (strides in
  * elements) that share one permutation: the values of a static pattern in the

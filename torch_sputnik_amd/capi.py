@@ -116,6 +116,12 @@ SIGNATURES = {
                              + [_c_ptr] * 5 + [_c_i64, _c_ptr]),
     "sputnik_hip_csr_topk_workspace_bytes": (_c_size, [_c_int] * 4),
     "sputnik_hip_csr_topk_launch_shape": (_c_int, [_c_int] * 5 + [_c_ptr] * 8),
+    "sputnik_hip_csr_topk_global_select": (_c_int, [_c_int] + [_c_ptr] * 4 + [_c_int, _c_i64, _c_ptr, _c_size]
+                                           + [_c_ptr] * 3),
+    "sputnik_hip_csr_topk_global_fill": (_c_int, [_c_int] + [_c_ptr] * 5 + [_c_int, _c_ptr, _c_size]
+                                         + [_c_ptr] * 7),
+    "sputnik_hip_csr_topk_global_workspace_bytes": (_c_size, [_c_int, _c_ptr]),
+    "sputnik_hip_csr_topk_global_launch_shape": (_c_int, [_c_int, _c_ptr, _c_ptr, _c_int] + [_c_ptr] * 5),
     "sputnik_hip_csr_transpose_checked": (_c_int, [_c_int] * 4 + [_c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
                                                          _c_size, _c_ptr]),
@@ -582,6 +588,27 @@ def csr_topk_launch_shape(m, n, nonzeros, value_bytes, total):
     _check(lib().sputnik_hip_csr_topk_launch_shape(
         m, n, nonzeros, value_bytes, int(bool(total)), *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
         "sputnik_hip_csr_topk_launch_shape")
+    shape = {name: o.value for name, o in zip(names, outs)}
+    shape["served"] = bool(shape["served"])
+    return shape
+
+
+def csr_topk_global_launch_shape(rows, nonzeros, value_bytes):
+    """The instance of the one top-k across several CSR patterns (``rows[l]`` rows and
+    ``nonzeros[l]`` values of that width, 2 or 4 bytes, per layer): a dict of served (bool: every
+    layer within the row-order kernel's rows and the entries within int32; the other fields are
+    -1 where it is not), digit_passes, layers_per_launch (layers one digit launch takes in its
+    argument table), elements_per_workgroup (entries one workgroup of the flat walk covers) and
+    digit_launches (include/sputnik_hip.h).  Host only; raises for sizes the entry rejects."""
+    if len(rows) != len(nonzeros):
+        raise ValueError(f"csr_topk_global_launch_shape: {len(rows)} rows for {len(nonzeros)} nonzeros")
+    names = ("served", "digit_passes", "layers_per_launch", "elements_per_workgroup", "digit_launches")
+    outs = [_c_int(-1) for _ in names]
+    layers = len(rows)
+    c_rows, c_nonzeros = (_c_int * layers)(*rows), (_c_int * layers)(*nonzeros)
+    _check(lib().sputnik_hip_csr_topk_global_launch_shape(
+        layers, ctypes.cast(c_rows, _c_ptr), ctypes.cast(c_nonzeros, _c_ptr), value_bytes,
+        *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]), "sputnik_hip_csr_topk_global_launch_shape")
     shape = {name: o.value for name, o in zip(names, outs)}
     shape["served"] = bool(shape["served"])
     return shape

@@ -1,6 +1,7 @@
 // CSR topologies from dense masks / matrices, built on the device for gfx950
 // (include/sputnik_hip.h: sputnik_hip_dense_to_csr_*, sputnik_hip_csr_row_order), and the
-// selections that write one out: sputnik_hip_topk_to_csr, sputnik_hip_csr_regrow, sputnik_hip_csr_topk.
+// selections that write one out: sputnik_hip_topk_to_csr, sputnik_hip_csr_regrow, sputnik_hip_csr_topk,
+// sputnik_hip_csr_topk_global_*.
 //
 // Replaces the torch loop of topology.dense_to_sparse_3d (per mask: != 0, to_sparse_csr, two
 // casts, a stable argsort and a host read of the count) by a fixed number of launches for any
@@ -1247,13 +1248,12 @@ __global__ __launch_bounds__(kScanBlock) void csr_topk_clear_kernel(unsigned* __
   bins[threadIdx.x] = 0u;
 }
 
-// Total mode, one digit pass over the flat values array: this workgroup's kFlatSteps * 256
-// pieces into an LDS histogram, that into bins[pass][*] with one integer atomic add per
-// non-empty bin.
+// Total mode, one digit pass of one workgroup of kBuildBlock threads over a flat values array:
+// the kFlatSteps * 256 pieces of the array's workgroup `block` into an LDS histogram, that into
+// bins[pass][*] with one integer atomic add per non-empty bin.
 template <typename U>
-__global__ __launch_bounds__(kBuildBlock) void csr_topk_flat_hist_kernel(int nonzeros, int pass, unsigned count,
-                                                                         const U* __restrict__ values,
-                                                                         unsigned* bins) {
+__device__ __forceinline__ void flat_digit_pass(const U* __restrict__ values, int64_t nonzeros, int64_t block,
+                                                int pass, unsigned count, unsigned* bins) {
   constexpr int V = kLoadBytes / sizeof(U), P = sizeof(U) * 8 / kDigitBits;
   __shared__ unsigned hist[kDigitBins];
   __shared__ unsigned select[kSelectWords];
@@ -1264,9 +1264,9 @@ __global__ __launch_bounds__(kBuildBlock) void csr_topk_flat_hist_kernel(int non
   const int shift = kDigitBits * (P - 1 - pass);
   const int lead = static_cast<int>((reinterpret_cast<uintptr_t>(values) % kLoadBytes) / sizeof(U));
   for (int s = 0; s < kFlatSteps; ++s) {
-    const int64_t piece = (static_cast<int64_t>(blockIdx.x) * kFlatSteps + s) * kBuildBlock + threadIdx.x;
+    const int64_t piece = (block * kFlatSteps + s) * kBuildBlock + threadIdx.x;
     unsigned valid;
-    const Piece<U> v = load_piece(values, piece * V - lead, static_cast<int64_t>(nonzeros), &valid);
+    const Piece<U> v = load_piece(values, piece * V - lead, nonzeros, &valid);
 #pragma unroll
     for (int e = 0; e < V; ++e) {
       const unsigned key = key_of(v.e[e]);
@@ -1277,6 +1277,13 @@ __global__ __launch_bounds__(kBuildBlock) void csr_topk_flat_hist_kernel(int non
   __syncthreads();
   const unsigned c = hist[threadIdx.x];
   if (c != 0u) atomicAdd(&bins[pass * kDigitBins + threadIdx.x], c);
+}
+
+template <typename U>
+__global__ __launch_bounds__(kBuildBlock) void csr_topk_flat_hist_kernel(int nonzeros, int pass, unsigned count,
+                                                                         const U* __restrict__ values,
+                                                                         unsigned* bins) {
+  flat_digit_pass(values, static_cast<int64_t>(nonzeros), static_cast<int64_t>(blockIdx.x), pass, count, bins);
 }
 
 // Total mode: out_offsets[row + 1] = #(key > T), ties[row] = #(key == T) of the row's entries.
@@ -1379,6 +1386,204 @@ int launch_csr_topk(const CsrTopkShape& s, int m, int nonzeros, const int* row_o
   hipLaunchKernelGGL((csr_topk_total_fill_kernel<U>), grid, block, 0, stream, m, nonzeros, s.rows_per_wave,
                      row_offsets, column_indices, values, th, q, out_offsets, capacity, out_columns, out_values,
                      out_source);
+  return launch_status();
+}
+
+// ---------------------------------------------------------------------------
+// One top-k across the entries of SEVERAL CSR patterns (sputnik_hip_csr_topk_global_*): global
+// magnitude pruning.  The total mode above, with the layers' flat values arrays walked into the
+// SAME 256 bins, so that every layer derives the one threshold T and the one tie quota Q; the
+// quota is handed out in layer order, inside a layer in entry order.
+//   digits   one launch per digit serves up to kGlobalLayers layers: a workgroup finds its layer
+//            and its piece range in a table that travels as a kernel argument; more layers
+//            take further launches of the same pass, which add into the same bins
+//   rows     per layer, csr_topk_total_rows_kernel under the shared bins and count
+//   scan     per layer and in layer order, one workgroup: the scan of the total mode with the
+//            ties handed out to the layers in front read from (and this layer's added to) one
+//            word of the workspace; the layer's new size lands in sizes[layer]
+//   fill     per layer, csr_topk_total_fill_kernel and the row order, once the caller has read
+//            the sizes and has the arrays
+// ---------------------------------------------------------------------------
+constexpr int kGlobalLayers = 32;   // layers of one digit launch: 520 bytes of kernel arguments
+
+struct GlobalTable {
+  const void* values[kGlobalLayers];
+  int nonzeros[kGlobalLayers];
+  int first_block[kGlobalLayers + 1];   // (unused slots: the grid)
+};
+
+inline int global_flat_blocks(int nonzeros, int value_bytes) {
+  if (nonzeros <= 0) return 0;
+  const int64_t pieces = static_cast<int64_t>(nonzeros) / (kLoadBytes / value_bytes) + 2;
+  return static_cast<int>(ceil_div64(pieces, int64_t{kBuildBlock} * kFlatSteps));
+}
+
+struct GlobalTopkShape {
+  int status = 0;
+  int served = 0;
+  int digit_passes = -1, layers_per_launch = -1, elements_per_workgroup = -1, digit_launches = -1;
+  int64_t entries = 0, rows = 0;
+};
+inline GlobalTopkShape global_topk_shape(int layers, const int* rows, const int* nonzeros, int value_bytes) {
+  GlobalTopkShape g;
+  if (layers < 0 || (layers > 0 && (rows == nullptr || nonzeros == nullptr)) ||
+      (value_bytes != 2 && value_bytes != 4)) {
+    g.status = SPUTNIK_HIP_INVALID_ARGUMENT;
+    return g;
+  }
+  bool served = true;
+  for (int l = 0; l < layers; ++l) {
+    const CsrTopkShape s = csr_topk_shape(rows[l], nonzeros[l], value_bytes, 1);
+    if (s.status != 0) {
+      g.status = s.status;
+      return g;
+    }
+    served = served && s.served;
+    g.entries += nonzeros[l];
+    g.rows += rows[l];
+  }
+  if (!served || g.entries > INT_MAX) return g;   // (the counts of a bin are 32 bit)
+  g.served = 1;
+  g.digit_passes = value_bytes * 8 / kDigitBits;
+  g.layers_per_launch = kGlobalLayers;
+  g.elements_per_workgroup = kBuildBlock * kFlatSteps * (kLoadBytes / value_bytes);
+  g.digit_launches = static_cast<int>(ceil_div64(layers, kGlobalLayers));
+  return g;
+}
+// bins, T, the ties handed out so far; then per layer the quotas and the ties of its rows
+inline size_t global_topk_workspace_words(int64_t rows) {
+  return static_cast<size_t>(kMaxDigitPasses) * kDigitBins + 2 + 2 * static_cast<size_t>(rows);
+}
+
+// One digit pass over the flat values arrays of the table's layers: flat_digit_pass with the
+// layer and the workgroup's place inside it looked up first.
+template <typename U>
+__global__ __launch_bounds__(kBuildBlock) void csr_topk_global_hist_kernel(GlobalTable table, int pass,
+                                                                           unsigned count, unsigned* bins) {
+  const int block = blockIdx.x;
+  int layer = 0;   // (an empty layer has no workgroup: it is stepped over)
+#pragma unroll
+  for (int i = 1; i < kGlobalLayers; ++i) layer += block >= table.first_block[i] ? 1 : 0;
+  flat_digit_pass(static_cast<const U*>(table.values[layer]), static_cast<int64_t>(table.nonzeros[layer]),
+                  static_cast<int64_t>(block - table.first_block[layer]), pass, count, bins);
+}
+
+// topk_total_scan_kernel for one layer of several: the quota left for this layer is Q less
+// *handed (the ties of the layers in front; none for handed_in == nullptr, the first layer).
+// *handed_out = that plus this layer's ties; *new_size = the layer's kept entries.
+__global__ __launch_bounds__(kScanBlock) void csr_topk_global_scan_kernel(
+    int m, int digit_passes, unsigned count, const unsigned* __restrict__ bins, const int* __restrict__ ties,
+    int* __restrict__ quotas, int* __restrict__ offsets, unsigned* __restrict__ threshold,
+    const unsigned* handed_in, unsigned* handed_out, int* __restrict__ new_size) {
+  __shared__ int wave_sums[kScanBlock / kWave];
+  __shared__ unsigned select[kSelectWords];
+  const int64_t in_front = handed_in != nullptr ? static_cast<int64_t>(*handed_in) : int64_t{0};
+  unsigned need;
+  const unsigned prefix = total_select(bins, digit_passes, count, select, &need);   // (barriers: *handed_in is read)
+  const int64_t quota = static_cast<int64_t>(need) - in_front;
+  const int t = threadIdx.x;
+  const int64_t per = (static_cast<int64_t>(m) + kScanBlock - 1) / kScanBlock;
+  const int64_t i0 = min(static_cast<int64_t>(m), t * per), i1 = min(static_cast<int64_t>(m), i0 + per);
+  int mine = 0;
+  for (int64_t i = i0; i < i1; ++i) mine += ties[i];
+  int tied_here;
+  int64_t ties_before = block_exclusive_scan(mine, wave_sums, &tied_here);
+  __syncthreads();   // (wave_sums is written again)
+  mine = 0;
+  for (int64_t i = i0; i < i1; ++i) {
+    const int tied = ties[i];
+    const int q = static_cast<int>(max(int64_t{0}, min(static_cast<int64_t>(tied), quota - ties_before)));
+    ties_before += tied;
+    quotas[i] = q;
+    const int length = offsets[1 + i] + q;
+    offsets[1 + i] = length;
+    mine += length;
+  }
+  int total;
+  int running = block_exclusive_scan(mine, wave_sums, &total);
+  for (int64_t i = i0; i < i1; ++i) {
+    running += offsets[1 + i];
+    offsets[1 + i] = running;
+  }
+  if (t == 0) {
+    offsets[0] = 0;
+    *threshold = count > 0 ? prefix : kNoThreshold;
+    *handed_out = static_cast<unsigned>(in_front + tied_here);
+    *new_size = total;
+  }
+}
+
+struct GlobalWorkspace {
+  unsigned *bins, *threshold, *handed;
+  int* rows;   // per layer: quotas [m], ties [m]
+};
+inline GlobalWorkspace global_workspace(void* workspace) {
+  GlobalWorkspace w;
+  w.bins = static_cast<unsigned*>(workspace);
+  w.threshold = w.bins + kMaxDigitPasses * kDigitBins;
+  w.handed = w.threshold + 1;
+  w.rows = reinterpret_cast<int*>(w.handed + 1);
+  return w;
+}
+
+template <typename U>
+int launch_global_select(const GlobalTopkShape& g, int layers, const int* rows, const int* nonzeros,
+                         const int* const* row_offsets, const void* const* values, unsigned count,
+                         void* workspace, int* const* out_offsets, int* out_sizes, hipStream_t stream) {
+  const GlobalWorkspace w = global_workspace(workspace);
+  const dim3 block(kBuildBlock);
+  hipLaunchKernelGGL(csr_topk_clear_kernel, dim3(1), dim3(kScanBlock), 0, stream, w.bins);
+  for (int p = 0; p < g.digit_passes; ++p)
+    for (int l0 = 0; l0 < layers; l0 += kGlobalLayers) {
+      GlobalTable table;
+      int grid = 0;
+      for (int i = 0; i < kGlobalLayers; ++i) {
+        const bool used = l0 + i < layers;
+        table.values[i] = used ? values[l0 + i] : nullptr;
+        table.nonzeros[i] = used ? nonzeros[l0 + i] : 0;
+        table.first_block[i] = grid;
+        if (used) grid += global_flat_blocks(nonzeros[l0 + i], static_cast<int>(sizeof(U)));
+      }
+      table.first_block[kGlobalLayers] = grid;
+      if (grid > 0)
+        hipLaunchKernelGGL((csr_topk_global_hist_kernel<U>), dim3(grid), block, 0, stream, table, p, count, w.bins);
+    }
+  int* per_row = w.rows;
+  for (int l = 0; l < layers; ++l) {
+    const int m = rows[l];
+    const CsrTopkShape s = csr_topk_shape(m, nonzeros[l], static_cast<int>(sizeof(U)), 1);
+    int* q = per_row;
+    int* ties = q + m;
+    per_row = ties + m;
+    if (m > 0)
+      hipLaunchKernelGGL((csr_topk_total_rows_kernel<U>), dim3(s.rows_grid), block, 0, stream, m, nonzeros[l],
+                         s.rows_per_wave, count, row_offsets[l], static_cast<const U*>(values[l]), w.bins,
+                         out_offsets[l], ties);
+    hipLaunchKernelGGL(csr_topk_global_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, m, g.digit_passes, count,
+                       w.bins, ties, q, out_offsets[l], w.threshold,
+                       l == 0 ? static_cast<const unsigned*>(nullptr) : w.handed, w.handed, out_sizes + l);
+  }
+  return launch_status();
+}
+
+template <typename U>
+int launch_global_fill(int layers, const int* rows, const int* nonzeros, const int* const* row_offsets,
+                       const int* const* column_indices, const void* const* values, void* workspace,
+                       const int64_t* capacity, int* const* out_offsets, int* const* out_columns,
+                       void* const* out_values, int64_t* const* out_source, hipStream_t stream) {
+  const GlobalWorkspace w = global_workspace(workspace);
+  const int* per_row = w.rows;
+  for (int l = 0; l < layers; ++l) {
+    const int m = rows[l];
+    const CsrTopkShape s = csr_topk_shape(m, nonzeros[l], static_cast<int>(sizeof(U)), 1);
+    const int* q = per_row;
+    per_row += 2 * static_cast<int64_t>(m);
+    if (m == 0 || capacity[l] == 0) continue;   // (nothing of this layer is kept)
+    hipLaunchKernelGGL((csr_topk_total_fill_kernel<U>), dim3(s.rows_grid), dim3(kBuildBlock), 0, stream, m,
+                       nonzeros[l], s.rows_per_wave, row_offsets[l], column_indices[l],
+                       static_cast<const U*>(values[l]), w.threshold, q, out_offsets[l], capacity[l], out_columns[l],
+                       static_cast<U*>(out_values[l]), out_source[l]);
+  }
   return launch_status();
 }
 
@@ -1645,6 +1850,103 @@ int sputnik_hip_csr_topk(int m, int n, int nonzeros, const int* row_offsets, con
   }
   if (out_row_indices == nullptr || m == 0) return launch_status();
   return sputnik_hip_csr_row_order(1, m, n, out_row_offsets, out_row_indices, stream_);
+}
+
+int sputnik_hip_csr_topk_global_launch_shape(int layers, const int* rows, const int* nonzeros, int value_bytes,
+                                             int* served, int* digit_passes, int* layers_per_launch,
+                                             int* elements_per_workgroup, int* digit_launches) {
+  const GlobalTopkShape g = global_topk_shape(layers, rows, nonzeros, value_bytes);
+  if (g.status != 0) return g.status;
+  if (served) *served = g.served;
+  if (digit_passes) *digit_passes = g.digit_passes;
+  if (layers_per_launch) *layers_per_launch = g.layers_per_launch;
+  if (elements_per_workgroup) *elements_per_workgroup = g.elements_per_workgroup;
+  if (digit_launches) *digit_launches = g.digit_launches;
+  return 0;
+}
+
+size_t sputnik_hip_csr_topk_global_workspace_bytes(int layers, const int* rows) {
+  if (layers < 0 || (layers > 0 && rows == nullptr)) return 0;
+  int64_t all = 0;
+  for (int l = 0; l < layers; ++l) {
+    if (rows[l] < 0) return 0;
+    all += rows[l];
+  }
+  return sizeof(unsigned) * global_topk_workspace_words(all);
+}
+
+int sputnik_hip_csr_topk_global_select(int layers, const int* rows, const int* nonzeros,
+                                       const int* const* row_offsets, const void* const* values, int value_bytes,
+                                       int64_t count, void* workspace, size_t workspace_bytes,
+                                       int* const* out_row_offsets, int* out_nonzeros, sputnik_hip_stream_t stream_) {
+  const GlobalTopkShape g = global_topk_shape(layers, rows, nonzeros, value_bytes);
+  if (g.status != 0) return g.status;
+  if (!g.served || count < 0 || count > g.entries) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (layers == 0) return 0;
+  if (row_offsets == nullptr || values == nullptr || out_row_offsets == nullptr || out_nonzeros == nullptr ||
+      !aligned_to(out_nonzeros, sizeof(int)) || workspace == nullptr || !aligned_to(workspace, sizeof(unsigned)) ||
+      workspace_bytes < sizeof(unsigned) * global_topk_workspace_words(g.rows))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  for (int l = 0; l < layers; ++l)
+    if (out_row_offsets[l] == nullptr || !aligned_to(out_row_offsets[l], sizeof(int)) ||
+        (rows[l] > 0 && (row_offsets[l] == nullptr || !aligned_to(row_offsets[l], sizeof(int)))) ||
+        (nonzeros[l] > 0 && (values[l] == nullptr || !aligned_to(values[l], value_bytes))))
+      return SPUTNIK_HIP_INVALID_ARGUMENT;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  return value_bytes == 2 ? launch_global_select<uint16_t>(g, layers, rows, nonzeros, row_offsets, values,
+                                                           static_cast<unsigned>(count), workspace,
+                                                           out_row_offsets, out_nonzeros, stream)
+                          : launch_global_select<uint32_t>(g, layers, rows, nonzeros, row_offsets, values,
+                                                           static_cast<unsigned>(count), workspace,
+                                                           out_row_offsets, out_nonzeros, stream);
+}
+
+int sputnik_hip_csr_topk_global_fill(int layers, const int* rows, const int* nonzeros,
+                                     const int* const* row_offsets, const int* const* column_indices,
+                                     const void* const* values, int value_bytes, void* workspace,
+                                     size_t workspace_bytes, const int64_t* out_capacity,
+                                     int* const* out_row_indices, int* const* out_row_offsets,
+                                     int* const* out_column_indices, void* const* out_values,
+                                     int64_t* const* out_source, sputnik_hip_stream_t stream_) {
+  const GlobalTopkShape g = global_topk_shape(layers, rows, nonzeros, value_bytes);
+  if (g.status != 0) return g.status;
+  if (!g.served) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  if (layers == 0) return 0;
+  if (row_offsets == nullptr || column_indices == nullptr || values == nullptr || out_capacity == nullptr ||
+      out_row_indices == nullptr || out_row_offsets == nullptr || out_column_indices == nullptr ||
+      out_values == nullptr || out_source == nullptr || workspace == nullptr ||
+      !aligned_to(workspace, sizeof(unsigned)) ||
+      workspace_bytes < sizeof(unsigned) * global_topk_workspace_words(g.rows))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  for (int l = 0; l < layers; ++l) {
+    if (out_capacity[l] < 0 || out_capacity[l] > nonzeros[l] || out_row_offsets[l] == nullptr ||
+        !aligned_to(out_row_offsets[l], sizeof(int)) ||
+        (rows[l] > 0 && (out_row_indices[l] == nullptr || !aligned_to(out_row_indices[l], sizeof(int)))))
+      return SPUTNIK_HIP_INVALID_ARGUMENT;
+    if (rows[l] > 0 && out_capacity[l] > 0 &&
+        (row_offsets[l] == nullptr || !aligned_to(row_offsets[l], sizeof(int)) || column_indices[l] == nullptr ||
+         !aligned_to(column_indices[l], sizeof(int)) || values[l] == nullptr ||
+         !aligned_to(values[l], value_bytes) || out_column_indices[l] == nullptr ||
+         !aligned_to(out_column_indices[l], sizeof(int)) || out_values[l] == nullptr ||
+         !aligned_to(out_values[l], value_bytes) || out_source[l] == nullptr ||
+         !aligned_to(out_source[l], sizeof(int64_t))))
+      return SPUTNIK_HIP_INVALID_ARGUMENT;
+  }
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int st = value_bytes == 2
+                     ? launch_global_fill<uint16_t>(layers, rows, nonzeros, row_offsets, column_indices, values,
+                                                    workspace, out_capacity, out_row_offsets, out_column_indices,
+                                                    out_values, out_source, stream)
+                     : launch_global_fill<uint32_t>(layers, rows, nonzeros, row_offsets, column_indices, values,
+                                                    workspace, out_capacity, out_row_offsets, out_column_indices,
+                                                    out_values, out_source, stream);
+  if (st != 0) return st;
+  for (int l = 0; l < layers; ++l)
+    if (rows[l] > 0) {
+      const int order = sputnik_hip_csr_row_order(1, rows[l], 0, out_row_offsets[l], out_row_indices[l], stream_);
+      if (order != 0) return order;
+    }
+  return launch_status();
 }
 
 }  // extern "C"

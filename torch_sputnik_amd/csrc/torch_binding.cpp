@@ -2194,6 +2194,116 @@ std::vector<Tensor> csr_topk(const Tensor& values_in, const Tensor& row_offsets_
   return {out_row_indices, out_row_offsets, out_columns, out_values, source};
 }
 
+// Several CSR patterns (lists of equal length: values[l] [nnz_l], row_offsets[l] [m_l + 1],
+// column_indices[l] [nnz_l]) -> for every layer, one after the other, [row_indices, row_offsets,
+// column_indices, values, source (int64)] of what it keeps when the `total` entries of largest
+// |value| over ALL layers stay: sputnik_hip.h: sputnik_hip_csr_topk_global_*.  The layers' new
+// sizes are read back once -- the ONE synchronisation, whatever the number of layers --
+// between the select half and the fill half.
+std::vector<Tensor> csr_topk_global(at::TensorList values_in, at::TensorList row_offsets_in,
+                                    at::TensorList column_indices_in, int64_t total) {
+  const size_t count_layers = values_in.size();
+  TORCH_CHECK(row_offsets_in.size() == count_layers && column_indices_in.size() == count_layers,
+              "csr_topk_global: ", count_layers, " values, ", row_offsets_in.size(), " row_offsets and ",
+              column_indices_in.size(), " column_indices");
+  if (count_layers == 0) {
+    TORCH_CHECK(total == 0, "torch_sputnik::csr_topk_global: ", total, " entries asked of 0");
+    return {};
+  }
+  const int layers = to_int(static_cast<int64_t>(count_layers), "layers");
+  const auto device = values_in[0].device();
+  const auto type = values_in[0].scalar_type();
+  TORCH_CHECK(values_in[0].is_cuda(), "values must be GPU (HIP) tensors, got ", device);
+  TORCH_CHECK(type == at::kFloat || type == at::kHalf || type == at::kBFloat16,
+              "values must be float32, float16 or bfloat16, got ", type);
+  std::vector<Tensor> values, row_offsets, column_indices;
+  std::vector<int> rows(layers), nonzeros(layers);
+  int64_t entries = 0;
+  for (int l = 0; l < layers; ++l) {
+    for (const Tensor* t : {&values_in[l], &row_offsets_in[l], &column_indices_in[l]})
+      TORCH_CHECK(t->device() == device, "every tensor must be on ", device, ", got ", t->device(), " in layer ", l);
+    for (const Tensor* t : {&row_offsets_in[l], &column_indices_in[l]})
+      TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1, "row_offsets and column_indices must be 1-D "
+                  "int32 tensors, got ", t->scalar_type(), " ", t->sizes(), " in layer ", l);
+    TORCH_CHECK(values_in[l].scalar_type() == type, "values must be of one dtype, got ", type, " and ",
+                values_in[l].scalar_type());
+    TORCH_CHECK(row_offsets_in[l].numel() >= 1, "row_offsets should be [m + 1], got ", row_offsets_in[l].sizes());
+    TORCH_CHECK(values_in[l].dim() == 1 && values_in[l].numel() == column_indices_in[l].numel(),
+                "values should be [nnz] like column_indices ", column_indices_in[l].sizes(), ", got ",
+                values_in[l].sizes(), " in layer ", l);
+    values.push_back(values_in[l].contiguous());
+    row_offsets.push_back(row_offsets_in[l].contiguous());
+    column_indices.push_back(column_indices_in[l].contiguous());
+    rows[l] = to_int(row_offsets[l].numel() - 1, "m");
+    nonzeros[l] = to_int(values[l].numel(), "nnz");
+    entries += nonzeros[l];
+  }
+  const c10::DeviceGuard guard(device);
+  const int value_bytes = static_cast<int>(values[0].element_size());
+  int served = 0;
+  check_status(sputnik_hip_csr_topk_global_launch_shape(layers, rows.data(), nonzeros.data(), value_bytes, &served,
+                                                        nullptr, nullptr, nullptr, nullptr),
+               "csr_topk_global");
+  TORCH_CHECK(served, "torch_sputnik::csr_topk_global: a layer of more rows than the row-order kernel serves, or "
+              "more entries than int32 holds (sputnik_hip_csr_topk_global_launch_shape); take "
+              "topology.prune_csr_global");
+  TORCH_CHECK(total >= 0 && total <= entries, "torch_sputnik::csr_topk_global: ", total, " entries asked of ",
+              entries);
+  const auto index_options = row_offsets[0].options();
+  std::vector<Tensor> out_row_indices, out_row_offsets;
+  std::vector<const int*> offsets_in(layers), columns_in(layers);
+  std::vector<const void*> values_ptr(layers);
+  std::vector<int*> order_out(layers), offsets_out(layers);
+  for (int l = 0; l < layers; ++l) {
+    out_row_offsets.push_back(at::empty({rows[l] + 1}, index_options));
+    out_row_indices.push_back(at::empty({rows[l]}, index_options));
+    offsets_in[l] = row_offsets[l].data_ptr<int>();
+    columns_in[l] = column_indices[l].data_ptr<int>();
+    values_ptr[l] = values[l].data_ptr();
+    offsets_out[l] = out_row_offsets[l].data_ptr<int>();
+    order_out[l] = out_row_indices[l].data_ptr<int>();
+  }
+  const size_t ws_bytes = sputnik_hip_csr_topk_global_workspace_bytes(layers, rows.data());
+  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, values[0].options().dtype(at::kByte));
+  Tensor sizes = at::empty({layers}, index_options);
+  const auto stream = current_stream(values[0]);
+  check_status(sputnik_hip_csr_topk_global_select(layers, rows.data(), nonzeros.data(), offsets_in.data(),
+                                                  values_ptr.data(), value_bytes, total, workspace.data_ptr(),
+                                                  ws_bytes, offsets_out.data(), sizes.data_ptr<int>(), stream),
+               "csr_topk_global (select)");
+  const Tensor host_sizes = sizes.cpu();   // the synchronisation
+  const int* kept = host_sizes.data_ptr<int>();
+  std::vector<int64_t> capacity(layers);
+  std::vector<int*> columns_out(layers);
+  std::vector<void*> values_out(layers);
+  std::vector<int64_t*> source_out(layers);
+  std::vector<Tensor> result;
+  result.reserve(5 * count_layers);
+  int64_t kept_all = 0;
+  for (int l = 0; l < layers; ++l) {
+    TORCH_CHECK(kept[l] >= 0 && kept[l] <= nonzeros[l], "torch_sputnik::csr_topk_global: row_offsets of layer ", l,
+                " do not ascend inside 0 .. ", nonzeros[l]);
+    capacity[l] = kept[l];
+    kept_all += kept[l];
+    Tensor out_columns = at::empty({capacity[l]}, index_options);
+    Tensor out_values = at::empty({capacity[l]}, values[l].options());
+    Tensor source = at::empty({capacity[l]}, index_options.dtype(at::kLong));
+    columns_out[l] = out_columns.data_ptr<int>();
+    values_out[l] = out_values.data_ptr();
+    source_out[l] = source.data_ptr<int64_t>();
+    result.insert(result.end(), {out_row_indices[l], out_row_offsets[l], out_columns, out_values, source});
+  }
+  TORCH_CHECK(kept_all == total, "torch_sputnik::csr_topk_global: the layers keep ", kept_all, " entries, not ",
+              total, ": row_offsets do not describe the values");
+  check_status(sputnik_hip_csr_topk_global_fill(layers, rows.data(), nonzeros.data(), offsets_in.data(),
+                                                columns_in.data(), values_ptr.data(), value_bytes,
+                                                workspace.data_ptr(), ws_bytes, capacity.data(), order_out.data(),
+                                                offsets_out.data(), columns_out.data(), values_out.data(),
+                                                source_out.data(), stream),
+               "csr_topk_global (fill)");
+  return result;
+}
+
 // ---- the fused attention with one mask per batch element (sputnik_hip.h:
 // sparse_attention_many_mask_*, sparse_attention_heads_many_mask_*) ----
 
@@ -2643,6 +2753,7 @@ TORCH_LIBRARY(torch_sputnik, m) {
   m.def("csr_regrow(Tensor values, Tensor row_offsets, Tensor column_indices, Tensor drop_counts, "
         "Tensor scores) -> Tensor[]");
   m.def("csr_topk(Tensor values, Tensor row_offsets, Tensor column_indices, int per_row, int total) -> Tensor[]");
+  m.def("csr_topk_global(Tensor[] values, Tensor[] row_offsets, Tensor[] column_indices, int total) -> Tensor[]");
   m.def(
       "sparse_attention_many_mask(int b, Tensor nonzeros, Tensor query, Tensor key, Tensor value, "
       "Tensor row_indices, Tensor row_offsets, Tensor column_indices, float scale, bool want_lse, "
@@ -2746,6 +2857,7 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("topk_to_csr", &topk_to_csr);
   m.impl("csr_regrow", &csr_regrow);
   m.impl("csr_topk", &csr_topk);
+  m.impl("csr_topk_global", &csr_topk_global);
   m.impl("sparse_attention_many_mask", &sparse_attention_many_mask);
   m.impl("sparse_attention_many_mask_plan", &sparse_attention_many_mask_plan);
   m.impl("sparse_attention_heads_many_mask", &sparse_attention_heads_many_mask);

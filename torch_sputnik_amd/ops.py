@@ -445,6 +445,53 @@ def csr_topk(values, row_offsets, column_indices, per_row=None, total=None):
                                -1 if total is None else count))
 
 
+def check_csr_topk_global_arguments(values, row_offsets, column_indices, total):
+    """ValueError unless the three are sequences of one length whose l-th elements are one CSR
+    pattern with its values (``check_csr_topk_arguments``), every tensor is on one device and
+    ``total`` is a count within 0 .. sum nnz_l.  -> the count.  The dtypes of the values are the
+    caller's matter."""
+    values, row_offsets, column_indices = list(values), list(row_offsets), list(column_indices)
+    if not len(values) == len(row_offsets) == len(column_indices):
+        raise ValueError(f"csr_topk_global: {len(values)} values, {len(row_offsets)} row_offsets and "
+                         f"{len(column_indices)} column_indices")
+    if total is None:
+        raise ValueError("csr_topk_global: total is missing")
+    for v, ro, ci in zip(values, row_offsets, column_indices):
+        check_csr_topk_arguments(v, ro, ci, None, 0)
+        if v.device != values[0].device:
+            raise ValueError(f"csr_topk_global: values are on {values[0].device} and on {v.device}")
+    entries = sum(v.numel() for v in values)
+    count = int(total)
+    if not 0 <= count <= entries:
+        raise ValueError(f"csr_topk_global: total = {count} is outside 0 .. {entries}")
+    return count
+
+
+def csr_topk_global(values, row_offsets, column_indices, total):
+    """ONE top-k across the entries of several CSR patterns on the device (csrc/topology.hip):
+    three lists of equal length -- values[l] [nnz_l] (float32 / float16 / bfloat16, one dtype for
+    all), row_offsets[l] [m_l + 1] and column_indices[l] [nnz_l] (int32) -- of which the
+    ``total = K`` entries of largest ``|value|`` over ALL layers are kept
+    (``topology.magnitude_keys``); among equal magnitudes the layer listed first wins, then the
+    lower entry index.  -> a list of (row_indices, row_offsets, column_indices, values, source),
+    one per layer, as ``csr_topk`` returns them; a layer may keep nothing.  The layers' new
+    sizes are read back once, whatever their number.  Raises for CPU tensors, mixed dtypes, a
+    layer of more rows than ``capi.csr_topk_global_launch_shape`` serves (16384) and more than
+    2**31 - 1 entries in all."""
+    count = check_csr_topk_global_arguments(values, row_offsets, column_indices, total)
+    values, row_offsets, column_indices = list(values), list(row_offsets), list(column_indices)
+    if not values:
+        return []
+    for v in values:
+        if v.dtype not in _TOPK_DTYPES or v.dtype != values[0].dtype:
+            raise ValueError(f"csr_topk_global: values must be float32, float16 or bfloat16 and of one dtype, got "
+                             f"{values[0].dtype} and {v.dtype}")
+    if not values[0].is_cuda:
+        raise RuntimeError("csr_topk_global: GPU tensors only (topology.prune_csr_global serves CPU tensors)")
+    flat = _ops.csr_topk_global(values, row_offsets, column_indices, count)
+    return [tuple(flat[5 * l:5 * l + 5]) for l in range(len(values))]
+
+
 def sparse_attention_many_mask(b, nonzeros, row_indices, row_offsets, column_indices, query, key,
                                value, scale, with_lse=False, plan=None):
     """softmax(scale * q k^T at the mask) v with one mask per batch element in ONE kernel:

@@ -316,6 +316,127 @@ def prune_csr(values, row_offsets, column_indices, n, per_row=None, total=None):
     return (diffsort(new_offsets), new_offsets, column_indices[source], _take_bits(values, source), source)
 
 
+_INT_MAX = 2 ** 31 - 1
+
+
+def _csr_topk_global_served(values, row_offsets):
+    first = values[0]
+    if not (_device_build and first.is_cuda and first.dtype in _TOPK_DTYPES):
+        return False
+    if any(v.device != first.device or v.dtype != first.dtype for v in values):
+        return False
+    rows, nonzeros = [ro.numel() - 1 for ro in row_offsets], [v.numel() for v in values]
+    if max(rows) > _INT_MAX or sum(nonzeros) > _INT_MAX:
+        return False
+    return capi.csr_topk_global_launch_shape(rows, nonzeros, first.element_size())["served"]
+
+
+def prune_csr_global(layers, total):
+    """Global magnitude pruning: ONE top-k across the entries of several CSR patterns.
+    ``layers`` is a sequence of ``(values, row_offsets, column_indices, n)`` -- the pattern of an
+    ``m_l x n_l`` matrix as ``prune_csr`` takes it -- and ``total = K`` (``0 <= K <= sum nnz_l``)
+    keeps the K entries of largest key over all layers (``magnitude_keys``: NaN above inf, -0.0
+    with 0.0).  Among equal keys the entry of the layer listed first wins, then the lower entry
+    index.
+
+    -> a list with one ``(row_indices, row_offsets, column_indices, values, source)`` per layer,
+    new tensors, as ``prune_csr`` returns them: a kept entry carries its column, its value bit
+    for bit and, in ``source`` (int64, ascending), its index in the layer's old arrays.  A layer
+    may end with no entry at all.  One layer gives ``prune_csr(..., total=K)``.
+
+    Values on one GPU and of one dtype among float32 / float16 / bfloat16 take the device
+    kernels (``ops.csr_topk_global``: the digit passes of a radix select walk all layers into one
+    set of bins; the layers' new sizes are read back once) while every layer has at most 16384
+    rows and the layers hold at most 2**31 - 1 entries together.  CPU tensors, other or mixed
+    dtypes (every layer ranked as ``.float()`` then), more rows and
+    ``enable_device_build(False)`` take the same rule in torch for the whole call: the keys of
+    all layers in one array, one stable descending argsort, the first K split at the layer
+    boundaries.  Both give the same integers and value bits."""
+    layers = [tuple(layer) for layer in layers]
+    for layer in layers:
+        if len(layer) != 4:
+            raise ValueError("prune_csr_global: a layer is (values, row_offsets, column_indices, n), got "
+                             f"{len(layer)} elements")
+    values = [layer[0].detach() for layer in layers]
+    row_offsets, column_indices = [layer[1] for layer in layers], [layer[2] for layer in layers]
+    count = ops.check_csr_topk_global_arguments(values, row_offsets, column_indices, total)
+    if not layers:
+        return []
+    if _csr_topk_global_served(values, row_offsets):
+        return ops.csr_topk_global(values, row_offsets, column_indices, count)
+    native = values[0].dtype in _TOPK_DTYPES and all(v.dtype == values[0].dtype for v in values)
+    keys = torch.cat([magnitude_keys(v if native else v.float()) for v in values])
+    order = torch.argsort(keys, descending=True, stable=True)   # key descending, then layer, then index
+    kept = torch.sort(order[:count]).values
+    sizes = [v.numel() for v in values]
+    bounds = torch.tensor([0] + sizes, dtype=torch.int64).cumsum(0)
+    cuts = torch.searchsorted(kept, bounds.to(kept.device)).tolist()   # the one read of the new sizes
+    results = []
+    for l, v in enumerate(values):
+        source = kept[cuts[l]:cuts[l + 1]] - int(bounds[l])
+        m = row_offsets[l].numel() - 1
+        lengths = (row_offsets[l][1:] - row_offsets[l][:-1]).to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(m, dtype=torch.int64, device=v.device), lengths,
+                                       output_size=sizes[l])
+        new_offsets = torch.zeros(m + 1, dtype=torch.int32, device=v.device)
+        new_offsets[1:] = torch.cumsum(torch.bincount(rows[source], minlength=m), 0)
+        results.append((diffsort(new_offsets), new_offsets, column_indices[l][source], _take_bits(v, source), source))
+    return results
+
+
+def prune_layers_to(modules, density=None, nonzeros=None, optimizer=None):
+    """One step of GLOBAL magnitude pruning over a list of ``SparseLinear``: the layers' values
+    are ranked together and the K of largest ``|values|`` over all of them stay
+    (``prune_csr_global``; ties to the layer listed first, then to the lower entry index).
+    ``density`` is a share of all positions, ``K = round(density * sum out_l * in_l)``;
+    ``nonzeros`` is K itself.  Give exactly one of the two.
+
+    ``K`` at or above the current number of entries changes nothing: the same Parameters, every
+    ``source = arange(nnz_l)``.  Otherwise EVERY listed layer gets a new, shorter ``values``
+    ``nn.Parameter`` (the old one's ``requires_grad``, no ``.grad``), kept entries bit for bit,
+    and new index tensors (the old ones are unregistered, never written to, the new ones
+    registered as static) -- also a layer that happened to keep all its entries.
+    Global pruning can EMPTY a layer: nothing keeps a layer of small weights from losing every
+    entry; its forward pass then returns zeros.  ``dense_grad`` is left alone.
+
+    A dense model enters the same way: ``SparseLinear.from_dense(weight, density=1.0)`` per
+    layer, then this call -- there is no separate dense variant.
+
+    Returns the list of ``source`` tensors, int64 ``[new nnz_l]``, ascending: for every new
+    entry its index in the layer's old ``values``.  With ``optimizer=`` the state of every
+    layer's old Parameter is handed to the new one (``remap_optimizer_state``)."""
+    from torch import nn
+
+    from . import functional
+    modules = list(modules)
+    if (density is None) == (nonzeros is None):
+        raise ValueError("prune_layers_to: give exactly one of density / nonzeros")
+    most = sum(module.output_features * module.input_features for module in modules)
+    if density is not None:
+        if not 0.0 <= density <= 1.0:
+            raise ValueError(f"prune_layers_to: density {density} is outside 0 .. 1")
+        nonzeros = round(density * most)
+    count = int(nonzeros)
+    if not 0 <= count <= most:
+        raise ValueError(f"prune_layers_to: {count} entries asked of {most}")
+    olds = [module.values for module in modules]
+    if count >= sum(old.numel() for old in olds):
+        return [torch.arange(old.numel(), dtype=torch.int64, device=old.device) for old in olds]
+    with torch.no_grad():
+        results = prune_csr_global(
+            [(old.detach(), module.row_offsets, module.column_indices, module.input_features)
+             for old, module in zip(olds, modules)], count)
+        sources = []
+        for module, old, (row_indices, row_offsets, column_indices, values, source) in zip(modules, olds, results):
+            functional.unregister_static_topology(module.row_indices, module.row_offsets, module.column_indices)
+            module._set_topology(nn.Parameter(values, requires_grad=old.requires_grad), row_indices, row_offsets,
+                                 column_indices)
+            if optimizer is not None:
+                remap_optimizer_state(optimizer, old, module.values, source)
+            sources.append(source)
+    return sources
+
+
 def gradual_density(step, begin_step, end_step, initial_density, final_density):
     """The density at ``step`` of the cubic schedule of gradual magnitude pruning (Zhu & Gupta,
     "To prune, or not to prune", 2017): ``d_f + (d_i - d_f) * (1 - (t - t0) / (t1 - t0)) ** 3``
