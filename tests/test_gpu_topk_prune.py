@@ -300,6 +300,30 @@ def test_reproducible():
     check(device.cpu(), per_row=110)
 
 
+def test_total_mode_is_capturable():
+    """Total mode neither synchronises nor reads back, its allocations are torch's own per call
+    and every launch is a kernel (the bins are cleared by one, not by a memset): it is captured
+    into a graph on a side stream, and each replay on new scores in the captured buffer equals
+    the eager call."""
+    generator = torch.Generator().manual_seed(2035)
+    m, n = 70, 300
+    K = m * n // 3
+    scores = random_scores(m, n, torch.float32, generator).cuda()
+    ops.topk_to_csr(scores, total=K)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        captured = ops.topk_to_csr(scores, total=K)
+    for _ in range(2):
+        fresh = random_scores(m, n, torch.float32, generator)
+        scores.copy_(fresh)
+        graph.replay()
+        torch.cuda.synchronize()
+        eager = check(fresh, total=K, device=scores)        # eager op == the torch path on the CPU tensor
+        for c, e in zip(captured, eager):
+            assert c.dtype == e.dtype and c.shape == e.shape and torch.equal(bits_of(c), bits_of(e))
+
+
 # ---- the modules ----
 
 OUT, IN, BATCH, SEQ = 64, 96, 2, 8

@@ -3,28 +3,39 @@
 // selections that write one out: sputnik_hip_topk_to_csr, sputnik_hip_csr_regrow, sputnik_hip_csr_topk,
 // sputnik_hip_csr_topk_global_*.
 //
-// Replaces the torch loop of topology.dense_to_sparse_3d (per mask: != 0, to_sparse_csr, two
-// casts, a stable argsort and a host read of the count) by a fixed number of launches for any
-// number of masks:
+// The build replaces the torch loop of topology.dense_to_sparse_3d (per mask: != 0,
+// to_sparse_csr, two casts, a stable argsort and a host read of the count) by a fixed number of
+// launches for any number of masks:
 //   count   one GROUP of lanes per row walks the row and counts the kept elements; the counts
 //           land in row_offsets[mask][row + 1]
 //   scan    one workgroup per mask: in-place inclusive scan of those counts = the offsets;
 //           row_offsets[mask][0] = 0, nonzeros[mask] = the last one
 //   bases   one workgroup: bases[mask] = entries of the masks in front (64 bit)
 //   fill    the same walk as count; a kept element's slot is its row's offset + the kept
-//           elements of the row in front of it (wave ballot + lane prefix count)
+//           elements of the row in front of it
 //   order   one workgroup per mask sorts the unique keys (length, row) in LDS
 // An element is kept exactly when torch's `x != 0` says so, decided on the BITS: any bit set
 // for integer / bool types, any bit but the sign for floating types (-0.0 goes, NaN, +-inf and
 // denormals stay whatever the denormal mode of the float unit is).
 //
-// The walk: a lane loads 16 bytes = V elements (V = 16 / element bytes) and a group of
-// 64 / rows_per_wave lanes covers group_lanes * V consecutive columns per step.  The 16-byte
-// pieces are laid out from the row start's address ROUNDED DOWN to 16 bytes, so that every
-// piece that lies inside the row is one aligned wide load whatever the row start is (odd n
-// with a 1-byte type, a sliced view); the at most two pieces per row that stick out of it are
-// read element by element, inside the row only.  Nothing outside [row start, row start + n)
-// is ever read.
+// The build and every selection are made of the same parts, each written once:
+//   RowGroup       the lanes of a wave that share a row: 64 / rows_per_wave of them, their mask
+//                  in the wave's ballots, a lane's share of the row's 256 bins
+//   load_piece     a lane loads 16 bytes = V elements (V = 16 / element bytes).  The pieces are
+//                  laid out from the array start's address ROUNDED DOWN to 16 bytes, so that
+//                  every piece that lies inside the array is one aligned wide load whatever the
+//                  start is (odd n with a 1-byte type, a sliced view); the at most two pieces
+//                  that stick out of it are read element by element, inside the array only.
+//                  Nothing outside [start, start + n) is ever read.
+//   RowWalk        a group covers group_lanes * V consecutive columns per step; made over a
+//                  dense row (the constructor) or over the entries of a CSR row (entry_walk)
+//   radix_select   the need-th largest key of a group's row, MSB first, 8-bit digits, a 256-bin
+//                  histogram per row in LDS filled by the caller's step (count_digit per key)
+//   group_prefix   the flagged elements of a step in front of a lane's piece and in the whole
+//                  step: one wave ballot per element slot and a lane-prefix count
+//   admit_ties     the first `quota` elements equal to the threshold join the flags, the tie
+//                  count is carried across the steps of the row
+//   thread_span, inclusive_scan_span   a 1024-thread workgroup's scan over any number of items
 #include <limits.h>
 
 #include <type_traits>
@@ -40,6 +51,11 @@ constexpr int kBuildWaves = kBuildBlock / kWave;
 constexpr int kLoadBytes = 16;
 constexpr int kMaxRowsPerWave = 16;   // groups of 4 lanes
 constexpr int kScanBlock = 1024;
+constexpr int kDigitBits = 8;
+constexpr int kDigitBins = 1 << kDigitBits;
+constexpr int kMaxDigitPasses = 4;
+constexpr unsigned kNoThreshold = 0xffffffffu;   // above every key: nothing is kept by it
+static_assert(kDigitBins == kBuildBlock, "one thread per bin when a workgroup merges its histogram");
 
 // The host's launch decisions for count and fill: both entries launch what this returns,
 // sputnik_hip_dense_to_csr_launch_shape reports it.
@@ -68,82 +84,287 @@ inline BuildShape build_shape(int masks, int m, int n, int element_bytes) {
   return s;
 }
 
+// ---------------------------------------------------------------------------
+// The shared parts.
+// ---------------------------------------------------------------------------
+// The group of lanes of one row: workgroup `block` of a matrix serves the rows from
+// block * kBuildWaves * rows_per_wave, one per group, wave after wave.
+struct RowGroup {
+  int lane, wave, group_lanes, group, group_lane;
+  int slot;   // the group's place in the workgroup
+  int64_t row;
+  unsigned long long group_mask, below;   // my group's lanes in a ballot; those of them in front of me
+
+  __device__ __forceinline__ explicit RowGroup(int rows_per_wave, int block = blockIdx.x) {
+    lane = threadIdx.x % kWave;
+    wave = threadIdx.x / kWave;
+    group_lanes = kWave / rows_per_wave;
+    group = lane / group_lanes;
+    group_lane = lane % group_lanes;
+    slot = wave * rows_per_wave + group;
+    row = (static_cast<int64_t>(block) * kBuildWaves + wave) * rows_per_wave + group;
+    group_mask = (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
+    below = group_mask & ((1ull << lane) - 1ull);
+  }
+  // A lane owns the `chunk` consecutive bins from `base` of its row's 256: 4 .. 256 of them.
+  __device__ __forceinline__ int chunk() const { return kDigitBins / group_lanes; }
+  __device__ __forceinline__ int base() const { return group_lane * chunk(); }
+};
+
 template <typename U>
 struct alignas(kLoadBytes) Piece {
   U e[kLoadBytes / sizeof(U)];
 };
 
-// FILL = false: row_offsets[mask][row + 1] = kept elements of the row.
-// FILL = true:  the kept columns (and, VALUES, the kept elements) of the row go to
-//               bases[mask] + row_offsets[mask][row] onwards, ascending.
-template <typename U, bool FILL, bool VALUES>
-__global__ __launch_bounds__(kBuildBlock) void topology_rows_kernel(
-    int m, int n, int rows_per_wave, int blocks_per_mask, const U* __restrict__ dense,
-    int64_t batch_stride, int64_t row_stride, U keep, int* __restrict__ row_offsets,
-    const int64_t* __restrict__ bases, int* __restrict__ column_indices, U* __restrict__ values) {
+// The 16-byte piece whose first element is src[c0], of an array of n elements: one wide load
+// where it lies inside the array, else element by element, inside the array only.  *valid: a
+// bit per element that lies inside the array (the others read as 0 and are not loaded).  A lane
+// for which the array is not `there` loads nothing.
+template <typename U>
+__device__ __forceinline__ Piece<U> load_piece(const U* __restrict__ src, int64_t c0, int64_t n, unsigned* valid,
+                                               bool there = true) {
   constexpr int V = kLoadBytes / sizeof(U);
-  const int mask = blockIdx.x / blocks_per_mask;
-  const int block = blockIdx.x % blocks_per_mask;
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  const int group_lanes = kWave / rows_per_wave;
-  const int group = lane / group_lanes, group_lane = lane % group_lanes;
-  const int64_t row = (static_cast<int64_t>(block) * kBuildWaves + wave) * rows_per_wave + group;
-  const bool live = row < m;
-  const unsigned long long group_mask =
-      (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
-  const unsigned long long below = group_mask & ((1ull << lane) - 1ull);   // my group's lanes in front of me
-
-  const U* __restrict__ src = dense + (live ? mask * batch_stride + row * row_stride : int64_t{0});
-  // elements between the 16-byte boundary at or in front of the row start and the row start
-  const int lead = live ? static_cast<int>((reinterpret_cast<uintptr_t>(src) % kLoadBytes) / sizeof(U)) : 0;
-  const bool any_lead = __ballot(lead != 0) != 0ull;
-  const int64_t span = static_cast<int64_t>(group_lanes) * V;
-  const int steps = static_cast<int>((static_cast<int64_t>(n) + (any_lead ? V - 1 : 0) + span - 1) / span);
-
-  int64_t out = 0;
-  if constexpr (FILL) {
-    if (live) out = bases[mask] + row_offsets[mask * (int64_t{1} + m) + row];
-  }
-  int count = 0;
-  for (int s = 0; s < steps; ++s) {
-    const int64_t c0 = (static_cast<int64_t>(s) * group_lanes + group_lane) * V - lead;   // my piece's first column
-    Piece<U> v;
-    if (live && c0 >= 0 && c0 + V <= n) {
-      v = *reinterpret_cast<const Piece<U>*>(src + c0);
-    } else {
+  Piece<U> v;
+  if (there && c0 >= 0 && c0 + V <= n) {
+    v = *reinterpret_cast<const Piece<U>*>(src + c0);
+    *valid = (1u << V) - 1u;
+  } else {
+    unsigned in = 0;
 #pragma unroll
-      for (int e = 0; e < V; ++e) v.e[e] = live && c0 + e >= 0 && c0 + e < n ? src[c0 + e] : U{0};
+    for (int e = 0; e < V; ++e) {
+      const bool inside = there && c0 + e >= 0 && c0 + e < n;
+      v.e[e] = inside ? src[c0 + e] : U{0};
+      in |= (inside ? 1u : 0u) << e;
     }
-    unsigned flags = 0;
+    *valid = in;
+  }
+  return v;
+}
+
+// One group of lanes on one row of n elements from src.  A group without a row (live = false)
+// takes the steps and loads nothing.
+template <typename U>
+struct RowWalk {
+  static constexpr int V = kLoadBytes / sizeof(U);
+  const U* src;
+  bool live;
+  int n, lead, steps, group_lanes, group_lane;
+
+  __device__ __forceinline__ RowWalk() {}   // (entry_walk)
+  // Row g.row of a dense [m, n] matrix.  Every row of the wave takes the same steps: one more
+  // piece per row where any of them starts off a 16-byte boundary.
+  __device__ __forceinline__ RowWalk(const RowGroup& g, const U* dense, int64_t row_stride, int m, int n_) {
+    group_lanes = g.group_lanes;
+    group_lane = g.group_lane;
+    live = g.row < m;
+    n = n_;
+    src = dense + (live ? g.row * row_stride : int64_t{0});
+    // elements between the 16-byte boundary at or in front of the row start and the row start
+    lead = live ? static_cast<int>((reinterpret_cast<uintptr_t>(src) % kLoadBytes) / sizeof(U)) : 0;
+    const bool any_lead = __ballot(lead != 0) != 0ull;
+    const int64_t span = static_cast<int64_t>(group_lanes) * V;
+    steps = static_cast<int>((static_cast<int64_t>(n_) + (any_lead ? V - 1 : 0) + span - 1) / span);
+  }
+  // My piece of step s, its first column, and a bit per element that lies inside the row.
+  __device__ __forceinline__ Piece<U> load(int s, int64_t* first_column, unsigned* valid) const {
+    const int64_t c0 = (static_cast<int64_t>(s) * group_lanes + group_lane) * V - lead;
+    *first_column = c0;
+    return load_piece(src, c0, static_cast<int64_t>(n), valid, live);
+  }
+};
+
+// The slots [begin, end) of a row's entries, inside [0, nonzeros) whatever the offsets say.
+__device__ __forceinline__ void row_slots(const int* __restrict__ row_offsets, int64_t row, bool live, int nonzeros,
+                                          int* begin, int* end) {
+  *begin = 0;
+  *end = 0;
+  if (live) {
+    *begin = min(max(row_offsets[row], 0), nonzeros);
+    *end = min(max(row_offsets[row + 1], *begin), nonzeros);
+  }
+}
+
+// The walk of a group over the entries [begin, end) of its CSR row, like a dense row:
+// values + begin is the row start.  Every lane of the wave takes as many steps as the wave's
+// longest row needs (the ballots of a fill are the wave's).
+template <typename U>
+__device__ __forceinline__ RowWalk<U> entry_walk(const RowGroup& g, const U* __restrict__ values, int begin, int end,
+                                                 bool live) {
+  constexpr int V = kLoadBytes / sizeof(U);
+  RowWalk<U> w;
+  w.n = end - begin;
+  w.group_lanes = g.group_lanes;
+  w.group_lane = g.group_lane;
+  w.live = live;
+  w.src = values + begin;
+  w.lead = static_cast<int>((reinterpret_cast<uintptr_t>(w.src) % kLoadBytes) / sizeof(U));
+  const int64_t span = static_cast<int64_t>(w.group_lanes) * V;
+  int steps = static_cast<int>((static_cast<int64_t>(w.n) + w.lead + span - 1) / span);
+  for (int o = kWave / 2; o > 0; o >>= 1) steps = max(steps, __shfl_xor(steps, o, kWave));
+  w.steps = steps;
+  return w;
+}
+
+// An element's KEY: its bit pattern without the sign bit, read as an unsigned integer.
+template <typename U>
+__device__ __forceinline__ unsigned key_of(U bits) {
+  return static_cast<unsigned>(bits & static_cast<U>(static_cast<U>(~U{0}) >> 1));
+}
+
+// A bit per element of the piece whose key (at most key_limit) is above / equal to the threshold.
+template <typename U>
+__device__ __forceinline__ void compare_piece(const Piece<U>& v, unsigned threshold, unsigned key_limit,
+                                              unsigned* greater, unsigned* equal) {
+  unsigned above = 0, same = 0;
 #pragma unroll
-    for (int e = 0; e < V; ++e) flags |= ((v.e[e] & keep) != 0 ? 1u : 0u) << e;
-    if constexpr (!FILL) {
-      count += __popc(flags);
-    } else {
-      // the kept elements of the step in column order: lane after lane, element after element
-      // inside a lane.  One ballot per element slot = per 64 elements of the step.
-      int before = 0, total = 0;
+  for (int e = 0; e < static_cast<int>(kLoadBytes / sizeof(U)); ++e) {
+    const unsigned key = min(key_of(v.e[e]), key_limit);
+    above |= (key > threshold ? 1u : 0u) << e;
+    same |= (key == threshold ? 1u : 0u) << e;
+  }
+  *greater = above;
+  *equal = same;
+}
+
+// One key into the histogram of digit `shift / 8`, if it is counted and its higher digits
+// equal `prefix`.
+__device__ __forceinline__ void count_digit(unsigned key, bool counted, int shift, unsigned prefix,
+                                            unsigned* __restrict__ bins) {
+  // (64 bit: the first pass shifts everything out and compares with prefix 0)
+  if (counted && static_cast<unsigned>(static_cast<uint64_t>(key) >> (shift + kDigitBits)) == prefix)
+    atomicAdd(&bins[(key >> shift) & (kDigitBins - 1)], 1u);
+}
+
+// Histogram of digit `shift / 8` of the row's keys (at most key_limit) whose higher digits equal
+// `prefix`; open(first column) = a bit per element of the piece that takes part.
+template <typename U, typename Open>
+__device__ __forceinline__ void digit_histogram(const RowWalk<U>& walk, int shift, unsigned prefix,
+                                                unsigned* __restrict__ bins, unsigned key_limit, Open open) {
+  for (int s = 0; s < walk.steps; ++s) {
+    int64_t c0;
+    unsigned valid;
+    const Piece<U> v = walk.load(s, &c0, &valid);
+    const unsigned counted = valid & open(c0);
 #pragma unroll
-      for (int e = 0; e < V; ++e) {
-        const unsigned long long b = __ballot((flags >> e) & 1u);
-        before += __popcll(b & below);
-        total += __popcll(b & group_mask);
+    for (int e = 0; e < RowWalk<U>::V; ++e)
+      count_digit(min(key_of(v.e[e]), key_limit), (counted >> e) & 1u, shift, prefix, bins);
+  }
+}
+template <typename U>
+__device__ __forceinline__ void digit_histogram(const RowWalk<U>& walk, int shift, unsigned prefix,
+                                                unsigned* __restrict__ bins) {
+  digit_histogram(walk, shift, prefix, bins, kNoThreshold, [](int64_t) { return ~0u; });
+}
+
+// One digit of a row's radix select, from the row's filled bins: the digit whose bin holds the
+// need-th largest of the elements counted, to every lane of the group; *need becomes what is
+// still to take inside that bin, or 0 where there is nothing to take (need = 0, no row here).
+__device__ __forceinline__ unsigned pick_digit(const RowGroup& g, const unsigned* __restrict__ bins, int* need_io) {
+  const int need = *need_io, base = g.base(), chunk = g.chunk();
+  unsigned mine = 0;
+  for (int j = 0; j < chunk; ++j) mine += bins[base + j];
+  unsigned incl = mine;   // elements in my bins and in those of the group's lanes above me
+  for (int off = 1; off < g.group_lanes; off <<= 1) {
+    const unsigned up = __shfl_down(incl, off, kWave);
+    if (g.group_lane + off < g.group_lanes) incl += up;
+  }
+  const unsigned above = incl - mine;
+  // the lane whose bins hold the need-th largest element
+  const bool owner = need > 0 && above < static_cast<unsigned>(need) && static_cast<unsigned>(need) <= above + mine;
+  int digit = 0, left = 0;
+  if (owner) {
+    unsigned acc = above;
+    for (int j = chunk - 1; j >= 0; --j) {
+      const unsigned c = bins[base + j];
+      if (acc + c >= static_cast<unsigned>(need)) {
+        digit = base + j;
+        left = need - static_cast<int>(acc);
+        break;
       }
-      int64_t p = out + before;
-#pragma unroll
-      for (int e = 0; e < V; ++e)
-        if ((flags >> e) & 1u) {
-          column_indices[p] = static_cast<int>(c0 + e);
-          if constexpr (VALUES) values[p] = v.e[e];
-          ++p;
-        }
-      out += total;
+      acc += c;
     }
   }
-  if constexpr (!FILL) {
-    for (int o = group_lanes / 2; o > 0; o >>= 1) count += __shfl_xor(count, o, kWave);
-    if (live && group_lane == 0) row_offsets[mask * (int64_t{1} + m) + row + 1] = count;
+  const unsigned long long who = __ballot(owner) & g.group_mask;
+  const int from = who != 0ull ? __ffsll(who) - 1 : g.lane;
+  digit = __shfl(digit, from, kWave);
+  left = __shfl(left, from, kWave);
+  *need_io = who != 0ull ? left : 0;   // (no owner: nothing to take, or no row here)
+  return static_cast<unsigned>(digit);
+}
+
+// What a selection comes down to: an element is kept iff key > threshold, or key == threshold
+// and it is among the first `quota` such elements of its row.
+struct Selection {
+  unsigned threshold;
+  int quota;
+};
+
+// The `need` largest keys of the group's row by an MSB-first radix select over P digits in the
+// row's 256 LDS bins.  histogram(shift, prefix, bins) counts digit `shift / 8` of the row's keys
+// whose higher digits equal the prefix.  Every thread of the workgroup calls it: three barriers
+// per digit.
+template <int P, typename Histogram>
+__device__ __forceinline__ Selection radix_select(const RowGroup& g, unsigned* __restrict__ bins, int need,
+                                                  Histogram histogram) {
+  const bool any = need > 0;
+  const int base = g.base(), chunk = g.chunk();
+  unsigned prefix = 0;   // (need: still to take among the elements whose higher digits equal it)
+  for (int p = 0; p < P; ++p) {
+    const int shift = kDigitBits * (P - 1 - p);
+    for (int j = 0; j < chunk; ++j) bins[base + j] = 0u;
+    __syncthreads();
+    histogram(shift, prefix, bins);
+    __syncthreads();
+    prefix = (prefix << kDigitBits) | pick_digit(g, bins, &need);
+    __syncthreads();   // (the bins are cleared again)
   }
+  return {any ? prefix : kNoThreshold, need};
+}
+
+// Of the elements of a step whose bit is set in a lane's `flags` -- column order: lane after
+// lane, element after element inside a lane -- those in front of my piece and those of the
+// whole step.  One ballot per element slot = per 64 elements of the step.
+struct Prefix {
+  int before, total;
+};
+template <int V>
+__device__ __forceinline__ Prefix group_prefix(const RowGroup& g, unsigned flags) {
+  Prefix at = {0, 0};
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    const unsigned long long b = __ballot((flags >> e) & 1u);
+    at.before += __popcll(b & g.below);
+    at.total += __popcll(b & g.group_mask);
+  }
+  return at;
+}
+
+// flags plus those elements of `equal` (the step's ties with the threshold) whose rank among
+// the row's ties is below the quota; *ties_seen = the ties of the steps behind.
+template <int V>
+__device__ __forceinline__ unsigned admit_ties(const RowGroup& g, unsigned flags, unsigned equal, int quota,
+                                               int* ties_seen) {
+  const Prefix ties = group_prefix<V>(g, equal);
+  int rank = *ties_seen + ties.before;
+#pragma unroll
+  for (int e = 0; e < V; ++e)
+    if ((equal >> e) & 1u) {
+      if (rank < quota) flags |= 1u << e;
+      ++rank;
+    }
+  *ties_seen += ties.total;
+  return flags;
+}
+
+// The items of thread threadIdx.x when a workgroup of kScanBlock threads shares `count` items
+// in order.
+struct Span {
+  int64_t begin, end;
+};
+__device__ __forceinline__ Span thread_span(int64_t count) {
+  const int64_t per = (count + kScanBlock - 1) / kScanBlock;
+  const int64_t begin = min(count, threadIdx.x * per);
+  return {begin, min(count, begin + per)};
 }
 
 // Exclusive scan of one value per thread over a workgroup of kScanBlock threads; *total = the sum.
@@ -167,23 +388,80 @@ __device__ __forceinline__ T block_exclusive_scan(T value, T* __restrict__ wave_
   return before + incl - value;
 }
 
+// out[i] = count(0) + .. + count(i) over all items of the workgroup; `mine` = the sum of
+// count over my span.  -> the sum over all items.  One barrier.
+template <typename Count>
+__device__ __forceinline__ int inclusive_scan_span(const Span& span, int mine, int* __restrict__ wave_sums,
+                                                   int* out, Count count) {
+  int total;
+  int running = block_exclusive_scan(mine, wave_sums, &total);
+  for (int64_t i = span.begin; i < span.end; ++i) {
+    running += count(i);
+    out[i] = running;
+  }
+  return total;
+}
+
+// ---------------------------------------------------------------------------
+// The build.
+// FILL = false: row_offsets[mask][row + 1] = kept elements of the row.
+// FILL = true:  the kept columns (and, VALUES, the kept elements) of the row go to
+//               bases[mask] + row_offsets[mask][row] onwards, ascending.
+// ---------------------------------------------------------------------------
+template <typename U, bool FILL, bool VALUES>
+__global__ __launch_bounds__(kBuildBlock) void topology_rows_kernel(
+    int m, int n, int rows_per_wave, int blocks_per_mask, const U* __restrict__ dense,
+    int64_t batch_stride, int64_t row_stride, U keep, int* __restrict__ row_offsets,
+    const int64_t* __restrict__ bases, int* __restrict__ column_indices, U* __restrict__ values) {
+  constexpr int V = RowWalk<U>::V;
+  const int mask = blockIdx.x / blocks_per_mask;
+  const RowGroup g(rows_per_wave, blockIdx.x % blocks_per_mask);
+  const RowWalk<U> walk(g, dense + mask * batch_stride, row_stride, m, n);
+
+  int64_t out = 0;
+  if constexpr (FILL) {
+    if (walk.live) out = bases[mask] + row_offsets[mask * (int64_t{1} + m) + g.row];
+  }
+  int count = 0;
+  for (int s = 0; s < walk.steps; ++s) {
+    int64_t c0;
+    unsigned valid;   // (an element outside the row reads 0: not kept)
+    const Piece<U> v = walk.load(s, &c0, &valid);
+    unsigned flags = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) flags |= ((v.e[e] & keep) != 0 ? 1u : 0u) << e;
+    if constexpr (!FILL) {
+      count += __popc(flags);
+    } else {
+      const Prefix at = group_prefix<V>(g, flags);
+      int64_t p = out + at.before;
+#pragma unroll
+      for (int e = 0; e < V; ++e)
+        if ((flags >> e) & 1u) {
+          column_indices[p] = static_cast<int>(c0 + e);
+          if constexpr (VALUES) values[p] = v.e[e];
+          ++p;
+        }
+      out += at.total;
+    }
+  }
+  if constexpr (!FILL) {
+    for (int o = g.group_lanes / 2; o > 0; o >>= 1) count += __shfl_xor(count, o, kWave);
+    if (walk.live && g.group_lane == 0) row_offsets[mask * (int64_t{1} + m) + g.row + 1] = count;
+  }
+}
+
 // row_offsets[mask][1 .. m] hold the rows' counts: scanned in place into the offsets.
 __global__ __launch_bounds__(kScanBlock) void topology_scan_kernel(int m, int* __restrict__ row_offsets,
                                                                    int* __restrict__ nonzeros) {
   __shared__ int wave_sums[kScanBlock / kWave];
   int* __restrict__ offsets = row_offsets + blockIdx.x * (int64_t{1} + m);
-  const int t = threadIdx.x;
-  const int64_t per = (static_cast<int64_t>(m) + kScanBlock - 1) / kScanBlock;
-  const int64_t i0 = min(static_cast<int64_t>(m), t * per), i1 = min(static_cast<int64_t>(m), i0 + per);
+  const Span span = thread_span(m);
+  const auto count = [&](int64_t i) { return offsets[1 + i]; };
   int mine = 0;
-  for (int64_t i = i0; i < i1; ++i) mine += offsets[1 + i];
-  int total;
-  int running = block_exclusive_scan(mine, wave_sums, &total);
-  for (int64_t i = i0; i < i1; ++i) {
-    running += offsets[1 + i];
-    offsets[1 + i] = running;
-  }
-  if (t == 0) {
+  for (int64_t i = span.begin; i < span.end; ++i) mine += count(i);
+  const int total = inclusive_scan_span(span, mine, wave_sums, offsets + 1, count);
+  if (threadIdx.x == 0) {
     offsets[0] = 0;
     nonzeros[blockIdx.x] = total;
   }
@@ -193,14 +471,12 @@ __global__ __launch_bounds__(kScanBlock) void topology_scan_kernel(int m, int* _
 __global__ __launch_bounds__(kScanBlock) void topology_bases_kernel(int masks, const int* __restrict__ nonzeros,
                                                                     int64_t* __restrict__ bases) {
   __shared__ int64_t wave_sums[kScanBlock / kWave];
-  const int t = threadIdx.x;
-  const int per = (masks + kScanBlock - 1) / kScanBlock;
-  const int i0 = min(masks, t * per), i1 = min(masks, i0 + per);
+  const Span span = thread_span(masks);
   int64_t mine = 0;
-  for (int i = i0; i < i1; ++i) mine += nonzeros[i];
+  for (int64_t i = span.begin; i < span.end; ++i) mine += nonzeros[i];
   int64_t total;
   int64_t running = block_exclusive_scan(mine, wave_sums, &total);
-  for (int i = i0; i < i1; ++i) {
+  for (int64_t i = span.begin; i < span.end; ++i) {
     bases[i] = running;
     running += nonzeros[i];
   }
@@ -306,33 +582,25 @@ inline bool dense_ok(const void* dense, int element_bytes, int64_t batch_stride,
 
 // ---------------------------------------------------------------------------
 // Top-k selection over a dense floating matrix, written straight out as a CSR topology
-// (sputnik_hip_topk_to_csr).  An element's KEY is its bit pattern without the sign bit, read
-// as an unsigned integer: ranking by key is ranking by |x|, -0.0 ties with 0.0, denormals rank
-// by their bits, inf above every finite value and NaN above inf.  Both modes come down to a
-// pair (T_r, q_r) per row: an element is kept iff key > T_r, or key == T_r and it is among the
-// first q_r such elements of its row (ascending column).
-//   per row   every row keeps its k largest keys: ONE launch selects (T_r, q_r) of every row
-//             by an MSB-first radix select, 8-bit digits, a 256-bin histogram per row in LDS;
+// (sputnik_hip_topk_to_csr).  Ranking by key (key_of) is ranking by |x|: -0.0 ties with 0.0,
+// denormals rank by their bits, inf above every finite value and NaN above inf.  Both modes
+// come down to a Selection (T_r, q_r) per row, ties in ascending column order.
+//   per row   every row keeps its k largest keys: ONE launch runs radix_select for every row;
 //             it writes offsets r * k and row_indices r as well (equal lengths: no sort)
-//   total     the matrix keeps its K largest keys, ties to the lowest flat index: one launch
-//             per digit merges the workgroups' LDS histograms into 256 global bins (integer
-//             atomic adds, order independent); every later workgroup derives the digits chosen
-//             so far from those bins itself.  A rows launch counts g_r = #(key > T) and
-//             t_r = #(key == T), a scan launch turns Q = K - #(key > T) into the rows' quotas
-//             q_r = clamp(Q - ties of the rows in front, 0, t_r) and the offsets.
-// The fill is the ballot + lane-prefix placement of topology_rows_kernel plus a tie count
-// carried across the steps of a row.  Every walk is the 16-byte-piece walk described at the
-// top of this file; a row is RE-READ per digit pass (it comes from L2: a 2048 x 2048 float32
-// matrix is 16 MB) rather than held in registers, which would bound n, or in LDS, which the
-// per-row histograms already fill.  Every count is an integer, every store a vector store:
-// results are bitwise reproducible.  Nothing on the host depends on the data.
+//   total     the matrix keeps its K largest keys, ties to the lowest flat index: after a launch
+//             that clears them, one launch per digit (workgroup_digit_pass) merges the
+//             workgroups' LDS histograms into 256 global bins (integer atomic adds, order
+//             independent); every later workgroup derives the digits chosen so far from those
+//             bins itself (total_select).  A rows launch counts g_r = #(key > T) and
+//             t_r = #(key == T) (count_against_total), a scan launch (total_scan_kernel) turns
+//             Q = K - #(key > T) into the rows' quotas q_r = clamp(Q - ties of the rows in
+//             front, 0, t_r) and the offsets.
+// The fill (fill_row) is group_prefix + admit_ties per step.  A row is RE-READ per digit pass
+// (it comes from L2: a 2048 x 2048 float32 matrix is 16 MB) rather than held in registers,
+// which would bound n, or in LDS, which the per-row histograms already fill.  Every count is an
+// integer, every store a vector store: results are bitwise reproducible.  Nothing on the host
+// depends on the data, and every launch is a kernel: a call is captured into a graph whole.
 // ---------------------------------------------------------------------------
-constexpr int kDigitBits = 8;
-constexpr int kDigitBins = 1 << kDigitBits;
-constexpr int kMaxDigitPasses = 4;
-constexpr unsigned kNoThreshold = 0xffffffffu;   // above every key: nothing is kept by it
-static_assert(kDigitBins == kBuildBlock, "one thread per bin when a workgroup merges its histogram");
-
 struct TopkShape {
   int status = 0;
   int served = 0, digit_passes = 0;
@@ -353,120 +621,26 @@ inline TopkShape topk_shape(int m, int n, int element_bytes, int total_mode) {
   return t;
 }
 
-// workspace, in 32-bit words.  per row: thresholds [m], quotas [m].
-// total: bins [4][256], threshold [1], quotas [m], ties [m].
-inline size_t topk_workspace_words(int m, int total_mode) {
-  return total_mode ? static_cast<size_t>(kMaxDigitPasses) * kDigitBins + 1 + 2 * static_cast<size_t>(m)
-                    : 2 * static_cast<size_t>(m);
-}
-
-// One group of lanes on one row: the walk of topology_rows_kernel.
-template <typename U>
-struct RowWalk {
-  static constexpr int V = kLoadBytes / sizeof(U);
-  const U* src;
-  bool live;
-  int n, lead, steps, group_lanes, group_lane;
-
-  __device__ __forceinline__ RowWalk() {}   // (entry_walk: the entries of a CSR row)
-  __device__ __forceinline__ RowWalk(const U* dense, int64_t row, int64_t row_stride, int m, int n_,
-                                     int rows_per_wave) {
-    const int lane = threadIdx.x % kWave;
-    n = n_;
-    group_lanes = kWave / rows_per_wave;
-    group_lane = lane % group_lanes;
-    live = row < m;
-    src = dense + (live ? row * row_stride : int64_t{0});
-    lead = live ? static_cast<int>((reinterpret_cast<uintptr_t>(src) % kLoadBytes) / sizeof(U)) : 0;
-    const bool any_lead = __ballot(lead != 0) != 0ull;
-    const int64_t span = static_cast<int64_t>(group_lanes) * V;
-    steps = static_cast<int>((static_cast<int64_t>(n) + (any_lead ? V - 1 : 0) + span - 1) / span);
+// The workspace of a total selection, in 32-bit words: bins [4][256], threshold [1], for several
+// layers the ties handed out so far [1]; then per layer quotas [m], ties [m].
+struct TotalWorkspace {
+  unsigned *bins, *threshold, *handed;
+  int* rows;
+  static size_t words(int64_t rows, bool layers) {
+    return static_cast<size_t>(kMaxDigitPasses) * kDigitBins + 1 + (layers ? 1 : 0) + 2 * static_cast<size_t>(rows);
   }
-  // My piece of step s, its first column, and a bit per element that lies inside the row
-  // (the others read as 0 and are not loaded).
-  __device__ __forceinline__ Piece<U> load(int s, int64_t* first_column, unsigned* valid) const {
-    const int64_t c0 = (static_cast<int64_t>(s) * group_lanes + group_lane) * V - lead;
-    Piece<U> v;
-    if (live && c0 >= 0 && c0 + V <= n) {
-      v = *reinterpret_cast<const Piece<U>*>(src + c0);
-      *valid = (1u << V) - 1u;
-    } else {
-      unsigned in = 0;
-#pragma unroll
-      for (int e = 0; e < V; ++e) {
-        const bool inside = live && c0 + e >= 0 && c0 + e < n;
-        v.e[e] = inside ? src[c0 + e] : U{0};
-        in |= (inside ? 1u : 0u) << e;
-      }
-      *valid = in;
-    }
-    *first_column = c0;
-    return v;
+  TotalWorkspace(void* workspace, bool layers) {
+    bins = static_cast<unsigned*>(workspace);
+    threshold = bins + kMaxDigitPasses * kDigitBins;
+    handed = layers ? threshold + 1 : nullptr;
+    rows = reinterpret_cast<int*>(threshold + 1 + (layers ? 1 : 0));
   }
+  // of a layer of m rows: its quotas, and its ties m words on
+  int* quotas(int64_t rows_in_front = 0) const { return rows + 2 * rows_in_front; }
 };
-
-template <typename U>
-__device__ __forceinline__ unsigned key_of(U bits) {
-  return static_cast<unsigned>(bits & static_cast<U>(static_cast<U>(~U{0}) >> 1));
-}
-
-// Histogram of digit `shift / 8` of the row's keys whose higher digits equal `prefix`.
-template <typename U>
-__device__ __forceinline__ void digit_histogram(const RowWalk<U>& walk, int shift, unsigned prefix,
-                                                unsigned* __restrict__ bins) {
-  constexpr int V = RowWalk<U>::V;
-  for (int s = 0; s < walk.steps; ++s) {
-    int64_t c0;
-    unsigned valid;
-    const Piece<U> v = walk.load(s, &c0, &valid);
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned key = key_of(v.e[e]);
-      // (64 bit: the first pass shifts everything out and compares with prefix 0)
-      if (((valid >> e) & 1u) && static_cast<unsigned>(static_cast<uint64_t>(key) >> (shift + kDigitBits)) == prefix)
-        atomicAdd(&bins[(key >> shift) & (kDigitBins - 1)], 1u);
-    }
-  }
-}
-
-// One digit of a row's radix select, from the row's filled bins: the digit whose bin holds the
-// need-th largest of the elements counted, to every lane of the group; *need becomes what is
-// still to take inside that bin, or 0 where there is nothing to take (need = 0, no row here).
-// A lane owns the `chunk` consecutive bins from `base`.
-__device__ __forceinline__ unsigned pick_digit(const unsigned* __restrict__ bins, int base, int chunk,
-                                               int group_lane, int group_lanes, unsigned long long group_mask,
-                                               int* need_io) {
-  const int lane = threadIdx.x % kWave;
-  const int need = *need_io;
-  unsigned mine = 0;
-  for (int j = 0; j < chunk; ++j) mine += bins[base + j];
-  unsigned incl = mine;   // elements in my bins and in those of the group's lanes above me
-  for (int off = 1; off < group_lanes; off <<= 1) {
-    const unsigned up = __shfl_down(incl, off, kWave);
-    if (group_lane + off < group_lanes) incl += up;
-  }
-  const unsigned above = incl - mine;
-  // the lane whose bins hold the need-th largest element
-  const bool owner = need > 0 && above < static_cast<unsigned>(need) && static_cast<unsigned>(need) <= above + mine;
-  int digit = 0, left = 0;
-  if (owner) {
-    unsigned acc = above;
-    for (int j = chunk - 1; j >= 0; --j) {
-      const unsigned c = bins[base + j];
-      if (acc + c >= static_cast<unsigned>(need)) {
-        digit = base + j;
-        left = need - static_cast<int>(acc);
-        break;
-      }
-      acc += c;
-    }
-  }
-  const unsigned long long who = __ballot(owner) & group_mask;
-  const int from = who != 0ull ? __ffsll(who) - 1 : lane;
-  digit = __shfl(digit, from, kWave);
-  left = __shfl(left, from, kWave);
-  *need_io = who != 0ull ? left : 0;   // (no owner: nothing to take, or no row here)
-  return static_cast<unsigned>(digit);
+// per row: thresholds [m], quotas [m].
+inline size_t topk_workspace_words(int m, int total_mode) {
+  return total_mode ? TotalWorkspace::words(m, false) : 2 * static_cast<size_t>(m);
 }
 
 // Per-row mode: (T_r, q_r), the offsets r * k and the row order 0 .. m - 1.
@@ -477,35 +651,26 @@ __global__ __launch_bounds__(kBuildBlock) void topk_row_select_kernel(
     int* __restrict__ row_indices) {
   constexpr int P = sizeof(U) * 8 / kDigitBits;
   __shared__ unsigned hist[kBuildWaves * kMaxRowsPerWave][kDigitBins];   // 64 KiB
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  const int group_lanes = kWave / rows_per_wave;
-  const int group = lane / group_lanes, group_lane = lane % group_lanes;
-  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
-  const unsigned long long group_mask =
-      (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
-  const RowWalk<U> walk(scores, row, row_stride, m, n, rows_per_wave);
-  unsigned* __restrict__ bins = hist[wave * rows_per_wave + group];
-  const int chunk = kDigitBins / group_lanes;   // my bins: 4 .. 256 consecutive ones
-  const int base = group_lane * chunk;
-
-  unsigned prefix = 0;
-  int need = k;   // still to take among the elements whose higher digits equal the prefix
-  for (int p = 0; p < P; ++p) {
-    const int shift = kDigitBits * (P - 1 - p);
-    for (int j = 0; j < chunk; ++j) bins[base + j] = 0u;
-    __syncthreads();
+  const RowGroup g(rows_per_wave);
+  const RowWalk<U> walk(g, scores, row_stride, m, n);
+  const Selection kept = radix_select<P>(g, hist[g.slot], k, [&](int shift, unsigned prefix, unsigned* bins) {
     digit_histogram(walk, shift, prefix, bins);
-    __syncthreads();
-    prefix = (prefix << kDigitBits) | pick_digit(bins, base, chunk, group_lane, group_lanes, group_mask, &need);
-    __syncthreads();   // (the bins are cleared again)
-  }
-  if (walk.live && group_lane == 0) {
-    thresholds[row] = k > 0 ? prefix : kNoThreshold;
-    quotas[row] = need;
+  });
+  if (walk.live && g.group_lane == 0) {
+    const int64_t row = g.row;
+    thresholds[row] = kept.threshold;
+    quotas[row] = kept.quota;
     row_offsets[row] = static_cast<int>(row * k);
     row_indices[row] = static_cast<int>(row);
     if (row == m - 1) row_offsets[m] = static_cast<int>(static_cast<int64_t>(m) * k);
   }
+}
+
+// Total mode: the global bins of every digit pass start at zero.  (A kernel, not a memset: a
+// captured call clears them on every replay.)
+static_assert(kMaxDigitPasses * kDigitBins == kScanBlock, "one thread per bin");
+__global__ __launch_bounds__(kScanBlock) void total_clear_kernel(unsigned* __restrict__ bins) {
+  bins[threadIdx.x] = 0u;
 }
 
 // Total mode: the digits chosen by the first `passes` passes, from their global bins; by EVERY
@@ -544,27 +709,62 @@ __device__ __forceinline__ unsigned total_select(const unsigned* bins, int passe
 }
 constexpr int kSelectWords = kDigitBins / kWave + 2;
 
-// One digit pass over the whole matrix: this workgroup's rows into an LDS histogram, that into
+// Total mode, digit pass `pass` of P by one workgroup of kBuildBlock threads:
+// walk(shift, prefix, hist) counts the workgroup's keys into an LDS histogram, that goes into
 // bins[pass][*] with one integer atomic add per non-empty bin.
-template <typename U>
-__global__ __launch_bounds__(kBuildBlock) void topk_total_hist_kernel(
-    int m, int n, int rows_per_wave, int pass, unsigned count, const U* __restrict__ scores,
-    int64_t row_stride, unsigned* bins) {
-  constexpr int P = sizeof(U) * 8 / kDigitBits;
+template <int P, typename Walk>
+__device__ __forceinline__ void workgroup_digit_pass(int pass, unsigned count, unsigned* bins, Walk walk) {
   __shared__ unsigned hist[kDigitBins];
   __shared__ unsigned select[kSelectWords];
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  const int group = lane / (kWave / rows_per_wave);
-  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
   unsigned need;
   const unsigned prefix = total_select(bins, pass, count, select, &need);
   hist[threadIdx.x] = 0u;
   __syncthreads();
-  const RowWalk<U> walk(scores, row, row_stride, m, n, rows_per_wave);
-  digit_histogram(walk, kDigitBits * (P - 1 - pass), prefix, hist);
+  walk(kDigitBits * (P - 1 - pass), prefix, hist);
   __syncthreads();
   const unsigned c = hist[threadIdx.x];
   if (c != 0u) atomicAdd(&bins[pass * kDigitBins + threadIdx.x], c);
+}
+
+// One digit pass over the whole matrix: this workgroup's rows.
+template <typename U>
+__global__ __launch_bounds__(kBuildBlock) void topk_total_hist_kernel(
+    int m, int n, int rows_per_wave, int pass, unsigned count, const U* __restrict__ scores,
+    int64_t row_stride, unsigned* bins) {
+  workgroup_digit_pass<sizeof(U) * 8 / kDigitBits>(pass, count, bins, [&](int shift, unsigned prefix, unsigned* hist) {
+    const RowGroup g(rows_per_wave);
+    const RowWalk<U> walk(g, scores, row_stride, m, n);
+    digit_histogram(walk, shift, prefix, hist);
+  });
+}
+
+// Total mode: greater[row] = #(key > T), ties[row] = #(key == T) of the walk's row, T from the
+// filled bins.
+template <typename U>
+__device__ __forceinline__ void count_against_total(const RowGroup& g, const RowWalk<U>& walk, unsigned count,
+                                                    const unsigned* __restrict__ bins, int* __restrict__ greater_out,
+                                                    int* __restrict__ ties) {
+  __shared__ unsigned select[kSelectWords];
+  unsigned need;
+  const unsigned prefix = total_select(bins, sizeof(U) * 8 / kDigitBits, count, select, &need);
+  const unsigned threshold = count > 0 ? prefix : kNoThreshold;
+  int greater = 0, equal = 0;
+  for (int s = 0; s < walk.steps; ++s) {
+    int64_t c0;
+    unsigned valid, above, same;
+    const Piece<U> v = walk.load(s, &c0, &valid);
+    compare_piece(v, threshold, kNoThreshold, &above, &same);
+    greater += __popc(above & valid);
+    equal += __popc(same & valid);
+  }
+  for (int o = g.group_lanes / 2; o > 0; o >>= 1) {
+    greater += __shfl_xor(greater, o, kWave);
+    equal += __shfl_xor(equal, o, kWave);
+  }
+  if (walk.live && g.group_lane == 0) {
+    greater_out[g.row] = greater;
+    ties[g.row] = equal;
+  }
 }
 
 // Total mode: row_offsets[row + 1] = #(key > T), ties[row] = #(key == T).
@@ -572,59 +772,34 @@ template <typename U>
 __global__ __launch_bounds__(kBuildBlock) void topk_total_rows_kernel(
     int m, int n, int rows_per_wave, unsigned count, const U* __restrict__ scores, int64_t row_stride,
     const unsigned* __restrict__ bins, int* __restrict__ row_offsets, int* __restrict__ ties) {
-  constexpr int V = RowWalk<U>::V, P = sizeof(U) * 8 / kDigitBits;
-  __shared__ unsigned select[kSelectWords];
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  const int group_lanes = kWave / rows_per_wave;
-  const int group = lane / group_lanes, group_lane = lane % group_lanes;
-  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
-  unsigned need;
-  const unsigned prefix = total_select(bins, P, count, select, &need);
-  const unsigned threshold = count > 0 ? prefix : kNoThreshold;
-  const RowWalk<U> walk(scores, row, row_stride, m, n, rows_per_wave);
-  int greater = 0, equal = 0;
-  for (int s = 0; s < walk.steps; ++s) {
-    int64_t c0;
-    unsigned valid;
-    const Piece<U> v = walk.load(s, &c0, &valid);
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned key = key_of(v.e[e]);
-      const bool in = (valid >> e) & 1u;
-      greater += in && key > threshold ? 1 : 0;
-      equal += in && key == threshold ? 1 : 0;
-    }
-  }
-  for (int o = group_lanes / 2; o > 0; o >>= 1) {
-    greater += __shfl_xor(greater, o, kWave);
-    equal += __shfl_xor(equal, o, kWave);
-  }
-  if (walk.live && group_lane == 0) {
-    row_offsets[row + 1] = greater;
-    ties[row] = equal;
-  }
+  const RowGroup g(rows_per_wave);
+  const RowWalk<U> walk(g, scores, row_stride, m, n);
+  count_against_total(g, walk, count, bins, row_offsets + 1, ties);
 }
 
-// Total mode, one workgroup: quotas[r] = clamp(Q - ties of the rows in front, 0, ties[r]); the
-// lengths #(key > T) + quotas[r], scanned in place into the offsets; *threshold = T.
-__global__ __launch_bounds__(kScanBlock) void topk_total_scan_kernel(
+// Total mode, one workgroup per layer, the layers of a selection in order: quotas[r] =
+// clamp(Q - ties handed out in front, 0, ties[r]); the lengths #(key > T) + quotas[r], scanned
+// in place into the offsets; *threshold = T.  The ties of the layers in front are *handed_in
+// (null: none, the first or only layer); *handed_out = that plus this layer's ties and
+// *new_size = the layer's kept entries, where asked for.
+__global__ __launch_bounds__(kScanBlock) void total_scan_kernel(
     int m, int digit_passes, unsigned count, const unsigned* __restrict__ bins, const int* __restrict__ ties,
-    int* __restrict__ quotas, int* __restrict__ offsets, unsigned* __restrict__ threshold) {
+    int* __restrict__ quotas, int* __restrict__ offsets, unsigned* __restrict__ threshold,
+    const unsigned* handed_in, unsigned* handed_out, int* new_size) {
   __shared__ int wave_sums[kScanBlock / kWave];
   __shared__ unsigned select[kSelectWords];
+  const int64_t in_front = handed_in != nullptr ? static_cast<int64_t>(*handed_in) : int64_t{0};
   unsigned need;
-  const unsigned prefix = total_select(bins, digit_passes, count, select, &need);
-  const int64_t quota = need;
-  const int t = threadIdx.x;
-  const int64_t per = (static_cast<int64_t>(m) + kScanBlock - 1) / kScanBlock;
-  const int64_t i0 = min(static_cast<int64_t>(m), t * per), i1 = min(static_cast<int64_t>(m), i0 + per);
+  const unsigned prefix = total_select(bins, digit_passes, count, select, &need);   // (barriers: *handed_in is read)
+  const int64_t quota = static_cast<int64_t>(need) - in_front;
+  const Span span = thread_span(m);
   int mine = 0;
-  for (int64_t i = i0; i < i1; ++i) mine += ties[i];
-  int total;
-  int64_t ties_before = block_exclusive_scan(mine, wave_sums, &total);
+  for (int64_t i = span.begin; i < span.end; ++i) mine += ties[i];
+  int tied_here;
+  int64_t ties_before = block_exclusive_scan(mine, wave_sums, &tied_here);
   __syncthreads();   // (wave_sums is written again)
   mine = 0;
-  for (int64_t i = i0; i < i1; ++i) {
+  for (int64_t i = span.begin; i < span.end; ++i) {
     const int tied = ties[i];
     const int q = static_cast<int>(max(int64_t{0}, min(static_cast<int64_t>(tied), quota - ties_before)));
     ties_before += tied;
@@ -633,14 +808,37 @@ __global__ __launch_bounds__(kScanBlock) void topk_total_scan_kernel(
     offsets[1 + i] = length;
     mine += length;
   }
-  int running = block_exclusive_scan(mine, wave_sums, &total);
-  for (int64_t i = i0; i < i1; ++i) {
-    running += offsets[1 + i];
-    offsets[1 + i] = running;
-  }
-  if (t == 0) {
+  const int total = inclusive_scan_span(span, mine, wave_sums, offsets + 1, [&](int64_t i) { return offsets[1 + i]; });
+  if (threadIdx.x == 0) {
     offsets[0] = 0;
     *threshold = count > 0 ? prefix : kNoThreshold;
+    if (handed_out != nullptr) *handed_out = static_cast<unsigned>(in_front + tied_here);
+    if (new_size != nullptr) *new_size = total;
+  }
+}
+
+// The elements of the walk's row that `kept` selects into the slots [out, end), in the order of
+// the walk: store(slot, the element's index in the row, the element).
+template <typename U, typename Store>
+__device__ __forceinline__ void fill_row(const RowGroup& g, const RowWalk<U>& walk, Selection kept, int64_t out,
+                                         int64_t end, Store store) {
+  constexpr int V = RowWalk<U>::V;
+  int ties_seen = 0;   // elements equal to the threshold in the steps behind
+  for (int s = 0; s < walk.steps; ++s) {
+    int64_t c0;
+    unsigned valid, greater, equal;
+    const Piece<U> v = walk.load(s, &c0, &valid);
+    compare_piece(v, kept.threshold, kNoThreshold, &greater, &equal);
+    const unsigned flags = admit_ties<V>(g, greater & valid, equal & valid, kept.quota, &ties_seen);
+    const Prefix at = group_prefix<V>(g, flags);
+    int64_t p = out + at.before;
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      if (((flags >> e) & 1u) && p < end) {   // (no store ever leaves the row's slots)
+        store(p, c0 + e, v.e[e]);
+        ++p;
+      }
+    out += at.total;
   }
 }
 
@@ -652,70 +850,39 @@ __global__ __launch_bounds__(kBuildBlock) void topk_fill_kernel(
     const unsigned* __restrict__ thresholds, int threshold_stride, const int* __restrict__ quotas,
     const int* __restrict__ row_offsets, const void* __restrict__ values_from, int64_t values_row_stride,
     int* __restrict__ column_indices, void* __restrict__ values) {
-  constexpr int V = RowWalk<U>::V;
   using W = typename std::conditional<VB == 2, uint16_t, uint32_t>::type;
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  const int group_lanes = kWave / rows_per_wave;
-  const int group = lane / group_lanes;
-  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
-  const unsigned long long group_mask =
-      (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
-  const unsigned long long below = group_mask & ((1ull << lane) - 1ull);
-  const RowWalk<U> walk(scores, row, row_stride, m, n, rows_per_wave);
-  const unsigned threshold = walk.live ? thresholds[row * threshold_stride] : kNoThreshold;
-  const int quota = walk.live ? quotas[row] : 0;
+  const RowGroup g(rows_per_wave);
+  const RowWalk<U> walk(g, scores, row_stride, m, n);
+  const int64_t row = g.row;
+  const Selection kept = {walk.live ? thresholds[row * threshold_stride] : kNoThreshold, walk.live ? quotas[row] : 0};
   const W* __restrict__ payload =
       static_cast<const W*>(values_from) + (VB != 0 && walk.live ? row * values_row_stride : int64_t{0});
-  int64_t out = walk.live ? row_offsets[row] : 0;
-  const int64_t end = walk.live ? row_offsets[row + 1] : 0;   // (no store ever leaves the row's slots)
-  int ties_seen = 0;   // elements equal to the threshold in the steps behind
-  for (int s = 0; s < walk.steps; ++s) {
-    int64_t c0;
-    unsigned valid;
-    const Piece<U> v = walk.load(s, &c0, &valid);
-    unsigned greater = 0, equal = 0;
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned key = key_of(v.e[e]);
-      greater |= (key > threshold ? 1u : 0u) << e;
-      equal |= (key == threshold ? 1u : 0u) << e;
-    }
-    greater &= valid;
-    equal &= valid;
-    // column order: lane after lane, element after element inside a lane
-    int ties_before = 0, ties_step = 0;
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned long long b = __ballot((equal >> e) & 1u);
-      ties_before += __popcll(b & below);
-      ties_step += __popcll(b & group_mask);
-    }
-    unsigned flags = greater;
-    int rank = ties_seen + ties_before;
-#pragma unroll
-    for (int e = 0; e < V; ++e)
-      if ((equal >> e) & 1u) {
-        if (rank < quota) flags |= 1u << e;
-        ++rank;
-      }
-    ties_seen += ties_step;
-    int before = 0, total = 0;
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned long long b = __ballot((flags >> e) & 1u);
-      before += __popcll(b & below);
-      total += __popcll(b & group_mask);
-    }
-    int64_t p = out + before;
-#pragma unroll
-    for (int e = 0; e < V; ++e)
-      if (((flags >> e) & 1u) && p < end) {
-        column_indices[p] = static_cast<int>(c0 + e);
-        if constexpr (VB != 0) static_cast<W*>(values)[p] = payload[c0 + e];
-        ++p;
-      }
-    out += total;
-  }
+  fill_row(g, walk, kept, walk.live ? row_offsets[row] : 0, walk.live ? row_offsets[row + 1] : 0,
+           [&](int64_t p, int64_t column, U) {
+             column_indices[p] = static_cast<int>(column);
+             if constexpr (VB != 0) static_cast<W*>(values)[p] = payload[column];
+           });
+}
+
+// f(uint16_t{}) or f(uint32_t{}): the launch for 2- or 4-byte elements (the entries check the width).
+template <typename F>
+inline int by_width(int element_bytes, F f) {
+  return element_bytes == 2 ? f(uint16_t{}) : f(uint32_t{});
+}
+
+// Total mode: the bins cleared, then hist(pass) launches each of the digit passes.
+template <typename Hist>
+inline void launch_digit_passes(unsigned* bins, int digit_passes, hipStream_t stream, Hist hist) {
+  hipLaunchKernelGGL(total_clear_kernel, dim3(1), dim3(kScanBlock), 0, stream, bins);
+  for (int p = 0; p < digit_passes; ++p) hist(p);
+}
+
+// Total mode: the scan of a layer of m rows whose quotas start at `quotas`; `first`: no layer in front.
+inline void launch_total_scan(const TotalWorkspace& w, int* quotas, int m, int digit_passes, unsigned count,
+                              int* offsets, bool first, int* new_size, hipStream_t stream) {
+  hipLaunchKernelGGL(total_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, m, digit_passes, count, w.bins,
+                     quotas + m, quotas, offsets, w.threshold,
+                     first ? static_cast<const unsigned*>(nullptr) : w.handed, w.handed, new_size);
 }
 
 template <typename U>
@@ -736,35 +903,30 @@ int launch_topk(const TopkShape& t, int m, int n, const void* scores_, int64_t r
     thresholds = th;
     quotas = q;
   } else {
-    unsigned* bins = workspace;
-    unsigned* th = workspace + kMaxDigitPasses * kDigitBins;
-    int* q = reinterpret_cast<int*>(th + 1);
-    int* ties = q + m;
-    if (hipMemsetAsync(bins, 0, sizeof(unsigned) * kMaxDigitPasses * kDigitBins, stream) != hipSuccess)
-      return launch_status();
-    for (int p = 0; p < t.digit_passes; ++p)
+    const TotalWorkspace w(workspace, false);
+    launch_digit_passes(w.bins, t.digit_passes, stream, [&](int p) {
       hipLaunchKernelGGL((topk_total_hist_kernel<U>), grid, block, 0, stream, m, n, rows, p, count, scores,
-                         row_stride, bins);
+                         row_stride, w.bins);
+    });
     hipLaunchKernelGGL((topk_total_rows_kernel<U>), grid, block, 0, stream, m, n, rows, count, scores, row_stride,
-                       bins, row_offsets, ties);
-    hipLaunchKernelGGL(topk_total_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, m, t.digit_passes, count,
-                       bins, ties, q, row_offsets, th);
-    thresholds = th;
-    quotas = q;
+                       w.bins, row_offsets, w.quotas() + m);
+    launch_total_scan(w, w.quotas(), m, t.digit_passes, count, row_offsets, true, nullptr, stream);
+    thresholds = w.threshold;
+    quotas = w.quotas();
   }
   int st = launch_status();
   if (st != 0) return st;
   if (count > 0 && column_indices != nullptr) {
     const int stride = total_mode ? 0 : 1;
-#define SPUTNIK_TOPK_FILL(VB)                                                                             \
-  hipLaunchKernelGGL((topk_fill_kernel<U, VB>), grid, block, 0, stream, m, n, rows, scores, row_stride,   \
-                     thresholds, stride, quotas, row_offsets, values_from, values_row_stride,             \
-                     column_indices, values)
-    if (values == nullptr) SPUTNIK_TOPK_FILL(0);
-    else if (value_bytes == 2) SPUTNIK_TOPK_FILL(2);
-    else SPUTNIK_TOPK_FILL(4);
-#undef SPUTNIK_TOPK_FILL
-    st = launch_status();
+    const auto fill = [&](auto vb) {
+      hipLaunchKernelGGL((topk_fill_kernel<U, decltype(vb)::value>), grid, block, 0, stream, m, n, rows, scores,
+                         row_stride, thresholds, stride, quotas, row_offsets, values_from, values_row_stride,
+                         column_indices, values);
+      return launch_status();
+    };
+    if (values == nullptr) st = fill(std::integral_constant<int, 0>{});
+    else if (value_bytes == 2) st = fill(std::integral_constant<int, 2>{});
+    else st = fill(std::integral_constant<int, 4>{});
   }
   return st;
 }
@@ -777,12 +939,12 @@ int launch_topk(const TopkShape& t, int m, int n, const void* scores_, int64_t r
 // the old / kept bits of the columns, (T_s, q_s) -- stays in its registers and in its part of
 // LDS.  (A select + fill pair, as the top-k build has, would have to write the kept bits of
 // every row out and read them back, or mark them twice.)
-//   1  radix select over values[row_offsets[r] ..] (a ragged read, lane after lane): (T_v, q_v)
+//   1  radix_select over values[row_offsets[r] ..] (a ragged read, lane after lane): (T_v, q_v)
 //   2  the row's entries again: the old columns and the kept ones into two bit planes in LDS
-//   3  radix select over the dense score row outside the kept columns, keys clamped to the
+//   3  radix_select over the dense score row outside the kept columns, keys clamped to the
 //      largest finite one: (T_s, q_s)
-//   4  the fill walk of topk_fill_kernel over the score row; a running count of old bits is
-//      the old entry index of a kept column
+//   4  admit_ties + group_prefix per step of the score row, as fill_row does; a running
+//      group_prefix of the old bits is the old entry index of a kept column
 // LDS of a row: the 256 bins and 2 * ceil(n / 32) words of bit planes.  Four rows of that at
 // one row per wave fit 64 KiB up to n = kRegrowMaxN; 64 rows (16 per wave) do not at any n, so
 // the narrowest instance is 8 rows per wave.
@@ -839,98 +1001,53 @@ __global__ __launch_bounds__(kBuildBlock) void csr_regrow_kernel(
   constexpr int V = RowWalk<S>::V;
   constexpr int PV = sizeof(W) * 8 / kDigitBits, PS = sizeof(S) * 8 / kDigitBits;
   extern __shared__ unsigned regrow_lds[];   // per row: bins [256], old bits [words], kept bits [words]
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  const int group_lanes = kWave / rows_per_wave;
-  const int group = lane / group_lanes, group_lane = lane % group_lanes;
-  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
-  const unsigned long long group_mask =
-      (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
-  const unsigned long long below = group_mask & ((1ull << lane) - 1ull);
-  const RowWalk<S> walk(scores, row, row_stride, m, n, rows_per_wave);
-  unsigned* __restrict__ bins = regrow_lds + (wave * rows_per_wave + group) * (kDigitBins + 2 * words);
+  const RowGroup g(rows_per_wave);
+  const RowWalk<S> walk(g, scores, row_stride, m, n);
+  unsigned* __restrict__ bins = regrow_lds + g.slot * (kDigitBins + 2 * words);
   unsigned* __restrict__ old_bits = bins + kDigitBins;
   unsigned* __restrict__ kept_bits = old_bits + words;
-  const int chunk = kDigitBins / group_lanes;
-  const int base = group_lane * chunk;
 
-  // the row's slots, inside [0, nonzeros) whatever the offsets say
-  int begin = 0, end = 0, drop = 0;
-  if (walk.live) {
-    begin = min(max(row_offsets[row], 0), nonzeros);
-    end = min(max(row_offsets[row + 1], begin), nonzeros);
-    drop = min(max(drop_counts[row], 0), end - begin);
-  }
-  const int length = end - begin, keep = length - drop;
+  int begin, end;
+  row_slots(row_offsets, g.row, walk.live, nonzeros, &begin, &end);
+  const int length = end - begin;
+  const int drop = walk.live ? min(max(drop_counts[g.row], 0), length) : 0;
   // steps of the walk over the row's entries, the most of the wave's rows: every lane of the
   // wave takes part in every ballot
-  int entry_steps = static_cast<int>((static_cast<int64_t>(length) + group_lanes - 1) / group_lanes);
+  int entry_steps = static_cast<int>((static_cast<int64_t>(length) + g.group_lanes - 1) / g.group_lanes);
   for (int o = kWave / 2; o > 0; o >>= 1) entry_steps = max(entry_steps, __shfl_xor(entry_steps, o, kWave));
 
-  // 1: (T_v, q_v) of the keep largest value keys
-  unsigned prefix = 0;
-  int need = keep;
-  for (int p = 0; p < PV; ++p) {
-    const int shift = kDigitBits * (PV - 1 - p);
-    for (int j = 0; j < chunk; ++j) bins[base + j] = 0u;
-    __syncthreads();
-    for (int64_t i = static_cast<int64_t>(begin) + group_lane; i < end; i += group_lanes) {
-      const unsigned key = key_of(values[i]);
-      if (static_cast<unsigned>(static_cast<uint64_t>(key) >> (shift + kDigitBits)) == prefix)
-        atomicAdd(&bins[(key >> shift) & (kDigitBins - 1)], 1u);
-    }
-    __syncthreads();
-    prefix = (prefix << kDigitBits) | pick_digit(bins, base, chunk, group_lane, group_lanes, group_mask, &need);
-    __syncthreads();
-  }
-  const unsigned value_threshold = keep > 0 ? prefix : kNoThreshold;
-  const int value_quota = need;
+  // 1: (T_v, q_v) of the length - drop largest value keys: a ragged read, lane after lane
+  const Selection keep = radix_select<PV>(g, bins, length - drop, [&](int shift, unsigned prefix, unsigned* b) {
+    for (int64_t i = static_cast<int64_t>(begin) + g.group_lane; i < end; i += g.group_lanes)
+      count_digit(key_of(values[i]), true, shift, prefix, b);
+  });
 
   // 2: the old and the kept columns.  A column outside the row sets no bit.
-  for (int j = group_lane; j < 2 * words; j += group_lanes) old_bits[j] = 0u;
+  for (int j = g.group_lane; j < 2 * words; j += g.group_lanes) old_bits[j] = 0u;
   __syncthreads();
   int ties_seen = 0;
   for (int s = 0; s < entry_steps; ++s) {
-    const int64_t i = static_cast<int64_t>(begin) + static_cast<int64_t>(s) * group_lanes + group_lane;
+    const int64_t i = static_cast<int64_t>(begin) + static_cast<int64_t>(s) * g.group_lanes + g.group_lane;
     const bool in = i < end;
     const unsigned key = in ? key_of(values[i]) : 0u;
     const int column = in ? column_indices[i] : -1;
-    const bool tie = in && key == value_threshold;
-    const unsigned long long b = __ballot(tie);
-    const int rank = ties_seen + __popcll(b & below);
-    ties_seen += __popcll(b & group_mask);
+    const bool tie = in && key == keep.threshold;
+    const Prefix ties = group_prefix<1>(g, tie ? 1u : 0u);
+    const int rank = ties_seen + ties.before;
+    ties_seen += ties.total;
     if (in && static_cast<unsigned>(column) < static_cast<unsigned>(n)) {
       const unsigned bit = 1u << (column & 31);
       atomicOr(&old_bits[column >> 5], bit);
-      if (key > value_threshold || (tie && rank < value_quota)) atomicOr(&kept_bits[column >> 5], bit);
+      if (key > keep.threshold || (tie && rank < keep.quota)) atomicOr(&kept_bits[column >> 5], bit);
     }
   }
   __syncthreads();
 
-  // 3: (T_s, q_s) of the drop largest score keys outside the kept columns
-  prefix = 0;
-  need = drop;
-  for (int p = 0; p < PS; ++p) {
-    const int shift = kDigitBits * (PS - 1 - p);
-    for (int j = 0; j < chunk; ++j) bins[base + j] = 0u;
-    __syncthreads();
-    for (int s = 0; s < walk.steps; ++s) {
-      int64_t c0;
-      unsigned valid;
-      const Piece<S> v = walk.load(s, &c0, &valid);
-      const unsigned open = valid & ~plane_bits(kept_bits, words, c0);
-#pragma unroll
-      for (int e = 0; e < V; ++e) {
-        const unsigned key = min(key_of(v.e[e]), key_limit);
-        if (((open >> e) & 1u) && static_cast<unsigned>(static_cast<uint64_t>(key) >> (shift + kDigitBits)) == prefix)
-          atomicAdd(&bins[(key >> shift) & (kDigitBins - 1)], 1u);
-      }
-    }
-    __syncthreads();
-    prefix = (prefix << kDigitBits) | pick_digit(bins, base, chunk, group_lane, group_lanes, group_mask, &need);
-    __syncthreads();
-  }
-  const unsigned score_threshold = drop > 0 ? prefix : kNoThreshold;
-  const int score_quota = need;
+  // 3: (T_s, q_s) of the drop largest score keys outside the kept columns, keys clamped
+  const Selection grow = radix_select<PS>(g, bins, drop, [&](int shift, unsigned prefix, unsigned* b) {
+    digit_histogram(walk, shift, prefix, b, key_limit,
+                    [&](int64_t c0) { return ~plane_bits(kept_bits, words, c0); });
+  });
 
   // 4: the new row, ascending, into [begin, end)
   int64_t out = begin;
@@ -938,48 +1055,16 @@ __global__ __launch_bounds__(kBuildBlock) void csr_regrow_kernel(
   ties_seen = 0;      // open columns equal to the threshold in the steps behind
   for (int s = 0; s < walk.steps; ++s) {
     int64_t c0;
-    unsigned valid;
+    unsigned valid, greater, equal;
     const Piece<S> v = walk.load(s, &c0, &valid);
     const unsigned old = valid & plane_bits(old_bits, words, c0);
     const unsigned kept = valid & plane_bits(kept_bits, words, c0);
-    unsigned greater = 0, equal = 0;
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned key = min(key_of(v.e[e]), key_limit);
-      greater |= (key > score_threshold ? 1u : 0u) << e;
-      equal |= (key == score_threshold ? 1u : 0u) << e;
-    }
-    greater &= valid & ~kept;
-    equal &= valid & ~kept;
-    // column order: lane after lane, element after element inside a lane
-    int ties_before = 0, ties_step = 0, old_before = 0, old_step = 0;
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned long long t = __ballot((equal >> e) & 1u);
-      ties_before += __popcll(t & below);
-      ties_step += __popcll(t & group_mask);
-      const unsigned long long o = __ballot((old >> e) & 1u);
-      old_before += __popcll(o & below);
-      old_step += __popcll(o & group_mask);
-    }
-    unsigned flags = kept | greater;
-    int rank = ties_seen + ties_before;
-#pragma unroll
-    for (int e = 0; e < V; ++e)
-      if ((equal >> e) & 1u) {
-        if (rank < score_quota) flags |= 1u << e;
-        ++rank;
-      }
-    ties_seen += ties_step;
-    int before = 0, total = 0;
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned long long b = __ballot((flags >> e) & 1u);
-      before += __popcll(b & below);
-      total += __popcll(b & group_mask);
-    }
-    int64_t p = out + before;
-    int64_t from = static_cast<int64_t>(begin) + old_seen + old_before;   // old entries in front of my piece
+    compare_piece(v, grow.threshold, key_limit, &greater, &equal);
+    const unsigned open = valid & ~kept;
+    const unsigned flags = admit_ties<V>(g, kept | (greater & open), equal & open, grow.quota, &ties_seen);
+    const Prefix at = group_prefix<V>(g, flags), olds = group_prefix<V>(g, old);
+    int64_t p = out + at.before;
+    int64_t from = static_cast<int64_t>(begin) + old_seen + olds.before;   // old entries in front of my piece
 #pragma unroll
     for (int e = 0; e < V; ++e) {
       if (((flags >> e) & 1u) && p < end) {
@@ -991,8 +1076,8 @@ __global__ __launch_bounds__(kBuildBlock) void csr_regrow_kernel(
       }
       from += (old >> e) & 1u;
     }
-    out += total;
-    old_seen += old_step;
+    out += at.total;
+    old_seen += olds.total;
   }
 }
 
@@ -1011,17 +1096,16 @@ int launch_regrow(const RegrowShape& r, int m, int n, int nonzeros, const int* r
 // ---------------------------------------------------------------------------
 // Top-k over the entries of a CSR pattern, written out as a smaller CSR pattern
 // (sputnik_hip_csr_topk): gradual magnitude pruning of a layer that has no dense weight any
-// more.  The keys and the pair (T, q) are those of the dense top-k above; what is ranked are
+// more.  The keys and the Selection are those of the dense top-k above; what is ranked are
 // the nnz stored values, and a kept entry keeps its column, its value bits and its old index.
 // The kept set is the old pattern filtered, so its columns are in order already.
 //   per row   the new lengths min(len_r, k) follow from the offsets alone: one scan launch; then
-//             ONE launch in which the group of lanes that walks a row's entries selects
-//             (T_r, q_r) (histogram in LDS) and fills the row's new slots
-//   total     one launch per digit over the FLAT values array (entries, not rows), a rows
-//             launch for g_r and t_r, the scan launch of the dense top-k, the fill
-// A row's entries are walked like a dense row: values + row_offsets[r] is the row start, the
-// 16-byte pieces are laid out from that address rounded down to 16 bytes.  The group width
-// comes from the mean row length nnz / m; a longer row takes more steps.
+//             ONE launch in which the group of lanes that walks a row's entries runs
+//             radix_select and fill_row into the row's new slots
+//   total     the launches of the dense total mode, the digit passes (flat_digit_pass) over
+//             the FLAT values array (entries, not rows)
+// A row's entries are walked by entry_walk.  The group width comes from the mean row length
+// nnz / m; a longer row takes more steps.
 // ---------------------------------------------------------------------------
 constexpr int kFlatSteps = 8;   // 16-byte pieces per lane of a workgroup of the flat walk
 
@@ -1054,118 +1138,18 @@ inline CsrTopkShape csr_topk_shape(int m, int nonzeros, int value_bytes, int tot
   return s;
 }
 
-// The 16-byte piece whose first element is src[c0], of an array of n elements: one wide load
-// where it lies inside the array, else element by element, inside the array only.
+// fill_row over a row's entries from slot `begin`: a kept entry's column, value bits and old index.
 template <typename U>
-__device__ __forceinline__ Piece<U> load_piece(const U* __restrict__ src, int64_t c0, int64_t n, unsigned* valid) {
-  constexpr int V = kLoadBytes / sizeof(U);
-  Piece<U> v;
-  if (c0 >= 0 && c0 + V <= n) {
-    v = *reinterpret_cast<const Piece<U>*>(src + c0);
-    *valid = (1u << V) - 1u;
-  } else {
-    unsigned in = 0;
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const bool inside = c0 + e >= 0 && c0 + e < n;
-      v.e[e] = inside ? src[c0 + e] : U{0};
-      in |= (inside ? 1u : 0u) << e;
-    }
-    *valid = in;
-  }
-  return v;
-}
-
-// The slots [begin, end) of a row's entries, inside [0, nonzeros) whatever the offsets say.
-__device__ __forceinline__ void row_slots(const int* __restrict__ row_offsets, int64_t row, bool live, int nonzeros,
-                                          int* begin, int* end) {
-  *begin = 0;
-  *end = 0;
-  if (live) {
-    *begin = min(max(row_offsets[row], 0), nonzeros);
-    *end = min(max(row_offsets[row + 1], *begin), nonzeros);
-  }
-}
-
-// The walk of one group of lanes over the entries [begin, end) of its row; every lane of the
-// wave takes as many steps as the wave's longest row needs (the fill's ballots are the wave's).
-template <typename U>
-__device__ __forceinline__ RowWalk<U> entry_walk(const U* __restrict__ values, int begin, int end, bool live,
-                                                 int rows_per_wave) {
-  constexpr int V = kLoadBytes / sizeof(U);
-  RowWalk<U> w;
-  w.n = end - begin;
-  w.group_lanes = kWave / rows_per_wave;
-  w.group_lane = (threadIdx.x % kWave) % w.group_lanes;
-  w.live = live;
-  w.src = values + begin;
-  w.lead = static_cast<int>((reinterpret_cast<uintptr_t>(w.src) % kLoadBytes) / sizeof(U));
-  const int64_t span = static_cast<int64_t>(w.group_lanes) * V;
-  int steps = static_cast<int>((static_cast<int64_t>(w.n) + w.lead + span - 1) / span);
-  for (int o = kWave / 2; o > 0; o >>= 1) steps = max(steps, __shfl_xor(steps, o, kWave));
-  w.steps = steps;
-  return w;
-}
-
-// The entries of the walk's row with key > threshold, and the first `quota` with key ==
-// threshold, into the slots [out, end) in entry order: column, value bits and old index.
-template <typename U>
-__device__ __forceinline__ void csr_fill_row(const RowWalk<U>& walk, int begin, unsigned threshold, int quota,
-                                             int64_t out, int64_t end, unsigned long long group_mask,
-                                             unsigned long long below, const int* __restrict__ column_indices,
+__device__ __forceinline__ void csr_fill_row(const RowGroup& g, const RowWalk<U>& walk, int begin, Selection kept,
+                                             int64_t out, int64_t end, const int* __restrict__ column_indices,
                                              int* __restrict__ out_columns, U* __restrict__ out_values,
                                              int64_t* __restrict__ out_source) {
-  constexpr int V = RowWalk<U>::V;
-  int ties_seen = 0;   // entries equal to the threshold in the steps behind
-  for (int s = 0; s < walk.steps; ++s) {
-    int64_t c0;
-    unsigned valid;
-    const Piece<U> v = walk.load(s, &c0, &valid);
-    unsigned greater = 0, equal = 0;
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned key = key_of(v.e[e]);
-      greater |= (key > threshold ? 1u : 0u) << e;
-      equal |= (key == threshold ? 1u : 0u) << e;
-    }
-    greater &= valid;
-    equal &= valid;
-    // entry order: lane after lane, element after element inside a lane
-    int ties_before = 0, ties_step = 0;
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned long long b = __ballot((equal >> e) & 1u);
-      ties_before += __popcll(b & below);
-      ties_step += __popcll(b & group_mask);
-    }
-    unsigned flags = greater;
-    int rank = ties_seen + ties_before;
-#pragma unroll
-    for (int e = 0; e < V; ++e)
-      if ((equal >> e) & 1u) {
-        if (rank < quota) flags |= 1u << e;
-        ++rank;
-      }
-    ties_seen += ties_step;
-    int before = 0, total = 0;
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned long long b = __ballot((flags >> e) & 1u);
-      before += __popcll(b & below);
-      total += __popcll(b & group_mask);
-    }
-    int64_t p = out + before;
-#pragma unroll
-    for (int e = 0; e < V; ++e)
-      if (((flags >> e) & 1u) && p < end) {
-        const int64_t from = begin + c0 + e;   // (a valid element: inside the row's slots)
-        out_columns[p] = column_indices[from];
-        out_values[p] = v.e[e];
-        out_source[p] = from;
-        ++p;
-      }
-    out += total;
-  }
+  fill_row(g, walk, kept, out, end, [&](int64_t p, int64_t entry, U bits) {
+    const int64_t from = begin + entry;   // (a valid element: inside the row's slots)
+    out_columns[p] = column_indices[from];
+    out_values[p] = bits;
+    out_source[p] = from;
+  });
 }
 
 // The new slots of a row, inside [0, capacity) whatever the offsets say.
@@ -1180,24 +1164,16 @@ __global__ __launch_bounds__(kScanBlock) void csr_topk_lengths_kernel(int m, int
                                                                       const int* __restrict__ row_offsets,
                                                                       int* __restrict__ out_offsets) {
   __shared__ int wave_sums[kScanBlock / kWave];
-  const int t = threadIdx.x;
-  const int64_t per = (static_cast<int64_t>(m) + kScanBlock - 1) / kScanBlock;
-  const int64_t i0 = min(static_cast<int64_t>(m), t * per), i1 = min(static_cast<int64_t>(m), i0 + per);
+  const Span span = thread_span(m);
+  const auto length = [&](int64_t i) {
+    int begin, end;
+    row_slots(row_offsets, i, true, nonzeros, &begin, &end);
+    return min(end - begin, k);
+  };
   int mine = 0;
-  for (int64_t i = i0; i < i1; ++i) {
-    int begin, end;
-    row_slots(row_offsets, i, true, nonzeros, &begin, &end);
-    mine += min(end - begin, k);
-  }
-  int total;
-  int running = block_exclusive_scan(mine, wave_sums, &total);
-  for (int64_t i = i0; i < i1; ++i) {
-    int begin, end;
-    row_slots(row_offsets, i, true, nonzeros, &begin, &end);
-    running += min(end - begin, k);
-    out_offsets[1 + i] = running;
-  }
-  if (t == 0) out_offsets[0] = 0;
+  for (int64_t i = span.begin; i < span.end; ++i) mine += length(i);
+  inclusive_scan_span(span, mine, wave_sums, out_offsets + 1, length);
+  if (threadIdx.x == 0) out_offsets[0] = 0;
 }
 
 // Per-row mode: select and fill of every row in one launch.
@@ -1208,75 +1184,36 @@ __global__ __launch_bounds__(kBuildBlock) void csr_topk_rows_kernel(
     int64_t capacity, int* __restrict__ out_columns, U* __restrict__ out_values, int64_t* __restrict__ out_source) {
   constexpr int P = sizeof(U) * 8 / kDigitBits;
   __shared__ unsigned hist[kBuildWaves * kMaxRowsPerWave][kDigitBins];   // 64 KiB
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  const int group_lanes = kWave / rows_per_wave;
-  const int group = lane / group_lanes, group_lane = lane % group_lanes;
-  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
-  const bool live = row < m;
-  const unsigned long long group_mask =
-      (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
-  const unsigned long long below = group_mask & ((1ull << lane) - 1ull);
+  const RowGroup g(rows_per_wave);
+  const bool live = g.row < m;
   int begin, end;
-  row_slots(row_offsets, row, live, nonzeros, &begin, &end);
-  const RowWalk<U> walk = entry_walk(values, begin, end, live, rows_per_wave);
-  unsigned* __restrict__ bins = hist[wave * rows_per_wave + group];
-  const int chunk = kDigitBins / group_lanes;
-  const int base = group_lane * chunk;
-
-  const int keep = min(end - begin, k);
-  unsigned prefix = 0;
-  int need = keep;
-  for (int p = 0; p < P; ++p) {
-    const int shift = kDigitBits * (P - 1 - p);
-    for (int j = 0; j < chunk; ++j) bins[base + j] = 0u;
-    __syncthreads();
-    digit_histogram(walk, shift, prefix, bins);
-    __syncthreads();
-    prefix = (prefix << kDigitBits) | pick_digit(bins, base, chunk, group_lane, group_lanes, group_mask, &need);
-    __syncthreads();   // (the bins are cleared again)
-  }
-  const unsigned threshold = keep > 0 ? prefix : kNoThreshold;
+  row_slots(row_offsets, g.row, live, nonzeros, &begin, &end);
+  const RowWalk<U> walk = entry_walk(g, values, begin, end, live);
+  const Selection kept = radix_select<P>(g, hist[g.slot], min(end - begin, k),
+                                         [&](int shift, unsigned prefix, unsigned* bins) {
+                                           digit_histogram(walk, shift, prefix, bins);
+                                         });
   int64_t out, out_end;
-  new_slots(out_offsets, row, live, capacity, &out, &out_end);
-  csr_fill_row(walk, begin, threshold, need, out, out_end, group_mask, below, column_indices, out_columns,
-               out_values, out_source);
+  new_slots(out_offsets, g.row, live, capacity, &out, &out_end);
+  csr_fill_row(g, walk, begin, kept, out, out_end, column_indices, out_columns, out_values, out_source);
 }
 
-// Total mode: the global bins of every digit pass start at zero.
-static_assert(kMaxDigitPasses * kDigitBins == kScanBlock, "one thread per bin");
-__global__ __launch_bounds__(kScanBlock) void csr_topk_clear_kernel(unsigned* __restrict__ bins) {
-  bins[threadIdx.x] = 0u;
-}
-
-// Total mode, one digit pass of one workgroup of kBuildBlock threads over a flat values array:
-// the kFlatSteps * 256 pieces of the array's workgroup `block` into an LDS histogram, that into
-// bins[pass][*] with one integer atomic add per non-empty bin.
+// Total mode, one digit pass over a flat values array: workgroup `block` of the array counts
+// its kFlatSteps * 256 pieces.
 template <typename U>
 __device__ __forceinline__ void flat_digit_pass(const U* __restrict__ values, int64_t nonzeros, int64_t block,
                                                 int pass, unsigned count, unsigned* bins) {
-  constexpr int V = kLoadBytes / sizeof(U), P = sizeof(U) * 8 / kDigitBits;
-  __shared__ unsigned hist[kDigitBins];
-  __shared__ unsigned select[kSelectWords];
-  unsigned need;
-  const unsigned prefix = total_select(bins, pass, count, select, &need);
-  hist[threadIdx.x] = 0u;
-  __syncthreads();
-  const int shift = kDigitBits * (P - 1 - pass);
-  const int lead = static_cast<int>((reinterpret_cast<uintptr_t>(values) % kLoadBytes) / sizeof(U));
-  for (int s = 0; s < kFlatSteps; ++s) {
-    const int64_t piece = (block * kFlatSteps + s) * kBuildBlock + threadIdx.x;
-    unsigned valid;
-    const Piece<U> v = load_piece(values, piece * V - lead, nonzeros, &valid);
+  constexpr int V = kLoadBytes / sizeof(U);
+  workgroup_digit_pass<sizeof(U) * 8 / kDigitBits>(pass, count, bins, [&](int shift, unsigned prefix, unsigned* hist) {
+    const int lead = static_cast<int>((reinterpret_cast<uintptr_t>(values) % kLoadBytes) / sizeof(U));
+    for (int s = 0; s < kFlatSteps; ++s) {
+      const int64_t piece = (block * kFlatSteps + s) * kBuildBlock + threadIdx.x;
+      unsigned valid;
+      const Piece<U> v = load_piece(values, piece * V - lead, nonzeros, &valid);
 #pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned key = key_of(v.e[e]);
-      if (((valid >> e) & 1u) && static_cast<unsigned>(static_cast<uint64_t>(key) >> (shift + kDigitBits)) == prefix)
-        atomicAdd(&hist[(key >> shift) & (kDigitBins - 1)], 1u);
+      for (int e = 0; e < V; ++e) count_digit(key_of(v.e[e]), (valid >> e) & 1u, shift, prefix, hist);
     }
-  }
-  __syncthreads();
-  const unsigned c = hist[threadIdx.x];
-  if (c != 0u) atomicAdd(&bins[pass * kDigitBins + threadIdx.x], c);
+  });
 }
 
 template <typename U>
@@ -1292,40 +1229,12 @@ __global__ __launch_bounds__(kBuildBlock) void csr_topk_total_rows_kernel(
     int m, int nonzeros, int rows_per_wave, unsigned count, const int* __restrict__ row_offsets,
     const U* __restrict__ values, const unsigned* __restrict__ bins, int* __restrict__ out_offsets,
     int* __restrict__ ties) {
-  constexpr int V = RowWalk<U>::V, P = sizeof(U) * 8 / kDigitBits;
-  __shared__ unsigned select[kSelectWords];
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  const int group_lanes = kWave / rows_per_wave;
-  const int group = lane / group_lanes, group_lane = lane % group_lanes;
-  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
-  const bool live = row < m;
-  unsigned need;
-  const unsigned prefix = total_select(bins, P, count, select, &need);
-  const unsigned threshold = count > 0 ? prefix : kNoThreshold;
+  const RowGroup g(rows_per_wave);
+  const bool live = g.row < m;
   int begin, end;
-  row_slots(row_offsets, row, live, nonzeros, &begin, &end);
-  const RowWalk<U> walk = entry_walk(values, begin, end, live, rows_per_wave);
-  int greater = 0, equal = 0;
-  for (int s = 0; s < walk.steps; ++s) {
-    int64_t c0;
-    unsigned valid;
-    const Piece<U> v = walk.load(s, &c0, &valid);
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const unsigned key = key_of(v.e[e]);
-      const bool in = (valid >> e) & 1u;
-      greater += in && key > threshold ? 1 : 0;
-      equal += in && key == threshold ? 1 : 0;
-    }
-  }
-  for (int o = group_lanes / 2; o > 0; o >>= 1) {
-    greater += __shfl_xor(greater, o, kWave);
-    equal += __shfl_xor(equal, o, kWave);
-  }
-  if (live && group_lane == 0) {
-    out_offsets[row + 1] = greater;
-    ties[row] = equal;
-  }
+  row_slots(row_offsets, g.row, live, nonzeros, &begin, &end);
+  const RowWalk<U> walk = entry_walk(g, values, begin, end, live);
+  count_against_total(g, walk, count, bins, out_offsets + 1, ties);
 }
 
 // Total mode: the fill of every row under the one threshold and the rows' quotas.
@@ -1335,28 +1244,22 @@ __global__ __launch_bounds__(kBuildBlock) void csr_topk_total_fill_kernel(
     const int* __restrict__ column_indices, const U* __restrict__ values, const unsigned* __restrict__ threshold,
     const int* __restrict__ quotas, const int* __restrict__ out_offsets, int64_t capacity,
     int* __restrict__ out_columns, U* __restrict__ out_values, int64_t* __restrict__ out_source) {
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  const int group_lanes = kWave / rows_per_wave;
-  const int group = lane / group_lanes;
-  const int64_t row = (static_cast<int64_t>(blockIdx.x) * kBuildWaves + wave) * rows_per_wave + group;
-  const bool live = row < m;
-  const unsigned long long group_mask =
-      (group_lanes == kWave ? ~0ull : (1ull << group_lanes) - 1ull) << (group * group_lanes);
-  const unsigned long long below = group_mask & ((1ull << lane) - 1ull);
+  const RowGroup g(rows_per_wave);
+  const bool live = g.row < m;
   int begin, end;
-  row_slots(row_offsets, row, live, nonzeros, &begin, &end);
-  const RowWalk<U> walk = entry_walk(values, begin, end, live, rows_per_wave);
+  row_slots(row_offsets, g.row, live, nonzeros, &begin, &end);
+  const RowWalk<U> walk = entry_walk(g, values, begin, end, live);
   int64_t out, out_end;
-  new_slots(out_offsets, row, live, capacity, &out, &out_end);
-  csr_fill_row(walk, begin, *threshold, live ? quotas[row] : 0, out, out_end, group_mask, below, column_indices,
-               out_columns, out_values, out_source);
+  new_slots(out_offsets, g.row, live, capacity, &out, &out_end);
+  csr_fill_row(g, walk, begin, {*threshold, live ? quotas[g.row] : 0}, out, out_end, column_indices, out_columns,
+               out_values, out_source);
 }
 
 // `fill`: the output arrays are there.  Per-row mode with `offsets`: the scan launch first.
 template <typename U>
 int launch_csr_topk(const CsrTopkShape& s, int m, int nonzeros, const int* row_offsets, const int* column_indices,
                     const void* values_, int total_mode, unsigned count, bool offsets, bool fill,
-                    unsigned* workspace, int* out_offsets, int64_t capacity, int* out_columns, void* out_values_,
+                    void* workspace, int* out_offsets, int64_t capacity, int* out_columns, void* out_values_,
                     int64_t* out_source, hipStream_t stream) {
   const U* values = static_cast<const U*>(values_);
   U* out_values = static_cast<U*>(out_values_);
@@ -1371,21 +1274,17 @@ int launch_csr_topk(const CsrTopkShape& s, int m, int nonzeros, const int* row_o
                          out_columns, out_values, out_source);
     return launch_status();
   }
-  unsigned* bins = workspace;
-  unsigned* th = workspace + kMaxDigitPasses * kDigitBins;
-  int* q = reinterpret_cast<int*>(th + 1);
-  int* ties = q + m;
-  hipLaunchKernelGGL(csr_topk_clear_kernel, dim3(1), dim3(kScanBlock), 0, stream, bins);
-  for (int p = 0; p < s.digit_passes; ++p)
+  const TotalWorkspace w(workspace, false);
+  launch_digit_passes(w.bins, s.digit_passes, stream, [&](int p) {
     hipLaunchKernelGGL((csr_topk_flat_hist_kernel<U>), dim3(s.flat_grid), block, 0, stream, nonzeros, p, count,
-                       values, bins);
+                       values, w.bins);
+  });
   hipLaunchKernelGGL((csr_topk_total_rows_kernel<U>), grid, block, 0, stream, m, nonzeros, s.rows_per_wave, count,
-                     row_offsets, values, bins, out_offsets, ties);
-  hipLaunchKernelGGL(topk_total_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, m, s.digit_passes, count, bins,
-                     ties, q, out_offsets, th);
+                     row_offsets, values, w.bins, out_offsets, w.quotas() + m);
+  launch_total_scan(w, w.quotas(), m, s.digit_passes, count, out_offsets, true, nullptr, stream);
   hipLaunchKernelGGL((csr_topk_total_fill_kernel<U>), grid, block, 0, stream, m, nonzeros, s.rows_per_wave,
-                     row_offsets, column_indices, values, th, q, out_offsets, capacity, out_columns, out_values,
-                     out_source);
+                     row_offsets, column_indices, values, w.threshold, w.quotas(), out_offsets, capacity,
+                     out_columns, out_values, out_source);
   return launch_status();
 }
 
@@ -1398,9 +1297,9 @@ int launch_csr_topk(const CsrTopkShape& s, int m, int nonzeros, const int* row_o
 //            and its piece range in a table that travels as a kernel argument; more layers
 //            take further launches of the same pass, which add into the same bins
 //   rows     per layer, csr_topk_total_rows_kernel under the shared bins and count
-//   scan     per layer and in layer order, one workgroup: the scan of the total mode with the
-//            ties handed out to the layers in front read from (and this layer's added to) one
-//            word of the workspace; the layer's new size lands in sizes[layer]
+//   scan     per layer and in layer order, total_scan_kernel with the ties handed out to the
+//            layers in front read from (and this layer's added to) one word of the workspace;
+//            the layer's new size lands in sizes[layer]
 //   fill     per layer, csr_topk_total_fill_kernel and the row order, once the caller has read
 //            the sizes and has the arrays
 // ---------------------------------------------------------------------------
@@ -1450,10 +1349,7 @@ inline GlobalTopkShape global_topk_shape(int layers, const int* rows, const int*
   g.digit_launches = static_cast<int>(ceil_div64(layers, kGlobalLayers));
   return g;
 }
-// bins, T, the ties handed out so far; then per layer the quotas and the ties of its rows
-inline size_t global_topk_workspace_words(int64_t rows) {
-  return static_cast<size_t>(kMaxDigitPasses) * kDigitBins + 2 + 2 * static_cast<size_t>(rows);
-}
+inline size_t global_topk_workspace_words(int64_t rows) { return TotalWorkspace::words(rows, true); }
 
 // One digit pass over the flat values arrays of the table's layers: flat_digit_pass with the
 // layer and the workgroup's place inside it looked up first.
@@ -1468,72 +1364,13 @@ __global__ __launch_bounds__(kBuildBlock) void csr_topk_global_hist_kernel(Globa
                   static_cast<int64_t>(block - table.first_block[layer]), pass, count, bins);
 }
 
-// topk_total_scan_kernel for one layer of several: the quota left for this layer is Q less
-// *handed (the ties of the layers in front; none for handed_in == nullptr, the first layer).
-// *handed_out = that plus this layer's ties; *new_size = the layer's kept entries.
-__global__ __launch_bounds__(kScanBlock) void csr_topk_global_scan_kernel(
-    int m, int digit_passes, unsigned count, const unsigned* __restrict__ bins, const int* __restrict__ ties,
-    int* __restrict__ quotas, int* __restrict__ offsets, unsigned* __restrict__ threshold,
-    const unsigned* handed_in, unsigned* handed_out, int* __restrict__ new_size) {
-  __shared__ int wave_sums[kScanBlock / kWave];
-  __shared__ unsigned select[kSelectWords];
-  const int64_t in_front = handed_in != nullptr ? static_cast<int64_t>(*handed_in) : int64_t{0};
-  unsigned need;
-  const unsigned prefix = total_select(bins, digit_passes, count, select, &need);   // (barriers: *handed_in is read)
-  const int64_t quota = static_cast<int64_t>(need) - in_front;
-  const int t = threadIdx.x;
-  const int64_t per = (static_cast<int64_t>(m) + kScanBlock - 1) / kScanBlock;
-  const int64_t i0 = min(static_cast<int64_t>(m), t * per), i1 = min(static_cast<int64_t>(m), i0 + per);
-  int mine = 0;
-  for (int64_t i = i0; i < i1; ++i) mine += ties[i];
-  int tied_here;
-  int64_t ties_before = block_exclusive_scan(mine, wave_sums, &tied_here);
-  __syncthreads();   // (wave_sums is written again)
-  mine = 0;
-  for (int64_t i = i0; i < i1; ++i) {
-    const int tied = ties[i];
-    const int q = static_cast<int>(max(int64_t{0}, min(static_cast<int64_t>(tied), quota - ties_before)));
-    ties_before += tied;
-    quotas[i] = q;
-    const int length = offsets[1 + i] + q;
-    offsets[1 + i] = length;
-    mine += length;
-  }
-  int total;
-  int running = block_exclusive_scan(mine, wave_sums, &total);
-  for (int64_t i = i0; i < i1; ++i) {
-    running += offsets[1 + i];
-    offsets[1 + i] = running;
-  }
-  if (t == 0) {
-    offsets[0] = 0;
-    *threshold = count > 0 ? prefix : kNoThreshold;
-    *handed_out = static_cast<unsigned>(in_front + tied_here);
-    *new_size = total;
-  }
-}
-
-struct GlobalWorkspace {
-  unsigned *bins, *threshold, *handed;
-  int* rows;   // per layer: quotas [m], ties [m]
-};
-inline GlobalWorkspace global_workspace(void* workspace) {
-  GlobalWorkspace w;
-  w.bins = static_cast<unsigned*>(workspace);
-  w.threshold = w.bins + kMaxDigitPasses * kDigitBins;
-  w.handed = w.threshold + 1;
-  w.rows = reinterpret_cast<int*>(w.handed + 1);
-  return w;
-}
-
 template <typename U>
 int launch_global_select(const GlobalTopkShape& g, int layers, const int* rows, const int* nonzeros,
                          const int* const* row_offsets, const void* const* values, unsigned count,
                          void* workspace, int* const* out_offsets, int* out_sizes, hipStream_t stream) {
-  const GlobalWorkspace w = global_workspace(workspace);
+  const TotalWorkspace w(workspace, true);
   const dim3 block(kBuildBlock);
-  hipLaunchKernelGGL(csr_topk_clear_kernel, dim3(1), dim3(kScanBlock), 0, stream, w.bins);
-  for (int p = 0; p < g.digit_passes; ++p)
+  launch_digit_passes(w.bins, g.digit_passes, stream, [&](int p) {
     for (int l0 = 0; l0 < layers; l0 += kGlobalLayers) {
       GlobalTable table;
       int grid = 0;
@@ -1548,20 +1385,18 @@ int launch_global_select(const GlobalTopkShape& g, int layers, const int* rows, 
       if (grid > 0)
         hipLaunchKernelGGL((csr_topk_global_hist_kernel<U>), dim3(grid), block, 0, stream, table, p, count, w.bins);
     }
-  int* per_row = w.rows;
+  });
+  int64_t rows_in_front = 0;
   for (int l = 0; l < layers; ++l) {
     const int m = rows[l];
     const CsrTopkShape s = csr_topk_shape(m, nonzeros[l], static_cast<int>(sizeof(U)), 1);
-    int* q = per_row;
-    int* ties = q + m;
-    per_row = ties + m;
+    int* q = w.quotas(rows_in_front);
+    rows_in_front += m;
     if (m > 0)
       hipLaunchKernelGGL((csr_topk_total_rows_kernel<U>), dim3(s.rows_grid), block, 0, stream, m, nonzeros[l],
                          s.rows_per_wave, count, row_offsets[l], static_cast<const U*>(values[l]), w.bins,
-                         out_offsets[l], ties);
-    hipLaunchKernelGGL(csr_topk_global_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, m, g.digit_passes, count,
-                       w.bins, ties, q, out_offsets[l], w.threshold,
-                       l == 0 ? static_cast<const unsigned*>(nullptr) : w.handed, w.handed, out_sizes + l);
+                         out_offsets[l], q + m);
+    launch_total_scan(w, q, m, g.digit_passes, count, out_offsets[l], l == 0, out_sizes + l, stream);
   }
   return launch_status();
 }
@@ -1571,13 +1406,13 @@ int launch_global_fill(int layers, const int* rows, const int* nonzeros, const i
                        const int* const* column_indices, const void* const* values, void* workspace,
                        const int64_t* capacity, int* const* out_offsets, int* const* out_columns,
                        void* const* out_values, int64_t* const* out_source, hipStream_t stream) {
-  const GlobalWorkspace w = global_workspace(workspace);
-  const int* per_row = w.rows;
+  const TotalWorkspace w(workspace, true);
+  int64_t rows_in_front = 0;
   for (int l = 0; l < layers; ++l) {
     const int m = rows[l];
     const CsrTopkShape s = csr_topk_shape(m, nonzeros[l], static_cast<int>(sizeof(U)), 1);
-    const int* q = per_row;
-    per_row += 2 * static_cast<int64_t>(m);
+    const int* q = w.quotas(rows_in_front);
+    rows_in_front += m;
     if (m == 0 || capacity[l] == 0) continue;   // (nothing of this layer is kept)
     hipLaunchKernelGGL((csr_topk_total_fill_kernel<U>), dim3(s.rows_grid), dim3(kBuildBlock), 0, stream, m,
                        nonzeros[l], s.rows_per_wave, row_offsets[l], column_indices[l],
@@ -1585,6 +1420,10 @@ int launch_global_fill(int layers, const int* rows, const int* nonzeros, const i
                        static_cast<U*>(out_values[l]), out_source[l]);
   }
   return launch_status();
+}
+
+inline void put(int* p, int v) {
+  if (p) *p = v;
 }
 
 }  // namespace
@@ -1598,10 +1437,10 @@ int sputnik_hip_dense_to_csr_launch_shape(int masks, int m, int n, int element_b
                                           int* elements_per_lane, int* rows_per_workgroup, int* grid) {
   const BuildShape s = build_shape(masks, m, n, element_bytes);
   if (s.status != 0) return s.status;
-  if (rows_per_wave) *rows_per_wave = s.rows_per_wave;
-  if (elements_per_lane) *elements_per_lane = s.elements_per_lane;
-  if (rows_per_workgroup) *rows_per_workgroup = s.rows_per_workgroup;
-  if (grid) *grid = s.grid;
+  put(rows_per_wave, s.rows_per_wave);
+  put(elements_per_lane, s.elements_per_lane);
+  put(rows_per_workgroup, s.rows_per_workgroup);
+  put(grid, s.grid);
   return 0;
 }
 
@@ -1646,10 +1485,10 @@ int sputnik_hip_csr_row_order_route(int masks, int m, int n, int* served, int* c
                                     int* sort_size) {
   const OrderRoute r = order_route(masks, m, n);
   if (r.status != 0) return r.status;
-  if (served) *served = r.served;
-  if (capacity) *capacity = r.capacity;
-  if (threads) *threads = r.threads;
-  if (sort_size) *sort_size = r.sort_size;
+  put(served, r.served);
+  put(capacity, r.capacity);
+  put(threads, r.threads);
+  put(sort_size, r.sort_size);
   return 0;
 }
 
@@ -1675,12 +1514,12 @@ int sputnik_hip_topk_to_csr_launch_shape(int m, int n, int element_bytes, int to
                                          int* digit_passes, int* grid) {
   const TopkShape t = topk_shape(m, n, element_bytes, total_mode);
   if (t.status != 0) return t.status;
-  if (served) *served = t.served;
-  if (rows_per_wave) *rows_per_wave = t.walk.rows_per_wave;
-  if (elements_per_lane) *elements_per_lane = t.walk.elements_per_lane;
-  if (rows_per_workgroup) *rows_per_workgroup = t.walk.rows_per_workgroup;
-  if (digit_passes) *digit_passes = t.digit_passes;
-  if (grid) *grid = t.walk.grid;
+  put(served, t.served);
+  put(rows_per_wave, t.walk.rows_per_wave);
+  put(elements_per_lane, t.walk.elements_per_lane);
+  put(rows_per_workgroup, t.walk.rows_per_workgroup);
+  put(digit_passes, t.digit_passes);
+  put(grid, t.walk.grid);
   return 0;
 }
 
@@ -1711,14 +1550,11 @@ int sputnik_hip_topk_to_csr(int m, int n, const void* scores, int element_bytes,
       ((value_bytes != 2 && value_bytes != 4) || values_row_stride < 0 || !aligned_to(values, value_bytes) ||
        (nonzeros > 0 && (values_from == nullptr || !aligned_to(values_from, value_bytes)))))
     return SPUTNIK_HIP_INVALID_ARGUMENT;
-  const int st =
-      element_bytes == 2
-          ? launch_topk<uint16_t>(t, m, n, scores, row_stride, total_mode, static_cast<unsigned>(count), values_from,
-                                  value_bytes, values_row_stride, static_cast<unsigned*>(workspace), row_indices,
-                                  row_offsets, column_indices, values, stream)
-          : launch_topk<uint32_t>(t, m, n, scores, row_stride, total_mode, static_cast<unsigned>(count), values_from,
-                                  value_bytes, values_row_stride, static_cast<unsigned*>(workspace), row_indices,
-                                  row_offsets, column_indices, values, stream);
+  const int st = by_width(element_bytes, [&](auto u) {
+    return launch_topk<decltype(u)>(t, m, n, scores, row_stride, total_mode, static_cast<unsigned>(count), values_from,
+                                    value_bytes, values_row_stride, static_cast<unsigned*>(workspace), row_indices,
+                                    row_offsets, column_indices, values, stream);
+  });
   if (st != 0 || !total_mode) return st;
   return sputnik_hip_csr_row_order(1, m, n, row_offsets, row_indices, stream_);
 }
@@ -1729,15 +1565,15 @@ int sputnik_hip_csr_regrow_launch_shape(int m, int n, int score_bytes, int value
                                         int* max_n, int* grid) {
   const RegrowShape r = regrow_shape(m, n, score_bytes, value_bytes);
   if (r.status != 0) return r.status;
-  if (served) *served = r.served;
-  if (rows_per_wave) *rows_per_wave = r.rows_per_wave;
-  if (elements_per_lane) *elements_per_lane = r.elements_per_lane;
-  if (rows_per_workgroup) *rows_per_workgroup = r.rows_per_workgroup;
-  if (value_digit_passes) *value_digit_passes = r.value_passes;
-  if (score_digit_passes) *score_digit_passes = r.score_passes;
-  if (lds_bytes) *lds_bytes = r.lds_bytes;
-  if (max_n) *max_n = r.max_n;
-  if (grid) *grid = r.grid;
+  put(served, r.served);
+  put(rows_per_wave, r.rows_per_wave);
+  put(elements_per_lane, r.elements_per_lane);
+  put(rows_per_workgroup, r.rows_per_workgroup);
+  put(value_digit_passes, r.value_passes);
+  put(score_digit_passes, r.score_passes);
+  put(lds_bytes, r.lds_bytes);
+  put(max_n, r.max_n);
+  put(grid, r.grid);
   return 0;
 }
 
@@ -1764,16 +1600,13 @@ int sputnik_hip_csr_regrow(int m, int n, int nonzeros, const int* row_offsets, c
       !aligned_to(drop_counts, sizeof(int)) || !aligned_to(out_column_indices, sizeof(int)))
     return SPUTNIK_HIP_INVALID_ARGUMENT;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-#define SPUTNIK_REGROW(S, W)                                                                                \
-  return launch_regrow<S, W>(r, m, n, nonzeros, row_offsets, column_indices, values, drop_counts, scores, \
-                             scores_row_stride, score_key_limit, out_column_indices, out_values, out_source, stream)
-  if (score_bytes == 2) {
-    if (value_bytes == 2) SPUTNIK_REGROW(uint16_t, uint16_t);
-    SPUTNIK_REGROW(uint16_t, uint32_t);
-  }
-  if (value_bytes == 2) SPUTNIK_REGROW(uint32_t, uint16_t);
-  SPUTNIK_REGROW(uint32_t, uint32_t);
-#undef SPUTNIK_REGROW
+  return by_width(score_bytes, [&](auto s) {
+    return by_width(value_bytes, [&](auto w) {
+      return launch_regrow<decltype(s), decltype(w)>(r, m, n, nonzeros, row_offsets, column_indices, values,
+                                                     drop_counts, scores, scores_row_stride, score_key_limit,
+                                                     out_column_indices, out_values, out_source, stream);
+    });
+  });
 }
 
 int sputnik_hip_csr_topk_launch_shape(int m, int n, int nonzeros, int value_bytes, int total_mode, int* served,
@@ -1782,14 +1615,14 @@ int sputnik_hip_csr_topk_launch_shape(int m, int n, int nonzeros, int value_byte
   if (n < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
   const CsrTopkShape s = csr_topk_shape(m, nonzeros, value_bytes, total_mode);
   if (s.status != 0) return s.status;
-  if (served) *served = s.served;
-  if (rows_per_wave) *rows_per_wave = s.rows_per_wave;
-  if (group_lanes) *group_lanes = s.group_lanes;
-  if (elements_per_lane) *elements_per_lane = s.elements_per_lane;
-  if (rows_per_workgroup) *rows_per_workgroup = s.rows_per_workgroup;
-  if (digit_passes) *digit_passes = s.digit_passes;
-  if (rows_grid) *rows_grid = s.rows_grid;
-  if (flat_grid) *flat_grid = s.flat_grid;
+  put(served, s.served);
+  put(rows_per_wave, s.rows_per_wave);
+  put(group_lanes, s.group_lanes);
+  put(elements_per_lane, s.elements_per_lane);
+  put(rows_per_workgroup, s.rows_per_workgroup);
+  put(digit_passes, s.digit_passes);
+  put(rows_grid, s.rows_grid);
+  put(flat_grid, s.flat_grid);
   return 0;
 }
 
@@ -1837,15 +1670,11 @@ int sputnik_hip_csr_topk(int m, int n, int nonzeros, const int* row_offsets, con
     if (offsets && hipMemsetAsync(out_row_offsets, 0, sizeof(int) * (static_cast<size_t>(m) + 1), stream) != hipSuccess)
       return launch_status();
   } else {
-    const int st = value_bytes == 2
-                       ? launch_csr_topk<uint16_t>(s, m, nonzeros, row_offsets, column_indices, values, total_mode,
-                                                   static_cast<unsigned>(count), offsets, fill,
-                                                   static_cast<unsigned*>(workspace), out_row_offsets, out_capacity,
-                                                   out_column_indices, out_values, out_source, stream)
-                       : launch_csr_topk<uint32_t>(s, m, nonzeros, row_offsets, column_indices, values, total_mode,
-                                                   static_cast<unsigned>(count), offsets, fill,
-                                                   static_cast<unsigned*>(workspace), out_row_offsets, out_capacity,
-                                                   out_column_indices, out_values, out_source, stream);
+    const int st = by_width(value_bytes, [&](auto u) {
+      return launch_csr_topk<decltype(u)>(s, m, nonzeros, row_offsets, column_indices, values, total_mode,
+                                          static_cast<unsigned>(count), offsets, fill, workspace, out_row_offsets,
+                                          out_capacity, out_column_indices, out_values, out_source, stream);
+    });
     if (st != 0) return st;
   }
   if (out_row_indices == nullptr || m == 0) return launch_status();
@@ -1857,11 +1686,11 @@ int sputnik_hip_csr_topk_global_launch_shape(int layers, const int* rows, const 
                                              int* elements_per_workgroup, int* digit_launches) {
   const GlobalTopkShape g = global_topk_shape(layers, rows, nonzeros, value_bytes);
   if (g.status != 0) return g.status;
-  if (served) *served = g.served;
-  if (digit_passes) *digit_passes = g.digit_passes;
-  if (layers_per_launch) *layers_per_launch = g.layers_per_launch;
-  if (elements_per_workgroup) *elements_per_workgroup = g.elements_per_workgroup;
-  if (digit_launches) *digit_launches = g.digit_launches;
+  put(served, g.served);
+  put(digit_passes, g.digit_passes);
+  put(layers_per_launch, g.layers_per_launch);
+  put(elements_per_workgroup, g.elements_per_workgroup);
+  put(digit_launches, g.digit_launches);
   return 0;
 }
 
@@ -1893,12 +1722,11 @@ int sputnik_hip_csr_topk_global_select(int layers, const int* rows, const int* n
         (nonzeros[l] > 0 && (values[l] == nullptr || !aligned_to(values[l], value_bytes))))
       return SPUTNIK_HIP_INVALID_ARGUMENT;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  return value_bytes == 2 ? launch_global_select<uint16_t>(g, layers, rows, nonzeros, row_offsets, values,
-                                                           static_cast<unsigned>(count), workspace,
-                                                           out_row_offsets, out_nonzeros, stream)
-                          : launch_global_select<uint32_t>(g, layers, rows, nonzeros, row_offsets, values,
-                                                           static_cast<unsigned>(count), workspace,
-                                                           out_row_offsets, out_nonzeros, stream);
+  return by_width(value_bytes, [&](auto u) {
+    return launch_global_select<decltype(u)>(g, layers, rows, nonzeros, row_offsets, values,
+                                             static_cast<unsigned>(count), workspace, out_row_offsets, out_nonzeros,
+                                             stream);
+  });
 }
 
 int sputnik_hip_csr_topk_global_fill(int layers, const int* rows, const int* nonzeros,
@@ -1933,13 +1761,11 @@ int sputnik_hip_csr_topk_global_fill(int layers, const int* rows, const int* non
       return SPUTNIK_HIP_INVALID_ARGUMENT;
   }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const int st = value_bytes == 2
-                     ? launch_global_fill<uint16_t>(layers, rows, nonzeros, row_offsets, column_indices, values,
-                                                    workspace, out_capacity, out_row_offsets, out_column_indices,
-                                                    out_values, out_source, stream)
-                     : launch_global_fill<uint32_t>(layers, rows, nonzeros, row_offsets, column_indices, values,
-                                                    workspace, out_capacity, out_row_offsets, out_column_indices,
-                                                    out_values, out_source, stream);
+  const int st = by_width(value_bytes, [&](auto u) {
+    return launch_global_fill<decltype(u)>(layers, rows, nonzeros, row_offsets, column_indices, values, workspace,
+                                           out_capacity, out_row_offsets, out_column_indices, out_values, out_source,
+                                           stream);
+  });
   if (st != 0) return st;
   for (int l = 0; l < layers; ++l)
     if (rows[l] > 0) {
