@@ -1520,6 +1520,83 @@ SPUTNIK_HIP_API int sputnik_hip_csr_regrow_launch_shape(int m, int n, int score_
                              int* score_digit_passes, int* lds_bytes, int* max_n, int* grid);
 
 /* ------------------------------------------------------------------------
+ * Matrix-wide drop-and-grow of a CSR topology (topology.regrow_total,
+ * SparseLinear.update_topology / rigl_update with per_row=False): the layer-wise rule of SET and
+ * RigL.  The number of entries stays, the row lengths change.
+ *
+ * Inputs (device): the pattern, values and scores of sputnik_hip_csr_regrow, and a HOST count
+ * `drop` = d, 0 <= d <= nonzeros.  KEYS are those of sputnik_hip_topk_to_csr.
+ *   Kept    the nonzeros - d entries of largest value key, ties to the lower entry index
+ *   Grown   the d positions outside Kept of largest score key, ties to the lower flat (row-major)
+ *           index; a score key is clamped to `score_key_limit` as in sputnik_hip_csr_regrow.
+ *           Positions dropped in this call are eligible.
+ * Outputs (device): the CSR pattern of Kept and Grown, exactly `nonzeros` entries:
+ * out_row_offsets [m + 1], out_row_indices [m] (the rows by ascending new length, ties by row),
+ * out_column_indices [nonzeros] ascending inside a row, out_values [nonzeros] (a kept entry's old
+ * value bit for bit, all bits zero for a grown one), out_source [nonzeros] (int64: a kept entry's
+ * old index, -1 for a grown one).  d = 0 reproduces the pattern.
+ *
+ * Every size is known up front: the call enqueues its launches, reads nothing back and can be
+ * captured in a graph.  Launches (sputnik_hip_csr_regrow_total_launch_shape counts them): a clear
+ * launch for the bins of both selections; over the flat values array the digit launches, the
+ * rows launch and the scan of sputnik_hip_csr_topk's total mode with count nonzeros - d; a planes
+ * launch that marks every row's old and kept columns in two bit planes (built in LDS, written to
+ * the workspace by the lanes that own the row); over the dense score rows one digit launch per
+ * score digit with the kept plane as a mask and the keys clamped, a rows launch and the scan that
+ * gives the new offsets; the fill; the row order.  All counting is integer, every store a vector
+ * store to a slot one lane owns: two calls give equal arrays.  `workspace`:
+ * sputnik_hip_csr_regrow_total_workspace_bytes(...) bytes, 4-byte aligned, the call's own until
+ * its launches have run (it need not be cleared): two sets of 4 x 256 bins, thresholds, quotas
+ * and tie counts per row, the kept lengths, and the planes, 2 * m * ceil(n / 32) words.
+ * m = 0 or nonzeros = 0 writes the zero offsets and the row order and nothing else.  A column
+ * index outside 0 .. n - 1, a column stored twice or offsets that do not ascend inside
+ * 0 .. nonzeros are caller errors with an unspecified result, but nothing outside the arrays is
+ * read or written.
+ *
+ * SPUTNIK_HIP_INVALID_ARGUMENT, before any launch: an element width other than 2 / 4, a negative
+ * size or stride, d outside 0 .. nonzeros, m above 16384 (the row order and the scan), n above
+ * 65536 (the LDS planes), m * n above INT_MAX, a missing or misaligned pointer, a workspace too
+ * small.
+ * ---------------------------------------------------------------------- */
+SPUTNIK_HIP_API int sputnik_hip_csr_regrow_total(int m, int n, int nonzeros, const int* row_offsets,
+                             const int* column_indices, const void* values, int value_bytes,
+                             int64_t drop, const void* scores, int score_bytes,
+                             int64_t scores_row_stride, unsigned score_key_limit, void* workspace,
+                             size_t workspace_bytes, int* out_row_indices, int* out_row_offsets,
+                             int* out_column_indices, void* out_values, int64_t* out_source,
+                             sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API size_t sputnik_hip_csr_regrow_total_workspace_bytes(int m, int n, int nonzeros);
+
+/* The instances sputnik_hip_csr_regrow_total runs for a call of this shape; the entry takes its
+ * decisions from the same function this reports, and from nothing else.
+ *   served               1 for m <= max_m and n <= max_n, else 0 (every field but the two limits
+ *                        is -1 then)
+ *   max_m                16384: the rows sputnik_hip_csr_row_order and the scan serve
+ *   max_n                65536: four rows per workgroup, two bits per column each, in the 64 KiB
+ *                        of LDS the planes launch gets without asking for more
+ *   rows_per_wave, elements_per_lane, rows_per_workgroup, grid
+ *                        the walk of every launch over the score rows (and of the planes launch):
+ *                        that of sputnik_hip_dense_to_csr_launch_shape(1, m, n, score_bytes)
+ *   value_digit_passes, score_digit_passes
+ *                        8-bit digits of a value key and of a score key: the element bytes
+ *   lds_bytes            dynamic LDS of the planes launch: rows_per_workgroup * 8 * ceil(n / 32)
+ *   value_rows_per_wave, value_rows_grid, flat_grid
+ *                        the launches over the old entries: rows_per_wave, rows_grid and flat_grid
+ *                        of sputnik_hip_csr_topk_launch_shape(m, n, nonzeros, value_bytes, 1)
+ *   launches             kernels one call enqueues: 8 + value_digit_passes + score_digit_passes;
+ *                        1 (the row order) for nonzeros = 0, 0 for m = 0
+ * Host only, launches nothing; any output pointer may be NULL.  Returns
+ * SPUTNIK_HIP_INVALID_ARGUMENT for a negative size, an element width other than 2 / 4 and
+ * m * n above INT_MAX. */
+SPUTNIK_HIP_API int sputnik_hip_csr_regrow_total_launch_shape(int m, int n, int nonzeros, int score_bytes,
+                             int value_bytes, int* served, int* rows_per_wave, int* elements_per_lane,
+                             int* rows_per_workgroup, int* value_digit_passes, int* score_digit_passes,
+                             int* lds_bytes, int* max_m, int* max_n, int* grid,
+                             int* value_rows_per_wave, int* value_rows_grid, int* flat_grid,
+                             int* launches);
+
+/* ------------------------------------------------------------------------
  * Top-k over the entries of a CSR pattern, written out as a smaller CSR pattern
  * (topology.prune_csr, SparseLinear.prune_to): gradual magnitude pruning of a layer that has
  * no dense weight any more.

@@ -112,6 +112,10 @@ SIGNATURES = {
                                         ctypes.c_uint, _c_ptr, _c_size] + [_c_ptr] * 4),
     "sputnik_hip_csr_regrow_workspace_bytes": (_c_size, [_c_int] * 3),
     "sputnik_hip_csr_regrow_launch_shape": (_c_int, [_c_int] * 4 + [_c_ptr] * 9),
+    "sputnik_hip_csr_regrow_total": (_c_int, [_c_int] * 3 + [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_i64, _c_ptr, _c_int,
+                                              _c_i64, ctypes.c_uint, _c_ptr, _c_size] + [_c_ptr] * 6),
+    "sputnik_hip_csr_regrow_total_workspace_bytes": (_c_size, [_c_int] * 3),
+    "sputnik_hip_csr_regrow_total_launch_shape": (_c_int, [_c_int] * 5 + [_c_ptr] * 14),
     "sputnik_hip_csr_topk": (_c_int, [_c_int] * 3 + [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_int, _c_i64, _c_ptr, _c_size]
                              + [_c_ptr] * 5 + [_c_i64, _c_ptr]),
     "sputnik_hip_csr_topk_workspace_bytes": (_c_size, [_c_int] * 4),
@@ -573,6 +577,32 @@ def csr_regrow_launch_shape(m, n, score_bytes, value_bytes):
     shape = {name: o.value for name, o in zip(names, outs)}
     shape["served"] = bool(shape["served"])
     return shape
+
+
+def csr_regrow_total_launch_shape(m, n, nonzeros, score_bytes, value_bytes):
+    """The instances of the matrix-wide drop-and-grow step for an m x n pattern of `nonzeros`
+    entries with scores and values of those widths (2 or 4 bytes): a dict of served (bool:
+    m <= max_m and n <= max_n; the fields but the two limits are -1 where it is not),
+    rows_per_wave, elements_per_lane, rows_per_workgroup, value_digit_passes, score_digit_passes,
+    lds_bytes, max_m, max_n, grid, value_rows_per_wave, value_rows_grid, flat_grid and launches
+    (include/sputnik_hip.h).  Host only; raises for sizes the entry rejects."""
+    names = ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "value_digit_passes",
+             "score_digit_passes", "lds_bytes", "max_m", "max_n", "grid", "value_rows_per_wave",
+             "value_rows_grid", "flat_grid", "launches")
+    outs = [_c_int(-1) for _ in names]
+    _check(lib().sputnik_hip_csr_regrow_total_launch_shape(
+        m, n, nonzeros, score_bytes, value_bytes, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
+        "sputnik_hip_csr_regrow_total_launch_shape")
+    shape = {name: o.value for name, o in zip(names, outs)}
+    shape["served"] = bool(shape["served"])
+    return shape
+
+
+def csr_regrow_total_workspace_bytes(m, n, nonzeros):
+    """Bytes of workspace one matrix-wide drop-and-grow call takes (host only): two sets of bins,
+    thresholds, quotas and tie counts, the kept lengths, and 2 * m * ceil(n / 32) words of bit
+    planes."""
+    return lib().sputnik_hip_csr_regrow_total_workspace_bytes(m, n, nonzeros)
 
 
 def csr_topk_launch_shape(m, n, nonzeros, value_bytes, total):

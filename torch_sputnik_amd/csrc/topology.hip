@@ -1,7 +1,7 @@
 // CSR topologies from dense masks / matrices, built on the device for gfx950
 // (include/sputnik_hip.h: sputnik_hip_dense_to_csr_*, sputnik_hip_csr_row_order), and the
 // selections that write one out: sputnik_hip_topk_to_csr, sputnik_hip_csr_regrow, sputnik_hip_csr_topk,
-// sputnik_hip_csr_topk_global_*.
+// sputnik_hip_csr_topk_global_*, sputnik_hip_csr_regrow_total.
 //
 // The build replaces the torch loop of topology.dense_to_sparse_3d (per mask: != 0,
 // to_sparse_csr, two casts, a stable argsort and a host read of the count) by a fixed number of
@@ -738,12 +738,13 @@ __global__ __launch_bounds__(kBuildBlock) void topk_total_hist_kernel(
   });
 }
 
-// Total mode: greater[row] = #(key > T), ties[row] = #(key == T) of the walk's row, T from the
-// filled bins.
-template <typename U>
+// Total mode: greater[row] = base + #(key > T), ties[row] = #(key == T) of the walk's row, T from
+// the filled bins; keys at most key_limit, open(first column) = a bit per element of the piece
+// that takes part.
+template <typename U, typename Open>
 __device__ __forceinline__ void count_against_total(const RowGroup& g, const RowWalk<U>& walk, unsigned count,
-                                                    const unsigned* __restrict__ bins, int* __restrict__ greater_out,
-                                                    int* __restrict__ ties) {
+                                                    const unsigned* __restrict__ bins, unsigned key_limit, Open open,
+                                                    int base, int* __restrict__ greater_out, int* __restrict__ ties) {
   __shared__ unsigned select[kSelectWords];
   unsigned need;
   const unsigned prefix = total_select(bins, sizeof(U) * 8 / kDigitBits, count, select, &need);
@@ -753,18 +754,25 @@ __device__ __forceinline__ void count_against_total(const RowGroup& g, const Row
     int64_t c0;
     unsigned valid, above, same;
     const Piece<U> v = walk.load(s, &c0, &valid);
-    compare_piece(v, threshold, kNoThreshold, &above, &same);
-    greater += __popc(above & valid);
-    equal += __popc(same & valid);
+    compare_piece(v, threshold, key_limit, &above, &same);
+    const unsigned counted = valid & open(c0);
+    greater += __popc(above & counted);
+    equal += __popc(same & counted);
   }
   for (int o = g.group_lanes / 2; o > 0; o >>= 1) {
     greater += __shfl_xor(greater, o, kWave);
     equal += __shfl_xor(equal, o, kWave);
   }
   if (walk.live && g.group_lane == 0) {
-    greater_out[g.row] = greater;
+    greater_out[g.row] = base + greater;
     ties[g.row] = equal;
   }
+}
+template <typename U>
+__device__ __forceinline__ void count_against_total(const RowGroup& g, const RowWalk<U>& walk, unsigned count,
+                                                    const unsigned* __restrict__ bins, int* __restrict__ greater_out,
+                                                    int* __restrict__ ties) {
+  count_against_total(g, walk, count, bins, kNoThreshold, [](int64_t) { return ~0u; }, 0, greater_out, ties);
 }
 
 // Total mode: row_offsets[row + 1] = #(key > T), ties[row] = #(key == T).
@@ -992,38 +1000,22 @@ __device__ __forceinline__ unsigned plane_bits(const unsigned* __restrict__ plan
   return static_cast<unsigned>(((static_cast<uint64_t>(hi) << 32) | lo) >> (shifted & 31));
 }
 
-template <typename S, typename W>
-__global__ __launch_bounds__(kBuildBlock) void csr_regrow_kernel(
-    int m, int n, int nonzeros, int rows_per_wave, int words, unsigned key_limit,
-    const int* __restrict__ row_offsets, const int* __restrict__ column_indices, const W* __restrict__ values,
-    const int* __restrict__ drop_counts, const S* __restrict__ scores, int64_t row_stride,
-    int* __restrict__ out_columns, W* __restrict__ out_values, int64_t* __restrict__ out_source) {
-  constexpr int V = RowWalk<S>::V;
-  constexpr int PV = sizeof(W) * 8 / kDigitBits, PS = sizeof(S) * 8 / kDigitBits;
-  extern __shared__ unsigned regrow_lds[];   // per row: bins [256], old bits [words], kept bits [words]
-  const RowGroup g(rows_per_wave);
-  const RowWalk<S> walk(g, scores, row_stride, m, n);
-  unsigned* __restrict__ bins = regrow_lds + g.slot * (kDigitBins + 2 * words);
-  unsigned* __restrict__ old_bits = bins + kDigitBins;
-  unsigned* __restrict__ kept_bits = old_bits + words;
-
-  int begin, end;
-  row_slots(row_offsets, g.row, walk.live, nonzeros, &begin, &end);
-  const int length = end - begin;
-  const int drop = walk.live ? min(max(drop_counts[g.row], 0), length) : 0;
+// The old columns of the row's entries [begin, end) and those of them that `keep` selects, into
+// two bit planes of `words` words in LDS.  A column outside 0 .. n - 1 sets no bit.  Every thread
+// of the workgroup calls it: two barriers.
+template <typename W>
+__device__ __forceinline__ void mark_row_planes(const RowGroup& g, int begin, int end, int n, Selection keep,
+                                                const int* __restrict__ column_indices, const W* __restrict__ values,
+                                                unsigned* __restrict__ old_bits, unsigned* __restrict__ kept_bits,
+                                                int words) {
   // steps of the walk over the row's entries, the most of the wave's rows: every lane of the
   // wave takes part in every ballot
-  int entry_steps = static_cast<int>((static_cast<int64_t>(length) + g.group_lanes - 1) / g.group_lanes);
+  int entry_steps = static_cast<int>((static_cast<int64_t>(end - begin) + g.group_lanes - 1) / g.group_lanes);
   for (int o = kWave / 2; o > 0; o >>= 1) entry_steps = max(entry_steps, __shfl_xor(entry_steps, o, kWave));
-
-  // 1: (T_v, q_v) of the length - drop largest value keys: a ragged read, lane after lane
-  const Selection keep = radix_select<PV>(g, bins, length - drop, [&](int shift, unsigned prefix, unsigned* b) {
-    for (int64_t i = static_cast<int64_t>(begin) + g.group_lane; i < end; i += g.group_lanes)
-      count_digit(key_of(values[i]), true, shift, prefix, b);
-  });
-
-  // 2: the old and the kept columns.  A column outside the row sets no bit.
-  for (int j = g.group_lane; j < 2 * words; j += g.group_lanes) old_bits[j] = 0u;
+  for (int j = g.group_lane; j < words; j += g.group_lanes) {
+    old_bits[j] = 0u;
+    kept_bits[j] = 0u;
+  }
   __syncthreads();
   int ties_seen = 0;
   for (int s = 0; s < entry_steps; ++s) {
@@ -1042,17 +1034,23 @@ __global__ __launch_bounds__(kBuildBlock) void csr_regrow_kernel(
     }
   }
   __syncthreads();
+}
 
-  // 3: (T_s, q_s) of the drop largest score keys outside the kept columns, keys clamped
-  const Selection grow = radix_select<PS>(g, bins, drop, [&](int shift, unsigned prefix, unsigned* b) {
-    digit_histogram(walk, shift, prefix, b, key_limit,
-                    [&](int64_t c0) { return ~plane_bits(kept_bits, words, c0); });
-  });
-
-  // 4: the new row, ascending, into [begin, end)
-  int64_t out = begin;
-  int old_seen = 0;   // old columns in the steps behind
-  ties_seen = 0;      // open columns equal to the threshold in the steps behind
+// The new row of a drop-and-grow step, ascending, into the slots [out, out_end): the kept
+// columns and those open ones that `grow` selects by their clamped score keys.  admit_ties +
+// group_prefix per step of the score row, as fill_row does; a running group_prefix of the old
+// bits is the old entry index of a kept column, checked against the old row's end before the
+// value is read.
+template <typename S, typename W>
+__device__ __forceinline__ void regrow_fill_row(const RowGroup& g, const RowWalk<S>& walk,
+                                                const unsigned* __restrict__ old_bits,
+                                                const unsigned* __restrict__ kept_bits, int words, Selection grow,
+                                                unsigned key_limit, int begin, int end, int64_t out, int64_t out_end,
+                                                const W* __restrict__ values, int* __restrict__ out_columns,
+                                                W* __restrict__ out_values, int64_t* __restrict__ out_source) {
+  constexpr int V = RowWalk<S>::V;
+  int old_seen = 0;    // old columns in the steps behind
+  int ties_seen = 0;   // open columns equal to the threshold in the steps behind
   for (int s = 0; s < walk.steps; ++s) {
     int64_t c0;
     unsigned valid, greater, equal;
@@ -1067,7 +1065,7 @@ __global__ __launch_bounds__(kBuildBlock) void csr_regrow_kernel(
     int64_t from = static_cast<int64_t>(begin) + old_seen + olds.before;   // old entries in front of my piece
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-      if (((flags >> e) & 1u) && p < end) {
+      if (((flags >> e) & 1u) && p < out_end) {   // (no store ever leaves the row's slots)
         const bool carried = ((kept >> e) & 1u) && from < end;
         out_columns[p] = static_cast<int>(c0 + e);
         out_values[p] = carried ? values[from] : W{0};
@@ -1079,6 +1077,45 @@ __global__ __launch_bounds__(kBuildBlock) void csr_regrow_kernel(
     out += at.total;
     old_seen += olds.total;
   }
+}
+
+template <typename S, typename W>
+__global__ __launch_bounds__(kBuildBlock) void csr_regrow_kernel(
+    int m, int n, int nonzeros, int rows_per_wave, int words, unsigned key_limit,
+    const int* __restrict__ row_offsets, const int* __restrict__ column_indices, const W* __restrict__ values,
+    const int* __restrict__ drop_counts, const S* __restrict__ scores, int64_t row_stride,
+    int* __restrict__ out_columns, W* __restrict__ out_values, int64_t* __restrict__ out_source) {
+  constexpr int PV = sizeof(W) * 8 / kDigitBits, PS = sizeof(S) * 8 / kDigitBits;
+  extern __shared__ unsigned regrow_lds[];   // per row: bins [256], old bits [words], kept bits [words]
+  const RowGroup g(rows_per_wave);
+  const RowWalk<S> walk(g, scores, row_stride, m, n);
+  unsigned* __restrict__ bins = regrow_lds + g.slot * (kDigitBins + 2 * words);
+  unsigned* __restrict__ old_bits = bins + kDigitBins;
+  unsigned* __restrict__ kept_bits = old_bits + words;
+
+  int begin, end;
+  row_slots(row_offsets, g.row, walk.live, nonzeros, &begin, &end);
+  const int length = end - begin;
+  const int drop = walk.live ? min(max(drop_counts[g.row], 0), length) : 0;
+
+  // 1: (T_v, q_v) of the length - drop largest value keys: a ragged read, lane after lane
+  const Selection keep = radix_select<PV>(g, bins, length - drop, [&](int shift, unsigned prefix, unsigned* b) {
+    for (int64_t i = static_cast<int64_t>(begin) + g.group_lane; i < end; i += g.group_lanes)
+      count_digit(key_of(values[i]), true, shift, prefix, b);
+  });
+
+  // 2: the old and the kept columns
+  mark_row_planes(g, begin, end, n, keep, column_indices, values, old_bits, kept_bits, words);
+
+  // 3: (T_s, q_s) of the drop largest score keys outside the kept columns, keys clamped
+  const Selection grow = radix_select<PS>(g, bins, drop, [&](int shift, unsigned prefix, unsigned* b) {
+    digit_histogram(walk, shift, prefix, b, key_limit,
+                    [&](int64_t c0) { return ~plane_bits(kept_bits, words, c0); });
+  });
+
+  // 4: the new row, ascending, into [begin, end)
+  regrow_fill_row(g, walk, old_bits, kept_bits, words, grow, key_limit, begin, end, begin, end, values, out_columns,
+                  out_values, out_source);
 }
 
 template <typename S, typename W>
@@ -1422,6 +1459,202 @@ int launch_global_fill(int layers, const int* rows, const int* nonzeros, const i
   return launch_status();
 }
 
+// ---------------------------------------------------------------------------
+// Matrix-wide drop-and-grow of a CSR topology (sputnik_hip_csr_regrow_total): the matrix keeps the
+// nnz - d entries of largest value key and takes the d positions outside them of largest clamped
+// score key.  The two total selections above composed, nothing read back: nnz does not change,
+// so every size is known before the first launch.
+//   clear    the global bins of both selections (a kernel: every replay of a captured call)
+//   values   the digit passes of sputnik_hip_csr_topk's total mode over the flat values array with
+//            count nnz - d, its rows launch and its scan: T_v, the rows' quotas q_r and the scanned
+//            kept lengths
+//   planes   per row, mark_row_planes under (T_v, q_r) in LDS, then both planes go to the
+//            workspace, every word stored by the lanes that own the row.  Written ONCE and read by
+//            the launches below (2 * m * ceil(n / 32) words, 1 MiB at 2048 x 2048) rather than
+//            rebuilt in LDS by each of them: a rebuild is another walk of the row's entries and two
+//            more barriers in up to six launches, and LDS next to the per-row bins would bound n
+//            lower.
+//   scores   the digit passes of the dense total mode over the score rows with count d, the kept
+//            plane as the open mask and the keys clamped; a rows launch that counts the open
+//            columns above and at T_s and adds the row's kept length; the scan: the quotas in
+//            row-major order and the new row_offsets
+//   fill     regrow_fill_row per row into [new_offsets[r], new_offsets[r + 1]), then the row order
+// LDS of the planes launch: 2 * ceil(n / 32) words per row; four rows (one per wave) fit 64 KiB up
+// to n = kRegrowTotalMaxN.
+// ---------------------------------------------------------------------------
+constexpr int kRegrowTotalMaxN = 32 * (kRegrowLdsBytes / kBuildWaves / 8);
+static_assert(kRegrowTotalMaxN >= kRegrowMaxN, "no narrower than the per-row kernel");
+
+struct RegrowTotalShape {
+  int status = 0;
+  int served = 0, max_m = kOrderLargeRows, max_n = kRegrowTotalMaxN;
+  int rows_per_wave = -1, elements_per_lane = -1, rows_per_workgroup = -1;
+  int value_passes = -1, score_passes = -1, words = -1, lds_bytes = -1, grid = -1, launches = -1;
+  CsrTopkShape values;   // the launches over the old entries
+};
+inline RegrowTotalShape regrow_total_shape(int m, int n, int nonzeros, int score_bytes, int value_bytes) {
+  RegrowTotalShape r;
+  if ((score_bytes != 2 && score_bytes != 4) || nonzeros < 0) {
+    r.status = SPUTNIK_HIP_INVALID_ARGUMENT;
+    return r;
+  }
+  r.values = csr_topk_shape(m, nonzeros, value_bytes, 1);
+  const BuildShape walk = build_shape(1, m, n, score_bytes);
+  r.status = r.values.status != 0 ? r.values.status : walk.status;
+  if (r.status != 0 || !r.values.served || n > kRegrowTotalMaxN) return r;
+  r.served = 1;
+  r.rows_per_wave = walk.rows_per_wave;
+  r.elements_per_lane = walk.elements_per_lane;
+  r.rows_per_workgroup = walk.rows_per_workgroup;
+  r.value_passes = r.values.digit_passes;
+  r.score_passes = score_bytes * 8 / kDigitBits;
+  r.words = n / 32 + (n % 32 != 0 ? 1 : 0);
+  r.lds_bytes = r.rows_per_workgroup * 2 * r.words * static_cast<int>(sizeof(unsigned));
+  r.grid = walk.grid;
+  // clear; values: digits, rows, scan; planes; scores: digits, rows, scan; fill; row order
+  r.launches = m > 0 && nonzeros > 0 ? 1 + (r.value_passes + 2) + 1 + (r.score_passes + 2) + 1 + 1 : (m > 0 ? 1 : 0);
+  return r;
+}
+
+// The workspace, in 32-bit words: the total workspace of the values, that of the scores, the
+// scanned kept lengths [m + 1], the planes [m][2][words] (a row's old plane, then its kept one).
+struct RegrowTotalWorkspace {
+  TotalWorkspace values, scores;
+  int* kept_offsets;
+  unsigned* planes;
+  static size_t words(int64_t m, int64_t plane_words) {
+    return 2 * TotalWorkspace::words(m, false) + static_cast<size_t>(m) + 1 +
+           2 * static_cast<size_t>(m) * static_cast<size_t>(plane_words);
+  }
+  RegrowTotalWorkspace(void* workspace, int m)
+      : values(workspace, false),
+        scores(static_cast<unsigned*>(workspace) + TotalWorkspace::words(m, false), false),
+        kept_offsets(reinterpret_cast<int*>(static_cast<unsigned*>(workspace) + 2 * TotalWorkspace::words(m, false))),
+        planes(reinterpret_cast<unsigned*>(kept_offsets + m + 1)) {}
+};
+
+// A row's planes in the workspace; a group without a row has planes of no words (plane_bits
+// reads nothing then).
+struct RowPlanes {
+  const unsigned *old_bits, *kept_bits;
+  int words;
+  __device__ __forceinline__ RowPlanes(const unsigned* __restrict__ planes, int words_, int64_t row, bool live) {
+    words = live ? words_ : 0;
+    old_bits = planes + (live ? row * 2 * words_ : int64_t{0});
+    kept_bits = old_bits + words;
+  }
+};
+
+// The global bins of both selections start at zero.
+__global__ __launch_bounds__(kScanBlock) void regrow_total_clear_kernel(unsigned* __restrict__ value_bins,
+                                                                        unsigned* __restrict__ score_bins) {
+  value_bins[threadIdx.x] = 0u;
+  score_bins[threadIdx.x] = 0u;
+}
+
+// The old and the kept columns of every row under (T_v, q_r), marked in LDS and written out.
+template <typename W>
+__global__ __launch_bounds__(kBuildBlock) void regrow_total_planes_kernel(
+    int m, int n, int nonzeros, int rows_per_wave, int words, const int* __restrict__ row_offsets,
+    const int* __restrict__ column_indices, const W* __restrict__ values, const unsigned* __restrict__ threshold,
+    const int* __restrict__ quotas, unsigned* __restrict__ planes) {
+  extern __shared__ unsigned regrow_lds[];   // per row: old bits [words], kept bits [words]
+  const RowGroup g(rows_per_wave);
+  const bool live = g.row < m;
+  unsigned* __restrict__ old_bits = regrow_lds + g.slot * 2 * words;
+  unsigned* __restrict__ kept_bits = old_bits + words;
+  int begin, end;
+  row_slots(row_offsets, g.row, live, nonzeros, &begin, &end);
+  mark_row_planes(g, begin, end, n, {*threshold, live ? quotas[g.row] : 0}, column_indices, values, old_bits,
+                  kept_bits, words);
+  if (live) {
+    unsigned* __restrict__ out = planes + g.row * 2 * words;
+    for (int j = g.group_lane; j < 2 * words; j += g.group_lanes) out[j] = old_bits[j];
+  }
+}
+
+// One digit pass over the score rows outside the kept columns, keys clamped.
+template <typename S>
+__global__ __launch_bounds__(kBuildBlock) void regrow_total_hist_kernel(
+    int m, int n, int rows_per_wave, int words, int pass, unsigned count, unsigned key_limit,
+    const S* __restrict__ scores, int64_t row_stride, const unsigned* __restrict__ planes, unsigned* bins) {
+  workgroup_digit_pass<sizeof(S) * 8 / kDigitBits>(pass, count, bins, [&](int shift, unsigned prefix, unsigned* hist) {
+    const RowGroup g(rows_per_wave);
+    const RowWalk<S> walk(g, scores, row_stride, m, n);
+    const RowPlanes row(planes, words, g.row, walk.live);
+    digit_histogram(walk, shift, prefix, hist, key_limit,
+                    [&](int64_t c0) { return ~plane_bits(row.kept_bits, row.words, c0); });
+  });
+}
+
+// out_offsets[row + 1] = the row's kept length + #(open key > T_s), ties[row] = #(open key == T_s).
+template <typename S>
+__global__ __launch_bounds__(kBuildBlock) void regrow_total_rows_kernel(
+    int m, int n, int rows_per_wave, int words, unsigned count, unsigned key_limit, const S* __restrict__ scores,
+    int64_t row_stride, const unsigned* __restrict__ planes, const int* __restrict__ kept_offsets,
+    const unsigned* __restrict__ bins, int* __restrict__ out_offsets, int* __restrict__ ties) {
+  const RowGroup g(rows_per_wave);
+  const RowWalk<S> walk(g, scores, row_stride, m, n);
+  const RowPlanes row(planes, words, g.row, walk.live);
+  const int kept = walk.live ? kept_offsets[g.row + 1] - kept_offsets[g.row] : 0;
+  count_against_total(g, walk, count, bins, key_limit,
+                      [&](int64_t c0) { return ~plane_bits(row.kept_bits, row.words, c0); }, kept, out_offsets + 1,
+                      ties);
+}
+
+// The new rows under the one score threshold and the rows' quotas.
+template <typename S, typename W>
+__global__ __launch_bounds__(kBuildBlock) void regrow_total_fill_kernel(
+    int m, int n, int nonzeros, int rows_per_wave, int words, unsigned key_limit,
+    const int* __restrict__ row_offsets, const W* __restrict__ values, const S* __restrict__ scores,
+    int64_t row_stride, const unsigned* __restrict__ planes, const unsigned* __restrict__ threshold,
+    const int* __restrict__ quotas, const int* __restrict__ out_offsets, int* __restrict__ out_columns,
+    W* __restrict__ out_values, int64_t* __restrict__ out_source) {
+  const RowGroup g(rows_per_wave);
+  const RowWalk<S> walk(g, scores, row_stride, m, n);
+  const RowPlanes row(planes, words, g.row, walk.live);
+  int begin, end;
+  row_slots(row_offsets, g.row, walk.live, nonzeros, &begin, &end);
+  int64_t out, out_end;
+  new_slots(out_offsets, g.row, walk.live, nonzeros, &out, &out_end);
+  regrow_fill_row(g, walk, row.old_bits, row.kept_bits, row.words, {*threshold, walk.live ? quotas[g.row] : 0},
+                  key_limit, begin, end, out, out_end, values, out_columns, out_values, out_source);
+}
+
+template <typename S, typename W>
+int launch_regrow_total(const RegrowTotalShape& r, int m, int n, int nonzeros, const int* row_offsets,
+                        const int* column_indices, const void* values_, unsigned drop, const void* scores_,
+                        int64_t row_stride, unsigned key_limit, void* workspace, int* out_offsets, int* out_columns,
+                        void* out_values, int64_t* out_source, hipStream_t stream) {
+  const W* values = static_cast<const W*>(values_);
+  const S* scores = static_cast<const S*>(scores_);
+  const RegrowTotalWorkspace w(workspace, m);
+  const dim3 block(kBuildBlock), grid(r.grid), entry_grid(r.values.rows_grid);
+  const unsigned keep = static_cast<unsigned>(nonzeros) - drop;
+  hipLaunchKernelGGL(regrow_total_clear_kernel, dim3(1), dim3(kScanBlock), 0, stream, w.values.bins, w.scores.bins);
+  for (int p = 0; p < r.value_passes; ++p)
+    hipLaunchKernelGGL((csr_topk_flat_hist_kernel<W>), dim3(r.values.flat_grid), block, 0, stream, nonzeros, p, keep,
+                       values, w.values.bins);
+  hipLaunchKernelGGL((csr_topk_total_rows_kernel<W>), entry_grid, block, 0, stream, m, nonzeros,
+                     r.values.rows_per_wave, keep, row_offsets, values, w.values.bins, w.kept_offsets,
+                     w.values.quotas() + m);
+  launch_total_scan(w.values, w.values.quotas(), m, r.value_passes, keep, w.kept_offsets, true, nullptr, stream);
+  hipLaunchKernelGGL((regrow_total_planes_kernel<W>), grid, block, r.lds_bytes, stream, m, n, nonzeros,
+                     r.rows_per_wave, r.words, row_offsets, column_indices, values, w.values.threshold,
+                     w.values.quotas(), w.planes);
+  for (int p = 0; p < r.score_passes; ++p)
+    hipLaunchKernelGGL((regrow_total_hist_kernel<S>), grid, block, 0, stream, m, n, r.rows_per_wave, r.words, p, drop,
+                       key_limit, scores, row_stride, w.planes, w.scores.bins);
+  hipLaunchKernelGGL((regrow_total_rows_kernel<S>), grid, block, 0, stream, m, n, r.rows_per_wave, r.words, drop,
+                     key_limit, scores, row_stride, w.planes, w.kept_offsets, w.scores.bins, out_offsets,
+                     w.scores.quotas() + m);
+  launch_total_scan(w.scores, w.scores.quotas(), m, r.score_passes, drop, out_offsets, true, nullptr, stream);
+  hipLaunchKernelGGL((regrow_total_fill_kernel<S, W>), grid, block, 0, stream, m, n, nonzeros, r.rows_per_wave,
+                     r.words, key_limit, row_offsets, values, scores, row_stride, w.planes, w.scores.threshold,
+                     w.scores.quotas(), out_offsets, out_columns, static_cast<W*>(out_values), out_source);
+  return launch_status();
+}
+
 inline void put(int* p, int v) {
   if (p) *p = v;
 }
@@ -1607,6 +1840,77 @@ int sputnik_hip_csr_regrow(int m, int n, int nonzeros, const int* row_offsets, c
                                                      out_column_indices, out_values, out_source, stream);
     });
   });
+}
+
+int sputnik_hip_csr_regrow_total_launch_shape(int m, int n, int nonzeros, int score_bytes, int value_bytes,
+                                              int* served, int* rows_per_wave, int* elements_per_lane,
+                                              int* rows_per_workgroup, int* value_digit_passes,
+                                              int* score_digit_passes, int* lds_bytes, int* max_m, int* max_n,
+                                              int* grid, int* value_rows_per_wave, int* value_rows_grid,
+                                              int* flat_grid, int* launches) {
+  const RegrowTotalShape r = regrow_total_shape(m, n, nonzeros, score_bytes, value_bytes);
+  if (r.status != 0) return r.status;
+  put(served, r.served);
+  put(rows_per_wave, r.rows_per_wave);
+  put(elements_per_lane, r.elements_per_lane);
+  put(rows_per_workgroup, r.rows_per_workgroup);
+  put(value_digit_passes, r.value_passes);
+  put(score_digit_passes, r.score_passes);
+  put(lds_bytes, r.lds_bytes);
+  put(max_m, r.max_m);
+  put(max_n, r.max_n);
+  put(grid, r.grid);
+  put(value_rows_per_wave, r.served ? r.values.rows_per_wave : -1);
+  put(value_rows_grid, r.served ? r.values.rows_grid : -1);
+  put(flat_grid, r.served ? r.values.flat_grid : -1);
+  put(launches, r.launches);
+  return 0;
+}
+
+size_t sputnik_hip_csr_regrow_total_workspace_bytes(int m, int n, int nonzeros) {
+  if (m < 0 || n < 0 || nonzeros < 0) return 0;
+  return sizeof(unsigned) * RegrowTotalWorkspace::words(m, n / 32 + (n % 32 != 0 ? 1 : 0));
+}
+
+int sputnik_hip_csr_regrow_total(int m, int n, int nonzeros, const int* row_offsets, const int* column_indices,
+                                 const void* values, int value_bytes, int64_t drop, const void* scores,
+                                 int score_bytes, int64_t scores_row_stride, unsigned score_key_limit,
+                                 void* workspace, size_t workspace_bytes, int* out_row_indices,
+                                 int* out_row_offsets, int* out_column_indices, void* out_values,
+                                 int64_t* out_source, sputnik_hip_stream_t stream_) {
+  const RegrowTotalShape r = regrow_total_shape(m, n, nonzeros, score_bytes, value_bytes);
+  if (r.status != 0) return r.status;
+  if (!r.served || drop < 0 || drop > nonzeros || scores_row_stride < 0 ||
+      score_key_limit >= (1u << (8 * score_bytes - 1)) || out_row_offsets == nullptr ||
+      !aligned_to(out_row_offsets, sizeof(int)) ||
+      (m > 0 && (out_row_indices == nullptr || !aligned_to(out_row_indices, sizeof(int)))))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (m == 0 || nonzeros == 0) {
+    // no entries: the zero offsets and the row order 0 .. m - 1 of equal lengths
+    if (hipMemsetAsync(out_row_offsets, 0, sizeof(int) * (static_cast<size_t>(m) + 1), stream) != hipSuccess)
+      return launch_status();
+    if (m == 0) return launch_status();
+    return sputnik_hip_csr_row_order(1, m, n, out_row_offsets, out_row_indices, stream_);
+  }
+  if (row_offsets == nullptr || !aligned_to(row_offsets, sizeof(int)) || column_indices == nullptr ||
+      !aligned_to(column_indices, sizeof(int)) || values == nullptr || !aligned_to(values, value_bytes) ||
+      scores == nullptr || !aligned_to(scores, score_bytes) || out_column_indices == nullptr ||
+      !aligned_to(out_column_indices, sizeof(int)) || out_values == nullptr || !aligned_to(out_values, value_bytes) ||
+      out_source == nullptr || !aligned_to(out_source, sizeof(int64_t)) || workspace == nullptr ||
+      !aligned_to(workspace, sizeof(unsigned)) ||
+      workspace_bytes < sputnik_hip_csr_regrow_total_workspace_bytes(m, n, nonzeros))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const int st = by_width(score_bytes, [&](auto s) {
+    return by_width(value_bytes, [&](auto w) {
+      return launch_regrow_total<decltype(s), decltype(w)>(
+          r, m, n, nonzeros, row_offsets, column_indices, values, static_cast<unsigned>(drop), scores,
+          scores_row_stride, score_key_limit, workspace, out_row_offsets, out_column_indices, out_values, out_source,
+          stream);
+    });
+  });
+  if (st != 0) return st;
+  return sputnik_hip_csr_row_order(1, m, n, out_row_offsets, out_row_indices, stream_);
 }
 
 int sputnik_hip_csr_topk_launch_shape(int m, int n, int nonzeros, int value_bytes, int total_mode, int* served,

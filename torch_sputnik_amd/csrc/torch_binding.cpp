@@ -2125,6 +2125,70 @@ std::vector<Tensor> csr_regrow(const Tensor& values_in, const Tensor& row_offset
   return {out_columns, out_values, source};
 }
 
+// One matrix-wide drop-and-grow step of the CSR pattern (row_offsets [m + 1], column_indices
+// [nnz]) with `values` [nnz] under dense `scores` [m, n]: `drop` entries go, as many come ->
+// [row_indices, row_offsets, column_indices, values, source (int64)] of the new pattern
+// (sputnik_hip.h: sputnik_hip_csr_regrow_total).  nnz does not change, so every size is known up
+// front: no synchronisation, torch allocations only; the workspace is this call's own allocation
+// on the stream's allocator.  Scores with a dense last dimension are read in place.
+std::vector<Tensor> csr_regrow_total(const Tensor& values_in, const Tensor& row_offsets_in,
+                                     const Tensor& column_indices_in, int64_t drop, const Tensor& scores_in) {
+  TORCH_CHECK(values_in.is_cuda(), "values must be a GPU (HIP) tensor, got ", values_in.device());
+  for (const Tensor* t : {&row_offsets_in, &column_indices_in, &scores_in})
+    TORCH_CHECK(t->device() == values_in.device(), "every tensor must be on ", values_in.device(), ", got ",
+                t->device());
+  const auto floating = [](const Tensor& t) {
+    return t.scalar_type() == at::kFloat || t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16;
+  };
+  TORCH_CHECK(floating(values_in), "values must be float32, float16 or bfloat16, got ", values_in.scalar_type());
+  TORCH_CHECK(floating(scores_in), "scores must be float32, float16 or bfloat16, got ", scores_in.scalar_type());
+  for (const Tensor* t : {&row_offsets_in, &column_indices_in})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1, "row_offsets and column_indices must be 1-D int32 "
+                "tensors, got ", t->scalar_type(), " ", t->sizes());
+  TORCH_CHECK(scores_in.dim() == 2, "expected [m, n] scores, got ", scores_in.sizes());
+  TORCH_CHECK(row_offsets_in.numel() == scores_in.size(0) + 1, "row_offsets should be [m + 1] for [m, n] scores ",
+              scores_in.sizes(), ", got ", row_offsets_in.sizes());
+  TORCH_CHECK(values_in.dim() == 1 && values_in.numel() == column_indices_in.numel(),
+              "values should be [nnz] like column_indices ", column_indices_in.sizes(), ", got ", values_in.sizes());
+  TORCH_CHECK(drop >= 0 && drop <= values_in.numel(), "torch_sputnik::csr_regrow_total: drop = ", drop,
+              " is outside 0 .. ", values_in.numel());
+  const c10::DeviceGuard guard(values_in.device());
+  const Tensor scores = scores_in.size(1) > 1 && scores_in.stride(1) != 1 ? scores_in.contiguous() : scores_in;
+  const Tensor values = values_in.contiguous(), row_offsets = row_offsets_in.contiguous();
+  const Tensor column_indices = column_indices_in.contiguous();
+  const int m = to_int(scores.size(0), "m"), n = to_int(scores.size(1), "n");
+  const int nonzeros = to_int(values.numel(), "nnz");
+  const int score_bytes = static_cast<int>(scores.element_size());
+  const int value_bytes = static_cast<int>(values.element_size());
+  int served = 0, max_m = 0, max_n = 0;
+  check_status(sputnik_hip_csr_regrow_total_launch_shape(m, n, nonzeros, score_bytes, value_bytes, &served, nullptr,
+                                                         nullptr, nullptr, nullptr, nullptr, nullptr, &max_m, &max_n,
+                                                         nullptr, nullptr, nullptr, nullptr, nullptr),
+               "csr_regrow_total");
+  TORCH_CHECK(served, "torch_sputnik::csr_regrow_total: [", m, ", ", n, "] is beyond the ", max_m, " rows of the "
+              "row-order kernel or the ", max_n, " columns of the LDS bit planes "
+              "(sputnik_hip_csr_regrow_total_launch_shape); take topology.regrow_total");
+  // the key of the largest finite value of the scores' dtype
+  const unsigned key_limit = scores.scalar_type() == at::kFloat ? 0x7f7fffffu
+                             : scores.scalar_type() == at::kHalf ? 0x7bffu : 0x7f7fu;
+  const auto index_options = row_offsets.options();
+  Tensor out_row_indices = at::empty({m}, index_options);
+  Tensor out_row_offsets = at::empty({m + 1}, index_options);
+  Tensor out_columns = at::empty({nonzeros}, index_options);
+  Tensor out_values = at::empty_like(values);
+  Tensor source = at::empty({nonzeros}, index_options.dtype(at::kLong));
+  const size_t ws_bytes = sputnik_hip_csr_regrow_total_workspace_bytes(m, n, nonzeros);
+  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, values.options().dtype(at::kByte));
+  check_status(sputnik_hip_csr_regrow_total(
+                   m, n, nonzeros, row_offsets.data_ptr<int>(), column_indices.data_ptr<int>(), values.data_ptr(),
+                   value_bytes, drop, scores.data_ptr(), score_bytes, m > 1 ? scores.stride(0) : 0, key_limit,
+                   workspace.data_ptr(), ws_bytes, out_row_indices.data_ptr<int>(), out_row_offsets.data_ptr<int>(),
+                   out_columns.data_ptr<int>(), out_values.data_ptr(), source.data_ptr<int64_t>(),
+                   current_stream(values)),
+               "csr_regrow_total");
+  return {out_row_indices, out_row_offsets, out_columns, out_values, source};
+}
+
 // The CSR pattern (row_offsets [m + 1], column_indices [nnz]) with `values` [nnz] -> [row_indices,
 // row_offsets, column_indices, values, source (int64)] of its `total` entries of largest |value|,
 // or of the `per_row` largest of every row (the other one -1): sputnik_hip.h:
@@ -2752,6 +2816,8 @@ TORCH_LIBRARY(torch_sputnik, m) {
   m.def("topk_to_csr(Tensor scores, int per_row, int total, Tensor? values_from) -> Tensor[]");
   m.def("csr_regrow(Tensor values, Tensor row_offsets, Tensor column_indices, Tensor drop_counts, "
         "Tensor scores) -> Tensor[]");
+  m.def("csr_regrow_total(Tensor values, Tensor row_offsets, Tensor column_indices, int drop, "
+        "Tensor scores) -> Tensor[]");
   m.def("csr_topk(Tensor values, Tensor row_offsets, Tensor column_indices, int per_row, int total) -> Tensor[]");
   m.def("csr_topk_global(Tensor[] values, Tensor[] row_offsets, Tensor[] column_indices, int total) -> Tensor[]");
   m.def(
@@ -2856,6 +2922,7 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("row_order", &row_order);
   m.impl("topk_to_csr", &topk_to_csr);
   m.impl("csr_regrow", &csr_regrow);
+  m.impl("csr_regrow_total", &csr_regrow_total);
   m.impl("csr_topk", &csr_topk);
   m.impl("csr_topk_global", &csr_topk_global);
   m.impl("sparse_attention_many_mask", &sparse_attention_many_mask);

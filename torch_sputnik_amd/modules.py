@@ -142,8 +142,10 @@ class SparseLinear(nn.Module):
         old ``values``, or -1 where it was grown -- to permute or reset optimizer state.
         ``d == 0`` changes nothing (``source = arange(nnz)``).
 
-        Selection and CSR build are one ``topology.topk_to_csr`` call (on the device for a GPU
-        module).
+        The step is one ``topology.regrow_total`` call.  On a GPU module it runs on the layer's
+        own arrays on the device: a fixed number of kernel launches, no ``[out, in]`` temporary
+        (the only dense tensor is ``grow_scores``, or the random scores of SET) and no host
+        synchronisation.
 
         ``per_row=True`` (SET per neuron, RigL with a fixed fan-in): every row keeps its
         length.  Row r of ``len_r`` entries drops ``d_r = floor(float64(len_r) *
@@ -173,14 +175,6 @@ class SparseLinear(nn.Module):
         if d == 0:
             return torch.arange(nnz, dtype=torch.int64, device=device)
         out_f, in_f = self.output_features, self.input_features
-        rank_values = values if values.dtype in topology._TOPK_DTYPES else values.float()
-        order = torch.argsort(topology.magnitude_keys(rank_values), descending=True, stable=True)
-        kept = torch.sort(order[:nnz - d]).values                     # old entry indices, ascending
-        lengths = (self.row_offsets[1:] - self.row_offsets[:-1]).to(torch.int64)
-        rows = torch.repeat_interleave(torch.arange(out_f, device=device), lengths, output_size=nnz)
-        flat = rows * in_f + self.column_indices.to(torch.int64)      # ascending: CSR is row major
-        kept_flat = flat[kept]
-
         if grow_scores is None:
             where = generator.device if generator is not None else device
             scores = torch.rand(out_f, in_f, generator=generator, device=where).to(device)
@@ -189,27 +183,8 @@ class SparseLinear(nn.Module):
                 raise ValueError(f"update_topology: grow_scores should be [{out_f}, {in_f}], got "
                                  f"{tuple(grow_scores.shape)}")
             scores = grow_scores.detach().to(device)
-            if scores.dtype not in topology._TOPK_DTYPES:
-                scores = scores.float()
-            largest = torch.finfo(scores.dtype).max
-            scores = torch.nan_to_num(scores.abs(), nan=largest, posinf=largest)
-        scores = scores.contiguous()
-        scores.view(-1)[kept_flat] = float("inf")                      # Kept comes first ...
-        image = torch.zeros(out_f, in_f, dtype=values.dtype, device=device)
-        bits = topology._BIT_VIEWS[values.element_size()]                # ... and carries its values,
-        image.view(bits).view(-1)[kept_flat] = values.contiguous().view(bits)[kept]   # bit for bit
-        row_indices, row_offsets, column_indices, new_values = topology.topk_to_csr(
-            scores, total=nnz, values_from=image)
-
-        new_lengths = (row_offsets[1:] - row_offsets[:-1]).to(torch.int64)
-        new_rows = torch.repeat_interleave(torch.arange(out_f, device=device), new_lengths, output_size=nnz)
-        new_flat = new_rows * in_f + column_indices.to(torch.int64)
-        at = torch.searchsorted(kept_flat, new_flat).clamp_(max=kept_flat.numel() - 1)
-        if kept_flat.numel():
-            source = torch.where(kept_flat[at] == new_flat, kept[at], torch.full_like(at, -1))
-        else:
-            source = torch.full_like(new_flat, -1)
-
+        row_indices, row_offsets, column_indices, new_values, source = topology.regrow_total(
+            values, self.row_offsets, self.column_indices, d, scores)
         self.values.copy_(new_values)
         functional.unregister_static_topology(self.row_indices, self.row_offsets, self.column_indices)
         self._set_topology(None, row_indices, row_offsets, column_indices)

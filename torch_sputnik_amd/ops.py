@@ -400,6 +400,50 @@ def csr_regrow(values, row_offsets, column_indices, drop_counts, scores):
     return tuple(_ops.csr_regrow(values, row_offsets, column_indices, drop_counts, scores))
 
 
+def check_regrow_total_arguments(values, row_offsets, column_indices, drop, scores):
+    """ValueError unless the four tensors are one CSR pattern with its values and dense scores
+    (shapes, int32 indices, one device) and ``drop`` is a count within 0 .. nnz.  -> the count.
+    Dtypes of values and scores are the caller's matter."""
+    if scores.dim() != 2:
+        raise ValueError(f"csr_regrow_total: expected [m, n] scores, got {tuple(scores.shape)}")
+    if values.dim() != 1:
+        raise ValueError(f"csr_regrow_total: values should be [nnz], got {tuple(values.shape)}")
+    for name, t, size in (("row_offsets", row_offsets, scores.size(0) + 1),
+                          ("column_indices", column_indices, values.numel())):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != size:
+            raise ValueError(f"csr_regrow_total: {name} should be int32 [{size}], got {t.dtype} {tuple(t.shape)}")
+    for name, t in (("row_offsets", row_offsets), ("column_indices", column_indices), ("scores", scores)):
+        if t.device != values.device:
+            raise ValueError(f"csr_regrow_total: {name} is on {t.device}, values on {values.device}")
+    count = int(drop)
+    if not 0 <= count <= values.numel():
+        raise ValueError(f"csr_regrow_total: drop = {count} is outside 0 .. {values.numel()}")
+    return count
+
+
+def csr_regrow_total(values, row_offsets, column_indices, drop, scores):
+    """One matrix-wide drop-and-grow step of a CSR pattern on the device (csrc/topology.hip):
+    ``drop = d`` (a host integer, ``0 <= d <= nnz``) entries go and as many come, ``nnz`` stays.
+    Kept: the ``nnz - d`` entries of largest ``|values|``, ties to the lower entry index.  Grown:
+    the ``d`` positions outside the kept ones of largest ``|scores|``, ties to the lower flat
+    (row-major) index; NaN and inf scores count as the dtype's largest finite value; positions
+    dropped in this call are eligible.  Magnitudes rank by the bit pattern without the sign
+    (``topology.magnitude_keys``).  values [nnz] and scores [m, n] are float32 / float16 /
+    bfloat16, each of its own dtype; row_offsets [m + 1] and column_indices [nnz] (ascending
+    inside a row) are int32.  -> (row_indices, row_offsets, column_indices, values, source) of
+    the new pattern, columns ascending inside a row: a kept entry carries its value bit for bit
+    and its old index in ``source`` (int64), a grown one is +0.0 and -1.  A fixed number of
+    launches, no host synchronisation: the call can be captured in a graph.  Raises for CPU
+    tensors and beyond the rows and columns ``capi.csr_regrow_total_launch_shape`` serves."""
+    count = check_regrow_total_arguments(values, row_offsets, column_indices, drop, scores)
+    for name, t in (("values", values), ("scores", scores)):
+        if t.dtype not in _TOPK_DTYPES:
+            raise ValueError(f"csr_regrow_total: {name} must be float32, float16 or bfloat16, got {t.dtype}")
+    if not values.is_cuda:
+        raise RuntimeError("csr_regrow_total: GPU tensors only (topology.regrow_total serves CPU tensors)")
+    return tuple(_ops.csr_regrow_total(values, row_offsets, column_indices, count, scores))
+
+
 def check_csr_topk_arguments(values, row_offsets, column_indices, per_row, total):
     """ValueError unless the three tensors are one CSR pattern with its values (shapes, int32
     indices, one device) and exactly one of per_row / total is a count in range (``total`` at

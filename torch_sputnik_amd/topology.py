@@ -263,6 +263,88 @@ def regrow_per_row(values, row_offsets, column_indices, drop_counts, scores):
     return new_columns.to(torch.int32), new_bits.view(values.dtype), source
 
 
+def _regrow_total_served(values, scores):
+    if not (_device_build and values.is_cuda and values.dtype in _TOPK_DTYPES and scores.dtype in _TOPK_DTYPES):
+        return False
+    try:
+        return capi.csr_regrow_total_launch_shape(scores.size(0), scores.size(1), values.numel(),
+                                                  scores.element_size(), values.element_size())["served"]
+    except RuntimeError:   # (more than INT_MAX elements)
+        return False
+
+
+def regrow_total_composed(values, row_offsets, column_indices, drop, scores):
+    """The rule of ``regrow_total`` composed from torch indexing and one ``topk_to_csr`` call
+    (which itself picks the device build or torch): the kept entries are forced first in a dense
+    image of the scores, their values travel in a second dense image, and ``source`` is looked up
+    afterwards.  What ``regrow_total`` runs where the device step does not serve the call; under
+    its own name so that the two can be compared on a GPU."""
+    d = ops.check_regrow_total_arguments(values, row_offsets, column_indices, drop, scores)
+    values, scores = values.detach(), scores.detach()
+    m, n = scores.shape
+    nnz = values.numel()
+    device = values.device
+    rank_values = values if values.dtype in _TOPK_DTYPES else values.float()
+    order = torch.argsort(magnitude_keys(rank_values), descending=True, stable=True)
+    kept = torch.sort(order[:nnz - d]).values                     # old entry indices, ascending
+    lengths = (row_offsets[1:] - row_offsets[:-1]).to(torch.int64)
+    rows = torch.repeat_interleave(torch.arange(m, device=device), lengths, output_size=nnz)
+    flat = rows * n + column_indices.to(torch.int64)              # ascending: CSR is row major
+    kept_flat = flat[kept]
+
+    if scores.dtype not in _TOPK_DTYPES:
+        scores = scores.float()
+    largest = torch.finfo(scores.dtype).max
+    scores = torch.nan_to_num(scores.abs(), nan=largest, posinf=largest).contiguous()
+    scores.view(-1)[kept_flat] = float("inf")                      # Kept comes first ...
+    image = torch.zeros(m, n, dtype=values.dtype, device=device)
+    bits = _BIT_VIEWS[values.element_size()]                         # ... and carries its values,
+    image.view(bits).view(-1)[kept_flat] = values.contiguous().view(bits)[kept]   # bit for bit
+    row_indices, new_offsets, new_columns, new_values = topk_to_csr(scores, total=nnz, values_from=image)
+
+    new_lengths = (new_offsets[1:] - new_offsets[:-1]).to(torch.int64)
+    new_rows = torch.repeat_interleave(torch.arange(m, device=device), new_lengths, output_size=nnz)
+    new_flat = new_rows * n + new_columns.to(torch.int64)
+    at = torch.searchsorted(kept_flat, new_flat).clamp_(max=kept_flat.numel() - 1)
+    if kept_flat.numel():
+        source = torch.where(kept_flat[at] == new_flat, kept[at], torch.full_like(at, -1))
+    else:
+        source = torch.full_like(new_flat, -1)
+    return row_indices, new_offsets, new_columns, new_values, source
+
+
+def regrow_total(values, row_offsets, column_indices, drop, scores):
+    """``ops.csr_regrow_total`` for any tensor: one matrix-wide drop-and-grow step of the CSR
+    pattern (row_offsets [m + 1], column_indices [nnz], int32, ascending inside a row) with
+    ``values`` [nnz] under dense ``scores`` [m, n]; ``drop = d`` is a host integer,
+    ``0 <= d <= nnz``.  The layer-wise rule of SET and RigL:
+
+    * Kept: the ``nnz - d`` entries of largest value key (``magnitude_keys``: NaN above inf,
+      -0.0 with 0.0), ties to the lower entry index.
+    * Grown: the ``d`` positions outside Kept of largest score key, ties to the lower flat
+      (row-major) index; a score key is clamped to that of the dtype's largest finite value (NaN
+      and inf count as it); the sign is ignored; positions dropped in this step are eligible.
+    * The new pattern is Kept and Grown, ``nnz`` entries, columns ascending inside a row; the row
+      lengths change.
+
+    -> (row_indices, row_offsets, column_indices int32 [nnz], values [nnz], source int64 [nnz]),
+    new tensors: a kept entry carries its value bit for bit and its old entry index, a grown one
+    is +0.0 and -1.  ``d = 0`` reproduces the pattern (``source = arange(nnz)``).
+
+    GPU float32 / float16 / bfloat16 values and scores take the device step where
+    ``capi.csr_regrow_total_launch_shape`` serves the shape (up to 16384 rows and 65536 columns:
+    a fixed number of launches, no dense temporary, no host synchronisation); CPU tensors, other
+    dtypes (ranked as ``.float()``), larger shapes and ``enable_device_build(False)`` take
+    ``regrow_total_composed``.  Both give the same integers and value bits."""
+    d = ops.check_regrow_total_arguments(values, row_offsets, column_indices, drop, scores)
+    values, scores = values.detach(), scores.detach()
+    if scores.dtype not in _TOPK_DTYPES:
+        scores = scores.float()
+    if _regrow_total_served(values, scores):
+        return ops.csr_regrow_total(values, row_offsets, column_indices, d, scores)
+    return regrow_total_composed(values, row_offsets, column_indices, d, scores)
+
+
 def _csr_topk_served(values, m, n, total):
     if not (_device_build and values.is_cuda and values.dtype in _TOPK_DTYPES):
         return False
