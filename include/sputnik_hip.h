@@ -1453,6 +1453,58 @@ SPUTNIK_HIP_API int sputnik_hip_topk_to_csr_launch_shape(int m, int n, int eleme
                              int* rows_per_workgroup, int* digit_passes, int* grid);
 
 /* ------------------------------------------------------------------------
+ * A uniformly random CSR topology with its initial values, drawn on the device
+ * (topology.random_csr, SparseLinear.random): how a sparse layer starts when there is no
+ * trained dense weight (SET, RigL).  It is sputnik_hip_topk_to_csr over a key matrix that is
+ * never stored.  With the Philox4x32-10 and the state of "Attention dropout" above (the
+ * offset a multiple of 4), replica = row and entry = column:
+ *   w        = philox(key (seed lo, seed hi), counter (offset/4 lo, offset/4 hi, c >> 2, r))
+ *   key(r,c) = w[c & 3] & key_mask                key_mask <= 0x7fffffff; 0x7fffffff in use,
+ *                                                 smaller masks force ties (tests)
+ *   total_mode = 0   every row keeps its `count` (0 <= count <= n) largest keys, ties to the
+ *                    lowest column
+ *   total_mode = 1   the matrix keeps its `count` (0 <= count <= m * n) largest keys, ties to
+ *                    the lowest flat (row-major) index
+ * Exactly that many positions are kept.  The value of a kept position:
+ *   v          = philox(..., counter (offset/4 lo, offset/4 hi, c >> 2, r | 0x80000000))
+ *   q          = int(v[c & 3] >> 8) - 2^23                       in [-2^23, 2^23)
+ *   value(r,c) = float32(q) * scale                              one conversion, one multiply
+ * rounded to nearest even into `dtype` (SPUTNIK_HIP_F32 / F16 / BF16): uniform on
+ * [-bound, bound) for scale = float32(bound / 2^23).
+ *
+ * Outputs (device): row_offsets [m + 1], row_indices [m], column_indices [nonzeros] ascending
+ * inside a row and values [nonzeros], nonzeros = m * count or count, as
+ * sputnik_hip_topk_to_csr writes them; `rng_state_out` (may be NULL), int64 [2], receives the
+ * {seed, offset} the call resolved -- a call whose state points at it draws the same pattern.
+ * Every size is known before the first launch: the call never synchronises and is captured
+ * into a graph whole.
+ *
+ * Launches: per row ONE (a row's lanes select it in LDS, fill it and write its offset and its
+ * place in the row order).  Total: nine -- the clear, four digit passes, the rows launch, the
+ * scan, the fill, the row order.  A count of 0 launches no selection.  `workspace`:
+ * sputnik_hip_random_csr_workspace_bytes(m, n, total_mode) bytes (0 per row), 4-byte aligned.
+ *
+ * SPUTNIK_HIP_INVALID_ARGUMENT: a negative size, m * n above INT_MAX, a count out of range,
+ * total mode with more than 16384 rows, a key_mask above 0x7fffffff, an unknown dtype, a
+ * missing or misaligned pointer, a workspace too small.
+ * ---------------------------------------------------------------------- */
+SPUTNIK_HIP_API int sputnik_hip_random_csr(int m, int n, int total_mode, int64_t count, int dtype,
+                             float scale, unsigned key_mask, sputnik_hip_philox_state rng,
+                             int64_t* rng_state_out, void* workspace, size_t workspace_bytes,
+                             int* row_indices, int* row_offsets, int* column_indices, void* values,
+                             sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API size_t sputnik_hip_random_csr_workspace_bytes(int m, int n, int total_mode);
+
+/* The instance sputnik_hip_random_csr runs: served (0 in total mode above 16384 rows), the
+ * walk of sputnik_hip_dense_to_csr_launch_shape(1, m, n, 4) (four generated 32-bit keys per
+ * lane and step), digit_passes = 4 and the launches of a call with count > 0 (1 or 9).  Host
+ * only; any output pointer may be NULL. */
+SPUTNIK_HIP_API int sputnik_hip_random_csr_launch_shape(int m, int n, int total_mode, int* served,
+                             int* rows_per_wave, int* elements_per_lane, int* rows_per_workgroup,
+                             int* digit_passes, int* grid, int* launches);
+
+/* ------------------------------------------------------------------------
  * Per-row drop-and-grow of a CSR topology (topology.regrow_per_row,
  * SparseLinear.update_topology(..., per_row=True)): every row keeps its length, drops its
  * entries of smallest magnitude and grows as many where a dense score matrix is largest.

@@ -108,6 +108,10 @@ SIGNATURES = {
                                          _c_i64, _c_ptr, _c_size] + [_c_ptr] * 5),
     "sputnik_hip_topk_to_csr_workspace_bytes": (_c_size, [_c_int] * 3),
     "sputnik_hip_topk_to_csr_launch_shape": (_c_int, [_c_int] * 4 + [_c_ptr] * 6),
+    "sputnik_hip_random_csr": (_c_int, [_c_int] * 3 + [_c_i64, _c_int, _c_float, ctypes.c_uint, PhiloxState, _c_ptr,
+                                        _c_ptr, _c_size] + [_c_ptr] * 5),
+    "sputnik_hip_random_csr_workspace_bytes": (_c_size, [_c_int] * 3),
+    "sputnik_hip_random_csr_launch_shape": (_c_int, [_c_int] * 3 + [_c_ptr] * 7),
     "sputnik_hip_csr_regrow": (_c_int, [_c_int] * 3 + [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_int, _c_i64,
                                         ctypes.c_uint, _c_ptr, _c_size] + [_c_ptr] * 4),
     "sputnik_hip_csr_regrow_workspace_bytes": (_c_size, [_c_int] * 3),
@@ -560,6 +564,27 @@ def topk_to_csr_launch_shape(m, n, element_bytes, total):
     shape = {name: o.value for name, o in zip(names, outs)}
     shape["served"] = bool(shape["served"])
     return shape
+
+
+def random_csr_launch_shape(m, n, total):
+    """The instance of the device draw of a random m x n topology, ``total`` mode or per row: a
+    dict of served (bool; total mode stops at the row-order kernel's rows), rows_per_wave,
+    elements_per_lane, rows_per_workgroup, digit_passes, grid and launches (1 per row, 9 in
+    total mode; include/sputnik_hip.h).  Host only; raises for sizes the entry rejects."""
+    names = ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "digit_passes", "grid",
+             "launches")
+    outs = [_c_int(-1) for _ in names]
+    _check(lib().sputnik_hip_random_csr_launch_shape(
+        m, n, int(bool(total)), *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
+        "sputnik_hip_random_csr_launch_shape")
+    shape = {name: o.value for name, o in zip(names, outs)}
+    shape["served"] = bool(shape["served"])
+    return shape
+
+
+def random_csr_workspace_bytes(m, n, total):
+    """Bytes of workspace sputnik_hip_random_csr wants (0 per row).  Host only."""
+    return int(lib().sputnik_hip_random_csr_workspace_bytes(m, n, int(bool(total))))
 
 
 def csr_regrow_launch_shape(m, n, score_bytes, value_bytes):

@@ -1,7 +1,7 @@
 // CSR topologies from dense masks / matrices, built on the device for gfx950
 // (include/sputnik_hip.h: sputnik_hip_dense_to_csr_*, sputnik_hip_csr_row_order), and the
 // selections that write one out: sputnik_hip_topk_to_csr, sputnik_hip_csr_regrow, sputnik_hip_csr_topk,
-// sputnik_hip_csr_topk_global_*, sputnik_hip_csr_regrow_total.
+// sputnik_hip_csr_topk_global_*, sputnik_hip_csr_regrow_total, sputnik_hip_random_csr.
 //
 // The build replaces the torch loop of topology.dense_to_sparse_3d (per mask: != 0,
 // to_sparse_csr, two casts, a stable argsort and a host read of the count) by a fixed number of
@@ -29,6 +29,7 @@
 //                  Nothing outside [start, start + n) is ever read.
 //   RowWalk        a group covers group_lanes * V consecutive columns per step; made over a
 //                  dense row (the constructor) or over the entries of a CSR row (entry_walk)
+//   KeyWalk        the same walk over keys that are computed, not loaded (a random topology)
 //   radix_select   the need-th largest key of a group's row, MSB first, 8-bit digits, a 256-bin
 //                  histogram per row in LDS filled by the caller's step (count_digit per key)
 //   group_prefix   the flagged elements of a step in front of a lane's piece and in the whole
@@ -41,6 +42,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "philox.h"
 #include "wave_utils.h"
 
 namespace sputnik_hip {
@@ -145,6 +147,7 @@ __device__ __forceinline__ Piece<U> load_piece(const U* __restrict__ src, int64_
 // takes the steps and loads nothing.
 template <typename U>
 struct RowWalk {
+  using Element = U;
   static constexpr int V = kLoadBytes / sizeof(U);
   const U* src;
   bool live;
@@ -236,22 +239,23 @@ __device__ __forceinline__ void count_digit(unsigned key, bool counted, int shif
 }
 
 // Histogram of digit `shift / 8` of the row's keys (at most key_limit) whose higher digits equal
-// `prefix`; open(first column) = a bit per element of the piece that takes part.
-template <typename U, typename Open>
-__device__ __forceinline__ void digit_histogram(const RowWalk<U>& walk, int shift, unsigned prefix,
+// `prefix`; open(first column) = a bit per element of the piece that takes part.  Walk: a
+// RowWalk over memory, or a KeyWalk over generated keys.
+template <typename Walk, typename Open>
+__device__ __forceinline__ void digit_histogram(const Walk& walk, int shift, unsigned prefix,
                                                 unsigned* __restrict__ bins, unsigned key_limit, Open open) {
   for (int s = 0; s < walk.steps; ++s) {
     int64_t c0;
     unsigned valid;
-    const Piece<U> v = walk.load(s, &c0, &valid);
+    const Piece<typename Walk::Element> v = walk.load(s, &c0, &valid);
     const unsigned counted = valid & open(c0);
 #pragma unroll
-    for (int e = 0; e < RowWalk<U>::V; ++e)
+    for (int e = 0; e < Walk::V; ++e)
       count_digit(min(key_of(v.e[e]), key_limit), (counted >> e) & 1u, shift, prefix, bins);
   }
 }
-template <typename U>
-__device__ __forceinline__ void digit_histogram(const RowWalk<U>& walk, int shift, unsigned prefix,
+template <typename Walk>
+__device__ __forceinline__ void digit_histogram(const Walk& walk, int shift, unsigned prefix,
                                                 unsigned* __restrict__ bins) {
   digit_histogram(walk, shift, prefix, bins, kNoThreshold, [](int64_t) { return ~0u; });
 }
@@ -741,10 +745,11 @@ __global__ __launch_bounds__(kBuildBlock) void topk_total_hist_kernel(
 // Total mode: greater[row] = base + #(key > T), ties[row] = #(key == T) of the walk's row, T from
 // the filled bins; keys at most key_limit, open(first column) = a bit per element of the piece
 // that takes part.
-template <typename U, typename Open>
-__device__ __forceinline__ void count_against_total(const RowGroup& g, const RowWalk<U>& walk, unsigned count,
+template <typename Walk, typename Open>
+__device__ __forceinline__ void count_against_total(const RowGroup& g, const Walk& walk, unsigned count,
                                                     const unsigned* __restrict__ bins, unsigned key_limit, Open open,
                                                     int base, int* __restrict__ greater_out, int* __restrict__ ties) {
+  using U = typename Walk::Element;
   __shared__ unsigned select[kSelectWords];
   unsigned need;
   const unsigned prefix = total_select(bins, sizeof(U) * 8 / kDigitBits, count, select, &need);
@@ -768,8 +773,8 @@ __device__ __forceinline__ void count_against_total(const RowGroup& g, const Row
     ties[g.row] = equal;
   }
 }
-template <typename U>
-__device__ __forceinline__ void count_against_total(const RowGroup& g, const RowWalk<U>& walk, unsigned count,
+template <typename Walk>
+__device__ __forceinline__ void count_against_total(const RowGroup& g, const Walk& walk, unsigned count,
                                                     const unsigned* __restrict__ bins, int* __restrict__ greater_out,
                                                     int* __restrict__ ties) {
   count_against_total(g, walk, count, bins, kNoThreshold, [](int64_t) { return ~0u; }, 0, greater_out, ties);
@@ -827,10 +832,11 @@ __global__ __launch_bounds__(kScanBlock) void total_scan_kernel(
 
 // The elements of the walk's row that `kept` selects into the slots [out, end), in the order of
 // the walk: store(slot, the element's index in the row, the element).
-template <typename U, typename Store>
-__device__ __forceinline__ void fill_row(const RowGroup& g, const RowWalk<U>& walk, Selection kept, int64_t out,
+template <typename Walk, typename Store>
+__device__ __forceinline__ void fill_row(const RowGroup& g, const Walk& walk, Selection kept, int64_t out,
                                          int64_t end, Store store) {
-  constexpr int V = RowWalk<U>::V;
+  using U = typename Walk::Element;
+  constexpr int V = Walk::V;
   int ties_seen = 0;   // elements equal to the threshold in the steps behind
   for (int s = 0; s < walk.steps; ++s) {
     int64_t c0;
@@ -1655,6 +1661,199 @@ int launch_regrow_total(const RegrowTotalShape& r, int m, int n, int nonzeros, c
   return launch_status();
 }
 
+// ---------------------------------------------------------------------------
+// A uniformly random CSR topology with its initial values (sputnik_hip_random_csr): the top-k
+// selection above over a key matrix that never exists.  With the Philox4x32-10 of philox.h,
+// replica = row and entry = column,
+//   key(r, c)   = philox(seed, counter (offset/4, c >> 2, r))[c & 3] & key_mask
+//   value(r, c) = float(int(philox(seed, counter (offset/4, c >> 2, r | 2^31))[c & 3] >> 8) - 2^23) * scale
+// rounded to nearest even into the values type.  KeyWalk computes a piece of four keys with one
+// Philox call where RowWalk loads one, and radix_select, digit_histogram, count_against_total
+// and fill_row run on it as they run on memory: the Selection, the tie rule and the row order
+// are those of the dense top-k.
+//   per row   ONE launch: the group of lanes that walks a row selects it (four digit passes in
+//             its LDS bins), fills its columns and values and writes its offset r * k and its
+//             place r in the row order
+//   total     the launches of the dense total mode on generated keys: clear, four digit passes,
+//             rows, scan, a fill that also writes the values, the row order -- nine
+// A key is recomputed per pass instead of stored: 5 Philox calls per four columns and no
+// [m, n] array.  The resolved {seed, offset} is published by one lane of one launch.
+// ---------------------------------------------------------------------------
+constexpr int kKeyDigitPasses = 4;   // 32-bit keys
+
+struct RandomArgs {
+  DropArgs state;      // the Philox state and where it is published (threshold, scale unused)
+  unsigned key_mask;   // at most 0x7fffffff
+  float scale;         // bound / 2^23
+};
+
+// One group of lanes on one row of n generated keys.  No lead: a piece starts at a multiple of 4.
+struct KeyWalk {
+  using Element = uint32_t;
+  static constexpr int V = 4;
+  PhiloxKey key;
+  unsigned key_mask, row;
+  bool live;
+  int n, steps, group_lanes, group_lane;
+
+  __device__ __forceinline__ KeyWalk(const RowGroup& g, const PhiloxKey& key_, unsigned key_mask_, int m, int n_) {
+    key = key_;
+    key_mask = key_mask_;
+    group_lanes = g.group_lanes;
+    group_lane = g.group_lane;
+    live = g.row < m;
+    row = static_cast<unsigned>(g.row);
+    n = n_;
+    const int64_t span = static_cast<int64_t>(group_lanes) * V;
+    steps = static_cast<int>((static_cast<int64_t>(n_) + span - 1) / span);
+  }
+  // My piece of step s, its first column, and a bit per key that lies inside the row.
+  __device__ __forceinline__ Piece<uint32_t> load(int s, int64_t* first_column, unsigned* valid) const {
+    const int64_t c0 = (static_cast<int64_t>(s) * group_lanes + group_lane) * V;
+    *first_column = c0;
+    Piece<uint32_t> v = {{0u, 0u, 0u, 0u}};
+    unsigned in = 0;
+    if (live && c0 < n) {
+      const uint4 w = philox4x32_10(key, static_cast<unsigned>(c0 >> 2), row);
+      v.e[0] = w.x & key_mask;
+      v.e[1] = w.y & key_mask;
+      v.e[2] = w.z & key_mask;
+      v.e[3] = w.w & key_mask;
+      const int64_t inside = static_cast<int64_t>(n) - c0;
+      in = inside >= V ? (1u << V) - 1u : (1u << inside) - 1u;
+    }
+    *valid = in;
+    return v;
+  }
+};
+
+template <typename T>
+__device__ __forceinline__ T random_value(unsigned word, float scale) {
+  const float x = static_cast<float>(static_cast<int>(word >> 8) - (1 << 23)) * scale;
+  return static_cast<T>(x);
+}
+
+// fill_row over a row of generated keys: a kept column and its value.  The value words of a
+// piece are drawn once, for its first kept column.
+template <typename T>
+__device__ __forceinline__ void random_fill_row(const RowGroup& g, const KeyWalk& walk, Selection kept, int64_t out,
+                                                int64_t end, float scale, int* __restrict__ column_indices,
+                                                T* __restrict__ values) {
+  int64_t drawn = -1;
+  uint4 words = make_uint4(0u, 0u, 0u, 0u);
+  fill_row(g, walk, kept, out, end, [&](int64_t p, int64_t column, uint32_t) {
+    const int64_t piece = column >> 2;
+    if (piece != drawn) {
+      words = philox4x32_10(walk.key, static_cast<unsigned>(piece), walk.row | 0x80000000u);
+      drawn = piece;
+    }
+    column_indices[p] = static_cast<int>(column);
+    values[p] = random_value<T>(uint4_word(words, static_cast<int>(column & 3)), scale);
+  });
+}
+
+// Per-row mode: select and fill of every row, its offset and its place in the row order.
+template <typename T>
+__global__ __launch_bounds__(kBuildBlock) void random_rows_kernel(
+    int m, int n, int rows_per_wave, int k, RandomArgs args, int* __restrict__ row_offsets,
+    int* __restrict__ row_indices, int* __restrict__ column_indices, T* __restrict__ values) {
+  __shared__ unsigned hist[kBuildWaves * kMaxRowsPerWave][kDigitBins];   // 64 KiB
+  const PhiloxKey key = philox_key(args.state, blockIdx.x == 0 && threadIdx.x == 0);
+  const RowGroup g(rows_per_wave);
+  const KeyWalk walk(g, key, args.key_mask, m, n);
+  const Selection kept = radix_select<kKeyDigitPasses>(g, hist[g.slot], k,
+                                                       [&](int shift, unsigned prefix, unsigned* bins) {
+                                                         digit_histogram(walk, shift, prefix, bins);
+                                                       });
+  const int64_t out = g.row * k;
+  if (walk.live && g.group_lane == 0) {
+    row_offsets[g.row] = static_cast<int>(out);
+    row_indices[g.row] = static_cast<int>(g.row);
+    if (g.row == m - 1) row_offsets[m] = static_cast<int>(out + k);
+  }
+  random_fill_row(g, walk, kept, walk.live ? out : 0, walk.live ? out + k : 0, args.scale, column_indices, values);
+}
+
+// Total mode, one digit pass over the generated keys: this workgroup's rows.
+__global__ __launch_bounds__(kBuildBlock) void random_total_hist_kernel(int m, int n, int rows_per_wave, int pass,
+                                                                       unsigned count, RandomArgs args,
+                                                                       unsigned* bins) {
+  const PhiloxKey key = philox_key(args.state, false);
+  workgroup_digit_pass<kKeyDigitPasses>(pass, count, bins, [&](int shift, unsigned prefix, unsigned* hist) {
+    const RowGroup g(rows_per_wave);
+    const KeyWalk walk(g, key, args.key_mask, m, n);
+    digit_histogram(walk, shift, prefix, hist);
+  });
+}
+
+// Total mode: row_offsets[row + 1] = #(key > T), ties[row] = #(key == T).
+__global__ __launch_bounds__(kBuildBlock) void random_total_rows_kernel(
+    int m, int n, int rows_per_wave, unsigned count, RandomArgs args, const unsigned* __restrict__ bins,
+    int* __restrict__ row_offsets, int* __restrict__ ties) {
+  const PhiloxKey key = philox_key(args.state, false);
+  const RowGroup g(rows_per_wave);
+  const KeyWalk walk(g, key, args.key_mask, m, n);
+  count_against_total(g, walk, count, bins, row_offsets + 1, ties);
+}
+
+// Total mode: the fill of every row under the one threshold and the rows' quotas; publishes the state.
+template <typename T>
+__global__ __launch_bounds__(kBuildBlock) void random_total_fill_kernel(
+    int m, int n, int rows_per_wave, int64_t capacity, RandomArgs args, const unsigned* __restrict__ threshold,
+    const int* __restrict__ quotas, const int* __restrict__ row_offsets, int* __restrict__ column_indices,
+    T* __restrict__ values) {
+  const PhiloxKey key = philox_key(args.state, blockIdx.x == 0 && threadIdx.x == 0);
+  const RowGroup g(rows_per_wave);
+  const KeyWalk walk(g, key, args.key_mask, m, n);
+  int64_t out, end;
+  new_slots(row_offsets, g.row, walk.live, capacity, &out, &end);
+  random_fill_row(g, walk, {*threshold, walk.live ? quotas[g.row] : 0}, out, end, args.scale, column_indices, values);
+}
+
+struct RandomShape {
+  int status = 0;
+  int served = 0, launches = 0;
+  BuildShape walk;
+};
+inline RandomShape random_shape(int m, int n, int total_mode) {
+  RandomShape r;
+  if (total_mode != 0 && total_mode != 1) {
+    r.status = SPUTNIK_HIP_INVALID_ARGUMENT;
+    return r;
+  }
+  r.walk = build_shape(1, m, n, static_cast<int>(sizeof(uint32_t)));
+  r.status = r.walk.status;
+  if (r.status != 0) return r;
+  r.served = total_mode ? order_route(1, m, n).served : 1;
+  // total: clear, digits, rows, scan, fill, row order
+  r.launches = total_mode ? 1 + kKeyDigitPasses + 4 : 1;
+  return r;
+}
+
+template <typename T>
+int launch_random(const RandomShape& r, int m, int n, int total_mode, unsigned count, const RandomArgs& args,
+                  void* workspace, int* row_indices, int* row_offsets, int* column_indices, void* values_,
+                  hipStream_t stream) {
+  T* values = static_cast<T*>(values_);
+  const int rows = r.walk.rows_per_wave;
+  const dim3 grid(r.walk.grid), block(kBuildBlock);
+  if (!total_mode) {
+    hipLaunchKernelGGL((random_rows_kernel<T>), grid, block, 0, stream, m, n, rows, static_cast<int>(count), args,
+                       row_offsets, row_indices, column_indices, values);
+    return launch_status();
+  }
+  const TotalWorkspace w(workspace, false);
+  launch_digit_passes(w.bins, kKeyDigitPasses, stream, [&](int p) {
+    hipLaunchKernelGGL(random_total_hist_kernel, grid, block, 0, stream, m, n, rows, p, count, args, w.bins);
+  });
+  hipLaunchKernelGGL(random_total_rows_kernel, grid, block, 0, stream, m, n, rows, count, args, w.bins, row_offsets,
+                     w.quotas() + m);
+  launch_total_scan(w, w.quotas(), m, kKeyDigitPasses, count, row_offsets, true, nullptr, stream);
+  hipLaunchKernelGGL((random_total_fill_kernel<T>), grid, block, 0, stream, m, n, rows, static_cast<int64_t>(count),
+                     args, w.threshold, w.quotas(), row_offsets, column_indices, values);
+  return launch_status();
+}
+
 inline void put(int* p, int v) {
   if (p) *p = v;
 }
@@ -2077,6 +2276,79 @@ int sputnik_hip_csr_topk_global_fill(int layers, const int* rows, const int* non
       if (order != 0) return order;
     }
   return launch_status();
+}
+
+int sputnik_hip_random_csr_launch_shape(int m, int n, int total_mode, int* served, int* rows_per_wave,
+                                        int* elements_per_lane, int* rows_per_workgroup, int* digit_passes,
+                                        int* grid, int* launches) {
+  const RandomShape r = random_shape(m, n, total_mode);
+  if (r.status != 0) return r.status;
+  put(served, r.served);
+  put(rows_per_wave, r.walk.rows_per_wave);
+  put(elements_per_lane, r.walk.elements_per_lane);
+  put(rows_per_workgroup, r.walk.rows_per_workgroup);
+  put(digit_passes, kKeyDigitPasses);
+  put(grid, r.walk.grid);
+  put(launches, r.launches);
+  return 0;
+}
+
+size_t sputnik_hip_random_csr_workspace_bytes(int m, int n, int total_mode) {
+  if (m < 0 || n < 0 || !total_mode) return 0;   // per row: registers and LDS only
+  return sizeof(unsigned) * topk_workspace_words(m, 1);
+}
+
+int sputnik_hip_random_csr(int m, int n, int total_mode, int64_t count, int dtype, float scale, unsigned key_mask,
+                           sputnik_hip_philox_state rng, int64_t* rng_state_out, void* workspace,
+                           size_t workspace_bytes, int* row_indices, int* row_offsets, int* column_indices,
+                           void* values, sputnik_hip_stream_t stream_) {
+  const RandomShape r = random_shape(m, n, total_mode);
+  if (r.status != 0) return r.status;
+  if (!r.served || key_mask > 0x7fffffffu ||
+      (dtype != SPUTNIK_HIP_F32 && dtype != SPUTNIK_HIP_F16 && dtype != SPUTNIK_HIP_BF16))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const int64_t most = total_mode ? static_cast<int64_t>(m) * n : n;
+  if (count < 0 || count > most || row_offsets == nullptr || !aligned_to(row_offsets, sizeof(int)) ||
+      (rng_state_out != nullptr && !aligned_to(rng_state_out, sizeof(int64_t))) ||
+      (m > 0 && (row_indices == nullptr || !aligned_to(row_indices, sizeof(int)))))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  RandomArgs args;
+  args.state.rng = rng;
+  args.state.rng_state_out = rng_state_out;
+  args.state.threshold = 0u;
+  args.state.scale = 0.f;
+  args.state.replica0 = 0;
+  args.key_mask = key_mask;
+  args.scale = scale;
+  if (m == 0 || count == 0) {
+    // nothing is kept: the zero offsets, the row order 0 .. m - 1 of equal lengths, and the state
+    if (hipMemsetAsync(row_offsets, 0, sizeof(int) * (static_cast<size_t>(m) + 1), stream) != hipSuccess)
+      return launch_status();
+    if (m > 0) {
+      const int order = sputnik_hip_csr_row_order(1, m, n, row_offsets, row_indices, stream_);
+      if (order != 0) return order;
+    }
+    return publish_rng_state(args.state, stream);
+  }
+  const int value_bytes = dtype == SPUTNIK_HIP_F32 ? 4 : 2;
+  const size_t ws_bytes = sputnik_hip_random_csr_workspace_bytes(m, n, total_mode);
+  if (column_indices == nullptr || !aligned_to(column_indices, sizeof(int)) || values == nullptr ||
+      !aligned_to(values, value_bytes) ||
+      (ws_bytes > 0 && (workspace == nullptr || !aligned_to(workspace, sizeof(unsigned)) || workspace_bytes < ws_bytes)))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  int st;
+  if (dtype == SPUTNIK_HIP_F32)
+    st = launch_random<float>(r, m, n, total_mode, static_cast<unsigned>(count), args, workspace, row_indices,
+                              row_offsets, column_indices, values, stream);
+  else if (dtype == SPUTNIK_HIP_F16)
+    st = launch_random<_Float16>(r, m, n, total_mode, static_cast<unsigned>(count), args, workspace, row_indices,
+                                 row_offsets, column_indices, values, stream);
+  else
+    st = launch_random<__bf16>(r, m, n, total_mode, static_cast<unsigned>(count), args, workspace, row_indices,
+                               row_offsets, column_indices, values, stream);
+  if (st != 0 || !total_mode) return st;
+  return sputnik_hip_csr_row_order(1, m, n, row_offsets, row_indices, stream_);
 }
 
 }  // extern "C"

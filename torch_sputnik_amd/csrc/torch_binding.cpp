@@ -1192,10 +1192,10 @@ void check_p(double p) {
   TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout probability must lie in [0, 1), got ", p);
 }
 
-Drop make_drop(double p, const c10::optional<Tensor>& rng_state, const Tensor& like) {
-  check_p(p);
+// The Philox state of one call on `like`'s device: the replay of `rng_state`, or a fresh draw
+// of 4 from the device's default generator.
+Drop draw_state(const c10::optional<Tensor>& rng_state, const Tensor& like) {
   Drop d;
-  d.p = p;
   if (rng_state.has_value() && rng_state->defined()) {
     const Tensor& st = *rng_state;
     TORCH_CHECK(st.scalar_type() == at::kLong && st.numel() == 2 && st.is_contiguous() &&
@@ -1206,9 +1206,6 @@ Drop make_drop(double p, const c10::optional<Tensor>& rng_state, const Tensor& l
     d.rng.offset_ptr = st.data_ptr<int64_t>() + 1;
     return d;
   }
-  // p = 0 drops nothing and draws nothing: no state exists, and rng_state stays undefined
-  // (None in Python).  ops.sparse_dropout(values, 0) comes here; the attention ops refuse p = 0.
-  if (p == 0.0) return d;
   d.rng_state = at::empty({2}, like.options().dtype(at::kLong));
   d.rng_state_out = d.rng_state.data_ptr<int64_t>();
   auto* gen = at::get_generator_or_default<at::CUDAGeneratorImpl>(
@@ -1226,6 +1223,16 @@ Drop make_drop(double p, const c10::optional<Tensor>& rng_state, const Tensor& l
     d.rng.seed = state.seed_.val;
     d.rng.offset = state.offset_.val;
   }
+  return d;
+}
+
+Drop make_drop(double p, const c10::optional<Tensor>& rng_state, const Tensor& like) {
+  check_p(p);
+  // p = 0 drops nothing and draws nothing: no state exists, and rng_state stays undefined
+  // (None in Python).  ops.sparse_dropout(values, 0) comes here; the attention ops refuse p = 0.
+  const bool replay = rng_state.has_value() && rng_state->defined();
+  Drop d = replay || p != 0.0 ? draw_state(rng_state, like) : Drop();
+  d.p = p;
   return d;
 }
 
@@ -2067,6 +2074,53 @@ std::vector<Tensor> topk_to_csr(const Tensor& scores_in, int64_t per_row, int64_
   return {row_indices, row_offsets, column_indices, values};
 }
 
+// A uniformly random m x n CSR topology with its initial values, drawn on `device`
+// (sputnik_hip.h: sputnik_hip_random_csr) -> [row_indices, row_offsets, column_indices, values,
+// rng_state]: `per_row` positions of every row or `total` of the matrix (the other one -1),
+// values of `dtype` uniform on [-2^23 scale, 2^23 scale).  The state comes from the device's
+// default generator as attention dropout's does (draw_state), or replays `rng_state`; the
+// returned rng_state holds what the kernels resolved.  Every size is known up front: no
+// synchronisation, and a captured call draws a new pattern on every replay.
+std::vector<Tensor> random_csr(int64_t m_in, int64_t n_in, int64_t per_row, int64_t total, at::ScalarType dtype,
+                               double scale, c10::Device device, const c10::optional<Tensor>& rng_state,
+                               int64_t key_mask) {
+  TORCH_CHECK(device.is_cuda(), "random_csr: a GPU (HIP) device is needed, got ", device);
+  TORCH_CHECK(type_code(dtype) >= 0, "random_csr: values must be float32, float16 or bfloat16, got ", dtype);
+  TORCH_CHECK((per_row >= 0) != (total >= 0), "give exactly one of per_row / total");
+  TORCH_CHECK(key_mask >= 0 && key_mask <= 0x7fffffff, "random_csr: key_mask must lie in 0 .. 0x7fffffff");
+  TORCH_CHECK(m_in >= 0 && n_in >= 0, "random_csr: negative size");
+  const c10::DeviceGuard guard(device);
+  if (!device.has_index()) device = c10::Device(device.type(), at::cuda::current_device());
+  const int m = to_int(m_in, "m"), n = to_int(n_in, "n");
+  const int total_mode = total >= 0 ? 1 : 0;
+  const int64_t count = total_mode ? total : per_row;
+  int served = 0;
+  check_status(sputnik_hip_random_csr_launch_shape(m, n, total_mode, &served, nullptr, nullptr, nullptr, nullptr,
+                                                   nullptr, nullptr),
+               "random_csr");
+  TORCH_CHECK(served, "torch_sputnik::random_csr: total mode over ", m, " rows is beyond the row-order "
+              "kernel (sputnik_hip_random_csr_launch_shape); take topology.random_csr");
+  TORCH_CHECK(count <= (total_mode ? static_cast<int64_t>(m) * n : static_cast<int64_t>(n)),
+              "torch_sputnik::random_csr: ", count, " entries asked of ", total_mode ? "a matrix" : "rows",
+              " of ", total_mode ? static_cast<int64_t>(m) * n : static_cast<int64_t>(n));
+  const int64_t nonzeros = total_mode ? count : count * m;
+  const auto index_options = at::TensorOptions().device(device).dtype(at::kInt);
+  Tensor row_indices = at::empty({m}, index_options);
+  Tensor row_offsets = at::empty({m + 1}, index_options);
+  Tensor column_indices = at::empty({nonzeros}, index_options);
+  Tensor values = at::empty({nonzeros}, index_options.dtype(dtype));
+  const Drop state = draw_state(rng_state, row_offsets);
+  const size_t ws_bytes = sputnik_hip_random_csr_workspace_bytes(m, n, total_mode);
+  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, index_options.dtype(at::kByte));
+  check_status(sputnik_hip_random_csr(m, n, total_mode, count, type_code(dtype), static_cast<float>(scale),
+                                      static_cast<unsigned>(key_mask), state.rng, state.rng_state_out,
+                                      workspace.data_ptr(), ws_bytes, row_indices.data_ptr<int>(),
+                                      row_offsets.data_ptr<int>(), column_indices.data_ptr<int>(),
+                                      values.data_ptr(), current_stream(row_offsets)),
+               "random_csr");
+  return {row_indices, row_offsets, column_indices, values, state.rng_state};
+}
+
 // One per-row drop-and-grow step of the CSR pattern (row_offsets [m + 1], column_indices [nnz])
 // with `values` [nnz] under dense `scores` [m, n] -> [column_indices, values, source (int64)] of
 // the new pattern in the same slots (sputnik_hip.h: sputnik_hip_csr_regrow).  nnz is known up
@@ -2814,6 +2868,9 @@ TORCH_LIBRARY(torch_sputnik, m) {
   m.def("dense_to_csr(Tensor dense, bool with_values) -> Tensor[]");
   m.def("row_order(Tensor row_offsets) -> Tensor");
   m.def("topk_to_csr(Tensor scores, int per_row, int total, Tensor? values_from) -> Tensor[]");
+  // (no tensor among the arguments of a fresh draw: registered for every backend, GPU devices only)
+  m.def("random_csr(int m, int n, int per_row, int total, ScalarType dtype, float scale, Device device, "
+        "Tensor? rng_state, int key_mask) -> Tensor[]", &random_csr);
   m.def("csr_regrow(Tensor values, Tensor row_offsets, Tensor column_indices, Tensor drop_counts, "
         "Tensor scores) -> Tensor[]");
   m.def("csr_regrow_total(Tensor values, Tensor row_offsets, Tensor column_indices, int drop, "

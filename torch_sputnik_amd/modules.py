@@ -14,7 +14,10 @@ opts in to a softmax with a gradient.
 Additions: ``SparseLinear.from_dense`` builds a ready layer from a dense weight by
 magnitude, ``SparseLinear.update_topology`` is one drop-and-grow step (SET, RigL),
 ``SparseLinear.collect_dense_grad`` / ``rigl_update`` gather RigL's grow scores in the backward,
-``SparseLinear.prune_to`` is one step of gradual magnitude pruning (the layer becomes sparser).
+``SparseLinear.prune_to`` is one step of gradual magnitude pruning (the layer becomes sparser),
+``SparseLinear.random`` builds a ready layer with a uniformly random topology and a sparse-aware
+initialisation, drawn on the device (with ``topology.erk_densities`` for the layers' densities:
+the start of SET and RigL).
 """
 import copy
 import math
@@ -109,6 +112,29 @@ class SparseLinear(nn.Module):
         module = cls(weight.size(1), weight.size(0)).to(device=weight.device, dtype=weight.dtype)
         values, row_indices, row_offsets, column_indices = topology.magnitude_prune(
             weight.detach(), density=density, nonzeros=nonzeros, per_row=per_row)
+        module._set_topology(nn.Parameter(values), row_indices, row_offsets, column_indices)
+        return module
+
+    @classmethod
+    def random(cls, input_features, output_features, density=None, nonzeros=None, per_row=False,
+               dtype=torch.float32, bound=None, device=None, rng_state=None):
+        """A sparse layer with a uniformly random topology, for training sparse from scratch
+        (SET, RigL): ``round(density * out * in)`` (or ``nonzeros``) positions of the matrix,
+        ``per_row`` that share of every row -- exactly that many, every position equally likely
+        -- and values uniform on ``[-bound, bound)``, by default ``bound = 1 / sqrt(entries per
+        row)``: kaiming-uniform on the effective fan-in (``topology.random_csr`` states the
+        rule).  On a GPU ``device`` pattern and values are drawn by the device kernels from the
+        device's default generator (``torch.manual_seed``) without an ``[out, in]`` array and
+        without a host synchronisation; ``rng_state`` (int64 [2]) reproduces a draw, on any
+        device.  ``topology.erk_densities`` gives the layers of a model their densities.
+        ``values`` is a Parameter of ``dtype``, the topology is registered as static: ready to
+        call, and ``update_topology``, ``rigl_update`` and ``prune_to`` work on it.  As
+        everywhere in this module ``weight`` and ``bias`` are uninitialised and unused."""
+        device = torch.device("cpu" if device is None else device)
+        module = cls(input_features, output_features).to(device=device, dtype=dtype)
+        values, row_indices, row_offsets, column_indices = topology.random_csr(
+            output_features, input_features, density=density, nonzeros=nonzeros, per_row=per_row, dtype=dtype,
+            bound=bound, device=device, rng_state=rng_state)
         module._set_topology(nn.Parameter(values), row_indices, row_offsets, column_indices)
         return module
 

@@ -358,6 +358,62 @@ def topk_to_csr(scores, per_row=None, total=None, values_from=None):
                                   values_from))
 
 
+RANDOM_KEY_MASK = 0x7fffffff
+
+
+def random_value_scale(bound):
+    """``float32(bound / 2**23)`` as a Python float: the step between two values of a random
+    topology, computed in double and rounded once."""
+    bound = float(bound)
+    if not (0.0 <= bound < float("inf")):
+        raise ValueError(f"random_csr: bound {bound} should be a finite number >= 0")
+    return float(torch.tensor(bound / 2.0 ** 23, dtype=torch.float64).to(torch.float32))
+
+
+def check_random_arguments(m, n, per_row, total, dtype, key_mask):
+    """ValueError unless the arguments describe a random ``m x n`` topology; -> the count."""
+    if (per_row is None) == (total is None):
+        raise ValueError("random_csr: give exactly one of per_row / total")
+    m, n = int(m), int(n)
+    if m < 0 or n < 0:
+        raise ValueError(f"random_csr: expected sizes >= 0, got {m} x {n}")
+    if dtype not in _TOPK_DTYPES:
+        raise ValueError(f"random_csr: values must be float32, float16 or bfloat16, got {dtype}")
+    count, most = (int(total), m * n) if per_row is None else (int(per_row), n)
+    if not 0 <= count <= most:
+        raise ValueError(f"random_csr: {'total' if per_row is None else 'per_row'} = {count} is outside 0 .. {most}")
+    if not 0 <= int(key_mask) <= RANDOM_KEY_MASK:
+        raise ValueError(f"random_csr: key_mask {key_mask} is outside 0 .. 0x7fffffff")
+    return count
+
+
+def random_csr(m, n, per_row=None, total=None, dtype=torch.float32, bound=1.0, device=None, rng_state=None,
+               key_mask=RANDOM_KEY_MASK):
+    """A uniformly random ``m x n`` CSR topology with its initial values, drawn on the device
+    (csrc/topology.hip): ``per_row = k`` keeps k positions of every row, ``total = K`` K positions
+    of the matrix -- exactly one of the two; exactly that many, every position equally likely.
+    It is ``topk_to_csr`` over Philox keys that are computed where a score would be loaded
+    (include/sputnik_hip.h states the rule), so no ``[m, n]`` array exists.  ``values``
+    (float32 / float16 / bfloat16) are uniform on ``[-bound, bound)``.
+    -> (row_indices, row_offsets, column_indices, values, rng_state); ``rng_state`` (int64 [2],
+    {seed, offset}) is what the call drew from the device's default generator
+    (``torch.manual_seed`` makes runs repeat; a captured call draws a new pattern per replay), or
+    the ``rng_state`` given, which reproduces the call that returned it.  ``key_mask`` below
+    0x7fffffff forces ties between keys (tests).  One launch per row, nine in total mode, no host
+    synchronisation.  Raises for a CPU device and for shapes ``capi.random_csr_launch_shape``
+    does not serve (total mode above 16384 rows)."""
+    count = check_random_arguments(m, n, per_row, total, dtype, key_mask)
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise RuntimeError("random_csr: GPU devices only (topology.random_csr serves the CPU)")
+    if rng_state is not None and (rng_state.dtype != torch.int64 or rng_state.numel() != 2):
+        raise ValueError("random_csr: rng_state must be an int64 [2] tensor {seed, offset}")
+    if rng_state is not None:
+        rng_state = rng_state.to(device).contiguous()
+    return tuple(_ops.random_csr(int(m), int(n), -1 if per_row is None else count, -1 if total is None else count,
+                                 dtype, random_value_scale(bound), device, rng_state, int(key_mask)))
+
+
 def check_regrow_arguments(values, row_offsets, column_indices, drop_counts, scores):
     """ValueError unless the five tensors are one CSR pattern with its values, drop counts and
     dense scores (shapes, int32 indices, one device).  Dtypes of values and scores are the

@@ -3,7 +3,11 @@
 modules/sparse_attention.py:12-36).  CPU tensors take pure torch; GPU tensors are
 built by the device kernels of csrc/topology.hip (``ops.dense_to_csr``,
 ``ops.row_order``) where their host queries serve the shape -- the same integers
-either way (``enable_device_build``)."""
+either way (``enable_device_build``).  ``random_csr`` draws a uniformly random topology
+with its initial values (``ops.random_csr`` on a GPU), ``erk_densities`` gives the layers of
+a model their Erdos-Renyi-Kernel densities."""
+import math
+
 import numpy as np
 import torch
 
@@ -137,6 +141,14 @@ def topk_to_csr(scores, per_row=None, total=None, values_from=None):
         scores = scores.float()
     if _topk_served(scores, values_from, per_row is None):
         return ops.topk_to_csr(scores, per_row, total, values_from)
+    return _topk_to_csr_torch(scores, None if per_row is None else count, None if total is None else count,
+                              values_from)
+
+
+def _topk_to_csr_torch(scores, per_row, total, values_from):
+    """the torch path of ``topk_to_csr``: float32 / float16 / bfloat16 scores, checked arguments"""
+    m, n = scores.shape
+    count = total if per_row is None else per_row
     keys = magnitude_keys(scores)
     int32 = dict(dtype=torch.int32, device=scores.device)
     if per_row is not None:
@@ -153,6 +165,168 @@ def topk_to_csr(scores, per_row=None, total=None, values_from=None):
     row_offsets[1:] = torch.cumsum(torch.bincount(rows, minlength=m), 0)
     return (diffsort(row_offsets), row_offsets, (flat - rows * n).to(torch.int32),
             _take_bits(values_from, flat))
+
+
+_PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+_PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+_LO32 = 0xffffffff
+
+
+def _mulhilo32(multiplier, c):
+    """(high, low) 32-bit words of ``multiplier * c`` for int64 tensors holding 32-bit words,
+    through 16-bit halves so that no product leaves int64"""
+    upper, lower = (c >> 16) * multiplier, (c & 0xffff) * multiplier   # below 2**48 each
+    return (upper + (lower >> 16)) >> 16, (((upper & 0xffff) << 16) + lower) & _LO32
+
+
+def _philox4x32_10(key, counter):
+    """Philox4x32-10 (csrc/philox.h) on int64 tensors that hold 32-bit words: ``key`` two Python
+    ints, ``counter`` four broadcastable tensors -> the four output words."""
+    k0, k1 = key
+    c0, c1, c2, c3 = torch.broadcast_tensors(*counter)
+    for _ in range(10):
+        hi0, lo0 = _mulhilo32(_PHILOX_M[0], c0)
+        hi1, lo1 = _mulhilo32(_PHILOX_M[1], c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + _PHILOX_W[0]) & _LO32, (k1 + _PHILOX_W[1]) & _LO32
+    return c0, c1, c2, c3
+
+
+def _random_words(m, n, seed, offset, device, values):
+    """int64 [m, n]: word ``c & 3`` of Philox(seed, counter (offset / 4, c >> 2, r)) for every
+    position (r, c); ``values``: r | 2**31 in the counter (the stream of the values)"""
+    seed, block = int(seed) & 0xffffffffffffffff, (int(offset) & 0xffffffffffffffff) // 4
+    index = dict(dtype=torch.int64, device=device)
+    quads = torch.arange((n + 3) // 4, **index)[None, :]
+    rows = torch.arange(m, **index)[:, None] | (0x80000000 if values else 0)
+    words = _philox4x32_10((seed & _LO32, seed >> 32),
+                           (torch.full((1, 1), block & _LO32, **index), torch.full((1, 1), block >> 32, **index),
+                            quads, rows))
+    return torch.stack(words, dim=2).reshape(m, -1)[:, :n]
+
+
+def _random_csr_torch(m, n, per_row, total, dtype, scale, seed, offset, device, key_mask=ops.RANDOM_KEY_MASK):
+    """The rule of ``random_csr`` in torch: the keys and the values of every position as dense
+    [m, n] images, through the torch path of ``topk_to_csr`` -- a key viewed as float32 bits ranks
+    by exactly ``magnitude_keys``.  -> (row_indices, row_offsets, column_indices, values)"""
+    keys = _random_words(m, n, seed, offset, device, False) & int(key_mask)
+    q = (_random_words(m, n, seed, offset, device, True) >> 8) - 2 ** 23
+    values = (q.to(torch.float32) * scale).to(dtype)      # one conversion, one float32 multiply, one rounding
+    scores = keys.to(torch.int32).view(torch.float32)
+    return _topk_to_csr_torch(scores, per_row, total, values)
+
+
+def _random_served(m, n, device, total):
+    if not (_device_build and device.type == "cuda"):
+        return False
+    try:
+        return capi.random_csr_launch_shape(m, n, total)["served"]
+    except RuntimeError:   # (more than INT_MAX positions)
+        return False
+
+
+def _draw_philox_state(device):
+    """(seed, offset) for a call without an ``rng_state``: 4 of the device's default generator
+    on a GPU, as the device path draws them; a seed from torch's CPU generator otherwise"""
+    if device.type == "cuda":
+        index = torch.cuda.current_device() if device.index is None else device.index
+        generator = torch.cuda.default_generators[index]
+        offset = generator.get_offset()
+        generator.set_offset(offset + 4)
+        return generator.initial_seed(), offset
+    return int(torch.randint(0, 2 ** 62, (1,))), 0
+
+
+def random_csr(m, n, density=None, nonzeros=None, per_row=False, dtype=torch.float32, bound=None, device=None,
+               rng_state=None, return_rng_state=False):
+    """A uniformly random ``m x n`` topology with its initial values -> (values, row_indices,
+    row_offsets, column_indices), the tuple of ``dense_to_sparse``: how a layer of SET, RigL or
+    any sparse-from-scratch method starts.  Counts are ``magnitude_prune``'s: ``density`` keeps
+    ``round(density * m * n)`` positions of the matrix, or ``per_row`` ``round(density * n)`` of
+    every row; ``nonzeros`` is that number itself.  Exactly that many positions are kept, every
+    position with the same probability, columns ascending inside a row.
+
+    The rule, for ``rng_state = {seed, offset}`` (offset a multiple of 4), with Philox4x32-10:
+    ``key(r, c) = Philox(seed, (offset / 4, c >> 2, r))[c & 3] & 0x7fffffff``; the positions of
+    largest key are kept, ties to the lowest flat index (column, ``per_row``) --
+    ``topk_to_csr``'s selection.  A kept position's value is ``float32(q) * float32(bound /
+    2**23)`` with ``q = (Philox(seed, (offset / 4, c >> 2, r | 2**31))[c & 3] >> 8) - 2**23``,
+    rounded to nearest even into ``dtype``: uniform on ``[-bound, bound)``.  ``bound=None`` is
+    ``1 / sqrt(max(1, count_per_row))`` with the (mean) entries of a row: kaiming-uniform on the
+    effective fan-in.
+
+    A GPU ``device`` takes the device kernels (``ops.random_csr``: the keys are computed where a
+    score would be loaded, one launch per row or nine matrix-wide, no ``[m, n]`` array, no host
+    synchronisation); the CPU, ``enable_device_build(False)`` and matrix-wide draws over more
+    than 16384 rows take the same rule in torch.  Given the same ``rng_state`` (int64 [2]) both
+    return the same integers and value bits.  Without one a GPU call draws 4 from the device's
+    default generator (``torch.manual_seed`` makes runs repeat) and a CPU call a seed from
+    torch's CPU generator with offset 0.  ``return_rng_state``: the state used is appended."""
+    if (density is None) == (nonzeros is None):
+        raise ValueError("random_csr: give exactly one of density / nonzeros")
+    m, n = int(m), int(n)
+    if m < 0 or n < 0:
+        raise ValueError(f"random_csr: expected sizes >= 0, got {m} x {n}")
+    most = n if per_row else m * n
+    if density is not None:
+        if not 0.0 <= density <= 1.0:
+            raise ValueError(f"random_csr: density {density} is outside 0 .. 1")
+        nonzeros = round(density * most)
+    count = int(nonzeros)
+    if not 0 <= count <= most:
+        raise ValueError(f"random_csr: {count} entries asked of {most}")
+    per_row_count, total = (count, None) if per_row else (None, count)
+    ops.check_random_arguments(m, n, per_row_count, total, dtype, ops.RANDOM_KEY_MASK)
+    if bound is None:
+        bound = 1.0 / math.sqrt(max(1.0, float(count) if per_row else count / max(m, 1)))
+    device = torch.device("cpu" if device is None else device)
+    if _random_served(m, n, device, not per_row):
+        row_indices, row_offsets, column_indices, values, state = ops.random_csr(
+            m, n, per_row=per_row_count, total=total, dtype=dtype, bound=bound, device=device, rng_state=rng_state)
+    else:
+        if rng_state is None:
+            seed, offset = _draw_philox_state(device)
+            state = torch.tensor([seed, offset], dtype=torch.int64, device=device)
+        else:
+            state = rng_state
+            seed, offset = (int(v) for v in rng_state.tolist())
+        if offset % 4 != 0:
+            raise ValueError(f"random_csr: the offset of rng_state must be a multiple of 4, got {offset}")
+        row_indices, row_offsets, column_indices, values = _random_csr_torch(
+            m, n, per_row_count, total, dtype, ops.random_value_scale(bound), seed, offset, device)
+    result = (values, row_indices, row_offsets, column_indices)
+    return result + (state,) if return_rng_state else result
+
+
+def erk_densities(shapes, density, power=1.0):
+    """The Erdos-Renyi-Kernel densities of a list of layers (Evci et al., "Rigging the Lottery",
+    2020): ``shapes`` a list of ``(out, in)``, layer l gets ``eps * ((out + in) / (out * in)) **
+    power`` with eps such that the layers hold ``density`` of all positions together,
+    ``sum density_l * out_l * in_l = density * sum out_l * in_l``.  While the layer of largest
+    density would exceed 1 it is made dense and eps is solved again without it (RigL's
+    procedure).  ``power = 0`` is the uniform distribution.  Host only -> a list of floats in
+    (0, 1], to pass to ``SparseLinear.random(..., density=)``."""
+    if not 0.0 < density <= 1.0:
+        raise ValueError(f"erk_densities: density {density} is outside (0, 1]")
+    shapes = [(int(out), int(inp)) for out, inp in shapes]
+    if any(out <= 0 or inp <= 0 for out, inp in shapes):
+        raise ValueError(f"erk_densities: every shape must be (out, in) with positive sizes, got {shapes}")
+    if density == 1.0:
+        return [1.0] * len(shapes)
+    sizes = [out * inp for out, inp in shapes]
+    raw = [((out + inp) / (out * inp)) ** power for out, inp in shapes]
+    dense = set()
+    while True:
+        sparse = [l for l in range(len(shapes)) if l not in dense]
+        if not sparse:
+            break
+        budget = density * sum(sizes) - sum(sizes[l] for l in dense)
+        eps = budget / sum(raw[l] * sizes[l] for l in sparse)
+        largest = max(raw[l] for l in sparse)
+        if largest * eps <= 1.0:
+            break
+        dense.update(l for l in sparse if raw[l] == largest)
+    return [1.0 if l in dense else min(1.0, eps * raw[l]) for l in range(len(shapes))]
 
 
 def magnitude_prune(matrix, density=None, nonzeros=None, per_row=False):
