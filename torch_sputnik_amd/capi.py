@@ -325,6 +325,19 @@ def sddmm_kernel_name(m, k, n, nonzeros, replicas=1, elem_bytes=4, planned=False
                                                int(bool(planned))).decode()
 
 
+def _check(status, what):
+    if status != 0:
+        raise RuntimeError(f"{what} failed with status {status}")
+
+
+def _query(symbol, args, names, flags=("served",)):
+    """One host query of the C API that answers through int out-parameters behind ``args``:
+    -> a dict of ``names``, those among ``flags`` as bool.  Raises for a status other than 0."""
+    outs = [_c_int(-1) for _ in names]
+    _check(getattr(lib(), symbol)(*args, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]), symbol)
+    return {name: bool(o.value) if name in flags else o.value for name, o in zip(names, outs)}
+
+
 SUM_KERNELS = ("rowwave", "tiled", "mfma", "plain")   # SPUTNIK_HIP_SUM_ROWWAVE / _TILED / _MFMA / _PLAIN
 
 
@@ -333,12 +346,9 @@ def sddmm_sum_route(m, k, n, nonzeros, replicas, dtype=torch.float32, planned=Fa
     scratch as large as the size queries ask: a dict of kernel (one of SUM_KERNELS), panel_width,
     panels, slab_rows and splits (include/sputnik_hip.h).  `mixed`: a (float32, half) pair whose
     half operand is `dtype`.  Host only."""
-    names = ("kernel", "panel_width", "panels", "slab_rows", "splits")
-    outs = [_c_int(-1) for _ in names]
-    _check(lib().sputnik_hip_sddmm_sum_route(
-        m, k, n, nonzeros, replicas, TYPE_CODES[dtype], int(bool(planned)), int(bool(mixed)),
-        *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]), "sputnik_hip_sddmm_sum_route")
-    route = {name: o.value for name, o in zip(names, outs)}
+    route = _query("sputnik_hip_sddmm_sum_route",
+                   (m, k, n, nonzeros, replicas, TYPE_CODES[dtype], int(bool(planned)), int(bool(mixed))),
+                   ("kernel", "panel_width", "panels", "slab_rows", "splits"))
     route["kernel"] = SUM_KERNELS[route["kernel"]]
     return route
 
@@ -352,16 +362,12 @@ def sddmm_launch_shape(m, k, n, nonzeros, replicas, dtype=torch.float32, out_dty
     of SDDMM_FAMILIES), panel_width, slab_rows, passes, accumulates, grid_x, grid_y, grid_z and
     row_blocks (include/sputnik_hip.h).  `summed`: the summed form; `mask_heads` > 0: a many-mask
     call, `nonzeros` the largest mask's count.  Host only."""
-    names = ("family", "panel_width", "slab_rows", "passes", "accumulates", "grid_x", "grid_y",
-             "grid_z", "row_blocks")
-    outs = [_c_int(-1) for _ in names]
-    _check(lib().sputnik_hip_sddmm_launch_shape(
-        m, k, n, nonzeros, replicas, TYPE_CODES[dtype], TYPE_CODES[out_dtype], int(bool(planned)),
-        int(bool(summed)), mask_heads, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
-        "sputnik_hip_sddmm_launch_shape")
-    shape = {name: o.value for name, o in zip(names, outs)}
+    shape = _query("sputnik_hip_sddmm_launch_shape",
+                   (m, k, n, nonzeros, replicas, TYPE_CODES[dtype], TYPE_CODES[out_dtype], int(bool(planned)),
+                    int(bool(summed)), mask_heads),
+                   ("family", "panel_width", "slab_rows", "passes", "accumulates", "grid_x", "grid_y", "grid_z",
+                    "row_blocks"), flags=("accumulates",))
     shape["family"] = SDDMM_FAMILIES[shape["family"]]
-    shape["accumulates"] = bool(shape["accumulates"])
     return shape
 
 
@@ -369,12 +375,8 @@ def sparse_softmax_route(m, nonzeros, replicas, dtype=torch.float32, backward=Fa
     """Kernel instance the sparse softmax launches for a call of this shape under the current
     options: a dict of lanes_per_row, base_pieces, pieces (the class), rows_per_group, depth
     and nontemporal.  Host only."""
-    names = ("lanes_per_row", "base_pieces", "pieces", "rows_per_group", "depth", "nontemporal")
-    outs = [_c_int(-1) for _ in names]
-    _check(lib().sputnik_hip_sparse_softmax_route(
-        m, nonzeros, replicas, TYPE_CODES[dtype], int(bool(backward)),
-        *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]), "sputnik_hip_sparse_softmax_route")
-    return {name: o.value for name, o in zip(names, outs)}
+    return _query("sputnik_hip_sparse_softmax_route", (m, nonzeros, replicas, TYPE_CODES[dtype], int(bool(backward))),
+                  ("lanes_per_row", "base_pieces", "pieces", "rows_per_group", "depth", "nontemporal"))
 
 
 def reload_options():
@@ -388,11 +390,6 @@ def _ptr(t):
 
 def _stream(t):
     return _c_ptr(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _check(status, what):
-    if status != 0:
-        raise RuntimeError(f"{what} failed with status {status}")
 
 
 def _require(t, dtype, name):
@@ -497,13 +494,8 @@ def csr_transpose_route(m, n, nonzeros):
     """Launches csr_transpose makes for a call of this shape: a dict of path (one of
     TRANSPOSE_PATHS), chunks, ranges, groups, parts, scan_chunks_per_group and long_rank_launch
     (include/sputnik_hip.h); -1 where a field does not apply to the path.  Host only."""
-    names = ("path", "chunks", "ranges", "groups", "parts", "scan_chunks_per_group",
-             "long_rank_launch")
-    outs = [_c_int(-1) for _ in names]
-    _check(lib().sputnik_hip_csr_transpose_route(
-        m, n, nonzeros, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
-        "sputnik_hip_csr_transpose_route")
-    route = {name: o.value for name, o in zip(names, outs)}
+    route = _query("sputnik_hip_csr_transpose_route", (m, n, nonzeros),
+                   ("path", "chunks", "ranges", "groups", "parts", "scan_chunks_per_group", "long_rank_launch"))
     route["path"] = TRANSPOSE_PATHS[route["path"]]
     return route
 
@@ -529,26 +521,15 @@ def dense_to_csr_launch_shape(masks, m, n, element_bytes):
     """The count / fill instance of the device topology build for `masks` dense matrices of
     m x n elements of that width: a dict of rows_per_wave, elements_per_lane, rows_per_workgroup
     and grid (include/sputnik_hip.h).  Host only; raises for sizes the entries reject."""
-    names = ("rows_per_wave", "elements_per_lane", "rows_per_workgroup", "grid")
-    outs = [_c_int(-1) for _ in names]
-    _check(lib().sputnik_hip_dense_to_csr_launch_shape(
-        masks, m, n, element_bytes, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
-        "sputnik_hip_dense_to_csr_launch_shape")
-    return {name: o.value for name, o in zip(names, outs)}
+    return _query("sputnik_hip_dense_to_csr_launch_shape", (masks, m, n, element_bytes),
+                  ("rows_per_wave", "elements_per_lane", "rows_per_workgroup", "grid"))
 
 
 def csr_row_order_route(masks, m, n):
     """Whether the row-order kernel serves `masks` masks of m rows and n columns, and how: a dict
     of served (bool), capacity, threads and sort_size (include/sputnik_hip.h; -1 where it does
     not serve).  Host only."""
-    names = ("served", "capacity", "threads", "sort_size")
-    outs = [_c_int(-1) for _ in names]
-    _check(lib().sputnik_hip_csr_row_order_route(
-        masks, m, n, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
-        "sputnik_hip_csr_row_order_route")
-    route = {name: o.value for name, o in zip(names, outs)}
-    route["served"] = bool(route["served"])
-    return route
+    return _query("sputnik_hip_csr_row_order_route", (masks, m, n), ("served", "capacity", "threads", "sort_size"))
 
 
 def topk_to_csr_launch_shape(m, n, element_bytes, total):
@@ -556,14 +537,8 @@ def topk_to_csr_launch_shape(m, n, element_bytes, total):
     bytes), ``total`` mode or per row: a dict of served (bool; total mode stops at the row-order
     kernel's rows), rows_per_wave, elements_per_lane, rows_per_workgroup, digit_passes and grid
     (include/sputnik_hip.h).  Host only; raises for sizes the entry rejects."""
-    names = ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "digit_passes", "grid")
-    outs = [_c_int(-1) for _ in names]
-    _check(lib().sputnik_hip_topk_to_csr_launch_shape(
-        m, n, element_bytes, int(bool(total)), *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
-        "sputnik_hip_topk_to_csr_launch_shape")
-    shape = {name: o.value for name, o in zip(names, outs)}
-    shape["served"] = bool(shape["served"])
-    return shape
+    return _query("sputnik_hip_topk_to_csr_launch_shape", (m, n, element_bytes, int(bool(total))),
+                  ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "digit_passes", "grid"))
 
 
 def random_csr_launch_shape(m, n, total):
@@ -571,15 +546,9 @@ def random_csr_launch_shape(m, n, total):
     dict of served (bool; total mode stops at the row-order kernel's rows), rows_per_wave,
     elements_per_lane, rows_per_workgroup, digit_passes, grid and launches (1 per row, 9 in
     total mode; include/sputnik_hip.h).  Host only; raises for sizes the entry rejects."""
-    names = ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "digit_passes", "grid",
-             "launches")
-    outs = [_c_int(-1) for _ in names]
-    _check(lib().sputnik_hip_random_csr_launch_shape(
-        m, n, int(bool(total)), *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
-        "sputnik_hip_random_csr_launch_shape")
-    shape = {name: o.value for name, o in zip(names, outs)}
-    shape["served"] = bool(shape["served"])
-    return shape
+    return _query("sputnik_hip_random_csr_launch_shape", (m, n, int(bool(total))),
+                  ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "digit_passes", "grid",
+                   "launches"))
 
 
 def random_csr_workspace_bytes(m, n, total):
@@ -593,15 +562,9 @@ def csr_regrow_launch_shape(m, n, score_bytes, value_bytes):
     max_n are -1 where it is not), rows_per_wave, elements_per_lane, rows_per_workgroup,
     value_digit_passes, score_digit_passes, lds_bytes, max_n and grid (include/sputnik_hip.h).
     Host only; raises for sizes the entry rejects."""
-    names = ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "value_digit_passes",
-             "score_digit_passes", "lds_bytes", "max_n", "grid")
-    outs = [_c_int(-1) for _ in names]
-    _check(lib().sputnik_hip_csr_regrow_launch_shape(
-        m, n, score_bytes, value_bytes, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
-        "sputnik_hip_csr_regrow_launch_shape")
-    shape = {name: o.value for name, o in zip(names, outs)}
-    shape["served"] = bool(shape["served"])
-    return shape
+    return _query("sputnik_hip_csr_regrow_launch_shape", (m, n, score_bytes, value_bytes),
+                  ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "value_digit_passes",
+                   "score_digit_passes", "lds_bytes", "max_n", "grid"))
 
 
 def csr_regrow_total_launch_shape(m, n, nonzeros, score_bytes, value_bytes):
@@ -611,16 +574,10 @@ def csr_regrow_total_launch_shape(m, n, nonzeros, score_bytes, value_bytes):
     rows_per_wave, elements_per_lane, rows_per_workgroup, value_digit_passes, score_digit_passes,
     lds_bytes, max_m, max_n, grid, value_rows_per_wave, value_rows_grid, flat_grid and launches
     (include/sputnik_hip.h).  Host only; raises for sizes the entry rejects."""
-    names = ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "value_digit_passes",
-             "score_digit_passes", "lds_bytes", "max_m", "max_n", "grid", "value_rows_per_wave",
-             "value_rows_grid", "flat_grid", "launches")
-    outs = [_c_int(-1) for _ in names]
-    _check(lib().sputnik_hip_csr_regrow_total_launch_shape(
-        m, n, nonzeros, score_bytes, value_bytes, *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
-        "sputnik_hip_csr_regrow_total_launch_shape")
-    shape = {name: o.value for name, o in zip(names, outs)}
-    shape["served"] = bool(shape["served"])
-    return shape
+    return _query("sputnik_hip_csr_regrow_total_launch_shape", (m, n, nonzeros, score_bytes, value_bytes),
+                  ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "value_digit_passes",
+                   "score_digit_passes", "lds_bytes", "max_m", "max_n", "grid", "value_rows_per_wave",
+                   "value_rows_grid", "flat_grid", "launches"))
 
 
 def csr_regrow_total_workspace_bytes(m, n, nonzeros):
@@ -637,15 +594,9 @@ def csr_topk_launch_shape(m, n, nonzeros, value_bytes, total):
     group_lanes, elements_per_lane, rows_per_workgroup, digit_passes, rows_grid and flat_grid
     (include/sputnik_hip.h).  The group width follows the mean row length ``nonzeros // m``.
     Host only; raises for sizes the entry rejects."""
-    names = ("served", "rows_per_wave", "group_lanes", "elements_per_lane", "rows_per_workgroup",
-             "digit_passes", "rows_grid", "flat_grid")
-    outs = [_c_int(-1) for _ in names]
-    _check(lib().sputnik_hip_csr_topk_launch_shape(
-        m, n, nonzeros, value_bytes, int(bool(total)), *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]),
-        "sputnik_hip_csr_topk_launch_shape")
-    shape = {name: o.value for name, o in zip(names, outs)}
-    shape["served"] = bool(shape["served"])
-    return shape
+    return _query("sputnik_hip_csr_topk_launch_shape", (m, n, nonzeros, value_bytes, int(bool(total))),
+                  ("served", "rows_per_wave", "group_lanes", "elements_per_lane", "rows_per_workgroup", "digit_passes",
+                   "rows_grid", "flat_grid"))
 
 
 def csr_topk_global_launch_shape(rows, nonzeros, value_bytes):
@@ -657,16 +608,11 @@ def csr_topk_global_launch_shape(rows, nonzeros, value_bytes):
     digit_launches (include/sputnik_hip.h).  Host only; raises for sizes the entry rejects."""
     if len(rows) != len(nonzeros):
         raise ValueError(f"csr_topk_global_launch_shape: {len(rows)} rows for {len(nonzeros)} nonzeros")
-    names = ("served", "digit_passes", "layers_per_launch", "elements_per_workgroup", "digit_launches")
-    outs = [_c_int(-1) for _ in names]
     layers = len(rows)
     c_rows, c_nonzeros = (_c_int * layers)(*rows), (_c_int * layers)(*nonzeros)
-    _check(lib().sputnik_hip_csr_topk_global_launch_shape(
-        layers, ctypes.cast(c_rows, _c_ptr), ctypes.cast(c_nonzeros, _c_ptr), value_bytes,
-        *[ctypes.cast(ctypes.pointer(o), _c_ptr) for o in outs]), "sputnik_hip_csr_topk_global_launch_shape")
-    shape = {name: o.value for name, o in zip(names, outs)}
-    shape["served"] = bool(shape["served"])
-    return shape
+    return _query("sputnik_hip_csr_topk_global_launch_shape",
+                  (layers, ctypes.cast(c_rows, _c_ptr), ctypes.cast(c_nonzeros, _c_ptr), value_bytes),
+                  ("served", "digit_passes", "layers_per_launch", "elements_per_workgroup", "digit_launches"))
 
 
 def csr_transpose(m, n, replicas, values, row_offsets, column_indices, out_values,

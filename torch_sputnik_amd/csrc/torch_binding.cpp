@@ -73,11 +73,14 @@ Tensor as_index(const Tensor& t, const char* name, const Tensor& like) {
 //   transpose_last2_as                   -> the type its out_type argument names.
 // Ops that take float32 only in their kernels widen half operands once with as_float
 // below; the ops whose kernels read half storage natively take as_storage.
+int type_code(at::ScalarType t) {   // -1: not a storage type of the library
+  return t == at::kFloat ? SPUTNIK_HIP_F32 : t == at::kHalf ? SPUTNIK_HIP_F16
+         : t == at::kBFloat16 ? SPUTNIK_HIP_BF16 : -1;
+}
 Tensor as_float(const Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be a GPU (HIP) tensor, got ", t.device());
-  const auto st = t.scalar_type();
-  TORCH_CHECK(st == at::kFloat || st == at::kHalf || st == at::kBFloat16, name,
-              " must be float32 (or float16 / bfloat16 storage), got ", st);
+  TORCH_CHECK(type_code(t.scalar_type()) >= 0, name, " must be float32 (or float16 / bfloat16 storage), got ",
+              t.scalar_type());
   return t.to(at::kFloat).contiguous();
 }
 
@@ -85,14 +88,9 @@ Tensor as_float(const Tensor& t, const char* name) {
 // bfloat16 storage is handed to the kernel as it is -- no widening copy.
 Tensor as_storage(const Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be a GPU (HIP) tensor, got ", t.device());
-  const auto st = t.scalar_type();
-  TORCH_CHECK(st == at::kFloat || st == at::kHalf || st == at::kBFloat16, name,
-              " must be float32, float16 or bfloat16, got ", st);
+  TORCH_CHECK(type_code(t.scalar_type()) >= 0, name, " must be float32, float16 or bfloat16, got ",
+              t.scalar_type());
   return t.contiguous();
-}
-int type_code(at::ScalarType t) {   // -1: not a storage type of the library
-  return t == at::kFloat ? SPUTNIK_HIP_F32 : t == at::kHalf ? SPUTNIK_HIP_F16
-         : t == at::kBFloat16 ? SPUTNIK_HIP_BF16 : -1;
 }
 
 struct Topology {
@@ -119,6 +117,99 @@ Topology check_topology(int64_t m, const Tensor& row_indices, const Tensor& row_
 int to_int(int64_t v, const char* name) {
   TORCH_CHECK(v >= 0 && v < (int64_t{1} << 31), name, " out of range: ", v);
   return static_cast<int>(v);
+}
+
+// ---- the argument contract of the topology ops (dense_to_csr ... csr_topk_global, below):
+// every message names the op and the argument it turns away ----
+
+// One CSR pattern with its values as the topology kernels read it: `values` [nnz] of a storage
+// type on the GPU, row_offsets [m + 1] and column_indices [nnz] 1-D int32 on its device, all
+// contiguous.
+struct CsrValues {
+  Tensor values, row_offsets, column_indices;
+  int m, nonzeros, value_bytes;
+};
+
+void check_index(const char* op, const char* name, const Tensor& t, const Tensor& values) {
+  TORCH_CHECK(t.device() == values.device(), "torch_sputnik::", op, ": ", name, " must be on ", values.device(),
+              " with values, got ", t.device());
+  TORCH_CHECK(t.scalar_type() == at::kInt && t.dim() == 1, "torch_sputnik::", op, ": ", name,
+              " must be a 1-D int32 tensor, got ", t.scalar_type(), " ", t.sizes());
+}
+
+CsrValues check_csr_values(const char* op, const Tensor& values, const Tensor& row_offsets,
+                           const Tensor& column_indices) {
+  TORCH_CHECK(values.is_cuda(), "torch_sputnik::", op, ": values must be a GPU (HIP) tensor, got ", values.device());
+  TORCH_CHECK(type_code(values.scalar_type()) >= 0, "torch_sputnik::", op,
+              ": values must be float32, float16 or bfloat16, got ", values.scalar_type());
+  check_index(op, "row_offsets", row_offsets, values);
+  check_index(op, "column_indices", column_indices, values);
+  TORCH_CHECK(row_offsets.numel() >= 1, "torch_sputnik::", op, ": row_offsets should be [m + 1], got ",
+              row_offsets.sizes());
+  TORCH_CHECK(values.dim() == 1 && values.numel() == column_indices.numel(), "torch_sputnik::", op,
+              ": values should be [nnz] like column_indices ", column_indices.sizes(), ", got ", values.sizes());
+  return {values.contiguous(), row_offsets.contiguous(), column_indices.contiguous(),
+          to_int(row_offsets.numel() - 1, "m"), to_int(values.numel(), "nnz"),
+          static_cast<int>(values.element_size())};
+}
+
+// A dense [..., m, n] operand whose rows the kernels read in place: the tensor itself where its
+// last dimension is dense, else a contiguous copy, and its row stride (0 for at most one row).
+struct DenseRows {
+  Tensor tensor;
+  int64_t row_stride;
+};
+
+DenseRows rows_in_place(const Tensor& t) {
+  Tensor rows = t.size(-1) > 1 && t.stride(-1) != 1 ? t.contiguous() : t;
+  return {rows, rows.size(-2) > 1 ? rows.stride(-2) : 0};
+}
+
+// Dense [m, n] scores of a storage type on the GPU, rows read in place; with a pattern, on its
+// device and of its m rows.
+DenseRows check_scores(const char* op, const Tensor& scores, const CsrValues* csr = nullptr) {
+  TORCH_CHECK(scores.is_cuda(), "torch_sputnik::", op, ": scores must be a GPU (HIP) tensor, got ", scores.device());
+  TORCH_CHECK(scores.dim() == 2, "torch_sputnik::", op, ": expected [m, n] scores, got ", scores.sizes());
+  TORCH_CHECK(type_code(scores.scalar_type()) >= 0, "torch_sputnik::", op,
+              ": scores must be float32, float16 or bfloat16, got ", scores.scalar_type());
+  if (csr != nullptr) {
+    TORCH_CHECK(scores.device() == csr->values.device(), "torch_sputnik::", op, ": scores must be on ",
+                csr->values.device(), " with values, got ", scores.device());
+    TORCH_CHECK(scores.size(0) == csr->m, "torch_sputnik::", op, ": row_offsets should be [m + 1] for [m, n] scores ",
+                scores.sizes(), ", got ", csr->row_offsets.sizes());
+  }
+  return rows_in_place(scores);
+}
+
+// per_row / total, the other one -1 -> which mode and its count
+struct Selection {
+  int total_mode;
+  int64_t count;
+};
+
+Selection parse_selection(const char* op, int64_t per_row, int64_t total) {
+  TORCH_CHECK((per_row >= 0) != (total >= 0), "torch_sputnik::", op, ": give exactly one of per_row / total");
+  return {total >= 0 ? 1 : 0, total >= 0 ? total : per_row};
+}
+
+void check_count(const char* op, const char* name, int64_t count, int64_t most) {
+  TORCH_CHECK(count >= 0 && count <= most, "torch_sputnik::", op, ": ", name, " = ", count, " is outside 0 .. ", most);
+}
+
+// The key of the largest finite value of a storage type: what NaN and inf grow scores count as.
+unsigned key_limit(at::ScalarType t) {
+  return t == at::kFloat ? 0x7f7fffffu : t == at::kHalf ? 0x7bffu : 0x7f7fu;
+}
+
+// A call's own workspace, on the stream's allocator: no other call can be writing it.
+Tensor workspace_like(const Tensor& like, size_t bytes) {
+  return at::empty({static_cast<int64_t>(bytes)}, like.options().dtype(at::kByte));
+}
+
+// The `served` answer of a *_launch_shape / *_route query: raise unless the kernels serve the sizes.
+void check_served(const char* op, int served, const char* query, const char* fallback) {
+  TORCH_CHECK(served, "torch_sputnik::", op, ": the sizes are beyond what the kernels serve (", query,
+              " states the limits); take ", fallback);
 }
 
 // A plan is the workspace of the matching *_workspace_bytes query after the
@@ -1958,10 +2049,8 @@ Tensor row_order(const Tensor& row_offsets_in) {
   const int masks = row_offsets.dim() == 2 ? to_int(row_offsets.size(0), "b") : 1;
   const int m = to_int(row_offsets.size(-1) - 1, "m");
   int served = 0;
-  check_status(sputnik_hip_csr_row_order_route(masks, m, 0, &served, nullptr, nullptr, nullptr),
-               "row_order");
-  TORCH_CHECK(served, "torch_sputnik::row_order: ", m, " rows per mask are beyond the kernel "
-              "(sputnik_hip_csr_row_order_route); take torch.argsort");
+  check_status(sputnik_hip_csr_row_order_route(masks, m, 0, &served, nullptr, nullptr, nullptr), "row_order");
+  check_served("row_order", served, "sputnik_hip_csr_row_order_route", "torch.argsort");
   Tensor row_indices = row_offsets.dim() == 2 ? at::empty({masks, m}, row_offsets.options())
                                               : at::empty({m}, row_offsets.options());
   check_status(sputnik_hip_csr_row_order(masks, m, 0, row_offsets.data_ptr<int>(),
@@ -1985,13 +2074,11 @@ std::vector<Tensor> dense_to_csr(const Tensor& dense_in, bool with_values) {
   const auto type = dense_in.scalar_type();
   TORCH_CHECK(!c10::isComplexType(type) && !c10::isQIntType(type), "unsupported element type ", type);
   const c10::DeviceGuard guard(dense_in.device());
-  Tensor dense = dense_in.dim() == 4 ? dense_in.select(1, 0) : dense_in;
-  if (dense.size(-1) > 1 && dense.stride(-1) != 1) dense = dense.contiguous();
+  const auto [dense, row_stride] = rows_in_place(dense_in.dim() == 4 ? dense_in.select(1, 0) : dense_in);
   const bool batched = dense.dim() == 3;
   const int masks = batched ? to_int(dense.size(0), "b") : 1;
   const int m = to_int(dense.size(-2), "m"), n = to_int(dense.size(-1), "n");
   const int64_t batch_stride = batched && masks > 1 ? dense.stride(0) : 0;
-  const int64_t row_stride = m > 1 ? dense.stride(-2) : 0;
   const int element_bytes = static_cast<int>(dense.element_size());
   const int floating = c10::isFloatingType(type) ? 1 : 0;
   const auto index_options = dense.options().dtype(at::kInt);
@@ -2028,34 +2115,25 @@ std::vector<Tensor> dense_to_csr(const Tensor& dense_in, bool with_values) {
 // stream's allocator, so no other call can be writing its histograms.
 std::vector<Tensor> topk_to_csr(const Tensor& scores_in, int64_t per_row, int64_t total,
                                 const c10::optional<Tensor>& values_from_in) {
-  TORCH_CHECK(scores_in.is_cuda(), "scores must be a GPU (HIP) tensor, got ", scores_in.device());
-  TORCH_CHECK(scores_in.dim() == 2, "expected [m, n] scores, got ", scores_in.sizes());
-  const auto type = scores_in.scalar_type();
-  TORCH_CHECK(type == at::kFloat || type == at::kHalf || type == at::kBFloat16,
-              "scores must be float32, float16 or bfloat16, got ", type);
-  TORCH_CHECK((per_row >= 0) != (total >= 0), "give exactly one of per_row / total");
-  const c10::DeviceGuard guard(scores_in.device());
-  const Tensor scores = scores_in.size(1) > 1 && scores_in.stride(1) != 1 ? scores_in.contiguous() : scores_in;
+  const char* op = "topk_to_csr";
+  const auto [scores, score_stride] = check_scores(op, scores_in);
+  const auto [total_mode, count] = parse_selection(op, per_row, total);
+  const c10::DeviceGuard guard(scores.device());
   const int m = to_int(scores.size(0), "m"), n = to_int(scores.size(1), "n");
-  const int total_mode = total >= 0 ? 1 : 0;
-  const int64_t count = total_mode ? total : per_row;
   const int element_bytes = static_cast<int>(scores.element_size());
   int served = 0;
   check_status(sputnik_hip_topk_to_csr_launch_shape(m, n, element_bytes, total_mode, &served, nullptr, nullptr,
                                                     nullptr, nullptr, nullptr),
-               "topk_to_csr");
-  TORCH_CHECK(served, "torch_sputnik::topk_to_csr: total mode over ", m, " rows is beyond the row-order "
-              "kernel (sputnik_hip_topk_to_csr_launch_shape); take topology.magnitude_prune");
-  TORCH_CHECK(count <= (total_mode ? static_cast<int64_t>(m) * n : static_cast<int64_t>(n)),
-              "torch_sputnik::topk_to_csr: ", count, " entries asked of ", total_mode ? "a matrix" : "rows",
-              " of ", total_mode ? static_cast<int64_t>(m) * n : static_cast<int64_t>(n));
-  Tensor values_from = values_from_in.has_value() ? *values_from_in : scores;
-  TORCH_CHECK(values_from.is_cuda() && values_from.device() == scores.device() &&
-                  values_from.sizes() == scores.sizes(),
-              "values_from must be a tensor of the scores' shape on their device, got ", values_from.sizes());
-  TORCH_CHECK(values_from.element_size() == 2 || values_from.element_size() == 4,
-              "values_from must have 2- or 4-byte elements, got ", values_from.scalar_type());
-  if (n > 1 && values_from.stride(1) != 1) values_from = values_from.contiguous();
+               op);
+  check_served(op, served, "sputnik_hip_topk_to_csr_launch_shape", "topology.magnitude_prune");
+  check_count(op, total_mode ? "total" : "per_row", count, total_mode ? static_cast<int64_t>(m) * n : n);
+  const Tensor& from = values_from_in.has_value() ? *values_from_in : scores;
+  TORCH_CHECK(from.is_cuda() && from.device() == scores.device() && from.sizes() == scores.sizes(),
+              "torch_sputnik::topk_to_csr: values_from must be a tensor of the scores' shape on their device, got ",
+              from.sizes(), " on ", from.device());
+  TORCH_CHECK(from.element_size() == 2 || from.element_size() == 4,
+              "torch_sputnik::topk_to_csr: values_from must have 2- or 4-byte elements, got ", from.scalar_type());
+  const auto [values_from, from_stride] = rows_in_place(from);
   const int64_t nonzeros = total_mode ? count : count * m;
   const auto index_options = scores.options().dtype(at::kInt);
   Tensor row_indices = at::empty({m}, index_options);
@@ -2063,14 +2141,13 @@ std::vector<Tensor> topk_to_csr(const Tensor& scores_in, int64_t per_row, int64_
   Tensor column_indices = at::empty({nonzeros}, index_options);
   Tensor values = at::empty({nonzeros}, values_from.options());
   const size_t ws_bytes = sputnik_hip_topk_to_csr_workspace_bytes(m, n, total_mode);
-  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, scores.options().dtype(at::kByte));
+  Tensor workspace = workspace_like(scores, ws_bytes);
   check_status(sputnik_hip_topk_to_csr(
-                   m, n, scores.data_ptr(), element_bytes, m > 1 ? scores.stride(0) : 0, total_mode, count,
-                   values_from.data_ptr(), static_cast<int>(values_from.element_size()),
-                   m > 1 ? values_from.stride(0) : 0, workspace.data_ptr(), ws_bytes, row_indices.data_ptr<int>(),
-                   row_offsets.data_ptr<int>(), column_indices.data_ptr<int>(), values.data_ptr(),
-                   current_stream(scores)),
-               "topk_to_csr");
+                   m, n, scores.data_ptr(), element_bytes, score_stride, total_mode, count, values_from.data_ptr(),
+                   static_cast<int>(values_from.element_size()), from_stride, workspace.data_ptr(), ws_bytes,
+                   row_indices.data_ptr<int>(), row_offsets.data_ptr<int>(), column_indices.data_ptr<int>(),
+                   values.data_ptr(), current_stream(scores)),
+               op);
   return {row_indices, row_offsets, column_indices, values};
 }
 
@@ -2084,25 +2161,21 @@ std::vector<Tensor> topk_to_csr(const Tensor& scores_in, int64_t per_row, int64_
 std::vector<Tensor> random_csr(int64_t m_in, int64_t n_in, int64_t per_row, int64_t total, at::ScalarType dtype,
                                double scale, c10::Device device, const c10::optional<Tensor>& rng_state,
                                int64_t key_mask) {
-  TORCH_CHECK(device.is_cuda(), "random_csr: a GPU (HIP) device is needed, got ", device);
-  TORCH_CHECK(type_code(dtype) >= 0, "random_csr: values must be float32, float16 or bfloat16, got ", dtype);
-  TORCH_CHECK((per_row >= 0) != (total >= 0), "give exactly one of per_row / total");
-  TORCH_CHECK(key_mask >= 0 && key_mask <= 0x7fffffff, "random_csr: key_mask must lie in 0 .. 0x7fffffff");
-  TORCH_CHECK(m_in >= 0 && n_in >= 0, "random_csr: negative size");
+  const char* op = "random_csr";
+  TORCH_CHECK(device.is_cuda(), "torch_sputnik::random_csr: device must be a GPU (HIP) device, got ", device);
+  TORCH_CHECK(type_code(dtype) >= 0, "torch_sputnik::random_csr: dtype must be float32, float16 or bfloat16, got ",
+              dtype);
+  const auto [total_mode, count] = parse_selection(op, per_row, total);
+  check_count(op, "key_mask", key_mask, 0x7fffffff);
   const c10::DeviceGuard guard(device);
   if (!device.has_index()) device = c10::Device(device.type(), at::cuda::current_device());
   const int m = to_int(m_in, "m"), n = to_int(n_in, "n");
-  const int total_mode = total >= 0 ? 1 : 0;
-  const int64_t count = total_mode ? total : per_row;
   int served = 0;
   check_status(sputnik_hip_random_csr_launch_shape(m, n, total_mode, &served, nullptr, nullptr, nullptr, nullptr,
                                                    nullptr, nullptr),
-               "random_csr");
-  TORCH_CHECK(served, "torch_sputnik::random_csr: total mode over ", m, " rows is beyond the row-order "
-              "kernel (sputnik_hip_random_csr_launch_shape); take topology.random_csr");
-  TORCH_CHECK(count <= (total_mode ? static_cast<int64_t>(m) * n : static_cast<int64_t>(n)),
-              "torch_sputnik::random_csr: ", count, " entries asked of ", total_mode ? "a matrix" : "rows",
-              " of ", total_mode ? static_cast<int64_t>(m) * n : static_cast<int64_t>(n));
+               op);
+  check_served(op, served, "sputnik_hip_random_csr_launch_shape", "topology.random_csr");
+  check_count(op, total_mode ? "total" : "per_row", count, total_mode ? static_cast<int64_t>(m) * n : n);
   const int64_t nonzeros = total_mode ? count : count * m;
   const auto index_options = at::TensorOptions().device(device).dtype(at::kInt);
   Tensor row_indices = at::empty({m}, index_options);
@@ -2111,13 +2184,13 @@ std::vector<Tensor> random_csr(int64_t m_in, int64_t n_in, int64_t per_row, int6
   Tensor values = at::empty({nonzeros}, index_options.dtype(dtype));
   const Drop state = draw_state(rng_state, row_offsets);
   const size_t ws_bytes = sputnik_hip_random_csr_workspace_bytes(m, n, total_mode);
-  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, index_options.dtype(at::kByte));
+  Tensor workspace = workspace_like(row_offsets, ws_bytes);
   check_status(sputnik_hip_random_csr(m, n, total_mode, count, type_code(dtype), static_cast<float>(scale),
                                       static_cast<unsigned>(key_mask), state.rng, state.rng_state_out,
                                       workspace.data_ptr(), ws_bytes, row_indices.data_ptr<int>(),
                                       row_offsets.data_ptr<int>(), column_indices.data_ptr<int>(),
                                       values.data_ptr(), current_stream(row_offsets)),
-               "random_csr");
+               op);
   return {row_indices, row_offsets, column_indices, values, state.rng_state};
 }
 
@@ -2129,53 +2202,33 @@ std::vector<Tensor> random_csr(int64_t m_in, int64_t n_in, int64_t per_row, int6
 std::vector<Tensor> csr_regrow(const Tensor& values_in, const Tensor& row_offsets_in,
                                const Tensor& column_indices_in, const Tensor& drop_counts_in,
                                const Tensor& scores_in) {
-  TORCH_CHECK(values_in.is_cuda(), "values must be a GPU (HIP) tensor, got ", values_in.device());
-  for (const Tensor* t : {&row_offsets_in, &column_indices_in, &drop_counts_in, &scores_in})
-    TORCH_CHECK(t->device() == values_in.device(), "every tensor must be on ", values_in.device(), ", got ",
-                t->device());
-  const auto floating = [](const Tensor& t) {
-    return t.scalar_type() == at::kFloat || t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16;
-  };
-  TORCH_CHECK(floating(values_in), "values must be float32, float16 or bfloat16, got ", values_in.scalar_type());
-  TORCH_CHECK(floating(scores_in), "scores must be float32, float16 or bfloat16, got ", scores_in.scalar_type());
-  for (const Tensor* t : {&row_offsets_in, &column_indices_in, &drop_counts_in})
-    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1, "row_offsets, column_indices and drop_counts "
-                "must be 1-D int32 tensors, got ", t->scalar_type(), " ", t->sizes());
-  TORCH_CHECK(scores_in.dim() == 2, "expected [m, n] scores, got ", scores_in.sizes());
-  TORCH_CHECK(row_offsets_in.numel() == scores_in.size(0) + 1 && drop_counts_in.numel() == scores_in.size(0),
-              "row_offsets should be [m + 1] and drop_counts [m] for [m, n] scores ", scores_in.sizes(),
-              ", got ", row_offsets_in.sizes(), " and ", drop_counts_in.sizes());
-  TORCH_CHECK(values_in.dim() == 1 && values_in.numel() == column_indices_in.numel(),
-              "values should be [nnz] like column_indices ", column_indices_in.sizes(), ", got ", values_in.sizes());
-  const c10::DeviceGuard guard(values_in.device());
-  const Tensor scores = scores_in.size(1) > 1 && scores_in.stride(1) != 1 ? scores_in.contiguous() : scores_in;
-  const Tensor values = values_in.contiguous(), row_offsets = row_offsets_in.contiguous();
-  const Tensor column_indices = column_indices_in.contiguous(), drop_counts = drop_counts_in.contiguous();
-  const int m = to_int(scores.size(0), "m"), n = to_int(scores.size(1), "n");
-  const int nonzeros = to_int(values.numel(), "nnz");
+  const char* op = "csr_regrow";
+  const CsrValues csr = check_csr_values(op, values_in, row_offsets_in, column_indices_in);
+  const auto [scores, score_stride] = check_scores(op, scores_in, &csr);
+  check_index(op, "drop_counts", drop_counts_in, csr.values);
+  TORCH_CHECK(drop_counts_in.numel() == csr.m, "torch_sputnik::csr_regrow: drop_counts should be [m] for [m, n] scores ",
+              scores.sizes(), ", got ", drop_counts_in.sizes());
+  const c10::DeviceGuard guard(csr.values.device());
+  const Tensor drop_counts = drop_counts_in.contiguous();
+  const int m = csr.m, n = to_int(scores.size(1), "n"), nonzeros = csr.nonzeros;
   const int score_bytes = static_cast<int>(scores.element_size());
-  const int value_bytes = static_cast<int>(values.element_size());
-  int served = 0, max_n = 0;
-  check_status(sputnik_hip_csr_regrow_launch_shape(m, n, score_bytes, value_bytes, &served, nullptr, nullptr,
-                                                   nullptr, nullptr, nullptr, nullptr, &max_n, nullptr),
-               "csr_regrow");
-  TORCH_CHECK(served, "torch_sputnik::csr_regrow: n = ", n, " is beyond the ", max_n, " columns the kernel's "
-              "LDS bitmap holds (sputnik_hip_csr_regrow_launch_shape); take topology.regrow_per_row");
-  // the key of the largest finite value of the scores' dtype
-  const unsigned key_limit = scores.scalar_type() == at::kFloat ? 0x7f7fffffu
-                             : scores.scalar_type() == at::kHalf ? 0x7bffu : 0x7f7fu;
-  Tensor out_columns = at::empty_like(column_indices);
-  Tensor out_values = at::empty_like(values);
-  Tensor source = at::empty({static_cast<int64_t>(nonzeros)}, column_indices.options().dtype(at::kLong));
+  int served = 0;
+  check_status(sputnik_hip_csr_regrow_launch_shape(m, n, score_bytes, csr.value_bytes, &served, nullptr, nullptr,
+                                                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
+               op);
+  check_served(op, served, "sputnik_hip_csr_regrow_launch_shape", "topology.regrow_per_row");
+  Tensor out_columns = at::empty_like(csr.column_indices);
+  Tensor out_values = at::empty_like(csr.values);
+  Tensor source = at::empty({static_cast<int64_t>(nonzeros)}, csr.column_indices.options().dtype(at::kLong));
   const size_t ws_bytes = sputnik_hip_csr_regrow_workspace_bytes(m, n, nonzeros);
-  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, scores.options().dtype(at::kByte));
+  Tensor workspace = workspace_like(scores, ws_bytes);
   check_status(sputnik_hip_csr_regrow(
-                   m, n, nonzeros, row_offsets.data_ptr<int>(), column_indices.data_ptr<int>(), values.data_ptr(),
-                   value_bytes, drop_counts.data_ptr<int>(), scores.data_ptr(), score_bytes,
-                   m > 1 ? scores.stride(0) : 0, key_limit, ws_bytes ? workspace.data_ptr() : nullptr, ws_bytes,
+                   m, n, nonzeros, csr.row_offsets.data_ptr<int>(), csr.column_indices.data_ptr<int>(),
+                   csr.values.data_ptr(), csr.value_bytes, drop_counts.data_ptr<int>(), scores.data_ptr(), score_bytes,
+                   score_stride, key_limit(scores.scalar_type()), ws_bytes ? workspace.data_ptr() : nullptr, ws_bytes,
                    out_columns.data_ptr<int>(), out_values.data_ptr(), source.data_ptr<int64_t>(),
-                   current_stream(values)),
-               "csr_regrow");
+                   current_stream(csr.values)),
+               op);
   return {out_columns, out_values, source};
 }
 
@@ -2187,59 +2240,34 @@ std::vector<Tensor> csr_regrow(const Tensor& values_in, const Tensor& row_offset
 // on the stream's allocator.  Scores with a dense last dimension are read in place.
 std::vector<Tensor> csr_regrow_total(const Tensor& values_in, const Tensor& row_offsets_in,
                                      const Tensor& column_indices_in, int64_t drop, const Tensor& scores_in) {
-  TORCH_CHECK(values_in.is_cuda(), "values must be a GPU (HIP) tensor, got ", values_in.device());
-  for (const Tensor* t : {&row_offsets_in, &column_indices_in, &scores_in})
-    TORCH_CHECK(t->device() == values_in.device(), "every tensor must be on ", values_in.device(), ", got ",
-                t->device());
-  const auto floating = [](const Tensor& t) {
-    return t.scalar_type() == at::kFloat || t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16;
-  };
-  TORCH_CHECK(floating(values_in), "values must be float32, float16 or bfloat16, got ", values_in.scalar_type());
-  TORCH_CHECK(floating(scores_in), "scores must be float32, float16 or bfloat16, got ", scores_in.scalar_type());
-  for (const Tensor* t : {&row_offsets_in, &column_indices_in})
-    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1, "row_offsets and column_indices must be 1-D int32 "
-                "tensors, got ", t->scalar_type(), " ", t->sizes());
-  TORCH_CHECK(scores_in.dim() == 2, "expected [m, n] scores, got ", scores_in.sizes());
-  TORCH_CHECK(row_offsets_in.numel() == scores_in.size(0) + 1, "row_offsets should be [m + 1] for [m, n] scores ",
-              scores_in.sizes(), ", got ", row_offsets_in.sizes());
-  TORCH_CHECK(values_in.dim() == 1 && values_in.numel() == column_indices_in.numel(),
-              "values should be [nnz] like column_indices ", column_indices_in.sizes(), ", got ", values_in.sizes());
-  TORCH_CHECK(drop >= 0 && drop <= values_in.numel(), "torch_sputnik::csr_regrow_total: drop = ", drop,
-              " is outside 0 .. ", values_in.numel());
-  const c10::DeviceGuard guard(values_in.device());
-  const Tensor scores = scores_in.size(1) > 1 && scores_in.stride(1) != 1 ? scores_in.contiguous() : scores_in;
-  const Tensor values = values_in.contiguous(), row_offsets = row_offsets_in.contiguous();
-  const Tensor column_indices = column_indices_in.contiguous();
-  const int m = to_int(scores.size(0), "m"), n = to_int(scores.size(1), "n");
-  const int nonzeros = to_int(values.numel(), "nnz");
+  const char* op = "csr_regrow_total";
+  const CsrValues csr = check_csr_values(op, values_in, row_offsets_in, column_indices_in);
+  const auto [scores, score_stride] = check_scores(op, scores_in, &csr);
+  check_count(op, "drop", drop, csr.nonzeros);
+  const c10::DeviceGuard guard(csr.values.device());
+  const int m = csr.m, n = to_int(scores.size(1), "n"), nonzeros = csr.nonzeros;
   const int score_bytes = static_cast<int>(scores.element_size());
-  const int value_bytes = static_cast<int>(values.element_size());
-  int served = 0, max_m = 0, max_n = 0;
-  check_status(sputnik_hip_csr_regrow_total_launch_shape(m, n, nonzeros, score_bytes, value_bytes, &served, nullptr,
-                                                         nullptr, nullptr, nullptr, nullptr, nullptr, &max_m, &max_n,
-                                                         nullptr, nullptr, nullptr, nullptr, nullptr),
-               "csr_regrow_total");
-  TORCH_CHECK(served, "torch_sputnik::csr_regrow_total: [", m, ", ", n, "] is beyond the ", max_m, " rows of the "
-              "row-order kernel or the ", max_n, " columns of the LDS bit planes "
-              "(sputnik_hip_csr_regrow_total_launch_shape); take topology.regrow_total");
-  // the key of the largest finite value of the scores' dtype
-  const unsigned key_limit = scores.scalar_type() == at::kFloat ? 0x7f7fffffu
-                             : scores.scalar_type() == at::kHalf ? 0x7bffu : 0x7f7fu;
-  const auto index_options = row_offsets.options();
+  int served = 0;
+  check_status(sputnik_hip_csr_regrow_total_launch_shape(
+                   m, n, nonzeros, score_bytes, csr.value_bytes, &served, nullptr, nullptr, nullptr, nullptr, nullptr,
+                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
+               op);
+  check_served(op, served, "sputnik_hip_csr_regrow_total_launch_shape", "topology.regrow_total");
+  const auto index_options = csr.row_offsets.options();
   Tensor out_row_indices = at::empty({m}, index_options);
   Tensor out_row_offsets = at::empty({m + 1}, index_options);
   Tensor out_columns = at::empty({nonzeros}, index_options);
-  Tensor out_values = at::empty_like(values);
+  Tensor out_values = at::empty_like(csr.values);
   Tensor source = at::empty({nonzeros}, index_options.dtype(at::kLong));
   const size_t ws_bytes = sputnik_hip_csr_regrow_total_workspace_bytes(m, n, nonzeros);
-  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, values.options().dtype(at::kByte));
+  Tensor workspace = workspace_like(csr.values, ws_bytes);
   check_status(sputnik_hip_csr_regrow_total(
-                   m, n, nonzeros, row_offsets.data_ptr<int>(), column_indices.data_ptr<int>(), values.data_ptr(),
-                   value_bytes, drop, scores.data_ptr(), score_bytes, m > 1 ? scores.stride(0) : 0, key_limit,
-                   workspace.data_ptr(), ws_bytes, out_row_indices.data_ptr<int>(), out_row_offsets.data_ptr<int>(),
-                   out_columns.data_ptr<int>(), out_values.data_ptr(), source.data_ptr<int64_t>(),
-                   current_stream(values)),
-               "csr_regrow_total");
+                   m, n, nonzeros, csr.row_offsets.data_ptr<int>(), csr.column_indices.data_ptr<int>(),
+                   csr.values.data_ptr(), csr.value_bytes, drop, scores.data_ptr(), score_bytes, score_stride,
+                   key_limit(scores.scalar_type()), workspace.data_ptr(), ws_bytes, out_row_indices.data_ptr<int>(),
+                   out_row_offsets.data_ptr<int>(), out_columns.data_ptr<int>(), out_values.data_ptr(),
+                   source.data_ptr<int64_t>(), current_stream(csr.values)),
+               op);
   return {out_row_indices, out_row_offsets, out_columns, out_values, source};
 }
 
@@ -2253,62 +2281,46 @@ std::vector<Tensor> csr_regrow_total(const Tensor& values_in, const Tensor& row_
 // min(len_r, per_row)).
 std::vector<Tensor> csr_topk(const Tensor& values_in, const Tensor& row_offsets_in,
                              const Tensor& column_indices_in, int64_t per_row, int64_t total) {
-  TORCH_CHECK(values_in.is_cuda(), "values must be a GPU (HIP) tensor, got ", values_in.device());
-  for (const Tensor* t : {&row_offsets_in, &column_indices_in}) {
-    TORCH_CHECK(t->device() == values_in.device(), "every tensor must be on ", values_in.device(), ", got ",
-                t->device());
-    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1, "row_offsets and column_indices must be 1-D "
-                "int32 tensors, got ", t->scalar_type(), " ", t->sizes());
-  }
-  const auto type = values_in.scalar_type();
-  TORCH_CHECK(type == at::kFloat || type == at::kHalf || type == at::kBFloat16,
-              "values must be float32, float16 or bfloat16, got ", type);
-  TORCH_CHECK(row_offsets_in.numel() >= 1, "row_offsets should be [m + 1], got ", row_offsets_in.sizes());
-  TORCH_CHECK(values_in.dim() == 1 && values_in.numel() == column_indices_in.numel(),
-              "values should be [nnz] like column_indices ", column_indices_in.sizes(), ", got ", values_in.sizes());
-  TORCH_CHECK((per_row >= 0) != (total >= 0), "give exactly one of per_row / total");
-  const c10::DeviceGuard guard(values_in.device());
-  const Tensor values = values_in.contiguous(), row_offsets = row_offsets_in.contiguous();
-  const Tensor column_indices = column_indices_in.contiguous();
-  const int m = to_int(row_offsets.numel() - 1, "m");
-  const int nonzeros = to_int(values.numel(), "nnz");
-  const int total_mode = total >= 0 ? 1 : 0;
+  const char* op = "csr_topk";
+  const CsrValues csr = check_csr_values(op, values_in, row_offsets_in, column_indices_in);
+  const Selection mode = parse_selection(op, per_row, total);
+  const c10::DeviceGuard guard(csr.values.device());
+  const int m = csr.m, nonzeros = csr.nonzeros, total_mode = mode.total_mode;
   const int n = std::numeric_limits<int>::max();   // (not known here: bounds per_row alone)
-  const int64_t count = total_mode ? total : std::min<int64_t>(per_row, n);
-  const int value_bytes = static_cast<int>(values.element_size());
+  const int64_t count = total_mode ? mode.count : std::min<int64_t>(mode.count, n);
   int served = 0;
-  check_status(sputnik_hip_csr_topk_launch_shape(m, n, nonzeros, value_bytes, total_mode, &served, nullptr,
+  check_status(sputnik_hip_csr_topk_launch_shape(m, n, nonzeros, csr.value_bytes, total_mode, &served, nullptr,
                                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
-               "csr_topk");
-  TORCH_CHECK(served, "torch_sputnik::csr_topk: ", m, " rows are beyond the row-order kernel "
-              "(sputnik_hip_csr_topk_launch_shape); take topology.prune_csr");
-  TORCH_CHECK(!total_mode || count <= nonzeros, "torch_sputnik::csr_topk: ", count, " entries asked of ", nonzeros);
-  const auto index_options = row_offsets.options();
+               op);
+  check_served(op, served, "sputnik_hip_csr_topk_launch_shape", "topology.prune_csr");
+  if (total_mode) check_count(op, "total", count, nonzeros);
+  const auto index_options = csr.row_offsets.options();
   Tensor out_row_indices = at::empty({m}, index_options);
   Tensor out_row_offsets = at::empty({m + 1}, index_options);
   const size_t ws_bytes = sputnik_hip_csr_topk_workspace_bytes(m, n, nonzeros, total_mode);
-  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, values.options().dtype(at::kByte));
-  const auto stream = current_stream(values);
+  Tensor workspace = workspace_like(csr.values, ws_bytes);
+  const auto stream = current_stream(csr.values);
+  const int* offsets_in = csr.row_offsets.data_ptr<int>();
   int64_t kept = count;
   if (!total_mode) {
-    check_status(sputnik_hip_csr_topk(m, n, nonzeros, row_offsets.data_ptr<int>(), nullptr, nullptr, value_bytes,
-                                      0, count, nullptr, 0, out_row_indices.data_ptr<int>(),
-                                      out_row_offsets.data_ptr<int>(), nullptr, nullptr, nullptr, 0, stream),
+    check_status(sputnik_hip_csr_topk(m, n, nonzeros, offsets_in, nullptr, nullptr, csr.value_bytes, 0, count, nullptr,
+                                      0, out_row_indices.data_ptr<int>(), out_row_offsets.data_ptr<int>(), nullptr,
+                                      nullptr, nullptr, 0, stream),
                  "csr_topk (offsets)");
     kept = out_row_offsets[m].item<int>();   // the synchronisation
     TORCH_CHECK(kept >= 0 && kept <= nonzeros, "torch_sputnik::csr_topk: row_offsets do not ascend inside 0 .. ",
                 nonzeros);
   }
   Tensor out_columns = at::empty({kept}, index_options);
-  Tensor out_values = at::empty({kept}, values.options());
+  Tensor out_values = at::empty({kept}, csr.values.options());
   Tensor source = at::empty({kept}, index_options.dtype(at::kLong));
   if (total_mode || kept > 0)
     check_status(sputnik_hip_csr_topk(
-                     m, n, nonzeros, row_offsets.data_ptr<int>(), column_indices.data_ptr<int>(), values.data_ptr(),
-                     value_bytes, total_mode, count, ws_bytes ? workspace.data_ptr() : nullptr, ws_bytes,
+                     m, n, nonzeros, offsets_in, csr.column_indices.data_ptr<int>(), csr.values.data_ptr(),
+                     csr.value_bytes, total_mode, count, ws_bytes ? workspace.data_ptr() : nullptr, ws_bytes,
                      total_mode ? out_row_indices.data_ptr<int>() : nullptr, out_row_offsets.data_ptr<int>(),
                      out_columns.data_ptr<int>(), out_values.data_ptr(), source.data_ptr<int64_t>(), kept, stream),
-                 "csr_topk");
+                 op);
   return {out_row_indices, out_row_offsets, out_columns, out_values, source};
 }
 
@@ -2320,54 +2332,40 @@ std::vector<Tensor> csr_topk(const Tensor& values_in, const Tensor& row_offsets_
 // between the select half and the fill half.
 std::vector<Tensor> csr_topk_global(at::TensorList values_in, at::TensorList row_offsets_in,
                                     at::TensorList column_indices_in, int64_t total) {
+  const char* op = "csr_topk_global";
   const size_t count_layers = values_in.size();
   TORCH_CHECK(row_offsets_in.size() == count_layers && column_indices_in.size() == count_layers,
-              "csr_topk_global: ", count_layers, " values, ", row_offsets_in.size(), " row_offsets and ",
-              column_indices_in.size(), " column_indices");
+              "torch_sputnik::csr_topk_global: ", count_layers, " values, ", row_offsets_in.size(),
+              " row_offsets and ", column_indices_in.size(), " column_indices");
   if (count_layers == 0) {
-    TORCH_CHECK(total == 0, "torch_sputnik::csr_topk_global: ", total, " entries asked of 0");
+    check_count(op, "total", total, 0);
     return {};
   }
   const int layers = to_int(static_cast<int64_t>(count_layers), "layers");
-  const auto device = values_in[0].device();
-  const auto type = values_in[0].scalar_type();
-  TORCH_CHECK(values_in[0].is_cuda(), "values must be GPU (HIP) tensors, got ", device);
-  TORCH_CHECK(type == at::kFloat || type == at::kHalf || type == at::kBFloat16,
-              "values must be float32, float16 or bfloat16, got ", type);
-  std::vector<Tensor> values, row_offsets, column_indices;
+  std::vector<CsrValues> csr;
   std::vector<int> rows(layers), nonzeros(layers);
   int64_t entries = 0;
   for (int l = 0; l < layers; ++l) {
-    for (const Tensor* t : {&values_in[l], &row_offsets_in[l], &column_indices_in[l]})
-      TORCH_CHECK(t->device() == device, "every tensor must be on ", device, ", got ", t->device(), " in layer ", l);
-    for (const Tensor* t : {&row_offsets_in[l], &column_indices_in[l]})
-      TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1, "row_offsets and column_indices must be 1-D "
-                  "int32 tensors, got ", t->scalar_type(), " ", t->sizes(), " in layer ", l);
-    TORCH_CHECK(values_in[l].scalar_type() == type, "values must be of one dtype, got ", type, " and ",
-                values_in[l].scalar_type());
-    TORCH_CHECK(row_offsets_in[l].numel() >= 1, "row_offsets should be [m + 1], got ", row_offsets_in[l].sizes());
-    TORCH_CHECK(values_in[l].dim() == 1 && values_in[l].numel() == column_indices_in[l].numel(),
-                "values should be [nnz] like column_indices ", column_indices_in[l].sizes(), ", got ",
-                values_in[l].sizes(), " in layer ", l);
-    values.push_back(values_in[l].contiguous());
-    row_offsets.push_back(row_offsets_in[l].contiguous());
-    column_indices.push_back(column_indices_in[l].contiguous());
-    rows[l] = to_int(row_offsets[l].numel() - 1, "m");
-    nonzeros[l] = to_int(values[l].numel(), "nnz");
+    csr.push_back(check_csr_values(op, values_in[l], row_offsets_in[l], column_indices_in[l]));
+    TORCH_CHECK(csr[l].values.device() == csr[0].values.device() &&
+                    csr[l].values.scalar_type() == csr[0].values.scalar_type(),
+                "torch_sputnik::csr_topk_global: values must be on one device and of one dtype, got ",
+                csr[0].values.scalar_type(), " on ", csr[0].values.device(), " and ", csr[l].values.scalar_type(),
+                " on ", csr[l].values.device(), " in layer ", l);
+    rows[l] = csr[l].m;
+    nonzeros[l] = csr[l].nonzeros;
     entries += nonzeros[l];
   }
-  const c10::DeviceGuard guard(device);
-  const int value_bytes = static_cast<int>(values[0].element_size());
+  const Tensor& like = csr[0].values;
+  const c10::DeviceGuard guard(like.device());
+  const int value_bytes = csr[0].value_bytes;
   int served = 0;
   check_status(sputnik_hip_csr_topk_global_launch_shape(layers, rows.data(), nonzeros.data(), value_bytes, &served,
                                                         nullptr, nullptr, nullptr, nullptr),
-               "csr_topk_global");
-  TORCH_CHECK(served, "torch_sputnik::csr_topk_global: a layer of more rows than the row-order kernel serves, or "
-              "more entries than int32 holds (sputnik_hip_csr_topk_global_launch_shape); take "
-              "topology.prune_csr_global");
-  TORCH_CHECK(total >= 0 && total <= entries, "torch_sputnik::csr_topk_global: ", total, " entries asked of ",
-              entries);
-  const auto index_options = row_offsets[0].options();
+               op);
+  check_served(op, served, "sputnik_hip_csr_topk_global_launch_shape", "topology.prune_csr_global");
+  check_count(op, "total", total, entries);
+  const auto index_options = csr[0].row_offsets.options();
   std::vector<Tensor> out_row_indices, out_row_offsets;
   std::vector<const int*> offsets_in(layers), columns_in(layers);
   std::vector<const void*> values_ptr(layers);
@@ -2375,16 +2373,16 @@ std::vector<Tensor> csr_topk_global(at::TensorList values_in, at::TensorList row
   for (int l = 0; l < layers; ++l) {
     out_row_offsets.push_back(at::empty({rows[l] + 1}, index_options));
     out_row_indices.push_back(at::empty({rows[l]}, index_options));
-    offsets_in[l] = row_offsets[l].data_ptr<int>();
-    columns_in[l] = column_indices[l].data_ptr<int>();
-    values_ptr[l] = values[l].data_ptr();
+    offsets_in[l] = csr[l].row_offsets.data_ptr<int>();
+    columns_in[l] = csr[l].column_indices.data_ptr<int>();
+    values_ptr[l] = csr[l].values.data_ptr();
     offsets_out[l] = out_row_offsets[l].data_ptr<int>();
     order_out[l] = out_row_indices[l].data_ptr<int>();
   }
   const size_t ws_bytes = sputnik_hip_csr_topk_global_workspace_bytes(layers, rows.data());
-  Tensor workspace = at::empty({static_cast<int64_t>(ws_bytes)}, values[0].options().dtype(at::kByte));
+  Tensor workspace = workspace_like(like, ws_bytes);
   Tensor sizes = at::empty({layers}, index_options);
-  const auto stream = current_stream(values[0]);
+  const auto stream = current_stream(like);
   check_status(sputnik_hip_csr_topk_global_select(layers, rows.data(), nonzeros.data(), offsets_in.data(),
                                                   values_ptr.data(), value_bytes, total, workspace.data_ptr(),
                                                   ws_bytes, offsets_out.data(), sizes.data_ptr<int>(), stream),
@@ -2404,7 +2402,7 @@ std::vector<Tensor> csr_topk_global(at::TensorList values_in, at::TensorList row
     capacity[l] = kept[l];
     kept_all += kept[l];
     Tensor out_columns = at::empty({capacity[l]}, index_options);
-    Tensor out_values = at::empty({capacity[l]}, values[l].options());
+    Tensor out_values = at::empty({capacity[l]}, csr[l].values.options());
     Tensor source = at::empty({capacity[l]}, index_options.dtype(at::kLong));
     columns_out[l] = out_columns.data_ptr<int>();
     values_out[l] = out_values.data_ptr();

@@ -146,6 +146,30 @@ class SparseLinear(nn.Module):
         self.column_indices = column_indices
         functional.register_static_topology(row_indices, row_offsets, column_indices)
 
+    def _install_topology(self, values, row_indices, row_offsets, column_indices, into_parameter):
+        """The end of a topology step: the new values are written INTO the ``values`` Parameter
+        (``into_parameter``; same nnz) or replace it by a new one of its ``requires_grad``; the
+        old index tensors are unregistered -- never written to -- and the new ones registered."""
+        if into_parameter:
+            self.values.copy_(values)
+            values = None
+        else:
+            values = nn.Parameter(values, requires_grad=self.values.requires_grad)
+        functional.unregister_static_topology(self.row_indices, self.row_offsets, self.column_indices)
+        self._set_topology(values, row_indices, row_offsets, column_indices)
+
+    def _grow_scores(self, grow_scores, generator):
+        """``grow_scores`` ([out, in], checked) on the layer's device, or SET's uniform random
+        scores drawn with ``generator`` on its own device"""
+        shape, device = (self.output_features, self.input_features), self.values.device
+        if grow_scores is None:
+            where = generator.device if generator is not None else device
+            return torch.rand(*shape, generator=generator, device=where).to(device)
+        if tuple(grow_scores.shape) != shape:
+            raise ValueError(f"update_topology: grow_scores should be [{shape[0]}, {shape[1]}], got "
+                             f"{tuple(grow_scores.shape)}")
+        return grow_scores.detach().to(device)
+
     @torch.no_grad()
     def update_topology(self, drop_fraction, grow_scores=None, generator=None, per_row=False):
         """One drop-and-grow step of dynamic sparse training (SET, RigL) with an unchanged
@@ -200,47 +224,28 @@ class SparseLinear(nn.Module):
             raise ValueError(f"update_topology: drop_fraction {drop_fraction} is outside 0 .. 1")
         if d == 0:
             return torch.arange(nnz, dtype=torch.int64, device=device)
-        out_f, in_f = self.output_features, self.input_features
-        if grow_scores is None:
-            where = generator.device if generator is not None else device
-            scores = torch.rand(out_f, in_f, generator=generator, device=where).to(device)
-        else:
-            if tuple(grow_scores.shape) != (out_f, in_f):
-                raise ValueError(f"update_topology: grow_scores should be [{out_f}, {in_f}], got "
-                                 f"{tuple(grow_scores.shape)}")
-            scores = grow_scores.detach().to(device)
         row_indices, row_offsets, column_indices, new_values, source = topology.regrow_total(
-            values, self.row_offsets, self.column_indices, d, scores)
-        self.values.copy_(new_values)
-        functional.unregister_static_topology(self.row_indices, self.row_offsets, self.column_indices)
-        self._set_topology(None, row_indices, row_offsets, column_indices)
+            values, self.row_offsets, self.column_indices, d, self._grow_scores(grow_scores, generator))
+        self._install_topology(new_values, row_indices, row_offsets, column_indices, into_parameter=True)
         return source
 
     def _update_topology_per_row(self, drop_fraction, grow_scores, generator):
         values = self.values.detach()
-        nnz = values.numel()
-        device = values.device
-        out_f, in_f = self.output_features, self.input_features
         if not 0.0 <= drop_fraction <= 1.0:
             raise ValueError(f"update_topology: drop_fraction {drop_fraction} is outside 0 .. 1")
-        if grow_scores is not None and tuple(grow_scores.shape) != (out_f, in_f):
-            raise ValueError(f"update_topology: grow_scores should be [{out_f}, {in_f}], got "
-                             f"{tuple(grow_scores.shape)}")
+        # (given scores are checked before anything returns; random ones are drawn only for a step)
+        scores = None if grow_scores is None else self._grow_scores(grow_scores, generator)
         # len_r <= in_features is known on the host; the lengths themselves are not read back
-        if math.floor(float(in_f) * drop_fraction) == 0:
-            return torch.arange(nnz, dtype=torch.int64, device=device)
+        if math.floor(float(self.input_features) * drop_fraction) == 0:
+            return torch.arange(values.numel(), dtype=torch.int64, device=values.device)
+        if scores is None:
+            scores = self._grow_scores(None, generator)
         lengths = self.row_offsets[1:] - self.row_offsets[:-1]
         drop_counts = torch.floor(lengths.to(torch.float64) * drop_fraction).to(torch.int32)
-        if grow_scores is None:
-            where = generator.device if generator is not None else device
-            scores = torch.rand(out_f, in_f, generator=generator, device=where).to(device)
-        else:
-            scores = grow_scores.detach().to(device)
         column_indices, new_values, source = topology.regrow_per_row(
             values, self.row_offsets, self.column_indices, drop_counts, scores)
-        self.values.copy_(new_values)
-        functional.unregister_static_topology(self.row_indices, self.row_offsets, self.column_indices)
-        self._set_topology(None, self.row_indices.clone(), self.row_offsets.clone(), column_indices)
+        self._install_topology(new_values, self.row_indices.clone(), self.row_offsets.clone(), column_indices,
+                               into_parameter=True)
         return source
 
     @torch.no_grad()
@@ -267,17 +272,8 @@ class SparseLinear(nn.Module):
             source = layer.prune_to(density=topology.gradual_density(step, t0, t1, d_i, d_f))
             topology.remap_optimizer_state(optimizer, old, layer.values, source)
         """
-        if (density is None) == (nonzeros is None):
-            raise ValueError("prune_to: give exactly one of density / nonzeros")
         out_f, in_f = self.output_features, self.input_features
-        most = in_f if per_row else out_f * in_f
-        if density is not None:
-            if not 0.0 <= density <= 1.0:
-                raise ValueError(f"prune_to: density {density} is outside 0 .. 1")
-            nonzeros = round(density * most)
-        count = int(nonzeros)
-        if not 0 <= count <= most:
-            raise ValueError(f"prune_to: {count} entries asked of {most}")
+        count = topology._count_of("prune_to", density, nonzeros, in_f if per_row else out_f * in_f)
         old = self.values
         nnz = old.numel()
         if not per_row and count >= nnz:
@@ -285,9 +281,7 @@ class SparseLinear(nn.Module):
         row_indices, row_offsets, column_indices, values, source = topology.prune_csr(
             old.detach(), self.row_offsets, self.column_indices, in_f,
             per_row=count if per_row else None, total=None if per_row else count)
-        functional.unregister_static_topology(self.row_indices, self.row_offsets, self.column_indices)
-        self._set_topology(nn.Parameter(values, requires_grad=old.requires_grad), row_indices, row_offsets,
-                           column_indices)
+        self._install_topology(values, row_indices, row_offsets, column_indices, into_parameter=False)
         return source
 
     def forward(self, x):

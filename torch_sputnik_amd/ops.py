@@ -325,7 +325,69 @@ def row_order(row_offsets):
     return _ops.row_order(row_offsets)
 
 
+# ---- the argument contract of the topology ops below (topology.py checks with the same
+# functions): a ValueError names the op and the argument, the binding never sees such a call ----
 _TOPK_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _resolve_count(op, per_row, total, per_row_most, total_most):
+    """ValueError unless exactly one of per_row / total is given and lies within 0 .. its bound
+    (``None``: unbounded).  -> the count."""
+    if (per_row is None) == (total is None):
+        raise ValueError(f"{op}: give exactly one of per_row / total")
+    name, count, most = ("total", int(total), total_most) if per_row is None else ("per_row", int(per_row), per_row_most)
+    if count < 0 or (most is not None and count > most):
+        raise ValueError(f"{op}: {name} = {count} is outside 0 .. {'n' if most is None else most}")
+    return count
+
+
+def _binding_counts(per_row, count):
+    """(per_row, total) as the binding takes them: the count and -1 for the other one"""
+    return (-1, count) if per_row is None else (count, -1)
+
+
+def _device_floats(op, fallback, **tensors):
+    """The guard of a device op, after its other checks: ValueError unless every tensor given by
+    name is float32 / float16 / bfloat16, RuntimeError unless the first one is on a GPU."""
+    for name, t in tensors.items():
+        if t.dtype not in _TOPK_DTYPES:
+            raise ValueError(f"{op}: {name} must be float32, float16 or bfloat16, got {t.dtype}")
+    if not next(iter(tensors.values())).is_cuda:
+        raise RuntimeError(f"{op}: GPU tensors only ({fallback} serves CPU tensors)")
+
+
+def _check_csr_pattern(op, values, row_offsets, column_indices, scores=None, drop_counts=None):
+    """ValueError unless values [nnz], row_offsets [m + 1] and column_indices [nnz] (int32) are
+    one CSR pattern with its values on one device; with dense ``scores`` they are [m, n] on that
+    device, and ``drop_counts`` is int32 [m] there.  Dtypes of values and scores are the caller's
+    matter."""
+    if scores is not None and scores.dim() != 2:
+        raise ValueError(f"{op}: expected [m, n] scores, got {tuple(scores.shape)}")
+    if values.dim() != 1:
+        raise ValueError(f"{op}: values should be [nnz], got {tuple(values.shape)}")
+    indices = [("row_offsets", row_offsets, None if scores is None else scores.size(0) + 1),
+               ("column_indices", column_indices, values.numel())]
+    if drop_counts is not None:
+        indices.append(("drop_counts", drop_counts, scores.size(0)))
+    for name, t, size in indices:
+        if t.dtype != torch.int32 or t.dim() != 1 or (t.numel() < 1 if size is None else t.numel() != size):
+            raise ValueError(f"{op}: {name} should be int32 [{'m + 1' if size is None else size}], got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    for name, t in [entry[:2] for entry in indices] + [("scores", scores)] * (scores is not None):
+        if t.device != values.device:
+            raise ValueError(f"{op}: {name} is on {t.device}, values on {values.device}")
+
+
+def _check_topk_arguments(op, scores, per_row, total, values_from):
+    """ValueError unless scores are [m, n], exactly one of per_row / total is a count in range and
+    ``values_from`` (if any) has the scores' shape and device.  -> the count."""
+    if scores.dim() != 2:
+        raise ValueError(f"{op}: expected [m, n] scores, got {tuple(scores.shape)}")
+    count = _resolve_count(op, per_row, total, scores.size(1), scores.numel())
+    if values_from is not None and (values_from.shape != scores.shape or values_from.device != scores.device):
+        raise ValueError(f"{op}: values_from must have the scores' shape and device, got "
+                         f"{tuple(values_from.shape)} on {values_from.device}")
+    return count
 
 
 def topk_to_csr(scores, per_row=None, total=None, values_from=None):
@@ -338,24 +400,11 @@ def topk_to_csr(scores, per_row=None, total=None, values_from=None):
     ``values_from`` (same shape, any 2- or 4-byte dtype; default: the scores) at the kept
     positions, bit for bit.  No host synchronisation.  Raises for CPU tensors and for shapes
     ``capi.topk_to_csr_launch_shape`` does not serve (total mode above 16384 rows)."""
-    if (per_row is None) == (total is None):
-        raise ValueError("topk_to_csr: give exactly one of per_row / total")
-    if scores.dim() != 2:
-        raise ValueError(f"topk_to_csr: expected [m, n] scores, got {tuple(scores.shape)}")
-    if scores.dtype not in _TOPK_DTYPES:
-        raise ValueError(f"topk_to_csr: scores must be float32, float16 or bfloat16, got {scores.dtype}")
-    m, n = scores.shape
-    count, most = (int(total), m * n) if per_row is None else (int(per_row), n)
-    if not 0 <= count <= most:
-        raise ValueError(f"topk_to_csr: {'total' if per_row is None else 'per_row'} = {count} is outside 0 .. {most}")
-    if values_from is not None and (values_from.shape != scores.shape or values_from.device != scores.device
-                                    or values_from.element_size() not in (2, 4)):
-        raise ValueError("topk_to_csr: values_from must have the scores' shape and device and 2- or 4-byte "
-                         f"elements, got {tuple(values_from.shape)} {values_from.dtype} on {values_from.device}")
-    if not scores.is_cuda:
-        raise RuntimeError("topk_to_csr: GPU tensors only (topology.magnitude_prune serves CPU tensors)")
-    return tuple(_ops.topk_to_csr(scores, -1 if per_row is None else count, -1 if total is None else count,
-                                  values_from))
+    count = _check_topk_arguments("topk_to_csr", scores, per_row, total, values_from)
+    if values_from is not None and values_from.element_size() not in (2, 4):
+        raise ValueError(f"topk_to_csr: values_from must have 2- or 4-byte elements, got {values_from.dtype}")
+    _device_floats("topk_to_csr", "topology.magnitude_prune", scores=scores)
+    return tuple(_ops.topk_to_csr(scores, *_binding_counts(per_row, count), values_from))
 
 
 RANDOM_KEY_MASK = 0x7fffffff
@@ -372,16 +421,12 @@ def random_value_scale(bound):
 
 def check_random_arguments(m, n, per_row, total, dtype, key_mask):
     """ValueError unless the arguments describe a random ``m x n`` topology; -> the count."""
-    if (per_row is None) == (total is None):
-        raise ValueError("random_csr: give exactly one of per_row / total")
     m, n = int(m), int(n)
     if m < 0 or n < 0:
         raise ValueError(f"random_csr: expected sizes >= 0, got {m} x {n}")
     if dtype not in _TOPK_DTYPES:
-        raise ValueError(f"random_csr: values must be float32, float16 or bfloat16, got {dtype}")
-    count, most = (int(total), m * n) if per_row is None else (int(per_row), n)
-    if not 0 <= count <= most:
-        raise ValueError(f"random_csr: {'total' if per_row is None else 'per_row'} = {count} is outside 0 .. {most}")
+        raise ValueError(f"random_csr: dtype must be float32, float16 or bfloat16, got {dtype}")
+    count = _resolve_count("random_csr", per_row, total, n, m * n)
     if not 0 <= int(key_mask) <= RANDOM_KEY_MASK:
         raise ValueError(f"random_csr: key_mask {key_mask} is outside 0 .. 0x7fffffff")
     return count
@@ -410,27 +455,15 @@ def random_csr(m, n, per_row=None, total=None, dtype=torch.float32, bound=1.0, d
         raise ValueError("random_csr: rng_state must be an int64 [2] tensor {seed, offset}")
     if rng_state is not None:
         rng_state = rng_state.to(device).contiguous()
-    return tuple(_ops.random_csr(int(m), int(n), -1 if per_row is None else count, -1 if total is None else count,
-                                 dtype, random_value_scale(bound), device, rng_state, int(key_mask)))
+    return tuple(_ops.random_csr(int(m), int(n), *_binding_counts(per_row, count), dtype, random_value_scale(bound),
+                                 device, rng_state, int(key_mask)))
 
 
 def check_regrow_arguments(values, row_offsets, column_indices, drop_counts, scores):
     """ValueError unless the five tensors are one CSR pattern with its values, drop counts and
     dense scores (shapes, int32 indices, one device).  Dtypes of values and scores are the
     caller's matter."""
-    if scores.dim() != 2:
-        raise ValueError(f"csr_regrow: expected [m, n] scores, got {tuple(scores.shape)}")
-    m = scores.size(0)
-    for name, t, size in (("row_offsets", row_offsets, m + 1), ("drop_counts", drop_counts, m),
-                          ("column_indices", column_indices, values.numel())):
-        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != size:
-            raise ValueError(f"csr_regrow: {name} should be int32 [{size}], got {t.dtype} {tuple(t.shape)}")
-    if values.dim() != 1:
-        raise ValueError(f"csr_regrow: values should be [nnz], got {tuple(values.shape)}")
-    for name, t in (("row_offsets", row_offsets), ("column_indices", column_indices),
-                    ("drop_counts", drop_counts), ("scores", scores)):
-        if t.device != values.device:
-            raise ValueError(f"csr_regrow: {name} is on {t.device}, values on {values.device}")
+    _check_csr_pattern("csr_regrow", values, row_offsets, column_indices, scores, drop_counts)
 
 
 def csr_regrow(values, row_offsets, column_indices, drop_counts, scores):
@@ -448,11 +481,7 @@ def csr_regrow(values, row_offsets, column_indices, drop_counts, scores):
     host synchronisation.  Raises for CPU tensors and for ``n`` beyond
     ``capi.csr_regrow_launch_shape(...)["max_n"]``."""
     check_regrow_arguments(values, row_offsets, column_indices, drop_counts, scores)
-    for name, t in (("values", values), ("scores", scores)):
-        if t.dtype not in _TOPK_DTYPES:
-            raise ValueError(f"csr_regrow: {name} must be float32, float16 or bfloat16, got {t.dtype}")
-    if not values.is_cuda:
-        raise RuntimeError("csr_regrow: GPU tensors only (topology.regrow_per_row serves CPU tensors)")
+    _device_floats("csr_regrow", "topology.regrow_per_row", values=values, scores=scores)
     return tuple(_ops.csr_regrow(values, row_offsets, column_indices, drop_counts, scores))
 
 
@@ -460,17 +489,7 @@ def check_regrow_total_arguments(values, row_offsets, column_indices, drop, scor
     """ValueError unless the four tensors are one CSR pattern with its values and dense scores
     (shapes, int32 indices, one device) and ``drop`` is a count within 0 .. nnz.  -> the count.
     Dtypes of values and scores are the caller's matter."""
-    if scores.dim() != 2:
-        raise ValueError(f"csr_regrow_total: expected [m, n] scores, got {tuple(scores.shape)}")
-    if values.dim() != 1:
-        raise ValueError(f"csr_regrow_total: values should be [nnz], got {tuple(values.shape)}")
-    for name, t, size in (("row_offsets", row_offsets, scores.size(0) + 1),
-                          ("column_indices", column_indices, values.numel())):
-        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != size:
-            raise ValueError(f"csr_regrow_total: {name} should be int32 [{size}], got {t.dtype} {tuple(t.shape)}")
-    for name, t in (("row_offsets", row_offsets), ("column_indices", column_indices), ("scores", scores)):
-        if t.device != values.device:
-            raise ValueError(f"csr_regrow_total: {name} is on {t.device}, values on {values.device}")
+    _check_csr_pattern("csr_regrow_total", values, row_offsets, column_indices, scores)
     count = int(drop)
     if not 0 <= count <= values.numel():
         raise ValueError(f"csr_regrow_total: drop = {count} is outside 0 .. {values.numel()}")
@@ -492,11 +511,7 @@ def csr_regrow_total(values, row_offsets, column_indices, drop, scores):
     launches, no host synchronisation: the call can be captured in a graph.  Raises for CPU
     tensors and beyond the rows and columns ``capi.csr_regrow_total_launch_shape`` serves."""
     count = check_regrow_total_arguments(values, row_offsets, column_indices, drop, scores)
-    for name, t in (("values", values), ("scores", scores)):
-        if t.dtype not in _TOPK_DTYPES:
-            raise ValueError(f"csr_regrow_total: {name} must be float32, float16 or bfloat16, got {t.dtype}")
-    if not values.is_cuda:
-        raise RuntimeError("csr_regrow_total: GPU tensors only (topology.regrow_total serves CPU tensors)")
+    _device_floats("csr_regrow_total", "topology.regrow_total", values=values, scores=scores)
     return tuple(_ops.csr_regrow_total(values, row_offsets, column_indices, count, scores))
 
 
@@ -505,24 +520,8 @@ def check_csr_topk_arguments(values, row_offsets, column_indices, per_row, total
     indices, one device) and exactly one of per_row / total is a count in range (``total`` at
     most nnz, ``per_row`` at least 0).  -> the count.  The dtype of values is the caller's
     matter."""
-    if (per_row is None) == (total is None):
-        raise ValueError("csr_topk: give exactly one of per_row / total")
-    if values.dim() != 1:
-        raise ValueError(f"csr_topk: values should be [nnz], got {tuple(values.shape)}")
-    if row_offsets.dtype != torch.int32 or row_offsets.dim() != 1 or row_offsets.numel() < 1:
-        raise ValueError(f"csr_topk: row_offsets should be int32 [m + 1], got {row_offsets.dtype} "
-                         f"{tuple(row_offsets.shape)}")
-    if column_indices.dtype != torch.int32 or column_indices.dim() != 1 or column_indices.numel() != values.numel():
-        raise ValueError(f"csr_topk: column_indices should be int32 [{values.numel()}], got "
-                         f"{column_indices.dtype} {tuple(column_indices.shape)}")
-    for name, t in (("row_offsets", row_offsets), ("column_indices", column_indices)):
-        if t.device != values.device:
-            raise ValueError(f"csr_topk: {name} is on {t.device}, values on {values.device}")
-    count = int(total if per_row is None else per_row)
-    if count < 0 or (per_row is None and count > values.numel()):
-        raise ValueError(f"csr_topk: {'total' if per_row is None else 'per_row'} = {count} is outside 0 .. "
-                         f"{values.numel() if per_row is None else 'n'}")
-    return count
+    _check_csr_pattern("csr_topk", values, row_offsets, column_indices)
+    return _resolve_count("csr_topk", per_row, total, None, values.numel())
 
 
 def csr_topk(values, row_offsets, column_indices, per_row=None, total=None):
@@ -537,12 +536,8 @@ def csr_topk(values, row_offsets, column_indices, per_row=None, total=None):
     arrays.  ``total`` never synchronises; ``per_row`` reads the new size back once.  Raises for
     CPU tensors and for more rows than ``capi.csr_topk_launch_shape`` serves (16384)."""
     count = check_csr_topk_arguments(values, row_offsets, column_indices, per_row, total)
-    if values.dtype not in _TOPK_DTYPES:
-        raise ValueError(f"csr_topk: values must be float32, float16 or bfloat16, got {values.dtype}")
-    if not values.is_cuda:
-        raise RuntimeError("csr_topk: GPU tensors only (topology.prune_csr serves CPU tensors)")
-    return tuple(_ops.csr_topk(values, row_offsets, column_indices, -1 if per_row is None else count,
-                               -1 if total is None else count))
+    _device_floats("csr_topk", "topology.prune_csr", values=values)
+    return tuple(_ops.csr_topk(values, row_offsets, column_indices, *_binding_counts(per_row, count)))
 
 
 def check_csr_topk_global_arguments(values, row_offsets, column_indices, total):
@@ -557,14 +552,10 @@ def check_csr_topk_global_arguments(values, row_offsets, column_indices, total):
     if total is None:
         raise ValueError("csr_topk_global: total is missing")
     for v, ro, ci in zip(values, row_offsets, column_indices):
-        check_csr_topk_arguments(v, ro, ci, None, 0)
+        _check_csr_pattern("csr_topk_global", v, ro, ci)
         if v.device != values[0].device:
             raise ValueError(f"csr_topk_global: values are on {values[0].device} and on {v.device}")
-    entries = sum(v.numel() for v in values)
-    count = int(total)
-    if not 0 <= count <= entries:
-        raise ValueError(f"csr_topk_global: total = {count} is outside 0 .. {entries}")
-    return count
+    return _resolve_count("csr_topk_global", None, total, None, sum(v.numel() for v in values))
 
 
 def csr_topk_global(values, row_offsets, column_indices, total):
@@ -583,11 +574,9 @@ def csr_topk_global(values, row_offsets, column_indices, total):
     if not values:
         return []
     for v in values:
-        if v.dtype not in _TOPK_DTYPES or v.dtype != values[0].dtype:
-            raise ValueError(f"csr_topk_global: values must be float32, float16 or bfloat16 and of one dtype, got "
-                             f"{values[0].dtype} and {v.dtype}")
-    if not values[0].is_cuda:
-        raise RuntimeError("csr_topk_global: GPU tensors only (topology.prune_csr_global serves CPU tensors)")
+        if v.dtype != values[0].dtype:
+            raise ValueError(f"csr_topk_global: values must be of one dtype, got {values[0].dtype} and {v.dtype}")
+    _device_floats("csr_topk_global", "topology.prune_csr_global", values=values[0])
     flat = _ops.csr_topk_global(values, row_offsets, column_indices, count)
     return [tuple(flat[5 * l:5 * l + 5]) for l in range(len(values))]
 

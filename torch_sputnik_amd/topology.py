@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import capi, ops
+from .ops import _TOPK_DTYPES
 
 _device_build = True
 
@@ -29,19 +30,28 @@ def enable_device_build(enabled=True):
     return _device_build
 
 
+def _served(where, query, *args):
+    """Whether the device kernels take a call: the device build is on, ``where`` (a tensor or a
+    device) is a GPU and the host query ``capi.<query>(*args)`` serves the sizes -- its "served"
+    field, or, for a query without one, that it does not raise (it raises RuntimeError for sizes
+    beyond int32).  The dtypes are the caller's matter."""
+    device = where.device if torch.is_tensor(where) else where
+    if not (_device_build and device.type == "cuda"):
+        return False
+    try:
+        return getattr(capi, query)(*args).get("served", True)
+    except RuntimeError:
+        return False
+
+
 def _row_order_served(masks, rows):
     """(the kernel's limit is on the rows alone; its 64-bit keys hold every length)"""
     return rows >= 0 and capi.csr_row_order_route(masks, rows, 0)["served"]
 
 
 def _build_served(dense, masks, m, n):
-    if not (_device_build and dense.is_cuda and dense.dtype in _BUILD_DTYPES):
-        return False
-    try:
-        capi.dense_to_csr_launch_shape(masks, m, n, dense.element_size())
-    except RuntimeError:   # (more than INT_MAX elements per mask, or workgroups)
-        return False
-    return _row_order_served(masks, m)
+    return (dense.dtype in _BUILD_DTYPES and _served(dense, "dense_to_csr_launch_shape", masks, m, n, dense.element_size())
+            and _row_order_served(masks, m))
 
 
 def diffsort(row_offsets):
@@ -82,9 +92,6 @@ def dense_to_sparse(matrix):
     return values, diffsort(row_offsets), row_offsets, column_indices
 
 
-_TOPK_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
-
-
 def magnitude_keys(x):
     """The selection key of every element of a float32 / float16 / bfloat16 tensor, int64: its
     bit pattern with the sign bit cleared, read as an unsigned integer.  Ranking by key is
@@ -105,16 +112,47 @@ def _take_bits(tensor, flat):
     return bits[flat].view(tensor.dtype)
 
 
-def _topk_served(scores, values_from, total):
-    if not (_device_build and scores.is_cuda and scores.dtype in _TOPK_DTYPES):
-        return False
-    if values_from is not None and values_from.element_size() not in (2, 4):
-        return False
-    try:
-        return capi.topk_to_csr_launch_shape(scores.size(0), scores.size(1), scores.element_size(),
-                                             total)["served"]
-    except RuntimeError:   # (more than INT_MAX elements)
-        return False
+def _rankable(x):
+    """``x`` itself where it is float32 / float16 / bfloat16, else ``x.float()``: what is ranked
+    in its place"""
+    return x if x.dtype in _TOPK_DTYPES else x.float()
+
+
+def _entry_rows(row_offsets, nnz):
+    """int64 [nnz]: the row of every entry of a CSR pattern (nnz is given: nothing is read back)"""
+    lengths = (row_offsets[1:] - row_offsets[:-1]).to(torch.int64)
+    rows = torch.arange(lengths.numel(), dtype=torch.int64, device=row_offsets.device)
+    return torch.repeat_interleave(rows, lengths, output_size=nnz)
+
+
+def _offsets_of(rows, m):
+    """int32 row_offsets [m + 1] of a pattern of ``m`` rows whose entries lie in ``rows``"""
+    row_offsets = torch.zeros(m + 1, dtype=torch.int32, device=rows.device)
+    row_offsets[1:] = torch.cumsum(torch.bincount(rows, minlength=m), 0)
+    return row_offsets
+
+
+def _csr_from_source(values, rows, m, column_indices, source):
+    """(row_indices, row_offsets, column_indices, values, source) of the entries ``source``
+    (old entry indices, ascending) of a pattern of ``m`` rows whose entries lie in ``rows``"""
+    row_offsets = _offsets_of(rows[source], m)
+    return diffsort(row_offsets), row_offsets, column_indices[source], _take_bits(values, source), source
+
+
+def _count_of(op, density, nonzeros, most):
+    """The entries a ``density`` / ``nonzeros`` pair asks of ``most`` positions:
+    ``round(density * most)``, or ``nonzeros`` itself.  ValueError unless exactly one of the two
+    is given, the density lies within 0 .. 1 and the count within 0 .. most."""
+    if (density is None) == (nonzeros is None):
+        raise ValueError(f"{op}: give exactly one of density / nonzeros")
+    if density is not None:
+        if not 0.0 <= density <= 1.0:
+            raise ValueError(f"{op}: density {density} is outside 0 .. 1")
+        nonzeros = round(density * most)
+    count = int(nonzeros)
+    if not 0 <= count <= most:
+        raise ValueError(f"{op}: nonzeros = {count} is outside 0 .. {most}")
+    return count
 
 
 def topk_to_csr(scores, per_row=None, total=None, values_from=None):
@@ -123,23 +161,11 @@ def topk_to_csr(scores, per_row=None, total=None, values_from=None):
     to the lowest column (per row) or flat index (total).  Scores of another dtype are ranked
     as ``.float()``.  -> (row_indices, row_offsets, column_indices, values), the same integers
     and value bits on both paths."""
-    if (per_row is None) == (total is None):
-        raise ValueError("topk_to_csr: give exactly one of per_row / total")
-    if scores.dim() != 2:
-        raise ValueError(f"topk_to_csr: expected [m, n] scores, got {tuple(scores.shape)}")
-    m, n = scores.shape
-    count, most = (int(total), m * n) if per_row is None else (int(per_row), n)
-    if not 0 <= count <= most:
-        raise ValueError(f"topk_to_csr: {'total' if per_row is None else 'per_row'} = {count} is outside 0 .. {most}")
-    if values_from is None:
-        values_from = scores
-    elif values_from.shape != scores.shape or values_from.device != scores.device:
-        raise ValueError("topk_to_csr: values_from must have the scores' shape and device, got "
-                         f"{tuple(values_from.shape)} on {values_from.device}")
-    scores, values_from = scores.detach(), values_from.detach()
-    if scores.dtype not in _TOPK_DTYPES:
-        scores = scores.float()
-    if _topk_served(scores, values_from, per_row is None):
+    count = ops._check_topk_arguments("topk_to_csr", scores, per_row, total, values_from)
+    values_from = (scores if values_from is None else values_from).detach()
+    scores = _rankable(scores.detach())
+    if values_from.element_size() in (2, 4) and _served(scores, "topk_to_csr_launch_shape", scores.size(0),
+                                                         scores.size(1), scores.element_size(), per_row is None):
         return ops.topk_to_csr(scores, per_row, total, values_from)
     return _topk_to_csr_torch(scores, None if per_row is None else count, None if total is None else count,
                               values_from)
@@ -161,8 +187,7 @@ def _topk_to_csr_torch(scores, per_row, total, values_from):
     kept = torch.argsort(keys.reshape(-1), descending=True, stable=True)[:count]
     flat = torch.sort(kept).values
     rows = torch.div(flat, max(n, 1), rounding_mode="floor")
-    row_offsets = torch.zeros(m + 1, **int32)
-    row_offsets[1:] = torch.cumsum(torch.bincount(rows, minlength=m), 0)
+    row_offsets = _offsets_of(rows, m)
     return (diffsort(row_offsets), row_offsets, (flat - rows * n).to(torch.int32),
             _take_bits(values_from, flat))
 
@@ -216,15 +241,6 @@ def _random_csr_torch(m, n, per_row, total, dtype, scale, seed, offset, device, 
     return _topk_to_csr_torch(scores, per_row, total, values)
 
 
-def _random_served(m, n, device, total):
-    if not (_device_build and device.type == "cuda"):
-        return False
-    try:
-        return capi.random_csr_launch_shape(m, n, total)["served"]
-    except RuntimeError:   # (more than INT_MAX positions)
-        return False
-
-
 def _draw_philox_state(device):
     """(seed, offset) for a call without an ``rng_state``: 4 of the device's default generator
     on a GPU, as the device path draws them; a seed from torch's CPU generator otherwise"""
@@ -262,25 +278,16 @@ def random_csr(m, n, density=None, nonzeros=None, per_row=False, dtype=torch.flo
     return the same integers and value bits.  Without one a GPU call draws 4 from the device's
     default generator (``torch.manual_seed`` makes runs repeat) and a CPU call a seed from
     torch's CPU generator with offset 0.  ``return_rng_state``: the state used is appended."""
-    if (density is None) == (nonzeros is None):
-        raise ValueError("random_csr: give exactly one of density / nonzeros")
     m, n = int(m), int(n)
     if m < 0 or n < 0:
         raise ValueError(f"random_csr: expected sizes >= 0, got {m} x {n}")
-    most = n if per_row else m * n
-    if density is not None:
-        if not 0.0 <= density <= 1.0:
-            raise ValueError(f"random_csr: density {density} is outside 0 .. 1")
-        nonzeros = round(density * most)
-    count = int(nonzeros)
-    if not 0 <= count <= most:
-        raise ValueError(f"random_csr: {count} entries asked of {most}")
+    count = _count_of("random_csr", density, nonzeros, n if per_row else m * n)
     per_row_count, total = (count, None) if per_row else (None, count)
     ops.check_random_arguments(m, n, per_row_count, total, dtype, ops.RANDOM_KEY_MASK)
     if bound is None:
         bound = 1.0 / math.sqrt(max(1.0, float(count) if per_row else count / max(m, 1)))
     device = torch.device("cpu" if device is None else device)
-    if _random_served(m, n, device, not per_row):
+    if _served(device, "random_csr_launch_shape", m, n, not per_row):
         row_indices, row_offsets, column_indices, values, state = ops.random_csr(
             m, n, per_row=per_row_count, total=total, dtype=dtype, bound=bound, device=device, rng_state=rng_state)
     else:
@@ -345,30 +352,10 @@ def magnitude_prune(matrix, density=None, nonzeros=None, per_row=False):
     rows take the same rule in torch.  Both give the same integers and value bits."""
     if matrix.dim() != 2:
         raise ValueError(f"magnitude_prune: expected a [m, n] matrix, got {tuple(matrix.shape)}")
-    if (density is None) == (nonzeros is None):
-        raise ValueError("magnitude_prune: give exactly one of density / nonzeros")
-    m, n = matrix.shape
-    most = n if per_row else m * n
-    if density is not None:
-        if not 0.0 <= density <= 1.0:
-            raise ValueError(f"magnitude_prune: density {density} is outside 0 .. 1")
-        nonzeros = round(density * most)
-    count = int(nonzeros)
-    if not 0 <= count <= most:
-        raise ValueError(f"magnitude_prune: {count} entries asked of {most}")
+    count = _count_of("magnitude_prune", density, nonzeros, matrix.size(1) if per_row else matrix.numel())
     row_indices, row_offsets, column_indices, values = topk_to_csr(
         matrix, per_row=count if per_row else None, total=None if per_row else count)
     return values, row_indices, row_offsets, column_indices
-
-
-def _regrow_served(values, scores):
-    if not (_device_build and values.is_cuda and values.dtype in _TOPK_DTYPES and scores.dtype in _TOPK_DTYPES):
-        return False
-    try:
-        return capi.csr_regrow_launch_shape(scores.size(0), scores.size(1), scores.element_size(),
-                                            values.element_size())["served"]
-    except RuntimeError:   # (more than INT_MAX elements)
-        return False
 
 
 def _first_in_stable_order(keys, counts):
@@ -403,22 +390,20 @@ def regrow_per_row(values, row_offsets, column_indices, drop_counts, scores):
     take the same rule in torch: per row a stable descending argsort of the keys, with the kept
     columns forced first.  Both give the same integers and value bits."""
     ops.check_regrow_arguments(values, row_offsets, column_indices, drop_counts, scores)
-    values, scores = values.detach(), scores.detach()
-    if scores.dtype not in _TOPK_DTYPES:
-        scores = scores.float()
-    if _regrow_served(values, scores):
-        return ops.csr_regrow(values, row_offsets, column_indices, drop_counts, scores)
+    values, scores = values.detach(), _rankable(scores.detach())
     m, n = scores.shape
+    if values.dtype in _TOPK_DTYPES and _served(values, "csr_regrow_launch_shape", m, n, scores.element_size(),
+                                                values.element_size()):
+        return ops.csr_regrow(values, row_offsets, column_indices, drop_counts, scores)
     nnz = column_indices.numel()
     index = dict(dtype=torch.int64, device=values.device)
     lengths = (row_offsets[1:] - row_offsets[:-1]).to(torch.int64)
-    rows = torch.repeat_interleave(torch.arange(m, **index), lengths, output_size=nnz)
-    flat = rows * n + column_indices.to(torch.int64)
+    flat = _entry_rows(row_offsets, nnz) * n + column_indices.to(torch.int64)
     drop = torch.minimum(drop_counts.to(torch.int64).clamp(min=0), lengths)
     # dense images of the old entries: their value keys (-1 elsewhere: behind every entry) and
     # their indices
     value_keys = torch.full((m * n,), -1, **index)
-    value_keys[flat] = magnitude_keys(values if values.dtype in _TOPK_DTYPES else values.float())
+    value_keys[flat] = magnitude_keys(_rankable(values))
     entry = torch.full((m * n,), -1, **index)
     entry[flat] = torch.arange(nnz, **index)
     kept = _first_in_stable_order(value_keys.view(m, n), lengths - drop)
@@ -437,16 +422,6 @@ def regrow_per_row(values, row_offsets, column_indices, drop_counts, scores):
     return new_columns.to(torch.int32), new_bits.view(values.dtype), source
 
 
-def _regrow_total_served(values, scores):
-    if not (_device_build and values.is_cuda and values.dtype in _TOPK_DTYPES and scores.dtype in _TOPK_DTYPES):
-        return False
-    try:
-        return capi.csr_regrow_total_launch_shape(scores.size(0), scores.size(1), values.numel(),
-                                                  scores.element_size(), values.element_size())["served"]
-    except RuntimeError:   # (more than INT_MAX elements)
-        return False
-
-
 def regrow_total_composed(values, row_offsets, column_indices, drop, scores):
     """The rule of ``regrow_total`` composed from torch indexing and one ``topk_to_csr`` call
     (which itself picks the device build or torch): the kept entries are forced first in a dense
@@ -458,16 +433,12 @@ def regrow_total_composed(values, row_offsets, column_indices, drop, scores):
     m, n = scores.shape
     nnz = values.numel()
     device = values.device
-    rank_values = values if values.dtype in _TOPK_DTYPES else values.float()
-    order = torch.argsort(magnitude_keys(rank_values), descending=True, stable=True)
+    order = torch.argsort(magnitude_keys(_rankable(values)), descending=True, stable=True)
     kept = torch.sort(order[:nnz - d]).values                     # old entry indices, ascending
-    lengths = (row_offsets[1:] - row_offsets[:-1]).to(torch.int64)
-    rows = torch.repeat_interleave(torch.arange(m, device=device), lengths, output_size=nnz)
-    flat = rows * n + column_indices.to(torch.int64)              # ascending: CSR is row major
+    flat = _entry_rows(row_offsets, nnz) * n + column_indices.to(torch.int64)   # ascending: CSR is row major
     kept_flat = flat[kept]
 
-    if scores.dtype not in _TOPK_DTYPES:
-        scores = scores.float()
+    scores = _rankable(scores)
     largest = torch.finfo(scores.dtype).max
     scores = torch.nan_to_num(scores.abs(), nan=largest, posinf=largest).contiguous()
     scores.view(-1)[kept_flat] = float("inf")                      # Kept comes first ...
@@ -476,9 +447,7 @@ def regrow_total_composed(values, row_offsets, column_indices, drop, scores):
     image.view(bits).view(-1)[kept_flat] = values.contiguous().view(bits)[kept]   # bit for bit
     row_indices, new_offsets, new_columns, new_values = topk_to_csr(scores, total=nnz, values_from=image)
 
-    new_lengths = (new_offsets[1:] - new_offsets[:-1]).to(torch.int64)
-    new_rows = torch.repeat_interleave(torch.arange(m, device=device), new_lengths, output_size=nnz)
-    new_flat = new_rows * n + new_columns.to(torch.int64)
+    new_flat = _entry_rows(new_offsets, nnz) * n + new_columns.to(torch.int64)
     at = torch.searchsorted(kept_flat, new_flat).clamp_(max=kept_flat.numel() - 1)
     if kept_flat.numel():
         source = torch.where(kept_flat[at] == new_flat, kept[at], torch.full_like(at, -1))
@@ -511,21 +480,11 @@ def regrow_total(values, row_offsets, column_indices, drop, scores):
     dtypes (ranked as ``.float()``), larger shapes and ``enable_device_build(False)`` take
     ``regrow_total_composed``.  Both give the same integers and value bits."""
     d = ops.check_regrow_total_arguments(values, row_offsets, column_indices, drop, scores)
-    values, scores = values.detach(), scores.detach()
-    if scores.dtype not in _TOPK_DTYPES:
-        scores = scores.float()
-    if _regrow_total_served(values, scores):
+    values, scores = values.detach(), _rankable(scores.detach())
+    if values.dtype in _TOPK_DTYPES and _served(values, "csr_regrow_total_launch_shape", scores.size(0), scores.size(1),
+                                                values.numel(), scores.element_size(), values.element_size()):
         return ops.csr_regrow_total(values, row_offsets, column_indices, d, scores)
     return regrow_total_composed(values, row_offsets, column_indices, d, scores)
-
-
-def _csr_topk_served(values, m, n, total):
-    if not (_device_build and values.is_cuda and values.dtype in _TOPK_DTYPES):
-        return False
-    try:
-        return capi.csr_topk_launch_shape(m, n, values.numel(), values.element_size(), total)["served"]
-    except RuntimeError:   # (sizes beyond int32)
-        return False
 
 
 def prune_csr(values, row_offsets, column_indices, n, per_row=None, total=None):
@@ -551,13 +510,13 @@ def prune_csr(values, row_offsets, column_indices, n, per_row=None, total=None):
         raise ValueError(f"prune_csr: per_row = {count} is outside 0 .. {n}")
     values = values.detach()
     m, nnz = row_offsets.numel() - 1, values.numel()
-    if _csr_topk_served(values, m, n, per_row is None):
+    if values.dtype in _TOPK_DTYPES and _served(values, "csr_topk_launch_shape", m, n, nnz, values.element_size(),
+                                                per_row is None):
         return ops.csr_topk(values, row_offsets, column_indices, per_row=per_row, total=total)
     index = dict(dtype=torch.int64, device=values.device)
-    keys = magnitude_keys(values if values.dtype in _TOPK_DTYPES else values.float())
-    order = torch.argsort(keys, descending=True, stable=True)     # key descending, index ascending
-    lengths = (row_offsets[1:] - row_offsets[:-1]).to(torch.int64)
-    rows = torch.repeat_interleave(torch.arange(m, **index), lengths, output_size=nnz)
+    # key descending, index ascending
+    order = torch.argsort(magnitude_keys(_rankable(values)), descending=True, stable=True)
+    rows = _entry_rows(row_offsets, nnz)
     if per_row is None:
         source = torch.sort(order[:count]).values
     else:
@@ -567,9 +526,7 @@ def prune_csr(values, row_offsets, column_indices, n, per_row=None, total=None):
         rank = torch.empty(nnz, **index)
         rank[by_row] = torch.arange(nnz, **index) - row_offsets[:-1].to(torch.int64)[rows[by_row]]
         source = torch.nonzero(rank < count).reshape(-1)
-    new_offsets = torch.zeros(m + 1, dtype=torch.int32, device=values.device)
-    new_offsets[1:] = torch.cumsum(torch.bincount(rows[source], minlength=m), 0)
-    return (diffsort(new_offsets), new_offsets, column_indices[source], _take_bits(values, source), source)
+    return _csr_from_source(values, rows, m, column_indices, source)
 
 
 _INT_MAX = 2 ** 31 - 1
@@ -577,14 +534,12 @@ _INT_MAX = 2 ** 31 - 1
 
 def _csr_topk_global_served(values, row_offsets):
     first = values[0]
-    if not (_device_build and first.is_cuda and first.dtype in _TOPK_DTYPES):
-        return False
-    if any(v.device != first.device or v.dtype != first.dtype for v in values):
+    if first.dtype not in _TOPK_DTYPES or any(v.device != first.device or v.dtype != first.dtype for v in values):
         return False
     rows, nonzeros = [ro.numel() - 1 for ro in row_offsets], [v.numel() for v in values]
-    if max(rows) > _INT_MAX or sum(nonzeros) > _INT_MAX:
+    if max(rows) > _INT_MAX or sum(nonzeros) > _INT_MAX:   # (the query takes C ints)
         return False
-    return capi.csr_topk_global_launch_shape(rows, nonzeros, first.element_size())["served"]
+    return _served(first, "csr_topk_global_launch_shape", rows, nonzeros, first.element_size())
 
 
 def prune_csr_global(layers, total):
@@ -630,13 +585,8 @@ def prune_csr_global(layers, total):
     results = []
     for l, v in enumerate(values):
         source = kept[cuts[l]:cuts[l + 1]] - int(bounds[l])
-        m = row_offsets[l].numel() - 1
-        lengths = (row_offsets[l][1:] - row_offsets[l][:-1]).to(torch.int64)
-        rows = torch.repeat_interleave(torch.arange(m, dtype=torch.int64, device=v.device), lengths,
-                                       output_size=sizes[l])
-        new_offsets = torch.zeros(m + 1, dtype=torch.int32, device=v.device)
-        new_offsets[1:] = torch.cumsum(torch.bincount(rows[source], minlength=m), 0)
-        results.append((diffsort(new_offsets), new_offsets, column_indices[l][source], _take_bits(v, source), source))
+        results.append(_csr_from_source(v, _entry_rows(row_offsets[l], sizes[l]), row_offsets[l].numel() - 1,
+                                        column_indices[l], source))
     return results
 
 
@@ -661,20 +611,9 @@ def prune_layers_to(modules, density=None, nonzeros=None, optimizer=None):
     Returns the list of ``source`` tensors, int64 ``[new nnz_l]``, ascending: for every new
     entry its index in the layer's old ``values``.  With ``optimizer=`` the state of every
     layer's old Parameter is handed to the new one (``remap_optimizer_state``)."""
-    from torch import nn
-
-    from . import functional
     modules = list(modules)
-    if (density is None) == (nonzeros is None):
-        raise ValueError("prune_layers_to: give exactly one of density / nonzeros")
-    most = sum(module.output_features * module.input_features for module in modules)
-    if density is not None:
-        if not 0.0 <= density <= 1.0:
-            raise ValueError(f"prune_layers_to: density {density} is outside 0 .. 1")
-        nonzeros = round(density * most)
-    count = int(nonzeros)
-    if not 0 <= count <= most:
-        raise ValueError(f"prune_layers_to: {count} entries asked of {most}")
+    count = _count_of("prune_layers_to", density, nonzeros,
+                      sum(module.output_features * module.input_features for module in modules))
     olds = [module.values for module in modules]
     if count >= sum(old.numel() for old in olds):
         return [torch.arange(old.numel(), dtype=torch.int64, device=old.device) for old in olds]
@@ -684,9 +623,7 @@ def prune_layers_to(modules, density=None, nonzeros=None, optimizer=None):
              for old, module in zip(olds, modules)], count)
         sources = []
         for module, old, (row_indices, row_offsets, column_indices, values, source) in zip(modules, olds, results):
-            functional.unregister_static_topology(module.row_indices, module.row_offsets, module.column_indices)
-            module._set_topology(nn.Parameter(values, requires_grad=old.requires_grad), row_indices, row_offsets,
-                                 column_indices)
+            module._install_topology(values, row_indices, row_offsets, column_indices, into_parameter=False)
             if optimizer is not None:
                 remap_optimizer_state(optimizer, old, module.values, source)
             sources.append(source)
