@@ -72,7 +72,8 @@ Tensor as_index(const Tensor& t, const char* name, const Tensor& like) {
 //   sddmm_narrow                         -> the operands' (half) type, on request only;
 //   transpose_last2_as                   -> the type its out_type argument names.
 // Ops that take float32 only in their kernels widen half operands once with as_float
-// below; the ops whose kernels read half storage natively take as_storage.
+// below; the ops whose kernels read half storage natively take as_storage.  The SpMM ops
+// choose per call: THE NATIVE-HALF RULE at check_spmm says which.
 int type_code(at::ScalarType t) {   // -1: not a storage type of the library
   return t == at::kFloat ? SPUTNIK_HIP_F32 : t == at::kHalf ? SPUTNIK_HIP_F16
          : t == at::kBFloat16 ? SPUTNIK_HIP_BF16 : -1;
@@ -223,27 +224,94 @@ void check_plan(const Tensor& plan, size_t bytes, const Tensor& like) {
               " bytes): it was made for other sizes");
 }
 
+// The workspace of a call: the plan where one is given (checked against `bytes`), else fresh
+// memory that `keep` holds for the call; no pointer where the call needs no workspace.
+struct Workspace {
+  void* ptr;
+  int planned;
+  Tensor keep;
+};
+
+Workspace plan_or_workspace(const c10::optional<Tensor>& plan, size_t bytes, const Tensor& like) {
+  if (plan.has_value()) {
+    check_plan(*plan, bytes, like);
+    return {bytes ? plan->data_ptr() : nullptr, 1, Tensor()};
+  }
+  if (bytes == 0) return {nullptr, 0, Tensor()};
+  Tensor fresh = workspace_like(like, bytes);
+  return {fresh.data_ptr(), 0, fresh};
+}
+
 Tensor permute_last(const Tensor& values_in, const Tensor& permutation);
 Tensor transpose_last2(const Tensor& x);
 
-// Shared by spmm (values [nnz] / [R,nnz]) and left_spmm (values [nnz], shared).
-Tensor spmm_impl(int64_t m64, int64_t k64, const Tensor& values_in, const Tensor& row_indices,
-                 const Tensor& row_offsets, const Tensor& column_indices, const Tensor& dense_in,
-                 bool left, const char* what, const c10::optional<Tensor>& bias_in = c10::nullopt,
-                 bool relu = false, const c10::optional<Tensor>& plan = c10::nullopt,
-                 const c10::optional<Tensor>& permutation = c10::nullopt, int64_t block_rows = 0) {
-  const int m = to_int(m64, "m"), k = to_int(k64, "k");
-  // float16 / bfloat16 operands of the plain product go to the kernels as they are
-  // (sputnik_hip_spmm_typed); the permuted / transposed-store forms, which the modules
-  // reach with float32 operands, and a float16 / bfloat16 mix take the widened path.
-  const auto is_half = [](const Tensor& t) {
-    return t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16;
-  };
-  const bool native_half =
-      (is_half(values_in) || is_half(dense_in)) && !permutation.has_value() && block_rows == 0 &&
-      !(is_half(values_in) && is_half(dense_in) && values_in.scalar_type() != dense_in.scalar_type());
-  Tensor values = native_half ? as_storage(values_in, "values") : as_float(values_in, "values");
-  const Tensor dense = native_half ? as_storage(dense_in, "dense") : as_float(dense_in, "dense");
+// ---------------------------------------------------------------------------
+// The SpMM host stack: one operand contract (check_spmm), one product with its
+// ladder of routes (spmm_product), and on top of it the transposed-store form and the groups.
+// ---------------------------------------------------------------------------
+
+// Entry p of the topology takes values[..., permutation[p]]: int32 [nonzeros], contiguous, on
+// `like`'s device.
+void check_permutation(const Tensor& permutation, int64_t nonzeros, const Tensor& like) {
+  TORCH_CHECK(permutation.scalar_type() == at::kInt && permutation.dim() == 1 &&
+                  permutation.is_contiguous() && permutation.device() == like.device() &&
+                  permutation.size(0) == nonzeros,
+              "permutation must be a contiguous int32 vector of ", nonzeros, " entries on ",
+              like.device());
+}
+
+// One value per output row -> float32 [m] on `like`'s device.
+Tensor check_bias(const Tensor& bias_in, int m, const Tensor& like) {
+  const Tensor bias = as_float(bias_in, "bias");
+  TORCH_CHECK(bias.device() == like.device() && bias.dim() == 1 && bias.size(0) == m,
+              "bias should have m = ", m, " elements on ", like.device(), ", got ", bias.sizes());
+  return bias;
+}
+
+bool is_half(const Tensor& t) {
+  return t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16;
+}
+
+// THE NATIVE-HALF RULE.  A product with a float16 / bfloat16 operand -- one of them, or both of ONE
+// half type -- goes to the typed kernels as it is stored (sputnik_hip_spmm_typed: no widening
+// copy).  A float16 x bfloat16 mix widens both to float32, and so does a permutation (the permuted
+// forms, which the modules reach with float32 operands, gather float32 values).  The
+// transposed-store form asks the same question without its block_rows: its fused launch reads
+// float32 and widens such operands for itself, and where that launch does not serve the call the
+// product it falls back to reads the operands as they came, half included.
+bool native_half(const Tensor& values, const Tensor& dense, bool permuted) {
+  return (is_half(values) || is_half(dense)) && !permuted &&
+         !(is_half(values) && is_half(dense) && values.scalar_type() != dense.scalar_type());
+}
+
+// The operands of spmm (values [nnz] against dense [k, n], or [R, nnz] against [R, k, n]) and
+// left_spmm (values [nnz], shared, against dense [k, n] / [R, k, n]) after every check: contiguous,
+// on one device, as stored (native_half) or float32; the product is [replicas, m, n] float32,
+// [m, n] for the one replica of a spmm.
+struct SpmmCall {
+  const char* what;
+  Tensor values, dense;
+  c10::optional<Tensor> permutation;
+  Topology topo;
+  int m, k, n, replicas;
+  int64_t values_stride;   // 0: one row of values for every replica
+  bool left, native_half;
+};
+
+SpmmCall check_spmm(const char* what, int64_t m64, int64_t k64, const Tensor& values_in,
+                    const Tensor& row_indices, const Tensor& row_offsets,
+                    const Tensor& column_indices, const Tensor& dense_in, bool left,
+                    const c10::optional<Tensor>& permutation = c10::nullopt) {
+  SpmmCall c;
+  c.what = what;
+  c.left = left;
+  c.m = to_int(m64, "m");
+  c.k = to_int(k64, "k");
+  c.native_half = native_half(values_in, dense_in, permutation.has_value());
+  c.values = c.native_half ? as_storage(values_in, "values") : as_float(values_in, "values");
+  c.dense = c.native_half ? as_storage(dense_in, "dense") : as_float(dense_in, "dense");
+  const Tensor& values = c.values;
+  const Tensor& dense = c.dense;
   TORCH_CHECK(dense.device() == values.device(), "values and dense must be on one device");
   TORCH_CHECK(dense.dim() == 2 || dense.dim() == 3, "dense should have 2 or 3 dimensions, got ",
               dense.dim());
@@ -257,339 +325,296 @@ Tensor spmm_impl(int64_t m64, int64_t k64, const Tensor& values_in, const Tensor
                 "values and dense must be replicated the same: values.dim()=", values.dim(),
                 ", dense.dim()=", dense.dim());
   }
-  const c10::DeviceGuard guard(values.device());
-  const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, values);
-
+  c.topo = check_topology(c.m, row_indices, row_offsets, column_indices, values);
   const int dim_offset = static_cast<int>(dense.dim()) - 2;
-  const int replicas = dim_offset == 1 ? to_int(dense.size(0), "replicas") : 1;
-  const int n = to_int(dense.size(dim_offset + 1), "n");
-  TORCH_CHECK(values.size(-1) == topo.nonzeros, "number of values (", values.size(-1),
-              ") must equal the number of column_indices (", topo.nonzeros, ")");
-  TORCH_CHECK(dense.size(dim_offset) == k, "inner matrix dimensions must match: dense has ",
-              dense.size(dim_offset), " rows, k = ", k);
+  c.replicas = dim_offset == 1 ? to_int(dense.size(0), "replicas") : 1;
+  c.n = to_int(dense.size(dim_offset + 1), "n");
+  TORCH_CHECK(values.size(-1) == c.topo.nonzeros, "number of values (", values.size(-1),
+              ") must equal the number of column_indices (", c.topo.nonzeros, ")");
+  TORCH_CHECK(dense.size(dim_offset) == c.k, "inner matrix dimensions must match: dense has ",
+              dense.size(dim_offset), " rows, k = ", c.k);
   if (!left && values.dim() == 2) {
-    TORCH_CHECK(values.size(0) == replicas, "first dim of values (", values.size(0),
-                ") and dense (", replicas, ") must match");
+    TORCH_CHECK(values.size(0) == c.replicas, "first dim of values (", values.size(0),
+                ") and dense (", c.replicas, ") must match");
   }
-
-  const auto options = values.options().dtype(at::kFloat);   // the product is float32
-  const int64_t values_stride = (left || values.dim() == 1) ? 0 : topo.nonzeros;
-  if (block_rows > 0) {
-    // The product stored as the transposes of its blocks of `block_rows` rows,
-    // [replicas * m / block_rows, n, block_rows]: the head split behind a projection
-    // (modules/sparse_attention.py:38-45) or the whole C^T (block_rows = m), written
-    // by the panel kernel's store phase where it serves the shape; elsewhere the
-    // usual product followed by the tiled transpose kernel.
-    TORCH_CHECK(m % block_rows == 0, "block_rows (", block_rows, ") must divide m = ", m);
-    if (permutation.has_value())
-      TORCH_CHECK(permutation->scalar_type() == at::kInt && permutation->dim() == 1 &&
-                      permutation->is_contiguous() && permutation->device() == values.device() &&
-                      permutation->size(0) == topo.nonzeros,
-                  "permutation must be a contiguous int32 vector of ", topo.nonzeros,
-                  " entries on ", values.device());
-    const bool fused_perm = !permutation.has_value() ||
-                            sputnik_hip_spmm_permuted_supported(m, k, n, topo.nonzeros);
-    if (fused_perm && sputnik_hip_spmm_transposed_out_supported(m, k, n, topo.nonzeros,
-                                                                static_cast<int>(block_rows))) {
-      Tensor bias;
-      if (bias_in.has_value()) {
-        bias = as_float(*bias_in, "bias");
-        TORCH_CHECK(bias.device() == values.device() && bias.dim() == 1 && bias.size(0) == m,
-                    "bias should have m = ", m, " elements on ", values.device());
-      }
-      Tensor tout = at::empty({replicas * (m / block_rows), n, block_rows}, options);
-      const int st = sputnik_hip_spmm_transposed_out_batched(
-          m, k, n, topo.nonzeros, replicas, values.data_ptr<float>(), values_stride,
-          permutation.has_value() ? permutation->data_ptr<int>() : nullptr,
-          topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(),
-          dense.data_ptr<float>(), static_cast<int64_t>(k) * n,
-          bias.defined() ? bias.data_ptr<float>() : nullptr, relu ? 1 : 0,
-          static_cast<int>(block_rows), tout.data_ptr<float>(), static_cast<int64_t>(m) * n,
-          current_stream(values));
-      if (st != SPUTNIK_HIP_UNSUPPORTED) {
-        check_status(st, what);
-        return tout;
-      }
-    }
-    const Tensor c = spmm_impl(m64, k64, values_in, row_indices, row_offsets, column_indices,
-                               dense_in, left, what, bias_in, relu, plan, permutation, 0);
-    return transpose_last2(c.reshape({replicas * (m / block_rows), block_rows, n}));
-  }
-  Tensor out = (replicas == 1 && !left) ? at::empty({m, n}, options)
-                                        : at::empty({replicas, m, n}, options);
+  c.values_stride = (left || values.dim() == 1) ? 0 : c.topo.nonzeros;
   if (permutation.has_value()) {
-    // values are those of ANOTHER ordering of the same entries (the topology here
-    // is its transpose): entry p takes values[permutation[p]].  One kernel where
-    // the panel kernel serves the shape in one pass; otherwise the values are
-    // permuted first and the call goes on as usual.
-    TORCH_CHECK(permutation->scalar_type() == at::kInt && permutation->dim() == 1 &&
-                    permutation->is_contiguous() && permutation->device() == values.device() &&
-                    permutation->size(0) == topo.nonzeros,
-                "permutation must be a contiguous int32 vector of ", topo.nonzeros,
-                " entries on ", values.device());
-    int st = SPUTNIK_HIP_UNSUPPORTED;
-    if (sputnik_hip_spmm_permuted_supported(m, k, n, topo.nonzeros))
-      st = sputnik_hip_spmm_permuted_batched(
-          m, k, n, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
-          values.data_ptr<float>(), values_stride, permutation->data_ptr<int>(),
-          topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(),
-          dense.data_ptr<float>(), static_cast<int64_t>(k) * n, out.data_ptr<float>(),
-          static_cast<int64_t>(m) * n, current_stream(values));
-    if (st != SPUTNIK_HIP_UNSUPPORTED) {
-      check_status(st, what);
-      return out;
-    }
-    values = permute_last(values, *permutation);
+    check_permutation(*permutation, c.topo.nonzeros, values);
+    c.permutation = permutation;
   }
-  if (native_half) {   // (a plan has nothing to add: the half-reading kernels have no pre-pass)
-    Tensor bias;
-    if (bias_in.has_value()) {
-      bias = as_float(*bias_in, "bias");
-      TORCH_CHECK(bias.device() == values.device() && bias.dim() == 1 && bias.size(0) == m,
-                  "bias should have m = ", m, " elements on ", values.device());
+  return c;
+}
+
+// The product of a checked call: the ladder  permuted -> native half -> planned -> per call.
+// `bias_in` / `relu` come from spmm_bias* alone: no permutation and no plan with them.
+Tensor spmm_product(const SpmmCall& c, const c10::optional<Tensor>& plan,
+                    const c10::optional<Tensor>& bias_in = c10::nullopt, bool relu = false) {
+  TORCH_INTERNAL_ASSERT(!bias_in.has_value() || (!plan.has_value() && !c.permutation.has_value()));
+  const int m = c.m, k = c.k, n = c.n, nonzeros = c.topo.nonzeros, replicas = c.replicas;
+  const int* row_indices = c.topo.row_indices.data_ptr<int>();
+  const int* row_offsets = c.topo.row_offsets.data_ptr<int>();
+  const int* column_indices = c.topo.column_indices.data_ptr<int>();
+  const int64_t dense_stride = static_cast<int64_t>(k) * n, out_stride = static_cast<int64_t>(m) * n;
+  const sputnik_hip_stream_t stream = current_stream(c.values);
+  const auto options = c.values.options().dtype(at::kFloat);   // the product is float32
+  Tensor out = (replicas == 1 && !c.left) ? at::empty({m, n}, options)
+                                          : at::empty({replicas, m, n}, options);
+  Tensor values = c.values;
+  if (c.permutation.has_value()) {
+    // values are those of ANOTHER ordering of the same entries (the topology here is its
+    // transpose).  One kernel where the panel kernel serves the shape in one pass; otherwise
+    // the values are permuted first and the call goes on as usual.
+    if (sputnik_hip_spmm_permuted_supported(m, k, n, nonzeros)) {
+      const int st = sputnik_hip_spmm_permuted_batched(
+          m, k, n, nonzeros, replicas, row_indices, values.data_ptr<float>(), c.values_stride,
+          c.permutation->data_ptr<int>(), row_offsets, column_indices, c.dense.data_ptr<float>(),
+          dense_stride, out.data_ptr<float>(), out_stride, stream);
+      if (st != SPUTNIK_HIP_UNSUPPORTED) {
+        check_status(st, c.what);
+        return out;
+      }
     }
+    values = permute_last(values, *c.permutation);
+  }
+  Tensor bias;
+  if (bias_in.has_value()) bias = check_bias(*bias_in, m, values);
+  const float* bias_ptr = bias.defined() ? bias.data_ptr<float>() : nullptr;
+  if (c.native_half) {   // (a plan has nothing to add: the half-reading kernels have no pre-pass)
+    const int values_type = type_code(values.scalar_type()), dense_type = type_code(c.dense.scalar_type());
     const size_t typed_ws = sputnik_hip_spmm_typed_workspace_bytes(
-        m, k, n, topo.nonzeros, replicas, type_code(values.scalar_type()), values_stride,
-        type_code(dense.scalar_type()));
+        m, k, n, nonzeros, replicas, values_type, c.values_stride, dense_type);
     Tensor workspace;
     char* ws = nullptr;
     if (typed_ws > 0) {
-      workspace = at::empty({static_cast<int64_t>(typed_ws + 256)}, options.dtype(at::kByte));
+      workspace = workspace_like(values, typed_ws + 256);
       ws = static_cast<char*>(workspace.data_ptr());
       ws += (256 - reinterpret_cast<uintptr_t>(ws) % 256) % 256;
     }
-    check_status(sputnik_hip_spmm_typed(
-                     m, k, n, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
-                     values.data_ptr(), type_code(values.scalar_type()), values_stride,
-                     topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(),
-                     dense.data_ptr(), type_code(dense.scalar_type()), static_cast<int64_t>(k) * n,
-                     bias.defined() ? bias.data_ptr<float>() : nullptr, relu ? 1 : 0,
-                     out.data_ptr<float>(), static_cast<int64_t>(m) * n, ws, typed_ws,
-                     current_stream(values)),
-                 what);
+    check_status(sputnik_hip_spmm_typed(m, k, n, nonzeros, replicas, row_indices, values.data_ptr(),
+                                        values_type, c.values_stride, row_offsets, column_indices,
+                                        c.dense.data_ptr(), dense_type, dense_stride, bias_ptr,
+                                        relu ? 1 : 0, out.data_ptr<float>(), out_stride, ws, typed_ws,
+                                        stream),
+                 c.what);
     return out;
   }
-  const size_t ws_bytes = sputnik_hip_spmm_workspace_bytes(m, k, n, topo.nonzeros);
-  if (plan.has_value()) {
-    // static topology: the pre-pass ran once (spmm_plan); kernels only
-    check_plan(*plan, ws_bytes, values);
+  const size_t ws_bytes = sputnik_hip_spmm_workspace_bytes(m, k, n, nonzeros);
+  const Workspace ws = plan_or_workspace(plan, ws_bytes, values);
+  if (ws.planned) {   // static topology: the pre-pass ran once (spmm_plan); kernels only
     check_status(sputnik_hip_spmm_batched_planned(
-                     m, k, n, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
-                     values.data_ptr<float>(), values_stride, topo.row_offsets.data_ptr<int>(),
-                     topo.column_indices.data_ptr<int>(), dense.data_ptr<float>(),
-                     static_cast<int64_t>(k) * n, out.data_ptr<float>(),
-                     static_cast<int64_t>(m) * n, ws_bytes ? plan->data_ptr() : nullptr, ws_bytes,
-                     current_stream(values)),
-                 what);
+                     m, k, n, nonzeros, replicas, row_indices, values.data_ptr<float>(),
+                     c.values_stride, row_offsets, column_indices, c.dense.data_ptr<float>(),
+                     dense_stride, out.data_ptr<float>(), out_stride, ws.ptr, ws_bytes, stream),
+                 c.what);
     return out;
-  }
-  Tensor workspace;
-  if (ws_bytes > 0)
-    workspace = at::empty({static_cast<int64_t>(ws_bytes)}, options.dtype(at::kByte));
-
-  Tensor bias;
-  if (bias_in.has_value()) {
-    bias = as_float(*bias_in, "bias");
-    TORCH_CHECK(bias.device() == values.device(), "bias must be on ", values.device());
-    TORCH_CHECK(bias.dim() == 1 && bias.size(0) == m, "bias should have m = ", m,
-                " elements (one per output row), got ", bias.sizes());
   }
   check_status(sputnik_hip_spmm_bias_batched(
-                   m, k, n, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
-                   values.data_ptr<float>(), values_stride, topo.row_offsets.data_ptr<int>(),
-                   topo.column_indices.data_ptr<int>(), dense.data_ptr<float>(),
-                   static_cast<int64_t>(k) * n, bias.defined() ? bias.data_ptr<float>() : nullptr,
-                   relu ? 1 : 0, out.data_ptr<float>(), static_cast<int64_t>(m) * n,
-                   ws_bytes ? workspace.data_ptr() : nullptr, ws_bytes, current_stream(values)),
-               what);
+                   m, k, n, nonzeros, replicas, row_indices, values.data_ptr<float>(),
+                   c.values_stride, row_offsets, column_indices, c.dense.data_ptr<float>(),
+                   dense_stride, bias_ptr, relu ? 1 : 0, out.data_ptr<float>(), out_stride, ws.ptr,
+                   ws_bytes, stream),
+               c.what);
   return out;
 }
 
-Tensor spmm(int64_t m, int64_t k, const Tensor& values, const Tensor& row_indices,
-            const Tensor& row_offsets, const Tensor& column_indices, const Tensor& dense) {
-  return spmm_impl(m, k, values, row_indices, row_offsets, column_indices, dense, false, "spmm");
+// The product stored as the transposes of its blocks of `block_rows` rows,
+// [replicas * m / block_rows, n, block_rows]: the head split behind a projection
+// (modules/sparse_attention.py:38-45) or the whole C^T (block_rows = m), written by the panel
+// kernel's store phase where it serves the shape (float32: half operands are widened for it);
+// elsewhere the product of the operands as they came, then the tiled transpose kernel.
+Tensor spmm_transposed_store(const SpmmCall& c, int64_t block_rows,
+                             const c10::optional<Tensor>& plan) {
+  TORCH_CHECK(c.m % block_rows == 0, "block_rows (", block_rows, ") must divide m = ", c.m);
+  const int64_t blocks = c.replicas * (c.m / block_rows);
+  const int nonzeros = c.topo.nonzeros;
+  if ((!c.permutation.has_value() || sputnik_hip_spmm_permuted_supported(c.m, c.k, c.n, nonzeros)) &&
+      sputnik_hip_spmm_transposed_out_supported(c.m, c.k, c.n, nonzeros, static_cast<int>(block_rows))) {
+    const Tensor values = c.native_half ? c.values.to(at::kFloat) : c.values;
+    const Tensor dense = c.native_half ? c.dense.to(at::kFloat) : c.dense;
+    Tensor out = at::empty({blocks, c.n, block_rows}, values.options());
+    const int st = sputnik_hip_spmm_transposed_out_batched(
+        c.m, c.k, c.n, nonzeros, c.replicas, values.data_ptr<float>(), c.values_stride,
+        c.permutation.has_value() ? c.permutation->data_ptr<int>() : nullptr,
+        c.topo.row_offsets.data_ptr<int>(), c.topo.column_indices.data_ptr<int>(),
+        dense.data_ptr<float>(), static_cast<int64_t>(c.k) * c.n, nullptr, 0,
+        static_cast<int>(block_rows), out.data_ptr<float>(), static_cast<int64_t>(c.m) * c.n,
+        current_stream(values));
+    if (st != SPUTNIK_HIP_UNSUPPORTED) {
+      check_status(st, c.what);
+      return out;
+    }
+  }
+  return transpose_last2(spmm_product(c, plan).reshape({blocks, block_rows, c.n}));
 }
 
-// spmm / left_spmm over a topology whose values are given in another order
-// (values_here[p] = values[permutation[p]]): the transposed products of the
-// backward passes, modules/spmm.py:59-66, without the permuted copy.
+// One op: the operands checked, then the product or (block_rows > 0) its transposed store.
+Tensor spmm_op(const char* what, int64_t m, int64_t k, const Tensor& values,
+               const Tensor& row_indices, const Tensor& row_offsets, const Tensor& column_indices,
+               const Tensor& dense, bool left, const c10::optional<Tensor>& permutation = c10::nullopt,
+               const c10::optional<Tensor>& plan = c10::nullopt, int64_t block_rows = 0,
+               const c10::optional<Tensor>& bias = c10::nullopt, bool relu = false) {
+  const SpmmCall c = check_spmm(what, m, k, values, row_indices, row_offsets, column_indices, dense,
+                                left, permutation);
+  const c10::DeviceGuard guard(c.values.device());
+  return block_rows > 0 ? spmm_transposed_store(c, block_rows, plan)
+                        : spmm_product(c, plan, bias, relu);
+}
+
+// The registered ops.  spmm / left_spmm (`left`): plain, through a plan, and over a topology whose
+// values are given in another order (values_here[p] = values[permutation[p]]: the transposed
+// products of the backward passes, modules/spmm.py:59-66, without the permuted copy).
+template <bool left>
+Tensor spmm_plain(int64_t m, int64_t k, const Tensor& values, const Tensor& row_indices,
+                  const Tensor& row_offsets, const Tensor& column_indices, const Tensor& dense) {
+  return spmm_op(left ? "left_spmm" : "spmm", m, k, values, row_indices, row_offsets, column_indices,
+                 dense, left);
+}
+constexpr auto spmm = &spmm_plain<false>;   // (the composed attention routes call it)
+
+template <bool left>
+Tensor spmm_planned(int64_t m, int64_t k, const Tensor& values, const Tensor& row_indices,
+                    const Tensor& row_offsets, const Tensor& column_indices, const Tensor& dense,
+                    const Tensor& plan) {
+  return spmm_op(left ? "left_spmm_planned" : "spmm_planned", m, k, values, row_indices, row_offsets,
+                 column_indices, dense, left, c10::nullopt, plan);
+}
+
+template <bool left>
 Tensor spmm_permuted(int64_t m, int64_t k, const Tensor& values, const Tensor& permutation,
                      const Tensor& row_indices, const Tensor& row_offsets,
                      const Tensor& column_indices, const Tensor& dense,
                      const c10::optional<Tensor>& plan) {
-  return spmm_impl(m, k, values, row_indices, row_offsets, column_indices, dense, false,
-                   "spmm_permuted", c10::nullopt, false, plan, permutation);
+  return spmm_op(left ? "left_spmm_permuted" : "spmm_permuted", m, k, values, row_indices,
+                 row_offsets, column_indices, dense, left, permutation, plan);
 }
 
-// spmm / left_spmm with the product stored as the transposes of its blocks of
-// `block_rows` rows -> [replicas * m / block_rows, n, block_rows]; `permutation`
-// as in spmm_permuted.
+template <bool relu>
+Tensor spmm_bias(int64_t m, int64_t k, const Tensor& values, const Tensor& row_indices,
+                 const Tensor& row_offsets, const Tensor& column_indices, const Tensor& bias,
+                 const Tensor& dense) {
+  return spmm_op(relu ? "spmm_bias_relu" : "spmm_bias", m, k, values, row_indices, row_offsets,
+                 column_indices, dense, false, c10::nullopt, c10::nullopt, 0, bias, relu);
+}
+
+// spmm / left_spmm stored as spmm_transposed_store writes it; `permutation` as in spmm_permuted.
 Tensor spmm_transposed_out(int64_t m, int64_t k, const Tensor& values,
                            const c10::optional<Tensor>& permutation, const Tensor& row_indices,
                            const Tensor& row_offsets, const Tensor& column_indices,
                            const Tensor& dense, int64_t block_rows, bool left,
                            const c10::optional<Tensor>& plan) {
   TORCH_CHECK(block_rows > 0, "block_rows must be positive, got ", block_rows);
-  return spmm_impl(m, k, values, row_indices, row_offsets, column_indices, dense, left,
-                   "spmm_transposed_out", c10::nullopt, false, plan, permutation, block_rows);
+  return spmm_op("spmm_transposed_out", m, k, values, row_indices, row_offsets, column_indices,
+                 dense, left, permutation, plan, block_rows);
 }
 
 // ---------------------------------------------------------------------------
-// Groups of projections in one launch (sputnik_hip.h: sputnik_hip_spmm_group_batched).
+// Groups of projections in one launch (sputnik_hip.h: sputnik_hip_spmm_group_batched):
+// float32 throughout; a group the kernel does not take runs one by one through spmm_op.
 // ---------------------------------------------------------------------------
-struct GroupArgs {
-  std::vector<Tensor> values, permutations, dense;
-  std::vector<Topology> topo;
-  int m, k, n, replicas;
-};
-
-GroupArgs check_group(int64_t m64, int64_t k64, at::TensorList values, at::TensorList permutations,
-                      at::TensorList row_indices, at::TensorList row_offsets,
-                      at::TensorList column_indices, at::TensorList dense, const char* what) {
+// One checked left_spmm call per weight, widened to float32, all of one shape on one device;
+// `dense`: one input per weight, or one that every weight shares.
+std::vector<SpmmCall> check_group(const char* what, int64_t m, int64_t k, at::TensorList values,
+                                  at::TensorList permutations, at::TensorList row_indices,
+                                  at::TensorList row_offsets, at::TensorList column_indices,
+                                  at::TensorList dense) {
   const size_t count = values.size();
   TORCH_CHECK(count >= 1, what, ": expected at least one matrix");
   TORCH_CHECK(row_indices.size() == count && row_offsets.size() == count &&
                   column_indices.size() == count && (dense.size() == count || dense.size() == 1) &&
                   (permutations.empty() || permutations.size() == count),
               what, ": the lists must have one entry per matrix");
-  GroupArgs a;
-  a.m = to_int(m64, "m");
-  a.k = to_int(k64, "k");
-  for (size_t p = 0; p < dense.size(); ++p) {
-    Tensor d = as_float(dense[p], "dense");
-    TORCH_CHECK(d.dim() == 3 && d.size(1) == a.k, what, ": dense should be [B, k = ", a.k,
-                ", n], got ", d.sizes());
-    if (p == 0) {
-      a.replicas = to_int(d.size(0), "replicas");
-      a.n = to_int(d.size(2), "n");
-    }
-    TORCH_CHECK(d.size(0) == a.replicas && d.size(2) == a.n && d.device() == dense[0].device(),
-                what, ": all dense operands must have one shape and device");
-    a.dense.push_back(d);
+  std::vector<Tensor> wide;
+  for (const Tensor& d : dense) {
+    wide.push_back(as_float(d, "dense"));
+    TORCH_CHECK(d.dim() == 3 && d.sizes() == dense[0].sizes() && d.device() == dense[0].device(), what,
+                ": the dense operands should be [B, k, n] of one shape on one device, got ", d.sizes());
   }
-  for (size_t p = 0; p < count; ++p) {
-    Tensor v = as_float(values[p], "values");
-    TORCH_CHECK(v.dim() == 1 && v.device() == a.dense[0].device(), what,
-                ": values should have 1 dimension (shared by the batch) on ", a.dense[0].device());
-    Topology t = check_topology(a.m, row_indices[p], row_offsets[p], column_indices[p], v);
-    TORCH_CHECK(v.size(0) == t.nonzeros, "number of values (", v.size(0),
-                ") must equal the number of column_indices (", t.nonzeros, ")");
-    if (!permutations.empty()) {
-      const Tensor& perm = permutations[p];
-      TORCH_CHECK(perm.scalar_type() == at::kInt && perm.dim() == 1 && perm.is_contiguous() &&
-                      perm.device() == v.device() && perm.size(0) == t.nonzeros,
-                  "permutation must be a contiguous int32 vector of ", t.nonzeros, " entries");
-      a.permutations.push_back(perm);
-    }
-    a.values.push_back(v);
-    a.topo.push_back(t);
-  }
-  return a;
+  std::vector<SpmmCall> calls;
+  for (size_t p = 0; p < count; ++p)
+    calls.push_back(check_spmm(
+        what, m, k, as_float(values[p], "values"), row_indices[p], row_offsets[p], column_indices[p],
+        wide[wide.size() == 1 ? 0 : p], true,
+        permutations.empty() ? c10::optional<Tensor>() : c10::optional<Tensor>(permutations[p])));
+  return calls;
+}
+
+// Weight p's problem: its own output, or the one the group sums into.
+std::vector<sputnik_hip_spmm_problem> group_problems(const std::vector<SpmmCall>& calls,
+                                                     const std::vector<Tensor>& outs) {
+  std::vector<sputnik_hip_spmm_problem> problems;
+  for (const SpmmCall& c : calls)
+    problems.push_back({c.topo.row_indices.data_ptr<int>(), c.topo.row_offsets.data_ptr<int>(),
+                        c.topo.column_indices.data_ptr<int>(), c.values.data_ptr<float>(),
+                        c.permutation.has_value() ? c.permutation->data_ptr<int>() : nullptr,
+                        c.dense.data_ptr<float>(),
+                        outs[outs.size() == 1 ? 0 : problems.size()].data_ptr<float>(), c.topo.nonzeros});
+  return problems;
+}
+
+// The group's one launch into `outs`.  False: not this group (a weight without entries, or the
+// library turns it down) -- the caller runs it one by one.
+bool group_launch(const char* what, const std::vector<SpmmCall>& calls, const std::vector<Tensor>& outs,
+                  int64_t block_rows, int accumulate) {
+  for (const SpmmCall& c : calls)
+    if (c.topo.nonzeros == 0) return false;
+  const SpmmCall& c = calls[0];
+  const std::vector<sputnik_hip_spmm_problem> problems = group_problems(calls, outs);
+  const int st = sputnik_hip_spmm_group_batched(
+      c.m, c.k, c.n, c.replicas, static_cast<int>(problems.size()), problems.data(),
+      static_cast<int64_t>(c.k) * c.n, static_cast<int64_t>(c.m) * c.n, static_cast<int>(block_rows),
+      accumulate, current_stream(c.dense));
+  if (st == SPUTNIK_HIP_UNSUPPORTED) return false;
+  check_status(st, what);
+  return true;
 }
 
 // One input, several sparse weights, every product stored head split
 // ([B * m / block_rows, n, block_rows] each; block_rows = 0: plain [B, m, n]).
-std::vector<Tensor> left_spmm_group(int64_t m64, int64_t k64, at::TensorList values,
+std::vector<Tensor> left_spmm_group(int64_t m, int64_t k, at::TensorList values,
                                     at::TensorList row_indices, at::TensorList row_offsets,
                                     at::TensorList column_indices, const Tensor& dense,
                                     int64_t block_rows) {
-  const GroupArgs a = check_group(m64, k64, values, {}, row_indices, row_offsets, column_indices,
-                                  {dense}, "left_spmm_group");
-  const c10::DeviceGuard guard(a.dense[0].device());
-  const size_t count = a.values.size();
+  const std::vector<SpmmCall> calls = check_group("left_spmm_group", m, k, values, {}, row_indices,
+                                                  row_offsets, column_indices, {dense});
+  const SpmmCall& c = calls[0];
+  const c10::DeviceGuard guard(c.dense.device());
   std::vector<Tensor> outs;
-  if (sputnik_hip_spmm_group_supported(a.m, a.k, a.n, static_cast<int>(count),
+  if (sputnik_hip_spmm_group_supported(c.m, c.k, c.n, static_cast<int>(calls.size()),
                                        static_cast<int>(block_rows), 0)) {
-    std::vector<sputnik_hip_spmm_problem> problems(count);
-    bool all_nonempty = true;
-    for (size_t p = 0; p < count; ++p) {
+    for (const SpmmCall& each : calls)
       outs.push_back(block_rows > 0
-                         ? at::empty({a.replicas * (a.m / block_rows), a.n, block_rows},
-                                     a.values[p].options())
-                         : at::empty({a.replicas, a.m, a.n}, a.values[p].options()));
-      all_nonempty = all_nonempty && a.topo[p].nonzeros > 0;
-      problems[p] = {a.topo[p].row_indices.data_ptr<int>(), a.topo[p].row_offsets.data_ptr<int>(),
-                     a.topo[p].column_indices.data_ptr<int>(), a.values[p].data_ptr<float>(),
-                     nullptr, a.dense[0].data_ptr<float>(), outs[p].data_ptr<float>(),
-                     a.topo[p].nonzeros};
-    }
-    const int st = !all_nonempty ? SPUTNIK_HIP_UNSUPPORTED
-                                 : sputnik_hip_spmm_group_batched(
-                                       a.m, a.k, a.n, a.replicas, static_cast<int>(count),
-                                       problems.data(), static_cast<int64_t>(a.k) * a.n,
-                                       static_cast<int64_t>(a.m) * a.n,
-                                       static_cast<int>(block_rows), 0,
-                                       current_stream(a.dense[0]));
-    if (st != SPUTNIK_HIP_UNSUPPORTED) {
-      check_status(st, "left_spmm_group");
-      return outs;
-    }
+                         ? at::empty({c.replicas * (c.m / block_rows), c.n, block_rows}, each.values.options())
+                         : at::empty({c.replicas, c.m, c.n}, each.values.options()));
+    if (group_launch("left_spmm_group", calls, outs, block_rows, 0)) return outs;
     outs.clear();
   }
-  for (size_t p = 0; p < count; ++p)   // one by one
-    outs.push_back(spmm_impl(m64, k64, values[p], row_indices[p], row_offsets[p],
-                             column_indices[p], dense, true, "left_spmm_group", c10::nullopt,
-                             false, c10::nullopt, c10::nullopt, block_rows));
+  for (size_t p = 0; p < calls.size(); ++p)   // one by one
+    outs.push_back(spmm_op("left_spmm_group", m, k, values[p], row_indices[p], row_offsets[p],
+                           column_indices[p], dense, true, c10::nullopt, c10::nullopt, block_rows));
   return outs;
 }
 
 // sum over the matrices of  A_p @ dense_p  (values gathered through
 // `permutations` when given): the input gradient of a group of projections.
-Tensor left_spmm_group_sum(int64_t m64, int64_t k64, at::TensorList values,
-                           at::TensorList permutations, at::TensorList row_indices,
-                           at::TensorList row_offsets, at::TensorList column_indices,
-                           at::TensorList dense) {
-  const GroupArgs a = check_group(m64, k64, values, permutations, row_indices, row_offsets,
-                                  column_indices, dense, "left_spmm_group_sum");
-  TORCH_CHECK(a.dense.size() == a.values.size(),
-              "left_spmm_group_sum: one dense operand per matrix");
-  const c10::DeviceGuard guard(a.dense[0].device());
-  const size_t count = a.values.size();
-  if (sputnik_hip_spmm_group_supported(a.m, a.k, a.n, static_cast<int>(count), 0, 1)) {
-    Tensor out = at::empty({a.replicas, a.m, a.n}, a.values[0].options());
-    std::vector<sputnik_hip_spmm_problem> problems(count);
-    bool all_nonempty = true;
-    for (size_t p = 0; p < count; ++p) {
-      all_nonempty = all_nonempty && a.topo[p].nonzeros > 0;
-      problems[p] = {a.topo[p].row_indices.data_ptr<int>(), a.topo[p].row_offsets.data_ptr<int>(),
-                     a.topo[p].column_indices.data_ptr<int>(), a.values[p].data_ptr<float>(),
-                     a.permutations.empty() ? nullptr : a.permutations[p].data_ptr<int>(),
-                     a.dense[p].data_ptr<float>(), out.data_ptr<float>(), a.topo[p].nonzeros};
-    }
-    const int st = !all_nonempty ? SPUTNIK_HIP_UNSUPPORTED
-                                 : sputnik_hip_spmm_group_batched(
-                                       a.m, a.k, a.n, a.replicas, static_cast<int>(count),
-                                       problems.data(), static_cast<int64_t>(a.k) * a.n,
-                                       static_cast<int64_t>(a.m) * a.n, 0, 1,
-                                       current_stream(a.dense[0]));
-    if (st != SPUTNIK_HIP_UNSUPPORTED) {
-      check_status(st, "left_spmm_group_sum");
-      return out;
-    }
+Tensor left_spmm_group_sum(int64_t m, int64_t k, at::TensorList values, at::TensorList permutations,
+                           at::TensorList row_indices, at::TensorList row_offsets,
+                           at::TensorList column_indices, at::TensorList dense) {
+  const std::vector<SpmmCall> calls = check_group("left_spmm_group_sum", m, k, values, permutations,
+                                                  row_indices, row_offsets, column_indices, dense);
+  TORCH_CHECK(dense.size() == values.size(), "left_spmm_group_sum: one dense operand per matrix");
+  const SpmmCall& c = calls[0];
+  const c10::DeviceGuard guard(c.dense.device());
+  if (sputnik_hip_spmm_group_supported(c.m, c.k, c.n, static_cast<int>(calls.size()), 0, 1)) {
+    Tensor out = at::empty({c.replicas, c.m, c.n}, c.values.options());
+    if (group_launch("left_spmm_group_sum", calls, {out}, 0, 1)) return out;
   }
   Tensor total;
-  for (size_t p = 0; p < count; ++p) {   // one by one
-    const Tensor part = spmm_impl(
-        m64, k64, values[p], row_indices[p], row_offsets[p], column_indices[p], dense[p], true,
-        "left_spmm_group_sum", c10::nullopt, false, c10::nullopt,
-        permutations.empty() ? c10::optional<Tensor>() : c10::optional<Tensor>(permutations[p]));
+  for (size_t p = 0; p < calls.size(); ++p) {   // one by one
+    const Tensor part = spmm_op("left_spmm_group_sum", m, k, values[p], row_indices[p], row_offsets[p],
+                                column_indices[p], dense[p], true, calls[p].permutation);
     total = p == 0 ? part : total + part;
   }
   return total;
-}
-
-Tensor left_spmm_permuted(int64_t m, int64_t k, const Tensor& values, const Tensor& permutation,
-                          const Tensor& row_indices, const Tensor& row_offsets,
-                          const Tensor& column_indices, const Tensor& dense,
-                          const c10::optional<Tensor>& plan) {
-  return spmm_impl(m, k, values, row_indices, row_offsets, column_indices, dense, true,
-                   "left_spmm_permuted", c10::nullopt, false, plan, permutation);
-}
-
-Tensor left_spmm(int64_t m, int64_t k, const Tensor& values, const Tensor& row_indices,
-                 const Tensor& row_offsets, const Tensor& column_indices, const Tensor& dense) {
-  return spmm_impl(m, k, values, row_indices, row_offsets, column_indices, dense, true,
-                   "left_spmm");
 }
 
 // left_spmm as a dense contraction on half tiles (sputnik_hip.h: left_spmm_half_tiles):
@@ -829,9 +854,6 @@ Tensor half_linear_input_gradient(int64_t out64, int64_t in64, const Tensor& gra
 bool sddmm_sum_mixed(int m, int n, const Tensor& row_indices, const Tensor& row_offsets,
                      const Tensor& column_indices, const Tensor& lhs_in, const Tensor& rhs_in,
                      const c10::optional<Tensor>& plan, Tensor* result) {
-  const auto is_half = [](const Tensor& t) {
-    return t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16;
-  };
   if (!((lhs_in.scalar_type() == at::kFloat && is_half(rhs_in)) ||
         (rhs_in.scalar_type() == at::kFloat && is_half(lhs_in))))
     return false;
@@ -848,22 +870,14 @@ bool sddmm_sum_mixed(int m, int n, const Tensor& row_indices, const Tensor& row_
       m, k, n, topo.nonzeros, replicas, lhs_code, rhs_code);
   if (scratch_bytes == 0) return false;
   const size_t ws_bytes = sputnik_hip_sddmm_sum_workspace_bytes(m, k, n, topo.nonzeros);
-  Tensor workspace;
-  void* ws = nullptr;
-  if (plan.has_value()) {
-    check_plan(*plan, ws_bytes, lhs);
-    ws = ws_bytes ? plan->data_ptr() : nullptr;
-  } else if (ws_bytes > 0) {
-    workspace = at::empty({static_cast<int64_t>(ws_bytes)}, lhs.options().dtype(at::kByte));
-    ws = workspace.data_ptr();
-  }
-  Tensor scratch = at::empty({static_cast<int64_t>(scratch_bytes)}, lhs.options().dtype(at::kByte));
+  const Workspace ws = plan_or_workspace(plan, ws_bytes, lhs);
+  Tensor scratch = workspace_like(lhs, scratch_bytes);
   Tensor out = at::empty({topo.nonzeros}, lhs.options().dtype(at::kFloat));
   const int status = sputnik_hip_sddmm_sum_mixed(
       m, k, n, topo.nonzeros, replicas, topo.row_indices.data_ptr<int>(),
       topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(), lhs.data_ptr(), lhs_code,
       static_cast<int64_t>(m) * k, rhs.data_ptr(), rhs_code, static_cast<int64_t>(n) * k,
-      out.data_ptr<float>(), ws, ws_bytes, plan.has_value() ? 1 : 0, scratch.data_ptr(),
+      out.data_ptr<float>(), ws.ptr, ws_bytes, ws.planned, scratch.data_ptr(),
       scratch_bytes, current_stream(lhs));
   if (status == SPUTNIK_HIP_UNSUPPORTED) return false;
   check_status(status, "sddmm_sum (float32 x half)");
@@ -920,16 +934,9 @@ Tensor sddmm_impl(int64_t m64, int64_t n64, const Tensor& row_indices, const Ten
   const size_t ws_bytes = sum_replicas
                               ? sputnik_hip_sddmm_sum_workspace_bytes(m, k, n, topo.nonzeros)
                               : sputnik_hip_sddmm_workspace_bytes(m, k, n, topo.nonzeros);
-  Tensor workspace;
-  void* ws = nullptr;
-  if (plan.has_value()) {
-    check_plan(*plan, ws_bytes, lhs);
-    ws = ws_bytes ? plan->data_ptr() : nullptr;
-  } else if (ws_bytes > 0) {
-    workspace = at::empty({static_cast<int64_t>(ws_bytes)}, lhs.options().dtype(at::kByte));
-    ws = workspace.data_ptr();
-  }
-  const int planned = plan.has_value() ? 1 : 0;
+  const Workspace workspace = plan_or_workspace(plan, ws_bytes, lhs);
+  void* const ws = workspace.ptr;
+  const int planned = workspace.planned;
   if (sum_replicas) {
     // sum over the batch inside the call (sputnik_hip.h: sddmm_sum_batched)
     const size_t scratch_bytes =
@@ -984,52 +991,40 @@ Tensor make_plan_tensor(size_t bytes, const Tensor& like) {
                    like.options().dtype(at::kByte));
 }
 
-Tensor spmm_plan(int64_t m64, int64_t k64, int64_t n64, const Tensor& row_indices,
+// The plan of one m-row topology for the sizes (m, a, b), in the library's order ((m, k, n) for
+// the products, (m, n, d) for the attention): `bytes_of` sizes it, `prepass` fills it -- unless
+// `served` is given and says the kernels do not take the shape (the plan is then never read).
+using PlanBytes = size_t (*)(int, int, int, int);
+using PlanServed = int (*)(int, int, int, int);
+using PlanPrepass = int (*)(int, int, int, int, const int*, const int*, const int*, void*, size_t,
+                            sputnik_hip_stream_t);
+
+Tensor make_plan(const char* what, int m, int a, int b, const Tensor& row_indices,
+                 const Tensor& row_offsets, const Tensor& column_indices, PlanBytes bytes_of,
+                 PlanPrepass prepass, PlanServed served = nullptr) {
+  TORCH_CHECK(row_offsets.is_cuda(), "row_offsets must be a GPU (HIP) tensor");
+  const c10::DeviceGuard guard(row_offsets.device());
+  const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, row_offsets);
+  const size_t bytes = bytes_of(m, a, b, topo.nonzeros);
+  Tensor plan = make_plan_tensor(bytes, row_offsets);
+  if (served == nullptr || served(m, a, b, topo.nonzeros))
+    check_status(prepass(m, a, b, topo.nonzeros, topo.row_indices.data_ptr<int>(),
+                         topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(),
+                         bytes ? plan.data_ptr() : nullptr, bytes, current_stream(row_offsets)),
+                 what);
+  return plan;
+}
+
+Tensor spmm_plan(int64_t m, int64_t k, int64_t n, const Tensor& row_indices,
                  const Tensor& row_offsets, const Tensor& column_indices) {
-  const int m = to_int(m64, "m"), k = to_int(k64, "k"), n = to_int(n64, "n");
-  TORCH_CHECK(row_offsets.is_cuda(), "row_offsets must be a GPU (HIP) tensor");
-  const c10::DeviceGuard guard(row_offsets.device());
-  const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, row_offsets);
-  const size_t bytes = sputnik_hip_spmm_workspace_bytes(m, k, n, topo.nonzeros);
-  Tensor plan = make_plan_tensor(bytes, row_offsets);
-  check_status(sputnik_hip_spmm_plan(m, k, n, topo.nonzeros, topo.row_indices.data_ptr<int>(),
-                                     topo.row_offsets.data_ptr<int>(),
-                                     topo.column_indices.data_ptr<int>(),
-                                     bytes ? plan.data_ptr() : nullptr, bytes,
-                                     current_stream(row_offsets)),
-               "spmm_plan");
-  return plan;
+  return make_plan("spmm_plan", to_int(m, "m"), to_int(k, "k"), to_int(n, "n"), row_indices,
+                   row_offsets, column_indices, sputnik_hip_spmm_workspace_bytes, sputnik_hip_spmm_plan);
 }
 
-Tensor spmm_planned(int64_t m, int64_t k, const Tensor& values, const Tensor& row_indices,
-                    const Tensor& row_offsets, const Tensor& column_indices, const Tensor& dense,
-                    const Tensor& plan) {
-  return spmm_impl(m, k, values, row_indices, row_offsets, column_indices, dense, false,
-                   "spmm_planned", c10::nullopt, false, plan);
-}
-
-Tensor left_spmm_planned(int64_t m, int64_t k, const Tensor& values, const Tensor& row_indices,
-                         const Tensor& row_offsets, const Tensor& column_indices,
-                         const Tensor& dense, const Tensor& plan) {
-  return spmm_impl(m, k, values, row_indices, row_offsets, column_indices, dense, true,
-                   "left_spmm_planned", c10::nullopt, false, plan);
-}
-
-Tensor sddmm_plan(int64_t m64, int64_t n64, int64_t k64, const Tensor& row_indices,
+Tensor sddmm_plan(int64_t m, int64_t n, int64_t k, const Tensor& row_indices,
                   const Tensor& row_offsets, const Tensor& column_indices) {
-  const int m = to_int(m64, "m"), n = to_int(n64, "n"), k = to_int(k64, "k");
-  TORCH_CHECK(row_offsets.is_cuda(), "row_offsets must be a GPU (HIP) tensor");
-  const c10::DeviceGuard guard(row_offsets.device());
-  const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, row_offsets);
-  const size_t bytes = sputnik_hip_sddmm_workspace_bytes(m, k, n, topo.nonzeros);
-  Tensor plan = make_plan_tensor(bytes, row_offsets);
-  check_status(sputnik_hip_sddmm_plan(m, k, n, topo.nonzeros, topo.row_indices.data_ptr<int>(),
-                                      topo.row_offsets.data_ptr<int>(),
-                                      topo.column_indices.data_ptr<int>(),
-                                      bytes ? plan.data_ptr() : nullptr, bytes,
-                                      current_stream(row_offsets)),
-               "sddmm_plan");
-  return plan;
+  return make_plan("sddmm_plan", to_int(m, "m"), to_int(k, "k"), to_int(n, "n"), row_indices,
+                   row_offsets, column_indices, sputnik_hip_sddmm_workspace_bytes, sputnik_hip_sddmm_plan);
 }
 
 // Several summed products of one shape in one call: the weight gradients of a group of
@@ -1090,22 +1085,11 @@ std::vector<Tensor> sddmm_sum_group_planned(int64_t m64, int64_t n64,
 }
 
 // the summed product has a plan of its own (sputnik_hip.h: sddmm_sum_plan)
-Tensor sddmm_sum_plan(int64_t m64, int64_t n64, int64_t k64, const Tensor& row_indices,
+Tensor sddmm_sum_plan(int64_t m, int64_t n, int64_t k, const Tensor& row_indices,
                       const Tensor& row_offsets, const Tensor& column_indices) {
-  const int m = to_int(m64, "m"), n = to_int(n64, "n"), k = to_int(k64, "k");
-  TORCH_CHECK(row_offsets.is_cuda(), "row_offsets must be a GPU (HIP) tensor");
-  const c10::DeviceGuard guard(row_offsets.device());
-  const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, row_offsets);
-  const size_t bytes = sputnik_hip_sddmm_sum_workspace_bytes(m, k, n, topo.nonzeros);
-  Tensor plan = make_plan_tensor(bytes, row_offsets);
-  check_status(sputnik_hip_sddmm_sum_plan(m, k, n, topo.nonzeros,
-                                          topo.row_indices.data_ptr<int>(),
-                                          topo.row_offsets.data_ptr<int>(),
-                                          topo.column_indices.data_ptr<int>(),
-                                          bytes ? plan.data_ptr() : nullptr, bytes,
-                                          current_stream(row_offsets)),
-               "sddmm_sum_plan");
-  return plan;
+  return make_plan("sddmm_sum_plan", to_int(m, "m"), to_int(k, "k"), to_int(n, "n"), row_indices,
+                   row_offsets, column_indices, sputnik_hip_sddmm_sum_workspace_bytes,
+                   sputnik_hip_sddmm_sum_plan);
 }
 
 Tensor sddmm_planned(int64_t m, int64_t n, const Tensor& row_indices, const Tensor& row_offsets,
@@ -1368,14 +1352,11 @@ std::vector<Tensor> attention_result(const Tensor& out, const Tensor& lse, bool 
 template <typename Args, typename F, typename FP, typename FD, typename FPD>
 int run_forward(const Args& args, F unplanned, FP planned, FD unplanned_dropout, FPD planned_dropout,
                 const c10::optional<Tensor>& plan, size_t ws_bytes, const Tensor& like, const Drop* drop) {
-  Tensor workspace;
-  if (plan.has_value()) check_plan(*plan, ws_bytes, like);
-  else workspace = at::empty({static_cast<int64_t>(ws_bytes)}, like.options().dtype(at::kByte));
+  const Workspace ws = plan_or_workspace(plan, ws_bytes, like);   // (never empty where the kernels serve)
   const sputnik_hip_stream_t stream = current_stream(like);
   auto with_workspace = [&](auto fresh, auto from_plan, auto... dropout) {
-    return plan.has_value()
-               ? args(from_plan, dropout..., static_cast<const void*>(plan->data_ptr()), ws_bytes, stream)
-               : args(fresh, dropout..., workspace.data_ptr(), ws_bytes, stream);
+    return ws.planned ? args(from_plan, dropout..., static_cast<const void*>(ws.ptr), ws_bytes, stream)
+                      : args(fresh, dropout..., ws.ptr, ws_bytes, stream);
   };
   return drop != nullptr
              ? with_workspace(unplanned_dropout, planned_dropout, drop->p, drop->rng, drop->rng_state_out)
@@ -1470,21 +1451,11 @@ std::vector<Tensor> sparse_attention_with_lse(const Tensor& q, const Tensor& k, 
 
 // Empty plan (numel 0 is never returned; 16 bytes) when the fused kernel does not
 // serve the shape: sparse_attention_planned then composes the three operators.
-Tensor sparse_attention_plan(int64_t m64, int64_t n64, int64_t d64, const Tensor& row_indices,
+Tensor sparse_attention_plan(int64_t m, int64_t n, int64_t d, const Tensor& row_indices,
                              const Tensor& row_offsets, const Tensor& column_indices) {
-  const int m = to_int(m64, "m"), n = to_int(n64, "n"), d = to_int(d64, "d");
-  TORCH_CHECK(row_offsets.is_cuda(), "row_offsets must be a GPU (HIP) tensor");
-  const c10::DeviceGuard guard(row_offsets.device());
-  const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, row_offsets);
-  const size_t bytes = sputnik_hip_sparse_attention_workspace_bytes(m, n, d, topo.nonzeros);
-  Tensor plan = make_plan_tensor(bytes, row_offsets);
-  if (sputnik_hip_sparse_attention_supported(m, n, d, topo.nonzeros))
-    check_status(sputnik_hip_sparse_attention_plan(
-                     m, n, d, topo.nonzeros, topo.row_indices.data_ptr<int>(),
-                     topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(),
-                     plan.data_ptr(), bytes, current_stream(row_offsets)),
-                 "sparse_attention_plan");
-  return plan;
+  return make_plan("sparse_attention_plan", to_int(m, "m"), to_int(n, "n"), to_int(d, "d"),
+                   row_indices, row_offsets, column_indices, sputnik_hip_sparse_attention_workspace_bytes,
+                   sputnik_hip_sparse_attention_plan, sputnik_hip_sparse_attention_supported);
 }
 
 Tensor sparse_attention_planned(const Tensor& q, const Tensor& k, const Tensor& v,
@@ -1787,20 +1758,6 @@ Tensor half_linear_rows(int64_t out64, const Tensor& image, int64_t values_type,
   if (st == SPUTNIK_HIP_UNSUPPORTED) return at::empty({0}, x.options().dtype(out_st));
   check_status(st, "half_linear_rows");
   return y;
-}
-
-Tensor spmm_bias(int64_t m, int64_t k, const Tensor& values, const Tensor& row_indices,
-                 const Tensor& row_offsets, const Tensor& column_indices, const Tensor& bias,
-                 const Tensor& dense) {
-  return spmm_impl(m, k, values, row_indices, row_offsets, column_indices, dense, false,
-                   "spmm_bias", bias, false);
-}
-
-Tensor spmm_bias_relu(int64_t m, int64_t k, const Tensor& values, const Tensor& row_indices,
-                      const Tensor& row_offsets, const Tensor& column_indices,
-                      const Tensor& bias, const Tensor& dense) {
-  return spmm_impl(m, k, values, row_indices, row_offsets, column_indices, dense, false,
-                   "spmm_bias_relu", bias, true);
 }
 
 // ---------------------------------------------------------------------------
@@ -2690,11 +2647,7 @@ Tensor permute_last(const Tensor& values_in, const Tensor& permutation) {
   const Tensor values = as_float(values_in, "values");
   TORCH_CHECK(values.dim() == 1 || values.dim() == 2, "values should have 1 or 2 dimensions, got ",
               values.dim());
-  TORCH_CHECK(permutation.scalar_type() == at::kInt && permutation.dim() == 1 &&
-                  permutation.is_contiguous() && permutation.device() == values.device(),
-              "permutation must be a contiguous int32 vector on ", values.device());
-  TORCH_CHECK(permutation.size(0) == values.size(-1), "permutation has ", permutation.size(0),
-              " entries, values ", values.size(-1));
+  check_permutation(permutation, values.size(-1), values);
   const c10::DeviceGuard guard(values.device());
   const int n = to_int(values.size(-1), "n");
   const int rows = values.dim() == 2 ? to_int(values.size(0), "rows") : 1;
@@ -2929,15 +2882,15 @@ TORCH_LIBRARY(torch_sputnik, m) {
 
 // "CUDA" is the dispatch key of HIP tensors in a ROCm build of PyTorch.
 TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
-  m.impl("spmm", &spmm);
-  m.impl("left_spmm", &left_spmm);
+  m.impl("spmm", &spmm_plain<false>);
+  m.impl("left_spmm", &spmm_plain<true>);
   m.impl("sddmm", &sddmm);
   m.impl("sddmm_narrow", &sddmm_narrow);
   m.impl("sparse_softmax", &sparse_softmax);
   m.impl("csr_transpose", &csr_transpose);
   m.impl("csr_transpose_with_permutation", &csr_transpose_with_permutation);
-  m.impl("spmm_bias", &spmm_bias);
-  m.impl("spmm_bias_relu", &spmm_bias_relu);
+  m.impl("spmm_bias", &spmm_bias<false>);
+  m.impl("spmm_bias_relu", &spmm_bias<true>);
   m.impl("sparse_softmax_scaled", &sparse_softmax_scaled);
   m.impl("sparse_softmax_backward", &sparse_softmax_backward);
   m.impl("sparse_attention", &sparse_attention);
@@ -2946,8 +2899,8 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("sparse_attention_rows", &sparse_attention_rows);
   m.impl("sparse_attention_backward", &sparse_attention_backward);
   m.impl("spmm_plan", &spmm_plan);
-  m.impl("spmm_planned", &spmm_planned);
-  m.impl("left_spmm_planned", &left_spmm_planned);
+  m.impl("spmm_planned", &spmm_planned<false>);
+  m.impl("left_spmm_planned", &spmm_planned<true>);
   m.impl("sddmm_plan", &sddmm_plan);
   m.impl("sddmm_planned", &sddmm_planned);
   m.impl("left_spmm_half_tiles", &left_spmm_half_tiles);
@@ -2990,11 +2943,11 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("sparse_attention_heads_many_mask_dropout", &sparse_attention_heads_many_mask_dropout);
   m.impl("permute_last", &permute_last);
   m.impl("permute_last_banded", &permute_last_banded);
-  m.impl("spmm_permuted", &spmm_permuted);
+  m.impl("spmm_permuted", &spmm_permuted<false>);
   m.impl("spmm_transposed_out", &spmm_transposed_out);
   m.impl("left_spmm_group", &left_spmm_group);
   m.impl("left_spmm_group_sum", &left_spmm_group_sum);
-  m.impl("left_spmm_permuted", &left_spmm_permuted);
+  m.impl("left_spmm_permuted", &spmm_permuted<true>);
   m.impl("transpose_last2", &transpose_last2);
   m.impl("transpose_last2_as", &transpose_last2_as);
 }

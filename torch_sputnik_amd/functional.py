@@ -334,54 +334,23 @@ def _permute_cached(values, perm):
     return ops.permute_last(values, perm)
 
 
-def _transpose(m, n, values, row_offsets, column_indices):
-    """(values_t, row_indices_t, row_offsets_t, column_indices_t)."""
-    values = values.contiguous()
-    if _cache is not None and _cache.serves(row_offsets, column_indices):
-        row_indices_t, row_offsets_t, column_indices_t, perm = _cache.lookup(
-            m, n, row_offsets, column_indices, values)
-        return _permute_cached(values, perm), row_indices_t, row_offsets_t, column_indices_t
-    # a pattern no cache serves: the reference's per-call transpose (asynchronous, one pass)
-    values_t, row_offsets_t, column_indices_t = ops.csr_transpose(
-        m, n, values, row_offsets, column_indices)
-    return values_t, diffsort(row_offsets_t), row_offsets_t, column_indices_t
-
-
-def _spmm_transposed(m, n, values, row_offsets, column_indices, dense, left=False,
-                     block_rows=0):
-    """(A^T) @ dense for the m x n CSR matrix A: with the transposed-topology cache
-    the values stay in A's order and the kernel gathers them through the cached
-    permutation (ops.spmm_permuted); without it the reference's per-call
-    csr_transpose (modules/spmm.py:59-62).  ``block_rows``: the product comes
-    back as ops.spmm_transposed_out stores it, [R * n / block_rows, width, block_rows]."""
-    if _cache is None or not _cache.serves(row_offsets, column_indices):
-        values_t, row_indices_t, row_offsets_t, column_indices_t = _transpose(
-            m, n, values, row_offsets, column_indices)
-        perm = None
-    else:
-        values = values.contiguous()
-        row_indices_t, row_offsets_t, column_indices_t, perm = _cache.lookup(
-            m, n, row_offsets, column_indices, values)
-        if ops.spmm_permuted_fused(n, m, dense.size(-1), perm.numel()):
-            values_t = values          # gathered through `perm` inside the kernel
-        else:
-            values_t, perm = _permute_cached(values, perm), None
-    plan = None if _plans is None else _plans.spmm(n, m, dense.size(-1), row_indices_t,
-                                                   row_offsets_t, column_indices_t)
-    if block_rows:
-        return ops.spmm_transposed_out(n, m, values_t, row_indices_t, row_offsets_t,
-                                       column_indices_t, dense, block_rows, permutation=perm,
-                                       plan=plan, left=left)
-    if perm is not None:
-        return ops.spmm_permuted(n, m, values_t, perm, row_indices_t, row_offsets_t,
-                                 column_indices_t, dense, plan, left=left)
-    return _spmm(n, m, values_t, row_indices_t, row_offsets_t, column_indices_t, dense, left=left)
-
-
-def _spmm(m, k, values, row_indices, row_offsets, column_indices, dense, left=False):
-    """spmm / left_spmm, through the cached plan of the topology when enabled."""
+def _spmm(m, k, values, row_indices, row_offsets, column_indices, dense, left=False, block_rows=0,
+          permutation=None, blocks=0):
+    """THE sparse x dense product of this layer (DESIGN 3.3b): spmm, or left_spmm with ``left``;
+    ``block_rows = d``: stored head split, [R * m/d, n, d] (ops.spmm_transposed_out);
+    ``blocks = d``: the same buffer handed back as its transposed VIEW, [R * m/d, d, n];
+    ``permutation``: the values are in another order of the entries (ops.spmm_permuted).
+    The plan of a static topology is looked up here and nowhere else; which kernel serves the
+    call, and every fallback, is the binding's business."""
     plan = None if _plans is None else _plans.spmm(m, k, dense.size(-1), row_indices, row_offsets,
                                                    column_indices)
+    if block_rows or blocks:
+        out = ops.spmm_transposed_out(m, k, values, row_indices, row_offsets, column_indices, dense,
+                                      block_rows or blocks, permutation=permutation, plan=plan, left=left)
+        return out.transpose(1, 2) if blocks else out
+    if permutation is not None:
+        return ops.spmm_permuted(m, k, values, permutation, row_indices, row_offsets,
+                                 column_indices, dense, plan, left=left)
     if plan is None:
         return (ops.left_spmm if left else ops.spmm)(m, k, values, row_indices, row_offsets,
                                                      column_indices, dense)
@@ -390,13 +359,48 @@ def _spmm(m, k, values, row_indices, row_offsets, column_indices, dense, left=Fa
 
 
 def _linear(m, k, values, row_indices, row_offsets, column_indices, dense, split_rows=0):
-    """left_spmm, optionally with the head-split store (ops.spmm_transposed_out)."""
-    if not split_rows:
-        return _spmm(m, k, values, row_indices, row_offsets, column_indices, dense, left=True)
-    plan = None if _plans is None else _plans.spmm(m, k, dense.size(-1), row_indices,
-                                                   row_offsets, column_indices)
-    return ops.spmm_transposed_out(m, k, values, row_indices, row_offsets, column_indices, dense,
-                                   block_rows=split_rows, plan=plan, left=True)
+    """left_spmm, optionally with the head-split store."""
+    return _spmm(m, k, values, row_indices, row_offsets, column_indices, dense, left=True,
+                 block_rows=split_rows)
+
+
+def _transposed(m, n, values, row_offsets, column_indices, width=None):
+    """The transposed topology of the m x n pattern and the values that go with it:
+    (values, permutation, row_indices_t, row_offsets_t, column_indices_t).  Where the transpose
+    cache serves the pattern the transpose is the cached one and the values are gathered
+    through its permutation -- inside the product's kernel where that serves a dense operand
+    of ``width`` columns (ops.spmm_permuted_fused: the values come back in A's order WITH the
+    permutation), else here (permutation None).  A pattern no cache serves takes the
+    reference's per-call csr_transpose (modules/spmm.py:59-62; asynchronous, one pass).
+    (The attention backwards and the group's input gradient ask another question -- "is the
+    cache ON": they need the permutation itself, served pattern or not -- `_transposed_topology`.)"""
+    values = values.contiguous()
+    if _cache is not None and _cache.serves(row_offsets, column_indices):
+        row_indices_t, row_offsets_t, column_indices_t, perm = _cache.lookup(
+            m, n, row_offsets, column_indices, values)
+        if width is not None and ops.spmm_permuted_fused(n, m, width, perm.numel()):
+            return values, perm, row_indices_t, row_offsets_t, column_indices_t
+        return _permute_cached(values, perm), None, row_indices_t, row_offsets_t, column_indices_t
+    values_t, row_offsets_t, column_indices_t = ops.csr_transpose(
+        m, n, values, row_offsets, column_indices)
+    return values_t, None, diffsort(row_offsets_t), row_offsets_t, column_indices_t
+
+
+def _spmm_transposed(m, n, values, row_offsets, column_indices, dense, left=False, blocks=0):
+    """(A^T) @ dense for the m x n CSR matrix A, [R, n, width]; ``blocks = d``: as the
+    transposed view of the head-split buffer the kernel wrote (`_spmm`), [R * n/d, d, width]."""
+    values_t, perm, *topology_t = _transposed(m, n, values, row_offsets, column_indices,
+                                              width=dense.size(-1))
+    return _spmm(n, m, values_t, *topology_t, dense, left=left, permutation=perm, blocks=blocks)
+
+
+def _incoming(grad_output, m=0, split_rows=0):
+    """The gradient of a product as the backward products read it: contiguous [..., m, n]; with
+    ``split_rows`` from the head-split [B * m/d, n, d] form (free where it arrives as the
+    transposed view of a buffer a kernel wrote that way)."""
+    if split_rows:
+        return _as_transposed(grad_output).reshape(-1, m, grad_output.size(-2))
+    return _contiguous(grad_output)
 
 
 def _sddmm(m, n, row_indices, row_offsets, column_indices, lhs_matrix, rhs_matrix,
@@ -523,24 +527,17 @@ class Spmm(torch.autograd.Function):
         ctx.transposed_out = bool(transposed_out)
         ctx.transposed_grads = bool(transposed_grads)
         ctx.save_for_backward(values, dense)
-        if transposed_out:
-            plan = None if _plans is None else _plans.spmm(m, k, dense.size(-1), row_indices,
-                                                           row_offsets, column_indices)
-            return ops.spmm_transposed_out(m, k, values, row_indices, row_offsets,
-                                           column_indices, dense, block_rows=m, plan=plan)
-        return _spmm(m, k, values, row_indices, row_offsets, column_indices, dense)
+        return _spmm(m, k, values, row_indices, row_offsets, column_indices, dense,
+                     block_rows=m if transposed_out else 0)
 
     @staticmethod
     def backward(ctx, grad_output):
         m, k = ctx.shape
         row_indices, row_offsets, column_indices = ctx.topology
         values, dense = ctx.saved_tensors
-        if ctx.transposed_out:   # [R, n, m] -> the product's own layout
-            grad_output = _as_transposed(grad_output)
-            if dense.dim() == 2:
-                grad_output = grad_output[0]
-        else:
-            grad_output = _contiguous(grad_output)
+        grad_output = _incoming(grad_output, m, ctx.transposed_out)   # [R, n, m] -> the product's own layout
+        if ctx.transposed_out and dense.dim() == 2:
+            grad_output = grad_output[0]
         grad_values = grad_dense = None
         if ctx.needs_input_grad[2]:
             # dL/dA sampled at the pattern: <dC[i,:], B[j,:]>
@@ -548,12 +545,8 @@ class Spmm(torch.autograd.Function):
                                  dense.contiguous())
         if ctx.needs_input_grad[6]:
             # dL/dB = A^T @ dC
-            if ctx.transposed_grads and dense.dim() == 3:
-                grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices,
-                                              grad_output, block_rows=k).transpose(1, 2)
-            else:
-                grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices,
-                                              grad_output)
+            grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices, grad_output,
+                                          blocks=k if ctx.transposed_grads and dense.dim() == 3 else 0)
         return None, None, grad_values, None, None, None, grad_dense, None, None
 
 
@@ -580,23 +573,12 @@ class Sddmm(torch.autograd.Function):
         grad_lhs = grad_rhs = None
         if ctx.needs_input_grad[5]:
             # dL/dlhs = dS @ rhs, dS sparse with the mask's pattern
-            rhs = rhs_matrix.contiguous()
-            if ctx.transposed_grads:
-                plan = None if _plans is None else _plans.spmm(m, n, rhs.size(-1), row_indices,
-                                                               row_offsets, column_indices)
-                grad_lhs = ops.spmm_transposed_out(m, n, grad_output, row_indices, row_offsets,
-                                                   column_indices, rhs, block_rows=m,
-                                                   plan=plan).transpose(1, 2)
-            else:
-                grad_lhs = _spmm(m, n, grad_output, row_indices, row_offsets, column_indices, rhs)
+            grad_lhs = _spmm(m, n, grad_output, row_indices, row_offsets, column_indices,
+                             rhs_matrix.contiguous(), blocks=m if ctx.transposed_grads else 0)
         if ctx.needs_input_grad[6]:
             # dL/drhs = dS^T @ lhs
-            if ctx.transposed_grads:
-                grad_rhs = _spmm_transposed(m, n, grad_output, row_offsets, column_indices,
-                                            lhs_matrix.contiguous(), block_rows=n).transpose(1, 2)
-            else:
-                grad_rhs = _spmm_transposed(m, n, grad_output, row_offsets, column_indices,
-                                            lhs_matrix.contiguous())
+            grad_rhs = _spmm_transposed(m, n, grad_output, row_offsets, column_indices,
+                                        lhs_matrix.contiguous(), blocks=n if ctx.transposed_grads else 0)
         return None, None, None, None, None, grad_lhs, grad_rhs, None
 
 
@@ -616,6 +598,14 @@ def _collect_dense_grad(sink, dense):
             sink.dense_grad = dense
         else:
             sink.dense_grad.add_(dense)
+
+
+def _sink_dense(ctx, grad_output, operand, layout):
+    """While the layer behind ``ctx.dense_grad_sink`` is armed: one ops.dense_weight_grad launch on
+    dy [B, out, S] and the kept operand (``layout`` "bis" / "bsi"), added into its ``dense_grad``."""
+    sink = _armed(ctx.dense_grad_sink)
+    if sink is not None:
+        _collect_dense_grad(sink, ops.dense_weight_grad(grad_output, operand, layout))
 
 
 class SparseLinearFunction(torch.autograd.Function):
@@ -650,30 +640,31 @@ class SparseLinearFunction(torch.autograd.Function):
         m, k = ctx.shape
         row_indices, row_offsets, column_indices = ctx.topology
         values, dense = ctx.saved_tensors
-        if ctx.split_rows:   # [B * m/d, n, d] -> [B, m, n]
-            grad_output = _as_transposed(grad_output).reshape(-1, m, grad_output.size(-2))
-        else:
-            grad_output = _contiguous(grad_output)
+        grad_output = _incoming(grad_output, m, ctx.split_rows)   # [B * m/d, n, d] -> [B, m, n]
         grad_values = grad_dense = None
-        sink = _armed(ctx.dense_grad_sink)
-        if sink is not None:
-            _collect_dense_grad(sink, ops.dense_weight_grad(grad_output, dense, "bis"))
+        _sink_dense(ctx, grad_output, dense, "bis")
         if ctx.needs_input_grad[2]:
             # the [B,nnz] products summed over B (what autograd makes of the
             # reference's result for the shared `values`), inside the call
             grad_values = _sddmm(m, k, row_indices, row_offsets, column_indices, grad_output,
                                  dense.contiguous(), sum_replicas=True)
         if ctx.needs_input_grad[6]:
-            if ctx.dense_blocks:
-                grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices,
-                                              grad_output, left=True,
-                                              block_rows=ctx.dense_blocks).transpose(1, 2)
-            else:
-                grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices,
-                                              grad_output, left=True)
-                if dense.dim() == 2:
-                    grad_dense = grad_dense[0]
+            grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices, grad_output,
+                                          left=True, blocks=ctx.dense_blocks)
+            if not ctx.dense_blocks and dense.dim() == 2:
+                grad_dense = grad_dense[0]
         return None, None, grad_values, None, None, None, grad_dense, None, None, None
+
+
+def _half_input_gradient(m, k, values, row_offsets, column_indices, image, x, grad, planes, plain_grad):
+    """dx [B, S, in] of the half layer's tile routes from dy [B, out, S] (``grad``: in x's type, or
+    its half planes) and the weight's image; where that launch does not serve (bfloat16 tiles with
+    float32 values AND a float32 dy) W^T dy on ``plain_grad`` and the layout pass back to x's type."""
+    grad_x = ops.half_linear_input_gradient(m, k, grad, planes, image, values.dtype, x, x.size(0), x.size(1))
+    if grad_x is None:
+        grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices, plain_grad, left=True)
+        grad_x = ops.transpose_last2(grad_dense, x.dtype)
+    return grad_x
 
 
 class HalfSparseLinearFunction(torch.autograd.Function):
@@ -717,11 +708,10 @@ class HalfSparseLinearFunction(torch.autograd.Function):
     def backward(ctx, grad_output):
         m, k = ctx.shape
         row_indices, row_offsets, column_indices = ctx.topology
-        grad_output = _contiguous(grad_output)
+        grad_output = _incoming(grad_output)
         grad_values = grad_x = None
         if ctx.tiles:
             values, x, image = ctx.saved_tensors
-            batch, seq = x.size(0), x.size(1)
             # dy as planes, once for both gradients (float32 dy), or as it is (dy in x's type)
             planes = grad_output.dtype == torch.float32
             grad = ops.half_planes(grad_output, x.dtype) if planes else grad_output.to(x.dtype)
@@ -735,19 +725,14 @@ class HalfSparseLinearFunction(torch.autograd.Function):
                     grad_values, dense_grad = ops.half_linear_weight_gradient_dense(
                         m, row_offsets, column_indices, grad, planes, x, plan)
                     _collect_dense_grad(sink, dense_grad)
-            elif sink is not None:   # (frozen values: nothing is sampled)
-                _collect_dense_grad(sink, ops.dense_weight_grad(grad_output, x, "bsi"))
+            else:   # (frozen values: nothing is sampled)
+                _sink_dense(ctx, grad_output, x, "bsi")
             if ctx.needs_input_grad[6]:
-                grad_x = ops.half_linear_input_gradient(m, k, grad, planes, image, values.dtype, x, batch, seq)
-                if grad_x is None:   # (bfloat16 tiles with float32 values AND a float32 dy)
-                    grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices, grad_output,
-                                                  left=True)
-                    grad_x = ops.transpose_last2(grad_dense, ctx.in_dtype)
+                grad_x = _half_input_gradient(m, k, values, row_offsets, column_indices, image, x, grad,
+                                              planes, grad_output)
             return None, None, grad_values, None, None, None, grad_x, None
         values, dense = ctx.saved_tensors
-        sink = _armed(ctx.dense_grad_sink)
-        if sink is not None:
-            _collect_dense_grad(sink, ops.dense_weight_grad(grad_output, dense, "bis"))
+        _sink_dense(ctx, grad_output, dense, "bis")
         if ctx.needs_input_grad[2]:
             grad_values = _sddmm(m, k, row_indices, row_offsets, column_indices, grad_output, dense,
                                  sum_replicas=True)
@@ -756,7 +741,7 @@ class HalfSparseLinearFunction(torch.autograd.Function):
             if grad_output.dim() == 3:
                 # W^T dy as a dense contraction on half tiles where that route serves the
                 # shape (the float32 gradient enters as half planes over its range)
-                values_t, _, row_offsets_t, column_indices_t = _transpose(
+                values_t, _, _, row_offsets_t, column_indices_t = _transposed(
                     m, k, values, row_offsets, column_indices)
                 grad_dense = ops.left_spmm_half_tiles(k, m, values_t, row_offsets_t, column_indices_t,
                                                       grad_output, ctx.in_dtype)
@@ -789,17 +774,12 @@ class GroupProjectionFunction(torch.autograd.Function):
     def backward(ctx, *grads):
         m, k, split_rows = ctx.shape
         dense, *values = ctx.saved_tensors
-        n = dense.size(-1)
         live, grad_ys = [], []
         for w, g in enumerate(grads):
             if g is None:
                 continue
-            if split_rows:   # [B * m/d, n, d] -> [B, m, n]
-                g = _as_transposed(g).reshape(-1, m, n)
-            else:
-                g = _contiguous(g)
             live.append(w)
-            grad_ys.append(g)
+            grad_ys.append(_incoming(g, m, split_rows))   # [B * m/d, n, d] -> [B, m, n]
         grad_values = [None] * len(values)
         wanted = [(w, g) for w, g in zip(live, grad_ys) if ctx.needs_input_grad[4 + 4 * w]]
         grouped = (_plans is not None and 2 <= len(wanted) <= 4 and dense.dim() == 3 and dense.is_cuda
@@ -1100,11 +1080,7 @@ class HalfRowLinearFunction(torch.autograd.Function):
             plan = None if _plans is None else _plans.half_linear(m, k, row_offsets, column_indices)
             grad_values = ops.half_linear_weight_gradient(m, row_offsets, column_indices, grad, False, x, plan)
         if ctx.needs_input_grad[6]:
-            grad_x = ops.half_linear_input_gradient(m, k, grad, False, image, values.dtype, x, x.size(0),
-                                                    x.size(1))
-            if grad_x is None:
-                grad_dense = _spmm_transposed(m, k, values, row_offsets, column_indices, grad, left=True)
-                grad_x = ops.transpose_last2(grad_dense, x.dtype)
+            grad_x = _half_input_gradient(m, k, values, row_offsets, column_indices, image, x, grad, False, grad)
         return None, None, grad_values, None, None, None, grad_x
 
 
