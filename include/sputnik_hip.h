@@ -154,6 +154,58 @@ SPUTNIK_HIP_API int sputnik_hip_sddmm_launch_shape(int m, int k, int n, int nonz
                                                    int* panel_width, int* slab_rows, int* passes,
                                                    int* accumulates, int* grid_x, int* grid_y,
                                                    int* grid_z, int* row_blocks);
+/* What a float32 SpMM call of this shape (sputnik_hip_spmm_batched / _bias_batched /
+ * _batched_planned) launches under the current options, down to the kernel instance, its grid
+ * and where its tables lie in the workspace -- when the workspace is as large as
+ * sputnik_hip_spmm_workspace_bytes asks and 16-byte aligned, the dense operand is 16-byte
+ * aligned, the replica strides are multiples of four elements, and `out` is aligned to
+ * `out_alignment` bytes (a power of two from 4; 16 and more: every kernel's rule is met; less:
+ * the 256- / 512-column and the panel kernel are not taken, and the 64-column kernel runs
+ * without its K split).
+ *   family          SPUTNIK_HIP_SPMM_ROWGATHER / _PANEL / _NARROW64 (spmm_tiled64_kernel) /
+ *                   _WIDE256 / _WIDE512 (spmm_tiled_kernel on 256- / 512-column tiles) / _FLAT
+ * For _NARROW64, _WIDE256 and _WIDE512 (0, offsets -1, for the other families):
+ *   tile_cols, tile_rows        the tile of the output a workgroup owns
+ *   waves, rows_per_wave        of a workgroup; tile_rows = waves * rows_per_wave
+ *   chunk                       rows of the dense operand per LDS stage
+ *   sparse, batch               1 and 4 / 8: the short-segment form and the entries of one of its
+ *                               LDS round trips; 0 and 0: the long-segment form (_NARROW64: 0, 0)
+ *   grid_x, grid_y              of the product's launch (_NARROW64: grid_x counts the K splits)
+ *   slots, nchunks, n_tiles     row slots of the chunk table, K chunks, column tiles
+ *   ksplits                     workgroups that share a tile's K walk (_NARROW64; 1: no split,
+ *                               no sum kernel)
+ *   workspace_bytes             sputnik_hip_spmm_workspace_bytes(m, k, n, nonzeros)
+ *   row_ok_offset, table_offset, partials_offset
+ *                               bytes from the workspace's start to this kernel's row order
+ *                               words, its chunk table [nchunks + 1][slots] and the partial tiles
+ *                               [ksplits][m][n] of a K split (-1: none).  The layout depends on
+ *                               the shape and the options alone: a workspace that
+ *                               sputnik_hip_spmm_plan filled (replica count unknown: the tables
+ *                               of every kernel a later call may take, side by side) and one
+ *                               that the call fills for itself hold this kernel's tables at the
+ *                               same offsets.  (_FLAT: table_offset is where its plan starts.)
+ * The call runs the launch path itself and launches nothing; `launch` may be NULL.  Returns
+ * SPUTNIK_HIP_INVALID_ARGUMENT for a call that launches nothing (m, k, n or replicas < 1) or an
+ * out_alignment that is no power of two from 4.  For tests, which assert the instance they mean
+ * to reach. */
+#define SPUTNIK_HIP_SPMM_ROWGATHER 0
+#define SPUTNIK_HIP_SPMM_PANEL 1
+#define SPUTNIK_HIP_SPMM_NARROW64 2
+#define SPUTNIK_HIP_SPMM_WIDE256 3
+#define SPUTNIK_HIP_SPMM_WIDE512 4
+#define SPUTNIK_HIP_SPMM_FLAT 5
+typedef struct sputnik_hip_spmm_launch {
+  int family;
+  int tile_cols, tile_rows, waves, rows_per_wave, chunk;
+  int sparse, batch;
+  int grid_x, grid_y;
+  int slots, nchunks, n_tiles;
+  int ksplits;
+  int64_t workspace_bytes, row_ok_offset, table_offset, partials_offset;
+} sputnik_hip_spmm_launch;
+SPUTNIK_HIP_API int sputnik_hip_spmm_launch_shape(int m, int k, int n, int nonzeros, int replicas,
+                                                  int out_alignment,
+                                                  sputnik_hip_spmm_launch* launch);
 /* The instance of the sparse softmax kernel (softmax.hip) that a call of this shape launches
  * for its first grid slice under the current options: values stored as `dtype`
  * (SPUTNIK_HIP_F32 / F16 / BF16), `backward` != 0 for the gradient.  The class is

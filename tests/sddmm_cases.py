@@ -41,14 +41,15 @@ def dealt_index(slot, slots, per=PER):
     return (slot % per) * (slots // per) + slot // per
 
 
-def slots_of(m):
-    return ceil_div(m, PER) * PER
+def slots_of(m, per=PER):
+    return ceil_div(m, per) * per
 
 
-def slot_rows(row_indices, m):
-    """[slots] the row in every row slot; -1: padding."""
-    slots = slots_of(m)
-    entry = dealt_index(np.arange(slots), slots)
+def slot_rows(row_indices, m, per=PER):
+    """[slots] the row in every row slot; -1: padding.  `per`: the run of slots the rows are dealt
+    in (256 for the SDDMM and the 256- / 512-column SpMM kernels, 128 for the 64-column SpMM)."""
+    slots = slots_of(m, per)
+    entry = dealt_index(np.arange(slots), slots, per)
     rows = np.full(slots, -1, dtype=np.int64)
     rows[entry < m] = np.asarray(row_indices, np.int64)[entry[entry < m]]
     return rows
@@ -75,7 +76,7 @@ def row_ok_ints(slots):
     return ceil_div(4 * slots, 256) * 64
 
 
-def plan_model(row_indices, row_offsets, column_indices, m, n, rows):
+def plan_model(row_indices, row_offsets, column_indices, m, n, rows, per=PER):
     """(row_ok [slots], table [(slabs + 1) * slots], defined [like table]) as
     chunk_table_body<rows> writes them: table[c * slots + slot] = position of the first entry of
     the slot's row in a slab >= c (the row's end if none).  A row is ok iff its columns ascend
@@ -85,7 +86,7 @@ def plan_model(row_indices, row_offsets, column_indices, m, n, rows):
     row whole, from global memory, and no slab reads its table words)."""
     ro = np.asarray(row_offsets, np.int64)
     ci = np.asarray(column_indices, np.int64)
-    srows = slot_rows(row_indices, m)
+    srows = slot_rows(row_indices, m, per)
     slots, slabs = len(srows), ceil_div(n, rows)
     row_ok = np.ones(slots, dtype=np.int32)
     table = np.zeros((slabs + 1, slots), dtype=np.int32)
@@ -114,9 +115,9 @@ def plan_model(row_indices, row_offsets, column_indices, m, n, rows):
     return row_ok, table.reshape(-1), defined.reshape(-1)
 
 
-def workspace_model(row_indices, row_offsets, column_indices, m, n, rows):
+def workspace_model(row_indices, row_offsets, column_indices, m, n, rows, per=PER):
     """(words, defined) of the front of a plan's workspace: row_ok, then the table."""
-    row_ok, table, table_defined = plan_model(row_indices, row_offsets, column_indices, m, n, rows)
+    row_ok, table, table_defined = plan_model(row_indices, row_offsets, column_indices, m, n, rows, per)
     first = row_ok_ints(len(row_ok))
     words = np.zeros(first + len(table), dtype=np.int32)
     defined = np.zeros(len(words), dtype=bool)

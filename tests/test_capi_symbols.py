@@ -67,6 +67,24 @@ def test_sddmm_launch_query_is_host_only():
         ("quad", 256, 64, 2, True)
 
 
+def test_spmm_launch_query_is_host_only():
+    """sputnik_hip_spmm_launch_shape runs the launch path without a device and reports the
+    family and, for the LDS-tiled kernels, the instance, the grid and the workspace offsets:
+    the row gather below the tiled routes' shapes, the flat-stream kernel at the headline shape,
+    the 256-column kernel on 128-row tiles for 16 replicas of 2048 x 2048 x 256."""
+    from torch_sputnik_amd import capi
+    assert "sputnik_hip_spmm_launch_shape" in declared_symbols()
+    assert set(capi.SPMM_FAMILIES) == {"rowgather", "panel", "narrow64", "wide256", "wide512", "flat"}
+    assert capi.spmm_launch_shape(72, 64, 7, 464, 1)["family"] == "rowgather"
+    assert capi.spmm_launch_shape(4096, 4096, 4096, 1677724, 1)["family"] == "flat"
+    shape = capi.spmm_launch_shape(2048, 2048, 256, 838860, 16)
+    bytes_ = capi.spmm_workspace_bytes(2048, 2048, 256, 838860)
+    assert shape == dict(family="wide256", tile_cols=256, tile_rows=128, waves=16, rows_per_wave=8, chunk=64,
+                         sparse=True, batch=8, grid_x=16, grid_y=16, slots=2048, nchunks=32, n_tiles=1,
+                         ksplits=1, workspace_bytes=bytes_, row_ok_offset=0, table_offset=8192,
+                         partials_offset=-1)
+
+
 def test_ops_registered_without_cpu_kernels():
     """The product registers HIP kernels only: CPU tensors must raise."""
     import pytest

@@ -20,9 +20,13 @@ on the operands as stored.
 
 NOT REACHED, by shape rules only (no mask kind is excluded anywhere):
   route                               why the shapes here cannot reach it
-  256-column SpMM, 128-row tile       taken from 192 row-block x column tiles per call
-                                      (spmm_tiled_exec): m = 203 x n = 512 gives 2
+  256-column SpMM, 256-row tile       taken from 192 tiles of 256 x 256 per call (choose_instance,
+                                      spmm_tiled.hip): m = 203 x n = 512 gives 2.  The 128-row
+                                      tile (from 96) IS reached under SPMM_MEDIUM=1.
   512-column SpMM, 128-row tile       taken from 192 tiles per call: 2 x replicas here
+                                      (both tiles, in both forms, run at their edges in
+                                      tests/test_gpu_spmm_instances.py, which takes the replica
+                                      count it needs: 96 replicas of 203 rows, 17 of 1283)
   tiled SDDMM, k % 64 != 0            no panel width divides k: the row-wave kernel serves it
   half SDDMM, half OUTPUT, k = 512    two passes of 256 would round twice: float32 output only
   half pair-flat SDDMM, k >= 256      its rows are 128 or 256 bytes: k = 64 / 128 in half
@@ -35,10 +39,13 @@ NOT REACHED, by shape rules only (no mask kind is excluded anywhere):
                                       replicas, the panel one at n = 264 and nnz >= 32 m
   typed SpMM on widened copies        from nnz * n * replicas >= 2^28: not a small shape
 
-NOT OBSERVABLE through the queries (the variant rests on the knob alone; the name asserted is
-that of the kernel family): the long- / short-segment form and the tile (small / medium) of the
-256-column SpMM kernel, the panel width and the number of accumulating panels of the plain
-SDDMM kernels.  The flat kernel's loop IS named (spmm_flat_kernel<0 / 1 / 2>) and asserted.
+NOT ASSERTED here (the variant rests on the knob alone; the name asserted is that of the kernel
+family): the long- / short-segment form and the tile (small / medium) of the 256-column SpMM
+kernel, the panel width and the number of accumulating panels of the plain SDDMM kernels.  Both
+are observable since -- capi.spmm_launch_shape reports the tile, the form, kBatch, the grid and
+the K split, capi.sddmm_launch_shape the panel and the passes -- and are asserted, instance by
+instance, by tests/test_gpu_spmm_instances.py and tests/test_gpu_sddmm_instances.py.  The flat
+kernel's loop IS named (spmm_flat_kernel<0 / 1 / 2>) and asserted.
 """
 import numpy as np
 import pytest

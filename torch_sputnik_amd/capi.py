@@ -40,6 +40,7 @@ SIGNATURES = {
     "sputnik_hip_sddmm_kernel_name": (ctypes.c_char_p, [_c_int] * 7),
     "sputnik_hip_sddmm_sum_route": (_c_int, [_c_int] * 8 + [_c_ptr] * 5),
     "sputnik_hip_sddmm_launch_shape": (_c_int, [_c_int] * 10 + [_c_ptr] * 9),
+    "sputnik_hip_spmm_launch_shape": (_c_int, [_c_int] * 6 + [_c_ptr]),
     "sputnik_hip_sparse_softmax_route": (_c_int, [_c_int] * 5 + [_c_ptr] * 6),
     "sputnik_hip_reload_options": (None, []),
     "sputnik_hip_spmm": (_c_int, [_c_int] * 4 + [_c_ptr] * 7),
@@ -368,6 +369,35 @@ def sddmm_launch_shape(m, k, n, nonzeros, replicas, dtype=torch.float32, out_dty
                    ("family", "panel_width", "slab_rows", "passes", "accumulates", "grid_x", "grid_y", "grid_z",
                     "row_blocks"), flags=("accumulates",))
     shape["family"] = SDDMM_FAMILIES[shape["family"]]
+    return shape
+
+
+SPMM_FAMILIES = ("rowgather", "panel", "narrow64", "wide256", "wide512", "flat")   # SPUTNIK_HIP_SPMM_*
+
+
+class SpmmLaunch(ctypes.Structure):
+    """sputnik_hip_spmm_launch (include/sputnik_hip.h)."""
+    _fields_ = [(name, _c_int) for name in
+                ("family", "tile_cols", "tile_rows", "waves", "rows_per_wave", "chunk", "sparse", "batch",
+                 "grid_x", "grid_y", "slots", "nchunks", "n_tiles", "ksplits")] + \
+               [(name, _c_i64) for name in
+                ("workspace_bytes", "row_ok_offset", "table_offset", "partials_offset")]
+
+
+def spmm_launch_shape(m, k, n, nonzeros, replicas, out_alignment=16):
+    """What a float32 SpMM call of this shape launches under the current options: a dict of family
+    (one of SPMM_FAMILIES) and, for the LDS-tiled kernels, tile_cols, tile_rows, waves,
+    rows_per_wave, chunk, sparse, batch, grid_x, grid_y, slots, nchunks, n_tiles, ksplits,
+    workspace_bytes and the byte offsets row_ok_offset, table_offset, partials_offset of the
+    kernel's tables in the workspace (include/sputnik_hip.h).  `out_alignment`: bytes the output
+    pointer is aligned to.  Host only."""
+    launch = SpmmLaunch()
+    _check(lib().sputnik_hip_spmm_launch_shape(m, k, n, nonzeros, replicas, out_alignment,
+                                               ctypes.cast(ctypes.pointer(launch), _c_ptr)),
+           "sputnik_hip_spmm_launch_shape")
+    shape = {name: getattr(launch, name) for name, _ in SpmmLaunch._fields_}
+    shape["family"] = SPMM_FAMILIES[shape["family"]]
+    shape["sparse"] = bool(shape["sparse"])
     return shape
 
 

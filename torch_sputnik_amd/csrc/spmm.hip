@@ -17,6 +17,7 @@
 #include "common.h"
 #include "mfma.h"
 #include "options.h"
+#include "spmm_launch.h"
 #include "wave_utils.h"
 
 namespace sputnik_hip {
@@ -28,7 +29,8 @@ int spmm_tiled_exec(int m, int k, int n, int nonzeros, int replicas, const int* 
                     const float* values, int64_t values_stride, const int* row_offsets,
                     const int* column_indices, const float* dense, int64_t dense_stride,
                     float* out, int64_t out_stride, const void* workspace,
-                    size_t workspace_bytes, hipStream_t stream, Epilogue epi, bool* handled);
+                    size_t workspace_bytes, hipStream_t stream, Epilogue epi, bool* handled,
+                    SpmmLaunchShape* shape);
 size_t spmm_tiled_workspace_bytes(int m, int k, int n, int nonzeros);
 int spmm_tiled_choice(int m, int k, int n, int nonzeros, int replicas);
 const char* spmm_tiled_kernel_name(int m, int k, int n, int nonzeros, int replicas);
@@ -374,18 +376,29 @@ int spmm_exec(int m, int k, int n, int nonzeros, int replicas, const int* row_in
               const float* values, int64_t values_stride, const int* row_offsets,
               const int* column_indices, const float* dense, int64_t dense_stride, float* out,
               int64_t out_stride, const void* workspace, size_t workspace_bytes,
-              hipStream_t stream, Epilogue epi) {
+              hipStream_t stream, Epilogue epi, SpmmLaunchShape* shape = nullptr) {
+  // (`shape` != nullptr, the launch query: the same walk, nothing launched, no operand read)
   if (m < 0 || k < 0 || n < 0 || nonzeros < 0 || replicas < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
   if (m == 0 || n == 0 || replicas == 0) return 0;
-  if (takes_panel(m, k, n, nonzeros, replicas, dense, dense_stride, out, out_stride))
+  if (takes_panel(m, k, n, nonzeros, replicas, dense, dense_stride, out, out_stride)) {
+    if (shape != nullptr) {
+      *shape = spmm_launch_shape_of(SPUTNIK_HIP_SPMM_PANEL);
+      return 0;
+    }
     return spmm_panel_launch(m, k, n, nonzeros, replicas, row_indices, values, values_stride,
                              row_offsets, column_indices, dense, dense_stride, out, out_stride,
                              stream, epi);
+  }
   bool handled = false;
   const int st = spmm_tiled_exec(m, k, n, nonzeros, replicas, row_indices, values, values_stride,
                                  row_offsets, column_indices, dense, dense_stride, out,
-                                 out_stride, workspace, workspace_bytes, stream, epi, &handled);
+                                 out_stride, workspace, workspace_bytes, stream, epi, &handled,
+                                 shape);
   if (st != 0 || handled) return st;
+  if (shape != nullptr) {
+    *shape = spmm_launch_shape_of(SPUTNIK_HIP_SPMM_ROWGATHER);
+    return 0;
+  }
   return spmm_rowgather_launch(m, n, replicas, row_indices, values, values_stride, row_offsets,
                                column_indices, dense, dense_stride, out, out_stride, stream, epi);
 }
@@ -446,6 +459,39 @@ const char* sputnik_hip_spmm_kernel_name(int m, int k, int n, int nonzeros, int 
   if (m <= 0 || n <= 0 || replicas <= 0) return "none";
   if (takes_panel(m, k, n, nonzeros, replicas, nullptr, 0, nullptr, 0)) return "spmm_panel64_kernel";
   return spmm_tiled_kernel_name(m, k, n, nonzeros, replicas);
+}
+
+int sputnik_hip_spmm_launch_shape(int m, int k, int n, int nonzeros, int replicas, int out_alignment,
+                                  sputnik_hip_spmm_launch* launch) {
+  if (m <= 0 || k <= 0 || n <= 0 || nonzeros < 0 || replicas <= 0 || out_alignment < 4 ||
+      (out_alignment & (out_alignment - 1)) != 0)
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  // The call's own walk (spmm_exec) on operands that are never read: a workspace of the
+  // size the query asks for at a 256-byte aligned address, contiguous replicas, `out` at an
+  // address with exactly the alignment asked about.
+  const size_t bytes = spmm_tiled_workspace_bytes(m, k, n, nonzeros);
+  const void* workspace = bytes != 0 ? reinterpret_cast<const void*>(uintptr_t{1} << 20) : nullptr;
+  const float* dense = reinterpret_cast<const float*>(uintptr_t{1} << 21);
+  float* out = reinterpret_cast<float*>((uintptr_t{1} << 22) + (out_alignment >= 16 ? 0 : out_alignment));
+  SpmmLaunchShape shape = spmm_launch_shape_of(SPUTNIK_HIP_SPMM_ROWGATHER);
+  const int st = spmm_exec(m, k, n, nonzeros, replicas, nullptr, nullptr, 0, nullptr, nullptr, dense,
+                           static_cast<int64_t>(k) * n, out, static_cast<int64_t>(m) * n, workspace,
+                           bytes, nullptr, Epilogue{}, &shape);
+  if (st != 0) return st;
+  if (launch != nullptr) {
+    launch->family = shape.family;
+    launch->tile_cols = shape.tile_cols, launch->tile_rows = shape.tile_rows;
+    launch->waves = shape.waves, launch->rows_per_wave = shape.rows_per_wave;
+    launch->chunk = shape.chunk, launch->sparse = shape.sparse, launch->batch = shape.batch;
+    launch->grid_x = shape.grid_x, launch->grid_y = shape.grid_y;
+    launch->slots = shape.slots, launch->nchunks = shape.nchunks, launch->n_tiles = shape.n_tiles;
+    launch->ksplits = shape.ksplits;
+    launch->workspace_bytes = static_cast<int64_t>(bytes);
+    launch->row_ok_offset = shape.row_ok_offset;
+    launch->table_offset = shape.table_offset;
+    launch->partials_offset = shape.partials_offset;
+  }
+  return 0;
 }
 
 int sputnik_hip_spmm_permuted_supported(int m, int k, int n, int nonzeros) {

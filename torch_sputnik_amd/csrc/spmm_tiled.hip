@@ -45,6 +45,7 @@
 #include <algorithm>
 
 #include "options.h"
+#include "spmm_launch.h"
 #include "spmm_tiled_common.h"
 
 namespace sputnik_hip {
@@ -58,7 +59,7 @@ int spmm_tiled64_exec(int m, int k, int n, int nonzeros, int replicas, const int
                       const float* values, int64_t values_stride, const int* row_offsets,
                       const int* column_indices, const float* dense, int64_t dense_stride,
                       float* out, int64_t out_stride, const void* workspace,
-                      hipStream_t stream, Epilogue epi);
+                      hipStream_t stream, Epilogue epi, SpmmLaunchShape* shape);
 
 // Flat-stream form of the 128 x 512 tile (spmm_flat.hip).
 bool spmm_flat_applicable(int m, int k, int n, int nonzeros);
@@ -744,12 +745,62 @@ int spmm_tiled_plan(int m, int k, int n, int nonzeros, int replicas, const int* 
   return 0;
 }
 
-// Main kernel on a planned workspace.
+namespace {
+// Which instance of spmm_tiled_kernel serves a call that choose_kernel gave to this file's
+// kernels (`w512`: Kernel::kWide512, else Kernel::kWide): the launch and the launch query
+// (sputnik_hip_spmm_launch_shape) both take it here.
+enum class Tile { kLarge, kMedium, kSmall, kWide512, kWide512Half };
+struct Instance {
+  Tile tile;
+  bool sparse;   // the short-segment form
+};
+inline Instance choose_instance(bool w512, int m, int n, int nonzeros, int replicas, const Plan& plan) {
+  const int force_tile = options().spmm_tile;  // developer knob: 1 = medium, 2 = small tile
+  if (w512) {
+    // 128-row tiles when they give about one workgroup per CU, else 64-row tiles.
+    // The 512-column tile always takes the short-segment variant: its 32-row chunks
+    // hold at most 32 entries of a row, and it measured faster up to density 0.9
+    // (55.3 vs 52.5 TFLOP/s), so the long-segment form is not even built for it.
+    return {tiles512(m, n) * replicas >= kTiles512From && force_tile == 0 ? Tile::kWide512
+                                                                          : Tile::kWide512Half,
+            true};
+  }
+  const int forced = options().spmm_sparse;  // developer knob: 0 / 1 forces the variant
+  // Mean number of entries of a row inside one K chunk picks the variant
+  // (measured cross-over with 64-row chunks, 4096^3 and 2048^3 x 8: density 0.2
+  // short-segment form 7-9 % ahead, 0.25 a tie, 0.3 and above the long-segment form).
+  const bool sparse = forced >= 0 ? forced != 0
+                                  : static_cast<int64_t>(nonzeros) < int64_t{15} * m * plan.nchunks;
+  // Largest tile that still gives about one workgroup per CU (256 CUs).
+  const int blocks = (plan.slots / CfgLarge::kBM) * plan.n_tiles;
+  const int64_t large_blocks = static_cast<int64_t>(blocks) * replicas;
+  const int tile = force_tile ? force_tile : large_blocks >= 192 ? 0 : 2 * large_blocks >= 192 ? 1 : 2;
+  return {tile == 0 ? Tile::kLarge : tile == 1 ? Tile::kMedium : Tile::kSmall, sparse};
+}
+
+template <typename Cfg>
+void describe_launch(SpmmLaunchShape* shape, bool sparse, const Plan& plan, int replicas,
+                     size_t ws_offset) {
+  *shape = spmm_launch_shape_of(Cfg::kBN == 512 ? SPUTNIK_HIP_SPMM_WIDE512 : SPUTNIK_HIP_SPMM_WIDE256);
+  shape->tile_cols = Cfg::kBN, shape->tile_rows = Cfg::kBM, shape->waves = Cfg::kWaves;
+  shape->rows_per_wave = Cfg::kRPW, shape->chunk = Cfg::kBK;
+  shape->sparse = sparse ? 1 : 0, shape->batch = sparse ? Cfg::kBatch : 0;
+  shape->grid_x = (plan.slots / Cfg::kBM) * plan.n_tiles, shape->grid_y = replicas;
+  shape->slots = plan.slots, shape->nchunks = plan.nchunks, shape->n_tiles = plan.n_tiles;
+  shape->ksplits = 1;
+  shape->row_ok_offset = static_cast<int64_t>(ws_offset);
+  shape->table_offset = static_cast<int64_t>(ws_offset + row_ok_bytes(plan.slots));
+}
+}  // namespace
+
+// Main kernel on a planned workspace.  `shape` != nullptr (the launch query): nothing is
+// launched, no operand is read, and what the call would launch is described there.
 int spmm_tiled_exec(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
                     const float* values, int64_t values_stride, const int* row_offsets,
                     const int* column_indices, const float* dense, int64_t dense_stride,
                     float* out, int64_t out_stride, const void* workspace,
-                    size_t workspace_bytes, hipStream_t stream, Epilogue epi, bool* handled) {
+                    size_t workspace_bytes, hipStream_t stream, Epilogue epi, bool* handled,
+                    SpmmLaunchShape* shape) {
   *handled = false;
   const Kernel which = choose_kernel(m, k, n, nonzeros, replicas);
   if (which == Kernel::kNone || workspace == nullptr || !aligned_to(workspace, 16) ||
@@ -763,69 +814,72 @@ int spmm_tiled_exec(int m, int k, int n, int nonzeros, int replicas, const int* 
     return 0;
   if (which == Kernel::kNarrow) {
     const bool both_possible = choose_kernel(m, k, n, nonzeros, -1) == Kernel::kEither;
-    const void* ws64 = both_possible
-                           ? static_cast<const char*>(workspace) + wide_workspace_bytes(m, k, n)
-                           : workspace;
+    const size_t ws64_offset = both_possible ? wide_workspace_bytes(m, k, n) : 0;
+    const void* ws64 = static_cast<const char*>(workspace) + ws64_offset;
     *handled = true;
-    return spmm_tiled64_exec(m, k, n, nonzeros, replicas, row_indices, values, values_stride,
-                             row_offsets, column_indices, dense, dense_stride, out, out_stride,
-                             ws64, stream, epi);
+    const int st = spmm_tiled64_exec(m, k, n, nonzeros, replicas, row_indices, values, values_stride,
+                                     row_offsets, column_indices, dense, dense_stride, out, out_stride,
+                                     ws64, stream, epi, shape);
+    if (shape != nullptr && st == 0) {   // (offsets from the workspace's start)
+      shape->row_ok_offset += static_cast<int64_t>(ws64_offset);
+      shape->table_offset += static_cast<int64_t>(ws64_offset);
+      if (shape->partials_offset >= 0) shape->partials_offset += static_cast<int64_t>(ws64_offset);
+    }
+    return st;
   }
   using Cfg = CfgLarge;
   const bool w512 = which == Kernel::kWide512;
   if (which == Kernel::kFlat) {
     *handled = true;
+    if (shape != nullptr) {
+      *shape = spmm_launch_shape_of(SPUTNIK_HIP_SPMM_FLAT);
+      shape->table_offset = static_cast<int64_t>(flat_offset(m, k, n, nonzeros));   // (its plan)
+      return 0;
+    }
     return spmm_flat_exec(m, k, n, nonzeros, replicas, row_indices, values, values_stride,
                           row_offsets, column_indices, dense, dense_stride, out, out_stride,
                           static_cast<const char*>(workspace) + flat_offset(m, k, n, nonzeros),
                           stream, epi);
   }
   const Plan plan = w512 ? make_plan<CfgWide512>(m, k, n) : make_plan<Cfg>(m, k, n);
-  const char* ws_base =
-      static_cast<const char*>(workspace) + (w512 ? wide512_offset(m, k, n, nonzeros) : 0);
+  const size_t ws_offset = w512 ? wide512_offset(m, k, n, nonzeros) : 0;
+  const char* ws_base = static_cast<const char*>(workspace) + ws_offset;
   const int* row_ok = reinterpret_cast<const int*>(ws_base);
   const int* table = reinterpret_cast<const int*>(ws_base + row_ok_bytes(plan.slots));
 
-  const int blocks = (plan.slots / Cfg::kBM) * plan.n_tiles;
-  const int forced = options().spmm_sparse;  // developer knob: 0 / 1 forces the variant
   const int debug = options().spmm_debug;    // timing experiments only
-  // Mean number of entries of a row inside one K chunk picks the variant
-  // (measured cross-over with 64-row chunks, 4096^3 and 2048^3 x 8: density 0.2
-  // short-segment form 7-9 % ahead, 0.25 a tie, 0.3 and above the long-segment form).
-  // The 512-column tile always takes the short-segment variant: its 32-row chunks
-  // hold at most 32 entries of a row, and it measured faster up to density 0.9
-  // (55.3 vs 52.5 TFLOP/s), so the long-segment form is not even built for it.
-  const bool sparse = w512 ? true
-                      : forced >= 0
-                          ? forced != 0
-                          : static_cast<int64_t>(nonzeros) < int64_t{15} * m * plan.nchunks;
-  const int force_tile = options().spmm_tile;  // developer knob: 1 = medium, 2 = small tile
-  // Largest tile that still gives about one workgroup per CU (256 CUs).
-  const int64_t large_blocks = static_cast<int64_t>(blocks) * replicas;
-  const int tile = force_tile ? force_tile : large_blocks >= 192 ? 0 : 2 * large_blocks >= 192 ? 1 : 2;
-#define SPUTNIK_HIP_LAUNCH_TILED(CFG, SPARSE_)                                                    \
-  hipLaunchKernelGGL((spmm_tiled_kernel<CFG, SPARSE_>),                                           \
-                     dim3((plan.slots / CFG::kBM) * plan.n_tiles, replicas), dim3(CFG::kThreads), \
-                     0, stream, m, k, n, nonzeros, plan.slots, plan.nchunks, plan.n_tiles,        \
-                     row_indices, values, values_stride, column_indices, table, dense,            \
-                     dense_stride, out, out_stride, row_ok, row_offsets, debug, epi)
-  if (w512) {
-    // 128-row tiles when they give about one workgroup per CU, else 64-row tiles
-    if (tiles512(m, n) * replicas >= kTiles512From && force_tile == 0) SPUTNIK_HIP_LAUNCH_TILED(CfgWide512, true);
-    else SPUTNIK_HIP_LAUNCH_TILED(CfgWide512Half, true);
-  } else if (tile == 0) {
-    if (sparse) SPUTNIK_HIP_LAUNCH_TILED(CfgLarge, true);
-    else SPUTNIK_HIP_LAUNCH_TILED(CfgLarge, false);
-  } else if (tile == 1) {
-    if (sparse) SPUTNIK_HIP_LAUNCH_TILED(CfgMedium, true);
-    else SPUTNIK_HIP_LAUNCH_TILED(CfgMedium, false);
-  } else {
-    if (sparse) SPUTNIK_HIP_LAUNCH_TILED(CfgSmall, true);
-    else SPUTNIK_HIP_LAUNCH_TILED(CfgSmall, false);
+  const Instance inst = choose_instance(w512, m, n, nonzeros, replicas, plan);
+#define SPUTNIK_HIP_LAUNCH_TILED(CFG, SPARSE_)                                                      \
+  do {                                                                                              \
+    if (shape != nullptr) {                                                                         \
+      describe_launch<CFG>(shape, SPARSE_, plan, replicas, ws_offset);                              \
+      break;                                                                                        \
+    }                                                                                               \
+    hipLaunchKernelGGL((spmm_tiled_kernel<CFG, SPARSE_>),                                           \
+                       dim3((plan.slots / CFG::kBM) * plan.n_tiles, replicas), dim3(CFG::kThreads), \
+                       0, stream, m, k, n, nonzeros, plan.slots, plan.nchunks, plan.n_tiles,        \
+                       row_indices, values, values_stride, column_indices, table, dense,            \
+                       dense_stride, out, out_stride, row_ok, row_offsets, debug, epi);             \
+  } while (0)
+  switch (inst.tile) {
+    case Tile::kWide512: SPUTNIK_HIP_LAUNCH_TILED(CfgWide512, true); break;
+    case Tile::kWide512Half: SPUTNIK_HIP_LAUNCH_TILED(CfgWide512Half, true); break;
+    case Tile::kLarge:
+      if (inst.sparse) SPUTNIK_HIP_LAUNCH_TILED(CfgLarge, true);
+      else SPUTNIK_HIP_LAUNCH_TILED(CfgLarge, false);
+      break;
+    case Tile::kMedium:
+      if (inst.sparse) SPUTNIK_HIP_LAUNCH_TILED(CfgMedium, true);
+      else SPUTNIK_HIP_LAUNCH_TILED(CfgMedium, false);
+      break;
+    case Tile::kSmall:
+      if (inst.sparse) SPUTNIK_HIP_LAUNCH_TILED(CfgSmall, true);
+      else SPUTNIK_HIP_LAUNCH_TILED(CfgSmall, false);
+      break;
   }
 #undef SPUTNIK_HIP_LAUNCH_TILED
   *handled = true;
-  return launch_status();
+  return shape != nullptr ? 0 : launch_status();
 }
 
 }  // namespace sputnik_hip

@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "options.h"
+#include "spmm_launch.h"
 #include "spmm_tiled_common.h"
 
 namespace sputnik_hip {
@@ -355,19 +356,40 @@ int spmm_tiled64_plan(int m, int k, const int* row_indices, const int* row_offse
   return launch_status();
 }
 
+namespace {
+// Splits of the K walk a call runs: those of ksplits_of for ONE replica whose output the sum
+// kernel can write in 16-byte pieces, 1 otherwise (the launch and the launch query take it here).
+// (debug bit 6: no K split -- the one-workgroup-per-tile form of rounds 1-3)
+inline int launch_splits(int m, int k, int n, int replicas, const float* out, int debug) {
+  return replicas == 1 && !(debug & 64) && aligned_to(out, 16) ? ksplits_of(m, k, n) : 1;
+}
+}  // namespace
+
 int spmm_tiled64_exec(int m, int k, int n, int nonzeros, int replicas, const int* row_indices,
                       const float* values, int64_t values_stride, const int* row_offsets,
                       const int* column_indices, const float* dense, int64_t dense_stride,
                       float* out, int64_t out_stride, const void* workspace,
-                      hipStream_t stream, Epilogue epi) {
+                      hipStream_t stream, Epilogue epi, SpmmLaunchShape* shape) {
   const int slots = slots_of(m);
   const int* row_ok = static_cast<const int*>(workspace);
   const int* table =
       reinterpret_cast<const int*>(static_cast<const char*>(workspace) + row_ok_bytes(slots));
   const int n_tiles = ceil_div(n, kBN);
   const int debug = options().spmm_debug;  // timing experiments only
-  // (debug bit 6: no K split -- the one-workgroup-per-tile form of rounds 1-3)
-  const int splits = replicas == 1 && !(debug & 64) && aligned_to(out, 16) ? ksplits_of(m, k, n) : 1;
+  const int splits = launch_splits(m, k, n, replicas, out, debug);
+  if (shape != nullptr) {   // (the launch query; offsets from `workspace`, this kernel's tables)
+    const int64_t base = 0;
+    *shape = spmm_launch_shape_of(SPUTNIK_HIP_SPMM_NARROW64);
+    shape->tile_cols = kBN, shape->tile_rows = kBM, shape->waves = kWaves;
+    shape->rows_per_wave = kRQ * 4, shape->chunk = kBK;
+    shape->grid_x = (slots / kBM) * n_tiles * splits, shape->grid_y = replicas;
+    shape->slots = slots, shape->nchunks = chunks_of(k), shape->n_tiles = n_tiles;
+    shape->ksplits = splits;
+    shape->row_ok_offset = base;
+    shape->table_offset = base + static_cast<int64_t>(row_ok_bytes(slots));
+    shape->partials_offset = splits > 1 ? base + static_cast<int64_t>(tables_bytes(m, k)) : -1;
+    return 0;
+  }
   float* partials = splits > 1 ? reinterpret_cast<float*>(const_cast<char*>(
                                      static_cast<const char*>(workspace) + tables_bytes(m, k)))
                                : nullptr;
