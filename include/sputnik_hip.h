@@ -1701,6 +1701,87 @@ SPUTNIK_HIP_API int sputnik_hip_csr_regrow_total_launch_shape(int m, int n, int 
                              int* launches);
 
 /* ------------------------------------------------------------------------
+ * Drop-and-grow of a CSR topology under random scores that are never stored
+ * (topology.regrow_per_row_random / regrow_total_random, SparseLinear.set_update): the step of
+ * SET (Mocanu et al. 2018), without an [m, n] array.
+ *
+ * THE RULE.  With the Philox4x32-10 and the state {seed, offset} of "Attention dropout" above
+ * (the offset a multiple of 4), replica = row and entry = column, as in sputnik_hip_random_csr:
+ *   key(r,c) = philox(key (seed lo, seed hi), counter (offset/4 lo, offset/4 hi, c >> 2, r))[c & 3]
+ *              & key_mask                          key_mask <= 0x3fffffff (30 bits); 0x3fffffff in
+ *                                                  use, smaller masks force ties (tests)
+ * A masked key read as float32 bits is a finite, non-negative number, so the clamp of the
+ * regrow rule to the largest finite score never acts: the step is EXACTLY
+ * sputnik_hip_csr_regrow (sputnik_hip_csr_regrow_total) under dense float32 scores whose bit
+ * patterns are key(r, c).  Kept entries, the tie rule (lowest column per row, lowest flat index
+ * matrix-wide), the eligibility of dropped positions, ascending columns, out_source and (matrix-
+ * wide) the row order are those of that contract.  A grown entry's value:
+ *   grow_values = 0   all bits zero (+0.0), as the stored-score steps write it (RigL's choice)
+ *   grow_values = 1   value(r, c) of sputnik_hip_random_csr under scale = grow_scale:
+ *                     float32(int(v[c & 3] >> 8) - 2^23) * grow_scale with v from the value
+ *                     stream (r | 0x80000000 in the counter), rounded to nearest even into
+ *                     `dtype`: uniform on [-bound, bound) for grow_scale = float32(bound / 2^23)
+ *                     (SET re-initialises what it grows)
+ * out_source is -1 for a grown entry either way.
+ *
+ * The arguments are those of sputnik_hip_csr_regrow / sputnik_hip_csr_regrow_total with the
+ * score pointer, width, stride and key limit replaced by the Philox arguments of
+ * sputnik_hip_random_csr, the mask and the grow flag and scale; the values are given by `dtype`
+ * (SPUTNIK_HIP_F32 / F16 / BF16), which says how a grown value is rounded.  `rng_state_out` (may
+ * be NULL), int64 [2], receives the {seed, offset} the call resolved, written by one lane of
+ * one launch (the per-row kernel, the matrix-wide fill; a call without entries launches one lane
+ * for it).  The launches are those of the stored-score steps, the score half instantiated on
+ * generated keys: per row ONE, matrix-wide 8 + value digits + 4.  A key is recomputed per pass
+ * and never stored: per four columns of a row 5 Philox calls per row, 6 matrix-wide, and one
+ * more of the value stream where a piece grows an entry under grow_values = 1.  Nothing is read
+ * back: a call is captured into a graph whole, and with a state that points into the device
+ * generator every replay draws new scores.  `workspace`:
+ * sputnik_hip_csr_regrow_random_workspace_bytes(m, n, nonzeros, total_mode) bytes (0 per row,
+ * sputnik_hip_csr_regrow_total_workspace_bytes matrix-wide), 4-byte aligned.
+ *
+ * SPUTNIK_HIP_INVALID_ARGUMENT: what the stored-score entry returns it for at 4-byte scores (per
+ * row n above 61440; matrix-wide m above 16384 or n above 65536), an unknown dtype, a key_mask
+ * above 0x3fffffff, grow_values != 0 with a grow_scale that is negative or not finite.
+ * ---------------------------------------------------------------------- */
+SPUTNIK_HIP_API int sputnik_hip_csr_regrow_random(int m, int n, int nonzeros, const int* row_offsets,
+                             const int* column_indices, const void* values, int dtype,
+                             const int* drop_counts, sputnik_hip_philox_state rng,
+                             int64_t* rng_state_out, unsigned key_mask, int grow_values,
+                             float grow_scale, void* workspace, size_t workspace_bytes,
+                             int* out_column_indices, void* out_values, int64_t* out_source,
+                             sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_csr_regrow_total_random(int m, int n, int nonzeros, const int* row_offsets,
+                             const int* column_indices, const void* values, int dtype, int64_t drop,
+                             sputnik_hip_philox_state rng, int64_t* rng_state_out, unsigned key_mask,
+                             int grow_values, float grow_scale, void* workspace,
+                             size_t workspace_bytes, int* out_row_indices, int* out_row_offsets,
+                             int* out_column_indices, void* out_values, int64_t* out_source,
+                             sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API size_t sputnik_hip_csr_regrow_random_workspace_bytes(int m, int n, int nonzeros,
+                             int total_mode);
+
+/* The instances the two entries above run: total_mode = 0 reports
+ * sputnik_hip_csr_regrow_launch_shape(m, n, 4, value_bytes), total_mode = 1
+ * sputnik_hip_csr_regrow_total_launch_shape(m, n, nonzeros, 4, value_bytes) -- the walk of
+ * sputnik_hip_dense_to_csr_launch_shape(1, m, n, 4), four generated 32-bit keys per lane and
+ * step, score_digit_passes = 4.
+ *   served     per row: n <= max_n = 61440; matrix-wide: m <= max_m = 16384 and n <= max_n =
+ *              65536 (max_m is -1 per row: no limit of its own); the other fields are -1 where
+ *              the shape is not served
+ *   launches   kernels of one call that publishes its state: per row 1; matrix-wide
+ *              8 + value_digit_passes + 4, and without entries the row order (m > 0) plus the
+ *              lane that publishes the state
+ * Host only, launches nothing; any output pointer may be NULL.  Returns
+ * SPUTNIK_HIP_INVALID_ARGUMENT for a negative size, a value width other than 2 / 4, a
+ * total_mode other than 0 / 1 and m * n above INT_MAX. */
+SPUTNIK_HIP_API int sputnik_hip_csr_regrow_random_launch_shape(int m, int n, int nonzeros, int value_bytes,
+                             int total_mode, int* served, int* rows_per_wave, int* elements_per_lane,
+                             int* rows_per_workgroup, int* value_digit_passes, int* score_digit_passes,
+                             int* lds_bytes, int* max_m, int* max_n, int* grid, int* launches);
+
+/* ------------------------------------------------------------------------
  * Top-k over the entries of a CSR pattern, written out as a smaller CSR pattern
  * (topology.prune_csr, SparseLinear.prune_to): gradual magnitude pruning of a layer that has
  * no dense weight any more.

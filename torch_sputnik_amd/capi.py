@@ -121,6 +121,13 @@ SIGNATURES = {
                                               _c_i64, ctypes.c_uint, _c_ptr, _c_size] + [_c_ptr] * 6),
     "sputnik_hip_csr_regrow_total_workspace_bytes": (_c_size, [_c_int] * 3),
     "sputnik_hip_csr_regrow_total_launch_shape": (_c_int, [_c_int] * 5 + [_c_ptr] * 14),
+    "sputnik_hip_csr_regrow_random": (_c_int, [_c_int] * 3 + [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, PhiloxState, _c_ptr,
+                                               ctypes.c_uint, _c_int, _c_float, _c_ptr, _c_size] + [_c_ptr] * 4),
+    "sputnik_hip_csr_regrow_total_random": (_c_int, [_c_int] * 3 + [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_i64, PhiloxState,
+                                                     _c_ptr, ctypes.c_uint, _c_int, _c_float, _c_ptr, _c_size]
+                                            + [_c_ptr] * 6),
+    "sputnik_hip_csr_regrow_random_workspace_bytes": (_c_size, [_c_int] * 4),
+    "sputnik_hip_csr_regrow_random_launch_shape": (_c_int, [_c_int] * 5 + [_c_ptr] * 11),
     "sputnik_hip_csr_topk": (_c_int, [_c_int] * 3 + [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_int, _c_i64, _c_ptr, _c_size]
                              + [_c_ptr] * 5 + [_c_i64, _c_ptr]),
     "sputnik_hip_csr_topk_workspace_bytes": (_c_size, [_c_int] * 4),
@@ -615,6 +622,26 @@ def csr_regrow_total_workspace_bytes(m, n, nonzeros):
     thresholds, quotas and tie counts, the kept lengths, and 2 * m * ceil(n / 32) words of bit
     planes."""
     return lib().sputnik_hip_csr_regrow_total_workspace_bytes(m, n, nonzeros)
+
+
+def csr_regrow_random_launch_shape(m, n, nonzeros, value_bytes, total):
+    """The instances of the drop-and-grow step under generated scores (SET) for an m x n pattern
+    of `nonzeros` values of that width (2 or 4 bytes), ``total`` (matrix-wide) or per row: a
+    dict of served (bool: per row n <= max_n = 61440; matrix-wide m <= max_m = 16384 and
+    n <= max_n = 65536; the other fields are -1 where it is not), rows_per_wave,
+    elements_per_lane, rows_per_workgroup, value_digit_passes, score_digit_passes (4: 32-bit
+    keys), lds_bytes, max_m (-1 per row), max_n, grid and launches (1 per row, 8 +
+    value_digit_passes + 4 matrix-wide; include/sputnik_hip.h).  Host only; raises for sizes
+    the entry rejects."""
+    return _query("sputnik_hip_csr_regrow_random_launch_shape", (m, n, nonzeros, value_bytes, int(bool(total))),
+                  ("served", "rows_per_wave", "elements_per_lane", "rows_per_workgroup", "value_digit_passes",
+                   "score_digit_passes", "lds_bytes", "max_m", "max_n", "grid", "launches"))
+
+
+def csr_regrow_random_workspace_bytes(m, n, nonzeros, total):
+    """Bytes of workspace one drop-and-grow call under generated scores takes (0 per row, that of
+    ``csr_regrow_total_workspace_bytes`` matrix-wide).  Host only."""
+    return int(lib().sputnik_hip_csr_regrow_random_workspace_bytes(m, n, nonzeros, int(bool(total))))
 
 
 def csr_topk_launch_shape(m, n, nonzeros, value_bytes, total):

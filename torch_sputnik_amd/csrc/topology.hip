@@ -1,7 +1,8 @@
 // CSR topologies from dense masks / matrices, built on the device for gfx950
 // (include/sputnik_hip.h: sputnik_hip_dense_to_csr_*, sputnik_hip_csr_row_order), and the
 // selections that write one out: sputnik_hip_topk_to_csr, sputnik_hip_csr_regrow, sputnik_hip_csr_topk,
-// sputnik_hip_csr_topk_global_*, sputnik_hip_csr_regrow_total, sputnik_hip_random_csr.
+// sputnik_hip_csr_topk_global_*, sputnik_hip_csr_regrow_total, sputnik_hip_random_csr,
+// sputnik_hip_csr_regrow_random, sputnik_hip_csr_regrow_total_random.
 //
 // The build replaces the torch loop of topology.dense_to_sparse_3d (per mask: != 0,
 // to_sparse_csr, two casts, a stable argsort and a host read of the count) by a fixed number of
@@ -1046,15 +1047,18 @@ __device__ __forceinline__ void mark_row_planes(const RowGroup& g, int begin, in
 // columns and those open ones that `grow` selects by their clamped score keys.  admit_ties +
 // group_prefix per step of the score row, as fill_row does; a running group_prefix of the old
 // bits is the old entry index of a kept column, checked against the old row's end before the
-// value is read.
-template <typename S, typename W>
-__device__ __forceinline__ void regrow_fill_row(const RowGroup& g, const RowWalk<S>& walk,
+// value is read.  grown(column) = the bits a grown slot stores; it is called for grown slots only,
+// in ascending column order.
+template <typename Walk, typename W, typename Grown>
+__device__ __forceinline__ void regrow_fill_row(const RowGroup& g, const Walk& walk,
                                                 const unsigned* __restrict__ old_bits,
                                                 const unsigned* __restrict__ kept_bits, int words, Selection grow,
                                                 unsigned key_limit, int begin, int end, int64_t out, int64_t out_end,
                                                 const W* __restrict__ values, int* __restrict__ out_columns,
-                                                W* __restrict__ out_values, int64_t* __restrict__ out_source) {
-  constexpr int V = RowWalk<S>::V;
+                                                W* __restrict__ out_values, int64_t* __restrict__ out_source,
+                                                Grown grown) {
+  using S = typename Walk::Element;
+  constexpr int V = Walk::V;
   int old_seen = 0;    // old columns in the steps behind
   int ties_seen = 0;   // open columns equal to the threshold in the steps behind
   for (int s = 0; s < walk.steps; ++s) {
@@ -1074,7 +1078,10 @@ __device__ __forceinline__ void regrow_fill_row(const RowGroup& g, const RowWalk
       if (((flags >> e) & 1u) && p < out_end) {   // (no store ever leaves the row's slots)
         const bool carried = ((kept >> e) & 1u) && from < end;
         out_columns[p] = static_cast<int>(c0 + e);
-        out_values[p] = carried ? values[from] : W{0};
+        W bits;
+        if (carried) bits = values[from];
+        else bits = grown(c0 + e);
+        out_values[p] = bits;
         out_source[p] = carried ? from : int64_t{-1};
         ++p;
       }
@@ -1085,16 +1092,34 @@ __device__ __forceinline__ void regrow_fill_row(const RowGroup& g, const RowWalk
   }
 }
 
-template <typename S, typename W>
+// The SCORES of a drop-and-grow step, a kernel argument: walk(g, m, n, publish) = the walk of
+// the group's score row, grown<W>(walk) = what a grown slot of that row stores.  Stored scores
+// are a dense matrix in memory and grow zeros; KeyScores (below, next to KeyWalk) are generated.
+template <typename S>
+struct StoredScores {
+  using Walk = RowWalk<S>;
+  const S* scores;
+  int64_t row_stride;
+  __device__ __forceinline__ Walk walk(const RowGroup& g, int m, int n, bool) const {
+    return Walk(g, scores, row_stride, m, n);
+  }
+  template <typename W>
+  __device__ __forceinline__ auto grown(const Walk&) const {
+    return [](int64_t) { return W{0}; };
+  }
+};
+
+template <typename Scores, typename W>
 __global__ __launch_bounds__(kBuildBlock) void csr_regrow_kernel(
     int m, int n, int nonzeros, int rows_per_wave, int words, unsigned key_limit,
     const int* __restrict__ row_offsets, const int* __restrict__ column_indices, const W* __restrict__ values,
-    const int* __restrict__ drop_counts, const S* __restrict__ scores, int64_t row_stride,
-    int* __restrict__ out_columns, W* __restrict__ out_values, int64_t* __restrict__ out_source) {
-  constexpr int PV = sizeof(W) * 8 / kDigitBits, PS = sizeof(S) * 8 / kDigitBits;
+    const int* __restrict__ drop_counts, Scores scores, int* __restrict__ out_columns, W* __restrict__ out_values,
+    int64_t* __restrict__ out_source) {
+  using Walk = typename Scores::Walk;
+  constexpr int PV = sizeof(W) * 8 / kDigitBits, PS = sizeof(typename Walk::Element) * 8 / kDigitBits;
   extern __shared__ unsigned regrow_lds[];   // per row: bins [256], old bits [words], kept bits [words]
   const RowGroup g(rows_per_wave);
-  const RowWalk<S> walk(g, scores, row_stride, m, n);
+  const Walk walk = scores.walk(g, m, n, blockIdx.x == 0 && threadIdx.x == 0);
   unsigned* __restrict__ bins = regrow_lds + g.slot * (kDigitBins + 2 * words);
   unsigned* __restrict__ old_bits = bins + kDigitBins;
   unsigned* __restrict__ kept_bits = old_bits + words;
@@ -1121,18 +1146,17 @@ __global__ __launch_bounds__(kBuildBlock) void csr_regrow_kernel(
 
   // 4: the new row, ascending, into [begin, end)
   regrow_fill_row(g, walk, old_bits, kept_bits, words, grow, key_limit, begin, end, begin, end, values, out_columns,
-                  out_values, out_source);
+                  out_values, out_source, scores.template grown<W>(walk));
 }
 
-template <typename S, typename W>
+template <typename Scores, typename W>
 int launch_regrow(const RegrowShape& r, int m, int n, int nonzeros, const int* row_offsets,
-                  const int* column_indices, const void* values, const int* drop_counts, const void* scores,
-                  int64_t row_stride, unsigned key_limit, int* out_columns, void* out_values,
-                  int64_t* out_source, hipStream_t stream) {
-  hipLaunchKernelGGL((csr_regrow_kernel<S, W>), dim3(r.grid), dim3(kBuildBlock), r.lds_bytes, stream, m, n,
+                  const int* column_indices, const void* values, const int* drop_counts, const Scores& scores,
+                  unsigned key_limit, int* out_columns, void* out_values, int64_t* out_source, hipStream_t stream) {
+  hipLaunchKernelGGL((csr_regrow_kernel<Scores, W>), dim3(r.grid), dim3(kBuildBlock), r.lds_bytes, stream, m, n,
                      nonzeros, r.rows_per_wave, r.words, key_limit, row_offsets, column_indices,
-                     static_cast<const W*>(values), drop_counts, static_cast<const S*>(scores), row_stride,
-                     out_columns, static_cast<W*>(out_values), out_source);
+                     static_cast<const W*>(values), drop_counts, scores, out_columns, static_cast<W*>(out_values),
+                     out_source);
   return launch_status();
 }
 
@@ -1580,13 +1604,15 @@ __global__ __launch_bounds__(kBuildBlock) void regrow_total_planes_kernel(
 }
 
 // One digit pass over the score rows outside the kept columns, keys clamped.
-template <typename S>
+template <typename Scores>
 __global__ __launch_bounds__(kBuildBlock) void regrow_total_hist_kernel(
-    int m, int n, int rows_per_wave, int words, int pass, unsigned count, unsigned key_limit,
-    const S* __restrict__ scores, int64_t row_stride, const unsigned* __restrict__ planes, unsigned* bins) {
-  workgroup_digit_pass<sizeof(S) * 8 / kDigitBits>(pass, count, bins, [&](int shift, unsigned prefix, unsigned* hist) {
+    int m, int n, int rows_per_wave, int words, int pass, unsigned count, unsigned key_limit, Scores scores,
+    const unsigned* __restrict__ planes, unsigned* bins) {
+  using Walk = typename Scores::Walk;
+  constexpr int P = sizeof(typename Walk::Element) * 8 / kDigitBits;
+  workgroup_digit_pass<P>(pass, count, bins, [&](int shift, unsigned prefix, unsigned* hist) {
     const RowGroup g(rows_per_wave);
-    const RowWalk<S> walk(g, scores, row_stride, m, n);
+    const Walk walk = scores.walk(g, m, n, false);
     const RowPlanes row(planes, words, g.row, walk.live);
     digit_histogram(walk, shift, prefix, hist, key_limit,
                     [&](int64_t c0) { return ~plane_bits(row.kept_bits, row.words, c0); });
@@ -1594,13 +1620,13 @@ __global__ __launch_bounds__(kBuildBlock) void regrow_total_hist_kernel(
 }
 
 // out_offsets[row + 1] = the row's kept length + #(open key > T_s), ties[row] = #(open key == T_s).
-template <typename S>
+template <typename Scores>
 __global__ __launch_bounds__(kBuildBlock) void regrow_total_rows_kernel(
-    int m, int n, int rows_per_wave, int words, unsigned count, unsigned key_limit, const S* __restrict__ scores,
-    int64_t row_stride, const unsigned* __restrict__ planes, const int* __restrict__ kept_offsets,
+    int m, int n, int rows_per_wave, int words, unsigned count, unsigned key_limit, Scores scores,
+    const unsigned* __restrict__ planes, const int* __restrict__ kept_offsets,
     const unsigned* __restrict__ bins, int* __restrict__ out_offsets, int* __restrict__ ties) {
   const RowGroup g(rows_per_wave);
-  const RowWalk<S> walk(g, scores, row_stride, m, n);
+  const typename Scores::Walk walk = scores.walk(g, m, n, false);
   const RowPlanes row(planes, words, g.row, walk.live);
   const int kept = walk.live ? kept_offsets[g.row + 1] - kept_offsets[g.row] : 0;
   count_against_total(g, walk, count, bins, key_limit,
@@ -1608,32 +1634,35 @@ __global__ __launch_bounds__(kBuildBlock) void regrow_total_rows_kernel(
                       ties);
 }
 
-// The new rows under the one score threshold and the rows' quotas.
-template <typename S, typename W>
+// The new rows under the one score threshold and the rows' quotas; generated scores publish
+// their state here.
+template <typename Scores, typename W>
 __global__ __launch_bounds__(kBuildBlock) void regrow_total_fill_kernel(
     int m, int n, int nonzeros, int rows_per_wave, int words, unsigned key_limit,
-    const int* __restrict__ row_offsets, const W* __restrict__ values, const S* __restrict__ scores,
-    int64_t row_stride, const unsigned* __restrict__ planes, const unsigned* __restrict__ threshold,
+    const int* __restrict__ row_offsets, const W* __restrict__ values, Scores scores,
+    const unsigned* __restrict__ planes, const unsigned* __restrict__ threshold,
     const int* __restrict__ quotas, const int* __restrict__ out_offsets, int* __restrict__ out_columns,
     W* __restrict__ out_values, int64_t* __restrict__ out_source) {
   const RowGroup g(rows_per_wave);
-  const RowWalk<S> walk(g, scores, row_stride, m, n);
+  const typename Scores::Walk walk = scores.walk(g, m, n, blockIdx.x == 0 && threadIdx.x == 0);
   const RowPlanes row(planes, words, g.row, walk.live);
   int begin, end;
   row_slots(row_offsets, g.row, walk.live, nonzeros, &begin, &end);
   int64_t out, out_end;
   new_slots(out_offsets, g.row, walk.live, nonzeros, &out, &out_end);
   regrow_fill_row(g, walk, row.old_bits, row.kept_bits, row.words, {*threshold, walk.live ? quotas[g.row] : 0},
-                  key_limit, begin, end, out, out_end, values, out_columns, out_values, out_source);
+                  key_limit, begin, end, out, out_end, values, out_columns, out_values, out_source,
+                  scores.template grown<W>(walk));
 }
 
-template <typename S, typename W>
+// `scores` serves the digit passes and the rows launch, `fill_scores` (the same scores, with what
+// a grown slot stores) the fill.
+template <typename Scores, typename FillScores, typename W>
 int launch_regrow_total(const RegrowTotalShape& r, int m, int n, int nonzeros, const int* row_offsets,
-                        const int* column_indices, const void* values_, unsigned drop, const void* scores_,
-                        int64_t row_stride, unsigned key_limit, void* workspace, int* out_offsets, int* out_columns,
-                        void* out_values, int64_t* out_source, hipStream_t stream) {
+                        const int* column_indices, const void* values_, unsigned drop, const Scores& scores,
+                        const FillScores& fill_scores, unsigned key_limit, void* workspace, int* out_offsets,
+                        int* out_columns, void* out_values, int64_t* out_source, hipStream_t stream) {
   const W* values = static_cast<const W*>(values_);
-  const S* scores = static_cast<const S*>(scores_);
   const RegrowTotalWorkspace w(workspace, m);
   const dim3 block(kBuildBlock), grid(r.grid), entry_grid(r.values.rows_grid);
   const unsigned keep = static_cast<unsigned>(nonzeros) - drop;
@@ -1649,14 +1678,14 @@ int launch_regrow_total(const RegrowTotalShape& r, int m, int n, int nonzeros, c
                      r.rows_per_wave, r.words, row_offsets, column_indices, values, w.values.threshold,
                      w.values.quotas(), w.planes);
   for (int p = 0; p < r.score_passes; ++p)
-    hipLaunchKernelGGL((regrow_total_hist_kernel<S>), grid, block, 0, stream, m, n, r.rows_per_wave, r.words, p, drop,
-                       key_limit, scores, row_stride, w.planes, w.scores.bins);
-  hipLaunchKernelGGL((regrow_total_rows_kernel<S>), grid, block, 0, stream, m, n, r.rows_per_wave, r.words, drop,
-                     key_limit, scores, row_stride, w.planes, w.kept_offsets, w.scores.bins, out_offsets,
+    hipLaunchKernelGGL((regrow_total_hist_kernel<Scores>), grid, block, 0, stream, m, n, r.rows_per_wave, r.words, p,
+                       drop, key_limit, scores, w.planes, w.scores.bins);
+  hipLaunchKernelGGL((regrow_total_rows_kernel<Scores>), grid, block, 0, stream, m, n, r.rows_per_wave, r.words, drop,
+                     key_limit, scores, w.planes, w.kept_offsets, w.scores.bins, out_offsets,
                      w.scores.quotas() + m);
   launch_total_scan(w.scores, w.scores.quotas(), m, r.score_passes, drop, out_offsets, true, nullptr, stream);
-  hipLaunchKernelGGL((regrow_total_fill_kernel<S, W>), grid, block, 0, stream, m, n, nonzeros, r.rows_per_wave,
-                     r.words, key_limit, row_offsets, values, scores, row_stride, w.planes, w.scores.threshold,
+  hipLaunchKernelGGL((regrow_total_fill_kernel<FillScores, W>), grid, block, 0, stream, m, n, nonzeros, r.rows_per_wave,
+                     r.words, key_limit, row_offsets, values, fill_scores, w.planes, w.scores.threshold,
                      w.scores.quotas(), out_offsets, out_columns, static_cast<W*>(out_values), out_source);
   return launch_status();
 }
@@ -1854,6 +1883,108 @@ int launch_random(const RandomShape& r, int m, int n, int total_mode, unsigned c
   return launch_status();
 }
 
+// ---------------------------------------------------------------------------
+// Drop-and-grow under random scores that are never stored (sputnik_hip_csr_regrow_random,
+// sputnik_hip_csr_regrow_total_random): SET's step.  The regrow kernels above, instantiated on
+// KeyScores where the RigL step has StoredScores: the score half walks a KeyWalk, so a score key
+// is key(r, c) of the random topology under a mask of at most 30 bits -- read as float32 bits a
+// finite, non-negative number, which the clamp of the regrow rule never touches.  The step is
+// therefore exactly the stored one under dense float32 scores whose bits are the keys.  A key is
+// recomputed per pass: per four columns of a row the per-row kernel makes 5 Philox calls (four
+// digit passes and the fill), the matrix-wide step 6 (four digit launches, rows, fill), plus one
+// of the value stream where a piece grows an entry and the grown entries are initialised.
+//   KeyScores           the walk; a grown slot stores +0.0 (hist and rows launches, and a fill
+//                       that is not asked for values)
+//   KeyScoresOf<T>      a grown slot stores value(r, c) of the random topology in T, drawn once
+//                       per piece of four columns as random_fill_row draws it; `draw` = 0: +0.0
+// The per-row kernel and the matrix-wide fill publish the resolved state.
+// ---------------------------------------------------------------------------
+constexpr unsigned kRegrowKeyMask = 0x3fffffffu;
+
+struct KeyScores {
+  using Walk = KeyWalk;
+  RandomArgs args;
+  int draw;   // grown slots take the value stream (else +0.0)
+  __device__ __forceinline__ Walk walk(const RowGroup& g, int m, int n, bool publish) const {
+    return KeyWalk(g, philox_key(args.state, publish), args.key_mask, m, n);
+  }
+  template <typename W>
+  __device__ __forceinline__ auto grown(const Walk&) const {
+    return [](int64_t) { return W{0}; };
+  }
+};
+
+// random_value with the float32 product held in a register before it is rounded into T.  Left
+// to itself the compiler fuses a multiply and a rounding to float16 into one v_fma_mixlo_f16
+// with a +0.0 addend, which turns a -0.0 product (scale = 0: grow_bound = 0) into +0.0; the
+// rule says one float32 multiply, then one rounding.
+template <typename T>
+__device__ __forceinline__ T grown_value(unsigned word, float scale) {
+  float x = static_cast<float>(static_cast<int>(word >> 8) - (1 << 23)) * scale;
+  asm volatile("" : "+v"(x));
+  return static_cast<T>(x);
+}
+
+// The bits of value(r, c) in T for the grown columns of one row, asked for in ascending order.
+template <typename T, typename W>
+struct GrownValue {
+  static_assert(sizeof(T) == sizeof(W), "the values array is read as W");
+  PhiloxKey key;
+  unsigned row;
+  float scale;
+  bool draw;
+  int64_t drawn;
+  uint4 words;
+  __device__ __forceinline__ W operator()(int64_t column) {
+    if (!draw) return W{0};
+    const int64_t piece = column >> 2;
+    if (piece != drawn) {
+      words = philox4x32_10(key, static_cast<unsigned>(piece), row | 0x80000000u);
+      drawn = piece;
+    }
+    const T x = grown_value<T>(uint4_word(words, static_cast<int>(column & 3)), scale);
+    W bits;
+    __builtin_memcpy(&bits, &x, sizeof(W));
+    return bits;
+  }
+};
+
+template <typename T>
+struct KeyScoresOf : KeyScores {
+  template <typename W>
+  __device__ __forceinline__ GrownValue<T, W> grown(const KeyWalk& walk) const {
+    return GrownValue<T, W>{walk.key, walk.row, args.scale, draw != 0, int64_t{-1}, make_uint4(0u, 0u, 0u, 0u)};
+  }
+};
+
+// f(float{}), f(_Float16{}) or f(__bf16{}) for a checked SPUTNIK_HIP_F32 / F16 / BF16.
+template <typename F>
+inline int by_dtype(int dtype, F f) {
+  return dtype == SPUTNIK_HIP_F32 ? f(float{}) : dtype == SPUTNIK_HIP_F16 ? f(_Float16{}) : f(__bf16{});
+}
+
+inline KeyScores key_scores(const sputnik_hip_philox_state& rng, int64_t* rng_state_out, unsigned key_mask,
+                            int grow_values, float grow_scale) {
+  KeyScores k;
+  k.args.state.rng = rng;
+  k.args.state.rng_state_out = rng_state_out;
+  k.args.state.threshold = 0u;
+  k.args.state.scale = 0.f;
+  k.args.state.replica0 = 0;
+  k.args.key_mask = key_mask;
+  k.args.scale = grow_scale;
+  k.draw = grow_values != 0 ? 1 : 0;
+  return k;
+}
+
+// What both entries check alike: the dtype, the mask, the scale and where the state goes.
+inline bool key_scores_ok(int dtype, unsigned key_mask, int grow_values, float grow_scale,
+                          const int64_t* rng_state_out) {
+  return (dtype == SPUTNIK_HIP_F32 || dtype == SPUTNIK_HIP_F16 || dtype == SPUTNIK_HIP_BF16) &&
+         key_mask <= kRegrowKeyMask && (grow_values == 0 || (grow_scale >= 0.f && grow_scale < INFINITY)) &&
+         (rng_state_out == nullptr || aligned_to(rng_state_out, sizeof(int64_t)));
+}
+
 inline void put(int* p, int v) {
   if (p) *p = v;
 }
@@ -2034,9 +2165,11 @@ int sputnik_hip_csr_regrow(int m, int n, int nonzeros, const int* row_offsets, c
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   return by_width(score_bytes, [&](auto s) {
     return by_width(value_bytes, [&](auto w) {
-      return launch_regrow<decltype(s), decltype(w)>(r, m, n, nonzeros, row_offsets, column_indices, values,
-                                                     drop_counts, scores, scores_row_stride, score_key_limit,
-                                                     out_column_indices, out_values, out_source, stream);
+      using S = decltype(s);
+      const StoredScores<S> stored = {static_cast<const S*>(scores), scores_row_stride};
+      return launch_regrow<StoredScores<S>, decltype(w)>(r, m, n, nonzeros, row_offsets, column_indices, values,
+                                                         drop_counts, stored, score_key_limit, out_column_indices,
+                                                         out_values, out_source, stream);
     });
   });
 }
@@ -2102,10 +2235,11 @@ int sputnik_hip_csr_regrow_total(int m, int n, int nonzeros, const int* row_offs
     return SPUTNIK_HIP_INVALID_ARGUMENT;
   const int st = by_width(score_bytes, [&](auto s) {
     return by_width(value_bytes, [&](auto w) {
-      return launch_regrow_total<decltype(s), decltype(w)>(
-          r, m, n, nonzeros, row_offsets, column_indices, values, static_cast<unsigned>(drop), scores,
-          scores_row_stride, score_key_limit, workspace, out_row_offsets, out_column_indices, out_values, out_source,
-          stream);
+      using S = decltype(s);
+      const StoredScores<S> stored = {static_cast<const S*>(scores), scores_row_stride};
+      return launch_regrow_total<StoredScores<S>, StoredScores<S>, decltype(w)>(
+          r, m, n, nonzeros, row_offsets, column_indices, values, static_cast<unsigned>(drop), stored, stored,
+          score_key_limit, workspace, out_row_offsets, out_column_indices, out_values, out_source, stream);
     });
   });
   if (st != 0) return st;
@@ -2349,6 +2483,135 @@ int sputnik_hip_random_csr(int m, int n, int total_mode, int64_t count, int dtyp
                                row_offsets, column_indices, values, stream);
   if (st != 0 || !total_mode) return st;
   return sputnik_hip_csr_row_order(1, m, n, row_offsets, row_indices, stream_);
+}
+
+int sputnik_hip_csr_regrow_random_launch_shape(int m, int n, int nonzeros, int value_bytes, int total_mode,
+                                               int* served, int* rows_per_wave, int* elements_per_lane,
+                                               int* rows_per_workgroup, int* value_digit_passes,
+                                               int* score_digit_passes, int* lds_bytes, int* max_m, int* max_n,
+                                               int* grid, int* launches) {
+  if ((total_mode != 0 && total_mode != 1) || nonzeros < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  constexpr int key_bytes = static_cast<int>(sizeof(uint32_t));
+  if (total_mode) {
+    const RegrowTotalShape r = regrow_total_shape(m, n, nonzeros, key_bytes, value_bytes);
+    if (r.status != 0) return r.status;
+    put(served, r.served);
+    put(rows_per_wave, r.rows_per_wave);
+    put(elements_per_lane, r.elements_per_lane);
+    put(rows_per_workgroup, r.rows_per_workgroup);
+    put(value_digit_passes, r.value_passes);
+    put(score_digit_passes, r.score_passes);
+    put(lds_bytes, r.lds_bytes);
+    put(max_m, r.max_m);
+    put(max_n, r.max_n);
+    put(grid, r.grid);
+    // (without entries: the row order if there are rows, and the lane that publishes the state)
+    put(launches, r.served ? (m > 0 && nonzeros > 0 ? r.launches : r.launches + 1) : -1);
+    return 0;
+  }
+  const RegrowShape r = regrow_shape(m, n, key_bytes, value_bytes);
+  if (r.status != 0) return r.status;
+  put(served, r.served);
+  put(rows_per_wave, r.rows_per_wave);
+  put(elements_per_lane, r.elements_per_lane);
+  put(rows_per_workgroup, r.rows_per_workgroup);
+  put(value_digit_passes, r.value_passes);
+  put(score_digit_passes, r.score_passes);
+  put(lds_bytes, r.lds_bytes);
+  put(max_m, -1);
+  put(max_n, r.max_n);
+  put(grid, r.grid);
+  put(launches, r.served ? 1 : -1);   // (without entries: the lane that publishes the state)
+  return 0;
+}
+
+size_t sputnik_hip_csr_regrow_random_workspace_bytes(int m, int n, int nonzeros, int total_mode) {
+  return total_mode ? sputnik_hip_csr_regrow_total_workspace_bytes(m, n, nonzeros) : 0;
+}
+
+int sputnik_hip_csr_regrow_random(int m, int n, int nonzeros, const int* row_offsets, const int* column_indices,
+                                  const void* values, int dtype, const int* drop_counts,
+                                  sputnik_hip_philox_state rng, int64_t* rng_state_out, unsigned key_mask,
+                                  int grow_values, float grow_scale, void* workspace, size_t workspace_bytes,
+                                  int* out_column_indices, void* out_values, int64_t* out_source,
+                                  sputnik_hip_stream_t stream_) {
+  if (!key_scores_ok(dtype, key_mask, grow_values, grow_scale, rng_state_out)) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const int value_bytes = dtype == SPUTNIK_HIP_F32 ? 4 : 2;
+  const RegrowShape r = regrow_shape(m, n, static_cast<int>(sizeof(uint32_t)), value_bytes);
+  if (r.status != 0) return r.status;
+  if (!r.served || nonzeros < 0) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const KeyScores keys = key_scores(rng, rng_state_out, key_mask, grow_values, grow_scale);
+  if (m == 0 || nonzeros == 0) return publish_rng_state(keys.args.state, stream);   // no entry, but a state
+  if (row_offsets == nullptr || column_indices == nullptr || drop_counts == nullptr || values == nullptr ||
+      !aligned_to(values, value_bytes) || out_column_indices == nullptr || out_values == nullptr ||
+      !aligned_to(out_values, value_bytes) || out_source == nullptr || !aligned_to(out_source, sizeof(int64_t)) ||
+      !aligned_to(row_offsets, sizeof(int)) || !aligned_to(column_indices, sizeof(int)) ||
+      !aligned_to(drop_counts, sizeof(int)) || !aligned_to(out_column_indices, sizeof(int)))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    KeyScoresOf<T> typed;
+    static_cast<KeyScores&>(typed) = keys;
+    return by_width(value_bytes, [&](auto w) {
+      if constexpr (sizeof(w) == sizeof(T))
+        return launch_regrow<KeyScoresOf<T>, decltype(w)>(r, m, n, nonzeros, row_offsets, column_indices, values,
+                                                          drop_counts, typed, kNoThreshold, out_column_indices,
+                                                          out_values, out_source, stream);
+      else
+        return static_cast<int>(SPUTNIK_HIP_INVALID_ARGUMENT);
+    });
+  });
+}
+
+int sputnik_hip_csr_regrow_total_random(int m, int n, int nonzeros, const int* row_offsets,
+                                        const int* column_indices, const void* values, int dtype, int64_t drop,
+                                        sputnik_hip_philox_state rng, int64_t* rng_state_out, unsigned key_mask,
+                                        int grow_values, float grow_scale, void* workspace, size_t workspace_bytes,
+                                        int* out_row_indices, int* out_row_offsets, int* out_column_indices,
+                                        void* out_values, int64_t* out_source, sputnik_hip_stream_t stream_) {
+  if (!key_scores_ok(dtype, key_mask, grow_values, grow_scale, rng_state_out)) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const int value_bytes = dtype == SPUTNIK_HIP_F32 ? 4 : 2;
+  const RegrowTotalShape r = regrow_total_shape(m, n, nonzeros, static_cast<int>(sizeof(uint32_t)), value_bytes);
+  if (r.status != 0) return r.status;
+  if (!r.served || drop < 0 || drop > nonzeros || out_row_offsets == nullptr ||
+      !aligned_to(out_row_offsets, sizeof(int)) ||
+      (m > 0 && (out_row_indices == nullptr || !aligned_to(out_row_indices, sizeof(int)))))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const KeyScores keys = key_scores(rng, rng_state_out, key_mask, grow_values, grow_scale);
+  if (m == 0 || nonzeros == 0) {
+    // no entries: the zero offsets, the row order 0 .. m - 1 of equal lengths, and the state
+    if (hipMemsetAsync(out_row_offsets, 0, sizeof(int) * (static_cast<size_t>(m) + 1), stream) != hipSuccess)
+      return launch_status();
+    if (m > 0) {
+      const int order = sputnik_hip_csr_row_order(1, m, n, out_row_offsets, out_row_indices, stream_);
+      if (order != 0) return order;
+    }
+    return publish_rng_state(keys.args.state, stream);
+  }
+  if (row_offsets == nullptr || !aligned_to(row_offsets, sizeof(int)) || column_indices == nullptr ||
+      !aligned_to(column_indices, sizeof(int)) || values == nullptr || !aligned_to(values, value_bytes) ||
+      out_column_indices == nullptr || !aligned_to(out_column_indices, sizeof(int)) || out_values == nullptr ||
+      !aligned_to(out_values, value_bytes) || out_source == nullptr || !aligned_to(out_source, sizeof(int64_t)) ||
+      workspace == nullptr || !aligned_to(workspace, sizeof(unsigned)) ||
+      workspace_bytes < sputnik_hip_csr_regrow_total_workspace_bytes(m, n, nonzeros))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const int st = by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    KeyScoresOf<T> typed;
+    static_cast<KeyScores&>(typed) = keys;
+    return by_width(value_bytes, [&](auto w) {
+      if constexpr (sizeof(w) == sizeof(T))
+        return launch_regrow_total<KeyScores, KeyScoresOf<T>, decltype(w)>(
+            r, m, n, nonzeros, row_offsets, column_indices, values, static_cast<unsigned>(drop), keys, typed,
+            kNoThreshold, workspace, out_row_offsets, out_column_indices, out_values, out_source, stream);
+      else
+        return static_cast<int>(SPUTNIK_HIP_INVALID_ARGUMENT);
+    });
+  });
+  if (st != 0) return st;
+  return sputnik_hip_csr_row_order(1, m, n, out_row_offsets, out_row_indices, stream_);
 }
 
 }  // extern "C"

@@ -2228,6 +2228,99 @@ std::vector<Tensor> csr_regrow_total(const Tensor& values_in, const Tensor& row_
   return {out_row_indices, out_row_offsets, out_columns, out_values, source};
 }
 
+// The arguments the two steps under generated scores share (sputnik_hip.h:
+// sputnik_hip_csr_regrow_random): the width of the matrix, the mask and the scale of a grown
+// value (negative: grown entries are +0.0).
+struct KeyStep {
+  int n;
+  unsigned key_mask;
+  int grow_values;
+  float grow_scale;
+};
+KeyStep check_key_step(const char* op, int64_t n, int64_t key_mask, double grow_scale) {
+  check_count(op, "key_mask", key_mask, 0x3fffffff);
+  TORCH_CHECK(!(grow_scale >= 0.0) || grow_scale < std::numeric_limits<float>::infinity(), "torch_sputnik::", op,
+              ": grow_scale must be finite, got ", grow_scale);
+  const bool grow = grow_scale >= 0.0;
+  return {to_int(n, "n"), static_cast<unsigned>(key_mask), grow ? 1 : 0, grow ? static_cast<float>(grow_scale) : 0.f};
+}
+
+// One per-row drop-and-grow step of the CSR pattern of an m x n matrix under random scores that
+// are never stored (sputnik_hip.h: sputnik_hip_csr_regrow_random) -> [column_indices, values,
+// source (int64), rng_state].  The state comes from the device's default generator (draw_state)
+// or replays `rng_state`; grow_scale < 0: grown entries are +0.0, else the value stream under
+// that scale.  One launch, no synchronisation, torch allocations only.
+std::vector<Tensor> csr_regrow_random(const Tensor& values_in, const Tensor& row_offsets_in,
+                                      const Tensor& column_indices_in, const Tensor& drop_counts_in, int64_t n_in,
+                                      double grow_scale, const c10::optional<Tensor>& rng_state, int64_t key_mask) {
+  const char* op = "csr_regrow_random";
+  const CsrValues csr = check_csr_values(op, values_in, row_offsets_in, column_indices_in);
+  const KeyStep step = check_key_step(op, n_in, key_mask, grow_scale);
+  check_index(op, "drop_counts", drop_counts_in, csr.values);
+  TORCH_CHECK(drop_counts_in.numel() == csr.m, "torch_sputnik::csr_regrow_random: drop_counts should be [", csr.m,
+              "], got ", drop_counts_in.sizes());
+  const c10::DeviceGuard guard(csr.values.device());
+  const Tensor drop_counts = drop_counts_in.contiguous();
+  const int m = csr.m, n = step.n, nonzeros = csr.nonzeros;
+  int served = 0;
+  check_status(sputnik_hip_csr_regrow_random_launch_shape(m, n, nonzeros, csr.value_bytes, 0, &served, nullptr,
+                                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                          nullptr, nullptr, nullptr),
+               op);
+  check_served(op, served, "sputnik_hip_csr_regrow_random_launch_shape", "topology.regrow_per_row_random");
+  Tensor out_columns = at::empty_like(csr.column_indices);
+  Tensor out_values = at::empty_like(csr.values);
+  Tensor source = at::empty({static_cast<int64_t>(nonzeros)}, csr.column_indices.options().dtype(at::kLong));
+  const Drop state = draw_state(rng_state, csr.row_offsets);
+  check_status(sputnik_hip_csr_regrow_random(
+                   m, n, nonzeros, csr.row_offsets.data_ptr<int>(), csr.column_indices.data_ptr<int>(),
+                   csr.values.data_ptr(), type_code(csr.values.scalar_type()), drop_counts.data_ptr<int>(), state.rng,
+                   state.rng_state_out, step.key_mask, step.grow_values, step.grow_scale, nullptr, 0,
+                   out_columns.data_ptr<int>(), out_values.data_ptr(), source.data_ptr<int64_t>(),
+                   current_stream(csr.values)),
+               op);
+  return {out_columns, out_values, source, state.rng_state};
+}
+
+// One matrix-wide drop-and-grow step under random scores that are never stored (sputnik_hip.h:
+// sputnik_hip_csr_regrow_total_random) -> [row_indices, row_offsets, column_indices, values,
+// source (int64), rng_state].  No synchronisation, torch allocations only; the workspace is this
+// call's own allocation on the stream's allocator.
+std::vector<Tensor> csr_regrow_total_random(const Tensor& values_in, const Tensor& row_offsets_in,
+                                            const Tensor& column_indices_in, int64_t drop, int64_t n_in,
+                                            double grow_scale, const c10::optional<Tensor>& rng_state,
+                                            int64_t key_mask) {
+  const char* op = "csr_regrow_total_random";
+  const CsrValues csr = check_csr_values(op, values_in, row_offsets_in, column_indices_in);
+  const KeyStep step = check_key_step(op, n_in, key_mask, grow_scale);
+  check_count(op, "drop", drop, csr.nonzeros);
+  const c10::DeviceGuard guard(csr.values.device());
+  const int m = csr.m, n = step.n, nonzeros = csr.nonzeros;
+  int served = 0;
+  check_status(sputnik_hip_csr_regrow_random_launch_shape(m, n, nonzeros, csr.value_bytes, 1, &served, nullptr,
+                                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                          nullptr, nullptr, nullptr),
+               op);
+  check_served(op, served, "sputnik_hip_csr_regrow_random_launch_shape", "topology.regrow_total_random");
+  const auto index_options = csr.row_offsets.options();
+  Tensor out_row_indices = at::empty({m}, index_options);
+  Tensor out_row_offsets = at::empty({m + 1}, index_options);
+  Tensor out_columns = at::empty({nonzeros}, index_options);
+  Tensor out_values = at::empty_like(csr.values);
+  Tensor source = at::empty({nonzeros}, index_options.dtype(at::kLong));
+  const Drop state = draw_state(rng_state, csr.row_offsets);
+  const size_t ws_bytes = sputnik_hip_csr_regrow_random_workspace_bytes(m, n, nonzeros, 1);
+  Tensor workspace = workspace_like(csr.values, ws_bytes);
+  check_status(sputnik_hip_csr_regrow_total_random(
+                   m, n, nonzeros, csr.row_offsets.data_ptr<int>(), csr.column_indices.data_ptr<int>(),
+                   csr.values.data_ptr(), type_code(csr.values.scalar_type()), drop, state.rng, state.rng_state_out,
+                   step.key_mask, step.grow_values, step.grow_scale, workspace.data_ptr(), ws_bytes,
+                   out_row_indices.data_ptr<int>(), out_row_offsets.data_ptr<int>(), out_columns.data_ptr<int>(),
+                   out_values.data_ptr(), source.data_ptr<int64_t>(), current_stream(csr.values)),
+               op);
+  return {out_row_indices, out_row_offsets, out_columns, out_values, source, state.rng_state};
+}
+
 // The CSR pattern (row_offsets [m + 1], column_indices [nnz]) with `values` [nnz] -> [row_indices,
 // row_offsets, column_indices, values, source (int64)] of its `total` entries of largest |value|,
 // or of the `per_row` largest of every row (the other one -1): sputnik_hip.h:
@@ -2826,6 +2919,10 @@ TORCH_LIBRARY(torch_sputnik, m) {
         "Tensor scores) -> Tensor[]");
   m.def("csr_regrow_total(Tensor values, Tensor row_offsets, Tensor column_indices, int drop, "
         "Tensor scores) -> Tensor[]");
+  m.def("csr_regrow_random(Tensor values, Tensor row_offsets, Tensor column_indices, Tensor drop_counts, int n, "
+        "float grow_scale, Tensor? rng_state, int key_mask) -> Tensor[]");
+  m.def("csr_regrow_total_random(Tensor values, Tensor row_offsets, Tensor column_indices, int drop, int n, "
+        "float grow_scale, Tensor? rng_state, int key_mask) -> Tensor[]");
   m.def("csr_topk(Tensor values, Tensor row_offsets, Tensor column_indices, int per_row, int total) -> Tensor[]");
   m.def("csr_topk_global(Tensor[] values, Tensor[] row_offsets, Tensor[] column_indices, int total) -> Tensor[]");
   m.def(
@@ -2931,6 +3028,8 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("topk_to_csr", &topk_to_csr);
   m.impl("csr_regrow", &csr_regrow);
   m.impl("csr_regrow_total", &csr_regrow_total);
+  m.impl("csr_regrow_random", &csr_regrow_random);
+  m.impl("csr_regrow_total_random", &csr_regrow_total_random);
   m.impl("csr_topk", &csr_topk);
   m.impl("csr_topk_global", &csr_topk_global);
   m.impl("sparse_attention_many_mask", &sparse_attention_many_mask);

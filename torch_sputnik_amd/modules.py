@@ -181,8 +181,9 @@ class SparseLinear(nn.Module):
         2. ``d`` entries are grown where ``|grow_scores|`` (``[out, in]``, e.g. the magnitude of
            the dense weight gradient, RigL) is largest outside the kept positions, ties to the
            lower flat index; non-finite scores count as the largest finite value;
-           ``grow_scores=None`` draws uniform random scores with ``generator`` (SET).  Positions
-           dropped in step 1 are eligible.
+           ``grow_scores=None`` draws uniform random scores with ``generator`` (SET) into an
+           ``[out, in]`` float32 array -- ``set_update`` is SET's step without that array.
+           Positions dropped in step 1 are eligible.
         3. The new values are written INTO the existing ``values`` Parameter -- an optimizer
            keeps its handle -- kept ones bit for bit, grown ones exactly 0.  The index tensors
            are replaced by new ones (the old ones are unregistered, never written to), so no
@@ -247,6 +248,59 @@ class SparseLinear(nn.Module):
         self._install_topology(new_values, self.row_indices.clone(), self.row_offsets.clone(), column_indices,
                                into_parameter=True)
         return source
+
+    @torch.no_grad()
+    def set_update(self, drop_fraction, per_row=False, grow_bound=None, rng_state=None, return_rng_state=False):
+        """One SET step (Mocanu et al. 2018) without a dense tensor: ``update_topology(drop_fraction,
+        grow_scores=None, per_row=per_row)`` with the random grow scores computed where they are
+        compared instead of drawn into an ``[out, in]`` array.  The drop counts, the shortcuts
+        (``d == 0``, ``floor(in_features * drop_fraction) == 0``: nothing changes, ``source =
+        arange(nnz)``, no state is drawn), the error messages, the kept entries, the ties and
+        the installation -- the new values INTO the ``values`` Parameter, new index tensors --
+        are those of ``update_topology``.
+
+        The scores are Philox keys of 30 bits, ``topology.regrow_total_random`` /
+        ``regrow_per_row_random`` state the rule: the step is exactly ``update_topology`` under
+        float32 ``grow_scores`` whose bits are those keys.  ``grow_bound=None`` grows entries of
+        exactly 0 as ``update_topology`` does; a finite ``grow_bound >= 0`` re-initialises them
+        uniformly on ``[-grow_bound, grow_bound)`` as ``SparseLinear.random(bound=)`` would have
+        drawn those positions (SET as published).  On a GPU module the step runs on the layer's
+        own arrays: a fixed number of launches, no host synchronisation, and the state comes
+        from the device's default generator (``torch.manual_seed``); ``rng_state`` (int64 [2])
+        reproduces a step, on any device.
+
+        Returns ``source`` as ``update_topology`` does, and ``(source, rng_state)`` with
+        ``return_rng_state`` (``rng_state`` is None where a shortcut drew nothing)."""
+        values = self.values.detach()
+        nnz, n = values.numel(), self.input_features
+        unchanged = None
+        if per_row:
+            if not 0.0 <= drop_fraction <= 1.0:
+                raise ValueError(f"update_topology: drop_fraction {drop_fraction} is outside 0 .. 1")
+            # len_r <= in_features is known on the host; the lengths themselves are not read back
+            if math.floor(float(n) * drop_fraction) == 0:
+                unchanged = torch.arange(nnz, dtype=torch.int64, device=values.device)
+        else:
+            d = int(drop_fraction * nnz)
+            if not 0 <= d <= nnz:
+                raise ValueError(f"update_topology: drop_fraction {drop_fraction} is outside 0 .. 1")
+            if d == 0:
+                unchanged = torch.arange(nnz, dtype=torch.int64, device=values.device)
+        if unchanged is not None:
+            return (unchanged, None) if return_rng_state else unchanged
+        if per_row:
+            lengths = self.row_offsets[1:] - self.row_offsets[:-1]
+            drop_counts = torch.floor(lengths.to(torch.float64) * drop_fraction).to(torch.int32)
+            column_indices, new_values, source, state = topology.regrow_per_row_random(
+                values, self.row_offsets, self.column_indices, drop_counts, n, grow_bound=grow_bound,
+                rng_state=rng_state, return_rng_state=True)
+            row_indices, row_offsets = self.row_indices.clone(), self.row_offsets.clone()
+        else:
+            row_indices, row_offsets, column_indices, new_values, source, state = topology.regrow_total_random(
+                values, self.row_offsets, self.column_indices, d, n, grow_bound=grow_bound, rng_state=rng_state,
+                return_rng_state=True)
+        self._install_topology(new_values, row_indices, row_offsets, column_indices, into_parameter=True)
+        return (source, state) if return_rng_state else source
 
     @torch.no_grad()
     def prune_to(self, density=None, nonzeros=None, per_row=False):

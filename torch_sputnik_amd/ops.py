@@ -515,6 +515,100 @@ def csr_regrow_total(values, row_offsets, column_indices, drop, scores):
     return tuple(_ops.csr_regrow_total(values, row_offsets, column_indices, count, scores))
 
 
+REGROW_KEY_MASK = 0x3fffffff
+
+
+def _check_key_step(op, values, n, grow_bound, rng_state, key_mask):
+    """ValueError unless ``n`` is a width, ``key_mask`` lies in 0 .. 0x3fffffff, ``grow_bound`` is
+    None or a finite number >= 0 and ``rng_state`` is None or int64 [2].  -> (the grow scale the
+    binding takes: ``random_value_scale(grow_bound)``, -1.0 for None; the state on the values'
+    device)"""
+    if int(n) < 0:
+        raise ValueError(f"{op}: expected n >= 0, got {int(n)}")
+    if not 0 <= int(key_mask) <= REGROW_KEY_MASK:
+        raise ValueError(f"{op}: key_mask {key_mask} is outside 0 .. 0x3fffffff")
+    if grow_bound is not None and not 0.0 <= float(grow_bound) < float("inf"):
+        raise ValueError(f"{op}: grow_bound {grow_bound} should be None or a finite number >= 0")
+    if rng_state is not None and (rng_state.dtype != torch.int64 or rng_state.numel() != 2):
+        raise ValueError(f"{op}: rng_state must be an int64 [2] tensor {{seed, offset}}")
+    if rng_state is not None:
+        rng_state = rng_state.to(values.device).contiguous()
+    return -1.0 if grow_bound is None else random_value_scale(grow_bound), rng_state
+
+
+def check_regrow_random_arguments(values, row_offsets, column_indices, drop_counts, n, grow_bound=None,
+                                  rng_state=None, key_mask=REGROW_KEY_MASK):
+    """ValueError unless the four tensors are one CSR pattern of ``m = row_offsets.numel() - 1``
+    rows with its values and drop counts (shapes, int32 indices, one device) and the other
+    arguments are those of a step under generated scores.  -> (grow scale, rng_state)"""
+    op = "csr_regrow_random"
+    _check_csr_pattern(op, values, row_offsets, column_indices)
+    m = row_offsets.numel() - 1
+    if drop_counts.dtype != torch.int32 or drop_counts.dim() != 1 or drop_counts.numel() != m:
+        raise ValueError(f"{op}: drop_counts should be int32 [{m}], got {drop_counts.dtype} {tuple(drop_counts.shape)}")
+    if drop_counts.device != values.device:
+        raise ValueError(f"{op}: drop_counts is on {drop_counts.device}, values on {values.device}")
+    return _check_key_step(op, values, n, grow_bound, rng_state, key_mask)
+
+
+def csr_regrow_random(values, row_offsets, column_indices, drop_counts, n, grow_bound=None, rng_state=None,
+                      key_mask=REGROW_KEY_MASK):
+    """One per-row drop-and-grow step of the CSR pattern of an ``m x n`` matrix under random grow
+    scores that are never stored (csrc/topology.hip): SET's step.  For ``rng_state = {seed,
+    offset}`` (offset a multiple of 4), with Philox4x32-10, ``key(r, c) = Philox(seed, (offset / 4,
+    c >> 2, r))[c & 3] & key_mask`` -- the key stream of ``random_csr``, under a mask of at most
+    30 bits (``REGROW_KEY_MASK``), so that a key read as float32 bits is finite and non-negative
+    and the clamp of the regrow rule never acts.  The step is EXACTLY ``csr_regrow`` under dense
+    float32 scores whose bits are the keys: kept entries, ties (lowest column), eligibility of
+    dropped columns, ascending columns and ``source`` are its.  A grown entry is ``+0.0``
+    (``grow_bound=None``; RigL's choice) or the value ``random_csr`` gives that position under
+    ``bound = grow_bound``: ``float32((word' >> 8) - 2**23) * float32(grow_bound / 2**23)`` from
+    the value stream, rounded to nearest even into the values' dtype (SET re-initialises what it
+    grows); its ``source`` is -1 either way.
+    -> (column_indices, values, source, rng_state); ``rng_state`` (int64 [2]) is what the call
+    drew from the device's default generator (4 of its offset; ``torch.manual_seed`` makes runs
+    repeat; a captured call draws new scores per replay), or the one given, which reproduces the
+    call that returned it.  One launch, 5 Philox calls per four columns of a row, no ``[m, n]``
+    array, no host synchronisation.  Raises for CPU tensors and for ``n`` beyond
+    ``capi.csr_regrow_random_launch_shape(...)["max_n"]`` (61440)."""
+    scale, rng_state = check_regrow_random_arguments(values, row_offsets, column_indices, drop_counts, n, grow_bound,
+                                                     rng_state, key_mask)
+    _device_floats("csr_regrow_random", "topology.regrow_per_row_random", values=values)
+    return tuple(_ops.csr_regrow_random(values, row_offsets, column_indices, drop_counts, int(n), scale, rng_state,
+                                        int(key_mask)))
+
+
+def check_regrow_total_random_arguments(values, row_offsets, column_indices, drop, n, grow_bound=None,
+                                        rng_state=None, key_mask=REGROW_KEY_MASK):
+    """ValueError unless the three tensors are one CSR pattern with its values (shapes, int32
+    indices, one device), ``drop`` is a count within 0 .. nnz and the other arguments are those
+    of a step under generated scores.  -> (the count, grow scale, rng_state)"""
+    op = "csr_regrow_total_random"
+    _check_csr_pattern(op, values, row_offsets, column_indices)
+    count = int(drop)
+    if not 0 <= count <= values.numel():
+        raise ValueError(f"{op}: drop = {count} is outside 0 .. {values.numel()}")
+    return (count,) + _check_key_step(op, values, n, grow_bound, rng_state, key_mask)
+
+
+def csr_regrow_total_random(values, row_offsets, column_indices, drop, n, grow_bound=None, rng_state=None,
+                            key_mask=REGROW_KEY_MASK):
+    """One matrix-wide drop-and-grow step of the CSR pattern of an ``m x n`` matrix under random
+    grow scores that are never stored (csrc/topology.hip): the layer-wise step of SET.  The keys,
+    the mask, ``grow_bound`` and ``rng_state`` are those of ``csr_regrow_random``; the step is
+    EXACTLY ``csr_regrow_total`` under dense float32 scores whose bits are the keys (ties to the
+    lowest flat index).  -> (row_indices, row_offsets, column_indices, values, source,
+    rng_state).  8 + value digits + 4 launches, 6 Philox calls per four positions, no ``[m, n]``
+    array, no host synchronisation: the call is captured in a graph whole.  Raises for CPU
+    tensors and beyond the 16384 rows and 65536 columns ``capi.csr_regrow_random_launch_shape``
+    serves."""
+    count, scale, rng_state = check_regrow_total_random_arguments(values, row_offsets, column_indices, drop, n,
+                                                                  grow_bound, rng_state, key_mask)
+    _device_floats("csr_regrow_total_random", "topology.regrow_total_random", values=values)
+    return tuple(_ops.csr_regrow_total_random(values, row_offsets, column_indices, count, int(n), scale, rng_state,
+                                              int(key_mask)))
+
+
 def check_csr_topk_arguments(values, row_offsets, column_indices, per_row, total):
     """ValueError unless the three tensors are one CSR pattern with its values (shapes, int32
     indices, one device) and exactly one of per_row / total is a count in range (``total`` at

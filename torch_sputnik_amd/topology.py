@@ -487,6 +487,111 @@ def regrow_total(values, row_offsets, column_indices, drop, scores):
     return regrow_total_composed(values, row_offsets, column_indices, d, scores)
 
 
+def _key_step_state(op, device, rng_state):
+    """(seed, offset, state tensor) of a step under generated scores that takes the torch path:
+    the ``rng_state`` given, or a fresh draw (``_draw_philox_state``)"""
+    if rng_state is None:
+        seed, offset = _draw_philox_state(device)
+        state = torch.tensor([seed, offset], dtype=torch.int64, device=device)
+    else:
+        state = rng_state
+        seed, offset = (int(v) for v in rng_state.tolist())
+    if offset % 4 != 0:
+        raise ValueError(f"{op}: the offset of rng_state must be a multiple of 4, got {offset}")
+    return seed, offset, state
+
+
+def _key_scores(m, n, seed, offset, device, key_mask):
+    """float32 [m, n] whose bit patterns are the masked keys of every position: the dense scores
+    the step under generated scores is defined by"""
+    keys = _random_words(m, n, seed, offset, device, False) & int(key_mask)
+    return keys.to(torch.int32).view(torch.float32)
+
+
+def _write_grown_values(values, row_offsets, column_indices, source, n, seed, offset, grow_bound):
+    """``values`` with the entries of ``source == -1`` replaced by the value stream of their
+    positions under ``grow_bound``"""
+    m = row_offsets.numel() - 1
+    q = (_random_words(m, n, seed, offset, values.device, True) >> 8) - 2 ** 23
+    image = (q.to(torch.float32) * ops.random_value_scale(grow_bound)).to(values.dtype)
+    flat = _entry_rows(row_offsets, values.numel()) * n + column_indices.to(torch.int64)
+    return torch.where(source < 0, image.reshape(-1)[flat], values) if values.numel() else values
+
+
+def regrow_per_row_random(values, row_offsets, column_indices, drop_counts, n, grow_bound=None, rng_state=None,
+                          return_rng_state=False, key_mask=ops.REGROW_KEY_MASK):
+    """``ops.csr_regrow_random`` for any tensor: one per-row drop-and-grow step of the CSR pattern
+    of an ``m x n`` matrix (row_offsets [m + 1], column_indices [nnz], int32, ascending inside a
+    row) with ``values`` [nnz] under random grow scores that are never stored -- SET's step.
+
+    The rule, for ``rng_state = {seed, offset}`` (offset a multiple of 4), with Philox4x32-10:
+    ``key(r, c) = Philox(seed, (offset / 4, c >> 2, r))[c & 3] & 0x3fffffff``, the key stream of
+    ``random_csr`` under a 30-bit mask.  Every such key read as float32 bits is a finite,
+    non-negative number, so the step is EXACTLY ``regrow_per_row`` under dense float32 scores
+    whose bits are ``key(r, c)``: Kept, Grown, the ties (lowest column), the eligibility of
+    dropped columns, ascending columns and ``source`` are its.  A grown entry is ``+0.0``
+    (``grow_bound=None``, as RigL initialises) or, for a finite ``grow_bound >= 0``, the value
+    ``random_csr`` gives that position: ``float32((word' >> 8) - 2**23) * float32(grow_bound /
+    2**23)`` with ``word'`` from the value stream (``r | 2**31`` in the counter), rounded to
+    nearest even into the values' dtype (SET re-initialises what it grows).
+
+    -> (column_indices, values, source), and the ``rng_state`` used (int64 [2]) with
+    ``return_rng_state``.  GPU float32 / float16 / bfloat16 values take the device kernel where
+    ``capi.csr_regrow_random_launch_shape`` serves ``n`` (up to 61440: one launch, no ``[m, n]``
+    array, no host synchronisation); CPU tensors, other dtypes, wider rows and
+    ``enable_device_build(False)`` take the rule as written: the keys as a dense image through
+    ``regrow_per_row``.  Given the same ``rng_state`` both return the same integers and value
+    bits.  Without one a GPU call draws 4 from the device's default generator
+    (``torch.manual_seed`` makes runs repeat) and a CPU call a seed from torch's CPU generator
+    with offset 0."""
+    ops.check_regrow_random_arguments(values, row_offsets, column_indices, drop_counts, n, grow_bound, rng_state,
+                                      key_mask)
+    values, n = values.detach(), int(n)
+    m = row_offsets.numel() - 1
+    if values.dtype in _TOPK_DTYPES and _served(values, "csr_regrow_random_launch_shape", m, n, values.numel(),
+                                                values.element_size(), False):
+        new_columns, new_values, source, state = ops.csr_regrow_random(
+            values, row_offsets, column_indices, drop_counts, n, grow_bound, rng_state, key_mask)
+    else:
+        seed, offset, state = _key_step_state("regrow_per_row_random", values.device, rng_state)
+        new_columns, new_values, source = regrow_per_row(
+            values, row_offsets, column_indices, drop_counts, _key_scores(m, n, seed, offset, values.device, key_mask))
+        if grow_bound is not None:
+            new_values = _write_grown_values(new_values, row_offsets, new_columns, source, n, seed, offset, grow_bound)
+    result = (new_columns, new_values, source)
+    return result + (state,) if return_rng_state else result
+
+
+def regrow_total_random(values, row_offsets, column_indices, drop, n, grow_bound=None, rng_state=None,
+                        return_rng_state=False, key_mask=ops.REGROW_KEY_MASK):
+    """``ops.csr_regrow_total_random`` for any tensor: one matrix-wide drop-and-grow step of the CSR
+    pattern of an ``m x n`` matrix under random grow scores that are never stored -- the layer-wise
+    step of SET.  Keys, ``grow_bound``, ``rng_state`` and the fallback are those of
+    ``regrow_per_row_random``; the step is EXACTLY ``regrow_total`` under dense float32 scores
+    whose bits are ``key(r, c)`` (ties to the lowest flat index; the row lengths change).
+
+    -> (row_indices, row_offsets, column_indices, values, source), and the ``rng_state`` used with
+    ``return_rng_state``.  The device step serves up to 16384 rows and 65536 columns
+    (``capi.csr_regrow_random_launch_shape``): a fixed number of launches, no ``[m, n]`` array, no
+    host synchronisation."""
+    d, _, _ = ops.check_regrow_total_random_arguments(values, row_offsets, column_indices, drop, n, grow_bound,
+                                                      rng_state, key_mask)
+    values, n = values.detach(), int(n)
+    m = row_offsets.numel() - 1
+    if values.dtype in _TOPK_DTYPES and _served(values, "csr_regrow_random_launch_shape", m, n, values.numel(),
+                                                values.element_size(), True):
+        row_indices, new_offsets, new_columns, new_values, source, state = ops.csr_regrow_total_random(
+            values, row_offsets, column_indices, d, n, grow_bound, rng_state, key_mask)
+    else:
+        seed, offset, state = _key_step_state("regrow_total_random", values.device, rng_state)
+        row_indices, new_offsets, new_columns, new_values, source = regrow_total(
+            values, row_offsets, column_indices, d, _key_scores(m, n, seed, offset, values.device, key_mask))
+        if grow_bound is not None:
+            new_values = _write_grown_values(new_values, new_offsets, new_columns, source, n, seed, offset, grow_bound)
+    result = (row_indices, new_offsets, new_columns, new_values, source)
+    return result + (state,) if return_rng_state else result
+
+
 def prune_csr(values, row_offsets, column_indices, n, per_row=None, total=None):
     """``ops.csr_topk`` for any tensor: the entries of largest magnitude of the CSR pattern
     (row_offsets [m + 1], column_indices [nnz], int32, ascending inside a row) of an ``m x n``
