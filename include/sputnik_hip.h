@@ -1557,6 +1557,80 @@ SPUTNIK_HIP_API int sputnik_hip_random_csr_launch_shape(int m, int n, int total_
                              int* digit_passes, int* grid, int* launches);
 
 /* ------------------------------------------------------------------------
+ * Attention patterns built straight to CSR on the device (topology.AttentionPattern,
+ * SparseAttention(pattern=...)): sliding and dilated windows, block-local attention, summary
+ * columns, global tokens, random blocks and the causal form of each, with no dense mask.
+ *
+ * The rule.  A pattern over m query rows and n key columns with an integer `offset`: row r
+ * sits at position p = r + offset, and d = c - p.  Entry (r, c), 0 <= r < m, 0 <= c < n, is
+ * kept iff (not causal or d <= 0) and at least one component keeps it:
+ *   window    -window_left <= d <= window_right and d mod dilation == 0 (floor-mod);
+ *             window_left = left * dilation and window_right = right * dilation, the products
+ *             formed by the caller and clamped to 2^33 (beyond every |d|), as a dilation
+ *             above 2^33 is.  window_left < 0: no window.
+ *   block     c / block == p / block in floor division (a negative p matches no column);
+ *             block = 0: none
+ *   summary   c mod summary_stride >= summary_first, summary_first = stride - width;
+ *             summary_stride = 0: none
+ *   global    flag[c] != 0, or, with global_rows, 0 <= p < n and flag[p] != 0 (a full row);
+ *             global_flags: n bytes on the device, 4-byte aligned; NULL: none
+ *   random    key(r / random_block, c / random_block) < random_threshold (0 .. 2^31) with
+ *             key(R, C) = philox(key (seed lo, seed hi), counter (offset/4 lo, offset/4 hi,
+ *             C >> 2, R))[C & 3] & 0x7fffffff: the key stream of sputnik_hip_random_csr under
+ *             the state `rng` (the offset a multiple of 4); random_block = 0: none
+ * Columns ascend inside a row and an entry appears once however many components keep it.  A
+ * row without an entry is legal.
+ *
+ * sputnik_hip_attention_pattern_count writes row_offsets [m + 1] and nonzeros [1] (device):
+ * one rows launch -- a group of lanes walks a row in steps of group_lanes * 4 columns, a lane
+ * evaluates the rule at its 4 consecutive columns; the flag vector is the only memory it
+ * reads -- and the scan of sputnik_hip_dense_to_csr_count.  With random blocks the resolved
+ * {seed, offset} goes to rng_state_out (int64 [2], may be NULL).  The caller reads nonzeros
+ * back, allocates column_indices [nonzeros], and sputnik_hip_attention_pattern_fill, given the
+ * same rule and state, writes them (the same walk, the slots by wave ballots) and row_indices
+ * [m] (sputnik_hip_csr_row_order): four launches and one synchronisation in all.  Nothing of
+ * size m * n exists.  m = 0 and n = 0 give empty results.
+ *
+ * Served (sputnik_hip_attention_pattern_launch_shape, host only, any output pointer may be
+ * NULL): m <= 16384 (the row order's limit), m * n <= INT_MAX and |offset| < 2^30; the fields
+ * behind `served` -- the rows of a wave, the columns of a lane and step (4), the rows of a
+ * workgroup, the grid of the rows launches and the launches of a build (4) -- are -1 where it
+ * does not serve.
+ *
+ * SPUTNIK_HIP_INVALID_ARGUMENT: a negative size, a shape that is not served, a rule with a
+ * field outside its range, a missing or misaligned pointer.  (A rule without a component keeps
+ * nothing.)
+ * ---------------------------------------------------------------------- */
+typedef struct sputnik_hip_attention_pattern_args {
+  int64_t offset;
+  int64_t window_left;
+  int64_t window_right;
+  int64_t dilation;
+  int block;
+  int summary_stride;
+  int summary_first;
+  int random_block;
+  unsigned random_threshold;
+  int causal;
+  int global_rows;
+  const unsigned char* global_flags;
+} sputnik_hip_attention_pattern_args;
+
+SPUTNIK_HIP_API int sputnik_hip_attention_pattern_launch_shape(int m, int n, int64_t offset, int* served,
+                             int* rows_per_wave, int* columns_per_lane, int* rows_per_workgroup,
+                             int* grid, int* launches);
+
+SPUTNIK_HIP_API int sputnik_hip_attention_pattern_count(int m, int n,
+                             const sputnik_hip_attention_pattern_args* pattern,
+                             sputnik_hip_philox_state rng, int64_t* rng_state_out, int* row_offsets,
+                             int* nonzeros, sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_attention_pattern_fill(int m, int n,
+                             const sputnik_hip_attention_pattern_args* pattern,
+                             sputnik_hip_philox_state rng, int nonzeros, const int* row_offsets,
+                             int* row_indices, int* column_indices, sputnik_hip_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Per-row drop-and-grow of a CSR topology (topology.regrow_per_row,
  * SparseLinear.update_topology(..., per_row=True)): every row keeps its length, drops its
  * entries of smallest magnitude and grows as many where a dense score matrix is largest.

@@ -28,6 +28,16 @@ class PhiloxState(ctypes.Structure):
                 ("offset_intragraph", ctypes.c_uint64)]
 
 
+class AttentionPatternArgs(ctypes.Structure):
+    """sputnik_hip_attention_pattern_args: the rule of an attention pattern as the kernels take
+    it (include/sputnik_hip.h, "Attention patterns"; ops.attention_pattern_csr fills one in)."""
+    _fields_ = [("offset", ctypes.c_int64), ("window_left", ctypes.c_int64), ("window_right", ctypes.c_int64),
+                ("dilation", ctypes.c_int64), ("block", ctypes.c_int), ("summary_stride", ctypes.c_int),
+                ("summary_first", ctypes.c_int), ("random_block", ctypes.c_int),
+                ("random_threshold", ctypes.c_uint), ("causal", ctypes.c_int), ("global_rows", ctypes.c_int),
+                ("global_flags", ctypes.c_void_p)]
+
+
 _DROP = [ctypes.c_double, PhiloxState, _c_ptr]   # p, state, rng_state_out
 
 # name -> (restype, argtypes); must list every symbol include/sputnik_hip.h declares.
@@ -113,6 +123,11 @@ SIGNATURES = {
                                         _c_ptr, _c_size] + [_c_ptr] * 5),
     "sputnik_hip_random_csr_workspace_bytes": (_c_size, [_c_int] * 3),
     "sputnik_hip_random_csr_launch_shape": (_c_int, [_c_int] * 3 + [_c_ptr] * 7),
+    "sputnik_hip_attention_pattern_launch_shape": (_c_int, [_c_int, _c_int, _c_i64] + [_c_ptr] * 6),
+    "sputnik_hip_attention_pattern_count": (_c_int, [_c_int, _c_int, ctypes.POINTER(AttentionPatternArgs), PhiloxState]
+                                            + [_c_ptr] * 4),
+    "sputnik_hip_attention_pattern_fill": (_c_int, [_c_int, _c_int, ctypes.POINTER(AttentionPatternArgs), PhiloxState,
+                                                    _c_int] + [_c_ptr] * 4),
     "sputnik_hip_csr_regrow": (_c_int, [_c_int] * 3 + [_c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_int, _c_i64,
                                         ctypes.c_uint, _c_ptr, _c_size] + [_c_ptr] * 4),
     "sputnik_hip_csr_regrow_workspace_bytes": (_c_size, [_c_int] * 3),
@@ -591,6 +606,20 @@ def random_csr_launch_shape(m, n, total):
 def random_csr_workspace_bytes(m, n, total):
     """Bytes of workspace sputnik_hip_random_csr wants (0 per row).  Host only."""
     return int(lib().sputnik_hip_random_csr_workspace_bytes(m, n, int(bool(total))))
+
+
+def attention_pattern_launch_shape(m, n, offset=0):
+    """The instance of the device build of an attention pattern over m rows and n columns at
+    that offset: a dict of served (bool: m <= 16384, m * n <= INT_MAX, |offset| < 2**30; the
+    other fields are -1 where it is not), rows_per_wave, columns_per_lane (4),
+    rows_per_workgroup, grid and launches (4: count, scan, fill, row order;
+    include/sputnik_hip.h).  Host only; sizes beyond int32 and offsets beyond int64 are not
+    served, negative sizes raise."""
+    m, n, offset = int(m), int(n), int(offset)
+    if m > 2 ** 31 - 1 or n > 2 ** 31 - 1 or abs(offset) >= 2 ** 63:
+        return dict(served=False, rows_per_wave=-1, columns_per_lane=-1, rows_per_workgroup=-1, grid=-1, launches=-1)
+    return _query("sputnik_hip_attention_pattern_launch_shape", (max(m, -1), max(n, -1), offset),
+                  ("served", "rows_per_wave", "columns_per_lane", "rows_per_workgroup", "grid", "launches"))
 
 
 def csr_regrow_launch_shape(m, n, score_bytes, value_bytes):

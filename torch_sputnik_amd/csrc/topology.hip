@@ -2,7 +2,8 @@
 // (include/sputnik_hip.h: sputnik_hip_dense_to_csr_*, sputnik_hip_csr_row_order), and the
 // selections that write one out: sputnik_hip_topk_to_csr, sputnik_hip_csr_regrow, sputnik_hip_csr_topk,
 // sputnik_hip_csr_topk_global_*, sputnik_hip_csr_regrow_total, sputnik_hip_random_csr,
-// sputnik_hip_csr_regrow_random, sputnik_hip_csr_regrow_total_random.
+// sputnik_hip_csr_regrow_random, sputnik_hip_csr_regrow_total_random; and the attention patterns
+// that are built from a rule with no dense mask at all (sputnik_hip_attention_pattern_*).
 //
 // The build replaces the torch loop of topology.dense_to_sparse_3d (per mask: != 0,
 // to_sparse_csr, two casts, a stable argsort and a host read of the count) by a fixed number of
@@ -583,6 +584,244 @@ int launch_rows_typed(const BuildShape& s, int m, int n, const void* dense, int 
 
 inline bool dense_ok(const void* dense, int element_bytes, int64_t batch_stride, int64_t row_stride) {
   return dense != nullptr && aligned_to(dense, element_bytes) && batch_stride >= 0 && row_stride >= 0;
+}
+
+// ---------------------------------------------------------------------------
+// Attention patterns (sputnik_hip_attention_pattern_*): the build above over a mask that is
+// never stored.  topology_rows_kernel with the load replaced by the predicate of
+// include/sputnik_hip.h, "Attention patterns": a lane evaluates its V = 4 consecutive columns
+// into a flag word, the count pass reduces popcounts, the fill pass places columns with
+// group_prefix.  What depends on the row alone is computed once per row (PatternRow): the
+// position p, the columns of the window and of the block, the last column a causal row may
+// keep, whether the row is global, the row of random blocks.  The only memory read is the
+// flag vector of the global tokens: four bytes per lane and step, one aligned load where the
+// piece lies inside [0, n).  The random component draws one Philox call per distinct
+// (C >> 2, R) a lane meets: the four words stay in registers across the columns of a piece and
+// across steps.  All position arithmetic is 64 bit; the host hands over products that are
+// already clamped (pattern_ok).
+// ---------------------------------------------------------------------------
+constexpr int kPatternV = 4;                              // columns per lane and step
+constexpr int64_t kPatternReach = int64_t{1} << 33;       // beyond every |c - p|
+constexpr int64_t kPatternMaxOffset = int64_t{1} << 30;   // |offset| below it
+constexpr int kPatternLaunches = 4;                       // count, scan, fill, row order
+
+struct PatternArgs {
+  sputnik_hip_attention_pattern_args rule;
+  DropArgs state;   // the Philox state of the random blocks and where it is published
+};
+
+struct PatternShape {
+  int status = 0;
+  int served = 0;
+  BuildShape walk;
+};
+inline PatternShape pattern_shape(int m, int n, int64_t offset) {
+  PatternShape s;
+  if (m < 0 || n < 0) {
+    s.status = SPUTNIK_HIP_INVALID_ARGUMENT;
+    return s;
+  }
+  if (static_cast<int64_t>(m) * n > INT_MAX || offset <= -kPatternMaxOffset || offset >= kPatternMaxOffset ||
+      !order_route(1, m, n).served)
+    return s;
+  s.walk = build_shape(1, m, n, kLoadBytes / kPatternV);
+  s.status = s.walk.status;
+  s.served = s.status == 0 ? 1 : 0;
+  return s;
+}
+
+// What the entries refuse: a rule with a field outside its range.  (A rule without a component
+// keeps nothing; ops.attention_pattern_csr turns it away.)
+inline bool pattern_ok(const sputnik_hip_attention_pattern_args& a) {
+  const bool window = a.window_left >= 0;
+  if (a.dilation < 1 || a.dilation > kPatternReach || a.block < 0 || a.summary_stride < 0 || a.random_block < 0)
+    return false;
+  if (window && (a.window_left > kPatternReach || a.window_right < 0 || a.window_right > kPatternReach)) return false;
+  if (a.summary_stride > 0 && a.summary_first < 0) return false;
+  if (a.random_block > 0 && a.random_threshold > 0x80000000u) return false;
+  return a.global_flags == nullptr || aligned_to(a.global_flags, kPatternV);
+}
+
+// What a row fixes for all of its columns.
+struct PatternRow {
+  bool live, full;            // a row of the matrix; a global row: every column
+  int64_t p;                  // its position
+  int64_t lo, hi;             // the window's columns (lo > hi: none)
+  int64_t block_lo, block_hi; // the block's columns (none for p < 0)
+  int64_t last;               // the last column kept: p for a causal row, else n - 1
+  unsigned random_row;        // R = r / rb
+
+  __device__ __forceinline__ PatternRow(const RowGroup& g, const sputnik_hip_attention_pattern_args& a, int m, int n) {
+    live = g.row < m;
+    p = g.row + a.offset;
+    lo = 1;
+    hi = 0;
+    if (a.window_left >= 0) {
+      lo = max(p - a.window_left, int64_t{0});
+      hi = min(p + a.window_right, static_cast<int64_t>(n) - 1);
+    }
+    block_lo = 1;
+    block_hi = 0;
+    if (a.block > 0 && p >= 0) {
+      block_lo = p / a.block * a.block;
+      block_hi = block_lo + a.block - 1;
+    }
+    last = a.causal ? min(p, static_cast<int64_t>(n) - 1) : static_cast<int64_t>(n) - 1;
+    full = live && a.global_flags != nullptr && a.global_rows && p >= 0 && p < n && a.global_flags[p] != 0;
+    random_row = a.random_block > 0 ? static_cast<unsigned>(g.row / a.random_block) : 0u;
+  }
+};
+
+// The random blocks' words a lane holds: those of the last (C >> 2, R) it met.
+struct PatternDraw {
+  unsigned quad = 0xffffffffu;   // (C >> 2 stays below 2^29)
+  uint4 words = make_uint4(0u, 0u, 0u, 0u);
+};
+
+// A bit per column c0 .. c0 + 3 of the row that the rule keeps.
+__device__ __forceinline__ unsigned pattern_flags(const sputnik_hip_attention_pattern_args& a, const PhiloxKey& key,
+                                                  const PatternRow& row, int64_t c0, int n, PatternDraw* draw) {
+  constexpr int V = kPatternV;
+  if (!row.live || c0 >= n || c0 > row.last) return 0u;
+  const int64_t inside = min(static_cast<int64_t>(n) - 1, row.last) - c0 + 1;   // >= 1
+  const unsigned open = inside >= V ? (1u << V) - 1u : (1u << inside) - 1u;
+  if (row.full) return open;
+  unsigned keep = 0u;
+  if (c0 + (V - 1) >= row.lo && c0 <= row.hi) {   // the window
+    int64_t rem = 0;   // floor-mod of c0 - p
+    if (a.dilation > 1) {
+      rem = (c0 - row.p) % a.dilation;
+      if (rem < 0) rem += a.dilation;
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const int64_t c = c0 + e, t = rem + e;   // (t < dilation + 4: a multiple is one of four)
+      const bool on = a.dilation == 1 || t == 0 || t == a.dilation || t == 2 * a.dilation || t == 3 * a.dilation;
+      keep |= (c >= row.lo && c <= row.hi && on ? 1u : 0u) << e;
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < V; ++e) keep |= (c0 + e >= row.block_lo && c0 + e <= row.block_hi ? 1u : 0u) << e;
+  if (a.summary_stride > 0) {
+    const unsigned stride = static_cast<unsigned>(a.summary_stride), first = static_cast<unsigned>(a.summary_first);
+    unsigned t = static_cast<unsigned>(c0) % stride;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      keep |= (t >= first ? 1u : 0u) << e;
+      if (++t == stride) t = 0u;
+    }
+  }
+  if (a.global_flags != nullptr) {
+    if (c0 + V <= n) {   // (aligned: the vector starts on 4 bytes, c0 is a multiple of 4)
+      const unsigned four = *reinterpret_cast<const unsigned*>(a.global_flags + c0);
+#pragma unroll
+      for (int e = 0; e < V; ++e) keep |= (((four >> (8 * e)) & 0xffu) != 0u ? 1u : 0u) << e;
+    } else {
+#pragma unroll
+      for (int e = 0; e < V; ++e)
+        if (c0 + e < n) keep |= (a.global_flags[c0 + e] != 0 ? 1u : 0u) << e;
+    }
+  }
+  if (a.random_block > 0) {
+    const unsigned rb = static_cast<unsigned>(a.random_block);
+    unsigned block = static_cast<unsigned>(c0) / rb, at = static_cast<unsigned>(c0) % rb;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      if ((open >> e) & 1u) {
+        if ((block >> 2) != draw->quad) {
+          draw->quad = block >> 2;
+          draw->words = philox4x32_10(key, draw->quad, row.random_row);
+        }
+        const unsigned k = uint4_word(draw->words, static_cast<int>(block & 3u)) & 0x7fffffffu;
+        keep |= (k < a.random_threshold ? 1u : 0u) << e;
+      }
+      if (++at == rb) {
+        at = 0u;
+        ++block;
+      }
+    }
+  }
+  return keep & open;
+}
+
+// FILL = false: row_offsets[row + 1] = kept columns of the row.
+// FILL = true:  the kept columns of the row go to row_offsets[row] onwards, ascending, inside
+//               [0, nonzeros) whatever the offsets say.
+template <bool FILL>
+__global__ __launch_bounds__(kBuildBlock) void attention_pattern_rows_kernel(
+    int m, int n, int rows_per_wave, PatternArgs args, int nonzeros, int* __restrict__ row_offsets,
+    int* __restrict__ column_indices) {
+  constexpr int V = kPatternV;
+  const sputnik_hip_attention_pattern_args& a = args.rule;
+  const RowGroup g(rows_per_wave);
+  PhiloxKey key = {0u, 0u, 0u, 0u};
+  if (a.random_block > 0) key = philox_key(args.state, !FILL && blockIdx.x == 0 && threadIdx.x == 0);
+  const PatternRow row(g, a, m, n);
+  PatternDraw draw;
+  const int64_t span = static_cast<int64_t>(g.group_lanes) * V;
+  const int steps = static_cast<int>((static_cast<int64_t>(n) + span - 1) / span);   // (the wave's: ballots)
+  // A rule of window and block alone keeps nothing outside their columns: the wave walks the
+  // steps from the first such column of its rows to the last one.
+  int first_step = 0, end_step = steps;
+  if (a.global_flags == nullptr && a.summary_stride == 0 && a.random_block == 0) {
+    int64_t from = n, to = -1;
+    if (row.live) {
+      if (row.lo <= row.hi) {
+        from = row.lo;
+        to = row.hi;
+      }
+      if (row.block_lo <= row.block_hi) {
+        from = min(from, row.block_lo);
+        to = max(to, row.block_hi);
+      }
+      to = min(to, row.last);
+    }
+    first_step = to < from ? steps : static_cast<int>(min(from / span, static_cast<int64_t>(steps)));
+    end_step = to < from ? 0 : static_cast<int>(min(to / span + 1, static_cast<int64_t>(steps)));
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+      first_step = min(first_step, __shfl_xor(first_step, o, kWave));
+      end_step = max(end_step, __shfl_xor(end_step, o, kWave));
+    }
+  }
+
+  int64_t out = 0;
+  if constexpr (FILL) {
+    if (row.live) out = row_offsets[g.row];
+  }
+  int count = 0;
+  for (int s = first_step; s < end_step; ++s) {
+    const int64_t c0 = (static_cast<int64_t>(s) * g.group_lanes + g.group_lane) * V;
+    const unsigned flags = pattern_flags(a, key, row, c0, n, &draw);
+    if constexpr (!FILL) {
+      count += __popc(flags);
+    } else {
+      const Prefix at = group_prefix<V>(g, flags);
+      int64_t p = out + at.before;
+#pragma unroll
+      for (int e = 0; e < V; ++e)
+        if ((flags >> e) & 1u) {
+          if (p >= 0 && p < nonzeros) column_indices[p] = static_cast<int>(c0 + e);
+          ++p;
+        }
+      out += at.total;
+    }
+  }
+  if constexpr (!FILL) {
+    for (int o = g.group_lanes / 2; o > 0; o >>= 1) count += __shfl_xor(count, o, kWave);
+    if (row.live && g.group_lane == 0) row_offsets[g.row + 1] = count;
+  }
+}
+
+inline PatternArgs pattern_args(const sputnik_hip_attention_pattern_args& rule, const sputnik_hip_philox_state& rng,
+                                int64_t* rng_state_out) {
+  PatternArgs args;
+  args.rule = rule;
+  args.state.rng = rng;
+  args.state.rng_state_out = rng_state_out;
+  args.state.threshold = 0u;
+  args.state.scale = 0.f;
+  args.state.replica0 = 0;
+  return args;
 }
 
 // ---------------------------------------------------------------------------
@@ -2070,6 +2309,65 @@ int sputnik_hip_csr_row_order(int masks, int m, int n, const int* row_offsets, i
     hipLaunchKernelGGL((topology_row_order_kernel<kOrderLargeRows, kOrderLargeBlock>), dim3(masks),
                        dim3(kOrderLargeBlock), 0, stream, m, r.sort_size, row_offsets, row_indices);
   return launch_status();
+}
+
+int sputnik_hip_attention_pattern_launch_shape(int m, int n, int64_t offset, int* served, int* rows_per_wave,
+                                               int* columns_per_lane, int* rows_per_workgroup, int* grid,
+                                               int* launches) {
+  const PatternShape s = pattern_shape(m, n, offset);
+  if (s.status != 0) return s.status;
+  put(served, s.served);
+  put(rows_per_wave, s.served ? s.walk.rows_per_wave : -1);
+  put(columns_per_lane, s.served ? s.walk.elements_per_lane : -1);
+  put(rows_per_workgroup, s.served ? s.walk.rows_per_workgroup : -1);
+  put(grid, s.served ? s.walk.grid : -1);
+  put(launches, s.served ? kPatternLaunches : -1);
+  return 0;
+}
+
+int sputnik_hip_attention_pattern_count(int m, int n, const sputnik_hip_attention_pattern_args* pattern,
+                                        sputnik_hip_philox_state rng, int64_t* rng_state_out, int* row_offsets,
+                                        int* nonzeros, sputnik_hip_stream_t stream_) {
+  if (pattern == nullptr) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const PatternShape s = pattern_shape(m, n, pattern->offset);
+  if (s.status != 0) return s.status;
+  if (!s.served || !pattern_ok(*pattern) || row_offsets == nullptr || !aligned_to(row_offsets, sizeof(int)) ||
+      nonzeros == nullptr || !aligned_to(nonzeros, sizeof(int)) ||
+      (rng_state_out != nullptr && !aligned_to(rng_state_out, sizeof(int64_t))))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const PatternArgs args = pattern_args(*pattern, rng, pattern->random_block > 0 ? rng_state_out : nullptr);
+  if (s.walk.grid > 0) {
+    hipLaunchKernelGGL((attention_pattern_rows_kernel<false>), dim3(s.walk.grid), dim3(kBuildBlock), 0, stream, m, n,
+                       s.walk.rows_per_wave, args, 0, row_offsets, static_cast<int*>(nullptr));
+  } else if (pattern->random_block > 0) {
+    const int st = publish_rng_state(args.state, stream);   // (no row to publish it)
+    if (st != 0) return st;
+  }
+  hipLaunchKernelGGL(topology_scan_kernel, dim3(1), dim3(kScanBlock), 0, stream, m, row_offsets, nonzeros);
+  return launch_status();
+}
+
+int sputnik_hip_attention_pattern_fill(int m, int n, const sputnik_hip_attention_pattern_args* pattern,
+                                       sputnik_hip_philox_state rng, int nonzeros, const int* row_offsets,
+                                       int* row_indices, int* column_indices, sputnik_hip_stream_t stream_) {
+  if (pattern == nullptr) return SPUTNIK_HIP_INVALID_ARGUMENT;
+  const PatternShape s = pattern_shape(m, n, pattern->offset);
+  if (s.status != 0) return s.status;
+  if (!s.served || !pattern_ok(*pattern) || nonzeros < 0 || row_offsets == nullptr ||
+      !aligned_to(row_offsets, sizeof(int)) ||
+      (m > 0 && (row_indices == nullptr || !aligned_to(row_indices, sizeof(int)))) ||
+      (nonzeros > 0 && (column_indices == nullptr || !aligned_to(column_indices, sizeof(int)))))
+    return SPUTNIK_HIP_INVALID_ARGUMENT;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (s.walk.grid > 0 && nonzeros > 0) {
+    const PatternArgs args = pattern_args(*pattern, rng, nullptr);
+    hipLaunchKernelGGL((attention_pattern_rows_kernel<true>), dim3(s.walk.grid), dim3(kBuildBlock), 0, stream, m, n,
+                       s.walk.rows_per_wave, args, nonzeros, const_cast<int*>(row_offsets), column_indices);
+    const int st = launch_status();
+    if (st != 0) return st;
+  }
+  return sputnik_hip_csr_row_order(1, m, n, row_offsets, row_indices, stream_);
 }
 
 int sputnik_hip_topk_to_csr_launch_shape(int m, int n, int element_bytes, int total_mode, int* served,

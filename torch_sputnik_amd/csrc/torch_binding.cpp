@@ -2151,6 +2151,73 @@ std::vector<Tensor> random_csr(int64_t m_in, int64_t n_in, int64_t per_row, int6
   return {row_indices, row_offsets, column_indices, values, state.rng_state};
 }
 
+// The CSR topology of an attention pattern over m rows and n columns, built on `device` from
+// its rule (sputnik_hip.h, "Attention patterns"; ops.attention_pattern_csr checks and clamps
+// the fields) -> [row_indices, row_offsets, column_indices] (+ rng_state with random blocks).
+// Count and scan are launched, the one count is read back -- the ONE synchronisation -- and
+// the fill and the row order are launched.  `global_flags`: uint8 [n] on the device, or none.
+// Only a rule with random blocks has a Philox state: a replay of `rng_state`, or 4 drawn from
+// the device's default generator (draw_state).
+std::vector<Tensor> attention_pattern_csr(int64_t m_in, int64_t n_in, int64_t offset, int64_t window_left,
+                                          int64_t window_right, int64_t dilation, int64_t block,
+                                          int64_t summary_stride, int64_t summary_first, int64_t random_block,
+                                          int64_t random_threshold, bool causal, bool global_rows,
+                                          const c10::optional<Tensor>& global_flags_in, c10::Device device,
+                                          const c10::optional<Tensor>& rng_state) {
+  const char* op = "attention_pattern_csr";
+  TORCH_CHECK(device.is_cuda(), "torch_sputnik::attention_pattern_csr: device must be a GPU (HIP) device, got ",
+              device);
+  const c10::DeviceGuard guard(device);
+  if (!device.has_index()) device = c10::Device(device.type(), at::cuda::current_device());
+  const int m = to_int(m_in, "m"), n = to_int(n_in, "n");
+  int served = 0;
+  check_status(sputnik_hip_attention_pattern_launch_shape(m, n, offset, &served, nullptr, nullptr, nullptr, nullptr,
+                                                          nullptr),
+               op);
+  check_served(op, served, "sputnik_hip_attention_pattern_launch_shape", "topology.AttentionPattern.build");
+  sputnik_hip_attention_pattern_args rule{};
+  rule.offset = offset;
+  rule.window_left = window_left;
+  rule.window_right = window_right;
+  rule.dilation = dilation;
+  rule.block = to_int(block, "block");
+  rule.summary_stride = to_int(summary_stride, "summary_stride");
+  rule.summary_first = to_int(summary_first, "summary_first");
+  rule.random_block = to_int(random_block, "random_block");
+  check_count(op, "random_threshold", random_threshold, int64_t{1} << 31);
+  rule.random_threshold = static_cast<unsigned>(random_threshold);
+  rule.causal = causal ? 1 : 0;
+  rule.global_rows = global_rows ? 1 : 0;
+  Tensor global_flags;
+  if (global_flags_in.has_value() && global_flags_in->defined()) {
+    TORCH_CHECK(global_flags_in->device() == device && global_flags_in->scalar_type() == at::kByte &&
+                    global_flags_in->dim() == 1 && global_flags_in->numel() == n,
+                "torch_sputnik::attention_pattern_csr: global_flags must be a uint8 [n] tensor on ", device, ", got ",
+                global_flags_in->scalar_type(), " ", global_flags_in->sizes(), " on ", global_flags_in->device());
+    global_flags = global_flags_in->contiguous();
+    if (reinterpret_cast<uintptr_t>(global_flags.data_ptr()) % 4 != 0) global_flags = global_flags.clone();
+    rule.global_flags = static_cast<const unsigned char*>(global_flags.data_ptr());
+  }
+  const auto index_options = at::TensorOptions().device(device).dtype(at::kInt);
+  Tensor row_indices = at::empty({m}, index_options);
+  Tensor row_offsets = at::empty({m + 1}, index_options);
+  Tensor count = at::empty({1}, index_options);
+  const bool random = random_block > 0;
+  const Drop state = random ? draw_state(rng_state, row_offsets) : Drop();
+  const auto stream = current_stream(row_offsets);
+  check_status(sputnik_hip_attention_pattern_count(m, n, &rule, state.rng, state.rng_state_out,
+                                                   row_offsets.data_ptr<int>(), count.data_ptr<int>(), stream),
+               "attention_pattern_csr (count)");
+  const int nonzeros = count.to(at::kCPU).item<int>();   // the synchronisation
+  Tensor column_indices = at::empty({nonzeros}, index_options);
+  check_status(sputnik_hip_attention_pattern_fill(m, n, &rule, state.rng, nonzeros, row_offsets.data_ptr<int>(),
+                                                  row_indices.data_ptr<int>(), column_indices.data_ptr<int>(), stream),
+               "attention_pattern_csr (fill)");
+  std::vector<Tensor> out{row_indices, row_offsets, column_indices};
+  if (random) out.push_back(state.rng_state);
+  return out;
+}
+
 // One per-row drop-and-grow step of the CSR pattern (row_offsets [m + 1], column_indices [nnz])
 // with `values` [nnz] under dense `scores` [m, n] -> [column_indices, values, source (int64)] of
 // the new pattern in the same slots (sputnik_hip.h: sputnik_hip_csr_regrow).  nnz is known up
@@ -2915,6 +2982,10 @@ TORCH_LIBRARY(torch_sputnik, m) {
   // (no tensor among the arguments of a fresh draw: registered for every backend, GPU devices only)
   m.def("random_csr(int m, int n, int per_row, int total, ScalarType dtype, float scale, Device device, "
         "Tensor? rng_state, int key_mask) -> Tensor[]", &random_csr);
+  m.def("attention_pattern_csr(int m, int n, int offset, int window_left, int window_right, int dilation, "
+        "int block, int summary_stride, int summary_first, int random_block, int random_threshold, bool causal, "
+        "bool global_rows, Tensor? global_flags, Device device, Tensor? rng_state) -> Tensor[]",
+        &attention_pattern_csr);
   m.def("csr_regrow(Tensor values, Tensor row_offsets, Tensor column_indices, Tensor drop_counts, "
         "Tensor scores) -> Tensor[]");
   m.def("csr_regrow_total(Tensor values, Tensor row_offsets, Tensor column_indices, int drop, "

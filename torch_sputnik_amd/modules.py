@@ -398,12 +398,17 @@ class SparseAttention(nn.Module):
     inside the fused kernels' online softmax, or sparse_dropout between the softmax and the
     SpMM of the separate-operator path (the masks are the same: functional.sparse_dropout).
     ``fused_backward=True``: training runs the fused forward and the fused backward
-    (functional.FusedBackwardAttentionFunction), float32 only, head dimension 64 or 128."""
+    (functional.FusedBackwardAttentionFunction), float32 only, head dimension 64 or 128.
+    ``pattern`` (a topology.AttentionPattern: windows, blocks, summary columns, global tokens,
+    random blocks, causal) replaces the random mask by a structured one, built straight to CSR
+    on the module's device with no dense mask (``pattern_rng_state`` reproduces its random
+    blocks); ``set_pattern`` swaps it later."""
 
     def __init__(self, num_heads, embedding_size, max_sequence_length=512, device=None,
                  sparsity=0.9, mask_generator=None, differentiable_softmax=False,
                  fused_inference=True, low_memory_training=False, fused_training=None,
-                 half_storage=False, attention_dropout=0.0, fused_backward=False):
+                 half_storage=False, attention_dropout=0.0, fused_backward=False,
+                 pattern=None, pattern_rng_state=None):
         super().__init__()
         self.attention_dropout = ops.check_dropout_p(attention_dropout)
         if half_storage and fused_backward:
@@ -418,10 +423,18 @@ class SparseAttention(nn.Module):
         self.m = max_sequence_length
         self.n = max_sequence_length
         device = torch.device("cuda") if device is None else device
-        self.mask2d = generate_mask(self.m, self.n, device, sparsity=sparsity,
-                                    generator=mask_generator)
-        _, self.row_indices, self.row_offsets, self.column_indices = dense_to_sparse(self.mask2d)
-        functional.register_static_topology(self.row_indices, self.row_offsets, self.column_indices)
+        self.pattern = self.pattern_rng_state = None
+        if pattern is not None:
+            # a structured pattern (topology.AttentionPattern) is built straight to CSR: no
+            # dense mask exists, `sparsity` and `mask_generator` are unused
+            self.mask2d = None
+            self._pattern_device = device
+            self.set_pattern(pattern, pattern_rng_state)
+        else:
+            self.mask2d = generate_mask(self.m, self.n, device, sparsity=sparsity,
+                                        generator=mask_generator)
+            _, self.row_indices, self.row_offsets, self.column_indices = dense_to_sparse(self.mask2d)
+            functional.register_static_topology(self.row_indices, self.row_offsets, self.column_indices)
 
         self.sddmm = Sddmm.apply
         self.spmm = Spmm.apply
@@ -449,6 +462,26 @@ class SparseAttention(nn.Module):
         # low_memory_training; shapes the fused backward does not serve (head dimension other
         # than 64 or 128) train as low_memory_training does.
         self.fused_backward = bool(fused_backward)
+
+    def set_pattern(self, pattern, rng_state=None):
+        """Swaps the module's topology for that of ``pattern`` (topology.AttentionPattern) over
+        its ``max_sequence_length`` rows and columns, on the device of the topology in use.
+        The new index tensors are registered as static and the old ones unregistered, which
+        sends the plans and transposes cached for them out of use.  ``rng_state`` reproduces a
+        pattern with random blocks; the state used is kept in ``pattern_rng_state`` (None
+        without random blocks)."""
+        if not isinstance(pattern, topology.AttentionPattern):
+            raise TypeError(f"set_pattern: expected a topology.AttentionPattern, got {type(pattern).__name__}")
+        old = [getattr(self, name, None) for name in ("row_indices", "row_offsets", "column_indices")]
+        device = old[1].device if old[1] is not None else self._pattern_device
+        row_indices, row_offsets, column_indices, state = pattern.build(
+            self.m, self.n, device=device, rng_state=rng_state, return_rng_state=True)
+        if old[1] is not None:
+            functional.unregister_static_topology(*old)
+        self.row_indices, self.row_offsets, self.column_indices = row_indices, row_offsets, column_indices
+        functional.register_static_topology(self.row_indices, self.row_offsets, self.column_indices)
+        self.pattern, self.pattern_rng_state, self.mask2d = pattern, state, None
+        return self
 
     @property
     def fused_training(self):   # the flag's name in rounds 1-3

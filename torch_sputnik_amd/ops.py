@@ -8,6 +8,8 @@ GPU only: a CPU tensor raises from the dispatcher; there is no fallback.  (One d
 exception: ``dense_weight_grad``, which the module flow calls on layers of any size, computes
 what its kernel does not serve with ``torch.einsum``.)
 """
+import numbers
+
 import torch
 
 from ._native import load_ops
@@ -457,6 +459,157 @@ def random_csr(m, n, per_row=None, total=None, dtype=torch.float32, bound=1.0, d
         rng_state = rng_state.to(device).contiguous()
     return tuple(_ops.random_csr(int(m), int(n), *_binding_counts(per_row, count), dtype, random_value_scale(bound),
                                  device, rng_state, int(key_mask)))
+
+
+PATTERN_REACH = 2 ** 33          # beyond every |c - p| the device path serves
+PATTERN_MAX_OFFSET = 2 ** 30     # |offset| below it on the device path
+_INT_MAX = 2 ** 31 - 1
+
+
+def _pattern_int(op, name, value, least):
+    """``value`` as a Python int >= ``least``; ValueError otherwise (bools and floats included)"""
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral):
+        raise ValueError(f"{op}: {name} must be an integer, got {value!r}")
+    if int(value) < least:
+        raise ValueError(f"{op}: {name} = {int(value)} is below {least}")
+    return int(value)
+
+
+def _pattern_pair(op, name, value, what):
+    if not isinstance(value, (tuple, list)) or len(value) != 2:
+        raise ValueError(f"{op}: {name} must be {what}, got {value!r}")
+    return value
+
+
+def check_pattern_arguments(op, window=None, dilation=1, block=0, global_tokens=None, global_rows=True, summary=None,
+                            random_blocks=None, causal=False):
+    """The argument contract of an attention pattern (``attention_pattern_csr`` states the rule):
+    ValueError, naming ``op`` and the argument, unless ``window`` is None, an int w >= 0 or a pair
+    (left, right) of such, ``dilation`` an int >= 1, ``block`` an int >= 0, ``summary`` None or
+    (stride, width) with 0 < width <= stride, ``global_tokens`` None, an int >= 0 or a 1-D
+    integer tensor / list of positions (checked against n by ``pattern_global_flags``),
+    ``random_blocks`` None or (rb, probability) with rb >= 1 and 0 <= probability <= 1, and at
+    least one component is given.  -> a dict of Python values: window (left, right) or None,
+    dilation, block, summary (stride, width) or None, global_tokens, global_rows,
+    random_blocks (rb, threshold) or None with threshold = round(probability * 2**31), causal."""
+    if window is not None:
+        if isinstance(window, (tuple, list)):
+            left, right = _pattern_pair(op, "window", window, "an int or (left, right)")
+        else:
+            left = right = window
+        window = (_pattern_int(op, "window", left, 0), _pattern_int(op, "window", right, 0))
+    dilation = _pattern_int(op, "dilation", dilation, 1)
+    block = _pattern_int(op, "block", block, 0)
+    if summary is not None:
+        stride, width = _pattern_pair(op, "summary", summary, "(stride, width)")
+        stride, width = _pattern_int(op, "summary", stride, 1), _pattern_int(op, "summary", width, 1)
+        if width > stride:
+            raise ValueError(f"{op}: summary needs 0 < width <= stride, got stride {stride}, width {width}")
+        summary = (stride, width)
+    if global_tokens is not None:
+        if torch.is_tensor(global_tokens):
+            if global_tokens.dim() != 1 or global_tokens.dtype.is_floating_point or global_tokens.dtype.is_complex \
+                    or global_tokens.dtype == torch.bool:
+                raise ValueError(f"{op}: global_tokens must be an int or a 1-D integer tensor / list of positions, "
+                                 f"got {global_tokens.dtype} {tuple(global_tokens.shape)}")
+        elif isinstance(global_tokens, (tuple, list)):
+            global_tokens = [_pattern_int(op, "global_tokens", g, 0) for g in global_tokens]
+        else:
+            global_tokens = _pattern_int(op, "global_tokens", global_tokens, 0)
+    if random_blocks is not None:
+        rb, probability = _pattern_pair(op, "random_blocks", random_blocks, "(rb, probability)")
+        rb = _pattern_int(op, "random_blocks", rb, 1)
+        if isinstance(probability, bool) or not isinstance(probability, (int, float)) or not 0.0 <= probability <= 1.0:
+            raise ValueError(f"{op}: the probability of random_blocks must lie in 0 .. 1, got {probability!r}")
+        random_blocks = (rb, round(probability * 2 ** 31))
+    if window is None and block == 0 and summary is None and global_tokens is None and random_blocks is None:
+        raise ValueError(f"{op}: a pattern needs at least one of window / block / summary / global_tokens / "
+                         f"random_blocks")
+    return dict(window=window, dilation=dilation, block=block, summary=summary, global_tokens=global_tokens,
+                global_rows=bool(global_rows), random_blocks=random_blocks, causal=bool(causal))
+
+
+def pattern_global_flags(op, global_tokens, n, device):
+    """bool [n] on ``device``: True at the first ``g`` positions (int ``g``) or at the listed
+    ones; None for None.  ValueError for a position outside 0 .. n - 1 (a count outside 0 .. n)."""
+    if global_tokens is None:
+        return None
+    flags = torch.zeros(n, dtype=torch.bool, device=device)
+    if isinstance(global_tokens, int):
+        if global_tokens > n:
+            raise ValueError(f"{op}: global_tokens = {global_tokens} is outside 0 .. {n}")
+        flags[:global_tokens] = True
+        return flags
+    positions = torch.as_tensor(global_tokens, dtype=torch.int64).reshape(-1)
+    if positions.numel() > 0:
+        low, high = int(positions.min()), int(positions.max())
+        if low < 0 or high >= n:
+            raise ValueError(f"{op}: global_tokens holds position {low if low < 0 else high}, outside 0 .. {n - 1}")
+        flags[positions.to(device)] = True
+    return flags
+
+
+def check_pattern_sizes(op, m, n, offset):
+    """ValueError unless m, n >= 0 and offset are integers.  -> (m, n, offset) as Python ints"""
+    return _pattern_int(op, "m", m, 0), _pattern_int(op, "n", n, 0), _pattern_int(op, "offset", offset, -2 ** 62)
+
+
+def pattern_rng_state(op, rng_state):
+    """ValueError unless ``rng_state`` is an int64 [2] tensor {seed, offset}, offset a multiple of 4"""
+    if not torch.is_tensor(rng_state) or rng_state.dtype != torch.int64 or rng_state.numel() != 2:
+        raise ValueError(f"{op}: rng_state must be an int64 [2] tensor {{seed, offset}}")
+    return rng_state
+
+
+def attention_pattern_csr(m, n, offset=0, window=None, dilation=1, block=0, global_tokens=None, global_rows=True,
+                          summary=None, random_blocks=None, causal=False, device=None, rng_state=None):
+    """The CSR topology of a structured attention pattern over ``m`` query rows and ``n`` key
+    columns, built on the device from its rule with no dense mask (csrc/topology.hip).
+
+    The rule: row r sits at position ``p = r + offset`` and ``d = c - p``; entry (r, c) is kept
+    iff (not ``causal`` or d <= 0) and at least one component keeps it --
+    ``window=(left, right)`` (an int w: (w, w)) with ``dilation``: ``-left * dilation <= d <=
+    right * dilation`` and ``d % dilation == 0``; ``block=b``: ``c // b == p // b``;
+    ``summary=(stride, width)``: ``c % stride >= stride - width``; ``global_tokens`` (an int g:
+    the first g positions; or a 1-D integer tensor / list of positions): ``flag[c]``, or, with
+    ``global_rows``, ``0 <= p < n and flag[p]``; ``random_blocks=(rb, probability)``:
+    ``key(r // rb, c // rb) < round(probability * 2**31)`` with ``random_csr``'s key stream,
+    ``key(R, C) = Philox(seed, (offset_rng / 4, C >> 2, R))[C & 3] & 0x7fffffff``.  Columns ascend
+    inside a row, an entry appears once, a row may be empty.
+
+    -> (row_indices, row_offsets, column_indices, rng_state).  Without ``random_blocks`` no
+    generator state is consumed and ``rng_state`` is None; with them it is the int64 [2]
+    {seed, offset} the call drew from the device's default generator (4, as ``random_csr``), or
+    the ``rng_state`` given, which reproduces the call that returned it.  Four launches and one
+    synchronisation; nothing of size ``m * n`` is allocated.  Raises ValueError for an argument
+    outside the contract, RuntimeError for a CPU device and for sizes
+    ``capi.attention_pattern_launch_shape`` does not serve (more than 16384 rows, ``m * n``
+    above INT_MAX, ``|offset| >= 2**30``): ``topology.AttentionPattern.build`` serves those."""
+    op = "attention_pattern_csr"
+    m, n, offset = check_pattern_sizes(op, m, n, offset)
+    rule = check_pattern_arguments(op, window, dilation, block, global_tokens, global_rows, summary, random_blocks,
+                                   causal)
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise RuntimeError(f"{op}: GPU devices only (topology.AttentionPattern.build serves the CPU)")
+    if m > _INT_MAX or n > _INT_MAX or abs(offset) >= PATTERN_MAX_OFFSET:
+        raise RuntimeError(f"{op}: the sizes are beyond what the kernels serve (capi.attention_pattern_launch_shape "
+                           f"states the limits); take topology.AttentionPattern.build")
+    flags = pattern_global_flags(op, rule["global_tokens"], n, device)
+    if rule["random_blocks"] is None:
+        rng_state = None
+    elif rng_state is not None:
+        rng_state = pattern_rng_state(op, rng_state).to(device).contiguous()
+    # the products the kernel compares with, clamped beyond every |c - p| it can meet
+    reach = PATTERN_REACH
+    left, right = (-1, 0) if rule["window"] is None else (min(w * rule["dilation"], reach) for w in rule["window"])
+    stride, width = (0, 0) if rule["summary"] is None else rule["summary"]
+    rb, threshold = (0, 0) if rule["random_blocks"] is None else rule["random_blocks"]
+    out = _ops.attention_pattern_csr(
+        m, n, offset, left, right, min(rule["dilation"], reach), min(rule["block"], _INT_MAX),
+        min(stride, _INT_MAX), min(stride - width, _INT_MAX), min(rb, _INT_MAX), threshold, rule["causal"],
+        rule["global_rows"], None if flags is None else flags.view(torch.uint8), device, rng_state)
+    return tuple(out) + ((None,) if len(out) == 3 else ())
 
 
 def check_regrow_arguments(values, row_offsets, column_indices, drop_counts, scores):

@@ -826,3 +826,151 @@ def dense_to_sparse_3d(mask):
         column_indices.append(csr.col_indices().to(torch.int32))
         nonzeros.append(int(offsets[-1]))
     return (torch.stack(row_indices), torch.stack(row_offsets), torch.cat(column_indices), nonzeros)
+
+
+_PATTERN_SLAB = 2 ** 24     # elements of the largest mask image the torch path of a pattern holds
+_INT64_MAX = 2 ** 63 - 1
+
+
+def _pattern_keys(first_row, rows, columns, seed, offset, device):
+    """int64 [rows, columns]: ``key(R, C)`` of ``ops.attention_pattern_csr`` for the block rows
+    ``first_row .. first_row + rows - 1`` and the block columns ``0 .. columns - 1``"""
+    seed, block = int(seed) & 0xffffffffffffffff, (int(offset) & 0xffffffffffffffff) // 4
+    index = dict(dtype=torch.int64, device=device)
+    quads = torch.arange((columns + 3) // 4, **index)[None, :]
+    block_rows = (torch.arange(first_row, first_row + rows, **index)[:, None]) & _LO32
+    words = _philox4x32_10((seed & _LO32, seed >> 32),
+                           (torch.full((1, 1), block & _LO32, **index), torch.full((1, 1), block >> 32, **index),
+                            quads, block_rows))
+    return torch.stack(words, dim=2).reshape(rows, -1)[:, :columns] & 0x7fffffff
+
+
+class AttentionPattern:
+    """A structured attention pattern -- sliding and dilated windows (Longformer, Sparse
+    Transformer), block-local attention, "fixed" summary columns, global tokens, BigBird's random
+    blocks, and the causal form of each -- as a rule that is built straight into a CSR topology:
+    ``SparseAttention(..., pattern=AttentionPattern(window=256, causal=True))``.
+
+    The rule is ``ops.attention_pattern_csr``'s: row r sits at ``p = r + offset``, ``d = c - p``,
+    and (r, c) is kept iff (not ``causal`` or d <= 0) and a component keeps it -- ``window``
+    (``(left, right)`` or an int) with ``dilation``, ``block``, ``summary=(stride, width)``,
+    ``global_tokens`` (a count or positions; ``global_rows``: their rows are full as well),
+    ``random_blocks=(rb, probability)``.  The arguments are checked here
+    (``ops.check_pattern_arguments``); positions are checked against n when a pattern is built."""
+
+    def __init__(self, window=None, dilation=1, block=0, global_tokens=None, global_rows=True, summary=None,
+                 random_blocks=None, causal=False):
+        self.arguments = dict(window=window, dilation=dilation, block=block, global_tokens=global_tokens,
+                              global_rows=global_rows, summary=summary, random_blocks=random_blocks, causal=causal)
+        self.rule = ops.check_pattern_arguments("AttentionPattern", **self.arguments)
+
+    def __repr__(self):
+        given = ", ".join(f"{k}={v!r}" for k, v in self.arguments.items()
+                          if v is not None and not (k == "dilation" and v == 1) and not (k == "block" and v == 0)
+                          and not (k == "global_rows" and v is True) and not (k == "causal" and v is False))
+        return f"AttentionPattern({given})"
+
+    @property
+    def random(self):
+        """whether the pattern draws random blocks (and so has an ``rng_state``)"""
+        return self.rule["random_blocks"] is not None
+
+    def _state(self, op, device, rng_state):
+        """(seed, offset, state tensor) of a torch-path build: the ``rng_state`` given or a fresh
+        draw (``_draw_philox_state``); Nones for a pattern without random blocks"""
+        if not self.random:
+            return None, None, None
+        if rng_state is None:
+            seed, offset = _draw_philox_state(device)
+            state = torch.tensor([seed, offset], dtype=torch.int64, device=device)
+        else:
+            state = ops.pattern_rng_state(op, rng_state)
+            seed, offset = (int(v) for v in state.tolist())
+        if offset % 4 != 0:
+            raise ValueError(f"{op}: the offset of rng_state must be a multiple of 4, got {offset}")
+        return seed, offset, state
+
+    def _mask_rows(self, first, last, n, offset, flags, seed, rng_offset, device):
+        """bool [last - first, n]: the rule at the rows ``first .. last - 1``"""
+        rule = self.rule
+        index = dict(dtype=torch.int64, device=device)
+        rows = torch.arange(first, last, **index)[:, None]
+        p = rows + offset
+        c = torch.arange(n, **index)[None, :]
+        d = c - p
+        keep = torch.zeros(last - first, n, dtype=torch.bool, device=device)
+        if rule["window"] is not None:
+            dilation = min(rule["dilation"], _INT64_MAX)
+            left, right = (min(w * rule["dilation"], _INT64_MAX) for w in rule["window"])
+            keep |= (d >= -left) & (d <= right) & (d % dilation == 0)
+        if rule["block"] > 0:
+            b = min(rule["block"], _INT64_MAX)
+            keep |= torch.div(c, b, rounding_mode="floor") == torch.div(p, b, rounding_mode="floor")
+        if rule["summary"] is not None:
+            stride, width = rule["summary"]
+            # (a stride beyond int64 is beyond every column: c mod stride is c)
+            keep |= (c % min(stride, _INT64_MAX)) >= min(stride - width, _INT64_MAX)
+        if flags is not None:
+            keep |= flags[None, :]
+            if rule["global_rows"] and n > 0:
+                keep |= (p >= 0) & (p < n) & flags[p.clamp(0, n - 1)]
+        if rule["random_blocks"] is not None:
+            rb, threshold = rule["random_blocks"]
+            rb = min(rb, _INT64_MAX)
+            first_block, last_block = first // rb, (last - 1) // rb
+            keys = _pattern_keys(first_block, last_block - first_block + 1, (n - 1) // rb + 1 if n > 0 else 0,
+                                 seed, rng_offset, device)
+            block_rows = torch.div(rows[:, 0], rb, rounding_mode="floor") - first_block
+            block_columns = torch.div(c[0], rb, rounding_mode="floor")
+            keep |= (keys < threshold)[block_rows][:, block_columns]
+        if rule["causal"]:
+            keep &= d <= 0
+        return keep
+
+    def dense_mask(self, m, n=None, offset=0, device="cpu", rng_state=None):
+        """bool [m, n]: the rule itself, in torch -- for tests and for looking at a pattern.  A
+        pattern with random blocks needs the ``rng_state`` (int64 [2]) of the build it shows."""
+        op = "AttentionPattern.dense_mask"
+        m, n, offset = ops.check_pattern_sizes(op, m, m if n is None else n, offset)
+        device = torch.device(device)
+        if self.random and rng_state is None:
+            raise ValueError(f"{op}: a pattern with random_blocks needs the rng_state of the build it shows "
+                             f"(build(..., return_rng_state=True))")
+        seed, rng_offset, _ = self._state(op, device, rng_state)
+        flags = ops.pattern_global_flags(op, self.rule["global_tokens"], n, device)
+        return self._mask_rows(0, m, n, offset, flags, seed, rng_offset, device)
+
+    def build(self, m, n=None, offset=0, device=None, rng_state=None, return_rng_state=False):
+        """-> (row_indices, row_offsets, column_indices), int32, of the pattern over ``m`` query
+        rows and ``n`` key columns (default m) at that ``offset`` (``n - m`` aligns the last query
+        with the last key: decoding against a cache).
+
+        A GPU ``device`` takes the device kernels (``ops.attention_pattern_csr``: four launches,
+        one synchronisation, no ``[m, n]`` array) where ``capi.attention_pattern_launch_shape``
+        serves the sizes; the CPU, ``enable_device_build(False)`` and the sizes beyond (more than
+        16384 rows, ``m * n`` above INT_MAX, ``|offset| >= 2**30``) take the same rule in torch,
+        in row slabs of at most 2**24 mask elements -- the same integers.  ``rng_state`` (int64
+        [2] {seed, offset}) reproduces a pattern with random blocks on any path; without one a GPU
+        call draws 4 from the device's default generator (``torch.manual_seed`` makes runs
+        repeat), a CPU call a seed from torch's CPU generator.  ``return_rng_state``: the state
+        used (None without random blocks) is appended."""
+        op = "AttentionPattern.build"
+        m, n, offset = ops.check_pattern_sizes(op, m, m if n is None else n, offset)
+        device = torch.device("cpu" if device is None else device)
+        if _served(device, "attention_pattern_launch_shape", m, n, offset):
+            row_indices, row_offsets, column_indices, state = ops.attention_pattern_csr(
+                m, n, offset, device=device, rng_state=rng_state, **self.arguments)
+        else:
+            seed, rng_offset, state = self._state(op, device, rng_state)
+            flags = ops.pattern_global_flags(op, self.rule["global_tokens"], n, device)
+            slab = max(1, _PATTERN_SLAB // max(n, 1))
+            counts, columns = [torch.zeros(1, dtype=torch.int64, device=device)], []
+            for first in range(0, m, slab):
+                mask = self._mask_rows(first, min(m, first + slab), n, offset, flags, seed, rng_offset, device)
+                counts.append(mask.sum(dim=1))
+                columns.append(mask.nonzero()[:, 1].to(torch.int32))
+            row_offsets = torch.cumsum(torch.cat(counts), 0).to(torch.int32)
+            column_indices = torch.cat(columns) if columns else torch.zeros(0, dtype=torch.int32, device=device)
+            row_indices = diffsort(row_offsets)
+        result = (row_indices, row_offsets, column_indices)
+        return result + (state,) if return_rng_state else result
