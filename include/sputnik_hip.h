@@ -991,6 +991,55 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_forward_planned(int m, in
                              sputnik_hip_stream_t stream);
 
 /*
+ * The same forward on the MATRIX CORES: a masked flash attention over 64-column key tiles
+ * (v_mfma_f32_32x32x16_{f16,bf16}; attention_mfma.hip).  Opt-in; operands, `out`, `lse` and
+ * the addressing are those of sputnik_hip_sparse_attention_heads_forward, and
+ * sputnik_hip_sparse_attention_tiles_supported checks the same rules on the host, plus
+ * sputnik_hip_sparse_attention_tiles_plan_bytes(m, n) < 2^31.
+ * The plan is topology-only and its own: one 64-bit word per (row, 64 columns) with a bit per
+ * entry, and per block of 128 rows the ascending list of key tiles that hold an entry; three
+ * launches, no host synchronisation, bitwise reproducible, any column order inside a row.
+ * sputnik_hip_sparse_attention_tiles_plan returns SPUTNIK_HIP_UNSUPPORTED when m or n is 0 or
+ * the plan would take 2^31 bytes or more.  The forward always runs from a plan (the three
+ * topology arrays are part of the argument list for symmetry and are not read).
+ * Where the contract DIFFERS from the vector kernels:
+ *   - no duplicate columns within a row: the bitmap collapses duplicates, the vector kernels
+ *     count them twice;
+ *   - V must be finite in every key row that shares a 64-column tile with a kept entry of the
+ *     128-row block: on a dense tile a weight of exactly 0 times inf is NaN.  (Key rows at n
+ *     and beyond are zero-filled, never read.)
+ *   - the softmax weights are rounded once to `dtype` before they multiply V (the row sum and
+ *     lse take the unrounded float32 weights).
+ * Not served (SPUTNIK_HIP_UNSUPPORTED): d != 64, float32 storage, a mask without entries;
+ * there is no dropout form and no many-mask form.
+ */
+SPUTNIK_HIP_API size_t sputnik_hip_sparse_attention_tiles_plan_bytes(int m, int n);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_tiles_plan(int m, int n, int nonzeros,
+                             const int* row_offsets, const int* column_indices, void* plan,
+                             size_t plan_bytes, sputnik_hip_stream_t stream);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_tiles_supported(int m, int n, int d, int nonzeros,
+                             int batch, int heads, int dtype, int out_type, const void* q,
+                             int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                             const void* k, int64_t k_batch_stride, int64_t k_head_stride,
+                             int64_t k_row_stride, const void* v, int64_t v_batch_stride,
+                             int64_t v_head_stride, int64_t v_row_stride, const void* out,
+                             int64_t out_batch_stride, int64_t out_head_stride,
+                             int64_t out_row_stride);
+
+SPUTNIK_HIP_API int sputnik_hip_sparse_attention_tiles_forward(int m, int n, int d, int nonzeros,
+                             int batch, int heads, const int* row_indices, const int* row_offsets,
+                             const int* column_indices, int dtype, const void* q,
+                             int64_t q_batch_stride, int64_t q_head_stride, int64_t q_row_stride,
+                             const void* k, int64_t k_batch_stride, int64_t k_head_stride,
+                             int64_t k_row_stride, const void* v, int64_t v_batch_stride,
+                             int64_t v_head_stride, int64_t v_row_stride, float scale, void* out,
+                             int out_type, int64_t out_batch_stride, int64_t out_head_stride,
+                             int64_t out_row_stride, float* lse, int64_t lse_stride,
+                             const void* plan, size_t plan_bytes, sputnik_hip_stream_t stream);
+
+/*
  * The fused attention with one mask per batch element (the "many mask" layout below:
  * row_indices [masks * m], row_offsets [masks * (m + 1)] each starting at 0,
  * column_indices concatenated, `nonzeros` [masks] a HOST array).  `replicas` is a

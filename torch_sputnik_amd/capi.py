@@ -233,6 +233,12 @@ SIGNATURES = {
     "sputnik_hip_sparse_attention_heads_forward_planned": (_c_int, [_c_int] * 6 + [_c_ptr] * 3 + [_c_int] + [
         _c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [_c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64,
                                                _c_ptr, _c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_tiles_plan_bytes": (_c_size, [_c_int] * 2),
+    "sputnik_hip_sparse_attention_tiles_plan": (_c_int, [_c_int] * 3 + [_c_ptr] * 3 + [_c_size, _c_ptr]),
+    "sputnik_hip_sparse_attention_tiles_supported": (_c_int, [_c_int] * 8 + [_c_ptr, _c_i64, _c_i64, _c_i64] * 4),
+    "sputnik_hip_sparse_attention_tiles_forward": (_c_int, [_c_int] * 6 + [_c_ptr] * 3 + [_c_int] + [
+        _c_ptr, _c_i64, _c_i64, _c_i64] * 3 + [_c_float, _c_ptr, _c_int, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64,
+                                               _c_ptr, _c_size, _c_ptr]),
     "sputnik_hip_sparse_attention_many_mask_workspace_bytes": (_c_size, [_c_int] * 5),
     "sputnik_hip_sparse_attention_many_mask_plan": (_c_int, [_c_int] * 4 + [_c_ptr] * 5 + [_c_size, _c_ptr]),
     "sputnik_hip_sparse_attention_many_mask_forward": (_c_int, [_c_int] * 4 + [_c_ptr, _c_int] + [

@@ -1651,6 +1651,19 @@ int check_head_operands(const HeadOperand& q, const HeadOperand& k, const HeadOp
   return dtype;
 }
 
+// The context of a heads call: the [.., m, d] view the kernel writes of a fresh buffer laid out
+// [B, m, H, d] for 4-D operands (else as q), stored as `out_st`.
+Tensor head_context(const HeadOperand& q, at::ScalarType out_st) {
+  if (q.t.dim() == 4)
+    return at::empty({q.batch, q.rows, q.heads, q.d}, q.t.options().dtype(out_st)).permute({0, 2, 1, 3});
+  return at::empty(q.t.sizes(), q.t.options().dtype(out_st));
+}
+
+Tensor head_lse(const HeadOperand& q) {   // float32 [.., m]
+  std::vector<int64_t> shape(q.t.sizes().begin(), q.t.sizes().end() - 1);
+  return at::empty(shape, q.t.options().dtype(at::kFloat));
+}
+
 // q [.., m, 64], k and v [.., n, 64] of one half type (any strides with a unit last one);
 // out in the layout of the [B, m, H, d] buffer it views ([B, m, E] for 4-D operands), stored
 // as out_type (0 float32, else the operands' type); lse [.., m] float32 on request.
@@ -1670,16 +1683,9 @@ std::vector<Tensor> sparse_attention_heads_run(const Tensor& q_in, const Tensor&
   const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, q.t);
   const auto out_st = out_type == SPUTNIK_HIP_F32 ? at::kFloat : st;
 
-  Tensor buffer, out;   // out: the [.., m, d] view of `buffer` the kernel writes
-  if (q.t.dim() == 4) {
-    buffer = at::empty({q.batch, q.rows, q.heads, q.d}, q.t.options().dtype(out_st));
-    out = buffer.permute({0, 2, 1, 3});
-  } else {
-    out = buffer = at::empty(q.t.sizes(), q.t.options().dtype(out_st));
-  }
+  const Tensor out = head_context(q, out_st);
   const HeadOperand o = head_operand(out, "out");
-  std::vector<int64_t> lse_shape(q.t.sizes().begin(), q.t.sizes().end() - 1);
-  Tensor lse = want_lse ? at::empty(lse_shape, q.t.options().dtype(at::kFloat)) : Tensor();
+  Tensor lse = want_lse ? head_lse(q) : Tensor();
 
   const bool served = sputnik_hip_sparse_attention_heads_supported(
       m, n, d, topo.nonzeros, batch, heads, dtype, static_cast<int>(out_type), q.t.data_ptr(),
@@ -1723,6 +1729,75 @@ std::vector<Tensor> sparse_attention_heads_run(const Tensor& q_in, const Tensor&
                            drop),
                drop != nullptr ? "sparse_attention_heads_dropout" : "sparse_attention_heads");
   return attention_result(out, lse, want_lse, drop);
+}
+
+// ---- the same forward on the matrix cores (sputnik_hip.h: sparse_attention_tiles_*) ----
+// The tile plan of an m x n mask: the mask's bit planes and each 128-row block's list of
+// occupied 64-column key tiles.  Shapes the plan does not serve give an empty plan (16 bytes),
+// which sparse_attention_tiles never reads: it takes the vector route then.
+Tensor sparse_attention_tiles_plan(int64_t m64, int64_t n64, const Tensor& row_offsets,
+                                   const Tensor& column_indices) {
+  TORCH_CHECK(row_offsets.is_cuda(), "row_offsets must be a GPU (HIP) tensor");
+  const c10::DeviceGuard guard(row_offsets.device());
+  const int m = to_int(m64, "m"), n = to_int(n64, "n");
+  const Tensor offsets = as_index(row_offsets, "row_offsets", row_offsets);
+  const Tensor columns = as_index(column_indices, "column_indices", row_offsets);
+  TORCH_CHECK(offsets.size(0) == m64 + 1, "row_offsets should have m + 1 = ", m64 + 1, " entries, got ",
+              offsets.size(0));
+  const int nonzeros = to_int(columns.size(0), "nonzeros");
+  const size_t bytes = sputnik_hip_sparse_attention_tiles_plan_bytes(m, n);
+  const bool served = bytes > 0 && bytes < (size_t{1} << 31);
+  Tensor plan = make_plan_tensor(served ? bytes : 0, row_offsets);
+  if (served)
+    check_status(sputnik_hip_sparse_attention_tiles_plan(
+                     m, n, nonzeros, offsets.data_ptr<int>(), columns.data_ptr<int>(), plan.data_ptr(), bytes,
+                     current_stream(row_offsets)),
+                 "sparse_attention_tiles_plan");
+  return plan;
+}
+
+// sparse_attention_heads' operands and results, through the tile kernel where it serves the
+// call (a plan is made when none is given); anything else IS sparse_attention_heads.
+std::vector<Tensor> sparse_attention_tiles(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in,
+                                           const Tensor& row_indices, const Tensor& row_offsets,
+                                           const Tensor& column_indices, double scale, int64_t out_type,
+                                           bool want_lse, const c10::optional<Tensor>& plan_in) {
+  const HeadOperand q = head_operand(q_in, "query"), k = head_operand(k_in, "key"),
+                    v = head_operand(v_in, "value");
+  const int dtype = check_head_operands(q, k, v, out_type, "sparse_attention_tiles");
+  const c10::DeviceGuard guard(q.t.device());
+  const int m = to_int(q.rows, "m"), n = to_int(k.rows, "n"), d = to_int(q.d, "d");
+  const int batch = to_int(q.batch, "batch"), heads = to_int(q.heads, "heads");
+  const Topology topo = check_topology(m, row_indices, row_offsets, column_indices, q.t);
+  const Tensor out = head_context(q, out_type == SPUTNIK_HIP_F32 ? at::kFloat : q.t.scalar_type());
+  const HeadOperand o = head_operand(out, "out");
+  if (!sputnik_hip_sparse_attention_tiles_supported(
+          m, n, d, topo.nonzeros, batch, heads, dtype, static_cast<int>(out_type), q.t.data_ptr(),
+          q.batch_stride, q.head_stride, q.row_stride, k.t.data_ptr(), k.batch_stride, k.head_stride,
+          k.row_stride, v.t.data_ptr(), v.batch_stride, v.head_stride, v.row_stride, o.t.data_ptr(),
+          o.batch_stride, o.head_stride, o.row_stride))
+    return sparse_attention_heads_run(q_in, k_in, v_in, row_indices, row_offsets, column_indices, scale,
+                                      out_type, want_lse, c10::nullopt);
+  const size_t bytes = sputnik_hip_sparse_attention_tiles_plan_bytes(m, n);
+  Tensor plan;
+  if (plan_in.has_value()) {
+    check_plan(*plan_in, bytes, q.t);
+    plan = *plan_in;
+  } else {
+    plan = sparse_attention_tiles_plan(m, n, topo.row_offsets, topo.column_indices);
+  }
+  Tensor lse = want_lse ? head_lse(q) : Tensor();
+  check_status(sputnik_hip_sparse_attention_tiles_forward(
+                   m, n, d, topo.nonzeros, batch, heads, topo.row_indices.data_ptr<int>(),
+                   topo.row_offsets.data_ptr<int>(), topo.column_indices.data_ptr<int>(), dtype,
+                   q.t.data_ptr(), q.batch_stride, q.head_stride, q.row_stride, k.t.data_ptr(),
+                   k.batch_stride, k.head_stride, k.row_stride, v.t.data_ptr(), v.batch_stride,
+                   v.head_stride, v.row_stride, static_cast<float>(scale), o.t.data_ptr(),
+                   static_cast<int>(out_type), o.batch_stride, o.head_stride, o.row_stride,
+                   want_lse ? lse.data_ptr<float>() : nullptr, static_cast<int64_t>(m), plan.data_ptr(), bytes,
+                   current_stream(q.t)),
+               "sparse_attention_tiles");
+  return attention_result(out, lse, want_lse, nullptr);
 }
 
 // y [batch, seq, out] = x W^T per batch element in ROW orientation (sputnik_hip.h:
@@ -2955,6 +3030,11 @@ TORCH_LIBRARY(torch_sputnik, m) {
       "sparse_attention_heads(Tensor query, Tensor key, Tensor value, Tensor row_indices, "
       "Tensor row_offsets, Tensor column_indices, float scale, int out_type, bool want_lse, "
       "Tensor? plan) -> Tensor[]");
+  m.def("sparse_attention_tiles_plan(int m, int n, Tensor row_offsets, Tensor column_indices) -> Tensor");
+  m.def(
+      "sparse_attention_tiles(Tensor query, Tensor key, Tensor value, Tensor row_indices, "
+      "Tensor row_offsets, Tensor column_indices, float scale, int out_type, bool want_lse, "
+      "Tensor? plan) -> Tensor[]");
   m.def(
       "half_linear_rows(int out_features, Tensor image, int values_type, Tensor x, Tensor? out, "
       "int out_type) -> Tensor");
@@ -3087,6 +3167,8 @@ TORCH_LIBRARY_IMPL(torch_sputnik, CUDA, m) {
   m.impl("sparse_attention_plan", &sparse_attention_plan);
   m.impl("sparse_attention_planned", &sparse_attention_planned);
   m.impl("sparse_attention_heads", &sparse_attention_heads);
+  m.impl("sparse_attention_tiles_plan", &sparse_attention_tiles_plan);
+  m.impl("sparse_attention_tiles", &sparse_attention_tiles);
   m.impl("half_linear_rows", &half_linear_rows);
   m.impl("spmm_many_mask", &spmm_many_mask);
   m.impl("sddmm_many_mask", &sddmm_many_mask);

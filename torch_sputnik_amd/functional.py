@@ -239,6 +239,12 @@ class PlanCache(_TopologyCache):
                                                             column_indices),
                           row_indices, row_offsets, column_indices)
 
+    def attention_tiles(self, m, n, row_offsets, column_indices):
+        """Plan of the matrix-core attention (ops.sparse_attention_tiles_plan)."""
+        return self._plan("attention_tiles", (m, n),
+                          lambda: ops.sparse_attention_tiles_plan(m, n, row_offsets, column_indices),
+                          row_offsets, column_indices)
+
     def attention_many_mask(self, b, m, n, d, nonzeros, row_indices, row_offsets, column_indices):
         """Plan of the many-mask attention (ops.sparse_attention_many_mask_plan); `nonzeros` a
         host list / tensor, part of the key."""
@@ -1118,9 +1124,16 @@ def _merge_heads(g, like, heads):
         like.shape).to(like.dtype)
 
 
-def _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale, p=0.0):
-    """-> (context [B, S, E], None, rng_state or None), as `_attention_forward`."""
+def _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale, p=0.0,
+                     matrix_cores=False):
+    """-> (context [B, S, E], None, rng_state or None), as `_attention_forward`.
+    `matrix_cores`: the tile kernel (ops.sparse_attention_tiles) where there is no dropout."""
     q, k, v = _heads(query, heads), _heads(key, heads), _heads(value, heads)
+    if matrix_cores and p == 0.0 and query.is_cuda:
+        plan = None if _plans is None else _plans.attention_tiles(q.size(-2), k.size(-2), row_offsets,
+                                                                  column_indices)
+        out = ops.sparse_attention_tiles(q, k, v, row_indices, row_offsets, column_indices, scale, plan=plan)
+        return out.transpose(1, 2).reshape(query.size(0), query.size(1), -1), None, None
     plan = None if _plans is None else _plans.attention(q.size(-2), k.size(-2), q.size(-1), row_indices,
                                                         row_offsets, column_indices)
     operands = (q, k, v, row_indices, row_offsets, column_indices, scale)
@@ -1141,10 +1154,10 @@ class SparseAttentionHeadsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, query, key, value, heads, row_indices, row_offsets, column_indices, scale,
-                dropout_p=0.0):
+                dropout_p=0.0, matrix_cores=False):
         ctx.heads, ctx.scale, ctx.p = int(heads), float(scale), float(dropout_p)
         out, _, rng_state = _attention_heads(query, key, value, heads, row_indices, row_offsets,
-                                             column_indices, scale, ctx.p)
+                                             column_indices, scale, ctx.p, matrix_cores)
         ctx.save_for_backward(query, key, value, row_indices, row_offsets, column_indices, rng_state)
         return out
 
@@ -1155,11 +1168,11 @@ class SparseAttentionHeadsFunction(torch.autograd.Function):
         grads = _attention_backward(_single_mask_operators(topo, q.size(-2), k.size(-2)), q, k, v,
                                     ctx.scale, _contiguous(grad), ctx.needs_input_grad[:3], dropout)
         return (*(_merge_heads(g, x, ctx.heads) for g, x in zip(grads, (query, key, value))),
-                None, None, None, None, None, None)
+                None, None, None, None, None, None, None)
 
 
 def sparse_attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices, scale,
-                           dropout_p=0.0):
+                           dropout_p=0.0, matrix_cores=False):
     """softmax(scale * q k^T at the mask) v per head for [B, S, E] tensors in float16 /
     bfloat16 (query [B, m, E], key and value [B, n, E], any strides with a unit last one),
     E = heads * D: head h is columns h*D .. h*D+D-1 of every row -- read as strided views by
@@ -1167,13 +1180,18 @@ def sparse_attention_heads(query, key, value, heads, row_indices, row_offsets, c
     context [B, m, E] in the inputs' type (rounded once); scores, weights and sums are
     float32.  Differentiable: the backward recomputes the weights (SparseAttentionHeadsFunction),
     and the gradient reaches q, k and v.  ``dropout_p``: dropout on the attention weights
-    (replica r = b * heads + h of the library's mask contract)."""
+    (replica r = b * heads + h of the library's mask contract).  ``matrix_cores``: the forward
+    runs the tile kernel on the matrix cores (ops.sparse_attention_tiles, with its contract: no
+    duplicate columns in a row, weights rounded once to the inputs' type); the backward is the
+    same recomputing one.  With ``dropout_p > 0``, on CPU tensors or for a call the tile kernel
+    does not serve the flag changes nothing."""
     p = ops.check_dropout_p(dropout_p)
+    matrix_cores = bool(matrix_cores)
     if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
         return SparseAttentionHeadsFunction.apply(query, key, value, heads, row_indices, row_offsets,
-                                                  column_indices, scale, p)
+                                                  column_indices, scale, p, matrix_cores)
     return _attention_heads(query, key, value, heads, row_indices, row_offsets, column_indices,
-                            scale, p)[0]
+                            scale, p, matrix_cores)[0]
 
 
 # ---------------------------------------------------------------------------

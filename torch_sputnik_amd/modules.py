@@ -408,7 +408,7 @@ class SparseAttention(nn.Module):
                  sparsity=0.9, mask_generator=None, differentiable_softmax=False,
                  fused_inference=True, low_memory_training=False, fused_training=None,
                  half_storage=False, attention_dropout=0.0, fused_backward=False,
-                 pattern=None, pattern_rng_state=None):
+                 pattern=None, pattern_rng_state=None, attention_matrix_cores=False):
         super().__init__()
         self.attention_dropout = ops.check_dropout_p(attention_dropout)
         if half_storage and fused_backward:
@@ -457,6 +457,10 @@ class SparseAttention(nn.Module):
         # float16 / bfloat16 inputs (all three of one type) stay in that type through the
         # forward pass: see _forward_half_storage.  Off: today's widening path.
         self.half_storage = bool(half_storage)
+        # The half-storage forward's attention on the matrix cores
+        # (functional.sparse_attention_heads(matrix_cores=True)): read in
+        # _forward_half_storage only.
+        self.attention_matrix_cores = bool(attention_matrix_cores)
         # Training on the fused forward and the fused backward: nothing of
         # size [B*H, nnz] exists at any time, the backward included.  Takes precedence over
         # low_memory_training; shapes the fused backward does not serve (head dimension other
@@ -625,7 +629,9 @@ class SparseAttention(nn.Module):
         float32 gradients, half inputs half ones).  ``fused_inference``,
         ``low_memory_training``, ``differentiable_softmax`` and ``parallel_projections`` do
         not apply in this mode.  Shapes the kernels do not serve (head dimension other than
-        64, sizes off the tiles) are composed from the typed operators."""
+        64, sizes off the tiles) are composed from the typed operators.
+        ``attention_matrix_cores=True`` runs the attention's forward as the tile kernel on the
+        matrix cores (no effect with attention dropout in training mode)."""
         def project(net, x):
             return functional.half_linear_rows(net.output_features, net.input_features, net.values,
                                                net.row_indices, net.row_offsets, net.column_indices, x)
@@ -633,7 +639,8 @@ class SparseAttention(nn.Module):
         q, k, v = (project(net, x) for net, x in zip(self.linears, (query, key, value)))
         context = functional.sparse_attention_heads(q, k, v, self.num_heads, self.row_indices,
                                                     self.row_offsets, self.column_indices,
-                                                    1.0 / math.sqrt(self.head_dim), self._dropout_p())
+                                                    1.0 / math.sqrt(self.head_dim), self._dropout_p(),
+                                                    matrix_cores=self.attention_matrix_cores)
         return project(self.linears[-1], context)
 
     @staticmethod

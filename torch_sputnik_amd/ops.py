@@ -1096,6 +1096,33 @@ def sparse_attention_heads(query, key, value, row_indices, row_offsets, column_i
     return outs if with_lse else outs[0]
 
 
+def sparse_attention_tiles_plan(m, n, row_offsets, column_indices):
+    """The plan of the matrix-core attention (sparse_attention_tiles) for an m x n mask: a
+    64-bit word per (row, 64 columns) with a bit per entry, and for every block of 128 rows the
+    ascending list of the 64-column key tiles that hold an entry.  Topology only, no host
+    synchronisation, any column order inside a row; a row must not repeat a column."""
+    return _ops.sparse_attention_tiles_plan(int(m), int(n), row_offsets, column_indices)
+
+
+def sparse_attention_tiles(query, key, value, row_indices, row_offsets, column_indices, scale,
+                           out_dtype=None, with_lse=False, plan=None):
+    """sparse_attention_heads on the MATRIX CORES: a masked flash attention that walks the
+    occupied 64-column key tiles of each block of 128 query rows and runs them as dense
+    v_mfma tiles.  Operand forms, `out_dtype`, `with_lse` and the output buffer's layout are
+    those of sparse_attention_heads; `plan` is sparse_attention_tiles_plan's (made per call
+    when None).  Scores, the softmax and every sum are float32; the weights are rounded once to
+    the operands' type before they multiply V (the row sum and lse take them unrounded).
+    Contract beyond sparse_attention_heads': no duplicate columns within a row (the plan
+    collapses them), and V finite in every key row that shares a 64-column tile with an entry
+    of the row block (0 * inf is NaN on a dense tile).  A call the kernel does not serve (head
+    dimension other than 64, unaligned views, a mask without entries) runs
+    sparse_attention_heads."""
+    out_code = _half_code(query.dtype if out_dtype is None else out_dtype)
+    outs = _ops.sparse_attention_tiles(query, key, value, row_indices, row_offsets, column_indices,
+                                       float(scale), out_code, bool(with_lse), plan)
+    return outs if with_lse else outs[0]
+
+
 def half_linear_rows_supported(out_features, in_features, seq, batch, nonzeros, values_dtype, tile_dtype):
     """Whether y [B, S, out] = x W^T (half_linear_rows) takes the matrix-core route."""
     from . import capi
