@@ -993,10 +993,13 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_forward_planned(int m, in
 /*
  * The same forward on the MATRIX CORES: a masked flash attention over 64-column key tiles
  * (v_mfma_f32_32x32x16_{f16,bf16}; attention_mfma.hip).  Opt-in; operands, `out`, `lse` and
- * the addressing are those of sputnik_hip_sparse_attention_heads_forward, and
- * sputnik_hip_sparse_attention_tiles_supported checks the same rules on the host, plus
- * sputnik_hip_sparse_attention_tiles_plan_bytes(m, n) < 2^31.
- * The plan is topology-only and its own: one 64-bit word per (row, 64 columns) with a bit per
+ * the addressing are those of sputnik_hip_sparse_attention_heads_forward, at head dimension
+ * d = 64 or 128 (the heads entries serve 64 only), and
+ * sputnik_hip_sparse_attention_tiles_supported checks the same rules on the host with that d
+ * (float16 / bfloat16, out_type float32 or dtype, 16-byte aligned bases and strides, no
+ * negative stride, every in-replica extent ((rows - 1) * row_stride + d) * element size below
+ * 2^32 bytes), plus sputnik_hip_sparse_attention_tiles_plan_bytes(m, n) < 2^31.
+ * The plan is topology-only (it does not depend on d) and its own: one 64-bit word per (row, 64 columns) with a bit per
  * entry, and per block of 128 rows the ascending list of key tiles that hold an entry; three
  * launches, no host synchronisation, bitwise reproducible, any column order inside a row.
  * sputnik_hip_sparse_attention_tiles_plan returns SPUTNIK_HIP_UNSUPPORTED when m or n is 0 or
@@ -1010,7 +1013,8 @@ SPUTNIK_HIP_API int sputnik_hip_sparse_attention_heads_forward_planned(int m, in
  *     and beyond are zero-filled, never read.)
  *   - the softmax weights are rounded once to `dtype` before they multiply V (the row sum and
  *     lse take the unrounded float32 weights).
- * Not served (SPUTNIK_HIP_UNSUPPORTED): d != 64, float32 storage, a mask without entries;
+ * Not served (SPUTNIK_HIP_UNSUPPORTED): d other than 64 and 128, float32 storage, a mask
+ * without entries;
  * there is no dropout form and no many-mask form.
  */
 SPUTNIK_HIP_API size_t sputnik_hip_sparse_attention_tiles_plan_bytes(int m, int n);

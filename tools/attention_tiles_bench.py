@@ -16,7 +16,13 @@ plan's time alone, the share of 128 x 64 tiles the kernel walks, and ``tiles_fas
 false only where the medians differ by more than the vector route's own p10 - p90 spread in
 that run, else "within spread".  The results of the two routes are compared (largest
 difference relative to the largest value) before anything is timed.  ``--out FILE`` appends
-the lines.  Kernel times alone: run with ``--rounds 2 --inner 1`` under
+the lines.
+
+``--head-dim 128``: H = 8 heads of 128 on the D = 128 instances of the tile kernel.  No fused
+vector kernel serves half storage there: the other route is what the same call cost before
+those instances existed, ``ops.sparse_attention_heads`` COMPOSED from the typed SDDMM, softmax
+and SpMM on per-head copies, and the keys read ``composed`` / ``composed_over_tiles`` (plus
+``head_dim``).  Kernel times alone: run with ``--rounds 2 --inner 1`` under
 ``rocprofv3 --kernel-trace --stats``."""
 import argparse
 import json
@@ -29,7 +35,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-BATCH, HEADS, D = 8, 8, 64
+BATCH, HEADS = 8, 8
 SHAPES = (
     ("config3_random_0.1", 1024, None),
     ("longformer_window_256_global_16", 4096, dict(window=256, global_tokens=16)),
@@ -73,6 +79,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--head-dim", type=int, choices=(64, 128), default=64)
     ap.add_argument("--out")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -81,6 +88,8 @@ def main():
     from torch_sputnik_amd import functional, ops, topology
 
     dev = torch.device("cuda:0")
+    D = args.head_dim
+    other = "vector" if D == 64 else "composed"
     lines = []
     for name, size, pattern in SHAPES:
         if pattern is None:
@@ -93,7 +102,7 @@ def main():
             topo = built.build(size, device=dev, rng_state=state if built.random else None)
         nonzeros = topo[2].numel()
         tile_plan = ops.sparse_attention_tiles_plan(size, size, topo[1], topo[2])
-        vector_plan = ops.sparse_attention_plan(size, size, D, *topo)
+        vector_plan = ops.sparse_attention_plan(size, size, D, *topo) if D == 64 else None
         blocks, tiles = (size + 127) // 128, (size + 63) // 64
         lists = tile_plan[:blocks * (1 + tiles) * 4].view(torch.int32).view(blocks, 1 + tiles)
         walked = int(lists[:, 0].sum())
@@ -104,19 +113,20 @@ def main():
             scale = 1.0 / D ** 0.5
             fns = {
                 "tiles": lambda: ops.sparse_attention_tiles(q, k, v, *topo, scale, plan=tile_plan),
-                "vector": lambda: ops.sparse_attention_heads(q, k, v, *topo, scale, plan=vector_plan),
+                other: lambda: ops.sparse_attention_heads(q, k, v, *topo, scale, plan=vector_plan),
                 "tiles_plan": lambda: ops.sparse_attention_tiles_plan(size, size, topo[1], topo[2]),
             }
-            a, b = fns["tiles"]().float(), fns["vector"]().float()
+            a, b = fns["tiles"]().float(), fns[other]().float()
             difference = float((a - b).abs().max() / b.abs().max())
             timed = measure(fns, args.rounds, args.warmup, args.inner)
-            spread = timed["vector"]["p90_us"] - timed["vector"]["p10_us"]
-            gap = timed["vector"]["median_us"] - timed["tiles"]["median_us"]
-            line = dict(case="sparse_attention_tiles vs sparse_attention_heads", shape=name, rows=size,
+            spread = timed[other]["p90_us"] - timed[other]["p10_us"]
+            gap = timed[other]["median_us"] - timed["tiles"]["median_us"]
+            extra = {} if D == 64 else {"head_dim": D}
+            line = dict(case="sparse_attention_tiles vs sparse_attention_heads", shape=name, rows=size, **extra,
                         batch=BATCH, heads=HEADS, dtype=str(dtype).replace("torch.", ""), nonzeros=nonzeros,
                         tiles_walked=walked, tiles_total=blocks * tiles,
                         largest_difference_over_largest_value=difference, **timed,
-                        vector_over_tiles=round(timed["vector"]["median_us"] / timed["tiles"]["median_us"], 2),
+                        **{other + "_over_tiles": round(timed[other]["median_us"] / timed["tiles"]["median_us"], 2)},
                         tiles_faster=(gap > 0) if abs(gap) > spread else "within spread")
             lines.append(line)
             print(json.dumps(line), flush=True)

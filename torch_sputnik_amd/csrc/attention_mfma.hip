@@ -1,5 +1,5 @@
 // Fused sparse attention forward on the matrix cores, for float16 / bfloat16 head views and
-// head dimension 64:
+// head dimension 64 or 128:
 //
 //   out[i, :] = sum_j softmax_j(scale * <q_i, k_j>) * v_j      j over the stored columns of row i
 //
@@ -18,7 +18,7 @@
 //
 // The kernel: one workgroup of four waves per (replica, 128-row block), a wave owns 32 query
 // rows.  Q is read once into registers as MFMA operand fragments.  Per occupied tile, K and V
-// (64 rows of 128 bytes each) are staged in LDS by direct global->LDS copies, double buffered:
+// (64 rows of 2 d bytes each) are staged in LDS by direct global->LDS copies, double buffered:
 //   1. S^T = K Q^T (A = K tile rows from LDS, B = the Q fragments): in the 32 x 32 accumulator
 //      layout a lane then holds ONE query row (lane & 31) and 2 x 16 key columns, so the row's
 //      64-bit mask word masks all of them by selects, and the row maximum is 31 in-lane
@@ -31,10 +31,14 @@
 //      that order by the transposing 4 x 16 read (ds_read_b64_tr_b16), whose four rows are the
 //      keys 16s + 8t + 4h .. + 3.  The accumulator again holds one query row per lane, so the
 //      rescale by exp2(old max - new max) is one factor per lane.
-// LDS images are swizzled in the copies' per-lane SOURCE address (mfma_gemm.h): K's 16-byte
-// slot g of row r lands in slot g ^ ((r >> 1) & 7) for the ds_read_b128 fragments, V's 64-byte
-// half c of row r in half c ^ ((r >> 1) & 1), which spreads the four rows of a transposing
-// read over all 64 banks.
+// LDS images are swizzled in the copies' per-lane SOURCE address (mfma_gemm.h).  At d = 64 (two
+// rows span the 64 banks) K's 16-byte slot g of row r lands in slot g ^ ((r >> 1) & 7) for the
+// ds_read_b128 fragments, V's 64-byte half c of row r in half c ^ ((r >> 1) & 1), which spreads
+// the four rows of a transposing read over all 64 banks.  At d = 128 a row IS the 64 banks and
+// every row starts on bank 0: K's slot g (of 16) lands in slot g ^ (r & 15), so that 16 lanes on
+// consecutive rows and one fragment slot read 16 different slots, V's 64-byte quarter c in
+// quarter c ^ (r & 3), so that the four rows 4 j .. 4 j + 3 of a transposing read, which all ask
+// for one quarter, find it in four different ones (K_SWIZZLE / V_SWIZZLE below).
 #include <algorithm>
 #include <type_traits>
 
@@ -46,11 +50,28 @@ namespace {
 using namespace mfma_tiles;
 using tiled::xcd_local_index;
 
-constexpr int kD = 64;          // head dimension
 constexpr int kBM = 128;        // query rows per workgroup
 constexpr int kBN = 64;         // key rows per tile: one mask word per query row
 constexpr int kThreads = 256;   // four waves of 32 query rows
-constexpr int kTileBytes = kBN * kD * 2;   // 8 KiB: one of K / V
+
+// What depends on the head dimension D: the K / V tile images in LDS and their swizzles.
+template <int D>
+struct Geometry {
+  static_assert(D == 64 || D == 128, "head dimension 64 or 128");
+  static constexpr int kRowBytes = D * 2;                // 128 / 256
+  static constexpr int kTileBytes = kBN * kRowBytes;     // 8 / 16 KiB: one of K / V
+  static constexpr int kSlotBits = D == 64 ? 3 : 4;
+  static constexpr int kSlots = 1 << kSlotBits;          // 16-byte slots of a row: 8 / 16
+  static constexpr int kPieceRows = 1024 / kRowBytes;    // rows of a 1 KiB lane-linear copy: 8 / 4
+  static constexpr int kWavePieces = kBN / kPieceRows / 4;   // copies per operand, tile and wave: 2 / 4
+  static constexpr int kSteps = D / 16;                  // k-steps of the scores
+  static constexpr int kBlocks = D / 32;                 // 32 x 32 accumulators of O^T
+};
+// Source slot g of row `row` lands in slot g ^ swizzle: K's in g ^ K_SWIZZLE(D, row), V's 64-byte
+// part c in part c ^ V_SWIZZLE(D, row).  (Macros: the d = 64 instances are to stay, instruction
+// for instruction, what they were before the kernel had a D.)
+#define K_SWIZZLE(D, row) ((D) == 64 ? ((row) >> 1) & 7 : (row) & 15)
+#define V_SWIZZLE(D, row) ((D) == 64 ? ((row) >> 1) & 1 : (row) & 3)
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 
@@ -131,22 +152,23 @@ __global__ __launch_bounds__(256) void attention_tiles_list_kernel(int nt, const
 // ---- the attention kernel ----
 
 // Stages key rows key0 .. key0 + 63 of K and V into `stage` ([K tile | V tile]) with 1 KiB
-// copies of 8 rows, two of each per wave.  Rows at n and beyond are ZERO-FILLED by the lanes
-// that would have copied them (those lanes issue no copy): 0 x garbage never reaches an
-// accumulator.
-template <typename T>
+// copies of 8 rows, two of each per wave (d = 128: of 4 rows, four of each).  Rows at n and
+// beyond are ZERO-FILLED by the lanes that would have copied them (those lanes issue no
+// copy): 0 x garbage never reaches an accumulator.
+template <int D, typename T>
 __device__ __forceinline__ void stage_tile(char* stage, const T* k, unsigned k_row_bytes, const T* v,
                                            unsigned v_row_bytes, int n, int key0, int wave, int lane) {
+  using G = Geometry<D>;
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
+  for (int j = 0; j < G::kWavePieces; ++j) {
     const int piece = wave + 4 * j;
-    const int row = 8 * piece + (lane >> 3), slot = lane & 7;
+    const int row = G::kPieceRows * piece + (lane >> G::kSlotBits), slot = lane & (G::kSlots - 1);
     char* k_dst = stage + piece * 1024;
-    char* v_dst = stage + kTileBytes + piece * 1024;
+    char* v_dst = stage + G::kTileBytes + piece * 1024;
     const unsigned key = static_cast<unsigned>(key0 + row);
     if (key0 + row < n) {
-      copy_piece(k, key * k_row_bytes + static_cast<unsigned>(slot ^ ((row >> 1) & 7)) * 16u, k_dst);
-      copy_piece(v, key * v_row_bytes + static_cast<unsigned>(slot ^ (((row >> 1) & 1) * 4)) * 16u, v_dst);
+      copy_piece(k, key * k_row_bytes + static_cast<unsigned>(slot ^ K_SWIZZLE(D, row)) * 16u, k_dst);
+      copy_piece(v, key * v_row_bytes + static_cast<unsigned>(slot ^ (V_SWIZZLE(D, row) * 4)) * 16u, v_dst);
     } else {
       *reinterpret_cast<uint4*>(k_dst + lane * 16) = make_uint4(0u, 0u, 0u, 0u);
       *reinterpret_cast<uint4*>(v_dst + lane * 16) = make_uint4(0u, 0u, 0u, 0u);
@@ -154,15 +176,17 @@ __device__ __forceinline__ void stage_tile(char* stage, const T* k, unsigned k_r
   }
 }
 
-// T: storage type of q, k, v; TO: of the context (float, or T).  Replicas replica0 ..
-// replica0 + gridDim.y - 1 of the call (a grid slice); the row blocks of a replica read the
-// same K and V and the heads of a batch element neighbouring columns of the same rows: the
-// work index is decoded XCD-locally (xcd_local_index).
-template <typename T, typename TO>
+// D: head dimension; T: storage type of q, k, v; TO: of the context (float, or T).  Replicas
+// replica0 .. replica0 + gridDim.y - 1 of the call (a grid slice); the row blocks of a replica
+// read the same K and V and the heads of a batch element neighbouring columns of the same
+// rows: the work index is decoded XCD-locally (xcd_local_index).
+template <int D, typename T, typename TO>
 __global__ __launch_bounds__(kThreads) void sparse_attention_tiles_kernel(
     int m, int n, int nt, int heads, int replica0, const int* __restrict__ lists,
     const u64* __restrict__ bitmap, View qv, View kv, View vv, float scale_log2e, View ov,
     float* __restrict__ lse, int64_t lse_stride) {
+  using G = Geometry<D>;
+  enum { kRowBytes = G::kRowBytes, kTileBytes = G::kTileBytes };
   using H8 = typename Half8<T>::type;
   using T4 = T __attribute__((ext_vector_type(4)));
   using T8 = T __attribute__((ext_vector_type(8)));
@@ -189,28 +213,28 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_tiles_kernel(
   const u64* __restrict__ words = bitmap + static_cast<int64_t>(row) * nt;
 
   // Q as B operand fragments: column = query row, k = head elements 16 ks + 8 h .. + 7
-  H8 qf[4];
+  H8 qf[G::kSteps];
   {
     const T* q_row = q + static_cast<unsigned>(min(row, m - 1)) * static_cast<unsigned>(qv.row);
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const H8*>(q_row + 16 * ks + 8 * h);
+    for (int ks = 0; ks < G::kSteps; ++ks) qf[ks] = *reinterpret_cast<const H8*>(q_row + 16 * ks + 8 * h);
   }
 
-  f32x16 o[2] = {};        // O^T: head elements db * 32 + 8 (r / 4) + 4 h + r % 4 of this lane's row
+  f32x16 o[G::kBlocks] = {};   // O^T: head elements db * 32 + 8 (r / 4) + 4 h + r % 4 of this lane's row
   float mx = -INFINITY;    // running maximum, in units of log2
   float l = 0.f;           // this lane half's part of the row sum
 
   // fragment addresses inside a stage: K row qr (+ 32 kb), slot 2 ks + h; V rows 4 h + q4 (+ the
   // step's first key), columns 32 db + 16 g1 + 4 p .. + 3
-  const unsigned k_at = static_cast<unsigned>(qr * 128 + ((h ^ ((qr >> 1) & 7)) * 16));
+  const unsigned k_at = static_cast<unsigned>(qr * kRowBytes + ((h ^ K_SWIZZLE(D, qr)) * 16));
   const int q4 = (lane & 15) >> 2;
-  const unsigned v_at = static_cast<unsigned>(kTileBytes + (4 * h + q4) * 128 + (((q4 >> 1) & 1) * 64) +
+  const unsigned v_at = static_cast<unsigned>(kTileBytes + (4 * h + q4) * kRowBytes + (V_SWIZZLE(D, q4) * 64) +
                                               32 * ((lane >> 4) & 1) + 8 * (lane & 3));
 
   u64 word = 0;
   if (count > 0) {
     const int t0 = list[1];
-    stage_tile(stage[0], k, k_bytes, v, v_bytes, n, t0 * kBN, wave, lane);
+    stage_tile<D>(stage[0], k, k_bytes, v, v_bytes, n, t0 * kBN, wave, lane);
     word = words[t0];
     tiled::wait_vm<0>();
     __syncthreads();
@@ -221,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_tiles_kernel(
     u64 next_word = 0;
     if (i + 1 < count) {
       const int t1 = list[i + 2];
-      stage_tile(stage[(i & 1) ^ 1], k, k_bytes, v, v_bytes, n, t1 * kBN, wave, lane);
+      stage_tile<D>(stage[(i & 1) ^ 1], k, k_bytes, v, v_bytes, n, t1 * kBN, wave, lane);
       next_word = words[t1];
     }
 
@@ -230,8 +254,8 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_tiles_kernel(
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const H8 a = *reinterpret_cast<const H8*>(st + kb * 4096 + (k_at ^ (ks * 32u)));
+      for (int ks = 0; ks < G::kSteps; ++ks) {
+        const H8 a = *reinterpret_cast<const H8*>(st + kb * 32 * kRowBytes + (k_at ^ (ks * 32u)));
         s[kb] = Half8<T>::mfma(a, qf[ks], s[kb]);
       }
 
@@ -264,8 +288,12 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_tiles_kernel(
         sum += s[kb][r];
       }
     l = l * alpha + sum;
-    o[0] *= alpha;
+    o[0] *= alpha;   // (written out, not a loop: see K_SWIZZLE)
     o[1] *= alpha;
+    if constexpr (D == 128) {
+      o[2] *= alpha;
+      o[3] *= alpha;
+    }
 
     // 3. O^T += V^T P^T, the weights rounded once to T
 #pragma unroll
@@ -277,11 +305,11 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_tiles_kernel(
         for (int j = 0; j < 8; ++j) p8[j] = s[kb][8 * ss + j];
         const H8 pf = __builtin_bit_cast(H8, __builtin_convertvector(p8, T8));
 #pragma unroll
-        for (int db = 0; db < 2; ++db) {
-          const char* at = st + (kb * 32 + ss * 16) * 128 + (v_at ^ (db * 64u));
+        for (int db = 0; db < G::kBlocks; ++db) {
+          const char* at = st + (kb * 32 + ss * 16) * kRowBytes + (v_at ^ (db * 64u));
           const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(at));
           const s4v hi =
-              __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(at + 8 * 128));
+              __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(at + 8 * kRowBytes));
           const s8v both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
           o[db] = Half8<T>::mfma(__builtin_bit_cast(H8, both), pf, o[db]);
         }
@@ -298,7 +326,7 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_tiles_kernel(
   const float inv = l > 0.f ? 1.f / l : 0.f;
   TO* out_row = out + static_cast<unsigned>(row) * static_cast<unsigned>(ov.row);
 #pragma unroll
-  for (int db = 0; db < 2; ++db)
+  for (int db = 0; db < G::kBlocks; ++db)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const f4v r4 = {o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv,
@@ -309,13 +337,25 @@ __global__ __launch_bounds__(kThreads) void sparse_attention_tiles_kernel(
     lse[replica * lse_stride + row] = l > 0.f ? mx * kLn2 + __logf(l) : -INFINITY;
 }
 
-template <typename T, typename TO>
+// What the kernel assumes about a head view of `rows` rows of d elements: a 16-byte aligned
+// base and strides, non-negative strides, and a replica's extent below 2^32 bytes (its
+// in-replica offsets are 32-bit).  The vector kernel's check (attention.hip) is this one at
+// its own head dimension, 64.
+bool view_ok(const View& w, int rows, int d, int elem_bytes) {
+  if (w.base == nullptr || !aligned_to(w.base, 16)) return false;
+  if (w.batch < 0 || w.head < 0 || w.row < 0) return false;
+  if ((w.batch * elem_bytes) % 16 != 0 || (w.head * elem_bytes) % 16 != 0 || (w.row * elem_bytes) % 16 != 0)
+    return false;
+  return (static_cast<int64_t>(rows - 1) * w.row + d) * elem_bytes < (int64_t{1} << 32);
+}
+
+template <int D, typename T, typename TO>
 void launch_tiles(int m, int n, int heads, int r0, int count, const void* plan, const View& q, const View& k,
                   const View& v, float scale, const View& o, float* lse, int64_t lse_stride,
                   hipStream_t stream) {
   const int* lists = static_cast<const int*>(plan);
   const u64* bitmap = reinterpret_cast<const u64*>(static_cast<const char*>(plan) + list_bytes(m, n));
-  hipLaunchKernelGGL((sparse_attention_tiles_kernel<T, TO>), dim3(blocks_of(m), count), dim3(kThreads), 0,
+  hipLaunchKernelGGL((sparse_attention_tiles_kernel<D, T, TO>), dim3(blocks_of(m), count), dim3(kThreads), 0,
                      stream, m, n, tiles_of(n), heads, r0, lists, bitmap, q, k, v, scale * kLog2e, o, lse,
                      lse_stride);
 }
@@ -359,12 +399,18 @@ int sputnik_hip_sparse_attention_tiles_supported(
     int64_t k_batch_stride, int64_t k_head_stride, int64_t k_row_stride, const void* v,
     int64_t v_batch_stride, int64_t v_head_stride, int64_t v_row_stride, const void* out,
     int64_t out_batch_stride, int64_t out_head_stride, int64_t out_row_stride) {
-  // the heads contract (d = 64, half storage, a mask with entries, aligned views with 32-bit
-  // extents), and a plan this kernel's 32-bit offsets reach
-  if (!sputnik_hip_sparse_attention_heads_supported(
-          m, n, d, nonzeros, batch, heads, dtype, out_type, q, q_batch_stride, q_head_stride, q_row_stride,
-          k, k_batch_stride, k_head_stride, k_row_stride, v, v_batch_stride, v_head_stride, v_row_stride, out,
-          out_batch_stride, out_head_stride, out_row_stride))
+  // the heads contract with this kernel's head dimensions (half storage, a mask with entries
+  // and n below 2^24, aligned views with 32-bit extents), and a plan its 32-bit offsets reach
+  if (d != 64 && d != 128) return 0;
+  if (m <= 0 || n <= 0 || nonzeros <= 0 || n >= (1 << 24)) return 0;
+  if (dtype != SPUTNIK_HIP_F16 && dtype != SPUTNIK_HIP_BF16) return 0;
+  if (out_type != SPUTNIK_HIP_F32 && out_type != dtype) return 0;
+  if (batch <= 0 || heads <= 0 || static_cast<int64_t>(batch) * heads >= (int64_t{1} << 31)) return 0;
+  const int out_bytes = out_type == SPUTNIK_HIP_F32 ? 4 : 2;
+  if (!view_ok(View{q, q_batch_stride, q_head_stride, q_row_stride}, m, d, 2) ||
+      !view_ok(View{k, k_batch_stride, k_head_stride, k_row_stride}, n, d, 2) ||
+      !view_ok(View{v, v_batch_stride, v_head_stride, v_row_stride}, n, d, 2) ||
+      !view_ok(View{out, out_batch_stride, out_head_stride, out_row_stride}, m, d, out_bytes))
     return 0;
   return plan_bytes_of(m, n) < (int64_t{1} << 31) ? 1 : 0;
 }
@@ -391,10 +437,18 @@ int sputnik_hip_sparse_attention_tiles_forward(
   for (int r0 = 0; r0 < replicas; r0 += kMaxGridYZ) {
     const int count = min(replicas - r0, kMaxGridYZ);
     auto go = [&](auto launch) { launch(m, n, heads, r0, count, plan, qv, kv, vv, scale, ov, lse, lse_stride, stream); };
-    if (dtype == SPUTNIK_HIP_F16 && out_type == SPUTNIK_HIP_F32) go(launch_tiles<_Float16, float>);
-    else if (dtype == SPUTNIK_HIP_F16) go(launch_tiles<_Float16, _Float16>);
-    else if (out_type == SPUTNIK_HIP_F32) go(launch_tiles<__bf16, float>);
-    else go(launch_tiles<__bf16, __bf16>);
+    const bool f16 = dtype == SPUTNIK_HIP_F16, wide = out_type == SPUTNIK_HIP_F32;
+    if (d == 64) {
+      if (f16 && wide) go(launch_tiles<64, _Float16, float>);
+      else if (f16) go(launch_tiles<64, _Float16, _Float16>);
+      else if (wide) go(launch_tiles<64, __bf16, float>);
+      else go(launch_tiles<64, __bf16, __bf16>);
+    } else {
+      if (f16 && wide) go(launch_tiles<128, _Float16, float>);
+      else if (f16) go(launch_tiles<128, _Float16, _Float16>);
+      else if (wide) go(launch_tiles<128, __bf16, float>);
+      else go(launch_tiles<128, __bf16, __bf16>);
+    }
     const int st = launch_status();
     if (st != 0) return st;
   }

@@ -1694,7 +1694,8 @@ std::vector<Tensor> sparse_attention_heads_run(const Tensor& q_in, const Tensor&
       o.batch_stride, o.head_stride, o.row_stride);
   if (!served) {
     TORCH_CHECK(!want_lse || drop != nullptr, "sparse_attention_heads: lse needs a call the fused "
-                "kernel serves (head dimension 64, 16-byte aligned views)");
+                "kernel serves (head dimension 64, or 128 through sparse_attention_tiles; 16-byte "
+                "aligned views)");
     // the typed operators on per-head copies in the storage type: float32 scores and
     // weights, float32 product, narrowed into the output's layout
     const int64_t replicas = q.batch * q.heads;
@@ -1756,8 +1757,9 @@ Tensor sparse_attention_tiles_plan(int64_t m64, int64_t n64, const Tensor& row_o
   return plan;
 }
 
-// sparse_attention_heads' operands and results, through the tile kernel where it serves the
-// call (a plan is made when none is given); anything else IS sparse_attention_heads.
+// sparse_attention_heads' operands and results at head dimension 64 or 128, through the tile
+// kernel where it serves the call (a plan is made when none is given); anything else IS
+// sparse_attention_heads (which fuses 64 alone and composes 128 from the typed operators).
 std::vector<Tensor> sparse_attention_tiles(const Tensor& q_in, const Tensor& k_in, const Tensor& v_in,
                                            const Tensor& row_indices, const Tensor& row_offsets,
                                            const Tensor& column_indices, double scale, int64_t out_type,

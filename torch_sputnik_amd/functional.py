@@ -1181,8 +1181,8 @@ def sparse_attention_heads(query, key, value, heads, row_indices, row_offsets, c
     float32.  Differentiable: the backward recomputes the weights (SparseAttentionHeadsFunction),
     and the gradient reaches q, k and v.  ``dropout_p``: dropout on the attention weights
     (replica r = b * heads + h of the library's mask contract).  ``matrix_cores``: the forward
-    runs the tile kernel on the matrix cores (ops.sparse_attention_tiles, with its contract: no
-    duplicate columns in a row, weights rounded once to the inputs' type); the backward is the
+    runs the tile kernel on the matrix cores (ops.sparse_attention_tiles, with its contract:
+    D = 64 or 128, no duplicate columns in a row, weights rounded once to the inputs' type); the backward is the
     same recomputing one.  With ``dropout_p > 0``, on CPU tensors or for a call the tile kernel
     does not serve the flag changes nothing."""
     p = ops.check_dropout_p(dropout_p)

@@ -631,7 +631,8 @@ class SparseAttention(nn.Module):
         not apply in this mode.  Shapes the kernels do not serve (head dimension other than
         64, sizes off the tiles) are composed from the typed operators.
         ``attention_matrix_cores=True`` runs the attention's forward as the tile kernel on the
-        matrix cores (no effect with attention dropout in training mode)."""
+        matrix cores, which serves head dimension 64 or 128 (no effect with attention dropout
+        in training mode)."""
         def project(net, x):
             return functional.half_linear_rows(net.output_features, net.input_features, net.values,
                                                net.row_indices, net.row_offsets, net.column_indices, x)

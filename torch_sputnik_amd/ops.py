@@ -1108,14 +1108,14 @@ def sparse_attention_tiles(query, key, value, row_indices, row_offsets, column_i
                            out_dtype=None, with_lse=False, plan=None):
     """sparse_attention_heads on the MATRIX CORES: a masked flash attention that walks the
     occupied 64-column key tiles of each block of 128 query rows and runs them as dense
-    v_mfma tiles.  Operand forms, `out_dtype`, `with_lse` and the output buffer's layout are
-    those of sparse_attention_heads; `plan` is sparse_attention_tiles_plan's (made per call
+    v_mfma tiles, at head dimension 64 or 128.  Operand forms, `out_dtype`, `with_lse` and the
+    output buffer's layout are those of sparse_attention_heads; `plan` is sparse_attention_tiles_plan's (made per call
     when None).  Scores, the softmax and every sum are float32; the weights are rounded once to
     the operands' type before they multiply V (the row sum and lse take them unrounded).
     Contract beyond sparse_attention_heads': no duplicate columns within a row (the plan
     collapses them), and V finite in every key row that shares a 64-column tile with an entry
     of the row block (0 * inf is NaN on a dense tile).  A call the kernel does not serve (head
-    dimension other than 64, unaligned views, a mask without entries) runs
+    dimension other than 64 or 128, unaligned views, a mask without entries) runs
     sparse_attention_heads."""
     out_code = _half_code(query.dtype if out_dtype is None else out_dtype)
     outs = _ops.sparse_attention_tiles(query, key, value, row_indices, row_offsets, column_indices,
